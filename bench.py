@@ -22,8 +22,16 @@ Contract (driver): ``python bench.py --gpus N --steps K --warmup W`` prints ONE 
   * N > 1 = N independent talker replicas, one per rank ("replicas only"): the
     path does not shard and there is no collective on it.  ``--gpus`` only counts replicas;
     no GPU is used by any of them.
+  * A plain run (no ``--full``) does only what the headline figure needs: build check, the warm-up and timed steps of
+    the headline workload, the check of their output against the restated path (``check_output``), ``--dump-outputs``
+    if given, the line.  Everything below that is not the timed run itself
+    (``configs``, ``roofline``, ``cpu_baseline_port``, ``cpu_baseline_O0``, ``device_floor``, the full record) is
+    measured only under ``--full`` (N = 1, rank 0 only; ``--no-extras`` skips it there too).
+  * ``--dump-outputs DIR``: after the timed steps, what the timed run returned to its caller, as float64 ``.npy`` files
+    (``dump_outputs``): the run's delivery counts and each talker's system-call counters over the timed window.  They
+    depend only on the arguments (a seeded, fixed workload), so two builds can be compared output for output.
   * ``configs`` = every BASELINE configuration (#1, #2, #3, #5 at their formal sizes, plus the headline #4),
-    each with delivered == expected per client (N = 1, rank 0 only; skipped by ``--no-extras``).
+    each with delivered == expected per client.
   * ``roofline`` is the host system-call ceiling, not HBM/MFMA: achieved = lines written per second by
     the talker; peak = what one core reaches when it does ONLY the system calls the algorithm needs per
     input line -- 1 select(FD_SETSIZE) + 1 read + (recipients + 1) write(2) -- measured by
@@ -40,11 +48,11 @@ Contract (driver): ``python bench.py --gpus N --steps K --warmup W`` prints ONE 
     descheduled / cgroup throttle), and a restatement/reference ratio outside [0.9, 1.1].
   * exit code: 0 only when the timed run was exact AND every configuration in ``configs`` was.
   * the ONE line on stdout is the COMPACT record (``compact_line``, under LINE_BUDGET bytes): the driver keeps only the last
-    ~8 KB of stdout in ``BENCH_rNN.json`` and round 3's 12 KB line lost its head there (load average, restatement leg).  The
-    FULL record -- every probe repetition, every repetition's counters -- goes to ``gpurun_out/bench_full_n<N>.json``
-    (``full_record`` in the line names it; ``NUTS_BENCH_FULL_RECORD`` overrides the path, ``--full-line`` prints it instead).
-    That file comes back from builder-run gpurun calls only; the driver's round-end run does not pull it, so the line
-    carries what explains it: per probe leg the rates, CPU/wall ratio and load average (``roofline.probe_legs``).
+    ~8 KB of stdout in ``BENCH_rNN.json`` and round 3's 12 KB line lost its head there (load average, restatement leg).  Under
+    ``--full`` the FULL record -- every probe repetition, every repetition's counters -- goes to a file (``write_full_record``;
+    ``full_record`` in the line names it, ``NUTS_BENCH_FULL_RECORD`` sets the path, ``--full-line`` prints it instead).
+    A run that only keeps stdout loses that file, so the line carries what explains it: per probe leg the rates, CPU/wall
+    ratio and load average (``roofline.probe_legs``).
   * ``cpu_baseline_O0``: the headline workload on oracle/_ref/nuts333_O0 (the reference's as-shipped flags: no -O), x 3.
 """
 from __future__ import annotations
@@ -73,9 +81,13 @@ DEFAULT_LINES_PER_STEP = {"config1": 1000, "config2": 2000, "config2_all": 2000,
 WORKLOADS = list(DEFAULT_LINES_PER_STEP)
 
 
+#: the project's own restatement of the path's pure functions (oracle/nuts_path.c), built by ``make -C oracle port``
+PATH_LIB = REPO / "oracle" / "_build" / "libnuts_path.so"
+
+
 def ensure_built() -> None:
     """Build what can be built here; never silently substitute."""
-    if not PORT_BINARY.exists():
+    if not PORT_BINARY.exists() or not PATH_LIB.exists():
         subprocess.run(["make", "-s", "-C", str(REPO / "oracle"), "port"], check=True)
     workloads.build_loadgen()
 
@@ -448,7 +460,8 @@ def compact_line(full: dict, full_record: str | None, *, tight: int = 0) -> dict
     notes, prose = tight == 0, tight < 2
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data", "config", "gpu_used", "classification", "delivered", "expected_delivered", "input_lines_per_s",
-            "ack_latency_us", "server_cpu_us_per_written_line", "server_busy_frac", "server_syscalls", "configs_all_exact")
+            "ack_latency_us", "server_cpu_us_per_written_line", "server_busy_frac", "server_syscalls", "output_check",
+            "configs_all_exact")
     c = {k: full[k] for k in keep if k in full}
     h = full["host"]
     c["host"] = {"loadavg_before_run": h["loadavg_before_run"], "cpus_available": h["cpus_available"],
@@ -627,6 +640,79 @@ def device_floor_in_child() -> dict | None:
     return json.loads(lines[-1][6:])
 
 
+def predicted_output(workload: str, res: dict, lines: int) -> dict | None:
+    """What the talker must have written in the timed window, from the project's own restatement of the path: the texts
+    the say / shout handlers compose (nuts333.c:4062-4124, oracle/talker_port.c ``say`` / ``shout``), each run through
+    ``np_transduce`` / ``np_write_count`` of oracle/_build/libnuts_path.so -- the bytes and write(2) calls of the sender's
+    acknowledgement and of every recipient's copy, for every timed input line.  None for the workloads whose lines are
+    not single-room say / shout from fixed senders (#3's seeded mix, #5's two talkers): their check stays the counts."""
+    import ctypes
+    from nuts333_amd.provision import bot_name
+    if workload not in ("config1", "config2", "config2_all", "config4"):
+        return None
+    lib = ctypes.CDLL(str(PATH_LIB))
+    lib.np_transduce.restype = ctypes.c_size_t
+    lib.np_transduce.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
+    lib.np_write_count.argtypes = [ctypes.c_char_p, ctypes.c_int]
+    lib.np_say_verb.restype = ctypes.c_char_p
+    lib.np_say_verb.argtypes = [ctypes.c_char_p]
+    n = res["clients"]
+    if workload == "config1":
+        plan = [("Fred", k, 0) for k in range(lines)]
+    elif workload == "config2_all":
+        plan = [(bot_name(i), k, n - 1) for k in range(lines // n) for i in range(n)]
+    else:
+        plan = [(bot_name(0), k, n - 1) for k in range(lines)]
+    nbytes = writes = 0
+    for name, k, recipients in plan:
+        text = workloads.payload(k % 1_000_000)
+        if workload == "config4":
+            ack, copy = f"~OLYou shout:~RS {text}\n", f"~OL{name} shouts:~RS {text}\n"
+        else:
+            verb = lib.np_say_verb(text.encode()).decode()
+            ack, copy = f"You {verb}: {text}\n", f"{name} {verb}s: {text}\n"
+        for msg, times in ((ack.encode(), 1), (copy.encode(), recipients)):
+            nbytes += times * lib.np_transduce(msg, 0, None, 0)
+            writes += times * lib.np_write_count(msg, 0)
+    return {"bytes": nbytes, "writes": writes, "by": str(PATH_LIB.relative_to(REPO))}
+
+
+def check_output(workload: str, res: dict, lines: int) -> dict | None:
+    """``predicted_output`` against the timed run: the bytes the clients received, the bytes and write(2) calls the talker
+    issued.  Raises on a difference (the run then has no result line, as for a count that is not exact)."""
+    want = predicted_output(workload, res, lines)
+    if want is None:
+        return None
+    srv = res["servers"][0]
+    got = {"bytes_received": res["bytes_total"], "bytes_written": srv["bytes_written"], "writes": srv["write_syscalls"]}
+    if not got["bytes_received"] == got["bytes_written"] == want["bytes"] or got["writes"] != want["writes"]:
+        raise RuntimeError(f"the timed run's output differs from the restated path's prediction: {got} vs {want}")
+    return {**want, "exact": True}
+
+
+#: ``--dump-outputs``: file name -> the fields of the timed run's result it holds, in this order (float64; one row per talker
+#: for the server counters).  Counts only: every one is fixed by the arguments, none depends on timing.
+DUMP_COUNTS = ("planned_input_lines", "input_lines", "acks", "lines_total", "deliveries", "expected_deliveries", "bytes_total")
+DUMP_SERVER = ("read_syscalls", "write_syscalls", "bytes_written")
+
+
+def dump_outputs(res: dict, out_dir: str | os.PathLike) -> list[Path]:
+    """What the timed run computed, as its caller received it (``run_workload``'s result), written as ``.npy`` files into
+    ``out_dir``: ``delivery_counts`` (DUMP_COUNTS), ``server_counters`` (DUMP_SERVER per talker, taken over the timed
+    window) and ``exact`` (delivered == expected in total and per client).  A few hundred bytes in all."""
+    import numpy as np
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {"delivery_counts": np.array([res[k] for k in DUMP_COUNTS], dtype=np.float64),
+              "server_counters": np.array([[s[k] for k in DUMP_SERVER] for s in res["servers"]], dtype=np.float64),
+              "exact": np.array([res["exact"], res["per_client_exact"]], dtype=np.float64)}
+    paths = []
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
+        paths.append(d / f"{name}.npy")
+    return paths
+
+
 def hide_gpus_from_this_process() -> None:
     """Replicas use no GPU: say so to the runtimes before torch is imported.  (Necessary, not sufficient: see
     cpu_barrier.)"""
@@ -654,7 +740,12 @@ def main() -> int:
     ap.add_argument("--binary", default="auto", choices=["auto", "reference", "port"])
     ap.add_argument("--full-line", action="store_true", help="print the full record on stdout instead of the compact line")
     ap.add_argument("--no-extras", action="store_true",
-                    help="headline run only: skip the other four configurations, the syscall probe, the port comparison and the device floor")
+                    help="with --full: headline run only (the default without --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the other configurations, the syscall probe, the port "
+                         "and -O0 comparisons and the device floor; and write the full record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the timed run computed into DIR as .npy files")
     args = ap.parse_args()
     lines_per_step = args.lines_per_step or DEFAULT_LINES_PER_STEP[args.workload]
 
@@ -720,13 +811,15 @@ def main() -> int:
     throttled0 = workloads.cgroup_throttled()
     barrier()
     t_outer0 = time.perf_counter()
-    res, failure = None, ""
+    res, failure, output_check = None, "", None
     try:
         if os.environ.get("NUTS_BENCH_INJECT_FAILURE"):          # tests only: see test_bench_failed_replica_...
             raise RuntimeError("injected failure")
         res = run_workload(args.workload, total, warm, binary, pin)
         if not res["exact"]:
             failure = "delivered != expected: " + json.dumps({k: res[k] for k in ("deliveries", "expected_deliveries", "lines_total")})
+        else:
+            output_check = check_output(args.workload, res, total)
     except Exception:                           # a dead replica must not leave the others waiting in a collective
         failure = traceback.format_exc()
     t_outer1 = time.perf_counter()
@@ -759,6 +852,9 @@ def main() -> int:
     else:
         wall_max, deliveries_all, written_all = wall, float(deliveries), float(written)
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(res, args.dump_outputs)
+
     if rank != 0:
         if dist is not None:
             dist.destroy_process_group()
@@ -787,6 +883,7 @@ def main() -> int:
         "server_syscalls": {"read": srv.get("read_syscalls"), "write": srv.get("write_syscalls"),
                             "per_input_line": {"read": round(srv["read_syscalls_per_input_line"], 3),
                                                "write": round(srv["write_syscalls"] / max(1, res["input_lines"]), 3)}},
+        "output_check": output_check,
         "outer_wall_s": round(t_outer1 - t_outer0, 3), "login_s": res["login_s"],
         "host": {"cpus_available": len(os.sched_getaffinity(0)), "loadavg_before_run": loadavg0,
                  "cgroup_cpu_quota_cores": quota, "receiver_threads_per_replica": res["threads"],
@@ -802,7 +899,7 @@ def main() -> int:
     baseline = {"value": round(res["delivered_lines_per_s"], 1), "unit": UNIT, "cores": 1, "kind": kind,
                 "sample": f"the timed run itself: {res['input_lines']} input lines, {res['deliveries']} deliveries, one replica"}
     roofline = None
-    if not args.no_extras and world == 1:
+    if args.full and not args.no_extras and world == 1:
         # Everything below is context for the headline number, not part of it: a failure here (a probe that cannot
         # open 2000 descriptors, a talker that will not boot on a busy host) must not cost the driver its result
         # line.  It is reported in the line (`extras_errors`) and on stderr instead.
@@ -863,7 +960,7 @@ def main() -> int:
     if args.full_line:
         print(json.dumps(out))
     else:
-        print(render_line(out, write_full_record(out, world)))
+        print(render_line(out, write_full_record(out, world) if args.full else None))
     if dist is not None:
         dist.destroy_process_group()
     # stderr shares the driver's ~8 KB tail with the line (its record is stdout + "---- stderr ----" + stderr, cut from the

@@ -2,8 +2,8 @@
  * nuts_path.h -- CPU restatement of the NUTS 3.3.3 input -> broadcast path.
  *
  * TEST INFRASTRUCTURE.  This is the oracle: a from-scratch restatement of the functions
- * SURVEY.md section 8(a) lists, used only by tests/, __graft_entry__.smoke() and bench.py's
- * cpu_baseline leg.  Nothing here is a product path (the project has none: BASELINE.json's
+ * SURVEY.md section 8(a) lists, used only by tests/, __graft_entry__.smoke() and bench.py (its
+ * cpu_baseline leg, and the check of every run's output).  Nothing here is a product path (the project has none: BASELINE.json's
  * north_star flags the reference as not graft-eligible).
  *
  * Parity pin: byte-exact against tests/golden/ *.json, which are transcripts captured from

@@ -4,11 +4,11 @@
     "Two-server netlink (datafiles/config + config2) with cross-link .shout traffic"
 
 Every other run in this repository boots a tree that ``nuts333_amd/provision.py`` generates (same room graph, our
-own texts), because no reference file may travel to the GPU box.  This module is the container-only cross-check:
-it populates a temporary directory AT TEST TIME from ``/root/reference`` -- ``datafiles/config``, ``config2``, the
-room descriptions, ``userfiles/Fred.D``, ``motd1``/``motd2`` -- boots ``oracle/_ref/nuts333`` there and drives it
-with the same load generator.  Nothing is copied into the repository, committed or shipped; callers are
-``reference``-marked tests and ``tools/shipped_rows.py`` (which prints the BASELINE.md rows).
+own texts).  This module is the cross-check on the shipped files: it populates a temporary directory AT TEST TIME
+from ``tests/golden/shipped/`` -- byte-for-byte copies of the reference's data files ``datafiles/config``,
+``config2``, the room descriptions, ``userfiles/Fred.D``, ``motd1``/``motd2`` (data only, no source) -- boots
+``oracle/_ref/nuts333`` there and drives it with the same load generator; callers are ``reference``-marked tests and
+``tools/shipped_rows.py`` (which prints the BASELINE.md rows).
 
 What the shipped files force on the run (all measured behaviour of the reference):
 * fixed ports 7000-7002 and 5000-5002 (``datafiles/config:5-7``, ``config2:8-10``);
@@ -22,7 +22,6 @@ What the shipped files force on the run (all measured behaviour of the reference
 """
 from __future__ import annotations
 
-import os
 import shutil
 import socket
 import tempfile
@@ -32,13 +31,14 @@ from pathlib import Path
 from nuts333_amd import workloads
 from nuts333_amd.talker import REF_BINARY, Talker
 
-REFERENCE = Path(os.environ.get("REFERENCE", "/root/reference"))
+#: the reference's shipped data files, as fixtures (a talker working directory's data part, nuts333.h:3-14)
+SHIPPED = Path(__file__).resolve().parent / "golden" / "shipped"
 PORTS_T1 = (7000, 7001, 7002)     # datafiles/config:5-7
 PORTS_T2 = (5000, 5001, 5002)     # datafiles/config2:8-10
 
 
 def available() -> bool:
-    return (REFERENCE / "datafiles" / "config").exists() and REF_BINARY.exists()
+    return (SHIPPED / "datafiles" / "config").exists() and REF_BINARY.exists()
 
 
 def ports_free(ports) -> bool:
@@ -55,11 +55,11 @@ def populate(root: Path, fix_config2: bool = False) -> Path:
     """A talker working directory made of the reference's shipped files (nuts333.h:3-14)."""
     for d in ("datafiles", "userfiles", "helpfiles", "mailspool"):
         (root / d).mkdir(parents=True, exist_ok=True)
-    for f in (REFERENCE / "datafiles").iterdir():
-        shutil.copy(f, root / "datafiles" / f.name)
-    shutil.copy(REFERENCE / "userfiles" / "Fred.D", root / "userfiles" / "Fred.D")
+    for f in (SHIPPED / "datafiles").iterdir():
+        shutil.copyfile(f, root / "datafiles" / f.name)
+    shutil.copyfile(SHIPPED / "userfiles" / "Fred.D", root / "userfiles" / "Fred.D")
     for f in ("motd1", "motd2"):
-        shutil.copy(REFERENCE / f, root / f)
+        shutil.copyfile(SHIPPED / f, root / f)
     if fix_config2:
         path = root / "datafiles" / "config2"
         lines = path.read_text().split("\n")

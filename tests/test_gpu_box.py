@@ -173,7 +173,7 @@ def test_restatement_costs_the_same_system_calls_as_the_reference():
 # ------------------------------------------------------------------ bench line and probes on this host
 def test_bench_line_covers_all_five_configs_headline_config4(tmp_path):
     record = tmp_path / "full.json"
-    out = subprocess.run([sys.executable, str(REPO / "bench.py"), "--steps", "5", "--warmup", "1"], check=True,
+    out = subprocess.run([sys.executable, str(REPO / "bench.py"), "--steps", "5", "--warmup", "1", "--full"], check=True,
                          env={**os.environ, "NUTS_BENCH_FULL_RECORD": str(record)},
                          stdout=subprocess.PIPE, timeout=1100).stdout.decode().strip().splitlines()
     assert len(out) == 1
@@ -197,6 +197,7 @@ def test_bench_line_covers_all_five_configs_headline_config4(tmp_path):
     assert line["host"]["loadavg_before_run"] == j["host"]["loadavg_before_run"] is not None
     assert j["config"]["baseline_config"] == "config4" and j["config"]["clients"] == 1000 and j["gpu_used"] is False
     assert j["delivered"] == j["expected_delivered"] == 5 * 100 * 999
+    assert j["output_check"]["exact"] and j["output_check"]["bytes"] == 5 * 100 * (999 * 69 + 67) and line["output_check"] == j["output_check"]
     # BASELINE.json's five configurations, #3 both as shipped (5 rooms) and as worded ("all 6 rooms"), at formal sizes
     assert [c["name"] for c in j["configs"]] == ["config1", "config2", "config3", "config3_six_rooms", "config4", "config5"]
     assert all(c["exact"] for c in j["configs"]) and j["configs_all_exact"] and j["extras_errors"] == []

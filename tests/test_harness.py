@@ -140,15 +140,25 @@ def test_close_does_not_wait_for_a_broadcast_nobody_will_be_sent(tmp_path, port_
             s.shutdown()
 
 
-def test_restatement_survives_the_fd_setsize_cliff(tmp_path, port_binary):
+@pytest.fixture
+def nofile_1200():
+    """Descriptors for a talker started with 1000 already in use: the soft RLIMIT_NOFILE is lifted towards the hard one
+    (an unprivileged process may) for the test, and inherited by the talker it starts; restored afterwards."""
+    import resource
+    soft, hard = resource.getrlimit(resource.RLIMIT_NOFILE)
+    if soft < 1200:
+        if hard != resource.RLIM_INFINITY and hard < 1200:
+            pytest.skip(f"RLIMIT_NOFILE too low (hard limit {hard})")
+        resource.setrlimit(resource.RLIMIT_NOFILE, (4096 if hard == resource.RLIM_INFINITY else min(hard, 4096), hard))
+    yield
+    resource.setrlimit(resource.RLIMIT_NOFILE, (soft, hard))
+
+
+def test_restatement_survives_the_fd_setsize_cliff(tmp_path, port_binary, nofile_1200):
     """select() with FD_SETSIZE: the first descriptor >= 1024 cannot go into the mask.  The reference aborts there
     (-O2, fortified FD_SET) or corrupts memory (-O0) -- INTEGRATION.md section 4; the restatement turns the client
     away.  The daemon is started with 1000 descriptors already in use so that 40 connections reach the cliff."""
-    import resource
     import socket
-    soft, _ = resource.getrlimit(resource.RLIMIT_NOFILE)
-    if soft < 1200:
-        pytest.skip("RLIMIT_NOFILE too low")
     ports = free_ports(3)
     root = pv.write_tree(tmp_path / "t", pv.TalkerConfig(mainport=ports[0], wizport=ports[1], linkport=ports[2], max_users=2000))
     socks = []
@@ -171,13 +181,10 @@ def test_restatement_survives_the_fd_setsize_cliff(tmp_path, port_binary):
 
 
 @pytest.mark.reference
-def test_reference_dies_at_the_fd_setsize_cliff(tmp_path, ref_binary):
+def test_reference_dies_at_the_fd_setsize_cliff(tmp_path, ref_binary, nofile_1200):
     """Documents the defect (nuts333.c:94,251-258,274): the fortified -O2 build aborts on FD_SET(1024)."""
-    import resource
     import socket
     import time
-    if resource.getrlimit(resource.RLIMIT_NOFILE)[0] < 1200:
-        pytest.skip("RLIMIT_NOFILE too low")
     ports = free_ports(3)
     root = pv.write_tree(tmp_path / "t", pv.TalkerConfig(mainport=ports[0], wizport=ports[1], linkport=ports[2], max_users=2000))
     socks = []
@@ -456,7 +463,8 @@ def _assert_compact_free_text(line: dict, full: dict) -> None:
 
 
 def test_bench_single_replica_contract():
-    line, j = _bench("--steps", "2", "--warmup", "1", "--lines-per-step", "200", "--binary", "port", "--workload", "config2", full=True)
+    line, j = _bench("--steps", "2", "--warmup", "1", "--lines-per-step", "200", "--binary", "port", "--workload", "config2", "--full",
+                     full=True)
     assert CONTRACT_KEYS <= set(line) and CONTRACT_KEYS <= set(j)
     # the compact line copies, never recomputes: every figure it carries is the full record's
     for k in ("value", "ms_per_step", "delivered", "expected_delivered", "cpu_baseline", "configs_all_exact"):
@@ -505,6 +513,51 @@ def test_bench_single_replica_contract():
     assert "over 5 rooms" in five["workload"] and "over 6 rooms" in six["workload"] and "datafiles/config:34-39" in five["note"]
     assert six["input_lines"] == five["input_lines"] == 20000 and six["delivered"] != five["delivered"]
     assert j["configs"][5]["netlink"]["writes_t2_to_t1"] == 11000 and j["configs"][5]["netlink"]["writes_t1_to_t2"] == 1000
+
+
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full the run is the headline and nothing else: no probe, no comparison legs, no other configuration, no
+    full record.  --dump-outputs writes what the timed run returned as float64 .npy files, the same for the same arguments."""
+    import numpy as np
+    sys.path.insert(0, str(REPO))
+    import bench
+    args = ("--steps", "3", "--warmup", "1", "--lines-per-step", "100", "--binary", "port", "--workload", "config2")
+    runs = [_bench(*args, "--dump-outputs", str(tmp_path / k)) for k in ("a", "b")]
+    for j in runs:
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["delivered"] == j["expected_delivered"] == 3 * 100 * 9
+        assert j["roofline"] is None and j["full_record"] is None
+        assert not {"configs", "configs_all_exact", "cpu_baseline_port", "cpu_baseline_O0", "device_floor", "extras_errors"} & set(j)
+        assert {k: j[k] for k in ("metric", "unit", "higher_is_better", "dtype")} == \
+               {"metric": bench.METRIC, "unit": bench.UNIT, "higher_is_better": True, "dtype": "u8"}
+    names = {"delivery_counts.npy", "server_counters.npy", "exact.npy"}
+    assert {p.name for p in (tmp_path / "a").iterdir()} == {p.name for p in (tmp_path / "b").iterdir()} == names
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float64 and np.array_equal(a, b), n
+    counts = dict(zip(bench.DUMP_COUNTS, np.load(tmp_path / "a" / "delivery_counts.npy").tolist()))
+    assert counts["input_lines"] == counts["planned_input_lines"] == counts["acks"] == 300
+    assert counts["deliveries"] == counts["expected_deliveries"] == 300 * 9 and counts["lines_total"] == 300 * 10
+    server = np.load(tmp_path / "a" / "server_counters.npy")
+    assert server.shape == (1, len(bench.DUMP_SERVER)) and server[0].tolist() == [300, 3000, counts["bytes_total"]]
+    assert np.load(tmp_path / "a" / "exact.npy").tolist() == [1.0, 1.0]
+    # the timed run's bytes and write(2) calls, checked against the restated path (libnuts_path.so) in the benchmark itself
+    assert runs[0]["output_check"] == {"bytes": counts["bytes_total"], "writes": 3000, "by": "oracle/_build/libnuts_path.so", "exact": True}
+
+
+def test_bench_output_check_predicts_the_talkers_bytes_and_writes(port_binary):
+    """bench.check_output: the headline's 999 copies of 69 bytes + a 67-byte acknowledgement per line, one write(2) each
+    (the figures test_gpu_box asserts of config #4), predicted by np_transduce / np_write_count; a byte off is an error."""
+    sys.path.insert(0, str(REPO))
+    import bench
+    res = {"clients": 1000, "bytes_total": 3 * (999 * 69 + 67),
+           "servers": [{"bytes_written": 3 * (999 * 69 + 67), "write_syscalls": 3 * 1000}]}
+    assert bench.check_output("config4", res, 3) == {"bytes": 3 * (999 * 69 + 67), "writes": 3000,
+                                                     "by": "oracle/_build/libnuts_path.so", "exact": True}
+    for bad in ({**res, "bytes_total": res["bytes_total"] - 1},
+                {**res, "servers": [{"bytes_written": res["bytes_total"], "write_syscalls": 2999}]}):
+        with pytest.raises(RuntimeError, match="differs from the restated path"):
+            bench.check_output("config4", bad, 3)
+    assert bench.check_output("config3", res, 3) is None          # the seeded mix: counts only
 
 
 def test_bench_extras_cannot_cost_the_result_line(monkeypatch):
@@ -560,7 +613,8 @@ def test_bench_exit_code_is_nonzero_when_a_configuration_is_inexact(monkeypatch,
     verdicts = iter([[{"name": "config1", "exact": True}, {"name": "config2", "exact": False, "error": "stub"}],
                      [{"name": "config1", "exact": True}]])
     monkeypatch.setattr(bench, "all_configs", lambda *a, **kw: next(verdicts))
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "1", "--warmup", "0", "--workload", "config2", "--binary", "port"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "1", "--warmup", "0", "--lines-per-step", "60", "--workload", "config2",
+                                      "--binary", "port", "--full"])          # (the size of the stubbed run: bench checks its bytes)
     assert bench.main() == 1
     line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
     assert line["configs_all_exact"] is False and line["value"] > 0

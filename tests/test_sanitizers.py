@@ -60,13 +60,12 @@ SINGLE_TALKER = ["charecho", "afk_bcast", "speech_colour_off", "speech_colour_mi
 
 
 @pytest.fixture(scope="module")
-def asan_reference(tmp_path_factory):
-    src = Path("/root/reference/nuts333.c")
-    if not src.exists():
-        pytest.skip("no /root/reference on this machine")
-    out = tmp_path_factory.mktemp("asan_ref") / "nuts333"
-    subprocess.run(["gcc", "-w", "-g", "-O1", "-fno-omit-frame-pointer", "-fsanitize=address", "-I", str(src.parent),
-                    str(src), "-o", str(out), "-lcrypt"], check=True)
+def asan_reference(ref_binary):
+    """The reference under AddressSanitizer, compiled by __graft_entry__.build() beside the other reference builds
+    (oracle/Makefile, target ``ref``): present wherever ``ref_binary`` is."""
+    out = ref_binary.with_name("nuts333_asan")
+    if not out.exists():
+        pytest.fail(f"{out.relative_to(REPO)} is not built although {ref_binary.relative_to(REPO)} is: run __graft_entry__.build()")
     return out
 
 

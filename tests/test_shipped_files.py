@@ -1,7 +1,7 @@
-"""BASELINE configurations #1 and #5 on the reference's own shipped files (container only; see tests/shipped_tree.py).
+"""BASELINE configurations #1 and #5 on the reference's own shipped files (see tests/shipped_tree.py).
 
-``reference``-marked: needs /root/reference and oracle/_ref/nuts333; skipped on the GPU box, where neither the
-reference tree nor anything copied from it exists.
+``reference``-marked: needs oracle/_ref/nuts333 (the ``ref_binary`` fixture); the shipped data files are fixtures under
+tests/golden/shipped/.
 """
 from __future__ import annotations
 
@@ -18,7 +18,7 @@ pytestmark = pytest.mark.reference
 @pytest.fixture(autouse=True)
 def _needs_the_shipped_files(ref_binary):
     if not st.available():
-        pytest.skip("/root/reference is not mounted here")
+        pytest.skip("oracle/_ref/nuts333 or tests/golden/shipped/ is missing")
     if not (st.ports_free(st.PORTS_T1) and st.ports_free(st.PORTS_T2)):
         pytest.skip("the shipped configs' fixed ports 7000-7002 / 5000-5002 are in use")
 

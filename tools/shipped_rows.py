@@ -3,7 +3,7 @@
 
     python tools/shipped_rows.py [--reps 3]
 
-Uses tests/shipped_tree.py: a temporary directory is populated from /root/reference at run time, nothing is kept.
+Uses tests/shipped_tree.py: a temporary directory is populated from tests/golden/shipped/ at run time, nothing is kept.
 """
 from __future__ import annotations
 
@@ -33,7 +33,7 @@ def main() -> int:
     ap.add_argument("--reps", type=int, default=3)
     args = ap.parse_args()
     if not st.available():
-        raise SystemExit("needs /root/reference and oracle/_ref/nuts333")
+        raise SystemExit("needs oracle/_ref/nuts333")
     print("| Run | N | Input lines | exact | Input lines/s | Delivered lines/s | Server CPU µs / input line | µs / written line | B/line |")
     print("|---|---|---|---|---|---|---|---|---|")
     a, b, c = [], [], []
