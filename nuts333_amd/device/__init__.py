@@ -1,0 +1,230 @@
+"""The user-space stage of a broadcast on the MI355X: ``fanout.hip`` behind a small numpy API.
+
+``broadcast(text, listeners, rm_is_null, force_listen, com_num)`` does for every listener what ``write_room_except`` +
+``write_user`` do before ``write(2)`` (nuts333.c:1315-1365, 1410-1415): the admit predicate, then the colour-markup
+transducer through the 1000-byte staging buffer.  ``transduce_batch(texts, colours)`` runs the transducer over M
+independent items, none filtered.  Both return a :class:`Fanout`: the bytes of item ``i`` are
+``arena[out_offsets[i]:out_offsets[i + 1]]`` and its ``write(2)`` chunk sizes are
+``write_sizes[write_offsets[i]:write_offsets[i + 1]]`` -- byte-exact and boundary-exact with ``np_write_user_stream``
+of the CPU restatement (oracle/nuts_path.c).  An item that is not admitted has no bytes and no chunks.
+
+Input is validated before the device is touched (``ValueError``).  The library ``_build/libnuts_device.so`` is built by
+``__graft_entry__.build()`` where ``hipcc`` exists, and on demand here when it is missing or older than its source.
+There is no CPU fall-back: without a GPU the calls raise ``RuntimeError``.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+import shutil
+import subprocess
+from dataclasses import dataclass, field
+from pathlib import Path
+
+import numpy as np
+
+HERE = Path(__file__).resolve().parent
+SOURCE = HERE / "fanout.hip"
+LIBRARY = HERE / "_build" / "libnuts_device.so"
+
+#: NP_TEXT_SIZE (nuts333.h:280): a composed text is at most 1999 bytes
+TEXT_SIZE = 2000
+#: hard bounds per item, pinned by tests on the CPU restatement: bytes <= 6*len + 4, writes <= MAX_WRITES
+MAX_WRITES = 16
+#: the columns of a listener record: the six fields of ``struct np_listener`` (oracle/nuts_path.h), then ``colour``
+LISTENER_FIELDS = ("login", "has_room", "same_room", "ignall", "ignshout", "is_sender", "colour")
+#: NP_NUM_COMMANDS (oracle/nuts_path.h enum np_com)
+NUM_COMMANDS = 92
+COM_SAY, COM_SHOUT, COM_SEMOTE = 3, 4, 7
+#: the kernels of fanout.hip, as rocprofv3 names them (the scans are rocPRIM's)
+KERNELS = ("nuts_fanout_measure_broadcast", "nuts_fanout_emit_broadcast",
+           "nuts_fanout_measure_batch", "nuts_fanout_emit_batch")
+
+
+def max_bytes(text_len: int) -> int:
+    """Hard bound on the bytes one item of ``text_len`` input bytes produces (a colour '\\n' is 6, plus the reset)."""
+    return 6 * text_len + 4
+
+
+@dataclass
+class Fanout:
+    admitted: np.ndarray          # bool [M]
+    out_offsets: np.ndarray       # int64 [M + 1]
+    arena: np.ndarray             # uint8 [out_offsets[-1]]
+    write_offsets: np.ndarray     # int64 [M + 1]
+    write_sizes: np.ndarray       # int32 [write_offsets[-1]]
+    timing: dict = field(default_factory=dict)   # kernels_us (device events), end_to_end_us (host clock, H2D..D2H+sync)
+
+    def output(self, i: int) -> bytes:
+        return self.arena[self.out_offsets[i]:self.out_offsets[i + 1]].tobytes()
+
+
+def chunks(result: Fanout, i: int) -> list[bytes]:
+    """Item ``i`` as the list of ``write(2)`` chunks the reference would issue."""
+    data = result.output(i)
+    sizes = result.write_sizes[result.write_offsets[i]:result.write_offsets[i + 1]]
+    out, at = [], 0
+    for s in sizes.tolist():
+        out.append(data[at:at + s])
+        at += s
+    if at != len(data):
+        raise AssertionError(f"item {i}: chunk sizes sum to {at}, arena slot holds {len(data)} bytes")
+    return out
+
+
+# ------------------------------------------------------------------ validation (never touches the device)
+def _as_text(t) -> bytes:
+    if isinstance(t, str):
+        try:
+            t = t.encode("latin-1")
+        except UnicodeEncodeError as e:
+            raise ValueError(f"text has a character outside one byte: {e}") from None
+    elif isinstance(t, (bytearray, memoryview)):
+        t = bytes(t)
+    if not isinstance(t, bytes):
+        raise ValueError(f"text must be bytes or str, not {type(t).__name__}")
+    if b"\0" in t:
+        raise ValueError("text contains a NUL byte (the talker's strings end there)")
+    if len(t) >= TEXT_SIZE:
+        raise ValueError(f"text of {len(t)} bytes: the talker's text buffer holds at most {TEXT_SIZE - 1}")
+    return t
+
+
+def _flag(name: str, v) -> int:
+    if isinstance(v, (bool, np.bool_)) or (isinstance(v, (int, np.integer)) and int(v) in (0, 1)):
+        return int(v)
+    raise ValueError(f"{name} must be 0/1 or a bool, not {v!r}")
+
+
+def _listener_records(listeners) -> np.ndarray:
+    """(N, 7) 0/1 table in LISTENER_FIELDS order -> one byte per listener (bit k = column k)."""
+    try:
+        a = np.asarray(listeners)
+    except Exception as e:   # ragged nested lists
+        raise ValueError(f"listeners are not a table: {e}") from None
+    if a.ndim != 2 or a.shape[1] != len(LISTENER_FIELDS):
+        raise ValueError(f"listeners must have shape (N, {len(LISTENER_FIELDS)}) with columns {LISTENER_FIELDS}, "
+                         f"got {a.shape}")
+    if a.shape[0] == 0:
+        raise ValueError("empty broadcast: no listeners")
+    if a.dtype != np.bool_ and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"listener records must be integers or bools, got {a.dtype}")
+    if not np.isin(a, (0, 1)).all():
+        raise ValueError("listener record fields must be 0 or 1")
+    bits = (a.astype(np.uint8) << np.arange(len(LISTENER_FIELDS), dtype=np.uint8)).sum(axis=1)
+    return np.ascontiguousarray(bits.astype(np.uint8))
+
+
+def _prepare_batch(texts, colours):
+    texts = [_as_text(t) for t in texts]
+    if not texts:
+        raise ValueError("empty batch")
+    colours = list(colours)
+    if len(colours) != len(texts):
+        raise ValueError(f"{len(texts)} texts but {len(colours)} colour bits")
+    rec = np.array([_flag("colour", c) for c in colours], dtype=np.uint8) << 6
+    lens = np.fromiter((len(t) for t in texts), dtype=np.int32, count=len(texts))
+    if int(lens.sum(dtype=np.int64)) >= 2**31:
+        raise ValueError("batch text larger than 2 GiB: split it")
+    offs = np.zeros(len(texts), dtype=np.int32)
+    np.cumsum(lens[:-1], out=offs[1:])
+    return b"".join(texts), offs, lens, rec
+
+
+def _prepare_broadcast(text, listeners, rm_is_null, force_listen, com_num):
+    text = _as_text(text)
+    rec = _listener_records(listeners)
+    flags = _flag("rm_is_null", rm_is_null), _flag("force_listen", force_listen)
+    if not isinstance(com_num, (int, np.integer)) or isinstance(com_num, bool) or not 0 <= int(com_num) < NUM_COMMANDS:
+        raise ValueError(f"com_num must be a command number in [0, {NUM_COMMANDS}), not {com_num!r}")
+    return text, rec, flags[0], flags[1], int(com_num)
+
+
+# ------------------------------------------------------------------ the library
+class _Timing(ctypes.Structure):
+    _fields_ = [("kernels_us", ctypes.c_double), ("end_to_end_us", ctypes.c_double)]
+
+
+_LIB = None
+
+
+def hipcc() -> str | None:
+    return shutil.which("hipcc") or next((p for p in ("/opt/rocm/bin/hipcc",) if os.access(p, os.X_OK)), None)
+
+
+def build_library(force: bool = False, timeout: float = 600) -> Path:
+    """Compile fanout.hip for gfx950 into _build/libnuts_device.so (when missing, stale, or ``force``)."""
+    if not force and LIBRARY.exists() and LIBRARY.stat().st_mtime >= SOURCE.stat().st_mtime:
+        return LIBRARY
+    cc = hipcc()
+    if cc is None:
+        raise RuntimeError("hipcc not found: cannot build nuts333_amd/device/_build/libnuts_device.so")
+    LIBRARY.parent.mkdir(exist_ok=True)
+    tmp = LIBRARY.with_name(f".{LIBRARY.name}.{os.getpid()}")
+    subprocess.run([cc, "--offload-arch=gfx950", "-O3", "-shared", "-fPIC", str(SOURCE), "-o", str(tmp)],
+                   check=True, timeout=timeout)
+    os.replace(tmp, LIBRARY)
+    return LIBRARY
+
+
+def _load():
+    global _LIB
+    if _LIB is None:
+        lib = ctypes.CDLL(str(build_library()))
+        lib.nd_last_error.restype = ctypes.c_char_p
+        lib.nd_device_count.restype = ctypes.c_int
+        P = ctypes.c_void_p
+        lib.nd_fanout.argtypes = [ctypes.c_int, P, ctypes.c_int64, P, P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                  ctypes.c_int, P, P, P, ctypes.c_int64, ctypes.POINTER(_Timing)]
+        lib.nd_fanout.restype = ctypes.c_int
+        lib.nd_arena.restype = P
+        lib.nd_write_sizes.restype = P
+        _LIB = lib
+    return _LIB
+
+
+def device_count() -> int:
+    """Visible GPUs (loads, and if needed builds, the library; does not allocate on the device)."""
+    n = _load().nd_device_count()
+    if n < 0:
+        raise RuntimeError(_LIB.nd_last_error().decode(errors="replace"))
+    return n
+
+
+def _ptr(a: np.ndarray) -> int:
+    return a.ctypes.data
+
+
+def _run(broadcast: bool, text: bytes, offs, lens, rec, rm_is_null=0, force_listen=0, com_num=0) -> Fanout:
+    lib = _load()
+    n = len(rec)
+    admitted = np.zeros(n, dtype=np.uint8)
+    out_off = np.zeros(n + 1, dtype=np.int64)
+    w_off = np.zeros(n + 1, dtype=np.int32)
+    tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
+    arena_bound = n * max_bytes(len(text)) if broadcast else int(max_bytes(0) * n + 6 * lens.sum(dtype=np.int64))
+    t = _Timing()
+    rc = lib.nd_fanout(int(broadcast), _ptr(tbuf), len(text), _ptr(offs) if offs is not None else None, _ptr(lens),
+                       _ptr(rec), n, rm_is_null, force_listen, com_num, _ptr(admitted), _ptr(out_off), _ptr(w_off),
+                       arena_bound, ctypes.byref(t))
+    if rc != 0:
+        raise RuntimeError(f"device fan-out failed: {lib.nd_last_error().decode(errors='replace')}")
+    nbytes, nwrites = int(out_off[-1]), int(w_off[-1])
+    arena = np.ctypeslib.as_array(ctypes.cast(lib.nd_arena(), ctypes.POINTER(ctypes.c_uint8)), (max(nbytes, 1),))
+    wsz = np.ctypeslib.as_array(ctypes.cast(lib.nd_write_sizes(), ctypes.POINTER(ctypes.c_int32)), (max(nwrites, 1),))
+    return Fanout(admitted=admitted.astype(bool), out_offsets=out_off, arena=arena[:nbytes].copy(),
+                  write_offsets=w_off.astype(np.int64), write_sizes=wsz[:nwrites].copy(),
+                  timing={"kernels_us": t.kernels_us, "end_to_end_us": t.end_to_end_us})
+
+
+def transduce_batch(texts, colours) -> Fanout:
+    """M independent (text, colour) items through the transducer; every item is admitted."""
+    text, offs, lens, rec = _prepare_batch(texts, colours)
+    return _run(False, text, offs, lens, rec)
+
+
+def broadcast(text, listeners, rm_is_null, force_listen, com_num) -> Fanout:
+    """One text to N listeners.  ``listeners``: (N, 7) table of 0/1 in LISTENER_FIELDS order."""
+    text, rec, rm_is_null, force_listen, com_num = _prepare_broadcast(text, listeners, rm_is_null, force_listen, com_num)
+    lens = np.array([len(text)], dtype=np.int32)
+    return _run(True, text, None, lens, rec, rm_is_null, force_listen, com_num)

@@ -1,0 +1,148 @@
+"""What one broadcast's user-space stage costs on the MI355X, done by a kernel that does the work.
+
+    python -m nuts333_amd.devpath [--reps R] [--warmup W] [--pathbench-iterations I]   -> one JSON line
+
+For N in {10, 100, 1000} listeners, the two texts oracle/pathbench.c times (``say``; ``shout`` carrying ``~OL``/``~RS``)
+and colour all-off / all-on / half, one ``nuts333_amd.device.broadcast`` per repetition (listener 0 is the sender, the
+rest are admitted: the bench headline's shape).  Per case:
+
+* ``kernels_us``: device events around the fan-out kernels (measure, two rocPRIM scans, emit);
+* ``end_to_end_us``: host clock around the listener table + text H2D, the kernels, the results' D2H and a synchronise;
+* ``cpu_derived_us``: the CPU user-space time of the same broadcast, DERIVED from ``oracle/_build/pathbench`` run in the
+  same call: (N - 1) per-recipient transduces + N predicates + one ``format_line_once``;
+* ``bytes_out``: output bytes per broadcast (checked against the CPU restatement once per case).
+
+Median and spread (p10, p90) over the repetitions, after a warm-up.  With no GPU visible the command exits 2; it has
+no CPU fall-back.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes
+import json
+import statistics
+import subprocess
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+from nuts333_amd import device
+
+REPO = Path(__file__).resolve().parent.parent
+PATHBENCH = REPO / "oracle" / "_build" / "pathbench"
+PATH_LIB = REPO / "oracle" / "_build" / "libnuts_path.so"
+
+#: the texts oracle/pathbench.c times (its snprintf formats, line number 123)
+TEXTS = {
+    "say": b"Uaaa says: synthetic broadcast line 000123 from the nuts333 bench\n",
+    "shout": b"~OLUaaa shouts:~RS synthetic broadcast line 000123 from the nuts333 bench\n",
+}
+COM = {"say": device.COM_SAY, "shout": device.COM_SHOUT}
+SIZES = (10, 100, 1000)
+COLOURS = ("off", "on", "half")
+
+
+def listeners(n: int, colour: str) -> np.ndarray:
+    """n listeners in the sender's room; listener 0 is the sender; colour off / on / every other one."""
+    t = np.zeros((n, len(device.LISTENER_FIELDS)), dtype=np.uint8)
+    t[:, device.LISTENER_FIELDS.index("has_room")] = 1
+    t[:, device.LISTENER_FIELDS.index("same_room")] = 1
+    t[0, device.LISTENER_FIELDS.index("is_sender")] = 1
+    c = device.LISTENER_FIELDS.index("colour")
+    t[:, c] = {"off": 0, "on": 1}.get(colour, 0)
+    if colour == "half":
+        t[1::2, c] = 1
+    return t
+
+
+def _stats(xs: list[float]) -> dict:
+    q = np.percentile(xs, [10, 90])
+    return {"median": round(statistics.median(xs), 2), "p10": round(float(q[0]), 2), "p90": round(float(q[1]), 2)}
+
+
+def _cpu_expected_bytes(text: bytes, colour_of: np.ndarray) -> int:
+    lib = ctypes.CDLL(str(PATH_LIB))
+    lib.np_transduce.restype = ctypes.c_size_t
+    lib.np_transduce.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
+    per = {c: lib.np_transduce(text, c, None, 0) for c in (0, 1)}
+    return sum(per[int(c)] for c in colour_of)
+
+
+def pathbench(iterations: int) -> dict:
+    p = subprocess.run([str(PATHBENCH), str(iterations)], stdout=subprocess.PIPE, check=True, timeout=600)
+    return json.loads(p.stdout.decode())
+
+
+def cpu_derived_us(pb: dict, text: str, colour: str, n: int) -> float:
+    """(N - 1) transduces + N predicates + one format_line_once, from pathbench's per-recipient figures."""
+    on, off = pb[f"transduce_{text}_colour_on_ns"], pb[f"transduce_{text}_colour_off_ns"]
+    per = {"off": off, "on": on, "half": (on + off) / 2}[colour]
+    return ((n - 1) * per + n * pb["fanout_predicate_ns"] + pb["format_line_once_ns"]) / 1e3
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--reps", type=int, default=2000, help="timed broadcasts per case (default 2000)")
+    ap.add_argument("--warmup", type=int, default=200, help="untimed broadcasts per case first (default 200)")
+    ap.add_argument("--pathbench-iterations", type=int, default=2_000_000)
+    a = ap.parse_args(argv)
+    if a.reps < 1 or a.warmup < 0:
+        ap.error("--reps must be >= 1 and --warmup >= 0")
+    if not PATHBENCH.exists() or not PATH_LIB.exists():
+        subprocess.run(["make", "-s", "-C", str(REPO / "oracle"), "port"], check=True)
+    try:
+        ngpu = device.device_count()
+    except (RuntimeError, OSError, subprocess.SubprocessError) as e:
+        print(f"devpath: cannot use the device library: {e}", file=sys.stderr)
+        return 2
+    if ngpu < 1:
+        print("devpath: no GPU visible; this command measures the device path and has no CPU fall-back",
+              file=sys.stderr)
+        return 2
+
+    t_start = time.perf_counter()
+    pb = pathbench(a.pathbench_iterations)
+    cases = []
+    for n in SIZES:
+        for text in TEXTS:
+            for colour in COLOURS:
+                table = listeners(n, colour)
+                run = lambda: device.broadcast(TEXTS[text], table, 0, 0, COM[text])
+                first = run()
+                expect = _cpu_expected_bytes(TEXTS[text], table[1:, device.LISTENER_FIELDS.index("colour")])
+                if int(first.out_offsets[-1]) != expect or int(first.admitted.sum()) != n - 1:
+                    raise SystemExit(f"devpath: {n}/{text}/{colour}: device produced {int(first.out_offsets[-1])} "
+                                     f"bytes, the CPU restatement {expect}")
+                for _ in range(a.warmup):
+                    run()
+                k, e = [], []
+                for _ in range(a.reps):
+                    r = run()
+                    k.append(r.timing["kernels_us"])
+                    e.append(r.timing["end_to_end_us"])
+                cpu = cpu_derived_us(pb, text, colour, n)
+                ke = _stats(e)
+                cases.append({"n": n, "text": text, "colour": colour, "recipients": n - 1,
+                              "bytes_out": int(first.out_offsets[-1]), "writes": int(first.write_offsets[-1]),
+                              "kernels_us": _stats(k), "end_to_end_us": ke,
+                              "cpu_derived_us": round(cpu, 3),
+                              "end_to_end_over_cpu": round(ke["median"] / cpu, 1)})
+    out = {
+        "what": "user-space stage of one broadcast (admit predicate + transducer), device vs CPU",
+        "device": "gfx950",
+        "kernels": ["nuts_fanout_measure_broadcast", "rocprim device scan x2", "nuts_fanout_emit_broadcast"],
+        "reps": a.reps, "warmup": a.warmup,
+        "end_to_end_covers": "listener table + text H2D, kernels, admitted/offsets/arena/write-size D2H, synchronise",
+        "cpu_derived_from": {"pathbench": {k: v for k, v in pb.items() if k not in ("sink", "admitted")},
+                             "formula": "(N-1) x transduce + N x fanout_predicate + format_line_once (derived, not timed)"},
+        "cases": cases,
+        "wall_s": round(time.perf_counter() - t_start, 1),
+    }
+    print(json.dumps(out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
