@@ -175,7 +175,7 @@ def _load():
         lib.nd_device_count.restype = ctypes.c_int
         P = ctypes.c_void_p
         lib.nd_fanout.argtypes = [ctypes.c_int, P, ctypes.c_int64, P, P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                  ctypes.c_int, P, P, P, ctypes.c_int64, ctypes.POINTER(_Timing)]
+                                  ctypes.c_int, P, P, P, ctypes.POINTER(_Timing)]
         lib.nd_fanout.restype = ctypes.c_int
         lib.nd_arena.restype = P
         lib.nd_write_sizes.restype = P
@@ -202,11 +202,10 @@ def _run(broadcast: bool, text: bytes, offs, lens, rec, rm_is_null=0, force_list
     out_off = np.zeros(n + 1, dtype=np.int64)
     w_off = np.zeros(n + 1, dtype=np.int32)
     tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
-    arena_bound = n * max_bytes(len(text)) if broadcast else int(max_bytes(0) * n + 6 * lens.sum(dtype=np.int64))
     t = _Timing()
     rc = lib.nd_fanout(int(broadcast), _ptr(tbuf), len(text), _ptr(offs) if offs is not None else None, _ptr(lens),
                        _ptr(rec), n, rm_is_null, force_listen, com_num, _ptr(admitted), _ptr(out_off), _ptr(w_off),
-                       arena_bound, ctypes.byref(t))
+                       ctypes.byref(t))
     if rc != 0:
         raise RuntimeError(f"device fan-out failed: {lib.nd_last_error().decode(errors='replace')}")
     nbytes, nwrites = int(out_off[-1]), int(w_off[-1])

@@ -10,23 +10,28 @@
 // Work is a batch of items: (text offset, text length, colour bit) plus, in broadcast mode, a
 // listener record.  One lane per item, because the flush rule depends on the running position.
 //   pass 1  nuts_fanout_measure_{batch,broadcast}: admit flag, output bytes, write count per item
-//   scan    hipcub DeviceScan::ExclusiveSum of bytes (int64) and write counts (int32)
+//   scan    hipcub DeviceScan::ExclusiveSum of bytes (int64) and write counts (int32), over n + 1
+//           entries (the last one zero), so that the last offsets are the totals
 //   pass 2  nuts_fanout_emit_{batch,broadcast}: bytes into the arena, chunk sizes into write_sizes
-// In broadcast mode every item reads the same text, which each block stages in LDS once.
+// In broadcast mode every item reads the same text, which each block stages in LDS once.  All four
+// kernels take one argument struct (Args), filled by the host.
 //
 // Hard bounds per item of a text of len < 2000 bytes: 6*len + 4 output bytes (a '\n' with colour
 // on is the costliest input byte, plus the trailing reset) and 16 writes.  The host sizes its buffers
 // by them; pass 2 never writes past the counts pass 1 measured for its own item.
 //
-// C ABI at the bottom; built with
+// The host library keeps one device block, laid out afresh per call into every array the kernels
+// use and the scans' scratch.  C ABI at the bottom; built with
 //   hipcc --offload-arch=gfx950 -O3 -shared -fPIC fanout.hip -o _build/libnuts_device.so
 
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 
 namespace {
 
@@ -150,118 +155,100 @@ __device__ void transduce(const uint8_t* s, int len, bool colour, Sink<EMIT>& k)
     }
 }
 
-// Stage the broadcast's shared text in LDS (every lane of the block reads it byte by byte).
-__device__ __forceinline__ const uint8_t* stage_text(uint8_t* lds, const uint8_t* text, int len)
+// Everything a kernel reads or writes, filled on the host and passed by value to all four kernels.  The per-item
+// arrays hold n entries; nbytes / nwrites / out_off / w_off hold n + 1, the last count zero, so that the scans
+// leave the totals in out_off[n] / w_off[n].
+struct Args {
+    const uint8_t* text;         // broadcast: the shared text; batch: the items' texts, packed
+    const int32_t* text_off;     // batch only
+    const int32_t* text_len;     // broadcast: text_len[0] only
+    const uint8_t* rec;          // listener record (broadcast) or the colour bit alone (batch)
+    int n;
+    int rm_is_null, force_listen, com_num;   // broadcast only
+    uint8_t* admitted;
+    int64_t* nbytes;             // pass 1: bytes per item
+    int32_t* nwrites;            // pass 1: write(2) calls per item
+    int64_t* out_off;            // scan of nbytes: each item's slot in the arena
+    int32_t* w_off;              // scan of nwrites: each item's first entry in wsz
+    int* violations;             // items past the hard bounds
+    uint8_t* arena;
+    int64_t arena_cap;
+    int32_t* wsz;                // chunk sizes
+    int64_t wsz_cap;
+};
+
+// Lane i's item, or false past the end.  In a broadcast the whole block first stages the shared text in LDS
+// (every lane reads it byte by byte), so every lane calls this before it may return.
+template <bool BROADCAST>
+__device__ __forceinline__ bool load_item(const Args& a, int i, const uint8_t*& s, int& len)
 {
-    for (int j = threadIdx.x; j < len; j += blockDim.x) lds[j] = text[j];
-    __syncthreads();
-    return lds;
+    if (BROADCAST) {
+        __shared__ uint8_t lds[kTextSize];
+        len = a.text_len[0];
+        for (int j = threadIdx.x; j < len; j += blockDim.x) lds[j] = a.text[j];
+        __syncthreads();
+        s = lds;
+        return i < a.n;
+    }
+    if (i >= a.n) return false;
+    s = a.text + a.text_off[i];
+    len = a.text_len[i];
+    return true;
 }
 
 template <bool BROADCAST>
-__device__ void measure(const uint8_t* text, const int32_t* text_off, const int32_t* text_len, const uint8_t* rec,
-                        int n_items, int rm_is_null, int force_listen, int com_num, uint8_t* admitted, int64_t* nbytes,
-                        int32_t* nwrites, int* bound_violations)
+__device__ void measure(const Args& a)
 {
-    __shared__ uint8_t lds[kTextSize];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint8_t* s = text;
+    if (i == 0) {               // the scans' extra entry
+        a.nbytes[a.n] = 0;
+        a.nwrites[a.n] = 0;
+    }
+    const uint8_t* s;
     int len;
-    if (BROADCAST) {
-        len = text_len[0];
-        s = stage_text(lds, text, len);
-    }
-    if (i >= n_items) return;
-    if (!BROADCAST) {
-        s = text + text_off[i];
-        len = text_len[i];
-    }
-    const uint8_t l = rec[i];
-    const bool in = !BROADCAST || admits(l, rm_is_null, force_listen, com_num);
+    if (!load_item<BROADCAST>(a, i, s, len)) return;
+    const uint8_t l = a.rec[i];
+    const bool in = !BROADCAST || admits(l, a.rm_is_null, a.force_listen, a.com_num);
     Sink<false> k{nullptr, nullptr, 0, 0};
     if (in) transduce(s, len, (l & kColour) != 0, k);
-    if (k.n > 6 * (int64_t)len + 4 || k.writes > kMaxWrites) atomicAdd(bound_violations, 1);
-    admitted[i] = in;
-    nbytes[i] = k.n;
-    nwrites[i] = k.writes;
+    if (k.n > 6 * (int64_t)len + 4 || k.writes > kMaxWrites) atomicAdd(a.violations, 1);
+    a.admitted[i] = in;
+    a.nbytes[i] = k.n;
+    a.nwrites[i] = k.writes;
 }
 
 template <bool BROADCAST>
-__device__ void emit(const uint8_t* text, const int32_t* text_off, const int32_t* text_len, const uint8_t* rec,
-                     int n_items, const uint8_t* admitted, const int64_t* nbytes, const int32_t* nwrites,
-                     const int64_t* out_off, const int32_t* w_off, uint8_t* arena, int64_t arena_cap,
-                     int32_t* write_sizes, int64_t wsz_cap)
+__device__ void emit(const Args& a)
 {
-    __shared__ uint8_t lds[kTextSize];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint8_t* s = text;
+    const uint8_t* s;
     int len;
-    if (BROADCAST) {
-        len = text_len[0];
-        s = stage_text(lds, text, len);
-    }
-    if (i >= n_items || !admitted[i]) return;
-    if (!BROADCAST) {
-        s = text + text_off[i];
-        len = text_len[i];
-    }
+    if (!load_item<BROADCAST>(a, i, s, len) || !a.admitted[i]) return;
     // never past the arena or the chunk array, even if pass 1 broke the bounds the host allocated by
-    const int64_t room = arena_cap - out_off[i], wroom = (int64_t)wsz_cap - w_off[i];
-    const int64_t cap = nbytes[i] < room ? nbytes[i] : (room > 0 ? room : 0);
-    const int wcap = (int)(nwrites[i] < wroom ? nwrites[i] : (wroom > 0 ? wroom : 0));
-    Sink<true> k{arena + out_off[i], write_sizes + w_off[i], cap, wcap};
-    transduce(s, len, (rec[i] & kColour) != 0, k);
+    const int64_t room = a.arena_cap - a.out_off[i], wroom = a.wsz_cap - a.w_off[i];
+    const int64_t cap = a.nbytes[i] < room ? a.nbytes[i] : (room > 0 ? room : 0);
+    const int wcap = (int)(a.nwrites[i] < wroom ? a.nwrites[i] : (wroom > 0 ? wroom : 0));
+    Sink<true> k{a.arena + a.out_off[i], a.wsz + a.w_off[i], cap, wcap};
+    transduce(s, len, (a.rec[i] & kColour) != 0, k);
 }
 
 }  // namespace
 
 // Stable, unmangled kernel names (they are what rocprofv3 reports).
-extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_measure_batch(
-    const uint8_t* text, const int32_t* text_off, const int32_t* text_len, const uint8_t* rec, int n_items,
-    uint8_t* admitted, int64_t* nbytes, int32_t* nwrites, int* bound_violations)
-{
-    measure<false>(text, text_off, text_len, rec, n_items, 0, 0, 0, admitted, nbytes, nwrites, bound_violations);
-}
-
-extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_measure_broadcast(
-    const uint8_t* text, const int32_t* text_len, const uint8_t* rec, int n_items, int rm_is_null, int force_listen,
-    int com_num, uint8_t* admitted, int64_t* nbytes, int32_t* nwrites, int* bound_violations)
-{
-    measure<true>(text, nullptr, text_len, rec, n_items, rm_is_null, force_listen, com_num, admitted, nbytes, nwrites,
-                  bound_violations);
-}
-
-extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_emit_batch(
-    const uint8_t* text, const int32_t* text_off, const int32_t* text_len, const uint8_t* rec, int n_items,
-    const uint8_t* admitted, const int64_t* nbytes, const int32_t* nwrites, const int64_t* out_off, const int32_t* w_off,
-    uint8_t* arena, int64_t arena_cap, int32_t* write_sizes, int64_t wsz_cap)
-{
-    emit<false>(text, text_off, text_len, rec, n_items, admitted, nbytes, nwrites, out_off, w_off, arena, arena_cap,
-                write_sizes, wsz_cap);
-}
-
-extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_emit_broadcast(
-    const uint8_t* text, const int32_t* text_len, const uint8_t* rec, int n_items, const uint8_t* admitted,
-    const int64_t* nbytes, const int32_t* nwrites, const int64_t* out_off, const int32_t* w_off, uint8_t* arena,
-    int64_t arena_cap, int32_t* write_sizes, int64_t wsz_cap)
-{
-    emit<true>(text, nullptr, text_len, rec, n_items, admitted, nbytes, nwrites, out_off, w_off, arena, arena_cap,
-               write_sizes, wsz_cap);
-}
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_measure_batch(Args a) { measure<false>(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_measure_broadcast(Args a) { measure<true>(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_emit_batch(Args a) { emit<false>(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_emit_broadcast(Args a) { emit<true>(a); }
 
 // ------------------------------------------------------------------------------------------ host library
 
 namespace {
 
-// Device and pinned host buffers, grown on demand and kept across calls (one process, one caller).
+// One device block, laid out afresh for every call (layout()), and the pinned host buffers the results land in;
+// grown on demand and kept across calls (one process, one caller).
 struct Buffers {
-    size_t cap_items = 0, cap_text = 0, cap_arena = 0, cap_scan = 0;   // chunk sizes: cap_items * kMaxWrites
-    size_t cap_host_arena = 0, cap_host_writes = 0;
-    uint8_t *d_text = nullptr, *d_rec = nullptr, *d_admitted = nullptr, *d_arena = nullptr;
-    int32_t *d_text_off = nullptr, *d_text_len = nullptr, *d_nwrites = nullptr, *d_w_off = nullptr, *d_wsz = nullptr;
-    int64_t *d_nbytes = nullptr, *d_out_off = nullptr;
-    int* d_violations = nullptr;
-    void* d_scan = nullptr;
+    uint8_t* d_block = nullptr;
+    size_t cap_block = 0, cap_host_arena = 0, cap_host_writes = 0;
     uint8_t* h_arena = nullptr;         // pinned: the arena's D2H lands here
     int32_t* h_wsz = nullptr;
     hipStream_t stream = nullptr;
@@ -322,42 +309,34 @@ int ensure_ready()
     ND_CHECK(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
     ND_CHECK(hipEventCreate(&g.ev0));
     ND_CHECK(hipEventCreate(&g.ev1));
-    ND_CHECK(hipMalloc((void**)&g.d_violations, sizeof(int)));
     g.ready = true;
     return 0;
 }
 
-// Grow every device buffer for n items, text_bytes of text and the hard output bound of the arena.
-int reserve(size_t n, size_t text_bytes, size_t arena_bound)
+// Point every device array of a (a.n items, the arena and chunk capacities already set) and *scan into the block at
+// base, one 256-byte aligned slice each; returns the bytes they span.  layout(0, ...) sizes the block.
+size_t layout(uintptr_t base, size_t text_bytes, size_t scan_bytes, Args& a, uint8_t** scan)
 {
-    if (n > g.cap_items) {      // the per-item arrays share one capacity
-        (void)hipFree(g.d_rec); (void)hipFree(g.d_admitted); (void)hipFree(g.d_text_off); (void)hipFree(g.d_text_len);
-        (void)hipFree(g.d_nwrites); (void)hipFree(g.d_w_off); (void)hipFree(g.d_nbytes); (void)hipFree(g.d_out_off);
-        (void)hipFree(g.d_wsz); (void)hipFree(g.d_scan);
-        g.d_rec = g.d_admitted = nullptr;
-        g.d_text_off = g.d_text_len = g.d_nwrites = g.d_w_off = g.d_wsz = nullptr;
-        g.d_nbytes = g.d_out_off = nullptr;
-        g.d_scan = nullptr;
-        g.cap_items = g.cap_scan = 0;
-        ND_CHECK(hipMalloc((void**)&g.d_rec, n));
-        ND_CHECK(hipMalloc((void**)&g.d_admitted, n));
-        ND_CHECK(hipMalloc((void**)&g.d_text_off, n * sizeof(int32_t)));
-        ND_CHECK(hipMalloc((void**)&g.d_text_len, n * sizeof(int32_t)));
-        ND_CHECK(hipMalloc((void**)&g.d_nwrites, n * sizeof(int32_t)));
-        ND_CHECK(hipMalloc((void**)&g.d_w_off, n * sizeof(int32_t)));
-        ND_CHECK(hipMalloc((void**)&g.d_nbytes, n * sizeof(int64_t)));
-        ND_CHECK(hipMalloc((void**)&g.d_out_off, n * sizeof(int64_t)));
-        ND_CHECK(hipMalloc((void**)&g.d_wsz, n * kMaxWrites * sizeof(int32_t)));
-        size_t s1 = 0, s2 = 0;
-        ND_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, s1, g.d_nbytes, g.d_out_off, (int)n, g.stream));
-        ND_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, s2, g.d_nwrites, g.d_w_off, (int)n, g.stream));
-        g.cap_scan = s1 > s2 ? s1 : s2;
-        ND_CHECK(hipMalloc(&g.d_scan, g.cap_scan > 0 ? g.cap_scan : 1));
-        g.cap_items = n;
-    }
-    if (grow_dev(&g.d_text, &g.cap_text, text_bytes > 0 ? text_bytes : 1, "text")) return -1;
-    if (grow_dev(&g.d_arena, &g.cap_arena, arena_bound > 0 ? arena_bound : 1, "arena")) return -1;
-    return 0;
+    size_t at = 0;
+    auto take = [&](auto*& p, size_t count) {
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + at);
+        at += (count * sizeof(*p) + 255) & ~(size_t)255;
+    };
+    const size_t n = (size_t)a.n;
+    take(a.text, text_bytes);
+    take(a.text_off, n);
+    take(a.text_len, n);
+    take(a.rec, n);
+    take(a.admitted, n);
+    take(a.nbytes, n + 1);
+    take(a.nwrites, n + 1);
+    take(a.out_off, n + 1);
+    take(a.w_off, n + 1);
+    take(a.violations, 1);
+    take(a.arena, (size_t)a.arena_cap);
+    take(a.wsz, (size_t)a.wsz_cap);
+    take(*scan, scan_bytes);
+    return at;
 }
 
 double now_ns()
@@ -395,7 +374,7 @@ int nd_device_count(void)
 // nd_last_error() set.  The caller has validated the input (no NUL, len < 2000, offsets inside text).
 int nd_fanout(int broadcast, const uint8_t* text, int64_t text_bytes, const int32_t* text_off, const int32_t* text_len,
               const uint8_t* rec, int n, int rm_is_null, int force_listen, int com_num, uint8_t* admitted,
-              int64_t* out_off, int32_t* w_off, int64_t arena_bound, nd_timing* timing)
+              int64_t* out_off, int32_t* w_off, nd_timing* timing)
 {
     if (ensure_ready()) return -1;
     if (n < 1) {
@@ -403,64 +382,57 @@ int nd_fanout(int broadcast, const uint8_t* text, int64_t text_bytes, const int3
         return -1;
     }
     const double t0 = now_ns();
-    if (reserve((size_t)n, (size_t)text_bytes, (size_t)arena_bound)) return -1;
     hipStream_t st = g.stream;
-    size_t need1 = 0, need2 = 0;     // the scans' scratch for this n (reserve() sized it for the capacity)
-    ND_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, need1, g.d_nbytes, g.d_out_off, n, st));
-    ND_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, need2, g.d_nwrites, g.d_w_off, n, st));
-    if (grow_dev((uint8_t**)&g.d_scan, &g.cap_scan, need1 > need2 ? need1 : need2, "scan scratch")) return -1;
-    ND_CHECK(hipMemcpyAsync(g.d_text, text, (size_t)text_bytes, hipMemcpyHostToDevice, st));
-    ND_CHECK(hipMemcpyAsync(g.d_text_len, text_len, (broadcast ? 1 : (size_t)n) * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (!broadcast) ND_CHECK(hipMemcpyAsync(g.d_text_off, text_off, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    ND_CHECK(hipMemcpyAsync(g.d_rec, rec, (size_t)n, hipMemcpyHostToDevice, st));
-    ND_CHECK(hipMemsetAsync(g.d_violations, 0, sizeof(int), st));
+    Args a{};
+    a.n = n;
+    a.rm_is_null = rm_is_null;
+    a.force_listen = force_listen;
+    a.com_num = com_num;
+    a.arena_cap = 4 * (int64_t)n + 6 * text_bytes * (broadcast ? n : 1);   // the hard bound, summed over the items
+    a.wsz_cap = (int64_t)n * kMaxWrites;
+    size_t scan1 = 0, scan2 = 0;     // both scans run over n + 1 entries
+    ND_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan1, a.nbytes, a.out_off, n + 1, st));
+    ND_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan2, a.nwrites, a.w_off, n + 1, st));
+    const size_t scan_bytes = std::max(scan1, scan2);
+    uint8_t* scan = nullptr;
+    const size_t need = layout(0, (size_t)text_bytes, scan_bytes, a, &scan);
+    if (grow_dev(&g.d_block, &g.cap_block, need, "device buffers")) return -1;
+    layout((uintptr_t)g.d_block, (size_t)text_bytes, scan_bytes, a, &scan);
+
+    ND_CHECK(hipMemcpyAsync((void*)a.text, text, (size_t)text_bytes, hipMemcpyHostToDevice, st));
+    ND_CHECK(hipMemcpyAsync((void*)a.text_len, text_len, (broadcast ? 1 : (size_t)n) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (!broadcast) ND_CHECK(hipMemcpyAsync((void*)a.text_off, text_off, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    ND_CHECK(hipMemcpyAsync((void*)a.rec, rec, (size_t)n, hipMemcpyHostToDevice, st));
+    ND_CHECK(hipMemsetAsync(a.violations, 0, sizeof(int), st));
 
     const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
     ND_CHECK(hipEventRecord(g.ev0, st));
-    if (broadcast)
-        hipLaunchKernelGGL(nuts_fanout_measure_broadcast, grid, block, 0, st, g.d_text, g.d_text_len, g.d_rec, n,
-                           rm_is_null, force_listen, com_num, g.d_admitted, g.d_nbytes, g.d_nwrites, g.d_violations);
-    else
-        hipLaunchKernelGGL(nuts_fanout_measure_batch, grid, block, 0, st, g.d_text, g.d_text_off, g.d_text_len, g.d_rec,
-                           n, g.d_admitted, g.d_nbytes, g.d_nwrites, g.d_violations);
+    hipLaunchKernelGGL(broadcast ? nuts_fanout_measure_broadcast : nuts_fanout_measure_batch, grid, block, 0, st, a);
     ND_CHECK(hipGetLastError());
-    size_t scan_bytes = g.cap_scan;
-    ND_CHECK(hipcub::DeviceScan::ExclusiveSum(g.d_scan, scan_bytes, g.d_nbytes, g.d_out_off, n, st));
-    scan_bytes = g.cap_scan;
-    ND_CHECK(hipcub::DeviceScan::ExclusiveSum(g.d_scan, scan_bytes, g.d_nwrites, g.d_w_off, n, st));
-    if (broadcast)
-        hipLaunchKernelGGL(nuts_fanout_emit_broadcast, grid, block, 0, st, g.d_text, g.d_text_len, g.d_rec, n,
-                           g.d_admitted, g.d_nbytes, g.d_nwrites, g.d_out_off, g.d_w_off, g.d_arena,
-                           (int64_t)g.cap_arena, g.d_wsz, (int64_t)g.cap_items * kMaxWrites);
-    else
-        hipLaunchKernelGGL(nuts_fanout_emit_batch, grid, block, 0, st, g.d_text, g.d_text_off, g.d_text_len, g.d_rec, n,
-                           g.d_admitted, g.d_nbytes, g.d_nwrites, g.d_out_off, g.d_w_off, g.d_arena,
-                           (int64_t)g.cap_arena, g.d_wsz, (int64_t)g.cap_items * kMaxWrites);
+    size_t bytes = scan_bytes;
+    ND_CHECK(hipcub::DeviceScan::ExclusiveSum(scan, bytes, a.nbytes, a.out_off, n + 1, st));
+    bytes = scan_bytes;
+    ND_CHECK(hipcub::DeviceScan::ExclusiveSum(scan, bytes, a.nwrites, a.w_off, n + 1, st));
+    hipLaunchKernelGGL(broadcast ? nuts_fanout_emit_broadcast : nuts_fanout_emit_batch, grid, block, 0, st, a);
     ND_CHECK(hipGetLastError());
     ND_CHECK(hipEventRecord(g.ev1, st));
 
     // the small per-item arrays first: they say how much of the arena to fetch
-    int64_t last_len = 0;
-    int32_t last_w = 0;
     int violations = 0;
-    ND_CHECK(hipMemcpyAsync(admitted, g.d_admitted, (size_t)n, hipMemcpyDeviceToHost, st));
-    ND_CHECK(hipMemcpyAsync(out_off, g.d_out_off, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    ND_CHECK(hipMemcpyAsync(w_off, g.d_w_off, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    ND_CHECK(hipMemcpyAsync(&last_len, g.d_nbytes + (n - 1), sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    ND_CHECK(hipMemcpyAsync(&last_w, g.d_nwrites + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    ND_CHECK(hipMemcpyAsync(&violations, g.d_violations, sizeof(int), hipMemcpyDeviceToHost, st));
+    ND_CHECK(hipMemcpyAsync(admitted, a.admitted, (size_t)n, hipMemcpyDeviceToHost, st));
+    ND_CHECK(hipMemcpyAsync(out_off, a.out_off, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    ND_CHECK(hipMemcpyAsync(w_off, a.w_off, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    ND_CHECK(hipMemcpyAsync(&violations, a.violations, sizeof(int), hipMemcpyDeviceToHost, st));
     ND_CHECK(hipStreamSynchronize(st));
     if (violations) {
         snprintf(g_err, sizeof(g_err), "%d item(s) exceeded the hard output bounds (6*len+4 bytes, %d writes)",
                  violations, kMaxWrites);
         return -1;
     }
-    out_off[n] = out_off[n - 1] + last_len;
-    w_off[n] = w_off[n - 1] + last_w;
     if (grow_host(&g.h_arena, &g.cap_host_arena, (size_t)out_off[n] + 1, "pinned arena")) return -1;
     if (grow_host(&g.h_wsz, &g.cap_host_writes, (size_t)w_off[n] + 1, "pinned write sizes")) return -1;
-    ND_CHECK(hipMemcpyAsync(g.h_arena, g.d_arena, (size_t)out_off[n], hipMemcpyDeviceToHost, st));
-    ND_CHECK(hipMemcpyAsync(g.h_wsz, g.d_wsz, (size_t)w_off[n] * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    ND_CHECK(hipMemcpyAsync(g.h_arena, a.arena, (size_t)out_off[n], hipMemcpyDeviceToHost, st));
+    ND_CHECK(hipMemcpyAsync(g.h_wsz, a.wsz, (size_t)w_off[n] * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     ND_CHECK(hipStreamSynchronize(st));
     const double t1 = now_ns();
 

@@ -18,7 +18,6 @@ no CPU fall-back.
 from __future__ import annotations
 
 import argparse
-import ctypes
 import json
 import statistics
 import subprocess
@@ -28,11 +27,10 @@ from pathlib import Path
 
 import numpy as np
 
-from nuts333_amd import device
+from nuts333_amd import device, nuts_path
 
 REPO = Path(__file__).resolve().parent.parent
 PATHBENCH = REPO / "oracle" / "_build" / "pathbench"
-PATH_LIB = REPO / "oracle" / "_build" / "libnuts_path.so"
 
 #: the texts oracle/pathbench.c times (its snprintf formats, line number 123)
 TEXTS = {
@@ -62,14 +60,6 @@ def _stats(xs: list[float]) -> dict:
     return {"median": round(statistics.median(xs), 2), "p10": round(float(q[0]), 2), "p90": round(float(q[1]), 2)}
 
 
-def _cpu_expected_bytes(text: bytes, colour_of: np.ndarray) -> int:
-    lib = ctypes.CDLL(str(PATH_LIB))
-    lib.np_transduce.restype = ctypes.c_size_t
-    lib.np_transduce.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
-    per = {c: lib.np_transduce(text, c, None, 0) for c in (0, 1)}
-    return sum(per[int(c)] for c in colour_of)
-
-
 def pathbench(iterations: int) -> dict:
     p = subprocess.run([str(PATHBENCH), str(iterations)], stdout=subprocess.PIPE, check=True, timeout=600)
     return json.loads(p.stdout.decode())
@@ -90,8 +80,8 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
     if a.reps < 1 or a.warmup < 0:
         ap.error("--reps must be >= 1 and --warmup >= 0")
-    if not PATHBENCH.exists() or not PATH_LIB.exists():
-        subprocess.run(["make", "-s", "-C", str(REPO / "oracle"), "port"], check=True)
+    if not PATHBENCH.exists():
+        nuts_path.build()
     try:
         ngpu = device.device_count()
     except (RuntimeError, OSError, subprocess.SubprocessError) as e:
@@ -111,7 +101,8 @@ def main(argv=None) -> int:
                 table = listeners(n, colour)
                 run = lambda: device.broadcast(TEXTS[text], table, 0, 0, COM[text])
                 first = run()
-                expect = _cpu_expected_bytes(TEXTS[text], table[1:, device.LISTENER_FIELDS.index("colour")])
+                colour_of = table[1:, device.LISTENER_FIELDS.index("colour")]
+                expect = sum(len(nuts_path.transduce(TEXTS[text], int(c))) for c in colour_of)
                 if int(first.out_offsets[-1]) != expect or int(first.admitted.sum()) != n - 1:
                     raise SystemExit(f"devpath: {n}/{text}/{colour}: device produced {int(first.out_offsets[-1])} "
                                      f"bytes, the CPU restatement {expect}")

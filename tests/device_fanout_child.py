@@ -2,15 +2,14 @@
 
 A process that boots talkers never initialises HIP, so the test module starts this script once,
 under ``timeout``, and asserts on the one JSON line it prints (``DEVICE_FANOUT {...}``).  Every check compares the
-device's bytes AND write(2) chunk sizes with ``np_write_user_stream`` / ``np_fanout_admits`` of the CPU restatement
-(oracle/_build/libnuts_path.so), called through ctypes with a collecting callback.
+device's bytes AND write(2) chunk sizes with ``np_write_user_stream`` / ``np_fanout_admits`` of the CPU restatement,
+called through its binding (nuts333_amd.nuts_path).
 
     python tests/device_fanout_child.py [--fuzz N]
 """
 from __future__ import annotations
 
 import argparse
-import ctypes
 import json
 import random
 import sys
@@ -21,34 +20,11 @@ import numpy as np
 REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO))
 
+from nuts333_amd import nuts_path  # noqa: E402
+
 CODES = "RS OL UL LI RV FK FR FG FY FB FM FT FW BK BR BG BY BB BM BT BW".split()
 WORDS = ["hello", "there", "nuts", "talker", "lines", "x", "yy", "zzz", "Scunthorpe", "42", "ok"]
 TEXT_MAX = 1999
-
-
-# ------------------------------------------------------------------ the CPU restatement
-class _Listener(ctypes.Structure):
-    _fields_ = [(f, ctypes.c_int) for f in ("login", "has_room", "same_room", "ignall", "ignshout", "is_sender")]
-
-
-_EMIT = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
-
-
-class Oracle:
-    def __init__(self):
-        self.lib = ctypes.CDLL(str(REPO / "oracle" / "_build" / "libnuts_path.so"))
-        self.lib.np_write_user_stream.argtypes = [ctypes.c_char_p, ctypes.c_int, _EMIT, ctypes.c_void_p]
-        self.lib.np_fanout_admits.argtypes = [ctypes.POINTER(_Listener), ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        self._sink: list[bytes] = []
-        self._emit = _EMIT(lambda ctx, buf, n: self._sink.append(ctypes.string_at(buf, n)))
-
-    def chunks(self, text: bytes, colour: int) -> list[bytes]:
-        self._sink = []
-        self.lib.np_write_user_stream(text, colour, self._emit, None)
-        return self._sink
-
-    def admits(self, fields, rm_is_null: int, force_listen: int, com_num: int) -> bool:
-        return bool(self.lib.np_fanout_admits(ctypes.byref(_Listener(*fields)), rm_is_null, force_listen, com_num))
 
 
 # ------------------------------------------------------------------ inputs
@@ -116,7 +92,7 @@ def fuzz_items(seed: int, n: int):
 
 
 # ------------------------------------------------------------------ checks
-def compare_batch(dev, oracle: Oracle, items, batch: int = 50_000) -> dict:
+def compare_batch(dev, items, batch: int = 50_000) -> dict:
     from nuts333_amd import device
     bad, n_bad, total_bytes, total_writes, worst_bytes, worst_writes = [], 0, 0, 0, 0, 0
     for lo in range(0, len(items), batch):
@@ -124,7 +100,7 @@ def compare_batch(dev, oracle: Oracle, items, batch: int = 50_000) -> dict:
         r = dev.transduce_batch([t for t, _ in part], [c for _, c in part])
         for j, (t, c) in enumerate(part):
             got = device.chunks(r, j)
-            want = oracle.chunks(t, c)
+            want = nuts_path.chunks(t, c)
             nb = sum(map(len, got))
             total_bytes += nb
             total_writes += len(got)
@@ -139,7 +115,7 @@ def compare_batch(dev, oracle: Oracle, items, batch: int = 50_000) -> dict:
             "max_bytes_minus_bound": worst_bytes, "max_writes": worst_writes}
 
 
-def vectors(dev, oracle: Oracle) -> dict:
+def vectors(dev) -> dict:
     from nuts333_amd import device
     doc = json.loads((REPO / "tests" / "golden" / "vectors" / "transducer.json").read_text())
     texts, colours, expect = [], [], []
@@ -151,12 +127,12 @@ def vectors(dev, oracle: Oracle) -> dict:
             expect.append(v[key].encode("latin-1"))
     r = dev.transduce_batch(texts, colours)
     concat_bad = [i for i in range(len(texts)) if r.output(i) != expect[i]]
-    chunk_bad = [i for i in range(len(texts)) if device.chunks(r, i) != oracle.chunks(texts[i], colours[i])]
+    chunk_bad = [i for i in range(len(texts)) if device.chunks(r, i) != nuts_path.chunks(texts[i], colours[i])]
     return {"vectors": len(doc["vectors"]), "items": len(texts), "concat_bad": concat_bad[:10],
             "n_concat_bad": len(concat_bad), "n_chunk_bad": len(chunk_bad)}
 
 
-def predicate(dev, oracle: Oracle) -> dict:
+def predicate(dev) -> dict:
     """All 2^6 listener states x rm_is_null x force_listen x {SAY, SHOUT, SEMOTE}: one 64-listener broadcast each."""
     from nuts333_amd import device
     text = b"~OLUaaa shouts:~RS hello /~ there\n"
@@ -170,9 +146,9 @@ def predicate(dev, oracle: Oracle) -> dict:
                 r = dev.broadcast(text, table, rm_is_null, force_listen, com)
                 for i, st in enumerate(states):
                     cases += 1
-                    want = oracle.admits(st, rm_is_null, force_listen, com)
+                    want = nuts_path.admits(st, rm_is_null, force_listen, com)
                     out = device.chunks(r, i)
-                    ok = bool(r.admitted[i]) == want and out == (oracle.chunks(text, table[i][6]) if want else [])
+                    ok = bool(r.admitted[i]) == want and out == (nuts_path.chunks(text, table[i][6]) if want else [])
                     if not ok:
                         bad += 1
                         if len(first) < 5:
@@ -181,7 +157,7 @@ def predicate(dev, oracle: Oracle) -> dict:
     return {"cases": cases, "n_bad": bad, "first_bad": first}
 
 
-def broadcast_1000(dev, oracle: Oracle) -> dict:
+def broadcast_1000(dev) -> dict:
     """1000 listeners, mixed colour and ignshout, the sender among them, a few logging in / elsewhere: a .shout."""
     from nuts333_amd import device
     rng = random.Random(1410)
@@ -193,9 +169,9 @@ def broadcast_1000(dev, oracle: Oracle) -> dict:
     r = dev.broadcast(text, table, 1, 0, device.COM_SHOUT)
     want_admit, bad = [], 0
     for i, row in enumerate(table):
-        a = oracle.admits(row[:6], 1, 0, device.COM_SHOUT)
+        a = nuts_path.admits(row[:6], 1, 0, device.COM_SHOUT)
         want_admit.append(a)
-        if bool(r.admitted[i]) != a or device.chunks(r, i) != (oracle.chunks(text, row[6]) if a else []):
+        if bool(r.admitted[i]) != a or device.chunks(r, i) != (nuts_path.chunks(text, row[6]) if a else []):
             bad += 1
     return {"listeners": 1000, "admitted": int(r.admitted.sum()), "cpu_admitted": sum(want_admit),
             "sender_admitted": bool(r.admitted[417]), "n_bad": bad, "bytes": int(r.out_offsets[-1]),
@@ -208,20 +184,19 @@ def main() -> int:
     ap.add_argument("--seed", type=int, default=333)
     a = ap.parse_args()
     from nuts333_amd import device
-    oracle = Oracle()
     out = {"device_count": device.device_count()}
     if out["device_count"] < 1:
         print("device_fanout_child: no GPU visible", file=sys.stderr)
         return 2
-    out["vectors"] = vectors(device, oracle)
+    out["vectors"] = vectors(device)
     worst = [("\n" * TEXT_MAX).encode(), ("~RS" * 666).encode()]
-    out["worst"] = compare_batch(device, oracle, [(worst[0], 1), (worst[0], 0), (worst[1], 0), (worst[1], 1)])
+    out["worst"] = compare_batch(device, [(worst[0], 1), (worst[0], 0), (worst[1], 0), (worst[1], 1)])
     r = device.transduce_batch([worst[0], worst[1]], [1, 0])
     out["worst"]["newlines_colour_on"] = [int(r.out_offsets[1]), int(r.write_offsets[1])]
     out["worst"]["codes_colour_off"] = [int(r.out_offsets[2] - r.out_offsets[1]), int(r.write_offsets[2] - r.write_offsets[1])]
-    out["fuzz"] = compare_batch(device, oracle, fuzz_items(a.seed, a.fuzz))
-    out["predicate"] = predicate(device, oracle)
-    out["broadcast"] = broadcast_1000(device, oracle)
+    out["fuzz"] = compare_batch(device, fuzz_items(a.seed, a.fuzz))
+    out["predicate"] = predicate(device)
+    out["broadcast"] = broadcast_1000(device)
     print("DEVICE_FANOUT " + json.dumps(out))
     return 0
 

@@ -11,7 +11,6 @@ JSON -- the 314 transducer vectors, >= 200k seeded fuzz strings (bytes and write
 """
 from __future__ import annotations
 
-import ctypes
 import json
 import re
 import subprocess
@@ -21,7 +20,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from nuts333_amd import device
+from nuts333_amd import device, nuts_path
 
 REPO = Path(__file__).resolve().parent.parent
 FUZZ = 200_000
@@ -114,28 +113,19 @@ def test_chunks_helper_splits_an_item_by_its_write_sizes():
     assert device.chunks(r, 0) == [b"abc", b"de"] and device.chunks(r, 1) == [] and device.chunks(r, 2) == [b"XYZ"]
 
 
-@pytest.fixture(scope="module")
-def path_lib(built):
-    lib = ctypes.CDLL(str(REPO / "oracle" / "_build" / "libnuts_path.so"))
-    lib.np_transduce.restype = ctypes.c_size_t
-    lib.np_transduce.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
-    lib.np_write_count.argtypes = [ctypes.c_char_p, ctypes.c_int]
-    return lib
-
-
-def test_size_and_write_bounds_hold_on_the_cpu_restatement(path_lib):
+def test_size_and_write_bounds_hold_on_the_cpu_restatement():
     """The bounds the device library allocates by: 6*len + 4 bytes and MAX_WRITES writes per item of len < 2000."""
     worst = b"\n" * 1999
-    assert path_lib.np_transduce(worst, 1, None, 0) == 11_998 == device.max_bytes(1999)
-    assert path_lib.np_write_count(worst, 1) == 14 <= device.MAX_WRITES
+    assert len(nuts_path.transduce(worst, 1)) == 11_998 == device.max_bytes(1999)
+    assert nuts_path.write_count(worst, 1) == 14 <= device.MAX_WRITES
     codes = b"~RS" * 666
-    assert path_lib.np_transduce(codes, 0, None, 0) == 0 and path_lib.np_write_count(codes, 0) == 0
+    assert nuts_path.transduce(codes, 0) == b"" and nuts_path.write_count(codes, 0) == 0
     sys.path.insert(0, str(REPO / "tests"))
     import device_fanout_child as child
     for text, _ in child.fuzz_items(7, 3000) + [(b"~" * 1999, 0), (b"/~" * 999 + b"\n", 1), (b"~FR\n" * 499, 1)]:
         for colour in (0, 1):
-            assert path_lib.np_transduce(text, colour, None, 0) <= device.max_bytes(len(text)), text
-            assert path_lib.np_write_count(text, colour) <= device.MAX_WRITES, text
+            assert len(nuts_path.transduce(text, colour)) <= device.max_bytes(len(text)), text
+            assert nuts_path.write_count(text, colour) <= device.MAX_WRITES, text
 
 
 # ------------------------------------------------------------------ GPU tier: one child for the module
@@ -195,8 +185,12 @@ def test_device_1000_listener_broadcast_matches_the_cpu_loop(device_run):
     assert b["timing"]["kernels_us"] > 0 and b["timing"]["end_to_end_us"] >= b["timing"]["kernels_us"]
 
 
-def test_command_numbers_match_the_restatement(path_lib):
-    path_lib.np_command_lookup.argtypes = [ctypes.c_char_p]
-    assert device.NUM_COMMANDS == path_lib.np_command_count()
+def test_command_numbers_match_the_restatement():
+    lib = nuts_path.lib()
+    assert device.NUM_COMMANDS == lib.np_command_count()
     assert (device.COM_SAY, device.COM_SHOUT, device.COM_SEMOTE) == tuple(
-        path_lib.np_command_lookup(w) for w in (b"say", b"shout", b"semote"))
+        lib.np_command_lookup(w) for w in (b"say", b"shout", b"semote"))
+    # the listener record's first six columns are struct np_listener, field for field, in the header and the binding
+    body = re.search(r"struct np_listener \{(.*?)\};", (REPO / "oracle" / "nuts_path.h").read_text(), re.S).group(1)
+    header_fields = re.findall(r"(\w+)\s*[,;]", re.sub(r"/\*.*?\*/", "", body))
+    assert [f for f, _ in nuts_path.Listener._fields_] == header_fields == list(device.LISTENER_FIELDS[:6])

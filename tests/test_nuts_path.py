@@ -19,6 +19,8 @@ from pathlib import Path
 import pytest
 from hypothesis import given, settings, strategies as st
 
+from nuts333_amd import nuts_path
+
 REPO = Path(__file__).resolve().parent.parent
 VECTORS = json.loads((REPO / "tests" / "golden" / "vectors" / "transducer.json").read_text())
 ANSI = re.compile(rb"\x1b\[\d+m")
@@ -26,30 +28,7 @@ ANSI = re.compile(rb"\x1b\[\d+m")
 
 @pytest.fixture(scope="module")
 def lib(built):
-    lib = ctypes.CDLL(str(REPO / "oracle" / "_build" / "libnuts_path.so"))
-    lib.np_transduce.restype = ctypes.c_size_t
-    lib.np_transduce.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
-    lib.np_write_count.argtypes = [ctypes.c_char_p, ctypes.c_int]
-    lib.np_colour_com_strip.restype = ctypes.c_size_t
-    lib.np_colour_com_strip.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
-    lib.np_terminate.argtypes = [ctypes.c_char_p]
-    lib.np_wordfind.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
-    lib.np_remove_first.restype = ctypes.c_char_p
-    lib.np_remove_first.argtypes = [ctypes.c_char_p]
-    lib.np_command_lookup.argtypes = [ctypes.c_char_p]
-    lib.np_command_name.restype = ctypes.c_char_p
-    lib.np_say_verb.restype = ctypes.c_char_p
-    lib.np_say_verb.argtypes = [ctypes.c_char_p]
-    lib.np_contains_swearing.argtypes = [ctypes.c_char_p]
-    lib.np_record.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_char_p]
-    return lib
-
-
-def transduce(lib, s: bytes, colour: int) -> bytes:
-    out = ctypes.create_string_buffer(len(s) * 6 + 64)
-    n = lib.np_transduce(s, colour, out, len(out))
-    assert n <= len(out)
-    return out.raw[:n]
+    return nuts_path.lib()
 
 
 # ---------------------------------------------------------------- transducer vs the reference
@@ -58,38 +37,38 @@ def test_vector_file_is_what_the_generator_promises():
 
 
 @pytest.mark.parametrize("colour,key", [(1, "colour_on"), (0, "colour_off")])
-def test_transducer_matches_reference_vectors(lib, colour, key):
+def test_transducer_matches_reference_vectors(colour, key):
     bad = []
     for v in VECTORS["vectors"]:
         src = ("Bobby says: " + v["line"] + "\n").encode("latin-1")
-        if transduce(lib, src, colour) != v[key].encode("latin-1"):
+        if nuts_path.transduce(src, colour) != v[key].encode("latin-1"):
             bad.append(v["line"])
     assert not bad, f"{len(bad)} of {len(VECTORS['vectors'])} differ, first: {bad[0]!r}"
 
 
-def test_transducer_matches_reference_for_the_speaker_too(lib):
+def test_transducer_matches_reference_for_the_speaker_too():
     for v in VECTORS["vectors"]:
         src = ("You say: " + v["line"] + "\n").encode("latin-1")
-        assert transduce(lib, src, 0) == v["self"].encode("latin-1"), v["line"]
+        assert nuts_path.transduce(src, 0) == v["self"].encode("latin-1"), v["line"]
 
 
-def test_known_answers_from_golden_markup(lib):
+def test_known_answers_from_golden_markup():
     # tests/golden/markup.json, colour-off and colour-on listener
-    assert transduce(lib, b"escaped /~FR stays text, /~ alone, // and / ~\n", 0) == b"escaped ~FR stays text, ~ alone, // and / ~\n\r"
-    assert transduce(lib, b"adjacent ~FR~BGcodes~RS~RS\n", 1) == b"adjacent \x1b[31m\x1b[42mcodes\x1b[0m\x1b[0m\x1b[0m\n\r\x1b[0m"
-    assert transduce(lib, b"~~ double tilde ~~FR and /~~FG\n", 0) == b"~~ double tilde ~ and ~\n\r"
-    assert transduce(lib, b"\xff\xfb\x01", 0) == b"\xff\xfb\x01"          # echo_off bytes pass through
+    assert nuts_path.transduce(b"escaped /~FR stays text, /~ alone, // and / ~\n", 0) == b"escaped ~FR stays text, ~ alone, // and / ~\n\r"
+    assert nuts_path.transduce(b"adjacent ~FR~BGcodes~RS~RS\n", 1) == b"adjacent \x1b[31m\x1b[42mcodes\x1b[0m\x1b[0m\x1b[0m\n\r\x1b[0m"
+    assert nuts_path.transduce(b"~~ double tilde ~~FR and /~~FG\n", 0) == b"~~ double tilde ~ and ~\n\r"
+    assert nuts_path.transduce(b"\xff\xfb\x01", 0) == b"\xff\xfb\x01"          # echo_off bytes pass through
 
 
-def test_write_boundaries(lib):
+def test_write_boundaries():
     """One write per <=1000 staged bytes, plus one for the trailing reset when colour is on
     (nuts333.c:1359-1365): 67-byte broadcast = 1 write (2 with colour)."""
     line = b"Uaaa says: " + b"x" * 54 + b"\n"
-    assert len(transduce(lib, line, 0)) == 67
-    assert lib.np_write_count(line, 0) == 1 and lib.np_write_count(line, 1) == 2
-    assert lib.np_write_count(b"a" * 999 + b"\n", 0) == 2      # newline needs 6 spare bytes: early flush
-    assert lib.np_write_count(b"a" * 2500, 0) == 3
-    assert lib.np_write_count(b"", 0) == 0 and lib.np_write_count(b"", 1) == 1
+    assert len(nuts_path.transduce(line, 0)) == 67
+    assert nuts_path.write_count(line, 0) == 1 and nuts_path.write_count(line, 1) == 2
+    assert nuts_path.write_count(b"a" * 999 + b"\n", 0) == 2      # newline needs 6 spare bytes: early flush
+    assert nuts_path.write_count(b"a" * 2500, 0) == 3
+    assert nuts_path.write_count(b"", 0) == 0 and nuts_path.write_count(b"", 1) == 1
 
 
 def test_stage_keeps_its_fill_level_across_strings(lib):
@@ -98,23 +77,16 @@ def test_stage_keeps_its_fill_level_across_strings(lib):
     tests/test_harness.py::test_more_flushes_where_the_reference_does_for_long_banners: 995 | 995 | 1000 | rest."""
     import scenarios
 
-    class Stage(ctypes.Structure):
-        _fields_ = [("buff", ctypes.c_char * 1008), ("pos", ctypes.c_int)]
-
-    EMIT = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
     chunks = []
-    emit = EMIT(lambda ctx, buf, n: chunks.append(ctypes.string_at(buf, n)))
-    lib.np_stage_init.argtypes = [ctypes.POINTER(Stage)]
-    lib.np_stage_feed.argtypes = [ctypes.POINTER(Stage), ctypes.c_char_p, ctypes.c_int, EMIT, ctypes.c_void_p]
-    lib.np_stage_flush.argtypes = [ctypes.POINTER(Stage), EMIT, ctypes.c_void_p]
-    st_ = Stage()
+    emit = nuts_path.EMIT(lambda ctx, buf, n: chunks.append(ctypes.string_at(buf, n)))
+    st_ = nuts_path.Stage()
     lib.np_stage_init(ctypes.byref(st_))
     for line in scenarios.LONG_MOTD1.splitlines(keepends=True):
         lib.np_stage_feed(ctypes.byref(st_), line.encode(), 0, emit, None)
     lib.np_stage_flush(ctypes.byref(st_), emit, None)
     assert [len(c) for c in chunks][:3] == [995, 995, 1000]
     whole = b"".join(chunks)
-    assert whole == b"".join(transduce(lib, l.encode(), 0) for l in scenarios.LONG_MOTD1.splitlines(keepends=True))
+    assert whole == b"".join(nuts_path.transduce(l.encode(), 0) for l in scenarios.LONG_MOTD1.splitlines(keepends=True))
     assert whole.endswith(b"~FR escaped, ~ZZ unknown, the end of motd1\n\r\n\r")
 
 
@@ -123,16 +95,16 @@ PRINTABLE = st.text(alphabet=st.sampled_from(list("abcXYZ ~/FRSOLBG0123\n")), ma
 
 @settings(max_examples=300, deadline=None)
 @given(PRINTABLE)
-def test_colour_off_equals_colour_on_minus_ansi(lib, s):
+def test_colour_off_equals_colour_on_minus_ansi(s):
     b = s.encode()
-    assert ANSI.sub(b"", transduce(lib, b, 1)) == transduce(lib, b, 0)
+    assert ANSI.sub(b"", nuts_path.transduce(b, 1)) == nuts_path.transduce(b, 0)
 
 
 @settings(max_examples=300, deadline=None)
 @given(PRINTABLE)
-def test_newline_accounting(lib, s):
+def test_newline_accounting(s):
     b = s.encode()
-    out = transduce(lib, b, 0)
+    out = nuts_path.transduce(b, 0)
     assert out.count(b"\n\r") == b.count(b"\n")
     assert len(out) <= len(b) + b.count(b"\n")
 
@@ -194,14 +166,10 @@ def test_say_verb_and_swear_filter(lib):
 
 
 # ---------------------------------------------------------------- fan-out predicate
-class Listener(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int) for n in ("login", "has_room", "same_room", "ignall", "ignshout", "is_sender")]
-
-
 def test_fanout_predicate_truth_table(lib):
     SHOUT, SEMOTE, SAY = 4, 7, 3
     admit = lambda rm_null=0, force=0, com=SAY, **kw: lib.np_fanout_admits(
-        ctypes.byref(Listener(**{"login": 0, "has_room": 1, "same_room": 1, "ignall": 0, "ignshout": 0, "is_sender": 0, **kw})),
+        ctypes.byref(nuts_path.Listener(**{"login": 0, "has_room": 1, "same_room": 1, "ignall": 0, "ignshout": 0, "is_sender": 0, **kw})),
         rm_null, force, com)
     assert admit() == 1
     assert admit(login=3) == 0 and admit(has_room=0) == 0 and admit(is_sender=1) == 0
@@ -225,9 +193,11 @@ def test_record_ring(lib):
 
 # ---------------------------------------------------------------- ABI surface
 def test_library_exports_every_declared_symbol(lib):
-    """oracle/nuts_path.h is the only C header in the repo; the .so must export all of it."""
+    """oracle/nuts_path.h is the only C header in the repo; the .so must export all of it, and the binding must declare
+    a signature for every function of it."""
     header = (REPO / "oracle" / "nuts_path.h").read_text()
     declared = sorted(set(re.findall(r"\b(np_[a-z_]+)\s*\(", header)) - {"np_emit_fn"})
     assert len(declared) >= 15
+    assert sorted(nuts_path.SIGNATURES) == declared
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in nuts_path.h but not exported"
