@@ -7,6 +7,8 @@ independent items, none filtered.  Both return a :class:`Fanout`: the bytes of i
 ``arena[out_offsets[i]:out_offsets[i + 1]]`` and its ``write(2)`` chunk sizes are
 ``write_sizes[write_offsets[i]:write_offsets[i + 1]]`` -- byte-exact and boundary-exact with ``np_write_user_stream``
 of the CPU restatement (oracle/nuts_path.c).  An item that is not admitted has no bytes and no chunks.
+``broadcast_many(broadcasts)`` does K broadcasts, each what ``broadcast()`` takes, in one device call, with a fixed
+number of copies and kernel launches whatever K; its items run broadcast by broadcast (``Fanout.broadcast_offsets``).
 
 Input is validated before the device is touched (``ValueError``).  The library ``_build/libnuts_device.so`` is built by
 ``__graft_entry__.build()`` where ``hipcc`` exists, and on demand here when it is missing or older than its source.
@@ -38,7 +40,10 @@ NUM_COMMANDS = 92
 COM_SAY, COM_SHOUT, COM_SEMOTE = 3, 4, 7
 #: the kernels of fanout.hip, as rocprofv3 names them (the scans are rocPRIM's)
 KERNELS = ("nuts_fanout_measure_broadcast", "nuts_fanout_emit_broadcast",
-           "nuts_fanout_measure_batch", "nuts_fanout_emit_batch")
+           "nuts_fanout_measure_batch", "nuts_fanout_emit_batch",
+           "nuts_fanout_measure_many", "nuts_fanout_emit_many")
+#: broadcast_many() refuses a call whose arena bound, the sum over its broadcasts of N * max_bytes(len), exceeds this
+MANY_ARENA_CAP = 2 << 30
 
 
 def max_bytes(text_len: int) -> int:
@@ -54,9 +59,20 @@ class Fanout:
     write_offsets: np.ndarray     # int64 [M + 1]
     write_sizes: np.ndarray       # int32 [write_offsets[-1]]
     timing: dict = field(default_factory=dict)   # kernels_us (device events), end_to_end_us (host clock, H2D..D2H+sync)
+    broadcast_offsets: np.ndarray | None = None  # broadcast_many: int64 [K + 1], broadcast k's items are [bo[k], bo[k+1])
 
     def output(self, i: int) -> bytes:
         return self.arena[self.out_offsets[i]:self.out_offsets[i + 1]].tobytes()
+
+    def item(self, k: int, j: int) -> int:
+        """The flat index of listener ``j`` of broadcast ``k`` in a :func:`broadcast_many` result."""
+        if self.broadcast_offsets is None:
+            raise ValueError("not a broadcast_many result: it has no broadcast_offsets")
+        bo = self.broadcast_offsets
+        if not 0 <= k < len(bo) - 1 or not 0 <= j < bo[k + 1] - bo[k]:
+            raise IndexError(f"no item ({k}, {j}): {len(bo) - 1} broadcasts, "
+                             f"broadcast {k} has {int(bo[k + 1] - bo[k]) if 0 <= k < len(bo) - 1 else 0} listeners")
+        return int(bo[k] + j)
 
 
 def chunks(result: Fanout, i: int) -> list[bytes]:
@@ -140,6 +156,41 @@ def _prepare_broadcast(text, listeners, rm_is_null, force_listen, com_num):
     return text, rec, flags[0], flags[1], int(com_num)
 
 
+def _prepare_many(broadcasts):
+    """Each (text, listeners, rm_is_null, force_listen, com_num) through _prepare_broadcast, packed for
+    nd_fanout_many: texts, text offsets and lengths, flags (bit 0 rm_is_null, bit 1 force_listen), commands, item
+    offsets [K + 1] and the listener records, one byte each."""
+    if isinstance(broadcasts, (str, bytes, bytearray, np.ndarray)) or not hasattr(broadcasts, "__len__"):
+        raise ValueError(f"broadcasts must be a sequence of tuples, not {type(broadcasts).__name__}")
+    if len(broadcasts) == 0:
+        raise ValueError("empty call: no broadcasts")
+    texts, recs, flags, coms = [], [], [], []
+    for k, b in enumerate(broadcasts):
+        if not isinstance(b, tuple) or len(b) != 5:
+            raise ValueError(f"broadcast {k}: expected a (text, listeners, rm_is_null, force_listen, com_num) tuple, "
+                             f"got {type(b).__name__}{f' of {len(b)}' if isinstance(b, tuple) else ''}")
+        try:
+            text, rec, rm_is_null, force_listen, com_num = _prepare_broadcast(*b)
+        except ValueError as e:
+            raise ValueError(f"broadcast {k}: {e}") from None
+        texts.append(text)
+        recs.append(rec)
+        flags.append(rm_is_null | force_listen << 1)
+        coms.append(com_num)
+    lens = np.fromiter((len(t) for t in texts), dtype=np.int64, count=len(texts))
+    ns = np.fromiter((len(r) for r in recs), dtype=np.int64, count=len(recs))
+    bound = int((ns * (6 * lens + 4)).sum())
+    if bound > MANY_ARENA_CAP:
+        raise ValueError(f"call too large: its arena bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
+                         f"(MANY_ARENA_CAP): split it")
+    item_off = np.zeros(len(texts) + 1, dtype=np.int32)
+    np.cumsum(ns, out=item_off[1:])
+    text_off = np.zeros(len(texts), dtype=np.int32)
+    np.cumsum(lens[:-1], out=text_off[1:])
+    return (b"".join(texts), text_off, lens.astype(np.int32), np.array(flags, dtype=np.uint8),
+            np.array(coms, dtype=np.int32), item_off, np.concatenate(recs))
+
+
 # ------------------------------------------------------------------ the library
 class _Timing(ctypes.Structure):
     _fields_ = [("kernels_us", ctypes.c_double), ("end_to_end_us", ctypes.c_double)]
@@ -177,6 +228,9 @@ def _load():
         lib.nd_fanout.argtypes = [ctypes.c_int, P, ctypes.c_int64, P, P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                   ctypes.c_int, P, P, P, ctypes.POINTER(_Timing)]
         lib.nd_fanout.restype = ctypes.c_int
+        lib.nd_fanout_many.argtypes = [ctypes.c_int, P, ctypes.c_int64, P, P, P, P, P, P, P, P, P,
+                                       ctypes.POINTER(_Timing)]
+        lib.nd_fanout_many.restype = ctypes.c_int
         lib.nd_arena.restype = P
         lib.nd_write_sizes.restype = P
         _LIB = lib
@@ -208,6 +262,11 @@ def _run(broadcast: bool, text: bytes, offs, lens, rec, rm_is_null=0, force_list
                        ctypes.byref(t))
     if rc != 0:
         raise RuntimeError(f"device fan-out failed: {lib.nd_last_error().decode(errors='replace')}")
+    return _result(lib, admitted, out_off, w_off, t)
+
+
+def _result(lib, admitted, out_off, w_off, t: _Timing) -> Fanout:
+    """The Fanout of the last call: the arena and the chunk sizes copied out of the library's pinned buffers."""
     nbytes, nwrites = int(out_off[-1]), int(w_off[-1])
     arena = np.ctypeslib.as_array(ctypes.cast(lib.nd_arena(), ctypes.POINTER(ctypes.c_uint8)), (max(nbytes, 1),))
     wsz = np.ctypeslib.as_array(ctypes.cast(lib.nd_write_sizes(), ctypes.POINTER(ctypes.c_int32)), (max(nwrites, 1),))
@@ -227,3 +286,25 @@ def broadcast(text, listeners, rm_is_null, force_listen, com_num) -> Fanout:
     text, rec, rm_is_null, force_listen, com_num = _prepare_broadcast(text, listeners, rm_is_null, force_listen, com_num)
     lens = np.array([len(text)], dtype=np.int32)
     return _run(True, text, None, lens, rec, rm_is_null, force_listen, com_num)
+
+
+def broadcast_many(broadcasts) -> Fanout:
+    """K broadcasts in one device call: a sequence of ``(text, listeners, rm_is_null, force_listen, com_num)`` tuples,
+    each what :func:`broadcast` takes and checked by the same rules.  Items are ordered broadcast by broadcast, listeners
+    in table order; ``broadcast_offsets[k]:broadcast_offsets[k + 1]`` are broadcast k's (``Fanout.item(k, j)``).  A call
+    whose arena bound exceeds MANY_ARENA_CAP is refused (``ValueError``) before the device is touched."""
+    text, text_off, lens, flags, coms, item_off, rec = _prepare_many(broadcasts)
+    lib = _load()
+    m = len(rec)
+    admitted = np.zeros(m, dtype=np.uint8)
+    out_off = np.zeros(m + 1, dtype=np.int64)
+    w_off = np.zeros(m + 1, dtype=np.int32)
+    tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
+    t = _Timing()
+    rc = lib.nd_fanout_many(len(lens), _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(flags), _ptr(coms),
+                            _ptr(item_off), _ptr(rec), _ptr(admitted), _ptr(out_off), _ptr(w_off), ctypes.byref(t))
+    if rc != 0:
+        raise RuntimeError(f"device fan-out failed: {lib.nd_last_error().decode(errors='replace')}")
+    r = _result(lib, admitted, out_off, w_off, t)
+    r.broadcast_offsets = item_off.astype(np.int64)
+    return r

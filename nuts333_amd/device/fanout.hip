@@ -14,7 +14,8 @@
 //           entries (the last one zero), so that the last offsets are the totals
 //   pass 2  nuts_fanout_emit_{batch,broadcast}: bytes into the arena, chunk sizes into write_sizes
 // In broadcast mode every item reads the same text, which each block stages in LDS once.  All four
-// kernels take one argument struct (Args), filled by the host.
+// kernels take one argument struct (Args), filled by the host.  nuts_fanout_{measure,emit}_many do K broadcasts in
+// one call (their section below).
 //
 // Hard bounds per item of a text of len < 2000 bytes: 6*len + 4 output bytes (a '\n' with colour
 // on is the costliest input byte, plus the trailing reset) and 16 writes.  The host sizes its buffers
@@ -31,6 +32,7 @@
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <type_traits>
 
 namespace {
@@ -232,6 +234,168 @@ __device__ void emit(const Args& a)
     transduce(s, len, (a.rec[i] & kColour) != 0, k);
 }
 
+// ------------------------------------------------------------------ many broadcasts per call
+//
+// K broadcasts, each with its own text, flags, command and listener table; item = (broadcast k, listener j), items
+// ordered broadcast by broadcast.  One block per (broadcast, 256-listener tile).  A listener's output depends only on
+// its colour bit (nuts333.c:1321,1344), so a block transduces its text twice -- colour off on wave 0, colour on on
+// wave 1, concurrently -- and every item takes its variant's bytes and writes, or none if it is not admitted.
+//   measure  nuts_fanout_measure_many: both variants counted; admit flag, bytes, writes per item
+//   scan     as above, over m + 1 entries
+//   emit     nuts_fanout_emit_many: both variants transduced into LDS; the tile's items copied out of them with
+//            aligned 4-byte stores, kGroup lanes per item, and their chunk sizes likewise
+constexpr int kVarCap = 6 * (kTextSize - 1) + 4;   // the hard bound of the longest text: 11998 bytes
+constexpr int kGroup = 16;                          // lanes per item in emit (>= kMaxWrites)
+
+struct ManyArgs {
+    const uint8_t* text;         // the K texts, packed
+    const int32_t* text_off;     // [k]
+    const int32_t* text_len;     // [k]
+    const uint8_t* flags;        // [k] bit 0 rm_is_null, bit 1 force_listen
+    const int32_t* com_num;      // [k]
+    const int32_t* item_off;     // [k + 1] broadcast b owns items item_off[b] .. item_off[b + 1] - 1
+    const int32_t* tile_off;     // [k + 1] and blocks tile_off[b] .. tile_off[b + 1] - 1
+    const uint8_t* rec;          // [m] listener records
+    int k, m;
+    int* violations;             // items past the hard bounds (zeroed by the host's upload)
+    uint8_t* admitted;           // [m]
+    int64_t* out_off;            // [m + 1]
+    int32_t* w_off;              // [m + 1]
+    int64_t* nbytes;             // [m + 1]
+    int32_t* nwrites;            // [m + 1]
+    uint8_t* arena;
+    int64_t arena_cap;
+    int32_t* wsz;
+    int64_t wsz_cap;
+};
+
+struct Tile {
+    int b, lo, hi;               // broadcast, first item, one past the last item
+};
+
+// This block's broadcast: the b with tile_off[b] <= blockIdx.x < tile_off[b + 1] (every broadcast has >= 1 tile).
+__device__ __forceinline__ Tile find_tile(const ManyArgs& a)
+{
+    const int blk = (int)blockIdx.x;
+    int lo = 0, hi = a.k;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (a.tile_off[mid] <= blk) lo = mid;
+        else hi = mid;
+    }
+    const int first = a.item_off[lo] + (blk - a.tile_off[lo]) * kBlock;
+    const int end = a.item_off[lo + 1];
+    return {lo, first, first + kBlock < end ? first + kBlock : end};
+}
+
+// Stage broadcast b's text in LDS, then transduce it with colour off (lane 0 of wave 0) and on (lane 0 of wave 1).
+// EMIT: the bytes go to var[c * kVarCap ..] and the chunk sizes to vwsz[c * kMaxWrites ..], clamped to the hard bounds.
+// vn / vw get the full counts, so a bound violation stays visible.  Every thread of the block calls this.
+template <bool EMIT>
+__device__ __forceinline__ void stage_variants(const ManyArgs& a, int b, uint8_t* text, uint8_t* var, int32_t* vwsz,
+                                               int64_t* vn, int* vw)
+{
+    const int len = a.text_len[b];
+    const uint8_t* src = a.text + a.text_off[b];
+    for (int j = threadIdx.x; j < len; j += blockDim.x) text[j] = src[j];
+    __syncthreads();
+    if (threadIdx.x == 0 || threadIdx.x == 64) {
+        const int c = threadIdx.x >> 6;
+        Sink<EMIT> k{EMIT ? var + c * kVarCap : nullptr, EMIT ? vwsz + c * kMaxWrites : nullptr, 6 * (int64_t)len + 4,
+                     kMaxWrites};
+        transduce(text, len, c != 0, k);
+        vn[c] = k.n;
+        vw[c] = k.writes;
+    }
+    __syncthreads();
+}
+
+__device__ void measure_many(const ManyArgs& a)
+{
+    __shared__ uint8_t text[kTextSize];
+    __shared__ int64_t vn[2];
+    __shared__ int vw[2];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {      // the scans' extra entry
+        a.nbytes[a.m] = 0;
+        a.nwrites[a.m] = 0;
+    }
+    const Tile t = find_tile(a);
+    stage_variants<false>(a, t.b, text, nullptr, nullptr, vn, vw);
+    const int i = t.lo + (int)threadIdx.x;
+    if (i >= t.hi) return;
+    const uint8_t l = a.rec[i];
+    const int fl = a.flags[t.b];
+    const bool in = admits(l, fl & 1, (fl >> 1) & 1, a.com_num[t.b]);
+    const int c = (l & kColour) ? 1 : 0;
+    const int64_t nb = in ? vn[c] : 0;
+    const int nw = in ? vw[c] : 0;
+    if (nb > 6 * (int64_t)a.text_len[t.b] + 4 || nw > kMaxWrites) atomicAdd(a.violations, 1);
+    a.admitted[i] = in;
+    a.nbytes[i] = nb;
+    a.nwrites[i] = nw;
+}
+
+__device__ void emit_many(const ManyArgs& a)
+{
+    __shared__ uint8_t text[kTextSize];
+    __shared__ uint8_t var[2 * kVarCap];
+    __shared__ int32_t vwsz[2 * kMaxWrites];
+    __shared__ int64_t vn[2];
+    __shared__ int vw[2];
+    __shared__ int64_t s_off[kBlock], s_n[kBlock];   // per item of the tile: arena slot, bytes to write there
+    __shared__ int32_t s_woff[kBlock], s_nw[kBlock]; // first chunk-size entry, chunk sizes to write
+    __shared__ uint8_t s_c[kBlock];                  // variant
+    const Tile t = find_tile(a);
+    const int len = a.text_len[t.b];
+    {   // this item's metadata, loaded before the transduce so that the loads overlap it; clamped so that nothing is
+        // written past the arena, the chunk array or the LDS variant, even if measure broke the bounds
+        const int i = t.lo + (int)threadIdx.x;
+        if (i < t.hi) {
+            const bool in = a.admitted[i] != 0;
+            const int64_t off = a.out_off[i], woff = a.w_off[i];
+            const int64_t room = a.arena_cap - off, wroom = a.wsz_cap - woff;
+            int64_t n = in ? a.nbytes[i] : 0;
+            n = n < room ? n : room;
+            n = n < 6 * (int64_t)len + 4 ? n : 6 * (int64_t)len + 4;
+            int64_t nw = in ? a.nwrites[i] : 0;
+            nw = nw < wroom ? nw : wroom;
+            nw = nw < kMaxWrites ? nw : kMaxWrites;
+            s_off[threadIdx.x] = off;
+            s_n[threadIdx.x] = n > 0 ? n : 0;
+            s_woff[threadIdx.x] = (int32_t)woff;
+            s_nw[threadIdx.x] = nw > 0 ? (int32_t)nw : 0;
+            s_c[threadIdx.x] = (a.rec[i] & kColour) ? 1 : 0;
+        }
+    }
+    stage_variants<true>(a, t.b, text, var, vwsz, vn, vw);   // its barriers publish the metadata too
+    const int g = (int)threadIdx.x / kGroup, lane = (int)threadIdx.x % kGroup;
+    for (int j = g; j < t.hi - t.lo; j += kBlock / kGroup) {
+        const int c = s_c[j];
+        const int64_t n0 = s_n[j], vmax = vn[c] < kVarCap ? vn[c] : kVarCap;
+        const int64_t n = n0 < vmax ? n0 : vmax;
+        const uint8_t* src = var + c * kVarCap;
+        uint8_t* dst = a.arena + s_off[j];
+        // w: item-relative offset of a 4-byte word of the arena (the arena is 256-byte aligned), from the word
+        // holding the item's first byte; whole words in one store, the item's partial edge words byte by byte
+        const int head = (int)(s_off[j] & 3);
+        for (int64_t w = 4 * lane - head; w < n; w += 4 * kGroup) {
+            if (w >= 0 && w + 4 <= n) {
+                const uint32_t v = (uint32_t)src[w] | (uint32_t)src[w + 1] << 8 | (uint32_t)src[w + 2] << 16 |
+                                   (uint32_t)src[w + 3] << 24;
+                *reinterpret_cast<uint32_t*>(dst + w) = v;
+            } else {
+                for (int q = 0; q < 4; q++)
+                    if (w + q >= 0 && w + q < n) dst[w + q] = src[w + q];
+            }
+        }
+        const int nw = s_nw[j] < vw[c] ? s_nw[j] : vw[c];
+        if (lane < nw) a.wsz[s_woff[j] + lane] = vwsz[c * kMaxWrites + lane];
+    }
+}
+
+static_assert(kGroup >= kMaxWrites, "emit_many writes an item's chunk sizes with one lane each");
+static_assert(kBlock % kGroup == 0 && kBlock >= 128, "emit_many: whole lane groups; variants on waves 0 and 1");
+
 }  // namespace
 
 // Stable, unmangled kernel names (they are what rocprofv3 reports).
@@ -239,6 +403,8 @@ extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_measure_batch(A
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_measure_broadcast(Args a) { measure<true>(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_emit_batch(Args a) { emit<false>(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_emit_broadcast(Args a) { emit<true>(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_measure_many(ManyArgs a) { measure_many(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_emit_many(ManyArgs a) { emit_many(a); }
 
 // ------------------------------------------------------------------------------------------ host library
 
@@ -345,6 +511,46 @@ double now_ns()
                std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// nd_fanout_many's pinned host buffers (it shares g.d_block and the result buffers with nd_fanout): the inputs packed
+// exactly as they lie at the start of the device block, and the first results as they lie after them.
+struct ManyHost {
+    uint8_t* stage = nullptr;
+    uint8_t* res = nullptr;
+    size_t cap_stage = 0, cap_res = 0;
+};
+ManyHost gm;
+
+// As layout(), for ManyArgs (a.k, a.m and the capacities set).  The inputs come first and end with violations, so
+// one upload fills them all and zeroes violations; violations, admitted, out_off and w_off follow each other, so one
+// download fetches them.  layout_many(0, ...) gives every array's offset in the block.
+size_t layout_many(uintptr_t base, size_t text_bytes, size_t scan_bytes, ManyArgs& a, uint8_t** scan)
+{
+    size_t at = 0;
+    auto take = [&](auto*& p, size_t count) {
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + at);
+        at += (count * sizeof(*p) + 255) & ~(size_t)255;
+    };
+    const size_t k = (size_t)a.k, m = (size_t)a.m;
+    take(a.text, text_bytes);
+    take(a.text_off, k);
+    take(a.text_len, k);
+    take(a.flags, k);
+    take(a.com_num, k);
+    take(a.item_off, k + 1);
+    take(a.tile_off, k + 1);
+    take(a.rec, m);
+    take(a.violations, 1);
+    take(a.admitted, m);
+    take(a.out_off, m + 1);
+    take(a.w_off, m + 1);
+    take(a.nbytes, m + 1);
+    take(a.nwrites, m + 1);
+    take(a.arena, (size_t)a.arena_cap);
+    take(a.wsz, (size_t)a.wsz_cap);
+    take(*scan, scan_bytes);
+    return at;
+}
+
 }  // namespace
 
 extern "C" {
@@ -447,5 +653,107 @@ int nd_fanout(int broadcast, const uint8_t* text, int64_t text_bytes, const int3
 
 const uint8_t* nd_arena(void) { return g.h_arena; }
 const int32_t* nd_write_sizes(void) { return g.h_wsz; }
+
+// K broadcasts in one call.  Broadcast b: the text text[text_off[b] .. text_off[b] + text_len[b]), flags[b] (bit 0
+// rm_is_null, bit 1 force_listen), com_num[b], and the listener records rec[item_off[b] .. item_off[b + 1]), at least
+// one (item_off[0] = 0, m = item_off[k]).  Outputs as nd_fanout's, over the m items: admitted[m], out_off[m+1],
+// w_off[m+1]; the arena and the chunk sizes through nd_arena / nd_write_sizes until the next call.  Whatever k and m:
+// one upload, four kernels (two of them the scans), three downloads, two synchronises.  The arena holds the hard
+// bound sum of N_b * (6 * text_len[b] + 4); the caller keeps it under its cap and has validated the input as for
+// nd_fanout.  Returns 0, or -1 with nd_last_error() set.
+int nd_fanout_many(int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off, const int32_t* text_len,
+                   const uint8_t* flags, const int32_t* com_num, const int32_t* item_off, const uint8_t* rec,
+                   uint8_t* admitted, int64_t* out_off, int32_t* w_off, nd_timing* timing)
+{
+    if (ensure_ready()) return -1;
+    if (k < 1 || item_off[0] != 0) {
+        snprintf(g_err, sizeof(g_err), "empty call, or item offsets that do not start at 0");
+        return -1;
+    }
+    for (int b = 0; b < k; b++)
+        if (item_off[b + 1] <= item_off[b]) {
+            snprintf(g_err, sizeof(g_err), "broadcast %d has no listeners", b);
+            return -1;
+        }
+    const double t0 = now_ns();
+    hipStream_t st = g.stream;
+    ManyArgs a{};
+    a.k = k;
+    a.m = item_off[k];
+    for (int b = 0; b < k; b++) a.arena_cap += (int64_t)(item_off[b + 1] - item_off[b]) * (6 * (int64_t)text_len[b] + 4);
+    a.wsz_cap = (int64_t)a.m * kMaxWrites;
+    const int m = a.m;
+    size_t scan1 = 0, scan2 = 0;     // both scans run over m + 1 entries
+    ND_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan1, a.nbytes, a.out_off, m + 1, st));
+    ND_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan2, a.nwrites, a.w_off, m + 1, st));
+    const size_t scan_bytes = std::max(scan1, scan2);
+    uint8_t* scan = nullptr;
+    ManyArgs o = a;                  // offsets of every array in the block
+    const size_t need = layout_many(0, (size_t)text_bytes, scan_bytes, o, &scan);
+    if (grow_dev(&g.d_block, &g.cap_block, need, "device buffers")) return -1;
+    layout_many((uintptr_t)g.d_block, (size_t)text_bytes, scan_bytes, a, &scan);
+    const size_t in_bytes = (uintptr_t)o.violations + sizeof(int);
+    const size_t res_at = (uintptr_t)o.violations, res_bytes = (uintptr_t)o.nbytes - res_at;
+    if (grow_host(&gm.stage, &gm.cap_stage, in_bytes, "pinned staging")) return -1;
+    if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
+
+    // pack the inputs as they lie in the block; the block offsets go with them
+    uint8_t* h = gm.stage;
+    auto put = [&](const void* at, const void* src, size_t bytes) {
+        if (bytes) memcpy(h + (uintptr_t)at, src, bytes);
+    };
+    put(o.text, text, (size_t)text_bytes);
+    put(o.text_off, text_off, (size_t)k * sizeof(int32_t));
+    put(o.text_len, text_len, (size_t)k * sizeof(int32_t));
+    put(o.flags, flags, (size_t)k);
+    put(o.com_num, com_num, (size_t)k * sizeof(int32_t));
+    put(o.item_off, item_off, ((size_t)k + 1) * sizeof(int32_t));
+    int32_t* tiles = reinterpret_cast<int32_t*>(h + (uintptr_t)o.tile_off);
+    tiles[0] = 0;
+    for (int b = 0; b < k; b++) tiles[b + 1] = tiles[b] + (item_off[b + 1] - item_off[b] + kBlock - 1) / kBlock;
+    put(o.rec, rec, (size_t)m);
+    *reinterpret_cast<int*>(h + (uintptr_t)o.violations) = 0;
+    ND_CHECK(hipMemcpyAsync(g.d_block, h, in_bytes, hipMemcpyHostToDevice, st));
+
+    const dim3 grid((unsigned)tiles[k]), block(kBlock);
+    ND_CHECK(hipEventRecord(g.ev0, st));
+    hipLaunchKernelGGL(nuts_fanout_measure_many, grid, block, 0, st, a);
+    ND_CHECK(hipGetLastError());
+    size_t bytes = scan_bytes;
+    ND_CHECK(hipcub::DeviceScan::ExclusiveSum(scan, bytes, a.nbytes, a.out_off, m + 1, st));
+    bytes = scan_bytes;
+    ND_CHECK(hipcub::DeviceScan::ExclusiveSum(scan, bytes, a.nwrites, a.w_off, m + 1, st));
+    hipLaunchKernelGGL(nuts_fanout_emit_many, grid, block, 0, st, a);
+    ND_CHECK(hipGetLastError());
+    ND_CHECK(hipEventRecord(g.ev1, st));
+
+    // violations, admitted and the offsets in one download: they say how much of the arena to fetch
+    ND_CHECK(hipMemcpyAsync(gm.res, g.d_block + res_at, res_bytes, hipMemcpyDeviceToHost, st));
+    ND_CHECK(hipStreamSynchronize(st));
+    auto res = [&](const void* at) { return gm.res + ((uintptr_t)at - res_at); };
+    const int violations = *reinterpret_cast<const int*>(res(o.violations));
+    if (violations) {
+        snprintf(g_err, sizeof(g_err), "%d item(s) exceeded the hard output bounds (6*len+4 bytes, %d writes)",
+                 violations, kMaxWrites);
+        return -1;
+    }
+    memcpy(admitted, res(o.admitted), (size_t)m);
+    memcpy(out_off, res(o.out_off), ((size_t)m + 1) * sizeof(int64_t));
+    memcpy(w_off, res(o.w_off), ((size_t)m + 1) * sizeof(int32_t));
+    if (grow_host(&g.h_arena, &g.cap_host_arena, (size_t)out_off[m] + 1, "pinned arena")) return -1;
+    if (grow_host(&g.h_wsz, &g.cap_host_writes, (size_t)w_off[m] + 1, "pinned write sizes")) return -1;
+    ND_CHECK(hipMemcpyAsync(g.h_arena, a.arena, (size_t)out_off[m], hipMemcpyDeviceToHost, st));
+    ND_CHECK(hipMemcpyAsync(g.h_wsz, a.wsz, (size_t)w_off[m] * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    ND_CHECK(hipStreamSynchronize(st));
+    const double t1 = now_ns();
+
+    float ms = 0.f;
+    ND_CHECK(hipEventElapsedTime(&ms, g.ev0, g.ev1));
+    if (timing) {
+        timing->kernels_us = (double)ms * 1e3;
+        timing->end_to_end_us = (t1 - t0) * 1e-3;
+    }
+    return 0;
+}
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 """What one broadcast's user-space stage costs on the MI355X, done by a kernel that does the work.
 
-    python -m nuts333_amd.devpath [--reps R] [--warmup W] [--pathbench-iterations I]   -> one JSON line
+    python -m nuts333_amd.devpath [--reps R] [--warmup W] [--pathbench-iterations I] [--per-call K[,K...]]
+                                                                                       -> one JSON line
 
 For N in {10, 100, 1000} listeners, the two texts oracle/pathbench.c times (``say``; ``shout`` carrying ``~OL``/``~RS``)
 and colour all-off / all-on / half, one ``nuts333_amd.device.broadcast`` per repetition (listener 0 is the sender, the
@@ -14,6 +15,12 @@ rest are admitted: the bench headline's shape).  Per case:
 
 Median and spread (p10, p90) over the repetitions, after a warm-up.  With no GPU visible the command exits 2; it has
 no CPU fall-back.
+
+``--per-call K[,K...]`` adds ``per_call``: the same N x text x colour cases as K broadcasts per call
+(``nuts333_amd.device.broadcast_many``), the K texts differing in their line number (000000, 000001, ...).  Per case:
+``kernels_us`` and ``end_to_end_us`` per call and per broadcast, ``python_us`` (the host clock around the whole
+``broadcast_many`` call: packing the K tables, the library call, copying the results out of pinned memory), and
+``cpu_derived_us`` per broadcast with the ratios.  Bytes are checked against the CPU restatement once per case.
 """
 from __future__ import annotations
 
@@ -72,11 +79,66 @@ def cpu_derived_us(pb: dict, text: str, colour: str, n: int) -> float:
     return ((n - 1) * per + n * pb["fanout_predicate_ns"] + pb["format_line_once_ns"]) / 1e3
 
 
+def per_call_counts(s: str) -> list[int]:
+    """``--per-call``: broadcasts per call, comma-separated positive integers."""
+    try:
+        ks = [int(x) for x in s.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected positive integers separated by commas, got {s!r}") from None
+    if any(k < 1 for k in ks):
+        raise argparse.ArgumentTypeError(f"broadcasts per call must be >= 1, got {s!r}")
+    return ks
+
+
+def line_texts(text: str, k: int) -> list[bytes]:
+    """K distinct texts of one length: TEXTS[text] with line numbers 000000 .. k - 1."""
+    if k > 1_000_000:
+        raise ValueError("six-digit line numbers: at most 1,000,000 distinct texts")
+    return [TEXTS[text].replace(b"000123", b"%06d" % i) for i in range(k)]
+
+
+def per_call_case(n: int, text: str, colour: str, k: int, reps: int, warmup: int, pb: dict) -> dict:
+    """K broadcasts of ``text`` (distinct line numbers) to listeners(n, colour) per broadcast_many call."""
+    table = listeners(n, colour)
+    texts = line_texts(text, k)
+    calls = [(t, table, 0, 0, COM[text]) for t in texts]
+    run = lambda: device.broadcast_many(calls)
+    first = run()
+    colour_of = table[1:, device.LISTENER_FIELDS.index("colour")].tolist()
+    want = b"".join(b"".join(v[c] for c in colour_of)
+                    for v in ({0: nuts_path.transduce(t, 0), 1: nuts_path.transduce(t, 1)} for t in texts))
+    if first.arena.tobytes() != want or int(first.admitted.sum()) != k * (n - 1):
+        raise SystemExit(f"devpath: per call {k}, {n}/{text}/{colour}: device produced {int(first.out_offsets[-1])} "
+                         f"bytes, the CPU restatement {len(want)}")
+    for _ in range(warmup):
+        run()
+    kern, e2e, py = [], [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        r = run()
+        py.append((time.perf_counter() - t0) * 1e6)
+        kern.append(r.timing["kernels_us"])
+        e2e.append(r.timing["end_to_end_us"])
+    cpu = cpu_derived_us(pb, text, colour, n)
+    ks, es, ps = _stats(kern), _stats(e2e), _stats(py)
+    per = lambda s: {q: round(v / k, 3) for q, v in s.items()}
+    return {"n": n, "text": text, "colour": colour, "k": k, "recipients": k * (n - 1),
+            "bytes_out": int(first.out_offsets[-1]), "writes": int(first.write_offsets[-1]),
+            "kernels_us": ks, "end_to_end_us": es, "python_us": ps,
+            "kernels_us_per_broadcast": per(ks), "end_to_end_us_per_broadcast": per(es),
+            "python_us_per_broadcast": per(ps),
+            "cpu_derived_us": round(cpu, 3),
+            "end_to_end_over_cpu": round(es["median"] / k / cpu, 2),
+            "python_over_cpu": round(ps["median"] / k / cpu, 2)}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=2000, help="timed broadcasts per case (default 2000)")
     ap.add_argument("--warmup", type=int, default=200, help="untimed broadcasts per case first (default 200)")
     ap.add_argument("--pathbench-iterations", type=int, default=2_000_000)
+    ap.add_argument("--per-call", type=per_call_counts, default=None, metavar="K[,K...]",
+                    help="also time K broadcasts per broadcast_many call, for each K (the per_call cases)")
     a = ap.parse_args(argv)
     if a.reps < 1 or a.warmup < 0:
         ap.error("--reps must be >= 1 and --warmup >= 0")
@@ -120,6 +182,16 @@ def main(argv=None) -> int:
                               "kernels_us": _stats(k), "end_to_end_us": ke,
                               "cpu_derived_us": round(cpu, 3),
                               "end_to_end_over_cpu": round(ke["median"] / cpu, 1)})
+    per_call = {}
+    if a.per_call:
+        per_call = {
+            "per_call_kernels": ["nuts_fanout_measure_many", "rocprim device scan x2", "nuts_fanout_emit_many"],
+            "per_call_end_to_end_covers": "packing the K inputs into pinned memory, one H2D, kernels, three D2H, "
+                                          "two synchronises (python_us adds building the K tables and the copies "
+                                          "out of pinned memory)",
+            "per_call": [per_call_case(n, text, colour, k, a.reps, a.warmup, pb)
+                         for n in SIZES for text in TEXTS for colour in COLOURS for k in a.per_call],
+        }
     out = {
         "what": "user-space stage of one broadcast (admit predicate + transducer), device vs CPU",
         "device": "gfx950",
@@ -129,6 +201,7 @@ def main(argv=None) -> int:
         "cpu_derived_from": {"pathbench": {k: v for k, v in pb.items() if k not in ("sink", "admitted")},
                              "formula": "(N-1) x transduce + N x fanout_predicate + format_line_once (derived, not timed)"},
         "cases": cases,
+        **per_call,
         "wall_s": round(time.perf_counter() - t_start, 1),
     }
     print(json.dumps(out))
