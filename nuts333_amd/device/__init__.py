@@ -9,6 +9,9 @@ independent items, none filtered.  Both return a :class:`Fanout`: the bytes of i
 of the CPU restatement (oracle/nuts_path.c).  An item that is not admitted has no bytes and no chunks.
 ``broadcast_many(broadcasts)`` does K broadcasts, each what ``broadcast()`` takes, in one device call, with a fixed
 number of copies and kernel launches whatever K; its items run broadcast by broadcast (``Fanout.broadcast_offsets``).
+:class:`Roster` keeps the talker's listener state (room and flags per slot) on the device between calls; its
+``broadcast_many`` takes K ``(text, rm, sender, force_listen, com_num)`` tuples, addressed as ``write_room_except``
+addresses them, and the device builds every listener's record, so a call uploads the table only after an update.
 
 Input is validated before the device is touched (``ValueError``).  The library ``_build/libnuts_device.so`` is built by
 ``__graft_entry__.build()`` where ``hipcc`` exists, and on demand here when it is missing or older than its source.
@@ -41,9 +44,14 @@ COM_SAY, COM_SHOUT, COM_SEMOTE = 3, 4, 7
 #: the kernels of fanout.hip, as rocprofv3 names them (the scans are rocPRIM's)
 KERNELS = ("nuts_fanout_measure_broadcast", "nuts_fanout_emit_broadcast",
            "nuts_fanout_measure_batch", "nuts_fanout_emit_batch",
-           "nuts_fanout_measure_many", "nuts_fanout_emit_many")
+           "nuts_fanout_measure_many", "nuts_fanout_emit_many",
+           "nuts_roster_measure", "nuts_roster_emit")
 #: broadcast_many() refuses a call whose arena bound, the sum over its broadcasts of N * max_bytes(len), exceeds this
 MANY_ARENA_CAP = 2 << 30
+#: the most slots a Roster holds
+MAX_CAPACITY = 65536
+#: a room id is None (no room) or an int in [0, ROOM_LIMIT)
+ROOM_LIMIT = 2**31 - 1
 
 
 def max_bytes(text_len: int) -> int:
@@ -151,9 +159,13 @@ def _prepare_broadcast(text, listeners, rm_is_null, force_listen, com_num):
     text = _as_text(text)
     rec = _listener_records(listeners)
     flags = _flag("rm_is_null", rm_is_null), _flag("force_listen", force_listen)
-    if not isinstance(com_num, (int, np.integer)) or isinstance(com_num, bool) or not 0 <= int(com_num) < NUM_COMMANDS:
-        raise ValueError(f"com_num must be a command number in [0, {NUM_COMMANDS}), not {com_num!r}")
-    return text, rec, flags[0], flags[1], int(com_num)
+    return text, rec, flags[0], flags[1], _com_num(com_num)
+
+
+def _com_num(v) -> int:
+    if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) < NUM_COMMANDS:
+        raise ValueError(f"com_num must be a command number in [0, {NUM_COMMANDS}), not {v!r}")
+    return int(v)
 
 
 def _prepare_many(broadcasts):
@@ -196,6 +208,11 @@ class _Timing(ctypes.Structure):
     _fields_ = [("kernels_us", ctypes.c_double), ("end_to_end_us", ctypes.c_double)]
 
 
+class _RosterTiming(ctypes.Structure):
+    _fields_ = [("kernels_us", ctypes.c_double), ("end_to_end_us", ctypes.c_double),
+                ("h2d_bytes", ctypes.c_int64), ("d2h_bytes", ctypes.c_int64)]
+
+
 _LIB = None
 
 
@@ -231,6 +248,13 @@ def _load():
         lib.nd_fanout_many.argtypes = [ctypes.c_int, P, ctypes.c_int64, P, P, P, P, P, P, P, P, P,
                                        ctypes.POINTER(_Timing)]
         lib.nd_fanout_many.restype = ctypes.c_int
+        lib.nd_roster_create.argtypes = [ctypes.c_int]
+        lib.nd_roster_create.restype = ctypes.c_int
+        lib.nd_roster_destroy.argtypes = [ctypes.c_int]
+        lib.nd_roster_destroy.restype = ctypes.c_int
+        lib.nd_roster_fanout.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int64, P, P, P, P, P, P, P, P, P, P,
+                                         ctypes.POINTER(_RosterTiming)]
+        lib.nd_roster_fanout.restype = ctypes.c_int
         lib.nd_arena.restype = P
         lib.nd_write_sizes.restype = P
         _LIB = lib
@@ -308,3 +332,194 @@ def broadcast_many(broadcasts) -> Fanout:
     r = _result(lib, admitted, out_off, w_off, t)
     r.broadcast_offsets = item_off.astype(np.int64)
     return r
+
+
+# ------------------------------------------------------------------ a resident roster
+#: a Roster's flag fields, stored as their listener-record bits (bit k = LISTENER_FIELDS[k])
+ROSTER_FLAGS = {f: 1 << LISTENER_FIELDS.index(f) for f in ("login", "ignall", "ignshout", "colour")}
+_KEEP = object()
+
+
+def _room(v) -> int:
+    """A room id: None (no room) is -1, else an int in [0, ROOM_LIMIT)."""
+    if v is None:
+        return -1
+    if not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_)) or not 0 <= int(v) < ROOM_LIMIT:
+        raise ValueError(f"room must be None or an int in [0, {ROOM_LIMIT}), not {v!r}")
+    return int(v)
+
+
+class Roster:
+    """The talker's user list, kept on the device between calls: per slot a room (``None``: an empty slot, or a user
+    away over a netlink) and the ``login``, ``ignall``, ``ignshout`` and ``colour`` flags.  Broadcasts are addressed as
+    ``write_room_except(rm, str, user)`` addresses them (nuts333.c:1401-1415): ``rm`` is a room or ``None`` for every
+    room, ``sender`` a slot or ``None``.  The device builds each listener's record from its slot and the broadcast, so a
+    call carries K texts and K small tuples; the table travels only in the first call after an :meth:`update`.
+
+    Building and updating a roster does not touch the device; its first :meth:`broadcast_many` allocates there.  The
+    contract, for every call::
+
+        roster.broadcast_many(bs) == broadcast_many([(t, roster.table(rm, s), rm is None, fl, com)
+                                                     for t, rm, s, fl, com in bs])
+    """
+
+    def __init__(self, capacity: int):
+        if (not isinstance(capacity, (int, np.integer)) or isinstance(capacity, (bool, np.bool_))
+                or not 1 <= int(capacity) <= MAX_CAPACITY):
+            raise ValueError(f"roster capacity must be an int in [1, {MAX_CAPACITY}], not {capacity!r}")
+        self.capacity = int(capacity)
+        # the host mirror, as nd_roster_fanout takes it: `capacity` int32 rooms (-1: none), then `capacity` flag bytes
+        self._table = np.zeros(5 * self.capacity, dtype=np.uint8)
+        self._room = self._table[:4 * self.capacity].view(np.int32)
+        self._flags = self._table[4 * self.capacity:]
+        self._room[:] = -1
+        self._dirty = True
+        self._handle = None
+        self._closed = False
+
+    def _check_open(self) -> None:
+        if self._closed:
+            raise ValueError("the roster is closed")
+
+    def _slot(self, v) -> int:
+        if not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_)) or not 0 <= int(v) < self.capacity:
+            raise ValueError(f"slot must be an int in [0, {self.capacity}), not {v!r}")
+        return int(v)
+
+    def update(self, slots, *, room=_KEEP, login=_KEEP, ignall=_KEEP, ignshout=_KEEP, colour=_KEEP) -> None:
+        """Set fields of ``slots`` (a slot or a sequence of them).  Each field given is one value for every slot or a
+        sequence of one per slot; a field not given stays as it is.  ``room`` is None (no room) or an int in
+        [0, ROOM_LIMIT); the flags are 0/1 or bools.  A slot given more than once takes its last values.  Nothing
+        changes unless the whole update is valid."""
+        self._check_open()
+        if isinstance(slots, (int, np.integer)):
+            slots = [slots]
+        try:
+            idx = np.array([self._slot(s) for s in slots], dtype=np.int64)
+        except TypeError:
+            raise ValueError(f"slots must be a slot or a sequence of them, not {slots!r}") from None
+        n = len(idx)
+
+        def per_slot(name, v, conv, dtype):
+            if v is None or isinstance(v, (int, np.integer, bool, np.bool_)):
+                return np.full(n, conv(v), dtype=dtype)
+            if isinstance(v, (str, bytes)) or not hasattr(v, "__len__"):
+                raise ValueError(f"{name} must be a value or a sequence of one per slot, not {v!r}")
+            if len(v) != n:
+                raise ValueError(f"{name}: {len(v)} values for {n} slots")
+            return np.array([conv(x) for x in v], dtype=dtype)
+
+        rooms = None if room is _KEEP else per_slot("room", room, _room, np.int32)
+        flags = {f: per_slot(f, v, lambda x, f=f: _flag(f, x), np.uint8)
+                 for f, v in (("login", login), ("ignall", ignall), ("ignshout", ignshout), ("colour", colour))
+                 if v is not _KEEP}
+        _, last = np.unique(idx[::-1], return_index=True)        # each slot's last position: last write wins
+        keep = n - 1 - last
+        at = idx[keep]
+        if rooms is not None:
+            self._room[at] = rooms[keep]
+        for f, v in flags.items():
+            bit = np.uint8(ROSTER_FLAGS[f])
+            self._flags[at] = np.where(v[keep] != 0, self._flags[at] | bit, self._flags[at] & ~bit)
+        self._dirty = True
+
+    def table(self, rm, sender) -> np.ndarray:
+        """The (capacity, 7) listener table, in LISTENER_FIELDS order, that :func:`broadcast` would take for a broadcast
+        to room ``rm`` (None: every room) from slot ``sender`` (None: no sender), from the host mirror."""
+        self._check_open()
+        rm = _room(rm)
+        sender = -1 if sender is None else self._slot(sender)
+        col = LISTENER_FIELDS.index
+        t = np.zeros((self.capacity, len(LISTENER_FIELDS)), dtype=np.uint8)
+        for f, bit in ROSTER_FLAGS.items():
+            t[:, col(f)] = (self._flags & bit) != 0
+        t[:, col("has_room")] = self._room >= 0
+        if rm >= 0:
+            t[:, col("same_room")] = self._room == rm
+        if sender >= 0:
+            t[sender, col("is_sender")] = 1
+        return t
+
+    def _prepare(self, broadcasts):
+        """Each (text, rm, sender, force_listen, com_num) checked, packed for nd_roster_fanout: texts, text offsets and
+        lengths, rooms (-1: every room), senders (-1: none), flags (bit 1 force_listen) and commands."""
+        if isinstance(broadcasts, (str, bytes, bytearray, np.ndarray)) or not hasattr(broadcasts, "__len__"):
+            raise ValueError(f"broadcasts must be a sequence of tuples, not {type(broadcasts).__name__}")
+        if len(broadcasts) == 0:
+            raise ValueError("empty call: no broadcasts")
+        if len(broadcasts) * self.capacity >= 2**31:
+            raise ValueError(f"{len(broadcasts)} broadcasts to {self.capacity} slots: K x capacity must be below 2^31")
+        texts, rms, senders, flags, coms = [], [], [], [], []
+        for k, b in enumerate(broadcasts):
+            if not isinstance(b, tuple) or len(b) != 5:
+                raise ValueError(f"broadcast {k}: expected a (text, rm, sender, force_listen, com_num) tuple, "
+                                 f"got {type(b).__name__}{f' of {len(b)}' if isinstance(b, tuple) else ''}")
+            text, rm, sender, force_listen, com_num = b
+            try:
+                texts.append(_as_text(text))
+                rms.append(_room(rm))
+                senders.append(-1 if sender is None else self._slot(sender))
+                flags.append(_flag("force_listen", force_listen) << 1)
+                coms.append(_com_num(com_num))
+            except ValueError as e:
+                raise ValueError(f"broadcast {k}: {e}") from None
+        lens = np.fromiter((len(t) for t in texts), dtype=np.int64, count=len(texts))
+        if int(lens.sum()) >= 2**31:
+            raise ValueError("call text larger than 2 GiB: split it")
+        bound = int((self._room >= 0).sum()) * int((6 * lens + 4).sum())   # only a slot with a room is admitted
+        if bound > MANY_ARENA_CAP:
+            raise ValueError(f"call too large: its arena bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
+                             f"(MANY_ARENA_CAP): split it")
+        text_off = np.zeros(len(texts), dtype=np.int32)
+        np.cumsum(lens[:-1], out=text_off[1:])
+        return (b"".join(texts), text_off, lens.astype(np.int32), np.array(rms, dtype=np.int32),
+                np.array(senders, dtype=np.int32), np.array(flags, dtype=np.uint8), np.array(coms, dtype=np.int32))
+
+    def broadcast_many(self, broadcasts) -> Fanout:
+        """K broadcasts to this roster in one device call: a sequence of ``(text, rm, sender, force_listen, com_num)``
+        tuples, texts by :func:`broadcast`'s rules.  Item ``(k, j)`` is slot ``j`` of broadcast ``k``
+        (``Fanout.item``); ``timing`` adds ``h2d_bytes`` and ``d2h_bytes``.  Malformed calls, and calls whose arena
+        bound (slots with a room x the sum of max_bytes) exceeds MANY_ARENA_CAP, raise ``ValueError`` before the device
+        is touched."""
+        self._check_open()
+        text, text_off, lens, rm, sender, flags, coms = self._prepare(broadcasts)
+        lib = _load()
+        if self._handle is None:
+            h = lib.nd_roster_create(self.capacity)
+            if h < 0:
+                raise RuntimeError(f"cannot create a device roster: {lib.nd_last_error().decode(errors='replace')}")
+            self._handle = h
+        k = len(lens)
+        m = k * self.capacity
+        admitted = np.zeros(m, dtype=np.uint8)
+        out_off = np.zeros(m + 1, dtype=np.int64)
+        w_off = np.zeros(m + 1, dtype=np.int32)
+        tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
+        t = _RosterTiming()
+        rc = lib.nd_roster_fanout(self._handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(rm),
+                                  _ptr(sender), _ptr(flags), _ptr(coms), _ptr(self._table) if self._dirty else None,
+                                  _ptr(admitted), _ptr(out_off), _ptr(w_off), ctypes.byref(t))
+        if rc != 0:
+            raise RuntimeError(f"device fan-out failed: {lib.nd_last_error().decode(errors='replace')}")
+        self._dirty = False
+        r = _result(lib, admitted, out_off, w_off, t)
+        r.timing.update(h2d_bytes=t.h2d_bytes, d2h_bytes=t.d2h_bytes)
+        r.broadcast_offsets = np.arange(k + 1, dtype=np.int64) * self.capacity
+        return r
+
+    def close(self) -> None:
+        """Free the device table; the roster cannot be used afterwards.  Closing twice is harmless."""
+        if self._handle is not None and _LIB is not None:
+            _LIB.nd_roster_destroy(self._handle)
+        self._handle = None
+        self._closed = True
+
+    def __enter__(self) -> "Roster":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        if getattr(self, "_handle", None) is not None:
+            self.close()

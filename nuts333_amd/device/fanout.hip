@@ -15,7 +15,7 @@
 //   pass 2  nuts_fanout_emit_{batch,broadcast}: bytes into the arena, chunk sizes into write_sizes
 // In broadcast mode every item reads the same text, which each block stages in LDS once.  All four
 // kernels take one argument struct (Args), filled by the host.  nuts_fanout_{measure,emit}_many do K broadcasts in
-// one call (their section below).
+// one call, and nuts_roster_{measure,emit} K broadcasts to a roster kept on the device (their sections below).
 //
 // Hard bounds per item of a text of len < 2000 bytes: 6*len + 4 output bytes (a '\n' with colour
 // on is the costliest input byte, plus the trailing reset) and 16 writes.  The host sizes its buffers
@@ -291,8 +291,8 @@ __device__ __forceinline__ Tile find_tile(const ManyArgs& a)
 // Stage broadcast b's text in LDS, then transduce it with colour off (lane 0 of wave 0) and on (lane 0 of wave 1).
 // EMIT: the bytes go to var[c * kVarCap ..] and the chunk sizes to vwsz[c * kMaxWrites ..], clamped to the hard bounds.
 // vn / vw get the full counts, so a bound violation stays visible.  Every thread of the block calls this.
-template <bool EMIT>
-__device__ __forceinline__ void stage_variants(const ManyArgs& a, int b, uint8_t* text, uint8_t* var, int32_t* vwsz,
+template <bool EMIT, typename A>   // A: ManyArgs or RosterArgs
+__device__ __forceinline__ void stage_variants(const A& a, int b, uint8_t* text, uint8_t* var, int32_t* vwsz,
                                                int64_t* vn, int* vw)
 {
     const int len = a.text_len[b];
@@ -396,6 +396,188 @@ __device__ void emit_many(const ManyArgs& a)
 static_assert(kGroup >= kMaxWrites, "emit_many writes an item's chunk sizes with one lane each");
 static_assert(kBlock % kGroup == 0 && kBlock >= 128, "emit_many: whole lane groups; variants on waves 0 and 1");
 
+// ------------------------------------------------------------------ broadcasts to a resident roster
+//
+// A roster is the talker's user list kept on the device between calls: per slot a room (-1: none -- an empty slot, or
+// a user away over a netlink) and a flags byte holding the login, ignall, ignshout and colour bits of a listener record.
+// Broadcast b is addressed as write_room_except addresses it (nuts333.c:1401-1415): room rm[b] (-1: every room) and
+// the sender's slot sender[b] (-1: none).  Item (b, j) is slot j of broadcast b; every broadcast has `capacity` items.
+// One block per (broadcast, 256-slot tile).
+//   measure  nuts_roster_measure: each item's listener record built from its slot and its broadcast, and its admit flag;
+//            the first tile of each broadcast also transduces the two variants (stage_variants) and stores their bytes,
+//            chunk sizes and counts in the call's variant buffer -- once per broadcast per call
+//   scan     as above, over m + 1 entries; an item's bytes and writes are looked up from its broadcast's variant counts
+//   emit     nuts_roster_emit: the broadcast's variants staged in LDS from the buffer, the tile's items copied out of
+//            them with aligned 4-byte stores, as emit_many does (copy_items)
+struct RosterArgs {
+    const int32_t* room;         // [capacity] -1: no room
+    const uint8_t* slot;         // [capacity] kLogin | kIgnall | kIgnshout | kColour
+    const uint8_t* text;         // the K texts, packed
+    const int32_t* text_off;     // [k]
+    const int32_t* text_len;     // [k]
+    const int32_t* rm;           // [k] -1: every room (rm_is_null)
+    const int32_t* sender;       // [k] -1: none
+    const uint8_t* flags;        // [k] bit 1 force_listen
+    const int32_t* com_num;      // [k]
+    int k, capacity, tiles;      // tiles per broadcast
+    int* violations;             // variants past the hard bounds (zeroed by the host's upload)
+    uint8_t* admitted;           // [m], m = k * capacity
+    int64_t* out_off;            // [m + 1]
+    int32_t* w_off;              // [m + 1]
+    uint8_t* var;                // broadcast b's variants: var_at(b), var_at(b) + var_stride(len)
+    int64_t* vn;                 // [2k] bytes of broadcast b's colour-off / colour-on variant
+    int32_t* vw;                 // [2k] their write(2) counts
+    int32_t* vwsz;               // [2k * kMaxWrites] their chunk sizes
+    uint8_t* arena;
+    int64_t arena_cap;
+    int32_t* wsz;
+    int64_t wsz_cap;
+};
+
+// A variant's slot in the variant buffer: its hard bound rounded up to 4 bytes.  Broadcast b's two slots start at
+// 12 * text_off[b] + 16 * b, so the buffer holds 12 * text_bytes + 16 * k bytes and every slot is 4-byte aligned.
+__host__ __device__ __forceinline__ int64_t var_stride(int len) { return (6 * (int64_t)len + 4 + 3) & ~(int64_t)3; }
+__device__ __forceinline__ int64_t var_at(const RosterArgs& a, int b) { return 12 * (int64_t)a.text_off[b] + 16 * (int64_t)b; }
+
+__device__ void roster_measure(const RosterArgs& a)
+{
+    const int b = (int)blockIdx.x / a.tiles, tile = (int)blockIdx.x - b * a.tiles;
+    const int j = tile * kBlock + (int)threadIdx.x;
+    if (j < a.capacity) {
+        const int room = a.room[j], rm = a.rm[b];
+        const uint8_t l = (a.slot[j] & (kLogin | kIgnall | kIgnshout | kColour)) | (room >= 0 ? kHasRoom : 0) |
+                          (rm >= 0 && room == rm ? kSameRoom : 0) | (j == a.sender[b] ? kSender : 0);
+        a.admitted[b * a.capacity + j] = admits(l, rm < 0, (a.flags[b] >> 1) & 1, a.com_num[b]);
+    }
+    if (tile == 0) {            // block-uniform: this broadcast's variants, for the scan and emit
+        // Static LDS: every block of the kernel reserves these ~26 KB, the admit-only tiles too, so at most 6 blocks
+        // fit on a CU.  With at most 256 tiles per broadcast and the admit-only blocks this short, that costs little at
+        // the sizes measured; a variant stage of its own grid would lift it, for one more dispatch.
+        __shared__ uint8_t text[kTextSize];
+        __shared__ uint8_t var[2 * kVarCap];
+        __shared__ int32_t vwsz[2 * kMaxWrites];
+        __shared__ int64_t vn[2];
+        __shared__ int vw[2];
+        stage_variants<true>(a, b, text, var, vwsz, vn, vw);
+        const int len = a.text_len[b];
+        const int64_t cap = 6 * (int64_t)len + 4, stride = var_stride(len);
+        uint8_t* dst = a.var + var_at(a, b);
+        for (int c = 0; c < 2; c++) {
+            const int64_t n = vn[c] < cap ? vn[c] : cap;
+            for (int64_t q = threadIdx.x; q < n; q += kBlock) dst[c * stride + q] = var[c * kVarCap + q];
+            const int nw = vw[c] < kMaxWrites ? vw[c] : kMaxWrites;
+            if ((int)threadIdx.x < nw) a.vwsz[(2 * b + c) * kMaxWrites + threadIdx.x] = vwsz[c * kMaxWrites + threadIdx.x];
+        }
+        if (threadIdx.x < 2) {
+            a.vn[2 * b + threadIdx.x] = vn[threadIdx.x];
+            a.vw[2 * b + threadIdx.x] = vw[threadIdx.x];
+            if (vn[threadIdx.x] > cap || vw[threadIdx.x] > kMaxWrites) atomicAdd(a.violations, 1);
+        }
+    }
+}
+
+// The scans' input: item i's bytes (T = int64_t, v = vn) or writes (T = int32_t, v = vw), its admitted variant's count;
+// entry m, the scans' extra one, is zero.
+template <typename T>
+struct ItemCount {
+    const uint8_t* admitted;
+    const uint8_t* slot;
+    const T* v;
+    int capacity, m;
+    __host__ __device__ T operator()(int i) const
+    {
+        if (i >= m || !admitted[i]) return 0;
+        const int b = i / capacity;
+        return v[2 * b + ((slot[i - b * capacity] & kColour) ? 1 : 0)];
+    }
+};
+
+// nuts_roster_emit's copy of a tile's items out of the two variants in LDS: emit_many's copy loop, kept apart from it
+// (sharing one inlined helper changed the code the compiler makes for emit_many).  Item j takes variant s_c[j], s_n[j]
+// bytes into the arena at s_off[j] and s_nw[j] chunk sizes into wsz at s_woff[j], kGroup lanes per item.  The caller
+// has clamped s_n / s_nw to the arena, the chunk array and the hard bounds.
+__device__ __forceinline__ void copy_items(int count, const uint8_t* var, const int32_t* vwsz, const int64_t* vn,
+                                           const int* vw, const int64_t* s_off, const int64_t* s_n,
+                                           const int32_t* s_woff, const int32_t* s_nw, const uint8_t* s_c,
+                                           uint8_t* arena, int32_t* wsz)
+{
+    const int g = (int)threadIdx.x / kGroup, lane = (int)threadIdx.x % kGroup;
+    for (int j = g; j < count; j += kBlock / kGroup) {
+        const int c = s_c[j];
+        const int64_t n0 = s_n[j], vmax = vn[c] < kVarCap ? vn[c] : kVarCap;
+        const int64_t n = n0 < vmax ? n0 : vmax;
+        const uint8_t* src = var + c * kVarCap;
+        uint8_t* dst = arena + s_off[j];
+        // w: item-relative offset of a 4-byte word of the arena (the arena is 256-byte aligned), from the word
+        // holding the item's first byte; whole words in one store, the item's partial edge words byte by byte
+        const int head = (int)(s_off[j] & 3);
+        for (int64_t w = 4 * lane - head; w < n; w += 4 * kGroup) {
+            if (w >= 0 && w + 4 <= n) {
+                const uint32_t v = (uint32_t)src[w] | (uint32_t)src[w + 1] << 8 | (uint32_t)src[w + 2] << 16 |
+                                   (uint32_t)src[w + 3] << 24;
+                *reinterpret_cast<uint32_t*>(dst + w) = v;
+            } else {
+                for (int q = 0; q < 4; q++)
+                    if (w + q >= 0 && w + q < n) dst[w + q] = src[w + q];
+            }
+        }
+        const int nw = s_nw[j] < vw[c] ? s_nw[j] : vw[c];
+        if (lane < nw) wsz[s_woff[j] + lane] = vwsz[c * kMaxWrites + lane];
+    }
+}
+
+__device__ void roster_emit(const RosterArgs& a)
+{
+    __shared__ uint8_t var[2 * kVarCap];
+    __shared__ int32_t vwsz[2 * kMaxWrites];
+    __shared__ int64_t vn[2];
+    __shared__ int vw[2];
+    __shared__ int64_t s_off[kBlock], s_n[kBlock];   // as in emit_many
+    __shared__ int32_t s_woff[kBlock], s_nw[kBlock];
+    __shared__ uint8_t s_c[kBlock];
+    const int b = (int)blockIdx.x / a.tiles, j0 = ((int)blockIdx.x - b * a.tiles) * kBlock;
+    const int len = a.text_len[b];
+    const int64_t cap = 6 * (int64_t)len + 4;
+    {   // this item's metadata, clamped as in emit_many; its bytes and writes are the differences of the scans
+        const int j = j0 + (int)threadIdx.x;
+        if (j < a.capacity) {
+            const int i = b * a.capacity + j;
+            const bool in = a.admitted[i] != 0;
+            const int64_t off = a.out_off[i], woff = a.w_off[i];
+            const int64_t room = a.arena_cap - off, wroom = a.wsz_cap - woff;
+            int64_t n = in ? a.out_off[i + 1] - off : 0;
+            n = n < room ? n : room;
+            n = n < cap ? n : cap;
+            int64_t nw = in ? a.w_off[i + 1] - woff : 0;
+            nw = nw < wroom ? nw : wroom;
+            nw = nw < kMaxWrites ? nw : kMaxWrites;
+            s_off[threadIdx.x] = off;
+            s_n[threadIdx.x] = n > 0 ? n : 0;
+            s_woff[threadIdx.x] = (int32_t)woff;
+            s_nw[threadIdx.x] = nw > 0 ? (int32_t)nw : 0;
+            s_c[threadIdx.x] = (a.slot[j] & kColour) ? 1 : 0;
+        }
+    }
+    // the broadcast's variants, as measure stored them, clamped to the hard bounds
+    const uint8_t* src = a.var + var_at(a, b);
+    const int64_t stride = var_stride(len);
+    for (int c = 0; c < 2; c++) {
+        const int64_t n = a.vn[2 * b + c] < cap ? a.vn[2 * b + c] : cap;
+        for (int64_t q = threadIdx.x; q < n; q += kBlock) var[c * kVarCap + q] = src[c * stride + q];
+        const int nw = a.vw[2 * b + c] < kMaxWrites ? a.vw[2 * b + c] : kMaxWrites;
+        if ((int)threadIdx.x < nw) vwsz[c * kMaxWrites + threadIdx.x] = a.vwsz[(2 * b + c) * kMaxWrites + threadIdx.x];
+        if (threadIdx.x == 0) {
+            vn[c] = n;
+            vw[c] = nw;
+        }
+    }
+    __syncthreads();
+    const int count = a.capacity - j0 < kBlock ? a.capacity - j0 : kBlock;
+    copy_items(count, var, vwsz, vn, vw, s_off, s_n, s_woff, s_nw, s_c, a.arena, a.wsz);
+}
+
+static_assert(2 * kMaxWrites <= kBlock, "roster kernels move a broadcast's chunk sizes with one lane each");
+
 }  // namespace
 
 // Stable, unmangled kernel names (they are what rocprofv3 reports).
@@ -405,6 +587,8 @@ extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_emit_batch(Args
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_emit_broadcast(Args a) { emit<true>(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_measure_many(ManyArgs a) { measure_many(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_emit_many(ManyArgs a) { emit_many(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_measure(RosterArgs a) { roster_measure(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_emit(RosterArgs a) { roster_emit(a); }
 
 // ------------------------------------------------------------------------------------------ host library
 
@@ -549,6 +733,107 @@ size_t layout_many(uintptr_t base, size_t text_bytes, size_t scan_bytes, ManyArg
     take(a.wsz, (size_t)a.wsz_cap);
     take(*scan, scan_bytes);
     return at;
+}
+
+// A roster's own device allocation and its pinned mirror, laid out alike by layout_roster(): the table (room, slot),
+// then the call's inputs ending with violations, then admitted, out_off and w_off.  One upload fills the inputs, and
+// the table with them when it changed; one download fetches violations .. w_off.  Both grow on demand; the mirror
+// keeps the table across growth, and a new device allocation is filled from it.
+constexpr int kMaxRosters = 64;
+constexpr int kMaxCapacity = 65536;
+struct Roster {
+    bool live = false;
+    bool resident = false;       // the device allocation holds the mirror's table
+    int capacity = 0;
+    int64_t rooms = 0;           // slots with a room: only they can be admitted
+    uint8_t* d = nullptr;
+    uint8_t* mirror = nullptr;
+    size_t cap_d = 0, cap_mirror = 0;
+};
+Roster g_rosters[kMaxRosters];
+
+size_t layout_roster(uintptr_t base, size_t text_bytes, RosterArgs& a)
+{
+    size_t at = 0;
+    auto take = [&](auto*& p, size_t count) {
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + at);
+        at += (count * sizeof(*p) + 255) & ~(size_t)255;
+    };
+    const size_t k = (size_t)a.k, m = k * (size_t)a.capacity;
+    take(a.room, (size_t)a.capacity);
+    take(a.slot, (size_t)a.capacity);
+    take(a.text, text_bytes);
+    take(a.text_off, k);
+    take(a.text_len, k);
+    take(a.rm, k);
+    take(a.sender, k);
+    take(a.flags, k);
+    take(a.com_num, k);
+    take(a.violations, 1);
+    take(a.admitted, m);
+    take(a.out_off, m + 1);
+    take(a.w_off, m + 1);
+    return at;
+}
+
+// The call's work arrays in the shared device block: the variants, the arena, the chunk sizes and the scans' scratch.
+size_t layout_roster_work(uintptr_t base, size_t var_bytes, size_t scan_bytes, RosterArgs& a, uint8_t** scan)
+{
+    size_t at = 0;
+    auto take = [&](auto*& p, size_t count) {
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + at);
+        at += (count * sizeof(*p) + 255) & ~(size_t)255;
+    };
+    const size_t k = (size_t)a.k;
+    take(a.var, var_bytes);
+    take(a.vn, 2 * k);
+    take(a.vw, 2 * k);
+    take(a.vwsz, 2 * k * kMaxWrites);
+    take(a.arena, (size_t)a.arena_cap);
+    take(a.wsz, (size_t)a.wsz_cap);
+    take(*scan, scan_bytes);
+    return at;
+}
+
+// Grow r's pinned mirror to want bytes, keeping its first keep bytes (the table); a new mirror starts with every slot
+// empty (no room, no flags).
+int grow_mirror(Roster& r, size_t want, size_t keep)
+{
+    if (want <= r.cap_mirror) return 0;
+    uint8_t* p = nullptr;
+    hipError_t e = hipHostMalloc((void**)&p, want, hipHostMallocDefault);
+    if (e != hipSuccess) return fail("pinned roster mirror", e);
+    if (r.mirror) {
+        memcpy(p, r.mirror, keep);
+        (void)hipHostFree(r.mirror);
+    } else {
+        memset(p, 0, keep);
+        memset(p, 0xff, (size_t)r.capacity * sizeof(int32_t));    // room -1
+    }
+    r.mirror = p;
+    r.cap_mirror = want;
+    return 0;
+}
+
+// The scans' inputs for a roster call of m items.
+auto item_bytes(const RosterArgs& a, int m)
+{
+    return rocprim::make_transform_iterator(rocprim::make_counting_iterator(0),
+                                            ItemCount<int64_t>{a.admitted, a.slot, a.vn, a.capacity, m});
+}
+auto item_writes(const RosterArgs& a, int m)
+{
+    return rocprim::make_transform_iterator(rocprim::make_counting_iterator(0),
+                                            ItemCount<int32_t>{a.admitted, a.slot, a.vw, a.capacity, m});
+}
+
+Roster* roster_at(int handle)
+{
+    if (handle < 0 || handle >= kMaxRosters || !g_rosters[handle].live) {
+        snprintf(g_err, sizeof(g_err), "no live roster %d", handle);
+        return nullptr;
+    }
+    return &g_rosters[handle];
 }
 
 }  // namespace
@@ -752,6 +1037,161 @@ int nd_fanout_many(int k, const uint8_t* text, int64_t text_bytes, const int32_t
     if (timing) {
         timing->kernels_us = (double)ms * 1e3;
         timing->end_to_end_us = (t1 - t0) * 1e-3;
+    }
+    return 0;
+}
+
+// Timings and copy volume of the last nd_roster_fanout call.
+struct nd_roster_timing {
+    double kernels_us;      // device events around measure .. emit (both scans included)
+    double end_to_end_us;   // host clock: packing the inputs, H2D, kernels, D2H of results, ending in a synchronise
+    int64_t h2d_bytes;      // the inputs, plus the table when it was given or the device allocation is new
+    int64_t d2h_bytes;
+};
+
+// A roster of `capacity` slots (1 .. 65536), every slot empty.  Nothing is allocated until its first nd_roster_fanout.
+// Returns a handle, or -1 with nd_last_error() set; at most 64 rosters are live at once.
+int nd_roster_create(int capacity)
+{
+    if (capacity < 1 || capacity > kMaxCapacity) {
+        snprintf(g_err, sizeof(g_err), "roster capacity %d outside 1 .. %d", capacity, kMaxCapacity);
+        return -1;
+    }
+    for (int h = 0; h < kMaxRosters; h++)
+        if (!g_rosters[h].live) {
+            g_rosters[h] = Roster{};
+            g_rosters[h].live = true;
+            g_rosters[h].capacity = capacity;
+            return h;
+        }
+    snprintf(g_err, sizeof(g_err), "%d rosters are live: destroy one first", kMaxRosters);
+    return -1;
+}
+
+// Frees the roster's device allocation and mirror.  Returns 0, or -1 for a handle that is not live.
+int nd_roster_destroy(int handle)
+{
+    Roster* r = roster_at(handle);
+    if (!r) return -1;
+    if (r->d) (void)hipFree(r->d);
+    if (r->mirror) (void)hipHostFree(r->mirror);
+    *r = Roster{};
+    return 0;
+}
+
+// K broadcasts to roster `handle`.  Broadcast b: the text text[text_off[b] .. text_off[b] + text_len[b]), room rm[b]
+// (-1: every room), sender slot sender[b] (-1: none), flags[b] (bit 1 force_listen, as nd_fanout_many's; rm_is_null is
+// rm[b] < 0) and com_num[b].  table is NULL when the roster has not changed since the last call, else all of it:
+// `capacity` int32 rooms (-1: none), then `capacity` flag bytes (login 1, ignall 8, ignshout 16, colour 64: their
+// listener-record bits).  Outputs as nd_fanout_many's over the m = k * capacity items, item (b, j) at b * capacity + j.
+// Whatever k: one upload (the table in it only when given or when the device allocation is new), four kernels (two of
+// them the scans), three downloads, two synchronises.  The arena holds the hard bound, the slots with a room times the
+// sum of 6 * text_len[b] + 4; the caller keeps it under its cap and has validated the input (texts as for nd_fanout,
+// rooms, senders).  Returns 0, or -1 with nd_last_error() set.
+int nd_roster_fanout(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off,
+                     const int32_t* text_len, const int32_t* rm, const int32_t* sender, const uint8_t* flags,
+                     const int32_t* com_num, const uint8_t* table, uint8_t* admitted, int64_t* out_off, int32_t* w_off,
+                     nd_roster_timing* timing)
+{
+    Roster* r = roster_at(handle);
+    if (!r || ensure_ready()) return -1;
+    const int64_t m64 = (int64_t)k * r->capacity;
+    if (k < 1 || m64 >= INT32_MAX) {
+        snprintf(g_err, sizeof(g_err), "%d broadcasts to %d slots: need 1 <= k * capacity < 2^31 - 1", k, r->capacity);
+        return -1;
+    }
+    const double t0 = now_ns();
+    hipStream_t st = g.stream;
+    const int m = (int)m64, cap = r->capacity;
+    RosterArgs a{};
+    a.k = k;
+    a.capacity = cap;
+    a.tiles = (cap + kBlock - 1) / kBlock;
+    RosterArgs o = a;                // offsets of every array in the roster's allocation
+    const size_t need = layout_roster(0, (size_t)text_bytes, o);
+    const size_t table_bytes = (uintptr_t)o.text, in_bytes = (uintptr_t)o.violations + sizeof(int);
+    const size_t res_at = (uintptr_t)o.violations, res_bytes = (uintptr_t)o.w_off + ((size_t)m + 1) * sizeof(int32_t) - res_at;
+    if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
+    if (table) {
+        memcpy(r->mirror + (uintptr_t)o.room, table, (size_t)cap * sizeof(int32_t));
+        memcpy(r->mirror + (uintptr_t)o.slot, table + (size_t)cap * sizeof(int32_t), (size_t)cap);
+        const int32_t* room = reinterpret_cast<const int32_t*>(r->mirror + (uintptr_t)o.room);
+        r->rooms = std::count_if(room, room + cap, [](int32_t x) { return x >= 0; });
+        r->resident = false;
+    }
+    const size_t cap_d = r->cap_d;
+    if (grow_dev(&r->d, &r->cap_d, need, "roster device allocation")) return -1;
+    if (r->cap_d != cap_d) r->resident = false;
+    layout_roster((uintptr_t)r->d, (size_t)text_bytes, a);
+    for (int b = 0; b < k; b++) a.arena_cap += r->rooms * (6 * (int64_t)text_len[b] + 4);
+    a.wsz_cap = r->rooms * k * kMaxWrites;
+    size_t scan1 = 0, scan2 = 0;     // both scans run over m + 1 entries
+    ND_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan1, item_bytes(a, m), a.out_off, m + 1, st));
+    ND_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan2, item_writes(a, m), a.w_off, m + 1, st));
+    const size_t scan_bytes = std::max(scan1, scan2), var_bytes = 12 * (size_t)text_bytes + 16 * (size_t)k;
+    uint8_t* scan = nullptr;
+    RosterArgs w = a;
+    const size_t work = layout_roster_work(0, var_bytes, scan_bytes, w, &scan);
+    if (grow_dev(&g.d_block, &g.cap_block, work, "device buffers")) return -1;
+    layout_roster_work((uintptr_t)g.d_block, var_bytes, scan_bytes, a, &scan);
+    if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
+
+    // the inputs packed after the table, as they lie in the device allocation; the table goes with them if it changed
+    uint8_t* h = r->mirror;
+    auto put = [&](const void* at, const void* src, size_t bytes) {
+        if (bytes) memcpy(h + (uintptr_t)at, src, bytes);
+    };
+    put(o.text, text, (size_t)text_bytes);
+    put(o.text_off, text_off, (size_t)k * sizeof(int32_t));
+    put(o.text_len, text_len, (size_t)k * sizeof(int32_t));
+    put(o.rm, rm, (size_t)k * sizeof(int32_t));
+    put(o.sender, sender, (size_t)k * sizeof(int32_t));
+    put(o.flags, flags, (size_t)k);
+    put(o.com_num, com_num, (size_t)k * sizeof(int32_t));
+    *reinterpret_cast<int*>(h + (uintptr_t)o.violations) = 0;
+    const size_t from = r->resident ? table_bytes : 0;
+    ND_CHECK(hipMemcpyAsync(r->d + from, h + from, in_bytes - from, hipMemcpyHostToDevice, st));
+    r->resident = true;
+
+    const dim3 grid((unsigned)(k * a.tiles)), block(kBlock);
+    ND_CHECK(hipEventRecord(g.ev0, st));
+    hipLaunchKernelGGL(nuts_roster_measure, grid, block, 0, st, a);
+    ND_CHECK(hipGetLastError());
+    size_t bytes = scan_bytes;
+    ND_CHECK(hipcub::DeviceScan::ExclusiveSum(scan, bytes, item_bytes(a, m), a.out_off, m + 1, st));
+    bytes = scan_bytes;
+    ND_CHECK(hipcub::DeviceScan::ExclusiveSum(scan, bytes, item_writes(a, m), a.w_off, m + 1, st));
+    hipLaunchKernelGGL(nuts_roster_emit, grid, block, 0, st, a);
+    ND_CHECK(hipGetLastError());
+    ND_CHECK(hipEventRecord(g.ev1, st));
+
+    // violations, admitted and the offsets in one download: they say how much of the arena to fetch
+    ND_CHECK(hipMemcpyAsync(gm.res, r->d + res_at, res_bytes, hipMemcpyDeviceToHost, st));
+    ND_CHECK(hipStreamSynchronize(st));
+    auto res = [&](const void* at) { return gm.res + ((uintptr_t)at - res_at); };
+    const int violations = *reinterpret_cast<const int*>(res(o.violations));
+    if (violations) {
+        snprintf(g_err, sizeof(g_err), "%d variant(s) exceeded the hard output bounds (6*len+4 bytes, %d writes)",
+                 violations, kMaxWrites);
+        return -1;
+    }
+    memcpy(admitted, res(o.admitted), (size_t)m);
+    memcpy(out_off, res(o.out_off), ((size_t)m + 1) * sizeof(int64_t));
+    memcpy(w_off, res(o.w_off), ((size_t)m + 1) * sizeof(int32_t));
+    if (grow_host(&g.h_arena, &g.cap_host_arena, (size_t)out_off[m] + 1, "pinned arena")) return -1;
+    if (grow_host(&g.h_wsz, &g.cap_host_writes, (size_t)w_off[m] + 1, "pinned write sizes")) return -1;
+    ND_CHECK(hipMemcpyAsync(g.h_arena, a.arena, (size_t)out_off[m], hipMemcpyDeviceToHost, st));
+    ND_CHECK(hipMemcpyAsync(g.h_wsz, a.wsz, (size_t)w_off[m] * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    ND_CHECK(hipStreamSynchronize(st));
+    const double t1 = now_ns();
+
+    float ms = 0.f;
+    ND_CHECK(hipEventElapsedTime(&ms, g.ev0, g.ev1));
+    if (timing) {
+        timing->kernels_us = (double)ms * 1e3;
+        timing->end_to_end_us = (t1 - t0) * 1e-3;
+        timing->h2d_bytes = (int64_t)(in_bytes - from);
+        timing->d2h_bytes = (int64_t)(res_bytes + (size_t)out_off[m] + (size_t)w_off[m] * sizeof(int32_t));
     }
     return 0;
 }

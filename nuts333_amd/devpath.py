@@ -1,7 +1,7 @@
 """What one broadcast's user-space stage costs on the MI355X, done by a kernel that does the work.
 
     python -m nuts333_amd.devpath [--reps R] [--warmup W] [--pathbench-iterations I] [--per-call K[,K...]]
-                                                                                       -> one JSON line
+                                  [--roster K[,K...]]                                  -> one JSON line
 
 For N in {10, 100, 1000} listeners, the two texts oracle/pathbench.c times (``say``; ``shout`` carrying ``~OL``/``~RS``)
 and colour all-off / all-on / half, one ``nuts333_amd.device.broadcast`` per repetition (listener 0 is the sender, the
@@ -21,6 +21,11 @@ no CPU fall-back.
 ``kernels_us`` and ``end_to_end_us`` per call and per broadcast, ``python_us`` (the host clock around the whole
 ``broadcast_many`` call: packing the K tables, the library call, copying the results out of pinned memory), and
 ``cpu_derived_us`` per broadcast with the ratios.  Bytes are checked against the CPU restatement once per case.
+
+``--roster K[,K...]`` adds ``roster``: the same cases through ``nuts333_amd.device.Roster.broadcast_many``, to a roster
+of N slots built once per case, untimed (everyone in room 0, slot 0 the sender), so every broadcast is
+``(text, 0, 0, 0, COM[text])``.  The same fields as ``per_call``, plus ``h2d_bytes`` uploaded per timed call (no table:
+nothing changed) and ``h2d_bytes_first_call`` (with the table).
 """
 from __future__ import annotations
 
@@ -100,29 +105,53 @@ def line_texts(text: str, k: int) -> list[bytes]:
 def per_call_case(n: int, text: str, colour: str, k: int, reps: int, warmup: int, pb: dict) -> dict:
     """K broadcasts of ``text`` (distinct line numbers) to listeners(n, colour) per broadcast_many call."""
     table = listeners(n, colour)
+    calls = [(t, table, 0, 0, COM[text]) for t in line_texts(text, k)]
+    case, _, _ = _timed_calls("per call", n, text, colour, k, lambda: device.broadcast_many(calls), reps, warmup, pb)
+    return case
+
+
+def roster_case(n: int, text: str, colour: str, k: int, reps: int, warmup: int, pb: dict) -> dict:
+    """K broadcasts of ``text`` per Roster.broadcast_many call, to a roster built once, untimed, in the
+    listeners(n, colour) shape: every slot in room 0, slot 0 the sender."""
+    with device.Roster(n) as roster:
+        roster.update(range(n), room=0, colour=listeners(n, colour)[:, device.LISTENER_FIELDS.index("colour")])
+        calls = [(t, 0, 0, 0, COM[text]) for t in line_texts(text, k)]
+        case, first, timed = _timed_calls("roster", n, text, colour, k, lambda: roster.broadcast_many(calls), reps,
+                                          warmup, pb)
+    h2d = {t["h2d_bytes"] for t in timed}
+    if len(h2d) != 1:
+        raise SystemExit(f"devpath: roster {k}, {n}/{text}/{colour}: timed calls uploaded {sorted(h2d)} bytes")
+    h2d = h2d.pop()
+    return {**case, "h2d_bytes": h2d, "h2d_bytes_per_broadcast": round(h2d / k, 1),
+            "h2d_bytes_first_call": first["h2d_bytes"], "d2h_bytes": first["d2h_bytes"]}
+
+
+def _timed_calls(label: str, n: int, text: str, colour: str, k: int, run, reps: int, warmup: int, pb: dict):
+    """One case: ``run()`` makes K broadcasts of ``text`` to listeners(n, colour); its first result is checked against
+    the CPU restatement, then it is warmed up and timed.  Returns the case, the first call's timing and the timed
+    calls' timings."""
     texts = line_texts(text, k)
-    calls = [(t, table, 0, 0, COM[text]) for t in texts]
-    run = lambda: device.broadcast_many(calls)
     first = run()
-    colour_of = table[1:, device.LISTENER_FIELDS.index("colour")].tolist()
+    colour_of = listeners(n, colour)[1:, device.LISTENER_FIELDS.index("colour")].tolist()
     want = b"".join(b"".join(v[c] for c in colour_of)
                     for v in ({0: nuts_path.transduce(t, 0), 1: nuts_path.transduce(t, 1)} for t in texts))
     if first.arena.tobytes() != want or int(first.admitted.sum()) != k * (n - 1):
-        raise SystemExit(f"devpath: per call {k}, {n}/{text}/{colour}: device produced {int(first.out_offsets[-1])} "
+        raise SystemExit(f"devpath: {label} {k}, {n}/{text}/{colour}: device produced {int(first.out_offsets[-1])} "
                          f"bytes, the CPU restatement {len(want)}")
     for _ in range(warmup):
         run()
-    kern, e2e, py = [], [], []
+    kern, e2e, py, timed = [], [], [], []
     for _ in range(reps):
         t0 = time.perf_counter()
         r = run()
         py.append((time.perf_counter() - t0) * 1e6)
         kern.append(r.timing["kernels_us"])
         e2e.append(r.timing["end_to_end_us"])
+        timed.append(r.timing)
     cpu = cpu_derived_us(pb, text, colour, n)
     ks, es, ps = _stats(kern), _stats(e2e), _stats(py)
     per = lambda s: {q: round(v / k, 3) for q, v in s.items()}
-    return {"n": n, "text": text, "colour": colour, "k": k, "recipients": k * (n - 1),
+    case = {"n": n, "text": text, "colour": colour, "k": k, "recipients": k * (n - 1),
             "bytes_out": int(first.out_offsets[-1]), "writes": int(first.write_offsets[-1]),
             "kernels_us": ks, "end_to_end_us": es, "python_us": ps,
             "kernels_us_per_broadcast": per(ks), "end_to_end_us_per_broadcast": per(es),
@@ -130,6 +159,7 @@ def per_call_case(n: int, text: str, colour: str, k: int, reps: int, warmup: int
             "cpu_derived_us": round(cpu, 3),
             "end_to_end_over_cpu": round(es["median"] / k / cpu, 2),
             "python_over_cpu": round(ps["median"] / k / cpu, 2)}
+    return case, first.timing, timed
 
 
 def main(argv=None) -> int:
@@ -139,6 +169,8 @@ def main(argv=None) -> int:
     ap.add_argument("--pathbench-iterations", type=int, default=2_000_000)
     ap.add_argument("--per-call", type=per_call_counts, default=None, metavar="K[,K...]",
                     help="also time K broadcasts per broadcast_many call, for each K (the per_call cases)")
+    ap.add_argument("--roster", type=per_call_counts, default=None, metavar="K[,K...]",
+                    help="also time K broadcasts per Roster.broadcast_many call, for each K (the roster cases)")
     a = ap.parse_args(argv)
     if a.reps < 1 or a.warmup < 0:
         ap.error("--reps must be >= 1 and --warmup >= 0")
@@ -192,6 +224,17 @@ def main(argv=None) -> int:
             "per_call": [per_call_case(n, text, colour, k, a.reps, a.warmup, pb)
                          for n in SIZES for text in TEXTS for colour in COLOURS for k in a.per_call],
         }
+    roster = {}
+    if a.roster:
+        roster = {
+            "roster_kernels": ["nuts_roster_measure", "rocprim device scan x2", "nuts_roster_emit"],
+            "roster_end_to_end_covers": "packing the K inputs into pinned memory, one H2D (the roster table only in a "
+                                        "call after an update: h2d_bytes_first_call), kernels, three D2H, two "
+                                        "synchronises (python_us adds checking the K tuples and the copies out of "
+                                        "pinned memory)",
+            "roster": [roster_case(n, text, colour, k, a.reps, a.warmup, pb)
+                       for n in SIZES for text in TEXTS for colour in COLOURS for k in a.roster],
+        }
     out = {
         "what": "user-space stage of one broadcast (admit predicate + transducer), device vs CPU",
         "device": "gfx950",
@@ -202,6 +245,7 @@ def main(argv=None) -> int:
                              "formula": "(N-1) x transduce + N x fanout_predicate + format_line_once (derived, not timed)"},
         "cases": cases,
         **per_call,
+        **roster,
         "wall_s": round(time.perf_counter() - t_start, 1),
     }
     print(json.dumps(out))
