@@ -12,6 +12,10 @@ number of copies and kernel launches whatever K; its items run broadcast by broa
 :class:`Roster` keeps the talker's listener state (room and flags per slot) on the device between calls; its
 ``broadcast_many`` takes K ``(text, rm, sender, force_listen, com_num)`` tuples, addressed as ``write_room_except``
 addresses them, and the device builds every listener's record, so a call uploads the table only after an update.
+``Roster.plan_many`` takes the same tuples and returns a :class:`Plan` instead: per broadcast the two variants a
+listener can get (colour off, colour on) with their ``write(2)`` chunk sizes, and one admit bit per slot -- what a talker
+needs to ``write(fd, variant[colour], size)`` to every admitted slot, in one kernel, one download and one synchronise.
+``Plan.expand()`` replicates it on the host into the :class:`Fanout` that ``Roster.broadcast_many`` returns.
 
 Input is validated before the device is touched (``ValueError``).  The library ``_build/libnuts_device.so`` is built by
 ``__graft_entry__.build()`` where ``hipcc`` exists, and on demand here when it is missing or older than its source.
@@ -45,8 +49,9 @@ COM_SAY, COM_SHOUT, COM_SEMOTE = 3, 4, 7
 KERNELS = ("nuts_fanout_measure_broadcast", "nuts_fanout_emit_broadcast",
            "nuts_fanout_measure_batch", "nuts_fanout_emit_batch",
            "nuts_fanout_measure_many", "nuts_fanout_emit_many",
-           "nuts_roster_measure", "nuts_roster_emit")
-#: broadcast_many() refuses a call whose arena bound, the sum over its broadcasts of N * max_bytes(len), exceeds this
+           "nuts_roster_measure", "nuts_roster_emit", "nuts_roster_plan")
+#: broadcast_many() refuses a call whose arena bound, the sum over its broadcasts of N * max_bytes(len), exceeds this;
+#: Roster.plan_many() one whose variant bound, 12 * text bytes + 16 * K, does
 MANY_ARENA_CAP = 2 << 30
 #: the most slots a Roster holds
 MAX_CAPACITY = 65536
@@ -94,6 +99,102 @@ def chunks(result: Fanout, i: int) -> list[bytes]:
     if at != len(data):
         raise AssertionError(f"item {i}: chunk sizes sum to {at}, arena slot holds {len(data)} bytes")
     return out
+
+
+def _gather(src: np.ndarray, starts: np.ndarray, counts: np.ndarray, step: int = 1 << 24) -> np.ndarray:
+    """``concatenate([src[s:s + n] for s, n in zip(starts, counts)])`` without a Python loop over the pieces: index
+    arithmetic over runs of pieces of about ``step`` elements, so that the index arrays stay small."""
+    ends = np.cumsum(counts)
+    total = int(ends[-1]) if len(ends) else 0
+    out = np.empty(total, dtype=src.dtype)
+    lo, at = 0, 0
+    while lo < len(counts):
+        hi = max(int(np.searchsorted(ends, at + step, side="right")), lo + 1)
+        n = int(ends[hi - 1]) - at
+        first = ends[lo:hi] - counts[lo:hi] - at          # where each piece starts in this run's output
+        out[at:at + n] = src[np.repeat(starts[lo:hi] - first, counts[lo:hi]) + np.arange(n, dtype=np.int64)]
+        lo, at = hi, at + n
+    return out
+
+
+def _unpack(words: np.ndarray, capacity: int) -> np.ndarray:
+    """uint64 [..., W] bitmap words -> bool [..., capacity]: bit j % 64 of word j // 64 is slot j."""
+    b = np.ascontiguousarray(words, dtype="<u8").view(np.uint8)
+    return np.unpackbits(b, axis=-1, bitorder="little")[..., :capacity].astype(bool)
+
+
+def _pack(flags: np.ndarray) -> np.ndarray:
+    """bool [capacity] -> uint64 [W] bitmap words, the tail bits of the last word zero."""
+    padded = np.zeros((len(flags) + 63) // 64 * 64, dtype=bool)
+    padded[:len(flags)] = flags
+    return np.packbits(padded, bitorder="little").view("<u8").astype(np.uint64)
+
+
+@dataclass
+class Plan:
+    """What a talker needs to deliver K broadcasts to a roster: slot ``j`` gets ``variant(k, colour of j)``, in the
+    chunks ``chunks(k, colour of j)``, if it is admitted.  :meth:`expand` replicates that into a :class:`Fanout`."""
+    capacity: int
+    admitted_bits: np.ndarray     # uint64 [K, W]  bit j % 64 of word j // 64 is slot j; bits past capacity are zero
+    colour_bits: np.ndarray       # uint64 [W]     the roster's colour flags when the call was made (a copy)
+    variants: np.ndarray          # uint8, flat; gaps between variants are allowed and unspecified
+    variant_starts: np.ndarray    # int64 [K, 2]   variant c of broadcast k is variants[start : start + size]
+    variant_sizes: np.ndarray     # int64 [K, 2]
+    write_counts: np.ndarray      # int32 [K, 2]
+    write_sizes: np.ndarray       # int32 [K, 2, MAX_WRITES]; entries at or past write_counts are unspecified
+    timing: dict = field(default_factory=dict)   # as Roster.broadcast_many's: kernels_us, end_to_end_us, h2d/d2h_bytes
+
+    def _check(self, k: int, c=0) -> None:
+        if not 0 <= k < len(self.admitted_bits) or c not in (0, 1):
+            raise IndexError(f"no variant ({k}, {c}): {len(self.admitted_bits)} broadcasts, colour 0 or 1")
+
+    def admitted(self, k: int) -> np.ndarray:
+        """bool [capacity]: the slots broadcast ``k`` is delivered to."""
+        self._check(k)
+        return _unpack(self.admitted_bits[k], self.capacity)
+
+    def recipients(self, k: int, c: int) -> np.ndarray:
+        """The admitted slots of broadcast ``k`` whose colour bit is ``c``, ascending."""
+        self._check(k, c)
+        return np.flatnonzero(self.admitted(k) & (_unpack(self.colour_bits, self.capacity) == bool(c)))
+
+    def variant(self, k: int, c: int) -> bytes:
+        """The bytes broadcast ``k`` sends to a listener with colour bit ``c``."""
+        self._check(k, c)
+        at = int(self.variant_starts[k, c])
+        return self.variants[at:at + int(self.variant_sizes[k, c])].tobytes()
+
+    def chunks(self, k: int, c: int) -> list[bytes]:
+        """``variant(k, c)`` as the list of ``write(2)`` chunks the reference would issue."""
+        data = self.variant(k, c)
+        out, at = [], 0
+        for s in self.write_sizes[k, c, :int(self.write_counts[k, c])].tolist():
+            out.append(data[at:at + s])
+            at += s
+        if at != len(data):
+            raise AssertionError(f"variant ({k}, {c}): chunk sizes sum to {at}, the variant holds {len(data)} bytes")
+        return out
+
+    def expand(self) -> Fanout:
+        """The :class:`Fanout` that ``Roster.broadcast_many`` returns for the same call (``timing`` aside), from this
+        plan's own arrays alone: item ``(k, j)`` is ``variant(k, colour of j)`` if slot ``j`` is admitted."""
+        k, cap = len(self.admitted_bits), self.capacity
+        admitted = _unpack(self.admitted_bits, cap).reshape(k * cap)
+        colour = _unpack(self.colour_bits, cap).astype(np.intp)
+        sizes = np.asarray(self.variant_sizes, dtype=np.int64)[:, colour].reshape(k * cap)
+        writes = np.asarray(self.write_counts, dtype=np.int64)[:, colour].reshape(k * cap)
+        out_off = np.zeros(k * cap + 1, dtype=np.int64)
+        np.cumsum(np.where(admitted, sizes, 0), out=out_off[1:])
+        w_off = np.zeros(k * cap + 1, dtype=np.int64)
+        np.cumsum(np.where(admitted, writes, 0), out=w_off[1:])
+        items = np.flatnonzero(admitted)
+        var = 2 * (items // cap) + colour[items % cap]                    # each admitted item's variant, as 2k + c
+        arena = _gather(np.asarray(self.variants, dtype=np.uint8),
+                        np.asarray(self.variant_starts, dtype=np.int64).reshape(2 * k)[var], sizes[items])
+        wsz = _gather(np.asarray(self.write_sizes, dtype=np.int32).reshape(2 * k * MAX_WRITES), var * MAX_WRITES,
+                      writes[items])
+        return Fanout(admitted=admitted, out_offsets=out_off, arena=arena, write_offsets=w_off, write_sizes=wsz,
+                      timing=dict(self.timing), broadcast_offsets=np.arange(k + 1, dtype=np.int64) * cap)
 
 
 # ------------------------------------------------------------------ validation (never touches the device)
@@ -255,6 +356,9 @@ def _load():
         lib.nd_roster_fanout.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int64, P, P, P, P, P, P, P, P, P, P,
                                          ctypes.POINTER(_RosterTiming)]
         lib.nd_roster_fanout.restype = ctypes.c_int
+        lib.nd_roster_plan.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int64, P, P, P, P, P, P, P, P, P, P, P,
+                                       P, ctypes.POINTER(_RosterTiming)]
+        lib.nd_roster_plan.restype = ctypes.c_int
         lib.nd_arena.restype = P
         lib.nd_write_sizes.restype = P
         _LIB = lib
@@ -355,8 +459,10 @@ class Roster:
     ``write_room_except(rm, str, user)`` addresses them (nuts333.c:1401-1415): ``rm`` is a room or ``None`` for every
     room, ``sender`` a slot or ``None``.  The device builds each listener's record from its slot and the broadcast, so a
     call carries K texts and K small tuples; the table travels only in the first call after an :meth:`update`.
+    :meth:`broadcast_many` returns every slot's bytes in an arena (a :class:`Fanout`), :meth:`plan_many` the two variants
+    and an admit bitmap per broadcast (a :class:`Plan`); they may be mixed in any order.
 
-    Building and updating a roster does not touch the device; its first :meth:`broadcast_many` allocates there.  The
+    Building and updating a roster does not touch the device; its first call allocates there.  The
     contract, for every call::
 
         roster.broadcast_many(bs) == broadcast_many([(t, roster.table(rm, s), rm is None, fl, com)
@@ -440,15 +546,16 @@ class Roster:
             t[sender, col("is_sender")] = 1
         return t
 
-    def _prepare(self, broadcasts):
-        """Each (text, rm, sender, force_listen, com_num) checked, packed for nd_roster_fanout: texts, text offsets and
-        lengths, rooms (-1: every room), senders (-1: none), flags (bit 1 force_listen) and commands."""
+    def _checked(self, broadcasts, cells: int, cells_what: str):
+        """Each (text, rm, sender, force_listen, com_num) checked, after the call as a whole (``cells`` per broadcast
+        must stay below 2^31 in all): the texts, their lengths, and the rooms (-1: every room), senders (-1: none),
+        flags (bit 1 force_listen) and commands as lists."""
         if isinstance(broadcasts, (str, bytes, bytearray, np.ndarray)) or not hasattr(broadcasts, "__len__"):
             raise ValueError(f"broadcasts must be a sequence of tuples, not {type(broadcasts).__name__}")
         if len(broadcasts) == 0:
             raise ValueError("empty call: no broadcasts")
-        if len(broadcasts) * self.capacity >= 2**31:
-            raise ValueError(f"{len(broadcasts)} broadcasts to {self.capacity} slots: K x capacity must be below 2^31")
+        if len(broadcasts) * cells >= 2**31:
+            raise ValueError(f"{len(broadcasts)} broadcasts to {self.capacity} slots: {cells_what} must be below 2^31")
         texts, rms, senders, flags, coms = [], [], [], [], []
         for k, b in enumerate(broadcasts):
             if not isinstance(b, tuple) or len(b) != 5:
@@ -466,14 +573,38 @@ class Roster:
         lens = np.fromiter((len(t) for t in texts), dtype=np.int64, count=len(texts))
         if int(lens.sum()) >= 2**31:
             raise ValueError("call text larger than 2 GiB: split it")
-        bound = int((self._room >= 0).sum()) * int((6 * lens + 4).sum())   # only a slot with a room is admitted
-        if bound > MANY_ARENA_CAP:
-            raise ValueError(f"call too large: its arena bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
-                             f"(MANY_ARENA_CAP): split it")
+        return texts, lens, rms, senders, flags, coms
+
+    @staticmethod
+    def _packed(texts, lens, rms, senders, flags, coms):
+        """What _checked returns, packed for nd_roster_fanout / nd_roster_plan: texts, text offsets and lengths, rooms,
+        senders, flags and commands."""
         text_off = np.zeros(len(texts), dtype=np.int32)
         np.cumsum(lens[:-1], out=text_off[1:])
         return (b"".join(texts), text_off, lens.astype(np.int32), np.array(rms, dtype=np.int32),
                 np.array(senders, dtype=np.int32), np.array(flags, dtype=np.uint8), np.array(coms, dtype=np.int32))
+
+    def _prepare(self, broadcasts):
+        """Each (text, rm, sender, force_listen, com_num) checked, packed for nd_roster_fanout: texts, text offsets and
+        lengths, rooms (-1: every room), senders (-1: none), flags (bit 1 force_listen) and commands."""
+        checked = self._checked(broadcasts, self.capacity, "K x capacity")
+        lens = checked[1]
+        bound = int((self._room >= 0).sum()) * int((6 * lens + 4).sum())   # only a slot with a room is admitted
+        if bound > MANY_ARENA_CAP:
+            raise ValueError(f"call too large: its arena bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
+                             f"(MANY_ARENA_CAP): split it")
+        return self._packed(*checked)
+
+    def _prepare_plan(self, broadcasts):
+        """As _prepare, for nd_roster_plan: there is no arena, so its bound does not apply; the variant buffer's does
+        (12 * text bytes + 16 * K at most MANY_ARENA_CAP), and K x bitmap words stays below 2^31."""
+        checked = self._checked(broadcasts, (self.capacity + 63) // 64, "K x ceil(capacity / 64)")
+        lens = checked[1]
+        bound = 12 * int(lens.sum()) + 16 * len(lens)
+        if bound > MANY_ARENA_CAP:
+            raise ValueError(f"call too large: its variant bound (12 x text bytes + 16 x K) is {bound} bytes, the cap "
+                             f"is {MANY_ARENA_CAP} (MANY_ARENA_CAP): split it")
+        return self._packed(*checked)
 
     def broadcast_many(self, broadcasts) -> Fanout:
         """K broadcasts to this roster in one device call: a sequence of ``(text, rm, sender, force_listen, com_num)``
@@ -484,11 +615,7 @@ class Roster:
         self._check_open()
         text, text_off, lens, rm, sender, flags, coms = self._prepare(broadcasts)
         lib = _load()
-        if self._handle is None:
-            h = lib.nd_roster_create(self.capacity)
-            if h < 0:
-                raise RuntimeError(f"cannot create a device roster: {lib.nd_last_error().decode(errors='replace')}")
-            self._handle = h
+        handle = self._device_handle(lib)
         k = len(lens)
         m = k * self.capacity
         admitted = np.zeros(m, dtype=np.uint8)
@@ -496,7 +623,7 @@ class Roster:
         w_off = np.zeros(m + 1, dtype=np.int32)
         tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
         t = _RosterTiming()
-        rc = lib.nd_roster_fanout(self._handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(rm),
+        rc = lib.nd_roster_fanout(handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(rm),
                                   _ptr(sender), _ptr(flags), _ptr(coms), _ptr(self._table) if self._dirty else None,
                                   _ptr(admitted), _ptr(out_off), _ptr(w_off), ctypes.byref(t))
         if rc != 0:
@@ -506,6 +633,50 @@ class Roster:
         r.timing.update(h2d_bytes=t.h2d_bytes, d2h_bytes=t.d2h_bytes)
         r.broadcast_offsets = np.arange(k + 1, dtype=np.int64) * self.capacity
         return r
+
+    def _device_handle(self, lib) -> int:
+        if self._handle is None:
+            h = lib.nd_roster_create(self.capacity)
+            if h < 0:
+                raise RuntimeError(f"cannot create a device roster: {lib.nd_last_error().decode(errors='replace')}")
+            self._handle = h
+        return self._handle
+
+    def plan_many(self, broadcasts) -> Plan:
+        """The delivery plan of K broadcasts to this roster, in one device call: what :meth:`broadcast_many` takes,
+        checked by the same rules, except that no arena bound applies; instead the variant bound, 12 x the call's text
+        bytes + 16 x K, must not exceed MANY_ARENA_CAP.  One upload, one kernel, one download, one synchronise,
+        whatever K and the capacity.  The contract::
+
+            roster.plan_many(bs).expand() == roster.broadcast_many(bs)
+        """
+        self._check_open()
+        text, text_off, lens, rm, sender, flags, coms = self._prepare_plan(broadcasts)
+        lib = _load()
+        handle = self._device_handle(lib)
+        k, words = len(lens), (self.capacity + 63) // 64
+        bits = np.empty((k, words), dtype=np.uint64)
+        vn = np.empty((k, 2), dtype=np.int64)
+        vw = np.empty((k, 2), dtype=np.int32)
+        vwsz = np.empty((k, 2, MAX_WRITES), dtype=np.int32)
+        var = np.empty(12 * len(text) + 16 * k, dtype=np.uint8)
+        tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
+        t = _RosterTiming()
+        rc = lib.nd_roster_plan(handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(rm), _ptr(sender),
+                                _ptr(flags), _ptr(coms), _ptr(self._table) if self._dirty else None, _ptr(bits),
+                                _ptr(vn), _ptr(vw), _ptr(vwsz), _ptr(var), ctypes.byref(t))
+        if rc != 0:
+            raise RuntimeError(f"device plan failed: {lib.nd_last_error().decode(errors='replace')}")
+        self._dirty = False
+        # the variant buffer's layout (var_at / var_stride of fanout.hip): two 4-byte aligned slots per broadcast
+        starts = np.empty((k, 2), dtype=np.int64)
+        starts[:, 0] = 12 * text_off.astype(np.int64) + 16 * np.arange(k, dtype=np.int64)
+        starts[:, 1] = starts[:, 0] + ((6 * lens.astype(np.int64) + 4 + 3) & ~3)
+        return Plan(capacity=self.capacity, admitted_bits=bits,
+                    colour_bits=_pack((self._flags & ROSTER_FLAGS["colour"]) != 0), variants=var,
+                    variant_starts=starts, variant_sizes=vn, write_counts=vw, write_sizes=vwsz,
+                    timing={"kernels_us": t.kernels_us, "end_to_end_us": t.end_to_end_us, "h2d_bytes": t.h2d_bytes,
+                            "d2h_bytes": t.d2h_bytes})
 
     def close(self) -> None:
         """Free the device table; the roster cannot be used afterwards.  Closing twice is harmless."""

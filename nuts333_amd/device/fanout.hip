@@ -16,13 +16,16 @@
 // In broadcast mode every item reads the same text, which each block stages in LDS once.  All four
 // kernels take one argument struct (Args), filled by the host.  nuts_fanout_{measure,emit}_many do K broadcasts in
 // one call, and nuts_roster_{measure,emit} K broadcasts to a roster kept on the device (their sections below).
+// nuts_roster_plan answers the same K broadcasts to a roster in another form, a delivery plan: per broadcast its two
+// variants (colour off, colour on) with their chunk sizes, and one admit bit per slot -- one kernel, no scan, no arena.
 //
 // Hard bounds per item of a text of len < 2000 bytes: 6*len + 4 output bytes (a '\n' with colour
 // on is the costliest input byte, plus the trailing reset) and 16 writes.  The host sizes its buffers
 // by them; pass 2 never writes past the counts pass 1 measured for its own item.
 //
 // The host library keeps one device block, laid out afresh per call into every array the kernels
-// use and the scans' scratch.  C ABI at the bottom; built with
+// use and the scans' scratch; a roster has an allocation of its own, which nd_roster_plan uses alone (one upload, one
+// launch, one download, one synchronise per call).  C ABI at the bottom; built with
 //   hipcc --offload-arch=gfx950 -O3 -shared -fPIC fanout.hip -o _build/libnuts_device.so
 
 #include <hip/hip_runtime.h>
@@ -578,6 +581,80 @@ __device__ void roster_emit(const RosterArgs& a)
 
 static_assert(2 * kMaxWrites <= kBlock, "roster kernels move a broadcast's chunk sizes with one lane each");
 
+// ------------------------------------------------------------------ a delivery plan for a resident roster
+//
+// A listener's output depends on nothing but its colour bit, so a broadcast has two outputs, not `capacity`: what a
+// talker needs back is the two variants with their write(2) chunk sizes, and who is admitted.  nuts_roster_plan gives
+// exactly that, in one launch: no per-item arrays, no scans, no emit, no arena, nothing whose size depends on how many
+// slots were admitted.  One block per (broadcast, 256-slot tile), as nuts_roster_measure:
+//   admit    each lane builds its slot's listener record as roster_measure does; the wave's 64 answers are one word of
+//            the bitmap (__ballot): slot j of broadcast b is bit j % 64 of bits[b * words + j / 64].  Lanes past the
+//            capacity vote false, so the tail bits of a broadcast's last word are zero.
+//   variants the first tile of each broadcast transduces the two variants (stage_variants) and stores their bytes,
+//            chunk sizes and counts, as roster_measure does.  Every block of the kernel reserves their ~26 KB of static
+//            LDS, the admit-only tiles too (roster_measure's comment applies).
+struct PlanArgs {
+    const int32_t* room;         // [capacity] -1: no room
+    const uint8_t* slot;         // [capacity] kLogin | kIgnall | kIgnshout | kColour
+    const uint8_t* text;         // the K texts, packed
+    const int32_t* text_off;     // [k]
+    const int32_t* text_len;     // [k]
+    const int32_t* rm;           // [k] -1: every room (rm_is_null)
+    const int32_t* sender;       // [k] -1: none
+    const uint8_t* flags;        // [k] bit 1 force_listen
+    const int32_t* com_num;      // [k]
+    int k, capacity, tiles;      // tiles per broadcast
+    int words;                   // bitmap words per broadcast: ceil(capacity / 64)
+    int* violations;             // variants past the hard bounds (zeroed by the host's upload)
+    int64_t* vn;                 // [2k] bytes of broadcast b's colour-off / colour-on variant
+    int32_t* vw;                 // [2k] their write(2) counts
+    int32_t* vwsz;               // [2k * kMaxWrites] their chunk sizes
+    uint64_t* bits;              // [k * words] the admit bitmap
+    uint8_t* var;                // broadcast b's variants: var_at(b), var_at(b) + var_stride(len)
+};
+
+__device__ __forceinline__ int64_t var_at(const PlanArgs& a, int b) { return 12 * (int64_t)a.text_off[b] + 16 * (int64_t)b; }
+
+__device__ void roster_plan(const PlanArgs& a)
+{
+    const int b = (int)blockIdx.x / a.tiles, tile = (int)blockIdx.x - b * a.tiles;
+    const int j = tile * kBlock + (int)threadIdx.x;
+    bool in = false;
+    if (j < a.capacity) {
+        const int room = a.room[j], rm = a.rm[b];
+        const uint8_t l = (a.slot[j] & (kLogin | kIgnall | kIgnshout | kColour)) | (room >= 0 ? kHasRoom : 0) |
+                          (rm >= 0 && room == rm ? kSameRoom : 0) | (j == a.sender[b] ? kSender : 0);
+        in = admits(l, rm < 0, (a.flags[b] >> 1) & 1, a.com_num[b]);
+    }
+    const uint64_t word = __ballot(in);          // the wave's 64 slots; every lane of the wave is here
+    const int w = j >> 6;                        // word of this broadcast: a tile holds kBlock / 64 of them
+    if ((threadIdx.x & 63) == 0 && w < a.words) a.bits[(int64_t)b * a.words + w] = word;
+    if (tile == 0) {            // block-uniform: this broadcast's variants, as roster_measure stores them
+        __shared__ uint8_t text[kTextSize];
+        __shared__ uint8_t var[2 * kVarCap];
+        __shared__ int32_t vwsz[2 * kMaxWrites];
+        __shared__ int64_t vn[2];
+        __shared__ int vw[2];
+        stage_variants<true>(a, b, text, var, vwsz, vn, vw);
+        const int len = a.text_len[b];
+        const int64_t cap = 6 * (int64_t)len + 4, stride = var_stride(len);
+        uint8_t* dst = a.var + var_at(a, b);
+        for (int c = 0; c < 2; c++) {
+            const int64_t n = vn[c] < cap ? vn[c] : cap;
+            for (int64_t q = threadIdx.x; q < n; q += kBlock) dst[c * stride + q] = var[c * kVarCap + q];
+            const int nw = vw[c] < kMaxWrites ? vw[c] : kMaxWrites;
+            if ((int)threadIdx.x < nw) a.vwsz[(2 * b + c) * kMaxWrites + threadIdx.x] = vwsz[c * kMaxWrites + threadIdx.x];
+        }
+        if (threadIdx.x < 2) {
+            a.vn[2 * b + threadIdx.x] = vn[threadIdx.x];
+            a.vw[2 * b + threadIdx.x] = vw[threadIdx.x];
+            if (vn[threadIdx.x] > cap || vw[threadIdx.x] > kMaxWrites) atomicAdd(a.violations, 1);
+        }
+    }
+}
+
+static_assert(kBlock % 64 == 0, "roster_plan: a tile is whole bitmap words, one per wave");
+
 }  // namespace
 
 // Stable, unmangled kernel names (they are what rocprofv3 reports).
@@ -589,6 +666,7 @@ extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_measure_many(Ma
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_emit_many(ManyArgs a) { emit_many(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_measure(RosterArgs a) { roster_measure(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_emit(RosterArgs a) { roster_emit(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_plan(PlanArgs a) { roster_plan(a); }
 
 // ------------------------------------------------------------------------------------------ host library
 
@@ -792,6 +870,35 @@ size_t layout_roster_work(uintptr_t base, size_t var_bytes, size_t scan_bytes, R
     take(a.arena, (size_t)a.arena_cap);
     take(a.wsz, (size_t)a.wsz_cap);
     take(*scan, scan_bytes);
+    return at;
+}
+
+// nd_roster_plan's layout of a roster's allocation: the table and the call's inputs as layout_roster() places them
+// (the table's place depends on the capacity alone, so it stays resident across both kinds of call), then the
+// results, violations .. var, next to each other: one download fetches them all at their bound size.
+size_t layout_plan(uintptr_t base, size_t text_bytes, size_t var_bytes, PlanArgs& a)
+{
+    size_t at = 0;
+    auto take = [&](auto*& p, size_t count) {
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + at);
+        at += (count * sizeof(*p) + 255) & ~(size_t)255;
+    };
+    const size_t k = (size_t)a.k;
+    take(a.room, (size_t)a.capacity);
+    take(a.slot, (size_t)a.capacity);
+    take(a.text, text_bytes);
+    take(a.text_off, k);
+    take(a.text_len, k);
+    take(a.rm, k);
+    take(a.sender, k);
+    take(a.flags, k);
+    take(a.com_num, k);
+    take(a.violations, 1);
+    take(a.vn, 2 * k);
+    take(a.vw, 2 * k);
+    take(a.vwsz, 2 * k * kMaxWrites);
+    take(a.bits, k * (size_t)a.words);
+    take(a.var, var_bytes);
     return at;
 }
 
@@ -1192,6 +1299,103 @@ int nd_roster_fanout(int handle, int k, const uint8_t* text, int64_t text_bytes,
         timing->end_to_end_us = (t1 - t0) * 1e-3;
         timing->h2d_bytes = (int64_t)(in_bytes - from);
         timing->d2h_bytes = (int64_t)(res_bytes + (size_t)out_off[m] + (size_t)w_off[m] * sizeof(int32_t));
+    }
+    return 0;
+}
+
+// A delivery plan for K broadcasts to roster `handle`: inputs and table exactly as nd_roster_fanout's.  Outputs (host,
+// caller-allocated), with W = ceil(capacity / 64): bits[k * W], slot j of broadcast b is bit j % 64 of
+// bits[b * W + j / 64] and the bits past the capacity are zero; vn[2k] / vw[2k], the bytes and write(2) counts of
+// broadcast b's colour-off (2b) and colour-on (2b + 1) variant; vwsz[2k * 16] their chunk sizes (entries at or past
+// vw are unspecified); var[12 * text_bytes + 16 * k] the variants' bytes, broadcast b's at 12 * text_off[b] + 16 * b and
+// that plus (6 * text_len[b] + 4 rounded up to 4), the gaps unspecified.  The results lie next to each other after the
+// inputs and are fetched at their bound size, so per call, whatever k and the capacity: one upload (the table in it
+// only when given or when the device allocation is new), one kernel, one download, one synchronise, no memset.  May be
+// mixed with nd_roster_fanout on one roster in any order.  Returns 0, or -1 with nd_last_error() set.
+int nd_roster_plan(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off,
+                   const int32_t* text_len, const int32_t* rm, const int32_t* sender, const uint8_t* flags,
+                   const int32_t* com_num, const uint8_t* table, uint64_t* bits, int64_t* vn, int32_t* vw,
+                   int32_t* vwsz, uint8_t* var, nd_roster_timing* timing)
+{
+    Roster* r = roster_at(handle);
+    if (!r || ensure_ready()) return -1;
+    const int cap = r->capacity, words = (cap + 63) / 64;
+    if (k < 1 || (int64_t)k * cap >= INT32_MAX || text_bytes < 0) {
+        snprintf(g_err, sizeof(g_err), "%d broadcasts to %d slots: need 1 <= k * capacity < 2^31 - 1", k, cap);
+        return -1;
+    }
+    const double t0 = now_ns();
+    hipStream_t st = g.stream;
+    PlanArgs a{};
+    a.k = k;
+    a.capacity = cap;
+    a.tiles = (cap + kBlock - 1) / kBlock;
+    a.words = words;
+    const size_t var_bytes = 12 * (size_t)text_bytes + 16 * (size_t)k;
+    PlanArgs o = a;                  // offsets of every array in the roster's allocation
+    const size_t need = layout_plan(0, (size_t)text_bytes, var_bytes, o);
+    const size_t table_bytes = (uintptr_t)o.text, in_bytes = (uintptr_t)o.violations + sizeof(int);
+    const size_t res_at = (uintptr_t)o.violations, res_bytes = (uintptr_t)o.var + var_bytes - res_at;
+    if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
+    if (table) {
+        memcpy(r->mirror + (uintptr_t)o.room, table, (size_t)cap * sizeof(int32_t));
+        memcpy(r->mirror + (uintptr_t)o.slot, table + (size_t)cap * sizeof(int32_t), (size_t)cap);
+        const int32_t* room = reinterpret_cast<const int32_t*>(r->mirror + (uintptr_t)o.room);
+        r->rooms = std::count_if(room, room + cap, [](int32_t x) { return x >= 0; });
+        r->resident = false;
+    }
+    const size_t cap_d = r->cap_d;
+    if (grow_dev(&r->d, &r->cap_d, need, "roster device allocation")) return -1;
+    if (r->cap_d != cap_d) r->resident = false;
+    layout_plan((uintptr_t)r->d, (size_t)text_bytes, var_bytes, a);
+    if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
+
+    // the inputs packed after the table, as they lie in the device allocation; the table goes with them if it changed
+    uint8_t* h = r->mirror;
+    auto put = [&](const void* at, const void* src, size_t bytes) {
+        if (bytes) memcpy(h + (uintptr_t)at, src, bytes);
+    };
+    put(o.text, text, (size_t)text_bytes);
+    put(o.text_off, text_off, (size_t)k * sizeof(int32_t));
+    put(o.text_len, text_len, (size_t)k * sizeof(int32_t));
+    put(o.rm, rm, (size_t)k * sizeof(int32_t));
+    put(o.sender, sender, (size_t)k * sizeof(int32_t));
+    put(o.flags, flags, (size_t)k);
+    put(o.com_num, com_num, (size_t)k * sizeof(int32_t));
+    *reinterpret_cast<int*>(h + (uintptr_t)o.violations) = 0;
+    const size_t from = r->resident ? table_bytes : 0;
+    ND_CHECK(hipMemcpyAsync(r->d + from, h + from, in_bytes - from, hipMemcpyHostToDevice, st));
+    r->resident = true;
+
+    const dim3 grid((unsigned)(k * a.tiles)), block(kBlock);
+    ND_CHECK(hipEventRecord(g.ev0, st));
+    hipLaunchKernelGGL(nuts_roster_plan, grid, block, 0, st, a);
+    ND_CHECK(hipGetLastError());
+    ND_CHECK(hipEventRecord(g.ev1, st));
+    ND_CHECK(hipMemcpyAsync(gm.res, r->d + res_at, res_bytes, hipMemcpyDeviceToHost, st));
+    ND_CHECK(hipStreamSynchronize(st));
+    const double t1 = now_ns();
+
+    auto res = [&](const void* at) { return gm.res + ((uintptr_t)at - res_at); };
+    const int violations = *reinterpret_cast<const int*>(res(o.violations));
+    if (violations) {
+        snprintf(g_err, sizeof(g_err), "%d variant(s) exceeded the hard output bounds (6*len+4 bytes, %d writes)",
+                 violations, kMaxWrites);
+        return -1;
+    }
+    memcpy(vn, res(o.vn), 2 * (size_t)k * sizeof(int64_t));
+    memcpy(vw, res(o.vw), 2 * (size_t)k * sizeof(int32_t));
+    memcpy(vwsz, res(o.vwsz), 2 * (size_t)k * kMaxWrites * sizeof(int32_t));
+    memcpy(bits, res(o.bits), (size_t)k * words * sizeof(uint64_t));
+    memcpy(var, res(o.var), var_bytes);
+
+    float ms = 0.f;
+    ND_CHECK(hipEventElapsedTime(&ms, g.ev0, g.ev1));
+    if (timing) {
+        timing->kernels_us = (double)ms * 1e3;
+        timing->end_to_end_us = (t1 - t0) * 1e-3;
+        timing->h2d_bytes = (int64_t)(in_bytes - from);
+        timing->d2h_bytes = (int64_t)res_bytes;
     }
     return 0;
 }

@@ -1,7 +1,7 @@
 """What one broadcast's user-space stage costs on the MI355X, done by a kernel that does the work.
 
     python -m nuts333_amd.devpath [--reps R] [--warmup W] [--pathbench-iterations I] [--per-call K[,K...]]
-                                  [--roster K[,K...]]                                  -> one JSON line
+                                  [--roster K[,K...]] [--plan K[,K...]]               -> one JSON line
 
 For N in {10, 100, 1000} listeners, the two texts oracle/pathbench.c times (``say``; ``shout`` carrying ``~OL``/``~RS``)
 and colour all-off / all-on / half, one ``nuts333_amd.device.broadcast`` per repetition (listener 0 is the sender, the
@@ -26,6 +26,12 @@ no CPU fall-back.
 of N slots built once per case, untimed (everyone in room 0, slot 0 the sender), so every broadcast is
 ``(text, 0, 0, 0, COM[text])``.  The same fields as ``per_call``, plus ``h2d_bytes`` uploaded per timed call (no table:
 nothing changed) and ``h2d_bytes_first_call`` (with the table).
+
+``--plan K[,K...]`` adds ``plan``: the same cases and rosters through ``nuts333_amd.device.Roster.plan_many``, which
+returns the two variants and an admit bitmap per broadcast instead of an arena (one kernel, one download, one
+synchronise).  The same fields as ``roster``; ``bytes_out``, ``writes`` and ``recipients`` are counted from the plan
+(admitted slots of each colour x that variant's bytes and writes).  ``python_us`` is the host clock around ``plan_many``
+alone; the first call's ``expand()`` is checked against the CPU restatement and is not timed.
 """
 from __future__ import annotations
 
@@ -110,33 +116,55 @@ def per_call_case(n: int, text: str, colour: str, k: int, reps: int, warmup: int
     return case
 
 
-def roster_case(n: int, text: str, colour: str, k: int, reps: int, warmup: int, pb: dict) -> dict:
-    """K broadcasts of ``text`` per Roster.broadcast_many call, to a roster built once, untimed, in the
-    listeners(n, colour) shape: every slot in room 0, slot 0 the sender."""
+def roster_case(n: int, text: str, colour: str, k: int, reps: int, warmup: int, pb: dict, plan: bool = False) -> dict:
+    """K broadcasts of ``text`` per Roster.broadcast_many call (``plan``: per Roster.plan_many call), to a roster
+    built once, untimed, in the listeners(n, colour) shape: every slot in room 0, slot 0 the sender."""
     with device.Roster(n) as roster:
         roster.update(range(n), room=0, colour=listeners(n, colour)[:, device.LISTENER_FIELDS.index("colour")])
         calls = [(t, 0, 0, 0, COM[text]) for t in line_texts(text, k)]
-        case, first, timed = _timed_calls("roster", n, text, colour, k, lambda: roster.broadcast_many(calls), reps,
-                                          warmup, pb)
+        run = (lambda: roster.plan_many(calls)) if plan else (lambda: roster.broadcast_many(calls))
+        case, first, timed = _timed_calls("plan" if plan else "roster", n, text, colour, k, run, reps, warmup, pb,
+                                          _plan_totals if plan else _fanout_totals)
     h2d = {t["h2d_bytes"] for t in timed}
     if len(h2d) != 1:
-        raise SystemExit(f"devpath: roster {k}, {n}/{text}/{colour}: timed calls uploaded {sorted(h2d)} bytes")
+        raise SystemExit(f"devpath: {'plan' if plan else 'roster'} {k}, {n}/{text}/{colour}: timed calls uploaded "
+                         f"{sorted(h2d)} bytes")
     h2d = h2d.pop()
     return {**case, "h2d_bytes": h2d, "h2d_bytes_per_broadcast": round(h2d / k, 1),
             "h2d_bytes_first_call": first["h2d_bytes"], "d2h_bytes": first["d2h_bytes"]}
 
 
-def _timed_calls(label: str, n: int, text: str, colour: str, k: int, run, reps: int, warmup: int, pb: dict):
+def plan_case(n: int, text: str, colour: str, k: int, reps: int, warmup: int, pb: dict) -> dict:
+    """roster_case through Roster.plan_many."""
+    return roster_case(n, text, colour, k, reps, warmup, pb, plan=True)
+
+
+def _fanout_totals(r: device.Fanout):
+    """A Fanout's arena, admitted items, bytes and writes."""
+    return r.arena.tobytes(), int(r.admitted.sum()), int(r.out_offsets[-1]), int(r.write_offsets[-1])
+
+
+def _plan_totals(p: device.Plan):
+    """The same of a Plan: the arena from expand(), for the check; the counts from the plan itself, admitted slots of
+    each colour x that variant's bytes and writes."""
+    count = np.array([[len(p.recipients(k, c)) for c in (0, 1)] for k in range(len(p.admitted_bits))], dtype=np.int64)
+    return (p.expand().arena.tobytes(), int(count.sum()), int((count * p.variant_sizes).sum()),
+            int((count * p.write_counts).sum()))
+
+
+def _timed_calls(label: str, n: int, text: str, colour: str, k: int, run, reps: int, warmup: int, pb: dict,
+                 totals=_fanout_totals):
     """One case: ``run()`` makes K broadcasts of ``text`` to listeners(n, colour); its first result is checked against
-    the CPU restatement, then it is warmed up and timed.  Returns the case, the first call's timing and the timed
-    calls' timings."""
+    the CPU restatement (``totals``: its arena, admitted items, bytes and writes), then it is warmed up and timed.
+    Returns the case, the first call's timing and the timed calls' timings."""
     texts = line_texts(text, k)
     first = run()
+    arena, admitted, bytes_out, writes = totals(first)
     colour_of = listeners(n, colour)[1:, device.LISTENER_FIELDS.index("colour")].tolist()
     want = b"".join(b"".join(v[c] for c in colour_of)
                     for v in ({0: nuts_path.transduce(t, 0), 1: nuts_path.transduce(t, 1)} for t in texts))
-    if first.arena.tobytes() != want or int(first.admitted.sum()) != k * (n - 1):
-        raise SystemExit(f"devpath: {label} {k}, {n}/{text}/{colour}: device produced {int(first.out_offsets[-1])} "
+    if arena != want or admitted != k * (n - 1) or bytes_out != len(want):
+        raise SystemExit(f"devpath: {label} {k}, {n}/{text}/{colour}: device produced {bytes_out} "
                          f"bytes, the CPU restatement {len(want)}")
     for _ in range(warmup):
         run()
@@ -152,7 +180,7 @@ def _timed_calls(label: str, n: int, text: str, colour: str, k: int, run, reps: 
     ks, es, ps = _stats(kern), _stats(e2e), _stats(py)
     per = lambda s: {q: round(v / k, 3) for q, v in s.items()}
     case = {"n": n, "text": text, "colour": colour, "k": k, "recipients": k * (n - 1),
-            "bytes_out": int(first.out_offsets[-1]), "writes": int(first.write_offsets[-1]),
+            "bytes_out": bytes_out, "writes": writes,
             "kernels_us": ks, "end_to_end_us": es, "python_us": ps,
             "kernels_us_per_broadcast": per(ks), "end_to_end_us_per_broadcast": per(es),
             "python_us_per_broadcast": per(ps),
@@ -171,6 +199,8 @@ def main(argv=None) -> int:
                     help="also time K broadcasts per broadcast_many call, for each K (the per_call cases)")
     ap.add_argument("--roster", type=per_call_counts, default=None, metavar="K[,K...]",
                     help="also time K broadcasts per Roster.broadcast_many call, for each K (the roster cases)")
+    ap.add_argument("--plan", type=per_call_counts, default=None, metavar="K[,K...]",
+                    help="also time K broadcasts per Roster.plan_many call, for each K (the plan cases)")
     a = ap.parse_args(argv)
     if a.reps < 1 or a.warmup < 0:
         ap.error("--reps must be >= 1 and --warmup >= 0")
@@ -235,6 +265,18 @@ def main(argv=None) -> int:
             "roster": [roster_case(n, text, colour, k, a.reps, a.warmup, pb)
                        for n in SIZES for text in TEXTS for colour in COLOURS for k in a.roster],
         }
+    plan = {}
+    if a.plan:
+        plan = {
+            "plan_kernels": ["nuts_roster_plan"],
+            "plan_end_to_end_covers": "packing the K inputs into pinned memory, one H2D (the roster table only in a "
+                                      "call after an update: h2d_bytes_first_call), one kernel, one D2H of the "
+                                      "variants, their chunk sizes and the admit bitmap at their bound size, one "
+                                      "synchronise (python_us adds checking the K tuples, the copies out of pinned "
+                                      "memory and building the Plan; expand() is not timed)",
+            "plan": [plan_case(n, text, colour, k, a.reps, a.warmup, pb)
+                     for n in SIZES for text in TEXTS for colour in COLOURS for k in a.plan],
+        }
     out = {
         "what": "user-space stage of one broadcast (admit predicate + transducer), device vs CPU",
         "device": "gfx950",
@@ -246,6 +288,7 @@ def main(argv=None) -> int:
         "cases": cases,
         **per_call,
         **roster,
+        **plan,
         "wall_s": round(time.perf_counter() - t_start, 1),
     }
     print(json.dumps(out))
