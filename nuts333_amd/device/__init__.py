@@ -16,6 +16,12 @@ addresses them, and the device builds every listener's record, so a call uploads
 listener can get (colour off, colour on) with their ``write(2)`` chunk sizes, and one admit bit per slot -- what a talker
 needs to ``write(fd, variant[colour], size)`` to every admitted slot, in one kernel, one download and one synchronise.
 ``Plan.expand()`` replicates it on the host into the :class:`Fanout` that ``Roster.broadcast_many`` returns.
+``Roster(capacity, review_rooms=R)`` also keeps the review rings of rooms ``0 .. R - 1`` on the device: what
+``record()`` keeps per room (nuts333.c:2062-2070), 15 lines of 202 bytes and a cursor.  ``plan_many(bs, record=...)``
+records broadcasts into their rooms' rings as ``say()`` does, planning first; ``Roster.review_many(rooms)`` returns
+what ``.review`` sends for each room (nuts333.c:5192-5222, without its header and footer): the non-empty lines, oldest
+first, one ``write_user`` each, as a :class:`Review` -- two variants per room with their ``write(2)`` chunk sizes, shaped
+like a :class:`Plan`.  ``Roster.clear_review(rooms)`` is ``clear_revbuff``.
 
 Input is validated before the device is touched (``ValueError``).  The library ``_build/libnuts_device.so`` is built by
 ``__graft_entry__.build()`` where ``hipcc`` exists, and on demand here when it is missing or older than its source.
@@ -49,7 +55,7 @@ COM_SAY, COM_SHOUT, COM_SEMOTE = 3, 4, 7
 KERNELS = ("nuts_fanout_measure_broadcast", "nuts_fanout_emit_broadcast",
            "nuts_fanout_measure_batch", "nuts_fanout_emit_batch",
            "nuts_fanout_measure_many", "nuts_fanout_emit_many",
-           "nuts_roster_measure", "nuts_roster_emit", "nuts_roster_plan")
+           "nuts_roster_measure", "nuts_roster_emit", "nuts_roster_plan", "nuts_roster_record", "nuts_roster_review")
 #: broadcast_many() refuses a call whose arena bound, the sum over its broadcasts of N * max_bytes(len), exceeds this;
 #: Roster.plan_many() one whose variant bound, 12 * text bytes + 16 * K, does
 MANY_ARENA_CAP = 2 << 30
@@ -57,6 +63,23 @@ MANY_ARENA_CAP = 2 << 30
 MAX_CAPACITY = 65536
 #: a room id is None (no room) or an int in [0, ROOM_LIMIT)
 ROOM_LIMIT = 2**31 - 1
+#: NP_REVIEW_LINES, NP_REVIEW_LEN (oracle/nuts_path.h): a room's review ring is 15 lines of 200 + 2 bytes
+REVIEW_LINES, REVIEW_LEN = 15, 200
+#: hard bounds of one stored line (at most 201 bytes) through the transducer, pinned by tests on the CPU restatement:
+#: 201 newlines with colour on are 6 * 201 + 4 = 1210 bytes in writes of 996, 210 and 4
+MAX_LINE_BYTES, MAX_LINE_WRITES = 6 * (REVIEW_LEN + 1) + 4, 3
+#: and of one room's review, 15 such lines: 18,150 bytes per variant in 45 writes
+MAX_REVIEW_BYTES, MAX_REVIEW_WRITES = REVIEW_LINES * MAX_LINE_BYTES, REVIEW_LINES * MAX_LINE_WRITES
+#: a review's variant slot in the download (MAX_REVIEW_BYTES rounded up to 4), as fanout.hip lays it out
+_REVIEW_STRIDE = (MAX_REVIEW_BYTES + 3) & ~3
+#: the most rooms of a Roster that own a review ring.  A ring is 3,030 bytes, so 1024 of them are 3.1 MB that stay
+#: allocated for the roster's life, and a recording call runs one block per ring room, each scanning the call's K
+#: rooms and flags: 1024 x K reads, which at K = 1000 is what nuts_roster_plan itself reads of a 1000-slot roster.  It
+#: is 32 times the rooms the restated talker can hold (MAX_ROOMS of oracle/talker_port.c), so room enough for a
+#: roster that spans many talkers
+MAX_REVIEW_ROOMS = 1024
+#: bit 2 of a broadcast's flags byte: record it (bit 1 is force_listen)
+_RECORD_BIT = 4
 
 
 def max_bytes(text_len: int) -> int:
@@ -195,6 +218,51 @@ class Plan:
                       writes[items])
         return Fanout(admitted=admitted, out_offsets=out_off, arena=arena, write_offsets=w_off, write_sizes=wsz,
                       timing=dict(self.timing), broadcast_offsets=np.arange(k + 1, dtype=np.int64) * cap)
+
+
+@dataclass
+class Review:
+    """What ``.review`` sends for each of Q rooms, between its header and its footer: with ``line_0 ..`` the non-empty
+    lines of the room's ring from the cursor onwards, ``chunks(q, c) == chunks(line_0, c) + chunks(line_1, c) + ...``
+    (one ``write_user`` per line, so with colour on every line ends in a 4-byte reset write of its own) and
+    ``variant(q, c) == b"".join(chunks(q, c))``."""
+    rooms: np.ndarray             # int32 [Q]      the rooms asked for, duplicates included
+    line_counts: np.ndarray       # int32 [Q]      non-empty lines
+    stored: np.ndarray            # uint8 [Q, 15, 202]  the ring's slots, oldest first; a line ends at its first NUL
+    variants: np.ndarray          # uint8, flat; gaps between variants are allowed and unspecified
+    variant_starts: np.ndarray    # int64 [Q, 2]   variant c of room q is variants[start : start + size]
+    variant_sizes: np.ndarray     # int64 [Q, 2]
+    write_counts: np.ndarray      # int32 [Q, 2]
+    write_sizes: np.ndarray       # int32 [Q, 2, MAX_REVIEW_WRITES]; entries at or past write_counts are unspecified
+    sequential: np.ndarray | None = None         # int32 [Q] (line, variant) pairs the device transduced sequentially
+    timing: dict = field(default_factory=dict)   # kernels_us, end_to_end_us, h2d_bytes, d2h_bytes
+
+    def _check(self, q: int, c=0) -> None:
+        if not 0 <= q < len(self.rooms) or c not in (0, 1):
+            raise IndexError(f"no review ({q}, {c}): {len(self.rooms)} rooms, colour 0 or 1")
+
+    def lines(self, q: int) -> list[bytes]:
+        """The non-empty lines stored in room ``q``'s ring, as stored, oldest first."""
+        self._check(q)
+        out = [bytes(row).split(b"\0", 1)[0] for row in np.asarray(self.stored[q], dtype=np.uint8)]
+        return [line for line in out if line]
+
+    def variant(self, q: int, c: int) -> bytes:
+        """The bytes a listener with colour bit ``c`` gets for room ``q``'s lines."""
+        self._check(q, c)
+        at = int(self.variant_starts[q, c])
+        return self.variants[at:at + int(self.variant_sizes[q, c])].tobytes()
+
+    def chunks(self, q: int, c: int) -> list[bytes]:
+        """``variant(q, c)`` as the list of ``write(2)`` chunks the reference would issue."""
+        data = self.variant(q, c)
+        out, at = [], 0
+        for s in self.write_sizes[q, c, :int(self.write_counts[q, c])].tolist():
+            out.append(data[at:at + s])
+            at += s
+        if at != len(data):
+            raise AssertionError(f"review ({q}, {c}): chunk sizes sum to {at}, the variant holds {len(data)} bytes")
+        return out
 
 
 # ------------------------------------------------------------------ validation (never touches the device)
@@ -359,6 +427,13 @@ def _load():
         lib.nd_roster_plan.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int64, P, P, P, P, P, P, P, P, P, P, P,
                                        P, ctypes.POINTER(_RosterTiming)]
         lib.nd_roster_plan.restype = ctypes.c_int
+        lib.nd_roster_plan_record.argtypes = lib.nd_roster_plan.argtypes + [P]
+        lib.nd_roster_plan_record.restype = ctypes.c_int
+        lib.nd_roster_review_rooms.argtypes = [ctypes.c_int, ctypes.c_int]
+        lib.nd_roster_review_rooms.restype = ctypes.c_int
+        lib.nd_roster_review.argtypes = [ctypes.c_int, ctypes.c_int, P, P, P, P, P, P, P, P, P,
+                                         ctypes.POINTER(_RosterTiming)]
+        lib.nd_roster_review.restype = ctypes.c_int
         lib.nd_arena.restype = P
         lib.nd_write_sizes.restype = P
         _LIB = lib
@@ -460,7 +535,9 @@ class Roster:
     room, ``sender`` a slot or ``None``.  The device builds each listener's record from its slot and the broadcast, so a
     call carries K texts and K small tuples; the table travels only in the first call after an :meth:`update`.
     :meth:`broadcast_many` returns every slot's bytes in an arena (a :class:`Fanout`), :meth:`plan_many` the two variants
-    and an admit bitmap per broadcast (a :class:`Plan`); they may be mixed in any order.
+    and an admit bitmap per broadcast (a :class:`Plan`); they may be mixed in any order.  With ``review_rooms=R`` rooms
+    ``0 .. R - 1`` each own a review ring on the device, empty at first: ``plan_many(bs, record=...)`` records into them,
+    :meth:`review_many` reads them, :meth:`clear_review` empties them.  ``review_rooms=0`` is a roster without rings.
 
     Building and updating a roster does not touch the device; its first call allocates there.  The
     contract, for every call::
@@ -469,11 +546,18 @@ class Roster:
                                                      for t, rm, s, fl, com in bs])
     """
 
-    def __init__(self, capacity: int):
+    def __init__(self, capacity: int, review_rooms: int = 0):
         if (not isinstance(capacity, (int, np.integer)) or isinstance(capacity, (bool, np.bool_))
                 or not 1 <= int(capacity) <= MAX_CAPACITY):
             raise ValueError(f"roster capacity must be an int in [1, {MAX_CAPACITY}], not {capacity!r}")
+        if (not isinstance(review_rooms, (int, np.integer)) or isinstance(review_rooms, (bool, np.bool_))
+                or not 0 <= int(review_rooms) <= MAX_REVIEW_ROOMS):
+            raise ValueError(f"review_rooms must be an int in [0, {MAX_REVIEW_ROOMS}], not {review_rooms!r}")
         self.capacity = int(capacity)
+        self.review_rooms = int(review_rooms)
+        # rooms whose ring clear_review() emptied since the last recording or reviewing call: one byte per ring room
+        self._clear = np.zeros(self.review_rooms, dtype=np.uint8)
+        self._clear_pending = False
         # the host mirror, as nd_roster_fanout takes it: `capacity` int32 rooms (-1: none), then `capacity` flag bytes
         self._table = np.zeros(5 * self.capacity, dtype=np.uint8)
         self._room = self._table[:4 * self.capacity].view(np.int32)
@@ -595,16 +679,39 @@ class Roster:
                              f"(MANY_ARENA_CAP): split it")
         return self._packed(*checked)
 
-    def _prepare_plan(self, broadcasts):
+    def _prepare_plan(self, broadcasts, record=None):
         """As _prepare, for nd_roster_plan: there is no arena, so its bound does not apply; the variant buffer's does
-        (12 * text bytes + 16 * K at most MANY_ARENA_CAP), and K x bitmap words stays below 2^31."""
+        (12 * text bytes + 16 * K at most MANY_ARENA_CAP), and K x bitmap words stays below 2^31.  ``record`` (None, one
+        bool, or K of them) sets bit 2 of the flags of the broadcasts to record, each of which needs a ring room."""
         checked = self._checked(broadcasts, (self.capacity + 63) // 64, "K x ceil(capacity / 64)")
         lens = checked[1]
         bound = 12 * int(lens.sum()) + 16 * len(lens)
         if bound > MANY_ARENA_CAP:
             raise ValueError(f"call too large: its variant bound (12 x text bytes + 16 x K) is {bound} bytes, the cap "
                              f"is {MANY_ARENA_CAP} (MANY_ARENA_CAP): split it")
-        return self._packed(*checked)
+        packed = self._packed(*checked)
+        if record is None:
+            return packed
+        k, rms, flags = len(lens), checked[2], packed[5]
+        if isinstance(record, (bool, np.bool_)):
+            record = [record] * k
+        elif isinstance(record, (str, bytes, bytearray)) or not hasattr(record, "__len__"):
+            raise ValueError(f"record must be None, a bool or a sequence of one bool per broadcast, not {record!r}")
+        if len(record) != k:
+            raise ValueError(f"record: {len(record)} values for {k} broadcasts")
+        for b, (on, rm) in enumerate(zip(record, rms)):
+            if not isinstance(on, (bool, np.bool_)):
+                raise ValueError(f"record must hold bools, not {on!r} (broadcast {b})")
+            if not on:
+                continue
+            if self.review_rooms == 0:
+                raise ValueError(f"broadcast {b}: it is to be recorded, but the roster has no review rings "
+                                 f"(review_rooms is 0)")
+            if not 0 <= rm < self.review_rooms:
+                raise ValueError(f"broadcast {b}: it is to be recorded, but room {None if rm < 0 else rm} has no review "
+                                 f"ring (the ring rooms are 0 .. {self.review_rooms - 1})")
+            flags[b] |= _RECORD_BIT
+        return packed
 
     def broadcast_many(self, broadcasts) -> Fanout:
         """K broadcasts to this roster in one device call: a sequence of ``(text, rm, sender, force_listen, com_num)``
@@ -639,19 +746,37 @@ class Roster:
             h = lib.nd_roster_create(self.capacity)
             if h < 0:
                 raise RuntimeError(f"cannot create a device roster: {lib.nd_last_error().decode(errors='replace')}")
+            if self.review_rooms and lib.nd_roster_review_rooms(h, self.review_rooms) != 0:
+                lib.nd_roster_destroy(h)
+                raise RuntimeError(f"cannot create a device roster: {lib.nd_last_error().decode(errors='replace')}")
             self._handle = h
         return self._handle
 
-    def plan_many(self, broadcasts) -> Plan:
+    def _pending_clear(self):
+        """The clear bytes to send with a recording or reviewing call: a copy, or None when nothing is pending."""
+        return self._clear.copy() if self._clear_pending else None
+
+    def _clear_sent(self) -> None:
+        self._clear[:] = 0
+        self._clear_pending = False
+
+    def plan_many(self, broadcasts, record=None) -> Plan:
         """The delivery plan of K broadcasts to this roster, in one device call: what :meth:`broadcast_many` takes,
         checked by the same rules, except that no arena bound applies; instead the variant bound, 12 x the call's text
         bytes + 16 x K, must not exceed MANY_ARENA_CAP.  One upload, one kernel, one download, one synchronise,
         whatever K and the capacity.  The contract::
 
             roster.plan_many(bs).expand() == roster.broadcast_many(bs)
-        """
+
+        ``record`` is None, one bool for every broadcast, or K bools.  A broadcast with a true ``record`` is also
+        stored in the review ring of its room ``rm``, which must be a ring room, as ``say()`` does: planned, then
+        ``record(rm, text)`` -- ``np_record`` for k = 0 .. K - 1 in order, within a call and across calls.  A text of
+        200 bytes or more is stored cut to 200 with a forced newline; an empty text stores an empty line.  The plan is
+        the one returned without ``record``; a call that records nothing enqueues nothing more, one that does adds
+        one kernel after the plan's, and no copy or synchronise."""
         self._check_open()
-        text, text_off, lens, rm, sender, flags, coms = self._prepare_plan(broadcasts)
+        text, text_off, lens, rm, sender, flags, coms = self._prepare_plan(broadcasts, record)
+        recording = bool((flags & _RECORD_BIT).any())
         lib = _load()
         handle = self._device_handle(lib)
         k, words = len(lens), (self.capacity + 63) // 64
@@ -662,12 +787,19 @@ class Roster:
         var = np.empty(12 * len(text) + 16 * k, dtype=np.uint8)
         tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
         t = _RosterTiming()
-        rc = lib.nd_roster_plan(handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(rm), _ptr(sender),
-                                _ptr(flags), _ptr(coms), _ptr(self._table) if self._dirty else None, _ptr(bits),
-                                _ptr(vn), _ptr(vw), _ptr(vwsz), _ptr(var), ctypes.byref(t))
+        args = (handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(rm), _ptr(sender), _ptr(flags),
+                _ptr(coms), _ptr(self._table) if self._dirty else None, _ptr(bits), _ptr(vn), _ptr(vw), _ptr(vwsz),
+                _ptr(var), ctypes.byref(t))
+        if recording:                       # the pending clears go first, with the same upload
+            clear = self._pending_clear()
+            rc = lib.nd_roster_plan_record(*args, _ptr(clear) if clear is not None else None)
+        else:
+            rc = lib.nd_roster_plan(*args)
         if rc != 0:
             raise RuntimeError(f"device plan failed: {lib.nd_last_error().decode(errors='replace')}")
         self._dirty = False
+        if recording:
+            self._clear_sent()
         # the variant buffer's layout (var_at / var_stride of fanout.hip): two 4-byte aligned slots per broadcast
         starts = np.empty((k, 2), dtype=np.int64)
         starts[:, 0] = 12 * text_off.astype(np.int64) + 16 * np.arange(k, dtype=np.int64)
@@ -678,8 +810,67 @@ class Roster:
                     timing={"kernels_us": t.kernels_us, "end_to_end_us": t.end_to_end_us, "h2d_bytes": t.h2d_bytes,
                             "d2h_bytes": t.d2h_bytes})
 
+    def _ring_room(self, v) -> int:
+        if (not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_))
+                or not 0 <= int(v) < self.review_rooms):
+            raise ValueError(f"room {v!r} has no review ring: " +
+                             (f"the ring rooms are 0 .. {self.review_rooms - 1}" if self.review_rooms else
+                              "the roster has none (review_rooms is 0)"))
+        return int(v)
+
+    def _ring_rooms(self, rooms, what: str) -> np.ndarray:
+        if isinstance(rooms, (str, bytes, bytearray)) or not hasattr(rooms, "__len__"):
+            raise ValueError(f"{what} must be a sequence of ring rooms, not {rooms!r}")
+        return np.array([self._ring_room(v) for v in rooms], dtype=np.int32)
+
+    def clear_review(self, rooms) -> None:
+        """``clear_revbuff`` (as ``.revclr`` uses it) for ``rooms``, a ring room or a sequence of them: their lines
+        become empty and their cursor 0.  Like :meth:`update` it does not touch the device; it takes effect before the
+        records and reviews of the next recording or reviewing call, in the order the caller issued them."""
+        self._check_open()
+        idx = self._ring_rooms([rooms] if isinstance(rooms, (int, np.integer)) else rooms, "rooms")
+        if len(idx):
+            self._clear[idx] = 1
+            self._clear_pending = True
+
+    def review_many(self, rooms) -> Review:
+        """What ``.review`` sends for each of ``rooms``, a non-empty sequence of ring rooms (duplicates allowed), as a
+        :class:`Review`.  One upload, one kernel, one download, one synchronise, whatever the number of rooms and
+        whatever the rings hold: every variant is fetched at its bound size, about 40 KB per room.  Anything else raises
+        ``ValueError`` before the device is touched."""
+        self._check_open()
+        idx = self._ring_rooms(rooms, "rooms")
+        q = len(idx)
+        if q == 0:
+            raise ValueError("empty call: no rooms to review")
+        if 2 * q * _REVIEW_STRIDE > MANY_ARENA_CAP:
+            raise ValueError(f"call too large: {q} rooms x 2 x {_REVIEW_STRIDE} bytes exceed the cap of {MANY_ARENA_CAP} "
+                             f"(MANY_ARENA_CAP): split it")
+        lib = _load()
+        handle = self._device_handle(lib)
+        counts = np.empty(q, dtype=np.int32)
+        seq = np.empty(q, dtype=np.int32)
+        vn = np.empty((q, 2), dtype=np.int32)
+        vw = np.empty((q, 2), dtype=np.int32)
+        vwsz = np.empty((q, 2, MAX_REVIEW_WRITES), dtype=np.int32)
+        stored = np.empty((q, REVIEW_LINES, REVIEW_LEN + 2), dtype=np.uint8)
+        var = np.empty(2 * q * _REVIEW_STRIDE, dtype=np.uint8)
+        clear = self._pending_clear()
+        t = _RosterTiming()
+        rc = lib.nd_roster_review(handle, q, _ptr(idx), _ptr(clear) if clear is not None else None, _ptr(counts),
+                                  _ptr(seq), _ptr(vn), _ptr(vw), _ptr(vwsz), _ptr(stored), _ptr(var), ctypes.byref(t))
+        if rc != 0:
+            raise RuntimeError(f"device review failed: {lib.nd_last_error().decode(errors='replace')}")
+        self._clear_sent()
+        starts = (np.arange(2 * q, dtype=np.int64) * _REVIEW_STRIDE).reshape(q, 2)
+        return Review(rooms=idx, line_counts=counts, stored=stored, variants=var, variant_starts=starts,
+                      variant_sizes=vn.astype(np.int64), write_counts=vw, write_sizes=vwsz, sequential=seq,
+                      timing={"kernels_us": t.kernels_us, "end_to_end_us": t.end_to_end_us, "h2d_bytes": t.h2d_bytes,
+                              "d2h_bytes": t.d2h_bytes})
+
     def close(self) -> None:
-        """Free the device table; the roster cannot be used afterwards.  Closing twice is harmless."""
+        """Free the device table and the review rings; the roster cannot be used afterwards.  Closing twice is
+        harmless."""
         if self._handle is not None and _LIB is not None:
             _LIB.nd_roster_destroy(self._handle)
         self._handle = None

@@ -18,6 +18,9 @@
 // one call, and nuts_roster_{measure,emit} K broadcasts to a roster kept on the device (their sections below).
 // nuts_roster_plan answers the same K broadcasts to a roster in another form, a delivery plan: per broadcast its two
 // variants (colour off, colour on) with their chunk sizes, and one admit bit per slot -- one kernel, no scan, no arena.
+// A roster can also own review rings, the device's record() / .review (nuts333.c:2062-2070, 5192-5222): nuts_roster_record
+// stores a plan call's recorded broadcasts in their rooms' rings, nuts_roster_review transduces the rings of a list of
+// rooms, one wave per (line, colour variant), parallel over the line's bytes (their section below).
 //
 // Hard bounds per item of a text of len < 2000 bytes: 6*len + 4 output bytes (a '\n' with colour
 // on is the costliest input byte, plus the trailing reset) and 16 writes.  The host sizes its buffers
@@ -655,6 +658,302 @@ __device__ void roster_plan(const PlanArgs& a)
 
 static_assert(kBlock % 64 == 0, "roster_plan: a tile is whole bitmap words, one per wave");
 
+// ------------------------------------------------------------------ review rings of a resident roster
+//
+// record() keeps the last 15 lines said in a room in a ring of 15 x 202 bytes with a cursor, revline (nuts333.c:2062-2070;
+// np_record of oracle/nuts_path.c): strncpy of 200 bytes -- the text cut there, or padded with zeros --, '\n' at byte 200,
+// NUL at byte 201, cursor + 1.  A stored line is the C string in its slot: a text below 200 bytes as it is, a longer one
+// cut to 200 with the forced '\n' (201 bytes); an empty text stores an empty line.  .review (nuts333.c:5192-5222) sends
+// the non-empty lines from the cursor onwards, oldest first, one write_user each.  A roster owns the rings of rooms
+// 0 .. review_rooms - 1 and their cursors, in a device allocation of their own that never moves.
+//   record   nuts_roster_record, after nuts_roster_plan of a call that records, on that call's uploaded inputs: one block
+//            per ring room.  Wave 0 scans the K (flags, rm) pairs 64 at a time; a broadcast's rank among its room's recorded
+//            broadcasts of the call is the running count plus the popcount of the ballot below its lane, so the order is
+//            the call's own and the same on every run.  Only the last min(count, 15) survive, rank r in slot
+//            (revline + r) % 15; the block copies them with byte stores and the cursor advances by count.
+//   review   nuts_roster_review, one block per requested room: the ring staged in LDS oldest line first, then one wave
+//            per (line, colour variant).  A byte's output depends on the bytes i-3 .. i+2 alone unless the staging buffer
+//            flushes in mid-line, and it cannot while the line's output stays at or below kOutBuff - 6 = 994 bytes (the
+//            flush test is pos > 994): lane l expands bytes 4l .. 4l+3, a 64-lane scan gives their offsets, the stores are
+//            scattered.  A longer output (colour on, more than 165 newlines) takes the sequential transduce<>, a lane
+//            per such (line, variant), after the waves.
+//            The line outputs are built in LDS and copied out next to each other, so a variant is contiguous.
+//   clear    clear_revbuff (nuts333.c: rev[i][0] = 0 for every line, revline = 0) travels as a byte per ring room with
+//            the next record or review call.  A room whose byte is set is never read in that call: record starts it from
+//            an empty ring, review shows it empty, and extra blocks past the requested rooms store the zeros.
+constexpr int kRevLines = 15;                              // nuts333.h:37 REVIEW_LINES
+constexpr int kRevLen = 200;                               // nuts333.h:39 REVIEW_LEN
+constexpr int kRevSlot = kRevLen + 2;                      // one line of a ring
+constexpr int kRevRing = kRevLines * kRevSlot;             // 3030 bytes per room
+constexpr int kRevLineCap = 6 * (kRevLen + 1) + 4;         // 1210: 201 newlines with colour on, and the reset
+constexpr int kRevLineStride = (kRevLineCap + 1 + 3) & ~3;   // a line's output in LDS, and a spare byte after it
+constexpr int kRevLineWrites = 3;                          // 996 + 210 + 4 for that line
+constexpr int kRevVarCap = kRevLines * kRevLineCap;        // 18150 bytes per variant
+constexpr int kRevVarStride = (kRevVarCap + 3) & ~3;
+constexpr int kRevWrites = kRevLines * kRevLineWrites;     // 45 writes per variant
+constexpr int kRevTasks = 2 * kRevLines;                   // (line, variant) pairs of a room
+constexpr int kWaveLimit = kOutBuff - 6;                   // a line output up to here never flushes in mid-line
+constexpr uint8_t kRecordBit = 4;                          // bit 2 of a broadcast's flags byte: record it
+constexpr int kMaxReviewRooms = 1024;
+
+struct RecordArgs {
+    const uint8_t* text;         // the plan call's inputs, as PlanArgs has them
+    const int32_t* text_off;     // [k]
+    const int32_t* text_len;     // [k]
+    const int32_t* rm;           // [k]
+    const uint8_t* flags;        // [k] bit 2: record this broadcast into the ring of room rm
+    const uint8_t* clear;        // [review_rooms] non-zero: clear the room's ring first; nullptr: none
+    int k, review_rooms;
+    uint8_t* rings;              // [review_rooms * kRevRing]
+    int32_t* revline;            // [review_rooms]
+};
+
+__device__ void roster_record(const RecordArgs& a)
+{
+    __shared__ int s_surv[kRevLines];   // the broadcast of rank r, at r % 15, for the last 15 ranks
+    __shared__ int s_count, s_base;
+    const int room = (int)blockIdx.x;
+    const bool cleared = a.clear && a.clear[room];
+    if (threadIdx.x < 64) {             // wave 0: every lane of it is here
+        const int lane = (int)threadIdx.x;
+        int count = 0;
+        for (int b0 = 0; b0 < a.k; b0 += 64) {
+            const int b = b0 + lane;
+            const bool hit = b < a.k && (a.flags[b] & kRecordBit) && a.rm[b] == room;
+            const uint64_t word = __ballot(hit);
+            const int n = __popcll(word);
+            const int rank = count + __popcll(word & ((1ull << lane) - 1));
+            // the last 15 of this tile are distinct mod 15; a later tile's stores follow these in program order
+            if (hit && rank >= count + n - kRevLines) s_surv[rank % kRevLines] = b;
+            count += n;
+        }
+        if (lane == 0) {
+            s_count = count;
+            s_base = cleared ? 0 : (int)((uint32_t)a.revline[room] % kRevLines);   // read by the thread that stores it
+        }
+    }
+    __syncthreads();
+    const int count = s_count, base = s_base;
+    if (!count && !cleared) return;
+    uint8_t* ring = a.rings + (size_t)room * kRevRing;
+    const int nsurv = count < kRevLines ? count : kRevLines;
+    const int first = (count - nsurv) % kRevLines;      // rank of the oldest survivor, mod 15
+    if (cleared && threadIdx.x < kRevLines) {           // empty the slots no survivor lands in
+        const int d = ((int)threadIdx.x - base - first + 2 * kRevLines) % kRevLines;
+        if (d >= nsurv) ring[threadIdx.x * kRevSlot] = 0;
+    }
+    for (int idx = (int)threadIdx.x; idx < nsurv * kRevSlot; idx += kBlock) {
+        const int j = idx / kRevSlot, i = idx - j * kRevSlot;
+        const int r = (first + j) % kRevLines;
+        const int b = s_surv[r];
+        uint8_t v = 0;
+        if (i < kRevLen) {
+            if (i < a.text_len[b]) v = a.text[a.text_off[b] + i];
+        } else if (i == kRevLen) {
+            v = '\n';
+        }
+        ring[((base + r) % kRevLines) * kRevSlot + i] = v;
+    }
+    if (threadIdx.x == 0) a.revline[room] = (base + count % kRevLines) % kRevLines;
+}
+
+struct ReviewArgs {
+    uint8_t* rings;              // [review_rooms * kRevRing]
+    int32_t* revline;            // [review_rooms]
+    const int32_t* rooms;        // [q] the rooms to review, duplicates allowed
+    const uint8_t* clear;        // as RecordArgs.clear
+    int q, review_rooms;
+    int* violations;             // lines past the hard bounds (zeroed by the host's upload)
+    int32_t* line_count;         // [q] non-empty lines
+    int32_t* sequential;         // [q] (line, variant) pairs that took the sequential transducer
+    int32_t* vn;                 // [2q] bytes of room q's colour-off / colour-on review
+    int32_t* vw;                 // [2q] their write(2) counts
+    int32_t* vwsz;               // [2q * kRevWrites] their chunk sizes
+    uint8_t* lines;              // [q * kRevRing] the ring's slots, oldest first
+    uint8_t* var;                // [2q * kRevVarStride] the reviews' bytes
+};
+
+// The output of line byte `ch` given the byte before it, p1, and the one after it, n1 (0 outside the line; no line byte
+// is 0): its length, and its bytes packed into *v, first byte lowest.  Valid while no flush fires in mid-line.
+//   consumed: a command tilde stands one or two bytes before it.  A tilde is a command tilde iff it is not preceded by
+//   '/' and a colour command follows (own: which one, for a tilde; else -1); the two letters of a command are never
+//   '~', '/' or '\n', so a command tilde is never itself consumed.  A '/' is dropped iff a '~' follows.
+//   (transduce<>, without its position.)
+__device__ __forceinline__ int expand_byte(uint8_t p1, uint8_t ch, uint8_t n1, bool consumed, int own, bool colour,
+                                           uint64_t* v)
+{
+    *v = ch;
+    if (ch == 0 || consumed) return 0;
+    if (ch == '\n') {
+        if (colour) {
+            *v = 27ull | (uint64_t)'[' << 8 | (uint64_t)'0' << 16 | (uint64_t)'m' << 24 | (uint64_t)'\n' << 32 |
+                 (uint64_t)'\r' << 40;
+            return 6;
+        }
+        *v = (uint64_t)'\n' | (uint64_t)'\r' << 8;
+        return 2;
+    }
+    if (ch == '/' && n1 == '~') return 0;
+    if (ch == '~' && p1 != '/' && own >= 0) {
+        if (!colour) return 0;
+        const uint64_t a0 = (uint8_t)kColArg[own][0], a1 = (uint8_t)kColArg[own][1];
+        *v = 27ull | (uint64_t)'[' << 8 | a0 << 16 | (a1 ? a1 << 24 | (uint64_t)'m' << 32 : (uint64_t)'m' << 24);
+        return a1 ? 5 : 4;
+    }
+    return 1;
+}
+
+__device__ void roster_review(const ReviewArgs& a)
+{
+    if ((int)blockIdx.x >= a.q) {       // the blocks past the requested rooms store the pending clears, a room per lane
+        const int room = ((int)blockIdx.x - a.q) * kBlock + (int)threadIdx.x;
+        if (a.clear && room < a.review_rooms && a.clear[room]) {
+            for (int i = 0; i < kRevLines; i++) a.rings[(size_t)room * kRevRing + i * kRevSlot] = 0;
+            a.revline[room] = 0;
+        }
+        return;
+    }
+    __shared__ uint8_t s_line[kRevLines][kRevSlot + 2];       // the ring, oldest line first
+    __shared__ uint8_t s_out[kRevTasks][kRevLineStride];      // task 2 * line + colour: its output
+    __shared__ int32_t s_wsz[kRevTasks][kRevLineWrites + 1];  // its chunk sizes
+    __shared__ int s_n[kRevTasks], s_w[kRevTasks], s_off[kRevTasks], s_woff[kRevTasks];
+    __shared__ int s_len[kRevLines], s_seq;
+    const int q = (int)blockIdx.x, room = a.rooms[q];
+    const bool cleared = a.clear && a.clear[room];   // then the ring is not read: other blocks are storing its zeros
+    const int rev = cleared ? 0 : (int)((uint32_t)a.revline[room] % kRevLines);
+    const uint8_t* ring = a.rings + (size_t)room * kRevRing;
+    for (int idx = (int)threadIdx.x; idx < kRevRing; idx += kBlock) {
+        const int i = idx / kRevSlot, j = idx - i * kRevSlot;
+        const uint8_t v = cleared ? 0 : ring[((rev + i) % kRevLines) * kRevSlot + j];
+        s_line[i][j] = v;
+        a.lines[(size_t)q * kRevRing + idx] = v;
+    }
+    if (threadIdx.x == 0) s_seq = 0;
+    __syncthreads();
+
+    const int lane = (int)threadIdx.x & 63;
+    for (int t = (int)threadIdx.x >> 6; t < kRevTasks; t += kBlock / 64) {     // wave-uniform
+        const int i = t >> 1;
+        const bool colour = (t & 1) != 0;
+        const uint8_t* s = s_line[i];
+        // this lane's bytes 4 * lane .. + 3 at w[3 .. 6], with three bytes before and two after; 0 outside the slot
+        uint8_t w[9];
+#pragma unroll
+        for (int x = 0; x < 9; x++) {
+            const int at = 4 * lane - 3 + x;
+            w[x] = at >= 0 && at < kRevSlot ? s[at] : 0;
+        }
+        // the line ends at its first NUL (byte 201 is one, at the latest): blank everything from there on
+        const int nul = w[3] == 0 ? 0 : w[4] == 0 ? 1 : w[5] == 0 ? 2 : w[6] == 0 ? 3 : 4;
+        const uint64_t ends = __ballot(nul < 4);
+        const int end_lane = __ffsll((unsigned long long)ends) - 1;          // >= 0: lane 50 holds byte 201
+        const int len = 4 * end_lane + __shfl(nul, end_lane, 64);
+#pragma unroll
+        for (int x = 0; x < 9; x++)
+            if (4 * lane - 3 + x >= len) w[x] = 0;
+        // cmd[x]: the colour command of a command tilde at w[x + 1], the bytes 4 * lane - 2 .. + 3; else -1
+        // (key[x]: the two letters after a tilde that is not preceded by '/', as one number)
+        int cmd[6], key[6];
+        bool tilde = false;
+#pragma unroll
+        for (int x = 0; x < 6; x++) {
+            cmd[x] = -1;
+            key[x] = w[x + 1] == '~' && w[x] != '/' ? w[x + 2] << 8 | w[x + 3] : -1;
+            tilde |= key[x] >= 0;
+        }
+        if (tilde) {
+#pragma unroll 1
+            for (int c = 0; c < kNumCols; c++) {
+                const int pair = (uint8_t)kColCom[c][0] << 8 | (uint8_t)kColCom[c][1];
+#pragma unroll
+                for (int x = 0; x < 6; x++) cmd[x] = key[x] == pair ? c : cmd[x];
+            }
+        }
+        int n[4], mine = 0;
+        uint64_t v[4];
+#pragma unroll
+        for (int x = 0; x < 4; x++) {
+            n[x] = expand_byte(w[x + 2], w[x + 3], w[x + 4], cmd[x] >= 0 || cmd[x + 1] >= 0, cmd[x + 2], colour, &v[x]);
+            mine += n[x];
+        }
+        int incl = mine;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int y = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += y;
+        }
+        const int body = __shfl(incl, 63, 64);
+        uint8_t* out = s_out[t];
+        if (len == 0) {                 // .review skips an empty line: not even a reset
+            if (lane == 0) {
+                s_n[t] = 0;
+                s_w[t] = 0;
+            }
+        } else if (body <= kWaveLimit) {
+            int at = incl - mine;
+#pragma unroll
+            for (int x = 0; x < 4; x++) {
+#pragma unroll
+                for (int y = 0; y < 6; y++)      // without a branch: what is not output goes to the row's spare byte
+                    out[y < n[x] ? at + y : kRevLineStride - 1] = (uint8_t)(v[x] >> (8 * y));
+                at += n[x];
+            }
+            if (colour && lane < 4) out[body + lane] = lane == 0 ? 27 : lane == 1 ? '[' : lane == 2 ? '0' : 'm';
+            if (lane == 0) {            // one write of the body if there is one, then the reset in a write of its own
+                int nw = 0;
+                if (body) s_wsz[t][nw++] = body;
+                if (colour) s_wsz[t][nw++] = 4;
+                s_n[t] = body + (colour ? 4 : 0);
+                s_w[t] = nw;
+            }
+        } else if (lane == 0) {
+            s_n[t] = -1;                // a flush in mid-line: left to the sequential transducer below
+        }
+        if (lane == 0 && !colour) s_len[i] = len;
+    }
+    __syncthreads();
+    if (threadIdx.x < kRevTasks && s_n[threadIdx.x] < 0) {   // the sequential transducer knows the flush rule; a lane each
+        const int t = (int)threadIdx.x;
+        Sink<true> k{s_out[t], s_wsz[t], kRevLineCap, kRevLineWrites};
+        transduce(s_line[t >> 1], s_len[t >> 1], (t & 1) != 0, k);
+        if (k.n > kRevLineCap || k.writes > kRevLineWrites) atomicAdd(a.violations, 1);
+        s_n[t] = k.n < kRevLineCap ? (int)k.n : kRevLineCap;
+        s_w[t] = k.writes < kRevLineWrites ? k.writes : kRevLineWrites;
+        atomicAdd(&s_seq, 1);
+    }
+    __syncthreads();
+    if (threadIdx.x < kRevTasks) {      // each task's place in its variant: after the earlier lines' outputs
+        const int t = (int)threadIdx.x;
+        int off = 0, woff = 0;
+        for (int j = t & 1; j < t; j += 2) {
+            off += s_n[j];
+            woff += s_w[j];
+        }
+        s_off[t] = off;
+        s_woff[t] = woff;
+        if (t >= kRevTasks - 2) {
+            a.vn[2 * q + (t & 1)] = off + s_n[t];
+            a.vw[2 * q + (t & 1)] = woff + s_w[t];
+        }
+    }
+    if (threadIdx.x == 64) {
+        int lines = 0;
+        for (int i = 0; i < kRevLines; i++) lines += s_len[i] > 0;
+        a.line_count[q] = lines;
+        a.sequential[q] = s_seq;
+    }
+    __syncthreads();
+    for (int t = 0; t < kRevTasks; t++) {
+        const int var = 2 * q + (t & 1);
+        uint8_t* dst = a.var + (size_t)var * kRevVarStride + s_off[t];
+        for (int j = (int)threadIdx.x; j < s_n[t]; j += kBlock) dst[j] = s_out[t][j];
+        if ((int)threadIdx.x < s_w[t]) a.vwsz[var * kRevWrites + s_woff[t] + (int)threadIdx.x] = s_wsz[t][threadIdx.x];
+    }
+}
+
+static_assert(kBlock / 64 >= 1 && 64 * 4 >= kRevSlot, "roster_review: a wave holds a whole slot, four bytes per lane");
+static_assert(kBlock >= kRevTasks + 64 && kBlock >= kRevLines, "roster_review / roster_record: a lane per task, per line");
+
 }  // namespace
 
 // Stable, unmangled kernel names (they are what rocprofv3 reports).
@@ -667,6 +966,8 @@ extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_emit_many(ManyA
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_measure(RosterArgs a) { roster_measure(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_emit(RosterArgs a) { roster_emit(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_plan(PlanArgs a) { roster_plan(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_record(RecordArgs a) { roster_record(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_review(ReviewArgs a) { roster_review(a); }
 
 // ------------------------------------------------------------------------------------------ host library
 
@@ -827,8 +1128,14 @@ struct Roster {
     uint8_t* d = nullptr;
     uint8_t* mirror = nullptr;
     size_t cap_d = 0, cap_mirror = 0;
+    int review_rooms = 0;        // rooms 0 .. review_rooms - 1 own a review ring
+    uint8_t* rings = nullptr;    // the rings, then the cursors: an allocation of its own, made on first use, never moved
 };
 Roster g_rosters[kMaxRosters];
+
+// Where the cursors start in r.rings, and the allocation's size.
+size_t revline_at(const Roster& r) { return ((size_t)r.review_rooms * kRevRing + 255) & ~(size_t)255; }
+size_t rings_bytes(const Roster& r) { return revline_at(r) + (size_t)r.review_rooms * sizeof(int32_t); }
 
 size_t layout_roster(uintptr_t base, size_t text_bytes, RosterArgs& a)
 {
@@ -876,7 +1183,8 @@ size_t layout_roster_work(uintptr_t base, size_t var_bytes, size_t scan_bytes, R
 // nd_roster_plan's layout of a roster's allocation: the table and the call's inputs as layout_roster() places them
 // (the table's place depends on the capacity alone, so it stays resident across both kinds of call), then the
 // results, violations .. var, next to each other: one download fetches them all at their bound size.
-size_t layout_plan(uintptr_t base, size_t text_bytes, size_t var_bytes, PlanArgs& a)
+size_t layout_plan(uintptr_t base, size_t text_bytes, size_t var_bytes, PlanArgs& a, size_t clear_bytes,
+                   const uint8_t** clear)
 {
     size_t at = 0;
     auto take = [&](auto*& p, size_t count) {
@@ -893,6 +1201,7 @@ size_t layout_plan(uintptr_t base, size_t text_bytes, size_t var_bytes, PlanArgs
     take(a.sender, k);
     take(a.flags, k);
     take(a.com_num, k);
+    take(*clear, clear_bytes);      // a recording call's pending clears; no bytes, and no change of layout, without them
     take(a.violations, 1);
     take(a.vn, 2 * k);
     take(a.vw, 2 * k);
@@ -900,6 +1209,50 @@ size_t layout_plan(uintptr_t base, size_t text_bytes, size_t var_bytes, PlanArgs
     take(a.bits, k * (size_t)a.words);
     take(a.var, var_bytes);
     return at;
+}
+
+// nd_roster_review's layout of a roster's allocation: the table where layout_roster() places it (it stays resident and
+// is not uploaded), the call's inputs ending with violations, then the results next to each other.
+size_t layout_review(uintptr_t base, int capacity, size_t clear_bytes, ReviewArgs& a)
+{
+    size_t at = 0;
+    auto take = [&](auto*& p, size_t count) {
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + at);
+        at += (count * sizeof(*p) + 255) & ~(size_t)255;
+    };
+    const size_t q = (size_t)a.q;
+    const int32_t* room;
+    const uint8_t* slot;
+    take(room, (size_t)capacity);
+    take(slot, (size_t)capacity);
+    take(a.rooms, q);
+    take(a.clear, clear_bytes);
+    take(a.violations, 1);
+    take(a.line_count, q);
+    take(a.sequential, q);
+    take(a.vn, 2 * q);
+    take(a.vw, 2 * q);
+    take(a.vwsz, 2 * q * kRevWrites);
+    take(a.lines, q * kRevRing);
+    take(a.var, 2 * q * kRevVarStride);
+    return at;
+}
+
+// The roster's rings, made and zeroed in the stream on first use.
+int ensure_rings(Roster& r, hipStream_t st)
+{
+    if (r.rings) return 0;
+    if (r.review_rooms < 1) {
+        snprintf(g_err, sizeof(g_err), "the roster has no review rings");
+        return -1;
+    }
+    hipError_t e = hipMalloc((void**)&r.rings, rings_bytes(r));
+    if (e != hipSuccess) {
+        r.rings = nullptr;
+        return fail("review rings", e);
+    }
+    ND_CHECK(hipMemsetAsync(r.rings, 0, rings_bytes(r), st));
+    return 0;
 }
 
 // Grow r's pinned mirror to want bytes, keeping its first keep bytes (the table); a new mirror starts with every slot
@@ -1181,6 +1534,7 @@ int nd_roster_destroy(int handle)
     Roster* r = roster_at(handle);
     if (!r) return -1;
     if (r->d) (void)hipFree(r->d);
+    if (r->rings) (void)hipFree(r->rings);
     if (r->mirror) (void)hipHostFree(r->mirror);
     *r = Roster{};
     return 0;
@@ -1312,13 +1666,19 @@ int nd_roster_fanout(int handle, int k, const uint8_t* text, int64_t text_bytes,
 // inputs and are fetched at their bound size, so per call, whatever k and the capacity: one upload (the table in it
 // only when given or when the device allocation is new), one kernel, one download, one synchronise, no memset.  May be
 // mixed with nd_roster_fanout on one roster in any order.  Returns 0, or -1 with nd_last_error() set.
-int nd_roster_plan(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off,
-                   const int32_t* text_len, const int32_t* rm, const int32_t* sender, const uint8_t* flags,
-                   const int32_t* com_num, const uint8_t* table, uint64_t* bits, int64_t* vn, int32_t* vw,
-                   int32_t* vwsz, uint8_t* var, nd_roster_timing* timing)
+//
+// record (nd_roster_plan_record): also store every broadcast whose flags byte has bit 2 set in the review ring of its
+// room rm, in the call's order, as np_record does (the caller has checked 0 <= rm < review_rooms for them), after
+// clearing the rings of the rooms whose byte in clear (NULL: none, else review_rooms bytes) is non-zero.  That adds
+// nuts_roster_record after nuts_roster_plan in the stream and the clear bytes to the upload: no copy, no synchronise.
+static int plan_call(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off,
+                     const int32_t* text_len, const int32_t* rm, const int32_t* sender, const uint8_t* flags,
+                     const int32_t* com_num, const uint8_t* table, uint64_t* bits, int64_t* vn, int32_t* vw,
+                     int32_t* vwsz, uint8_t* var, nd_roster_timing* timing, bool record, const uint8_t* clear)
 {
     Roster* r = roster_at(handle);
     if (!r || ensure_ready()) return -1;
+    if (record && ensure_rings(*r, g.stream)) return -1;
     const int cap = r->capacity, words = (cap + 63) / 64;
     if (k < 1 || (int64_t)k * cap >= INT32_MAX || text_bytes < 0) {
         snprintf(g_err, sizeof(g_err), "%d broadcasts to %d slots: need 1 <= k * capacity < 2^31 - 1", k, cap);
@@ -1333,7 +1693,9 @@ int nd_roster_plan(int handle, int k, const uint8_t* text, int64_t text_bytes, c
     a.words = words;
     const size_t var_bytes = 12 * (size_t)text_bytes + 16 * (size_t)k;
     PlanArgs o = a;                  // offsets of every array in the roster's allocation
-    const size_t need = layout_plan(0, (size_t)text_bytes, var_bytes, o);
+    const size_t clear_bytes = record && clear ? (size_t)r->review_rooms : 0;
+    const uint8_t *o_clear = nullptr, *d_clear = nullptr;
+    const size_t need = layout_plan(0, (size_t)text_bytes, var_bytes, o, clear_bytes, &o_clear);
     const size_t table_bytes = (uintptr_t)o.text, in_bytes = (uintptr_t)o.violations + sizeof(int);
     const size_t res_at = (uintptr_t)o.violations, res_bytes = (uintptr_t)o.var + var_bytes - res_at;
     if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
@@ -1347,7 +1709,7 @@ int nd_roster_plan(int handle, int k, const uint8_t* text, int64_t text_bytes, c
     const size_t cap_d = r->cap_d;
     if (grow_dev(&r->d, &r->cap_d, need, "roster device allocation")) return -1;
     if (r->cap_d != cap_d) r->resident = false;
-    layout_plan((uintptr_t)r->d, (size_t)text_bytes, var_bytes, a);
+    layout_plan((uintptr_t)r->d, (size_t)text_bytes, var_bytes, a, clear_bytes, &d_clear);
     if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
 
     // the inputs packed after the table, as they lie in the device allocation; the table goes with them if it changed
@@ -1362,6 +1724,7 @@ int nd_roster_plan(int handle, int k, const uint8_t* text, int64_t text_bytes, c
     put(o.sender, sender, (size_t)k * sizeof(int32_t));
     put(o.flags, flags, (size_t)k);
     put(o.com_num, com_num, (size_t)k * sizeof(int32_t));
+    put(o_clear, clear, clear_bytes);
     *reinterpret_cast<int*>(h + (uintptr_t)o.violations) = 0;
     const size_t from = r->resident ? table_bytes : 0;
     ND_CHECK(hipMemcpyAsync(r->d + from, h + from, in_bytes - from, hipMemcpyHostToDevice, st));
@@ -1371,6 +1734,12 @@ int nd_roster_plan(int handle, int k, const uint8_t* text, int64_t text_bytes, c
     ND_CHECK(hipEventRecord(g.ev0, st));
     hipLaunchKernelGGL(nuts_roster_plan, grid, block, 0, st, a);
     ND_CHECK(hipGetLastError());
+    if (record) {                    // on the inputs just uploaded; the rings are touched by this stream alone
+        RecordArgs rec{a.text, a.text_off, a.text_len, a.rm, a.flags, clear_bytes ? d_clear : nullptr, k,
+                       r->review_rooms, r->rings, reinterpret_cast<int32_t*>(r->rings + revline_at(*r))};
+        hipLaunchKernelGGL(nuts_roster_record, dim3((unsigned)r->review_rooms), block, 0, st, rec);
+        ND_CHECK(hipGetLastError());
+    }
     ND_CHECK(hipEventRecord(g.ev1, st));
     ND_CHECK(hipMemcpyAsync(gm.res, r->d + res_at, res_bytes, hipMemcpyDeviceToHost, st));
     ND_CHECK(hipStreamSynchronize(st));
@@ -1395,6 +1764,126 @@ int nd_roster_plan(int handle, int k, const uint8_t* text, int64_t text_bytes, c
         timing->kernels_us = (double)ms * 1e3;
         timing->end_to_end_us = (t1 - t0) * 1e-3;
         timing->h2d_bytes = (int64_t)(in_bytes - from);
+        timing->d2h_bytes = (int64_t)res_bytes;
+    }
+    return 0;
+}
+
+// The plan alone (plan_call above): bit 2 of flags[] is not looked at, and nothing touches the rings.
+int nd_roster_plan(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off,
+                   const int32_t* text_len, const int32_t* rm, const int32_t* sender, const uint8_t* flags,
+                   const int32_t* com_num, const uint8_t* table, uint64_t* bits, int64_t* vn, int32_t* vw,
+                   int32_t* vwsz, uint8_t* var, nd_roster_timing* timing)
+{
+    return plan_call(handle, k, text, text_bytes, text_off, text_len, rm, sender, flags, com_num, table, bits, vn, vw,
+                     vwsz, var, timing, false, nullptr);
+}
+
+// The plan, then the records (plan_call above): nd_roster_plan's arguments, and clear.  The roster needs review rings.
+int nd_roster_plan_record(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off,
+                          const int32_t* text_len, const int32_t* rm, const int32_t* sender, const uint8_t* flags,
+                          const int32_t* com_num, const uint8_t* table, uint64_t* bits, int64_t* vn, int32_t* vw,
+                          int32_t* vwsz, uint8_t* var, nd_roster_timing* timing, const uint8_t* clear)
+{
+    return plan_call(handle, k, text, text_bytes, text_off, text_len, rm, sender, flags, com_num, table, bits, vn, vw,
+                     vwsz, var, timing, true, clear);
+}
+
+// Give roster `handle` review rings for rooms 0 .. n - 1 (0 .. 1024), all empty; before its first recording or
+// reviewing call, which allocates them.  Returns 0, or -1 with nd_last_error() set.
+int nd_roster_review_rooms(int handle, int n)
+{
+    Roster* r = roster_at(handle);
+    if (!r) return -1;
+    if (n < 0 || n > kMaxReviewRooms || r->rings) {
+        snprintf(g_err, sizeof(g_err), "review rooms %d outside 0 .. %d, or the rings are already in use", n,
+                 kMaxReviewRooms);
+        return -1;
+    }
+    r->review_rooms = n;
+    return 0;
+}
+
+// What .review sends for each of the q rooms[] (ring rooms, duplicates allowed; the caller has checked them), after
+// clearing the rings that clear marks, as nd_roster_plan_record does.  Outputs (host, caller-allocated): line_count[q]
+// the non-empty lines; sequential[q] the (line, variant) pairs that took the sequential transducer; vn[2q] / vw[2q] the
+// bytes and write(2) counts of room i's colour-off (2i) and colour-on (2i + 1) review; vwsz[2q * 45] their chunk sizes
+// (entries at or past vw unspecified); lines[q * 15 * 202] the ring's slots, oldest first; var[2q * 18152] the reviews'
+// bytes, variant v at v * 18152, the rest unspecified.  Per call, whatever q and whatever the rings hold: one upload,
+// one kernel, one download at the bound size, one synchronise.  Returns 0, or -1 with nd_last_error() set.
+int nd_roster_review(int handle, int q, const int32_t* rooms, const uint8_t* clear, int32_t* line_count,
+                     int32_t* sequential, int32_t* vn, int32_t* vw, int32_t* vwsz, uint8_t* lines, uint8_t* var,
+                     nd_roster_timing* timing)
+{
+    Roster* r = roster_at(handle);
+    if (!r || ensure_ready()) return -1;
+    if (q < 1 || (int64_t)q * 2 * kRevVarStride >= INT32_MAX) {
+        snprintf(g_err, sizeof(g_err), "%d rooms to review: need 1 <= q and 2 * q * %d < 2^31 - 1", q, kRevVarStride);
+        return -1;
+    }
+    if (ensure_rings(*r, g.stream)) return -1;
+    for (int i = 0; i < q; i++)
+        if (rooms[i] < 0 || rooms[i] >= r->review_rooms) {
+            snprintf(g_err, sizeof(g_err), "room %d has no review ring", rooms[i]);
+            return -1;
+        }
+    const double t0 = now_ns();
+    hipStream_t st = g.stream;
+    ReviewArgs a{};
+    a.q = q;
+    a.review_rooms = r->review_rooms;
+    const size_t clear_bytes = clear ? (size_t)r->review_rooms : 0;
+    ReviewArgs o = a;                // offsets of every array in the roster's allocation
+    const size_t need = layout_review(0, r->capacity, clear_bytes, o);
+    const size_t table_bytes = (uintptr_t)o.rooms, in_bytes = (uintptr_t)o.violations + sizeof(int);
+    const size_t res_at = (uintptr_t)o.violations, res_bytes = need - res_at;
+    if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
+    const size_t cap_d = r->cap_d;
+    if (grow_dev(&r->d, &r->cap_d, need, "roster device allocation")) return -1;
+    if (r->cap_d != cap_d) r->resident = false;      // the next broadcast call refills the table from the mirror
+    layout_review((uintptr_t)r->d, r->capacity, clear_bytes, a);
+    if (!clear) a.clear = nullptr;
+    a.rings = r->rings;
+    a.revline = reinterpret_cast<int32_t*>(r->rings + revline_at(*r));
+    if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
+
+    uint8_t* h = r->mirror;
+    memcpy(h + (uintptr_t)o.rooms, rooms, (size_t)q * sizeof(int32_t));
+    if (clear) memcpy(h + (uintptr_t)o.clear, clear, clear_bytes);
+    *reinterpret_cast<int*>(h + (uintptr_t)o.violations) = 0;
+    ND_CHECK(hipMemcpyAsync(r->d + table_bytes, h + table_bytes, in_bytes - table_bytes, hipMemcpyHostToDevice, st));
+
+    // one block per requested room, then the blocks that store the pending clears, a ring room per lane
+    const unsigned grid = (unsigned)q + (clear ? (unsigned)((r->review_rooms + kBlock - 1) / kBlock) : 0u);
+    ND_CHECK(hipEventRecord(g.ev0, st));
+    hipLaunchKernelGGL(nuts_roster_review, dim3(grid), dim3(kBlock), 0, st, a);
+    ND_CHECK(hipGetLastError());
+    ND_CHECK(hipEventRecord(g.ev1, st));
+    ND_CHECK(hipMemcpyAsync(gm.res, r->d + res_at, res_bytes, hipMemcpyDeviceToHost, st));
+    ND_CHECK(hipStreamSynchronize(st));
+    const double t1 = now_ns();
+
+    auto res = [&](const void* at) { return gm.res + ((uintptr_t)at - res_at); };
+    const int violations = *reinterpret_cast<const int*>(res(o.violations));
+    if (violations) {
+        snprintf(g_err, sizeof(g_err), "%d line(s) exceeded the hard output bounds (%d bytes, %d writes)", violations,
+                 kRevLineCap, kRevLineWrites);
+        return -1;
+    }
+    memcpy(line_count, res(o.line_count), (size_t)q * sizeof(int32_t));
+    memcpy(sequential, res(o.sequential), (size_t)q * sizeof(int32_t));
+    memcpy(vn, res(o.vn), 2 * (size_t)q * sizeof(int32_t));
+    memcpy(vw, res(o.vw), 2 * (size_t)q * sizeof(int32_t));
+    memcpy(vwsz, res(o.vwsz), 2 * (size_t)q * kRevWrites * sizeof(int32_t));
+    memcpy(lines, res(o.lines), (size_t)q * kRevRing);
+    memcpy(var, res(o.var), 2 * (size_t)q * kRevVarStride);
+
+    float ms = 0.f;
+    ND_CHECK(hipEventElapsedTime(&ms, g.ev0, g.ev1));
+    if (timing) {
+        timing->kernels_us = (double)ms * 1e3;
+        timing->end_to_end_us = (t1 - t0) * 1e-3;
+        timing->h2d_bytes = (int64_t)(in_bytes - table_bytes);
         timing->d2h_bytes = (int64_t)res_bytes;
     }
     return 0;

@@ -1,7 +1,7 @@
 """What one broadcast's user-space stage costs on the MI355X, done by a kernel that does the work.
 
     python -m nuts333_amd.devpath [--reps R] [--warmup W] [--pathbench-iterations I] [--per-call K[,K...]]
-                                  [--roster K[,K...]] [--plan K[,K...]]               -> one JSON line
+                                  [--roster K[,K...]] [--plan K[,K...]] [--review Q[,Q...]]   -> one JSON line
 
 For N in {10, 100, 1000} listeners, the two texts oracle/pathbench.c times (``say``; ``shout`` carrying ``~OL``/``~RS``)
 and colour all-off / all-on / half, one ``nuts333_amd.device.broadcast`` per repetition (listener 0 is the sender, the
@@ -32,10 +32,19 @@ returns the two variants and an admit bitmap per broadcast instead of an arena (
 synchronise).  The same fields as ``roster``; ``bytes_out``, ``writes`` and ``recipients`` are counted from the plan
 (admitted slots of each colour x that variant's bytes and writes).  ``python_us`` is the host clock around ``plan_many``
 alone; the first call's ``expand()`` is checked against the CPU restatement and is not timed.
+
+``--review Q[,Q...]`` adds ``review``: a 1000-slot roster with max(Q) review rings, every ring filled by recording 15
+``say`` lines through ``plan_many(record=True)``, then ``Roster.review_many`` of Q rooms per call, for each Q:
+``kernels_us``, ``end_to_end_us``, ``python_us``, the copy volume, and the CPU doing the same work, timed in the same
+command (``cpu_us``: ``np_transduce`` of the restatement over the same 15 x Q lines, both colours, one ctypes call each;
+``cpu_derived_us``: 15 x Q x pathbench's two per-line ``say`` figures, without the calls).  The first review of each Q
+is checked against the restatement.  And ``record``: ``plan_many`` of K = 100 to that roster with and without
+``record``, alternating in one run.
 """
 from __future__ import annotations
 
 import argparse
+import ctypes
 import json
 import statistics
 import subprocess
@@ -190,6 +199,79 @@ def _timed_calls(label: str, n: int, text: str, colour: str, k: int, run, reps: 
     return case, first.timing, timed
 
 
+def review_cases(qs: list[int], reps: int, warmup: int, pb: dict) -> dict:
+    """The ``review`` section: review_many of Q rooms for each Q, and plan_many of K = 100 with and without record."""
+    rings = max(qs)
+    n, k = 1000, 100
+    lib = nuts_path.lib()
+    with device.Roster(n, review_rooms=rings) as roster:
+        roster.update(range(n), room=0)
+        lines = line_texts("say", device.REVIEW_LINES * rings)
+        roster.plan_many([(t, i // device.REVIEW_LINES, 0, 0, COM["say"]) for i, t in enumerate(lines)], record=True)
+        cases = []
+        for q in qs:
+            rooms = list(range(q))
+            mine = lines[:device.REVIEW_LINES * q]
+            first = roster.review_many(rooms)
+            for room in rooms:
+                own = mine[device.REVIEW_LINES * room:device.REVIEW_LINES * (room + 1)]
+                for c in (0, 1):
+                    if first.variant(room, c) != b"".join(nuts_path.transduce(t, c) for t in own):
+                        raise SystemExit(f"devpath: review {q}: room {room}, colour {c} differs from the CPU restatement")
+            for _ in range(warmup):
+                roster.review_many(rooms)
+            kern, e2e, py, copies = [], [], [], set()
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                r = roster.review_many(rooms)
+                py.append((time.perf_counter() - t0) * 1e6)
+                kern.append(r.timing["kernels_us"])
+                e2e.append(r.timing["end_to_end_us"])
+                copies.add((r.timing["h2d_bytes"], r.timing["d2h_bytes"]))
+            if len(copies) != 1:
+                raise SystemExit(f"devpath: review {q}: timed calls copied {sorted(copies)} bytes")
+            out = ctypes.create_string_buffer(device.MAX_LINE_BYTES)
+            cpu = []
+            for _ in range(warmup + reps):
+                t0 = time.perf_counter()
+                for t in mine:
+                    lib.np_transduce(t, 0, out, len(out))
+                    lib.np_transduce(t, 1, out, len(out))
+                cpu.append((time.perf_counter() - t0) * 1e6)
+            cpu = _stats(cpu[warmup:])
+            es = _stats(e2e)
+            derived = len(mine) * (pb["transduce_say_colour_off_ns"] + pb["transduce_say_colour_on_ns"]) / 1e3
+            h2d, d2h = copies.pop()
+            cases.append({"q": q, "lines": len(mine), "bytes_out": int(first.variant_sizes.sum()),
+                          "writes": int(first.write_counts.sum()), "sequential": int(first.sequential.sum()),
+                          "kernels_us": _stats(kern), "end_to_end_us": es, "python_us": _stats(py),
+                          "h2d_bytes": h2d, "d2h_bytes": d2h, "cpu_us": cpu, "cpu_derived_us": round(derived, 3),
+                          "end_to_end_over_cpu": round(es["median"] / cpu["median"], 2),
+                          "end_to_end_over_cpu_derived": round(es["median"] / derived, 2)})
+        calls = [(t, 0, 0, 0, COM["say"]) for t in line_texts("say", k)]
+        timed = {False: {"kernels_us": [], "end_to_end_us": [], "python_us": []},
+                 True: {"kernels_us": [], "end_to_end_us": [], "python_us": []}}
+        for i in range(2 * (warmup + reps)):
+            rec = bool(i % 2)
+            t0 = time.perf_counter()
+            p = roster.plan_many(calls, record=rec or None)
+            if i >= 2 * warmup:
+                timed[rec]["python_us"].append((time.perf_counter() - t0) * 1e6)
+                timed[rec]["kernels_us"].append(p.timing["kernels_us"])
+                timed[rec]["end_to_end_us"].append(p.timing["end_to_end_us"])
+        record = {"n": n, "k": k, "text": "say", "room": 0,
+                  "without_record": {f: _stats(v) for f, v in timed[False].items()},
+                  "with_record": {f: _stats(v) for f, v in timed[True].items()}}
+        record["record_adds_us"] = {f: round(record["with_record"][f]["median"] - record["without_record"][f]["median"], 2)
+                                    for f in ("kernels_us", "end_to_end_us", "python_us")}
+    return {"review_kernels": ["nuts_roster_review"], "record_kernels": ["nuts_roster_plan", "nuts_roster_record"],
+            "review_end_to_end_covers": "one H2D of the Q rooms, one kernel, one D2H of the rings' lines, both variants "
+                                        "and their chunk sizes at their bound size (about 40 KB per room), one "
+                                        "synchronise (python_us adds checking the rooms, the copies out of pinned "
+                                        "memory and building the Review)",
+            "review_rings": rings, "review": cases, "record": record}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=2000, help="timed broadcasts per case (default 2000)")
@@ -201,9 +283,14 @@ def main(argv=None) -> int:
                     help="also time K broadcasts per Roster.broadcast_many call, for each K (the roster cases)")
     ap.add_argument("--plan", type=per_call_counts, default=None, metavar="K[,K...]",
                     help="also time K broadcasts per Roster.plan_many call, for each K (the plan cases)")
+    ap.add_argument("--review", type=per_call_counts, default=None, metavar="Q[,Q...]",
+                    help="also time Roster.review_many of Q rooms per call, for each Q, and what recording adds to "
+                         "plan_many (the review section)")
     a = ap.parse_args(argv)
     if a.reps < 1 or a.warmup < 0:
         ap.error("--reps must be >= 1 and --warmup >= 0")
+    if a.review and max(a.review) > device.MAX_REVIEW_ROOMS:
+        ap.error(f"argument --review: a roster has at most {device.MAX_REVIEW_ROOMS} review rings")
     if not PATHBENCH.exists():
         nuts_path.build()
     try:
@@ -277,6 +364,7 @@ def main(argv=None) -> int:
             "plan": [plan_case(n, text, colour, k, a.reps, a.warmup, pb)
                      for n in SIZES for text in TEXTS for colour in COLOURS for k in a.plan],
         }
+    review = review_cases(a.review, a.reps, a.warmup, pb) if a.review else {}
     out = {
         "what": "user-space stage of one broadcast (admit predicate + transducer), device vs CPU",
         "device": "gfx950",
@@ -289,6 +377,7 @@ def main(argv=None) -> int:
         **per_call,
         **roster,
         **plan,
+        **review,
         "wall_s": round(time.perf_counter() - t_start, 1),
     }
     print(json.dumps(out))
