@@ -22,6 +22,10 @@ records broadcasts into their rooms' rings as ``say()`` does, planning first; ``
 what ``.review`` sends for each room (nuts333.c:5192-5222, without its header and footer): the non-empty lines, oldest
 first, one ``write_user`` each, as a :class:`Review` -- two variants per room with their ``write(2)`` chunk sizes, shaped
 like a :class:`Plan`.  ``Roster.clear_review(rooms)`` is ``clear_revbuff``.
+``Roster.update(name=, vis=, muzzled=, command_mode=)`` keeps what the speech commands read of a speaker, and
+``Roster.speak_many(events)`` does for K ``(slot, com, inpstr, word_count)`` events what ``say()``, ``shout()``,
+``emote()`` and ``semote()`` do (nuts333.c:4062-4226): the muzzle, "Say what?" and swearing checks, the verb, the
+invisible speaker's name, the two composed texts, and their plans -- a :class:`Speech`.
 
 Input is validated before the device is touched (``ValueError``).  The library ``_build/libnuts_device.so`` is built by
 ``__graft_entry__.build()`` where ``hipcc`` exists, and on demand here when it is missing or older than its source.
@@ -50,12 +54,28 @@ MAX_WRITES = 16
 LISTENER_FIELDS = ("login", "has_room", "same_room", "ignall", "ignshout", "is_sender", "colour")
 #: NP_NUM_COMMANDS (oracle/nuts_path.h enum np_com)
 NUM_COMMANDS = 92
-COM_SAY, COM_SHOUT, COM_SEMOTE = 3, 4, 7
+COM_SAY, COM_SHOUT, COM_EMOTE, COM_SEMOTE = 3, 4, 6, 7
 #: the kernels of fanout.hip, as rocprofv3 names them (the scans are rocPRIM's)
 KERNELS = ("nuts_fanout_measure_broadcast", "nuts_fanout_emit_broadcast",
            "nuts_fanout_measure_batch", "nuts_fanout_emit_batch",
            "nuts_fanout_measure_many", "nuts_fanout_emit_many",
-           "nuts_roster_measure", "nuts_roster_emit", "nuts_roster_plan", "nuts_roster_record", "nuts_roster_review")
+           "nuts_roster_measure", "nuts_roster_emit", "nuts_roster_plan", "nuts_roster_record", "nuts_roster_review",
+           "nuts_roster_speak", "nuts_roster_speak_plan")
+#: NP_ARR_SIZE (nuts333.h:19): the input line a speech command receives is at most 999 bytes
+ARR_SIZE = 1000
+#: USER_NAME_LEN (nuts333.h:23) and invisname (nuts333.h:150), the name an invisible speaker is shown by
+USER_NAME_LEN, INVISNAME = 12, b"A presence"
+#: the talker's word_count is at most MAX_WORDS (nuts333.h:17)
+MAX_WORDS = 10
+#: what became of a speech event (Speech.outcome): spoken, or one of the three notices to the speaker alone
+SPOKEN, MUZZLED, NOTHING, SWEARING = 0, 1, 2, 3
+#: a text composed from ``inpstr`` is at most ``len(inpstr) + COMPOSED_EXTRA`` bytes (pinned by a host test) ...
+COMPOSED_EXTRA = 32
+#: ... and its slot in a speech call's text buffer is ``len(inpstr) + _SPEAK_SLACK`` wide (kSpeakSlack of fanout.hip):
+#: the longest notice, 35 bytes, has to fit beside an empty inpstr
+_SPEAK_SLACK = 36
+#: the flags byte of a slot's speaker state, as fanout.hip reads it
+SPEECH_FLAGS = {"vis": 1, "muzzled": 2, "command_mode": 4}
 #: broadcast_many() refuses a call whose arena bound, the sum over its broadcasts of N * max_bytes(len), exceeds this;
 #: Roster.plan_many() one whose variant bound, 12 * text bytes + 16 * K, does
 MANY_ARENA_CAP = 2 << 30
@@ -265,6 +285,39 @@ class Review:
         return out
 
 
+@dataclass
+class Speech:
+    """What ``say()``, ``shout()``, ``emote()`` and ``semote()`` write for K speech events (``Roster.speak_many``).
+    ``outcome[k]`` is SPOKEN, MUZZLED, NOTHING or SWEARING.  ``room`` plans the line the room (or every room) gets, K
+    entries: ``room.admitted(k)`` is empty and both variants are 0 bytes in 0 writes when event ``k`` was not spoken.
+    ``reply`` plans what the speaker alone gets -- the echo of a say or a shout, or the notice: ``reply.admitted(k)`` is
+    the speaker's slot alone when there is a reply, else empty with zero sizes (a spoken emote or semote has none: no
+    ``write_user`` call at all, which is not the 4-byte reset of an empty text).  Both are ordinary plans and share one
+    variant buffer.  ``line(k)`` / ``reply_text(k)`` are the composed texts before the transducer."""
+    outcome: np.ndarray           # int8 [K]
+    room: Plan
+    reply: Plan
+    texts: np.ndarray             # uint8, flat: the composed texts; gaps are allowed and unspecified
+    text_starts: np.ndarray       # int64 [2, K]   row 0 the room lines, row 1 the replies
+    text_sizes: np.ndarray        # int64 [2, K]   -1: there is no such text
+    timing: dict = field(default_factory=dict)   # as Plan's: kernels_us, end_to_end_us, h2d_bytes, d2h_bytes
+
+    def _text(self, row: int, k: int) -> bytes:
+        if not 0 <= k < len(self.outcome):
+            raise IndexError(f"no event {k}: {len(self.outcome)} events")
+        at, n = int(self.text_starts[row, k]), int(self.text_sizes[row, k])
+        return self.texts[at:at + n].tobytes() if n >= 0 else b""
+
+    def line(self, k: int) -> bytes:
+        """The line event ``k`` sends to its room, or to every room; ``b""`` when it was not spoken (a composed line
+        is never empty: it ends in a newline)."""
+        return self._text(0, k)
+
+    def reply_text(self, k: int) -> bytes:
+        """What event ``k`` sends to its speaker alone: the echo or the notice; ``b""`` when there is none."""
+        return self._text(1, k)
+
+
 # ------------------------------------------------------------------ validation (never touches the device)
 def _as_text(t) -> bytes:
     if isinstance(t, str):
@@ -434,6 +487,9 @@ def _load():
         lib.nd_roster_review.argtypes = [ctypes.c_int, ctypes.c_int, P, P, P, P, P, P, P, P, P,
                                          ctypes.POINTER(_RosterTiming)]
         lib.nd_roster_review.restype = ctypes.c_int
+        lib.nd_roster_speak.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int64, P, P, P, P, P, ctypes.c_int,
+                                        ctypes.c_int, P, P, P, P, P, P, P, P, P, P, P, ctypes.POINTER(_RosterTiming)]
+        lib.nd_roster_speak.restype = ctypes.c_int
         lib.nd_arena.restype = P
         lib.nd_write_sizes.restype = P
         _LIB = lib
@@ -528,6 +584,26 @@ def _room(v) -> int:
     return int(v)
 
 
+def _speaker_name(v) -> bytes:
+    """``user->name``: bytes or str of 1 .. USER_NAME_LEN bytes, no NUL."""
+    if isinstance(v, str):
+        try:
+            v = v.encode("latin-1")
+        except UnicodeEncodeError as e:
+            raise ValueError(f"name has a character outside one byte: {e}") from None
+    elif isinstance(v, (bytearray, memoryview)):
+        v = bytes(v)
+    if not isinstance(v, bytes):
+        raise ValueError(f"name must be bytes or str, not {type(v).__name__}")
+    if not 1 <= len(v) <= USER_NAME_LEN or b"\0" in v:
+        raise ValueError(f"name must be 1 .. {USER_NAME_LEN} bytes without a NUL, not {v!r}")
+    return v
+
+
+#: the commands speak_many answers, and whether their room line goes to the speaker's room (and is recorded there)
+_SPEECH_COMS = {COM_SAY: True, COM_SHOUT: False, COM_EMOTE: True, COM_SEMOTE: False}
+
+
 class Roster:
     """The talker's user list, kept on the device between calls: per slot a room (``None``: an empty slot, or a user
     away over a netlink) and the ``login``, ``ignall``, ``ignshout`` and ``colour`` flags.  Broadcasts are addressed as
@@ -564,6 +640,11 @@ class Roster:
         self._flags = self._table[4 * self.capacity:]
         self._room[:] = -1
         self._dirty = True
+        # the speakers' mirror, as nd_roster_speak takes it: 16 bytes per slot -- 12 name bytes, the name's length, a
+        # flags byte (SPEECH_FLAGS), two bytes of padding.  Only speak_many uploads it, after an update of its fields
+        self._speech = np.zeros((self.capacity, 16), dtype=np.uint8)
+        self._speech[:, USER_NAME_LEN + 1] = SPEECH_FLAGS["vis"]
+        self._speech_dirty = True
         self._handle = None
         self._closed = False
 
@@ -576,11 +657,17 @@ class Roster:
             raise ValueError(f"slot must be an int in [0, {self.capacity}), not {v!r}")
         return int(v)
 
-    def update(self, slots, *, room=_KEEP, login=_KEEP, ignall=_KEEP, ignshout=_KEEP, colour=_KEEP) -> None:
+    def update(self, slots, *, room=_KEEP, login=_KEEP, ignall=_KEEP, ignshout=_KEEP, colour=_KEEP, name=_KEEP,
+               vis=_KEEP, muzzled=_KEEP, command_mode=_KEEP) -> None:
         """Set fields of ``slots`` (a slot or a sequence of them).  Each field given is one value for every slot or a
         sequence of one per slot; a field not given stays as it is.  ``room`` is None (no room) or an int in
         [0, ROOM_LIMIT); the flags are 0/1 or bools.  A slot given more than once takes its last values.  Nothing
-        changes unless the whole update is valid."""
+        changes unless the whole update is valid.
+
+        ``name`` (bytes or str of 1 .. USER_NAME_LEN bytes, no NUL; unset at first), ``vis`` (1 at first), ``muzzled``
+        and ``command_mode`` (0 at first) are what the speech commands read of a speaker.  They live in a mirror of
+        their own that only :meth:`speak_many` uploads: an update of these fields alone does not make the next
+        ``broadcast_many`` / ``plan_many`` upload the table."""
         self._check_open()
         if isinstance(slots, (int, np.integer)):
             slots = [slots]
@@ -603,6 +690,18 @@ class Roster:
         flags = {f: per_slot(f, v, lambda x, f=f: _flag(f, x), np.uint8)
                  for f, v in (("login", login), ("ignall", ignall), ("ignshout", ignshout), ("colour", colour))
                  if v is not _KEEP}
+        names = None
+        if name is not _KEEP:
+            if isinstance(name, (str, bytes, bytearray, memoryview)):
+                names = [_speaker_name(name)] * n
+            elif not hasattr(name, "__len__"):
+                raise ValueError(f"name must be a name or a sequence of one per slot, not {name!r}")
+            elif len(name) != n:
+                raise ValueError(f"name: {len(name)} values for {n} slots")
+            else:
+                names = [_speaker_name(x) for x in name]
+        speech = {f: per_slot(f, v, lambda x, f=f: _flag(f, x), np.uint8)
+                  for f, v in (("vis", vis), ("muzzled", muzzled), ("command_mode", command_mode)) if v is not _KEEP}
         _, last = np.unique(idx[::-1], return_index=True)        # each slot's last position: last write wins
         keep = n - 1 - last
         at = idx[keep]
@@ -611,7 +710,18 @@ class Roster:
         for f, v in flags.items():
             bit = np.uint8(ROSTER_FLAGS[f])
             self._flags[at] = np.where(v[keep] != 0, self._flags[at] | bit, self._flags[at] & ~bit)
-        self._dirty = True
+        if names is not None:
+            for j, p in zip(at.tolist(), keep.tolist()):
+                self._speech[j, :USER_NAME_LEN] = 0
+                self._speech[j, :len(names[p])] = np.frombuffer(names[p], dtype=np.uint8)
+                self._speech[j, USER_NAME_LEN] = len(names[p])
+        for f, v in speech.items():
+            bit, col = np.uint8(SPEECH_FLAGS[f]), self._speech[:, USER_NAME_LEN + 1]
+            col[at] = np.where(v[keep] != 0, col[at] | bit, col[at] & ~bit)
+        if names is not None or speech:
+            self._speech_dirty = True
+        if rooms is not None or flags or not (names is not None or speech):
+            self._dirty = True
 
     def table(self, rm, sender) -> np.ndarray:
         """The (capacity, 7) listener table, in LISTENER_FIELDS order, that :func:`broadcast` would take for a broadcast
@@ -809,6 +919,133 @@ class Roster:
                     variant_starts=starts, variant_sizes=vn, write_counts=vw, write_sizes=vwsz,
                     timing={"kernels_us": t.kernels_us, "end_to_end_us": t.end_to_end_us, "h2d_bytes": t.h2d_bytes,
                             "d2h_bytes": t.d2h_bytes})
+
+    def _prepare_speech(self, events, ban_swearing, record):
+        """Each (slot, com, inpstr, word_count) and its speaker's state checked, packed for nd_roster_speak: the inpstr,
+        their offsets and lengths, the slots, commands and word counts, the two flags, and whether the call records."""
+        if isinstance(events, (str, bytes, bytearray, np.ndarray)) or not hasattr(events, "__len__"):
+            raise ValueError(f"events must be a sequence of tuples, not {type(events).__name__}")
+        if len(events) == 0:
+            raise ValueError("empty call: no events")
+        ban_swearing, record = _flag("ban_swearing", ban_swearing), _flag("record", record)
+        if len(events) * self.capacity >= 2**31 - 1:
+            raise ValueError(f"{len(events)} events to {self.capacity} slots: K x capacity must be below 2^31 - 1")
+        texts, slots, coms, wcs = [], [], [], []
+        recording = False
+        for k, ev in enumerate(events):
+            if not isinstance(ev, tuple) or len(ev) != 4:
+                raise ValueError(f"event {k}: expected a (slot, com, inpstr, word_count) tuple, "
+                                 f"got {type(ev).__name__}{f' of {len(ev)}' if isinstance(ev, tuple) else ''}")
+            slot, com, inpstr, wc = ev
+            try:
+                slot = self._slot(slot)
+                if isinstance(com, (bool, np.bool_)) or not isinstance(com, (int, np.integer)) or int(com) not in _SPEECH_COMS:
+                    raise ValueError(f"com must be COM_SAY, COM_SHOUT, COM_EMOTE or COM_SEMOTE "
+                                     f"({', '.join(map(str, _SPEECH_COMS))}), not {com!r}")
+                text = _as_text(inpstr)
+                if len(text) >= ARR_SIZE:
+                    raise ValueError(f"inpstr of {len(text)} bytes: the talker's input line holds at most {ARR_SIZE - 1}")
+                if (isinstance(wc, (bool, np.bool_)) or not isinstance(wc, (int, np.integer))
+                        or not 0 <= int(wc) <= MAX_WORDS):
+                    raise ValueError(f"word_count must be an int in [0, {MAX_WORDS}], not {wc!r}")
+                if self._room[slot] < 0:
+                    raise ValueError(f"the speaker, slot {slot}, has no room (the talker relays such a user over its "
+                                     f"netlink)")
+                if self._flags[slot] & ROSTER_FLAGS["login"]:
+                    raise ValueError(f"the speaker, slot {slot}, is still logging in")
+                if self._speech[slot, USER_NAME_LEN] == 0:
+                    raise ValueError(f"the speaker, slot {slot}, has no name")
+                if record and _SPEECH_COMS[int(com)]:
+                    if not 0 <= self._room[slot] < self.review_rooms:
+                        raise ValueError(f"it is to be recorded, but room {int(self._room[slot])} has no review ring: " +
+                                         (f"the ring rooms are 0 .. {self.review_rooms - 1}" if self.review_rooms else
+                                          "the roster has none (review_rooms is 0)"))
+                    recording = True
+            except ValueError as e:
+                raise ValueError(f"event {k}: {e}") from None
+            texts.append(text)
+            slots.append(slot)
+            coms.append(int(com))
+            wcs.append(int(wc))
+        lens = np.fromiter((len(t) for t in texts), dtype=np.int64, count=len(texts))
+        bound = 12 * (2 * int(lens.sum()) + 2 * _SPEAK_SLACK * len(lens)) + 32 * len(lens)
+        if bound > MANY_ARENA_CAP:
+            raise ValueError(f"call too large: its variant bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
+                             f"(MANY_ARENA_CAP): split it")
+        text_off = np.zeros(len(texts), dtype=np.int32)
+        np.cumsum(lens[:-1], out=text_off[1:])
+        return (b"".join(texts), text_off, lens.astype(np.int32), np.array(slots, dtype=np.int32),
+                np.array(coms, dtype=np.uint8), np.array(wcs, dtype=np.uint8), ban_swearing, recording)
+
+    def speak_many(self, events, ban_swearing=False, record=False) -> Speech:
+        """K speech events in one device call: a non-empty sequence of ``(slot, com, inpstr, word_count)`` tuples, what
+        the talker's ``say()``, ``shout()``, ``emote()`` and ``semote()`` receive (nuts333.c:4062-4226).  ``com`` is
+        COM_SAY, COM_SHOUT, COM_EMOTE or COM_SEMOTE; ``inpstr`` is a text by :func:`broadcast`'s rules of at most 999
+        bytes -- ``.shout X`` passes ``X``, a plain line the whole line, the ``;x`` / ``#x`` shortcuts the whole line
+        with its first byte; ``word_count`` is the talker's, an int in [0, 10].  The speaker must have a room, a name
+        and no ``login`` flag.  Anything else raises ``ValueError("event k: ...")`` before the device is touched.
+
+        The device decides each event's outcome in the reference's order: MUZZLED if the speaker is muzzled; NOTHING if
+        ``word_count < 2`` and, for a say, ``command_mode``, for an emote or semote, byte 1 of ``inpstr`` as a signed
+        char below 33; SWEARING if ``ban_swearing`` and the text holds a swear word (not for a semote, which the
+        reference does not check); else SPOKEN.  In the NOTHING test byte 1 of an ``inpstr`` shorter than 2 bytes counts
+        as 0: the reference reads a stale byte of its input buffer there.  Returns a :class:`Speech`; for every spoken
+        event ``k`` its ``room`` plan at ``k`` is ``plan_many([(speech.line(k), rm, sender, 0, com)])`` at 0, with
+        ``(rm, sender)`` the speaker's room and slot for a say, ``(None, slot)`` for a shout, ``(room, None)`` for an
+        emote and ``(None, None)`` for a semote.
+
+        ``record=True`` stores every spoken say and emote in its speaker's room ring as ``plan_many(record=)`` stores a
+        line, in event order, after the pending ``clear_review``; every say and emote event's speaker must then be in a
+        ring room, whatever its outcome turns out to be.  Shouts and semotes are never recorded.
+
+        One upload (the table and the speaker state only after an update of theirs), two kernel launches
+        (nuts_roster_speak, nuts_roster_speak_plan) -- three in a call that records (nuts_roster_record) --, one
+        download at the bound size and one synchronise, whatever K and the capacity."""
+        self._check_open()
+        text, text_off, lens, slots, coms, wcs, ban, recording = self._prepare_speech(events, ban_swearing, record)
+        lib = _load()
+        handle = self._device_handle(lib)
+        k, words = len(lens), (self.capacity + 63) // 64
+        ctext_bytes = 2 * len(text) + 2 * _SPEAK_SLACK * k
+        outcome = np.empty(k, dtype=np.int8)
+        clen = np.empty((2, k), dtype=np.int32)
+        bits = np.empty((k, words), dtype=np.uint64)
+        vn = np.empty((2, k, 2), dtype=np.int64)
+        vw = np.empty((2, k, 2), dtype=np.int32)
+        vwsz = np.empty((2, k, 2, MAX_WRITES), dtype=np.int32)
+        ctext = np.empty(ctext_bytes, dtype=np.uint8)
+        var = np.empty(12 * ctext_bytes + 32 * k, dtype=np.uint8)
+        tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
+        clear = self._pending_clear() if recording else None
+        t = _RosterTiming()
+        rc = lib.nd_roster_speak(handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(slots), _ptr(coms),
+                                 _ptr(wcs), ban, int(recording), _ptr(self._table) if self._dirty else None,
+                                 _ptr(self._speech) if self._speech_dirty else None,
+                                 _ptr(clear) if clear is not None else None, _ptr(outcome), _ptr(clen), _ptr(bits),
+                                 _ptr(vn), _ptr(vw), _ptr(vwsz), _ptr(ctext), _ptr(var), ctypes.byref(t))
+        if rc != 0:
+            raise RuntimeError(f"device speech failed: {lib.nd_last_error().decode(errors='replace')}")
+        self._dirty = self._speech_dirty = False
+        if recording:
+            self._clear_sent()
+        # the buffers' layout (nd_roster_speak): text t = k is event k's room line, K + k its reply
+        tstarts = np.empty((2, k), dtype=np.int64)
+        tstarts[0] = text_off.astype(np.int64) + _SPEAK_SLACK * np.arange(k, dtype=np.int64)
+        tstarts[1] = tstarts[0] + len(text) + _SPEAK_SLACK * k
+        starts = np.empty((2, k, 2), dtype=np.int64)
+        starts[:, :, 0] = 12 * tstarts + 16 * np.arange(2 * k, dtype=np.int64).reshape(2, k)
+        starts[:, :, 1] = starts[:, :, 0] + ((6 * np.maximum(clen, 0).astype(np.int64) + 4 + 3) & ~3)
+        reply_bits = np.zeros((k, words), dtype=np.uint64)
+        has = np.flatnonzero(clen[1] >= 0)
+        reply_bits[has, slots[has] // 64] = np.uint64(1) << (slots[has] % 64).astype(np.uint64)
+        timing = {"kernels_us": t.kernels_us, "end_to_end_us": t.end_to_end_us, "h2d_bytes": t.h2d_bytes,
+                  "d2h_bytes": t.d2h_bytes}
+        colour_bits = _pack((self._flags & ROSTER_FLAGS["colour"]) != 0)
+        plans = [Plan(capacity=self.capacity, admitted_bits=b, colour_bits=colour_bits, variants=var,
+                      variant_starts=starts[i], variant_sizes=vn[i], write_counts=vw[i], write_sizes=vwsz[i],
+                      timing=dict(timing)) for i, b in enumerate((bits, reply_bits))]
+        return Speech(outcome=outcome, room=plans[0], reply=plans[1], texts=ctext, text_starts=tstarts,
+                      text_sizes=clen.astype(np.int64), timing=timing)
 
     def _ring_room(self, v) -> int:
         if (not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_))

@@ -21,6 +21,9 @@
 // A roster can also own review rings, the device's record() / .review (nuts333.c:2062-2070, 5192-5222): nuts_roster_record
 // stores a plan call's recorded broadcasts in their rooms' rings, nuts_roster_review transduces the rings of a list of
 // rooms, one wave per (line, colour variant), parallel over the line's bytes (their section below).
+// And it can keep what the speech commands read of a speaker: nuts_roster_speak composes what say(), shout(), emote() and
+// semote() write for K (user, command, inpstr, word_count) events, a wave per event, and nuts_roster_speak_plan plans the
+// composed texts as nuts_roster_plan would (their section below).
 //
 // Hard bounds per item of a text of len < 2000 bytes: 6*len + 4 output bytes (a '\n' with colour
 // on is the costliest input byte, plus the trailing reset) and 16 writes.  The host sizes its buffers
@@ -954,6 +957,266 @@ __device__ void roster_review(const ReviewArgs& a)
 static_assert(kBlock / 64 >= 1 && 64 * 4 >= kRevSlot, "roster_review: a wave holds a whole slot, four bytes per lane");
 static_assert(kBlock >= kRevTasks + 64 && kBlock >= kRevLines, "roster_review / roster_record: a lane per task, per line");
 
+// ------------------------------------------------------------------ speech commands of a resident roster
+//
+// The stage in front of write_room_except: say(), shout(), emote() and semote() (nuts333.c:4062-4226; say / shout /
+// emote / semote of oracle/talker_port.c) turn (user, command, inpstr, word_count) into a notice to the speaker, or into
+// the speaker's echo and the line its room, or every room, gets.  A roster keeps what they read of a speaker, 16 bytes per
+// slot in a device allocation of its own that never moves: 12 name bytes, the name's length, a flags byte (vis, muzzled,
+// command_mode) and two bytes of padding.
+//   compose  nuts_roster_speak, one wave per event, four events per block.  The wave reads its speaker's state and decides
+//            the outcome in the reference's order, wave-uniformly: muzzled, nothing to say, swearing, spoken.  The swear
+//            scan is parallel over the bytes: lane l lowers A-Z in bytes 16l .. 16l+18 (its 16 and 3 of overlap) and
+//            tests the three words of nuts333.h:275-277 at its 16 positions; a ballot is the answer.  The verb comes from
+//            the last byte.  Both texts are composed with parallel byte copies into the call's composed-text buffer:
+//            event k's room line in slot k and its reply in slot K + k, each in_len + kSpeakSlack bytes wide at an offset
+//            the host computed (a composed text is at most in_len + 32 bytes; the longest notice, 35 bytes, must fit
+//            beside an empty inpstr).  A text that does not exist -- the line of an event that was not spoken, the reply
+//            of an emote -- has length -1.  Lane 0 stores the lengths, the outcome, and rm / sender / com / flags (the
+//            record bit included) of the room line as nuts_roster_plan and nuts_roster_record take them.
+//            When the call uploaded the speaker table, the waves read the upload, and blocks past the events' copy it
+//            into the kept allocation for the calls that follow.
+//   plan     nuts_roster_speak_plan over the 2K composed texts, sharing stage_variants and admits with nuts_roster_plan:
+//            one block per (room line, 256-slot tile) as there, then one block per reply, which has variants only (its
+//            admit bitmap, the speaker alone, is the host's).  A text of length -1 is void: nobody is admitted and both
+//            variants have 0 bytes in 0 writes -- not the 4-byte reset of an empty text.
+//   record   nuts_roster_record, as it is, on the arrays the compose kernel wrote.
+constexpr int kComSay = 3, kComEmote = 6;                  // enum np_com: NP_SAY, NP_EMOTE
+constexpr int kArrSize = 1000;                             // nuts333.h:19 ARR_SIZE: inpstr is at most 999 bytes
+constexpr int kSpeakSlack = 36;                            // a composed text's slot is this much wider than inpstr
+constexpr int kSpeechRec = 16;                             // bytes of speaker state per slot
+constexpr int kNameLen = 12;                               // nuts333.h:23 USER_NAME_LEN
+constexpr uint8_t kVis = 1, kMuzzled = 2, kCommandMode = 4;   // the flags byte of a slot's speaker state
+constexpr int kSpoken = 0, kOutMuzzled = 1, kOutNothing = 2, kOutSwearing = 3;
+constexpr int kSwearSlice = 16;                            // bytes of inpstr per lane in the swear scan
+
+struct SpeakArgs {
+    const int32_t* room;         // [capacity] the roster's table: -1, no room
+    const uint8_t* speech;       // [capacity * 16] the speaker state this call reads: the upload, or the kept table
+    const uint8_t* speech_new;   // the upload when there is one, to be copied to speech_keep; else nullptr
+    uint8_t* speech_keep;        // [capacity * 16] the kept table
+    const uint8_t* text;         // the K inpstr, packed
+    const int32_t* text_off;     // [k]
+    const int32_t* text_len;     // [k]
+    const int32_t* slot;         // [k] the speaker
+    const uint8_t* com;          // [k] NP_SAY, NP_SHOUT, NP_EMOTE or NP_SEMOTE
+    const uint8_t* words;        // [k] word_count
+    const int32_t* ctext_off;    // [2k] where each composed text's slot starts in ctext
+    int k, capacity, blocks;     // blocks: those that compose; the ones after them copy the speaker table
+    int ban_swearing, record;
+    int* violations;             // composed texts past their slot (zeroed by the host's upload)
+    uint8_t* ctext;              // the composed texts
+    int32_t* clen;               // [2k] their lengths; -1: no such text
+    int32_t* rm;                 // [k] the room line's room (-1: every room), as PlanArgs.rm
+    int32_t* sender;             // [k] and its sender (-1: none)
+    int32_t* com_num;            // [k]
+    uint8_t* flags;              // [k] bit 2: record the room line
+    int8_t* outcome;             // [k]
+};
+
+struct Piece {
+    const uint8_t* p;
+    int n;
+};
+template <int N>
+__device__ __forceinline__ Piece lit(const char (&s)[N]) { return {reinterpret_cast<const uint8_t*>(s), N - 1}; }
+
+// np_contains_swearing (nuts333.c:2540-2559) over s[0 .. len), len < kArrSize, by a whole wave.
+__device__ __forceinline__ bool swears(const uint8_t* s, int len, int lane)
+{
+    constexpr uint32_t w0 = 'f' | 'u' << 8 | 'c' << 16 | (uint32_t)'k' << 24;
+    constexpr uint32_t w1 = 's' | 'h' << 8 | 'i' << 16 | (uint32_t)'t' << 24;
+    constexpr uint32_t w2 = 'c' | 'u' << 8 | 'n' << 16 | (uint32_t)'t' << 24;
+    uint32_t low[kSwearSlice + 3];
+#pragma unroll
+    for (int x = 0; x < kSwearSlice + 3; x++) {
+        const int at = kSwearSlice * lane + x;
+        const uint32_t c = at < len ? s[at] : 0;
+        low[x] = c >= 'A' && c <= 'Z' ? c + 32 : c;          // tolower in the C locale
+    }
+    bool hit = false;
+#pragma unroll
+    for (int x = 0; x < kSwearSlice; x++) {
+        const uint32_t v = low[x] | low[x + 1] << 8 | low[x + 2] << 16 | low[x + 3] << 24;
+        hit |= v == w0 || v == w1 || v == w2;
+    }
+    return __ballot(hit) != 0;
+}
+
+// The five pieces, then body[0 .. blen), then '\n' if newline, into dst by a whole wave; returns the text's length, or -1
+// and a violation when it would pass cap.  The pieces are shorter than a wave together: lane i stores their byte i.
+__device__ __forceinline__ int compose(uint8_t* dst, int cap, const Piece (&pc)[5], const uint8_t* body, int blen,
+                                       bool newline, int lane, int* violations)
+{
+    const uint8_t* src = nullptr;
+    int plen = 0;
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        if (lane >= plen && lane < plen + pc[i].n) src = pc[i].p + (lane - plen);
+        plen += pc[i].n;
+    }
+    const int total = plen + blen + (newline ? 1 : 0);
+    if (plen > 64 || total > cap) {
+        if (lane == 0) atomicAdd(violations, 1);
+        return -1;
+    }
+    if (src) dst[lane] = *src;
+    for (int i = lane; i < blen; i += 64) dst[plen + i] = body[i];
+    if (newline && lane == 0) dst[plen + blen] = '\n';
+    return total;
+}
+
+__device__ void roster_speak(const SpeakArgs& a)
+{
+    if ((int)blockIdx.x >= a.blocks) {      // the speaker table just uploaded, into the kept allocation: a word per lane
+        const int w = ((int)blockIdx.x - a.blocks) * kBlock + (int)threadIdx.x;
+        if (a.speech_new && w < a.capacity * (kSpeechRec / 4))
+            reinterpret_cast<uint32_t*>(a.speech_keep)[w] = reinterpret_cast<const uint32_t*>(a.speech_new)[w];
+        return;
+    }
+    const int lane = (int)threadIdx.x & 63;
+    const int k = (int)blockIdx.x * (kBlock / 64) + ((int)threadIdx.x >> 6);      // wave-uniform
+    if (k >= a.k) return;
+    const int slot = a.slot[k], com = a.com[k], wc = a.words[k], len = a.text_len[k];
+    const uint8_t* in = a.text + a.text_off[k];
+    const uint8_t* sp = a.speech + (size_t)slot * kSpeechRec;
+    const uint8_t state = sp[kNameLen + 1];
+    const int nlen = sp[kNameLen] < kNameLen ? sp[kNameLen] : kNameLen;
+    const int room = a.room[slot];
+    const uint8_t b0 = len > 0 ? in[0] : 0, b1 = len > 1 ? in[1] : 0, last = len > 0 ? in[len - 1] : 0;
+    const bool say = com == kComSay, shout = com == kComShout, emote = com == kComEmote;   // else semote
+
+    // say() c:4068-4082, shout() c:4110-4118, emote() c:4192-4200, semote() c:4216-4221, in their order
+    int outcome = kSpoken;
+    if (state & kMuzzled) outcome = kOutMuzzled;
+    else if (say ? wc < 2 && (state & kCommandMode) : shout ? wc < 2 : wc < 2 && (int8_t)b1 < 33) outcome = kOutNothing;
+    else if (a.ban_swearing && com != kComSemote && swears(in, len, lane)) outcome = kOutSwearing;
+
+    uint8_t* line = a.ctext + a.ctext_off[k];
+    uint8_t* reply = a.ctext + a.ctext_off[a.k + k];
+    const int cap = len + kSpeakSlack;
+    const Piece none{nullptr, 0};
+    int line_len = -1, reply_len = -1;
+    if (outcome == kOutMuzzled) {
+        const Piece p[5] = {say ? lit("You are muzzled, you cannot speak.\n") : shout ? lit("You are muzzled, you cannot shout.\n")
+                                : lit("You are muzzled, you cannot emote.\n"), none, none, none, none};
+        reply_len = compose(reply, cap, p, nullptr, 0, false, lane, a.violations);
+    } else if (outcome == kOutNothing) {
+        const Piece p[5] = {say ? lit("Say what?\n") : shout ? lit("Shout what?\n") : emote ? lit("Emote what?\n")
+                                : lit("Shout emote what?\n"), none, none, none, none};
+        reply_len = compose(reply, cap, p, nullptr, 0, false, lane, a.violations);
+    } else if (outcome == kOutSwearing) {
+        const Piece p[5] = {lit("Swearing is not allowed here.\n"), none, none, none, none};
+        reply_len = compose(reply, cap, p, nullptr, 0, false, lane, a.violations);
+    } else {
+        const Piece name = (state & kVis) ? Piece{sp, nlen} : lit("A presence");      // invisname, nuts333.h:150
+        const Piece verb = last == '?' ? lit("ask") : last == '!' ? lit("exclaim") : lit("say");   // c:4080-4082
+        if (say) {                          // c:4091-4096
+            const Piece r[5] = {lit("You "), none, none, verb, lit(": ")};
+            const Piece l[5] = {none, name, lit(" "), verb, lit("s: ")};
+            reply_len = compose(reply, cap, r, in, len, true, lane, a.violations);
+            line_len = compose(line, cap, l, in, len, true, lane, a.violations);
+        } else if (shout) {                 // c:4119-4122
+            const Piece r[5] = {lit("~OLYou shout:~RS "), none, none, none, none};
+            const Piece l[5] = {lit("~OL"), name, lit(" shouts:~RS "), none, none};
+            reply_len = compose(reply, cap, r, in, len, true, lane, a.violations);
+            line_len = compose(line, cap, l, in, len, true, lane, a.violations);
+        } else {                            // c:4202-4203, c:4223-4224: ";x" and "#x" join the name
+            const int skip = b0 == (emote ? ';' : '#') ? 1 : 0;
+            const Piece l[5] = {emote ? none : lit("~OL!!~RS "), name, skip ? none : lit(" "), none, none};
+            line_len = compose(line, cap, l, in + skip, len - skip, true, lane, a.violations);
+        }
+        if (line_len < 0 || (reply_len < 0 && (say || shout))) line_len = reply_len = -1;   // a violation: the call fails
+    }
+    if (lane == 0) {
+        const bool spoken = line_len >= 0;
+        const bool here = say || emote;     // to the speaker's room, and recorded there; else to every room
+        a.clen[k] = line_len;
+        a.clen[a.k + k] = reply_len;
+        a.rm[k] = spoken && here ? room : -1;
+        a.sender[k] = spoken && (say || shout) ? slot : -1;
+        a.com_num[k] = com;
+        a.flags[k] = spoken && here && a.record ? kRecordBit : 0;
+        a.outcome[k] = (int8_t)outcome;
+    }
+}
+
+static_assert(64 * kSwearSlice >= kArrSize, "roster_speak: the swear scan's 64 slices cover the longest inpstr");
+static_assert(kSpeechRec % 4 == 0 && kNameLen + 2 <= kSpeechRec, "roster_speak: a slot's speaker state is whole words");
+
+struct SpeakPlanArgs {
+    const int32_t* room;         // [capacity] as PlanArgs
+    const uint8_t* slot;         // [capacity]
+    const uint8_t* text;         // the 2K composed texts' buffer (SpeakArgs.ctext)
+    const int32_t* text_off;     // [2k] SpeakArgs.ctext_off
+    const int32_t* text_len;     // [2k] SpeakArgs.clen; -1: void
+    const int32_t* rm;           // [k] what nuts_roster_speak wrote
+    const int32_t* sender;       // [k]
+    const int32_t* com_num;      // [k]
+    int k, capacity, tiles, words;
+    int* violations;
+    int64_t* vn;                 // [4k] bytes of text t's colour-off / colour-on variant; room lines first, then replies
+    int32_t* vw;                 // [4k]
+    int32_t* vwsz;               // [4k * kMaxWrites]
+    uint64_t* bits;              // [k * words] the room lines' admit bitmap
+    uint8_t* var;                // text t's variants: var_at(t), var_at(t) + var_stride(len)
+};
+
+__device__ __forceinline__ int64_t var_at(const SpeakPlanArgs& a, int t) { return 12 * (int64_t)a.text_off[t] + 16 * (int64_t)t; }
+
+__device__ void roster_speak_plan(const SpeakPlanArgs& a)
+{
+    const int lines = a.k * a.tiles;        // the blocks of the room lines; then a block per reply
+    int t;
+    if ((int)blockIdx.x < lines) {
+        const int b = (int)blockIdx.x / a.tiles, tile = (int)blockIdx.x - b * a.tiles;
+        const int j = tile * kBlock + (int)threadIdx.x;
+        bool in = false;
+        if (j < a.capacity && a.text_len[b] >= 0) {
+            const int room = a.room[j], rm = a.rm[b];
+            const uint8_t l = (a.slot[j] & (kLogin | kIgnall | kIgnshout | kColour)) | (room >= 0 ? kHasRoom : 0) |
+                              (rm >= 0 && room == rm ? kSameRoom : 0) | (j == a.sender[b] ? kSender : 0);
+            in = admits(l, rm < 0, 0, a.com_num[b]);
+        }
+        const uint64_t word = __ballot(in);
+        const int w = j >> 6;
+        if ((threadIdx.x & 63) == 0 && w < a.words) a.bits[(int64_t)b * a.words + w] = word;
+        if (tile != 0) return;              // block-uniform
+        t = b;
+    } else {
+        t = a.k + ((int)blockIdx.x - lines);
+    }
+    const int len = a.text_len[t];
+    if (len < 0) {                          // block-uniform: a void text has no variant, not even a reset
+        if (threadIdx.x < 2) {
+            a.vn[2 * t + threadIdx.x] = 0;
+            a.vw[2 * t + threadIdx.x] = 0;
+        }
+        return;
+    }
+    __shared__ uint8_t text[kTextSize];
+    __shared__ uint8_t var[2 * kVarCap];
+    __shared__ int32_t vwsz[2 * kMaxWrites];
+    __shared__ int64_t vn[2];
+    __shared__ int vw[2];
+    stage_variants<true>(a, t, text, var, vwsz, vn, vw);
+    const int64_t cap = 6 * (int64_t)len + 4, stride = var_stride(len);
+    uint8_t* dst = a.var + var_at(a, t);
+    for (int c = 0; c < 2; c++) {
+        const int64_t n = vn[c] < cap ? vn[c] : cap;
+        for (int64_t q = threadIdx.x; q < n; q += kBlock) dst[c * stride + q] = var[c * kVarCap + q];
+        const int nw = vw[c] < kMaxWrites ? vw[c] : kMaxWrites;
+        if ((int)threadIdx.x < nw) a.vwsz[(2 * t + c) * kMaxWrites + threadIdx.x] = vwsz[c * kMaxWrites + threadIdx.x];
+    }
+    if (threadIdx.x < 2) {
+        a.vn[2 * t + threadIdx.x] = vn[threadIdx.x];
+        a.vw[2 * t + threadIdx.x] = vw[threadIdx.x];
+        if (vn[threadIdx.x] > cap || vw[threadIdx.x] > kMaxWrites) atomicAdd(a.violations, 1);
+    }
+}
+
+static_assert(kArrSize - 1 + kSpeakSlack < kTextSize, "roster_speak_plan: a composed text fits stage_variants' LDS text");
+
 }  // namespace
 
 // Stable, unmangled kernel names (they are what rocprofv3 reports).
@@ -968,6 +1231,8 @@ extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_emit(RosterArgs
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_plan(PlanArgs a) { roster_plan(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_record(RecordArgs a) { roster_record(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_review(ReviewArgs a) { roster_review(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_speak(SpeakArgs a) { roster_speak(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_speak_plan(SpeakPlanArgs a) { roster_speak_plan(a); }
 
 // ------------------------------------------------------------------------------------------ host library
 
@@ -1130,6 +1395,7 @@ struct Roster {
     size_t cap_d = 0, cap_mirror = 0;
     int review_rooms = 0;        // rooms 0 .. review_rooms - 1 own a review ring
     uint8_t* rings = nullptr;    // the rings, then the cursors: an allocation of its own, made on first use, never moved
+    uint8_t* speech = nullptr;   // the speakers' state, 16 bytes per slot: likewise, made by the first nd_roster_speak
 };
 Roster g_rosters[kMaxRosters];
 
@@ -1235,6 +1501,55 @@ size_t layout_review(uintptr_t base, int capacity, size_t clear_bytes, ReviewArg
     take(a.vwsz, 2 * q * kRevWrites);
     take(a.lines, q * kRevRing);
     take(a.var, 2 * q * kRevVarStride);
+    return at;
+}
+
+// nd_roster_speak's layout of a roster's allocation: the table where layout_roster() places it, then the upload of the
+// speaker table (which the kept one, r.speech, is filled from), the call's inputs ending with violations, the results
+// next to each other, and last what only the kernels pass to each other.  One upload starts at the table, at the speaker
+// table or at the inputs, whichever is the first that changed.
+size_t layout_speak(uintptr_t base, size_t text_bytes, size_t clear_bytes, SpeakArgs& s, SpeakPlanArgs& p,
+                    const uint8_t** clear)
+{
+    size_t at = 0;
+    auto take = [&](auto*& ptr, size_t count) {
+        ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(base + at);
+        at += (count * sizeof(*ptr) + 255) & ~(size_t)255;
+    };
+    const size_t k = (size_t)s.k, cap = (size_t)s.capacity;
+    const size_t ctext_bytes = 2 * text_bytes + 2 * k * kSpeakSlack;
+    take(s.room, cap);
+    take(p.slot, cap);
+    take(s.speech_new, cap * kSpeechRec);
+    take(s.text, text_bytes);
+    take(s.text_off, k);
+    take(s.text_len, k);
+    take(s.slot, k);
+    take(s.com, k);
+    take(s.words, k);
+    take(s.ctext_off, 2 * k);
+    take(*clear, clear_bytes);
+    take(s.violations, 1);
+    take(s.outcome, k);
+    take(s.clen, 2 * k);
+    take(p.vn, 4 * k);
+    take(p.vw, 4 * k);
+    take(p.vwsz, 4 * k * kMaxWrites);
+    take(p.bits, k * (size_t)p.words);
+    take(s.ctext, ctext_bytes);
+    take(p.var, 12 * ctext_bytes + 32 * k);
+    take(s.rm, k);
+    take(s.sender, k);
+    take(s.com_num, k);
+    take(s.flags, k);
+    p.room = s.room;
+    p.text = s.ctext;
+    p.text_off = s.ctext_off;
+    p.text_len = s.clen;
+    p.rm = s.rm;
+    p.sender = s.sender;
+    p.com_num = s.com_num;
+    p.violations = s.violations;
     return at;
 }
 
@@ -1535,6 +1850,7 @@ int nd_roster_destroy(int handle)
     if (!r) return -1;
     if (r->d) (void)hipFree(r->d);
     if (r->rings) (void)hipFree(r->rings);
+    if (r->speech) (void)hipFree(r->speech);
     if (r->mirror) (void)hipHostFree(r->mirror);
     *r = Roster{};
     return 0;
@@ -1884,6 +2200,168 @@ int nd_roster_review(int handle, int q, const int32_t* rooms, const uint8_t* cle
         timing->kernels_us = (double)ms * 1e3;
         timing->end_to_end_us = (t1 - t0) * 1e-3;
         timing->h2d_bytes = (int64_t)(in_bytes - table_bytes);
+        timing->d2h_bytes = (int64_t)res_bytes;
+    }
+    return 0;
+}
+
+// K speech events of roster `handle`, as say(), shout(), emote() and semote() answer them.  Event b: the speaker's slot
+// slots[b], the command coms[b] (NP_SAY 3, NP_SHOUT 4, NP_EMOTE 6, NP_SEMOTE 7), inpstr text[text_off[b] .. + text_len[b])
+// (packed: text_off[0] = 0, text_off[b + 1] = text_off[b] + text_len[b]; at most 999 bytes each) and word_count words[b].
+// table as nd_roster_plan's.  speech is NULL when no speaker state changed since the last nd_roster_speak of this roster,
+// else all of it: 16 bytes per slot, the name's 12 bytes, its length, a flags byte (vis 1, muzzled 2, command_mode 4) and
+// two bytes of padding; the first call of a roster must give it.  record: store the spoken says and emotes in their
+// rooms' rings, after clearing those that clear marks (NULL: none), as nd_roster_plan_record does; the caller has checked
+// that their speakers' rooms are ring rooms.
+// Outputs (host, caller-allocated), with W = ceil(capacity / 64) and text t = b for event b's room line, k + b for its
+// reply: outcome[k] (0 spoken, 1 muzzled, 2 nothing to say, 3 swearing); clen[2k] the composed texts' lengths, -1 where
+// there is none; ctext[2 * text_bytes + 72 * k] their bytes, text t at ctext_off(t) = text_off[b] + 36 * b, plus
+// text_bytes + 36 * k for a reply; bits[k * W] the room lines' admit bitmap, as nd_roster_plan's; vn[4k], vw[4k],
+// vwsz[4k * 16] the two variants of text t at 2t and 2t + 1, all zero for a text that is not there; var[12 * ctext bytes +
+// 32 * k] their bytes, text t's at 12 * ctext_off(t) + 16 * t and that plus (6 * clen[t] + 4 rounded up to 4).
+// Per call, whatever k and the capacity: one upload, two kernels (nuts_roster_speak, nuts_roster_speak_plan) and
+// nuts_roster_record as a third when record is set, one download at the bound size, one synchronise.
+// Returns 0, or -1 with nd_last_error() set.
+int nd_roster_speak(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off,
+                    const int32_t* text_len, const int32_t* slots, const uint8_t* coms, const uint8_t* words,
+                    int ban_swearing, int record, const uint8_t* table, const uint8_t* speech, const uint8_t* clear,
+                    int8_t* outcome, int32_t* clen, uint64_t* bits, int64_t* vn, int32_t* vw, int32_t* vwsz,
+                    uint8_t* ctext, uint8_t* var, nd_roster_timing* timing)
+{
+    Roster* r = roster_at(handle);
+    if (!r || ensure_ready()) return -1;
+    const int cap = r->capacity, nwords = (cap + 63) / 64;
+    if (k < 1 || (int64_t)k * cap >= INT32_MAX || text_bytes < 0 || text_bytes >= INT32_MAX / 32) {
+        snprintf(g_err, sizeof(g_err), "%d events to %d slots: need 1 <= k * capacity < 2^31 - 1", k, cap);
+        return -1;
+    }
+    int64_t sum = 0;
+    for (int b = 0; b < k; b++) {       // the kernels index by these: nothing out of range reaches them
+        const bool com_ok = coms[b] == kComSay || coms[b] == kComShout || coms[b] == kComEmote || coms[b] == kComSemote;
+        if (slots[b] < 0 || slots[b] >= cap || !com_ok || text_len[b] < 0 || text_len[b] >= kArrSize ||
+            text_off[b] != sum) {
+            snprintf(g_err, sizeof(g_err), "event %d: slot, command, text length or text offset out of range", b);
+            return -1;
+        }
+        sum += text_len[b];
+    }
+    if (sum != text_bytes) {
+        snprintf(g_err, sizeof(g_err), "the events' texts hold %lld bytes, not %lld", (long long)sum, (long long)text_bytes);
+        return -1;
+    }
+    if (!r->speech && !speech) {
+        snprintf(g_err, sizeof(g_err), "the roster's first speech call must give the speaker table");
+        return -1;
+    }
+    if (record && ensure_rings(*r, g.stream)) return -1;
+    if (!r->speech) {
+        hipError_t e = hipMalloc((void**)&r->speech, (size_t)cap * kSpeechRec);
+        if (e != hipSuccess) {
+            r->speech = nullptr;
+            return fail("speaker table", e);
+        }
+    }
+    const double t0 = now_ns();
+    hipStream_t st = g.stream;
+    SpeakArgs s{};
+    SpeakPlanArgs p{};
+    s.k = p.k = k;
+    s.capacity = p.capacity = cap;
+    s.blocks = (k + kBlock / 64 - 1) / (kBlock / 64);
+    s.ban_swearing = ban_swearing != 0;
+    s.record = record != 0;
+    p.tiles = (cap + kBlock - 1) / kBlock;
+    p.words = nwords;
+    const size_t ctext_bytes = 2 * (size_t)text_bytes + 2 * (size_t)k * kSpeakSlack;
+    const size_t var_bytes = 12 * ctext_bytes + 32 * (size_t)k;
+    const size_t clear_bytes = record && clear ? (size_t)r->review_rooms : 0;
+    SpeakArgs so = s;                // offsets of every array in the roster's allocation
+    SpeakPlanArgs po = p;
+    const uint8_t *o_clear = nullptr, *d_clear = nullptr;
+    const size_t need = layout_speak(0, (size_t)text_bytes, clear_bytes, so, po, &o_clear);
+    const size_t table_bytes = (uintptr_t)so.speech_new, speech_end = (uintptr_t)so.text;
+    const size_t in_bytes = (uintptr_t)so.violations + sizeof(int);
+    const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
+    if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
+    if (table) {
+        memcpy(r->mirror + (uintptr_t)so.room, table, (size_t)cap * sizeof(int32_t));
+        memcpy(r->mirror + (uintptr_t)po.slot, table + (size_t)cap * sizeof(int32_t), (size_t)cap);
+        const int32_t* room = reinterpret_cast<const int32_t*>(r->mirror + (uintptr_t)so.room);
+        r->rooms = std::count_if(room, room + cap, [](int32_t x) { return x >= 0; });
+        r->resident = false;
+    }
+    const size_t cap_d = r->cap_d;
+    if (grow_dev(&r->d, &r->cap_d, need, "roster device allocation")) return -1;
+    if (r->cap_d != cap_d) r->resident = false;      // this call's upload refills the table from the mirror
+    layout_speak((uintptr_t)r->d, (size_t)text_bytes, clear_bytes, s, p, &d_clear);
+    if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
+
+    uint8_t* h = r->mirror;
+    auto put = [&](const void* at, const void* src, size_t bytes) {
+        if (bytes) memcpy(h + (uintptr_t)at, src, bytes);
+    };
+    if (speech) put(so.speech_new, speech, (size_t)cap * kSpeechRec);
+    put(so.text, text, (size_t)text_bytes);
+    put(so.text_off, text_off, (size_t)k * sizeof(int32_t));
+    put(so.text_len, text_len, (size_t)k * sizeof(int32_t));
+    put(so.slot, slots, (size_t)k * sizeof(int32_t));
+    put(so.com, coms, (size_t)k);
+    put(so.words, words, (size_t)k);
+    int32_t* coff = reinterpret_cast<int32_t*>(h + (uintptr_t)so.ctext_off);
+    for (int b = 0; b < k; b++) {
+        coff[b] = text_off[b] + kSpeakSlack * b;
+        coff[k + b] = (int32_t)text_bytes + kSpeakSlack * k + coff[b];
+    }
+    put(o_clear, clear, clear_bytes);
+    *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
+    // the speaker table's upload lies between the table and the inputs: when only the table changed it travels too, but
+    // the kernel is not told, so the mirror's bytes there need not be current
+    const size_t from = !r->resident ? 0 : speech ? table_bytes : speech_end;
+    ND_CHECK(hipMemcpyAsync(r->d + from, h + from, in_bytes - from, hipMemcpyHostToDevice, st));
+    r->resident = true;
+    s.speech = speech ? s.speech_new : r->speech;
+    if (!speech) s.speech_new = nullptr;
+    s.speech_keep = r->speech;
+
+    const unsigned copy_blocks = speech ? (unsigned)(((size_t)cap * (kSpeechRec / 4) + kBlock - 1) / kBlock) : 0u;
+    ND_CHECK(hipEventRecord(g.ev0, st));
+    hipLaunchKernelGGL(nuts_roster_speak, dim3((unsigned)s.blocks + copy_blocks), dim3(kBlock), 0, st, s);
+    ND_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)(k * p.tiles + k)), dim3(kBlock), 0, st, p);
+    ND_CHECK(hipGetLastError());
+    if (record) {                    // on the arrays nuts_roster_speak wrote; the rings are touched by this stream alone
+        RecordArgs rec{s.ctext, s.ctext_off, s.clen, s.rm, s.flags, clear_bytes ? d_clear : nullptr, k,
+                       r->review_rooms, r->rings, reinterpret_cast<int32_t*>(r->rings + revline_at(*r))};
+        hipLaunchKernelGGL(nuts_roster_record, dim3((unsigned)r->review_rooms), dim3(kBlock), 0, st, rec);
+        ND_CHECK(hipGetLastError());
+    }
+    ND_CHECK(hipEventRecord(g.ev1, st));
+    ND_CHECK(hipMemcpyAsync(gm.res, r->d + res_at, res_bytes, hipMemcpyDeviceToHost, st));
+    ND_CHECK(hipStreamSynchronize(st));
+    const double t1 = now_ns();
+
+    auto res = [&](const void* at) { return gm.res + ((uintptr_t)at - res_at); };
+    const int violations = *reinterpret_cast<const int*>(res(so.violations));
+    if (violations) {
+        snprintf(g_err, sizeof(g_err), "%d text(s) exceeded the hard bounds (inpstr + %d bytes composed; 6*len+4 bytes, "
+                 "%d writes transduced)", violations, kSpeakSlack, kMaxWrites);
+        return -1;
+    }
+    memcpy(outcome, res(so.outcome), (size_t)k);
+    memcpy(clen, res(so.clen), 2 * (size_t)k * sizeof(int32_t));
+    memcpy(vn, res(po.vn), 4 * (size_t)k * sizeof(int64_t));
+    memcpy(vw, res(po.vw), 4 * (size_t)k * sizeof(int32_t));
+    memcpy(vwsz, res(po.vwsz), 4 * (size_t)k * kMaxWrites * sizeof(int32_t));
+    memcpy(bits, res(po.bits), (size_t)k * nwords * sizeof(uint64_t));
+    memcpy(ctext, res(so.ctext), ctext_bytes);
+    memcpy(var, res(po.var), var_bytes);
+
+    float ms = 0.f;
+    ND_CHECK(hipEventElapsedTime(&ms, g.ev0, g.ev1));
+    if (timing) {
+        timing->kernels_us = (double)ms * 1e3;
+        timing->end_to_end_us = (t1 - t0) * 1e-3;
+        timing->h2d_bytes = (int64_t)(in_bytes - from);
         timing->d2h_bytes = (int64_t)res_bytes;
     }
     return 0;

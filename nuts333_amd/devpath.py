@@ -1,7 +1,8 @@
 """What one broadcast's user-space stage costs on the MI355X, done by a kernel that does the work.
 
     python -m nuts333_amd.devpath [--reps R] [--warmup W] [--pathbench-iterations I] [--per-call K[,K...]]
-                                  [--roster K[,K...]] [--plan K[,K...]] [--review Q[,Q...]]   -> one JSON line
+                                  [--roster K[,K...]] [--plan K[,K...]] [--review Q[,Q...]] [--speak K[,K...]]
+                                                                                              -> one JSON line
 
 For N in {10, 100, 1000} listeners, the two texts oracle/pathbench.c times (``say``; ``shout`` carrying ``~OL``/``~RS``)
 and colour all-off / all-on / half, one ``nuts333_amd.device.broadcast`` per repetition (listener 0 is the sender, the
@@ -40,6 +41,13 @@ command (``cpu_us``: ``np_transduce`` of the restatement over the same 15 x Q li
 ``cpu_derived_us``: 15 x Q x pathbench's two per-line ``say`` figures, without the calls).  The first review of each Q
 is checked against the restatement.  And ``record``: ``plan_many`` of K = 100 to that roster with and without
 ``record``, alternating in one run.
+
+``--speak K[,K...]`` adds ``speak``: a 1000-slot roster (colour off, on, half) and K ``say`` events per
+``Roster.speak_many`` call whose room lines are the K ``say`` texts, timed alternating, in one process, with
+``plan_many`` of those K lines composed beforehand: ``kernels_us``, ``end_to_end_us`` and ``python_us`` of both, the
+copy volume, what composing adds over ``plan_many``, and the CPU composing the same events (``cpu_us``: ``np_say_verb``,
+``np_contains_swearing`` and the two formats of ``say()``, one ctypes call each; ``cpu_derived_us``: 2 x K x pathbench's
+``format_line_once_ns``).  The first call of each case is checked against the restatement.
 """
 from __future__ import annotations
 
@@ -272,6 +280,96 @@ def review_cases(qs: list[int], reps: int, warmup: int, pb: dict) -> dict:
             "review_rings": rings, "review": cases, "record": record}
 
 
+def speak_events(k: int) -> list[tuple]:
+    """K ``say`` events of slot 0 whose room lines are ``line_texts("say", k)``: the speaker is named as TEXTS["say"]
+    names it, and ``inpstr`` is what follows "Uaaa says: " without the newline."""
+    head = b"Uaaa says: "
+    return [(0, device.COM_SAY, t[len(head):-1], 8) for t in line_texts("say", k)]
+
+
+def speak_cpu_us(events, reps: int, warmup: int) -> dict:
+    """The CPU composing the same K says, timed here: per event np_say_verb, np_contains_swearing and the two formats of
+    say() (nuts333.c:4094,4097) by the C library's snprintf, one ctypes call each."""
+    lib, libc = nuts_path.lib(), ctypes.CDLL(None)
+    out, size = ctypes.create_string_buffer(device.TEXT_SIZE), ctypes.c_size_t(device.TEXT_SIZE)
+    runs = []
+    for _ in range(warmup + reps):
+        t0 = time.perf_counter()
+        for _, _, inpstr, _ in events:
+            verb = lib.np_say_verb(inpstr)
+            lib.np_contains_swearing(inpstr)
+            libc.snprintf(out, size, b"You %s: %s\n", ctypes.c_char_p(verb), ctypes.c_char_p(inpstr))
+            libc.snprintf(out, size, b"%s %ss: %s\n", ctypes.c_char_p(b"Uaaa"), ctypes.c_char_p(verb),
+                          ctypes.c_char_p(inpstr))
+        runs.append((time.perf_counter() - t0) * 1e6)
+    return _stats(runs[warmup:])
+
+
+def speak_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
+    """The ``speak`` section: speak_many of K says to a 1000-slot roster, alternating with plan_many of the same K
+    lines composed beforehand, for each colour case and each K."""
+    n = 1000
+    cases = []
+    for colour in COLOURS:
+        with device.Roster(n) as roster:
+            roster.update(range(n), room=0, colour=listeners(n, colour)[:, device.LISTENER_FIELDS.index("colour")])
+            roster.update(0, name=b"Uaaa")
+            for k in ks:
+                events, lines = speak_events(k), line_texts("say", k)
+                calls = [(t, 0, 0, 0, COM["say"]) for t in lines]
+                first, plan = roster.speak_many(events, ban_swearing=True), roster.plan_many(calls)
+                for i, t in enumerate(lines):
+                    ok = (first.outcome[i] == device.SPOKEN and first.line(i) == t
+                          and first.reply_text(i) == b"You say: " + events[i][2] + b"\n"
+                          and np.array_equal(first.room.admitted_bits[i], plan.admitted_bits[i])
+                          and all(first.room.variant(i, c) == nuts_path.transduce(t, c) == plan.variant(i, c)
+                                  and first.reply.variant(i, c) == nuts_path.transduce(first.reply_text(i), c)
+                                  for c in (0, 1)))
+                    if not ok:
+                        raise SystemExit(f"devpath: speak {k}, {colour}: event {i} differs from the CPU restatement")
+                timed = {name: {"kernels_us": [], "end_to_end_us": [], "python_us": [], "copies": set()}
+                         for name in ("speak", "plan")}
+                for i in range(2 * (warmup + reps)):
+                    name = ("speak", "plan")[i % 2]
+                    t0 = time.perf_counter()
+                    r = roster.speak_many(events, ban_swearing=True) if name == "speak" else roster.plan_many(calls)
+                    if i >= 2 * warmup:
+                        timed[name]["python_us"].append((time.perf_counter() - t0) * 1e6)
+                        timed[name]["kernels_us"].append(r.timing["kernels_us"])
+                        timed[name]["end_to_end_us"].append(r.timing["end_to_end_us"])
+                        timed[name]["copies"].add((r.timing["h2d_bytes"], r.timing["d2h_bytes"]))
+                for name, t in timed.items():
+                    if len(t["copies"]) != 1:
+                        raise SystemExit(f"devpath: speak {k}, {colour}: timed {name} calls copied {sorted(t['copies'])} bytes")
+                fields = ("kernels_us", "end_to_end_us", "python_us")
+                sp = {f: _stats(timed["speak"][f]) for f in fields}
+                pl = {f: _stats(timed["plan"][f]) for f in fields}
+                h2d, d2h = timed["speak"]["copies"].pop()
+                ph2d, pd2h = timed["plan"]["copies"].pop()
+                cpu = speak_cpu_us(events, reps, warmup)
+                derived = 2 * k * pb["format_line_once_ns"] / 1e3
+                cases.append({"n": n, "k": k, "text": "say", "colour": colour, "ban_swearing": True,
+                              "recipients": k * (n - 1), **sp, "h2d_bytes": h2d, "d2h_bytes": d2h,
+                              "plan_many_of_the_composed_lines": {**pl, "h2d_bytes": ph2d, "d2h_bytes": pd2h},
+                              "composing_adds_us": {f: round(sp[f]["median"] - pl[f]["median"], 2) for f in fields},
+                              "composing_adds_us_per_event": {f: round((sp[f]["median"] - pl[f]["median"]) / k, 3)
+                                                              for f in fields},
+                              "cpu_us": cpu, "cpu_derived_us": round(derived, 3),
+                              "composing_adds_end_to_end_over_cpu":
+                                  round((sp["end_to_end_us"]["median"] - pl["end_to_end_us"]["median"]) / cpu["median"], 2)})
+    return {"speak_kernels": ["nuts_roster_speak", "nuts_roster_speak_plan"],
+            "speak_end_to_end_covers": "packing the K events into pinned memory, one H2D (the table and the speaker "
+                                       "state only in a call after an update of theirs), two kernels, one D2H of the "
+                                       "outcomes, the composed texts, both plans' variants and chunk sizes and the admit "
+                                       "bitmap at their bound size, one synchronise (python_us adds checking the K "
+                                       "events and their speakers, the copies out of pinned memory and building the "
+                                       "Speech)",
+            "speak_cpu_us_covers": "np_say_verb + np_contains_swearing + the two snprintf formats of say() per event, "
+                                   "one ctypes call each; cpu_derived_us is 2 x K x pathbench's format_line_once_ns, "
+                                   "without the calls and without the verb and the swear scan",
+            "speak": cases}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=2000, help="timed broadcasts per case (default 2000)")
@@ -286,6 +384,9 @@ def main(argv=None) -> int:
     ap.add_argument("--review", type=per_call_counts, default=None, metavar="Q[,Q...]",
                     help="also time Roster.review_many of Q rooms per call, for each Q, and what recording adds to "
                          "plan_many (the review section)")
+    ap.add_argument("--speak", type=per_call_counts, default=None, metavar="K[,K...]",
+                    help="also time K say events per Roster.speak_many call, for each K, beside plan_many of the "
+                         "same lines composed beforehand (the speak section)")
     a = ap.parse_args(argv)
     if a.reps < 1 or a.warmup < 0:
         ap.error("--reps must be >= 1 and --warmup >= 0")
@@ -365,6 +466,7 @@ def main(argv=None) -> int:
                      for n in SIZES for text in TEXTS for colour in COLOURS for k in a.plan],
         }
     review = review_cases(a.review, a.reps, a.warmup, pb) if a.review else {}
+    speak = speak_cases(a.speak, a.reps, a.warmup, pb) if a.speak else {}
     out = {
         "what": "user-space stage of one broadcast (admit predicate + transducer), device vs CPU",
         "device": "gfx950",
@@ -378,6 +480,7 @@ def main(argv=None) -> int:
         **roster,
         **plan,
         **review,
+        **speak,
         "wall_s": round(time.perf_counter() - t_start, 1),
     }
     print(json.dumps(out))
