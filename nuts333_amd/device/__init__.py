@@ -26,6 +26,17 @@ like a :class:`Plan`.  ``Roster.clear_review(rooms)`` is ``clear_revbuff``.
 ``Roster.speak_many(events)`` does for K ``(slot, com, inpstr, word_count)`` events what ``say()``, ``shout()``,
 ``emote()`` and ``semote()`` do (nuts333.c:4062-4226): the muzzle, "Say what?" and swearing checks, the verb, the
 invisible speaker's name, the two composed texts, and their plans -- a :class:`Speech`.
+``Roster.input_many(reads)`` starts one stage earlier, from K ``(slot, data)`` reads of clients in line mode, and does
+what ``user_input()`` and ``exec_com()`` do before a command function runs (nuts333.c:136-235, 403-432, 2350-2358,
+3753-3831): the read is cut at its first control byte, split into words, the ``; # ! < > -`` shortcuts are mapped, the
+command is looked up by prefix in the 92-entry table and checked against the speaker's ``level``
+(``Roster.update(level=)``), and the first word is stripped.  It returns an :class:`Input`: per read its ``kind`` (IAC,
+EMPTY, REPEAT, UNKNOWN, SPEECH or COMMAND), the command, ``word_count``, the line and ``inpstr`` ranges, and a
+``Speech`` of K entries in which every SPEECH read is answered as ``speak_many`` answers it, an UNKNOWN read has the
+reply ``Unknown command.`` and every other read is void.  Left to the caller: a REPEAT read (``.`` alone: substitute
+the user's stored line and resubmit; with none stored the reference answers ``Unknown command.``), AFK users, users away
+over a netlink (rejected, as in ``speak_many``), reads that do not end a line (``get_charclient_line``'s per-user
+buffer), the prompt, and every command that is not speech: COMMAND hands back ``com``, ``inpstr`` and ``word_count``.
 
 Input is validated before the device is touched (``ValueError``).  The library ``_build/libnuts_device.so`` is built by
 ``__graft_entry__.build()`` where ``hipcc`` exists, and on demand here when it is missing or older than its source.
@@ -60,7 +71,7 @@ KERNELS = ("nuts_fanout_measure_broadcast", "nuts_fanout_emit_broadcast",
            "nuts_fanout_measure_batch", "nuts_fanout_emit_batch",
            "nuts_fanout_measure_many", "nuts_fanout_emit_many",
            "nuts_roster_measure", "nuts_roster_emit", "nuts_roster_plan", "nuts_roster_record", "nuts_roster_review",
-           "nuts_roster_speak", "nuts_roster_speak_plan")
+           "nuts_roster_speak", "nuts_roster_speak_plan", "nuts_roster_parse")
 #: NP_ARR_SIZE (nuts333.h:19): the input line a speech command receives is at most 999 bytes
 ARR_SIZE = 1000
 #: USER_NAME_LEN (nuts333.h:23) and invisname (nuts333.h:150), the name an invisible speaker is shown by
@@ -76,6 +87,15 @@ COMPOSED_EXTRA = 32
 _SPEAK_SLACK = 36
 #: the flags byte of a slot's speaker state, as fanout.hip reads it
 SPEECH_FLAGS = {"vis": 1, "muzzled": 2, "command_mode": 4}
+#: where a slot's speaker state keeps the speaker's level, and the highest one (enum np_level: NEW 0 .. GOD 4)
+_LEVEL_BYTE, MAX_LEVEL = 14, 4
+#: what became of a read (Input.kind): a telnet IAC reply, a line without a word, "." alone, a line exec_com answers
+#: "Unknown command.", a say / shout / emote / semote, any other command
+IAC, EMPTY, REPEAT, UNKNOWN, SPEECH, COMMAND = 0, 1, 2, 3, 4, 5
+#: Speech.outcome of an input_many read that no speech command answers
+NOT_SPEECH = -1
+#: user_input reads at most ARR_SIZE bytes at a time (nuts333.c:142)
+READ_SIZE = ARR_SIZE
 #: broadcast_many() refuses a call whose arena bound, the sum over its broadcasts of N * max_bytes(len), exceeds this;
 #: Roster.plan_many() one whose variant bound, 12 * text bytes + 16 * K, does
 MANY_ARENA_CAP = 2 << 30
@@ -293,7 +313,9 @@ class Speech:
     ``reply`` plans what the speaker alone gets -- the echo of a say or a shout, or the notice: ``reply.admitted(k)`` is
     the speaker's slot alone when there is a reply, else empty with zero sizes (a spoken emote or semote has none: no
     ``write_user`` call at all, which is not the 4-byte reset of an empty text).  Both are ordinary plans and share one
-    variant buffer.  ``line(k)`` / ``reply_text(k)`` are the composed texts before the transducer."""
+    variant buffer.  ``line(k)`` / ``reply_text(k)`` are the composed texts before the transducer.  In the ``Speech`` of
+    an :class:`Input` the outcome of a read that no speech command answers is NOT_SPEECH: it has neither text, but for
+    the reply ``Unknown command.`` of an UNKNOWN read."""
     outcome: np.ndarray           # int8 [K]
     room: Plan
     reply: Plan
@@ -316,6 +338,40 @@ class Speech:
     def reply_text(self, k: int) -> bytes:
         """What event ``k`` sends to its speaker alone: the echo or the notice; ``b""`` when there is none."""
         return self._text(1, k)
+
+
+@dataclass
+class Input:
+    """What ``user_input()`` and ``exec_com()`` make of K reads (``Roster.input_many``).  ``kind[k]`` is IAC, EMPTY,
+    REPEAT, UNKNOWN, SPEECH or COMMAND; ``com[k]`` the command (enum np_com) of a SPEECH or COMMAND read, else -1;
+    ``word_count[k]`` the talker's, 0 .. 9 (0 for IAC); the line is ``data[:line_sizes[k]]`` (0 for IAC, which is not
+    framed) and ``inpstr(k)`` what the command function receives, for a SPEECH or COMMAND read.  ``speech`` has K
+    entries: a SPEECH read's is what ``speak_many`` returns for ``(slot, com, inpstr, word_count)`` -- except a say
+    that came through ``exec_com`` with fewer than two words, which is NOTHING (``Say what?``) whatever the speaker's
+    muzzle and mode --, an UNKNOWN read's has the reply ``Unknown command.`` and no line, every other read's is void;
+    the outcome of all that is not SPEECH is NOT_SPEECH."""
+    kind: np.ndarray              # int8 [K]
+    com: np.ndarray               # int8 [K]   -1: none
+    word_count: np.ndarray        # uint8 [K]
+    line_sizes: np.ndarray        # int32 [K]
+    inpstr_starts: np.ndarray     # int64 [K]  into read k's own data
+    inpstr_sizes: np.ndarray      # int64 [K]  -1: there is no inpstr
+    speech: Speech
+    data: list = field(default_factory=list)     # the K reads' bytes, as given
+    timing: dict = field(default_factory=dict)   # as Speech's
+
+    def inpstr(self, k: int) -> bytes:
+        """What the command function of read ``k`` receives; ``b""`` when there is none."""
+        if not 0 <= k < len(self.kind):
+            raise IndexError(f"no read {k}: {len(self.kind)} reads")
+        at, n = int(self.inpstr_starts[k]), int(self.inpstr_sizes[k])
+        return bytes(self.data[k][at:at + n]) if n >= 0 else b""
+
+    def line(self, k: int) -> bytes:
+        """Read ``k`` cut at its first control byte."""
+        if not 0 <= k < len(self.kind):
+            raise IndexError(f"no read {k}: {len(self.kind)} reads")
+        return bytes(self.data[k][:int(self.line_sizes[k])])
 
 
 # ------------------------------------------------------------------ validation (never touches the device)
@@ -490,6 +546,10 @@ def _load():
         lib.nd_roster_speak.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int64, P, P, P, P, P, ctypes.c_int,
                                         ctypes.c_int, P, P, P, P, P, P, P, P, P, P, P, ctypes.POINTER(_RosterTiming)]
         lib.nd_roster_speak.restype = ctypes.c_int
+        lib.nd_roster_input.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int64, P, P, P, ctypes.c_int,
+                                        ctypes.c_int, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
+                                        ctypes.POINTER(_RosterTiming)]
+        lib.nd_roster_input.restype = ctypes.c_int
         lib.nd_arena.restype = P
         lib.nd_write_sizes.restype = P
         _LIB = lib
@@ -600,6 +660,31 @@ def _speaker_name(v) -> bytes:
     return v
 
 
+def _level(v) -> int:
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= MAX_LEVEL:
+        raise ValueError(f"level must be an int in [0, {MAX_LEVEL}] (enum np_level), not {v!r}")
+    return int(v)
+
+
+def _read_data(v) -> bytes:
+    """One read(2) of a client in line mode: 1 .. READ_SIZE bytes of any value, the last one ending the line."""
+    if isinstance(v, str):
+        try:
+            v = v.encode("latin-1")
+        except UnicodeEncodeError as e:
+            raise ValueError(f"data has a character outside one byte: {e}") from None
+    elif isinstance(v, (bytearray, memoryview)):
+        v = bytes(v)
+    if not isinstance(v, bytes):
+        raise ValueError(f"data must be bytes or str, not {type(v).__name__}")
+    if not 1 <= len(v) <= READ_SIZE:
+        raise ValueError(f"data of {len(v)} bytes: a read holds 1 .. {READ_SIZE}")
+    if 32 <= v[-1] < 128:
+        raise ValueError(f"the read does not end a line (its last byte is {v[-1]}, not below 32 as a signed char): it "
+                         f"belongs to get_charclient_line, whose per-user buffer the roster does not keep")
+    return v
+
+
 #: the commands speak_many answers, and whether their room line goes to the speaker's room (and is recorded there)
 _SPEECH_COMS = {COM_SAY: True, COM_SHOUT: False, COM_EMOTE: True, COM_SEMOTE: False}
 
@@ -641,7 +726,8 @@ class Roster:
         self._room[:] = -1
         self._dirty = True
         # the speakers' mirror, as nd_roster_speak takes it: 16 bytes per slot -- 12 name bytes, the name's length, a
-        # flags byte (SPEECH_FLAGS), two bytes of padding.  Only speak_many uploads it, after an update of its fields
+        # flags byte (SPEECH_FLAGS), the level, a byte of padding.  Only speak_many and input_many upload it, after an
+        # update of its fields
         self._speech = np.zeros((self.capacity, 16), dtype=np.uint8)
         self._speech[:, USER_NAME_LEN + 1] = SPEECH_FLAGS["vis"]
         self._speech_dirty = True
@@ -658,7 +744,7 @@ class Roster:
         return int(v)
 
     def update(self, slots, *, room=_KEEP, login=_KEEP, ignall=_KEEP, ignshout=_KEEP, colour=_KEEP, name=_KEEP,
-               vis=_KEEP, muzzled=_KEEP, command_mode=_KEEP) -> None:
+               vis=_KEEP, muzzled=_KEEP, command_mode=_KEEP, level=_KEEP) -> None:
         """Set fields of ``slots`` (a slot or a sequence of them).  Each field given is one value for every slot or a
         sequence of one per slot; a field not given stays as it is.  ``room`` is None (no room) or an int in
         [0, ROOM_LIMIT); the flags are 0/1 or bools.  A slot given more than once takes its last values.  Nothing
@@ -667,7 +753,9 @@ class Roster:
         ``name`` (bytes or str of 1 .. USER_NAME_LEN bytes, no NUL; unset at first), ``vis`` (1 at first), ``muzzled``
         and ``command_mode`` (0 at first) are what the speech commands read of a speaker.  They live in a mirror of
         their own that only :meth:`speak_many` uploads: an update of these fields alone does not make the next
-        ``broadcast_many`` / ``plan_many`` upload the table."""
+        ``broadcast_many`` / ``plan_many`` upload the table.  ``level`` (an int in [0, MAX_LEVEL] as enum np_level, 0
+        -- NEW -- at first) lives there too: :meth:`input_many` checks a command's minimum level against it, and
+        ``speak_many`` does not read it."""
         self._check_open()
         if isinstance(slots, (int, np.integer)):
             slots = [slots]
@@ -702,6 +790,7 @@ class Roster:
                 names = [_speaker_name(x) for x in name]
         speech = {f: per_slot(f, v, lambda x, f=f: _flag(f, x), np.uint8)
                   for f, v in (("vis", vis), ("muzzled", muzzled), ("command_mode", command_mode)) if v is not _KEEP}
+        levels = None if level is _KEEP else per_slot("level", level, _level, np.uint8)
         _, last = np.unique(idx[::-1], return_index=True)        # each slot's last position: last write wins
         keep = n - 1 - last
         at = idx[keep]
@@ -718,9 +807,11 @@ class Roster:
         for f, v in speech.items():
             bit, col = np.uint8(SPEECH_FLAGS[f]), self._speech[:, USER_NAME_LEN + 1]
             col[at] = np.where(v[keep] != 0, col[at] | bit, col[at] & ~bit)
-        if names is not None or speech:
+        if levels is not None:
+            self._speech[at, _LEVEL_BYTE] = levels[keep]
+        if names is not None or speech or levels is not None:
             self._speech_dirty = True
-        if rooms is not None or flags or not (names is not None or speech):
+        if rooms is not None or flags or not (names is not None or speech or levels is not None):
             self._dirty = True
 
     def table(self, rm, sender) -> np.ndarray:
@@ -1028,10 +1119,15 @@ class Roster:
         self._dirty = self._speech_dirty = False
         if recording:
             self._clear_sent()
+        return self._speech_of(len(text), text_off, slots, outcome, clen, bits, vn, vw, vwsz, ctext, var, t)
+
+    def _speech_of(self, text_bytes, text_off, slots, outcome, clen, bits, vn, vw, vwsz, ctext, var, t) -> Speech:
+        """The Speech of what nd_roster_speak / nd_roster_input filled in."""
+        k, words = len(slots), (self.capacity + 63) // 64
         # the buffers' layout (nd_roster_speak): text t = k is event k's room line, K + k its reply
         tstarts = np.empty((2, k), dtype=np.int64)
         tstarts[0] = text_off.astype(np.int64) + _SPEAK_SLACK * np.arange(k, dtype=np.int64)
-        tstarts[1] = tstarts[0] + len(text) + _SPEAK_SLACK * k
+        tstarts[1] = tstarts[0] + text_bytes + _SPEAK_SLACK * k
         starts = np.empty((2, k, 2), dtype=np.int64)
         starts[:, :, 0] = 12 * tstarts + 16 * np.arange(2 * k, dtype=np.int64).reshape(2, k)
         starts[:, :, 1] = starts[:, :, 0] + ((6 * np.maximum(clen, 0).astype(np.int64) + 4 + 3) & ~3)
@@ -1046,6 +1142,111 @@ class Roster:
                       timing=dict(timing)) for i, b in enumerate((bits, reply_bits))]
         return Speech(outcome=outcome, room=plans[0], reply=plans[1], texts=ctext, text_starts=tstarts,
                       text_sizes=clen.astype(np.int64), timing=timing)
+
+    def _prepare_input(self, reads, ban_swearing, record):
+        """Each (slot, data) and its speaker's state checked, packed for nd_roster_input: the reads as given, their
+        bytes, offsets and lengths, the slots, the two flags."""
+        if isinstance(reads, (str, bytes, bytearray, np.ndarray)) or not hasattr(reads, "__len__"):
+            raise ValueError(f"reads must be a sequence of tuples, not {type(reads).__name__}")
+        if len(reads) == 0:
+            raise ValueError("empty call: no reads")
+        ban_swearing, record = _flag("ban_swearing", ban_swearing), _flag("record", record)
+        if len(reads) * self.capacity >= 2**31 - 1:
+            raise ValueError(f"{len(reads)} reads to {self.capacity} slots: K x capacity must be below 2^31 - 1")
+        datas, slots = [], []
+        for k, rd in enumerate(reads):
+            if not isinstance(rd, tuple) or len(rd) != 2:
+                raise ValueError(f"read {k}: expected a (slot, data) tuple, "
+                                 f"got {type(rd).__name__}{f' of {len(rd)}' if isinstance(rd, tuple) else ''}")
+            try:
+                slot = self._slot(rd[0])
+                data = _read_data(rd[1])
+                if self._room[slot] < 0:
+                    raise ValueError(f"the speaker, slot {slot}, has no room (the talker relays such a user over its "
+                                     f"netlink)")
+                if self._flags[slot] & ROSTER_FLAGS["login"]:
+                    raise ValueError(f"the speaker, slot {slot}, is still logging in")
+                if self._speech[slot, USER_NAME_LEN] == 0:
+                    raise ValueError(f"the speaker, slot {slot}, has no name")
+                if record and not 0 <= self._room[slot] < self.review_rooms:     # the device decides what is a say
+                    raise ValueError(f"it may be recorded, but room {int(self._room[slot])} has no review ring: " +
+                                     (f"the ring rooms are 0 .. {self.review_rooms - 1}" if self.review_rooms else
+                                      "the roster has none (review_rooms is 0)"))
+            except ValueError as e:
+                raise ValueError(f"read {k}: {e}") from None
+            datas.append(data)
+            slots.append(slot)
+        lens = np.fromiter((len(d) for d in datas), dtype=np.int64, count=len(datas))
+        bound = 12 * (2 * int(lens.sum()) + 2 * _SPEAK_SLACK * len(lens)) + 32 * len(lens)
+        if bound > MANY_ARENA_CAP:
+            raise ValueError(f"call too large: its variant bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
+                             f"(MANY_ARENA_CAP): split it")
+        off = np.zeros(len(datas), dtype=np.int32)
+        np.cumsum(lens[:-1], out=off[1:])
+        return datas, b"".join(datas), off, lens.astype(np.int32), np.array(slots, dtype=np.int32), ban_swearing, record
+
+    def input_many(self, reads, ban_swearing=False, record=False) -> Input:
+        """K reads of clients in line mode in one device call: a non-empty sequence of ``(slot, data)`` tuples, what
+        ``user_input()`` gets from ``read(2)`` (nuts333.c:136-235).  ``data`` is bytes, bytearray, memoryview or a
+        latin-1 str of 1 .. READ_SIZE bytes of any value, NUL included, whose last byte is below 32 as a signed char;
+        a read that does not end so belongs to ``get_charclient_line``, whose per-user buffer the roster does not keep.
+        The speaker must have a room, a name and no ``login`` flag, as for :meth:`speak_many`.  Anything else raises
+        ``ValueError("read k: ...")`` before the device is touched.
+
+        The device does, per read and in the reference's order: ``data[0] == 255`` is IAC and nothing else happens; the
+        line is ``data`` up to its first byte below 32 as a signed char (``np_terminate``); it is split as
+        ``np_wordfind`` splits it, a run of more than 39 bytes counting as several words and ten or more words as nine;
+        ``.`` alone is REPEAT; a line without a word is EMPTY; a speaker not in ``command_mode`` whose line does not
+        begin with one of ``.;!<>-#`` says the whole line; otherwise ``exec_com``'s front part (nuts333.c:3753-3785)
+        finds the command -- ``comword`` is the first word without one leading ``.``, the words ``>``, ``<``, ``-`` and
+        ``!`` are tell, pemote, echo and shout, a line that begins with ``;`` or ``#`` is an emote or semote of the
+        whole line, and else the first of the 92 names that begins with ``comword`` wins and ``inpstr`` starts at the
+        second word (``np_remove_first``).  No command, or one above the speaker's ``level``, is UNKNOWN; say, shout,
+        emote and semote are SPEECH, answered as :meth:`speak_many` answers ``(slot, com, inpstr, word_count)``; every
+        other command is COMMAND and left to the caller.  A say through ``exec_com`` with fewer than two words is
+        answered ``Say what?`` before the muzzle is looked at, whatever the mode (nuts333.c:3826-3829).
+
+        ``record=True`` records as ``speak_many(record=True)`` does.  Which reads are says and emotes is decided on the
+        device, so every speaker must then stand in a ring room.
+
+        One upload (the table and the speaker state only after an update of theirs), three kernel launches
+        (nuts_roster_parse, nuts_roster_speak, nuts_roster_speak_plan) -- four in a call that records
+        (nuts_roster_record) --, one download at the bound size and one synchronise, whatever K and the capacity.  A
+        composed text's slot in the text buffer is ``len(data) + 36`` bytes wide."""
+        self._check_open()
+        datas, data, off, lens, slots, ban, record = self._prepare_input(reads, ban_swearing, record)
+        lib = _load()
+        handle = self._device_handle(lib)
+        k, words = len(lens), (self.capacity + 63) // 64
+        ctext_bytes = 2 * len(data) + 2 * _SPEAK_SLACK * k
+        kind, com = np.empty(k, dtype=np.int8), np.empty(k, dtype=np.int8)
+        wcs = np.empty(k, dtype=np.uint8)
+        line_len, inp_off, inp_len = (np.empty(k, dtype=np.int32) for _ in range(3))
+        outcome = np.empty(k, dtype=np.int8)
+        clen = np.empty((2, k), dtype=np.int32)
+        bits = np.empty((k, words), dtype=np.uint64)
+        vn = np.empty((2, k, 2), dtype=np.int64)
+        vw = np.empty((2, k, 2), dtype=np.int32)
+        vwsz = np.empty((2, k, 2, MAX_WRITES), dtype=np.int32)
+        ctext = np.empty(ctext_bytes, dtype=np.uint8)
+        var = np.empty(12 * ctext_bytes + 32 * k, dtype=np.uint8)
+        dbuf = np.frombuffer(data, dtype=np.uint8)
+        clear = self._pending_clear() if record else None
+        t = _RosterTiming()
+        rc = lib.nd_roster_input(handle, k, _ptr(dbuf), len(data), _ptr(off), _ptr(lens), _ptr(slots), ban, record,
+                                 _ptr(self._table) if self._dirty else None,
+                                 _ptr(self._speech) if self._speech_dirty else None,
+                                 _ptr(clear) if clear is not None else None, _ptr(kind), _ptr(com), _ptr(wcs),
+                                 _ptr(line_len), _ptr(inp_off), _ptr(inp_len), _ptr(outcome), _ptr(clen), _ptr(bits),
+                                 _ptr(vn), _ptr(vw), _ptr(vwsz), _ptr(ctext), _ptr(var), ctypes.byref(t))
+        if rc != 0:
+            raise RuntimeError(f"device input failed: {lib.nd_last_error().decode(errors='replace')}")
+        self._dirty = self._speech_dirty = False
+        if record:
+            self._clear_sent()
+        speech = self._speech_of(len(data), off, slots, outcome, clen, bits, vn, vw, vwsz, ctext, var, t)
+        return Input(kind=kind, com=com, word_count=wcs, line_sizes=line_len, inpstr_starts=inp_off.astype(np.int64),
+                     inpstr_sizes=inp_len.astype(np.int64), speech=speech, data=datas, timing=dict(speech.timing))
 
     def _ring_room(self, v) -> int:
         if (not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_))

@@ -963,7 +963,7 @@ static_assert(kBlock >= kRevTasks + 64 && kBlock >= kRevLines, "roster_review / 
 // emote / semote of oracle/talker_port.c) turn (user, command, inpstr, word_count) into a notice to the speaker, or into
 // the speaker's echo and the line its room, or every room, gets.  A roster keeps what they read of a speaker, 16 bytes per
 // slot in a device allocation of its own that never moves: 12 name bytes, the name's length, a flags byte (vis, muzzled,
-// command_mode) and two bytes of padding.
+// command_mode), the level (read by nuts_roster_parse alone) and a byte of padding.
 //   compose  nuts_roster_speak, one wave per event, four events per block.  The wave reads its speaker's state and decides
 //            the outcome in the reference's order, wave-uniformly: muzzled, nothing to say, swearing, spoken.  The swear
 //            scan is parallel over the bytes: lane l lowers A-Z in bytes 16l .. 16l+18 (its 16 and 3 of overlap) and
@@ -981,6 +981,9 @@ static_assert(kBlock >= kRevTasks + 64 && kBlock >= kRevLines, "roster_review / 
 //            admit bitmap, the speaker alone, is the host's).  A text of length -1 is void: nobody is admitted and both
 //            variants have 0 bytes in 0 writes -- not the 4-byte reset of an empty text.
 //   record   nuts_roster_record, as it is, on the arrays the compose kernel wrote.
+//   preset   nd_roster_input's events come from nuts_roster_parse with a verdict each (SpeakArgs.preset; see there): a
+//            void event has no text at all, an unknown command has exec_com's reply and no line, a forced "Say what?"
+//            skips the muzzle and the mode.  Without a preset array every event is what nd_roster_speak was given.
 constexpr int kComSay = 3, kComEmote = 6;                  // enum np_com: NP_SAY, NP_EMOTE
 constexpr int kArrSize = 1000;                             // nuts333.h:19 ARR_SIZE: inpstr is at most 999 bytes
 constexpr int kSpeakSlack = 36;                            // a composed text's slot is this much wider than inpstr
@@ -989,6 +992,9 @@ constexpr int kNameLen = 12;                               // nuts333.h:23 USER_
 constexpr uint8_t kVis = 1, kMuzzled = 2, kCommandMode = 4;   // the flags byte of a slot's speaker state
 constexpr int kSpoken = 0, kOutMuzzled = 1, kOutNothing = 2, kOutSwearing = 3;
 constexpr int kSwearSlice = 16;                            // bytes of inpstr per lane in the swear scan
+constexpr int kNotSpeech = -1;                             // the outcome of an event that no speech command answers
+// what nuts_roster_parse decided of an event before the command functions run (SpeakArgs.preset)
+constexpr uint8_t kPresetNone = 0, kPresetVoid = 1, kPresetNothing = 2, kPresetUnknown = 3;
 
 struct SpeakArgs {
     const int32_t* room;         // [capacity] the roster's table: -1, no room
@@ -1001,6 +1007,7 @@ struct SpeakArgs {
     const int32_t* slot;         // [k] the speaker
     const uint8_t* com;          // [k] NP_SAY, NP_SHOUT, NP_EMOTE or NP_SEMOTE
     const uint8_t* words;        // [k] word_count
+    const uint8_t* preset;       // [k] nuts_roster_parse's verdict; nullptr: every event is a speech event as it stands
     const int32_t* ctext_off;    // [2k] where each composed text's slot starts in ctext
     int k, capacity, blocks;     // blocks: those that compose; the ones after them copy the speaker table
     int ban_swearing, record;
@@ -1077,6 +1084,24 @@ __device__ void roster_speak(const SpeakArgs& a)
     const int lane = (int)threadIdx.x & 63;
     const int k = (int)blockIdx.x * (kBlock / 64) + ((int)threadIdx.x >> 6);      // wave-uniform
     if (k >= a.k) return;
+    const uint8_t preset = a.preset ? a.preset[k] : kPresetNone;
+    const Piece none{nullptr, 0};
+    if (preset == kPresetVoid || preset == kPresetUnknown) {   // no speech command runs: no line, nothing recorded, and
+        int reply_len = -1;                                    // exec_com's own notice (c:3763, 3782) or nothing at all
+        if (preset == kPresetUnknown) {
+            const Piece p[5] = {lit("Unknown command.\n"), none, none, none, none};
+            reply_len = compose(a.ctext + a.ctext_off[a.k + k], kSpeakSlack, p, nullptr, 0, false, lane, a.violations);
+        }
+        if (lane == 0) {
+            a.clen[k] = -1;
+            a.clen[a.k + k] = reply_len;
+            a.rm[k] = a.sender[k] = -1;
+            a.com_num[k] = 0;
+            a.flags[k] = 0;
+            a.outcome[k] = (int8_t)kNotSpeech;
+        }
+        return;
+    }
     const int slot = a.slot[k], com = a.com[k], wc = a.words[k], len = a.text_len[k];
     const uint8_t* in = a.text + a.text_off[k];
     const uint8_t* sp = a.speech + (size_t)slot * kSpeechRec;
@@ -1088,14 +1113,14 @@ __device__ void roster_speak(const SpeakArgs& a)
 
     // say() c:4068-4082, shout() c:4110-4118, emote() c:4192-4200, semote() c:4216-4221, in their order
     int outcome = kSpoken;
-    if (state & kMuzzled) outcome = kOutMuzzled;
+    if (preset == kPresetNothing) outcome = kOutNothing;       // exec_com's "Say what?" (c:3826-3829), before say()
+    else if (state & kMuzzled) outcome = kOutMuzzled;
     else if (say ? wc < 2 && (state & kCommandMode) : shout ? wc < 2 : wc < 2 && (int8_t)b1 < 33) outcome = kOutNothing;
     else if (a.ban_swearing && com != kComSemote && swears(in, len, lane)) outcome = kOutSwearing;
 
     uint8_t* line = a.ctext + a.ctext_off[k];
     uint8_t* reply = a.ctext + a.ctext_off[a.k + k];
     const int cap = len + kSpeakSlack;
-    const Piece none{nullptr, 0};
     int line_len = -1, reply_len = -1;
     if (outcome == kOutMuzzled) {
         const Piece p[5] = {say ? lit("You are muzzled, you cannot speak.\n") : shout ? lit("You are muzzled, you cannot shout.\n")
@@ -1217,6 +1242,215 @@ __device__ void roster_speak_plan(const SpeakPlanArgs& a)
 
 static_assert(kArrSize - 1 + kSpeakSlack < kTextSize, "roster_speak_plan: a composed text fits stage_variants' LDS text");
 
+// ------------------------------------------------------------------ client reads of a resident roster
+//
+// The stage in front of the speech commands: what user_input() and exec_com() do with one read(2) of a client in line
+// mode before a command function runs (nuts333.c:136-235, 403-432, 2350-2358, 3753-3831; user_input / exec_com of
+// oracle/talker_port.c with np_terminate, np_wordfind, np_remove_first, np_command_lookup and np_command_level of
+// oracle/nuts_path.c).  The speaker's level is byte 14 of its 16 bytes of speaker state.
+//   parse    nuts_roster_parse, one wave per read, four reads per block; lane l owns bytes 16l .. 16l+15 of the read and
+//            keeps two 16-bit masks of them: "ends the line" (the byte as a signed char is below 32) and "word byte"
+//            (above 32, and in front of the line's end).  Every position the reference finds with a byte loop is the
+//            first set bit at or after some index: a ballot over "my slice has one" gives the lane, that lane's mask the
+//            byte (first_from).  So come the line's end n, the first word's start and end, and where np_remove_first
+//            stops.  np_wordfind cuts a run of word bytes every 39 bytes, so a word starts where the distance from the
+//            run's start is a multiple of 39.  The distance a lane's first byte inherits is a segmented scan over the
+//            lanes whose operator carries one flag, "this slice is all word bytes"; it collapses to the nearest lane
+//            below that is not, found with a ballot, and that lane's trailing word bytes.  The starts are summed over the
+//            wave; ten or more count as nine.
+//            The command is the first of the 92 names that begins with comword: lane l tests entries l and l + 64 on
+//            names packed into twelve bytes, two ballots and the lowest set bit answer.
+//            Lane 0 writes what the caller gets (kind, command, word_count, the line's length, where inpstr starts and
+//            its length) and, in place, what nuts_roster_speak reads as its event: the same arrays, and a preset.
+//   preset   void: no speech command runs, the event has no text at all.  unknown: the reply is exec_com's
+//            "Unknown command.\n".  nothing: a say that came through exec_com with fewer than two words is answered
+//            "Say what?" there (c:3826-3829), before say() looks at the muzzle or the mode.
+constexpr int kReadSlice = 16;                             // bytes of a read per lane
+constexpr int kWordLen = 39;                               // nuts333.h:18 WORD_LEN - 1: the longest word[] entry
+constexpr int kMaxWords = 10;                              // nuts333.h:17 MAX_WORDS
+constexpr int kLevelByte = kNameLen + 2;                   // the speaker's level in its speaker state
+constexpr int kKindIac = 0, kKindEmpty = 1, kKindRepeat = 2, kKindUnknown = 3, kKindSpeech = 4, kKindCommand = 5;
+constexpr int kComTell = 5, kComPemote = 8, kComEcho = 9;  // enum np_com: NP_TELL, NP_PEMOTE, NP_ECHO
+constexpr int kNumCommands = 92;
+constexpr int kNew = 0, kUser = 1, kWiz = 2, kArch = 3, kGod = 4;   // nuts333.h:51-55
+
+// A command: its name's bytes 0 .. 7 in lo, 8 and 9 in the low half of hi, padded with zeros; its level in hi's top byte.
+struct Command {
+    uint64_t lo;
+    uint32_t hi;
+};
+constexpr Command cmd(const char* name, int level)
+{
+    Command c{0, (uint32_t)level << 24};
+    for (int i = 0; name[i]; i++) {
+        if (i < 8) c.lo |= (uint64_t)(uint8_t)name[i] << (8 * i);
+        else c.hi |= (uint32_t)(uint8_t)name[i] << (8 * (i - 8));
+    }
+    return c;
+}
+// names nuts333.h:157-177, minimum levels nuts333.h:206-226, in enum np_com's order
+__constant__ Command kCommands[kNumCommands] = {
+    cmd("quit", kNew), cmd("look", kNew), cmd("mode", kNew), cmd("say", kNew), cmd("shout", kUser),
+    cmd("tell", kUser), cmd("emote", kUser), cmd("semote", kUser), cmd("pemote", kUser), cmd("echo", kUser),
+    cmd("go", kUser), cmd("ignall", kUser), cmd("prompt", kNew), cmd("desc", kUser), cmd("inphr", kUser),
+    cmd("outphr", kUser), cmd("public", kUser), cmd("private", kUser), cmd("letmein", kUser), cmd("invite", kUser),
+    cmd("topic", kUser), cmd("move", kWiz), cmd("bcast", kWiz), cmd("who", kNew), cmd("people", kWiz),
+    cmd("help", kNew), cmd("shutdown", kGod), cmd("news", kUser), cmd("read", kNew), cmd("write", kUser),
+    cmd("wipe", kWiz), cmd("search", kUser), cmd("review", kUser), cmd("home", kUser), cmd("status", kNew),
+    cmd("version", kNew), cmd("rmail", kNew), cmd("smail", kUser), cmd("dmail", kUser), cmd("from", kUser),
+    cmd("entpro", kUser), cmd("examine", kUser), cmd("rmst", kNew), cmd("rmsn", kNew), cmd("netstat", kWiz),
+    cmd("netdata", kArch), cmd("connect", kGod), cmd("disconnect", kGod), cmd("passwd", kUser), cmd("kill", kArch),
+    cmd("promote", kWiz), cmd("demote", kWiz), cmd("listbans", kWiz), cmd("ban", kArch), cmd("unban", kArch),
+    cmd("vis", kArch), cmd("invis", kArch), cmd("site", kWiz), cmd("wake", kUser), cmd("wizshout", kWiz),
+    cmd("muzzle", kWiz), cmd("unmuzzle", kWiz), cmd("map", kUser), cmd("logging", kGod), cmd("minlogin", kGod),
+    cmd("system", kWiz), cmd("charecho", kNew), cmd("clearline", kArch), cmd("fix", kGod), cmd("unfix", kGod),
+    cmd("viewlog", kWiz), cmd("accreq", kNew), cmd("revclr", kUser), cmd("clone", kArch), cmd("destroy", kArch),
+    cmd("myclones", kArch), cmd("allclones", kUser), cmd("switch", kArch), cmd("csay", kArch), cmd("chear", kArch),
+    cmd("rstat", kWiz), cmd("swban", kArch), cmd("afk", kUser), cmd("cls", kNew), cmd("colour", kNew),
+    cmd("ignshout", kUser), cmd("igntell", kUser), cmd("suicide", kNew), cmd("delete", kGod), cmd("reboot", kGod),
+    cmd("recount", kGod), cmd("revtell", kUser),
+};
+constexpr int kNameMax = 10;                               // the longest name, "disconnect"
+
+struct ParseArgs {
+    const uint8_t* speech;       // [capacity * 16] the speaker state this call reads, as SpeakArgs.speech
+    const uint8_t* data;         // the K reads, packed
+    const int32_t* read_off;     // [k]
+    const int32_t* read_len;     // [k] 1 .. 1000; the last byte ends the line
+    const int32_t* slot;         // [k] the speaker
+    int k;
+    int8_t* kind;                // [k]
+    int8_t* com;                 // [k] the command; -1: none.  SpeakArgs.com
+    uint8_t* words;              // [k] word_count.  SpeakArgs.words
+    int32_t* line_len;           // [k]
+    int32_t* text_off;           // [k] where inpstr starts in data.  SpeakArgs.text_off
+    int32_t* text_len;           // [k] inpstr's length; -1: none.  SpeakArgs.text_len
+    uint8_t* preset;             // [k] SpeakArgs.preset
+};
+
+// The index of the first set bit at or after `from` over the wave's 64 x 16 mask bits, or `none`; wave-uniform.
+__device__ __forceinline__ int first_from(uint32_t bits, int from, int lane, int none)
+{
+    const int rel = from - kReadSlice * lane;
+    const uint32_t m = rel >= kReadSlice ? 0u : rel <= 0 ? bits : bits & ~((1u << rel) - 1u);
+    const uint64_t b = __ballot(m != 0);
+    if (!b) return none;
+    return __shfl(kReadSlice * lane + __ffs((int)m) - 1, __ffsll((unsigned long long)b) - 1);
+}
+
+__device__ void roster_parse(const ParseArgs& a)
+{
+    const int lane = (int)threadIdx.x & 63;
+    const int k = (int)blockIdx.x * (kBlock / 64) + ((int)threadIdx.x >> 6);      // wave-uniform
+    if (k >= a.k) return;
+    const int len = a.read_len[k];
+    const uint8_t* in = a.data + a.read_off[k];
+    const uint8_t* sp = a.speech + (size_t)a.slot[k] * kSpeechRec;
+    const bool command_mode = (sp[kNameLen + 1] & kCommandMode) != 0;
+    const int level = sp[kLevelByte];
+
+    uint32_t ends = 0, wordb = 0;           // a byte past the read counts as 0: it ends the line
+#pragma unroll
+    for (int x = 0; x < kReadSlice; x++) {
+        const int at = kReadSlice * lane + x;
+        const int c = at < len ? (int)(int8_t)in[at] : 0;
+        ends |= (uint32_t)(c < 32) << x;
+        wordb |= (uint32_t)(c > 32) << x;
+    }
+    const int n = first_from(ends, 0, lane, len);                                  // np_terminate, c:403-411
+    const int live = n - kReadSlice * lane;
+    wordb &= live >= kReadSlice ? 0xffffu : live <= 0 ? 0u : (1u << live) - 1u;
+
+    // np_wordfind, c:417-432: the distance my first byte inherits, then the word starts of my slice
+    const uint64_t full = __ballot(wordb == 0xffffu);
+    const uint64_t broken = ~full & ((1ull << lane) - 1);                          // lanes below me that end a run
+    const int prev = broken ? 63 - __clzll((long long)broken) : -1;
+    const int tail = __shfl(__clz((int)~(wordb << 16)), prev < 0 ? 0 : prev);      // that lane's trailing word bytes
+    const int carry = prev < 0 ? kReadSlice * lane : kReadSlice * (lane - 1 - prev) + tail;
+    int dist = carry % kWordLen, total = 0;
+#pragma unroll
+    for (int x = 0; x < kReadSlice; x++) {
+        if (wordb >> x & 1) {
+            total += dist == 0;
+            dist = dist == kWordLen - 1 ? 0 : dist + 1;
+        } else {
+            dist = 0;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) total += __shfl_xor(total, d);
+    const int wc = total >= kMaxWords ? kMaxWords - 1 : total;
+
+    const uint8_t b0 = in[0];
+    int kind, com = -1, start = 0, ilen = -1;
+    uint8_t preset = kPresetVoid;
+    if (b0 == 255) {                                                               // telnet IAC, c:150s
+        kind = kKindIac;
+    } else if (n == 1 && b0 == '.') {                                              // c:185: the caller's inpstr_old
+        kind = kKindRepeat;
+    } else if (total == 0) {                                                       // c:207-211
+        kind = kKindEmpty;
+    } else if (!command_mode && b0 != '.' && b0 != ';' && b0 != '!' && b0 != '<' && b0 != '>' && b0 != '-' && b0 != '#') {
+        kind = kKindSpeech;                                                        // c:213-214: say(user, inpstr)
+        com = kComSay;
+        ilen = n;
+        preset = kPresetNone;
+    } else {                                                                       // exec_com, c:3753-3785
+        const int w0 = first_from(wordb, 0, lane, n);                              // word[0]: there is one
+        const int w0_end = first_from(~wordb & 0xffffu, w0, lane, n);
+        const int rest = first_from(wordb, w0_end, lane, n);                       // np_remove_first, c:2350-2358
+        const int wlen = w0_end - w0 < kWordLen ? w0_end - w0 : kWordLen;
+        const uint8_t first = in[w0];
+        const int cw = w0 + (first == '.' ? 1 : 0), cwlen = w0 + wlen - cw;        // comword
+        kind = kKindUnknown;
+        preset = kPresetUnknown;
+        if (cwlen > 0) {
+            const bool whole = b0 == ';' || b0 == '#';                             // c:3769-3771: inpstr stays whole
+            if (whole) {
+                com = b0 == ';' ? kComEmote : kComSemote;
+            } else if (wlen == 1 && (first == '>' || first == '<' || first == '-' || first == '!')) {
+                com = first == '>' ? kComTell : first == '<' ? kComPemote : first == '-' ? kComEcho : kComShout;
+            } else if (cwlen <= kNameMax) {                                        // np_command_lookup, c:3776-3781
+                uint64_t lo = 0;
+                uint32_t hi = 0;
+#pragma unroll
+                for (int i = 0; i < kNameMax; i++) {
+                    const uint64_t c = i < cwlen ? in[cw + i] : 0;
+                    if (i < 8) lo |= c << (8 * i);
+                    else hi |= (uint32_t)c << (8 * (i - 8));
+                }
+                const uint64_t mlo = cwlen >= 8 ? ~0ull : (1ull << (8 * cwlen)) - 1;
+                const uint32_t mhi = cwlen <= 8 ? 0u : (1u << (8 * (cwlen - 8))) - 1u;
+                const Command e0 = kCommands[lane];
+                const Command e1 = kCommands[lane + 64 < kNumCommands ? lane + 64 : 0];
+                const uint64_t hit0 = __ballot((e0.lo & mlo) == lo && (e0.hi & mhi) == hi);
+                const uint64_t hit1 = __ballot(lane + 64 < kNumCommands && (e1.lo & mlo) == lo && (e1.hi & mhi) == hi);
+                com = hit0 ? __ffsll((unsigned long long)hit0) - 1 : hit1 ? 64 + __ffsll((unsigned long long)hit1) - 1 : -1;
+            }
+            if (com >= 0 && (int)(kCommands[com].hi >> 24) > level) com = -1;      // c:3782: as if there were none
+            if (com >= 0) {
+                const bool speech = com == kComSay || com == kComShout || com == kComEmote || com == kComSemote;
+                kind = speech ? kKindSpeech : kKindCommand;
+                preset = !speech ? kPresetVoid : com == kComSay && wc < 2 ? kPresetNothing : kPresetNone;
+                start = whole ? 0 : rest;
+                ilen = n - start;
+            }
+        }
+    }
+    if (lane == 0) {
+        a.kind[k] = (int8_t)kind;
+        a.com[k] = (int8_t)com;
+        a.words[k] = (uint8_t)wc;
+        a.line_len[k] = n;
+        a.text_off[k] = a.read_off[k] + start;
+        a.text_len[k] = ilen;
+        a.preset[k] = preset;
+    }
+}
+
+static_assert(64 * kReadSlice >= kArrSize + 1, "roster_parse: the 64 slices cover the longest read and a byte past it");
+static_assert(kNumCommands <= 128 && kLevelByte < kSpeechRec, "roster_parse: two table entries per lane; the level's byte");
+
 }  // namespace
 
 // Stable, unmangled kernel names (they are what rocprofv3 reports).
@@ -1233,6 +1467,7 @@ extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_record(RecordAr
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_review(ReviewArgs a) { roster_review(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_speak(SpeakArgs a) { roster_speak(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_speak_plan(SpeakPlanArgs a) { roster_speak_plan(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_parse(ParseArgs a) { roster_parse(a); }
 
 // ------------------------------------------------------------------------------------------ host library
 
@@ -1508,8 +1743,11 @@ size_t layout_review(uintptr_t base, int capacity, size_t clear_bytes, ReviewArg
 // speaker table (which the kept one, r.speech, is filled from), the call's inputs ending with violations, the results
 // next to each other, and last what only the kernels pass to each other.  One upload starts at the table, at the speaker
 // table or at the inputs, whichever is the first that changed.
+// nd_roster_input's (q given) differs in what describes an event: the upload carries the reads' offsets and lengths
+// where the inpstr's were, no commands and no word counts; nuts_roster_parse writes those, and they lie among the
+// results with what else it found.
 size_t layout_speak(uintptr_t base, size_t text_bytes, size_t clear_bytes, SpeakArgs& s, SpeakPlanArgs& p,
-                    const uint8_t** clear)
+                    const uint8_t** clear, ParseArgs* q = nullptr)
 {
     size_t at = 0;
     auto take = [&](auto*& ptr, size_t count) {
@@ -1522,16 +1760,31 @@ size_t layout_speak(uintptr_t base, size_t text_bytes, size_t clear_bytes, Speak
     take(p.slot, cap);
     take(s.speech_new, cap * kSpeechRec);
     take(s.text, text_bytes);
-    take(s.text_off, k);
-    take(s.text_len, k);
+    if (q) {
+        take(q->read_off, k);
+        take(q->read_len, k);
+    } else {
+        take(s.text_off, k);
+        take(s.text_len, k);
+    }
     take(s.slot, k);
-    take(s.com, k);
-    take(s.words, k);
+    if (!q) {
+        take(s.com, k);
+        take(s.words, k);
+    }
     take(s.ctext_off, 2 * k);
     take(*clear, clear_bytes);
     take(s.violations, 1);
     take(s.outcome, k);
     take(s.clen, 2 * k);
+    if (q) {
+        take(q->kind, k);
+        take(q->com, k);
+        take(q->words, k);
+        take(q->line_len, k);
+        take(q->text_off, k);
+        take(q->text_len, k);
+    }
     take(p.vn, 4 * k);
     take(p.vw, 4 * k);
     take(p.vwsz, 4 * k * kMaxWrites);
@@ -1542,6 +1795,16 @@ size_t layout_speak(uintptr_t base, size_t text_bytes, size_t clear_bytes, Speak
     take(s.sender, k);
     take(s.com_num, k);
     take(s.flags, k);
+    if (q) {
+        take(q->preset, k);
+        q->data = s.text;
+        q->slot = s.slot;
+        s.text_off = q->text_off;
+        s.text_len = q->text_len;
+        s.com = reinterpret_cast<const uint8_t*>(q->com);
+        s.words = q->words;
+        s.preset = q->preset;
+    }
     p.room = s.room;
     p.text = s.ctext;
     p.text_off = s.ctext_off;
@@ -2205,28 +2468,23 @@ int nd_roster_review(int handle, int q, const int32_t* rooms, const uint8_t* cle
     return 0;
 }
 
-// K speech events of roster `handle`, as say(), shout(), emote() and semote() answer them.  Event b: the speaker's slot
-// slots[b], the command coms[b] (NP_SAY 3, NP_SHOUT 4, NP_EMOTE 6, NP_SEMOTE 7), inpstr text[text_off[b] .. + text_len[b])
-// (packed: text_off[0] = 0, text_off[b + 1] = text_off[b] + text_len[b]; at most 999 bytes each) and word_count words[b].
-// table as nd_roster_plan's.  speech is NULL when no speaker state changed since the last nd_roster_speak of this roster,
-// else all of it: 16 bytes per slot, the name's 12 bytes, its length, a flags byte (vis 1, muzzled 2, command_mode 4) and
-// two bytes of padding; the first call of a roster must give it.  record: store the spoken says and emotes in their
-// rooms' rings, after clearing those that clear marks (NULL: none), as nd_roster_plan_record does; the caller has checked
-// that their speakers' rooms are ring rooms.
-// Outputs (host, caller-allocated), with W = ceil(capacity / 64) and text t = b for event b's room line, k + b for its
-// reply: outcome[k] (0 spoken, 1 muzzled, 2 nothing to say, 3 swearing); clen[2k] the composed texts' lengths, -1 where
-// there is none; ctext[2 * text_bytes + 72 * k] their bytes, text t at ctext_off(t) = text_off[b] + 36 * b, plus
-// text_bytes + 36 * k for a reply; bits[k * W] the room lines' admit bitmap, as nd_roster_plan's; vn[4k], vw[4k],
-// vwsz[4k * 16] the two variants of text t at 2t and 2t + 1, all zero for a text that is not there; var[12 * ctext bytes +
-// 32 * k] their bytes, text t's at 12 * ctext_off(t) + 16 * t and that plus (6 * clen[t] + 4 rounded up to 4).
-// Per call, whatever k and the capacity: one upload, two kernels (nuts_roster_speak, nuts_roster_speak_plan) and
-// nuts_roster_record as a third when record is set, one download at the bound size, one synchronise.
-// Returns 0, or -1 with nd_last_error() set.
-int nd_roster_speak(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off,
-                    const int32_t* text_len, const int32_t* slots, const uint8_t* coms, const uint8_t* words,
-                    int ban_swearing, int record, const uint8_t* table, const uint8_t* speech, const uint8_t* clear,
-                    int8_t* outcome, int32_t* clen, uint64_t* bits, int64_t* vn, int32_t* vw, int32_t* vwsz,
-                    uint8_t* ctext, uint8_t* var, nd_roster_timing* timing)
+// What nd_roster_input returns of nuts_roster_parse: host arrays of k entries each.
+struct ParseOut {
+    int8_t* kind;
+    int8_t* com;
+    uint8_t* words;
+    int32_t* line_len;
+    int32_t* inp_off;
+    int32_t* inp_len;
+};
+
+// nd_roster_speak (parsed NULL), and nd_roster_input: there text, text_off and text_len are the reads, coms and words
+// are NULL, and nuts_roster_parse runs first.
+static int speech_call(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off,
+                       const int32_t* text_len, const int32_t* slots, const uint8_t* coms, const uint8_t* words,
+                       int ban_swearing, int record, const uint8_t* table, const uint8_t* speech, const uint8_t* clear,
+                       int8_t* outcome, int32_t* clen, uint64_t* bits, int64_t* vn, int32_t* vw, int32_t* vwsz,
+                       uint8_t* ctext, uint8_t* var, nd_roster_timing* timing, const ParseOut* parsed)
 {
     Roster* r = roster_at(handle);
     if (!r || ensure_ready()) return -1;
@@ -2237,6 +2495,15 @@ int nd_roster_speak(int handle, int k, const uint8_t* text, int64_t text_bytes, 
     }
     int64_t sum = 0;
     for (int b = 0; b < k; b++) {       // the kernels index by these: nothing out of range reaches them
+        if (parsed) {                   // a read: 1 .. 1000 bytes, and its last byte ends the line
+            if (slots[b] < 0 || slots[b] >= cap || text_len[b] < 1 || text_len[b] > kArrSize || text_off[b] != sum ||
+                sum + text_len[b] > text_bytes || (int8_t)text[sum + text_len[b] - 1] >= 32) {
+                snprintf(g_err, sizeof(g_err), "read %d: slot, length, offset or last byte out of range", b);
+                return -1;
+            }
+            sum += text_len[b];
+            continue;
+        }
         const bool com_ok = coms[b] == kComSay || coms[b] == kComShout || coms[b] == kComEmote || coms[b] == kComSemote;
         if (slots[b] < 0 || slots[b] >= cap || !com_ok || text_len[b] < 0 || text_len[b] >= kArrSize ||
             text_off[b] != sum) {
@@ -2278,7 +2545,9 @@ int nd_roster_speak(int handle, int k, const uint8_t* text, int64_t text_bytes, 
     SpeakArgs so = s;                // offsets of every array in the roster's allocation
     SpeakPlanArgs po = p;
     const uint8_t *o_clear = nullptr, *d_clear = nullptr;
-    const size_t need = layout_speak(0, (size_t)text_bytes, clear_bytes, so, po, &o_clear);
+    ParseArgs q{}, qo{};
+    q.k = qo.k = k;
+    const size_t need = layout_speak(0, (size_t)text_bytes, clear_bytes, so, po, &o_clear, parsed ? &qo : nullptr);
     const size_t table_bytes = (uintptr_t)so.speech_new, speech_end = (uintptr_t)so.text;
     const size_t in_bytes = (uintptr_t)so.violations + sizeof(int);
     const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
@@ -2293,7 +2562,7 @@ int nd_roster_speak(int handle, int k, const uint8_t* text, int64_t text_bytes, 
     const size_t cap_d = r->cap_d;
     if (grow_dev(&r->d, &r->cap_d, need, "roster device allocation")) return -1;
     if (r->cap_d != cap_d) r->resident = false;      // this call's upload refills the table from the mirror
-    layout_speak((uintptr_t)r->d, (size_t)text_bytes, clear_bytes, s, p, &d_clear);
+    layout_speak((uintptr_t)r->d, (size_t)text_bytes, clear_bytes, s, p, &d_clear, parsed ? &q : nullptr);
     if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
 
     uint8_t* h = r->mirror;
@@ -2302,11 +2571,13 @@ int nd_roster_speak(int handle, int k, const uint8_t* text, int64_t text_bytes, 
     };
     if (speech) put(so.speech_new, speech, (size_t)cap * kSpeechRec);
     put(so.text, text, (size_t)text_bytes);
-    put(so.text_off, text_off, (size_t)k * sizeof(int32_t));
-    put(so.text_len, text_len, (size_t)k * sizeof(int32_t));
+    put(parsed ? qo.read_off : so.text_off, text_off, (size_t)k * sizeof(int32_t));
+    put(parsed ? qo.read_len : so.text_len, text_len, (size_t)k * sizeof(int32_t));
     put(so.slot, slots, (size_t)k * sizeof(int32_t));
-    put(so.com, coms, (size_t)k);
-    put(so.words, words, (size_t)k);
+    if (!parsed) {
+        put(so.com, coms, (size_t)k);
+        put(so.words, words, (size_t)k);
+    }
     int32_t* coff = reinterpret_cast<int32_t*>(h + (uintptr_t)so.ctext_off);
     for (int b = 0; b < k; b++) {
         coff[b] = text_off[b] + kSpeakSlack * b;
@@ -2325,6 +2596,11 @@ int nd_roster_speak(int handle, int k, const uint8_t* text, int64_t text_bytes, 
 
     const unsigned copy_blocks = speech ? (unsigned)(((size_t)cap * (kSpeechRec / 4) + kBlock - 1) / kBlock) : 0u;
     ND_CHECK(hipEventRecord(g.ev0, st));
+    if (parsed) {
+        q.speech = s.speech;
+        hipLaunchKernelGGL(nuts_roster_parse, dim3((unsigned)s.blocks), dim3(kBlock), 0, st, q);
+        ND_CHECK(hipGetLastError());
+    }
     hipLaunchKernelGGL(nuts_roster_speak, dim3((unsigned)s.blocks + copy_blocks), dim3(kBlock), 0, st, s);
     ND_CHECK(hipGetLastError());
     hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)(k * p.tiles + k)), dim3(kBlock), 0, st, p);
@@ -2347,6 +2623,15 @@ int nd_roster_speak(int handle, int k, const uint8_t* text, int64_t text_bytes, 
                  "%d writes transduced)", violations, kSpeakSlack, kMaxWrites);
         return -1;
     }
+    if (parsed) {
+        memcpy(parsed->kind, res(qo.kind), (size_t)k);
+        memcpy(parsed->com, res(qo.com), (size_t)k);
+        memcpy(parsed->words, res(qo.words), (size_t)k);
+        memcpy(parsed->line_len, res(qo.line_len), (size_t)k * sizeof(int32_t));
+        memcpy(parsed->inp_len, res(qo.text_len), (size_t)k * sizeof(int32_t));
+        const int32_t* at = reinterpret_cast<const int32_t*>(res(qo.text_off));
+        for (int b = 0; b < k; b++) parsed->inp_off[b] = at[b] - text_off[b];      // relative to the read's own data
+    }
     memcpy(outcome, res(so.outcome), (size_t)k);
     memcpy(clen, res(so.clen), 2 * (size_t)k * sizeof(int32_t));
     memcpy(vn, res(po.vn), 4 * (size_t)k * sizeof(int64_t));
@@ -2365,6 +2650,55 @@ int nd_roster_speak(int handle, int k, const uint8_t* text, int64_t text_bytes, 
         timing->d2h_bytes = (int64_t)res_bytes;
     }
     return 0;
+}
+
+// K speech events of roster `handle`, as say(), shout(), emote() and semote() answer them.  Event b: the speaker's slot
+// slots[b], the command coms[b] (NP_SAY 3, NP_SHOUT 4, NP_EMOTE 6, NP_SEMOTE 7), inpstr text[text_off[b] .. + text_len[b])
+// (packed: text_off[0] = 0, text_off[b + 1] = text_off[b] + text_len[b]; at most 999 bytes each) and word_count words[b].
+// table as nd_roster_plan's.  speech is NULL when no speaker state changed since the last nd_roster_speak of this roster,
+// else all of it: 16 bytes per slot, the name's 12 bytes, its length, a flags byte (vis 1, muzzled 2, command_mode 4),
+// the level and a byte of padding; the first call of a roster must give it.  record: store the spoken says and emotes in their
+// rooms' rings, after clearing those that clear marks (NULL: none), as nd_roster_plan_record does; the caller has checked
+// that their speakers' rooms are ring rooms.
+// Outputs (host, caller-allocated), with W = ceil(capacity / 64) and text t = b for event b's room line, k + b for its
+// reply: outcome[k] (0 spoken, 1 muzzled, 2 nothing to say, 3 swearing); clen[2k] the composed texts' lengths, -1 where
+// there is none; ctext[2 * text_bytes + 72 * k] their bytes, text t at ctext_off(t) = text_off[b] + 36 * b, plus
+// text_bytes + 36 * k for a reply; bits[k * W] the room lines' admit bitmap, as nd_roster_plan's; vn[4k], vw[4k],
+// vwsz[4k * 16] the two variants of text t at 2t and 2t + 1, all zero for a text that is not there; var[12 * ctext bytes +
+// 32 * k] their bytes, text t's at 12 * ctext_off(t) + 16 * t and that plus (6 * clen[t] + 4 rounded up to 4).
+// Per call, whatever k and the capacity: one upload, two kernels (nuts_roster_speak, nuts_roster_speak_plan) and
+// nuts_roster_record as a third when record is set, one download at the bound size, one synchronise.
+// Returns 0, or -1 with nd_last_error() set.
+int nd_roster_speak(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off,
+                    const int32_t* text_len, const int32_t* slots, const uint8_t* coms, const uint8_t* words,
+                    int ban_swearing, int record, const uint8_t* table, const uint8_t* speech, const uint8_t* clear,
+                    int8_t* outcome, int32_t* clen, uint64_t* bits, int64_t* vn, int32_t* vw, int32_t* vwsz,
+                    uint8_t* ctext, uint8_t* var, nd_roster_timing* timing)
+{
+    return speech_call(handle, k, text, text_bytes, text_off, text_len, slots, coms, words, ban_swearing, record, table,
+                       speech, clear, outcome, clen, bits, vn, vw, vwsz, ctext, var, timing, nullptr);
+}
+
+// K reads of clients in line mode, framed and dispatched as user_input() and exec_com() do, and the speech among them
+// answered as nd_roster_speak answers it.  Read b: the speaker's slot slots[b] and the bytes data[read_off[b] .. +
+// read_len[b]) (packed, 1 .. 1000 bytes each, the last one below 32 as a signed char).  table, speech, record and clear
+// as nd_roster_speak's; the speaker's level is byte 14 of its 16 bytes.
+// Outputs of the parse, k entries each: kind (0 IAC, 1 empty, 2 repeat, 3 unknown, 4 speech, 5 command), com (-1: none),
+// words, line_len, and inp_off / inp_len, where inpstr lies in the read's own bytes (inp_len -1: none).  The others as
+// nd_roster_speak's with the reads in the inpstr's place: text t's slot is read_len[b] + 36 bytes wide at read_off[b] +
+// 36 * b.  outcome is -1 for a read that no speech command answers: it has no texts, but for an unknown command's reply.
+// Per call, whatever k and the capacity: one upload, three kernels (nuts_roster_parse, nuts_roster_speak,
+// nuts_roster_speak_plan) and nuts_roster_record as a fourth when record is set, one download at the bound size, one
+// synchronise.  Returns 0, or -1 with nd_last_error() set.
+int nd_roster_input(int handle, int k, const uint8_t* data, int64_t data_bytes, const int32_t* read_off,
+                    const int32_t* read_len, const int32_t* slots, int ban_swearing, int record, const uint8_t* table,
+                    const uint8_t* speech, const uint8_t* clear, int8_t* kind, int8_t* com, uint8_t* words,
+                    int32_t* line_len, int32_t* inp_off, int32_t* inp_len, int8_t* outcome, int32_t* clen, uint64_t* bits,
+                    int64_t* vn, int32_t* vw, int32_t* vwsz, uint8_t* ctext, uint8_t* var, nd_roster_timing* timing)
+{
+    const ParseOut parsed{kind, com, words, line_len, inp_off, inp_len};
+    return speech_call(handle, k, data, data_bytes, read_off, read_len, slots, nullptr, nullptr, ban_swearing, record,
+                       table, speech, clear, outcome, clen, bits, vn, vw, vwsz, ctext, var, timing, &parsed);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 
     python -m nuts333_amd.devpath [--reps R] [--warmup W] [--pathbench-iterations I] [--per-call K[,K...]]
                                   [--roster K[,K...]] [--plan K[,K...]] [--review Q[,Q...]] [--speak K[,K...]]
-                                                                                              -> one JSON line
+                                  [--input K[,K...]]                                          -> one JSON line
 
 For N in {10, 100, 1000} listeners, the two texts oracle/pathbench.c times (``say``; ``shout`` carrying ``~OL``/``~RS``)
 and colour all-off / all-on / half, one ``nuts333_amd.device.broadcast`` per repetition (listener 0 is the sender, the
@@ -48,6 +48,14 @@ is checked against the restatement.  And ``record``: ``plan_many`` of K = 100 to
 copy volume, what composing adds over ``plan_many``, and the CPU composing the same events (``cpu_us``: ``np_say_verb``,
 ``np_contains_swearing`` and the two formats of ``say()``, one ctypes call each; ``cpu_derived_us``: 2 x K x pathbench's
 ``format_line_once_ns``).  The first call of each case is checked against the restatement.
+
+``--input K[,K...]`` adds ``input``: the same rosters and K raw reads per ``Roster.input_many`` call -- the K ``say``
+events as their clients send them, ``inpstr`` and a newline -- timed alternating, in one process, with ``speak_many``
+of the same events parsed beforehand: the three times and the copy volume of both, what parsing adds over
+``speak_many``, and the CPU parsing the same reads with the restatement's functions (``cpu_us``: ``np_terminate`` and
+``np_wordfind``, all that ``user_input()`` runs on a plain line; ``cpu_exec_com_us``: those and ``np_remove_first``,
+``np_command_lookup`` and ``np_command_level``, the most a read can need; one ctypes call each).  The first call of each
+case is checked against ``speak_many`` and the restatement.
 """
 from __future__ import annotations
 
@@ -370,6 +378,98 @@ def speak_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
             "speak": cases}
 
 
+def input_reads(k: int) -> list[tuple]:
+    """The K reads whose parse is ``speak_events(k)``: slot 0's plain lines, each ``inpstr`` and a newline."""
+    return [(slot, inpstr + b"\n") for slot, _, inpstr, _ in speak_events(k)]
+
+
+def input_cpu_us(reads, reps: int, warmup: int, exec_com: bool) -> dict:
+    """The CPU parsing the same K reads, timed here: np_terminate on a copy of the read and np_wordfind, as user_input()
+    does for a plain line; with ``exec_com`` also np_remove_first, np_command_lookup and np_command_level on the first
+    word, as exec_com() would; one ctypes call each."""
+    lib = nuts_path.lib()
+    words = ctypes.create_string_buffer(10 * 41)
+    bufs = [ctypes.create_string_buffer(data, len(data) + 1) for _, data in reads]
+    runs = []
+    for _ in range(warmup + reps):
+        for buf, (_, data) in zip(bufs, reads):                # np_terminate cuts in place: a fresh copy per run
+            ctypes.memmove(buf, data, len(data))
+        t0 = time.perf_counter()
+        for buf in bufs:
+            lib.np_terminate(buf)
+            lib.np_wordfind(buf, words)
+            if exec_com:
+                lib.np_remove_first(buf)
+                lib.np_command_level(lib.np_command_lookup(words))
+        runs.append((time.perf_counter() - t0) * 1e6)
+    return _stats(runs[warmup:])
+
+
+def input_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
+    """The ``input`` section: input_many of K raw reads to a 1000-slot roster, alternating with speak_many of the same
+    events parsed beforehand, for each colour case and each K."""
+    n = 1000
+    cases = []
+    for colour in COLOURS:
+        with device.Roster(n) as roster:
+            roster.update(range(n), room=0, colour=listeners(n, colour)[:, device.LISTENER_FIELDS.index("colour")])
+            roster.update(0, name=b"Uaaa", level=1)
+            for k in ks:
+                reads, events, lines = input_reads(k), speak_events(k), line_texts("say", k)
+                first, spoken = roster.input_many(reads, ban_swearing=True), roster.speak_many(events, ban_swearing=True)
+                for i, t in enumerate(lines):
+                    a, b = first.speech, spoken
+                    ok = (first.kind[i] == device.SPEECH and first.com[i] == device.COM_SAY
+                          and first.inpstr(i) == events[i][2] and first.word_count[i] == events[i][3]
+                          and a.outcome[i] == b.outcome[i] == device.SPOKEN and a.line(i) == b.line(i) == t
+                          and a.reply_text(i) == b.reply_text(i)
+                          and np.array_equal(a.room.admitted_bits[i], b.room.admitted_bits[i])
+                          and all(a.room.variant(i, c) == nuts_path.transduce(t, c) == b.room.variant(i, c)
+                                  and a.reply.variant(i, c) == b.reply.variant(i, c) for c in (0, 1)))
+                    if not ok:
+                        raise SystemExit(f"devpath: input {k}, {colour}: read {i} differs from speak_many of its event")
+                timed = {name: {"kernels_us": [], "end_to_end_us": [], "python_us": [], "copies": set()}
+                         for name in ("input", "speak")}
+                for i in range(2 * (warmup + reps)):
+                    name = ("input", "speak")[i % 2]
+                    t0 = time.perf_counter()
+                    r = (roster.input_many(reads, ban_swearing=True) if name == "input"
+                         else roster.speak_many(events, ban_swearing=True))
+                    if i >= 2 * warmup:
+                        timed[name]["python_us"].append((time.perf_counter() - t0) * 1e6)
+                        timed[name]["kernels_us"].append(r.timing["kernels_us"])
+                        timed[name]["end_to_end_us"].append(r.timing["end_to_end_us"])
+                        timed[name]["copies"].add((r.timing["h2d_bytes"], r.timing["d2h_bytes"]))
+                for name, t in timed.items():
+                    if len(t["copies"]) != 1:
+                        raise SystemExit(f"devpath: input {k}, {colour}: timed {name} calls copied {sorted(t['copies'])} bytes")
+                fields = ("kernels_us", "end_to_end_us", "python_us")
+                ip = {f: _stats(timed["input"][f]) for f in fields}
+                sp = {f: _stats(timed["speak"][f]) for f in fields}
+                h2d, d2h = timed["input"]["copies"].pop()
+                sh2d, sd2h = timed["speak"]["copies"].pop()
+                cpu = input_cpu_us(reads, reps, warmup, False)
+                cases.append({"n": n, "k": k, "text": "say", "colour": colour, "ban_swearing": True,
+                              "recipients": k * (n - 1), **ip, "h2d_bytes": h2d, "d2h_bytes": d2h,
+                              "speak_many_of_the_parsed_events": {**sp, "h2d_bytes": sh2d, "d2h_bytes": sd2h},
+                              "parsing_adds_us": {f: round(ip[f]["median"] - sp[f]["median"], 2) for f in fields},
+                              "parsing_adds_us_per_read": {f: round((ip[f]["median"] - sp[f]["median"]) / k, 3)
+                                                           for f in fields},
+                              "cpu_us": cpu, "cpu_exec_com_us": input_cpu_us(reads, reps, warmup, True),
+                              "parsing_adds_end_to_end_over_cpu":
+                                  round((ip["end_to_end_us"]["median"] - sp["end_to_end_us"]["median"]) / cpu["median"], 2)})
+    return {"input_kernels": ["nuts_roster_parse", "nuts_roster_speak", "nuts_roster_speak_plan"],
+            "input_end_to_end_covers": "packing the K reads into pinned memory, one H2D (the table and the speaker state "
+                                       "only in a call after an update of theirs), three kernels, one D2H of what the "
+                                       "parse found and of all that speak_many downloads, at the bound size, one "
+                                       "synchronise (python_us adds checking the K reads and their speakers, the copies "
+                                       "out of pinned memory and building the Input)",
+            "input_cpu_us_covers": "np_terminate + np_wordfind per read, one ctypes call each: what user_input() runs "
+                                   "on a plain line; cpu_exec_com_us adds np_remove_first, np_command_lookup and "
+                                   "np_command_level, the most a read can need",
+            "input": cases}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=2000, help="timed broadcasts per case (default 2000)")
@@ -387,6 +487,9 @@ def main(argv=None) -> int:
     ap.add_argument("--speak", type=per_call_counts, default=None, metavar="K[,K...]",
                     help="also time K say events per Roster.speak_many call, for each K, beside plan_many of the "
                          "same lines composed beforehand (the speak section)")
+    ap.add_argument("--input", type=per_call_counts, default=None, metavar="K[,K...]",
+                    help="also time K raw reads per Roster.input_many call, for each K, beside speak_many of the same "
+                         "events parsed beforehand (the input section)")
     a = ap.parse_args(argv)
     if a.reps < 1 or a.warmup < 0:
         ap.error("--reps must be >= 1 and --warmup >= 0")
@@ -467,6 +570,7 @@ def main(argv=None) -> int:
         }
     review = review_cases(a.review, a.reps, a.warmup, pb) if a.review else {}
     speak = speak_cases(a.speak, a.reps, a.warmup, pb) if a.speak else {}
+    inputs = input_cases(a.input, a.reps, a.warmup, pb) if a.input else {}
     out = {
         "what": "user-space stage of one broadcast (admit predicate + transducer), device vs CPU",
         "device": "gfx950",
@@ -481,6 +585,7 @@ def main(argv=None) -> int:
         **plan,
         **review,
         **speak,
+        **inputs,
         "wall_s": round(time.perf_counter() - t_start, 1),
     }
     print(json.dumps(out))
