@@ -151,17 +151,29 @@ class Fanout:
         return int(bo[k] + j)
 
 
-def chunks(result: Fanout, i: int) -> list[bytes]:
-    """Item ``i`` as the list of ``write(2)`` chunks the reference would issue."""
-    data = result.output(i)
-    sizes = result.write_sizes[result.write_offsets[i]:result.write_offsets[i + 1]]
+def _split(data: bytes, sizes: np.ndarray, what: str, holder: str) -> list[bytes]:
+    """``data`` cut into consecutive chunks of ``sizes`` bytes, which must use it up."""
     out, at = [], 0
     for s in sizes.tolist():
         out.append(data[at:at + s])
         at += s
     if at != len(data):
-        raise AssertionError(f"item {i}: chunk sizes sum to {at}, arena slot holds {len(data)} bytes")
+        raise AssertionError(f"{what}: chunk sizes sum to {at}, {holder} holds {len(data)} bytes")
     return out
+
+
+def chunks(result: Fanout, i: int) -> list[bytes]:
+    """Item ``i`` as the list of ``write(2)`` chunks the reference would issue."""
+    sizes = result.write_sizes[result.write_offsets[i]:result.write_offsets[i + 1]]
+    return _split(result.output(i), sizes, f"item {i}", "arena slot")
+
+
+def _offsets(counts, dtype, total: bool = False) -> np.ndarray:
+    """Where each piece starts when pieces of ``counts`` elements lie one after another; with ``total`` one entry more,
+    where they end."""
+    off = np.zeros(len(counts) + 1, dtype=dtype)
+    np.cumsum(counts, out=off[1:])
+    return off if total else off[:-1]
 
 
 def _gather(src: np.ndarray, starts: np.ndarray, counts: np.ndarray, step: int = 1 << 24) -> np.ndarray:
@@ -180,6 +192,30 @@ def _gather(src: np.ndarray, starts: np.ndarray, counts: np.ndarray, step: int =
     return out
 
 
+def _variant_at(text_off, t):
+    """Where text ``t``, whose bytes start at ``text_off`` among the call's texts, has its two variants in the variant
+    buffer (var_at of fanout.hip); ``_variant_at(text bytes, texts)`` is the buffer's size."""
+    return 12 * text_off + 16 * t
+
+
+def _variant_starts(text_starts: np.ndarray, sizes: np.ndarray) -> np.ndarray:
+    """int64 [..., 2]: the two variant slots of every text, the texts numbered in the arrays' own order; the second slot
+    follows the first's hard bound, max_bytes(size) rounded up to 4 (var_stride of fanout.hip; a text that is not
+    there, size -1, counts as empty)."""
+    starts = np.empty(text_starts.shape + (2,), dtype=np.int64)
+    t = np.arange(text_starts.size, dtype=np.int64).reshape(text_starts.shape)
+    starts[..., 0] = _variant_at(text_starts.astype(np.int64), t)
+    starts[..., 1] = starts[..., 0] + ((max_bytes(np.maximum(sizes, 0).astype(np.int64)) + 3) & ~3)
+    return starts
+
+
+def _composed_at(text_off, t):
+    """Where composed text ``t``, whose inpstr starts at ``text_off`` among the call's, has its slot in a speech call's
+    text buffer (ctext_at of fanout.hip): room line k is text k, its reply text K + k over the same inpstr once more.
+    ``_composed_at(2 * text bytes, 2 * K)`` is the buffer's size."""
+    return text_off + _SPEAK_SLACK * t
+
+
 def _unpack(words: np.ndarray, capacity: int) -> np.ndarray:
     """uint64 [..., W] bitmap words -> bool [..., capacity]: bit j % 64 of word j // 64 is slot j."""
     b = np.ascontiguousarray(words, dtype="<u8").view(np.uint8)
@@ -193,8 +229,25 @@ def _pack(flags: np.ndarray) -> np.ndarray:
     return np.packbits(padded, bitorder="little").view("<u8").astype(np.uint64)
 
 
+class _Variants:
+    """Two variants (colour off, colour on) per entry in one flat buffer, with their ``write(2)`` chunk sizes: the
+    fields ``variants``, ``variant_starts``, ``variant_sizes``, ``write_counts`` and ``write_sizes`` that a
+    :class:`Plan` and a :class:`Review` share.  ``_what`` names an entry in their messages."""
+
+    def variant(self, k: int, c: int) -> bytes:
+        """The bytes entry ``k`` sends to a listener with colour bit ``c``."""
+        self._check(k, c)
+        at = int(self.variant_starts[k, c])
+        return self.variants[at:at + int(self.variant_sizes[k, c])].tobytes()
+
+    def chunks(self, k: int, c: int) -> list[bytes]:
+        """``variant(k, c)`` as the list of ``write(2)`` chunks the reference would issue."""
+        return _split(self.variant(k, c), self.write_sizes[k, c, :int(self.write_counts[k, c])],
+                      f"{self._what} ({k}, {c})", "the variant")
+
+
 @dataclass
-class Plan:
+class Plan(_Variants):
     """What a talker needs to deliver K broadcasts to a roster: slot ``j`` gets ``variant(k, colour of j)``, in the
     chunks ``chunks(k, colour of j)``, if it is admitted.  :meth:`expand` replicates that into a :class:`Fanout`."""
     capacity: int
@@ -206,6 +259,7 @@ class Plan:
     write_counts: np.ndarray      # int32 [K, 2]
     write_sizes: np.ndarray       # int32 [K, 2, MAX_WRITES]; entries at or past write_counts are unspecified
     timing: dict = field(default_factory=dict)   # as Roster.broadcast_many's: kernels_us, end_to_end_us, h2d/d2h_bytes
+    _what = "variant"
 
     def _check(self, k: int, c=0) -> None:
         if not 0 <= k < len(self.admitted_bits) or c not in (0, 1):
@@ -221,23 +275,6 @@ class Plan:
         self._check(k, c)
         return np.flatnonzero(self.admitted(k) & (_unpack(self.colour_bits, self.capacity) == bool(c)))
 
-    def variant(self, k: int, c: int) -> bytes:
-        """The bytes broadcast ``k`` sends to a listener with colour bit ``c``."""
-        self._check(k, c)
-        at = int(self.variant_starts[k, c])
-        return self.variants[at:at + int(self.variant_sizes[k, c])].tobytes()
-
-    def chunks(self, k: int, c: int) -> list[bytes]:
-        """``variant(k, c)`` as the list of ``write(2)`` chunks the reference would issue."""
-        data = self.variant(k, c)
-        out, at = [], 0
-        for s in self.write_sizes[k, c, :int(self.write_counts[k, c])].tolist():
-            out.append(data[at:at + s])
-            at += s
-        if at != len(data):
-            raise AssertionError(f"variant ({k}, {c}): chunk sizes sum to {at}, the variant holds {len(data)} bytes")
-        return out
-
     def expand(self) -> Fanout:
         """The :class:`Fanout` that ``Roster.broadcast_many`` returns for the same call (``timing`` aside), from this
         plan's own arrays alone: item ``(k, j)`` is ``variant(k, colour of j)`` if slot ``j`` is admitted."""
@@ -246,10 +283,8 @@ class Plan:
         colour = _unpack(self.colour_bits, cap).astype(np.intp)
         sizes = np.asarray(self.variant_sizes, dtype=np.int64)[:, colour].reshape(k * cap)
         writes = np.asarray(self.write_counts, dtype=np.int64)[:, colour].reshape(k * cap)
-        out_off = np.zeros(k * cap + 1, dtype=np.int64)
-        np.cumsum(np.where(admitted, sizes, 0), out=out_off[1:])
-        w_off = np.zeros(k * cap + 1, dtype=np.int64)
-        np.cumsum(np.where(admitted, writes, 0), out=w_off[1:])
+        out_off = _offsets(np.where(admitted, sizes, 0), np.int64, total=True)
+        w_off = _offsets(np.where(admitted, writes, 0), np.int64, total=True)
         items = np.flatnonzero(admitted)
         var = 2 * (items // cap) + colour[items % cap]                    # each admitted item's variant, as 2k + c
         arena = _gather(np.asarray(self.variants, dtype=np.uint8),
@@ -261,7 +296,7 @@ class Plan:
 
 
 @dataclass
-class Review:
+class Review(_Variants):
     """What ``.review`` sends for each of Q rooms, between its header and its footer: with ``line_0 ..`` the non-empty
     lines of the room's ring from the cursor onwards, ``chunks(q, c) == chunks(line_0, c) + chunks(line_1, c) + ...``
     (one ``write_user`` per line, so with colour on every line ends in a 4-byte reset write of its own) and
@@ -276,6 +311,7 @@ class Review:
     write_sizes: np.ndarray       # int32 [Q, 2, MAX_REVIEW_WRITES]; entries at or past write_counts are unspecified
     sequential: np.ndarray | None = None         # int32 [Q] (line, variant) pairs the device transduced sequentially
     timing: dict = field(default_factory=dict)   # kernels_us, end_to_end_us, h2d_bytes, d2h_bytes
+    _what = "review"
 
     def _check(self, q: int, c=0) -> None:
         if not 0 <= q < len(self.rooms) or c not in (0, 1):
@@ -286,23 +322,6 @@ class Review:
         self._check(q)
         out = [bytes(row).split(b"\0", 1)[0] for row in np.asarray(self.stored[q], dtype=np.uint8)]
         return [line for line in out if line]
-
-    def variant(self, q: int, c: int) -> bytes:
-        """The bytes a listener with colour bit ``c`` gets for room ``q``'s lines."""
-        self._check(q, c)
-        at = int(self.variant_starts[q, c])
-        return self.variants[at:at + int(self.variant_sizes[q, c])].tobytes()
-
-    def chunks(self, q: int, c: int) -> list[bytes]:
-        """``variant(q, c)`` as the list of ``write(2)`` chunks the reference would issue."""
-        data = self.variant(q, c)
-        out, at = [], 0
-        for s in self.write_sizes[q, c, :int(self.write_counts[q, c])].tolist():
-            out.append(data[at:at + s])
-            at += s
-        if at != len(data):
-            raise AssertionError(f"review ({q}, {c}): chunk sizes sum to {at}, the variant holds {len(data)} bytes")
-        return out
 
 
 @dataclass
@@ -375,16 +394,27 @@ class Input:
 
 
 # ------------------------------------------------------------------ validation (never touches the device)
-def _as_text(t) -> bytes:
-    if isinstance(t, str):
+def _as_bytes(what: str, v) -> bytes:
+    """bytes as they are, a str as latin-1, a bytearray or memoryview as a copy; ``what`` names the value."""
+    if isinstance(v, str):
         try:
-            t = t.encode("latin-1")
+            v = v.encode("latin-1")
         except UnicodeEncodeError as e:
-            raise ValueError(f"text has a character outside one byte: {e}") from None
-    elif isinstance(t, (bytearray, memoryview)):
-        t = bytes(t)
-    if not isinstance(t, bytes):
-        raise ValueError(f"text must be bytes or str, not {type(t).__name__}")
+            raise ValueError(f"{what} has a character outside one byte: {e}") from None
+    elif isinstance(v, (bytearray, memoryview)):
+        v = bytes(v)
+    if not isinstance(v, bytes):
+        raise ValueError(f"{what} must be bytes or str, not {type(v).__name__}")
+    return v
+
+
+def _is_int(v, lo: int, hi: int) -> bool:
+    """An int, numpy's included, that is not a bool and lies in [lo, hi]."""
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and lo <= int(v) <= hi
+
+
+def _as_text(t) -> bytes:
+    t = _as_bytes("text", t)
     if b"\0" in t:
         raise ValueError("text contains a NUL byte (the talker's strings end there)")
     if len(t) >= TEXT_SIZE:
@@ -428,9 +458,7 @@ def _prepare_batch(texts, colours):
     lens = np.fromiter((len(t) for t in texts), dtype=np.int32, count=len(texts))
     if int(lens.sum(dtype=np.int64)) >= 2**31:
         raise ValueError("batch text larger than 2 GiB: split it")
-    offs = np.zeros(len(texts), dtype=np.int32)
-    np.cumsum(lens[:-1], out=offs[1:])
-    return b"".join(texts), offs, lens, rec
+    return b"".join(texts), _offsets(lens, np.int32), lens, rec
 
 
 def _prepare_broadcast(text, listeners, rm_is_null, force_listen, com_num):
@@ -441,7 +469,7 @@ def _prepare_broadcast(text, listeners, rm_is_null, force_listen, com_num):
 
 
 def _com_num(v) -> int:
-    if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) < NUM_COMMANDS:
+    if not _is_int(v, 0, NUM_COMMANDS - 1):
         raise ValueError(f"com_num must be a command number in [0, {NUM_COMMANDS}), not {v!r}")
     return int(v)
 
@@ -473,12 +501,8 @@ def _prepare_many(broadcasts):
     if bound > MANY_ARENA_CAP:
         raise ValueError(f"call too large: its arena bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
                          f"(MANY_ARENA_CAP): split it")
-    item_off = np.zeros(len(texts) + 1, dtype=np.int32)
-    np.cumsum(ns, out=item_off[1:])
-    text_off = np.zeros(len(texts), dtype=np.int32)
-    np.cumsum(lens[:-1], out=text_off[1:])
-    return (b"".join(texts), text_off, lens.astype(np.int32), np.array(flags, dtype=np.uint8),
-            np.array(coms, dtype=np.int32), item_off, np.concatenate(recs))
+    return (b"".join(texts), _offsets(lens, np.int32), lens.astype(np.int32), np.array(flags, dtype=np.uint8),
+            np.array(coms, dtype=np.int32), _offsets(ns, np.int32, total=True), np.concatenate(recs))
 
 
 # ------------------------------------------------------------------ the library
@@ -556,6 +580,19 @@ def _load():
     return _LIB
 
 
+def _check(rc: int, what: str) -> int:
+    """What a call of the library returned, or ``RuntimeError("what: the library's message")`` when it is negative."""
+    if rc < 0:
+        raise RuntimeError(f"{what}: {_LIB.nd_last_error().decode(errors='replace')}")
+    return rc
+
+
+def _timing_of(t) -> dict:
+    """A call's timing struct as the dict its result carries: kernels_us and end_to_end_us, and a roster call's
+    h2d_bytes and d2h_bytes."""
+    return {name: getattr(t, name) for name, _ in t._fields_}
+
+
 def device_count() -> int:
     """Visible GPUs (loads, and if needed builds, the library; does not allocate on the device)."""
     n = _load().nd_device_count()
@@ -579,19 +616,18 @@ def _run(broadcast: bool, text: bytes, offs, lens, rec, rm_is_null=0, force_list
     rc = lib.nd_fanout(int(broadcast), _ptr(tbuf), len(text), _ptr(offs) if offs is not None else None, _ptr(lens),
                        _ptr(rec), n, rm_is_null, force_listen, com_num, _ptr(admitted), _ptr(out_off), _ptr(w_off),
                        ctypes.byref(t))
-    if rc != 0:
-        raise RuntimeError(f"device fan-out failed: {lib.nd_last_error().decode(errors='replace')}")
+    _check(rc, "device fan-out failed")
     return _result(lib, admitted, out_off, w_off, t)
 
 
-def _result(lib, admitted, out_off, w_off, t: _Timing) -> Fanout:
+def _result(lib, admitted, out_off, w_off, t) -> Fanout:
     """The Fanout of the last call: the arena and the chunk sizes copied out of the library's pinned buffers."""
     nbytes, nwrites = int(out_off[-1]), int(w_off[-1])
     arena = np.ctypeslib.as_array(ctypes.cast(lib.nd_arena(), ctypes.POINTER(ctypes.c_uint8)), (max(nbytes, 1),))
     wsz = np.ctypeslib.as_array(ctypes.cast(lib.nd_write_sizes(), ctypes.POINTER(ctypes.c_int32)), (max(nwrites, 1),))
     return Fanout(admitted=admitted.astype(bool), out_offsets=out_off, arena=arena[:nbytes].copy(),
                   write_offsets=w_off.astype(np.int64), write_sizes=wsz[:nwrites].copy(),
-                  timing={"kernels_us": t.kernels_us, "end_to_end_us": t.end_to_end_us})
+                  timing=_timing_of(t))
 
 
 def transduce_batch(texts, colours) -> Fanout:
@@ -622,8 +658,7 @@ def broadcast_many(broadcasts) -> Fanout:
     t = _Timing()
     rc = lib.nd_fanout_many(len(lens), _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(flags), _ptr(coms),
                             _ptr(item_off), _ptr(rec), _ptr(admitted), _ptr(out_off), _ptr(w_off), ctypes.byref(t))
-    if rc != 0:
-        raise RuntimeError(f"device fan-out failed: {lib.nd_last_error().decode(errors='replace')}")
+    _check(rc, "device fan-out failed")
     r = _result(lib, admitted, out_off, w_off, t)
     r.broadcast_offsets = item_off.astype(np.int64)
     return r
@@ -639,44 +674,28 @@ def _room(v) -> int:
     """A room id: None (no room) is -1, else an int in [0, ROOM_LIMIT)."""
     if v is None:
         return -1
-    if not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_)) or not 0 <= int(v) < ROOM_LIMIT:
+    if not _is_int(v, 0, ROOM_LIMIT - 1):
         raise ValueError(f"room must be None or an int in [0, {ROOM_LIMIT}), not {v!r}")
     return int(v)
 
 
 def _speaker_name(v) -> bytes:
     """``user->name``: bytes or str of 1 .. USER_NAME_LEN bytes, no NUL."""
-    if isinstance(v, str):
-        try:
-            v = v.encode("latin-1")
-        except UnicodeEncodeError as e:
-            raise ValueError(f"name has a character outside one byte: {e}") from None
-    elif isinstance(v, (bytearray, memoryview)):
-        v = bytes(v)
-    if not isinstance(v, bytes):
-        raise ValueError(f"name must be bytes or str, not {type(v).__name__}")
+    v = _as_bytes("name", v)
     if not 1 <= len(v) <= USER_NAME_LEN or b"\0" in v:
         raise ValueError(f"name must be 1 .. {USER_NAME_LEN} bytes without a NUL, not {v!r}")
     return v
 
 
 def _level(v) -> int:
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= MAX_LEVEL:
+    if not _is_int(v, 0, MAX_LEVEL):
         raise ValueError(f"level must be an int in [0, {MAX_LEVEL}] (enum np_level), not {v!r}")
     return int(v)
 
 
 def _read_data(v) -> bytes:
     """One read(2) of a client in line mode: 1 .. READ_SIZE bytes of any value, the last one ending the line."""
-    if isinstance(v, str):
-        try:
-            v = v.encode("latin-1")
-        except UnicodeEncodeError as e:
-            raise ValueError(f"data has a character outside one byte: {e}") from None
-    elif isinstance(v, (bytearray, memoryview)):
-        v = bytes(v)
-    if not isinstance(v, bytes):
-        raise ValueError(f"data must be bytes or str, not {type(v).__name__}")
+    v = _as_bytes("data", v)
     if not 1 <= len(v) <= READ_SIZE:
         raise ValueError(f"data of {len(v)} bytes: a read holds 1 .. {READ_SIZE}")
     if 32 <= v[-1] < 128:
@@ -708,11 +727,9 @@ class Roster:
     """
 
     def __init__(self, capacity: int, review_rooms: int = 0):
-        if (not isinstance(capacity, (int, np.integer)) or isinstance(capacity, (bool, np.bool_))
-                or not 1 <= int(capacity) <= MAX_CAPACITY):
+        if not _is_int(capacity, 1, MAX_CAPACITY):
             raise ValueError(f"roster capacity must be an int in [1, {MAX_CAPACITY}], not {capacity!r}")
-        if (not isinstance(review_rooms, (int, np.integer)) or isinstance(review_rooms, (bool, np.bool_))
-                or not 0 <= int(review_rooms) <= MAX_REVIEW_ROOMS):
+        if not _is_int(review_rooms, 0, MAX_REVIEW_ROOMS):
             raise ValueError(f"review_rooms must be an int in [0, {MAX_REVIEW_ROOMS}], not {review_rooms!r}")
         self.capacity = int(capacity)
         self.review_rooms = int(review_rooms)
@@ -734,12 +751,29 @@ class Roster:
         self._handle = None
         self._closed = False
 
+    def _ring_rooms_are(self) -> str:
+        return (f"the ring rooms are 0 .. {self.review_rooms - 1}" if self.review_rooms else
+                "the roster has none (review_rooms is 0)")
+
+    def _check_speaker(self, slot: int, recorded: str | None) -> None:
+        """What a speech event or a read needs of its speaker: a room, no ``login`` flag, a name, and a ring room when
+        ``recorded`` says why ("it is to be recorded", "it may be recorded"; None: it is not)."""
+        if self._room[slot] < 0:
+            raise ValueError(f"the speaker, slot {slot}, has no room (the talker relays such a user over its netlink)")
+        if self._flags[slot] & ROSTER_FLAGS["login"]:
+            raise ValueError(f"the speaker, slot {slot}, is still logging in")
+        if self._speech[slot, USER_NAME_LEN] == 0:
+            raise ValueError(f"the speaker, slot {slot}, has no name")
+        if recorded and not 0 <= self._room[slot] < self.review_rooms:
+            raise ValueError(f"{recorded}, but room {int(self._room[slot])} has no review ring: "
+                             f"{self._ring_rooms_are()}")
+
     def _check_open(self) -> None:
         if self._closed:
             raise ValueError("the roster is closed")
 
     def _slot(self, v) -> int:
-        if not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_)) or not 0 <= int(v) < self.capacity:
+        if not _is_int(v, 0, self.capacity - 1):
             raise ValueError(f"slot must be an int in [0, {self.capacity}), not {v!r}")
         return int(v)
 
@@ -864,9 +898,7 @@ class Roster:
     def _packed(texts, lens, rms, senders, flags, coms):
         """What _checked returns, packed for nd_roster_fanout / nd_roster_plan: texts, text offsets and lengths, rooms,
         senders, flags and commands."""
-        text_off = np.zeros(len(texts), dtype=np.int32)
-        np.cumsum(lens[:-1], out=text_off[1:])
-        return (b"".join(texts), text_off, lens.astype(np.int32), np.array(rms, dtype=np.int32),
+        return (b"".join(texts), _offsets(lens, np.int32), lens.astype(np.int32), np.array(rms, dtype=np.int32),
                 np.array(senders, dtype=np.int32), np.array(flags, dtype=np.uint8), np.array(coms, dtype=np.int32))
 
     def _prepare(self, broadcasts):
@@ -886,7 +918,7 @@ class Roster:
         bool, or K of them) sets bit 2 of the flags of the broadcasts to record, each of which needs a ring room."""
         checked = self._checked(broadcasts, (self.capacity + 63) // 64, "K x ceil(capacity / 64)")
         lens = checked[1]
-        bound = 12 * int(lens.sum()) + 16 * len(lens)
+        bound = _variant_at(int(lens.sum()), len(lens))
         if bound > MANY_ARENA_CAP:
             raise ValueError(f"call too large: its variant bound (12 x text bytes + 16 x K) is {bound} bytes, the cap "
                              f"is {MANY_ARENA_CAP} (MANY_ARENA_CAP): split it")
@@ -934,19 +966,15 @@ class Roster:
         rc = lib.nd_roster_fanout(handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(rm),
                                   _ptr(sender), _ptr(flags), _ptr(coms), _ptr(self._table) if self._dirty else None,
                                   _ptr(admitted), _ptr(out_off), _ptr(w_off), ctypes.byref(t))
-        if rc != 0:
-            raise RuntimeError(f"device fan-out failed: {lib.nd_last_error().decode(errors='replace')}")
+        _check(rc, "device fan-out failed")
         self._dirty = False
         r = _result(lib, admitted, out_off, w_off, t)
-        r.timing.update(h2d_bytes=t.h2d_bytes, d2h_bytes=t.d2h_bytes)
         r.broadcast_offsets = np.arange(k + 1, dtype=np.int64) * self.capacity
         return r
 
     def _device_handle(self, lib) -> int:
         if self._handle is None:
-            h = lib.nd_roster_create(self.capacity)
-            if h < 0:
-                raise RuntimeError(f"cannot create a device roster: {lib.nd_last_error().decode(errors='replace')}")
+            h = _check(lib.nd_roster_create(self.capacity), "cannot create a device roster")
             if self.review_rooms and lib.nd_roster_review_rooms(h, self.review_rooms) != 0:
                 lib.nd_roster_destroy(h)
                 raise RuntimeError(f"cannot create a device roster: {lib.nd_last_error().decode(errors='replace')}")
@@ -985,7 +1013,7 @@ class Roster:
         vn = np.empty((k, 2), dtype=np.int64)
         vw = np.empty((k, 2), dtype=np.int32)
         vwsz = np.empty((k, 2, MAX_WRITES), dtype=np.int32)
-        var = np.empty(12 * len(text) + 16 * k, dtype=np.uint8)
+        var = np.empty(_variant_at(len(text), k), dtype=np.uint8)
         tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
         t = _RosterTiming()
         args = (handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(rm), _ptr(sender), _ptr(flags),
@@ -996,20 +1024,14 @@ class Roster:
             rc = lib.nd_roster_plan_record(*args, _ptr(clear) if clear is not None else None)
         else:
             rc = lib.nd_roster_plan(*args)
-        if rc != 0:
-            raise RuntimeError(f"device plan failed: {lib.nd_last_error().decode(errors='replace')}")
+        _check(rc, "device plan failed")
         self._dirty = False
         if recording:
             self._clear_sent()
-        # the variant buffer's layout (var_at / var_stride of fanout.hip): two 4-byte aligned slots per broadcast
-        starts = np.empty((k, 2), dtype=np.int64)
-        starts[:, 0] = 12 * text_off.astype(np.int64) + 16 * np.arange(k, dtype=np.int64)
-        starts[:, 1] = starts[:, 0] + ((6 * lens.astype(np.int64) + 4 + 3) & ~3)
         return Plan(capacity=self.capacity, admitted_bits=bits,
                     colour_bits=_pack((self._flags & ROSTER_FLAGS["colour"]) != 0), variants=var,
-                    variant_starts=starts, variant_sizes=vn, write_counts=vw, write_sizes=vwsz,
-                    timing={"kernels_us": t.kernels_us, "end_to_end_us": t.end_to_end_us, "h2d_bytes": t.h2d_bytes,
-                            "d2h_bytes": t.d2h_bytes})
+                    variant_starts=_variant_starts(text_off, lens), variant_sizes=vn, write_counts=vw,
+                    write_sizes=vwsz, timing=_timing_of(t))
 
     def _prepare_speech(self, events, ban_swearing, record):
         """Each (slot, com, inpstr, word_count) and its speaker's state checked, packed for nd_roster_speak: the inpstr,
@@ -1030,28 +1052,17 @@ class Roster:
             slot, com, inpstr, wc = ev
             try:
                 slot = self._slot(slot)
-                if isinstance(com, (bool, np.bool_)) or not isinstance(com, (int, np.integer)) or int(com) not in _SPEECH_COMS:
+                if not _is_int(com, 0, NUM_COMMANDS - 1) or int(com) not in _SPEECH_COMS:
                     raise ValueError(f"com must be COM_SAY, COM_SHOUT, COM_EMOTE or COM_SEMOTE "
                                      f"({', '.join(map(str, _SPEECH_COMS))}), not {com!r}")
                 text = _as_text(inpstr)
                 if len(text) >= ARR_SIZE:
                     raise ValueError(f"inpstr of {len(text)} bytes: the talker's input line holds at most {ARR_SIZE - 1}")
-                if (isinstance(wc, (bool, np.bool_)) or not isinstance(wc, (int, np.integer))
-                        or not 0 <= int(wc) <= MAX_WORDS):
+                if not _is_int(wc, 0, MAX_WORDS):
                     raise ValueError(f"word_count must be an int in [0, {MAX_WORDS}], not {wc!r}")
-                if self._room[slot] < 0:
-                    raise ValueError(f"the speaker, slot {slot}, has no room (the talker relays such a user over its "
-                                     f"netlink)")
-                if self._flags[slot] & ROSTER_FLAGS["login"]:
-                    raise ValueError(f"the speaker, slot {slot}, is still logging in")
-                if self._speech[slot, USER_NAME_LEN] == 0:
-                    raise ValueError(f"the speaker, slot {slot}, has no name")
-                if record and _SPEECH_COMS[int(com)]:
-                    if not 0 <= self._room[slot] < self.review_rooms:
-                        raise ValueError(f"it is to be recorded, but room {int(self._room[slot])} has no review ring: " +
-                                         (f"the ring rooms are 0 .. {self.review_rooms - 1}" if self.review_rooms else
-                                          "the roster has none (review_rooms is 0)"))
-                    recording = True
+                to_record = bool(record and _SPEECH_COMS[int(com)])
+                self._check_speaker(slot, "it is to be recorded" if to_record else None)
+                recording |= to_record
             except ValueError as e:
                 raise ValueError(f"event {k}: {e}") from None
             texts.append(text)
@@ -1059,13 +1070,11 @@ class Roster:
             coms.append(int(com))
             wcs.append(int(wc))
         lens = np.fromiter((len(t) for t in texts), dtype=np.int64, count=len(texts))
-        bound = 12 * (2 * int(lens.sum()) + 2 * _SPEAK_SLACK * len(lens)) + 32 * len(lens)
+        bound = _variant_at(_composed_at(2 * int(lens.sum()), 2 * len(lens)), 2 * len(lens))
         if bound > MANY_ARENA_CAP:
             raise ValueError(f"call too large: its variant bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
                              f"(MANY_ARENA_CAP): split it")
-        text_off = np.zeros(len(texts), dtype=np.int32)
-        np.cumsum(lens[:-1], out=text_off[1:])
-        return (b"".join(texts), text_off, lens.astype(np.int32), np.array(slots, dtype=np.int32),
+        return (b"".join(texts), _offsets(lens, np.int32), lens.astype(np.int32), np.array(slots, dtype=np.int32),
                 np.array(coms, dtype=np.uint8), np.array(wcs, dtype=np.uint8), ban_swearing, recording)
 
     def speak_many(self, events, ban_swearing=False, record=False) -> Speech:
@@ -1096,46 +1105,41 @@ class Roster:
         text, text_off, lens, slots, coms, wcs, ban, recording = self._prepare_speech(events, ban_swearing, record)
         lib = _load()
         handle = self._device_handle(lib)
-        k, words = len(lens), (self.capacity + 63) // 64
-        ctext_bytes = 2 * len(text) + 2 * _SPEAK_SLACK * k
-        outcome = np.empty(k, dtype=np.int8)
-        clen = np.empty((2, k), dtype=np.int32)
-        bits = np.empty((k, words), dtype=np.uint64)
-        vn = np.empty((2, k, 2), dtype=np.int64)
-        vw = np.empty((2, k, 2), dtype=np.int32)
-        vwsz = np.empty((2, k, 2, MAX_WRITES), dtype=np.int32)
-        ctext = np.empty(ctext_bytes, dtype=np.uint8)
-        var = np.empty(12 * ctext_bytes + 32 * k, dtype=np.uint8)
+        k = len(lens)
+        out = self._speech_arrays(k, len(text))
         tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
         clear = self._pending_clear() if recording else None
         t = _RosterTiming()
         rc = lib.nd_roster_speak(handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(slots), _ptr(coms),
                                  _ptr(wcs), ban, int(recording), _ptr(self._table) if self._dirty else None,
                                  _ptr(self._speech) if self._speech_dirty else None,
-                                 _ptr(clear) if clear is not None else None, _ptr(outcome), _ptr(clen), _ptr(bits),
-                                 _ptr(vn), _ptr(vw), _ptr(vwsz), _ptr(ctext), _ptr(var), ctypes.byref(t))
-        if rc != 0:
-            raise RuntimeError(f"device speech failed: {lib.nd_last_error().decode(errors='replace')}")
+                                 _ptr(clear) if clear is not None else None, *map(_ptr, out), ctypes.byref(t))
+        _check(rc, "device speech failed")
         self._dirty = self._speech_dirty = False
         if recording:
             self._clear_sent()
-        return self._speech_of(len(text), text_off, slots, outcome, clen, bits, vn, vw, vwsz, ctext, var, t)
+        return self._speech_of(len(text), text_off, slots, *out, t)
+
+    def _speech_arrays(self, k: int, text_bytes: int):
+        """The arrays nd_roster_speak / nd_roster_input fill in for k events over text_bytes of inpstr or reads, in the
+        library's order and as _speech_of takes them: outcome, clen, bits, vn, vw, vwsz, ctext, var."""
+        ctext_bytes = _composed_at(2 * text_bytes, 2 * k)
+        return (np.empty(k, dtype=np.int8), np.empty((2, k), dtype=np.int32),
+                np.empty((k, (self.capacity + 63) // 64), dtype=np.uint64), np.empty((2, k, 2), dtype=np.int64),
+                np.empty((2, k, 2), dtype=np.int32), np.empty((2, k, 2, MAX_WRITES), dtype=np.int32),
+                np.empty(ctext_bytes, dtype=np.uint8), np.empty(_variant_at(ctext_bytes, 2 * k), dtype=np.uint8))
 
     def _speech_of(self, text_bytes, text_off, slots, outcome, clen, bits, vn, vw, vwsz, ctext, var, t) -> Speech:
         """The Speech of what nd_roster_speak / nd_roster_input filled in."""
         k, words = len(slots), (self.capacity + 63) // 64
-        # the buffers' layout (nd_roster_speak): text t = k is event k's room line, K + k its reply
-        tstarts = np.empty((2, k), dtype=np.int64)
-        tstarts[0] = text_off.astype(np.int64) + _SPEAK_SLACK * np.arange(k, dtype=np.int64)
-        tstarts[1] = tstarts[0] + text_bytes + _SPEAK_SLACK * k
-        starts = np.empty((2, k, 2), dtype=np.int64)
-        starts[:, :, 0] = 12 * tstarts + 16 * np.arange(2 * k, dtype=np.int64).reshape(2, k)
-        starts[:, :, 1] = starts[:, :, 0] + ((6 * np.maximum(clen, 0).astype(np.int64) + 4 + 3) & ~3)
+        # text t = k is event k's room line, K + k its reply
+        at = text_off.astype(np.int64)
+        tstarts = np.stack([_composed_at(at, np.arange(k)), _composed_at(text_bytes + at, k + np.arange(k))])
+        starts = _variant_starts(tstarts, clen)
         reply_bits = np.zeros((k, words), dtype=np.uint64)
         has = np.flatnonzero(clen[1] >= 0)
         reply_bits[has, slots[has] // 64] = np.uint64(1) << (slots[has] % 64).astype(np.uint64)
-        timing = {"kernels_us": t.kernels_us, "end_to_end_us": t.end_to_end_us, "h2d_bytes": t.h2d_bytes,
-                  "d2h_bytes": t.d2h_bytes}
+        timing = _timing_of(t)
         colour_bits = _pack((self._flags & ROSTER_FLAGS["colour"]) != 0)
         plans = [Plan(capacity=self.capacity, admitted_bits=b, colour_bits=colour_bits, variants=var,
                       variant_starts=starts[i], variant_sizes=vn[i], write_counts=vw[i], write_sizes=vwsz[i],
@@ -1161,29 +1165,19 @@ class Roster:
             try:
                 slot = self._slot(rd[0])
                 data = _read_data(rd[1])
-                if self._room[slot] < 0:
-                    raise ValueError(f"the speaker, slot {slot}, has no room (the talker relays such a user over its "
-                                     f"netlink)")
-                if self._flags[slot] & ROSTER_FLAGS["login"]:
-                    raise ValueError(f"the speaker, slot {slot}, is still logging in")
-                if self._speech[slot, USER_NAME_LEN] == 0:
-                    raise ValueError(f"the speaker, slot {slot}, has no name")
-                if record and not 0 <= self._room[slot] < self.review_rooms:     # the device decides what is a say
-                    raise ValueError(f"it may be recorded, but room {int(self._room[slot])} has no review ring: " +
-                                     (f"the ring rooms are 0 .. {self.review_rooms - 1}" if self.review_rooms else
-                                      "the roster has none (review_rooms is 0)"))
+                # which reads are says and emotes, the device decides
+                self._check_speaker(slot, "it may be recorded" if record else None)
             except ValueError as e:
                 raise ValueError(f"read {k}: {e}") from None
             datas.append(data)
             slots.append(slot)
         lens = np.fromiter((len(d) for d in datas), dtype=np.int64, count=len(datas))
-        bound = 12 * (2 * int(lens.sum()) + 2 * _SPEAK_SLACK * len(lens)) + 32 * len(lens)
+        bound = _variant_at(_composed_at(2 * int(lens.sum()), 2 * len(lens)), 2 * len(lens))
         if bound > MANY_ARENA_CAP:
             raise ValueError(f"call too large: its variant bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
                              f"(MANY_ARENA_CAP): split it")
-        off = np.zeros(len(datas), dtype=np.int32)
-        np.cumsum(lens[:-1], out=off[1:])
-        return datas, b"".join(datas), off, lens.astype(np.int32), np.array(slots, dtype=np.int32), ban_swearing, record
+        return (datas, b"".join(datas), _offsets(lens, np.int32), lens.astype(np.int32),
+                np.array(slots, dtype=np.int32), ban_swearing, record)
 
     def input_many(self, reads, ban_swearing=False, record=False) -> Input:
         """K reads of clients in line mode in one device call: a non-empty sequence of ``(slot, data)`` tuples, what
@@ -1217,19 +1211,11 @@ class Roster:
         datas, data, off, lens, slots, ban, record = self._prepare_input(reads, ban_swearing, record)
         lib = _load()
         handle = self._device_handle(lib)
-        k, words = len(lens), (self.capacity + 63) // 64
-        ctext_bytes = 2 * len(data) + 2 * _SPEAK_SLACK * k
+        k = len(lens)
         kind, com = np.empty(k, dtype=np.int8), np.empty(k, dtype=np.int8)
         wcs = np.empty(k, dtype=np.uint8)
         line_len, inp_off, inp_len = (np.empty(k, dtype=np.int32) for _ in range(3))
-        outcome = np.empty(k, dtype=np.int8)
-        clen = np.empty((2, k), dtype=np.int32)
-        bits = np.empty((k, words), dtype=np.uint64)
-        vn = np.empty((2, k, 2), dtype=np.int64)
-        vw = np.empty((2, k, 2), dtype=np.int32)
-        vwsz = np.empty((2, k, 2, MAX_WRITES), dtype=np.int32)
-        ctext = np.empty(ctext_bytes, dtype=np.uint8)
-        var = np.empty(12 * ctext_bytes + 32 * k, dtype=np.uint8)
+        out = self._speech_arrays(k, len(data))
         dbuf = np.frombuffer(data, dtype=np.uint8)
         clear = self._pending_clear() if record else None
         t = _RosterTiming()
@@ -1237,23 +1223,18 @@ class Roster:
                                  _ptr(self._table) if self._dirty else None,
                                  _ptr(self._speech) if self._speech_dirty else None,
                                  _ptr(clear) if clear is not None else None, _ptr(kind), _ptr(com), _ptr(wcs),
-                                 _ptr(line_len), _ptr(inp_off), _ptr(inp_len), _ptr(outcome), _ptr(clen), _ptr(bits),
-                                 _ptr(vn), _ptr(vw), _ptr(vwsz), _ptr(ctext), _ptr(var), ctypes.byref(t))
-        if rc != 0:
-            raise RuntimeError(f"device input failed: {lib.nd_last_error().decode(errors='replace')}")
+                                 _ptr(line_len), _ptr(inp_off), _ptr(inp_len), *map(_ptr, out), ctypes.byref(t))
+        _check(rc, "device input failed")
         self._dirty = self._speech_dirty = False
         if record:
             self._clear_sent()
-        speech = self._speech_of(len(data), off, slots, outcome, clen, bits, vn, vw, vwsz, ctext, var, t)
+        speech = self._speech_of(len(data), off, slots, *out, t)
         return Input(kind=kind, com=com, word_count=wcs, line_sizes=line_len, inpstr_starts=inp_off.astype(np.int64),
                      inpstr_sizes=inp_len.astype(np.int64), speech=speech, data=datas, timing=dict(speech.timing))
 
     def _ring_room(self, v) -> int:
-        if (not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_))
-                or not 0 <= int(v) < self.review_rooms):
-            raise ValueError(f"room {v!r} has no review ring: " +
-                             (f"the ring rooms are 0 .. {self.review_rooms - 1}" if self.review_rooms else
-                              "the roster has none (review_rooms is 0)"))
+        if not _is_int(v, 0, self.review_rooms - 1):
+            raise ValueError(f"room {v!r} has no review ring: {self._ring_rooms_are()}")
         return int(v)
 
     def _ring_rooms(self, rooms, what: str) -> np.ndarray:
@@ -1297,14 +1278,12 @@ class Roster:
         t = _RosterTiming()
         rc = lib.nd_roster_review(handle, q, _ptr(idx), _ptr(clear) if clear is not None else None, _ptr(counts),
                                   _ptr(seq), _ptr(vn), _ptr(vw), _ptr(vwsz), _ptr(stored), _ptr(var), ctypes.byref(t))
-        if rc != 0:
-            raise RuntimeError(f"device review failed: {lib.nd_last_error().decode(errors='replace')}")
+        _check(rc, "device review failed")
         self._clear_sent()
         starts = (np.arange(2 * q, dtype=np.int64) * _REVIEW_STRIDE).reshape(q, 2)
         return Review(rooms=idx, line_counts=counts, stored=stored, variants=var, variant_starts=starts,
                       variant_sizes=vn.astype(np.int64), write_counts=vw, write_sizes=vwsz, sequential=seq,
-                      timing={"kernels_us": t.kernels_us, "end_to_end_us": t.end_to_end_us, "h2d_bytes": t.h2d_bytes,
-                              "d2h_bytes": t.d2h_bytes})
+                      timing=_timing_of(t))
 
     def close(self) -> None:
         """Free the device table and the review rings; the roster cannot be used afterwards.  Closing twice is

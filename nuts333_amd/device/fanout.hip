@@ -42,7 +42,6 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
-#include <type_traits>
 
 namespace {
 
@@ -79,6 +78,15 @@ __device__ __forceinline__ bool admits(uint8_t l, int rm_is_null, int force_list
     if ((l & kIgnshout) && (com_num == kComShout || com_num == kComSemote)) return false;
     if (l & kSender) return false;
     return true;
+}
+
+// A roster slot's listener record for one broadcast: the slot's own bits from its flags byte, has_room from its room,
+// and the two that the broadcast decides, same_room (never set when rm is -1, every room) and is_sender (sender -1:
+// none).
+__device__ __forceinline__ uint8_t listener_record(int room, uint8_t slot, int rm, int sender, int j)
+{
+    return (slot & (kLogin | kIgnall | kIgnshout | kColour)) | (room >= 0 ? kHasRoom : 0) |
+           (rm >= 0 && room == rm ? kSameRoom : 0) | (j == sender ? kSender : 0);
 }
 
 __device__ __forceinline__ int colcom_at(const uint8_t* s, int i, int len)
@@ -433,7 +441,7 @@ struct RosterArgs {
     uint8_t* admitted;           // [m], m = k * capacity
     int64_t* out_off;            // [m + 1]
     int32_t* w_off;              // [m + 1]
-    uint8_t* var;                // broadcast b's variants: var_at(b), var_at(b) + var_stride(len)
+    uint8_t* var;                // broadcast b's variants: var_at(text_off[b], b), and that plus var_stride(len)
     int64_t* vn;                 // [2k] bytes of broadcast b's colour-off / colour-on variant
     int32_t* vw;                 // [2k] their write(2) counts
     int32_t* vwsz;               // [2k * kMaxWrites] their chunk sizes
@@ -443,46 +451,55 @@ struct RosterArgs {
     int64_t wsz_cap;
 };
 
-// A variant's slot in the variant buffer: its hard bound rounded up to 4 bytes.  Broadcast b's two slots start at
-// 12 * text_off[b] + 16 * b, so the buffer holds 12 * text_bytes + 16 * k bytes and every slot is 4-byte aligned.
+// The variant buffer's layout (Python: _variant_at and _variant_starts of device/__init__.py).  A variant's slot is its
+// hard bound rounded up to 4 bytes; text t, whose bytes start at text_off among the call's texts, has its two slots at
+// var_at(text_off, t) and that plus var_stride(len).  So every slot is 4-byte aligned, and k texts of text_bytes in all
+// need var_at(text_bytes, k) bytes.
 __host__ __device__ __forceinline__ int64_t var_stride(int len) { return (6 * (int64_t)len + 4 + 3) & ~(int64_t)3; }
-__device__ __forceinline__ int64_t var_at(const RosterArgs& a, int b) { return 12 * (int64_t)a.text_off[b] + 16 * (int64_t)b; }
+__host__ __device__ __forceinline__ int64_t var_at(int64_t text_off, int64_t t) { return 12 * text_off + 16 * t; }
+
+// Text t's two variants, by every thread of a block: transduced (stage_variants), then their bytes into the variant
+// buffer, their chunk sizes and counts into vwsz / vn / vw, and a violation for each that broke the hard bounds.
+// Static LDS: every block of a kernel that calls this reserves these ~26 KB, whether it gets here or not.
+template <typename A>   // RosterArgs, PlanArgs or SpeakPlanArgs
+__device__ __forceinline__ void store_variants(const A& a, int t)
+{
+    __shared__ uint8_t text[kTextSize];
+    __shared__ uint8_t var[2 * kVarCap];
+    __shared__ int32_t vwsz[2 * kMaxWrites];
+    __shared__ int64_t vn[2];
+    __shared__ int vw[2];
+    stage_variants<true>(a, t, text, var, vwsz, vn, vw);
+    const int len = a.text_len[t];
+    const int64_t cap = 6 * (int64_t)len + 4, stride = var_stride(len);
+    uint8_t* dst = a.var + var_at(a.text_off[t], t);
+    for (int c = 0; c < 2; c++) {
+        const int64_t n = vn[c] < cap ? vn[c] : cap;
+        for (int64_t q = threadIdx.x; q < n; q += kBlock) dst[c * stride + q] = var[c * kVarCap + q];
+        const int nw = vw[c] < kMaxWrites ? vw[c] : kMaxWrites;
+        if ((int)threadIdx.x < nw) a.vwsz[(2 * t + c) * kMaxWrites + threadIdx.x] = vwsz[c * kMaxWrites + threadIdx.x];
+    }
+    if (threadIdx.x < 2) {
+        a.vn[2 * t + threadIdx.x] = vn[threadIdx.x];
+        a.vw[2 * t + threadIdx.x] = vw[threadIdx.x];
+        if (vn[threadIdx.x] > cap || vw[threadIdx.x] > kMaxWrites) atomicAdd(a.violations, 1);
+    }
+}
 
 __device__ void roster_measure(const RosterArgs& a)
 {
     const int b = (int)blockIdx.x / a.tiles, tile = (int)blockIdx.x - b * a.tiles;
     const int j = tile * kBlock + (int)threadIdx.x;
     if (j < a.capacity) {
-        const int room = a.room[j], rm = a.rm[b];
-        const uint8_t l = (a.slot[j] & (kLogin | kIgnall | kIgnshout | kColour)) | (room >= 0 ? kHasRoom : 0) |
-                          (rm >= 0 && room == rm ? kSameRoom : 0) | (j == a.sender[b] ? kSender : 0);
+        const int rm = a.rm[b];
+        const uint8_t l = listener_record(a.room[j], a.slot[j], rm, a.sender[b], j);
         a.admitted[b * a.capacity + j] = admits(l, rm < 0, (a.flags[b] >> 1) & 1, a.com_num[b]);
     }
-    if (tile == 0) {            // block-uniform: this broadcast's variants, for the scan and emit
-        // Static LDS: every block of the kernel reserves these ~26 KB, the admit-only tiles too, so at most 6 blocks
-        // fit on a CU.  With at most 256 tiles per broadcast and the admit-only blocks this short, that costs little at
-        // the sizes measured; a variant stage of its own grid would lift it, for one more dispatch.
-        __shared__ uint8_t text[kTextSize];
-        __shared__ uint8_t var[2 * kVarCap];
-        __shared__ int32_t vwsz[2 * kMaxWrites];
-        __shared__ int64_t vn[2];
-        __shared__ int vw[2];
-        stage_variants<true>(a, b, text, var, vwsz, vn, vw);
-        const int len = a.text_len[b];
-        const int64_t cap = 6 * (int64_t)len + 4, stride = var_stride(len);
-        uint8_t* dst = a.var + var_at(a, b);
-        for (int c = 0; c < 2; c++) {
-            const int64_t n = vn[c] < cap ? vn[c] : cap;
-            for (int64_t q = threadIdx.x; q < n; q += kBlock) dst[c * stride + q] = var[c * kVarCap + q];
-            const int nw = vw[c] < kMaxWrites ? vw[c] : kMaxWrites;
-            if ((int)threadIdx.x < nw) a.vwsz[(2 * b + c) * kMaxWrites + threadIdx.x] = vwsz[c * kMaxWrites + threadIdx.x];
-        }
-        if (threadIdx.x < 2) {
-            a.vn[2 * b + threadIdx.x] = vn[threadIdx.x];
-            a.vw[2 * b + threadIdx.x] = vw[threadIdx.x];
-            if (vn[threadIdx.x] > cap || vw[threadIdx.x] > kMaxWrites) atomicAdd(a.violations, 1);
-        }
-    }
+    // Block-uniform: this broadcast's variants, for the scan and emit.  The admit-only tiles reserve store_variants'
+    // LDS too, so at most 6 blocks fit on a CU.  With at most 256 tiles per broadcast and the admit-only blocks this
+    // short, that costs little at the sizes measured; a variant stage of its own grid would lift it, for
+    // one more dispatch.
+    if (tile == 0) store_variants(a, b);
 }
 
 // The scans' input: item i's bytes (T = int64_t, v = vn) or writes (T = int32_t, v = vw), its admitted variant's count;
@@ -568,7 +585,7 @@ __device__ void roster_emit(const RosterArgs& a)
         }
     }
     // the broadcast's variants, as measure stored them, clamped to the hard bounds
-    const uint8_t* src = a.var + var_at(a, b);
+    const uint8_t* src = a.var + var_at(a.text_off[b], b);
     const int64_t stride = var_stride(len);
     for (int c = 0; c < 2; c++) {
         const int64_t n = a.vn[2 * b + c] < cap ? a.vn[2 * b + c] : cap;
@@ -616,10 +633,8 @@ struct PlanArgs {
     int32_t* vw;                 // [2k] their write(2) counts
     int32_t* vwsz;               // [2k * kMaxWrites] their chunk sizes
     uint64_t* bits;              // [k * words] the admit bitmap
-    uint8_t* var;                // broadcast b's variants: var_at(b), var_at(b) + var_stride(len)
+    uint8_t* var;                // broadcast b's variants: var_at(text_off[b], b), and that plus var_stride(len)
 };
-
-__device__ __forceinline__ int64_t var_at(const PlanArgs& a, int b) { return 12 * (int64_t)a.text_off[b] + 16 * (int64_t)b; }
 
 __device__ void roster_plan(const PlanArgs& a)
 {
@@ -627,36 +642,14 @@ __device__ void roster_plan(const PlanArgs& a)
     const int j = tile * kBlock + (int)threadIdx.x;
     bool in = false;
     if (j < a.capacity) {
-        const int room = a.room[j], rm = a.rm[b];
-        const uint8_t l = (a.slot[j] & (kLogin | kIgnall | kIgnshout | kColour)) | (room >= 0 ? kHasRoom : 0) |
-                          (rm >= 0 && room == rm ? kSameRoom : 0) | (j == a.sender[b] ? kSender : 0);
+        const int rm = a.rm[b];
+        const uint8_t l = listener_record(a.room[j], a.slot[j], rm, a.sender[b], j);
         in = admits(l, rm < 0, (a.flags[b] >> 1) & 1, a.com_num[b]);
     }
     const uint64_t word = __ballot(in);          // the wave's 64 slots; every lane of the wave is here
     const int w = j >> 6;                        // word of this broadcast: a tile holds kBlock / 64 of them
     if ((threadIdx.x & 63) == 0 && w < a.words) a.bits[(int64_t)b * a.words + w] = word;
-    if (tile == 0) {            // block-uniform: this broadcast's variants, as roster_measure stores them
-        __shared__ uint8_t text[kTextSize];
-        __shared__ uint8_t var[2 * kVarCap];
-        __shared__ int32_t vwsz[2 * kMaxWrites];
-        __shared__ int64_t vn[2];
-        __shared__ int vw[2];
-        stage_variants<true>(a, b, text, var, vwsz, vn, vw);
-        const int len = a.text_len[b];
-        const int64_t cap = 6 * (int64_t)len + 4, stride = var_stride(len);
-        uint8_t* dst = a.var + var_at(a, b);
-        for (int c = 0; c < 2; c++) {
-            const int64_t n = vn[c] < cap ? vn[c] : cap;
-            for (int64_t q = threadIdx.x; q < n; q += kBlock) dst[c * stride + q] = var[c * kVarCap + q];
-            const int nw = vw[c] < kMaxWrites ? vw[c] : kMaxWrites;
-            if ((int)threadIdx.x < nw) a.vwsz[(2 * b + c) * kMaxWrites + threadIdx.x] = vwsz[c * kMaxWrites + threadIdx.x];
-        }
-        if (threadIdx.x < 2) {
-            a.vn[2 * b + threadIdx.x] = vn[threadIdx.x];
-            a.vw[2 * b + threadIdx.x] = vw[threadIdx.x];
-            if (vn[threadIdx.x] > cap || vw[threadIdx.x] > kMaxWrites) atomicAdd(a.violations, 1);
-        }
-    }
+    if (tile == 0) store_variants(a, b);         // block-uniform: this broadcast's variants, as roster_measure's
 }
 
 static_assert(kBlock % 64 == 0, "roster_plan: a tile is whole bitmap words, one per wave");
@@ -996,6 +989,11 @@ constexpr int kNotSpeech = -1;                             // the outcome of an 
 // what nuts_roster_parse decided of an event before the command functions run (SpeakArgs.preset)
 constexpr uint8_t kPresetNone = 0, kPresetVoid = 1, kPresetNothing = 2, kPresetUnknown = 3;
 
+// The composed-text buffer's layout (Python: _composed_at of device/__init__.py).  Text t, whose inpstr starts at
+// text_off among the call's, has its slot at ctext_at(text_off, t); room line b is text b, its reply text k + b over
+// the same inpstr once more (text_off + text_bytes).  So 2k texts need ctext_at(2 * text_bytes, 2k) bytes.
+constexpr int64_t ctext_at(int64_t text_off, int64_t t) { return text_off + kSpeakSlack * t; }
+
 struct SpeakArgs {
     const int32_t* room;         // [capacity] the roster's table: -1, no room
     const uint8_t* speech;       // [capacity * 16] the speaker state this call reads: the upload, or the kept table
@@ -1184,10 +1182,8 @@ struct SpeakPlanArgs {
     int32_t* vw;                 // [4k]
     int32_t* vwsz;               // [4k * kMaxWrites]
     uint64_t* bits;              // [k * words] the room lines' admit bitmap
-    uint8_t* var;                // text t's variants: var_at(t), var_at(t) + var_stride(len)
+    uint8_t* var;                // text t's variants: var_at(text_off[t], t), and that plus var_stride(len)
 };
-
-__device__ __forceinline__ int64_t var_at(const SpeakPlanArgs& a, int t) { return 12 * (int64_t)a.text_off[t] + 16 * (int64_t)t; }
 
 __device__ void roster_speak_plan(const SpeakPlanArgs& a)
 {
@@ -1198,9 +1194,8 @@ __device__ void roster_speak_plan(const SpeakPlanArgs& a)
         const int j = tile * kBlock + (int)threadIdx.x;
         bool in = false;
         if (j < a.capacity && a.text_len[b] >= 0) {
-            const int room = a.room[j], rm = a.rm[b];
-            const uint8_t l = (a.slot[j] & (kLogin | kIgnall | kIgnshout | kColour)) | (room >= 0 ? kHasRoom : 0) |
-                              (rm >= 0 && room == rm ? kSameRoom : 0) | (j == a.sender[b] ? kSender : 0);
+            const int rm = a.rm[b];
+            const uint8_t l = listener_record(a.room[j], a.slot[j], rm, a.sender[b], j);
             in = admits(l, rm < 0, 0, a.com_num[b]);
         }
         const uint64_t word = __ballot(in);
@@ -1211,33 +1206,14 @@ __device__ void roster_speak_plan(const SpeakPlanArgs& a)
     } else {
         t = a.k + ((int)blockIdx.x - lines);
     }
-    const int len = a.text_len[t];
-    if (len < 0) {                          // block-uniform: a void text has no variant, not even a reset
+    if (a.text_len[t] < 0) {                // block-uniform: a void text has no variant, not even a reset
         if (threadIdx.x < 2) {
             a.vn[2 * t + threadIdx.x] = 0;
             a.vw[2 * t + threadIdx.x] = 0;
         }
         return;
     }
-    __shared__ uint8_t text[kTextSize];
-    __shared__ uint8_t var[2 * kVarCap];
-    __shared__ int32_t vwsz[2 * kMaxWrites];
-    __shared__ int64_t vn[2];
-    __shared__ int vw[2];
-    stage_variants<true>(a, t, text, var, vwsz, vn, vw);
-    const int64_t cap = 6 * (int64_t)len + 4, stride = var_stride(len);
-    uint8_t* dst = a.var + var_at(a, t);
-    for (int c = 0; c < 2; c++) {
-        const int64_t n = vn[c] < cap ? vn[c] : cap;
-        for (int64_t q = threadIdx.x; q < n; q += kBlock) dst[c * stride + q] = var[c * kVarCap + q];
-        const int nw = vw[c] < kMaxWrites ? vw[c] : kMaxWrites;
-        if ((int)threadIdx.x < nw) a.vwsz[(2 * t + c) * kMaxWrites + threadIdx.x] = vwsz[c * kMaxWrites + threadIdx.x];
-    }
-    if (threadIdx.x < 2) {
-        a.vn[2 * t + threadIdx.x] = vn[threadIdx.x];
-        a.vw[2 * t + threadIdx.x] = vw[threadIdx.x];
-        if (vn[threadIdx.x] > cap || vw[threadIdx.x] > kMaxWrites) atomicAdd(a.violations, 1);
-    }
+    store_variants(a, t);
 }
 
 static_assert(kArrSize - 1 + kSpeakSlack < kTextSize, "roster_speak_plan: a composed text fits stage_variants' LDS text");
@@ -1542,15 +1518,41 @@ int ensure_ready()
     return 0;
 }
 
+// Carves the block at `base` into arrays, one 256-byte aligned slice per call; `at` is the bytes taken so far.  With
+// base 0 the pointers are the arrays' offsets in the block.
+struct Carver {
+    uintptr_t base;
+    size_t at = 0;
+    template <typename T>
+    void operator()(T*& p, size_t count)
+    {
+        p = reinterpret_cast<T*>(base + at);
+        at += (count * sizeof(T) + 255) & ~(size_t)255;
+    }
+};
+
+// A call's inputs are packed in pinned memory at h as they lie on the device: `at` names an array by its offset in the
+// block, as a layout at base 0 gives it.
+struct Put {
+    uint8_t* h;
+    void operator()(const void* at, const void* src, size_t bytes) const
+    {
+        if (bytes) memcpy(h + (uintptr_t)at, src, bytes);
+    }
+};
+
+// And its first results land in pinned memory at h, from the block's byte `first` on: where the array at `at` is.
+struct Res {
+    const uint8_t* h;
+    size_t first;
+    const uint8_t* operator()(const void* at) const { return h + ((uintptr_t)at - first); }
+};
+
 // Point every device array of a (a.n items, the arena and chunk capacities already set) and *scan into the block at
-// base, one 256-byte aligned slice each; returns the bytes they span.  layout(0, ...) sizes the block.
+// base; returns the bytes they span.  layout(0, ...) sizes the block.
 size_t layout(uintptr_t base, size_t text_bytes, size_t scan_bytes, Args& a, uint8_t** scan)
 {
-    size_t at = 0;
-    auto take = [&](auto*& p, size_t count) {
-        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + at);
-        at += (count * sizeof(*p) + 255) & ~(size_t)255;
-    };
+    Carver take{base};
     const size_t n = (size_t)a.n;
     take(a.text, text_bytes);
     take(a.text_off, n);
@@ -1565,7 +1567,7 @@ size_t layout(uintptr_t base, size_t text_bytes, size_t scan_bytes, Args& a, uin
     take(a.arena, (size_t)a.arena_cap);
     take(a.wsz, (size_t)a.wsz_cap);
     take(*scan, scan_bytes);
-    return at;
+    return take.at;
 }
 
 double now_ns()
@@ -1583,16 +1585,55 @@ struct ManyHost {
 };
 ManyHost gm;
 
+// The two clocks of a call whose kernels ran between g.ev0 and g.ev1 and whose host work took t0 .. t1.
+template <typename T>   // nd_timing or nd_roster_timing
+int fill_timing(T* timing, double t0, double t1)
+{
+    float ms = 0.f;
+    ND_CHECK(hipEventElapsedTime(&ms, g.ev0, g.ev1));
+    if (timing) {
+        timing->kernels_us = (double)ms * 1e3;
+        timing->end_to_end_us = (t1 - t0) * 1e-3;
+    }
+    return 0;
+}
+
+// And a roster call's copy volume.
+template <typename T>   // nd_roster_timing
+int fill_timing(T* timing, double t0, double t1, size_t h2d_bytes, size_t d2h_bytes)
+{
+    if (fill_timing(timing, t0, t1)) return -1;
+    if (timing) {
+        timing->h2d_bytes = (int64_t)h2d_bytes;
+        timing->d2h_bytes = (int64_t)d2h_bytes;
+    }
+    return 0;
+}
+
+// The kernels count what broke the transducer's hard bounds; any such `what` ("item", "variant") fails the call.
+int check_bounds(int violations, const char* what)
+{
+    if (!violations) return 0;
+    snprintf(g_err, sizeof(g_err), "%d %s(s) exceeded the hard output bounds (6*len+4 bytes, %d writes)", violations,
+             what, kMaxWrites);
+    return -1;
+}
+
+// The kernels end here: res_bytes of results from byte res_at of the device block d into gm.res, and a synchronise.
+int fetch_results(const uint8_t* d, size_t res_at, size_t res_bytes)
+{
+    ND_CHECK(hipEventRecord(g.ev1, g.stream));
+    ND_CHECK(hipMemcpyAsync(gm.res, d + res_at, res_bytes, hipMemcpyDeviceToHost, g.stream));
+    ND_CHECK(hipStreamSynchronize(g.stream));
+    return 0;
+}
+
 // As layout(), for ManyArgs (a.k, a.m and the capacities set).  The inputs come first and end with violations, so
 // one upload fills them all and zeroes violations; violations, admitted, out_off and w_off follow each other, so one
 // download fetches them.  layout_many(0, ...) gives every array's offset in the block.
 size_t layout_many(uintptr_t base, size_t text_bytes, size_t scan_bytes, ManyArgs& a, uint8_t** scan)
 {
-    size_t at = 0;
-    auto take = [&](auto*& p, size_t count) {
-        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + at);
-        at += (count * sizeof(*p) + 255) & ~(size_t)255;
-    };
+    Carver take{base};
     const size_t k = (size_t)a.k, m = (size_t)a.m;
     take(a.text, text_bytes);
     take(a.text_off, k);
@@ -1611,7 +1652,7 @@ size_t layout_many(uintptr_t base, size_t text_bytes, size_t scan_bytes, ManyArg
     take(a.arena, (size_t)a.arena_cap);
     take(a.wsz, (size_t)a.wsz_cap);
     take(*scan, scan_bytes);
-    return at;
+    return take.at;
 }
 
 // A roster's own device allocation and its pinned mirror, laid out alike by layout_roster(): the table (room, slot),
@@ -1638,16 +1679,19 @@ Roster g_rosters[kMaxRosters];
 size_t revline_at(const Roster& r) { return ((size_t)r.review_rooms * kRevRing + 255) & ~(size_t)255; }
 size_t rings_bytes(const Roster& r) { return revline_at(r) + (size_t)r.review_rooms * sizeof(int32_t); }
 
+// The head of every layout of a roster's allocation: the table.  Its place depends on the capacity alone, so the table
+// stays resident across every kind of call, and a call that does not read it need not upload it.
+void take_table(Carver& take, int capacity, const int32_t*& room, const uint8_t*& slot)
+{
+    take(room, (size_t)capacity);
+    take(slot, (size_t)capacity);
+}
+
 size_t layout_roster(uintptr_t base, size_t text_bytes, RosterArgs& a)
 {
-    size_t at = 0;
-    auto take = [&](auto*& p, size_t count) {
-        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + at);
-        at += (count * sizeof(*p) + 255) & ~(size_t)255;
-    };
+    Carver take{base};
     const size_t k = (size_t)a.k, m = k * (size_t)a.capacity;
-    take(a.room, (size_t)a.capacity);
-    take(a.slot, (size_t)a.capacity);
+    take_table(take, a.capacity, a.room, a.slot);
     take(a.text, text_bytes);
     take(a.text_off, k);
     take(a.text_len, k);
@@ -1659,17 +1703,13 @@ size_t layout_roster(uintptr_t base, size_t text_bytes, RosterArgs& a)
     take(a.admitted, m);
     take(a.out_off, m + 1);
     take(a.w_off, m + 1);
-    return at;
+    return take.at;
 }
 
 // The call's work arrays in the shared device block: the variants, the arena, the chunk sizes and the scans' scratch.
 size_t layout_roster_work(uintptr_t base, size_t var_bytes, size_t scan_bytes, RosterArgs& a, uint8_t** scan)
 {
-    size_t at = 0;
-    auto take = [&](auto*& p, size_t count) {
-        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + at);
-        at += (count * sizeof(*p) + 255) & ~(size_t)255;
-    };
+    Carver take{base};
     const size_t k = (size_t)a.k;
     take(a.var, var_bytes);
     take(a.vn, 2 * k);
@@ -1678,23 +1718,17 @@ size_t layout_roster_work(uintptr_t base, size_t var_bytes, size_t scan_bytes, R
     take(a.arena, (size_t)a.arena_cap);
     take(a.wsz, (size_t)a.wsz_cap);
     take(*scan, scan_bytes);
-    return at;
+    return take.at;
 }
 
-// nd_roster_plan's layout of a roster's allocation: the table and the call's inputs as layout_roster() places them
-// (the table's place depends on the capacity alone, so it stays resident across both kinds of call), then the
-// results, violations .. var, next to each other: one download fetches them all at their bound size.
+// nd_roster_plan's layout of a roster's allocation: the table and the call's inputs as layout_roster() places them,
+// then the results, violations .. var, next to each other: one download fetches them all at their bound size.
 size_t layout_plan(uintptr_t base, size_t text_bytes, size_t var_bytes, PlanArgs& a, size_t clear_bytes,
                    const uint8_t** clear)
 {
-    size_t at = 0;
-    auto take = [&](auto*& p, size_t count) {
-        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + at);
-        at += (count * sizeof(*p) + 255) & ~(size_t)255;
-    };
+    Carver take{base};
     const size_t k = (size_t)a.k;
-    take(a.room, (size_t)a.capacity);
-    take(a.slot, (size_t)a.capacity);
+    take_table(take, a.capacity, a.room, a.slot);
     take(a.text, text_bytes);
     take(a.text_off, k);
     take(a.text_len, k);
@@ -1709,23 +1743,18 @@ size_t layout_plan(uintptr_t base, size_t text_bytes, size_t var_bytes, PlanArgs
     take(a.vwsz, 2 * k * kMaxWrites);
     take(a.bits, k * (size_t)a.words);
     take(a.var, var_bytes);
-    return at;
+    return take.at;
 }
 
-// nd_roster_review's layout of a roster's allocation: the table where layout_roster() places it (it stays resident and
-// is not uploaded), the call's inputs ending with violations, then the results next to each other.
+// nd_roster_review's layout of a roster's allocation: the table, which the call neither reads nor uploads, the call's
+// inputs ending with violations, then the results next to each other.
 size_t layout_review(uintptr_t base, int capacity, size_t clear_bytes, ReviewArgs& a)
 {
-    size_t at = 0;
-    auto take = [&](auto*& p, size_t count) {
-        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + at);
-        at += (count * sizeof(*p) + 255) & ~(size_t)255;
-    };
+    Carver take{base};
     const size_t q = (size_t)a.q;
     const int32_t* room;
     const uint8_t* slot;
-    take(room, (size_t)capacity);
-    take(slot, (size_t)capacity);
+    take_table(take, capacity, room, slot);
     take(a.rooms, q);
     take(a.clear, clear_bytes);
     take(a.violations, 1);
@@ -1736,10 +1765,10 @@ size_t layout_review(uintptr_t base, int capacity, size_t clear_bytes, ReviewArg
     take(a.vwsz, 2 * q * kRevWrites);
     take(a.lines, q * kRevRing);
     take(a.var, 2 * q * kRevVarStride);
-    return at;
+    return take.at;
 }
 
-// nd_roster_speak's layout of a roster's allocation: the table where layout_roster() places it, then the upload of the
+// nd_roster_speak's layout of a roster's allocation: the table, then the upload of the
 // speaker table (which the kept one, r.speech, is filled from), the call's inputs ending with violations, the results
 // next to each other, and last what only the kernels pass to each other.  One upload starts at the table, at the speaker
 // table or at the inputs, whichever is the first that changed.
@@ -1749,15 +1778,10 @@ size_t layout_review(uintptr_t base, int capacity, size_t clear_bytes, ReviewArg
 size_t layout_speak(uintptr_t base, size_t text_bytes, size_t clear_bytes, SpeakArgs& s, SpeakPlanArgs& p,
                     const uint8_t** clear, ParseArgs* q = nullptr)
 {
-    size_t at = 0;
-    auto take = [&](auto*& ptr, size_t count) {
-        ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(base + at);
-        at += (count * sizeof(*ptr) + 255) & ~(size_t)255;
-    };
+    Carver take{base};
     const size_t k = (size_t)s.k, cap = (size_t)s.capacity;
-    const size_t ctext_bytes = 2 * text_bytes + 2 * k * kSpeakSlack;
-    take(s.room, cap);
-    take(p.slot, cap);
+    const size_t ctext_bytes = (size_t)ctext_at(2 * (int64_t)text_bytes, 2 * (int64_t)k);
+    take_table(take, s.capacity, s.room, p.slot);
     take(s.speech_new, cap * kSpeechRec);
     take(s.text, text_bytes);
     if (q) {
@@ -1790,7 +1814,7 @@ size_t layout_speak(uintptr_t base, size_t text_bytes, size_t clear_bytes, Speak
     take(p.vwsz, 4 * k * kMaxWrites);
     take(p.bits, k * (size_t)p.words);
     take(s.ctext, ctext_bytes);
-    take(p.var, 12 * ctext_bytes + 32 * k);
+    take(p.var, (size_t)var_at((int64_t)ctext_bytes, 2 * (int64_t)k));
     take(s.rm, k);
     take(s.sender, k);
     take(s.com_num, k);
@@ -1813,7 +1837,7 @@ size_t layout_speak(uintptr_t base, size_t text_bytes, size_t clear_bytes, Speak
     p.sender = s.sender;
     p.com_num = s.com_num;
     p.violations = s.violations;
-    return at;
+    return take.at;
 }
 
 // The roster's rings, made and zeroed in the stream on first use.
@@ -1850,6 +1874,39 @@ int grow_mirror(Roster& r, size_t want, size_t keep)
     }
     r.mirror = p;
     r.cap_mirror = want;
+    return 0;
+}
+
+// The caller's new table into r's mirror, at the offsets a layout gave the table; the device allocation is stale then.
+void new_table(Roster& r, const int32_t* room_at, const uint8_t* slot_at, const uint8_t* table)
+{
+    const int cap = r.capacity;
+    memcpy(r.mirror + (uintptr_t)room_at, table, (size_t)cap * sizeof(int32_t));
+    memcpy(r.mirror + (uintptr_t)slot_at, table + (size_t)cap * sizeof(int32_t), (size_t)cap);
+    const int32_t* room = reinterpret_cast<const int32_t*>(r.mirror + (uintptr_t)room_at);
+    r.rooms = std::count_if(room, room + cap, [](int32_t x) { return x >= 0; });
+    r.resident = false;
+}
+
+// Grow r's device allocation to `need` bytes.  A new one does not hold the table: the next call that reads the table
+// uploads it from the mirror.
+int grow_roster(Roster& r, size_t need)
+{
+    const size_t cap_d = r.cap_d;
+    if (grow_dev(&r.d, &r.cap_d, need, "roster device allocation")) return -1;
+    if (r.cap_d != cap_d) r.resident = false;
+    return 0;
+}
+
+// nuts_roster_record after a call's planning kernel, on device arrays of that call: the k texts, their rooms and flags
+// (bit 2: record), and the pending clears (nullptr: none).  The rings are touched by g.stream alone.
+int launch_record(const Roster& r, int k, const uint8_t* text, const int32_t* text_off, const int32_t* text_len,
+                  const int32_t* rm, const uint8_t* flags, const uint8_t* clear)
+{
+    RecordArgs rec{text, text_off, text_len, rm, flags, clear, k, r.review_rooms, r.rings,
+                   reinterpret_cast<int32_t*>(r.rings + revline_at(r))};
+    hipLaunchKernelGGL(nuts_roster_record, dim3((unsigned)r.review_rooms), dim3(kBlock), 0, g.stream, rec);
+    ND_CHECK(hipGetLastError());
     return 0;
 }
 
@@ -1953,11 +2010,7 @@ int nd_fanout(int broadcast, const uint8_t* text, int64_t text_bytes, const int3
     ND_CHECK(hipMemcpyAsync(w_off, a.w_off, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     ND_CHECK(hipMemcpyAsync(&violations, a.violations, sizeof(int), hipMemcpyDeviceToHost, st));
     ND_CHECK(hipStreamSynchronize(st));
-    if (violations) {
-        snprintf(g_err, sizeof(g_err), "%d item(s) exceeded the hard output bounds (6*len+4 bytes, %d writes)",
-                 violations, kMaxWrites);
-        return -1;
-    }
+    if (check_bounds(violations, "item")) return -1;
     if (grow_host(&g.h_arena, &g.cap_host_arena, (size_t)out_off[n] + 1, "pinned arena")) return -1;
     if (grow_host(&g.h_wsz, &g.cap_host_writes, (size_t)w_off[n] + 1, "pinned write sizes")) return -1;
     ND_CHECK(hipMemcpyAsync(g.h_arena, a.arena, (size_t)out_off[n], hipMemcpyDeviceToHost, st));
@@ -1965,13 +2018,7 @@ int nd_fanout(int broadcast, const uint8_t* text, int64_t text_bytes, const int3
     ND_CHECK(hipStreamSynchronize(st));
     const double t1 = now_ns();
 
-    float ms = 0.f;
-    ND_CHECK(hipEventElapsedTime(&ms, g.ev0, g.ev1));
-    if (timing) {
-        timing->kernels_us = (double)ms * 1e3;
-        timing->end_to_end_us = (t1 - t0) * 1e-3;
-    }
-    return 0;
+    return fill_timing(timing, t0, t1);
 }
 
 const uint8_t* nd_arena(void) { return g.h_arena; }
@@ -2022,9 +2069,7 @@ int nd_fanout_many(int k, const uint8_t* text, int64_t text_bytes, const int32_t
 
     // pack the inputs as they lie in the block; the block offsets go with them
     uint8_t* h = gm.stage;
-    auto put = [&](const void* at, const void* src, size_t bytes) {
-        if (bytes) memcpy(h + (uintptr_t)at, src, bytes);
-    };
+    const Put put{h};
     put(o.text, text, (size_t)text_bytes);
     put(o.text_off, text_off, (size_t)k * sizeof(int32_t));
     put(o.text_len, text_len, (size_t)k * sizeof(int32_t));
@@ -2048,18 +2093,11 @@ int nd_fanout_many(int k, const uint8_t* text, int64_t text_bytes, const int32_t
     ND_CHECK(hipcub::DeviceScan::ExclusiveSum(scan, bytes, a.nwrites, a.w_off, m + 1, st));
     hipLaunchKernelGGL(nuts_fanout_emit_many, grid, block, 0, st, a);
     ND_CHECK(hipGetLastError());
-    ND_CHECK(hipEventRecord(g.ev1, st));
 
     // violations, admitted and the offsets in one download: they say how much of the arena to fetch
-    ND_CHECK(hipMemcpyAsync(gm.res, g.d_block + res_at, res_bytes, hipMemcpyDeviceToHost, st));
-    ND_CHECK(hipStreamSynchronize(st));
-    auto res = [&](const void* at) { return gm.res + ((uintptr_t)at - res_at); };
-    const int violations = *reinterpret_cast<const int*>(res(o.violations));
-    if (violations) {
-        snprintf(g_err, sizeof(g_err), "%d item(s) exceeded the hard output bounds (6*len+4 bytes, %d writes)",
-                 violations, kMaxWrites);
-        return -1;
-    }
+    if (fetch_results(g.d_block, res_at, res_bytes)) return -1;
+    const Res res{gm.res, res_at};
+    if (check_bounds(*reinterpret_cast<const int*>(res(o.violations)), "item")) return -1;
     memcpy(admitted, res(o.admitted), (size_t)m);
     memcpy(out_off, res(o.out_off), ((size_t)m + 1) * sizeof(int64_t));
     memcpy(w_off, res(o.w_off), ((size_t)m + 1) * sizeof(int32_t));
@@ -2070,13 +2108,7 @@ int nd_fanout_many(int k, const uint8_t* text, int64_t text_bytes, const int32_t
     ND_CHECK(hipStreamSynchronize(st));
     const double t1 = now_ns();
 
-    float ms = 0.f;
-    ND_CHECK(hipEventElapsedTime(&ms, g.ev0, g.ev1));
-    if (timing) {
-        timing->kernels_us = (double)ms * 1e3;
-        timing->end_to_end_us = (t1 - t0) * 1e-3;
-    }
-    return 0;
+    return fill_timing(timing, t0, t1);
 }
 
 // Timings and copy volume of the last nd_roster_fanout call.
@@ -2152,23 +2184,15 @@ int nd_roster_fanout(int handle, int k, const uint8_t* text, int64_t text_bytes,
     const size_t table_bytes = (uintptr_t)o.text, in_bytes = (uintptr_t)o.violations + sizeof(int);
     const size_t res_at = (uintptr_t)o.violations, res_bytes = (uintptr_t)o.w_off + ((size_t)m + 1) * sizeof(int32_t) - res_at;
     if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
-    if (table) {
-        memcpy(r->mirror + (uintptr_t)o.room, table, (size_t)cap * sizeof(int32_t));
-        memcpy(r->mirror + (uintptr_t)o.slot, table + (size_t)cap * sizeof(int32_t), (size_t)cap);
-        const int32_t* room = reinterpret_cast<const int32_t*>(r->mirror + (uintptr_t)o.room);
-        r->rooms = std::count_if(room, room + cap, [](int32_t x) { return x >= 0; });
-        r->resident = false;
-    }
-    const size_t cap_d = r->cap_d;
-    if (grow_dev(&r->d, &r->cap_d, need, "roster device allocation")) return -1;
-    if (r->cap_d != cap_d) r->resident = false;
+    if (table) new_table(*r, o.room, o.slot, table);
+    if (grow_roster(*r, need)) return -1;
     layout_roster((uintptr_t)r->d, (size_t)text_bytes, a);
     for (int b = 0; b < k; b++) a.arena_cap += r->rooms * (6 * (int64_t)text_len[b] + 4);
     a.wsz_cap = r->rooms * k * kMaxWrites;
     size_t scan1 = 0, scan2 = 0;     // both scans run over m + 1 entries
     ND_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan1, item_bytes(a, m), a.out_off, m + 1, st));
     ND_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan2, item_writes(a, m), a.w_off, m + 1, st));
-    const size_t scan_bytes = std::max(scan1, scan2), var_bytes = 12 * (size_t)text_bytes + 16 * (size_t)k;
+    const size_t scan_bytes = std::max(scan1, scan2), var_bytes = (size_t)var_at(text_bytes, k);
     uint8_t* scan = nullptr;
     RosterArgs w = a;
     const size_t work = layout_roster_work(0, var_bytes, scan_bytes, w, &scan);
@@ -2178,9 +2202,7 @@ int nd_roster_fanout(int handle, int k, const uint8_t* text, int64_t text_bytes,
 
     // the inputs packed after the table, as they lie in the device allocation; the table goes with them if it changed
     uint8_t* h = r->mirror;
-    auto put = [&](const void* at, const void* src, size_t bytes) {
-        if (bytes) memcpy(h + (uintptr_t)at, src, bytes);
-    };
+    const Put put{h};
     put(o.text, text, (size_t)text_bytes);
     put(o.text_off, text_off, (size_t)k * sizeof(int32_t));
     put(o.text_len, text_len, (size_t)k * sizeof(int32_t));
@@ -2203,18 +2225,11 @@ int nd_roster_fanout(int handle, int k, const uint8_t* text, int64_t text_bytes,
     ND_CHECK(hipcub::DeviceScan::ExclusiveSum(scan, bytes, item_writes(a, m), a.w_off, m + 1, st));
     hipLaunchKernelGGL(nuts_roster_emit, grid, block, 0, st, a);
     ND_CHECK(hipGetLastError());
-    ND_CHECK(hipEventRecord(g.ev1, st));
 
     // violations, admitted and the offsets in one download: they say how much of the arena to fetch
-    ND_CHECK(hipMemcpyAsync(gm.res, r->d + res_at, res_bytes, hipMemcpyDeviceToHost, st));
-    ND_CHECK(hipStreamSynchronize(st));
-    auto res = [&](const void* at) { return gm.res + ((uintptr_t)at - res_at); };
-    const int violations = *reinterpret_cast<const int*>(res(o.violations));
-    if (violations) {
-        snprintf(g_err, sizeof(g_err), "%d variant(s) exceeded the hard output bounds (6*len+4 bytes, %d writes)",
-                 violations, kMaxWrites);
-        return -1;
-    }
+    if (fetch_results(r->d, res_at, res_bytes)) return -1;
+    const Res res{gm.res, res_at};
+    if (check_bounds(*reinterpret_cast<const int*>(res(o.violations)), "variant")) return -1;
     memcpy(admitted, res(o.admitted), (size_t)m);
     memcpy(out_off, res(o.out_off), ((size_t)m + 1) * sizeof(int64_t));
     memcpy(w_off, res(o.w_off), ((size_t)m + 1) * sizeof(int32_t));
@@ -2225,15 +2240,8 @@ int nd_roster_fanout(int handle, int k, const uint8_t* text, int64_t text_bytes,
     ND_CHECK(hipStreamSynchronize(st));
     const double t1 = now_ns();
 
-    float ms = 0.f;
-    ND_CHECK(hipEventElapsedTime(&ms, g.ev0, g.ev1));
-    if (timing) {
-        timing->kernels_us = (double)ms * 1e3;
-        timing->end_to_end_us = (t1 - t0) * 1e-3;
-        timing->h2d_bytes = (int64_t)(in_bytes - from);
-        timing->d2h_bytes = (int64_t)(res_bytes + (size_t)out_off[m] + (size_t)w_off[m] * sizeof(int32_t));
-    }
-    return 0;
+    return fill_timing(timing, t0, t1, in_bytes - from,
+                       res_bytes + (size_t)out_off[m] + (size_t)w_off[m] * sizeof(int32_t));
 }
 
 // A delivery plan for K broadcasts to roster `handle`: inputs and table exactly as nd_roster_fanout's.  Outputs (host,
@@ -2270,7 +2278,7 @@ static int plan_call(int handle, int k, const uint8_t* text, int64_t text_bytes,
     a.capacity = cap;
     a.tiles = (cap + kBlock - 1) / kBlock;
     a.words = words;
-    const size_t var_bytes = 12 * (size_t)text_bytes + 16 * (size_t)k;
+    const size_t var_bytes = (size_t)var_at(text_bytes, k);
     PlanArgs o = a;                  // offsets of every array in the roster's allocation
     const size_t clear_bytes = record && clear ? (size_t)r->review_rooms : 0;
     const uint8_t *o_clear = nullptr, *d_clear = nullptr;
@@ -2278,24 +2286,14 @@ static int plan_call(int handle, int k, const uint8_t* text, int64_t text_bytes,
     const size_t table_bytes = (uintptr_t)o.text, in_bytes = (uintptr_t)o.violations + sizeof(int);
     const size_t res_at = (uintptr_t)o.violations, res_bytes = (uintptr_t)o.var + var_bytes - res_at;
     if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
-    if (table) {
-        memcpy(r->mirror + (uintptr_t)o.room, table, (size_t)cap * sizeof(int32_t));
-        memcpy(r->mirror + (uintptr_t)o.slot, table + (size_t)cap * sizeof(int32_t), (size_t)cap);
-        const int32_t* room = reinterpret_cast<const int32_t*>(r->mirror + (uintptr_t)o.room);
-        r->rooms = std::count_if(room, room + cap, [](int32_t x) { return x >= 0; });
-        r->resident = false;
-    }
-    const size_t cap_d = r->cap_d;
-    if (grow_dev(&r->d, &r->cap_d, need, "roster device allocation")) return -1;
-    if (r->cap_d != cap_d) r->resident = false;
+    if (table) new_table(*r, o.room, o.slot, table);
+    if (grow_roster(*r, need)) return -1;
     layout_plan((uintptr_t)r->d, (size_t)text_bytes, var_bytes, a, clear_bytes, &d_clear);
     if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
 
     // the inputs packed after the table, as they lie in the device allocation; the table goes with them if it changed
     uint8_t* h = r->mirror;
-    auto put = [&](const void* at, const void* src, size_t bytes) {
-        if (bytes) memcpy(h + (uintptr_t)at, src, bytes);
-    };
+    const Put put{h};
     put(o.text, text, (size_t)text_bytes);
     put(o.text_off, text_off, (size_t)k * sizeof(int32_t));
     put(o.text_len, text_len, (size_t)k * sizeof(int32_t));
@@ -2313,39 +2311,21 @@ static int plan_call(int handle, int k, const uint8_t* text, int64_t text_bytes,
     ND_CHECK(hipEventRecord(g.ev0, st));
     hipLaunchKernelGGL(nuts_roster_plan, grid, block, 0, st, a);
     ND_CHECK(hipGetLastError());
-    if (record) {                    // on the inputs just uploaded; the rings are touched by this stream alone
-        RecordArgs rec{a.text, a.text_off, a.text_len, a.rm, a.flags, clear_bytes ? d_clear : nullptr, k,
-                       r->review_rooms, r->rings, reinterpret_cast<int32_t*>(r->rings + revline_at(*r))};
-        hipLaunchKernelGGL(nuts_roster_record, dim3((unsigned)r->review_rooms), block, 0, st, rec);
-        ND_CHECK(hipGetLastError());
-    }
-    ND_CHECK(hipEventRecord(g.ev1, st));
-    ND_CHECK(hipMemcpyAsync(gm.res, r->d + res_at, res_bytes, hipMemcpyDeviceToHost, st));
-    ND_CHECK(hipStreamSynchronize(st));
+    // on the inputs just uploaded
+    if (record && launch_record(*r, k, a.text, a.text_off, a.text_len, a.rm, a.flags, clear_bytes ? d_clear : nullptr))
+        return -1;
+    if (fetch_results(r->d, res_at, res_bytes)) return -1;
     const double t1 = now_ns();
 
-    auto res = [&](const void* at) { return gm.res + ((uintptr_t)at - res_at); };
-    const int violations = *reinterpret_cast<const int*>(res(o.violations));
-    if (violations) {
-        snprintf(g_err, sizeof(g_err), "%d variant(s) exceeded the hard output bounds (6*len+4 bytes, %d writes)",
-                 violations, kMaxWrites);
-        return -1;
-    }
+    const Res res{gm.res, res_at};
+    if (check_bounds(*reinterpret_cast<const int*>(res(o.violations)), "variant")) return -1;
     memcpy(vn, res(o.vn), 2 * (size_t)k * sizeof(int64_t));
     memcpy(vw, res(o.vw), 2 * (size_t)k * sizeof(int32_t));
     memcpy(vwsz, res(o.vwsz), 2 * (size_t)k * kMaxWrites * sizeof(int32_t));
     memcpy(bits, res(o.bits), (size_t)k * words * sizeof(uint64_t));
     memcpy(var, res(o.var), var_bytes);
 
-    float ms = 0.f;
-    ND_CHECK(hipEventElapsedTime(&ms, g.ev0, g.ev1));
-    if (timing) {
-        timing->kernels_us = (double)ms * 1e3;
-        timing->end_to_end_us = (t1 - t0) * 1e-3;
-        timing->h2d_bytes = (int64_t)(in_bytes - from);
-        timing->d2h_bytes = (int64_t)res_bytes;
-    }
-    return 0;
+    return fill_timing(timing, t0, t1, in_bytes - from, res_bytes);
 }
 
 // The plan alone (plan_call above): bit 2 of flags[] is not looked at, and nothing touches the rings.
@@ -2417,9 +2397,7 @@ int nd_roster_review(int handle, int q, const int32_t* rooms, const uint8_t* cle
     const size_t table_bytes = (uintptr_t)o.rooms, in_bytes = (uintptr_t)o.violations + sizeof(int);
     const size_t res_at = (uintptr_t)o.violations, res_bytes = need - res_at;
     if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
-    const size_t cap_d = r->cap_d;
-    if (grow_dev(&r->d, &r->cap_d, need, "roster device allocation")) return -1;
-    if (r->cap_d != cap_d) r->resident = false;      // the next broadcast call refills the table from the mirror
+    if (grow_roster(*r, need)) return -1;
     layout_review((uintptr_t)r->d, r->capacity, clear_bytes, a);
     if (!clear) a.clear = nullptr;
     a.rings = r->rings;
@@ -2437,12 +2415,10 @@ int nd_roster_review(int handle, int q, const int32_t* rooms, const uint8_t* cle
     ND_CHECK(hipEventRecord(g.ev0, st));
     hipLaunchKernelGGL(nuts_roster_review, dim3(grid), dim3(kBlock), 0, st, a);
     ND_CHECK(hipGetLastError());
-    ND_CHECK(hipEventRecord(g.ev1, st));
-    ND_CHECK(hipMemcpyAsync(gm.res, r->d + res_at, res_bytes, hipMemcpyDeviceToHost, st));
-    ND_CHECK(hipStreamSynchronize(st));
+    if (fetch_results(r->d, res_at, res_bytes)) return -1;
     const double t1 = now_ns();
 
-    auto res = [&](const void* at) { return gm.res + ((uintptr_t)at - res_at); };
+    const Res res{gm.res, res_at};
     const int violations = *reinterpret_cast<const int*>(res(o.violations));
     if (violations) {
         snprintf(g_err, sizeof(g_err), "%d line(s) exceeded the hard output bounds (%d bytes, %d writes)", violations,
@@ -2457,15 +2433,7 @@ int nd_roster_review(int handle, int q, const int32_t* rooms, const uint8_t* cle
     memcpy(lines, res(o.lines), (size_t)q * kRevRing);
     memcpy(var, res(o.var), 2 * (size_t)q * kRevVarStride);
 
-    float ms = 0.f;
-    ND_CHECK(hipEventElapsedTime(&ms, g.ev0, g.ev1));
-    if (timing) {
-        timing->kernels_us = (double)ms * 1e3;
-        timing->end_to_end_us = (t1 - t0) * 1e-3;
-        timing->h2d_bytes = (int64_t)(in_bytes - table_bytes);
-        timing->d2h_bytes = (int64_t)res_bytes;
-    }
-    return 0;
+    return fill_timing(timing, t0, t1, in_bytes - table_bytes, res_bytes);
 }
 
 // What nd_roster_input returns of nuts_roster_parse: host arrays of k entries each.
@@ -2539,8 +2507,8 @@ static int speech_call(int handle, int k, const uint8_t* text, int64_t text_byte
     s.record = record != 0;
     p.tiles = (cap + kBlock - 1) / kBlock;
     p.words = nwords;
-    const size_t ctext_bytes = 2 * (size_t)text_bytes + 2 * (size_t)k * kSpeakSlack;
-    const size_t var_bytes = 12 * ctext_bytes + 32 * (size_t)k;
+    const size_t ctext_bytes = (size_t)ctext_at(2 * text_bytes, 2 * (int64_t)k);
+    const size_t var_bytes = (size_t)var_at((int64_t)ctext_bytes, 2 * (int64_t)k);
     const size_t clear_bytes = record && clear ? (size_t)r->review_rooms : 0;
     SpeakArgs so = s;                // offsets of every array in the roster's allocation
     SpeakPlanArgs po = p;
@@ -2552,23 +2520,13 @@ static int speech_call(int handle, int k, const uint8_t* text, int64_t text_byte
     const size_t in_bytes = (uintptr_t)so.violations + sizeof(int);
     const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
     if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
-    if (table) {
-        memcpy(r->mirror + (uintptr_t)so.room, table, (size_t)cap * sizeof(int32_t));
-        memcpy(r->mirror + (uintptr_t)po.slot, table + (size_t)cap * sizeof(int32_t), (size_t)cap);
-        const int32_t* room = reinterpret_cast<const int32_t*>(r->mirror + (uintptr_t)so.room);
-        r->rooms = std::count_if(room, room + cap, [](int32_t x) { return x >= 0; });
-        r->resident = false;
-    }
-    const size_t cap_d = r->cap_d;
-    if (grow_dev(&r->d, &r->cap_d, need, "roster device allocation")) return -1;
-    if (r->cap_d != cap_d) r->resident = false;      // this call's upload refills the table from the mirror
+    if (table) new_table(*r, so.room, po.slot, table);
+    if (grow_roster(*r, need)) return -1;
     layout_speak((uintptr_t)r->d, (size_t)text_bytes, clear_bytes, s, p, &d_clear, parsed ? &q : nullptr);
     if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
 
     uint8_t* h = r->mirror;
-    auto put = [&](const void* at, const void* src, size_t bytes) {
-        if (bytes) memcpy(h + (uintptr_t)at, src, bytes);
-    };
+    const Put put{h};
     if (speech) put(so.speech_new, speech, (size_t)cap * kSpeechRec);
     put(so.text, text, (size_t)text_bytes);
     put(parsed ? qo.read_off : so.text_off, text_off, (size_t)k * sizeof(int32_t));
@@ -2580,8 +2538,8 @@ static int speech_call(int handle, int k, const uint8_t* text, int64_t text_byte
     }
     int32_t* coff = reinterpret_cast<int32_t*>(h + (uintptr_t)so.ctext_off);
     for (int b = 0; b < k; b++) {
-        coff[b] = text_off[b] + kSpeakSlack * b;
-        coff[k + b] = (int32_t)text_bytes + kSpeakSlack * k + coff[b];
+        coff[b] = (int32_t)ctext_at(text_off[b], b);
+        coff[k + b] = (int32_t)ctext_at(text_bytes + text_off[b], k + b);
     }
     put(o_clear, clear, clear_bytes);
     *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
@@ -2605,18 +2563,13 @@ static int speech_call(int handle, int k, const uint8_t* text, int64_t text_byte
     ND_CHECK(hipGetLastError());
     hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)(k * p.tiles + k)), dim3(kBlock), 0, st, p);
     ND_CHECK(hipGetLastError());
-    if (record) {                    // on the arrays nuts_roster_speak wrote; the rings are touched by this stream alone
-        RecordArgs rec{s.ctext, s.ctext_off, s.clen, s.rm, s.flags, clear_bytes ? d_clear : nullptr, k,
-                       r->review_rooms, r->rings, reinterpret_cast<int32_t*>(r->rings + revline_at(*r))};
-        hipLaunchKernelGGL(nuts_roster_record, dim3((unsigned)r->review_rooms), dim3(kBlock), 0, st, rec);
-        ND_CHECK(hipGetLastError());
-    }
-    ND_CHECK(hipEventRecord(g.ev1, st));
-    ND_CHECK(hipMemcpyAsync(gm.res, r->d + res_at, res_bytes, hipMemcpyDeviceToHost, st));
-    ND_CHECK(hipStreamSynchronize(st));
+    // on the arrays nuts_roster_speak wrote
+    if (record && launch_record(*r, k, s.ctext, s.ctext_off, s.clen, s.rm, s.flags, clear_bytes ? d_clear : nullptr))
+        return -1;
+    if (fetch_results(r->d, res_at, res_bytes)) return -1;
     const double t1 = now_ns();
 
-    auto res = [&](const void* at) { return gm.res + ((uintptr_t)at - res_at); };
+    const Res res{gm.res, res_at};
     const int violations = *reinterpret_cast<const int*>(res(so.violations));
     if (violations) {
         snprintf(g_err, sizeof(g_err), "%d text(s) exceeded the hard bounds (inpstr + %d bytes composed; 6*len+4 bytes, "
@@ -2641,15 +2594,7 @@ static int speech_call(int handle, int k, const uint8_t* text, int64_t text_byte
     memcpy(ctext, res(so.ctext), ctext_bytes);
     memcpy(var, res(po.var), var_bytes);
 
-    float ms = 0.f;
-    ND_CHECK(hipEventElapsedTime(&ms, g.ev0, g.ev1));
-    if (timing) {
-        timing->kernels_us = (double)ms * 1e3;
-        timing->end_to_end_us = (t1 - t0) * 1e-3;
-        timing->h2d_bytes = (int64_t)(in_bytes - from);
-        timing->d2h_bytes = (int64_t)res_bytes;
-    }
-    return 0;
+    return fill_timing(timing, t0, t1, in_bytes - from, res_bytes);
 }
 
 // K speech events of roster `handle`, as say(), shout(), emote() and semote() answer them.  Event b: the speaker's slot
