@@ -37,6 +37,14 @@ reply ``Unknown command.`` and every other read is void.  Left to the caller: a 
 the user's stored line and resubmit; with none stored the reference answers ``Unknown command.``), AFK users, users away
 over a netlink (rejected, as in ``speak_many``), reads that do not end a line (``get_charclient_line``'s per-user
 buffer), the prompt, and every command that is not speech: COMMAND hands back ``com``, ``inpstr`` and ``word_count``.
+``Roster.tell_many(events)`` answers the private speech commands among those, ``tell()`` and ``pemote()``
+(nuts333.c:4128-4182, 4230-4281), for K ``(slot, com, inpstr, word_count)`` events with ``com`` COM_TELL or COM_PEMOTE:
+``get_user()`` (nuts333.c:2362-2379) runs on the device over every slot's name, lowest slot first, then the muzzle, the
+AFK / ignall / igntell / offsite checks on the target (``Roster.update(afk=, igntell=, afk_mesg=)``), the verb and the two
+composed texts with their plans -- a :class:`Private`.  ``Roster(capacity, revtell=True)`` gives every slot the 5-line
+revtell ring of the talker (nuts333.c:7699-7715): ``tell_many(events, record=True)`` stores each told line in its target's
+ring, ``Roster.revtell_many(slots)`` returns what ``.revtell`` sends for each slot as a :class:`Review`, and
+``Roster.clear_revtell(slots)`` empties rings.
 
 Input is validated before the device is touched (``ValueError``).  The library ``_build/libnuts_device.so`` is built by
 ``__graft_entry__.build()`` where ``hipcc`` exists, and on demand here when it is missing or older than its source.
@@ -66,12 +74,15 @@ LISTENER_FIELDS = ("login", "has_room", "same_room", "ignall", "ignshout", "is_s
 #: NP_NUM_COMMANDS (oracle/nuts_path.h enum np_com)
 NUM_COMMANDS = 92
 COM_SAY, COM_SHOUT, COM_EMOTE, COM_SEMOTE = 3, 4, 6, 7
+#: the private speech commands (NP_TELL, NP_PEMOTE)
+COM_TELL, COM_PEMOTE = 5, 8
 #: the kernels of fanout.hip, as rocprofv3 names them (the scans are rocPRIM's)
 KERNELS = ("nuts_fanout_measure_broadcast", "nuts_fanout_emit_broadcast",
            "nuts_fanout_measure_batch", "nuts_fanout_emit_batch",
            "nuts_fanout_measure_many", "nuts_fanout_emit_many",
            "nuts_roster_measure", "nuts_roster_emit", "nuts_roster_plan", "nuts_roster_record", "nuts_roster_review",
-           "nuts_roster_speak", "nuts_roster_speak_plan", "nuts_roster_parse")
+           "nuts_roster_speak", "nuts_roster_speak_plan", "nuts_roster_parse",
+           "nuts_roster_tell", "nuts_roster_record_tell", "nuts_roster_revtell")
 #: NP_ARR_SIZE (nuts333.h:19): the input line a speech command receives is at most 999 bytes
 ARR_SIZE = 1000
 #: USER_NAME_LEN (nuts333.h:23) and invisname (nuts333.h:150), the name an invisible speaker is shown by
@@ -80,13 +91,26 @@ USER_NAME_LEN, INVISNAME = 12, b"A presence"
 MAX_WORDS = 10
 #: what became of a speech event (Speech.outcome): spoken, or one of the three notices to the speaker alone
 SPOKEN, MUZZLED, NOTHING, SWEARING = 0, 1, 2, 3
+#: what became of a private speech event (Private.outcome): told, MUZZLED, NOTHING, or one of the other notices to the
+#: speaker alone -- nobody of that name, oneself, and the four of private_blocked in its order
+TOLD, NOBODY, SELF, AFK, IGNALL, IGNTELL, OFFSITE = 0, 4, 5, 6, 7, 8, 9
 #: a text composed from ``inpstr`` is at most ``len(inpstr) + COMPOSED_EXTRA`` bytes (pinned by a host test) ...
 COMPOSED_EXTRA = 32
 #: ... and its slot in a speech call's text buffer is ``len(inpstr) + _SPEAK_SLACK`` wide (kSpeakSlack of fanout.hip):
 #: the longest notice, 35 bytes, has to fit beside an empty inpstr
 _SPEAK_SLACK = 36
+#: a private text composed from ``inpstr`` is at most ``len(inpstr) + PRIVATE_EXTRA`` bytes: a pemote reply to and from
+#: 12-byte names over an empty inpstr (strstr finds the empty word in the first name), ``~OL(To `` + 12 + ``)~RS `` + 12 +
+#: `` `` + ``\n`` ...
+PRIVATE_EXTRA = 38
+#: ... and its slot in a private speech call's text buffer is ``len(inpstr) + _TELL_SLACK`` wide (kTellSlack of
+#: fanout.hip): the longest notice, a 12-byte name, `` is AFK, message is: ``, 60 bytes of message and a newline, 94 bytes,
+#: has to fit beside an empty inpstr (both pinned by a host test)
+_TELL_SLACK = 96
+#: AFK_MESG_LEN (nuts333.h:25), and a slot's row in the AFK-message mirror: the message padded with zeros, its length
+AFK_MESG_LEN, _AFK_ROW = 60, 64
 #: the flags byte of a slot's speaker state, as fanout.hip reads it
-SPEECH_FLAGS = {"vis": 1, "muzzled": 2, "command_mode": 4}
+SPEECH_FLAGS = {"vis": 1, "muzzled": 2, "command_mode": 4, "afk": 8, "igntell": 16}
 #: where a slot's speaker state keeps the speaker's level, and the highest one (enum np_level: NEW 0 .. GOD 4)
 _LEVEL_BYTE, MAX_LEVEL = 14, 4
 #: what became of a read (Input.kind): a telnet IAC reply, a line without a word, "." alone, a line exec_com answers
@@ -118,6 +142,11 @@ _REVIEW_STRIDE = (MAX_REVIEW_BYTES + 3) & ~3
 #: is 32 times the rooms the restated talker can hold (MAX_ROOMS of oracle/talker_port.c), so room enough for a
 #: roster that spans many talkers
 MAX_REVIEW_ROOMS = 1024
+#: NP_REVTELL_LINES: a user's revtell ring is 5 such lines; what ``.revtell`` sends of it is at most 6,050 bytes per
+#: variant in 15 writes
+REVTELL_LINES = 5
+MAX_REVTELL_BYTES, MAX_REVTELL_WRITES = REVTELL_LINES * MAX_LINE_BYTES, REVTELL_LINES * MAX_LINE_WRITES
+_REVTELL_STRIDE = (MAX_REVTELL_BYTES + 3) & ~3
 #: bit 2 of a broadcast's flags byte: record it (bit 1 is force_listen)
 _RECORD_BIT = 4
 
@@ -209,11 +238,12 @@ def _variant_starts(text_starts: np.ndarray, sizes: np.ndarray) -> np.ndarray:
     return starts
 
 
-def _composed_at(text_off, t):
+def _composed_at(text_off, t, slack=_SPEAK_SLACK):
     """Where composed text ``t``, whose inpstr starts at ``text_off`` among the call's, has its slot in a speech call's
     text buffer (ctext_at of fanout.hip): room line k is text k, its reply text K + k over the same inpstr once more.
-    ``_composed_at(2 * text bytes, 2 * K)`` is the buffer's size."""
-    return text_off + _SPEAK_SLACK * t
+    ``_composed_at(2 * text bytes, 2 * K)`` is the buffer's size.  A private speech call's slots are ``_TELL_SLACK``
+    wider than inpstr (ptext_at)."""
+    return text_off + slack * t
 
 
 def _unpack(words: np.ndarray, capacity: int) -> np.ndarray:
@@ -301,9 +331,10 @@ class Review(_Variants):
     lines of the room's ring from the cursor onwards, ``chunks(q, c) == chunks(line_0, c) + chunks(line_1, c) + ...``
     (one ``write_user`` per line, so with colour on every line ends in a 4-byte reset write of its own) and
     ``variant(q, c) == b"".join(chunks(q, c))``."""
-    rooms: np.ndarray             # int32 [Q]      the rooms asked for, duplicates included
+    rooms: np.ndarray             # int32 [Q]      the rooms asked for, duplicates included (revtell_many: the slots)
     line_counts: np.ndarray       # int32 [Q]      non-empty lines
     stored: np.ndarray            # uint8 [Q, 15, 202]  the ring's slots, oldest first; a line ends at its first NUL
+    #                               (revtell_many: [Q, 5, 202], and MAX_REVTELL_WRITES chunk sizes per variant)
     variants: np.ndarray          # uint8, flat; gaps between variants are allowed and unspecified
     variant_starts: np.ndarray    # int64 [Q, 2]   variant c of room q is variants[start : start + size]
     variant_sizes: np.ndarray     # int64 [Q, 2]
@@ -356,6 +387,35 @@ class Speech:
 
     def reply_text(self, k: int) -> bytes:
         """What event ``k`` sends to its speaker alone: the echo or the notice; ``b""`` when there is none."""
+        return self._text(1, k)
+
+
+@dataclass
+class Private:
+    """What ``tell()`` and ``pemote()`` write for K private speech events (``Roster.tell_many``), shaped like a
+    :class:`Speech`.  ``outcome[k]`` is TOLD, MUZZLED, NOTHING, NOBODY, SELF, AFK, IGNALL, IGNTELL or OFFSITE;
+    ``target[k]`` the slot ``get_user`` found, or -1 when nobody was found or the lookup was never reached (MUZZLED,
+    NOTHING, a pemote to one's own exact name).  ``told`` plans the line the target gets: ``told.admitted(k)`` is the
+    target's slot alone for a TOLD event, else empty with both variants 0 bytes in 0 writes.  ``reply`` plans what the
+    speaker alone gets, the echo or the notice; it always has a text.  Both are ordinary plans and share one variant
+    buffer.  ``line(k)`` / ``reply_text(k)`` are the composed texts before the transducer."""
+    outcome: np.ndarray           # int8 [K]
+    target: np.ndarray            # int32 [K]
+    told: Plan
+    reply: Plan
+    texts: np.ndarray             # uint8, flat: the composed texts; gaps are allowed and unspecified
+    text_starts: np.ndarray       # int64 [2, K]   row 0 the told lines, row 1 the replies
+    text_sizes: np.ndarray        # int64 [2, K]   -1: there is no such text
+    timing: dict = field(default_factory=dict)   # as Plan's: kernels_us, end_to_end_us, h2d_bytes, d2h_bytes
+
+    _text = Speech._text
+
+    def line(self, k: int) -> bytes:
+        """The line event ``k`` sends to its target; ``b""`` when it was not told."""
+        return self._text(0, k)
+
+    def reply_text(self, k: int) -> bytes:
+        """What event ``k`` sends to its speaker alone: the echo or the notice."""
         return self._text(1, k)
 
 
@@ -574,6 +634,13 @@ def _load():
                                         ctypes.c_int, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
                                         ctypes.POINTER(_RosterTiming)]
         lib.nd_roster_input.restype = ctypes.c_int
+        lib.nd_roster_revtell_rings.argtypes = [ctypes.c_int]
+        lib.nd_roster_revtell_rings.restype = ctypes.c_int
+        lib.nd_roster_revtell.argtypes = lib.nd_roster_review.argtypes
+        lib.nd_roster_revtell.restype = ctypes.c_int
+        lib.nd_roster_tell.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int64, P, P, P, P, P, ctypes.c_int,
+                                       P, P, P, P, P, P, P, P, P, P, P, P, ctypes.POINTER(_RosterTiming)]
+        lib.nd_roster_tell.restype = ctypes.c_int
         lib.nd_arena.restype = P
         lib.nd_write_sizes.restype = P
         _LIB = lib
@@ -704,6 +771,14 @@ def _read_data(v) -> bytes:
     return v
 
 
+def _afk_mesg(v) -> bytes:
+    """``user->afk_mesg``: bytes or str of 0 .. AFK_MESG_LEN bytes, no NUL."""
+    v = _as_bytes("afk_mesg", v)
+    if len(v) > AFK_MESG_LEN or b"\0" in v:
+        raise ValueError(f"afk_mesg must be 0 .. {AFK_MESG_LEN} bytes without a NUL, not {v!r}")
+    return v
+
+
 #: the commands speak_many answers, and whether their room line goes to the speaker's room (and is recorded there)
 _SPEECH_COMS = {COM_SAY: True, COM_SHOUT: False, COM_EMOTE: True, COM_SEMOTE: False}
 
@@ -718,6 +793,10 @@ class Roster:
     and an admit bitmap per broadcast (a :class:`Plan`); they may be mixed in any order.  With ``review_rooms=R`` rooms
     ``0 .. R - 1`` each own a review ring on the device, empty at first: ``plan_many(bs, record=...)`` records into them,
     :meth:`review_many` reads them, :meth:`clear_review` empties them.  ``review_rooms=0`` is a roster without rings.
+    With ``revtell=True`` every slot also owns a revtell ring on the device, 5 lines of 202 bytes and a cursor, empty at
+    first (1,010 bytes per slot in an allocation of its own, 66 MB at MAX_CAPACITY, so it has to be asked for):
+    ``tell_many(events, record=True)`` records into them, :meth:`revtell_many` reads them, :meth:`clear_revtell` empties
+    them.
 
     Building and updating a roster does not touch the device; its first call allocates there.  The
     contract, for every call::
@@ -726,13 +805,19 @@ class Roster:
                                                      for t, rm, s, fl, com in bs])
     """
 
-    def __init__(self, capacity: int, review_rooms: int = 0):
+    def __init__(self, capacity: int, review_rooms: int = 0, revtell: bool = False):
         if not _is_int(capacity, 1, MAX_CAPACITY):
             raise ValueError(f"roster capacity must be an int in [1, {MAX_CAPACITY}], not {capacity!r}")
         if not _is_int(review_rooms, 0, MAX_REVIEW_ROOMS):
             raise ValueError(f"review_rooms must be an int in [0, {MAX_REVIEW_ROOMS}], not {review_rooms!r}")
+        if not isinstance(revtell, (bool, np.bool_)):
+            raise ValueError(f"revtell must be a bool, not {revtell!r}")
         self.capacity = int(capacity)
         self.review_rooms = int(review_rooms)
+        self.revtell = bool(revtell)
+        # slots whose revtell ring clear_revtell() emptied since the last recording tell_many or revtell_many call
+        self._tell_clear = np.zeros(self.capacity if self.revtell else 0, dtype=np.uint8)
+        self._tell_clear_pending = False
         # rooms whose ring clear_review() emptied since the last recording or reviewing call: one byte per ring room
         self._clear = np.zeros(self.review_rooms, dtype=np.uint8)
         self._clear_pending = False
@@ -748,6 +833,13 @@ class Roster:
         self._speech = np.zeros((self.capacity, 16), dtype=np.uint8)
         self._speech[:, USER_NAME_LEN + 1] = SPEECH_FLAGS["vis"]
         self._speech_dirty = True
+        # afk and igntell live in the speaker mirror's flags byte, but only tell_many reads them: an update of theirs
+        # alone makes tell_many upload the speaker mirror, and no other call
+        self._private_dirty = False
+        # the AFK messages' mirror, as nd_roster_tell takes it: 64 bytes per slot -- the message padded with zeros, then
+        # its length at byte AFK_MESG_LEN.  Only tell_many uploads it, after an update of afk_mesg
+        self._afk = np.zeros((self.capacity, _AFK_ROW), dtype=np.uint8)
+        self._afk_dirty = True
         self._handle = None
         self._closed = False
 
@@ -778,7 +870,8 @@ class Roster:
         return int(v)
 
     def update(self, slots, *, room=_KEEP, login=_KEEP, ignall=_KEEP, ignshout=_KEEP, colour=_KEEP, name=_KEEP,
-               vis=_KEEP, muzzled=_KEEP, command_mode=_KEEP, level=_KEEP) -> None:
+               vis=_KEEP, muzzled=_KEEP, command_mode=_KEEP, level=_KEEP, afk=_KEEP, igntell=_KEEP,
+               afk_mesg=_KEEP) -> None:
         """Set fields of ``slots`` (a slot or a sequence of them).  Each field given is one value for every slot or a
         sequence of one per slot; a field not given stays as it is.  ``room`` is None (no room) or an int in
         [0, ROOM_LIMIT); the flags are 0/1 or bools.  A slot given more than once takes its last values.  Nothing
@@ -789,7 +882,13 @@ class Roster:
         their own that only :meth:`speak_many` uploads: an update of these fields alone does not make the next
         ``broadcast_many`` / ``plan_many`` upload the table.  ``level`` (an int in [0, MAX_LEVEL] as enum np_level, 0
         -- NEW -- at first) lives there too: :meth:`input_many` checks a command's minimum level against it, and
-        ``speak_many`` does not read it."""
+        ``speak_many`` does not read it.
+
+        ``afk`` and ``igntell`` (0/1, 0 at first) and ``afk_mesg`` (bytes or str of 0 .. AFK_MESG_LEN bytes, no NUL,
+        empty at first) are what :meth:`tell_many` reads of a **target**: a read that comes from an AFK slot remains
+        the caller's business.  The two flags live in the speaker mirror's flags byte, with a dirty flag of their
+        own; the messages in a mirror of their own.  Only ``tell_many`` uploads after an update of these three alone:
+        no other call copies more for it."""
         self._check_open()
         if isinstance(slots, (int, np.integer)):
             slots = [slots]
@@ -823,8 +922,19 @@ class Roster:
             else:
                 names = [_speaker_name(x) for x in name]
         speech = {f: per_slot(f, v, lambda x, f=f: _flag(f, x), np.uint8)
-                  for f, v in (("vis", vis), ("muzzled", muzzled), ("command_mode", command_mode)) if v is not _KEEP}
+                  for f, v in (("vis", vis), ("muzzled", muzzled), ("command_mode", command_mode), ("afk", afk),
+                               ("igntell", igntell)) if v is not _KEEP}
         levels = None if level is _KEEP else per_slot("level", level, _level, np.uint8)
+        mesgs = None
+        if afk_mesg is not _KEEP:
+            if isinstance(afk_mesg, (str, bytes, bytearray, memoryview)):
+                mesgs = [_afk_mesg(afk_mesg)] * n
+            elif not hasattr(afk_mesg, "__len__"):
+                raise ValueError(f"afk_mesg must be a message or a sequence of one per slot, not {afk_mesg!r}")
+            elif len(afk_mesg) != n:
+                raise ValueError(f"afk_mesg: {len(afk_mesg)} values for {n} slots")
+            else:
+                mesgs = [_afk_mesg(x) for x in afk_mesg]
         _, last = np.unique(idx[::-1], return_index=True)        # each slot's last position: last write wins
         keep = n - 1 - last
         at = idx[keep]
@@ -843,9 +953,17 @@ class Roster:
             col[at] = np.where(v[keep] != 0, col[at] | bit, col[at] & ~bit)
         if levels is not None:
             self._speech[at, _LEVEL_BYTE] = levels[keep]
-        if names is not None or speech or levels is not None:
+        if mesgs is not None:
+            for j, p in zip(at.tolist(), keep.tolist()):
+                self._afk[j] = 0
+                self._afk[j, :len(mesgs[p])] = np.frombuffer(mesgs[p], dtype=np.uint8)
+                self._afk[j, AFK_MESG_LEN] = len(mesgs[p])
+            self._afk_dirty = True
+        if names is not None or levels is not None or speech.keys() - {"afk", "igntell"}:
             self._speech_dirty = True
-        if rooms is not None or flags or not (names is not None or speech or levels is not None):
+        if speech.keys() & {"afk", "igntell"}:
+            self._private_dirty = True
+        if rooms is not None or flags or not (names is not None or speech or levels is not None or mesgs is not None):
             self._dirty = True
 
     def table(self, rm, sender) -> np.ndarray:
@@ -975,7 +1093,8 @@ class Roster:
     def _device_handle(self, lib) -> int:
         if self._handle is None:
             h = _check(lib.nd_roster_create(self.capacity), "cannot create a device roster")
-            if self.review_rooms and lib.nd_roster_review_rooms(h, self.review_rooms) != 0:
+            if ((self.review_rooms and lib.nd_roster_review_rooms(h, self.review_rooms) != 0)
+                    or (self.revtell and lib.nd_roster_revtell_rings(h) != 0)):
                 lib.nd_roster_destroy(h)
                 raise RuntimeError(f"cannot create a device roster: {lib.nd_last_error().decode(errors='replace')}")
             self._handle = h
@@ -1115,6 +1234,7 @@ class Roster:
                                  _ptr(self._speech) if self._speech_dirty else None,
                                  _ptr(clear) if clear is not None else None, *map(_ptr, out), ctypes.byref(t))
         _check(rc, "device speech failed")
+        self._private_dirty &= not self._speech_dirty      # the whole speaker mirror went up, or none of it
         self._dirty = self._speech_dirty = False
         if recording:
             self._clear_sent()
@@ -1225,12 +1345,173 @@ class Roster:
                                  _ptr(clear) if clear is not None else None, _ptr(kind), _ptr(com), _ptr(wcs),
                                  _ptr(line_len), _ptr(inp_off), _ptr(inp_len), *map(_ptr, out), ctypes.byref(t))
         _check(rc, "device input failed")
+        self._private_dirty &= not self._speech_dirty
         self._dirty = self._speech_dirty = False
         if record:
             self._clear_sent()
         speech = self._speech_of(len(data), off, slots, *out, t)
         return Input(kind=kind, com=com, word_count=wcs, line_sizes=line_len, inpstr_starts=inp_off.astype(np.int64),
                      inpstr_sizes=inp_len.astype(np.int64), speech=speech, data=datas, timing=dict(speech.timing))
+
+    def _prepare_private(self, events, record):
+        """Each (slot, com, inpstr, word_count) and its speaker's state checked as _prepare_speech checks them, packed for
+        nd_roster_tell: the inpstr, their offsets and lengths, the slots, commands and word counts, and the flag."""
+        if isinstance(events, (str, bytes, bytearray, np.ndarray)) or not hasattr(events, "__len__"):
+            raise ValueError(f"events must be a sequence of tuples, not {type(events).__name__}")
+        if len(events) == 0:
+            raise ValueError("empty call: no events")
+        record = _flag("record", record)
+        if record and not self.revtell:
+            raise ValueError("record: the roster has no revtell rings (revtell is False)")
+        if len(events) * self.capacity >= 2**31 - 1:
+            raise ValueError(f"{len(events)} events to {self.capacity} slots: K x capacity must be below 2^31 - 1")
+        texts, slots, coms, wcs = [], [], [], []
+        for k, ev in enumerate(events):
+            if not isinstance(ev, tuple) or len(ev) != 4:
+                raise ValueError(f"event {k}: expected a (slot, com, inpstr, word_count) tuple, "
+                                 f"got {type(ev).__name__}{f' of {len(ev)}' if isinstance(ev, tuple) else ''}")
+            slot, com, inpstr, wc = ev
+            try:
+                slot = self._slot(slot)
+                if not _is_int(com, 0, NUM_COMMANDS - 1) or int(com) not in (COM_TELL, COM_PEMOTE):
+                    raise ValueError(f"com must be COM_TELL or COM_PEMOTE ({COM_TELL}, {COM_PEMOTE}), not {com!r}")
+                text = _as_text(inpstr)
+                if len(text) >= ARR_SIZE:
+                    raise ValueError(f"inpstr of {len(text)} bytes: the talker's input line holds at most {ARR_SIZE - 1}")
+                if not _is_int(wc, 0, MAX_WORDS):
+                    raise ValueError(f"word_count must be an int in [0, {MAX_WORDS}], not {wc!r}")
+                self._check_speaker(slot, None)
+            except ValueError as e:
+                raise ValueError(f"event {k}: {e}") from None
+            texts.append(text)
+            slots.append(slot)
+            coms.append(int(com))
+            wcs.append(int(wc))
+        lens = np.fromiter((len(t) for t in texts), dtype=np.int64, count=len(texts))
+        bound = _variant_at(_composed_at(2 * int(lens.sum()), 2 * len(lens), _TELL_SLACK), 2 * len(lens))
+        if bound > MANY_ARENA_CAP:
+            raise ValueError(f"call too large: its variant bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
+                             f"(MANY_ARENA_CAP): split it")
+        return (b"".join(texts), _offsets(lens, np.int32), lens.astype(np.int32), np.array(slots, dtype=np.int32),
+                np.array(coms, dtype=np.uint8), np.array(wcs, dtype=np.uint8), record)
+
+    def tell_many(self, events, record=False) -> Private:
+        """K private speech events in one device call: a non-empty sequence of ``(slot, com, inpstr, word_count)``
+        tuples, what the talker's ``tell()`` and ``pemote()`` receive (nuts333.c:4128-4182, 4230-4281), shaped and
+        checked as :meth:`speak_many` checks them.  ``com`` is COM_TELL or COM_PEMOTE; ``inpstr`` is the line without
+        its first word, ``"bobby hello"`` for ``.tell bobby hello`` and for ``> bobby hello`` -- what a COMMAND read
+        of :meth:`input_many` with ``com`` 5 or 8 hands back.  There is no ``ban_swearing``: the reference does not
+        check tells.  Anything malformed raises ``ValueError("event k: ...")`` before the device is touched.
+
+        The device does, per event and in the reference's order: ``word[1]`` is the first word of ``inpstr`` as
+        ``np_wordfind`` finds it (leading bytes below 33 as signed chars skipped, the run of bytes above 32 cut at 39),
+        its first byte capitalised if it is a-z.  A tell is MUZZLED if the speaker is muzzled, NOTHING if
+        ``word_count < 3``, NOBODY if ``get_user`` finds nobody, SELF if it finds the speaker, then ``private_blocked``,
+        else TOLD.  A pemote is MUZZLED, NOTHING, SELF if the capitalised word equals the speaker's name exactly, NOBODY,
+        ``private_blocked``, else TOLD -- one that reaches the speaker through a substring match goes to the speaker
+        itself, as in the reference.  ``get_user`` runs over the slots in ascending order, skipping those with the
+        ``login`` flag or without a name: the lowest slot whose name equals the word, else the lowest whose name
+        contains it; a slot without a room is found, and answered OFFSITE.  ``private_blocked`` is AFK (with or without
+        the target's message), IGNALL and IGNTELL (the target's flag, and the speaker's level below 2 or below the
+        target's), OFFSITE.  A TOLD event composes the speaker's echo and the target's line from
+        ``np_remove_first(inpstr)``; every other outcome the one notice.  Returns a :class:`Private`; for a TOLD event
+        ``told.chunks(k, c) == plan_many([(private.line(k), None, None, 0, com)]).chunks(0, c)``, and ``reply`` likewise.
+
+        ``record=True`` needs ``Roster(..., revtell=True)`` and stores every TOLD event's line in its target's revtell
+        ring as ``np_record(ring, 5, &revline, line)`` does, in event order within a call and across calls, after the
+        pending :meth:`clear_revtell`; a line of 200 bytes or more is cut with the forced newline.
+
+        One upload (the table, the speaker state and the AFK messages only after an update of theirs), two kernel
+        launches (nuts_roster_tell, nuts_roster_speak_plan) -- three in a call that records (nuts_roster_record_tell)
+        --, one download at the bound size and one synchronise, whatever K and the capacity.  A composed text's slot in
+        the text buffer is ``len(inpstr) + 96`` bytes wide.
+
+        Out of scope: routing inside ``input_many`` (feed its COMMAND reads with ``com`` 5 or 8 here); the "is using
+        the editor" wording of the ignall notice (the roster has no editor state, and oracle/talker_port.c omits it
+        too); remote (``T_REMOTE``) targets and clones; the prompt; ``.afk`` and ``.igntell`` themselves -- the caller
+        updates the fields."""
+        self._check_open()
+        text, text_off, lens, slots, coms, wcs, record = self._prepare_private(events, record)
+        lib = _load()
+        handle = self._device_handle(lib)
+        k, words = len(lens), (self.capacity + 63) // 64
+        ctext_bytes = _composed_at(2 * len(text), 2 * k, _TELL_SLACK)
+        outcome, target = np.empty(k, dtype=np.int8), np.empty(k, dtype=np.int32)
+        clen = np.empty((2, k), dtype=np.int32)
+        vn, vw = np.empty((2, k, 2), dtype=np.int64), np.empty((2, k, 2), dtype=np.int32)
+        vwsz = np.empty((2, k, 2, MAX_WRITES), dtype=np.int32)
+        ctext = np.empty(ctext_bytes, dtype=np.uint8)
+        var = np.empty(_variant_at(ctext_bytes, 2 * k), dtype=np.uint8)
+        tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
+        clear = self._tell_clear.copy() if record and self._tell_clear_pending else None
+        t = _RosterTiming()
+        rc = lib.nd_roster_tell(handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(slots), _ptr(coms),
+                                _ptr(wcs), record, _ptr(self._table) if self._dirty else None,
+                                _ptr(self._speech) if self._speech_dirty or self._private_dirty else None,
+                                _ptr(self._afk) if self._afk_dirty else None,
+                                _ptr(clear) if clear is not None else None, _ptr(outcome), _ptr(target), _ptr(clen),
+                                _ptr(vn), _ptr(vw), _ptr(vwsz), _ptr(ctext), _ptr(var), ctypes.byref(t))
+        _check(rc, "device private speech failed")
+        self._dirty = self._speech_dirty = self._private_dirty = self._afk_dirty = False
+        if record:
+            self._tell_clear_sent()
+        at = text_off.astype(np.int64)
+        tstarts = np.stack([_composed_at(at, np.arange(k), _TELL_SLACK),
+                            _composed_at(len(text) + at, k + np.arange(k), _TELL_SLACK)])
+        starts = _variant_starts(tstarts, clen)
+        bits = np.zeros((2, k, words), dtype=np.uint64)            # the target alone, the speaker alone
+        for row, who in enumerate((target, slots)):
+            has = np.flatnonzero(clen[row] >= 0)
+            bits[row, has, who[has] // 64] = np.uint64(1) << (who[has] % 64).astype(np.uint64)
+        timing = _timing_of(t)
+        colour_bits = _pack((self._flags & ROSTER_FLAGS["colour"]) != 0)
+        plans = [Plan(capacity=self.capacity, admitted_bits=bits[i], colour_bits=colour_bits, variants=var,
+                      variant_starts=starts[i], variant_sizes=vn[i], write_counts=vw[i], write_sizes=vwsz[i],
+                      timing=dict(timing)) for i in (0, 1)]
+        return Private(outcome=outcome, target=target, told=plans[0], reply=plans[1], texts=ctext, text_starts=tstarts,
+                       text_sizes=clen.astype(np.int64), timing=timing)
+
+    def _tell_clear_sent(self) -> None:
+        self._tell_clear[:] = 0
+        self._tell_clear_pending = False
+
+    def _revtell_slots(self, slots, what: str) -> np.ndarray:
+        if not self.revtell:
+            raise ValueError("the roster has no revtell rings (revtell is False)")
+        if isinstance(slots, (str, bytes, bytearray)) or not hasattr(slots, "__len__"):
+            raise ValueError(f"{what} must be a sequence of slots, not {slots!r}")
+        return np.array([self._slot(v) for v in slots], dtype=np.int32)
+
+    def clear_revtell(self, slots) -> None:
+        """Empty the revtell rings of ``slots``, a slot or a sequence of them, for when a slot changes hands: their lines
+        become empty and their cursor 0.  Like :meth:`clear_review` it does not touch the device; it takes effect before
+        the records of the next recording :meth:`tell_many` or the next :meth:`revtell_many`, in the order the caller
+        issued them."""
+        self._check_open()
+        idx = self._revtell_slots([slots] if isinstance(slots, (int, np.integer)) else slots, "slots")
+        if len(idx):
+            self._tell_clear[idx] = 1
+            self._tell_clear_pending = True
+
+    def revtell_many(self, slots) -> Review:
+        """What ``.revtell`` sends for each of ``slots`` between its header and its footer (nuts333.c:7699-7715), a
+        non-empty sequence of slots (duplicates allowed), as a :class:`Review` whose ``rooms`` are the slots, ``stored``
+        is ``[Q, 5, 202]`` and whose variants are bounded by MAX_REVTELL_BYTES in MAX_REVTELL_WRITES writes.  One upload,
+        one kernel (nuts_roster_revtell), one download, one synchronise.  Anything else raises ``ValueError`` before the
+        device is touched."""
+        self._check_open()
+        idx = self._revtell_slots(slots, "slots")
+        q = len(idx)
+        if q == 0:
+            raise ValueError("empty call: no slots to review")
+        if 2 * q * _REVTELL_STRIDE > MANY_ARENA_CAP:
+            raise ValueError(f"call too large: {q} slots x 2 x {_REVTELL_STRIDE} bytes exceed the cap of {MANY_ARENA_CAP} "
+                             f"(MANY_ARENA_CAP): split it")
+        lib = _load()
+        clear = self._tell_clear.copy() if self._tell_clear_pending else None
+        review = self._review_of(lib.nd_roster_revtell, self._device_handle(lib), idx, clear, REVTELL_LINES)
+        self._tell_clear_sent()
+        return review
 
     def _ring_room(self, v) -> int:
         if not _is_int(v, 0, self.review_rooms - 1):
@@ -1266,21 +1547,25 @@ class Roster:
             raise ValueError(f"call too large: {q} rooms x 2 x {_REVIEW_STRIDE} bytes exceed the cap of {MANY_ARENA_CAP} "
                              f"(MANY_ARENA_CAP): split it")
         lib = _load()
-        handle = self._device_handle(lib)
+        review = self._review_of(lib.nd_roster_review, self._device_handle(lib), idx, self._pending_clear(), REVIEW_LINES)
+        self._clear_sent()
+        return review
+
+    def _review_of(self, call, handle, idx, clear, lines: int) -> Review:
+        """The Review of rings ``idx`` of ``lines`` lines each, through nd_roster_review or nd_roster_revtell."""
+        q, stride, writes = len(idx), (lines * MAX_LINE_BYTES + 3) & ~3, lines * MAX_LINE_WRITES
         counts = np.empty(q, dtype=np.int32)
         seq = np.empty(q, dtype=np.int32)
         vn = np.empty((q, 2), dtype=np.int32)
         vw = np.empty((q, 2), dtype=np.int32)
-        vwsz = np.empty((q, 2, MAX_REVIEW_WRITES), dtype=np.int32)
-        stored = np.empty((q, REVIEW_LINES, REVIEW_LEN + 2), dtype=np.uint8)
-        var = np.empty(2 * q * _REVIEW_STRIDE, dtype=np.uint8)
-        clear = self._pending_clear()
+        vwsz = np.empty((q, 2, writes), dtype=np.int32)
+        stored = np.empty((q, lines, REVIEW_LEN + 2), dtype=np.uint8)
+        var = np.empty(2 * q * stride, dtype=np.uint8)
         t = _RosterTiming()
-        rc = lib.nd_roster_review(handle, q, _ptr(idx), _ptr(clear) if clear is not None else None, _ptr(counts),
-                                  _ptr(seq), _ptr(vn), _ptr(vw), _ptr(vwsz), _ptr(stored), _ptr(var), ctypes.byref(t))
+        rc = call(handle, q, _ptr(idx), _ptr(clear) if clear is not None else None, _ptr(counts), _ptr(seq), _ptr(vn),
+                  _ptr(vw), _ptr(vwsz), _ptr(stored), _ptr(var), ctypes.byref(t))
         _check(rc, "device review failed")
-        self._clear_sent()
-        starts = (np.arange(2 * q, dtype=np.int64) * _REVIEW_STRIDE).reshape(q, 2)
+        starts = (np.arange(2 * q, dtype=np.int64) * stride).reshape(q, 2)
         return Review(rooms=idx, line_counts=counts, stored=stored, variants=var, variant_starts=starts,
                       variant_sizes=vn.astype(np.int64), write_counts=vw, write_sizes=vwsz, sequential=seq,
                       timing=_timing_of(t))

@@ -23,7 +23,9 @@
 // rooms, one wave per (line, colour variant), parallel over the line's bytes (their section below).
 // And it can keep what the speech commands read of a speaker: nuts_roster_speak composes what say(), shout(), emote() and
 // semote() write for K (user, command, inpstr, word_count) events, a wave per event, and nuts_roster_speak_plan plans the
-// composed texts as nuts_roster_plan would (their section below).
+// composed texts as nuts_roster_plan would (their section below).  nuts_roster_parse frames and dispatches client reads in
+// front of them, and nuts_roster_tell answers the private speech commands, tell() and pemote(), a block per event with
+// get_user() parallel over the roster's slots; the slots' revtell rings are roster_record / roster_review at 5 lines.
 //
 // Hard bounds per item of a text of len < 2000 bytes: 6*len + 4 output bytes (a '\n' with colour
 // on is the costliest input byte, plus the trailing reset) and 16 writes.  The host sizes its buffers
@@ -685,7 +687,9 @@ constexpr int kRevLineCap = 6 * (kRevLen + 1) + 4;         // 1210: 201 newlines
 constexpr int kRevLineStride = (kRevLineCap + 1 + 3) & ~3;   // a line's output in LDS, and a spare byte after it
 constexpr int kRevLineWrites = 3;                          // 996 + 210 + 4 for that line
 constexpr int kRevVarCap = kRevLines * kRevLineCap;        // 18150 bytes per variant
-constexpr int kRevVarStride = (kRevVarCap + 3) & ~3;
+constexpr int rev_var_stride(int lines) { return (lines * kRevLineCap + 3) & ~3; }   // a variant's slot in the download
+constexpr int kRevVarStride = rev_var_stride(kRevLines);
+constexpr int kTellLines = 5;                              // nuts333.h: REVTELL_LINES, a user's revtell ring
 constexpr int kRevWrites = kRevLines * kRevLineWrites;     // 45 writes per variant
 constexpr int kRevTasks = 2 * kRevLines;                   // (line, variant) pairs of a room
 constexpr int kWaveLimit = kOutBuff - 6;                   // a line output up to here never flushes in mid-line
@@ -704,9 +708,12 @@ struct RecordArgs {
     int32_t* revline;            // [review_rooms]
 };
 
+// LINES: the lines of a ring -- kRevLines for a room's review ring, kTellLines for a slot's revtell ring, whose "rooms" are
+// the roster's slots (RecordArgs.rm the tells' targets, review_rooms the capacity).
+template <int LINES>
 __device__ void roster_record(const RecordArgs& a)
 {
-    __shared__ int s_surv[kRevLines];   // the broadcast of rank r, at r % 15, for the last 15 ranks
+    __shared__ int s_surv[LINES];   // the broadcast of rank r, at r % LINES, for the last LINES ranks
     __shared__ int s_count, s_base;
     const int room = (int)blockIdx.x;
     const bool cleared = a.clear && a.clear[room];
@@ -719,28 +726,28 @@ __device__ void roster_record(const RecordArgs& a)
             const uint64_t word = __ballot(hit);
             const int n = __popcll(word);
             const int rank = count + __popcll(word & ((1ull << lane) - 1));
-            // the last 15 of this tile are distinct mod 15; a later tile's stores follow these in program order
-            if (hit && rank >= count + n - kRevLines) s_surv[rank % kRevLines] = b;
+            // the last LINES of this tile are distinct mod LINES; a later tile's stores follow these in program order
+            if (hit && rank >= count + n - LINES) s_surv[rank % LINES] = b;
             count += n;
         }
         if (lane == 0) {
             s_count = count;
-            s_base = cleared ? 0 : (int)((uint32_t)a.revline[room] % kRevLines);   // read by the thread that stores it
+            s_base = cleared ? 0 : (int)((uint32_t)a.revline[room] % LINES);   // read by the thread that stores it
         }
     }
     __syncthreads();
     const int count = s_count, base = s_base;
     if (!count && !cleared) return;
-    uint8_t* ring = a.rings + (size_t)room * kRevRing;
-    const int nsurv = count < kRevLines ? count : kRevLines;
-    const int first = (count - nsurv) % kRevLines;      // rank of the oldest survivor, mod 15
-    if (cleared && threadIdx.x < kRevLines) {           // empty the slots no survivor lands in
-        const int d = ((int)threadIdx.x - base - first + 2 * kRevLines) % kRevLines;
+    uint8_t* ring = a.rings + (size_t)room * LINES * kRevSlot;
+    const int nsurv = count < LINES ? count : LINES;
+    const int first = (count - nsurv) % LINES;      // rank of the oldest survivor, mod LINES
+    if (cleared && threadIdx.x < LINES) {           // empty the slots no survivor lands in
+        const int d = ((int)threadIdx.x - base - first + 2 * LINES) % LINES;
         if (d >= nsurv) ring[threadIdx.x * kRevSlot] = 0;
     }
     for (int idx = (int)threadIdx.x; idx < nsurv * kRevSlot; idx += kBlock) {
         const int j = idx / kRevSlot, i = idx - j * kRevSlot;
-        const int r = (first + j) % kRevLines;
+        const int r = (first + j) % LINES;
         const int b = s_surv[r];
         uint8_t v = 0;
         if (i < kRevLen) {
@@ -748,9 +755,9 @@ __device__ void roster_record(const RecordArgs& a)
         } else if (i == kRevLen) {
             v = '\n';
         }
-        ring[((base + r) % kRevLines) * kRevSlot + i] = v;
+        ring[((base + r) % LINES) * kRevSlot + i] = v;
     }
-    if (threadIdx.x == 0) a.revline[room] = (base + count % kRevLines) % kRevLines;
+    if (threadIdx.x == 0) a.revline[room] = (base + count % LINES) % LINES;
 }
 
 struct ReviewArgs {
@@ -799,36 +806,41 @@ __device__ __forceinline__ int expand_byte(uint8_t p1, uint8_t ch, uint8_t n1, b
     return 1;
 }
 
+// LINES as roster_record's: the outputs are then LINES * kRevSlot stored bytes, rev_var_stride(LINES) bytes per variant and
+// LINES * kRevLineWrites chunk sizes per variant.
+template <int LINES>
 __device__ void roster_review(const ReviewArgs& a)
 {
+    constexpr int TASKS = 2 * LINES;                      // (line, variant) pairs of a ring
+    constexpr int RING = LINES * kRevSlot, WRITES = LINES * kRevLineWrites;
     if ((int)blockIdx.x >= a.q) {       // the blocks past the requested rooms store the pending clears, a room per lane
         const int room = ((int)blockIdx.x - a.q) * kBlock + (int)threadIdx.x;
         if (a.clear && room < a.review_rooms && a.clear[room]) {
-            for (int i = 0; i < kRevLines; i++) a.rings[(size_t)room * kRevRing + i * kRevSlot] = 0;
+            for (int i = 0; i < LINES; i++) a.rings[(size_t)room * RING + i * kRevSlot] = 0;
             a.revline[room] = 0;
         }
         return;
     }
-    __shared__ uint8_t s_line[kRevLines][kRevSlot + 2];       // the ring, oldest line first
-    __shared__ uint8_t s_out[kRevTasks][kRevLineStride];      // task 2 * line + colour: its output
-    __shared__ int32_t s_wsz[kRevTasks][kRevLineWrites + 1];  // its chunk sizes
-    __shared__ int s_n[kRevTasks], s_w[kRevTasks], s_off[kRevTasks], s_woff[kRevTasks];
-    __shared__ int s_len[kRevLines], s_seq;
+    __shared__ uint8_t s_line[LINES][kRevSlot + 2];       // the ring, oldest line first
+    __shared__ uint8_t s_out[TASKS][kRevLineStride];      // task 2 * line + colour: its output
+    __shared__ int32_t s_wsz[TASKS][kRevLineWrites + 1];  // its chunk sizes
+    __shared__ int s_n[TASKS], s_w[TASKS], s_off[TASKS], s_woff[TASKS];
+    __shared__ int s_len[LINES], s_seq;
     const int q = (int)blockIdx.x, room = a.rooms[q];
     const bool cleared = a.clear && a.clear[room];   // then the ring is not read: other blocks are storing its zeros
-    const int rev = cleared ? 0 : (int)((uint32_t)a.revline[room] % kRevLines);
-    const uint8_t* ring = a.rings + (size_t)room * kRevRing;
-    for (int idx = (int)threadIdx.x; idx < kRevRing; idx += kBlock) {
+    const int rev = cleared ? 0 : (int)((uint32_t)a.revline[room] % LINES);
+    const uint8_t* ring = a.rings + (size_t)room * RING;
+    for (int idx = (int)threadIdx.x; idx < RING; idx += kBlock) {
         const int i = idx / kRevSlot, j = idx - i * kRevSlot;
-        const uint8_t v = cleared ? 0 : ring[((rev + i) % kRevLines) * kRevSlot + j];
+        const uint8_t v = cleared ? 0 : ring[((rev + i) % LINES) * kRevSlot + j];
         s_line[i][j] = v;
-        a.lines[(size_t)q * kRevRing + idx] = v;
+        a.lines[(size_t)q * RING + idx] = v;
     }
     if (threadIdx.x == 0) s_seq = 0;
     __syncthreads();
 
     const int lane = (int)threadIdx.x & 63;
-    for (int t = (int)threadIdx.x >> 6; t < kRevTasks; t += kBlock / 64) {     // wave-uniform
+    for (int t = (int)threadIdx.x >> 6; t < TASKS; t += kBlock / 64) {     // wave-uniform
         const int i = t >> 1;
         const bool colour = (t & 1) != 0;
         const uint8_t* s = s_line[i];
@@ -908,7 +920,7 @@ __device__ void roster_review(const ReviewArgs& a)
         if (lane == 0 && !colour) s_len[i] = len;
     }
     __syncthreads();
-    if (threadIdx.x < kRevTasks && s_n[threadIdx.x] < 0) {   // the sequential transducer knows the flush rule; a lane each
+    if (threadIdx.x < TASKS && s_n[threadIdx.x] < 0) {   // the sequential transducer knows the flush rule; a lane each
         const int t = (int)threadIdx.x;
         Sink<true> k{s_out[t], s_wsz[t], kRevLineCap, kRevLineWrites};
         transduce(s_line[t >> 1], s_len[t >> 1], (t & 1) != 0, k);
@@ -918,7 +930,7 @@ __device__ void roster_review(const ReviewArgs& a)
         atomicAdd(&s_seq, 1);
     }
     __syncthreads();
-    if (threadIdx.x < kRevTasks) {      // each task's place in its variant: after the earlier lines' outputs
+    if (threadIdx.x < TASKS) {      // each task's place in its variant: after the earlier lines' outputs
         const int t = (int)threadIdx.x;
         int off = 0, woff = 0;
         for (int j = t & 1; j < t; j += 2) {
@@ -927,28 +939,29 @@ __device__ void roster_review(const ReviewArgs& a)
         }
         s_off[t] = off;
         s_woff[t] = woff;
-        if (t >= kRevTasks - 2) {
+        if (t >= TASKS - 2) {
             a.vn[2 * q + (t & 1)] = off + s_n[t];
             a.vw[2 * q + (t & 1)] = woff + s_w[t];
         }
     }
     if (threadIdx.x == 64) {
         int lines = 0;
-        for (int i = 0; i < kRevLines; i++) lines += s_len[i] > 0;
+        for (int i = 0; i < LINES; i++) lines += s_len[i] > 0;
         a.line_count[q] = lines;
         a.sequential[q] = s_seq;
     }
     __syncthreads();
-    for (int t = 0; t < kRevTasks; t++) {
+    for (int t = 0; t < TASKS; t++) {
         const int var = 2 * q + (t & 1);
-        uint8_t* dst = a.var + (size_t)var * kRevVarStride + s_off[t];
+        uint8_t* dst = a.var + (size_t)var * rev_var_stride(LINES) + s_off[t];
         for (int j = (int)threadIdx.x; j < s_n[t]; j += kBlock) dst[j] = s_out[t][j];
-        if ((int)threadIdx.x < s_w[t]) a.vwsz[var * kRevWrites + s_woff[t] + (int)threadIdx.x] = s_wsz[t][threadIdx.x];
+        if ((int)threadIdx.x < s_w[t]) a.vwsz[var * WRITES + s_woff[t] + (int)threadIdx.x] = s_wsz[t][threadIdx.x];
     }
 }
 
 static_assert(kBlock / 64 >= 1 && 64 * 4 >= kRevSlot, "roster_review: a wave holds a whole slot, four bytes per lane");
 static_assert(kBlock >= kRevTasks + 64 && kBlock >= kRevLines, "roster_review / roster_record: a lane per task, per line");
+static_assert(kTellLines <= kRevLines && kRevVarStride == ((kRevVarCap + 3) & ~3), "the revtell ring is the smaller instance");
 
 // ------------------------------------------------------------------ speech commands of a resident roster
 //
@@ -1427,6 +1440,249 @@ __device__ void roster_parse(const ParseArgs& a)
 static_assert(64 * kReadSlice >= kArrSize + 1, "roster_parse: the 64 slices cover the longest read and a byte past it");
 static_assert(kNumCommands <= 128 && kLevelByte < kSpeechRec, "roster_parse: two table entries per lane; the level's byte");
 
+// ------------------------------------------------------------------ private speech of a resident roster
+//
+// tell() and pemote() (nuts333.c:4128-4182, 4230-4281; tell / pemote / private_blocked of oracle/talker_port.c) turn (user,
+// command, inpstr, word_count) into a notice to the speaker, or into the speaker's echo and the line one other user gets:
+// the one get_user() finds (nuts333.c:2362-2379), by an exact-name pass and then a substring pass over the user list, here
+// the slots in ascending order.  A slot's speaker state carries two more flags for it, afk and igntell (bits 8 and 16 of
+// the flags byte), and a third table kept like the speaker state holds every slot's AFK message: 64 bytes per slot, 60 of
+// message padded with zeros, then its length.
+//   tell     nuts_roster_tell, ONE BLOCK PER EVENT, because the lookup is the work: it reads every slot once, and a block
+//            has four waves to spread the slots over where a wave per event would walk them alone.  Per event that is
+//            `capacity` 16-byte speaker records and `capacity` flag bytes (login lives in the table's flags byte): 1000
+//            and 1000 at capacity 1000 in 4 steps of the block (16 of a single wave), 65536 and 65536 at capacity 65536 in
+//            256 steps (1024).  A slot's room is read for the slot that was found alone: get_user does not look at it.
+//            An event that never reaches get_user (muzzled, too few words, a pemote to one's own exact name) reads none.
+//            word[1] is found as nuts_roster_parse finds words (16 bytes of inpstr per lane, first_from), by every wave
+//            for itself; its first 12 bytes are packed as a name is, the first one capitalised.  Lane l of wave w tests
+//            slot 256 i + 64 w + l in step i: the name equals the word (same length, same bytes), or holds it at one of
+//            the 13 - length offsets.  Two ballots per step; the first set bit of the first non-empty ballot is the wave's
+//            lowest match, a wave that has an exact match stops (a substring match no longer matters), and the four
+//            waves' two minima meet in LDS.  No atomics: the same answer on every run.
+//            Wave 0 then decides the outcome in the reference's order and composes both texts with compose(), told line k
+//            in slot k and its reply in slot K + k of the composed-text buffer, each in_len + kTellSlack bytes wide (a
+//            composed text is at most in_len + 38 bytes, the AFK notice up to 94 whatever inpstr holds).  Lane 0 stores
+//            the lengths, the outcome, the target, and for nuts_roster_record_tell the ring (the target of a told event,
+//            else -1) and the record bit.  Blocks past the events copy an uploaded speaker or AFK-message table into the
+//            kept allocation, as nuts_roster_speak's do.
+//   plan     both texts need variants only: nuts_roster_speak_plan with no room lines (k = 0), a block per text.
+//   record   nuts_roster_record_tell is roster_record<5> over the slots' revtell rings, a block per slot, each scanning the
+//            call's K (record bit, target) pairs; nuts_roster_revtell is roster_review<5>.
+constexpr int kTellSlack = 96;                             // a composed private text's slot is this much wider than inpstr
+constexpr int kAfkRec = 64, kAfkMesgLen = 60;              // a slot's AFK message row; nuts333.h:25 AFK_MESG_LEN
+constexpr uint8_t kAfk = 8, kIgntell = 16;                 // more bits of the flags byte of a slot's speaker state
+constexpr int kTold = 0, kOutNobody = 4, kOutSelf = 5, kOutAfk = 6, kOutIgnall = 7, kOutIgntell = 8, kOutOffsite = 9;
+constexpr int kNoMatch = 0x7fffffff;
+
+constexpr int64_t ptext_at(int64_t text_off, int64_t t) { return text_off + kTellSlack * t; }   // ctext_at, for these texts
+
+struct TellArgs {
+    const int32_t* room;         // [capacity] the roster's table: -1, no room
+    const uint8_t* slotf;        // [capacity] and its flags byte: kLogin, kIgnall
+    const uint8_t* speech;       // [capacity * 16] the speaker state this call reads: the upload, or the kept table
+    const uint8_t* speech_new;   // the upload when there is one, to be copied to speech_keep; else nullptr
+    uint8_t* speech_keep;
+    const uint8_t* afk;          // [capacity * 64] the AFK messages, likewise
+    const uint8_t* afk_new;
+    uint8_t* afk_keep;
+    const uint8_t* text;         // the K inpstr, packed
+    const int32_t* text_off;     // [k]
+    const int32_t* text_len;     // [k]
+    const int32_t* slot;         // [k] the speaker
+    const uint8_t* com;          // [k] NP_TELL or NP_PEMOTE
+    const uint8_t* words;        // [k] word_count
+    const int32_t* ctext_off;    // [2k] where each composed text's slot starts in ctext
+    int k, capacity, record;
+    int* violations;             // composed texts past their slot (zeroed by the host's upload)
+    uint8_t* ctext;              // the composed texts
+    int32_t* clen;               // [2k] their lengths; -1: no such text
+    int8_t* outcome;             // [k]
+    int32_t* target;             // [k] the slot get_user found; -1: none, or it was not asked
+    int32_t* ring;               // [k] RecordArgs.rm of nuts_roster_record_tell: the target of a told event, else -1
+    uint8_t* flags;              // [k] bit 2: record the told line
+};
+
+// Does a name (its 12 bytes in lo and hi, padded with zeros, nlen of them used) equal the word (its wlen <= 12 bytes packed
+// alike, none of them zero), and does it contain it?  The padding is zero, so a match never runs past the name's end.
+__device__ __forceinline__ void name_match(uint64_t lo, uint32_t hi, int nlen, uint64_t wlo, uint32_t whi, int wlen,
+                                           bool* exact, bool* sub)
+{
+    const uint64_t mlo = wlen >= 8 ? ~0ull : (1ull << (8 * wlen)) - 1;
+    const uint32_t mhi = wlen <= 8 ? 0u : wlen >= 12 ? ~0u : (1u << (8 * (wlen - 8))) - 1u;
+    bool any = false;
+#pragma unroll
+    for (int o = 0; o <= kNameLen; o++) {                  // the name from its byte o on
+        const uint64_t slo = o == 0 ? lo : o < 8 ? lo >> (8 * o) | (uint64_t)hi << (64 - 8 * o) : o < 12 ? (uint64_t)(hi >> (8 * (o - 8))) : 0;
+        const uint32_t shi = o == 0 ? hi : o < 4 ? hi >> (8 * o) : 0u;
+        const bool hit = o + wlen <= nlen && (slo & mlo) == wlo && (shi & mhi) == whi;
+        if (o == 0) *exact = hit && wlen == nlen;
+        any |= hit;
+    }
+    *sub = any;
+}
+
+__device__ void roster_tell(const TellArgs& a)
+{
+    if ((int)blockIdx.x >= a.k) {           // the tables just uploaded, into the kept allocations: a word per lane
+        const int sw = a.speech_new ? a.capacity * (kSpeechRec / 4) : 0, aw = a.afk_new ? a.capacity * (kAfkRec / 4) : 0;
+        const int w = ((int)blockIdx.x - a.k) * kBlock + (int)threadIdx.x;
+        if (w < sw) reinterpret_cast<uint32_t*>(a.speech_keep)[w] = reinterpret_cast<const uint32_t*>(a.speech_new)[w];
+        else if (w - sw < aw) reinterpret_cast<uint32_t*>(a.afk_keep)[w - sw] = reinterpret_cast<const uint32_t*>(a.afk_new)[w - sw];
+        return;
+    }
+    __shared__ int s_exact[kBlock / 64], s_sub[kBlock / 64];
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int k = (int)blockIdx.x;
+    const int slot = a.slot[k], wc = a.words[k], len = a.text_len[k];
+    const bool pemote = a.com[k] == kComPemote;
+    const uint8_t* in = a.text + a.text_off[k];
+    const uint8_t* sp = a.speech + (size_t)slot * kSpeechRec;
+    const uint8_t state = sp[kNameLen + 1];
+    const int nlen = sp[kNameLen] < kNameLen ? sp[kNameLen] : kNameLen;
+
+    // word[1] as np_wordfind finds the line's second word, and where np_remove_first leaves inpstr (c:417-432, 2350-2358)
+    uint32_t wordb = 0;
+#pragma unroll
+    for (int x = 0; x < kReadSlice; x++) {
+        const int at = kReadSlice * lane + x;
+        wordb |= (uint32_t)(at < len && (int8_t)in[at] > 32) << x;
+    }
+    const int w0 = first_from(wordb, 0, lane, len);
+    const int w0_end = first_from(~wordb & 0xffffu, w0, lane, len);                // <= len: the byte at len is no word byte
+    const int rest = first_from(wordb, w0_end, lane, len);
+    const int wlen = w0_end - w0 < kWordLen ? w0_end - w0 : kWordLen;
+    uint64_t wlo = 0;
+    uint32_t whi = 0;
+#pragma unroll
+    for (int i = 0; i < kNameLen; i++) {
+        uint64_t c = i < wlen ? in[w0 + i] : 0;
+        if (i == 0 && c >= 'a' && c <= 'z') c -= 32;                               // get_user c:2366, pemote c:4243
+        if (i < 8) wlo |= c << (8 * i);
+        else whi |= (uint32_t)c << (8 * (i - 8));
+    }
+
+    // what comes before get_user, in the reference's order (tell c:4133-4140, pemote c:4235-4247); block-uniform
+    int outcome = kTold;
+    if (state & kMuzzled) outcome = kOutMuzzled;
+    else if (wc < 3) outcome = kOutNothing;
+    else if (pemote && wlen == nlen) {
+        const uint32_t* n = reinterpret_cast<const uint32_t*>(sp);
+        bool exact, sub;
+        name_match(n[0] | (uint64_t)n[1] << 32, n[2], nlen, wlo, whi, wlen, &exact, &sub);
+        if (exact) outcome = kOutSelf;
+    }
+
+    // get_user: this wave's lowest exact match and lowest substring match among its slots, 64 w + 256 i + lane
+    int best_exact = kNoMatch, best_sub = kNoMatch;
+    if (outcome == kTold && wlen <= kNameLen) {
+        for (int base = 64 * wave; base < a.capacity; base += kBlock) {            // wave-uniform
+            const int j = base + lane;
+            bool exact = false, sub = false;
+            if (j < a.capacity && !(a.slotf[j] & kLogin)) {
+                const uint4 rec = reinterpret_cast<const uint4*>(a.speech)[j];
+                const int jl = (int)(rec.w & 0xff) < kNameLen ? (int)(rec.w & 0xff) : kNameLen;
+                if (jl > 0) name_match(rec.x | (uint64_t)rec.y << 32, rec.z, jl, wlo, whi, wlen, &exact, &sub);
+            }
+            const uint64_t be = __ballot(exact);
+            if (be) {
+                best_exact = base + __ffsll((unsigned long long)be) - 1;
+                break;                      // a substring match no longer matters
+            }
+            const uint64_t bs = __ballot(sub);
+            if (bs && best_sub == kNoMatch) best_sub = base + __ffsll((unsigned long long)bs) - 1;
+        }
+    }
+    if (lane == 0) {
+        s_exact[wave] = best_exact;
+        s_sub[wave] = best_sub;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    for (int w = 0; w < kBlock / 64; w++) {
+        best_exact = s_exact[w] < best_exact ? s_exact[w] : best_exact;
+        best_sub = s_sub[w] < best_sub ? s_sub[w] : best_sub;
+    }
+    int target = -1;
+    const uint8_t* tp = sp;                 // the target's speaker state
+    if (outcome == kTold) {
+        target = best_exact != kNoMatch ? best_exact : best_sub != kNoMatch ? best_sub : -1;
+        if (target < 0) {
+            outcome = kOutNobody;
+        } else if (!pemote && target == slot) {
+            outcome = kOutSelf;
+        } else {                            // private_blocked, c:4149-4172 / 4251-4273
+            tp = a.speech + (size_t)target * kSpeechRec;
+            const int mine = sp[kLevelByte], theirs = tp[kLevelByte];
+            const bool deaf = mine < kWiz || theirs > mine;
+            if (tp[kNameLen + 1] & kAfk) outcome = kOutAfk;
+            else if ((a.slotf[target] & kIgnall) && deaf) outcome = kOutIgnall;
+            else if ((tp[kNameLen + 1] & kIgntell) && deaf) outcome = kOutIgntell;
+            else if (a.room[target] < 0) outcome = kOutOffsite;
+        }
+    }
+
+    uint8_t* line = a.ctext + a.ctext_off[k];
+    uint8_t* reply = a.ctext + a.ctext_off[a.k + k];
+    const int cap = len + kTellSlack;
+    const Piece none{nullptr, 0};
+    const Piece tname{tp, tp[kNameLen] < kNameLen ? tp[kNameLen] : kNameLen};
+    int line_len = -1, reply_len = -1;
+    if (outcome == kTold) {
+        const Piece shown = (state & kVis) ? Piece{sp, nlen} : lit("A presence");
+        const uint8_t* body = in + rest;
+        const int blen = len - rest;
+        if (pemote) {                       // c:4275-4279
+            const Piece r[5] = {lit("~OL(To "), tname, lit(")~RS "), shown, lit(" ")};
+            const Piece l[5] = {lit("~OL>>~RS "), shown, lit(" "), none, none};
+            reply_len = compose(reply, cap, r, body, blen, true, lane, a.violations);
+            line_len = compose(line, cap, l, body, blen, true, lane, a.violations);
+        } else {                            // c:4174-4180
+            const Piece verb = blen > 0 && body[blen - 1] == '?' ? lit("ask") : lit("tell");
+            const Piece r[5] = {lit("~OLYou "), verb, lit(" "), tname, lit(":~RS ")};
+            const Piece l[5] = {lit("~OL"), shown, lit(" "), verb, lit("s you:~RS ")};
+            reply_len = compose(reply, cap, r, body, blen, true, lane, a.violations);
+            line_len = compose(line, cap, l, body, blen, true, lane, a.violations);
+        }
+        if (line_len < 0 || reply_len < 0) line_len = reply_len = -1;              // a violation: the call fails
+    } else if (outcome == kOutAfk) {
+        const uint8_t* mesg = a.afk + (size_t)target * kAfkRec;
+        const int mlen = mesg[kAfkMesgLen] < kAfkMesgLen ? mesg[kAfkMesgLen] : kAfkMesgLen;
+        const Piece p[5] = {tname, mlen ? lit(" is AFK, message is: ") : lit(" is AFK at the moment."), none, none, none};
+        reply_len = compose(reply, cap, p, mesg, mlen, true, lane, a.violations);
+    } else if (outcome == kOutIgnall) {
+        const Piece p[5] = {tname, lit(" is ignoring everyone at the moment.\n"), none, none, none};
+        reply_len = compose(reply, cap, p, nullptr, 0, false, lane, a.violations);
+    } else if (outcome == kOutIgntell) {
+        const Piece p[5] = {tname, lit(" is ignoring "), pemote ? lit("private emotes") : lit("tells"), lit(" at the moment.\n"), none};
+        reply_len = compose(reply, cap, p, nullptr, 0, false, lane, a.violations);
+    } else if (outcome == kOutOffsite) {
+        const Piece p[5] = {tname, lit(" is offsite and would not be able to reply to you.\n"), none, none, none};
+        reply_len = compose(reply, cap, p, nullptr, 0, false, lane, a.violations);
+    } else {
+        const Piece p[5] = {outcome == kOutMuzzled ? (pemote ? lit("You are muzzled, you cannot emote.\n")
+                                                             : lit("You are muzzled, you cannot tell anyone anything.\n"))
+                            : outcome == kOutNothing ? (pemote ? lit("Private emote what?\n") : lit("Tell who what?\n"))
+                            : outcome == kOutNobody ? lit("There is no one of that name logged on.\n")
+                            : pemote ? lit("Emoting to yourself is the second sign of madness.\n")
+                                     : lit("Talking to yourself is the first sign of madness.\n"), none, none, none, none};
+        reply_len = compose(reply, cap, p, nullptr, 0, false, lane, a.violations);
+    }
+    if (lane == 0) {
+        const bool told = line_len >= 0;
+        a.clen[k] = line_len;
+        a.clen[a.k + k] = reply_len;
+        a.outcome[k] = (int8_t)outcome;
+        a.target[k] = target;
+        a.ring[k] = told ? target : -1;
+        a.flags[k] = told && a.record ? kRecordBit : 0;
+    }
+}
+
+static_assert(kAfkRec % 4 == 0 && kAfkMesgLen < kAfkRec, "roster_tell: an AFK message row is whole words and holds its length");
+static_assert(kArrSize - 1 + kTellSlack < kTextSize, "nuts_roster_speak_plan: a composed private text fits its LDS text");
+static_assert(kNameLen + 22 + 1 <= 64, "compose: the pieces of the longest notice fit a wave");
+
 }  // namespace
 
 // Stable, unmangled kernel names (they are what rocprofv3 reports).
@@ -1439,11 +1695,14 @@ extern "C" __global__ void __launch_bounds__(kBlock) nuts_fanout_emit_many(ManyA
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_measure(RosterArgs a) { roster_measure(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_emit(RosterArgs a) { roster_emit(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_plan(PlanArgs a) { roster_plan(a); }
-extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_record(RecordArgs a) { roster_record(a); }
-extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_review(ReviewArgs a) { roster_review(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_record(RecordArgs a) { roster_record<kRevLines>(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_review(ReviewArgs a) { roster_review<kRevLines>(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_speak(SpeakArgs a) { roster_speak(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_speak_plan(SpeakPlanArgs a) { roster_speak_plan(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_parse(ParseArgs a) { roster_parse(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_tell(TellArgs a) { roster_tell(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_record_tell(RecordArgs a) { roster_record<kTellLines>(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_revtell(ReviewArgs a) { roster_review<kTellLines>(a); }
 
 // ------------------------------------------------------------------------------------------ host library
 
@@ -1672,12 +1931,24 @@ struct Roster {
     int review_rooms = 0;        // rooms 0 .. review_rooms - 1 own a review ring
     uint8_t* rings = nullptr;    // the rings, then the cursors: an allocation of its own, made on first use, never moved
     uint8_t* speech = nullptr;   // the speakers' state, 16 bytes per slot: likewise, made by the first nd_roster_speak
+    bool revtell = false;        // every slot owns a revtell ring
+    uint8_t* tell_rings = nullptr;   // the revtell rings, then their cursors: as rings
+    uint8_t* afk = nullptr;      // the AFK messages, 64 bytes per slot: as speech, made by the first nd_roster_tell
 };
 Roster g_rosters[kMaxRosters];
 
-// Where the cursors start in r.rings, and the allocation's size.
-size_t revline_at(const Roster& r) { return ((size_t)r.review_rooms * kRevRing + 255) & ~(size_t)255; }
-size_t rings_bytes(const Roster& r) { return revline_at(r) + (size_t)r.review_rooms * sizeof(int32_t); }
+// One of a roster's two sets of rings: the rooms' review rings (15 lines each), or the slots' revtell rings (5 lines).
+struct RingSet {
+    uint8_t** p;                 // r.rings or r.tell_rings
+    int count, lines;
+    size_t revline_at() const { return ((size_t)count * lines * kRevSlot + 255) & ~(size_t)255; }   // where the cursors start
+    size_t bytes() const { return revline_at() + (size_t)count * sizeof(int32_t); }                // the allocation's size
+    int32_t* revline() const { return reinterpret_cast<int32_t*>(*p + revline_at()); }
+};
+RingSet rings_of(Roster& r, bool tell)
+{
+    return tell ? RingSet{&r.tell_rings, r.revtell ? r.capacity : 0, kTellLines} : RingSet{&r.rings, r.review_rooms, kRevLines};
+}
 
 // The head of every layout of a roster's allocation: the table.  Its place depends on the capacity alone, so the table
 // stays resident across every kind of call, and a call that does not read it need not upload it.
@@ -1748,7 +2019,7 @@ size_t layout_plan(uintptr_t base, size_t text_bytes, size_t var_bytes, PlanArgs
 
 // nd_roster_review's layout of a roster's allocation: the table, which the call neither reads nor uploads, the call's
 // inputs ending with violations, then the results next to each other.
-size_t layout_review(uintptr_t base, int capacity, size_t clear_bytes, ReviewArgs& a)
+size_t layout_review(uintptr_t base, int capacity, size_t clear_bytes, ReviewArgs& a, int lines = kRevLines)
 {
     Carver take{base};
     const size_t q = (size_t)a.q;
@@ -1762,9 +2033,9 @@ size_t layout_review(uintptr_t base, int capacity, size_t clear_bytes, ReviewArg
     take(a.sequential, q);
     take(a.vn, 2 * q);
     take(a.vw, 2 * q);
-    take(a.vwsz, 2 * q * kRevWrites);
-    take(a.lines, q * kRevRing);
-    take(a.var, 2 * q * kRevVarStride);
+    take(a.vwsz, 2 * q * lines * kRevLineWrites);
+    take(a.lines, q * lines * kRevSlot);
+    take(a.var, 2 * q * rev_var_stride(lines));
     return take.at;
 }
 
@@ -1840,20 +2111,61 @@ size_t layout_speak(uintptr_t base, size_t text_bytes, size_t clear_bytes, Speak
     return take.at;
 }
 
-// The roster's rings, made and zeroed in the stream on first use.
-int ensure_rings(Roster& r, hipStream_t st)
+// nd_roster_tell's layout of a roster's allocation, after layout_speak's pattern: the table, the uploads of the speaker
+// table and of the AFK messages (which the kept ones, r.speech and r.afk, are filled from), the call's inputs ending with
+// violations, the results next to each other, and last what only the kernels pass to each other.  One upload starts at
+// the first of the three tables that changed, or at the inputs.
+size_t layout_tell(uintptr_t base, size_t text_bytes, size_t clear_bytes, TellArgs& s, SpeakPlanArgs& p, const uint8_t** clear)
 {
-    if (r.rings) return 0;
-    if (r.review_rooms < 1) {
-        snprintf(g_err, sizeof(g_err), "the roster has no review rings");
+    Carver take{base};
+    const size_t k = (size_t)s.k, cap = (size_t)s.capacity;
+    const size_t ctext_bytes = (size_t)ptext_at(2 * (int64_t)text_bytes, 2 * (int64_t)k);
+    take_table(take, s.capacity, s.room, s.slotf);
+    take(s.speech_new, cap * kSpeechRec);
+    take(s.afk_new, cap * kAfkRec);
+    take(s.text, text_bytes);
+    take(s.text_off, k);
+    take(s.text_len, k);
+    take(s.slot, k);
+    take(s.com, k);
+    take(s.words, k);
+    take(s.ctext_off, 2 * k);
+    take(*clear, clear_bytes);
+    take(s.violations, 1);
+    take(s.outcome, k);
+    take(s.target, k);
+    take(s.clen, 2 * k);
+    take(p.vn, 4 * k);
+    take(p.vw, 4 * k);
+    take(p.vwsz, 4 * k * kMaxWrites);
+    take(s.ctext, ctext_bytes);
+    take(p.var, (size_t)var_at((int64_t)ctext_bytes, 2 * (int64_t)k));
+    take(s.ring, k);
+    take(s.flags, k);
+    p.room = s.room;
+    p.slot = s.slotf;
+    p.text = s.ctext;
+    p.text_off = s.ctext_off;
+    p.text_len = s.clen;
+    p.violations = s.violations;
+    return take.at;
+}
+
+// The roster's rings (tell: its revtell rings), made and zeroed in the stream on first use.
+int ensure_rings(Roster& r, hipStream_t st, bool tell = false)
+{
+    const RingSet s = rings_of(r, tell);
+    if (*s.p) return 0;
+    if (s.count < 1) {
+        snprintf(g_err, sizeof(g_err), tell ? "the roster has no revtell rings" : "the roster has no review rings");
         return -1;
     }
-    hipError_t e = hipMalloc((void**)&r.rings, rings_bytes(r));
+    hipError_t e = hipMalloc((void**)s.p, s.bytes());
     if (e != hipSuccess) {
-        r.rings = nullptr;
-        return fail("review rings", e);
+        *s.p = nullptr;
+        return fail(tell ? "revtell rings" : "review rings", e);
     }
-    ND_CHECK(hipMemsetAsync(r.rings, 0, rings_bytes(r), st));
+    ND_CHECK(hipMemsetAsync(*s.p, 0, s.bytes(), st));
     return 0;
 }
 
@@ -1899,13 +2211,15 @@ int grow_roster(Roster& r, size_t need)
 }
 
 // nuts_roster_record after a call's planning kernel, on device arrays of that call: the k texts, their rooms and flags
-// (bit 2: record), and the pending clears (nullptr: none).  The rings are touched by g.stream alone.
-int launch_record(const Roster& r, int k, const uint8_t* text, const int32_t* text_off, const int32_t* text_len,
-                  const int32_t* rm, const uint8_t* flags, const uint8_t* clear)
+// (bit 2: record), and the pending clears (nullptr: none).  tell: the texts are told lines, rm their targets, and the
+// rings the slots' revtell rings.  The rings are touched by g.stream alone.
+int launch_record(Roster& r, int k, const uint8_t* text, const int32_t* text_off, const int32_t* text_len,
+                  const int32_t* rm, const uint8_t* flags, const uint8_t* clear, bool tell = false)
 {
-    RecordArgs rec{text, text_off, text_len, rm, flags, clear, k, r.review_rooms, r.rings,
-                   reinterpret_cast<int32_t*>(r.rings + revline_at(r))};
-    hipLaunchKernelGGL(nuts_roster_record, dim3((unsigned)r.review_rooms), dim3(kBlock), 0, g.stream, rec);
+    const RingSet s = rings_of(r, tell);
+    RecordArgs rec{text, text_off, text_len, rm, flags, clear, k, s.count, *s.p, s.revline()};
+    hipLaunchKernelGGL(tell ? nuts_roster_record_tell : nuts_roster_record, dim3((unsigned)s.count), dim3(kBlock), 0,
+                       g.stream, rec);
     ND_CHECK(hipGetLastError());
     return 0;
 }
@@ -2145,7 +2459,9 @@ int nd_roster_destroy(int handle)
     if (!r) return -1;
     if (r->d) (void)hipFree(r->d);
     if (r->rings) (void)hipFree(r->rings);
+    if (r->tell_rings) (void)hipFree(r->tell_rings);
     if (r->speech) (void)hipFree(r->speech);
+    if (r->afk) (void)hipFree(r->afk);
     if (r->mirror) (void)hipHostFree(r->mirror);
     *r = Roster{};
     return 0;
@@ -2370,38 +2686,43 @@ int nd_roster_review_rooms(int handle, int n)
 // (entries at or past vw unspecified); lines[q * 15 * 202] the ring's slots, oldest first; var[2q * 18152] the reviews'
 // bytes, variant v at v * 18152, the rest unspecified.  Per call, whatever q and whatever the rings hold: one upload,
 // one kernel, one download at the bound size, one synchronise.  Returns 0, or -1 with nd_last_error() set.
-int nd_roster_review(int handle, int q, const int32_t* rooms, const uint8_t* clear, int32_t* line_count,
-                     int32_t* sequential, int32_t* vn, int32_t* vw, int32_t* vwsz, uint8_t* lines, uint8_t* var,
-                     nd_roster_timing* timing)
+//
+// tell (nd_roster_revtell): the same over the slots' revtell rings, rooms[] slots, clear `capacity` bytes, 5 lines where
+// there were 15: vwsz[2q * 15], lines[q * 5 * 202], var[2q * 6052].
+static int review_call(int handle, int q, const int32_t* rooms, const uint8_t* clear, int32_t* line_count,
+                       int32_t* sequential, int32_t* vn, int32_t* vw, int32_t* vwsz, uint8_t* lines, uint8_t* var,
+                       nd_roster_timing* timing, bool tell)
 {
     Roster* r = roster_at(handle);
     if (!r || ensure_ready()) return -1;
-    if (q < 1 || (int64_t)q * 2 * kRevVarStride >= INT32_MAX) {
-        snprintf(g_err, sizeof(g_err), "%d rooms to review: need 1 <= q and 2 * q * %d < 2^31 - 1", q, kRevVarStride);
+    const RingSet set = rings_of(*r, tell);
+    const int nlines = set.lines, stride = rev_var_stride(nlines);
+    if (q < 1 || (int64_t)q * 2 * stride >= INT32_MAX) {
+        snprintf(g_err, sizeof(g_err), "%d rooms to review: need 1 <= q and 2 * q * %d < 2^31 - 1", q, stride);
         return -1;
     }
-    if (ensure_rings(*r, g.stream)) return -1;
+    if (ensure_rings(*r, g.stream, tell)) return -1;
     for (int i = 0; i < q; i++)
-        if (rooms[i] < 0 || rooms[i] >= r->review_rooms) {
-            snprintf(g_err, sizeof(g_err), "room %d has no review ring", rooms[i]);
+        if (rooms[i] < 0 || rooms[i] >= set.count) {
+            snprintf(g_err, sizeof(g_err), tell ? "slot %d has no revtell ring" : "room %d has no review ring", rooms[i]);
             return -1;
         }
     const double t0 = now_ns();
     hipStream_t st = g.stream;
     ReviewArgs a{};
     a.q = q;
-    a.review_rooms = r->review_rooms;
-    const size_t clear_bytes = clear ? (size_t)r->review_rooms : 0;
+    a.review_rooms = set.count;
+    const size_t clear_bytes = clear ? (size_t)set.count : 0;
     ReviewArgs o = a;                // offsets of every array in the roster's allocation
-    const size_t need = layout_review(0, r->capacity, clear_bytes, o);
+    const size_t need = layout_review(0, r->capacity, clear_bytes, o, nlines);
     const size_t table_bytes = (uintptr_t)o.rooms, in_bytes = (uintptr_t)o.violations + sizeof(int);
     const size_t res_at = (uintptr_t)o.violations, res_bytes = need - res_at;
     if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
     if (grow_roster(*r, need)) return -1;
-    layout_review((uintptr_t)r->d, r->capacity, clear_bytes, a);
+    layout_review((uintptr_t)r->d, r->capacity, clear_bytes, a, nlines);
     if (!clear) a.clear = nullptr;
-    a.rings = r->rings;
-    a.revline = reinterpret_cast<int32_t*>(r->rings + revline_at(*r));
+    a.rings = *set.p;
+    a.revline = set.revline();
     if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
 
     uint8_t* h = r->mirror;
@@ -2411,9 +2732,9 @@ int nd_roster_review(int handle, int q, const int32_t* rooms, const uint8_t* cle
     ND_CHECK(hipMemcpyAsync(r->d + table_bytes, h + table_bytes, in_bytes - table_bytes, hipMemcpyHostToDevice, st));
 
     // one block per requested room, then the blocks that store the pending clears, a ring room per lane
-    const unsigned grid = (unsigned)q + (clear ? (unsigned)((r->review_rooms + kBlock - 1) / kBlock) : 0u);
+    const unsigned grid = (unsigned)q + (clear ? (unsigned)((set.count + kBlock - 1) / kBlock) : 0u);
     ND_CHECK(hipEventRecord(g.ev0, st));
-    hipLaunchKernelGGL(nuts_roster_review, dim3(grid), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(tell ? nuts_roster_revtell : nuts_roster_review, dim3(grid), dim3(kBlock), 0, st, a);
     ND_CHECK(hipGetLastError());
     if (fetch_results(r->d, res_at, res_bytes)) return -1;
     const double t1 = now_ns();
@@ -2429,11 +2750,37 @@ int nd_roster_review(int handle, int q, const int32_t* rooms, const uint8_t* cle
     memcpy(sequential, res(o.sequential), (size_t)q * sizeof(int32_t));
     memcpy(vn, res(o.vn), 2 * (size_t)q * sizeof(int32_t));
     memcpy(vw, res(o.vw), 2 * (size_t)q * sizeof(int32_t));
-    memcpy(vwsz, res(o.vwsz), 2 * (size_t)q * kRevWrites * sizeof(int32_t));
-    memcpy(lines, res(o.lines), (size_t)q * kRevRing);
-    memcpy(var, res(o.var), 2 * (size_t)q * kRevVarStride);
+    memcpy(vwsz, res(o.vwsz), 2 * (size_t)q * nlines * kRevLineWrites * sizeof(int32_t));
+    memcpy(lines, res(o.lines), (size_t)q * nlines * kRevSlot);
+    memcpy(var, res(o.var), 2 * (size_t)q * stride);
 
     return fill_timing(timing, t0, t1, in_bytes - table_bytes, res_bytes);
+}
+
+// The rooms' review rings (review_call above).
+int nd_roster_review(int handle, int q, const int32_t* rooms, const uint8_t* clear, int32_t* line_count,
+                     int32_t* sequential, int32_t* vn, int32_t* vw, int32_t* vwsz, uint8_t* lines, uint8_t* var,
+                     nd_roster_timing* timing)
+{
+    return review_call(handle, q, rooms, clear, line_count, sequential, vn, vw, vwsz, lines, var, timing, false);
+}
+
+// Give roster `handle` a revtell ring per slot, all empty; before its first recording nd_roster_tell or nd_roster_revtell,
+// which allocates them (1,010 bytes per slot and a cursor).  Returns 0, or -1 with nd_last_error() set.
+int nd_roster_revtell_rings(int handle)
+{
+    Roster* r = roster_at(handle);
+    if (!r) return -1;
+    r->revtell = true;
+    return 0;
+}
+
+// What .revtell sends for each of the q slots[] (nd_roster_review's comment, review_call above).
+int nd_roster_revtell(int handle, int q, const int32_t* slots, const uint8_t* clear, int32_t* line_count,
+                      int32_t* sequential, int32_t* vn, int32_t* vw, int32_t* vwsz, uint8_t* lines, uint8_t* var,
+                      nd_roster_timing* timing)
+{
+    return review_call(handle, q, slots, clear, line_count, sequential, vn, vw, vwsz, lines, var, timing, true);
 }
 
 // What nd_roster_input returns of nuts_roster_parse: host arrays of k entries each.
@@ -2644,6 +2991,147 @@ int nd_roster_input(int handle, int k, const uint8_t* data, int64_t data_bytes, 
     const ParseOut parsed{kind, com, words, line_len, inp_off, inp_len};
     return speech_call(handle, k, data, data_bytes, read_off, read_len, slots, nullptr, nullptr, ban_swearing, record,
                        table, speech, clear, outcome, clen, bits, vn, vw, vwsz, ctext, var, timing, &parsed);
+}
+
+// A kept per-slot table of a roster (the speaker state, the AFK messages), made on the first call that gives it.
+static int ensure_kept(uint8_t** p, size_t bytes, const char* what)
+{
+    if (*p) return 0;
+    hipError_t e = hipMalloc((void**)p, bytes);
+    if (e != hipSuccess) {
+        *p = nullptr;
+        return fail(what, e);
+    }
+    return 0;
+}
+
+// K private speech events of roster `handle`, as tell() and pemote() answer them.  Event b: the speaker's slot slots[b],
+// the command coms[b] (NP_TELL 5, NP_PEMOTE 8), inpstr and words[b] as nd_roster_speak's.  table and speech as
+// nd_roster_speak's, the speech flags byte with afk 8 and igntell 16 as well; afk is NULL when no AFK message changed
+// since the last nd_roster_tell of this roster, else all of them: 64 bytes per slot, 60 of message padded with zeros,
+// then its length; the roster's first call must give it.  record: store every told line in its target's revtell ring
+// (nd_roster_revtell_rings), after clearing the rings that clear marks (NULL: none, else `capacity` bytes).
+// Outputs (host, caller-allocated), text t = b for event b's told line, k + b for its reply: outcome[k] (0 told, 1
+// muzzled, 2 nothing, 4 nobody, 5 self, 6 afk, 7 ignall, 8 igntell, 9 offsite); target[k] the slot get_user found, or -1;
+// clen[2k]; ctext[2 * text_bytes + 192 * k], text t at text_off[b] + 96 * b, plus text_bytes + 96 * k for a reply; vn[4k],
+// vw[4k], vwsz[4k * 16] and var[12 * ctext bytes + 32 * k] as nd_roster_speak's.
+// Per call, whatever k and the capacity: one upload, two kernels (nuts_roster_tell, nuts_roster_speak_plan) and
+// nuts_roster_record_tell as a third when record is set, one download at the bound size, one synchronise.
+// Returns 0, or -1 with nd_last_error() set.
+int nd_roster_tell(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off,
+                   const int32_t* text_len, const int32_t* slots, const uint8_t* coms, const uint8_t* words, int record,
+                   const uint8_t* table, const uint8_t* speech, const uint8_t* afk, const uint8_t* clear, int8_t* outcome,
+                   int32_t* target, int32_t* clen, int64_t* vn, int32_t* vw, int32_t* vwsz, uint8_t* ctext, uint8_t* var,
+                   nd_roster_timing* timing)
+{
+    Roster* r = roster_at(handle);
+    if (!r || ensure_ready()) return -1;
+    const int cap = r->capacity;
+    if (k < 1 || (int64_t)k * cap >= INT32_MAX || text_bytes < 0 || text_bytes >= INT32_MAX / 32) {
+        snprintf(g_err, sizeof(g_err), "%d events to %d slots: need 1 <= k * capacity < 2^31 - 1", k, cap);
+        return -1;
+    }
+    int64_t sum = 0;
+    for (int b = 0; b < k; b++) {       // the kernels index by these: nothing out of range reaches them
+        if (slots[b] < 0 || slots[b] >= cap || (coms[b] != kComTell && coms[b] != kComPemote) || text_len[b] < 0 ||
+            text_len[b] >= kArrSize || text_off[b] != sum) {
+            snprintf(g_err, sizeof(g_err), "event %d: slot, command, text length or text offset out of range", b);
+            return -1;
+        }
+        sum += text_len[b];
+    }
+    if (sum != text_bytes) {
+        snprintf(g_err, sizeof(g_err), "the events' texts hold %lld bytes, not %lld", (long long)sum, (long long)text_bytes);
+        return -1;
+    }
+    if ((!r->speech && !speech) || (!r->afk && !afk)) {
+        snprintf(g_err, sizeof(g_err), "the roster's first private speech call must give the speaker table and the AFK messages");
+        return -1;
+    }
+    if (record && ensure_rings(*r, g.stream, true)) return -1;
+    if (ensure_kept(&r->speech, (size_t)cap * kSpeechRec, "speaker table")) return -1;
+    if (ensure_kept(&r->afk, (size_t)cap * kAfkRec, "AFK messages")) return -1;
+    const double t0 = now_ns();
+    hipStream_t st = g.stream;
+    TellArgs s{};
+    SpeakPlanArgs p{};                  // k = 0, tiles = 0: no room lines, a block per text
+    s.k = k;
+    s.capacity = p.capacity = cap;
+    s.record = record != 0;
+    const size_t ctext_bytes = (size_t)ptext_at(2 * text_bytes, 2 * (int64_t)k);
+    const size_t var_bytes = (size_t)var_at((int64_t)ctext_bytes, 2 * (int64_t)k);
+    const size_t clear_bytes = record && clear ? (size_t)cap : 0;
+    TellArgs so = s;                    // offsets of every array in the roster's allocation
+    SpeakPlanArgs po = p;
+    const uint8_t *o_clear = nullptr, *d_clear = nullptr;
+    const size_t need = layout_tell(0, (size_t)text_bytes, clear_bytes, so, po, &o_clear);
+    const size_t table_bytes = (uintptr_t)so.speech_new, afk_at = (uintptr_t)so.afk_new, tables_end = (uintptr_t)so.text;
+    const size_t in_bytes = (uintptr_t)so.violations + sizeof(int);
+    const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
+    if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
+    if (table) new_table(*r, so.room, so.slotf, table);
+    if (grow_roster(*r, need)) return -1;
+    layout_tell((uintptr_t)r->d, (size_t)text_bytes, clear_bytes, s, p, &d_clear);
+    if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
+
+    uint8_t* h = r->mirror;
+    const Put put{h};
+    if (speech) put(so.speech_new, speech, (size_t)cap * kSpeechRec);
+    if (afk) put(so.afk_new, afk, (size_t)cap * kAfkRec);
+    put(so.text, text, (size_t)text_bytes);
+    put(so.text_off, text_off, (size_t)k * sizeof(int32_t));
+    put(so.text_len, text_len, (size_t)k * sizeof(int32_t));
+    put(so.slot, slots, (size_t)k * sizeof(int32_t));
+    put(so.com, coms, (size_t)k);
+    put(so.words, words, (size_t)k);
+    int32_t* coff = reinterpret_cast<int32_t*>(h + (uintptr_t)so.ctext_off);
+    for (int b = 0; b < k; b++) {
+        coff[b] = (int32_t)ptext_at(text_off[b], b);
+        coff[k + b] = (int32_t)ptext_at(text_bytes + text_off[b], k + b);
+    }
+    put(o_clear, clear, clear_bytes);
+    *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
+    // the tables' uploads lie between the table and the inputs: what lies after the first one that changed travels too,
+    // but the kernel is told of the changed ones alone, so the mirror's bytes of the others need not be current
+    const size_t from = !r->resident ? 0 : speech ? table_bytes : afk ? afk_at : tables_end;
+    ND_CHECK(hipMemcpyAsync(r->d + from, h + from, in_bytes - from, hipMemcpyHostToDevice, st));
+    r->resident = true;
+    s.speech = speech ? s.speech_new : r->speech;
+    s.afk = afk ? s.afk_new : r->afk;
+    if (!speech) s.speech_new = nullptr;
+    if (!afk) s.afk_new = nullptr;
+    s.speech_keep = r->speech;
+    s.afk_keep = r->afk;
+
+    const size_t copy_words = (size_t)cap * ((speech ? kSpeechRec / 4 : 0) + (afk ? kAfkRec / 4 : 0));
+    ND_CHECK(hipEventRecord(g.ev0, st));
+    hipLaunchKernelGGL(nuts_roster_tell, dim3((unsigned)(k + (copy_words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, s);
+    ND_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)(2 * k)), dim3(kBlock), 0, st, p);
+    ND_CHECK(hipGetLastError());
+    // on the arrays nuts_roster_tell wrote
+    if (record && launch_record(*r, k, s.ctext, s.ctext_off, s.clen, s.ring, s.flags, clear_bytes ? d_clear : nullptr, true))
+        return -1;
+    if (fetch_results(r->d, res_at, res_bytes)) return -1;
+    const double t1 = now_ns();
+
+    const Res res{gm.res, res_at};
+    const int violations = *reinterpret_cast<const int*>(res(so.violations));
+    if (violations) {
+        snprintf(g_err, sizeof(g_err), "%d text(s) exceeded the hard bounds (inpstr + %d bytes composed; 6*len+4 bytes, "
+                 "%d writes transduced)", violations, kTellSlack, kMaxWrites);
+        return -1;
+    }
+    memcpy(outcome, res(so.outcome), (size_t)k);
+    memcpy(target, res(so.target), (size_t)k * sizeof(int32_t));
+    memcpy(clen, res(so.clen), 2 * (size_t)k * sizeof(int32_t));
+    memcpy(vn, res(po.vn), 4 * (size_t)k * sizeof(int64_t));
+    memcpy(vw, res(po.vw), 4 * (size_t)k * sizeof(int32_t));
+    memcpy(vwsz, res(po.vwsz), 4 * (size_t)k * kMaxWrites * sizeof(int32_t));
+    memcpy(ctext, res(so.ctext), ctext_bytes);
+    memcpy(var, res(po.var), var_bytes);
+
+    return fill_timing(timing, t0, t1, in_bytes - from, res_bytes);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 
     python -m nuts333_amd.devpath [--reps R] [--warmup W] [--pathbench-iterations I] [--per-call K[,K...]]
                                   [--roster K[,K...]] [--plan K[,K...]] [--review Q[,Q...]] [--speak K[,K...]]
-                                  [--input K[,K...]]                                          -> one JSON line
+                                  [--input K[,K...]] [--tell K[,K...]]                        -> one JSON line
 
 For N in {10, 100, 1000} listeners, the two texts oracle/pathbench.c times (``say``; ``shout`` carrying ``~OL``/``~RS``)
 and colour all-off / all-on / half, one ``nuts333_amd.device.broadcast`` per repetition (listener 0 is the sender, the
@@ -56,6 +56,13 @@ of the same events parsed beforehand: the three times and the copy volume of bot
 ``np_wordfind``, all that ``user_input()`` runs on a plain line; ``cpu_exec_com_us``: those and ``np_remove_first``,
 ``np_command_lookup`` and ``np_command_level``, the most a read can need; one ctypes call each).  The first call of each
 case is checked against ``speak_many`` and the restatement.
+
+``--tell K[,K...]`` adds ``tell``: a 1000-slot roster in which every slot has a name, and K tells of slot 0 to one target
+per ``Roster.tell_many`` call, their bodies the K ``say`` bodies, timed alternating, in one process, with ``speak_many``
+of K says of the same bodies: the three times and the copy volume of both, and their ratio.  ``get_user`` reads all 1000
+slots for every tell.  There is no C restatement of ``get_user`` or ``tell()`` to time beside it:
+``cpu_derived_estimate_us`` is 2 x K x pathbench's ``format_line_once_ns``, the two formats alone, an estimate and not
+the talker's cost of a tell.  The first call of each case is checked against the reference's two formats.
 """
 from __future__ import annotations
 
@@ -470,6 +477,78 @@ def input_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
             "input": cases}
 
 
+TELL_TARGET = (500, b"Zebedee")
+
+
+def tell_events(k: int) -> list[tuple]:
+    """K tells of slot 0 to TELL_TARGET whose bodies are the K says of ``speak_events(k)``: ``inpstr`` is what
+    ``.tell zebedee <body>`` hands to tell()."""
+    return [(0, device.COM_TELL, TELL_TARGET[1].lower() + b" " + inpstr, 9) for _, _, inpstr, _ in speak_events(k)]
+
+
+def tell_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
+    """The ``tell`` section: tell_many of K tells to one target in a 1000-slot roster in which every slot has a name,
+    alternating with speak_many of K says of the same bodies, for each colour case and each K."""
+    n = 1000
+    cases = []
+    for colour in COLOURS:
+        with device.Roster(n) as roster:
+            roster.update(range(n), room=0, colour=listeners(n, colour)[:, device.LISTENER_FIELDS.index("colour")],
+                          name=[b"User%d" % j for j in range(n)])
+            roster.update(0, name=b"Uaaa")
+            roster.update(TELL_TARGET[0], name=TELL_TARGET[1])
+            for k in ks:
+                tells, says = tell_events(k), speak_events(k)
+                first = roster.tell_many(tells)
+                for i, (_, _, body, _) in enumerate(says):
+                    verb = b"ask" if body.endswith(b"?") else b"tell"
+                    line = b"~OLUaaa %ss you:~RS %s\n" % (verb, body)
+                    reply = b"~OLYou %s %s:~RS %s\n" % (verb, TELL_TARGET[1], body)
+                    ok = (first.outcome[i] == device.TOLD and first.target[i] == TELL_TARGET[0] and first.line(i) == line
+                          and first.reply_text(i) == reply
+                          and first.told.admitted(i).nonzero()[0].tolist() == [TELL_TARGET[0]]
+                          and all(first.told.variant(i, c) == nuts_path.transduce(line, c)
+                                  and first.reply.variant(i, c) == nuts_path.transduce(reply, c) for c in (0, 1)))
+                    if not ok:
+                        raise SystemExit(f"devpath: tell {k}, {colour}: event {i} differs from the reference's formats")
+                timed = {name: {"kernels_us": [], "end_to_end_us": [], "python_us": [], "copies": set()}
+                         for name in ("tell", "speak")}
+                for i in range(2 * (warmup + reps)):
+                    name = ("tell", "speak")[i % 2]
+                    t0 = time.perf_counter()
+                    r = roster.tell_many(tells) if name == "tell" else roster.speak_many(says, ban_swearing=True)
+                    if i >= 2 * warmup:
+                        timed[name]["python_us"].append((time.perf_counter() - t0) * 1e6)
+                        timed[name]["kernels_us"].append(r.timing["kernels_us"])
+                        timed[name]["end_to_end_us"].append(r.timing["end_to_end_us"])
+                        timed[name]["copies"].add((r.timing["h2d_bytes"], r.timing["d2h_bytes"]))
+                for name, t in timed.items():
+                    if len(t["copies"]) != 1:
+                        raise SystemExit(f"devpath: tell {k}, {colour}: timed {name} calls copied {sorted(t['copies'])} bytes")
+                fields = ("kernels_us", "end_to_end_us", "python_us")
+                tl = {f: _stats(timed["tell"][f]) for f in fields}
+                sp = {f: _stats(timed["speak"][f]) for f in fields}
+                h2d, d2h = timed["tell"]["copies"].pop()
+                sh2d, sd2h = timed["speak"]["copies"].pop()
+                cases.append({"n": n, "k": k, "colour": colour, "target": TELL_TARGET[0], "recipients": k, **tl,
+                              "h2d_bytes": h2d, "d2h_bytes": d2h,
+                              "speak_many_of_the_same_bodies": {**sp, "h2d_bytes": sh2d, "d2h_bytes": sd2h},
+                              "tell_over_speak": {f: round(tl[f]["median"] / sp[f]["median"], 2) for f in fields},
+                              "cpu_derived_estimate_us": round(2 * k * pb["format_line_once_ns"] / 1e3, 3)})
+    return {"tell_kernels": ["nuts_roster_tell", "nuts_roster_speak_plan"],
+            "tell_end_to_end_covers": "packing the K events into pinned memory, one H2D (the table, the speaker state and "
+                                      "the AFK messages only in a call after an update of theirs), two kernels -- "
+                                      "get_user over all 1000 slots per event, the texts, their variants --, one D2H of "
+                                      "the outcomes, the targets, the composed texts and both plans' variants and chunk "
+                                      "sizes at their bound size, one synchronise (python_us adds checking the K events "
+                                      "and their speakers, the copies out of pinned memory and building the Private)",
+            "tell_cpu_derived_estimate_us_covers": "an estimate, not a measurement: 2 x K x pathbench's "
+                                                   "format_line_once_ns, the two formats of tell() alone, without "
+                                                   "get_user's two passes over the user list, which no C restatement "
+                                                   "here times",
+            "tell": cases}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=2000, help="timed broadcasts per case (default 2000)")
@@ -490,6 +569,9 @@ def main(argv=None) -> int:
     ap.add_argument("--input", type=per_call_counts, default=None, metavar="K[,K...]",
                     help="also time K raw reads per Roster.input_many call, for each K, beside speak_many of the same "
                          "events parsed beforehand (the input section)")
+    ap.add_argument("--tell", type=per_call_counts, default=None, metavar="K[,K...]",
+                    help="also time K tells to one target per Roster.tell_many call, for each K, beside speak_many of K "
+                         "says of the same bodies (the tell section)")
     a = ap.parse_args(argv)
     if a.reps < 1 or a.warmup < 0:
         ap.error("--reps must be >= 1 and --warmup >= 0")
@@ -571,6 +653,7 @@ def main(argv=None) -> int:
     review = review_cases(a.review, a.reps, a.warmup, pb) if a.review else {}
     speak = speak_cases(a.speak, a.reps, a.warmup, pb) if a.speak else {}
     inputs = input_cases(a.input, a.reps, a.warmup, pb) if a.input else {}
+    tell = tell_cases(a.tell, a.reps, a.warmup, pb) if a.tell else {}
     out = {
         "what": "user-space stage of one broadcast (admit predicate + transducer), device vs CPU",
         "device": "gfx950",
@@ -586,6 +669,7 @@ def main(argv=None) -> int:
         **review,
         **speak,
         **inputs,
+        **tell,
         "wall_s": round(time.perf_counter() - t_start, 1),
     }
     print(json.dumps(out))
