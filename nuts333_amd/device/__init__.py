@@ -45,6 +45,11 @@ composed texts with their plans -- a :class:`Private`.  ``Roster(capacity, revte
 revtell ring of the talker (nuts333.c:7699-7715): ``tell_many(events, record=True)`` stores each told line in its target's
 ring, ``Roster.revtell_many(slots)`` returns what ``.revtell`` sends for each slot as a :class:`Review`, and
 ``Roster.clear_revtell(slots)`` empties rings.
+``Roster(capacity, look_rooms=R)`` keeps a room table for rooms ``0 .. R - 1`` on the device (``Roster.set_rooms``:
+name, access, description, links, topic, board count, netlink) and every slot's ``desc`` (``Roster.update(desc=)``), and
+``Roster.look_many(slots)`` returns what ``look()`` writes for K lookers (nuts333.c:3942-4004) as a :class:`Look`: the
+texts of the call -- five per distinct room, three fixed ones, a line per user of those rooms -- with their two
+variants, and per looker the users it is shown, in list order.
 
 Input is validated before the device is touched (``ValueError``).  The library ``_build/libnuts_device.so`` is built by
 ``__graft_entry__.build()`` where ``hipcc`` exists, and on demand here when it is missing or older than its source.
@@ -82,7 +87,7 @@ KERNELS = ("nuts_fanout_measure_broadcast", "nuts_fanout_emit_broadcast",
            "nuts_fanout_measure_many", "nuts_fanout_emit_many",
            "nuts_roster_measure", "nuts_roster_emit", "nuts_roster_plan", "nuts_roster_record", "nuts_roster_review",
            "nuts_roster_speak", "nuts_roster_speak_plan", "nuts_roster_parse",
-           "nuts_roster_tell", "nuts_roster_record_tell", "nuts_roster_revtell")
+           "nuts_roster_tell", "nuts_roster_record_tell", "nuts_roster_revtell", "nuts_roster_look")
 #: NP_ARR_SIZE (nuts333.h:19): the input line a speech command receives is at most 999 bytes
 ARR_SIZE = 1000
 #: USER_NAME_LEN (nuts333.h:23) and invisname (nuts333.h:150), the name an invisible speaker is shown by
@@ -149,6 +154,29 @@ MAX_REVTELL_BYTES, MAX_REVTELL_WRITES = REVTELL_LINES * MAX_LINE_BYTES, REVTELL_
 _REVTELL_STRIDE = (MAX_REVTELL_BYTES + 3) & ~3
 #: bit 2 of a broadcast's flags byte: record it (bit 1 is force_listen)
 _RECORD_BIT = 4
+#: the most rooms of a Roster that own a room record (``Roster(look_rooms=)``): the figure and the reasoning of
+#: MAX_REVIEW_ROOMS -- a room's record and description are 1,072 bytes, 1.1 MB at 1024 rooms for the roster's life, and
+#: 32 times the rooms the restated talker can hold
+MAX_LOOK_ROOMS = 1024
+#: ROOM_NAME_LEN, ROOM_DESC_LEN, MAX_LINKS, TOPIC_LEN, SERV_NAME_LEN, USER_DESC_LEN (nuts333.h)
+ROOM_NAME_LEN, ROOM_DESC_LEN, MAX_LINKS, TOPIC_LEN, SERV_NAME_LEN, USER_DESC_LEN = 20, 810, 10, 60, 80, 30
+#: a room's access (nuts333.h): bit 0 is PRIVATE, bit 1 fixes it
+PUBLIC, PRIVATE, FIXED_PUBLIC, FIXED_PRIVATE = 0, 1, 2, 3
+#: the room table's rows as fanout.hip reads them (its look section has the fields): a 256-byte record and an 816-byte
+#: description row per room, the records first; and a slot's 32-byte row of the users' descriptions
+_ROOM_REC, _ROOM_DESC_ROW, _DESC_ROW = 256, 816, 32
+#: hard bounds of one member line of look() through the transducer, proven by a host test against the CPU restatement:
+#: with colour on its fixed parts give 42 bytes (5 blanks, ~FR, ``*``, ~RS, a blank, ~RS, 2 blanks, ~BR, ``(AFK)``, the
+#: newline, the trailing reset) and a byte of name or description at most 6; far below the 994 staged bytes that
+#: would flush in mid-line, so it is one write and the reset's
+MAX_MEMBER_BYTES, MAX_MEMBER_WRITES = 42 + 6 * (USER_NAME_LEN + USER_DESC_LEN), 2
+#: the longest member line before the transducer, and its slot among a look call's texts (kLineRow of fanout.hip)
+MAX_MEMBER_LINE, _LINE_ROW = 69, 72
+#: a look call's texts (look_text_at, look_fixed_at of fanout.hip): a room's five slots, 1376 bytes in all, are 36, 812, 352,
+#: 96 and 80 bytes wide, the longest form of each text; then the three fixed texts in 48 bytes; then the lines
+_LOOK_TEXT_AT, _LOOK_STRIDE, _LOOK_FIXED_AT, _LOOK_FIXED_STRIDE = (0, 36, 848, 1200, 1296), 1376, (0, 16, 44), 48
+#: the texts of a room in a Look, in look()'s order, and the fixed ones
+LOOK_NAME, LOOK_DESC, LOOK_EXITS, LOOK_ACCESS, LOOK_TOPIC = range(5)
 
 
 def max_bytes(text_len: int) -> int:
@@ -420,6 +448,79 @@ class Private:
 
 
 @dataclass
+class Look:
+    """What ``look()`` writes for K lookers (``Roster.look_many``), as a delivery plan: texts with two variants each, and
+    per looker which of them it gets.  The texts, T = 5 R + 3 + L of them for the R distinct rooms and L lines of the call:
+    text ``5 i + j`` is text ``j`` (LOOK_NAME, LOOK_DESC, LOOK_EXITS, LOOK_ACCESS, LOOK_TOPIC) of room ``rooms[i]``;
+    texts ``5 R``, ``5 R + 1`` and ``5 R + 2`` are ``You can see:``, ``You are all alone here.`` and the newline after the
+    list; text ``5 R + 3 + l`` is line ``l``, the line of slot ``line_slots[l]``, transduced once however many lookers
+    list it.  ``variants`` .. ``write_sizes`` hold their two variants as a :class:`Plan` holds a broadcast's, ``texts`` ..
+    ``text_sizes`` the composed texts before the transducer (size -1: no such text).  Looker ``k`` is slot ``slots[k]``
+    with colour bit ``colour[k]`` in room ``rooms[room_index[k]]``; its members are ``member_slots[member_starts[k]:][:
+    member_counts[k]]`` in slot order and their lines ``member_lines`` alike.  ``timing`` is as a Plan's."""
+    slots: np.ndarray             # int32 [K]
+    colour: np.ndarray            # uint8 [K]   the lookers' colour bits
+    room_index: np.ndarray        # int32 [K]   into rooms
+    rooms: np.ndarray             # int32 [R]   the distinct rooms, in the order of their first looker
+    member_slots: np.ndarray      # int32, flat
+    member_lines: np.ndarray      # int32, flat: line numbers
+    member_starts: np.ndarray     # int64 [K]
+    member_counts: np.ndarray     # int32 [K]
+    line_slots: np.ndarray        # int32 [L]   -1: a line nobody took
+    texts: np.ndarray             # uint8, flat: the composed texts; gaps are allowed and unspecified
+    text_starts: np.ndarray       # int64 [T]
+    text_sizes: np.ndarray        # int64 [T]   -1: there is no such text
+    variants: np.ndarray          # uint8, flat
+    variant_starts: np.ndarray    # int64 [T, 2]
+    variant_sizes: np.ndarray     # int64 [T, 2]
+    write_counts: np.ndarray      # int32 [T, 2]
+    write_sizes: np.ndarray       # int32 [T, 2, MAX_WRITES]   entries at or past write_counts are unspecified
+    timing: dict = field(default_factory=dict)
+
+    def _check(self, k: int) -> None:
+        if not 0 <= k < len(self.slots):
+            raise IndexError(f"no look {k}: {len(self.slots)} looks")
+
+    def members(self, k: int) -> np.ndarray:
+        """The slots look ``k`` lists, in list order."""
+        self._check(k)
+        at = int(self.member_starts[k])
+        return self.member_slots[at:at + int(self.member_counts[k])]
+
+    def text_numbers(self, k: int) -> list[int]:
+        """The texts look ``k`` is sent, in look()'s order: one ``write_user`` each."""
+        self._check(k)
+        i, fixed = 5 * int(self.room_index[k]), 5 * len(self.rooms)
+        at, n = int(self.member_starts[k]), int(self.member_counts[k])
+        listed = [fixed] + [fixed + 3 + int(l) for l in self.member_lines[at:at + n]] if n else [fixed + 1]
+        return [i + LOOK_NAME, i + LOOK_DESC, i + LOOK_EXITS] + listed + [fixed + 2, i + LOOK_ACCESS, i + LOOK_TOPIC]
+
+    def text(self, t: int) -> bytes:
+        """Text ``t`` before the transducer."""
+        if not 0 <= t < len(self.text_sizes) or self.text_sizes[t] < 0:
+            raise IndexError(f"no text {t}")
+        at = int(self.text_starts[t])
+        return self.texts[at:at + int(self.text_sizes[t])].tobytes()
+
+    def text_chunks(self, t: int, c: int) -> list[bytes]:
+        """Text ``t`` for colour bit ``c`` as the ``write(2)`` chunks the reference would issue."""
+        if not 0 <= t < len(self.text_sizes) or c not in (0, 1):
+            raise IndexError(f"no text ({t}, {c})")
+        at = int(self.variant_starts[t, c])
+        return _split(self.variants[at:at + int(self.variant_sizes[t, c])].tobytes(),
+                      self.write_sizes[t, c, :int(self.write_counts[t, c])], f"text ({t}, {c})", "the variant")
+
+    def chunks(self, k: int) -> list[bytes]:
+        """The ``write(2)`` payloads of look ``k``, in order."""
+        c = int(self.colour[k]) if 0 <= k < len(self.slots) else 0
+        return [ch for t in self.text_numbers(k) for ch in self.text_chunks(t, c)]
+
+    def output(self, k: int) -> bytes:
+        """Everything look ``k`` writes: the concatenation of ``chunks(k)``."""
+        return b"".join(self.chunks(k))
+
+
+@dataclass
 class Input:
     """What ``user_input()`` and ``exec_com()`` make of K reads (``Roster.input_many``).  ``kind[k]`` is IAC, EMPTY,
     REPEAT, UNKNOWN, SPEECH or COMMAND; ``com[k]`` the command (enum np_com) of a SPEECH or COMMAND read, else -1;
@@ -641,6 +742,10 @@ def _load():
         lib.nd_roster_tell.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int64, P, P, P, P, P, ctypes.c_int,
                                        P, P, P, P, P, P, P, P, P, P, P, P, ctypes.POINTER(_RosterTiming)]
         lib.nd_roster_tell.restype = ctypes.c_int
+        lib.nd_roster_look_rooms.argtypes = [ctypes.c_int, ctypes.c_int]
+        lib.nd_roster_look_rooms.restype = ctypes.c_int
+        lib.nd_roster_look.argtypes = [ctypes.c_int, ctypes.c_int, P, P, ctypes.c_int] + [P] * 18 + [ctypes.POINTER(_RosterTiming)]
+        lib.nd_roster_look.restype = ctypes.c_int
         lib.nd_arena.restype = P
         lib.nd_write_sizes.restype = P
         _LIB = lib
@@ -779,6 +884,29 @@ def _afk_mesg(v) -> bytes:
     return v
 
 
+def _limited_text(what: str, v, most: int) -> bytes:
+    """A talker string of at most ``most`` bytes: bytes or str, one byte per character, no NUL."""
+    v = _as_bytes(what, v)
+    if len(v) > most or b"\0" in v:
+        raise ValueError(f"{what} must be 0 .. {most} bytes without a NUL, not {v!r}")
+    return v
+
+
+def _one_or_each(what: str, v, n: int, conv, scalar) -> list:
+    """``v`` as one converted value per entry: itself n times when ``scalar(v)``, else a sequence of n."""
+    if scalar(v):
+        return [conv(v)] * n
+    if isinstance(v, (str, bytes, bytearray, memoryview)) or not hasattr(v, "__len__"):
+        raise ValueError(f"{what} must be a value or a sequence of one per entry, not {v!r}")
+    if len(v) != n:
+        raise ValueError(f"{what}: {len(v)} values for {n} entries")
+    return [conv(x) for x in v]
+
+
+_is_text = lambda v: isinstance(v, (str, bytes, bytearray, memoryview))
+_is_number = lambda v: isinstance(v, (int, np.integer, bool, np.bool_))
+
+
 #: the commands speak_many answers, and whether their room line goes to the speaker's room (and is recorded there)
 _SPEECH_COMS = {COM_SAY: True, COM_SHOUT: False, COM_EMOTE: True, COM_SEMOTE: False}
 
@@ -805,13 +933,15 @@ class Roster:
                                                      for t, rm, s, fl, com in bs])
     """
 
-    def __init__(self, capacity: int, review_rooms: int = 0, revtell: bool = False):
+    def __init__(self, capacity: int, review_rooms: int = 0, revtell: bool = False, look_rooms: int = 0):
         if not _is_int(capacity, 1, MAX_CAPACITY):
             raise ValueError(f"roster capacity must be an int in [1, {MAX_CAPACITY}], not {capacity!r}")
         if not _is_int(review_rooms, 0, MAX_REVIEW_ROOMS):
             raise ValueError(f"review_rooms must be an int in [0, {MAX_REVIEW_ROOMS}], not {review_rooms!r}")
         if not isinstance(revtell, (bool, np.bool_)):
             raise ValueError(f"revtell must be a bool, not {revtell!r}")
+        if not _is_int(look_rooms, 0, MAX_LOOK_ROOMS):
+            raise ValueError(f"look_rooms must be an int in [0, {MAX_LOOK_ROOMS}], not {look_rooms!r}")
         self.capacity = int(capacity)
         self.review_rooms = int(review_rooms)
         self.revtell = bool(revtell)
@@ -840,6 +970,17 @@ class Roster:
         # its length at byte AFK_MESG_LEN.  Only tell_many uploads it, after an update of afk_mesg
         self._afk = np.zeros((self.capacity, _AFK_ROW), dtype=np.uint8)
         self._afk_dirty = True
+        # what look_many alone reads and uploads: the room table -- a 256-byte record per look room, then an 816-byte
+        # description row per look room (the fields are listed in fanout.hip's look section) -- after set_rooms, and the
+        # users' descriptions, 32 bytes per slot -- 30 of description padded with zeros, then its length -- after
+        # update(desc=)
+        self.look_rooms = int(look_rooms)
+        self._rooms = np.zeros(self.look_rooms * (_ROOM_REC + _ROOM_DESC_ROW), dtype=np.uint8)
+        self._room_rec = self._rooms[:self.look_rooms * _ROOM_REC].reshape(self.look_rooms, _ROOM_REC)
+        self._room_desc = self._rooms[self.look_rooms * _ROOM_REC:].reshape(self.look_rooms, _ROOM_DESC_ROW)
+        self._rooms_dirty = True
+        self._udesc = np.zeros((self.capacity, _DESC_ROW), dtype=np.uint8)
+        self._udesc_dirty = True
         self._handle = None
         self._closed = False
 
@@ -871,7 +1012,7 @@ class Roster:
 
     def update(self, slots, *, room=_KEEP, login=_KEEP, ignall=_KEEP, ignshout=_KEEP, colour=_KEEP, name=_KEEP,
                vis=_KEEP, muzzled=_KEEP, command_mode=_KEEP, level=_KEEP, afk=_KEEP, igntell=_KEEP,
-               afk_mesg=_KEEP) -> None:
+               afk_mesg=_KEEP, desc=_KEEP) -> None:
         """Set fields of ``slots`` (a slot or a sequence of them).  Each field given is one value for every slot or a
         sequence of one per slot; a field not given stays as it is.  ``room`` is None (no room) or an int in
         [0, ROOM_LIMIT); the flags are 0/1 or bools.  A slot given more than once takes its last values.  Nothing
@@ -888,7 +1029,10 @@ class Roster:
         empty at first) are what :meth:`tell_many` reads of a **target**: a read that comes from an AFK slot remains
         the caller's business.  The two flags live in the speaker mirror's flags byte, with a dirty flag of their
         own; the messages in a mirror of their own.  Only ``tell_many`` uploads after an update of these three alone:
-        no other call copies more for it."""
+        no other call copies more for it.
+
+        ``desc`` (bytes or str of 0 .. USER_DESC_LEN bytes, no NUL, empty at first) is ``user->desc``, which ``look()``
+        shows beside a name.  It lives in a mirror of its own that only :meth:`look_many` uploads."""
         self._check_open()
         if isinstance(slots, (int, np.integer)):
             slots = [slots]
@@ -935,6 +1079,9 @@ class Roster:
                 raise ValueError(f"afk_mesg: {len(afk_mesg)} values for {n} slots")
             else:
                 mesgs = [_afk_mesg(x) for x in afk_mesg]
+        descs = None
+        if desc is not _KEEP:
+            descs = _one_or_each("desc", desc, n, lambda x: _limited_text("desc", x, USER_DESC_LEN), _is_text)
         _, last = np.unique(idx[::-1], return_index=True)        # each slot's last position: last write wins
         keep = n - 1 - last
         at = idx[keep]
@@ -959,11 +1106,18 @@ class Roster:
                 self._afk[j, :len(mesgs[p])] = np.frombuffer(mesgs[p], dtype=np.uint8)
                 self._afk[j, AFK_MESG_LEN] = len(mesgs[p])
             self._afk_dirty = True
+        if descs is not None:
+            for j, p in zip(at.tolist(), keep.tolist()):
+                self._udesc[j] = 0
+                self._udesc[j, :len(descs[p])] = np.frombuffer(descs[p], dtype=np.uint8)
+                self._udesc[j, USER_DESC_LEN] = len(descs[p])
+            self._udesc_dirty = True
         if names is not None or levels is not None or speech.keys() - {"afk", "igntell"}:
             self._speech_dirty = True
         if speech.keys() & {"afk", "igntell"}:
             self._private_dirty = True
-        if rooms is not None or flags or not (names is not None or speech or levels is not None or mesgs is not None):
+        if rooms is not None or flags or not (names is not None or speech or levels is not None or mesgs is not None
+                                              or descs is not None):
             self._dirty = True
 
     def table(self, rm, sender) -> np.ndarray:
@@ -1094,7 +1248,8 @@ class Roster:
         if self._handle is None:
             h = _check(lib.nd_roster_create(self.capacity), "cannot create a device roster")
             if ((self.review_rooms and lib.nd_roster_review_rooms(h, self.review_rooms) != 0)
-                    or (self.revtell and lib.nd_roster_revtell_rings(h) != 0)):
+                    or (self.revtell and lib.nd_roster_revtell_rings(h) != 0)
+                    or (self.look_rooms and lib.nd_roster_look_rooms(h, self.look_rooms) != 0)):
                 lib.nd_roster_destroy(h)
                 raise RuntimeError(f"cannot create a device roster: {lib.nd_last_error().decode(errors='replace')}")
             self._handle = h
@@ -1470,6 +1625,206 @@ class Roster:
                       timing=dict(timing)) for i in (0, 1)]
         return Private(outcome=outcome, target=target, told=plans[0], reply=plans[1], texts=ctext, text_starts=tstarts,
                        text_sizes=clen.astype(np.int64), timing=timing)
+
+    def _look_room(self, v) -> int:
+        if not _is_int(v, 0, self.look_rooms - 1):
+            raise ValueError(f"room {v!r} has no room record: " + (f"the look rooms are 0 .. {self.look_rooms - 1}"
+                             if self.look_rooms else "the roster has none (look_rooms is 0)"))
+        return int(v)
+
+    def set_rooms(self, rooms, *, name=_KEEP, access=_KEEP, desc=_KEEP, links=_KEEP, topic=_KEEP, mesg_cnt=_KEEP,
+                  netlink=_KEEP) -> None:
+        """Set fields of the room records of ``rooms`` (a look room or a sequence of them), by the conventions of
+        :meth:`update`: each field given is one value for every room or a sequence of one per room, a field not given
+        stays as it is, a room given more than once takes its last values, and nothing changes unless the whole call
+        is valid (``ValueError("room N: ...")`` names the first bad entry's position).  Like ``update`` it does not touch
+        the device; only :meth:`look_many` uploads the room table.
+
+        ``name`` is at most ROOM_NAME_LEN bytes, ``access`` PUBLIC, PRIVATE, FIXED_PUBLIC or FIXED_PRIVATE (0 .. 3),
+        ``desc`` at most ROOM_DESC_LEN bytes and may hold newlines, ``links`` at most MAX_LINKS look rooms in the order
+        ``look()`` lists them (one list of ints is one value for every room), ``topic`` at most TOPIC_LEN bytes (empty:
+        none set), ``mesg_cnt`` the board's message count in [0, 2^31), and ``netlink`` None, or ``(service, allow_in)``
+        for a room whose netlink is UP: a service name of at most SERV_NAME_LEN bytes and whether the link allows
+        incoming users only (nuts333.c:3966-3970).  The texts are bytes or str, one byte per character, without a NUL."""
+        self._check_open()
+        if isinstance(rooms, (int, np.integer)):
+            rooms = [rooms]
+        if isinstance(rooms, (str, bytes, bytearray)) or not hasattr(rooms, "__len__"):
+            raise ValueError(f"rooms must be a look room or a sequence of them, not {rooms!r}")
+        idx = np.array([self._look_room(v) for v in rooms], dtype=np.int64)
+        n = len(idx)
+
+        def numbered(what, v, conv, scalar):
+            """As _one_or_each, a bad entry reported by its position."""
+            if scalar(v):
+                try:
+                    return [conv(v)] * n
+                except ValueError as e:
+                    raise ValueError(f"room 0: {e}") from None
+            if _is_text(v) or not hasattr(v, "__len__"):
+                raise ValueError(f"{what} must be a value or a sequence of one per room, not {v!r}")
+            if len(v) != n:
+                raise ValueError(f"{what}: {len(v)} values for {n} rooms")
+            out = []
+            for i, x in enumerate(v):
+                try:
+                    out.append(conv(x))
+                except ValueError as e:
+                    raise ValueError(f"room {i}: {e}") from None
+            return out
+
+        def access_of(v):
+            if not _is_int(v, 0, 3):
+                raise ValueError(f"access must be PUBLIC, PRIVATE, FIXED_PUBLIC or FIXED_PRIVATE (0 .. 3), not {v!r}")
+            return int(v)
+
+        def links_of(v):
+            if _is_text(v) or not hasattr(v, "__len__") or len(v) > MAX_LINKS:
+                raise ValueError(f"links must be a sequence of at most {MAX_LINKS} look rooms, not {v!r}")
+            return [self._look_room(x) for x in v]
+
+        def count_of(v):
+            if not _is_int(v, 0, 2**31 - 1):
+                raise ValueError(f"mesg_cnt must be an int in [0, 2^31), not {v!r}")
+            return int(v)
+
+        def netlink_of(v):
+            if v is None:
+                return None
+            if not isinstance(v, tuple) or len(v) != 2 or not isinstance(v[1], (bool, np.bool_)):
+                raise ValueError(f"netlink must be None or a (service, allow_in: bool) tuple, not {v!r}")
+            return _limited_text("netlink service", v[0], SERV_NAME_LEN), bool(v[1])
+
+        text_of = lambda what, most: (lambda v: _limited_text(what, v, most))
+        new = {}
+        for what, v, conv, scalar in (
+                ("name", name, text_of("name", ROOM_NAME_LEN), _is_text), ("access", access, access_of, _is_number),
+                ("desc", desc, text_of("desc", ROOM_DESC_LEN), _is_text),
+                ("links", links, links_of, lambda v: hasattr(v, "__len__") and not _is_text(v) and all(_is_number(x) for x in v)),
+                ("topic", topic, text_of("topic", TOPIC_LEN), _is_text), ("mesg_cnt", mesg_cnt, count_of, _is_number),
+                ("netlink", netlink, netlink_of, lambda v: v is None or (isinstance(v, tuple) and len(v) == 2 and _is_text(v[0])))):
+            if v is not _KEEP:
+                new[what] = numbered(what, v, conv, scalar)
+        rec, rows = self._room_rec, self._room_desc
+
+        def put(row, at, text, len_at, most):
+            row[at:at + most] = 0
+            row[at:at + len(text)] = np.frombuffer(text, dtype=np.uint8)
+            row[len_at] = len(text)
+
+        for p, j in enumerate(idx.tolist()):                  # in order: the last value wins
+            if "name" in new:
+                put(rec[j], 0, new["name"][p], 20, ROOM_NAME_LEN)
+            if "access" in new:
+                rec[j, 21] = new["access"][p]
+            if "links" in new:
+                rec[j, 22] = len(new["links"][p])
+                rec[j, 32:72] = 0
+                rec[j, 32:32 + 4 * len(new["links"][p])] = np.array(new["links"][p], dtype="<i4").view(np.uint8)
+            if "topic" in new:
+                put(rec[j], 72, new["topic"][p], 23, TOPIC_LEN)
+            if "netlink" in new:
+                link = new["netlink"][p]
+                put(rec[j], 132, link[0] if link else b"", 25, SERV_NAME_LEN)
+                rec[j, 24] = (1 | (2 if link[1] else 0)) if link else 0
+            if "mesg_cnt" in new:
+                rec[j, 28:32] = np.array([new["mesg_cnt"][p]], dtype="<i4").view(np.uint8)
+            if "desc" in new:
+                rows[j] = 0
+                rows[j, :len(new["desc"][p])] = np.frombuffer(new["desc"][p], dtype=np.uint8)
+                rec[j, 26:28] = np.array([len(new["desc"][p])], dtype="<u2").view(np.uint8)
+        if new and n:
+            self._rooms_dirty = True
+
+    def look_many(self, slots) -> Look:
+        """What ``look()`` writes for each of ``slots``, K >= 1 lookers (duplicates allowed), in one device call
+        (nuts333.c:3942-4004).  Each looker needs a room with a room record, one in ``[0, look_rooms)``; otherwise the
+        call raises ``ValueError("look N: ...")`` before the device is touched.  The ``login`` flag is not consulted:
+        ``connect_user`` looks while it is still set.  The looker's level and colour are those in the roster.
+
+        For looker ``u`` in room ``rm`` the :class:`Look` holds, in order, what these ``write_user`` calls send, each
+        string transduced on its own with ``u``'s colour flag (an empty string, and the trailing reset with colour on,
+        are writes too): ``"\\n~FTRoom: ~FR|~FG<name>\\n\\n"``; the room's ``desc``; the exits -- the links with ``~FR`` /
+        ``~FG`` by each linked room's ``access & PRIVATE``, then the netlink's service with ``*`` (``~FR`` when
+        ``allow_in``), ``"\\n~FTThere are no exits."`` when there is neither --; ``"~FTYou can see:\\n"`` and a line per
+        member, or ``"~FTYou are all alone here.\\n"``; ``"\\n"``; the access sentence with the board's message count;
+        the topic, or ``"No topic has been set yet.\\n"``.  A member is a slot ``j != u``, ascending, with ``room[j] ==
+        rm``, a name, and ``vis[j] or level[j] <= level[u]``; its line is ``"      %s %s~RS  %s\\n"`` of name, desc and
+        ``~BR(AFK)`` or nothing, ``"     ~FR*~RS%s %s~RS  %s\\n"`` when it is invisible.  A slot without a name is not a
+        user, as in :meth:`tell_many`: the talker's user list holds no such entry.  ``login`` slots of the room are
+        listed, as the reference lists them once they have a room.
+
+        One upload (the table, the speaker state, the room table and the descriptions only after an update of theirs),
+        two kernel launches (nuts_roster_look, nuts_roster_speak_plan), one download at the bound size and one
+        synchronise, whatever K and the capacity.  The bound counts a line per slot of the call's distinct rooms and a
+        member per such slot and looker; a call whose variant bound exceeds MANY_ARENA_CAP is refused.
+
+        Out of scope: clones and remote users in the list, ``.go`` and ``.who``."""
+        self._check_open()
+        if isinstance(slots, (str, bytes, bytearray)) or not hasattr(slots, "__len__"):
+            raise ValueError(f"slots must be a sequence of slots, not {slots!r}")
+        if len(slots) == 0:
+            raise ValueError("empty call: no lookers")
+        if len(slots) * self.capacity >= 2**31 - 1:
+            raise ValueError(f"{len(slots)} looks at {self.capacity} slots: K x capacity must be below 2^31 - 1")
+        lookers, room_index, rooms = [], [], {}
+        for k, v in enumerate(slots):
+            try:
+                u = self._slot(v)
+                if not 0 <= self._room[u] < self.look_rooms:
+                    raise ValueError(f"the looker, slot {u}, is in " + (f"room {int(self._room[u])}, which has no room record"
+                                     if self._room[u] >= 0 else "no room") + f" (look_rooms is {self.look_rooms})")
+            except ValueError as e:
+                raise ValueError(f"look {k}: {e}") from None
+            lookers.append(u)
+            room_index.append(rooms.setdefault(int(self._room[u]), len(rooms)))
+        k, nr = len(lookers), len(rooms)
+        rms = np.array(list(rooms), dtype=np.int32)
+        population = np.array([int((self._room == rm).sum()) for rm in rooms], dtype=np.int64)
+        line_off = _offsets(population, np.int64, total=True)
+        lroom = np.array(room_index, dtype=np.int32)
+        m_off = _offsets(population[lroom], np.int64, total=True)
+        nl, nm = int(line_off[-1]), int(m_off[-1])
+        texts = 5 * nr + 3 + nl
+        ctext_bytes = _LOOK_STRIDE * nr + _LOOK_FIXED_STRIDE + _LINE_ROW * nl
+        bound = _variant_at(ctext_bytes, texts) + 8 * nm
+        if bound > MANY_ARENA_CAP:
+            raise ValueError(f"call too large: its variant and member bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
+                             f"(MANY_ARENA_CAP): split it")
+        lib = _load()
+        handle = self._device_handle(lib)
+        slot_arr = np.array(lookers, dtype=np.int32)
+        line_off32, m_off32 = line_off.astype(np.int32), m_off.astype(np.int32)
+        nmem, nline = np.empty(k, dtype=np.int32), np.empty(nr, dtype=np.int32)
+        clen = np.empty(texts, dtype=np.int32)
+        vn, vw = np.empty((texts, 2), dtype=np.int64), np.empty((texts, 2), dtype=np.int32)
+        vwsz = np.empty((texts, 2, MAX_WRITES), dtype=np.int32)
+        ctext = np.empty(ctext_bytes, dtype=np.uint8)
+        var = np.empty(_variant_at(ctext_bytes, texts), dtype=np.uint8)
+        members, mline = np.empty(max(nm, 1), dtype=np.int32), np.empty(max(nm, 1), dtype=np.int32)
+        line_slot = np.full(max(nl, 1), -1, dtype=np.int32)
+        t = _RosterTiming()
+        rc = lib.nd_roster_look(handle, k, _ptr(slot_arr), _ptr(lroom), nr, _ptr(rms), _ptr(line_off32), _ptr(m_off32),
+                                _ptr(self._table) if self._dirty else None,
+                                _ptr(self._speech) if self._speech_dirty or self._private_dirty else None,
+                                _ptr(self._rooms) if self._rooms_dirty else None,
+                                _ptr(self._udesc) if self._udesc_dirty else None, _ptr(nmem), _ptr(nline), _ptr(clen),
+                                _ptr(vn), _ptr(vw), _ptr(vwsz), _ptr(ctext), _ptr(var), _ptr(members), _ptr(mline),
+                                _ptr(line_slot), ctypes.byref(t))
+        _check(rc, "device look failed")
+        self._dirty = self._speech_dirty = self._private_dirty = self._rooms_dirty = self._udesc_dirty = False
+        tstarts = np.concatenate([
+            (_LOOK_STRIDE * np.arange(nr, dtype=np.int64)[:, None] + np.array(_LOOK_TEXT_AT, dtype=np.int64)).ravel(),
+            _LOOK_STRIDE * nr + np.array(_LOOK_FIXED_AT, dtype=np.int64),
+            _LOOK_STRIDE * nr + _LOOK_FIXED_STRIDE + _LINE_ROW * np.arange(nl, dtype=np.int64)])
+        for i in range(nr):                                     # the lines past a room's count are nobody's
+            line_slot[int(line_off[i]) + int(nline[i]):int(line_off[i + 1])] = -1
+        return Look(slots=slot_arr, colour=((self._flags[slot_arr] & ROSTER_FLAGS["colour"]) != 0).astype(np.uint8),
+                    room_index=lroom, rooms=rms, member_slots=members[:nm], member_lines=mline[:nm],
+                    member_starts=m_off[:-1].copy(), member_counts=nmem, line_slots=line_slot[:nl], texts=ctext,
+                    text_starts=tstarts, text_sizes=clen.astype(np.int64), variants=var,
+                    variant_starts=_variant_starts(tstarts, clen), variant_sizes=vn, write_counts=vw, write_sizes=vwsz,
+                    timing=_timing_of(t))
 
     def _tell_clear_sent(self) -> None:
         self._tell_clear[:] = 0

@@ -26,6 +26,9 @@
 // composed texts as nuts_roster_plan would (their section below).  nuts_roster_parse frames and dispatches client reads in
 // front of them, and nuts_roster_tell answers the private speech commands, tell() and pemote(), a block per event with
 // get_user() parallel over the roster's slots; the slots' revtell rings are roster_record / roster_review at 5 lines.
+// nuts_roster_look answers look() for K lookers as texts and lists: the five texts of every distinct room, a line per user
+// of those rooms, and per looker the users it is shown, by blocks that walk the roster's slots; nuts_roster_speak_plan
+// then gives every text its two variants (its section below).
 //
 // Hard bounds per item of a text of len < 2000 bytes: 6*len + 4 output bytes (a '\n' with colour
 // on is the costliest input byte, plus the trailing reset) and 16 writes.  The host sizes its buffers
@@ -1683,6 +1686,320 @@ static_assert(kAfkRec % 4 == 0 && kAfkMesgLen < kAfkRec, "roster_tell: an AFK me
 static_assert(kArrSize - 1 + kTellSlack < kTextSize, "nuts_roster_speak_plan: a composed private text fits its LDS text");
 static_assert(kNameLen + 22 + 1 <= 64, "compose: the pieces of the longest notice fit a wave");
 
+// ------------------------------------------------------------------ look() of a resident roster
+//
+// look() (nuts333.c:3942-4004) sends a user its room: five texts that depend on the room alone -- the name, the
+// description, the exits, the access sentence with the board's message count, the topic -- and between the third and the
+// fourth "You can see:" and one line per user it can see there, or "You are all alone here.", then "\n".  A user's line
+// depends on that user alone (name, description, visible or not, AFK); who is listed depends on both: every user of the
+// room in list order, here the slots in ascending order, but the looker itself, a slot without a name, and an invisible
+// user above the looker's level.  So a call has, like a delivery plan, texts with two variants each and per looker a
+// list of them: the five texts of every distinct room, the three fixed ones, and one line per named slot of those rooms,
+// each transduced once however many lookers list it.
+// A roster with look_rooms > 0 keeps two more tables for it, like the speaker state in device allocations of their own
+// that never move: a room table, one 256-byte record per room and then one 816-byte description row per room, and 32
+// bytes of description per slot.
+//   room record   0 name[20] | 20 its length | 21 access (PUBLIC 0, PRIVATE 1, FIXED_PUBLIC 2, FIXED_PRIVATE 3) |
+//                 22 links | 23 the topic's length | 24 netlink (bit 0: a link that is UP, bit 1: allow == IN) |
+//                 25 the service's length | 26 the description's length, 2 bytes | 28 mesg_cnt, 4 bytes |
+//                 32 link[10], 4 bytes each | 72 topic[60] | 132 service[80] | 212 zeros
+//   desc row      0 desc[810] | zeros
+//   slot row      0 desc[30] | 30 its length | 31 zero
+//   look     nuts_roster_look, one launch whose blocks take roles by their index:
+//            ROOM BLOCKS, one per distinct room of the call.  Wave 0 composes the five room texts with compose() into the
+//            room's five slots of the composed-text buffer (36, 812, 352, 96 and 80 bytes wide, their longest forms), the
+//            exits link by link, and the digits of mesg_cnt a lane each; the first room's also the three fixed texts.
+//            Then the block walks the roster, lane l of wave w on slot 256 i + 64 w + l in step i: a slot of the room
+//            that has a name is a candidate, and its rank among the room's candidates -- a ballot per wave, the four
+//            waves' counts through LDS, a carry over the steps -- is its line's number.  The lane composes the line (at
+//            most 69 bytes) into that line's 72-byte slot of the buffer, whole: a description ending in '/' makes the ~RS
+//            after it literal, so the transducer has to see the line as one text.  The host, which knows each room's
+//            population, gives every room its range of lines; the lines of the range that no candidate took are void.
+//            LOOKER BLOCKS, one per looker, walk the roster the same way: the same candidate ranks, and a second ballot
+//            for the candidates this looker is shown.  Looker b's members -- the slot and its line -- go to
+//            members[m_off[b] ..] and mline[m_off[b] ..] in slot order, the count to nmem[b].  No atomics anywhere:
+//            the same result on every run.
+//            COPY BLOCKS past those copy freshly uploaded tables into the kept allocations.
+//   plan     nuts_roster_speak_plan with no room lines (k = 0), a block per text: both variants and their writes.
+//            The transducer is not called from nuts_roster_look: inlined into a loop over the slots it leaves the
+//            compiler too few scalar registers, and the kernels here are built without spills.
+constexpr int kRoomRec = 256, kRoomDescRow = 816, kUserDescRow = 32;
+constexpr int kRoomRow = kRoomRec + kRoomDescRow;          // a room's bytes in the room table
+constexpr int kRoomNameLen = 20, kRoomDescLen = 810, kTopicLen = 60, kMaxLinks = 10, kServNameLen = 80, kUserDescLen = 30;
+constexpr int kRrNameLen = 20, kRrAccess = 21, kRrLinks = 22, kRrTopicLen = 23, kRrNet = 24, kRrServLen = 25, kRrDescLen = 26,
+              kRrMesgCnt = 28, kRrLink = 32, kRrTopic = 72, kRrServ = 132;
+constexpr int kMaxLookRooms = 1024;
+constexpr int kLookTexts = 5;                              // the room texts: name, description, exits, access, topic
+constexpr int kLookTextStride = 1376;                      // a room's five slots in the composed-text buffer
+constexpr int look_text_at(int i) { return i == 0 ? 0 : i == 1 ? 36 : i == 2 ? 848 : i == 3 ? 1200 : 1296; }
+constexpr int look_text_cap(int i) { return (i == 4 ? kLookTextStride : look_text_at(i + 1)) - look_text_at(i); }
+constexpr int kLookFixed = 3;                              // "You can see:", "You are all alone here.", "\n"
+constexpr int kLookFixedStride = 48;                       // their slots: 16, 28 and 4 bytes
+constexpr int look_fixed_at(int i) { return i == 0 ? 0 : i == 1 ? 16 : 44; }
+constexpr int kLineRow = 72;                               // a member line's slot: the longest line is 69 bytes
+
+// The composed-text buffer of a look call over nr rooms and nl lines: the rooms' texts, the fixed ones, the lines.
+constexpr int64_t look_ctext_bytes(int64_t nr, int64_t nl) { return nr * kLookTextStride + kLookFixedStride + nl * kLineRow; }
+
+struct LookArgs {
+    const int32_t* room;         // [capacity] the roster's table: -1, no room
+    const uint8_t* speech;       // [capacity * 16] the speaker state this call reads: the upload, or the kept table
+    const uint8_t* speech_new;   // the upload when there is one, to be copied to speech_keep; else nullptr
+    uint8_t* speech_keep;
+    const uint8_t* rooms;        // [look_rooms * 256] the room records, then [look_rooms * 816] the descriptions; likewise
+    const uint8_t* rooms_new;
+    uint8_t* rooms_keep;
+    const uint8_t* udesc;        // [capacity * 32] the users' descriptions, likewise
+    const uint8_t* udesc_new;
+    uint8_t* udesc_keep;
+    const int32_t* slot;         // [k] the lookers
+    const int32_t* lroom;        // [k] their rooms, as indices into rms
+    const int32_t* rms;          // [nr] the distinct rooms of the call
+    const int32_t* line_off;     // [nr + 1] room i owns lines line_off[i] .. line_off[i + 1] - 1
+    const int32_t* m_off;        // [k + 1] looker b owns members m_off[b] .. m_off[b + 1] - 1
+    const int32_t* ctext_off;    // [5 nr + 3 + nl] where each text's slot starts in ctext
+    int k, nr, capacity, look_rooms;
+    int* violations;             // texts past their slots, lines and members past their ranges (zeroed by the host's upload)
+    int32_t* nmem;               // [k] the members listed
+    int32_t* nline;              // [nr] the lines composed
+    int32_t* clen;               // [5 nr + 3 + nl] the texts' lengths; -1: a line nobody took
+    uint8_t* ctext;              // the texts
+    int32_t* members;            // the listed slots, looker by looker
+    int32_t* mline;              // and their lines
+    int32_t* line_slot;          // [nl] the slot each line is of
+};
+// One more compose() behind what a text already holds: at is its length so far, or -1 after a violation.
+__device__ __forceinline__ void append(uint8_t* dst, int cap, int& at, const Piece (&pc)[5], const uint8_t* body, int blen,
+                                       bool newline, int lane, int* violations)
+{
+    if (at < 0) return;
+    const int n = compose(dst + at, cap - at, pc, body, blen, newline, lane, violations);
+    at = n < 0 ? -1 : at + n;
+}
+
+// The five texts of room a.rms[r], by one wave.
+__device__ void look_room(const LookArgs& a, int r, int lane)
+{
+    const int rm = a.rms[r];
+    const uint8_t* rec = a.rooms + (size_t)rm * kRoomRec;
+    const uint8_t* desc = a.rooms + (size_t)a.look_rooms * kRoomRec + (size_t)rm * kRoomDescRow;
+    const Piece none{nullptr, 0};
+    const int nlen = rec[kRrNameLen] < kRoomNameLen ? rec[kRrNameLen] : kRoomNameLen;
+    const int access = rec[kRrAccess] & 3, nlinks = rec[kRrLinks] < kMaxLinks ? rec[kRrLinks] : kMaxLinks;
+    const int tlen = rec[kRrTopicLen] < kTopicLen ? rec[kRrTopicLen] : kTopicLen;
+    const int net = rec[kRrNet], slen = rec[kRrServLen] < kServNameLen ? rec[kRrServLen] : kServNameLen;
+    const int dl = rec[kRrDescLen] | rec[kRrDescLen + 1] << 8, dlen = dl < kRoomDescLen ? dl : kRoomDescLen;
+    const int32_t cnt = *reinterpret_cast<const int32_t*>(rec + kRrMesgCnt);
+    const int32_t* at = a.ctext_off + kLookTexts * r;
+    int32_t* clen = a.clen + kLookTexts * r;
+    {   // c:3952-3955
+        int len = 0;
+        const Piece p[5] = {lit("\n~FTRoom: "), (access & 1) ? lit("~FR") : lit("~FG"), Piece{rec, nlen}, lit("\n\n"), none};
+        append(a.ctext + at[0], look_text_cap(0), len, p, nullptr, 0, false, lane, a.violations);
+        if (lane == 0) clen[0] = len;
+        len = 0;
+        const Piece q[5] = {none, none, none, none, none};
+        append(a.ctext + at[1], look_text_cap(1), len, q, desc, dlen, false, lane, a.violations);
+        if (lane == 0) clen[1] = len;
+    }
+    {   // c:3956-3973
+        uint8_t* t = a.ctext + at[2];
+        int len = 0;
+        int exits = 0;
+        const Piece head[5] = {lit("\n~FTExits are:"), none, none, none, none};
+        append(t, look_text_cap(2), len, head, nullptr, 0, false, lane, a.violations);
+        for (int i = 0; i < nlinks; i++) {
+            const int32_t l = *reinterpret_cast<const int32_t*>(rec + kRrLink + 4 * i);
+            if (l < 0 || l >= a.look_rooms) {           // the host has checked them: never past the table
+                if (lane == 0) atomicAdd(a.violations, 1);
+                len = -1;
+                break;
+            }
+            const uint8_t* lrec = a.rooms + (size_t)l * kRoomRec;
+            const int ll = lrec[kRrNameLen] < kRoomNameLen ? lrec[kRrNameLen] : kRoomNameLen;
+            const Piece p[5] = {(lrec[kRrAccess] & 1) ? lit("  ~FR") : lit("  ~FG"), none, none, none, none};
+            append(t, look_text_cap(2), len, p, lrec, ll, false, lane, a.violations);
+            exits++;
+        }
+        if (net & 1) {
+            const Piece p[5] = {(net & 2) ? lit("  ~FR") : lit("  ~FG"), none, none, none, none};
+            append(t, look_text_cap(2), len, p, rec + kRrServ, slen, false, lane, a.violations);
+            const Piece star[5] = {lit("*"), none, none, none, none};
+            append(t, look_text_cap(2), len, star, nullptr, 0, false, lane, a.violations);
+        } else if (!exits && len >= 0) {
+            len = 0;
+            const Piece p[5] = {lit("\n~FTThere are no exits."), none, none, none, none};
+            append(t, look_text_cap(2), len, p, nullptr, 0, false, lane, a.violations);
+        }
+        const Piece tail[5] = {lit("\n\n"), none, none, none, none};
+        append(t, look_text_cap(2), len, tail, nullptr, 0, false, lane, a.violations);
+        if (lane == 0) clen[2] = len;
+    }
+    {   // c:3988-3997
+        const Piece how = access == 0 ? lit("set to ~FGPUBLIC~RS") : access == 1 ? lit("set to ~FRPRIVATE~RS")
+                          : access == 2 ? lit("~FRfixed~RS to ~FGPUBLIC~RS") : lit("~FRfixed~RS to ~FRPRIVATE~RS");
+        uint8_t* t = a.ctext + at[3];
+        int len = 0;
+        const Piece p[5] = {lit("Access is "), how, lit(" and there are ~OL~FM"), none, none};
+        append(t, look_text_cap(3), len, p, nullptr, 0, false, lane, a.violations);
+        const uint32_t v = cnt > 0 ? (uint32_t)cnt : 0u;   // %d: a lane per digit
+        int digits = 1;
+        for (uint32_t x = v; x >= 10; x /= 10) digits++;
+        if (len >= 0 && len + digits <= look_text_cap(3)) {
+            uint32_t x = v;
+            for (int i = digits - 1; i > lane; i--) x /= 10;
+            if (lane < digits) t[len + lane] = (uint8_t)('0' + x % 10);
+            len += digits;
+        } else {
+            len = -1;
+        }
+        const Piece q[5] = {lit("~RS messages on the board.\n"), none, none, none, none};
+        append(t, look_text_cap(3), len, q, nullptr, 0, false, lane, a.violations);
+        if (lane == 0) clen[3] = len;
+    }
+    {   // c:3998-4003
+        const Piece p[5] = {tlen ? lit("Current topic: ") : lit("No topic has been set yet.\n"), none, none, none, none};
+        int len = 0;
+        append(a.ctext + at[4], look_text_cap(4), len, p, rec + kRrTopic, tlen, tlen != 0, lane, a.violations);
+        if (lane == 0) clen[4] = len;
+    }
+    if (r == 0) {   // c:3979, 3985, 3986: the same for every room
+        const int32_t* fat = a.ctext_off + kLookTexts * a.nr;
+        int32_t* flen = a.clen + kLookTexts * a.nr;
+#pragma unroll
+        for (int i = 0; i < kLookFixed; i++) {
+            const Piece p[5] = {i == 0 ? lit("~FTYou can see:\n") : i == 1 ? lit("~FTYou are all alone here.\n") : lit("\n"), none,
+                                none, none, none};
+            int len = 0;
+            append(a.ctext + fat[i], i == 0 ? 16 : i == 1 ? 28 : 4, len, p, nullptr, 0, false, lane, a.violations);
+            if (lane == 0) flen[i] = len;
+        }
+    }
+}
+
+template <int N>
+__device__ __forceinline__ int row_lit(uint8_t* row, int pos, const char (&s)[N])
+{
+#pragma unroll
+    for (int i = 0; i < N - 1; i++) row[pos + i] = (uint8_t)s[i];
+    return pos + N - 1;
+}
+
+// Slot j's line (c:3980-3983) into row, by one lane; returns its length.
+__device__ __forceinline__ int look_line(uint8_t* row, const uint4 rec, int nlen, const uint8_t* udesc, int j)
+{
+    const uint32_t state = rec.w >> 8 & 0xff;
+    const uint4 d0 = reinterpret_cast<const uint4*>(udesc)[2 * j], d1 = reinterpret_cast<const uint4*>(udesc)[2 * j + 1];
+    const int dl = (int)(d1.w >> 16 & 0xff), dlen = dl < kUserDescLen ? dl : kUserDescLen;
+    int len = (state & kVis) ? row_lit(row, 0, "      ") : row_lit(row, 0, "     ~FR*~RS");
+#pragma unroll
+    for (int i = 0; i < kNameLen; i++) {                       // all twelve: what follows overwrites the padding
+        const uint32_t v = i < 4 ? rec.x : i < 8 ? rec.y : rec.z;
+        row[len + i] = (uint8_t)(v >> (8 * (i & 3)));
+    }
+    len += nlen;
+    row[len++] = ' ';
+#pragma unroll
+    for (int i = 0; i < kUserDescLen; i++) {                   // likewise
+        const uint32_t v = i < 4 ? d0.x : i < 8 ? d0.y : i < 12 ? d0.z : i < 16 ? d0.w : i < 20 ? d1.x : i < 24 ? d1.y
+                           : i < 28 ? d1.z : d1.w;
+        row[len + i] = (uint8_t)(v >> (8 * (i & 3)));
+    }
+    len += dlen;
+    len = row_lit(row, len, "~RS  ");
+    if (state & kAfk) len = row_lit(row, len, "~BR(AFK)");
+    row[len++] = '\n';
+    return len;
+}
+
+__device__ void roster_look(const LookArgs& a)
+{
+    __shared__ int s_cand[kBlock / 64], s_seen[kBlock / 64];
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    if ((int)blockIdx.x >= a.nr + a.k) {    // the tables just uploaded, into the kept allocations: a word per lane
+        const int sw = a.speech_new ? a.capacity * (kSpeechRec / 4) : 0, rw = a.rooms_new ? a.look_rooms * (kRoomRow / 4) : 0;
+        const int dw = a.udesc_new ? a.capacity * (kUserDescRow / 4) : 0;
+        const int w = ((int)blockIdx.x - a.nr - a.k) * kBlock + (int)threadIdx.x;
+        if (w < sw) reinterpret_cast<uint32_t*>(a.speech_keep)[w] = reinterpret_cast<const uint32_t*>(a.speech_new)[w];
+        else if (w - sw < rw) reinterpret_cast<uint32_t*>(a.rooms_keep)[w - sw] = reinterpret_cast<const uint32_t*>(a.rooms_new)[w - sw];
+        else if (w - sw - rw < dw)
+            reinterpret_cast<uint32_t*>(a.udesc_keep)[w - sw - rw] = reinterpret_cast<const uint32_t*>(a.udesc_new)[w - sw - rw];
+        return;
+    }
+    const bool looker = (int)blockIdx.x >= a.nr;                // block-uniform
+    const int b = looker ? (int)blockIdx.x - a.nr : (int)blockIdx.x;
+    if (!looker && wave == 0) look_room(a, b, lane);
+    const int r = looker ? a.lroom[b] : b, rm = a.rms[r];
+    const int u = looker ? a.slot[b] : -1;
+    const int ulevel = looker ? a.speech[(size_t)u * kSpeechRec + kLevelByte] : 0;
+    const int line0 = a.line_off[r], lines = a.line_off[r + 1] - line0;     // the room's lines
+    const int m0 = looker ? a.m_off[b] : 0, mcap = looker ? a.m_off[b + 1] - m0 : 0;
+    const int text0 = kLookTexts * a.nr + kLookFixed;           // the first line's text
+    int cands = 0, seen = 0;                                    // the carries: candidates, and those this looker is shown
+    for (int base = 0; base < a.capacity; base += kBlock) {     // block-uniform
+        const int j = base + (int)threadIdx.x;
+        bool cand = false, shown = false;
+        uint4 rec{};
+        int nlen = 0;
+        if (j < a.capacity && a.room[j] == rm) {
+            rec = reinterpret_cast<const uint4*>(a.speech)[j];
+            nlen = (int)(rec.w & 0xff) < kNameLen ? (int)(rec.w & 0xff) : kNameLen;
+            cand = nlen > 0;                                    // a slot without a name is no user
+            shown = cand && j != u && ((rec.w >> 8 & kVis) || (int)(rec.w >> 16 & 0xff) <= ulevel);    // c:3977
+        }
+        const uint64_t bc = __ballot(cand), bs = __ballot(shown);
+        if (lane == 0) {
+            s_cand[wave] = __popcll((unsigned long long)bc);
+            s_seen[wave] = __popcll((unsigned long long)bs);
+        }
+        __syncthreads();
+        const uint64_t below = (1ull << lane) - 1;
+        int crank = cands + __popcll((unsigned long long)(bc & below)), srank = seen + __popcll((unsigned long long)(bs & below));
+#pragma unroll
+        for (int x = 0; x < kBlock / 64; x++) {
+            if (x < wave) {
+                crank += s_cand[x];
+                srank += s_seen[x];
+            }
+            cands += s_cand[x];
+            seen += s_seen[x];
+        }
+        __syncthreads();                    // the next step overwrites the counts
+        if (!looker && cand) {
+            if (crank < lines) {
+                const int t = text0 + line0 + crank;
+                a.clen[t] = look_line(a.ctext + a.ctext_off[t], rec, nlen, a.udesc, j);
+                a.line_slot[line0 + crank] = j;
+            } else {
+                atomicAdd(a.violations, 1);
+            }
+        }
+        if (looker && shown) {
+            if (srank < mcap && crank < lines) {
+                a.members[m0 + srank] = j;
+                a.mline[m0 + srank] = line0 + crank;
+            } else {
+                atomicAdd(a.violations, 1);
+            }
+        }
+    }
+    if (looker) {
+        if (threadIdx.x == 0) a.nmem[b] = seen < mcap ? seen : mcap;
+        return;
+    }
+    for (int i = cands + (int)threadIdx.x; i < lines; i += kBlock) a.clen[text0 + line0 + i] = -1;    // nobody's lines
+    if (threadIdx.x == 0) a.nline[b] = cands < lines ? cands : lines;
+}
+
+static_assert(6 + 6 + kNameLen + 1 + kUserDescLen + 5 + 8 + 1 <= kLineRow, "roster_look: the longest member line fits its slot");
+static_assert(6 + 6 + kNameLen + 1 + 32 <= kLineRow, "roster_look: the whole description row may be stored before it is cut");
+static_assert(kRoomRow % 4 == 0 && kUserDescRow % 4 == 0 && kRrServ + kServNameLen <= kRoomRec, "roster_look: whole words");
+static_assert(look_text_cap(0) >= 13 + kRoomNameLen + 2 && look_text_cap(1) >= kRoomDescLen &&
+              look_text_cap(2) >= 14 + kMaxLinks * (5 + kRoomNameLen) + 5 + kServNameLen + 1 + 2 &&
+              look_text_cap(3) >= 10 + 28 + 21 + 10 + 27 && look_text_cap(4) >= 15 + kTopicLen + 1,
+              "roster_look: every room text fits its slot");
+static_assert(kLookTextStride < kTextSize, "nuts_roster_speak_plan: a room text fits its LDS text");
+
 }  // namespace
 
 // Stable, unmangled kernel names (they are what rocprofv3 reports).
@@ -1703,6 +2020,7 @@ extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_parse(ParseArgs
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_tell(TellArgs a) { roster_tell(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_record_tell(RecordArgs a) { roster_record<kTellLines>(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_revtell(ReviewArgs a) { roster_review<kTellLines>(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_look(LookArgs a) { roster_look(a); }
 
 // ------------------------------------------------------------------------------------------ host library
 
@@ -1934,6 +2252,9 @@ struct Roster {
     bool revtell = false;        // every slot owns a revtell ring
     uint8_t* tell_rings = nullptr;   // the revtell rings, then their cursors: as rings
     uint8_t* afk = nullptr;      // the AFK messages, 64 bytes per slot: as speech, made by the first nd_roster_tell
+    int look_rooms = 0;          // rooms 0 .. look_rooms - 1 own a room record
+    uint8_t* room_table = nullptr;   // their records, then their descriptions: as speech, made by the first nd_roster_look
+    uint8_t* udesc = nullptr;    // the users' descriptions, 32 bytes per slot: likewise
 };
 Roster g_rosters[kMaxRosters];
 
@@ -2144,6 +2465,44 @@ size_t layout_tell(uintptr_t base, size_t text_bytes, size_t clear_bytes, TellAr
     take(s.flags, k);
     p.room = s.room;
     p.slot = s.slotf;
+    p.text = s.ctext;
+    p.text_off = s.ctext_off;
+    p.text_len = s.clen;
+    p.violations = s.violations;
+    return take.at;
+}
+
+// nd_roster_look's layout of a roster's allocation, after layout_tell's pattern: the table, the uploads of the speaker
+// table, of the room table and of the users' descriptions (which the kept ones are filled from), the call's inputs ending
+// with violations, then the results next to each other: the counts, the texts and their variants, the lookers' members.
+size_t layout_look(uintptr_t base, size_t members, size_t nl, LookArgs& s, SpeakPlanArgs& p)
+{
+    Carver take{base};
+    const size_t k = (size_t)s.k, nr = (size_t)s.nr, cap = (size_t)s.capacity, t = kLookTexts * nr + kLookFixed + nl;
+    const size_t ctext_bytes = (size_t)look_ctext_bytes((int64_t)nr, (int64_t)nl);
+    take_table(take, s.capacity, s.room, p.slot);
+    take(s.speech_new, cap * kSpeechRec);
+    take(s.rooms_new, (size_t)s.look_rooms * kRoomRow);
+    take(s.udesc_new, cap * kUserDescRow);
+    take(s.slot, k);
+    take(s.lroom, k);
+    take(s.rms, nr);
+    take(s.line_off, nr + 1);
+    take(s.m_off, k + 1);
+    take(s.ctext_off, t);
+    take(s.violations, 1);
+    take(s.nmem, k);
+    take(s.nline, nr);
+    take(s.clen, t);
+    take(p.vn, 2 * t);
+    take(p.vw, 2 * t);
+    take(p.vwsz, 2 * t * kMaxWrites);
+    take(s.members, members);
+    take(s.mline, members);
+    take(s.line_slot, nl);
+    take(s.ctext, ctext_bytes);
+    take(p.var, (size_t)var_at((int64_t)ctext_bytes, (int64_t)t));
+    p.room = s.room;
     p.text = s.ctext;
     p.text_off = s.ctext_off;
     p.text_len = s.clen;
@@ -2462,6 +2821,8 @@ int nd_roster_destroy(int handle)
     if (r->tell_rings) (void)hipFree(r->tell_rings);
     if (r->speech) (void)hipFree(r->speech);
     if (r->afk) (void)hipFree(r->afk);
+    if (r->room_table) (void)hipFree(r->room_table);
+    if (r->udesc) (void)hipFree(r->udesc);
     if (r->mirror) (void)hipHostFree(r->mirror);
     *r = Roster{};
     return 0;
@@ -3128,6 +3489,165 @@ int nd_roster_tell(int handle, int k, const uint8_t* text, int64_t text_bytes, c
     memcpy(vn, res(po.vn), 4 * (size_t)k * sizeof(int64_t));
     memcpy(vw, res(po.vw), 4 * (size_t)k * sizeof(int32_t));
     memcpy(vwsz, res(po.vwsz), 4 * (size_t)k * kMaxWrites * sizeof(int32_t));
+    memcpy(ctext, res(so.ctext), ctext_bytes);
+    memcpy(var, res(po.var), var_bytes);
+
+    return fill_timing(timing, t0, t1, in_bytes - from, res_bytes);
+}
+
+// Give roster `handle` room records for rooms 0 .. n - 1 (0 .. 1024); before its first nd_roster_look, which allocates
+// them.  Returns 0, or -1 with nd_last_error() set.
+int nd_roster_look_rooms(int handle, int n)
+{
+    Roster* r = roster_at(handle);
+    if (!r) return -1;
+    if (n < 0 || n > kMaxLookRooms || r->room_table) {
+        snprintf(g_err, sizeof(g_err), "look rooms %d outside 0 .. %d, or the room table is already in use", n, kMaxLookRooms);
+        return -1;
+    }
+    r->look_rooms = n;
+    return 0;
+}
+
+// What look() writes for the k lookers slots[] of roster `handle` (duplicates allowed), each in a room below the roster's
+// look rooms, as texts and lists.  rms[nr] are the distinct rooms of the lookers and lroom[k] each looker's room as an index
+// into rms; line_off[nr + 1] gives room i its range of lines, as many as it has slots, and m_off[k + 1] looker b its
+// range of members, as many as its room has slots (both from 0, not decreasing: the caller counts the slots).  table and
+// speech as nd_roster_tell's; rooms is NULL when no room changed since the last nd_roster_look of this roster, else all
+// of them: a 256-byte record per look room, then an 816-byte description row per look room; udesc likewise the users'
+// descriptions, 32 bytes per slot (30 of description padded with zeros, then its length); the roster's first call must
+// give both.  The layouts are those of the look section above.
+// The texts, T = 5 nr + 3 + nl of them with nl = line_off[nr]: text 5 i + j is text j (name, description, exits, access,
+// topic) of room rms[i], at 1376 i + (0, 36, 848, 1200, 1296)[j] of ctext; texts 5 nr .. 5 nr + 2 are "You can see:", "You
+// are all alone here." and the newline, at 1376 nr + (0, 16, 44); text 5 nr + 3 + l is line l, at 1376 nr + 48 + 72 l.
+// Outputs (host, caller-allocated): nmem[k] the members listed for looker b, their slots at members[m_off[b] ..] and
+// their lines at mline[m_off[b] ..]; nline[nr] the lines composed for room i, line_off[i] onwards, and line_slot[nl] the
+// slot each is of; clen[T] (-1: a line nobody took), ctext[1376 nr + 48 + 72 nl]; vn[2T], vw[2T], vwsz[2T * 16] and
+// var[12 * ctext bytes + 16 T] as nd_roster_speak's.
+// Per call, whatever k and the capacity: one upload, two kernels (nuts_roster_look, nuts_roster_speak_plan), one download
+// at the bound size, one synchronise.  Returns 0, or -1 with nd_last_error() set.
+int nd_roster_look(int handle, int k, const int32_t* slots, const int32_t* lroom, int nr, const int32_t* rms,
+                   const int32_t* line_off, const int32_t* m_off, const uint8_t* table, const uint8_t* speech,
+                   const uint8_t* rooms, const uint8_t* udesc, int32_t* nmem, int32_t* nline, int32_t* clen, int64_t* vn,
+                   int32_t* vw, int32_t* vwsz, uint8_t* ctext, uint8_t* var, int32_t* members, int32_t* mline,
+                   int32_t* line_slot, nd_roster_timing* timing)
+{
+    Roster* r = roster_at(handle);
+    if (!r || ensure_ready()) return -1;
+    const int cap = r->capacity, nrooms = r->look_rooms;
+    if (k < 1 || nr < 1 || nr > k || nr > nrooms || (int64_t)k * cap >= INT32_MAX) {
+        snprintf(g_err, sizeof(g_err), "%d lookers in %d rooms of %d slots and %d look rooms: need 1 <= rooms <= lookers, "
+                 "k * capacity < 2^31 - 1", k, nr, cap, nrooms);
+        return -1;
+    }
+    if (line_off[0] || m_off[0]) {
+        snprintf(g_err, sizeof(g_err), "the rooms' lines and the lookers' members must start at 0");
+        return -1;
+    }
+    for (int b = 0; b < k; b++)          // the kernels index by these: nothing out of range reaches them
+        if (slots[b] < 0 || slots[b] >= cap || lroom[b] < 0 || lroom[b] >= nr || m_off[b + 1] < m_off[b]) {
+            snprintf(g_err, sizeof(g_err), "look %d: slot, room or members out of range", b);
+            return -1;
+        }
+    for (int i = 0; i < nr; i++)
+        if (rms[i] < 0 || rms[i] >= nrooms || line_off[i + 1] < line_off[i] || line_off[i + 1] > cap * (i + 1)) {
+            snprintf(g_err, sizeof(g_err), "room %d of the call: no look room (0 .. %d), or its lines out of range", rms[i], nrooms - 1);
+            return -1;
+        }
+    if ((!r->speech && !speech) || (!r->room_table && !rooms) || (!r->udesc && !udesc)) {
+        snprintf(g_err, sizeof(g_err), "the roster's first look call must give the speaker table, the room table and the descriptions");
+        return -1;
+    }
+    if (ensure_kept(&r->speech, (size_t)cap * kSpeechRec, "speaker table")) return -1;
+    if (ensure_kept(&r->room_table, (size_t)nrooms * kRoomRow, "room table")) return -1;
+    if (ensure_kept(&r->udesc, (size_t)cap * kUserDescRow, "user descriptions")) return -1;
+    const double t0 = now_ns();
+    hipStream_t st = g.stream;
+    LookArgs s{};
+    SpeakPlanArgs p{};                  // k = 0, tiles = 0: no room lines, a block per text
+    s.k = k;
+    s.nr = nr;
+    s.capacity = p.capacity = cap;
+    s.look_rooms = nrooms;
+    const size_t nm = (size_t)m_off[k], nl = (size_t)line_off[nr];
+    const size_t texts = (size_t)kLookTexts * nr + kLookFixed + nl, ctext_bytes = (size_t)look_ctext_bytes(nr, (int64_t)nl);
+    const size_t var_bytes = (size_t)var_at((int64_t)ctext_bytes, (int64_t)texts);
+    LookArgs so = s;                    // offsets of every array in the roster's allocation
+    SpeakPlanArgs po = p;
+    const size_t need = layout_look(0, nm, nl, so, po);
+    const size_t table_bytes = (uintptr_t)so.speech_new, rooms_at = (uintptr_t)so.rooms_new, udesc_at = (uintptr_t)so.udesc_new;
+    const size_t tables_end = (uintptr_t)so.slot, in_bytes = (uintptr_t)so.violations + sizeof(int);
+    const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
+    if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
+    if (table) new_table(*r, so.room, po.slot, table);
+    const int32_t* room_of = reinterpret_cast<const int32_t*>(r->mirror + (uintptr_t)so.room);
+    for (int b = 0; b < k; b++)
+        if (room_of[slots[b]] != rms[lroom[b]]) {
+            snprintf(g_err, sizeof(g_err), "look %d: the looker is in room %d, not in room %d", b, room_of[slots[b]], rms[lroom[b]]);
+            return -1;
+        }
+    if (grow_roster(*r, need)) return -1;
+    layout_look((uintptr_t)r->d, nm, nl, s, p);
+    if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
+
+    uint8_t* h = r->mirror;
+    const Put put{h};
+    if (speech) put(so.speech_new, speech, (size_t)cap * kSpeechRec);
+    if (rooms) put(so.rooms_new, rooms, (size_t)nrooms * kRoomRow);
+    if (udesc) put(so.udesc_new, udesc, (size_t)cap * kUserDescRow);
+    put(so.slot, slots, (size_t)k * sizeof(int32_t));
+    put(so.lroom, lroom, (size_t)k * sizeof(int32_t));
+    put(so.rms, rms, (size_t)nr * sizeof(int32_t));
+    put(so.line_off, line_off, ((size_t)nr + 1) * sizeof(int32_t));
+    put(so.m_off, m_off, ((size_t)k + 1) * sizeof(int32_t));
+    int32_t* coff = reinterpret_cast<int32_t*>(h + (uintptr_t)so.ctext_off);
+    for (int i = 0; i < nr; i++)
+        for (int j = 0; j < kLookTexts; j++) coff[kLookTexts * i + j] = i * kLookTextStride + look_text_at(j);
+    for (int j = 0; j < kLookFixed; j++) coff[kLookTexts * nr + j] = nr * kLookTextStride + look_fixed_at(j);
+    for (size_t l = 0; l < nl; l++)
+        coff[kLookTexts * nr + kLookFixed + l] = (int32_t)(nr * kLookTextStride + kLookFixedStride + l * kLineRow);
+    *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
+    // the tables' uploads lie between the table and the inputs: what lies after the first one that changed travels too,
+    // but the kernel is told of the changed ones alone, so the mirror's bytes of the others need not be current
+    const size_t from = !r->resident ? 0 : speech ? table_bytes : rooms ? rooms_at : udesc ? udesc_at : tables_end;
+    ND_CHECK(hipMemcpyAsync(r->d + from, h + from, in_bytes - from, hipMemcpyHostToDevice, st));
+    r->resident = true;
+    s.speech = speech ? s.speech_new : r->speech;
+    s.rooms = rooms ? s.rooms_new : r->room_table;
+    s.udesc = udesc ? s.udesc_new : r->udesc;
+    if (!speech) s.speech_new = nullptr;
+    if (!rooms) s.rooms_new = nullptr;
+    if (!udesc) s.udesc_new = nullptr;
+    s.speech_keep = r->speech;
+    s.rooms_keep = r->room_table;
+    s.udesc_keep = r->udesc;
+
+    const size_t copy_words = (speech ? (size_t)cap * (kSpeechRec / 4) : 0) + (rooms ? (size_t)nrooms * (kRoomRow / 4) : 0) +
+                              (udesc ? (size_t)cap * (kUserDescRow / 4) : 0);
+    ND_CHECK(hipEventRecord(g.ev0, st));
+    hipLaunchKernelGGL(nuts_roster_look, dim3((unsigned)(nr + k + (copy_words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, s);
+    ND_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)texts), dim3(kBlock), 0, st, p);
+    ND_CHECK(hipGetLastError());
+    if (fetch_results(r->d, res_at, res_bytes)) return -1;
+    const double t1 = now_ns();
+
+    const Res res{gm.res, res_at};
+    const int violations = *reinterpret_cast<const int*>(res(so.violations));
+    if (violations) {
+        snprintf(g_err, sizeof(g_err), "%d text(s) exceeded the hard bounds (a room text its slot, a room its lines, a looker its "
+                 "members; 6*len+4 bytes, %d writes transduced)", violations, kMaxWrites);
+        return -1;
+    }
+    memcpy(nmem, res(so.nmem), (size_t)k * sizeof(int32_t));
+    memcpy(nline, res(so.nline), (size_t)nr * sizeof(int32_t));
+    memcpy(clen, res(so.clen), texts * sizeof(int32_t));
+    memcpy(vn, res(po.vn), 2 * texts * sizeof(int64_t));
+    memcpy(vw, res(po.vw), 2 * texts * sizeof(int32_t));
+    memcpy(vwsz, res(po.vwsz), 2 * texts * kMaxWrites * sizeof(int32_t));
+    memcpy(members, res(so.members), nm * sizeof(int32_t));
+    memcpy(mline, res(so.mline), nm * sizeof(int32_t));
+    memcpy(line_slot, res(so.line_slot), nl * sizeof(int32_t));
     memcpy(ctext, res(so.ctext), ctext_bytes);
     memcpy(var, res(po.var), var_bytes);
 

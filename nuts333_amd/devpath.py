@@ -2,7 +2,7 @@
 
     python -m nuts333_amd.devpath [--reps R] [--warmup W] [--pathbench-iterations I] [--per-call K[,K...]]
                                   [--roster K[,K...]] [--plan K[,K...]] [--review Q[,Q...]] [--speak K[,K...]]
-                                  [--input K[,K...]] [--tell K[,K...]]                        -> one JSON line
+                                  [--input K[,K...]] [--tell K[,K...]] [--look K[,K...]]                      -> one JSON line
 
 For N in {10, 100, 1000} listeners, the two texts oracle/pathbench.c times (``say``; ``shout`` carrying ``~OL``/``~RS``)
 and colour all-off / all-on / half, one ``nuts333_amd.device.broadcast`` per repetition (listener 0 is the sender, the
@@ -63,6 +63,12 @@ of K says of the same bodies: the three times and the copy volume of both, and t
 slots for every tell.  There is no C restatement of ``get_user`` or ``tell()`` to time beside it:
 ``cpu_derived_estimate_us`` is 2 x K x pathbench's ``format_line_once_ns``, the two formats alone, an estimate and not
 the talker's cost of a tell.  The first call of each case is checked against the reference's two formats.
+
+``--look K[,K...]`` adds ``look``: a 1000-slot roster spread over 5 rooms, 200 users a room, and K looks (slots 0 .. K - 1)
+per ``Roster.look_many`` call: the three times and the copy volume, beside ``cpu_us``, the CPU restatement's transducer
+(``nuts_path``, through ctypes) over the strings ``look()`` composes for the same lookers.  The strings are composed
+beforehand, so ``cpu_us`` leaves the CPU's composing out (``look_cpu_us_covers`` says so).  The first call of each case is
+checked against that transducer over those strings.
 """
 from __future__ import annotations
 
@@ -549,6 +555,85 @@ def tell_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
             "tell": cases}
 
 
+LOOK_ROOMS = (b"drive", b"hallway", b"wizroom", b"corridor", b"lounge")
+
+
+def look_strings(n: int, slot: int) -> list[bytes]:
+    """What look() hands to write_user for ``slot`` of the roster ``look_cases`` builds: n slots spread over the five
+    rooms, slot j in room j % 5, every user visible, of one level and not AFK, each room linked to the next."""
+    rm = slot % len(LOOK_ROOMS)
+    nxt = (rm + 1) % len(LOOK_ROOMS)
+    lines = [b"      User%d is user %d~RS  \n" % (j, j) for j in range(rm, n, len(LOOK_ROOMS)) if j != slot]
+    return ([b"\n~FTRoom: ~FG%s\n\n" % LOOK_ROOMS[rm], b"The %s.\nA second line of description.\n" % LOOK_ROOMS[rm],
+             b"\n~FTExits are:  ~FG%s\n\n" % LOOK_ROOMS[nxt]]
+            + ([b"~FTYou can see:\n"] + lines if lines else [b"~FTYou are all alone here.\n"])
+            + [b"\n", b"Access is set to ~FGPUBLIC~RS and there are ~OL~FM%d~RS messages on the board.\n" % rm,
+               b"Current topic: the topic of room %d\n" % rm])
+
+
+def look_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
+    """The ``look`` section: look_many of K lookers (slots 0 .. K - 1) at a 1000-slot roster spread over 5 rooms, 200 users
+    a room, for each colour case and each K, beside the CPU's transducer over the same strings."""
+    n = 1000
+    cases = []
+    for colour in COLOURS:
+        with device.Roster(n, look_rooms=len(LOOK_ROOMS)) as roster:
+            col = listeners(n, colour)[:, device.LISTENER_FIELDS.index("colour")]
+            roster.update(range(n), room=[j % len(LOOK_ROOMS) for j in range(n)], colour=col,
+                          name=[b"User%d" % j for j in range(n)], desc=[b"is user %d" % j for j in range(n)])
+            ids = list(range(len(LOOK_ROOMS)))
+            roster.set_rooms(ids, name=list(LOOK_ROOMS), links=[[(i + 1) % len(ids)] for i in ids], mesg_cnt=ids,
+                             desc=[b"The %s.\nA second line of description.\n" % r for r in LOOK_ROOMS],
+                             topic=[b"the topic of room %d" % i for i in ids])
+            for k in ks:
+                slots = [j % n for j in range(k)]
+                strings = [look_strings(n, j) for j in slots]
+                first = roster.look_many(slots)
+                for i, j in enumerate(slots):
+                    want = [ch for text in strings[i] for ch in nuts_path.chunks(text, int(col[j]))]
+                    if first.chunks(i) != want:
+                        raise SystemExit(f"devpath: look {k}, {colour}: look {i} differs from the CPU's transducer over look()'s strings")
+                timed = {"kernels_us": [], "end_to_end_us": [], "python_us": [], "cpu_us": []}
+                copies = set()
+                for i in range(warmup + reps):
+                    t0 = time.perf_counter()
+                    r = roster.look_many(slots)
+                    t1 = time.perf_counter()
+                    for q, j in enumerate(slots):
+                        c = int(col[j])
+                        for text in strings[q]:
+                            nuts_path.chunks(text, c)
+                    t2 = time.perf_counter()
+                    if i >= warmup:
+                        timed["python_us"].append((t1 - t0) * 1e6)
+                        timed["cpu_us"].append((t2 - t1) * 1e6)
+                        timed["kernels_us"].append(r.timing["kernels_us"])
+                        timed["end_to_end_us"].append(r.timing["end_to_end_us"])
+                        copies.add((r.timing["h2d_bytes"], r.timing["d2h_bytes"]))
+                if len(copies) != 1:
+                    raise SystemExit(f"devpath: look {k}, {colour}: timed calls copied {sorted(copies)} bytes")
+                st = {f: _stats(v) for f, v in timed.items()}
+                h2d, d2h = copies.pop()
+                cases.append({"n": n, "k": k, "colour": colour, "rooms": len({j % len(LOOK_ROOMS) for j in slots}),
+                              "members": sum(len(x) - 7 for x in strings if len(x) > 7),
+                              "bytes_out": sum(len(first.output(i)) for i in range(k)),
+                              "writes": sum(len(first.chunks(i)) for i in range(k)), **st, "h2d_bytes": h2d, "d2h_bytes": d2h,
+                              # three significant digits: the ratio is far below 1 when many lines go through ctypes
+                              "end_to_end_over_cpu": float(f"{st['end_to_end_us']['median'] / st['cpu_us']['median']:.3g}")})
+    return {"look_kernels": ["nuts_roster_look", "nuts_roster_speak_plan"],
+            "look_end_to_end_covers": "packing the K lookers into pinned memory, one H2D (the table, the speaker state, the "
+                                      "room table and the descriptions only in a call after an update of theirs), two "
+                                      "kernels -- the rooms' texts, a line per user of those rooms, every looker's member "
+                                      "list; then both variants of every text --, one D2H at the bound size, one "
+                                      "synchronise (python_us adds checking the lookers, counting the rooms' slots, the "
+                                      "copies out of pinned memory and building the Look; Look.chunks() is not timed)",
+            "look_cpu_us_covers": "np_write_user_stream of the CPU restatement (nuts_path, through ctypes, a call per "
+                                  "string) over the strings look() composes for the K lookers, composed beforehand: this "
+                                  "leaves the CPU's composing out -- the sprintf calls and the walk over the user list "
+                                  "-- and includes a ctypes call per string",
+            "look": cases}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=2000, help="timed broadcasts per case (default 2000)")
@@ -572,6 +657,9 @@ def main(argv=None) -> int:
     ap.add_argument("--tell", type=per_call_counts, default=None, metavar="K[,K...]",
                     help="also time K tells to one target per Roster.tell_many call, for each K, beside speak_many of K "
                          "says of the same bodies (the tell section)")
+    ap.add_argument("--look", type=per_call_counts, default=None, metavar="K[,K...]",
+                    help="also time K looks per Roster.look_many call at a 1000-slot roster spread over 5 rooms, for each "
+                         "K, beside the CPU's transducer over look()'s strings (the look section)")
     a = ap.parse_args(argv)
     if a.reps < 1 or a.warmup < 0:
         ap.error("--reps must be >= 1 and --warmup >= 0")
@@ -654,6 +742,7 @@ def main(argv=None) -> int:
     speak = speak_cases(a.speak, a.reps, a.warmup, pb) if a.speak else {}
     inputs = input_cases(a.input, a.reps, a.warmup, pb) if a.input else {}
     tell = tell_cases(a.tell, a.reps, a.warmup, pb) if a.tell else {}
+    look = look_cases(a.look, a.reps, a.warmup, pb) if a.look else {}
     out = {
         "what": "user-space stage of one broadcast (admit predicate + transducer), device vs CPU",
         "device": "gfx950",
@@ -670,6 +759,7 @@ def main(argv=None) -> int:
         **speak,
         **inputs,
         **tell,
+        **look,
         "wall_s": round(time.perf_counter() - t_start, 1),
     }
     print(json.dumps(out))
