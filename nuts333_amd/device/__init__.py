@@ -50,6 +50,10 @@ name, access, description, links, topic, board count, netlink) and every slot's 
 ``Roster.look_many(slots)`` returns what ``look()`` writes for K lookers (nuts333.c:3942-4004) as a :class:`Look`: the
 texts of the call -- five per distinct room, three fixed ones, a line per user of those rooms -- with their two
 variants, and per looker the users it is shown, in list order.
+``Roster(capacity, look_rooms=R, clones=C)`` also keeps C clone records apart from the slots (``Roster.set_clones``: owner,
+room, ``clone_hear``), and ``Roster.relay_many(broadcasts)`` answers ``write_room_except`` whole for local users
+(nuts333.c:1401-1429): the :class:`Plan` of ``plan_many`` and, per broadcast, which clone records relay it to their owners,
+the relay text ``~FT[ <room name> ]:~RS `` + text and its two variants -- a :class:`Relay`.
 
 Input is validated before the device is touched (``ValueError``).  The library ``_build/libnuts_device.so`` is built by
 ``__graft_entry__.build()`` where ``hipcc`` exists, and on demand here when it is missing or older than its source.
@@ -88,6 +92,8 @@ KERNELS = ("nuts_fanout_measure_broadcast", "nuts_fanout_emit_broadcast",
            "nuts_roster_measure", "nuts_roster_emit", "nuts_roster_plan", "nuts_roster_record", "nuts_roster_review",
            "nuts_roster_speak", "nuts_roster_speak_plan", "nuts_roster_parse",
            "nuts_roster_tell", "nuts_roster_record_tell", "nuts_roster_revtell", "nuts_roster_look")
+#: the kernel relay_many adds to a plan call (it also runs nuts_roster_plan and, over the relay texts, nuts_roster_speak_plan)
+RELAY_KERNELS = ("nuts_roster_relay",)
 #: NP_ARR_SIZE (nuts333.h:19): the input line a speech command receives is at most 999 bytes
 ARR_SIZE = 1000
 #: USER_NAME_LEN (nuts333.h:23) and invisname (nuts333.h:150), the name an invisible speaker is shown by
@@ -177,6 +183,16 @@ MAX_MEMBER_LINE, _LINE_ROW = 69, 72
 _LOOK_TEXT_AT, _LOOK_STRIDE, _LOOK_FIXED_AT, _LOOK_FIXED_STRIDE = (0, 36, 848, 1200, 1296), 1376, (0, 16, 44), 48
 #: the texts of a room in a Look, in look()'s order, and the fixed ones
 LOOK_NAME, LOOK_DESC, LOOK_EXITS, LOOK_ACCESS, LOOK_TOPIC = range(5)
+
+
+#: a clone's ``clone_hear`` (nuts333.h:60-62): it relays nothing, lines that hold a swear word, or everything
+CLONE_HEAR_NOTHING, CLONE_HEAR_SWEARS, CLONE_HEAR_ALL = 0, 1, 2
+#: a look room's row of the names relay_many uploads (kRelayNameRow of fanout.hip): 20 bytes of name padded with zeros, then
+#: its length; and what a relay text is longer than its broadcast at most, ``~FT[ `` + a 20-byte name + `` ]:~RS ``
+#: (kRelaySlack): its slot among a relay call's relay texts is that much wider than the text
+_RELAY_NAME_ROW, _RELAY_SLACK = 24, 32
+#: the relay text's fixed bytes: ``~FT[ `` and `` ]:~RS ``
+RELAY_EXTRA = 12
 
 
 def max_bytes(text_len: int) -> int:
@@ -521,6 +537,68 @@ class Look:
 
 
 @dataclass
+class Relay:
+    """What ``write_room_except`` does with K broadcasts for a roster with clone records (``Roster.relay_many``): ``plan``
+    is the :class:`Plan` of the same broadcasts for the slots, and clone record ``c`` relays broadcast ``k`` iff bit
+    ``c % 64`` of ``relay_bits[k, c // 64]`` is set.  The relay text of broadcast ``k`` is ``relay_text(k)``, with its
+    two variants and their ``write(2)`` chunk sizes as a Plan holds a broadcast's; all of them are empty, 0 bytes in 0
+    writes, when no record relays ``k``.  ``clone_owner`` and ``owner_colour`` are the records' owners (-1: an empty
+    record) and the owners' colour bits when the call was made, from the host mirrors.
+
+    Delivery: for broadcast ``k`` a talker writes ``plan.variant(k, colour of j)`` to every admitted slot ``j``, then, for
+    every record ``c`` of ``relays(k)`` in ascending order, ``relay_variant(k, owner_colour[c])`` to ``clone_owner[c]``."""
+    plan: Plan
+    clones: int
+    relay_bits: np.ndarray        # uint64 [K, CW]  CW = ceil(clones / 64); bits past the records are zero
+    clone_owner: np.ndarray       # int32 [C]       a copy of the records' owners
+    owner_colour: np.ndarray      # uint8 [C]       the owners' colour bits (0 for an empty record)
+    texts: np.ndarray             # uint8, flat: the relay texts; gaps are allowed and unspecified
+    text_starts: np.ndarray       # int64 [K]
+    text_sizes: np.ndarray        # int64 [K]   -1: nothing relays
+    variants: np.ndarray          # uint8, flat
+    variant_starts: np.ndarray    # int64 [K, 2]
+    variant_sizes: np.ndarray     # int64 [K, 2]
+    write_counts: np.ndarray      # int32 [K, 2]
+    write_sizes: np.ndarray       # int32 [K, 2, MAX_WRITES]; entries at or past write_counts are unspecified
+    timing: dict = field(default_factory=dict)   # as Plan's: kernels_us, end_to_end_us, h2d_bytes, d2h_bytes
+
+    def _check(self, k: int, c=0) -> None:
+        if not 0 <= k < len(self.relay_bits) or c not in (0, 1):
+            raise IndexError(f"no relay ({k}, {c}): {len(self.relay_bits)} broadcasts, colour 0 or 1")
+
+    def relays(self, k: int) -> np.ndarray:
+        """The clone records that relay broadcast ``k``, ascending."""
+        self._check(k)
+        return np.flatnonzero(_unpack(self.relay_bits[k], self.clones))
+
+    def owners(self, k: int) -> np.ndarray:
+        """The slots the relay of broadcast ``k`` is written to, one per record of ``relays(k)`` and in its order; an
+        owner of two relaying records is there twice."""
+        return self.clone_owner[self.relays(k)]
+
+    def owner_colours(self, k: int) -> np.ndarray:
+        """The colour bits of ``owners(k)``."""
+        return self.owner_colour[self.relays(k)]
+
+    def relay_text(self, k: int) -> bytes:
+        """``b"~FT[ " + room name + b" ]:~RS " + text`` of broadcast ``k``; ``b""`` when nothing relays it."""
+        self._check(k)
+        at, n = int(self.text_starts[k]), int(self.text_sizes[k])
+        return self.texts[at:at + n].tobytes() if n >= 0 else b""
+
+    def relay_variant(self, k: int, c: int) -> bytes:
+        """The bytes an owner with colour bit ``c`` gets of broadcast ``k``."""
+        self._check(k, c)
+        at = int(self.variant_starts[k, c])
+        return self.variants[at:at + int(self.variant_sizes[k, c])].tobytes()
+
+    def relay_chunks(self, k: int, c: int) -> list[bytes]:
+        """``relay_variant(k, c)`` as the list of ``write(2)`` chunks the reference would issue."""
+        return _split(self.relay_variant(k, c), self.write_sizes[k, c, :int(self.write_counts[k, c])],
+                      f"relay ({k}, {c})", "the variant")
+
+
+@dataclass
 class Input:
     """What ``user_input()`` and ``exec_com()`` make of K reads (``Roster.input_many``).  ``kind[k]`` is IAC, EMPTY,
     REPEAT, UNKNOWN, SPEECH or COMMAND; ``com[k]`` the command (enum np_com) of a SPEECH or COMMAND read, else -1;
@@ -746,6 +824,12 @@ def _load():
         lib.nd_roster_look_rooms.restype = ctypes.c_int
         lib.nd_roster_look.argtypes = [ctypes.c_int, ctypes.c_int, P, P, ctypes.c_int] + [P] * 18 + [ctypes.POINTER(_RosterTiming)]
         lib.nd_roster_look.restype = ctypes.c_int
+        lib.nd_roster_clones.argtypes = [ctypes.c_int, ctypes.c_int]
+        lib.nd_roster_clones.restype = ctypes.c_int
+        lib.nd_roster_relay.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int64] + [P] * 22 + [ctypes.POINTER(_RosterTiming)]
+        lib.nd_roster_relay.restype = ctypes.c_int
+        lib.nd_roster_relay_record.argtypes = lib.nd_roster_relay.argtypes + [P]
+        lib.nd_roster_relay_record.restype = ctypes.c_int
         lib.nd_arena.restype = P
         lib.nd_write_sizes.restype = P
         _LIB = lib
@@ -925,6 +1009,8 @@ class Roster:
     first (1,010 bytes per slot in an allocation of its own, 66 MB at MAX_CAPACITY, so it has to be asked for):
     ``tell_many(events, record=True)`` records into them, :meth:`revtell_many` reads them, :meth:`clear_revtell` empties
     them.
+    With ``clones=C`` the roster also has clone records ``0 .. C - 1``, empty at first and kept apart from the slots
+    (:meth:`set_clones`): a clone is not a slot, and only :meth:`relay_many` sees it.
 
     Building and updating a roster does not touch the device; its first call allocates there.  The
     contract, for every call::
@@ -933,7 +1019,7 @@ class Roster:
                                                      for t, rm, s, fl, com in bs])
     """
 
-    def __init__(self, capacity: int, review_rooms: int = 0, revtell: bool = False, look_rooms: int = 0):
+    def __init__(self, capacity: int, review_rooms: int = 0, revtell: bool = False, look_rooms: int = 0, clones: int = 0):
         if not _is_int(capacity, 1, MAX_CAPACITY):
             raise ValueError(f"roster capacity must be an int in [1, {MAX_CAPACITY}], not {capacity!r}")
         if not _is_int(review_rooms, 0, MAX_REVIEW_ROOMS):
@@ -942,6 +1028,8 @@ class Roster:
             raise ValueError(f"revtell must be a bool, not {revtell!r}")
         if not _is_int(look_rooms, 0, MAX_LOOK_ROOMS):
             raise ValueError(f"look_rooms must be an int in [0, {MAX_LOOK_ROOMS}], not {look_rooms!r}")
+        if not _is_int(clones, 0, MAX_CAPACITY):
+            raise ValueError(f"clones must be an int in [0, {MAX_CAPACITY}], not {clones!r}")
         self.capacity = int(capacity)
         self.review_rooms = int(review_rooms)
         self.revtell = bool(revtell)
@@ -981,6 +1069,18 @@ class Roster:
         self._rooms_dirty = True
         self._udesc = np.zeros((self.capacity, _DESC_ROW), dtype=np.uint8)
         self._udesc_dirty = True
+        # what relay_many alone reads and uploads: the clone records, kept apart from the slots -- `clones` int32 owners
+        # (-1: an empty record), then `clones` int32 rooms, then `clones` clone_hear bytes -- after set_clones; and the look
+        # rooms' names, 24 bytes per room, when one differs from those relay_many uploaded last (None: none yet)
+        self.clones = int(clones)
+        self._clones = np.zeros(9 * self.clones, dtype=np.uint8)
+        self._clone_owner = self._clones[:4 * self.clones].view(np.int32)
+        self._clone_room = self._clones[4 * self.clones:8 * self.clones].view(np.int32)
+        self._clone_hear = self._clones[8 * self.clones:]
+        self._clone_owner[:] = -1
+        self._clone_room[:] = -1
+        self._clones_dirty = True
+        self._relay_names = None
         self._handle = None
         self._closed = False
 
@@ -1249,7 +1349,8 @@ class Roster:
             h = _check(lib.nd_roster_create(self.capacity), "cannot create a device roster")
             if ((self.review_rooms and lib.nd_roster_review_rooms(h, self.review_rooms) != 0)
                     or (self.revtell and lib.nd_roster_revtell_rings(h) != 0)
-                    or (self.look_rooms and lib.nd_roster_look_rooms(h, self.look_rooms) != 0)):
+                    or (self.look_rooms and lib.nd_roster_look_rooms(h, self.look_rooms) != 0)
+                    or (self.clones and lib.nd_roster_clones(h, self.clones) != 0)):
                 lib.nd_roster_destroy(h)
                 raise RuntimeError(f"cannot create a device roster: {lib.nd_last_error().decode(errors='replace')}")
             self._handle = h
@@ -1825,6 +1926,185 @@ class Roster:
                     text_starts=tstarts, text_sizes=clen.astype(np.int64), variants=var,
                     variant_starts=_variant_starts(tstarts, clen), variant_sizes=vn, write_counts=vw, write_sizes=vwsz,
                     timing=_timing_of(t))
+
+    def set_clones(self, clones, *, owner=_KEEP, room=_KEEP, hear=_KEEP) -> None:
+        """Set fields of the clone records ``clones`` (a record or a sequence of them, each in ``[0, clones)``), by the
+        conventions of :meth:`update` and :meth:`set_rooms`: each field given is one value for every record or a sequence
+        of one per record, a field not given stays as it is, a record given more than once takes its last values, and
+        nothing changes unless the whole call is valid (``ValueError``).  It does not touch the device; only
+        :meth:`relay_many` uploads the records, after a change.
+
+        ``owner`` is a slot, or None for an empty record: that record's room and ``hear`` are reset with it, whatever
+        else the entry gives.  ``room`` is a room with a room record, one in ``[0, look_rooms)``: the relay needs its name
+        from ``set_rooms(name=)``.  ``hear`` is CLONE_HEAR_NOTHING, CLONE_HEAR_SWEARS or CLONE_HEAR_ALL.  A record given
+        an owner without a ``hear`` starts at CLONE_HEAR_ALL, as ``create_user`` sets it (nuts333.c:2743)."""
+        self._check_open()
+        if isinstance(clones, (int, np.integer)):
+            clones = [clones]
+        if isinstance(clones, (str, bytes, bytearray)) or not hasattr(clones, "__len__"):
+            raise ValueError(f"clones must be a clone record or a sequence of them, not {clones!r}")
+        idx = [self._clone(v) for v in clones]
+        n = len(idx)
+
+        def hear_of(v):
+            if not _is_int(v, CLONE_HEAR_NOTHING, CLONE_HEAR_ALL):
+                raise ValueError(f"hear must be CLONE_HEAR_NOTHING, CLONE_HEAR_SWEARS or CLONE_HEAR_ALL (0 .. 2), not {v!r}")
+            return int(v)
+
+        is_owner = lambda v: v is None or _is_number(v)
+        owners = None if owner is _KEEP else _one_or_each("owner", owner, n, lambda v: -1 if v is None else self._slot(v), is_owner)
+        rooms = None if room is _KEEP else _one_or_each("room", room, n, self._look_room, _is_number)
+        hears = None if hear is _KEEP else _one_or_each("hear", hear, n, hear_of, _is_number)
+        for p, c in enumerate(idx):                           # in order: the last value wins
+            if owners is not None and owners[p] < 0:
+                self._clone_owner[c], self._clone_room[c], self._clone_hear[c] = -1, -1, CLONE_HEAR_NOTHING
+                continue
+            if owners is not None:
+                self._clone_owner[c] = owners[p]
+                self._clone_hear[c] = CLONE_HEAR_ALL
+            if rooms is not None:
+                self._clone_room[c] = rooms[p]
+            if hears is not None:
+                self._clone_hear[c] = hears[p]
+        if n and (owners is not None or rooms is not None or hears is not None):
+            self._clones_dirty = True
+
+    def _clone(self, v) -> int:
+        if not _is_int(v, 0, self.clones - 1):
+            raise ValueError(f"clone record {v!r}: " + (f"the records are 0 .. {self.clones - 1}" if self.clones else
+                             "the roster has none (clones is 0)"))
+        return int(v)
+
+    def _prepare_relay(self, broadcasts, record, clone_sender):
+        """What _prepare_plan returns, the clone senders (-1: none) and the look rooms' names as nd_roster_relay takes
+        them, after every check of relay_many."""
+        if self.clones == 0:
+            raise ValueError("the roster has no clone records (clones is 0): plan_many answers its broadcasts whole")
+        packed = self._prepare_plan(broadcasts, record)
+        lens, rms, senders = packed[2], packed[3], packed[4]
+        k = len(lens)
+        if clone_sender is None:
+            csender = np.full(k, -1, dtype=np.int32)
+        else:
+            if isinstance(clone_sender, (str, bytes, bytearray)) or not hasattr(clone_sender, "__len__"):
+                raise ValueError(f"clone_sender must be None or a sequence of one clone record or None per broadcast, "
+                                 f"not {clone_sender!r}")
+            if len(clone_sender) != k:
+                raise ValueError(f"clone_sender: {len(clone_sender)} values for {k} broadcasts")
+            csender = np.empty(k, dtype=np.int32)
+            for b, v in enumerate(clone_sender):
+                try:
+                    csender[b] = -1 if v is None else self._clone(v)
+                except ValueError as e:
+                    raise ValueError(f"broadcast {b}: clone_sender: {e}") from None
+                if v is not None and senders[b] >= 0:
+                    raise ValueError(f"broadcast {b}: its user is clone record {int(v)}, so its sender must be None, "
+                                     f"not slot {int(senders[b])}")
+        owned = np.flatnonzero(self._clone_owner >= 0)
+        for c in owned.tolist():
+            if not 0 <= self._clone_owner[c] < self.capacity:
+                raise ValueError(f"clone record {c}: its owner, slot {int(self._clone_owner[c])}, is out of range")
+            if not 0 <= self._clone_room[c] < self.look_rooms:
+                raise ValueError(f"clone record {c}: its room" + (f", {int(self._clone_room[c])}," if self._clone_room[c] >= 0
+                                 else "") + f" has no room record (look_rooms is {self.look_rooms}): set_clones(room=)")
+        name_len = self._room_rec[:, ROOM_NAME_LEN].astype(np.int64)
+        cloned = np.zeros(max(self.look_rooms, 1), dtype=bool)       # the rooms that hold a clone record, whatever its hear
+        cloned[self._clone_room[owned]] = True
+        for b in range(k):
+            rm = int(rms[b])
+            if 0 <= rm < self.look_rooms and cloned[rm] and RELAY_EXTRA + int(name_len[rm]) + int(lens[b]) > ARR_SIZE - 1:
+                raise ValueError(f"broadcast {b}: room {rm} holds a clone, and the relay text of its {int(lens[b])} bytes "
+                                 f"and the room's {int(name_len[rm])}-byte name would be "
+                                 f"{RELAY_EXTRA + int(name_len[rm]) + int(lens[b])} bytes: the reference's text2 holds at "
+                                 f"most {ARR_SIZE - 1}")
+        text_bytes = int(lens.sum(dtype=np.int64))
+        bound = _variant_at(text_bytes, k) + _variant_at(_composed_at(text_bytes, k, _RELAY_SLACK), k)
+        if bound > MANY_ARENA_CAP:
+            raise ValueError(f"call too large: its variant bound over the texts and the relay texts is {bound} bytes, the "
+                             f"cap is {MANY_ARENA_CAP} (MANY_ARENA_CAP): split it")
+        names = np.zeros((self.look_rooms, _RELAY_NAME_ROW), dtype=np.uint8)
+        names[:, :ROOM_NAME_LEN + 1] = self._room_rec[:, :ROOM_NAME_LEN + 1]
+        return packed, csender, names
+
+    def relay_many(self, broadcasts, record=None, clone_sender=None) -> Relay:
+        """``write_room_except`` whole for K broadcasts to a roster with clone records, in one device call
+        (nuts333.c:1401-1429).  ``broadcasts`` and ``record`` are what :meth:`plan_many` takes, checked by the same
+        rules; ``clone_sender`` is None, or K entries each None or the clone record that is ``user`` in
+        ``write_room_except(rm, str, user)`` (``clone_switch``, nuts333.c:7283) -- that broadcast's ``sender`` must then
+        be None.  Returns a :class:`Relay`: its ``plan`` equals ``plan_many(broadcasts, record)`` field by field, and
+        the rings end up as after it.
+
+        A clone standing in room ``rm`` does not receive a broadcast, it sends ``"~FT[ <room name> ]:~RS " + text`` to
+        its owner.  Clone record ``c`` relays broadcast ``k`` iff ``rm`` is not None and the record has an owner; its
+        room equals ``rm``; ``c`` is not ``clone_sender[k]``; its ``hear`` is not CLONE_HEAR_NOTHING; the owner's
+        ``ignall`` flag is clear, which ``force_listen`` does not override (nuts333.c:1417); and its ``hear`` is
+        CLONE_HEAR_ALL or the text holds a swear word (``np_contains_swearing``).  ``com_num`` plays no part, and a
+        clone is never ``login``, ``ignall`` or ``ignshout``.
+
+        Delivery: for broadcast ``k`` a talker writes ``plan.variant(k, colour[j])`` to every admitted slot ``j``, then,
+        for every relaying record ``c`` in ascending order, ``relay_variant(k, colour[owner[c]])`` to ``owner[c]``.
+        Direct, then relay, is the reference's order per socket, because a clone is always created after its owner
+        logged in.
+
+        Rejected with ``ValueError`` before the device is touched, with no mirror changed: a roster without clone
+        records; an owned record whose room has no room record or whose owner is no slot; a bad ``clone_sender``; a
+        broadcast to a room that holds a clone record, whatever its ``hear``, whose relay text would not fit the
+        reference's ``text2[ARR_SIZE]``, ``12 + len(name) + len(text) > ARR_SIZE - 1`` (the reference overflows a stack
+        buffer there); and a call whose variant bound over the texts and the relay texts exceeds MANY_ARENA_CAP.
+
+        One upload (the table and the clone records only after an update of theirs, the rooms' names, 24 bytes per look
+        room, only when one changed since the last ``relay_many``), three kernel launches (nuts_roster_plan,
+        nuts_roster_relay, nuts_roster_speak_plan over the relay texts) -- four in a call that records
+        (nuts_roster_record) --, one download at the bound size and one synchronise, whatever K, the capacity and the
+        records.
+
+        Out of scope: ``.clone``, ``.destroy``, ``.switch`` and ``.chear`` themselves -- the caller calls
+        :meth:`set_clones` --, and remote users."""
+        self._check_open()
+        packed, csender, names = self._prepare_relay(broadcasts, record, clone_sender)
+        text, text_off, lens, rm, sender, flags, coms = packed
+        recording = bool((flags & _RECORD_BIT).any())
+        new_names = self._relay_names is None or not np.array_equal(names, self._relay_names)
+        lib = _load()
+        handle = self._device_handle(lib)
+        k, words, cwords = len(lens), (self.capacity + 63) // 64, (self.clones + 63) // 64
+        rtext_bytes = _composed_at(len(text), k, _RELAY_SLACK)
+        bits = np.empty((k, words), dtype=np.uint64)
+        vn, rvn = np.empty((k, 2), dtype=np.int64), np.empty((k, 2), dtype=np.int64)
+        vw, rvw = np.empty((k, 2), dtype=np.int32), np.empty((k, 2), dtype=np.int32)
+        vwsz, rvwsz = np.empty((k, 2, MAX_WRITES), dtype=np.int32), np.empty((k, 2, MAX_WRITES), dtype=np.int32)
+        var = np.empty(_variant_at(len(text), k), dtype=np.uint8)
+        rbits, rlen = np.empty((k, cwords), dtype=np.uint64), np.empty(k, dtype=np.int32)
+        rtext, rvar = np.empty(rtext_bytes, dtype=np.uint8), np.empty(_variant_at(rtext_bytes, k), dtype=np.uint8)
+        tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
+        t = _RosterTiming()
+        args = (handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(rm), _ptr(sender), _ptr(flags),
+                _ptr(coms), _ptr(csender), _ptr(self._table) if self._dirty else None,
+                _ptr(self._clones) if self._clones_dirty else None, _ptr(names) if new_names else None, _ptr(bits),
+                _ptr(vn), _ptr(vw), _ptr(vwsz), _ptr(var), _ptr(rbits), _ptr(rlen), _ptr(rvn), _ptr(rvw), _ptr(rvwsz),
+                _ptr(rtext), _ptr(rvar), ctypes.byref(t))
+        if recording:                       # the pending clears go first, with the same upload
+            clear = self._pending_clear()
+            rc = lib.nd_roster_relay_record(*args, _ptr(clear) if clear is not None else None)
+        else:
+            rc = lib.nd_roster_relay(*args)
+        _check(rc, "device relay failed")
+        self._dirty = self._clones_dirty = False
+        self._relay_names = names
+        if recording:
+            self._clear_sent()
+        timing = _timing_of(t)
+        plan = Plan(capacity=self.capacity, admitted_bits=bits,
+                    colour_bits=_pack((self._flags & ROSTER_FLAGS["colour"]) != 0), variants=var,
+                    variant_starts=_variant_starts(text_off, lens), variant_sizes=vn, write_counts=vw,
+                    write_sizes=vwsz, timing=dict(timing))
+        tstarts = _composed_at(text_off.astype(np.int64), np.arange(k, dtype=np.int64), _RELAY_SLACK)
+        owner = self._clone_owner.copy()
+        colour = np.where(owner >= 0, (self._flags[np.maximum(owner, 0)] & ROSTER_FLAGS["colour"]) != 0, False)
+        return Relay(plan=plan, clones=self.clones, relay_bits=rbits, clone_owner=owner,
+                     owner_colour=colour.astype(np.uint8), texts=rtext, text_starts=tstarts,
+                     text_sizes=rlen.astype(np.int64), variants=rvar, variant_starts=_variant_starts(tstarts, rlen),
+                     variant_sizes=rvn, write_counts=rvw, write_sizes=rvwsz, timing=timing)
 
     def _tell_clear_sent(self) -> None:
         self._tell_clear[:] = 0

@@ -29,6 +29,8 @@
 // nuts_roster_look answers look() for K lookers as texts and lists: the five texts of every distinct room, a line per user
 // of those rooms, and per looker the users it is shown, by blocks that walk the roster's slots; nuts_roster_speak_plan
 // then gives every text its two variants (its section below).
+// nuts_roster_relay answers the clone branch of write_room_except after nuts_roster_plan, in the same call: which of the
+// roster's clone records relay each broadcast to their owners, and the prefixed text they send (its section below).
 //
 // Hard bounds per item of a text of len < 2000 bytes: 6*len + 4 output bytes (a '\n' with colour
 // on is the costliest input byte, plus the trailing reset) and 16 writes.  The host sizes its buffers
@@ -2000,6 +2002,112 @@ static_assert(look_text_cap(0) >= 13 + kRoomNameLen + 2 && look_text_cap(1) >= k
               "roster_look: every room text fits its slot");
 static_assert(kLookTextStride < kTextSize, "nuts_roster_speak_plan: a room text fits its LDS text");
 
+// ------------------------------------------------------------------ the clone relay of a resident roster
+//
+// The clone branch of write_room_except (nuts333.c:1416-1426; clone_relay of oracle/talker_port.c): a clone standing in
+// room rm does not receive a broadcast to rm, it sends "~FT[ <room name> ]:~RS " + str to its owner.  A roster keeps C
+// clone records apart from its slots, in a device allocation of their own that never moves: the owners' slots (int32, -1:
+// an empty record), the rooms (int32) and the clone_hear bytes (0 nothing, 1 swears, 2 all; nuts333.h:60-62), each array in a
+// 256-byte slice; and the look rooms' names, 24 bytes per room: 20 of name padded with zeros, then its length.
+//   relay    nuts_roster_relay after nuts_roster_plan on the same inputs, one block per broadcast.  Wave 0 scans the text
+//            for swearing once (swears).  The block walks the C records a lane per record, 256 at a time: record c relays
+//            broadcast b iff rm[b] >= 0, it has an owner, its room is rm[b], c is not csender[b] (the clone that is `user`
+//            in write_room_except(rm, str, user), -1: none), hear is not 0, the owner's ignall flag is clear
+//            (force_listen does not override it, c:1417), and hear is 2 or the text swears.  A wave's 64 answers are one
+//            word of the relay bitmap (__ballot); lanes past C vote false, so the tail bits are zero.  If any record
+//            relays, wave 0 composes the relay text into the call's relay-text buffer (compose), slot b at rtext_off[b],
+//            len + kRelaySlack bytes wide; a broadcast without relays has length -1.  A relay text that would not fit the
+//            reference's text2[ARR_SIZE] is a violation: the call fails.
+//            Blocks past the broadcasts copy the clone records and the names just uploaded into the kept allocations.
+//   plan     nuts_roster_speak_plan over the K relay texts, a block per text as after nuts_roster_look: stage_variants
+//            gives each its two variants, and a text of length -1 is void, 0 bytes in 0 writes.  Composing and transducing
+//            in one kernel spills scalar registers: store_variants alone takes every one the compiler has.
+constexpr int kRelayNameRow = 24;                          // a look room's row of the relay's name table
+constexpr int kRelaySlack = 5 + kRoomNameLen + 7;          // "~FT[ " + name + " ]:~RS ": a relay text's slot is this much wider
+constexpr uint8_t kHearNothing = 0, kHearAll = 2;          // nuts333.h:60-62, CLONE_HEAR_SWEARS between them
+
+struct RelayArgs {
+    const uint8_t* slot;         // [capacity] the roster's flag bytes: the owners' ignall
+    const uint8_t* records;      // the records this call reads, the upload or the kept ones, as take_clones lays them out
+    const uint8_t* names;        // [look_rooms * kRelayNameRow] likewise
+    const uint32_t* clones_new;  // the uploads when there are any, to be copied to the kept allocations; else nullptr
+    const uint32_t* names_new;
+    uint32_t* clones_keep;
+    uint32_t* names_keep;
+    int clone_words, name_words; // their sizes in words
+    const uint8_t* text;         // the K texts, packed, as PlanArgs
+    const int32_t* text_off;     // [k]
+    const int32_t* text_len;     // [k]
+    const int32_t* rm;           // [k] -1: every room
+    const int32_t* csender;      // [k] the clone record that sends the broadcast; -1: none
+    int k, capacity, clones, cwords, look_rooms;   // cwords: bitmap words per broadcast, ceil(clones / 64)
+    const int32_t* rtext_off;    // [k] where relay text b's slot starts in rtext
+    int* violations;             // relay texts past text2[ARR_SIZE] (zeroed by the host's upload)
+    uint8_t* rtext;              // the relay texts
+    int32_t* rlen;               // [k] their lengths; -1: nothing relays
+    uint64_t* rbits;             // [k * cwords] the relay bitmap
+};
+
+__device__ void roster_relay(const RelayArgs& a)
+{
+    if ((int)blockIdx.x >= a.k) {           // the tables just uploaded, into the kept allocations: a word per lane
+        const int w = ((int)blockIdx.x - a.k) * kBlock + (int)threadIdx.x;
+        const int cw = a.clones_new ? a.clone_words : 0;
+        if (w < cw) a.clones_keep[w] = a.clones_new[w];
+        else if (a.names_new && w - cw < a.name_words) a.names_keep[w - cw] = a.names_new[w - cw];
+        return;
+    }
+    __shared__ int s_swears, s_any;
+    const int b = (int)blockIdx.x, lane = (int)threadIdx.x & 63;
+    const int rm = a.rm[b], len = a.text_len[b], except = a.csender[b];
+    const uint8_t* text = a.text + a.text_off[b];
+    if (threadIdx.x == 0) s_any = 0;
+    if (threadIdx.x < 64) {                 // wave 0, whole: contains_swearing(str), once per broadcast
+        const bool sw = rm >= 0 && len < kArrSize && swears(text, len, lane);
+        if (lane == 0) s_swears = sw;
+    }
+    __syncthreads();
+    const bool sw = s_swears != 0;
+    const size_t slice = ((size_t)a.clones * sizeof(int32_t) + 255) & ~(size_t)255;      // a Carver slice of int32 [clones]
+    const int32_t* owner = reinterpret_cast<const int32_t*>(a.records);                  // -1: an empty record
+    const int32_t* croom = reinterpret_cast<const int32_t*>(a.records + slice);
+    const uint8_t* hear = a.records + 2 * slice;
+    bool any = false;
+    for (int base = 0; base < a.cwords * 64; base += kBlock) {      // block-uniform: every wave votes in every round
+        const int c = base + (int)threadIdx.x;
+        bool in = false;
+        if (c < a.clones && rm >= 0 && rm < a.look_rooms) {
+            const int o = owner[c];
+            const uint8_t h = hear[c];
+            in = o >= 0 && o < a.capacity && croom[c] == rm && c != except && h != kHearNothing &&
+                 !(a.slot[o] & kIgnall) && (h == kHearAll || sw);
+        }
+        const uint64_t word = __ballot(in);
+        const int w = c >> 6;
+        if (lane == 0 && w < a.cwords) a.rbits[(int64_t)b * a.cwords + w] = word;
+        any |= word != 0;
+    }
+    if (any && lane == 0) s_any = 1;
+    __syncthreads();
+    if (!s_any) {                           // block-uniform: nothing is relayed
+        if (threadIdx.x == 0) a.rlen[b] = -1;
+        return;
+    }
+    if (threadIdx.x < 64) {                 // wave 0: sprintf(text2, "~FT[ %s ]:~RS %s", u->room->name, str), c:1424
+        const uint8_t* row = a.names + (size_t)rm * kRelayNameRow;
+        const int nlen = row[kRoomNameLen] < kRoomNameLen ? row[kRoomNameLen] : kRoomNameLen;
+        const Piece none{nullptr, 0};
+        const Piece p[5] = {lit("~FT[ "), Piece{row, nlen}, lit(" ]:~RS "), none, none};
+        const int cap = len + kRelaySlack < kArrSize - 1 ? len + kRelaySlack : kArrSize - 1;   // text2[ARR_SIZE]
+        const int n = compose(a.rtext + a.rtext_off[b], cap, p, text, len, false, lane, a.violations);
+        if (lane == 0) a.rlen[b] = n;
+    }
+}
+
+static_assert(5 + kRoomNameLen + 7 <= 64 && kRelaySlack == 32, "roster_relay: the prefix pieces fit a wave; the slot's slack");
+static_assert(kRelayNameRow % 4 == 0 && kRoomNameLen < kRelayNameRow, "roster_relay: a name row is whole words and holds its length");
+static_assert(kArrSize - 1 < kTextSize, "nuts_roster_speak_plan: a relay text fits its LDS text");
+
 }  // namespace
 
 // Stable, unmangled kernel names (they are what rocprofv3 reports).
@@ -2021,6 +2129,7 @@ extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_tell(TellArgs a
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_record_tell(RecordArgs a) { roster_record<kTellLines>(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_revtell(ReviewArgs a) { roster_review<kTellLines>(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_look(LookArgs a) { roster_look(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_relay(RelayArgs a) { roster_relay(a); }
 
 // ------------------------------------------------------------------------------------------ host library
 
@@ -2255,6 +2364,9 @@ struct Roster {
     int look_rooms = 0;          // rooms 0 .. look_rooms - 1 own a room record
     uint8_t* room_table = nullptr;   // their records, then their descriptions: as speech, made by the first nd_roster_look
     uint8_t* udesc = nullptr;    // the users' descriptions, 32 bytes per slot: likewise
+    int clones = 0;              // clone records 0 .. clones - 1
+    uint8_t* clone_table = nullptr;  // their owners, rooms and hear bytes (take_clones): as speech, made by the first nd_roster_relay
+    uint8_t* relay_names = nullptr;  // the look rooms' names, 24 bytes per room: likewise
 };
 Roster g_rosters[kMaxRosters];
 
@@ -2507,6 +2619,65 @@ size_t layout_look(uintptr_t base, size_t members, size_t nl, LookArgs& s, Speak
     p.text_off = s.ctext_off;
     p.text_len = s.clen;
     p.violations = s.violations;
+    return take.at;
+}
+
+// A roster's clone records as they lie on the device, in the upload and in the kept allocation alike: three arrays in a
+// 256-byte slice each, so the bytes they span are whole words.
+void take_clones(Carver& take, int clones, const int32_t*& owner, const int32_t*& room, const uint8_t*& hear)
+{
+    take(owner, (size_t)clones);
+    take(room, (size_t)clones);
+    take(hear, (size_t)clones);
+}
+
+// nd_roster_relay's layout of a roster's allocation, after layout_plan's pattern: the table, the uploads of the rooms' names
+// and of the clone records (which the kept ones are filled from), nd_roster_plan's inputs with the clone senders and the
+// relay texts' offsets, ending with violations, then the plan's results and the relay's (p plans the relay texts) next to
+// each other: one download.
+// The clone records lie last of the tables, so an upload of theirs alone carries nothing else.
+size_t layout_relay(uintptr_t base, size_t text_bytes, size_t clear_bytes, PlanArgs& a, RelayArgs& q, SpeakPlanArgs& p, const uint8_t** clear,
+                    const int32_t** owner_new, const int32_t** room_new, const uint8_t** hear_new)
+{
+    Carver take{base};
+    const size_t k = (size_t)a.k;
+    const size_t rtext_bytes = text_bytes + (size_t)kRelaySlack * k;
+    take_table(take, a.capacity, a.room, a.slot);
+    take(q.names_new, (size_t)q.look_rooms * (kRelayNameRow / 4));
+    take_clones(take, q.clones, *owner_new, *room_new, *hear_new);
+    take(a.text, text_bytes);
+    take(a.text_off, k);
+    take(a.text_len, k);
+    take(a.rm, k);
+    take(a.sender, k);
+    take(a.flags, k);
+    take(a.com_num, k);
+    take(q.csender, k);
+    take(q.rtext_off, k);
+    take(*clear, clear_bytes);
+    take(a.violations, 1);
+    take(a.vn, 2 * k);
+    take(a.vw, 2 * k);
+    take(a.vwsz, 2 * k * kMaxWrites);
+    take(a.bits, k * (size_t)a.words);
+    take(a.var, (size_t)var_at((int64_t)text_bytes, (int64_t)k));
+    take(q.rbits, k * (size_t)q.cwords);
+    take(q.rlen, k);
+    take(p.vn, 2 * k);
+    take(p.vw, 2 * k);
+    take(p.vwsz, 2 * k * kMaxWrites);
+    take(q.rtext, rtext_bytes);
+    take(p.var, (size_t)var_at((int64_t)rtext_bytes, (int64_t)k));
+    q.clones_new = reinterpret_cast<const uint32_t*>(*owner_new);
+    q.slot = a.slot;
+    q.text = a.text;
+    q.text_off = a.text_off;
+    q.text_len = a.text_len;
+    q.rm = a.rm;
+    q.violations = p.violations = a.violations;
+    p.text = q.rtext;
+    p.text_off = q.rtext_off;
+    p.text_len = q.rlen;
     return take.at;
 }
 
@@ -2823,6 +2994,8 @@ int nd_roster_destroy(int handle)
     if (r->afk) (void)hipFree(r->afk);
     if (r->room_table) (void)hipFree(r->room_table);
     if (r->udesc) (void)hipFree(r->udesc);
+    if (r->clone_table) (void)hipFree(r->clone_table);
+    if (r->relay_names) (void)hipFree(r->relay_names);
     if (r->mirror) (void)hipHostFree(r->mirror);
     *r = Roster{};
     return 0;
@@ -3652,6 +3825,192 @@ int nd_roster_look(int handle, int k, const int32_t* slots, const int32_t* lroom
     memcpy(var, res(po.var), var_bytes);
 
     return fill_timing(timing, t0, t1, in_bytes - from, res_bytes);
+}
+
+// Give roster `handle` clone records 0 .. n - 1 (0 .. 65536), all empty; before its first nd_roster_relay, which allocates
+// them.  Returns 0, or -1 with nd_last_error() set.
+int nd_roster_clones(int handle, int n)
+{
+    Roster* r = roster_at(handle);
+    if (!r) return -1;
+    if (n < 0 || n > kMaxCapacity || r->clone_table) {
+        snprintf(g_err, sizeof(g_err), "clone records %d outside 0 .. %d, or the records are already in use", n, kMaxCapacity);
+        return -1;
+    }
+    r->clones = n;
+    return 0;
+}
+
+// nd_roster_plan (or nd_roster_plan_record) of the k broadcasts, and the clone relay of each: what the clone records
+// standing in its room send to their owners (the relay section above has the rule).  The arguments up to `table` and the
+// outputs bits .. var are nd_roster_plan's.  csender[k] is the clone record that is `user` of the broadcast, -1: none.
+// clones is NULL when no record changed since the last nd_roster_relay of this roster, else all of them: `clones` int32
+// owners (-1: empty), `clones` int32 rooms, `clones` hear bytes; names likewise the look rooms' names, 24 bytes per room (20
+// of name padded with zeros, then its length); the roster's first call must give both.  The caller has checked that every
+// owner is a slot and every owned record's room a look room.
+// Outputs (host, caller-allocated), with CW = ceil(clones / 64): rbits[k * CW], record c of broadcast b is bit c % 64 of
+// rbits[b * CW + c / 64], the bits past the records zero; rlen[k] the relay texts' lengths, -1 where nothing relays;
+// rtext[text_bytes + 32 k], relay text b at text_off[b] + 32 b; rvn[2k], rvw[2k], rvwsz[2k * 16] and rvar[12 * rtext bytes +
+// 16 k] as vn .. var, over the relay texts.
+// Per call, whatever k, the capacity and the records: one upload, three kernels (nuts_roster_plan, nuts_roster_relay,
+// nuts_roster_speak_plan over the relay texts) and nuts_roster_record after the first when recording, one download at the
+// bound size, one synchronise.
+static int relay_call(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off,
+                      const int32_t* text_len, const int32_t* rm, const int32_t* sender, const uint8_t* flags,
+                      const int32_t* com_num, const int32_t* csender, const uint8_t* table, const uint8_t* clones,
+                      const uint8_t* names, uint64_t* bits, int64_t* vn, int32_t* vw, int32_t* vwsz, uint8_t* var,
+                      uint64_t* rbits, int32_t* rlen, int64_t* rvn, int32_t* rvw, int32_t* rvwsz, uint8_t* rtext,
+                      uint8_t* rvar, nd_roster_timing* timing, bool record, const uint8_t* clear)
+{
+    Roster* r = roster_at(handle);
+    if (!r || ensure_ready()) return -1;
+    if (record && ensure_rings(*r, g.stream)) return -1;
+    const int cap = r->capacity, words = (cap + 63) / 64, nc = r->clones, nrooms = r->look_rooms;
+    if (k < 1 || (int64_t)k * cap >= INT32_MAX || text_bytes < 0 || nc < 1 || nrooms < 1 ||
+        text_bytes + (int64_t)kRelaySlack * k >= INT32_MAX) {
+        snprintf(g_err, sizeof(g_err), "%d broadcasts to %d slots, %d clone records and %d look rooms: need 1 <= k * capacity < "
+                 "2^31 - 1, a clone record and a look room", k, cap, nc, nrooms);
+        return -1;
+    }
+    for (int b = 0; b < k; b++)          // the kernel indexes by these: nothing out of range reaches it
+        if (csender[b] < -1 || csender[b] >= nc || text_off[b] < 0 || text_len[b] < 0 || text_off[b] + (int64_t)text_len[b] > text_bytes) {
+            snprintf(g_err, sizeof(g_err), "broadcast %d: clone sender or text out of range", b);
+            return -1;
+        }
+    if ((!r->clone_table && !clones) || (!r->relay_names && !names)) {
+        snprintf(g_err, sizeof(g_err), "the roster's first relay call must give the clone records and the rooms' names");
+        return -1;
+    }
+    const int32_t *ko = nullptr, *kr = nullptr;      // the kept records are laid out as the upload's
+    const uint8_t* kh = nullptr;
+    Carver sized{0};
+    take_clones(sized, nc, ko, kr, kh);
+    const size_t clone_bytes = sized.at, name_bytes = (size_t)nrooms * kRelayNameRow;
+    if (ensure_kept(&r->clone_table, clone_bytes, "clone records")) return -1;
+    if (ensure_kept(&r->relay_names, name_bytes, "room names")) return -1;
+    const double t0 = now_ns();
+    hipStream_t st = g.stream;
+    PlanArgs a{};
+    RelayArgs q{};
+    SpeakPlanArgs p{};                   // k = 0, tiles = 0: no room lines, a block per relay text
+    a.k = q.k = k;
+    a.capacity = q.capacity = p.capacity = cap;
+    a.tiles = (cap + kBlock - 1) / kBlock;
+    a.words = words;
+    q.clones = nc;
+    q.cwords = (nc + 63) / 64;
+    q.look_rooms = nrooms;
+    const size_t var_bytes = (size_t)var_at(text_bytes, k), rtext_bytes = (size_t)text_bytes + (size_t)kRelaySlack * k;
+    const size_t rvar_bytes = (size_t)var_at((int64_t)rtext_bytes, k);
+    PlanArgs o = a;                      // offsets of every array in the roster's allocation
+    RelayArgs qo = q;
+    SpeakPlanArgs po = p;
+    const size_t clear_bytes = record && clear ? (size_t)r->review_rooms : 0;
+    const uint8_t *o_clear = nullptr, *d_clear = nullptr, *o_hear = nullptr, *d_hear = nullptr;
+    const int32_t *o_owner = nullptr, *o_room = nullptr, *d_owner = nullptr, *d_room = nullptr;
+    const size_t need = layout_relay(0, (size_t)text_bytes, clear_bytes, o, qo, po, &o_clear, &o_owner, &o_room, &o_hear);
+    const size_t table_bytes = (uintptr_t)qo.names_new, clones_at = (uintptr_t)o_owner, tables_end = (uintptr_t)o.text;
+    const size_t in_bytes = (uintptr_t)o.violations + sizeof(int);
+    const size_t res_at = (uintptr_t)o.violations, res_bytes = (uintptr_t)po.var + rvar_bytes - res_at;
+    if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
+    if (table) new_table(*r, o.room, o.slot, table);
+    if (grow_roster(*r, need)) return -1;
+    layout_relay((uintptr_t)r->d, (size_t)text_bytes, clear_bytes, a, q, p, &d_clear, &d_owner, &d_room, &d_hear);
+    if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
+
+    uint8_t* h = r->mirror;
+    const Put put{h};
+    if (names) put(qo.names_new, names, name_bytes);
+    if (clones) {
+        put(o_owner, clones, (size_t)nc * sizeof(int32_t));
+        put(o_room, clones + (size_t)nc * sizeof(int32_t), (size_t)nc * sizeof(int32_t));
+        put(o_hear, clones + 2 * (size_t)nc * sizeof(int32_t), (size_t)nc);
+    }
+    put(o.text, text, (size_t)text_bytes);
+    put(o.text_off, text_off, (size_t)k * sizeof(int32_t));
+    put(o.text_len, text_len, (size_t)k * sizeof(int32_t));
+    put(o.rm, rm, (size_t)k * sizeof(int32_t));
+    put(o.sender, sender, (size_t)k * sizeof(int32_t));
+    put(o.flags, flags, (size_t)k);
+    put(o.com_num, com_num, (size_t)k * sizeof(int32_t));
+    put(qo.csender, csender, (size_t)k * sizeof(int32_t));
+    int32_t* roff = reinterpret_cast<int32_t*>(h + (uintptr_t)qo.rtext_off);
+    for (int b = 0; b < k; b++) roff[b] = text_off[b] + kRelaySlack * b;
+    put(o_clear, clear, clear_bytes);
+    *reinterpret_cast<int*>(h + (uintptr_t)o.violations) = 0;
+    // as nd_roster_look: what lies after the first table that changed travels too, but the kernel is told of the changed
+    // ones alone, so the mirror's bytes of the others need not be current
+    const size_t from = !r->resident ? 0 : names ? table_bytes : clones ? clones_at : tables_end;
+    ND_CHECK(hipMemcpyAsync(r->d + from, h + from, in_bytes - from, hipMemcpyHostToDevice, st));
+    r->resident = true;
+    q.records = clones ? reinterpret_cast<const uint8_t*>(d_owner) : r->clone_table;
+    q.names = names ? reinterpret_cast<const uint8_t*>(q.names_new) : r->relay_names;
+    if (!clones) q.clones_new = nullptr;
+    if (!names) q.names_new = nullptr;
+    q.clones_keep = reinterpret_cast<uint32_t*>(r->clone_table);
+    q.names_keep = reinterpret_cast<uint32_t*>(r->relay_names);
+    q.clone_words = (int)(clone_bytes / 4);
+    q.name_words = (int)(name_bytes / 4);
+    const size_t copy_words = (clones ? clone_bytes / 4 : 0) + (names ? name_bytes / 4 : 0);
+
+    ND_CHECK(hipEventRecord(g.ev0, st));
+    hipLaunchKernelGGL(nuts_roster_plan, dim3((unsigned)(k * a.tiles)), dim3(kBlock), 0, st, a);
+    ND_CHECK(hipGetLastError());
+    if (record && launch_record(*r, k, a.text, a.text_off, a.text_len, a.rm, a.flags, clear_bytes ? d_clear : nullptr))
+        return -1;
+    hipLaunchKernelGGL(nuts_roster_relay, dim3((unsigned)(k + (copy_words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, q);
+    ND_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)k), dim3(kBlock), 0, st, p);
+    ND_CHECK(hipGetLastError());
+    if (fetch_results(r->d, res_at, res_bytes)) return -1;
+    const double t1 = now_ns();
+
+    const Res res{gm.res, res_at};
+    const int violations = *reinterpret_cast<const int*>(res(o.violations));
+    if (violations) {
+        snprintf(g_err, sizeof(g_err), "%d variant(s) or relay text(s) exceeded the hard bounds (6*len+4 bytes, %d writes; a relay "
+                 "text %d bytes)", violations, kMaxWrites, kArrSize - 1);
+        return -1;
+    }
+    memcpy(vn, res(o.vn), 2 * (size_t)k * sizeof(int64_t));
+    memcpy(vw, res(o.vw), 2 * (size_t)k * sizeof(int32_t));
+    memcpy(vwsz, res(o.vwsz), 2 * (size_t)k * kMaxWrites * sizeof(int32_t));
+    memcpy(bits, res(o.bits), (size_t)k * words * sizeof(uint64_t));
+    memcpy(var, res(o.var), var_bytes);
+    memcpy(rbits, res(qo.rbits), (size_t)k * q.cwords * sizeof(uint64_t));
+    memcpy(rlen, res(qo.rlen), (size_t)k * sizeof(int32_t));
+    memcpy(rvn, res(po.vn), 2 * (size_t)k * sizeof(int64_t));
+    memcpy(rvw, res(po.vw), 2 * (size_t)k * sizeof(int32_t));
+    memcpy(rvwsz, res(po.vwsz), 2 * (size_t)k * kMaxWrites * sizeof(int32_t));
+    memcpy(rtext, res(qo.rtext), rtext_bytes);
+    memcpy(rvar, res(po.var), rvar_bytes);
+
+    return fill_timing(timing, t0, t1, in_bytes - from, res_bytes);
+}
+
+// The plan and the relay (relay_call above): bit 2 of flags[] is not looked at, and nothing touches the rings.
+int nd_roster_relay(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off,
+                    const int32_t* text_len, const int32_t* rm, const int32_t* sender, const uint8_t* flags,
+                    const int32_t* com_num, const int32_t* csender, const uint8_t* table, const uint8_t* clones,
+                    const uint8_t* names, uint64_t* bits, int64_t* vn, int32_t* vw, int32_t* vwsz, uint8_t* var,
+                    uint64_t* rbits, int32_t* rlen, int64_t* rvn, int32_t* rvw, int32_t* rvwsz, uint8_t* rtext,
+                    uint8_t* rvar, nd_roster_timing* timing)
+{
+    return relay_call(handle, k, text, text_bytes, text_off, text_len, rm, sender, flags, com_num, csender, table, clones,
+                      names, bits, vn, vw, vwsz, var, rbits, rlen, rvn, rvw, rvwsz, rtext, rvar, timing, false, nullptr);
+}
+
+// The plan, the records, then the relay (relay_call above): nd_roster_relay's arguments, and clear as
+// nd_roster_plan_record's.  The roster needs review rings.
+int nd_roster_relay_record(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off,
+                           const int32_t* text_len, const int32_t* rm, const int32_t* sender, const uint8_t* flags,
+                           const int32_t* com_num, const int32_t* csender, const uint8_t* table, const uint8_t* clones,
+                           const uint8_t* names, uint64_t* bits, int64_t* vn, int32_t* vw, int32_t* vwsz, uint8_t* var,
+                           uint64_t* rbits, int32_t* rlen, int64_t* rvn, int32_t* rvw, int32_t* rvwsz, uint8_t* rtext,
+                           uint8_t* rvar, nd_roster_timing* timing, const uint8_t* clear)
+{
+    return relay_call(handle, k, text, text_bytes, text_off, text_len, rm, sender, flags, com_num, csender, table, clones,
+                      names, bits, vn, vw, vwsz, var, rbits, rlen, rvn, rvw, rvwsz, rtext, rvar, timing, true, clear);
 }
 
 }  // extern "C"

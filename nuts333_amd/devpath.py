@@ -2,7 +2,7 @@
 
     python -m nuts333_amd.devpath [--reps R] [--warmup W] [--pathbench-iterations I] [--per-call K[,K...]]
                                   [--roster K[,K...]] [--plan K[,K...]] [--review Q[,Q...]] [--speak K[,K...]]
-                                  [--input K[,K...]] [--tell K[,K...]] [--look K[,K...]]                      -> one JSON line
+                                  [--input K[,K...]] [--tell K[,K...]] [--look K[,K...]] [--relay K[,K...]]   -> one JSON line
 
 For N in {10, 100, 1000} listeners, the two texts oracle/pathbench.c times (``say``; ``shout`` carrying ``~OL``/``~RS``)
 and colour all-off / all-on / half, one ``nuts333_amd.device.broadcast`` per repetition (listener 0 is the sender, the
@@ -69,6 +69,13 @@ per ``Roster.look_many`` call: the three times and the copy volume, beside ``cpu
 (``nuts_path``, through ctypes) over the strings ``look()`` composes for the same lookers.  The strings are composed
 beforehand, so ``cpu_us`` leaves the CPU's composing out (``look_cpu_us_covers`` says so).  The first call of each case is
 checked against that transducer over those strings.
+
+``--relay K[,K...]`` adds ``relay``: a 1000-slot roster spread over 5 rooms with 64 clone records, of which 0, 1 or 64 stand
+in room 0 and hear everything, and K says to room 0 per ``Roster.relay_many`` call, timed alternating, in one process, with
+``plan_many`` of the same K broadcasts: the three times and the copy volume of both, and their ratio.  ``cpu_us`` is the
+CPU doing ``clone_relay``'s work through ``nuts_path``: per relaying clone the swear scan and the transducer over the
+prefixed text (``relay_cpu_us_covers`` says what that leaves out); with no relaying clone there is none.  The first call
+of each case is checked against that transducer over the prefixed text.
 """
 from __future__ import annotations
 
@@ -634,6 +641,89 @@ def look_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
             "look": cases}
 
 
+RELAY_CLONES = 64
+
+
+def relay_broadcasts(k: int) -> list[tuple]:
+    """K says of slot 5 to room 0 of the roster ``relay_cases`` builds."""
+    return [(b"User5 says: " + body + b"\n", 0, 5, 0, device.COM_SAY) for body in (b"relayed line %06d of the bench" % i for i in range(k))]
+
+
+def relay_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
+    """The ``relay`` section: relay_many of K says to room 0 of a 1000-slot roster spread over 5 rooms, with 0, 1 and 64 of
+    its 64 clone records standing in that room, beside plan_many of the same broadcasts and the CPU doing clone_relay's
+    work."""
+    n = 1000
+    lib = nuts_path.lib()
+    cases = []
+    for colour in COLOURS:
+        col = listeners(n, colour)[:, device.LISTENER_FIELDS.index("colour")]
+        for relaying in (0, 1, RELAY_CLONES):
+            with device.Roster(n, look_rooms=len(LOOK_ROOMS), clones=RELAY_CLONES) as roster:
+                roster.update(range(n), room=[j % len(LOOK_ROOMS) for j in range(n)], colour=col)
+                roster.set_rooms(list(range(len(LOOK_ROOMS))), name=list(LOOK_ROOMS))
+                owners = [10 + c for c in range(relaying)]              # a clone of slots 10 .. in room 0, hearing all
+                if relaying:
+                    roster.set_clones(list(range(relaying)), owner=owners, room=0)
+                for k in ks:
+                    bs = relay_broadcasts(k)
+                    texts = [b"~FT[ " + LOOK_ROOMS[0] + b" ]:~RS " + b[0] for b in bs]
+                    first = roster.relay_many(bs)
+                    for i in range(k):
+                        if first.owners(i).tolist() != owners or any(
+                                first.relay_chunks(i, c) != (nuts_path.chunks(texts[i], c) if relaying else []) for c in (0, 1)):
+                            raise SystemExit(f"devpath: relay {k}, {colour}, {relaying} clones: broadcast {i} differs from the "
+                                             f"CPU's transducer over the prefixed text")
+                    timed = {f: [] for f in ("kernels_us", "end_to_end_us", "python_us", "plan_kernels_us", "plan_end_to_end_us",
+                                             "plan_python_us", "cpu_us")}
+                    copies = set()
+                    for i in range(warmup + reps):
+                        t0 = time.perf_counter()
+                        r = roster.relay_many(bs)
+                        t1 = time.perf_counter()
+                        p = roster.plan_many(bs)
+                        t2 = time.perf_counter()
+                        for q in range(k):
+                            for o in owners:
+                                lib.np_contains_swearing(bs[q][0])
+                                nuts_path.chunks(texts[q], int(col[o]))
+                        t3 = time.perf_counter()
+                        if i >= warmup:
+                            timed["python_us"].append((t1 - t0) * 1e6)
+                            timed["plan_python_us"].append((t2 - t1) * 1e6)
+                            timed["cpu_us"].append((t3 - t2) * 1e6)
+                            timed["kernels_us"].append(r.timing["kernels_us"])
+                            timed["end_to_end_us"].append(r.timing["end_to_end_us"])
+                            timed["plan_kernels_us"].append(p.timing["kernels_us"])
+                            timed["plan_end_to_end_us"].append(p.timing["end_to_end_us"])
+                            copies.add((r.timing["h2d_bytes"], r.timing["d2h_bytes"], p.timing["h2d_bytes"], p.timing["d2h_bytes"]))
+                    if len(copies) != 1:
+                        raise SystemExit(f"devpath: relay {k}, {colour}: timed calls copied {sorted(copies)} bytes")
+                    st = {f: _stats(v) for f, v in timed.items()}
+                    h2d, d2h, plan_h2d, plan_d2h = copies.pop()
+                    cases.append({"n": n, "k": k, "colour": colour, "relaying_clones": relaying, "relays": k * relaying,
+                                  "relay_bytes_out": sum(len(first.relay_variant(i, int(col[o]))) for i in range(k) for o in owners),
+                                  **st, "h2d_bytes": h2d, "d2h_bytes": d2h, "plan_h2d_bytes": plan_h2d, "plan_d2h_bytes": plan_d2h,
+                                  "end_to_end_over_plan": float(f"{st['end_to_end_us']['median'] / st['plan_end_to_end_us']['median']:.3g}"),
+                                  "end_to_end_over_cpu": float(f"{st['end_to_end_us']['median'] / st['cpu_us']['median']:.3g}")
+                                  if relaying else None})
+    return {"relay_kernels": list(device.RELAY_KERNELS),
+            "relay_end_to_end_covers": "what plan_many's covers -- packing the K inputs into pinned memory, one H2D (the table "
+                                       "and the clone records only in a call after an update of theirs, the rooms' names only "
+                                       "when one changed), nuts_roster_plan, one D2H at the bound size, one synchronise --, and "
+                                       "in the same call the clone senders and the relay texts' offsets in the upload, "
+                                       "nuts_roster_relay (the relay bitmap and the relay texts) and nuts_roster_speak_plan "
+                                       "over the K relay texts (their variants), and the relay bitmap, texts and variants in "
+                                       "the download (python_us adds the checks, the copies out of pinned memory and building "
+                                       "the Relay); the plan_ figures are plan_many of the same K broadcasts, timed alternating",
+            "relay_cpu_us_covers": "clone_relay's work on the CPU restatement (nuts_path, through ctypes): per broadcast and "
+                                   "relaying clone np_contains_swearing of the text and np_write_user_stream of the prefixed "
+                                   "text, composed beforehand: this leaves the sprintf and the walk over the user list out, "
+                                   "scans for swearing where a clone that hears everything would not, and includes two ctypes "
+                                   "calls per relay; with no relaying clone the CPU has nothing to do and the ratio is null",
+            "relay": cases}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=2000, help="timed broadcasts per case (default 2000)")
@@ -660,6 +750,10 @@ def main(argv=None) -> int:
     ap.add_argument("--look", type=per_call_counts, default=None, metavar="K[,K...]",
                     help="also time K looks per Roster.look_many call at a 1000-slot roster spread over 5 rooms, for each "
                          "K, beside the CPU's transducer over look()'s strings (the look section)")
+    ap.add_argument("--relay", type=per_call_counts, default=None, metavar="K[,K...]",
+                    help="also time K says per Roster.relay_many call to a room of a 1000-slot roster with 0, 1 and 64 "
+                         "relaying clones in it, for each K, beside plan_many of the same broadcasts and the CPU doing "
+                         "clone_relay's work (the relay section)")
     a = ap.parse_args(argv)
     if a.reps < 1 or a.warmup < 0:
         ap.error("--reps must be >= 1 and --warmup >= 0")
@@ -743,6 +837,7 @@ def main(argv=None) -> int:
     inputs = input_cases(a.input, a.reps, a.warmup, pb) if a.input else {}
     tell = tell_cases(a.tell, a.reps, a.warmup, pb) if a.tell else {}
     look = look_cases(a.look, a.reps, a.warmup, pb) if a.look else {}
+    relay = relay_cases(a.relay, a.reps, a.warmup, pb) if a.relay else {}
     out = {
         "what": "user-space stage of one broadcast (admit predicate + transducer), device vs CPU",
         "device": "gfx950",
@@ -760,6 +855,7 @@ def main(argv=None) -> int:
         **inputs,
         **tell,
         **look,
+        **relay,
         "wall_s": round(time.perf_counter() - t_start, 1),
     }
     print(json.dumps(out))
