@@ -2474,8 +2474,8 @@ size_t layout_review(uintptr_t base, int capacity, size_t clear_bytes, ReviewArg
 
 // nd_roster_speak's layout of a roster's allocation: the table, then the upload of the
 // speaker table (which the kept one, r.speech, is filled from), the call's inputs ending with violations, the results
-// next to each other, and last what only the kernels pass to each other.  One upload starts at the table, at the speaker
-// table or at the inputs, whichever is the first that changed.
+// next to each other, and last what only the kernels pass to each other.  One upload starts at the speaker table if it
+// was given, else at the inputs; a table the device does not hold goes in front of it (upload()).
 // nd_roster_input's (q given) differs in what describes an event: the upload carries the reads' offsets and lengths
 // where the inpstr's were, no commands and no word counts; nuts_roster_parse writes those, and they lie among the
 // results with what else it found.
@@ -2547,7 +2547,7 @@ size_t layout_speak(uintptr_t base, size_t text_bytes, size_t clear_bytes, Speak
 // nd_roster_tell's layout of a roster's allocation, after layout_speak's pattern: the table, the uploads of the speaker
 // table and of the AFK messages (which the kept ones, r.speech and r.afk, are filled from), the call's inputs ending with
 // violations, the results next to each other, and last what only the kernels pass to each other.  One upload starts at
-// the first of the three tables that changed, or at the inputs.
+// the first of the two tables behind the table that was given, or at the inputs (upload()).
 size_t layout_tell(uintptr_t base, size_t text_bytes, size_t clear_bytes, TellArgs& s, SpeakPlanArgs& p, const uint8_t** clear)
 {
     Carver take{base};
@@ -2737,6 +2737,24 @@ int grow_roster(Roster& r, size_t need)
     const size_t cap_d = r.cap_d;
     if (grow_dev(&r.d, &r.cap_d, need, "roster device allocation")) return -1;
     if (r.cap_d != cap_d) r.resident = false;
+    return 0;
+}
+
+// The upload of a call whose layout leaves room between the table and the inputs for tables the caller may pass: `first`
+// is where the first table that was passed starts, or the inputs when none was.  A device allocation that holds the table
+// gets the mirror's bytes from `first` on.  One that does not gets the table as well: in the same copy when `first`
+// follows it directly, else in a copy of its own, so that the gap -- room for tables that were not passed, whose bytes in
+// the mirror are not current -- does not travel.  *copied is what went up.
+int upload(Roster& r, size_t table_bytes, size_t first, size_t in_bytes, size_t* copied)
+{
+    *copied = in_bytes - first;
+    if (!r.resident) {
+        *copied += table_bytes;
+        if (first == table_bytes) first = 0;
+        else ND_CHECK(hipMemcpyAsync(r.d, r.mirror, table_bytes, hipMemcpyHostToDevice, g.stream));
+    }
+    ND_CHECK(hipMemcpyAsync(r.d + first, r.mirror + first, in_bytes - first, hipMemcpyHostToDevice, g.stream));
+    r.resident = true;
     return 0;
 }
 
@@ -3424,11 +3442,9 @@ static int speech_call(int handle, int k, const uint8_t* text, int64_t text_byte
     }
     put(o_clear, clear, clear_bytes);
     *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
-    // the speaker table's upload lies between the table and the inputs: when only the table changed it travels too, but
-    // the kernel is not told, so the mirror's bytes there need not be current
-    const size_t from = !r->resident ? 0 : speech ? table_bytes : speech_end;
-    ND_CHECK(hipMemcpyAsync(r->d + from, h + from, in_bytes - from, hipMemcpyHostToDevice, st));
-    r->resident = true;
+    // the speaker table's upload lies between the table and the inputs: it travels only when it was given
+    size_t h2d = 0;
+    if (upload(*r, table_bytes, speech ? table_bytes : speech_end, in_bytes, &h2d)) return -1;
     s.speech = speech ? s.speech_new : r->speech;
     if (!speech) s.speech_new = nullptr;
     s.speech_keep = r->speech;
@@ -3475,7 +3491,7 @@ static int speech_call(int handle, int k, const uint8_t* text, int64_t text_byte
     memcpy(ctext, res(so.ctext), ctext_bytes);
     memcpy(var, res(po.var), var_bytes);
 
-    return fill_timing(timing, t0, t1, in_bytes - from, res_bytes);
+    return fill_timing(timing, t0, t1, h2d, res_bytes);
 }
 
 // K speech events of roster `handle`, as say(), shout(), emote() and semote() answer them.  Event b: the speaker's slot
@@ -3627,9 +3643,8 @@ int nd_roster_tell(int handle, int k, const uint8_t* text, int64_t text_bytes, c
     *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
     // the tables' uploads lie between the table and the inputs: what lies after the first one that changed travels too,
     // but the kernel is told of the changed ones alone, so the mirror's bytes of the others need not be current
-    const size_t from = !r->resident ? 0 : speech ? table_bytes : afk ? afk_at : tables_end;
-    ND_CHECK(hipMemcpyAsync(r->d + from, h + from, in_bytes - from, hipMemcpyHostToDevice, st));
-    r->resident = true;
+    size_t h2d = 0;
+    if (upload(*r, table_bytes, speech ? table_bytes : afk ? afk_at : tables_end, in_bytes, &h2d)) return -1;
     s.speech = speech ? s.speech_new : r->speech;
     s.afk = afk ? s.afk_new : r->afk;
     if (!speech) s.speech_new = nullptr;
@@ -3665,7 +3680,7 @@ int nd_roster_tell(int handle, int k, const uint8_t* text, int64_t text_bytes, c
     memcpy(ctext, res(so.ctext), ctext_bytes);
     memcpy(var, res(po.var), var_bytes);
 
-    return fill_timing(timing, t0, t1, in_bytes - from, res_bytes);
+    return fill_timing(timing, t0, t1, h2d, res_bytes);
 }
 
 // Give roster `handle` room records for rooms 0 .. n - 1 (0 .. 1024); before its first nd_roster_look, which allocates
@@ -3782,9 +3797,8 @@ int nd_roster_look(int handle, int k, const int32_t* slots, const int32_t* lroom
     *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
     // the tables' uploads lie between the table and the inputs: what lies after the first one that changed travels too,
     // but the kernel is told of the changed ones alone, so the mirror's bytes of the others need not be current
-    const size_t from = !r->resident ? 0 : speech ? table_bytes : rooms ? rooms_at : udesc ? udesc_at : tables_end;
-    ND_CHECK(hipMemcpyAsync(r->d + from, h + from, in_bytes - from, hipMemcpyHostToDevice, st));
-    r->resident = true;
+    size_t h2d = 0;
+    if (upload(*r, table_bytes, speech ? table_bytes : rooms ? rooms_at : udesc ? udesc_at : tables_end, in_bytes, &h2d)) return -1;
     s.speech = speech ? s.speech_new : r->speech;
     s.rooms = rooms ? s.rooms_new : r->room_table;
     s.udesc = udesc ? s.udesc_new : r->udesc;
@@ -3824,7 +3838,7 @@ int nd_roster_look(int handle, int k, const int32_t* slots, const int32_t* lroom
     memcpy(ctext, res(so.ctext), ctext_bytes);
     memcpy(var, res(po.var), var_bytes);
 
-    return fill_timing(timing, t0, t1, in_bytes - from, res_bytes);
+    return fill_timing(timing, t0, t1, h2d, res_bytes);
 }
 
 // Give roster `handle` clone records 0 .. n - 1 (0 .. 65536), all empty; before its first nd_roster_relay, which allocates
@@ -3940,9 +3954,8 @@ static int relay_call(int handle, int k, const uint8_t* text, int64_t text_bytes
     *reinterpret_cast<int*>(h + (uintptr_t)o.violations) = 0;
     // as nd_roster_look: what lies after the first table that changed travels too, but the kernel is told of the changed
     // ones alone, so the mirror's bytes of the others need not be current
-    const size_t from = !r->resident ? 0 : names ? table_bytes : clones ? clones_at : tables_end;
-    ND_CHECK(hipMemcpyAsync(r->d + from, h + from, in_bytes - from, hipMemcpyHostToDevice, st));
-    r->resident = true;
+    size_t h2d = 0;
+    if (upload(*r, table_bytes, names ? table_bytes : clones ? clones_at : tables_end, in_bytes, &h2d)) return -1;
     q.records = clones ? reinterpret_cast<const uint8_t*>(d_owner) : r->clone_table;
     q.names = names ? reinterpret_cast<const uint8_t*>(q.names_new) : r->relay_names;
     if (!clones) q.clones_new = nullptr;
@@ -3985,7 +3998,7 @@ static int relay_call(int handle, int k, const uint8_t* text, int64_t text_bytes
     memcpy(rtext, res(qo.rtext), rtext_bytes);
     memcpy(rvar, res(po.var), rvar_bytes);
 
-    return fill_timing(timing, t0, t1, in_bytes - from, res_bytes);
+    return fill_timing(timing, t0, t1, h2d, res_bytes);
 }
 
 // The plan and the relay (relay_call above): bit 2 of flags[] is not looked at, and nothing touches the rings.

@@ -1,0 +1,736 @@
+"""The device work of tests/test_device_sequence.py, in a short-lived child process of its own, and what the host tier of
+that module shares with it: the state a sequence test owns, the fields every call kind reads, and the seeded step stream.
+
+As tests/device_relay_child.py: the test module starts this script once, under ``timeout``, and asserts on the one JSON
+line it prints (``DEVICE_SEQUENCE {...}``).  Every other ``device_*_child.py`` fuzzes one call kind on a roster it has just
+built.  This one interleaves the nine device calls of a ``device.Roster`` with ``update``, ``set_rooms``, ``set_clones``,
+``clear_review`` and ``clear_revtell`` on rosters that live long, two of them at once, and compares every call in full
+with the models of those children, computed from a ``State`` kept here in plain Python and never from the roster's mirrors.
+``regrowth_part`` makes, for every ordered pair of table-reading kinds, a small call of the one and then a large call of
+the other, so that the second finds a device allocation that was freed and made anew.
+
+    python tests/device_sequence_child.py [--seed S] [--seed2 T]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import random
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+REPO = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(REPO))
+sys.path.insert(0, str(REPO / "tests"))
+
+from device_fanout_child import fuzz_items  # noqa: E402
+from device_input_child import answer_of, fuzz_read, input_differences  # noqa: E402
+from device_input_child import new_counts as input_counts  # noqa: E402
+from device_look_child import WORST_DESCS, WORST_NAMES, fuzz_rooms, look_differences  # noqa: E402
+from device_look_child import new_counts as look_counts  # noqa: E402
+from device_many_child import COMS as BROADCAST_COMS  # noqa: E402
+from device_many_child import Cpu, compare, expected, table  # noqa: E402
+from device_plan_child import plan_differences  # noqa: E402
+from device_relay_child import ALL, NOTHING, SWEARS, longest_text, relay_text, relays  # noqa: E402
+from device_review_child import Rings, review_differences  # noqa: E402
+from device_roster_child import Model  # noqa: E402
+from device_speak_child import COMS as SPEECH_COMS  # noqa: E402
+from device_speak_child import EMOTE, SAY, fuzz_inpstr, model, speech_differences  # noqa: E402
+from device_tell_child import COMS as TELL_COMS  # noqa: E402
+from device_tell_child import TOLD, TellRings, fuzz_event, new_user, private, private_differences  # noqa: E402
+from device_tell_child import new_counts as tell_counts  # noqa: E402
+from nuts333_amd import device, nuts_path  # noqa: E402
+
+KINDS = ("broadcast_many", "plan_many", "speak_many", "input_many", "tell_many", "look_many", "relay_many", "review_many",
+         "revtell_many")
+#: the kinds whose kernels read the table (nd_roster_review and nd_roster_revtell neither read nor upload it)
+TABLE_KINDS = KINDS[:7]
+#: the kinds that can record into the rooms' review rings, and the two that touch the slots' revtell rings
+RECORDING_KINDS = ("plan_many", "speak_many", "input_many", "relay_many")
+REVIEW_ROOMS, LOOK_ROOMS = 3, 5
+CAPACITIES = (1, 64, 65, 257)
+#: the roster made in the closed one's place
+REPLACEMENT_CAPACITY = 130
+STEPS_PER_ROSTER = 120
+
+# ------------------------------------------------------------------ the fields, and where each lives
+TABLE_FIELDS = ("room", "login", "ignall", "ignshout", "colour")
+SPEECH_FIELDS = ("name", "vis", "muzzled", "command_mode", "level", "afk", "igntell")
+USER_FIELDS = TABLE_FIELDS + SPEECH_FIELDS + ("afk_mesg", "desc")
+ROOM_FIELDS = ("name", "access", "desc", "links", "topic", "mesg_cnt", "netlink")
+CLONE_FIELDS = ("owner", "room", "hear")
+#: the rooms' names as relay_many keeps them: no host mirror of the roster, an array it builds per call and compares
+RELAY_NAMES = "relay.names"
+#: field -> the mirror it lives in (an attribute of device.Roster, or "names" for the array of relay_many)
+MIRROR_OF = {**{f: "_table" for f in TABLE_FIELDS}, **{f: "_speech" for f in SPEECH_FIELDS}, "afk_mesg": "_afk", "desc": "_udesc",
+             **{f"rooms.{f}": "_rooms" for f in ROOM_FIELDS}, **{f"clones.{f}": "_clones" for f in CLONE_FIELDS},
+             RELAY_NAMES: "names"}
+FIELDS = tuple(MIRROR_OF)
+MIRRORS = ("_table", "_speech", "_afk", "_rooms", "_udesc", "_clones")
+
+_TABLE = frozenset(TABLE_FIELDS)
+#: What each call kind reads, from the kernels of nuts333_amd/device/fanout.hip and their nd_roster_* entry points (the
+#: lines are those of the kernels' bodies; an entry point hands a kernel the uploaded table or the kept one, never both).
+#: The table is one mirror with one flag, so a kind that reads one of its fields is listed with all five: colour is read
+#: on the host as well, by every kind that returns a Plan's colour_bits or a Look's colour.
+READS = {
+    # nd_roster_fanout -> roster_measure / roster_emit: listener_record(a.room[j], a.slot[j], ...) (fanout.hip:502), the
+    # colour bit of a.slot[j] picks the variant (fanout.hip:591)
+    "broadcast_many": _TABLE,
+    # plan_call -> roster_plan: listener_record(a.room[j], a.slot[j], ...) (fanout.hip:653)
+    "plan_many": _TABLE,
+    # speech_call -> roster_speak: a.room[slot] (fanout.hip:1126); of the speaker's 16 bytes the name and its length
+    # (1123-1125, 1153), muzzled (1133), command_mode (1134), vis (1153); roster_speak_plan: listener_record (1216).  Neither
+    # reads the level byte nor the afk and igntell bits
+    "speak_many": _TABLE | {"name", "vis", "muzzled", "command_mode"},
+    # ... and roster_parse in front of them: command_mode (fanout.hip:1343) and the level byte (1344)
+    "input_many": _TABLE | {"name", "vis", "muzzled", "command_mode", "level"},
+    # nd_roster_tell -> roster_tell: the speaker's name, muzzled and vis (fanout.hip:1545-1547, 1572, 1637); get_user over
+    # every slot's login flag and name (1587-1590); both levels (1621); the target's afk (1623), ignall (1624), igntell
+    # (1625), room (1626) and name (1634); its AFK message (1654).  It reads the level, which the issue's table of this
+    # test did not expect and update()'s docstring does not say; it does not read command_mode
+    "tell_many": _TABLE | {"name", "vis", "muzzled", "level", "afk", "igntell", "afk_mesg"},
+    # nd_roster_look -> roster_look: a.room[j] (fanout.hip:1946), the looker's level (1936), every slot's name, vis and level
+    # (1947-1950); look_line: vis (1896), the description (1894), afk (1912); look_room: the whole room record
+    "look_many": _TABLE | {"name", "vis", "level", "afk", "desc"} | {f"rooms.{f}" for f in ROOM_FIELDS},
+    # relay_call -> roster_plan (fanout.hip:653), roster_relay: the records' owner, room and hear (2072-2082), the owner's
+    # ignall (2083), the room's name from the 24-byte rows (2097-2098) and nothing else of the room table
+    "relay_many": _TABLE | {f"clones.{f}" for f in CLONE_FIELDS} | {RELAY_NAMES},
+    # review_call: its layout steps over the table (layout_review), the kernel reads the rings alone
+    "review_many": frozenset(),
+    "revtell_many": frozenset(),
+}
+#: a field each kind does not read, for the step "an update of only fields it does not read"
+UNREAD = {"broadcast_many": "desc", "plan_many": "name", "speak_many": "afk", "input_many": "igntell", "tell_many": "desc",
+          "look_many": "muzzled", "relay_many": "level", "review_many": "room", "revtell_many": "colour"}
+
+ROOM_NAME_POOL = (b"d", b"N" * 20, b"hallway", b"~FRred/", b"wiz", b"R" * 20, b"alone", b"pair", b"e", b"/~", b"drive")
+SYLLABLES = (b"al", b"ice", b"bob", b"by", b"car", b"ol", b"dave", b"x", b"Zed", b"9", b"\xe9", b"an", b"na")
+AFK_MESGS = (b"", b"", b"back in five", b"m" * 60, b"~FRred~RS \xe9")
+
+
+def slice_of(n: int) -> int:
+    """An array's 256-byte aligned slice of an upload (Carver of fanout.hip)."""
+    return -(-n // 256) * 256
+
+
+def op_for(field: str) -> tuple:
+    """The step that updates ``field`` and nothing else that lives elsewhere."""
+    if field == RELAY_NAMES:
+        return ("set_rooms", ("name",))
+    if field.startswith("rooms."):
+        return ("set_rooms", (field[6:],))
+    if field.startswith("clones."):
+        return ("set_clones", (field[7:],))
+    return ("update", (field,))
+
+
+# ------------------------------------------------------------------ the state the test owns
+class State:
+    """The truth, in plain Python: a dict per slot, the room records, the clone records as ``[owner, room, hear]`` (owner
+    None: an empty record) and both sets of rings.  Slot 0 is always a speaker in a ring room and record 0 always owned, so
+    that every call kind has somebody to call it for."""
+
+    def __init__(self, rng: random.Random, cap: int, nclones: int):
+        self.cap, self.nclones = cap, nclones
+        self.rooms = fuzz_rooms(rng)
+        self.users = {j: new_user(j, ignshout=0, desc=b"") for j in range(cap)}
+        for j, u in self.users.items():
+            for f in USER_FIELDS:
+                u[f] = self.value(rng, f, j)
+            if j and rng.random() < 0.1:
+                u["name"] = None                                         # a slot that never got a name
+        self.records = []
+        for c in range(nclones):
+            empty = c > 0 and rng.random() < 0.15
+            self.records.append([None, None, NOTHING] if empty else
+                                [rng.randrange(cap), rng.randrange(4), rng.choice((NOTHING, SWEARS, ALL, ALL))])
+        self.rings, self.tell_rings = Rings(REVIEW_ROOMS), TellRings(cap)
+
+    def value(self, rng: random.Random, f: str, slot: int):
+        if f == "room":
+            return rng.choice((0, 1, 2)) if slot == 0 else rng.choice((0, 0, 1, 2, 3, 4, None))
+        if f == "login":
+            return 0 if slot == 0 else int(rng.random() < 0.1)
+        if f == "name":
+            x = rng.random()
+            if x < 0.5:
+                name = b"".join(rng.choice(SYLLABLES) for _ in range(rng.randrange(1, 5)))[:rng.choice((12, 12, 5, 3))]
+                return name[:1].upper() + name[1:] if rng.random() < 0.8 else name
+            return rng.choice(WORST_NAMES) if x < 0.65 else b"Q%d" % slot
+        if f == "level":
+            return rng.randrange(5)
+        if f == "afk_mesg":
+            return rng.choice(AFK_MESGS)
+        if f == "desc":
+            return rng.choice(WORST_DESCS)
+        chance = {"ignall": 0.2, "ignshout": 0.3, "colour": 0.5, "vis": 0.7, "muzzled": 0.1, "command_mode": 0.3, "afk": 0.15,
+                  "igntell": 0.2}[f]
+        return int(rng.random() < chance)
+
+    def room_value(self, rng: random.Random, f: str, rm: int):
+        if f == "name":
+            return rng.choice([n for n in ROOM_NAME_POOL if n != self.rooms[rm]["name"]])
+        if f == "access":
+            return rng.randrange(4)
+        if f == "desc":
+            return rng.choice((b"\n" * 810, b"~FR" * 270, b"/~" * 405, b"", b"A room.\nWith ~OLtwo~RS lines and a slash/\n"))
+        if f == "links":
+            return [rng.randrange(LOOK_ROOMS) for _ in range(rng.choice((0, 1, 3, 10)))]
+        if f == "topic":
+            return rng.choice((b"", b"t" * 60, b"~OLbold~RS /~FR \xe9", b"a topic"))
+        if f == "mesg_cnt":
+            return rng.choice((0, 7, 2**31 - 1, rng.randrange(1000)))
+        return rng.choice((None, (b"s" * 80, True), (b"peer2", False), (b"in", True)))
+
+    def seat(self, roster: device.Roster) -> None:
+        """A roster that has just been made, in this state."""
+        slots = list(range(self.cap))
+        roster.update(slots, **{f: [self.users[j][f] for j in slots] for f in USER_FIELDS if f != "name"})
+        named = [j for j in slots if self.users[j]["name"]]
+        roster.update(named, name=[self.users[j]["name"] for j in named])
+        ids = list(range(LOOK_ROOMS))
+        roster.set_rooms(ids, **{f: [self.rooms[i][f] for i in ids] for f in ROOM_FIELDS})
+        for c, (owner, room, hear) in enumerate(self.records):
+            if owner is not None:
+                roster.set_clones(c, owner=owner, room=room, hear=hear)
+
+    def table_model(self) -> Model:
+        m = Model(self.cap)
+        for j, u in self.users.items():
+            m.room[j] = -1 if u["room"] is None else u["room"]
+            for f in m.flags:
+                m.flags[f][j] = u[f]
+        return m
+
+    def speakers(self, ring: bool = False) -> list:
+        """The slots that may speak: a room, no login flag, a name; ``ring``: and their room has a review ring."""
+        return [j for j, u in self.users.items() if u["room"] is not None and not u["login"] and u["name"]
+                and (not ring or u["room"] < REVIEW_ROOMS)]
+
+    def relay_records(self) -> list:
+        return [tuple(r) for r in self.records]
+
+    def cloned_rooms(self) -> set:
+        return {r[1] for r in self.records if r[0] is not None}
+
+
+# ------------------------------------------------------------------ what a run counts
+class Coverage:
+    """Which call kind ran directly after which update, and which was the first to touch the rings after a clear."""
+
+    def __init__(self):
+        self.runs, self.after_read, self.after_unread = {}, {}, {}
+        self.first_after_clear_review, self.first_after_clear_revtell = {}, {}
+        self.last = {}                                                   # roster label -> fields of the step just before
+        self.pending = {}                                                # roster label -> [review clear, revtell clear]
+
+    def updated(self, label: str, fields) -> None:
+        self.last[label] = set(fields)
+
+    def cleared(self, label: str, tell: bool) -> None:
+        self.last.pop(label, None)
+        self.pending.setdefault(label, [False, False])[int(tell)] = True
+
+    def called(self, label: str, kind: str, review_rings: bool, revtell_rings: bool) -> None:
+        """``review_rings`` / ``revtell_rings``: the call records into, or reads, those rings."""
+        per = self.runs.setdefault(label, {k: 0 for k in KINDS})
+        per[kind] += 1
+        last = self.last.pop(label, None)
+        if last:
+            for f in last & READS[kind]:
+                self.after_read[f"{kind}/{f}"] = self.after_read.get(f"{kind}/{f}", 0) + 1
+            if not last & READS[kind]:
+                self.after_unread[kind] = self.after_unread.get(kind, 0) + 1
+        pending = self.pending.setdefault(label, [False, False])
+        for i, (touches, first) in enumerate(((review_rings, self.first_after_clear_review),
+                                              (revtell_rings, self.first_after_clear_revtell))):
+            if touches and pending[i]:
+                first[kind] = first.get(kind, 0) + 1
+                pending[i] = False
+
+    def as_json(self) -> dict:
+        return {"runs": self.runs, "after_read": self.after_read, "after_unread": self.after_unread,
+                "first_after_clear_review": self.first_after_clear_review,
+                "first_after_clear_revtell": self.first_after_clear_revtell}
+
+
+def text_of(rng: random.Random, lo: int, hi: int) -> bytes:
+    """A text of lo .. hi bytes from fuzz_inpstr's kinds, without a NUL."""
+    n, t = rng.randint(lo, hi), b""
+    while len(t) < n:
+        t += fuzz_inpstr(rng) + b" "
+    return t[:n]
+
+
+# ------------------------------------------------------------------ one roster, its state, and the steps
+class Runner:
+    """Makes steps on ``roster`` and on ``state`` alike.  With ``check`` every call's result is compared with the models
+    (``bad`` collects what differs); without, only the calls are made, for a library that computes nothing.  ``seen`` is
+    told of every step: ``updated(label, fields)``, ``cleared(label, tell)``, ``called(label, kind, review, revtell)``."""
+
+    def __init__(self, rng: random.Random, roster: device.Roster, state: State, label: str, seen, check: bool = True,
+                 cpu: Cpu | None = None, pool=None):
+        self.rng, self.roster, self.state, self.label, self.seen, self.check = rng, roster, state, label, seen, check
+        self.cpu = cpu or Cpu()
+        self.pool = pool or [t for t, _ in fuzz_items(rng.randrange(1 << 30), 200)] + [b"", b"x" * 999, b"\n" * 999]
+        self.bad, self.steps, self.cache = [], 0, {}
+        self.counts = {"input": input_counts(), "tell": tell_counts(), "look": look_counts(), "speech": {},
+                       "review": {"rooms_reviewed": 0, "lines_compared": 0, "sequential_lines": 0, "wave_lines": 0},
+                       "recorded": 0, "told": 0, "relays": 0, "clone_senders": 0, "longest_text": 0, "empty_texts": 0}
+        self.last_timing = {}
+
+    # -------------------------------------------------------------- updates
+    def step(self, op: tuple) -> None:
+        what, arg = op[0], op[1] if len(op) > 1 else None
+        getattr(self, "_" + what)(arg if arg is not None else ({} if what in KINDS else ()))
+        self.steps += 1
+        self.table_is_the_states()
+
+    def table_is_the_states(self) -> None:
+        """roster.table() reads the roster's own mirror: speech_differences and input_differences admit through it, so it
+        has to be the table the state gives."""
+        want = table(self.state.table_model().records(None, None))
+        if not np.array_equal(self.roster.table(None, None), want):
+            self.bad.append({"step": self.steps, "what": "roster.table() is not the state's table"})
+
+    def _update(self, fields) -> None:
+        rng, st = self.rng, self.state
+        slots = [rng.randrange(st.cap) for _ in range(rng.randint(1, 4))]
+        values = {f: [st.value(rng, f, j) for j in slots] for f in fields}
+        self.roster.update(slots, **values)
+        for i, j in enumerate(slots):                                   # in order: the last value wins
+            for f in fields:
+                st.users[j][f] = values[f][i]
+        self.seen.updated(self.label, fields)
+
+    def _set_rooms(self, fields) -> None:
+        rng, st = self.rng, self.state
+        rooms = rng.sample(range(LOOK_ROOMS), rng.randint(1, 2))
+        values = {f: [st.room_value(rng, f, rm) for rm in rooms] for f in fields}
+        self.roster.set_rooms(rooms, **values)
+        for i, rm in enumerate(rooms):
+            for f in fields:
+                st.rooms[rm][f] = values[f][i]
+        self.seen.updated(self.label, [f"rooms.{f}" for f in fields] + ([RELAY_NAMES] if "name" in fields else []))
+
+    def _set_clones(self, fields) -> None:
+        """``owner`` alone gives an owned record another owner, and CLONE_HEAR_ALL with it; ``room`` or ``hear`` alone change
+        an owned record; all three make a record anew, or (owner None) empty it."""
+        rng, st = self.rng, self.state
+        owned = [c for c, r in enumerate(st.records) if r[0] is not None]
+        if set(fields) == set(CLONE_FIELDS):
+            c = rng.randrange(st.nclones)
+            if c and rng.random() < 0.25:
+                self.roster.set_clones(c, owner=None)
+                st.records[c] = [None, None, NOTHING]
+            else:
+                st.records[c] = [rng.randrange(st.cap), rng.randrange(4), rng.choice((NOTHING, SWEARS, ALL))]
+                self.roster.set_clones(c, owner=st.records[c][0], room=st.records[c][1], hear=st.records[c][2])
+        else:
+            c = rng.choice(owned)
+            new = {"owner": rng.randrange(st.cap), "room": rng.randrange(4), "hear": rng.choice((NOTHING, SWEARS, ALL))}
+            self.roster.set_clones(c, **{f: new[f] for f in fields})
+            if "owner" in fields:
+                st.records[c][0], st.records[c][2] = new["owner"], ALL
+            if "room" in fields:
+                st.records[c][1] = new["room"]
+            if "hear" in fields:
+                st.records[c][2] = new["hear"]
+        self.seen.updated(self.label, [f"clones.{f}" for f in fields])
+
+    def _clear_review(self, _=None) -> None:
+        rooms = [self.rng.randrange(REVIEW_ROOMS) for _ in range(self.rng.randint(1, 2))]
+        self.roster.clear_review(rooms)
+        for rm in rooms:
+            self.state.rings.clear(rm)
+        self.seen.cleared(self.label, False)
+
+    def _clear_revtell(self, _=None) -> None:
+        slots = [self.rng.randrange(self.state.cap) for _ in range(self.rng.randint(1, 3))]
+        self.roster.clear_revtell(slots)
+        for j in slots:
+            self.state.tell_rings.clear(j)
+        self.seen.cleared(self.label, True)
+
+    # -------------------------------------------------------------- the calls
+    def _k(self, opts) -> int:
+        return opts.get("k") or self.rng.randint(1, 16)
+
+    def _text(self, opts) -> bytes:
+        if "text" in opts:
+            return opts["text"]
+        if "sized" in opts:
+            return text_of(self.rng, *opts["sized"])
+        return self.rng.choice(self.pool)
+
+    def _note(self, kind: str, timing: dict, bad: list) -> None:
+        self.last_timing = timing
+        self.bad += [{"step": self.steps, "roster": self.label, "kind": kind, **b} for b in bad[:3]]
+
+    def broadcasts(self, opts, relay: bool = False):
+        """K ``(text, rm, sender, force_listen, com_num)`` tuples, which of them to record, and for relay_many the clone
+        senders; a text to a room that holds a clone record is at most what its relay text allows."""
+        rng, st = self.rng, self.state
+        cloned = st.cloned_rooms() if relay else set()
+        want_record = opts.get("record", rng.random() < 0.4)
+        bs, record, csenders = [], [], []
+        for b in range(self._k(opts)):
+            rm = rng.choice((0, 0, 1, 2, 3, 4, 77, None))
+            if b == 0 and opts.get("record"):
+                rm = rng.randrange(REVIEW_ROOMS)
+            text = self._text(opts)
+            if "longest" in opts and cloned:
+                rm = rng.choice(sorted(cloned))
+                text = text_of(rng, 999, 999)[:longest_text(st.rooms[rm]["name"])]
+            elif rm in cloned:
+                text = text[:longest_text(st.rooms[rm]["name"])]
+            csender = None
+            if relay and rm is not None and rm < 4 and rng.random() < 0.3:
+                here = [c for c, r in enumerate(st.records) if r[0] is not None and r[1] == rm]
+                csender = rng.choice(here) if here else rng.randrange(st.nclones)
+            sender = None if csender is not None or rng.random() < 0.3 else rng.randrange(st.cap)
+            bs.append((text, rm, sender, rng.randrange(2), rng.choice(BROADCAST_COMS)))
+            record.append(bool(want_record and rm is not None and rm < REVIEW_ROOMS and (rng.random() < 0.6 or (b == 0 and opts.get("record")))))
+            csenders.append(csender)
+        for text, *_ in bs:
+            self.counts["longest_text"] = max(self.counts["longest_text"], len(text))
+            self.counts["empty_texts"] += not text
+        return bs, record, csenders
+
+    def _record_broadcasts(self, bs, record) -> None:
+        for (text, rm, *_), on in zip(bs, record):
+            if on:
+                self.state.rings.record(rm, text)
+                self.counts["recorded"] += 1
+
+    def _broadcast_many(self, opts) -> None:
+        bs, _, _ = self.broadcasts(opts)
+        r = self.roster.broadcast_many(bs)
+        self.seen.called(self.label, "broadcast_many", False, False)
+        if self.check:
+            m = self.state.table_model()
+            as_tables = [(t, None, int(rm is None), fl, com) for t, rm, s, fl, com in bs]
+            n, first = compare(r, expected(self.cpu, as_tables, [m.records(rm, s) for _, rm, s, _, _ in bs]), as_tables)
+            self._note("broadcast_many", r.timing, first[:1] if n else [])
+
+    def _plan_many(self, opts) -> None:
+        bs, record, _ = self.broadcasts(opts)
+        p = self.roster.plan_many(bs, record=record if any(record) else None)
+        self.seen.called(self.label, "plan_many", any(record), False)
+        if self.check:
+            self._note("plan_many", p.timing, plan_differences(self.cpu, p, bs, self.state.table_model()))
+            self._record_broadcasts(bs, record)
+
+    def _relay_many(self, opts) -> None:
+        bs, record, csenders = self.broadcasts(opts, relay=True)
+        rl = self.roster.relay_many(bs, record=record if any(record) else None,
+                                    clone_sender=csenders if any(c is not None for c in csenders) else None)
+        self.seen.called(self.label, "relay_many", any(record), False)
+        if self.check:
+            bad = plan_differences(self.cpu, rl.plan, bs, self.state.table_model())
+            self._note("relay_many", rl.timing, bad + self.relay_differences(bs, csenders, rl))
+            self._record_broadcasts(bs, record)
+
+    def relay_differences(self, bs, csenders, rl: device.Relay) -> list:
+        """As relay_differences of tests/device_relay_child.py, with the rooms' names from the state: the bitmap in whole
+        words, the owners and their colours, the relay text and its two variants chunk by chunk."""
+        st, bad = self.state, []
+        records = st.relay_records()
+        ignall = {j: u["ignall"] for j, u in st.users.items()}
+        for k, ((text, rm, _sender, _fl, _com), cs) in enumerate(zip(bs, csenders)):
+            want = relays(records, ignall, rm, cs, text)
+            self.counts["relays"] += len(want)
+            self.counts["clone_senders"] += cs is not None
+            where = {"broadcast": k, "rm": rm, "clone_sender": cs, "text": text[:40].decode("latin-1")}
+            flags = np.zeros(st.nclones, dtype=bool)
+            flags[want] = True
+            if rl.relay_bits[k].tolist() != device._pack(flags).tolist():
+                bad.append({**where, "what": "bitmap", "device": rl.relays(k).tolist()[:20], "model": want[:20]})
+                continue
+            if rl.owners(k).tolist() != [records[c][0] for c in want]:
+                bad.append({**where, "what": "owners"})
+            if rl.owner_colours(k).tolist() != [st.users[records[c][0]]["colour"] for c in want]:
+                bad.append({**where, "what": "owner colours"})
+            text2 = relay_text(st.rooms[rm]["name"], text) if want else b""
+            if rl.relay_text(k) != text2 or int(rl.text_sizes[k]) != (len(text2) if want else -1):
+                bad.append({**where, "what": "text", "device": rl.relay_text(k)[:60].decode("latin-1")})
+            for c in (0, 1):
+                ch = self.cpu.chunks(text2, c) if want else []
+                if rl.relay_chunks(k, c) != ch or rl.relay_variant(k, c) != b"".join(ch):
+                    bad.append({**where, "what": "variant", "colour": c, "device": [len(x) for x in rl.relay_chunks(k, c)],
+                                "model": [len(x) for x in ch]})
+        return bad
+
+    def _speakers(self, opts, record: bool) -> list:
+        valid = self.state.speakers(ring=record)
+        return [self.rng.choice(valid) for _ in range(self._k(opts))]
+
+    def _speak_many(self, opts) -> None:
+        rng, st = self.rng, self.state
+        record, ban = opts.get("record", rng.random() < 0.4), rng.random() < 0.5
+        events = [(j, rng.choice(SPEECH_COMS), opts["text"] if "text" in opts else text_of(rng, *opts["sized"])
+                   if "sized" in opts else fuzz_inpstr(rng), rng.randrange(11)) for j in self._speakers(opts, record)]
+        if opts.get("record"):                                          # a say at least: the call records
+            events[0] = (events[0][0], SAY, events[0][2], events[0][3])
+        recording = record and any(com in (SAY, EMOTE) for _, com, _, _ in events)
+        sp = self.roster.speak_many(events, ban_swearing=ban, record=record)
+        self.seen.called(self.label, "speak_many", recording, False)
+        if self.check:
+            self._note("speak_many", sp.timing, speech_differences(self.roster, st.users, events, ban, sp, self.counts["speech"]))
+            for slot, com, inpstr, wc in events:
+                m = model(st.users[slot], com, inpstr, wc, ban)
+                if record and m["recorded"]:
+                    st.rings.record(m["rm"], m["line"])
+                    self.counts["recorded"] += 1
+
+    def _input_many(self, opts) -> None:
+        rng, st = self.rng, self.state
+        record, ban = opts.get("record", rng.random() < 0.4), rng.random() < 0.5
+        read = lambda: (opts["text"][:-1] + b"\n" if "text" in opts else text_of(rng, opts["sized"][0] - 1, opts["sized"][1] - 1) + b"\n"
+                        if "sized" in opts else fuzz_read(rng))
+        reads = [(j, read()) for j in self._speakers(opts, record)]
+        inp = self.roster.input_many(reads, ban_swearing=ban, record=record)
+        self.seen.called(self.label, "input_many", bool(record), False)
+        if self.check:
+            self._note("input_many", inp.timing, input_differences(self.roster, st.users, reads, ban, inp, self.counts["input"]))
+            for slot, data in reads:
+                _, m = answer_of(st.users[slot], data, ban)
+                if record and m["recorded"]:
+                    st.rings.record(m["rm"], m["line"])
+                    self.counts["recorded"] += 1
+
+    def _tell_many(self, opts) -> None:
+        rng, st = self.rng, self.state
+        record = opts.get("record", rng.random() < 0.5)
+        valid = st.speakers()
+        named = [j for j, u in st.users.items() if u["name"]]
+        events = []
+        for _ in range(self._k(opts)):
+            ev = fuzz_event(rng, st.users, valid, named)
+            if "text" in opts:
+                ev = (ev[0], ev[1], opts["text"], 3)
+            elif "sized" in opts:                                       # a word aimed at somebody, and a long rest
+                word = ev[2].split(b" ")[0][:40] or b"x"
+                rest = text_of(rng, *opts["sized"])
+                ev = (ev[0], ev[1], (word + b" " + rest)[:len(rest)], 3)
+            events.append(ev)
+        pv = self.roster.tell_many(events, record=record)
+        self.seen.called(self.label, "tell_many", False, bool(record))
+        if self.check:
+            self._note("tell_many", pv.timing, private_differences(self.roster, st.users, events, pv, self.counts["tell"]))
+            for slot, com, inpstr, wc in events:
+                m = private(st.users, slot, com, inpstr, wc)
+                if record and m["outcome"] == TOLD:
+                    st.tell_rings.record(m["target"], m["line"])
+                    self.counts["told"] += 1
+
+    def _look_many(self, opts) -> None:
+        st = self.state
+        seated = [j for j, u in st.users.items() if u["room"] is not None]
+        slots = [self.rng.choice(seated) for _ in range(self._k(opts))]
+        lk = self.roster.look_many(slots)
+        self.seen.called(self.label, "look_many", False, False)
+        if self.check:
+            self._note("look_many", lk.timing, look_differences(st.users, st.rooms, slots, lk, self.counts["look"]))
+
+    def _review_many(self, opts) -> None:
+        rooms = [self.rng.randrange(REVIEW_ROOMS) for _ in range(self.rng.randint(1, 4))]
+        rv = self.roster.review_many(rooms)
+        self.seen.called(self.label, "review_many", True, False)
+        if self.check:
+            self._note("review_many", rv.timing, review_differences(rv, rooms, self.state.rings, self.counts["review"], self.cache))
+
+    def _revtell_many(self, opts) -> None:
+        slots = [self.rng.randrange(self.state.cap) for _ in range(self.rng.randint(1, 8))]
+        rv = self.roster.revtell_many(slots)
+        self.seen.called(self.label, "revtell_many", False, True)
+        if self.check:
+            self._note("revtell_many", rv.timing, review_differences(rv, slots, self.state.tell_rings, self.counts["review"], self.cache))
+
+
+# ------------------------------------------------------------------ the step streams
+def pair_blocks() -> list:
+    """[an update of one field, a call]: every kind after every field it reads, and after one it does not."""
+    blocks = [[op_for(f), (kind, {})] for kind in KINDS for f in sorted(READS[kind])]
+    return blocks + [[op_for(UNREAD[kind]), (kind, {})] for kind in KINDS]
+
+
+def clear_blocks() -> list:
+    """[a clear, the first call to touch those rings after it]."""
+    return ([[("clear_review",), (kind, {"record": True})] for kind in RECORDING_KINDS] + [[("clear_review",), ("review_many", {})]]
+            + [[("clear_revtell",), ("tell_many", {"record": True})], [("clear_revtell",), ("revtell_many", {})]])
+
+
+def random_op(rng: random.Random) -> tuple:
+    x = rng.random()
+    if x < 0.30:
+        return ("update", tuple(rng.sample(USER_FIELDS, rng.choice((1, 1, 2, 3, 5)))))
+    if x < 0.37:
+        return ("set_rooms", tuple(rng.sample(ROOM_FIELDS, rng.choice((1, 2, 7)))))
+    if x < 0.44:
+        return ("set_clones", rng.choice((("owner",), ("room",), ("hear",), CLONE_FIELDS)))
+    if x < 0.48:
+        return ("clear_review",)
+    if x < 0.52:
+        return ("clear_revtell",)
+    return (rng.choice(KINDS), {})
+
+
+def roster_steps(rng: random.Random, blocks: list, steps: int, each: int = 8) -> list:
+    """A roster's steps: the blocks dealt to it, every clear block, ``each`` calls of every kind, and random steps up to
+    ``steps``; the blocks stay whole, their order is shuffled."""
+    blocks = [list(b) for b in blocks] + clear_blocks() + [[(kind, {})] for kind in KINDS for _ in range(each)]
+    while sum(map(len, blocks)) < steps:
+        blocks.append([random_op(rng)])
+    rng.shuffle(blocks)
+    return [op for b in blocks for op in b]
+
+
+def new_roster(cap: int, nclones: int) -> device.Roster:
+    return device.Roster(cap, review_rooms=REVIEW_ROOMS, revtell=True, look_rooms=LOOK_ROOMS, clones=nclones)
+
+
+# ------------------------------------------------------------------ the parts of the device run
+def sequence_part(seed: int, cov: Coverage) -> dict:
+    """One roster for each capacity; 1 and 64 on their own, then 65 and 257 live at once, their steps alternating; when
+    the 65-slot one has made its steps it is closed and a roster of another capacity takes its handle and its turn."""
+    rng = random.Random(seed)
+    cpu = Cpu()
+    pool = [t for t, _ in fuzz_items(seed, 300)] + [b"", b"x" * 999, b"\n" * 999]
+    clones = (1, 65) if seed % 2 else (65, 1)
+    dealt = [[] for _ in range(6)]                                      # the 257-slot roster makes twice the steps
+    blocks = pair_blocks()
+    rng.shuffle(blocks)
+    for i, b in enumerate(blocks):
+        dealt[i % 6].append(b)
+    out = {"rosters": [], "n_bad": 0, "first_bad": [], "steps": 0, "counts": {}}
+
+    def make(cap, nclones, share, steps):
+        state = State(rng, cap, nclones)
+        roster = new_roster(cap, nclones)
+        state.seat(roster)
+        runner = Runner(rng, roster, state, f"{seed}:{cap}/{nclones}", cov, cpu=cpu, pool=pool)
+        return runner, roster_steps(rng, share, steps)
+
+    def done(runner):
+        runner.roster.close()
+        out["rosters"].append({"label": runner.label, "capacity": runner.state.cap, "clones": runner.state.nclones,
+                               "steps": runner.steps})
+        out["n_bad"] += len(runner.bad)
+        out["first_bad"] += runner.bad[:3 - len(out["first_bad"])]
+        out["steps"] += runner.steps
+        c = runner.counts
+        for name, n in (("recorded", c["recorded"]), ("told", c["told"]), ("relays", c["relays"]), ("clone_senders", c["clone_senders"]),
+                        ("empty_texts", c["empty_texts"]), ("lines_compared", c["review"]["lines_compared"])):
+            out["counts"][name] = out["counts"].get(name, 0) + n
+        out["counts"]["longest_text"] = max(out["counts"].get("longest_text", 0), c["longest_text"])
+
+    for i, cap in enumerate(CAPACITIES[:2]):
+        runner, steps = make(cap, clones[i % 2], dealt[i], STEPS_PER_ROSTER)
+        for op in steps:
+            runner.step(op)
+        done(runner)
+    a, a_steps = make(65, clones[0], dealt[2], STEPS_PER_ROSTER)
+    b, b_steps = make(257, clones[1], dealt[3] + dealt[4], 2 * STEPS_PER_ROSTER)
+    n = min(len(a_steps), len(b_steps) // 2)
+    for op_a, op_b in zip(a_steps[:n], b_steps[:n]):
+        a.step(op_a)
+        b.step(op_b)
+    for op in a_steps[n:]:
+        a.step(op)
+    handle = a.roster._handle                                           # mid-run: the 257-slot roster goes on
+    done(a)
+    c, c_steps = make(REPLACEMENT_CAPACITY, clones[1], dealt[5], STEPS_PER_ROSTER)
+    rest = b_steps[n:]
+    for i in range(max(len(c_steps), len(rest))):
+        if i < len(c_steps):
+            c.step(c_steps[i])
+        if i < len(rest):
+            b.step(rest[i])
+    out["handle_reused"] = handle is not None and c.roster._handle == handle
+    out["alternated"] = n + min(len(c_steps), len(rest))
+    done(c)
+    done(b)
+    return out
+
+
+def regrowth_part(seed: int) -> dict:
+    """Every ordered pair (A, B) of the table-reading kinds on a fresh 65-slot roster whose every mirror has been uploaded:
+    a tiny A, then B with 16 long texts, twice.  The first B finds the allocation made anew and uploads the table from the
+    pinned mirror, though the roster passes none; its repeat does not.  A pair that does not regrow at 16 doubles K."""
+    rng = random.Random(seed)
+    cap, nclones = 65, 65
+    state = State(rng, cap, nclones)
+    cpu, cov = Cpu(), Coverage()
+    tiny = {"k": 1, "text": b"hello", "record": False}
+    out = {"pairs": {}, "n_bad": 0, "first_bad": [], "table_slices": slice_of(4 * cap) + slice_of(cap), "with_update": 0}
+
+    def fresh():
+        roster = new_roster(cap, nclones)
+        state.seat(roster)
+        runner = Runner(rng, roster, state, "regrowth", cov, cpu=cpu, pool=[b"hello"])
+        for kind in ("tell_many", "look_many", "relay_many", "input_many"):          # every mirror goes up once
+            runner.step((kind, tiny))
+        return runner
+
+    def big(kind, k):
+        return (kind, {"k": k, "sized": (900, 999), "record": False, **({"longest": True} if kind == "relay_many" else {})})
+
+    def finish(runner):
+        runner.roster.close()
+        out["n_bad"] += len(runner.bad)
+        out["first_bad"] += runner.bad[:3 - len(out["first_bad"])]
+
+    for a in TABLE_KINDS:
+        for b in TABLE_KINDS:
+            if a == b:
+                continue
+            k = 16
+            while True:
+                runner = fresh()
+                runner.step((a, tiny))
+                state_rng = rng.getstate()
+                runner.step(big(b, k))
+                first = runner.last_timing["h2d_bytes"]
+                rng.setstate(state_rng)                                 # the same B call once more
+                runner.step(big(b, k))
+                again = runner.last_timing["h2d_bytes"]
+                finish(runner)
+                if first != again or k >= 1024:
+                    break
+                k *= 2
+            out["pairs"][f"{a}>{b}"] = {"k": k, "first": first, "repeat": again}
+            runner = fresh()                                            # Python's upload and the regrowth coincide
+            runner.step((a, tiny))
+            runner.step(op_for(rng.choice(TABLE_FIELDS)))
+            runner.step(big(b, k))
+            finish(runner)
+            out["with_update"] += 1
+    return out
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seed", type=int, default=20262)
+    ap.add_argument("--seed2", type=int, default=20263)
+    args = ap.parse_args()
+    if device.device_count() < 1:
+        print("no GPU visible", file=sys.stderr)
+        return 3
+    t0 = time.time()
+    cov = Coverage()
+    res = {"seeds": [args.seed, args.seed2], "sequence": [sequence_part(s, cov) for s in (args.seed, args.seed2)]}
+    res["coverage"] = cov.as_json()
+    t1 = time.time()
+    res["regrowth"] = regrowth_part(args.seed + 7)
+    res["seconds"] = {"sequence": round(t1 - t0, 1), "regrowth": round(time.time() - t1, 1)}
+    print("DEVICE_SEQUENCE " + json.dumps(res, default=str))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

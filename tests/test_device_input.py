@@ -493,4 +493,5 @@ def test_nothing_else_moved(input_run):
     h = m["input_h2d"]
     assert len(set(h["clean"])) == 1 and len(m["input_d2h"]) == 1       # the copies depend on the reads alone
     assert 16 * cap <= h["after_level_update"] - h["clean"][0] < 16 * cap + 256           # the speaker table alone
-    assert h["after_table_update"] - h["clean"][0] >= 5 * cap + 16 * cap                  # the table, and what lies after it
+    # the table alone, in its two 256-byte aligned slices: the speaker table behind it was not given and does not travel
+    assert 5 * cap <= h["after_table_update"] - h["clean"][0] < 5 * cap + 512 < 16 * cap

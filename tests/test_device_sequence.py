@@ -1,0 +1,349 @@
+"""The nine device calls of ``device.Roster`` interleaved: the host mirrors and their dirty flags, the pending ring
+clears, and the device allocation that is freed and made anew when a call needs more.
+
+Host tier (unmarked): ``device._load`` is replaced by a library that computes nothing and records what it is passed.  A
+seeded stream of updates, ``set_rooms``, ``set_clones``, clears and calls runs over one roster with every feature on, and
+an independent model says which fields are stale on the device: an update makes its fields stale, passing a mirror to the
+library cleans every field that lives in it.  After every call no field that call kind reads (``READS`` of
+tests/device_sequence_child.py, from the kernels) may be stale, and a pending clear goes down with the first call that
+touches its rings and with no later one.
+
+GPU tier: everything that touches the device runs in ONE short-lived child for the module
+(tests/device_sequence_child.py, under ``timeout``), and the tests assert on its JSON.
+"""
+from __future__ import annotations
+
+import json
+import random
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from device_sequence_child import (CAPACITIES, CLONE_FIELDS, FIELDS, KINDS, LOOK_ROOMS, MIRROR_OF, MIRRORS, READS, RECORDING_KINDS,
+                                   RELAY_NAMES, REPLACEMENT_CAPACITY, REVIEW_ROOMS, ROOM_FIELDS, STEPS_PER_ROSTER, TABLE_KINDS,
+                                   UNREAD, USER_FIELDS, Coverage, Runner, State, clear_blocks, new_roster, op_for, random_op,
+                                   slice_of)
+from nuts333_amd import device
+
+REPO = Path(__file__).resolve().parent.parent
+HOST_STEPS = 2000
+#: where each entry point takes its pending clears, and the argument that says whether it records (None: it always
+#: touches the rings); nd_roster_plan and nd_roster_relay take no clears and touch no ring
+CLEAR_AT = {"nd_roster_plan_record": (-1, None, False), "nd_roster_relay_record": (-1, None, False),
+            "nd_roster_review": (3, None, False), "nd_roster_revtell": (3, None, True), "nd_roster_speak": (13, 10, False),
+            "nd_roster_input": (11, 8, False), "nd_roster_tell": (13, 9, True)}
+ENTRY_POINTS = {"broadcast_many": ("nd_roster_fanout",), "plan_many": ("nd_roster_plan", "nd_roster_plan_record"),
+                "speak_many": ("nd_roster_speak",), "input_many": ("nd_roster_input",), "tell_many": ("nd_roster_tell",),
+                "look_many": ("nd_roster_look",), "relay_many": ("nd_roster_relay", "nd_roster_relay_record"),
+                "review_many": ("nd_roster_review",), "revtell_many": ("nd_roster_revtell",)}
+
+
+# ------------------------------------------------------------------ a library that computes nothing
+class FakeLibrary:
+    """Every ``nd_roster_*`` call returns 0 and is kept in ``calls`` as ``(name, args)``.  ``arrays`` maps an address
+    ``device._ptr`` handed out to its array, so that what an argument points at can be looked at."""
+
+    def __init__(self, arrays: dict):
+        self.calls, self.arrays, self.handles = [], arrays, 0
+        self._buffer = np.zeros(16, dtype=np.uint8)
+
+    def nd_roster_create(self, capacity):
+        self.handles += 1
+        return self.handles - 1
+
+    def nd_arena(self):
+        return self._buffer.ctypes.data
+
+    nd_write_sizes = nd_arena
+
+    def nd_last_error(self):
+        return b"the fake library has no errors"
+
+    def __getattr__(self, name):
+        if not name.startswith("nd_roster_"):
+            raise AttributeError(name)
+
+        def call(*args):
+            if name in ("nd_roster_destroy", "nd_roster_review_rooms", "nd_roster_revtell_rings", "nd_roster_look_rooms",
+                        "nd_roster_clones"):
+                return 0
+            self.calls.append((name, args))
+            if name == "nd_roster_tell":                                # tell_many indexes by what the device found
+                self.arrays[args[15]][:] = -1
+                self.arrays[args[16]][:] = -1
+            return 0
+        return call
+
+
+@pytest.fixture
+def fake(monkeypatch):
+    arrays: dict = {}
+    lib = FakeLibrary(arrays)
+    real = device._ptr
+
+    def ptr(a):
+        arrays[a.ctypes.data] = a
+        return real(a)
+
+    monkeypatch.setattr(device, "_ptr", ptr)
+    monkeypatch.setattr(device, "_load", lambda: lib)
+    return lib
+
+
+# ------------------------------------------------------------------ which fields are stale on the device
+class Host(Coverage):
+    """The staleness model, fed by the Runner's steps and by what the fake library was passed."""
+
+    def __init__(self, lib: FakeLibrary, roster: device.Roster, state: State):
+        super().__init__()
+        self.lib, self.roster, self.state = lib, roster, state
+        self.stale = set(FIELDS)                                        # nothing is on the device yet
+        self.stale_at_call = set()                                      # (kind, field) with the field stale when kind was called
+        self.awaiting, self.read_clean_later = set(), set()             # (kind, unread stale field) pairs, and those confirmed
+        self.masks = [np.zeros(REVIEW_ROOMS, dtype=np.uint8), np.zeros(state.cap, dtype=np.uint8)]
+        self.clear_pending = [False, False]
+        self.clears_sent = [0, 0]
+        self.step = None
+
+    def updated(self, label, fields) -> None:
+        super().updated(label, fields)
+        self.stale |= set(fields)
+
+    def cleared(self, label, tell, which=()) -> None:
+        super().cleared(label, tell)
+        self.masks[int(tell)][list(which)] = 1
+        self.clear_pending[int(tell)] = True
+
+    def names(self) -> np.ndarray:
+        out = np.zeros((LOOK_ROOMS, device._RELAY_NAME_ROW), dtype=np.uint8)
+        for i, rm in enumerate(self.state.rooms):
+            out[i, :len(rm["name"])] = np.frombuffer(rm["name"], dtype=np.uint8)
+            out[i, device.ROOM_NAME_LEN] = len(rm["name"])
+        return out
+
+    def called(self, label, kind, review_rings, revtell_rings) -> None:
+        super().called(label, kind, review_rings, revtell_rings)
+        assert len(self.lib.calls) == 1, f"{self.step}: {kind} made {len(self.lib.calls)} library calls"
+        name, args = self.lib.calls.pop()
+        assert name in ENTRY_POINTS[kind], f"{self.step}: {kind} went through {name}"
+        ints = {a for a in args if isinstance(a, int) and not isinstance(a, bool)}
+        passed = {m for m in MIRRORS if device._ptr(getattr(self.roster, m)) in ints}
+        want = self.names()
+        if any(a in self.lib.arrays and self.lib.arrays[a].shape == want.shape and np.array_equal(self.lib.arrays[a], want)
+               for a in ints):
+            passed.add("names")
+        before = set(self.stale)
+        self.stale_at_call |= {(kind, f) for f in before}
+        self.stale -= {f for f in FIELDS if MIRROR_OF[f] in passed}
+        read_stale = sorted(READS[kind] & self.stale)
+        assert not read_stale, (f"{self.step}: {kind} ({name}) read {read_stale} stale: it was passed {sorted(passed)}, dirty flags "
+                                f"{ {f: getattr(self.roster, f) for f in ('_dirty', '_speech_dirty', '_private_dirty', '_afk_dirty', '_rooms_dirty', '_udesc_dirty', '_clones_dirty')} }")
+        self.read_clean_later |= {(k, f) for k, f in self.awaiting if f in READS[kind]}
+        self.awaiting |= {(kind, f) for f in before - READS[kind]}
+        # the pending clears: down with the first call that records into, or reads, their rings, and with no later one
+        at = CLEAR_AT.get(name)
+        touches = [False, False]
+        if at is not None:
+            where, record_at, tell = at
+            if record_at is None or args[record_at]:
+                touches[int(tell)] = True
+                clear = args[where]
+                if self.clear_pending[int(tell)]:
+                    assert isinstance(clear, int), f"{self.step}: {name} touches the rings and left the pending clear behind"
+                    assert np.array_equal(self.lib.arrays[clear], self.masks[int(tell)]), f"{self.step}: {name} sent other clears"
+                    self.masks[int(tell)][:] = 0
+                    self.clear_pending[int(tell)] = False
+                    self.clears_sent[int(tell)] += 1
+                else:
+                    assert clear is None, f"{self.step}: {name} sent clears though none is pending"
+            else:
+                assert args[where] is None, f"{self.step}: {name} does not record and sent clears"
+        assert touches == [bool(review_rings), bool(revtell_rings)], f"{self.step}: {name} and the test disagree on the rings"
+        self.lib.arrays.clear()
+
+
+class HostRunner(Runner):
+    """The Runner, telling the model which rings a clear names."""
+
+    def _clear_review(self, _=None) -> None:
+        rooms = [self.rng.randrange(REVIEW_ROOMS) for _ in range(self.rng.randint(1, 2))]
+        self.roster.clear_review(rooms)
+        self.seen.cleared(self.label, False, rooms)
+
+    def _clear_revtell(self, _=None) -> None:
+        slots = [self.rng.randrange(self.state.cap) for _ in range(self.rng.randint(1, 3))]
+        self.roster.clear_revtell(slots)
+        self.seen.cleared(self.label, True, slots)
+
+
+def host_blocks(rng: random.Random) -> list:
+    """[an update, a call] for every kind after every single field alone, and after the pairs that share a mirror but not a
+    flag; the clear blocks; random steps up to HOST_STEPS."""
+    blocks = [[op_for(f), (kind, {})] for kind in KINDS for f in FIELDS]
+    for pair in (("vis", "afk"), ("name", "igntell"), ("level", "afk"), ("muzzled", "igntell")):
+        blocks += [[("update", pair), (kind, {})] for kind in KINDS]
+    blocks += [[("update", tuple(rng.sample(USER_FIELDS, n))), (kind, {})] for kind in KINDS for n in (2, 3, 6)]
+    # afk and igntell alone, then a kind that reads the speaker mirror without them, then one that reads them: the mirror
+    # is clean when the update comes, so only the flag of their own can bring it up
+    blocks += [[("speak_many", {}), ("update", (f,)), (between, {}), (reader, {})] for f, readers in
+               (("afk", ("tell_many", "look_many")), ("igntell", ("tell_many",))) for between in ("speak_many", "input_many")
+               for reader in readers]
+    blocks += clear_blocks() * 3
+    while sum(map(len, blocks)) < HOST_STEPS:
+        blocks.append([random_op(rng)])
+    rng.shuffle(blocks)
+    return blocks
+
+
+def host_run(lib, seed: int, ops=None, cap: int = 9, nclones: int = 4):
+    rng = random.Random(seed)
+    state = State(rng, cap, nclones)
+    roster = new_roster(cap, nclones)
+    state.seat(roster)
+    host = Host(lib, roster, state)
+    runner = HostRunner(rng, roster, state, "host", host, check=False)
+    if ops is None:                                                     # and a last round, so that whatever is stale is read
+        ops = [op for b in host_blocks(rng) for op in b] + [(kind, {}) for kind in KINDS]
+    for i, op in enumerate(ops):
+        host.step = f"step {i} {op[0]}{list(op[1]) if len(op) > 1 and op[0] not in KINDS else ''}"
+        runner.step(op)
+        assert runner.bad == [], runner.bad
+    return host, runner, ops
+
+
+# ------------------------------------------------------------------ host tier
+def test_the_field_tables_are_whole():
+    assert set(FIELDS) == set(USER_FIELDS) | {f"rooms.{f}" for f in ROOM_FIELDS} | {f"clones.{f}" for f in CLONE_FIELDS} | {RELAY_NAMES}
+    assert set(MIRROR_OF.values()) == set(MIRRORS) | {"names"} and len(KINDS) == 9 and set(READS) == set(KINDS)
+    r = new_roster(3, 2)
+    for m in MIRRORS:
+        assert isinstance(getattr(r, m), np.ndarray), m
+    for kind in KINDS:
+        assert READS[kind] <= set(FIELDS) and UNREAD[kind] in set(FIELDS) - READS[kind], kind
+        assert bool(READS[kind]) == (kind in TABLE_KINDS)
+    # what the kernels read beyond what update()'s docstring and the issue's table say: tell_many reads the level
+    assert "level" in READS["tell_many"] and "level" not in READS["speak_many"] and "command_mode" not in READS["tell_many"]
+    assert READS["relay_many"] & {f"rooms.{f}" for f in ROOM_FIELDS} == set()
+
+
+def test_no_call_kind_ever_reads_a_stale_field(fake):
+    host, runner, ops = host_run(fake, 20264)
+    assert len(ops) >= HOST_STEPS and runner.steps == len(ops)
+    assert all(n >= 20 for n in host.runs["host"].values()), host.runs
+    # every kind was called with every field stale: those it reads (and was passed, or the run had stopped above) ...
+    missing = [(k, f) for k in KINDS for f in FIELDS if (k, f) not in host.stale_at_call]
+    assert missing == []
+    # ... and those it does not read, which a kind that reads them found clean later
+    unread = {(k, f) for k in KINDS for f in FIELDS if f not in READS[k]}
+    assert unread <= host.awaiting and unread <= host.read_clean_later, sorted(unread - host.read_clean_later)[:5]
+    # a clear went down with each of the kinds that can carry it, and each kind was the first after a clear
+    assert host.clears_sent[0] >= 15 and host.clears_sent[1] >= 6
+    assert set(host.first_after_clear_review) == set(RECORDING_KINDS) | {"review_many"}
+    assert set(host.first_after_clear_revtell) == {"tell_many", "revtell_many"}
+    for kind in KINDS:
+        for f in READS[kind]:
+            assert host.after_read.get(f"{kind}/{f}", 0) > 0, (kind, f)
+        assert host.after_unread.get(kind, 0) > 0, kind
+
+
+@pytest.mark.parametrize("ops", [
+    # afk lives in the speaker mirror's flags byte with a flag of its own: a speak_many in between must not lose it
+    [("tell_many", {}), ("update", ("afk",)), ("speak_many", {}), ("look_many", {})],
+    [("look_many", {}), ("update", ("igntell",)), ("input_many", {}), ("tell_many", {})],
+    # ... and with a field of the other flag in the same update, whichever kind uploads the mirror cleans both
+    [("update", ("vis", "afk")), ("speak_many", {}), ("tell_many", {}), ("update", ("afk",)), ("look_many", {}), ("tell_many", {})],
+    [("update", ("name", "igntell")), ("tell_many", {}), ("speak_many", {}), ("look_many", {})],
+    # a name set between two relay_many calls, with a look_many that uploads the room table in between
+    [("relay_many", {}), ("set_rooms", ("name",)), ("look_many", {}), ("relay_many", {}), ("relay_many", {})],
+    # a clear waits for a call that touches its rings: the calls that do not record leave it pending
+    [("clear_review",), ("plan_many", {"record": False}), ("speak_many", {"record": False}), ("tell_many", {"record": True}),
+     ("relay_many", {"record": True}), ("review_many", {})],
+    [("clear_revtell",), ("tell_many", {"record": False}), ("review_many", {}), ("revtell_many", {}), ("tell_many", {"record": True})],
+], ids=["afk-speak-look", "igntell-input-tell", "vis+afk", "name+igntell", "names-between-relays", "review-clear-waits",
+        "revtell-clear-waits"])
+def test_the_rules_that_are_not_uniform_one_by_one(fake, ops):
+    host, runner, _ = host_run(fake, 5, ops=ops)
+    assert runner.steps == len(ops)
+
+
+def test_the_model_notices_a_mirror_that_is_not_passed(fake, monkeypatch):
+    """The safety property is not vacuous: a look_many that forgets the afk flag's own dirty flag is caught."""
+    real = device.Roster.look_many
+
+    def forgetful(self, slots):
+        keep, self._private_dirty = self._private_dirty, False
+        try:
+            return real(self, slots)
+        finally:
+            self._private_dirty = self._private_dirty or keep
+    monkeypatch.setattr(device.Roster, "look_many", forgetful)
+    with pytest.raises(AssertionError, match=r"look_many \(nd_roster_look\) read \['afk'\] stale"):
+        host_run(fake, 5, ops=[("speak_many", {}), ("update", ("afk",)), ("look_many", {})])
+
+
+# ------------------------------------------------------------------ GPU tier: one child for the module
+@pytest.fixture(scope="module")
+def sequence_run(built):
+    cmd = ["timeout", "-k", "10", "300", sys.executable, str(REPO / "tests" / "device_sequence_child.py")]
+    try:
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=360, cwd=str(REPO))
+    except subprocess.TimeoutExpired:
+        pytest.fail("device child did not finish in 360 s")
+    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_SEQUENCE ")]
+    if p.returncode != 0 or not lines:
+        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
+    res = json.loads(lines[-1][len("DEVICE_SEQUENCE "):])
+    print("\n[sequence]", json.dumps(res)[:6000])
+    return res
+
+
+@pytest.mark.gpu
+def test_a_seeded_interleaving_matches_the_models_at_every_step(sequence_run):
+    assert len(sequence_run["seeds"]) == 2 and len(sequence_run["sequence"]) == 2
+    for s in sequence_run["sequence"]:
+        caps = [r["capacity"] for r in s["rosters"]]
+        assert sorted(caps) == sorted(CAPACITIES + (REPLACEMENT_CAPACITY,)) and {r["clones"] for r in s["rosters"]} == {1, 65}
+        assert all(r["steps"] >= STEPS_PER_ROSTER for r in s["rosters"]), s["rosters"]
+        # two rosters live at once, their steps alternating; one closed mid-run, its handle taken by a roster of another size
+        assert s["handle_reused"] is True and s["alternated"] >= 2 * STEPS_PER_ROSTER
+        c = s["counts"]
+        assert c["recorded"] > 50 and c["told"] > 10 and c["relays"] > 50 and c["clone_senders"] > 10 and c["lines_compared"] > 100
+        assert c["empty_texts"] > 0 and c["longest_text"] >= 999
+        assert s["n_bad"] == 0, s["first_bad"]
+
+
+@pytest.mark.gpu
+def test_every_kind_ran_after_every_update_that_matters_to_it(sequence_run):
+    cov = sequence_run["coverage"]
+    assert len(cov["runs"]) == 2 * (len(CAPACITIES) + 1)
+    for label, runs in cov["runs"].items():
+        assert set(runs) == set(KINDS) and all(n >= 8 for n in runs.values()), (label, runs)
+    for kind in KINDS:
+        for f in READS[kind]:
+            assert cov["after_read"].get(f"{kind}/{f}", 0) > 0, (kind, f)
+        assert cov["after_unread"].get(kind, 0) > 0, kind
+    for kind in RECORDING_KINDS:
+        assert cov["first_after_clear_review"].get(kind, 0) > 0, kind
+    for kind in ("tell_many", "revtell_many"):
+        assert cov["first_after_clear_revtell"].get(kind, 0) > 0, kind
+
+
+@pytest.mark.gpu
+def test_a_regrown_allocation_gets_the_table_again_for_every_ordered_pair(sequence_run):
+    """The first B after the small A finds the allocation freed and made anew, and uploads the table from the pinned mirror
+    though the roster passed none: the table's two 256-byte aligned slices more than its repeat, and nothing else.  (On the
+    MI355X broadcast_many as B needs K = 32 to outgrow the allocation, every other kind K = 16.  Before upload() of
+    fanout.hip, 30 of the 42 pairs copied the room behind the table as well: 2,048 bytes with speak_many or input_many as B,
+    6,400 with tell_many, 9,728 with look_many, 2,304 with relay_many, where 768 were due.)"""
+    g = sequence_run["regrowth"]
+    pairs = {f"{a}>{b}" for a in TABLE_KINDS for b in TABLE_KINDS if a != b}
+    assert len(pairs) == 42 and set(g["pairs"]) == pairs and g["with_update"] == 42
+    for pair, p in sorted(g["pairs"].items()):
+        print(pair, p)
+    assert g["table_slices"] == slice_of(4 * 65) + slice_of(65) == 768
+    for pair, p in g["pairs"].items():
+        assert p["first"] > p["repeat"] and p["first"] - p["repeat"] == g["table_slices"], (pair, p)
+    assert g["n_bad"] == 0, g["first_bad"]
