@@ -54,6 +54,10 @@ variants, and per looker the users it is shown, in list order.
 room, ``clone_hear``), and ``Roster.relay_many(broadcasts)`` answers ``write_room_except`` whole for local users
 (nuts333.c:1401-1429): the :class:`Plan` of ``plan_many`` and, per broadcast, which clone records relay it to their owners,
 the relay text ``~FT[ <room name> ]:~RS `` + text and its two variants -- a :class:`Relay`.
+``Roster.update(last_login=, away=)`` keeps the two fields ``who()`` reads beside those, and ``Roster.who_many(slots, now=,
+date=)`` returns what ``.who`` writes for K lookers (nuts333.c:4792-4856, ``people == 0``) as a :class:`Who`: the two headers,
+the footer and the tail, a line per listed user with ``colour_com_count``'s padding, and per looker a bitmap of the lines it
+is sent.
 
 Input is validated before the device is touched (``ValueError``).  The library ``_build/libnuts_device.so`` is built by
 ``__graft_entry__.build()`` where ``hipcc`` exists, and on demand here when it is missing or older than its source.
@@ -187,6 +191,28 @@ LOOK_NAME, LOOK_DESC, LOOK_EXITS, LOOK_ACCESS, LOOK_TOPIC = range(5)
 
 #: a clone's ``clone_hear`` (nuts333.h:60-62): it relays nothing, lines that hold a swear word, or everything
 CLONE_HEAR_NOTHING, CLONE_HEAR_SWEARS, CLONE_HEAR_ALL = 0, 1, 2
+#: the kernels who_many runs before nuts_roster_speak_plan
+WHO_KERNELS = ("nuts_roster_who", "nuts_roster_who_shown")
+#: a slot's row of the who mirror (kWhoRec of fanout.hip): int32 last_login, int32 away (-1: none)
+_WHO_REC = 8
+#: the fixed texts of a Who, and the level names ``who()`` prints with %-4s (nuts333.h level_name, without the NONE entry)
+WHO_HEAD_LOGIN, WHO_HEAD, WHO_FOOT, WHO_TAIL = range(4)
+LEVEL_NAMES = (b"NEW", b"USER", b"WIZ", b"ARCH", b"GOD")
+#: long_date()'s buffer is dstr[80]
+WHO_DATE_LEN = 79
+#: colour_com_count over ``"  " + name + " " + desc + "~RS"`` is at most 25: a count takes a byte of its own and a run a
+#: ``~`` before it, and a run is at most three (``~FBBM``), so 12 bytes of name hold 6, 30 of description 18, and ``~RS`` is
+#: 1.  The longest line before the transducer is then a first field of 40 + 3 * 25 bytes, `` : ``, 4 of level, `` : ``, ``@``
+#: and an 80-byte service, `` : ``, ``-35791394``, `` mins.`` and ``~BR(AFK)\n``: 233 bytes, in a slot of 236 (kWhoRow)
+MAX_WHO_COUNT = 25
+MAX_WHO_LINE, _WHO_ROW = 40 + 3 * MAX_WHO_COUNT + 3 + 4 + 3 + 1 + SERV_NAME_LEN + 3 + 9 + 6 + 9, 236
+#: hard bounds of one who line through the transducer: the transducer's own, 6 bytes for each of its bytes and the reset;
+#: and since a write before the last holds at least 995 bytes (the buffer is flushed only past 994), those 1,402 bytes are
+#: at most two writes and the reset's
+MAX_WHO_LINE_BYTES, MAX_WHO_LINE_WRITES = 6 * MAX_WHO_LINE + 4, 3
+#: a who call's texts (who_fixed_at of fanout.hip): the login header and the header in 108 bytes each, the footer in 80,
+#: the tail in 8; then the lines
+_WHO_FIXED_AT, _WHO_FIXED_STRIDE = (0, 108, 216, 296), 304
 #: a look room's row of the names relay_many uploads (kRelayNameRow of fanout.hip): 20 bytes of name padded with zeros, then
 #: its length; and what a relay text is longer than its broadcast at most, ``~FT[ `` + a 20-byte name + `` ]:~RS ``
 #: (kRelaySlack): its slot among a relay call's relay texts is that much wider than the text
@@ -537,6 +563,71 @@ class Look:
 
 
 @dataclass
+class Who:
+    """What ``who(user, 0)`` writes for K lookers (``Roster.who_many``), as a delivery plan like a :class:`Look`: texts
+    with two variants each, and per looker which of them it gets.  The texts, T = 4 + L of them for the L listed users:
+    WHO_HEAD_LOGIN (the header of a looker at the name prompt), WHO_HEAD, WHO_FOOT and WHO_TAIL, then text ``4 + l`` is
+    line ``l``, the line of slot ``line_slots[l]``, transduced once however many lookers are sent it.  ``texts`` ..
+    ``write_sizes`` are exactly as in a Look.  Looker ``k`` is slot ``slots[k]`` with colour bit ``colour[k]`` and login
+    flag ``login[k]``; it is sent line ``l`` iff bit ``l % 32`` of ``shown[k, l // 32]`` is set (bits at or past L are
+    zero): a bitmap like a :class:`Plan`'s, since K x L flat lists would dominate the download."""
+    slots: np.ndarray             # int32 [K]
+    colour: np.ndarray            # uint8 [K]   the lookers' colour bits
+    login: np.ndarray             # uint8 [K]   and whether they are at the name prompt
+    line_slots: np.ndarray        # int32 [L]
+    shown: np.ndarray             # uint32 [K, max(1, ceil(L / 32))]
+    texts: np.ndarray             # uint8, flat: the composed texts; gaps are allowed and unspecified
+    text_starts: np.ndarray       # int64 [T]
+    text_sizes: np.ndarray        # int64 [T]
+    variants: np.ndarray          # uint8, flat
+    variant_starts: np.ndarray    # int64 [T, 2]
+    variant_sizes: np.ndarray     # int64 [T, 2]
+    write_counts: np.ndarray      # int32 [T, 2]
+    write_sizes: np.ndarray       # int32 [T, 2, MAX_WRITES]   entries at or past write_counts are unspecified
+    timing: dict = field(default_factory=dict)
+
+    def _check(self, k: int) -> None:
+        if not 0 <= k < len(self.slots):
+            raise IndexError(f"no who {k}: {len(self.slots)} whos")
+
+    def lines(self, k: int) -> np.ndarray:
+        """The lines who ``k`` is sent, ascending."""
+        self._check(k)
+        bits = np.unpackbits(np.ascontiguousarray(self.shown[k], dtype="<u4").view(np.uint8), bitorder="little")
+        return np.flatnonzero(bits[:len(self.line_slots)])
+
+    def text_numbers(self, k: int) -> list[int]:
+        """The texts who ``k`` is sent, in who()'s order: one ``write_user`` each."""
+        listed = [4 + int(l) for l in self.lines(k)]
+        return [WHO_HEAD_LOGIN if self.login[k] else WHO_HEAD] + listed + [WHO_FOOT, WHO_TAIL]
+
+    def text(self, t: int) -> bytes:
+        """Text ``t`` before the transducer."""
+        if not 0 <= t < len(self.text_sizes) or self.text_sizes[t] < 0:
+            raise IndexError(f"no text {t}")
+        at = int(self.text_starts[t])
+        return self.texts[at:at + int(self.text_sizes[t])].tobytes()
+
+    def text_chunks(self, t: int, c: int) -> list[bytes]:
+        """Text ``t`` for colour bit ``c`` as the ``write(2)`` chunks the reference would issue."""
+        if not 0 <= t < len(self.text_sizes) or c not in (0, 1):
+            raise IndexError(f"no text ({t}, {c})")
+        at = int(self.variant_starts[t, c])
+        return _split(self.variants[at:at + int(self.variant_sizes[t, c])].tobytes(),
+                      self.write_sizes[t, c, :int(self.write_counts[t, c])], f"text ({t}, {c})", "the variant")
+
+    def chunks(self, k: int) -> list[bytes]:
+        """The ``write(2)`` payloads of who ``k``, in order."""
+        self._check(k)
+        c = int(self.colour[k])
+        return [ch for t in self.text_numbers(k) for ch in self.text_chunks(t, c)]
+
+    def output(self, k: int) -> bytes:
+        """Everything who ``k`` writes: the concatenation of ``chunks(k)``."""
+        return b"".join(self.chunks(k))
+
+
+@dataclass
 class Relay:
     """What ``write_room_except`` does with K broadcasts for a roster with clone records (``Roster.relay_many``): ``plan``
     is the :class:`Plan` of the same broadcasts for the slots, and clone record ``c`` relays broadcast ``k`` iff bit
@@ -824,6 +915,9 @@ def _load():
         lib.nd_roster_look_rooms.restype = ctypes.c_int
         lib.nd_roster_look.argtypes = [ctypes.c_int, ctypes.c_int, P, P, ctypes.c_int] + [P] * 18 + [ctypes.POINTER(_RosterTiming)]
         lib.nd_roster_look.restype = ctypes.c_int
+        lib.nd_roster_who.argtypes = ([ctypes.c_int, ctypes.c_int, P, ctypes.c_int, ctypes.c_int32, P, ctypes.c_int] + [P] * 13
+                                      + [ctypes.POINTER(_RosterTiming)])
+        lib.nd_roster_who.restype = ctypes.c_int
         lib.nd_roster_clones.argtypes = [ctypes.c_int, ctypes.c_int]
         lib.nd_roster_clones.restype = ctypes.c_int
         lib.nd_roster_relay.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int64] + [P] * 22 + [ctypes.POINTER(_RosterTiming)]
@@ -1069,6 +1163,11 @@ class Roster:
         self._rooms_dirty = True
         self._udesc = np.zeros((self.capacity, _DESC_ROW), dtype=np.uint8)
         self._udesc_dirty = True
+        # what who_many alone reads and uploads beside those: 8 bytes per slot -- int32 last_login, int32 away (-1: none) --
+        # after update(last_login=, away=)
+        self._who = np.zeros((self.capacity, 2), dtype=np.int32)
+        self._who[:, 1] = -1
+        self._who_dirty = True
         # what relay_many alone reads and uploads: the clone records, kept apart from the slots -- `clones` int32 owners
         # (-1: an empty record), then `clones` int32 rooms, then `clones` clone_hear bytes -- after set_clones; and the look
         # rooms' names, 24 bytes per room, when one differs from those relay_many uploaded last (None: none yet)
@@ -1112,7 +1211,7 @@ class Roster:
 
     def update(self, slots, *, room=_KEEP, login=_KEEP, ignall=_KEEP, ignshout=_KEEP, colour=_KEEP, name=_KEEP,
                vis=_KEEP, muzzled=_KEEP, command_mode=_KEEP, level=_KEEP, afk=_KEEP, igntell=_KEEP,
-               afk_mesg=_KEEP, desc=_KEEP) -> None:
+               afk_mesg=_KEEP, desc=_KEEP, last_login=_KEEP, away=_KEEP) -> None:
         """Set fields of ``slots`` (a slot or a sequence of them).  Each field given is one value for every slot or a
         sequence of one per slot; a field not given stays as it is.  ``room`` is None (no room) or an int in
         [0, ROOM_LIMIT); the flags are 0/1 or bools.  A slot given more than once takes its last values.  Nothing
@@ -1132,7 +1231,12 @@ class Roster:
         no other call copies more for it.
 
         ``desc`` (bytes or str of 0 .. USER_DESC_LEN bytes, no NUL, empty at first) is ``user->desc``, which ``look()``
-        shows beside a name.  It lives in a mirror of its own that only :meth:`look_many` uploads."""
+        shows beside a name.  It lives in a mirror of its own that only :meth:`look_many` and :meth:`who_many` upload.
+
+        ``last_login`` (an int in [0, 2^31), 0 at first) is ``user->last_login``, and ``away`` (None at first, or a look
+        room whose record has a netlink) the link a user without a room left through, whose service ``who()`` shows in
+        place of a room.  They live in a mirror of their own, 8 bytes per slot, that only ``who_many`` uploads: an update
+        of these two alone marks no other mirror."""
         self._check_open()
         if isinstance(slots, (int, np.integer)):
             slots = [slots]
@@ -1182,6 +1286,23 @@ class Roster:
         descs = None
         if desc is not _KEEP:
             descs = _one_or_each("desc", desc, n, lambda x: _limited_text("desc", x, USER_DESC_LEN), _is_text)
+        def login_time(v):
+            if not _is_int(v, 0, 2**31 - 1):
+                raise ValueError(f"last_login must be an int in [0, 2^31), not {v!r}")
+            return int(v)
+
+        def away_room(v):
+            if v is None:
+                return -1
+            if isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"away must be None or a look room, not {v!r}")
+            v = self._look_room(v)
+            if not self._room_rec[v, 24] & 1:
+                raise ValueError(f"away: room {v} has no netlink")
+            return v
+
+        logins = None if last_login is _KEEP else per_slot("last_login", last_login, login_time, np.int32)
+        aways = None if away is _KEEP else per_slot("away", away, away_room, np.int32)
         _, last = np.unique(idx[::-1], return_index=True)        # each slot's last position: last write wins
         keep = n - 1 - last
         at = idx[keep]
@@ -1212,12 +1333,18 @@ class Roster:
                 self._udesc[j, :len(descs[p])] = np.frombuffer(descs[p], dtype=np.uint8)
                 self._udesc[j, USER_DESC_LEN] = len(descs[p])
             self._udesc_dirty = True
+        if logins is not None:
+            self._who[at, 0] = logins[keep]
+        if aways is not None:
+            self._who[at, 1] = aways[keep]
+        if logins is not None or aways is not None:
+            self._who_dirty = True
         if names is not None or levels is not None or speech.keys() - {"afk", "igntell"}:
             self._speech_dirty = True
         if speech.keys() & {"afk", "igntell"}:
             self._private_dirty = True
         if rooms is not None or flags or not (names is not None or speech or levels is not None or mesgs is not None
-                                              or descs is not None):
+                                              or descs is not None or logins is not None or aways is not None):
             self._dirty = True
 
     def table(self, rm, sender) -> np.ndarray:
@@ -1860,7 +1987,7 @@ class Roster:
         synchronise, whatever K and the capacity.  The bound counts a line per slot of the call's distinct rooms and a
         member per such slot and looker; a call whose variant bound exceeds MANY_ARENA_CAP is refused.
 
-        Out of scope: clones and remote users in the list, ``.go`` and ``.who``."""
+        Out of scope: clones and remote users in the list, and ``.go``.  ``.who`` is :meth:`who_many`."""
         self._check_open()
         if isinstance(slots, (str, bytes, bytearray)) or not hasattr(slots, "__len__"):
             raise ValueError(f"slots must be a sequence of slots, not {slots!r}")
@@ -1926,6 +2053,94 @@ class Roster:
                     text_starts=tstarts, text_sizes=clen.astype(np.int64), variants=var,
                     variant_starts=_variant_starts(tstarts, clen), variant_sizes=vn, write_counts=vw, write_sizes=vwsz,
                     timing=_timing_of(t))
+
+    def who_many(self, slots, *, now, date) -> Who:
+        """What ``who(user, 0)`` writes for each of ``slots``, K >= 1 lookers (duplicates allowed), in one device call
+        (nuts333.c:4792-4856).  ``now`` is ``time(0)``, an int in [0, 2^31); ``date`` is ``long_date(1)``, bytes or str of
+        0 .. WHO_DATE_LEN bytes without a NUL.  A looker needs only to be a slot: its ``login`` flag picks the header
+        (``who`` typed at the name prompt, c:1470), its level and colour are those in the roster.
+
+        The listed users are the slots with a name and ``login == 0``, in ascending slot order, L of them; the looker is
+        among them.  Each needs a room with a room record, one in ``[0, look_rooms)``, or no room and an ``away``;
+        otherwise the call raises ``ValueError("who: slot N ...")`` before the device is touched.  For looker ``u`` the
+        :class:`Who` holds, in order, what these ``write_user`` calls send: ``"\\n~BB*** Current users <date> ***\\n\\n"``
+        (without ``~BB`` at the name prompt); a line per listed user ``j`` with ``vis[j] or level[j] <= level[u]``; the
+        footer ``"\\nThere are %d visible, %d invisible, 0 remote users.\\nTotal of %d users"`` of L less the invisible, the
+        invisible, and L, the same for every looker; ``".\\n\\n"``.  A line is ``"%-*s : %-4s : %-12s : %d mins."`` of
+        ``"  <name> <desc>~RS"`` (``*`` first when invisible) padded to ``40 + 3 * colour_com_count`` of it, the level's
+        name, the room's name or ``@`` and the ``away`` link's service, and ``(int)(now - last_login) / 60``; then
+        ``"~BR(AFK)\\n"`` or ``"\\n"``.  ``colour_com_count`` (c:2563-2583) is not the transducer's count: after a match
+        it advances one byte and walks on through the rest of the table, so ``~FBBM`` counts 3.
+
+        One upload (the table, the speaker state, the room table, the descriptions and the login times only after an
+        update of theirs; with none, the lookers and the date alone), three kernel launches (WHO_KERNELS, then
+        nuts_roster_speak_plan), one download at the bound size and one synchronise, whatever K and the capacity.  A
+        call whose variant and bitmap bound exceeds MANY_ARENA_CAP is refused.
+
+        Out of scope: ``.people``, clones and remote users."""
+        self._check_open()
+        if isinstance(slots, (str, bytes, bytearray)) or not hasattr(slots, "__len__"):
+            raise ValueError(f"slots must be a sequence of slots, not {slots!r}")
+        if len(slots) == 0:
+            raise ValueError("empty call: no lookers")
+        if len(slots) * self.capacity >= 2**31 - 1:
+            raise ValueError(f"{len(slots)} whos at {self.capacity} slots: K x capacity must be below 2^31 - 1")
+        lookers = []
+        for k, v in enumerate(slots):
+            try:
+                lookers.append(self._slot(v))
+            except ValueError as e:
+                raise ValueError(f"who {k}: {e}") from None
+        if not _is_int(now, 0, 2**31 - 1) or isinstance(now, (bool, np.bool_)):
+            raise ValueError(f"now must be an int in [0, 2^31), not {now!r}")
+        date = _limited_text("date", date, WHO_DATE_LEN)
+        listed = np.flatnonzero((self._speech[:, USER_NAME_LEN] != 0) & ((self._flags & ROSTER_FLAGS["login"]) == 0))
+        rooms, away = self._room[listed], self._who[listed, 1]
+        linked = np.zeros(len(listed), dtype=bool)
+        ok = (away >= 0) & (away < self.look_rooms)
+        linked[ok] = (self._room_rec[away[ok], 24] & 1) != 0
+        bad = np.flatnonzero(~(((rooms >= 0) & (rooms < self.look_rooms)) | ((rooms < 0) & linked)))
+        if len(bad):
+            j, rm = int(listed[bad[0]]), int(rooms[bad[0]])
+            raise ValueError(f"who: slot {j} is in " + (f"room {rm}, which has no room record (look_rooms is {self.look_rooms})"
+                             if rm >= 0 else "no room and is not away over a netlink (update(away=))"))
+        k, nl = len(lookers), len(listed)
+        texts, words = 4 + nl, max(1, (nl + 31) // 32)
+        ctext_bytes = _WHO_FIXED_STRIDE + _WHO_ROW * nl
+        bound = _variant_at(ctext_bytes, texts) + 4 * k * words
+        if bound > MANY_ARENA_CAP:
+            raise ValueError(f"call too large: its variant and bitmap bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
+                             f"(MANY_ARENA_CAP): split it")
+        lib = _load()
+        handle = self._device_handle(lib)
+        slot_arr = np.array(lookers, dtype=np.int32)
+        dbuf = np.frombuffer(date, dtype=np.uint8) if date else np.zeros(1, dtype=np.uint8)
+        clen = np.empty(texts, dtype=np.int32)
+        vn, vw = np.empty((texts, 2), dtype=np.int64), np.empty((texts, 2), dtype=np.int32)
+        vwsz = np.empty((texts, 2, MAX_WRITES), dtype=np.int32)
+        ctext = np.empty(ctext_bytes, dtype=np.uint8)
+        var = np.empty(_variant_at(ctext_bytes, texts), dtype=np.uint8)
+        line_slot = np.full(max(nl, 1), -1, dtype=np.int32)
+        shown = np.zeros((k, words), dtype=np.uint32)
+        t = _RosterTiming()
+        rc = lib.nd_roster_who(handle, k, _ptr(slot_arr), nl, int(now), _ptr(dbuf), len(date),
+                               _ptr(self._table) if self._dirty else None,
+                               _ptr(self._speech) if self._speech_dirty or self._private_dirty else None,
+                               _ptr(self._rooms) if self._rooms_dirty and self.look_rooms else None,
+                               _ptr(self._udesc) if self._udesc_dirty else None,
+                               _ptr(self._who) if self._who_dirty else None, _ptr(clen), _ptr(vn), _ptr(vw), _ptr(vwsz),
+                               _ptr(ctext), _ptr(var), _ptr(line_slot), _ptr(shown), ctypes.byref(t))
+        _check(rc, "device who failed")
+        self._dirty = self._speech_dirty = self._private_dirty = self._udesc_dirty = self._who_dirty = False
+        if self.look_rooms:
+            self._rooms_dirty = False
+        tstarts = np.concatenate([np.array(_WHO_FIXED_AT, dtype=np.int64),
+                                  _WHO_FIXED_STRIDE + _WHO_ROW * np.arange(nl, dtype=np.int64)])
+        return Who(slots=slot_arr, colour=((self._flags[slot_arr] & ROSTER_FLAGS["colour"]) != 0).astype(np.uint8),
+                   login=((self._flags[slot_arr] & ROSTER_FLAGS["login"]) != 0).astype(np.uint8),
+                   line_slots=line_slot[:nl], shown=shown, texts=ctext, text_starts=tstarts,
+                   text_sizes=clen.astype(np.int64), variants=var, variant_starts=_variant_starts(tstarts, clen),
+                   variant_sizes=vn, write_counts=vw, write_sizes=vwsz, timing=_timing_of(t))
 
     def set_clones(self, clones, *, owner=_KEEP, room=_KEEP, hear=_KEEP) -> None:
         """Set fields of the clone records ``clones`` (a record or a sequence of them, each in ``[0, clones)``), by the

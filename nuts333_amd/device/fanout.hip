@@ -2108,6 +2108,348 @@ static_assert(5 + kRoomNameLen + 7 <= 64 && kRelaySlack == 32, "roster_relay: th
 static_assert(kRelayNameRow % 4 == 0 && kRoomNameLen < kRelayNameRow, "roster_relay: a name row is whole words and holds its length");
 static_assert(kArrSize - 1 < kTextSize, "nuts_roster_speak_plan: a relay text fits its LDS text");
 
+// ------------------------------------------------------------------ who() of a resident roster
+//
+// who(user, 0) (nuts333.c:4792-4856) sends a user the whole talker: a header with the date, a line per user it may see, a
+// footer with the counts and a tail.  Like look() it is texts with two variants each and per looker a choice among them:
+// a line depends on its user alone, the footer on the roster alone, and only the header (the looker's login flag) and
+// which lines are sent (an invisible user above the looker's level is not) depend on the looker.  The listed users are
+// the slots with a name and no login flag, in ascending slot order: line l is the l-th of them.
+// A roster keeps one more table for it, 8 bytes per slot in a device allocation of its own that never moves: last_login
+// (int32) and away (int32: the look room whose netlink a roomless user left through, -1: none).
+//   who      nuts_roster_who, one launch whose blocks take roles by their index:
+//            LINE BLOCKS, one per 256 slots.  A block first counts the listed slots before its own -- a ballot per wave and
+//            step over the name lengths and login flags, the four waves' counts through LDS -- then ranks its own 256 the
+//            same way: no atomics, the same result on every run.  The lane of a listed slot composes its line (who_line)
+//            into the line's 236-byte slot of the composed-text buffer, whole, as look_line does and for its reason.
+//            THE FIXED BLOCK counts the listed and the invisible slots of the whole roster, and its wave 0 composes the two
+//            headers, the footer and the tail with compose().  The host sized the call for nl lines from its mirror:
+//            a different count here is a violation, and the lines past the count are void.
+//            COPY BLOCKS past those copy freshly uploaded tables into the kept allocations.
+//            The kernel also writes every text's offset, so that the upload carries the lookers and the date alone.
+//   shown    nuts_roster_who_shown, a block per looker and 256 lines, a lane per line: line l of slot line_slot[l] is
+//            sent unless its user is invisible and above the looker's level.  A wave's 64 answers (__ballot) are two
+//            words of the looker's bitmap; lanes past nl vote false, so the tail bits are zero.  It reads line_slot, which
+//            blocks of nuts_roster_who wrote: hence a launch of its own.
+//   plan     nuts_roster_speak_plan with no room lines (k = 0), a block per text, as after nuts_roster_look.
+constexpr int kWhoRec = 8;                                 // a slot's row of the who table: last_login, away
+constexpr int kWhoFixed = 4;                               // the login header, the header, the footer, the tail
+constexpr int kWhoHeadRow = 108, kWhoFootRow = 80, kWhoTailRow = 8;
+constexpr int kWhoFixedStride = 2 * kWhoHeadRow + kWhoFootRow + kWhoTailRow;
+constexpr int who_fixed_at(int i) { return i == 0 ? 0 : i == 1 ? kWhoHeadRow : i == 2 ? 2 * kWhoHeadRow : 2 * kWhoHeadRow + kWhoFootRow; }
+constexpr int kWhoDateLen = 79;                            // long_date's dstr[80]
+// colour_com_count is at most 25 over "  " + name + " " + desc + "~RS": a count takes a byte of its own and a '~' before
+// the first of a run, and a run is at most three ("~FBBM"), so 12 bytes of name hold 6, 30 of description 18, and ~RS is 1
+constexpr int kWhoMaxCount = 25;
+constexpr int kWhoPadMax = 40 + 3 * kWhoMaxCount;          // the widest first field
+constexpr int kWhoLineMax = kWhoPadMax + 3 + 4 + 3 + 1 + kServNameLen + 3 + 9 + 6 + 9;   // 233: ... " : " -35791394 " mins." ~BR(AFK)\n
+constexpr int kWhoRow = 236;                               // a line's slot
+
+constexpr int64_t who_ctext_bytes(int64_t nl) { return kWhoFixedStride + nl * kWhoRow; }
+
+struct WhoArgs {
+    const int32_t* room;         // [capacity] the roster's table
+    const uint8_t* slotf;        // [capacity] and its flag bytes: login
+    const uint8_t* speech;       // the tables this call reads, the uploads or the kept ones, as LookArgs
+    const uint8_t* speech_new;
+    uint8_t* speech_keep;
+    const uint8_t* rooms;
+    const uint8_t* rooms_new;
+    uint8_t* rooms_keep;
+    const uint8_t* udesc;
+    const uint8_t* udesc_new;
+    uint8_t* udesc_keep;
+    const uint8_t* who;          // [capacity * 8] last_login and away
+    const uint8_t* who_new;
+    uint8_t* who_keep;
+    const int32_t* slot;         // [k] the lookers
+    const uint8_t* date;         // [date_len] long_date(1)
+    int k, nl, capacity, look_rooms, words, date_len;   // words: bitmap words per looker, max(1, ceil(nl / 32))
+    int32_t now;
+    int* violations;             // texts past their slots, a listed slot without a room name, a count that is not nl
+    int32_t* clen;               // [4 + nl] the texts' lengths; -1: a line past the count
+    int32_t* ctext_off;          // [4 + nl] where each text's slot starts in ctext
+    uint8_t* ctext;              // the texts
+    int32_t* line_slot;          // [nl] the slot each line is of
+    uint32_t* shown;             // [k * words] the lookers' bitmaps
+};
+
+// Where "XY" stands in colcom[] (nuts333.h:249-255), or -1.
+__device__ __forceinline__ int who_code(uint8_t x, uint8_t y)
+{
+    if (x == 'F' || x == 'B') {
+        const int c = y == 'K' ? 0 : y == 'R' ? 1 : y == 'G' ? 2 : y == 'Y' ? 3 : y == 'B' ? 4 : y == 'M' ? 5 : y == 'T' ? 6
+                      : y == 'W' ? 7 : -1;
+        return c < 0 ? -1 : (x == 'F' ? 5 : 13) + c;
+    }
+    return x == 'R' ? (y == 'S' ? 0 : y == 'V' ? 4 : -1) : x == 'O' ? (y == 'L' ? 1 : -1) : x == 'U' ? (y == 'L' ? 2 : -1)
+           : x == 'L' ? (y == 'I' ? 3 : -1) : -1;
+}
+
+// colour_com_count (c:2563-2583) over s[0 .. len): after a match it advances one byte and goes on through the rest of
+// the table there, so "~FBBM" counts FB, BB and BM.  Two bytes name at most one entry, so the table walk from entry
+// `from` on matches iff that entry is not before `from`.
+__device__ __forceinline__ int who_count(const uint8_t* s, int len)
+{
+    int i = 0, cnt = 0;
+    while (i < len) {
+        if (s[i++] != '~') continue;
+        int from = 0;
+        while (i + 1 < len) {
+            const int c = who_code(s[i], s[i + 1]);
+            if (c < from) break;
+            cnt++;
+            i++;
+            from = c + 1;
+        }
+    }
+    return cnt;
+}
+
+// Slot j's line (c:4838-4848) into row, by one lane; returns its length.  rname is the room's name or, with `at`, the
+// service a roomless user is away over.
+__device__ __forceinline__ int who_line(uint8_t* row, const uint4 rec, int nlen, const uint8_t* udesc, int j, const uint8_t* rname,
+                                        int rlen, bool at, int32_t mins, int* violations)
+{
+    const uint32_t state = rec.w >> 8 & 0xff, level = rec.w >> 16 & 0xff;
+    const uint4 d0 = reinterpret_cast<const uint4*>(udesc)[2 * j], d1 = reinterpret_cast<const uint4*>(udesc)[2 * j + 1];
+    const int dl = (int)(d1.w >> 16 & 0xff), dlen = dl < kUserDescLen ? dl : kUserDescLen;
+    int len = (state & kVis) ? row_lit(row, 0, "  ") : row_lit(row, 0, "* ");
+#pragma unroll
+    for (int i = 0; i < kNameLen; i++) {                       // all twelve: what follows overwrites the padding
+        const uint32_t v = i < 4 ? rec.x : i < 8 ? rec.y : rec.z;
+        row[len + i] = (uint8_t)(v >> (8 * (i & 3)));
+    }
+    len += nlen;
+    row[len++] = ' ';
+#pragma unroll
+    for (int i = 0; i < kUserDescLen; i++) {                   // likewise
+        const uint32_t v = i < 4 ? d0.x : i < 8 ? d0.y : i < 12 ? d0.z : i < 16 ? d0.w : i < 20 ? d1.x : i < 24 ? d1.y
+                           : i < 28 ? d1.z : d1.w;
+        row[len + i] = (uint8_t)(v >> (8 * (i & 3)));
+    }
+    len += dlen;
+    len = row_lit(row, len, "~RS");
+    int width = 40 + 3 * who_count(row, len);                  // %-*s
+    if (width > kWhoPadMax) {                                  // never: kWhoMaxCount
+        atomicAdd(violations, 1);
+        width = kWhoPadMax;
+    }
+    while (len < width) row[len++] = ' ';
+    len = row_lit(row, len, " : ");
+    const uint32_t lname = level == 0 ? 'N' | 'E' << 8 | 'W' << 16 | (uint32_t)' ' << 24
+                           : level == 1 ? 'U' | 'S' << 8 | 'E' << 16 | (uint32_t)'R' << 24
+                           : level == 2 ? 'W' | 'I' << 8 | 'Z' << 16 | (uint32_t)' ' << 24
+                           : level == 3 ? 'A' | 'R' << 8 | 'C' << 16 | (uint32_t)'H' << 24
+                                        : 'G' | 'O' << 8 | 'D' << 16 | (uint32_t)' ' << 24;      // %-4s
+#pragma unroll
+    for (int i = 0; i < 4; i++) row[len + i] = (uint8_t)(lname >> (8 * i));
+    len = row_lit(row, len + 4, " : ");
+    const int field = len + 12;                                // %-12s
+    if (at) row[len++] = '@';
+    for (int i = 0; i < rlen; i++) row[len + i] = rname[i];
+    len += rlen;
+    while (len < field) row[len++] = ' ';
+    len = row_lit(row, len, " : ");
+    if (mins < 0) row[len++] = '-';                            // %d
+    uint32_t v = mins < 0 ? (uint32_t)(-mins) : (uint32_t)mins;
+    int digits = 1;
+    for (uint32_t x = v; x >= 10; x /= 10) digits++;
+    for (int i = digits - 1; i >= 0; i--, v /= 10) row[len + i] = (uint8_t)('0' + v % 10);
+    len = row_lit(row, len + digits, " mins.");
+    if (state & kAfk) len = row_lit(row, len, "~BR(AFK)");
+    row[len++] = '\n';
+    return len;
+}
+
+// %d of a count, a lane per digit, behind what a text already holds (append).
+__device__ __forceinline__ void append_count(uint8_t* dst, int cap, int& at, int count, int lane, int* violations)
+{
+    if (at < 0) return;
+    const uint32_t v = count > 0 ? (uint32_t)count : 0u;
+    int digits = 1;
+    for (uint32_t x = v; x >= 10; x /= 10) digits++;
+    if (at + digits > cap) {
+        if (lane == 0) atomicAdd(violations, 1);
+        at = -1;
+        return;
+    }
+    uint32_t x = v;
+    for (int i = digits - 1; i > lane; i--) x /= 10;
+    if (lane < digits) dst[at + lane] = (uint8_t)('0' + x % 10);
+    at += digits;
+}
+
+// The two headers, the footer and the tail (c:4804-4806, 4849-4853), by one wave.
+__device__ void who_fixed(const WhoArgs& a, int total, int invis, int lane)
+{
+    const Piece none{nullptr, 0};
+    const int dlen = a.date_len < kWhoDateLen ? a.date_len : kWhoDateLen;
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        uint8_t* t = a.ctext + who_fixed_at(i);
+        int len = 0;
+        const Piece p[5] = {i == 0 ? lit("\n*** Current users ") : lit("\n~BB*** Current users "), none, none, none, none};
+        append(t, kWhoHeadRow, len, p, a.date, dlen, false, lane, a.violations);
+        const Piece q[5] = {lit(" ***\n\n"), none, none, none, none};
+        append(t, kWhoHeadRow, len, q, nullptr, 0, false, lane, a.violations);
+        if (lane == 0) a.clen[i] = len;
+    }
+    {
+        uint8_t* t = a.ctext + who_fixed_at(2);
+        int len = 0;
+        const Piece p0[5] = {lit("\nThere are "), none, none, none, none};
+        append(t, kWhoFootRow, len, p0, nullptr, 0, false, lane, a.violations);
+        append_count(t, kWhoFootRow, len, total - invis, lane, a.violations);
+        const Piece p1[5] = {lit(" visible, "), none, none, none, none};
+        append(t, kWhoFootRow, len, p1, nullptr, 0, false, lane, a.violations);
+        append_count(t, kWhoFootRow, len, invis, lane, a.violations);
+        const Piece p2[5] = {lit(" invisible, 0 remote users.\nTotal of "), none, none, none, none};
+        append(t, kWhoFootRow, len, p2, nullptr, 0, false, lane, a.violations);
+        append_count(t, kWhoFootRow, len, total, lane, a.violations);
+        const Piece p3[5] = {lit(" users"), none, none, none, none};
+        append(t, kWhoFootRow, len, p3, nullptr, 0, false, lane, a.violations);
+        if (lane == 0) a.clen[2] = len;
+    }
+    {
+        int len = 0;
+        const Piece p[5] = {lit(".\n\n"), none, none, none, none};
+        append(a.ctext + who_fixed_at(3), kWhoTailRow, len, p, nullptr, 0, false, lane, a.violations);
+        if (lane == 0) a.clen[3] = len;
+    }
+    if (lane < kWhoFixed) a.ctext_off[lane] = lane == 0 ? who_fixed_at(0) : lane == 1 ? who_fixed_at(1) : lane == 2 ? who_fixed_at(2)
+                                                                                                        : who_fixed_at(3);
+}
+
+__device__ void roster_who(const WhoArgs& a)
+{
+    __shared__ int s_cnt[kBlock / 64], s_inv[kBlock / 64], s_own[kBlock / 64];
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int line_blocks = (a.capacity + kBlock - 1) / kBlock;
+    if ((int)blockIdx.x > line_blocks) {    // the tables just uploaded, into the kept allocations: a word per lane
+        const int sw = a.speech_new ? a.capacity * (kSpeechRec / 4) : 0, rw = a.rooms_new ? a.look_rooms * (kRoomRow / 4) : 0;
+        const int dw = a.udesc_new ? a.capacity * (kUserDescRow / 4) : 0, ww = a.who_new ? a.capacity * (kWhoRec / 4) : 0;
+        int w = ((int)blockIdx.x - line_blocks - 1) * kBlock + (int)threadIdx.x;
+        if (w < sw) { reinterpret_cast<uint32_t*>(a.speech_keep)[w] = reinterpret_cast<const uint32_t*>(a.speech_new)[w]; return; }
+        w -= sw;
+        if (w < rw) { reinterpret_cast<uint32_t*>(a.rooms_keep)[w] = reinterpret_cast<const uint32_t*>(a.rooms_new)[w]; return; }
+        w -= rw;
+        if (w < dw) { reinterpret_cast<uint32_t*>(a.udesc_keep)[w] = reinterpret_cast<const uint32_t*>(a.udesc_new)[w]; return; }
+        w -= dw;
+        if (w < ww) reinterpret_cast<uint32_t*>(a.who_keep)[w] = reinterpret_cast<const uint32_t*>(a.who_new)[w];
+        return;
+    }
+    const bool fixed = (int)blockIdx.x == line_blocks;          // block-uniform
+    const int first = fixed ? a.capacity : (int)blockIdx.x * kBlock;     // the slots before this block's own
+    const uint32_t* state = reinterpret_cast<const uint32_t*>(a.speech);  // word 3 of a slot: name length, flags, level
+    int before = 0, invis = 0;                                  // of this wave's share of them: listed, and invisible
+    for (int base = 0; base < first; base += kBlock) {          // block-uniform
+        const int j = base + (int)threadIdx.x;
+        bool listed = false, inv = false;
+        if (j < first) {
+            const uint32_t w = state[4 * (size_t)j + 3];
+            listed = (w & 0xff) != 0 && !(a.slotf[j] & kLogin); // a slot without a name is no user; c:4817
+            inv = listed && !(w >> 8 & kVis);
+        }
+        before += __popcll((unsigned long long)__ballot(listed));
+        invis += __popcll((unsigned long long)__ballot(inv));
+    }
+    if (lane == 0) {
+        s_cnt[wave] = before;
+        s_inv[wave] = invis;
+    }
+    __syncthreads();
+    int prior = 0, ninv = 0;
+#pragma unroll
+    for (int x = 0; x < kBlock / 64; x++) {
+        prior += s_cnt[x];
+        ninv += s_inv[x];
+    }
+    if (fixed) {
+        if (wave == 0) {
+            who_fixed(a, prior, ninv, lane);
+            if (lane == 0 && prior != a.nl) atomicAdd(a.violations, 1);
+        }
+        for (int l = prior + (int)threadIdx.x; l < a.nl; l += kBlock) {   // the lines past the count are nobody's
+            a.clen[kWhoFixed + l] = -1;
+            a.ctext_off[kWhoFixed + l] = kWhoFixedStride + l * kWhoRow;
+            a.line_slot[l] = -1;
+        }
+        return;
+    }
+    const int j = first + (int)threadIdx.x;
+    bool listed = false;
+    uint4 rec{};
+    if (j < a.capacity) {
+        rec = reinterpret_cast<const uint4*>(a.speech)[j];
+        listed = (rec.w & 0xff) != 0 && !(a.slotf[j] & kLogin);
+    }
+    const uint64_t bl = __ballot(listed);
+    if (lane == 0) s_own[wave] = __popcll((unsigned long long)bl);
+    __syncthreads();
+    int l = prior + __popcll((unsigned long long)(bl & ((1ull << lane) - 1)));
+#pragma unroll
+    for (int x = 0; x < kBlock / 64; x++)
+        if (x < wave) l += s_own[x];
+    if (!listed || l >= a.nl) return;       // past nl: the fixed block reports the count
+    const int t = kWhoFixed + l;
+    const int at = kWhoFixedStride + l * kWhoRow;
+    a.ctext_off[t] = at;
+    a.line_slot[l] = j;
+    const int rm = a.room[j];
+    const int32_t* wrec = reinterpret_cast<const int32_t*>(a.who) + 2 * (size_t)j;
+    const int away = wrec[1];
+    const uint8_t* rname = nullptr;
+    int rlen = 0;
+    const bool roomless = rm < 0;
+    if (!roomless && rm < a.look_rooms) {
+        rname = a.rooms + (size_t)rm * kRoomRec;
+        rlen = rname[kRrNameLen] < kRoomNameLen ? rname[kRrNameLen] : kRoomNameLen;
+    } else if (roomless && away >= 0 && away < a.look_rooms) {  // c:4841
+        const uint8_t* r = a.rooms + (size_t)away * kRoomRec;
+        rname = r + kRrServ;
+        rlen = r[kRrServLen] < kServNameLen ? r[kRrServLen] : kServNameLen;
+    } else {                                // the host has checked them: never past the table
+        atomicAdd(a.violations, 1);
+        a.clen[t] = -1;
+        return;
+    }
+    const int nlen = (int)(rec.w & 0xff) < kNameLen ? (int)(rec.w & 0xff) : kNameLen;
+    const int32_t mins = (a.now - wrec[0]) / 60;                // both in [0, 2^31): no overflow; C's truncation
+    a.clen[t] = who_line(a.ctext + at, rec, nlen, a.udesc, j, rname, rlen, roomless, mins, a.violations);
+}
+
+__device__ void roster_who_shown(const WhoArgs& a)
+{
+    const int tiles = a.nl > kBlock ? (a.nl + kBlock - 1) / kBlock : 1;
+    const int b = (int)blockIdx.x / tiles, tile = (int)blockIdx.x - b * tiles;
+    const int l = tile * kBlock + (int)threadIdx.x;
+    const uint32_t* state = reinterpret_cast<const uint32_t*>(a.speech);
+    const int ulevel = (int)(state[4 * (size_t)a.slot[b] + 3] >> 16 & 0xff);
+    bool in = false;
+    if (l < a.nl) {
+        const int j = a.line_slot[l];
+        if (j >= 0 && j < a.capacity) {
+            const uint32_t w = state[4 * (size_t)j + 3];
+            in = (w >> 8 & kVis) || (int)(w >> 16 & 0xff) <= ulevel;     // c:4832-4835
+        }
+    }
+    const uint64_t word = __ballot(in);
+    const int w = 2 * (l >> 6);
+    if (((int)threadIdx.x & 63) == 0) {
+        uint32_t* bits = a.shown + (int64_t)b * a.words;
+        if (w < a.words) bits[w] = (uint32_t)word;
+        if (w + 1 < a.words) bits[w + 1] = (uint32_t)(word >> 32);
+    }
+}
+
+static_assert(2 + kNameLen + 1 + kUserDescLen + 3 <= kWhoPadMax && kWhoLineMax <= kWhoRow && kWhoRow % 4 == 0,
+              "roster_who: the first field is at most kWhoPadMax wide, and the longest line fits its slot");
+static_assert(2 + kNameLen + 1 + 32 <= kWhoRow, "roster_who: the whole description row may be stored before it is cut");
+static_assert(22 + kWhoDateLen + 6 <= kWhoHeadRow && 11 + 5 + 10 + 5 + 37 + 5 + 6 <= kWhoFootRow && 3 <= kWhoTailRow,
+              "roster_who: every fixed text fits its slot");
+static_assert(kWhoRow < kTextSize && kWhoRec % 4 == 0, "nuts_roster_speak_plan: a line fits its LDS text; whole words");
+
 }  // namespace
 
 // Stable, unmangled kernel names (they are what rocprofv3 reports).
@@ -2130,6 +2472,8 @@ extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_record_tell(Rec
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_revtell(ReviewArgs a) { roster_review<kTellLines>(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_look(LookArgs a) { roster_look(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_relay(RelayArgs a) { roster_relay(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_who(WhoArgs a) { roster_who(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_who_shown(WhoArgs a) { roster_who_shown(a); }
 
 // ------------------------------------------------------------------------------------------ host library
 
@@ -2367,6 +2711,7 @@ struct Roster {
     int clones = 0;              // clone records 0 .. clones - 1
     uint8_t* clone_table = nullptr;  // their owners, rooms and hear bytes (take_clones): as speech, made by the first nd_roster_relay
     uint8_t* relay_names = nullptr;  // the look rooms' names, 24 bytes per room: likewise
+    uint8_t* who = nullptr;      // last_login and away, 8 bytes per slot: as speech, made by the first nd_roster_who
 };
 Roster g_rosters[kMaxRosters];
 
@@ -2615,6 +2960,41 @@ size_t layout_look(uintptr_t base, size_t members, size_t nl, LookArgs& s, Speak
     take(s.ctext, ctext_bytes);
     take(p.var, (size_t)var_at((int64_t)ctext_bytes, (int64_t)t));
     p.room = s.room;
+    p.text = s.ctext;
+    p.text_off = s.ctext_off;
+    p.text_len = s.clen;
+    p.violations = s.violations;
+    return take.at;
+}
+
+// nd_roster_who's layout of a roster's allocation, after layout_look's pattern: the table, the uploads of the speaker table,
+// of the room table, of the users' descriptions and of the who table (which the kept ones are filled from; the who table
+// last, so that an upload of it alone carries no other), the call's inputs -- the lookers and the date -- ending with
+// violations, then the results next to each other, and last the texts' offsets, which only the kernels pass to each other.
+size_t layout_who(uintptr_t base, WhoArgs& s, SpeakPlanArgs& p)
+{
+    Carver take{base};
+    const size_t k = (size_t)s.k, nl = (size_t)s.nl, cap = (size_t)s.capacity, t = kWhoFixed + nl;
+    const size_t ctext_bytes = (size_t)who_ctext_bytes((int64_t)nl);
+    take_table(take, s.capacity, s.room, s.slotf);
+    take(s.speech_new, cap * kSpeechRec);
+    take(s.rooms_new, (size_t)s.look_rooms * kRoomRow);
+    take(s.udesc_new, cap * kUserDescRow);
+    take(s.who_new, cap * kWhoRec);
+    take(s.slot, k);
+    take(s.date, (size_t)kWhoDateLen + 1);
+    take(s.violations, 1);
+    take(s.clen, t);
+    take(s.line_slot, nl);
+    take(s.shown, k * (size_t)s.words);
+    take(p.vn, 2 * t);
+    take(p.vw, 2 * t);
+    take(p.vwsz, 2 * t * kMaxWrites);
+    take(s.ctext, ctext_bytes);
+    take(p.var, (size_t)var_at((int64_t)ctext_bytes, (int64_t)t));
+    take(s.ctext_off, t);
+    p.room = s.room;
+    p.slot = s.slotf;
     p.text = s.ctext;
     p.text_off = s.ctext_off;
     p.text_len = s.clen;
@@ -3014,6 +3394,7 @@ int nd_roster_destroy(int handle)
     if (r->udesc) (void)hipFree(r->udesc);
     if (r->clone_table) (void)hipFree(r->clone_table);
     if (r->relay_names) (void)hipFree(r->relay_names);
+    if (r->who) (void)hipFree(r->who);
     if (r->mirror) (void)hipHostFree(r->mirror);
     *r = Roster{};
     return 0;
@@ -4024,6 +4405,131 @@ int nd_roster_relay_record(int handle, int k, const uint8_t* text, int64_t text_
 {
     return relay_call(handle, k, text, text_bytes, text_off, text_len, rm, sender, flags, com_num, csender, table, clones,
                       names, bits, vn, vw, vwsz, var, rbits, rlen, rvn, rvw, rvwsz, rtext, rvar, timing, true, clear);
+}
+
+// What who(user, 0) writes for the k lookers slots[] of roster `handle` (duplicates allowed), as texts and a bitmap.  nl is
+// the number of listed users, the slots with a name and no login flag, which the caller counts; each has a room below
+// the roster's look rooms, or no room and an away room there.  now is time(0) and date[date_len] long_date(1), at most 79
+// bytes.  table, speech, rooms and udesc as nd_roster_look's (it and this call fill the same kept tables); who is NULL when
+// no last_login or away changed since the last nd_roster_who of this roster, else all of them: 8 bytes per slot, int32
+// last_login and int32 away (-1: none); the roster's first call must give it.
+// The texts, T = 4 + nl of them: the header of a looker at the name prompt, the header, the footer and the tail at 0, 108,
+// 216 and 296 of ctext, then line l, the line of the l-th listed slot in ascending order, at 304 + 236 l.
+// Outputs (host, caller-allocated): clen[T], ctext[304 + 236 nl]; line_slot[nl] the slot each line is of; shown[k * W]
+// with W = max(1, ceil(nl / 32)): bit l % 32 of word l / 32 of looker b's W words is set when b is sent line l; vn[2T],
+// vw[2T], vwsz[2T * 16] and var[12 * ctext bytes + 16 T] as nd_roster_speak's.
+// Per call, whatever k and the capacity: one upload, three kernels (nuts_roster_who, nuts_roster_who_shown,
+// nuts_roster_speak_plan), one download at the bound size, one synchronise.  Returns 0, or -1 with nd_last_error() set.
+int nd_roster_who(int handle, int k, const int32_t* slots, int nl, int32_t now, const uint8_t* date, int date_len,
+                  const uint8_t* table, const uint8_t* speech, const uint8_t* rooms, const uint8_t* udesc, const uint8_t* who,
+                  int32_t* clen, int64_t* vn, int32_t* vw, int32_t* vwsz, uint8_t* ctext, uint8_t* var, int32_t* line_slot,
+                  uint32_t* shown, nd_roster_timing* timing)
+{
+    Roster* r = roster_at(handle);
+    if (!r || ensure_ready()) return -1;
+    const int cap = r->capacity, nrooms = r->look_rooms;
+    if (k < 1 || (int64_t)k * cap >= INT32_MAX || nl < 0 || nl > cap || now < 0 || date_len < 0 || date_len > kWhoDateLen) {
+        snprintf(g_err, sizeof(g_err), "%d lookers, %d lines of %d slots, a date of %d bytes: need k >= 1, k * capacity < 2^31 - 1, "
+                 "0 <= lines <= capacity, now >= 0, at most %d bytes of date", k, nl, cap, date_len, kWhoDateLen);
+        return -1;
+    }
+    for (int b = 0; b < k; b++)          // the kernels index by these: nothing out of range reaches them
+        if (slots[b] < 0 || slots[b] >= cap) {
+            snprintf(g_err, sizeof(g_err), "who %d: slot out of range", b);
+            return -1;
+        }
+    if (!nrooms) rooms = nullptr;        // a roster without look rooms has no room table: its listed users are violations
+    if ((!r->speech && !speech) || (nrooms && !r->room_table && !rooms) || (!r->udesc && !udesc) || (!r->who && !who)) {
+        snprintf(g_err, sizeof(g_err), "the roster's first who call must give the speaker table, the room table, the descriptions "
+                 "and the who table");
+        return -1;
+    }
+    if (ensure_kept(&r->speech, (size_t)cap * kSpeechRec, "speaker table")) return -1;
+    if (nrooms && ensure_kept(&r->room_table, (size_t)nrooms * kRoomRow, "room table")) return -1;
+    if (ensure_kept(&r->udesc, (size_t)cap * kUserDescRow, "user descriptions")) return -1;
+    if (ensure_kept(&r->who, (size_t)cap * kWhoRec, "who table")) return -1;
+    const double t0 = now_ns();
+    hipStream_t st = g.stream;
+    WhoArgs s{};
+    SpeakPlanArgs p{};                  // k = 0, tiles = 0: no room lines, a block per text
+    s.k = k;
+    s.nl = nl;
+    s.capacity = p.capacity = cap;
+    s.look_rooms = nrooms;
+    s.words = nl > 32 ? (nl + 31) / 32 : 1;
+    s.date_len = date_len;
+    s.now = now;
+    const size_t texts = (size_t)kWhoFixed + nl, ctext_bytes = (size_t)who_ctext_bytes(nl);
+    const size_t var_bytes = (size_t)var_at((int64_t)ctext_bytes, (int64_t)texts);
+    WhoArgs so = s;                     // offsets of every array in the roster's allocation
+    SpeakPlanArgs po = p;
+    const size_t need = layout_who(0, so, po);
+    const size_t table_bytes = (uintptr_t)so.speech_new, rooms_at = (uintptr_t)so.rooms_new, udesc_at = (uintptr_t)so.udesc_new;
+    const size_t who_at = (uintptr_t)so.who_new, tables_end = (uintptr_t)so.slot, in_bytes = (uintptr_t)so.violations + sizeof(int);
+    const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
+    if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
+    if (table) new_table(*r, so.room, so.slotf, table);
+    if (grow_roster(*r, need)) return -1;
+    layout_who((uintptr_t)r->d, s, p);
+    if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
+
+    uint8_t* h = r->mirror;
+    const Put put{h};
+    if (speech) put(so.speech_new, speech, (size_t)cap * kSpeechRec);
+    if (rooms) put(so.rooms_new, rooms, (size_t)nrooms * kRoomRow);
+    if (udesc) put(so.udesc_new, udesc, (size_t)cap * kUserDescRow);
+    if (who) put(so.who_new, who, (size_t)cap * kWhoRec);
+    put(so.slot, slots, (size_t)k * sizeof(int32_t));
+    put(so.date, date, (size_t)date_len);
+    *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
+    // the tables' uploads lie between the table and the inputs: what lies after the first one that changed travels too,
+    // but the kernel is told of the changed ones alone, so the mirror's bytes of the others need not be current
+    size_t h2d = 0;
+    if (upload(*r, table_bytes, speech ? table_bytes : rooms ? rooms_at : udesc ? udesc_at : who ? who_at : tables_end, in_bytes, &h2d))
+        return -1;
+    s.speech = speech ? s.speech_new : r->speech;
+    s.rooms = rooms ? s.rooms_new : r->room_table;
+    s.udesc = udesc ? s.udesc_new : r->udesc;
+    s.who = who ? s.who_new : r->who;
+    if (!speech) s.speech_new = nullptr;
+    if (!rooms) s.rooms_new = nullptr;
+    if (!udesc) s.udesc_new = nullptr;
+    if (!who) s.who_new = nullptr;
+    s.speech_keep = r->speech;
+    s.rooms_keep = r->room_table;
+    s.udesc_keep = r->udesc;
+    s.who_keep = r->who;
+
+    const size_t copy_words = (speech ? (size_t)cap * (kSpeechRec / 4) : 0) + (rooms ? (size_t)nrooms * (kRoomRow / 4) : 0) +
+                              (udesc ? (size_t)cap * (kUserDescRow / 4) : 0) + (who ? (size_t)cap * (kWhoRec / 4) : 0);
+    const unsigned line_blocks = (unsigned)((cap + kBlock - 1) / kBlock), tiles = nl > kBlock ? (unsigned)((nl + kBlock - 1) / kBlock) : 1u;
+    ND_CHECK(hipEventRecord(g.ev0, st));
+    hipLaunchKernelGGL(nuts_roster_who, dim3(line_blocks + 1 + (unsigned)((copy_words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, s);
+    ND_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(nuts_roster_who_shown, dim3((unsigned)k * tiles), dim3(kBlock), 0, st, s);
+    ND_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)texts), dim3(kBlock), 0, st, p);
+    ND_CHECK(hipGetLastError());
+    if (fetch_results(r->d, res_at, res_bytes)) return -1;
+    const double t1 = now_ns();
+
+    const Res res{gm.res, res_at};
+    const int violations = *reinterpret_cast<const int*>(res(so.violations));
+    if (violations) {
+        snprintf(g_err, sizeof(g_err), "%d text(s) exceeded the hard bounds (a text its slot, a listed slot without a room record, a "
+                 "count of listed slots that is not %d; 6*len+4 bytes, %d writes transduced)", violations, nl, kMaxWrites);
+        return -1;
+    }
+    memcpy(clen, res(so.clen), texts * sizeof(int32_t));
+    memcpy(line_slot, res(so.line_slot), (size_t)nl * sizeof(int32_t));
+    memcpy(shown, res(so.shown), (size_t)k * s.words * sizeof(uint32_t));
+    memcpy(vn, res(po.vn), 2 * texts * sizeof(int64_t));
+    memcpy(vw, res(po.vw), 2 * texts * sizeof(int32_t));
+    memcpy(vwsz, res(po.vwsz), 2 * texts * kMaxWrites * sizeof(int32_t));
+    memcpy(ctext, res(so.ctext), ctext_bytes);
+    memcpy(var, res(po.var), var_bytes);
+
+    return fill_timing(timing, t0, t1, h2d, res_bytes);
 }
 
 }  // extern "C"

@@ -2,7 +2,8 @@
 
     python -m nuts333_amd.devpath [--reps R] [--warmup W] [--pathbench-iterations I] [--per-call K[,K...]]
                                   [--roster K[,K...]] [--plan K[,K...]] [--review Q[,Q...]] [--speak K[,K...]]
-                                  [--input K[,K...]] [--tell K[,K...]] [--look K[,K...]] [--relay K[,K...]]   -> one JSON line
+                                  [--input K[,K...]] [--tell K[,K...]] [--look K[,K...]] [--relay K[,K...]]
+                                  [--who K[,K...]]   -> one JSON line
 
 For N in {10, 100, 1000} listeners, the two texts oracle/pathbench.c times (``say``; ``shout`` carrying ``~OL``/``~RS``)
 and colour all-off / all-on / half, one ``nuts333_amd.device.broadcast`` per repetition (listener 0 is the sender, the
@@ -76,6 +77,12 @@ in room 0 and hear everything, and K says to room 0 per ``Roster.relay_many`` ca
 CPU doing ``clone_relay``'s work through ``nuts_path``: per relaying clone the swear scan and the transducer over the
 prefixed text (``relay_cpu_us_covers`` says what that leaves out); with no relaying clone there is none.  The first call
 of each case is checked against that transducer over the prefixed text.
+
+``--who K[,K...]`` adds ``who``: the 1000-slot roster of ``--look``, every slot a listed user logged in at its own second,
+and K whos (slots 0 .. K - 1) per ``Roster.who_many`` call: the three times and the copy volume, beside ``cpu_us``, the
+CPU composing ``who()``'s 1003 strings for each looker -- in Python, ``colour_com_count`` included -- and the CPU
+restatement's transducer over them (``who_cpu_us_covers`` says what that is worth).  The first call of each case is
+checked against that transducer over those strings.
 """
 from __future__ import annotations
 
@@ -641,6 +648,94 @@ def look_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
             "look": cases}
 
 
+WHO_NOW, WHO_DATE = 1_000_000, b"on Monday 19 October 2026 at 00:07"
+_COLCOM = (b"RS", b"OL", b"UL", b"LI", b"RV", b"FK", b"FR", b"FG", b"FY", b"FB", b"FM", b"FT", b"FW", b"BK", b"BR", b"BG", b"BY",
+           b"BB", b"BM", b"BT", b"BW")
+
+
+def colour_com_count(s: bytes) -> int:
+    """colour_com_count (nuts333.c:2563-2583): behind a ``~`` the table is walked once; a match counts, advances one byte
+    and lets the walk go on with the entries after it at the new place."""
+    at, cnt = 0, 0
+    while at < len(s):
+        at += 1
+        if s[at - 1] == 0x7e:
+            for code in _COLCOM:
+                if s[at:at + 2] == code:
+                    cnt += 1
+                    at += 1
+    return cnt
+
+
+def who_strings(n: int, slot: int) -> list[bytes]:
+    """What who(user, 0) hands to write_user for ``slot`` of the roster ``who_cases`` builds: n users spread over the five
+    rooms, slot j in room j % 5 and logged in at second 60 j, every one visible, a USER and not AFK."""
+    out = [b"\n~BB*** Current users %s ***\n\n" % WHO_DATE]
+    for j in range(n):
+        line = b"  User%d is user %d~RS" % (j, j)
+        out.append(b"%-*s : %-4s : %-12s : %d mins.\n" % (40 + 3 * colour_com_count(line), line, b"USER", LOOK_ROOMS[j % len(LOOK_ROOMS)],
+                                                         (WHO_NOW - 60 * j) // 60))
+    return out + [b"\nThere are %d visible, 0 invisible, 0 remote users.\nTotal of %d users" % (n, n), b".\n\n"]
+
+
+def who_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
+    """The ``who`` section: who_many of K lookers (slots 0 .. K - 1) at a 1000-slot roster over LOOK_ROOMS, for each colour
+    case and each K, beside the CPU composing the same strings and transducing them."""
+    n = 1000
+    cases = []
+    for colour in COLOURS:
+        with device.Roster(n, look_rooms=len(LOOK_ROOMS)) as roster:
+            col = listeners(n, colour)[:, device.LISTENER_FIELDS.index("colour")]
+            roster.update(range(n), room=[j % len(LOOK_ROOMS) for j in range(n)], colour=col, name=[b"User%d" % j for j in range(n)],
+                          desc=[b"is user %d" % j for j in range(n)], last_login=[60 * j for j in range(n)], level=1)
+            roster.set_rooms(list(range(len(LOOK_ROOMS))), name=list(LOOK_ROOMS))
+            for k in ks:
+                slots = [j % n for j in range(k)]
+                first = roster.who_many(slots, now=WHO_NOW, date=WHO_DATE)
+                for i, j in enumerate(slots):
+                    want = [ch for text in who_strings(n, j) for ch in nuts_path.chunks(text, int(col[j]))]
+                    if first.chunks(i) != want:
+                        raise SystemExit(f"devpath: who {k}, {colour}: who {i} differs from the CPU's transducer over who()'s strings")
+                timed = {"kernels_us": [], "end_to_end_us": [], "python_us": [], "cpu_us": []}
+                copies = set()
+                for i in range(warmup + reps):
+                    t0 = time.perf_counter()
+                    r = roster.who_many(slots, now=WHO_NOW, date=WHO_DATE)
+                    t1 = time.perf_counter()
+                    for j in slots:
+                        c = int(col[j])
+                        for text in who_strings(n, j):
+                            nuts_path.chunks(text, c)
+                    t2 = time.perf_counter()
+                    if i >= warmup:
+                        timed["python_us"].append((t1 - t0) * 1e6)
+                        timed["cpu_us"].append((t2 - t1) * 1e6)
+                        timed["kernels_us"].append(r.timing["kernels_us"])
+                        timed["end_to_end_us"].append(r.timing["end_to_end_us"])
+                        copies.add((r.timing["h2d_bytes"], r.timing["d2h_bytes"]))
+                if len(copies) != 1:
+                    raise SystemExit(f"devpath: who {k}, {colour}: timed calls copied {sorted(copies)} bytes")
+                st = {f: _stats(v) for f, v in timed.items()}
+                h2d, d2h = copies.pop()
+                cases.append({"n": n, "k": k, "colour": colour, "lines": len(first.line_slots),
+                              "bytes_out": sum(len(first.output(i)) for i in range(k)),
+                              "writes": sum(len(first.chunks(i)) for i in range(k)), **st, "h2d_bytes": h2d, "d2h_bytes": d2h,
+                              "end_to_end_over_cpu": float(f"{st['end_to_end_us']['median'] / st['cpu_us']['median']:.3g}")})
+    return {"who_kernels": list(device.WHO_KERNELS) + ["nuts_roster_speak_plan"],
+            "who_end_to_end_covers": "packing the K lookers and the date into pinned memory, one H2D (the table, the speaker "
+                                     "state, the room table, the descriptions and the login times only in a call after an "
+                                     "update of theirs), three kernels -- a line per listed user in list order, the headers "
+                                     "and the footer; every looker's bitmap of lines; then both variants of every text --, "
+                                     "one D2H at the bound size, one synchronise (python_us adds checking the lookers and the "
+                                     "listed users' rooms, the copies out of pinned memory and building the Who; Who.chunks() "
+                                     "is not timed)",
+            "who_cpu_us_covers": "composing who()'s strings for each of the K lookers in Python (the walk over the user list, "
+                                 "colour_com_count and the format of every line: interpreted, far slower than the reference's "
+                                 "sprintf calls) and np_write_user_stream of the CPU restatement (nuts_path, through ctypes, a "
+                                 "call per string) over them",
+            "who": cases}
+
+
 RELAY_CLONES = 64
 
 
@@ -750,6 +845,9 @@ def main(argv=None) -> int:
     ap.add_argument("--look", type=per_call_counts, default=None, metavar="K[,K...]",
                     help="also time K looks per Roster.look_many call at a 1000-slot roster spread over 5 rooms, for each "
                          "K, beside the CPU's transducer over look()'s strings (the look section)")
+    ap.add_argument("--who", type=per_call_counts, default=None, metavar="K[,K...]",
+                    help="also time K whos per Roster.who_many call at a 1000-slot roster spread over 5 rooms, for each K, "
+                         "beside the CPU composing and transducing who()'s strings (the who section)")
     ap.add_argument("--relay", type=per_call_counts, default=None, metavar="K[,K...]",
                     help="also time K says per Roster.relay_many call to a room of a 1000-slot roster with 0, 1 and 64 "
                          "relaying clones in it, for each K, beside plan_many of the same broadcasts and the CPU doing "
@@ -838,6 +936,7 @@ def main(argv=None) -> int:
     tell = tell_cases(a.tell, a.reps, a.warmup, pb) if a.tell else {}
     look = look_cases(a.look, a.reps, a.warmup, pb) if a.look else {}
     relay = relay_cases(a.relay, a.reps, a.warmup, pb) if a.relay else {}
+    who = who_cases(a.who, a.reps, a.warmup, pb) if a.who else {}
     out = {
         "what": "user-space stage of one broadcast (admit predicate + transducer), device vs CPU",
         "device": "gfx950",
@@ -856,6 +955,7 @@ def main(argv=None) -> int:
         **tell,
         **look,
         **relay,
+        **who,
         "wall_s": round(time.perf_counter() - t_start, 1),
     }
     print(json.dumps(out))
