@@ -1,0 +1,207 @@
+"""Whole recorded sessions replayed, end to end, through the calls of ``device.Roster`` (tests/session_replay.py).
+
+The eight sessions tests/golden/reference_only/replay_<seed>.json are seeded random sessions recorded from the reference
+build by tests/golden/make_replay_golden.py: four to six users of every level in several rooms, with clones, toggles and
+invisible users between the speech.  One replayer keeps the whole talker's state and answers every line step through the
+Roster's calls; every client's bytes are compared with the recording at every step, and the two plans ``input_many`` and
+``relay_many`` make of the same room line are compared with each other.
+
+Host tier (unmarked): the CPU models of the per-call tests, joined by the replayer, reproduce all eight sessions; the
+sessions cover what they were chosen to cover; a model or a replayer that is wrong in one of five known ways no longer
+reproduces them; an unlisted command raises.  Where the reference build is present, every ``replay_*.json`` and ``who.json``
+are recorded again and compared with the committed files.
+
+GPU tier: ONE short-lived child for the module (tests/device_replay_child.py, under ``timeout``) replays the same sessions
+on the device, each in two rosters, and the tests assert on its JSON.
+"""
+from __future__ import annotations
+
+import copy
+import json
+import subprocess
+import sys
+from pathlib import Path
+
+import pytest
+
+import device_review_child
+import device_tell_child
+import scenarios
+import session_replay
+from nuts333_amd import nuts_path
+from session_replay import COMPACT, COVERAGE, SEEDS, SPREAD, ReplayError, coverage_gaps, load, replay
+
+REPO = Path(__file__).resolve().parent.parent
+GOLDEN = REPO / "tests" / "golden"
+sys.path.insert(0, str(GOLDEN))
+
+
+@pytest.fixture(scope="module")
+def docs():
+    return {seed: load(seed) for seed in SEEDS}
+
+
+@pytest.fixture(scope="module")
+def model_runs(docs):
+    """Every session through the CPU models, in both layouts: computed once, read by the tests below."""
+    return {(seed, layout): replay(doc, layout=layout) for seed, doc in docs.items() for layout in (COMPACT, SPREAD)}
+
+
+# ------------------------------------------------------------------ host tier
+def test_the_fixtures_are_eight_small_sessions(docs):
+    limit = (GOLDEN / "vectors" / "transducer.json").stat().st_size
+    assert len(SEEDS) == len(set(SEEDS)) == 8
+    for seed, doc in docs.items():
+        assert (GOLDEN / "reference_only" / f"replay_{seed}.json").stat().st_size < limit
+        ops = [s["op"] for s in doc["steps"]]
+        n = len(doc["accounts"][0])
+        assert 4 <= n <= 6 and ops.count("login") == n and ops.count("line") == 60
+        assert "line" not in ops[:2 * n]                                 # everybody logs in before the first line step
+        assert doc["config"]["max_clones"] == 2
+        assert not any(s.get("send", "").split()[:1] in ([".afk"], [".quit"]) for s in doc["steps"])
+
+
+def test_the_models_reproduce_every_session(model_runs):
+    for (seed, layout), res in model_runs.items():
+        assert res["mismatches"] == [], (seed, layout, res["mismatches"][:2])
+        assert res["plan_disagreements"] == 0 and res["plan_checks"] > 0
+        assert res["answered"] + res["tracked"] == 60 and res["answered_share"] >= 0.6, (seed, res["answered"])
+        # every client at every answered step, every client but the actor at every tracked one, a look per .go that succeeded
+        n = len(res["slots"])
+        assert res["comparisons"] >= n * res["answered"] + (n - 1) * res["tracked"]
+    for seed in SEEDS:                                                  # where the users sit changes nothing
+        a, b = model_runs[seed, COMPACT], model_runs[seed, SPREAD]
+        assert all(a[k] == b[k] for k in ("answered", "tracked", "comparisons", "plan_checks", "commands", "coverage"))
+        assert a["slots"] == list(range(len(a["slots"]))) and a["capacity"] == 8 + 2 * len(a["slots"])
+        assert set(b["slots"]) <= {0, 63, 64, 128, 255, 256} and b["capacity"] == 257 + 2 * len(b["slots"])
+    spread = {s for seed in SEEDS for s in model_runs[seed, SPREAD]["slots"]}
+    assert spread == {0, 63, 64, 128, 255, 256}
+
+
+def test_the_sessions_cover_what_they_were_chosen_for(docs, model_runs):
+    assert coverage_gaps(docs) == []
+    total = {k: sum(model_runs[seed, COMPACT]["coverage"][k] for seed in SEEDS) for k in COVERAGE}
+    print("\n[replay] coverage", total)
+    assert all(total.values()), total
+    commands = {}
+    for seed in SEEDS:
+        for what, n in model_runs[seed, COMPACT]["commands"].items():
+            commands[what] = commands.get(what, 0) + n
+    print("[replay] commands", commands)
+    assert set(commands) == {"say", "shout", "emote", "semote", "unknown", *session_replay.ANSWERED, *session_replay.TRACKED}
+
+
+def test_an_unlisted_command_raises(docs):
+    for send in (".afk", ".quit", ".desc is new", ".bcast hello", ""):
+        doc = copy.deepcopy(docs[SEEDS[0]])
+        at = next(i for i, s in enumerate(doc["steps"]) if s["op"] == "line") + 5
+        doc["steps"].insert(at, {"op": "line", "actor": "c", "send": send, "recv": {}})     # Carol is a WIZ: .bcast is hers
+        with pytest.raises(ReplayError, match=f"step {at}"):
+            replay(doc)
+
+
+def _ignshout_ignored(monkeypatch):
+    real = nuts_path.admits
+    monkeypatch.setattr(nuts_path, "admits", lambda f, *rest: real([*f[:4], 0, f[5]], *rest))
+
+
+def _substring_before_exact(monkeypatch):
+    def get_user(users, word):
+        name = device_tell_child.capitalised(word)
+        order = [users[j] for j in sorted(users) if not users[j]["login"] and users[j]["name"]]
+        return next((u["slot"] for u in order if name in u["name"]), None)
+    monkeypatch.setattr(device_tell_child, "get_user", get_user)
+
+
+def _record_cuts_at_199(monkeypatch):
+    real = device_review_child.Rings.record
+    monkeypatch.setattr(device_review_child.Rings, "record",
+                        lambda self, rm, text: real(self, rm, text if len(text) < 199 else text[:199] + b"\n"))
+
+
+def _nothing_hears_all(monkeypatch):
+    real = session_replay.relays
+    monkeypatch.setattr(session_replay, "relays", lambda records, *rest: real(
+        [(o, r, session_replay.ALL if h == session_replay.NOTHING else h) for o, r, h in records], *rest))
+
+
+@pytest.mark.parametrize("mutate", [_ignshout_ignored, _substring_before_exact, _record_cuts_at_199, _nothing_hears_all])
+def test_a_model_that_is_wrong_no_longer_reproduces_the_sessions(docs, monkeypatch, mutate):
+    """The predicate ignores ignshout; get_user tries strstr before the exact pass; the ring cuts a line at 199 bytes; a clone
+    told to hear nothing hears everything: each of these is caught by the recorded bytes of some session."""
+    mutate(monkeypatch)
+    bad = {seed: len(replay(doc)["mismatches"]) for seed, doc in docs.items()}
+    print("\n[replay]", mutate.__name__, bad)
+    assert any(bad.values()), mutate.__name__
+
+
+def test_keeping_everyone_in_room_0_no_longer_passes(docs):
+    """What replay_reads of tests/device_input_child.py assumes -- nobody ever moves -- fails on every session but those
+    in which nobody moved."""
+    bad = {seed: len(replay(doc, everyone_in_room_0=True)["mismatches"]) for seed, doc in docs.items()}
+    print("\n[replay] everyone in room 0", bad)
+    assert sum(n > 0 for n in bad.values()) >= 6, bad
+
+
+# ------------------------------------------------------------------ where the reference build is present
+@pytest.mark.reference
+@pytest.mark.parametrize("seed", SEEDS)
+def test_a_session_regenerates_byte_for_byte(seed, ref_binary):
+    import make_replay_golden
+    again = make_replay_golden.render(make_replay_golden.record(seed, ref_binary))
+    assert again == (GOLDEN / "reference_only" / f"replay_{seed}.json").read_text()
+
+
+@pytest.mark.reference
+def test_who_json_regenerates_byte_for_byte(ref_binary, monkeypatch):
+    import make_who_golden
+    monkeypatch.setitem(scenarios.REFERENCE_ONLY, "who", make_who_golden.who)
+    again = json.dumps(make_who_golden.record(ref_binary), indent=1, ensure_ascii=True) + "\n"
+    assert again == (GOLDEN / "reference_only" / "who.json").read_text()
+
+
+# ------------------------------------------------------------------ GPU tier: one child for the module
+@pytest.fixture(scope="module")
+def replay_run(built):
+    cmd = ["timeout", "-k", "10", "300", sys.executable, str(REPO / "tests" / "device_replay_child.py")]
+    try:
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=360, cwd=str(REPO))
+    except subprocess.TimeoutExpired:
+        pytest.fail("device child did not finish in 360 s")
+    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_REPLAY ")]
+    if p.returncode != 0 or not lines:
+        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
+    res = json.loads(lines[-1][len("DEVICE_REPLAY "):])
+    print("\n[replay]", json.dumps(res)[:6000])
+    return res
+
+
+@pytest.mark.gpu
+def test_the_device_reproduces_every_session_in_both_rosters(replay_run, model_runs):
+    assert set(replay_run["sessions"]) == {f"{seed}/{layout}" for seed in SEEDS for layout in (COMPACT, SPREAD)}
+    for (seed, layout), model in model_runs.items():
+        got = replay_run["sessions"][f"{seed}/{layout}"]
+        assert got["n_mismatches"] == 0, (seed, layout, got["mismatches"])
+        for k in ("answered", "tracked", "comparisons", "plan_checks", "commands", "capacity", "slots"):
+            assert got[k] == model[k], (seed, layout, k)
+    assert replay_run["steps"] == 2 * 8 * 60
+
+
+@pytest.mark.gpu
+def test_input_many_and_relay_many_plan_the_same_line_alike(replay_run, model_runs):
+    """Every room line a session speaks: admit bitmap, both variants and chunk sizes of the two kernels' plans."""
+    checks = sum(s["plan_checks"] for s in replay_run["sessions"].values())
+    assert checks == sum(m["plan_checks"] for m in model_runs.values()) > 0
+    assert all(s["plan_checks"] > 0 and s["plan_disagreements"] == 0 for s in replay_run["sessions"].values())
+
+
+@pytest.mark.gpu
+def test_every_call_of_the_roster_took_part(replay_run):
+    for key, s in replay_run["sessions"].items():
+        assert s["calls"]["input_many"] == 60 and s["calls"]["relay_many"] >= s["plan_checks"], key
+    calls = {}
+    for s in replay_run["sessions"].values():
+        for what, n in s["calls"].items():
+            calls[what] = calls.get(what, 0) + n
+    assert set(calls) == {"input_many", "relay_many", "tell_many", "look_many", "who_many", "review_many", "revtell_many"}
+    assert all(n >= 16 for n in calls.values()), calls
