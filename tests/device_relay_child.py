@@ -269,7 +269,8 @@ def fuzz_broadcasts(rng: random.Random, cap: int, records, counts) -> tuple:
     return bs, csenders
 
 
-def relay_differences(roster, users, records, bs, csenders, rl: device.Relay, counts) -> list:
+def relay_differences(roster, users, records, bs, csenders, rl: device.Relay, counts, names=ROOM_NAMES) -> list:
+    """``names`` maps a room to its name: the fuzz rosters' ROOM_NAMES, or a dict for a roster with other rooms."""
     bad = []
     ignall = {j: u["ignall"] for j, u in users.items()}
     for k, ((text, rm, sender, fl, com), cs) in enumerate(zip(bs, csenders)):
@@ -299,7 +300,7 @@ def relay_differences(roster, users, records, bs, csenders, rl: device.Relay, co
         counts["owner_colours"] |= {int(users[records[c][0]]["colour"]) for c in want}
         if rl.owner_colours(k).tolist() != [users[records[c][0]]["colour"] for c in want]:
             bad.append({**where, "what": "owner colours"})
-        model = relay_text(ROOM_NAMES[rm], text) if want else b""
+        model = relay_text(names[rm], text) if want else b""
         if rl.relay_text(k) != model:
             bad.append({**where, "what": "text", "device": rl.relay_text(k)[:60].decode("latin-1")})
         for c in (0, 1):
