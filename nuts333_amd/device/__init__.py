@@ -58,6 +58,10 @@ the relay text ``~FT[ <room name> ]:~RS `` + text and its two variants -- a :cla
 date=)`` returns what ``.who`` writes for K lookers (nuts333.c:4792-4856, ``people == 0``) as a :class:`Who`: the two headers,
 the footer and the tail, a line per listed user with ``colour_com_count``'s padding, and per looker a bitmap of the lines it
 is sent.
+``Roster.rooms_many(slots, topics=)`` returns what ``.rmst`` and ``.rmsn`` write for K lookers (``rooms()``,
+nuts333.c:5661-5700) as a :class:`Rooms`: the header of each kind, the tail and a line of each kind per named look room,
+with the users standing in every room counted over the whole roster on the device.  ``Roster.set_rooms(inlink=, netlink=)``
+keeps the three netlink facts ``.rmsn`` prints in the room record's flag byte.
 
 Input is validated before the device is touched (``ValueError``).  The library ``_build/libnuts_device.so`` is built by
 ``__graft_entry__.build()`` where ``hipcc`` exists, and on demand here when it is missing or older than its source.
@@ -89,6 +93,8 @@ NUM_COMMANDS = 92
 COM_SAY, COM_SHOUT, COM_EMOTE, COM_SEMOTE = 3, 4, 6, 7
 #: the private speech commands (NP_TELL, NP_PEMOTE)
 COM_TELL, COM_PEMOTE = 5, 8
+#: the room listings (NP_RMST, NP_RMSN): ``rooms(user, 1)`` and ``rooms(user, 0)``
+COM_RMST, COM_RMSN = 42, 43
 #: the kernels of fanout.hip, as rocprofv3 names them (the scans are rocPRIM's)
 KERNELS = ("nuts_fanout_measure_broadcast", "nuts_fanout_emit_broadcast",
            "nuts_fanout_measure_batch", "nuts_fanout_emit_batch",
@@ -213,6 +219,29 @@ MAX_WHO_LINE_BYTES, MAX_WHO_LINE_WRITES = 6 * MAX_WHO_LINE + 4, 3
 #: a who call's texts (who_fixed_at of fanout.hip): the login header and the header in 108 bytes each, the footer in 80,
 #: the tail in 8; then the lines
 _WHO_FIXED_AT, _WHO_FIXED_STRIDE = (0, 108, 216, 296), 304
+#: the kernels rooms_many runs before nuts_roster_speak_plan
+ROOMS_KERNELS = ("nuts_roster_rooms_count", "nuts_roster_rooms_lines")
+#: a netlink's state as ``rooms()`` tells them apart (nuts333.c:5690-5692): unconnected, connected and not yet up, up
+LINK_DOWN, LINK_VERIFYING, LINK_UP = 0, 1, 2
+#: the room record's flag byte (byte 24): a netlink that is UP, ``allow == IN``, ``inlink``, a netlink that is unconnected,
+#: one that is connected and not up.  A room has a netlink when one of the three state bits is set
+_NET_UP, _NET_ALLOW_IN, _NET_INLINK, _NET_DOWN, _NET_VERIFYING = 1, 2, 4, 8, 16
+_NET_STATE = {LINK_DOWN: _NET_DOWN, LINK_VERIFYING: _NET_VERIFYING, LINK_UP: _NET_UP}
+#: the fixed texts of a Rooms; then ``3 + r`` is room r's ``.rmst`` line and ``3 + look_rooms + r`` its ``.rmsn`` line
+ROOMS_HEAD_TOPICS, ROOMS_HEAD_LINKS, ROOMS_TAIL = range(3)
+#: the longest lines of ``rooms()`` before the transducer, from its two formats: ``%-20s : %9s~RS    %3d    %3d`` is a
+#: 20-byte name, `` : ``, 9 of access, ``~RS`` and four blanks, a count of 65,536 (``%3d`` widens to 5), four blanks and a
+#: mesg_cnt of 2^31 - 1 (10); then two blanks, a 60-byte topic and the newline, or five blanks, 3 of inlink, three blanks, 7
+#: of stat, ``~RS``, two blanks, an 80-byte service and the newline.  Their slots are kRmstRow and kRmsnRow of fanout.hip
+_ROOMS_LINE_FRONT = ROOM_NAME_LEN + 3 + 9 + 3 + 4 + len(str(MAX_CAPACITY)) + 4 + len(str(2**31 - 1))
+MAX_RMST_LINE, _RMST_ROW = _ROOMS_LINE_FRONT + 2 + TOPIC_LEN + 1, 124
+MAX_RMSN_LINE, _RMSN_ROW = _ROOMS_LINE_FRONT + 5 + 3 + 3 + 7 + 3 + 2 + SERV_NAME_LEN + 1, 164
+#: hard bounds of one such line through the transducer, by MAX_WHO_LINE_BYTES' reasoning: the transducer's own 6 bytes per
+#: byte and the reset, 730 and 976 bytes; both are below the 995 a flushed write holds, so one write and the reset's
+MAX_RMST_LINE_BYTES, MAX_RMSN_LINE_BYTES, MAX_ROOMS_LINE_WRITES = 6 * MAX_RMST_LINE + 4, 6 * MAX_RMSN_LINE + 4, 2
+#: a rooms call's texts (rooms_fixed_at of fanout.hip): the two headers in 80 and 96 bytes, the tail in 4; then the
+#: ``.rmst`` lines, then the ``.rmsn`` lines
+_ROOMS_FIXED_AT, _ROOMS_FIXED_STRIDE = (0, 80, 176), 180
 #: a look room's row of the names relay_many uploads (kRelayNameRow of fanout.hip): 20 bytes of name padded with zeros, then
 #: its length; and what a relay text is longer than its broadcast at most, ``~FT[ `` + a 20-byte name + `` ]:~RS ``
 #: (kRelaySlack): its slot among a relay call's relay texts is that much wider than the text
@@ -628,6 +657,53 @@ class Who:
 
 
 @dataclass
+class Rooms:
+    """What ``rooms(user, show_topics)`` writes for K lookers (``Roster.rooms_many``), as a delivery plan like a
+    :class:`Who`: texts with two variants each, and per looker which of them it gets.  The texts, T = 3 + 2 R of them for
+    the R look rooms: ROOMS_HEAD_TOPICS, ROOMS_HEAD_LINKS and ROOMS_TAIL, then text ``3 + r`` is room r's ``.rmst`` line
+    and text ``3 + R + r`` its ``.rmsn`` line.  A room without a name is not listed: its lines have size -1.  So have the
+    header and the lines of a kind that no looker of the call asks for, and they have no variants.  ``texts`` ..
+    ``write_sizes`` are exactly as in a Look.  Looker ``k`` is slot ``slots[k]`` with colour bit ``colour[k]``; it typed
+    ``.rmst`` when ``topics[k]`` is set, else ``.rmsn``, and is sent that kind's header, that kind's line of every listed
+    room in ascending room number, and the tail.  ``counts[r]`` is the number of users the device counted in room r."""
+    slots: np.ndarray             # int32 [K]
+    colour: np.ndarray            # uint8 [K]   the lookers' colour bits
+    topics: np.ndarray            # uint8 [K]   1: .rmst, 0: .rmsn
+    counts: np.ndarray            # int32 [R]
+    texts: np.ndarray             # uint8, flat: the composed texts; gaps are allowed and unspecified
+    text_starts: np.ndarray       # int64 [T]
+    text_sizes: np.ndarray        # int64 [T]   -1: there is no such text
+    variants: np.ndarray          # uint8, flat
+    variant_starts: np.ndarray    # int64 [T, 2]
+    variant_sizes: np.ndarray     # int64 [T, 2]
+    write_counts: np.ndarray      # int32 [T, 2]
+    write_sizes: np.ndarray       # int32 [T, 2, MAX_WRITES]   entries at or past write_counts are unspecified
+    timing: dict = field(default_factory=dict)
+
+    def text_numbers(self, k: int) -> list[int]:
+        """The texts looker ``k`` is sent, in rooms()'s order: one ``write_user`` each."""
+        if not 0 <= k < len(self.slots):
+            raise IndexError(f"no rooms {k}: {len(self.slots)} lookers")
+        nr = len(self.counts)
+        first = 3 if self.topics[k] else 3 + nr
+        listed = [first + r for r in range(nr) if self.text_sizes[first + r] >= 0]
+        return [ROOMS_HEAD_TOPICS if self.topics[k] else ROOMS_HEAD_LINKS] + listed + [ROOMS_TAIL]
+
+    text = Who.text
+    text_chunks = Who.text_chunks
+
+    def chunks(self, k: int) -> list[bytes]:
+        """The ``write(2)`` payloads of looker ``k``, in order."""
+        numbers = self.text_numbers(k)
+        c = int(self.colour[k])
+        return [ch for t in numbers for ch in self.text_chunks(t, c)]
+
+    def output(self, k: int) -> bytes:
+        """Everything looker ``k`` writes: the concatenation of ``chunks(k)``."""
+        return b"".join(self.chunks(k))
+
+
+@dataclass
 class Relay:
     """What ``write_room_except`` does with K broadcasts for a roster with clone records (``Roster.relay_many``): ``plan``
     is the :class:`Plan` of the same broadcasts for the slots, and clone record ``c`` relays broadcast ``k`` iff bit
@@ -918,6 +994,8 @@ def _load():
         lib.nd_roster_who.argtypes = ([ctypes.c_int, ctypes.c_int, P, ctypes.c_int, ctypes.c_int32, P, ctypes.c_int] + [P] * 13
                                       + [ctypes.POINTER(_RosterTiming)])
         lib.nd_roster_who.restype = ctypes.c_int
+        lib.nd_roster_rooms.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int] + [P] * 10 + [ctypes.POINTER(_RosterTiming)]
+        lib.nd_roster_rooms.restype = ctypes.c_int
         lib.nd_roster_clones.argtypes = [ctypes.c_int, ctypes.c_int]
         lib.nd_roster_clones.restype = ctypes.c_int
         lib.nd_roster_relay.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int64] + [P] * 22 + [ctypes.POINTER(_RosterTiming)]
@@ -1861,19 +1939,23 @@ class Roster:
         return int(v)
 
     def set_rooms(self, rooms, *, name=_KEEP, access=_KEEP, desc=_KEEP, links=_KEEP, topic=_KEEP, mesg_cnt=_KEEP,
-                  netlink=_KEEP) -> None:
+                  netlink=_KEEP, inlink=_KEEP) -> None:
         """Set fields of the room records of ``rooms`` (a look room or a sequence of them), by the conventions of
         :meth:`update`: each field given is one value for every room or a sequence of one per room, a field not given
         stays as it is, a room given more than once takes its last values, and nothing changes unless the whole call
         is valid (``ValueError("room N: ...")`` names the first bad entry's position).  Like ``update`` it does not touch
-        the device; only :meth:`look_many` uploads the room table.
+        the device; :meth:`look_many`, :meth:`who_many` and :meth:`rooms_many` upload the room table, whichever comes first.
 
         ``name`` is at most ROOM_NAME_LEN bytes, ``access`` PUBLIC, PRIVATE, FIXED_PUBLIC or FIXED_PRIVATE (0 .. 3),
         ``desc`` at most ROOM_DESC_LEN bytes and may hold newlines, ``links`` at most MAX_LINKS look rooms in the order
         ``look()`` lists them (one list of ints is one value for every room), ``topic`` at most TOPIC_LEN bytes (empty:
         none set), ``mesg_cnt`` the board's message count in [0, 2^31), and ``netlink`` None, or ``(service, allow_in)``
         for a room whose netlink is UP: a service name of at most SERV_NAME_LEN bytes and whether the link allows
-        incoming users only (nuts333.c:3966-3970).  The texts are bytes or str, one byte per character, without a NUL."""
+        incoming users only (nuts333.c:3966-3970).  ``netlink`` may also be ``(service, allow_in, state)`` with LINK_DOWN
+        (the link is unconnected), LINK_VERIFYING (connected, not yet up) or LINK_UP: ``.rmsn`` tells the three apart and
+        prints the service of each (c:5684-5694), while ``look()``, ``who()`` and ``update(away=)`` know a link only when
+        it is UP.  ``inlink`` (a bool, False at first) is ``rm->inlink``, which ``.rmsn`` prints.  The texts are bytes or
+        str, one byte per character, without a NUL."""
         self._check_open()
         if isinstance(rooms, (int, np.integer)):
             rooms = [rooms]
@@ -1919,9 +2001,17 @@ class Roster:
         def netlink_of(v):
             if v is None:
                 return None
-            if not isinstance(v, tuple) or len(v) != 2 or not isinstance(v[1], (bool, np.bool_)):
-                raise ValueError(f"netlink must be None or a (service, allow_in: bool) tuple, not {v!r}")
-            return _limited_text("netlink service", v[0], SERV_NAME_LEN), bool(v[1])
+            if not isinstance(v, tuple) or len(v) not in (2, 3) or not isinstance(v[1], (bool, np.bool_)):
+                raise ValueError(f"netlink must be None or a (service, allow_in: bool[, state]) tuple, not {v!r}")
+            state = v[2] if len(v) == 3 else LINK_UP
+            if isinstance(state, (bool, np.bool_)) or not _is_int(state, LINK_DOWN, LINK_UP):
+                raise ValueError(f"a netlink's state must be LINK_DOWN, LINK_VERIFYING or LINK_UP (0 .. 2), not {state!r}")
+            return _limited_text("netlink service", v[0], SERV_NAME_LEN), bool(v[1]), _NET_STATE[int(state)]
+
+        def inlink_of(v):
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"inlink must be a bool, not {v!r}")
+            return bool(v)
 
         text_of = lambda what, most: (lambda v: _limited_text(what, v, most))
         new = {}
@@ -1930,7 +2020,8 @@ class Roster:
                 ("desc", desc, text_of("desc", ROOM_DESC_LEN), _is_text),
                 ("links", links, links_of, lambda v: hasattr(v, "__len__") and not _is_text(v) and all(_is_number(x) for x in v)),
                 ("topic", topic, text_of("topic", TOPIC_LEN), _is_text), ("mesg_cnt", mesg_cnt, count_of, _is_number),
-                ("netlink", netlink, netlink_of, lambda v: v is None or (isinstance(v, tuple) and len(v) == 2 and _is_text(v[0])))):
+                ("netlink", netlink, netlink_of, lambda v: v is None or (isinstance(v, tuple) and len(v) in (2, 3) and _is_text(v[0]))),
+                ("inlink", inlink, inlink_of, lambda v: not hasattr(v, "__len__"))):
             if v is not _KEEP:
                 new[what] = numbered(what, v, conv, scalar)
         rec, rows = self._room_rec, self._room_desc
@@ -1954,7 +2045,9 @@ class Roster:
             if "netlink" in new:
                 link = new["netlink"][p]
                 put(rec[j], 132, link[0] if link else b"", 25, SERV_NAME_LEN)
-                rec[j, 24] = (1 | (2 if link[1] else 0)) if link else 0
+                rec[j, 24] = (int(rec[j, 24]) & _NET_INLINK) | ((link[2] | (_NET_ALLOW_IN if link[1] else 0)) if link else 0)
+            if "inlink" in new:
+                rec[j, 24] = (int(rec[j, 24]) & ~_NET_INLINK) | (_NET_INLINK if new["inlink"][p] else 0)
             if "mesg_cnt" in new:
                 rec[j, 28:32] = np.array([new["mesg_cnt"][p]], dtype="<i4").view(np.uint8)
             if "desc" in new:
@@ -2141,6 +2234,100 @@ class Roster:
                    line_slots=line_slot[:nl], shown=shown, texts=ctext, text_starts=tstarts,
                    text_sizes=clen.astype(np.int64), variants=var, variant_starts=_variant_starts(tstarts, clen),
                    variant_sizes=vn, write_counts=vw, write_sizes=vwsz, timing=_timing_of(t))
+
+    def rooms_many(self, slots, *, topics) -> Rooms:
+        """What ``rooms(user, show_topics)`` writes for each of ``slots``, K >= 1 lookers (duplicates allowed), in one
+        device call (nuts333.c:5661-5700): ``.rmst`` where ``topics`` is True, ``.rmsn`` where it is False.  ``topics`` is a
+        bool, or a sequence of one bool per looker.  A looker needs only to be a slot; its colour is the roster's.  The
+        roster needs ``look_rooms >= 1``.  Everything malformed raises ``ValueError("rooms N: ...")`` before the device is
+        touched.
+
+        For a looker the :class:`Rooms` holds, in order, what these ``write_user`` calls send: the header of its kind
+        (c:5672, 5673); a line per listed room in ascending room number; ``"\\n"``.  A room is listed when its record has
+        a name: the reference's room list holds no nameless room, as a slot without a name is no user.  The ``.rmst``
+        line is ``"%-20s : %9s~RS    %3d    %3d  %s\\n"`` of name, access (``"  ~FGPUB"`` or ``" ~FRPRIV"``, its first byte
+        ``*`` when the access is fixed), the users in the room, ``mesg_cnt`` and the topic; the ``.rmsn`` line is
+        ``"%-20s : %9s~RS    %3d    %3d     %s   %s~RS  %s\\n"``, ending in `` NO`` or ``YES`` by ``inlink``, the link's
+        state (``"   -"`` with neither netlink nor inlink, ``"~FRDOWN"`` with an inlink alone or an unconnected netlink,
+        ``"  ~FGUP"``, ``" ~FYVER"``) and the netlink's service, whatever its state.
+
+        The users in room r are the slots with a name, ``login == 0`` and ``room == r``: :meth:`who_many`'s population.
+        The reference counts every non-clone user object whose ``room`` is the room (c:5679-5680), and a non-clone user
+        has a room only once ``login`` is 0, because ``connect_user`` sets both within one call (c:1745-1758).  Clone
+        records are not slots and are not counted; invisible users are.  A slot without a room, or in a room at or past
+        ``look_rooms``, is counted nowhere.
+
+        One upload (the table, the speaker state and the room table only after an update of theirs; with none, the
+        lookers alone), three kernel launches (ROOMS_KERNELS, then nuts_roster_speak_plan), one download at the bound
+        size and one synchronise, whatever K and the capacity.  A call whose variant and count bound exceeds
+        MANY_ARENA_CAP is refused.
+
+        Out of scope: ``.people``, ``.netstat`` and the clone listings."""
+        self._check_open()
+        if isinstance(slots, (str, bytes, bytearray)) or not hasattr(slots, "__len__"):
+            raise ValueError(f"slots must be a sequence of slots, not {slots!r}")
+        if len(slots) == 0:
+            raise ValueError("empty call: no lookers")
+        if self.look_rooms < 1:
+            raise ValueError("the roster has no room records (look_rooms is 0): there is no room to list")
+        lookers = []
+        for k, v in enumerate(slots):
+            try:
+                lookers.append(self._slot(v))
+            except ValueError as e:
+                raise ValueError(f"rooms {k}: {e}") from None
+
+        def kind(v):
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"topics must be a bool, True for .rmst and False for .rmsn, not {v!r}")
+            return bool(v)
+
+        if isinstance(topics, (bool, np.bool_)):
+            kinds = [kind(topics)] * len(lookers)
+        elif _is_text(topics) or not hasattr(topics, "__len__"):
+            raise ValueError(f"topics must be a bool or a sequence of one per looker, not {topics!r}")
+        elif len(topics) != len(lookers):
+            raise ValueError(f"topics: {len(topics)} values for {len(lookers)} lookers")
+        else:
+            kinds = []
+            for k, v in enumerate(topics):
+                try:
+                    kinds.append(kind(v))
+                except ValueError as e:
+                    raise ValueError(f"rooms {k}: {e}") from None
+        k, nr = len(lookers), self.look_rooms
+        texts = 3 + 2 * nr
+        ctext_bytes = _ROOMS_FIXED_STRIDE + (_RMST_ROW + _RMSN_ROW) * nr
+        bound = _variant_at(ctext_bytes, texts) + 4 * nr
+        if bound > MANY_ARENA_CAP:
+            raise ValueError(f"call too large: its variant and count bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
+                             f"(MANY_ARENA_CAP): split it")
+        lib = _load()
+        handle = self._device_handle(lib)
+        slot_arr = np.array(lookers, dtype=np.int32)
+        kind_arr = np.array(kinds, dtype=np.uint8)
+        asked = (1 if kind_arr.any() else 0) | (2 if not kind_arr.all() else 0)
+        clen = np.empty(texts, dtype=np.int32)
+        vn, vw = np.empty((texts, 2), dtype=np.int64), np.empty((texts, 2), dtype=np.int32)
+        vwsz = np.empty((texts, 2, MAX_WRITES), dtype=np.int32)
+        ctext = np.empty(ctext_bytes, dtype=np.uint8)
+        var = np.empty(_variant_at(ctext_bytes, texts), dtype=np.uint8)
+        counts = np.zeros(nr, dtype=np.int32)
+        t = _RosterTiming()
+        rc = lib.nd_roster_rooms(handle, k, _ptr(slot_arr), asked, _ptr(self._table) if self._dirty else None,
+                                 _ptr(self._speech) if self._speech_dirty else None,
+                                 _ptr(self._rooms) if self._rooms_dirty else None, _ptr(clen), _ptr(vn), _ptr(vw), _ptr(vwsz),
+                                 _ptr(ctext), _ptr(var), _ptr(counts), ctypes.byref(t))
+        _check(rc, "device rooms failed")
+        self._private_dirty &= not self._speech_dirty         # the whole speaker mirror went up, or none of it
+        self._dirty = self._speech_dirty = self._rooms_dirty = False
+        tstarts = np.concatenate([np.array(_ROOMS_FIXED_AT, dtype=np.int64),
+                                  _ROOMS_FIXED_STRIDE + _RMST_ROW * np.arange(nr, dtype=np.int64),
+                                  _ROOMS_FIXED_STRIDE + _RMST_ROW * nr + _RMSN_ROW * np.arange(nr, dtype=np.int64)])
+        return Rooms(slots=slot_arr, colour=((self._flags[slot_arr] & ROSTER_FLAGS["colour"]) != 0).astype(np.uint8),
+                     topics=kind_arr, counts=counts, texts=ctext, text_starts=tstarts, text_sizes=clen.astype(np.int64),
+                     variants=var, variant_starts=_variant_starts(tstarts, clen), variant_sizes=vn, write_counts=vw,
+                     write_sizes=vwsz, timing=_timing_of(t))
 
     def set_clones(self, clones, *, owner=_KEEP, room=_KEEP, hear=_KEEP) -> None:
         """Set fields of the clone records ``clones`` (a record or a sequence of them, each in ``[0, clones)``), by the

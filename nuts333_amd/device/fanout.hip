@@ -2450,6 +2450,199 @@ static_assert(22 + kWhoDateLen + 6 <= kWhoHeadRow && 11 + 5 + 10 + 5 + 37 + 5 + 
               "roster_who: every fixed text fits its slot");
 static_assert(kWhoRow < kTextSize && kWhoRec % 4 == 0, "nuts_roster_speak_plan: a line fits its LDS text; whole words");
 
+// ------------------------------------------------------------------ rooms() of a resident roster
+//
+// rooms(user, show_topics) (nuts333.c:5661-5700; .rmst and .rmsn) sends a user the room list: a header of its kind, a
+// line per room and a tail.  Nothing but the colour depends on the looker, so a call has at most 3 + 2 R texts for the R
+// look rooms -- the two headers, the tail, room r's .rmst line at 3 + r and its .rmsn line at 3 + R + r -- each with two
+// variants.  A room whose record has no name is not listed; a kind no looker of the call asks for is not composed.
+// A line holds the number of users standing in its room (c:5679-5680): the slots with a name, no login flag and that
+// room, who_many's population.  That is a histogram over the whole roster.
+// The record's flag byte (kRrNet) holds for it, beside bit 0 (a link that is UP) and bit 1 (allow == IN): bit 2 inlink,
+// bit 3 a link that is unconnected, bit 4 a link that is connected and not yet up.  A room has a netlink when bit 0, 3
+// or 4 is set; look() and who() read bit 0 alone.
+//   count    nuts_roster_rooms_count, one launch whose blocks take roles by their index:
+//            COUNT BLOCKS, one per 256 slots, a lane per slot.  The block zeroes a histogram of look_rooms bins in LDS,
+//            the lane of a counted slot adds one to its room's bin (ds_add), and after a barrier the block adds its
+//            non-zero bins to the roster's counters in global memory, which the host zeroed on the stream before the
+//            launch.  Integer adds: the same result on every run, in whatever order the blocks arrive.
+//            COPY BLOCKS past those copy freshly uploaded tables into the kept allocations.
+//   lines    nuts_roster_rooms_lines, a lane per room, 256 per block: the lane of a listed room composes its line of each
+//            kind asked for into the room's rows of the composed-text buffer, whole, as who_line does.  It reads the
+//            counters that blocks of nuts_roster_rooms_count wrote: hence a launch of its own.  Wave 0 of one block more
+//            composes the headers and the tail with compose().  The kernel writes every text's offset and length and
+//            copies the counters next to the other results.
+//   plan     nuts_roster_speak_plan with no room lines (k = 0), a block per text, as after nuts_roster_who.
+constexpr int kRoomsFixed = 3;                             // the .rmst header, the .rmsn header, the tail
+constexpr int kRoomsHeadTRow = 80, kRoomsHeadNRow = 96, kRoomsTailRow = 4;
+constexpr int kRoomsFixedStride = kRoomsHeadTRow + kRoomsHeadNRow + kRoomsTailRow;
+constexpr int rooms_fixed_at(int i) { return i == 0 ? 0 : i == 1 ? kRoomsHeadTRow : kRoomsHeadTRow + kRoomsHeadNRow; }
+constexpr int kRoomsCountMax = 5, kRoomsMesgMax = 10;      // %3d widens: 65536 slots, a mesg_cnt of 2^31 - 1
+// "%-20s : %9s~RS    %3d    %3d  %s\n" and "%-20s : %9s~RS    %3d    %3d     %s   %s~RS  %s\n" at their longest
+constexpr int kRoomsLineFront = kRoomNameLen + 3 + 9 + 3 + 4 + kRoomsCountMax + 4 + kRoomsMesgMax;
+constexpr int kRmstLineMax = kRoomsLineFront + 2 + kTopicLen + 1;                          // 121
+constexpr int kRmsnLineMax = kRoomsLineFront + 5 + 3 + 3 + 7 + 3 + 2 + kServNameLen + 1;   // 162
+constexpr int kRmstRow = 124, kRmsnRow = 164;              // the lines' slots
+constexpr int kRoomsTopics = 1, kRoomsLinks = 2;           // the kinds of a call: .rmst, .rmsn
+constexpr int kNetUp = 1, kNetInlink = 4, kNetDown = 8, kNetVerifying = 16;
+
+constexpr int64_t rooms_ctext_bytes(int64_t nr) { return kRoomsFixedStride + nr * (kRmstRow + kRmsnRow); }
+
+struct RoomsArgs {
+    const int32_t* room;         // [capacity] the roster's table
+    const uint8_t* slotf;        // [capacity] and its flag bytes: login
+    const uint8_t* speech;       // the tables this call reads, the uploads or the kept ones, as LookArgs
+    const uint8_t* speech_new;
+    uint8_t* speech_keep;
+    const uint8_t* rooms;
+    const uint8_t* rooms_new;
+    uint8_t* rooms_keep;
+    const int32_t* slot;         // [k] the lookers: nothing of a text depends on them
+    int k, capacity, look_rooms, kinds;     // kinds: kRoomsTopics | kRoomsLinks, what the lookers ask for
+    int* violations;             // texts past their slots
+    int32_t* counters;           // [look_rooms] the users per room, zeroed by the host before nuts_roster_rooms_count
+    int32_t* counts;             // [look_rooms] and their copy among the results
+    int32_t* clen;               // [3 + 2 look_rooms] the texts' lengths; -1: a kind not asked for, a room without a name
+    int32_t* ctext_off;          // [3 + 2 look_rooms] where each text's slot starts in ctext
+    uint8_t* ctext;              // the texts
+};
+
+__device__ void roster_rooms_count(const RoomsArgs& a)
+{
+    __shared__ int s_hist[kMaxLookRooms];
+    const int count_blocks = (a.capacity + kBlock - 1) / kBlock;
+    if ((int)blockIdx.x >= count_blocks) {  // the tables just uploaded, into the kept allocations: a word per lane
+        const int sw = a.speech_new ? a.capacity * (kSpeechRec / 4) : 0, rw = a.rooms_new ? a.look_rooms * (kRoomRow / 4) : 0;
+        int w = ((int)blockIdx.x - count_blocks) * kBlock + (int)threadIdx.x;
+        if (w < sw) { reinterpret_cast<uint32_t*>(a.speech_keep)[w] = reinterpret_cast<const uint32_t*>(a.speech_new)[w]; return; }
+        w -= sw;
+        if (w < rw) reinterpret_cast<uint32_t*>(a.rooms_keep)[w] = reinterpret_cast<const uint32_t*>(a.rooms_new)[w];
+        return;
+    }
+    const int bins = a.look_rooms < kMaxLookRooms ? a.look_rooms : kMaxLookRooms;
+    for (int i = (int)threadIdx.x; i < bins; i += kBlock) s_hist[i] = 0;
+    __syncthreads();
+    const int j = (int)blockIdx.x * kBlock + (int)threadIdx.x;
+    if (j < a.capacity) {
+        const int rm = a.room[j];
+        const uint32_t w = reinterpret_cast<const uint32_t*>(a.speech)[4 * (size_t)j + 3];    // word 3: the name's length first
+        // c:5680 counts every non-clone user of the room; a slot without a name is no user, and one at login stage has
+        // no room yet in the reference (connect_user sets both at once, c:1745-1758)
+        if (rm >= 0 && rm < bins && (w & 0xff) != 0 && !(a.slotf[j] & kLogin)) atomicAdd(&s_hist[rm], 1);
+    }
+    __syncthreads();
+    for (int i = (int)threadIdx.x; i < bins; i += kBlock) {
+        const int n = s_hist[i];
+        if (n) atomicAdd(&a.counters[i], n);
+    }
+}
+
+// "%3d" of v >= 0 into row at pos, by one lane; returns the position behind it.
+__device__ __forceinline__ int row_count(uint8_t* row, int pos, int32_t count)
+{
+    uint32_t v = count > 0 ? (uint32_t)count : 0u;
+    int digits = 1;
+    for (uint32_t x = v; x >= 10; x /= 10) digits++;
+    for (int i = digits; i < 3; i++) row[pos++] = ' ';
+    for (int i = digits - 1; i >= 0; i--, v /= 10) row[pos + i] = (uint8_t)('0' + v % 10);
+    return pos + digits;
+}
+
+// What both kinds of line begin with (c:5682, 5695): "%-20s : %9s~RS    %3d    %3d" of name, access, count and mesg_cnt.
+__device__ __forceinline__ int rooms_line_front(uint8_t* row, const uint8_t* rec, int nlen, int32_t count)
+{
+    for (int i = 0; i < nlen; i++) row[i] = rec[i];
+    for (int i = nlen; i < kRoomNameLen; i++) row[i] = ' ';                // %-20s
+    int len = row_lit(row, kRoomNameLen, " :  ");                          // " : ", and %9s of eight bytes pads one
+    const int access = rec[kRrAccess];
+    row[len++] = (access & 2) ? '*' : ' ';                                 // FIXED: access[0] = '*'
+    len = (access & 1) ? row_lit(row, len, "~FRPRIV") : row_lit(row, len, " ~FGPUB");
+    len = row_lit(row, len, "~RS    ");
+    len = row_count(row, len, count);
+    len = row_lit(row, len, "    ");
+    return row_count(row, len, *reinterpret_cast<const int32_t*>(rec + kRrMesgCnt));
+}
+
+__device__ void roster_rooms_lines(const RoomsArgs& a)
+{
+    const int nr = a.look_rooms;
+    const int line_blocks = (nr + kBlock - 1) / kBlock;
+    if ((int)blockIdx.x == line_blocks) {   // the fixed texts (c:5672, 5673, 5699), by one wave
+        if (threadIdx.x >= 64) return;
+        const int lane = (int)threadIdx.x;
+        const Piece none{nullptr, 0};
+        const Piece top[5] = {lit("\n~BB*** Rooms data ***\n\n"), none, none, none, none};
+        const Piece names[5] = {lit("~FTRoom name            : Access  Users  Mesgs  "), none, none, none, none};
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            int len = -1;
+            if (a.kinds & (i == 0 ? kRoomsTopics : kRoomsLinks)) {
+                uint8_t* t = a.ctext + rooms_fixed_at(i);
+                const int cap = i == 0 ? kRoomsHeadTRow : kRoomsHeadNRow;
+                const Piece rest[5] = {i == 0 ? lit("Topic\n\n") : lit("Inlink  LStat  Service\n\n"), none, none, none, none};
+                len = 0;
+                append(t, cap, len, top, nullptr, 0, false, lane, a.violations);
+                append(t, cap, len, names, nullptr, 0, false, lane, a.violations);
+                append(t, cap, len, rest, nullptr, 0, false, lane, a.violations);
+            }
+            if (lane == 0) a.clen[i] = len;
+        }
+        int len = 0;
+        const Piece tail[5] = {lit("\n"), none, none, none, none};
+        append(a.ctext + rooms_fixed_at(2), kRoomsTailRow, len, tail, nullptr, 0, false, lane, a.violations);
+        if (lane == 0) a.clen[2] = len;
+        if (lane < kRoomsFixed) a.ctext_off[lane] = lane == 0 ? rooms_fixed_at(0) : lane == 1 ? rooms_fixed_at(1) : rooms_fixed_at(2);
+        return;
+    }
+    const int r = (int)blockIdx.x * kBlock + (int)threadIdx.x;
+    if (r >= nr) return;
+    const int tt = kRoomsFixed + r, tn = kRoomsFixed + nr + r;
+    const int at_t = kRoomsFixedStride + r * kRmstRow, at_n = kRoomsFixedStride + nr * kRmstRow + r * kRmsnRow;
+    const int32_t count = a.counters[r];
+    a.counts[r] = count;
+    a.ctext_off[tt] = at_t;
+    a.ctext_off[tn] = at_n;
+    const uint8_t* rec = a.rooms + (size_t)r * kRoomRec;
+    const int nlen = rec[kRrNameLen] < kRoomNameLen ? rec[kRrNameLen] : kRoomNameLen;
+    int len_t = -1, len_n = -1;
+    if (nlen && (a.kinds & kRoomsTopics)) {                     // a room without a name is no room of the list
+        uint8_t* row = a.ctext + at_t;
+        const int tlen = rec[kRrTopicLen] < kTopicLen ? rec[kRrTopicLen] : kTopicLen;
+        int len = rooms_line_front(row, rec, nlen, count);
+        len = row_lit(row, len, "  ");
+        for (int i = 0; i < tlen; i++) row[len + i] = rec[kRrTopic + i];
+        len += tlen;
+        row[len++] = '\n';
+        len_t = len;
+    }
+    if (nlen && (a.kinds & kRoomsLinks)) {
+        uint8_t* row = a.ctext + at_n;
+        const int net = rec[kRrNet];
+        const bool linked = (net & (kNetUp | kNetDown | kNetVerifying)) != 0;
+        const int slen = !linked ? 0 : rec[kRrServLen] < kServNameLen ? rec[kRrServLen] : kServNameLen;   // c:5694
+        int len = rooms_line_front(row, rec, nlen, count);
+        len = (net & kNetInlink) ? row_lit(row, len, "     YES   ") : row_lit(row, len, "      NO   ");    // noyes1[]
+        if (!linked) len = (net & kNetInlink) ? row_lit(row, len, "~FRDOWN") : row_lit(row, len, "   -");   // c:5685-5688
+        else if (net & kNetDown) len = row_lit(row, len, "~FRDOWN");                                       // c:5690-5692
+        else if (net & kNetUp) len = row_lit(row, len, "  ~FGUP");
+        else len = row_lit(row, len, " ~FYVER");
+        len = row_lit(row, len, "~RS  ");
+        for (int i = 0; i < slen; i++) row[len + i] = rec[kRrServ + i];
+        len += slen;
+        row[len++] = '\n';
+        len_n = len;
+    }
+    a.clen[tt] = len_t;
+    a.clen[tn] = len_n;
+}
+
+static_assert(sizeof("\n~BB*** Rooms data ***\n\n~FTRoom name            : Access  Users  Mesgs  Topic\n\n") - 1 <= kRoomsHeadTRow &&
+              sizeof("\n~BB*** Rooms data ***\n\n~FTRoom name            : Access  Users  Mesgs  Inlink  LStat  Service\n\n") - 1 <= kRoomsHeadNRow &&
+              1 <= kRoomsTailRow, "roster_rooms: every fixed text fits its slot");
+static_assert(kRmstLineMax == 121 && kRmsnLineMax == 162 && kRmstLineMax <= kRmstRow && kRmsnLineMax <= kRmsnRow &&
+              kRmstRow % 4 == 0 && kRmsnRow % 4 == 0 && kRoomsFixedStride % 4 == 0, "roster_rooms: the longest lines fit their slots");
+static_assert(kRmsnRow < kTextSize && kMaxLookRooms * sizeof(int) <= 4096, "roster_rooms: a line fits speak_plan's LDS text; a 4 KB histogram");
+
 }  // namespace
 
 // Stable, unmangled kernel names (they are what rocprofv3 reports).
@@ -2474,6 +2667,8 @@ extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_look(LookArgs a
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_relay(RelayArgs a) { roster_relay(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_who(WhoArgs a) { roster_who(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_who_shown(WhoArgs a) { roster_who_shown(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_rooms_count(RoomsArgs a) { roster_rooms_count(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_rooms_lines(RoomsArgs a) { roster_rooms_lines(a); }
 
 // ------------------------------------------------------------------------------------------ host library
 
@@ -2993,6 +3188,38 @@ size_t layout_who(uintptr_t base, WhoArgs& s, SpeakPlanArgs& p)
     take(s.ctext, ctext_bytes);
     take(p.var, (size_t)var_at((int64_t)ctext_bytes, (int64_t)t));
     take(s.ctext_off, t);
+    p.room = s.room;
+    p.slot = s.slotf;
+    p.text = s.ctext;
+    p.text_off = s.ctext_off;
+    p.text_len = s.clen;
+    p.violations = s.violations;
+    return take.at;
+}
+
+// nd_roster_rooms' layout of a roster's allocation, after layout_who's pattern: the table, the uploads of the speaker table
+// and of the room table (which the kept ones are filled from), the call's input -- the lookers -- ending with violations,
+// then the results next to each other, and last what only the kernels pass to each other: the texts' offsets and the
+// counters, which the host zeroes on the stream and no upload touches.
+size_t layout_rooms(uintptr_t base, RoomsArgs& s, SpeakPlanArgs& p)
+{
+    Carver take{base};
+    const size_t k = (size_t)s.k, nr = (size_t)s.look_rooms, cap = (size_t)s.capacity, t = kRoomsFixed + 2 * nr;
+    const size_t ctext_bytes = (size_t)rooms_ctext_bytes((int64_t)nr);
+    take_table(take, s.capacity, s.room, s.slotf);
+    take(s.speech_new, cap * kSpeechRec);
+    take(s.rooms_new, nr * kRoomRow);
+    take(s.slot, k);
+    take(s.violations, 1);
+    take(s.clen, t);
+    take(s.counts, nr);
+    take(p.vn, 2 * t);
+    take(p.vw, 2 * t);
+    take(p.vwsz, 2 * t * kMaxWrites);
+    take(s.ctext, ctext_bytes);
+    take(p.var, (size_t)var_at((int64_t)ctext_bytes, (int64_t)t));
+    take(s.ctext_off, t);
+    take(s.counters, nr);
     p.room = s.room;
     p.slot = s.slotf;
     p.text = s.ctext;
@@ -4523,6 +4750,110 @@ int nd_roster_who(int handle, int k, const int32_t* slots, int nl, int32_t now, 
     memcpy(clen, res(so.clen), texts * sizeof(int32_t));
     memcpy(line_slot, res(so.line_slot), (size_t)nl * sizeof(int32_t));
     memcpy(shown, res(so.shown), (size_t)k * s.words * sizeof(uint32_t));
+    memcpy(vn, res(po.vn), 2 * texts * sizeof(int64_t));
+    memcpy(vw, res(po.vw), 2 * texts * sizeof(int32_t));
+    memcpy(vwsz, res(po.vwsz), 2 * texts * kMaxWrites * sizeof(int32_t));
+    memcpy(ctext, res(so.ctext), ctext_bytes);
+    memcpy(var, res(po.var), var_bytes);
+
+    return fill_timing(timing, t0, t1, h2d, res_bytes);
+}
+
+// What rooms(user, show_topics) writes for the k lookers slots[] of roster `handle` (duplicates allowed), as texts.  kinds
+// says what they ask for between them: bit 0 .rmst (show_topics), bit 1 .rmsn; the texts of a kind not asked for are void.
+// table, speech and rooms as nd_roster_look's (it, nd_roster_who and this call fill the same kept tables); the roster needs
+// look rooms, R of them.
+// The texts, T = 3 + 2 R of them: the .rmst header, the .rmsn header and the tail at 0, 80 and 176 of ctext, then room r's
+// .rmst line at 180 + 124 r and its .rmsn line at 180 + 124 R + 164 r; a room without a name has neither.
+// Outputs (host, caller-allocated): clen[T] (-1: void), ctext[180 + 288 R]; counts[R] the users per room, the slots with a
+// name, no login flag and that room; vn[2T], vw[2T], vwsz[2T * 16] and var[12 * ctext bytes + 16 T] as nd_roster_speak's.
+// Per call, whatever k and the capacity: one upload, three kernels (nuts_roster_rooms_count over counters zeroed on the
+// stream, nuts_roster_rooms_lines, nuts_roster_speak_plan), one download at the bound size, one synchronise.  Returns 0,
+// or -1 with nd_last_error() set.
+int nd_roster_rooms(int handle, int k, const int32_t* slots, int kinds, const uint8_t* table, const uint8_t* speech,
+                    const uint8_t* rooms, int32_t* clen, int64_t* vn, int32_t* vw, int32_t* vwsz, uint8_t* ctext, uint8_t* var,
+                    int32_t* counts, nd_roster_timing* timing)
+{
+    Roster* r = roster_at(handle);
+    if (!r || ensure_ready()) return -1;
+    const int cap = r->capacity, nrooms = r->look_rooms;
+    if (k < 1 || nrooms < 1 || nrooms > kMaxLookRooms || kinds < 1 || kinds > (kRoomsTopics | kRoomsLinks)) {
+        snprintf(g_err, sizeof(g_err), "%d lookers of kinds %d over %d look rooms: need k >= 1, 1 <= look rooms <= %d, kinds in 1 .. 3",
+                 k, kinds, nrooms, kMaxLookRooms);
+        return -1;
+    }
+    for (int b = 0; b < k; b++)
+        if (slots[b] < 0 || slots[b] >= cap) {
+            snprintf(g_err, sizeof(g_err), "rooms %d: slot out of range", b);
+            return -1;
+        }
+    if ((!r->speech && !speech) || (!r->room_table && !rooms)) {
+        snprintf(g_err, sizeof(g_err), "the roster's first rooms call must give the speaker table and the room table");
+        return -1;
+    }
+    if (ensure_kept(&r->speech, (size_t)cap * kSpeechRec, "speaker table")) return -1;
+    if (ensure_kept(&r->room_table, (size_t)nrooms * kRoomRow, "room table")) return -1;
+    const double t0 = now_ns();
+    hipStream_t st = g.stream;
+    RoomsArgs s{};
+    SpeakPlanArgs p{};                  // k = 0, tiles = 0: no room lines, a block per text
+    s.k = k;
+    s.capacity = p.capacity = cap;
+    s.look_rooms = nrooms;
+    s.kinds = kinds;
+    const size_t texts = (size_t)kRoomsFixed + 2 * (size_t)nrooms, ctext_bytes = (size_t)rooms_ctext_bytes(nrooms);
+    const size_t var_bytes = (size_t)var_at((int64_t)ctext_bytes, (int64_t)texts);
+    RoomsArgs so = s;                   // offsets of every array in the roster's allocation
+    SpeakPlanArgs po = p;
+    const size_t need = layout_rooms(0, so, po);
+    const size_t table_bytes = (uintptr_t)so.speech_new, rooms_at = (uintptr_t)so.rooms_new, tables_end = (uintptr_t)so.slot;
+    const size_t in_bytes = (uintptr_t)so.violations + sizeof(int);
+    const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
+    if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
+    if (table) new_table(*r, so.room, so.slotf, table);
+    if (grow_roster(*r, need)) return -1;
+    layout_rooms((uintptr_t)r->d, s, p);
+    if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
+
+    uint8_t* h = r->mirror;
+    const Put put{h};
+    if (speech) put(so.speech_new, speech, (size_t)cap * kSpeechRec);
+    if (rooms) put(so.rooms_new, rooms, (size_t)nrooms * kRoomRow);
+    put(so.slot, slots, (size_t)k * sizeof(int32_t));
+    *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
+    // as nd_roster_who: what lies after the first table that changed travels too, but the kernel is told of the changed
+    // ones alone, so the mirror's bytes of the others need not be current
+    size_t h2d = 0;
+    if (upload(*r, table_bytes, speech ? table_bytes : rooms ? rooms_at : tables_end, in_bytes, &h2d)) return -1;
+    s.speech = speech ? s.speech_new : r->speech;
+    s.rooms = rooms ? s.rooms_new : r->room_table;
+    if (!speech) s.speech_new = nullptr;
+    if (!rooms) s.rooms_new = nullptr;
+    s.speech_keep = r->speech;
+    s.rooms_keep = r->room_table;
+
+    const size_t copy_words = (speech ? (size_t)cap * (kSpeechRec / 4) : 0) + (rooms ? (size_t)nrooms * (kRoomRow / 4) : 0);
+    const unsigned count_blocks = (unsigned)((cap + kBlock - 1) / kBlock), line_blocks = (unsigned)((nrooms + kBlock - 1) / kBlock);
+    ND_CHECK(hipEventRecord(g.ev0, st));
+    ND_CHECK(hipMemsetAsync(s.counters, 0, (size_t)nrooms * sizeof(int32_t), st));
+    hipLaunchKernelGGL(nuts_roster_rooms_count, dim3(count_blocks + (unsigned)((copy_words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, s);
+    ND_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(nuts_roster_rooms_lines, dim3(line_blocks + 1), dim3(kBlock), 0, st, s);
+    ND_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)texts), dim3(kBlock), 0, st, p);
+    ND_CHECK(hipGetLastError());
+    if (fetch_results(r->d, res_at, res_bytes)) return -1;
+    const double t1 = now_ns();
+
+    const Res res{gm.res, res_at};
+    const int violations = *reinterpret_cast<const int*>(res(so.violations));
+    if (violations) {
+        snprintf(g_err, sizeof(g_err), "%d text(s) exceeded the hard bounds (a text its slot; 6*len+4 bytes, %d writes transduced)",
+                 violations, kMaxWrites);
+        return -1;
+    }
+    memcpy(clen, res(so.clen), texts * sizeof(int32_t));
+    memcpy(counts, res(so.counts), (size_t)nrooms * sizeof(int32_t));
     memcpy(vn, res(po.vn), 2 * texts * sizeof(int64_t));
     memcpy(vw, res(po.vw), 2 * texts * sizeof(int32_t));
     memcpy(vwsz, res(po.vwsz), 2 * texts * kMaxWrites * sizeof(int32_t));

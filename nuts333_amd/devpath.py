@@ -3,7 +3,7 @@
     python -m nuts333_amd.devpath [--reps R] [--warmup W] [--pathbench-iterations I] [--per-call K[,K...]]
                                   [--roster K[,K...]] [--plan K[,K...]] [--review Q[,Q...]] [--speak K[,K...]]
                                   [--input K[,K...]] [--tell K[,K...]] [--look K[,K...]] [--relay K[,K...]]
-                                  [--who K[,K...]]   -> one JSON line
+                                  [--who K[,K...]] [--rooms K[,K...]]   -> one JSON line
 
 For N in {10, 100, 1000} listeners, the two texts oracle/pathbench.c times (``say``; ``shout`` carrying ``~OL``/``~RS``)
 and colour all-off / all-on / half, one ``nuts333_amd.device.broadcast`` per repetition (listener 0 is the sender, the
@@ -83,6 +83,12 @@ and K whos (slots 0 .. K - 1) per ``Roster.who_many`` call: the three times and 
 CPU composing ``who()``'s 1003 strings for each looker -- in Python, ``colour_com_count`` included -- and the CPU
 restatement's transducer over them (``who_cpu_us_covers`` says what that is worth).  The first call of each case is
 checked against that transducer over those strings.
+
+``--rooms K[,K...]`` adds ``rooms``: a 1000-slot roster over the 6 default rooms and one over 1,024 rooms, and K lookers of
+one kind (``.rmst``, then ``.rmsn``) per ``Roster.rooms_many`` call: the three times and the copy volume, beside ``cpu_us``,
+the CPU composing ``rooms()``'s strings for each looker in Python and the CPU restatement's transducer over them
+(``rooms_cpu_us_covers`` says what that is worth).  The first call of each case is checked against that transducer over
+those strings.
 """
 from __future__ import annotations
 
@@ -736,6 +742,100 @@ def who_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
             "who": cases}
 
 
+#: the room lists of the ``rooms`` section: the six rooms of provision.SIX_ROOMS with the shipped accesses, and 1,024 rooms
+ROOMS_LISTS = {"6": ([b"drive", b"hallway", b"wizroom", b"corridor", b"lounge", b"shop"],
+                     [device.FIXED_PUBLIC, device.FIXED_PUBLIC, device.FIXED_PRIVATE, device.PUBLIC, device.PUBLIC, device.PUBLIC]),
+               "1024": ([b"room%04d" % i for i in range(device.MAX_LOOK_ROOMS)], [i % 4 for i in range(device.MAX_LOOK_ROOMS)])}
+ROOMS_HEADS = {True: b"\n~BB*** Rooms data ***\n\n~FTRoom name            : Access  Users  Mesgs  Topic\n\n",
+               False: b"\n~BB*** Rooms data ***\n\n~FTRoom name            : Access  Users  Mesgs  Inlink  LStat  Service\n\n"}
+
+
+def rooms_strings(n: int, which: str, topics: bool) -> list[bytes]:
+    """What rooms(user, show_topics) hands to write_user at the roster ``rooms_cases`` builds: n users, slot j in room
+    j % R of the R rooms of ROOMS_LISTS[which]; room i has i messages and the topic ``the topic of room i``, every third
+    room an inlink, every fifth a netlink to ``service<i>`` in state i % 3."""
+    names, accesses = ROOMS_LISTS[which]
+    stats = (b"~FRDOWN", b" ~FYVER", b"  ~FGUP")
+    out = [ROOMS_HEADS[topics]]
+    for i, (name, access) in enumerate(zip(names, accesses)):
+        word = bytearray(b" ~FRPRIV" if access & 1 else b"  ~FGPUB")
+        if access & 2:
+            word[0] = 0x2a
+        count = len(range(i, n, len(names)))
+        if topics:
+            out.append(b"%-20s : %9s~RS    %3d    %3d  %s\n" % (name, bytes(word), count, i, b"the topic of room %d" % i))
+        else:
+            inlink, linked = i % 3 == 0, i % 5 == 0
+            stat = stats[i % 3] if linked else b"~FRDOWN" if inlink else b"   -"
+            out.append(b"%-20s : %9s~RS    %3d    %3d     %s   %s~RS  %s\n" % (name, bytes(word), count, i, b"YES" if inlink else b" NO",
+                                                                               stat, b"service%d" % i if linked else b""))
+    return out + [b"\n"]
+
+
+def rooms_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
+    """The ``rooms`` section: rooms_many of K lookers (slots 0 .. K - 1) of one kind at a 1000-slot roster, over the 6
+    default rooms and over 1,024 rooms, for each kind, each colour case and each K, beside the CPU composing the same
+    strings and transducing them."""
+    n = 1000
+    cases = []
+    for which, (names, accesses) in ROOMS_LISTS.items():
+        nr = len(names)
+        for colour in COLOURS:
+            with device.Roster(n, look_rooms=nr) as roster:
+                col = listeners(n, colour)[:, device.LISTENER_FIELDS.index("colour")]
+                roster.update(range(n), room=[j % nr for j in range(n)], colour=col, name=[b"User%d" % j for j in range(n)])
+                ids = list(range(nr))
+                roster.set_rooms(ids, name=names, access=accesses, mesg_cnt=ids, topic=[b"the topic of room %d" % i for i in ids],
+                                 inlink=[i % 3 == 0 for i in ids],
+                                 netlink=[(b"service%d" % i, False, i % 3) if i % 5 == 0 else None for i in ids])
+                for topics in (True, False):
+                    for k in ks:
+                        slots = [j % n for j in range(k)]
+                        first = roster.rooms_many(slots, topics=topics)
+                        for i, j in enumerate(slots):
+                            want = [ch for text in rooms_strings(n, which, topics) for ch in nuts_path.chunks(text, int(col[j]))]
+                            if first.chunks(i) != want:
+                                raise SystemExit(f"devpath: rooms {k}, {which} rooms, {colour}: looker {i} differs from the CPU's "
+                                                 f"transducer over rooms()'s strings")
+                        timed = {"kernels_us": [], "end_to_end_us": [], "python_us": [], "cpu_us": []}
+                        copies = set()
+                        for i in range(warmup + reps):
+                            t0 = time.perf_counter()
+                            r = roster.rooms_many(slots, topics=topics)
+                            t1 = time.perf_counter()
+                            for j in slots:
+                                c = int(col[j])
+                                for text in rooms_strings(n, which, topics):
+                                    nuts_path.chunks(text, c)
+                            t2 = time.perf_counter()
+                            if i >= warmup:
+                                timed["python_us"].append((t1 - t0) * 1e6)
+                                timed["cpu_us"].append((t2 - t1) * 1e6)
+                                timed["kernels_us"].append(r.timing["kernels_us"])
+                                timed["end_to_end_us"].append(r.timing["end_to_end_us"])
+                                copies.add((r.timing["h2d_bytes"], r.timing["d2h_bytes"]))
+                        if len(copies) != 1:
+                            raise SystemExit(f"devpath: rooms {k}, {which} rooms, {colour}: timed calls copied {sorted(copies)} bytes")
+                        st = {f: _stats(v) for f, v in timed.items()}
+                        h2d, d2h = copies.pop()
+                        cases.append({"n": n, "k": k, "colour": colour, "rooms": nr, "kind": "rmst" if topics else "rmsn",
+                                      "bytes_out": sum(len(first.output(i)) for i in range(k)),
+                                      "writes": sum(len(first.chunks(i)) for i in range(k)), **st, "h2d_bytes": h2d, "d2h_bytes": d2h,
+                                      "end_to_end_over_cpu": float(f"{st['end_to_end_us']['median'] / st['cpu_us']['median']:.3g}")})
+    return {"rooms_kernels": list(device.ROOMS_KERNELS) + ["nuts_roster_speak_plan"],
+            "rooms_end_to_end_covers": "packing the K lookers into pinned memory, one H2D (the table, the speaker state and the "
+                                       "room table only in a call after an update of theirs), a memset of the counters and "
+                                       "three kernels -- the users of every room counted over the whole roster; a line of the "
+                                       "kind asked for per room, the header and the tail; then both variants of every text --, "
+                                       "one D2H at the bound size, one synchronise (python_us adds checking the lookers, the "
+                                       "copies out of pinned memory and building the Rooms; Rooms.chunks() is not timed)",
+            "rooms_cpu_us_covers": "composing rooms()'s strings for each of the K lookers in Python (the count of every room in "
+                                   "closed form, not the reference's walk over the user list per room, and the format of every "
+                                   "line: interpreted, slower than the reference's sprintf calls) and np_write_user_stream of the "
+                                   "CPU restatement (nuts_path, through ctypes, a call per string) over them",
+            "rooms": cases}
+
+
 RELAY_CLONES = 64
 
 
@@ -852,6 +952,10 @@ def main(argv=None) -> int:
                     help="also time K says per Roster.relay_many call to a room of a 1000-slot roster with 0, 1 and 64 "
                          "relaying clones in it, for each K, beside plan_many of the same broadcasts and the CPU doing "
                          "clone_relay's work (the relay section)")
+    ap.add_argument("--rooms", type=per_call_counts, default=None, metavar="K[,K...]",
+                    help="also time K .rmst and K .rmsn listings per Roster.rooms_many call at a 1000-slot roster over 6 and "
+                         "over 1,024 rooms, for each K, beside the CPU composing and transducing rooms()'s strings (the "
+                         "rooms section)")
     a = ap.parse_args(argv)
     if a.reps < 1 or a.warmup < 0:
         ap.error("--reps must be >= 1 and --warmup >= 0")
@@ -937,6 +1041,7 @@ def main(argv=None) -> int:
     look = look_cases(a.look, a.reps, a.warmup, pb) if a.look else {}
     relay = relay_cases(a.relay, a.reps, a.warmup, pb) if a.relay else {}
     who = who_cases(a.who, a.reps, a.warmup, pb) if a.who else {}
+    rooms = rooms_cases(a.rooms, a.reps, a.warmup, pb) if a.rooms else {}
     out = {
         "what": "user-space stage of one broadcast (admit predicate + transducer), device vs CPU",
         "device": "gfx950",
@@ -956,6 +1061,7 @@ def main(argv=None) -> int:
         **look,
         **relay,
         **who,
+        **rooms,
         "wall_s": round(time.perf_counter() - t_start, 1),
     }
     print(json.dumps(out))
