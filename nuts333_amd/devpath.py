@@ -100,6 +100,7 @@ import subprocess
 import sys
 import time
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 
@@ -131,9 +132,78 @@ def listeners(n: int, colour: str) -> np.ndarray:
     return t
 
 
+def colours(n: int, colour: str) -> np.ndarray:
+    """The colour flag of each of listeners(n, colour)."""
+    return listeners(n, colour)[:, device.LISTENER_FIELDS.index("colour")]
+
+
 def _stats(xs: list[float]) -> dict:
     q = np.percentile(xs, [10, 90])
     return {"median": round(statistics.median(xs), 2), "p10": round(float(q[0]), 2), "p90": round(float(q[1]), 2)}
+
+
+FIELDS = ("kernels_us", "end_to_end_us", "python_us")
+
+
+class _Step(NamedTuple):
+    """What ``_timed`` found for one step."""
+    times: dict     # the _stats of kernels_us and end_to_end_us, where the results had a timing, and of python_us
+    copied: dict    # the h2d_bytes and d2h_bytes of every kept call, where the timings had them
+
+    @property
+    def host_us(self) -> dict:
+        """The host clock round the step: ``python_us`` of a device call, what a section prints as ``cpu_us`` of CPU work."""
+        return self.times["python_us"]
+
+    @property
+    def fields(self) -> dict:
+        return {**self.times, **self.copied}
+
+
+def _timed(label: str, steps: dict, reps: int, warmup: int) -> dict:
+    """The timed loop of every section.  A round calls every one of ``steps`` (name -> callable of no arguments) once, in
+    order; of ``warmup + reps`` rounds the last ``reps`` are kept.  Kept per step: the host clock round the call and nothing
+    else (``python_us``), the ``kernels_us`` and ``end_to_end_us`` of the result's ``timing`` where it has one, and that
+    timing's ``(h2d_bytes, d2h_bytes)`` where it has them.  A step whose kept calls did not all copy the same volume ends
+    the command.  Returns a ``_Step`` per step."""
+    kept = {name: {"kernels_us": [], "end_to_end_us": [], "python_us": [], "copies": set()} for name in steps}
+    for i in range(warmup + reps):
+        for name, step in steps.items():
+            t0 = time.perf_counter()
+            r = step()
+            us = (time.perf_counter() - t0) * 1e6
+            timing = getattr(r, "timing", None)
+            if i >= warmup:
+                kept[name]["python_us"].append(us)
+                if timing:
+                    kept[name]["kernels_us"].append(timing["kernels_us"])
+                    kept[name]["end_to_end_us"].append(timing["end_to_end_us"])
+                    if "h2d_bytes" in timing:
+                        kept[name]["copies"].add((timing["h2d_bytes"], timing["d2h_bytes"]))
+    out = {}
+    for name, lists in kept.items():
+        copies = lists.pop("copies")
+        if len(copies) > 1:
+            raise SystemExit(f"devpath: {label}: timed {name} calls copied {sorted(copies)} bytes")
+        out[name] = _Step({f: _stats(xs) for f, xs in lists.items() if xs},
+                          dict(zip(("h2d_bytes", "d2h_bytes"), next(iter(copies), ()))))
+    return out
+
+
+def _adds(a: _Step, b: _Step, per: int = 1, digits: int = 2) -> dict:
+    """What step ``a`` takes over step ``b``, median from median, per field."""
+    return {f: round((a.times[f]["median"] - b.times[f]["median"]) / per, digits) for f in FIELDS}
+
+
+def _listing_fields(label: str, name: str, call, cpu, first, k: int, reps: int, warmup: int) -> dict:
+    """What the cases of the three listing sections (look, who, rooms) share: the bytes and writes of the ``first`` result's K
+    listings, then ``call()`` timed as step ``name`` in rounds with ``cpu()``, the CPU doing the same work."""
+    timed = _timed(label, {name: call, "cpu": cpu}, reps, warmup)
+    dev, cpu_us = timed[name], timed["cpu"].host_us
+    return {"bytes_out": sum(len(first.output(i)) for i in range(k)), "writes": sum(len(first.chunks(i)) for i in range(k)),
+            **dev.times, "cpu_us": cpu_us, **dev.copied,
+            # three significant digits: the ratio is far below 1 when many lines go through ctypes
+            "end_to_end_over_cpu": float(f"{dev.times['end_to_end_us']['median'] / cpu_us['median']:.3g}")}
 
 
 def pathbench(iterations: int) -> dict:
@@ -170,24 +240,19 @@ def per_call_case(n: int, text: str, colour: str, k: int, reps: int, warmup: int
     """K broadcasts of ``text`` (distinct line numbers) to listeners(n, colour) per broadcast_many call."""
     table = listeners(n, colour)
     calls = [(t, table, 0, 0, COM[text]) for t in line_texts(text, k)]
-    case, _, _ = _timed_calls("per call", n, text, colour, k, lambda: device.broadcast_many(calls), reps, warmup, pb)
-    return case
+    return _timed_calls("per call", n, text, colour, k, lambda: device.broadcast_many(calls), reps, warmup, pb)[0]
 
 
 def roster_case(n: int, text: str, colour: str, k: int, reps: int, warmup: int, pb: dict, plan: bool = False) -> dict:
     """K broadcasts of ``text`` per Roster.broadcast_many call (``plan``: per Roster.plan_many call), to a roster
     built once, untimed, in the listeners(n, colour) shape: every slot in room 0, slot 0 the sender."""
     with device.Roster(n) as roster:
-        roster.update(range(n), room=0, colour=listeners(n, colour)[:, device.LISTENER_FIELDS.index("colour")])
+        roster.update(range(n), room=0, colour=colours(n, colour))
         calls = [(t, 0, 0, 0, COM[text]) for t in line_texts(text, k)]
         run = (lambda: roster.plan_many(calls)) if plan else (lambda: roster.broadcast_many(calls))
-        case, first, timed = _timed_calls("plan" if plan else "roster", n, text, colour, k, run, reps, warmup, pb,
-                                          _plan_totals if plan else _fanout_totals)
-    h2d = {t["h2d_bytes"] for t in timed}
-    if len(h2d) != 1:
-        raise SystemExit(f"devpath: {'plan' if plan else 'roster'} {k}, {n}/{text}/{colour}: timed calls uploaded "
-                         f"{sorted(h2d)} bytes")
-    h2d = h2d.pop()
+        case, first, copied = _timed_calls("plan" if plan else "roster", n, text, colour, k, run, reps, warmup, pb,
+                                           _plan_totals if plan else _fanout_totals)
+    h2d = copied["h2d_bytes"]
     return {**case, "h2d_bytes": h2d, "h2d_bytes_per_broadcast": round(h2d / k, 1),
             "h2d_bytes_first_call": first["h2d_bytes"], "d2h_bytes": first["d2h_bytes"]}
 
@@ -214,38 +279,25 @@ def _timed_calls(label: str, n: int, text: str, colour: str, k: int, run, reps: 
                  totals=_fanout_totals):
     """One case: ``run()`` makes K broadcasts of ``text`` to listeners(n, colour); its first result is checked against
     the CPU restatement (``totals``: its arena, admitted items, bytes and writes), then it is warmed up and timed.
-    Returns the case, the first call's timing and the timed calls' timings."""
+    Returns the case, the first call's timing and the copy volume of the timed calls."""
     texts = line_texts(text, k)
     first = run()
     arena, admitted, bytes_out, writes = totals(first)
-    colour_of = listeners(n, colour)[1:, device.LISTENER_FIELDS.index("colour")].tolist()
+    colour_of = colours(n, colour)[1:].tolist()
     want = b"".join(b"".join(v[c] for c in colour_of)
                     for v in ({0: nuts_path.transduce(t, 0), 1: nuts_path.transduce(t, 1)} for t in texts))
     if arena != want or admitted != k * (n - 1) or bytes_out != len(want):
         raise SystemExit(f"devpath: {label} {k}, {n}/{text}/{colour}: device produced {bytes_out} "
                          f"bytes, the CPU restatement {len(want)}")
-    for _ in range(warmup):
-        run()
-    kern, e2e, py, timed = [], [], [], []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        r = run()
-        py.append((time.perf_counter() - t0) * 1e6)
-        kern.append(r.timing["kernels_us"])
-        e2e.append(r.timing["end_to_end_us"])
-        timed.append(r.timing)
+    timed = _timed(f"{label} {k}, {n}/{text}/{colour}", {label: run}, reps, warmup)[label]
     cpu = cpu_derived_us(pb, text, colour, n)
-    ks, es, ps = _stats(kern), _stats(e2e), _stats(py)
-    per = lambda s: {q: round(v / k, 3) for q, v in s.items()}
     case = {"n": n, "text": text, "colour": colour, "k": k, "recipients": k * (n - 1),
-            "bytes_out": bytes_out, "writes": writes,
-            "kernels_us": ks, "end_to_end_us": es, "python_us": ps,
-            "kernels_us_per_broadcast": per(ks), "end_to_end_us_per_broadcast": per(es),
-            "python_us_per_broadcast": per(ps),
+            "bytes_out": bytes_out, "writes": writes, **timed.times,
+            **{f"{f}_per_broadcast": {q: round(v / k, 3) for q, v in s.items()} for f, s in timed.times.items()},
             "cpu_derived_us": round(cpu, 3),
-            "end_to_end_over_cpu": round(es["median"] / k / cpu, 2),
-            "python_over_cpu": round(ps["median"] / k / cpu, 2)}
-    return case, first.timing, timed
+            "end_to_end_over_cpu": round(timed.times["end_to_end_us"]["median"] / k / cpu, 2),
+            "python_over_cpu": round(timed.host_us["median"] / k / cpu, 2)}
+    return case, first.timing, timed.copied
 
 
 def review_cases(qs: list[int], reps: int, warmup: int, pb: dict) -> dict:
@@ -267,52 +319,26 @@ def review_cases(qs: list[int], reps: int, warmup: int, pb: dict) -> dict:
                 for c in (0, 1):
                     if first.variant(room, c) != b"".join(nuts_path.transduce(t, c) for t in own):
                         raise SystemExit(f"devpath: review {q}: room {room}, colour {c} differs from the CPU restatement")
-            for _ in range(warmup):
-                roster.review_many(rooms)
-            kern, e2e, py, copies = [], [], [], set()
-            for _ in range(reps):
-                t0 = time.perf_counter()
-                r = roster.review_many(rooms)
-                py.append((time.perf_counter() - t0) * 1e6)
-                kern.append(r.timing["kernels_us"])
-                e2e.append(r.timing["end_to_end_us"])
-                copies.add((r.timing["h2d_bytes"], r.timing["d2h_bytes"]))
-            if len(copies) != 1:
-                raise SystemExit(f"devpath: review {q}: timed calls copied {sorted(copies)} bytes")
             out = ctypes.create_string_buffer(device.MAX_LINE_BYTES)
-            cpu = []
-            for _ in range(warmup + reps):
-                t0 = time.perf_counter()
+
+            def cpu_work():
                 for t in mine:
                     lib.np_transduce(t, 0, out, len(out))
                     lib.np_transduce(t, 1, out, len(out))
-                cpu.append((time.perf_counter() - t0) * 1e6)
-            cpu = _stats(cpu[warmup:])
-            es = _stats(e2e)
+            timed = _timed(f"review {q}", {"review": lambda: roster.review_many(rooms)}, reps, warmup)["review"]
+            cpu = _timed(f"review {q}", {"cpu": cpu_work}, reps, warmup)["cpu"].host_us
+            es = timed.times["end_to_end_us"]
             derived = len(mine) * (pb["transduce_say_colour_off_ns"] + pb["transduce_say_colour_on_ns"]) / 1e3
-            h2d, d2h = copies.pop()
             cases.append({"q": q, "lines": len(mine), "bytes_out": int(first.variant_sizes.sum()),
                           "writes": int(first.write_counts.sum()), "sequential": int(first.sequential.sum()),
-                          "kernels_us": _stats(kern), "end_to_end_us": es, "python_us": _stats(py),
-                          "h2d_bytes": h2d, "d2h_bytes": d2h, "cpu_us": cpu, "cpu_derived_us": round(derived, 3),
+                          **timed.fields, "cpu_us": cpu, "cpu_derived_us": round(derived, 3),
                           "end_to_end_over_cpu": round(es["median"] / cpu["median"], 2),
                           "end_to_end_over_cpu_derived": round(es["median"] / derived, 2)})
         calls = [(t, 0, 0, 0, COM["say"]) for t in line_texts("say", k)]
-        timed = {False: {"kernels_us": [], "end_to_end_us": [], "python_us": []},
-                 True: {"kernels_us": [], "end_to_end_us": [], "python_us": []}}
-        for i in range(2 * (warmup + reps)):
-            rec = bool(i % 2)
-            t0 = time.perf_counter()
-            p = roster.plan_many(calls, record=rec or None)
-            if i >= 2 * warmup:
-                timed[rec]["python_us"].append((time.perf_counter() - t0) * 1e6)
-                timed[rec]["kernels_us"].append(p.timing["kernels_us"])
-                timed[rec]["end_to_end_us"].append(p.timing["end_to_end_us"])
-        record = {"n": n, "k": k, "text": "say", "room": 0,
-                  "without_record": {f: _stats(v) for f, v in timed[False].items()},
-                  "with_record": {f: _stats(v) for f, v in timed[True].items()}}
-        record["record_adds_us"] = {f: round(record["with_record"][f]["median"] - record["without_record"][f]["median"], 2)
-                                    for f in ("kernels_us", "end_to_end_us", "python_us")}
+        timed = _timed("record", {"without_record": lambda: roster.plan_many(calls),
+                                  "with_record": lambda: roster.plan_many(calls, record=True)}, reps, warmup)
+        record = {"n": n, "k": k, "text": "say", "room": 0, **{name: step.times for name, step in timed.items()},
+                  "record_adds_us": _adds(timed["with_record"], timed["without_record"])}
     return {"review_kernels": ["nuts_roster_review"], "record_kernels": ["nuts_roster_plan", "nuts_roster_record"],
             "review_end_to_end_covers": "one H2D of the Q rooms, one kernel, one D2H of the rings' lines, both variants "
                                         "and their chunk sizes at their bound size (about 40 KB per room), one "
@@ -333,17 +359,15 @@ def speak_cpu_us(events, reps: int, warmup: int) -> dict:
     say() (nuts333.c:4094,4097) by the C library's snprintf, one ctypes call each."""
     lib, libc = nuts_path.lib(), ctypes.CDLL(None)
     out, size = ctypes.create_string_buffer(device.TEXT_SIZE), ctypes.c_size_t(device.TEXT_SIZE)
-    runs = []
-    for _ in range(warmup + reps):
-        t0 = time.perf_counter()
+
+    def compose():
         for _, _, inpstr, _ in events:
             verb = lib.np_say_verb(inpstr)
             lib.np_contains_swearing(inpstr)
             libc.snprintf(out, size, b"You %s: %s\n", ctypes.c_char_p(verb), ctypes.c_char_p(inpstr))
             libc.snprintf(out, size, b"%s %ss: %s\n", ctypes.c_char_p(b"Uaaa"), ctypes.c_char_p(verb),
                           ctypes.c_char_p(inpstr))
-        runs.append((time.perf_counter() - t0) * 1e6)
-    return _stats(runs[warmup:])
+    return _timed("speak", {"cpu": compose}, reps, warmup)["cpu"].host_us
 
 
 def speak_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
@@ -353,7 +377,7 @@ def speak_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
     cases = []
     for colour in COLOURS:
         with device.Roster(n) as roster:
-            roster.update(range(n), room=0, colour=listeners(n, colour)[:, device.LISTENER_FIELDS.index("colour")])
+            roster.update(range(n), room=0, colour=colours(n, colour))
             roster.update(0, name=b"Uaaa")
             for k in ks:
                 events, lines = speak_events(k), line_texts("say", k)
@@ -368,36 +392,17 @@ def speak_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
                                   for c in (0, 1)))
                     if not ok:
                         raise SystemExit(f"devpath: speak {k}, {colour}: event {i} differs from the CPU restatement")
-                timed = {name: {"kernels_us": [], "end_to_end_us": [], "python_us": [], "copies": set()}
-                         for name in ("speak", "plan")}
-                for i in range(2 * (warmup + reps)):
-                    name = ("speak", "plan")[i % 2]
-                    t0 = time.perf_counter()
-                    r = roster.speak_many(events, ban_swearing=True) if name == "speak" else roster.plan_many(calls)
-                    if i >= 2 * warmup:
-                        timed[name]["python_us"].append((time.perf_counter() - t0) * 1e6)
-                        timed[name]["kernels_us"].append(r.timing["kernels_us"])
-                        timed[name]["end_to_end_us"].append(r.timing["end_to_end_us"])
-                        timed[name]["copies"].add((r.timing["h2d_bytes"], r.timing["d2h_bytes"]))
-                for name, t in timed.items():
-                    if len(t["copies"]) != 1:
-                        raise SystemExit(f"devpath: speak {k}, {colour}: timed {name} calls copied {sorted(t['copies'])} bytes")
-                fields = ("kernels_us", "end_to_end_us", "python_us")
-                sp = {f: _stats(timed["speak"][f]) for f in fields}
-                pl = {f: _stats(timed["plan"][f]) for f in fields}
-                h2d, d2h = timed["speak"]["copies"].pop()
-                ph2d, pd2h = timed["plan"]["copies"].pop()
+                sp, pl = _timed(f"speak {k}, {colour}", {"speak": lambda: roster.speak_many(events, ban_swearing=True),
+                                                         "plan": lambda: roster.plan_many(calls)}, reps, warmup).values()
                 cpu = speak_cpu_us(events, reps, warmup)
                 derived = 2 * k * pb["format_line_once_ns"] / 1e3
                 cases.append({"n": n, "k": k, "text": "say", "colour": colour, "ban_swearing": True,
-                              "recipients": k * (n - 1), **sp, "h2d_bytes": h2d, "d2h_bytes": d2h,
-                              "plan_many_of_the_composed_lines": {**pl, "h2d_bytes": ph2d, "d2h_bytes": pd2h},
-                              "composing_adds_us": {f: round(sp[f]["median"] - pl[f]["median"], 2) for f in fields},
-                              "composing_adds_us_per_event": {f: round((sp[f]["median"] - pl[f]["median"]) / k, 3)
-                                                              for f in fields},
+                              "recipients": k * (n - 1), **sp.fields, "plan_many_of_the_composed_lines": pl.fields,
+                              "composing_adds_us": _adds(sp, pl), "composing_adds_us_per_event": _adds(sp, pl, k, 3),
                               "cpu_us": cpu, "cpu_derived_us": round(derived, 3),
                               "composing_adds_end_to_end_over_cpu":
-                                  round((sp["end_to_end_us"]["median"] - pl["end_to_end_us"]["median"]) / cpu["median"], 2)})
+                                  round((sp.times["end_to_end_us"]["median"] - pl.times["end_to_end_us"]["median"])
+                                        / cpu["median"], 2)})
     return {"speak_kernels": ["nuts_roster_speak", "nuts_roster_speak_plan"],
             "speak_end_to_end_covers": "packing the K events into pinned memory, one H2D (the table and the speaker "
                                        "state only in a call after an update of theirs), two kernels, one D2H of the "
@@ -445,7 +450,7 @@ def input_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
     cases = []
     for colour in COLOURS:
         with device.Roster(n) as roster:
-            roster.update(range(n), room=0, colour=listeners(n, colour)[:, device.LISTENER_FIELDS.index("colour")])
+            roster.update(range(n), room=0, colour=colours(n, colour))
             roster.update(0, name=b"Uaaa", level=1)
             for k in ks:
                 reads, events, lines = input_reads(k), speak_events(k), line_texts("say", k)
@@ -461,36 +466,17 @@ def input_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
                                   and a.reply.variant(i, c) == b.reply.variant(i, c) for c in (0, 1)))
                     if not ok:
                         raise SystemExit(f"devpath: input {k}, {colour}: read {i} differs from speak_many of its event")
-                timed = {name: {"kernels_us": [], "end_to_end_us": [], "python_us": [], "copies": set()}
-                         for name in ("input", "speak")}
-                for i in range(2 * (warmup + reps)):
-                    name = ("input", "speak")[i % 2]
-                    t0 = time.perf_counter()
-                    r = (roster.input_many(reads, ban_swearing=True) if name == "input"
-                         else roster.speak_many(events, ban_swearing=True))
-                    if i >= 2 * warmup:
-                        timed[name]["python_us"].append((time.perf_counter() - t0) * 1e6)
-                        timed[name]["kernels_us"].append(r.timing["kernels_us"])
-                        timed[name]["end_to_end_us"].append(r.timing["end_to_end_us"])
-                        timed[name]["copies"].add((r.timing["h2d_bytes"], r.timing["d2h_bytes"]))
-                for name, t in timed.items():
-                    if len(t["copies"]) != 1:
-                        raise SystemExit(f"devpath: input {k}, {colour}: timed {name} calls copied {sorted(t['copies'])} bytes")
-                fields = ("kernels_us", "end_to_end_us", "python_us")
-                ip = {f: _stats(timed["input"][f]) for f in fields}
-                sp = {f: _stats(timed["speak"][f]) for f in fields}
-                h2d, d2h = timed["input"]["copies"].pop()
-                sh2d, sd2h = timed["speak"]["copies"].pop()
+                ip, sp = _timed(f"input {k}, {colour}", {"input": lambda: roster.input_many(reads, ban_swearing=True),
+                                                         "speak": lambda: roster.speak_many(events, ban_swearing=True)},
+                                reps, warmup).values()
                 cpu = input_cpu_us(reads, reps, warmup, False)
                 cases.append({"n": n, "k": k, "text": "say", "colour": colour, "ban_swearing": True,
-                              "recipients": k * (n - 1), **ip, "h2d_bytes": h2d, "d2h_bytes": d2h,
-                              "speak_many_of_the_parsed_events": {**sp, "h2d_bytes": sh2d, "d2h_bytes": sd2h},
-                              "parsing_adds_us": {f: round(ip[f]["median"] - sp[f]["median"], 2) for f in fields},
-                              "parsing_adds_us_per_read": {f: round((ip[f]["median"] - sp[f]["median"]) / k, 3)
-                                                           for f in fields},
+                              "recipients": k * (n - 1), **ip.fields, "speak_many_of_the_parsed_events": sp.fields,
+                              "parsing_adds_us": _adds(ip, sp), "parsing_adds_us_per_read": _adds(ip, sp, k, 3),
                               "cpu_us": cpu, "cpu_exec_com_us": input_cpu_us(reads, reps, warmup, True),
                               "parsing_adds_end_to_end_over_cpu":
-                                  round((ip["end_to_end_us"]["median"] - sp["end_to_end_us"]["median"]) / cpu["median"], 2)})
+                                  round((ip.times["end_to_end_us"]["median"] - sp.times["end_to_end_us"]["median"])
+                                        / cpu["median"], 2)})
     return {"input_kernels": ["nuts_roster_parse", "nuts_roster_speak", "nuts_roster_speak_plan"],
             "input_end_to_end_covers": "packing the K reads into pinned memory, one H2D (the table and the speaker state "
                                        "only in a call after an update of theirs), three kernels, one D2H of what the "
@@ -519,7 +505,7 @@ def tell_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
     cases = []
     for colour in COLOURS:
         with device.Roster(n) as roster:
-            roster.update(range(n), room=0, colour=listeners(n, colour)[:, device.LISTENER_FIELDS.index("colour")],
+            roster.update(range(n), room=0, colour=colours(n, colour),
                           name=[b"User%d" % j for j in range(n)])
             roster.update(0, name=b"Uaaa")
             roster.update(TELL_TARGET[0], name=TELL_TARGET[1])
@@ -537,29 +523,12 @@ def tell_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
                                   and first.reply.variant(i, c) == nuts_path.transduce(reply, c) for c in (0, 1)))
                     if not ok:
                         raise SystemExit(f"devpath: tell {k}, {colour}: event {i} differs from the reference's formats")
-                timed = {name: {"kernels_us": [], "end_to_end_us": [], "python_us": [], "copies": set()}
-                         for name in ("tell", "speak")}
-                for i in range(2 * (warmup + reps)):
-                    name = ("tell", "speak")[i % 2]
-                    t0 = time.perf_counter()
-                    r = roster.tell_many(tells) if name == "tell" else roster.speak_many(says, ban_swearing=True)
-                    if i >= 2 * warmup:
-                        timed[name]["python_us"].append((time.perf_counter() - t0) * 1e6)
-                        timed[name]["kernels_us"].append(r.timing["kernels_us"])
-                        timed[name]["end_to_end_us"].append(r.timing["end_to_end_us"])
-                        timed[name]["copies"].add((r.timing["h2d_bytes"], r.timing["d2h_bytes"]))
-                for name, t in timed.items():
-                    if len(t["copies"]) != 1:
-                        raise SystemExit(f"devpath: tell {k}, {colour}: timed {name} calls copied {sorted(t['copies'])} bytes")
-                fields = ("kernels_us", "end_to_end_us", "python_us")
-                tl = {f: _stats(timed["tell"][f]) for f in fields}
-                sp = {f: _stats(timed["speak"][f]) for f in fields}
-                h2d, d2h = timed["tell"]["copies"].pop()
-                sh2d, sd2h = timed["speak"]["copies"].pop()
-                cases.append({"n": n, "k": k, "colour": colour, "target": TELL_TARGET[0], "recipients": k, **tl,
-                              "h2d_bytes": h2d, "d2h_bytes": d2h,
-                              "speak_many_of_the_same_bodies": {**sp, "h2d_bytes": sh2d, "d2h_bytes": sd2h},
-                              "tell_over_speak": {f: round(tl[f]["median"] / sp[f]["median"], 2) for f in fields},
+                tl, sp = _timed(f"tell {k}, {colour}", {"tell": lambda: roster.tell_many(tells),
+                                                        "speak": lambda: roster.speak_many(says, ban_swearing=True)},
+                                reps, warmup).values()
+                cases.append({"n": n, "k": k, "colour": colour, "target": TELL_TARGET[0], "recipients": k, **tl.fields,
+                              "speak_many_of_the_same_bodies": sp.fields,
+                              "tell_over_speak": {f: round(tl.times[f]["median"] / sp.times[f]["median"], 2) for f in FIELDS},
                               "cpu_derived_estimate_us": round(2 * k * pb["format_line_once_ns"] / 1e3, 3)})
     return {"tell_kernels": ["nuts_roster_tell", "nuts_roster_speak_plan"],
             "tell_end_to_end_covers": "packing the K events into pinned memory, one H2D (the table, the speaker state and "
@@ -598,7 +567,7 @@ def look_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
     cases = []
     for colour in COLOURS:
         with device.Roster(n, look_rooms=len(LOOK_ROOMS)) as roster:
-            col = listeners(n, colour)[:, device.LISTENER_FIELDS.index("colour")]
+            col = colours(n, colour)
             roster.update(range(n), room=[j % len(LOOK_ROOMS) for j in range(n)], colour=col,
                           name=[b"User%d" % j for j in range(n)], desc=[b"is user %d" % j for j in range(n)])
             ids = list(range(len(LOOK_ROOMS)))
@@ -613,33 +582,16 @@ def look_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
                     want = [ch for text in strings[i] for ch in nuts_path.chunks(text, int(col[j]))]
                     if first.chunks(i) != want:
                         raise SystemExit(f"devpath: look {k}, {colour}: look {i} differs from the CPU's transducer over look()'s strings")
-                timed = {"kernels_us": [], "end_to_end_us": [], "python_us": [], "cpu_us": []}
-                copies = set()
-                for i in range(warmup + reps):
-                    t0 = time.perf_counter()
-                    r = roster.look_many(slots)
-                    t1 = time.perf_counter()
+
+                def cpu():
                     for q, j in enumerate(slots):
                         c = int(col[j])
                         for text in strings[q]:
                             nuts_path.chunks(text, c)
-                    t2 = time.perf_counter()
-                    if i >= warmup:
-                        timed["python_us"].append((t1 - t0) * 1e6)
-                        timed["cpu_us"].append((t2 - t1) * 1e6)
-                        timed["kernels_us"].append(r.timing["kernels_us"])
-                        timed["end_to_end_us"].append(r.timing["end_to_end_us"])
-                        copies.add((r.timing["h2d_bytes"], r.timing["d2h_bytes"]))
-                if len(copies) != 1:
-                    raise SystemExit(f"devpath: look {k}, {colour}: timed calls copied {sorted(copies)} bytes")
-                st = {f: _stats(v) for f, v in timed.items()}
-                h2d, d2h = copies.pop()
                 cases.append({"n": n, "k": k, "colour": colour, "rooms": len({j % len(LOOK_ROOMS) for j in slots}),
                               "members": sum(len(x) - 7 for x in strings if len(x) > 7),
-                              "bytes_out": sum(len(first.output(i)) for i in range(k)),
-                              "writes": sum(len(first.chunks(i)) for i in range(k)), **st, "h2d_bytes": h2d, "d2h_bytes": d2h,
-                              # three significant digits: the ratio is far below 1 when many lines go through ctypes
-                              "end_to_end_over_cpu": float(f"{st['end_to_end_us']['median'] / st['cpu_us']['median']:.3g}")})
+                              **_listing_fields(f"look {k}, {colour}", "look", lambda: roster.look_many(slots), cpu, first, k,
+                                                reps, warmup)})
     return {"look_kernels": ["nuts_roster_look", "nuts_roster_speak_plan"],
             "look_end_to_end_covers": "packing the K lookers into pinned memory, one H2D (the table, the speaker state, the "
                                       "room table and the descriptions only in a call after an update of theirs), two "
@@ -691,7 +643,7 @@ def who_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
     cases = []
     for colour in COLOURS:
         with device.Roster(n, look_rooms=len(LOOK_ROOMS)) as roster:
-            col = listeners(n, colour)[:, device.LISTENER_FIELDS.index("colour")]
+            col = colours(n, colour)
             roster.update(range(n), room=[j % len(LOOK_ROOMS) for j in range(n)], colour=col, name=[b"User%d" % j for j in range(n)],
                           desc=[b"is user %d" % j for j in range(n)], last_login=[60 * j for j in range(n)], level=1)
             roster.set_rooms(list(range(len(LOOK_ROOMS))), name=list(LOOK_ROOMS))
@@ -702,31 +654,16 @@ def who_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
                     want = [ch for text in who_strings(n, j) for ch in nuts_path.chunks(text, int(col[j]))]
                     if first.chunks(i) != want:
                         raise SystemExit(f"devpath: who {k}, {colour}: who {i} differs from the CPU's transducer over who()'s strings")
-                timed = {"kernels_us": [], "end_to_end_us": [], "python_us": [], "cpu_us": []}
-                copies = set()
-                for i in range(warmup + reps):
-                    t0 = time.perf_counter()
-                    r = roster.who_many(slots, now=WHO_NOW, date=WHO_DATE)
-                    t1 = time.perf_counter()
+
+                def cpu():
                     for j in slots:
                         c = int(col[j])
                         for text in who_strings(n, j):
                             nuts_path.chunks(text, c)
-                    t2 = time.perf_counter()
-                    if i >= warmup:
-                        timed["python_us"].append((t1 - t0) * 1e6)
-                        timed["cpu_us"].append((t2 - t1) * 1e6)
-                        timed["kernels_us"].append(r.timing["kernels_us"])
-                        timed["end_to_end_us"].append(r.timing["end_to_end_us"])
-                        copies.add((r.timing["h2d_bytes"], r.timing["d2h_bytes"]))
-                if len(copies) != 1:
-                    raise SystemExit(f"devpath: who {k}, {colour}: timed calls copied {sorted(copies)} bytes")
-                st = {f: _stats(v) for f, v in timed.items()}
-                h2d, d2h = copies.pop()
                 cases.append({"n": n, "k": k, "colour": colour, "lines": len(first.line_slots),
-                              "bytes_out": sum(len(first.output(i)) for i in range(k)),
-                              "writes": sum(len(first.chunks(i)) for i in range(k)), **st, "h2d_bytes": h2d, "d2h_bytes": d2h,
-                              "end_to_end_over_cpu": float(f"{st['end_to_end_us']['median'] / st['cpu_us']['median']:.3g}")})
+                              **_listing_fields(f"who {k}, {colour}", "who",
+                                                lambda: roster.who_many(slots, now=WHO_NOW, date=WHO_DATE), cpu, first, k,
+                                                reps, warmup)})
     return {"who_kernels": list(device.WHO_KERNELS) + ["nuts_roster_speak_plan"],
             "who_end_to_end_covers": "packing the K lookers and the date into pinned memory, one H2D (the table, the speaker "
                                      "state, the room table, the descriptions and the login times only in a call after an "
@@ -782,7 +719,7 @@ def rooms_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
         nr = len(names)
         for colour in COLOURS:
             with device.Roster(n, look_rooms=nr) as roster:
-                col = listeners(n, colour)[:, device.LISTENER_FIELDS.index("colour")]
+                col = colours(n, colour)
                 roster.update(range(n), room=[j % nr for j in range(n)], colour=col, name=[b"User%d" % j for j in range(n)])
                 ids = list(range(nr))
                 roster.set_rooms(ids, name=names, access=accesses, mesg_cnt=ids, topic=[b"the topic of room %d" % i for i in ids],
@@ -797,31 +734,16 @@ def rooms_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
                             if first.chunks(i) != want:
                                 raise SystemExit(f"devpath: rooms {k}, {which} rooms, {colour}: looker {i} differs from the CPU's "
                                                  f"transducer over rooms()'s strings")
-                        timed = {"kernels_us": [], "end_to_end_us": [], "python_us": [], "cpu_us": []}
-                        copies = set()
-                        for i in range(warmup + reps):
-                            t0 = time.perf_counter()
-                            r = roster.rooms_many(slots, topics=topics)
-                            t1 = time.perf_counter()
+
+                        def cpu():
                             for j in slots:
                                 c = int(col[j])
                                 for text in rooms_strings(n, which, topics):
                                     nuts_path.chunks(text, c)
-                            t2 = time.perf_counter()
-                            if i >= warmup:
-                                timed["python_us"].append((t1 - t0) * 1e6)
-                                timed["cpu_us"].append((t2 - t1) * 1e6)
-                                timed["kernels_us"].append(r.timing["kernels_us"])
-                                timed["end_to_end_us"].append(r.timing["end_to_end_us"])
-                                copies.add((r.timing["h2d_bytes"], r.timing["d2h_bytes"]))
-                        if len(copies) != 1:
-                            raise SystemExit(f"devpath: rooms {k}, {which} rooms, {colour}: timed calls copied {sorted(copies)} bytes")
-                        st = {f: _stats(v) for f, v in timed.items()}
-                        h2d, d2h = copies.pop()
                         cases.append({"n": n, "k": k, "colour": colour, "rooms": nr, "kind": "rmst" if topics else "rmsn",
-                                      "bytes_out": sum(len(first.output(i)) for i in range(k)),
-                                      "writes": sum(len(first.chunks(i)) for i in range(k)), **st, "h2d_bytes": h2d, "d2h_bytes": d2h,
-                                      "end_to_end_over_cpu": float(f"{st['end_to_end_us']['median'] / st['cpu_us']['median']:.3g}")})
+                                      **_listing_fields(f"rooms {k}, {which} rooms, {colour}", "rooms",
+                                                        lambda: roster.rooms_many(slots, topics=topics), cpu, first, k,
+                                                        reps, warmup)})
     return {"rooms_kernels": list(device.ROOMS_KERNELS) + ["nuts_roster_speak_plan"],
             "rooms_end_to_end_covers": "packing the K lookers into pinned memory, one H2D (the table, the speaker state and the "
                                        "room table only in a call after an update of theirs), a memset of the counters and "
@@ -852,7 +774,7 @@ def relay_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
     lib = nuts_path.lib()
     cases = []
     for colour in COLOURS:
-        col = listeners(n, colour)[:, device.LISTENER_FIELDS.index("colour")]
+        col = colours(n, colour)
         for relaying in (0, 1, RELAY_CLONES):
             with device.Roster(n, look_rooms=len(LOOK_ROOMS), clones=RELAY_CLONES) as roster:
                 roster.update(range(n), room=[j % len(LOOK_ROOMS) for j in range(n)], colour=col)
@@ -869,39 +791,22 @@ def relay_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
                                 first.relay_chunks(i, c) != (nuts_path.chunks(texts[i], c) if relaying else []) for c in (0, 1)):
                             raise SystemExit(f"devpath: relay {k}, {colour}, {relaying} clones: broadcast {i} differs from the "
                                              f"CPU's transducer over the prefixed text")
-                    timed = {f: [] for f in ("kernels_us", "end_to_end_us", "python_us", "plan_kernels_us", "plan_end_to_end_us",
-                                             "plan_python_us", "cpu_us")}
-                    copies = set()
-                    for i in range(warmup + reps):
-                        t0 = time.perf_counter()
-                        r = roster.relay_many(bs)
-                        t1 = time.perf_counter()
-                        p = roster.plan_many(bs)
-                        t2 = time.perf_counter()
+
+                    def cpu():
                         for q in range(k):
                             for o in owners:
                                 lib.np_contains_swearing(bs[q][0])
                                 nuts_path.chunks(texts[q], int(col[o]))
-                        t3 = time.perf_counter()
-                        if i >= warmup:
-                            timed["python_us"].append((t1 - t0) * 1e6)
-                            timed["plan_python_us"].append((t2 - t1) * 1e6)
-                            timed["cpu_us"].append((t3 - t2) * 1e6)
-                            timed["kernels_us"].append(r.timing["kernels_us"])
-                            timed["end_to_end_us"].append(r.timing["end_to_end_us"])
-                            timed["plan_kernels_us"].append(p.timing["kernels_us"])
-                            timed["plan_end_to_end_us"].append(p.timing["end_to_end_us"])
-                            copies.add((r.timing["h2d_bytes"], r.timing["d2h_bytes"], p.timing["h2d_bytes"], p.timing["d2h_bytes"]))
-                    if len(copies) != 1:
-                        raise SystemExit(f"devpath: relay {k}, {colour}: timed calls copied {sorted(copies)} bytes")
-                    st = {f: _stats(v) for f, v in timed.items()}
-                    h2d, d2h, plan_h2d, plan_d2h = copies.pop()
+                    rl, pl, cp = _timed(f"relay {k}, {colour}", {"relay": lambda: roster.relay_many(bs),
+                                                                 "plan": lambda: roster.plan_many(bs), "cpu": cpu},
+                                        reps, warmup).values()
+                    e2e = rl.times["end_to_end_us"]["median"]
                     cases.append({"n": n, "k": k, "colour": colour, "relaying_clones": relaying, "relays": k * relaying,
                                   "relay_bytes_out": sum(len(first.relay_variant(i, int(col[o]))) for i in range(k) for o in owners),
-                                  **st, "h2d_bytes": h2d, "d2h_bytes": d2h, "plan_h2d_bytes": plan_h2d, "plan_d2h_bytes": plan_d2h,
-                                  "end_to_end_over_plan": float(f"{st['end_to_end_us']['median'] / st['plan_end_to_end_us']['median']:.3g}"),
-                                  "end_to_end_over_cpu": float(f"{st['end_to_end_us']['median'] / st['cpu_us']['median']:.3g}")
-                                  if relaying else None})
+                                  **rl.times, **{f"plan_{f}": v for f, v in pl.times.items()}, "cpu_us": cp.host_us,
+                                  **rl.copied, **{f"plan_{f}": v for f, v in pl.copied.items()},
+                                  "end_to_end_over_plan": float(f"{e2e / pl.times['end_to_end_us']['median']:.3g}"),
+                                  "end_to_end_over_cpu": float(f"{e2e / cp.host_us['median']:.3g}") if relaying else None})
     return {"relay_kernels": list(device.RELAY_KERNELS),
             "relay_end_to_end_covers": "what plan_many's covers -- packing the K inputs into pinned memory, one H2D (the table "
                                        "and the clone records only in a call after an update of theirs, the rooms' names only "
@@ -919,43 +824,78 @@ def relay_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
             "relay": cases}
 
 
+def _grid(case, ks: list[int], reps: int, warmup: int, pb: dict) -> list[dict]:
+    """``case`` for every size, text and colour of the single-broadcast cases and each K."""
+    return [case(n, text, colour, k, reps, warmup, pb) for n in SIZES for text in TEXTS for colour in COLOURS for k in ks]
+
+
+def per_call_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
+    """The ``per_call`` section."""
+    return {"per_call_kernels": ["nuts_fanout_measure_many", "rocprim device scan x2", "nuts_fanout_emit_many"],
+            "per_call_end_to_end_covers": "packing the K inputs into pinned memory, one H2D, kernels, three D2H, "
+                                          "two synchronises (python_us adds building the K tables and the copies "
+                                          "out of pinned memory)",
+            "per_call": _grid(per_call_case, ks, reps, warmup, pb)}
+
+
+def roster_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
+    """The ``roster`` section."""
+    return {"roster_kernels": ["nuts_roster_measure", "rocprim device scan x2", "nuts_roster_emit"],
+            "roster_end_to_end_covers": "packing the K inputs into pinned memory, one H2D (the roster table only in a "
+                                        "call after an update: h2d_bytes_first_call), kernels, three D2H, two "
+                                        "synchronises (python_us adds checking the K tuples and the copies out of "
+                                        "pinned memory)",
+            "roster": _grid(roster_case, ks, reps, warmup, pb)}
+
+
+def plan_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
+    """The ``plan`` section."""
+    return {"plan_kernels": ["nuts_roster_plan"],
+            "plan_end_to_end_covers": "packing the K inputs into pinned memory, one H2D (the roster table only in a "
+                                      "call after an update: h2d_bytes_first_call), one kernel, one D2H of the "
+                                      "variants, their chunk sizes and the admit bitmap at their bound size, one "
+                                      "synchronise (python_us adds checking the K tuples, the copies out of pinned "
+                                      "memory and building the Plan; expand() is not timed)",
+            "plan": _grid(plan_case, ks, reps, warmup, pb)}
+
+
+#: the optional sections, in the order they run and are printed: option, metavar, help, and the name of the function that
+#: takes (the option's counts, reps, warmup, pathbench's figures) and returns the section's keys
+SECTIONS = (
+    ("per-call", "K[,K...]", "also time K broadcasts per broadcast_many call, for each K (the per_call cases)",
+     "per_call_cases"),
+    ("roster", "K[,K...]", "also time K broadcasts per Roster.broadcast_many call, for each K (the roster cases)",
+     "roster_cases"),
+    ("plan", "K[,K...]", "also time K broadcasts per Roster.plan_many call, for each K (the plan cases)", "plan_cases"),
+    ("review", "Q[,Q...]", "also time Roster.review_many of Q rooms per call, for each Q, and what recording adds to "
+                           "plan_many (the review section)", "review_cases"),
+    ("speak", "K[,K...]", "also time K say events per Roster.speak_many call, for each K, beside plan_many of the "
+                          "same lines composed beforehand (the speak section)", "speak_cases"),
+    ("input", "K[,K...]", "also time K raw reads per Roster.input_many call, for each K, beside speak_many of the same "
+                          "events parsed beforehand (the input section)", "input_cases"),
+    ("tell", "K[,K...]", "also time K tells to one target per Roster.tell_many call, for each K, beside speak_many of K "
+                         "says of the same bodies (the tell section)", "tell_cases"),
+    ("look", "K[,K...]", "also time K looks per Roster.look_many call at a 1000-slot roster spread over 5 rooms, for each "
+                         "K, beside the CPU's transducer over look()'s strings (the look section)", "look_cases"),
+    ("relay", "K[,K...]", "also time K says per Roster.relay_many call to a room of a 1000-slot roster with 0, 1 and 64 "
+                          "relaying clones in it, for each K, beside plan_many of the same broadcasts and the CPU doing "
+                          "clone_relay's work (the relay section)", "relay_cases"),
+    ("who", "K[,K...]", "also time K whos per Roster.who_many call at a 1000-slot roster spread over 5 rooms, for each K, "
+                        "beside the CPU composing and transducing who()'s strings (the who section)", "who_cases"),
+    ("rooms", "K[,K...]", "also time K .rmst and K .rmsn listings per Roster.rooms_many call at a 1000-slot roster over 6 and "
+                          "over 1,024 rooms, for each K, beside the CPU composing and transducing rooms()'s strings (the "
+                          "rooms section)", "rooms_cases"),
+)
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=2000, help="timed broadcasts per case (default 2000)")
     ap.add_argument("--warmup", type=int, default=200, help="untimed broadcasts per case first (default 200)")
     ap.add_argument("--pathbench-iterations", type=int, default=2_000_000)
-    ap.add_argument("--per-call", type=per_call_counts, default=None, metavar="K[,K...]",
-                    help="also time K broadcasts per broadcast_many call, for each K (the per_call cases)")
-    ap.add_argument("--roster", type=per_call_counts, default=None, metavar="K[,K...]",
-                    help="also time K broadcasts per Roster.broadcast_many call, for each K (the roster cases)")
-    ap.add_argument("--plan", type=per_call_counts, default=None, metavar="K[,K...]",
-                    help="also time K broadcasts per Roster.plan_many call, for each K (the plan cases)")
-    ap.add_argument("--review", type=per_call_counts, default=None, metavar="Q[,Q...]",
-                    help="also time Roster.review_many of Q rooms per call, for each Q, and what recording adds to "
-                         "plan_many (the review section)")
-    ap.add_argument("--speak", type=per_call_counts, default=None, metavar="K[,K...]",
-                    help="also time K say events per Roster.speak_many call, for each K, beside plan_many of the "
-                         "same lines composed beforehand (the speak section)")
-    ap.add_argument("--input", type=per_call_counts, default=None, metavar="K[,K...]",
-                    help="also time K raw reads per Roster.input_many call, for each K, beside speak_many of the same "
-                         "events parsed beforehand (the input section)")
-    ap.add_argument("--tell", type=per_call_counts, default=None, metavar="K[,K...]",
-                    help="also time K tells to one target per Roster.tell_many call, for each K, beside speak_many of K "
-                         "says of the same bodies (the tell section)")
-    ap.add_argument("--look", type=per_call_counts, default=None, metavar="K[,K...]",
-                    help="also time K looks per Roster.look_many call at a 1000-slot roster spread over 5 rooms, for each "
-                         "K, beside the CPU's transducer over look()'s strings (the look section)")
-    ap.add_argument("--who", type=per_call_counts, default=None, metavar="K[,K...]",
-                    help="also time K whos per Roster.who_many call at a 1000-slot roster spread over 5 rooms, for each K, "
-                         "beside the CPU composing and transducing who()'s strings (the who section)")
-    ap.add_argument("--relay", type=per_call_counts, default=None, metavar="K[,K...]",
-                    help="also time K says per Roster.relay_many call to a room of a 1000-slot roster with 0, 1 and 64 "
-                         "relaying clones in it, for each K, beside plan_many of the same broadcasts and the CPU doing "
-                         "clone_relay's work (the relay section)")
-    ap.add_argument("--rooms", type=per_call_counts, default=None, metavar="K[,K...]",
-                    help="also time K .rmst and K .rmsn listings per Roster.rooms_many call at a 1000-slot roster over 6 and "
-                         "over 1,024 rooms, for each K, beside the CPU composing and transducing rooms()'s strings (the "
-                         "rooms section)")
+    # the help lists --who before --relay; the two run, and are printed, the other way round
+    for option, metavar, text, _ in sorted(SECTIONS, key=lambda s: SECTIONS.index(s) - 1.5 * (s[0] == "who")):
+        ap.add_argument(f"--{option}", type=per_call_counts, default=None, metavar=metavar, help=text)
     a = ap.parse_args(argv)
     if a.reps < 1 or a.warmup < 0:
         ap.error("--reps must be >= 1 and --warmup >= 0")
@@ -982,66 +922,22 @@ def main(argv=None) -> int:
                 table = listeners(n, colour)
                 run = lambda: device.broadcast(TEXTS[text], table, 0, 0, COM[text])
                 first = run()
-                colour_of = table[1:, device.LISTENER_FIELDS.index("colour")]
-                expect = sum(len(nuts_path.transduce(TEXTS[text], int(c))) for c in colour_of)
+                expect = sum(len(nuts_path.transduce(TEXTS[text], int(c))) for c in colours(n, colour)[1:])
                 if int(first.out_offsets[-1]) != expect or int(first.admitted.sum()) != n - 1:
                     raise SystemExit(f"devpath: {n}/{text}/{colour}: device produced {int(first.out_offsets[-1])} "
                                      f"bytes, the CPU restatement {expect}")
-                for _ in range(a.warmup):
-                    run()
-                k, e = [], []
-                for _ in range(a.reps):
-                    r = run()
-                    k.append(r.timing["kernels_us"])
-                    e.append(r.timing["end_to_end_us"])
+                times = _timed(f"{n}/{text}/{colour}", {"broadcast": run}, a.reps, a.warmup)["broadcast"].times
                 cpu = cpu_derived_us(pb, text, colour, n)
-                ke = _stats(e)
                 cases.append({"n": n, "text": text, "colour": colour, "recipients": n - 1,
                               "bytes_out": int(first.out_offsets[-1]), "writes": int(first.write_offsets[-1]),
-                              "kernels_us": _stats(k), "end_to_end_us": ke,
+                              "kernels_us": times["kernels_us"], "end_to_end_us": times["end_to_end_us"],
                               "cpu_derived_us": round(cpu, 3),
-                              "end_to_end_over_cpu": round(ke["median"] / cpu, 1)})
-    per_call = {}
-    if a.per_call:
-        per_call = {
-            "per_call_kernels": ["nuts_fanout_measure_many", "rocprim device scan x2", "nuts_fanout_emit_many"],
-            "per_call_end_to_end_covers": "packing the K inputs into pinned memory, one H2D, kernels, three D2H, "
-                                          "two synchronises (python_us adds building the K tables and the copies "
-                                          "out of pinned memory)",
-            "per_call": [per_call_case(n, text, colour, k, a.reps, a.warmup, pb)
-                         for n in SIZES for text in TEXTS for colour in COLOURS for k in a.per_call],
-        }
-    roster = {}
-    if a.roster:
-        roster = {
-            "roster_kernels": ["nuts_roster_measure", "rocprim device scan x2", "nuts_roster_emit"],
-            "roster_end_to_end_covers": "packing the K inputs into pinned memory, one H2D (the roster table only in a "
-                                        "call after an update: h2d_bytes_first_call), kernels, three D2H, two "
-                                        "synchronises (python_us adds checking the K tuples and the copies out of "
-                                        "pinned memory)",
-            "roster": [roster_case(n, text, colour, k, a.reps, a.warmup, pb)
-                       for n in SIZES for text in TEXTS for colour in COLOURS for k in a.roster],
-        }
-    plan = {}
-    if a.plan:
-        plan = {
-            "plan_kernels": ["nuts_roster_plan"],
-            "plan_end_to_end_covers": "packing the K inputs into pinned memory, one H2D (the roster table only in a "
-                                      "call after an update: h2d_bytes_first_call), one kernel, one D2H of the "
-                                      "variants, their chunk sizes and the admit bitmap at their bound size, one "
-                                      "synchronise (python_us adds checking the K tuples, the copies out of pinned "
-                                      "memory and building the Plan; expand() is not timed)",
-            "plan": [plan_case(n, text, colour, k, a.reps, a.warmup, pb)
-                     for n in SIZES for text in TEXTS for colour in COLOURS for k in a.plan],
-        }
-    review = review_cases(a.review, a.reps, a.warmup, pb) if a.review else {}
-    speak = speak_cases(a.speak, a.reps, a.warmup, pb) if a.speak else {}
-    inputs = input_cases(a.input, a.reps, a.warmup, pb) if a.input else {}
-    tell = tell_cases(a.tell, a.reps, a.warmup, pb) if a.tell else {}
-    look = look_cases(a.look, a.reps, a.warmup, pb) if a.look else {}
-    relay = relay_cases(a.relay, a.reps, a.warmup, pb) if a.relay else {}
-    who = who_cases(a.who, a.reps, a.warmup, pb) if a.who else {}
-    rooms = rooms_cases(a.rooms, a.reps, a.warmup, pb) if a.rooms else {}
+                              "end_to_end_over_cpu": round(times["end_to_end_us"]["median"] / cpu, 1)})
+    sections = {}
+    for option, _, _, section in SECTIONS:
+        counts = getattr(a, option.replace("-", "_"))
+        if counts:
+            sections.update(globals()[section](counts, a.reps, a.warmup, pb))      # by name: whatever stands there now
     out = {
         "what": "user-space stage of one broadcast (admit predicate + transducer), device vs CPU",
         "device": "gfx950",
@@ -1051,17 +947,7 @@ def main(argv=None) -> int:
         "cpu_derived_from": {"pathbench": {k: v for k, v in pb.items() if k not in ("sink", "admitted")},
                              "formula": "(N-1) x transduce + N x fanout_predicate + format_line_once (derived, not timed)"},
         "cases": cases,
-        **per_call,
-        **roster,
-        **plan,
-        **review,
-        **speak,
-        **inputs,
-        **tell,
-        **look,
-        **relay,
-        **who,
-        **rooms,
+        **sections,
         "wall_s": round(time.perf_counter() - t_start, 1),
     }
     print(json.dumps(out))
