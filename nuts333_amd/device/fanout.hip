@@ -1012,11 +1012,33 @@ constexpr uint8_t kPresetNone = 0, kPresetVoid = 1, kPresetNothing = 2, kPresetU
 // the same inpstr once more (text_off + text_bytes).  So 2k texts need ctext_at(2 * text_bytes, 2k) bytes.
 constexpr int64_t ctext_at(int64_t text_off, int64_t t) { return text_off + kSpeakSlack * t; }
 
+// One of the tables a roster keeps on the device between calls, as a call's kernel sees it (the host's pass_kept fills it).
+struct Kept {
+    const uint32_t* fresh;       // the upload when the table was passed in this call, to be copied to keep; else nullptr
+    uint32_t* keep;              // the kept allocation
+    int words;                   // the table's size
+};
+
+// The copy tail of such a kernel, a word per lane: word w of the uploads among t, one after the other in that order, into
+// its kept allocation.  The loop unrolls, so t is indexed statically and stays in the kernel's arguments.
+template <int N>
+__device__ __forceinline__ void copy_kept(const Kept (&t)[N], int w)
+{
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        const int n = t[i].fresh ? t[i].words : 0;
+        if (w < n) {
+            t[i].keep[w] = t[i].fresh[w];
+            return;
+        }
+        w -= n;
+    }
+}
+
 struct SpeakArgs {
     const int32_t* room;         // [capacity] the roster's table: -1, no room
     const uint8_t* speech;       // [capacity * 16] the speaker state this call reads: the upload, or the kept table
-    const uint8_t* speech_new;   // the upload when there is one, to be copied to speech_keep; else nullptr
-    uint8_t* speech_keep;        // [capacity * 16] the kept table
+    Kept kept[1];                // the speaker table
     const uint8_t* text;         // the K inpstr, packed
     const int32_t* text_off;     // [k]
     const int32_t* text_len;     // [k]
@@ -1092,9 +1114,7 @@ __device__ __forceinline__ int compose(uint8_t* dst, int cap, const Piece (&pc)[
 __device__ void roster_speak(const SpeakArgs& a)
 {
     if ((int)blockIdx.x >= a.blocks) {      // the speaker table just uploaded, into the kept allocation: a word per lane
-        const int w = ((int)blockIdx.x - a.blocks) * kBlock + (int)threadIdx.x;
-        if (a.speech_new && w < a.capacity * (kSpeechRec / 4))
-            reinterpret_cast<uint32_t*>(a.speech_keep)[w] = reinterpret_cast<const uint32_t*>(a.speech_new)[w];
+        copy_kept(a.kept, ((int)blockIdx.x - a.blocks) * kBlock + (int)threadIdx.x);
         return;
     }
     const int lane = (int)threadIdx.x & 63;
@@ -1486,11 +1506,8 @@ struct TellArgs {
     const int32_t* room;         // [capacity] the roster's table: -1, no room
     const uint8_t* slotf;        // [capacity] and its flags byte: kLogin, kIgnall
     const uint8_t* speech;       // [capacity * 16] the speaker state this call reads: the upload, or the kept table
-    const uint8_t* speech_new;   // the upload when there is one, to be copied to speech_keep; else nullptr
-    uint8_t* speech_keep;
     const uint8_t* afk;          // [capacity * 64] the AFK messages, likewise
-    const uint8_t* afk_new;
-    uint8_t* afk_keep;
+    Kept kept[2];                // the speaker table, the AFK messages
     const uint8_t* text;         // the K inpstr, packed
     const int32_t* text_off;     // [k]
     const int32_t* text_len;     // [k]
@@ -1530,10 +1547,7 @@ __device__ __forceinline__ void name_match(uint64_t lo, uint32_t hi, int nlen, u
 __device__ void roster_tell(const TellArgs& a)
 {
     if ((int)blockIdx.x >= a.k) {           // the tables just uploaded, into the kept allocations: a word per lane
-        const int sw = a.speech_new ? a.capacity * (kSpeechRec / 4) : 0, aw = a.afk_new ? a.capacity * (kAfkRec / 4) : 0;
-        const int w = ((int)blockIdx.x - a.k) * kBlock + (int)threadIdx.x;
-        if (w < sw) reinterpret_cast<uint32_t*>(a.speech_keep)[w] = reinterpret_cast<const uint32_t*>(a.speech_new)[w];
-        else if (w - sw < aw) reinterpret_cast<uint32_t*>(a.afk_keep)[w - sw] = reinterpret_cast<const uint32_t*>(a.afk_new)[w - sw];
+        copy_kept(a.kept, ((int)blockIdx.x - a.k) * kBlock + (int)threadIdx.x);
         return;
     }
     __shared__ int s_exact[kBlock / 64], s_sub[kBlock / 64];
@@ -1746,14 +1760,9 @@ constexpr int64_t look_ctext_bytes(int64_t nr, int64_t nl) { return nr * kLookTe
 struct LookArgs {
     const int32_t* room;         // [capacity] the roster's table: -1, no room
     const uint8_t* speech;       // [capacity * 16] the speaker state this call reads: the upload, or the kept table
-    const uint8_t* speech_new;   // the upload when there is one, to be copied to speech_keep; else nullptr
-    uint8_t* speech_keep;
     const uint8_t* rooms;        // [look_rooms * 256] the room records, then [look_rooms * 816] the descriptions; likewise
-    const uint8_t* rooms_new;
-    uint8_t* rooms_keep;
     const uint8_t* udesc;        // [capacity * 32] the users' descriptions, likewise
-    const uint8_t* udesc_new;
-    uint8_t* udesc_keep;
+    Kept kept[3];                // the speaker table, the room table, the descriptions
     const int32_t* slot;         // [k] the lookers
     const int32_t* lroom;        // [k] their rooms, as indices into rms
     const int32_t* rms;          // [nr] the distinct rooms of the call
@@ -1919,13 +1928,7 @@ __device__ void roster_look(const LookArgs& a)
     __shared__ int s_cand[kBlock / 64], s_seen[kBlock / 64];
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     if ((int)blockIdx.x >= a.nr + a.k) {    // the tables just uploaded, into the kept allocations: a word per lane
-        const int sw = a.speech_new ? a.capacity * (kSpeechRec / 4) : 0, rw = a.rooms_new ? a.look_rooms * (kRoomRow / 4) : 0;
-        const int dw = a.udesc_new ? a.capacity * (kUserDescRow / 4) : 0;
-        const int w = ((int)blockIdx.x - a.nr - a.k) * kBlock + (int)threadIdx.x;
-        if (w < sw) reinterpret_cast<uint32_t*>(a.speech_keep)[w] = reinterpret_cast<const uint32_t*>(a.speech_new)[w];
-        else if (w - sw < rw) reinterpret_cast<uint32_t*>(a.rooms_keep)[w - sw] = reinterpret_cast<const uint32_t*>(a.rooms_new)[w - sw];
-        else if (w - sw - rw < dw)
-            reinterpret_cast<uint32_t*>(a.udesc_keep)[w - sw - rw] = reinterpret_cast<const uint32_t*>(a.udesc_new)[w - sw - rw];
+        copy_kept(a.kept, ((int)blockIdx.x - a.nr - a.k) * kBlock + (int)threadIdx.x);
         return;
     }
     const bool looker = (int)blockIdx.x >= a.nr;                // block-uniform
@@ -2030,11 +2033,7 @@ struct RelayArgs {
     const uint8_t* slot;         // [capacity] the roster's flag bytes: the owners' ignall
     const uint8_t* records;      // the records this call reads, the upload or the kept ones, as take_clones lays them out
     const uint8_t* names;        // [look_rooms * kRelayNameRow] likewise
-    const uint32_t* clones_new;  // the uploads when there are any, to be copied to the kept allocations; else nullptr
-    const uint32_t* names_new;
-    uint32_t* clones_keep;
-    uint32_t* names_keep;
-    int clone_words, name_words; // their sizes in words
+    Kept kept[2];                // the names, the clone records
     const uint8_t* text;         // the K texts, packed, as PlanArgs
     const int32_t* text_off;     // [k]
     const int32_t* text_len;     // [k]
@@ -2051,10 +2050,7 @@ struct RelayArgs {
 __device__ void roster_relay(const RelayArgs& a)
 {
     if ((int)blockIdx.x >= a.k) {           // the tables just uploaded, into the kept allocations: a word per lane
-        const int w = ((int)blockIdx.x - a.k) * kBlock + (int)threadIdx.x;
-        const int cw = a.clones_new ? a.clone_words : 0;
-        if (w < cw) a.clones_keep[w] = a.clones_new[w];
-        else if (a.names_new && w - cw < a.name_words) a.names_keep[w - cw] = a.names_new[w - cw];
+        copy_kept(a.kept, ((int)blockIdx.x - a.k) * kBlock + (int)threadIdx.x);
         return;
     }
     __shared__ int s_swears, s_any;
@@ -2151,17 +2147,10 @@ struct WhoArgs {
     const int32_t* room;         // [capacity] the roster's table
     const uint8_t* slotf;        // [capacity] and its flag bytes: login
     const uint8_t* speech;       // the tables this call reads, the uploads or the kept ones, as LookArgs
-    const uint8_t* speech_new;
-    uint8_t* speech_keep;
     const uint8_t* rooms;
-    const uint8_t* rooms_new;
-    uint8_t* rooms_keep;
     const uint8_t* udesc;
-    const uint8_t* udesc_new;
-    uint8_t* udesc_keep;
     const uint8_t* who;          // [capacity * 8] last_login and away
-    const uint8_t* who_new;
-    uint8_t* who_keep;
+    Kept kept[4];                // the speaker table, the room table, the descriptions, the who table
     const int32_t* slot;         // [k] the lookers
     const uint8_t* date;         // [date_len] long_date(1)
     int k, nl, capacity, look_rooms, words, date_len;   // words: bitmap words per looker, max(1, ceil(nl / 32))
@@ -2327,16 +2316,7 @@ __device__ void roster_who(const WhoArgs& a)
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const int line_blocks = (a.capacity + kBlock - 1) / kBlock;
     if ((int)blockIdx.x > line_blocks) {    // the tables just uploaded, into the kept allocations: a word per lane
-        const int sw = a.speech_new ? a.capacity * (kSpeechRec / 4) : 0, rw = a.rooms_new ? a.look_rooms * (kRoomRow / 4) : 0;
-        const int dw = a.udesc_new ? a.capacity * (kUserDescRow / 4) : 0, ww = a.who_new ? a.capacity * (kWhoRec / 4) : 0;
-        int w = ((int)blockIdx.x - line_blocks - 1) * kBlock + (int)threadIdx.x;
-        if (w < sw) { reinterpret_cast<uint32_t*>(a.speech_keep)[w] = reinterpret_cast<const uint32_t*>(a.speech_new)[w]; return; }
-        w -= sw;
-        if (w < rw) { reinterpret_cast<uint32_t*>(a.rooms_keep)[w] = reinterpret_cast<const uint32_t*>(a.rooms_new)[w]; return; }
-        w -= rw;
-        if (w < dw) { reinterpret_cast<uint32_t*>(a.udesc_keep)[w] = reinterpret_cast<const uint32_t*>(a.udesc_new)[w]; return; }
-        w -= dw;
-        if (w < ww) reinterpret_cast<uint32_t*>(a.who_keep)[w] = reinterpret_cast<const uint32_t*>(a.who_new)[w];
+        copy_kept(a.kept, ((int)blockIdx.x - line_blocks - 1) * kBlock + (int)threadIdx.x);
         return;
     }
     const bool fixed = (int)blockIdx.x == line_blocks;          // block-uniform
@@ -2492,11 +2472,8 @@ struct RoomsArgs {
     const int32_t* room;         // [capacity] the roster's table
     const uint8_t* slotf;        // [capacity] and its flag bytes: login
     const uint8_t* speech;       // the tables this call reads, the uploads or the kept ones, as LookArgs
-    const uint8_t* speech_new;
-    uint8_t* speech_keep;
     const uint8_t* rooms;
-    const uint8_t* rooms_new;
-    uint8_t* rooms_keep;
+    Kept kept[2];                // the speaker table, the room table
     const int32_t* slot;         // [k] the lookers: nothing of a text depends on them
     int k, capacity, look_rooms, kinds;     // kinds: kRoomsTopics | kRoomsLinks, what the lookers ask for
     int* violations;             // texts past their slots
@@ -2512,11 +2489,7 @@ __device__ void roster_rooms_count(const RoomsArgs& a)
     __shared__ int s_hist[kMaxLookRooms];
     const int count_blocks = (a.capacity + kBlock - 1) / kBlock;
     if ((int)blockIdx.x >= count_blocks) {  // the tables just uploaded, into the kept allocations: a word per lane
-        const int sw = a.speech_new ? a.capacity * (kSpeechRec / 4) : 0, rw = a.rooms_new ? a.look_rooms * (kRoomRow / 4) : 0;
-        int w = ((int)blockIdx.x - count_blocks) * kBlock + (int)threadIdx.x;
-        if (w < sw) { reinterpret_cast<uint32_t*>(a.speech_keep)[w] = reinterpret_cast<const uint32_t*>(a.speech_new)[w]; return; }
-        w -= sw;
-        if (w < rw) reinterpret_cast<uint32_t*>(a.rooms_keep)[w] = reinterpret_cast<const uint32_t*>(a.rooms_new)[w];
+        copy_kept(a.kept, ((int)blockIdx.x - count_blocks) * kBlock + (int)threadIdx.x);
         return;
     }
     const int bins = a.look_rooms < kMaxLookRooms ? a.look_rooms : kMaxLookRooms;
@@ -2886,6 +2859,15 @@ size_t layout_many(uintptr_t base, size_t text_bytes, size_t scan_bytes, ManyArg
 // keeps the table across growth, and a new device allocation is filled from it.
 constexpr int kMaxRosters = 64;
 constexpr int kMaxCapacity = 65536;
+
+// The tables a roster keeps on the device between calls, each in an allocation of its own that the first call to give
+// the table makes and that never moves.  A caller passes one only when it changed: see pass_kept().
+enum KeptId { kKeptSpeech, kKeptAfk, kKeptRooms, kKeptUdesc, kKeptWho, kKeptClones, kKeptNames, kKeptCount };
+struct KeptTable {
+    const char* what;            // for error messages
+    uint8_t* d = nullptr;
+};
+
 struct Roster {
     bool live = false;
     bool resident = false;       // the device allocation holds the mirror's table
@@ -2896,19 +2878,50 @@ struct Roster {
     size_t cap_d = 0, cap_mirror = 0;
     int review_rooms = 0;        // rooms 0 .. review_rooms - 1 own a review ring
     uint8_t* rings = nullptr;    // the rings, then the cursors: an allocation of its own, made on first use, never moved
-    uint8_t* speech = nullptr;   // the speakers' state, 16 bytes per slot: likewise, made by the first nd_roster_speak
     bool revtell = false;        // every slot owns a revtell ring
     uint8_t* tell_rings = nullptr;   // the revtell rings, then their cursors: as rings
-    uint8_t* afk = nullptr;      // the AFK messages, 64 bytes per slot: as speech, made by the first nd_roster_tell
     int look_rooms = 0;          // rooms 0 .. look_rooms - 1 own a room record
-    uint8_t* room_table = nullptr;   // their records, then their descriptions: as speech, made by the first nd_roster_look
-    uint8_t* udesc = nullptr;    // the users' descriptions, 32 bytes per slot: likewise
     int clones = 0;              // clone records 0 .. clones - 1
-    uint8_t* clone_table = nullptr;  // their owners, rooms and hear bytes (take_clones): as speech, made by the first nd_roster_relay
-    uint8_t* relay_names = nullptr;  // the look rooms' names, 24 bytes per room: likewise
-    uint8_t* who = nullptr;      // last_login and away, 8 bytes per slot: as speech, made by the first nd_roster_who
+    KeptTable kept[kKeptCount] = {{"speaker table"}, {"AFK messages"}, {"room table"}, {"user descriptions"},
+                                  {"who table"}, {"clone records"}, {"room names"}};   // by KeptId; kept_bytes() has their sizes
 };
 Roster g_rosters[kMaxRosters];
+
+// A roster's clone records as they lie on the device, in the upload and in the kept allocation alike: three arrays in a
+// 256-byte slice each, so the bytes they span are whole words.
+void take_clones(Carver& take, int clones, const int32_t*& owner, const int32_t*& room, const uint8_t*& hear)
+{
+    take(owner, (size_t)clones);
+    take(room, (size_t)clones);
+    take(hear, (size_t)clones);
+}
+
+// The size of kept table `id` of a roster with these dimensions, a whole number of words.
+size_t kept_bytes(int id, int capacity, int look_rooms, int clones)
+{
+    switch (id) {
+    case kKeptSpeech: return (size_t)capacity * kSpeechRec;                // the speakers' state, 16 bytes per slot
+    case kKeptAfk: return (size_t)capacity * kAfkRec;                      // the AFK messages, 64 bytes per slot
+    case kKeptRooms: return (size_t)look_rooms * kRoomRow;                 // the look rooms' records, then their descriptions
+    case kKeptUdesc: return (size_t)capacity * kUserDescRow;               // the users' descriptions, 32 bytes per slot
+    case kKeptWho: return (size_t)capacity * kWhoRec;                      // last_login and away, 8 bytes per slot
+    case kKeptNames: return (size_t)look_rooms * kRelayNameRow;            // the look rooms' names, 24 bytes per room
+    default: {                                                             // the clones' owners, rooms and hear bytes
+        Carver sized{0};
+        const int32_t *owner, *room;
+        const uint8_t* hear;
+        take_clones(sized, clones, owner, room, hear);
+        return sized.at;
+    }
+    }
+}
+size_t kept_bytes(const Roster& r, int id) { return kept_bytes(id, r.capacity, r.look_rooms, r.clones); }
+
+// Room for a kept table's upload in a layout; t.fresh is where it lies.
+void take_kept(Carver& take, Kept& t, int id, int capacity, int look_rooms = 0, int clones = 0)
+{
+    take(t.fresh, kept_bytes(id, capacity, look_rooms, clones) / sizeof(uint32_t));
+}
 
 // One of a roster's two sets of rings: the rooms' review rings (15 lines each), or the slots' revtell rings (5 lines).
 struct RingSet {
@@ -3013,7 +3026,7 @@ size_t layout_review(uintptr_t base, int capacity, size_t clear_bytes, ReviewArg
 }
 
 // nd_roster_speak's layout of a roster's allocation: the table, then the upload of the
-// speaker table (which the kept one, r.speech, is filled from), the call's inputs ending with violations, the results
+// speaker table (which the kept one, r.kept[], is filled from), the call's inputs ending with violations, the results
 // next to each other, and last what only the kernels pass to each other.  One upload starts at the speaker table if it
 // was given, else at the inputs; a table the device does not hold goes in front of it (upload()).
 // nd_roster_input's (q given) differs in what describes an event: the upload carries the reads' offsets and lengths
@@ -3023,10 +3036,10 @@ size_t layout_speak(uintptr_t base, size_t text_bytes, size_t clear_bytes, Speak
                     const uint8_t** clear, ParseArgs* q = nullptr)
 {
     Carver take{base};
-    const size_t k = (size_t)s.k, cap = (size_t)s.capacity;
+    const size_t k = (size_t)s.k;
     const size_t ctext_bytes = (size_t)ctext_at(2 * (int64_t)text_bytes, 2 * (int64_t)k);
     take_table(take, s.capacity, s.room, p.slot);
-    take(s.speech_new, cap * kSpeechRec);
+    take_kept(take, s.kept[0], kKeptSpeech, s.capacity);
     take(s.text, text_bytes);
     if (q) {
         take(q->read_off, k);
@@ -3085,17 +3098,17 @@ size_t layout_speak(uintptr_t base, size_t text_bytes, size_t clear_bytes, Speak
 }
 
 // nd_roster_tell's layout of a roster's allocation, after layout_speak's pattern: the table, the uploads of the speaker
-// table and of the AFK messages (which the kept ones, r.speech and r.afk, are filled from), the call's inputs ending with
+// table and of the AFK messages (which the kept ones of r.kept[] are filled from), the call's inputs ending with
 // violations, the results next to each other, and last what only the kernels pass to each other.  One upload starts at
 // the first of the two tables behind the table that was given, or at the inputs (upload()).
 size_t layout_tell(uintptr_t base, size_t text_bytes, size_t clear_bytes, TellArgs& s, SpeakPlanArgs& p, const uint8_t** clear)
 {
     Carver take{base};
-    const size_t k = (size_t)s.k, cap = (size_t)s.capacity;
+    const size_t k = (size_t)s.k;
     const size_t ctext_bytes = (size_t)ptext_at(2 * (int64_t)text_bytes, 2 * (int64_t)k);
     take_table(take, s.capacity, s.room, s.slotf);
-    take(s.speech_new, cap * kSpeechRec);
-    take(s.afk_new, cap * kAfkRec);
+    take_kept(take, s.kept[0], kKeptSpeech, s.capacity);
+    take_kept(take, s.kept[1], kKeptAfk, s.capacity);
     take(s.text, text_bytes);
     take(s.text_off, k);
     take(s.text_len, k);
@@ -3130,12 +3143,12 @@ size_t layout_tell(uintptr_t base, size_t text_bytes, size_t clear_bytes, TellAr
 size_t layout_look(uintptr_t base, size_t members, size_t nl, LookArgs& s, SpeakPlanArgs& p)
 {
     Carver take{base};
-    const size_t k = (size_t)s.k, nr = (size_t)s.nr, cap = (size_t)s.capacity, t = kLookTexts * nr + kLookFixed + nl;
+    const size_t k = (size_t)s.k, nr = (size_t)s.nr, t = kLookTexts * nr + kLookFixed + nl;
     const size_t ctext_bytes = (size_t)look_ctext_bytes((int64_t)nr, (int64_t)nl);
     take_table(take, s.capacity, s.room, p.slot);
-    take(s.speech_new, cap * kSpeechRec);
-    take(s.rooms_new, (size_t)s.look_rooms * kRoomRow);
-    take(s.udesc_new, cap * kUserDescRow);
+    take_kept(take, s.kept[0], kKeptSpeech, s.capacity);
+    take_kept(take, s.kept[1], kKeptRooms, s.capacity, s.look_rooms);
+    take_kept(take, s.kept[2], kKeptUdesc, s.capacity);
     take(s.slot, k);
     take(s.lroom, k);
     take(s.rms, nr);
@@ -3169,13 +3182,13 @@ size_t layout_look(uintptr_t base, size_t members, size_t nl, LookArgs& s, Speak
 size_t layout_who(uintptr_t base, WhoArgs& s, SpeakPlanArgs& p)
 {
     Carver take{base};
-    const size_t k = (size_t)s.k, nl = (size_t)s.nl, cap = (size_t)s.capacity, t = kWhoFixed + nl;
+    const size_t k = (size_t)s.k, nl = (size_t)s.nl, t = kWhoFixed + nl;
     const size_t ctext_bytes = (size_t)who_ctext_bytes((int64_t)nl);
     take_table(take, s.capacity, s.room, s.slotf);
-    take(s.speech_new, cap * kSpeechRec);
-    take(s.rooms_new, (size_t)s.look_rooms * kRoomRow);
-    take(s.udesc_new, cap * kUserDescRow);
-    take(s.who_new, cap * kWhoRec);
+    take_kept(take, s.kept[0], kKeptSpeech, s.capacity);
+    take_kept(take, s.kept[1], kKeptRooms, s.capacity, s.look_rooms);
+    take_kept(take, s.kept[2], kKeptUdesc, s.capacity);
+    take_kept(take, s.kept[3], kKeptWho, s.capacity);
     take(s.slot, k);
     take(s.date, (size_t)kWhoDateLen + 1);
     take(s.violations, 1);
@@ -3204,11 +3217,11 @@ size_t layout_who(uintptr_t base, WhoArgs& s, SpeakPlanArgs& p)
 size_t layout_rooms(uintptr_t base, RoomsArgs& s, SpeakPlanArgs& p)
 {
     Carver take{base};
-    const size_t k = (size_t)s.k, nr = (size_t)s.look_rooms, cap = (size_t)s.capacity, t = kRoomsFixed + 2 * nr;
+    const size_t k = (size_t)s.k, nr = (size_t)s.look_rooms, t = kRoomsFixed + 2 * nr;
     const size_t ctext_bytes = (size_t)rooms_ctext_bytes((int64_t)nr);
     take_table(take, s.capacity, s.room, s.slotf);
-    take(s.speech_new, cap * kSpeechRec);
-    take(s.rooms_new, nr * kRoomRow);
+    take_kept(take, s.kept[0], kKeptSpeech, s.capacity);
+    take_kept(take, s.kept[1], kKeptRooms, s.capacity, s.look_rooms);
     take(s.slot, k);
     take(s.violations, 1);
     take(s.clen, t);
@@ -3229,29 +3242,19 @@ size_t layout_rooms(uintptr_t base, RoomsArgs& s, SpeakPlanArgs& p)
     return take.at;
 }
 
-// A roster's clone records as they lie on the device, in the upload and in the kept allocation alike: three arrays in a
-// 256-byte slice each, so the bytes they span are whole words.
-void take_clones(Carver& take, int clones, const int32_t*& owner, const int32_t*& room, const uint8_t*& hear)
-{
-    take(owner, (size_t)clones);
-    take(room, (size_t)clones);
-    take(hear, (size_t)clones);
-}
-
 // nd_roster_relay's layout of a roster's allocation, after layout_plan's pattern: the table, the uploads of the rooms' names
 // and of the clone records (which the kept ones are filled from), nd_roster_plan's inputs with the clone senders and the
 // relay texts' offsets, ending with violations, then the plan's results and the relay's (p plans the relay texts) next to
 // each other: one download.
 // The clone records lie last of the tables, so an upload of theirs alone carries nothing else.
-size_t layout_relay(uintptr_t base, size_t text_bytes, size_t clear_bytes, PlanArgs& a, RelayArgs& q, SpeakPlanArgs& p, const uint8_t** clear,
-                    const int32_t** owner_new, const int32_t** room_new, const uint8_t** hear_new)
+size_t layout_relay(uintptr_t base, size_t text_bytes, size_t clear_bytes, PlanArgs& a, RelayArgs& q, SpeakPlanArgs& p, const uint8_t** clear)
 {
     Carver take{base};
     const size_t k = (size_t)a.k;
     const size_t rtext_bytes = text_bytes + (size_t)kRelaySlack * k;
     take_table(take, a.capacity, a.room, a.slot);
-    take(q.names_new, (size_t)q.look_rooms * (kRelayNameRow / 4));
-    take_clones(take, q.clones, *owner_new, *room_new, *hear_new);
+    take_kept(take, q.kept[0], kKeptNames, q.capacity, q.look_rooms);
+    take_kept(take, q.kept[1], kKeptClones, q.capacity, q.look_rooms, q.clones);   // whole slices, as take_clones gives them
     take(a.text, text_bytes);
     take(a.text_off, k);
     take(a.text_len, k);
@@ -3275,7 +3278,6 @@ size_t layout_relay(uintptr_t base, size_t text_bytes, size_t clear_bytes, PlanA
     take(p.vwsz, 2 * k * kMaxWrites);
     take(q.rtext, rtext_bytes);
     take(p.var, (size_t)var_at((int64_t)rtext_bytes, (int64_t)k));
-    q.clones_new = reinterpret_cast<const uint32_t*>(*owner_new);
     q.slot = a.slot;
     q.text = a.text;
     q.text_off = a.text_off;
@@ -3362,6 +3364,84 @@ int upload(Roster& r, size_t table_bytes, size_t first, size_t in_bytes, size_t*
     }
     ND_CHECK(hipMemcpyAsync(r.d + first, r.mirror + first, in_bytes - first, hipMemcpyHostToDevice, g.stream));
     r.resident = true;
+    return 0;
+}
+
+// One entry of a call's list of kept tables, which names them in the order the call's layout places their uploads:
+// everything such a call does about its kept tables follows from that list.
+struct Given {
+    int id;                      // which of the roster's kept tables
+    const uint8_t* src;          // the caller's, passed because it changed; else nullptr
+    const uint8_t** read;        // the kernel's pointer to what this call reads: the upload, or the kept table
+};
+
+// A table the device does not hold yet must be given: `sentence` is the call's own way to say so.  A table of no
+// bytes (the room table of a roster without look rooms) is neither asked for, made nor copied.
+template <int N>
+int check_given(const Roster& r, const Given (&t)[N], const char* sentence)
+{
+    for (const Given& e : t)
+        if (kept_bytes(r, e.id) && !r.kept[e.id].d && !e.src) {
+            snprintf(g_err, sizeof(g_err), "%s", sentence);
+            return -1;
+        }
+    return 0;
+}
+
+// The caller's table `id` into the mirror at dst, as it lies on the device.  The clone records alone arrive otherwise:
+// packed, the int32 owners, the int32 rooms, then the hear bytes, for take_clones' three slices.
+void pack_kept(const Roster& r, int id, uint8_t* dst, const uint8_t* src)
+{
+    if (id != kKeptClones) {
+        memcpy(dst, src, kept_bytes(r, id));
+        return;
+    }
+    Carver at{(uintptr_t)dst};
+    const int32_t *owner, *room;
+    const uint8_t* hear;
+    take_clones(at, r.clones, owner, room, hear);
+    const size_t n = (size_t)r.clones;
+    memcpy(const_cast<int32_t*>(owner), src, n * sizeof(int32_t));
+    memcpy(const_cast<int32_t*>(room), src + n * sizeof(int32_t), n * sizeof(int32_t));
+    memcpy(const_cast<uint8_t*>(hear), src + 2 * n * sizeof(int32_t), n);
+}
+
+// The kept tables of a call whose mirror and allocation are laid out: at[i].fresh is where table i's upload lies in the
+// layout at base 0, kept[i].fresh where it lies on the device, and the inputs start at tables_end.  Makes the kept
+// allocations that are not there yet and packs the given tables into the mirror.  What lies after the first given table
+// travels too, but the kernel is told of the given ones alone, so the mirror's bytes of the others need not be current:
+// one walk of the list gives both *first, where upload() starts -- the first given table, or the inputs -- and
+// *copy_blocks, the blocks the kernel's copy tail takes after the call's own.  kept[] is left as copy_kept() wants it,
+// and every read pointer at the upload or at the kept table.
+template <int N>
+int pass_kept(Roster& r, const Given (&t)[N], const Kept (&at)[N], Kept (&kept)[N], size_t tables_end, size_t* first,
+              unsigned* copy_blocks)
+{
+    size_t copy_words = 0;
+    *first = tables_end;
+    for (int i = 0; i < N; i++) {
+        KeptTable& k = r.kept[t[i].id];
+        const size_t bytes = kept_bytes(r, t[i].id);
+        if (bytes && !k.d) {
+            hipError_t e = hipMalloc((void**)&k.d, bytes);
+            if (e != hipSuccess) {
+                k.d = nullptr;
+                return fail(k.what, e);
+            }
+        }
+        kept[i].keep = reinterpret_cast<uint32_t*>(k.d);
+        kept[i].words = (int)(bytes / sizeof(uint32_t));
+        if (t[i].src) {
+            pack_kept(r, t[i].id, r.mirror + (uintptr_t)at[i].fresh, t[i].src);
+            *first = std::min(*first, (size_t)(uintptr_t)at[i].fresh);
+            copy_words += bytes / sizeof(uint32_t);
+            *t[i].read = reinterpret_cast<const uint8_t*>(kept[i].fresh);
+        } else {
+            *t[i].read = k.d;
+            kept[i].fresh = nullptr;
+        }
+    }
+    *copy_blocks = (unsigned)((copy_words + kBlock - 1) / kBlock);
     return 0;
 }
 
@@ -3615,13 +3695,8 @@ int nd_roster_destroy(int handle)
     if (r->d) (void)hipFree(r->d);
     if (r->rings) (void)hipFree(r->rings);
     if (r->tell_rings) (void)hipFree(r->tell_rings);
-    if (r->speech) (void)hipFree(r->speech);
-    if (r->afk) (void)hipFree(r->afk);
-    if (r->room_table) (void)hipFree(r->room_table);
-    if (r->udesc) (void)hipFree(r->udesc);
-    if (r->clone_table) (void)hipFree(r->clone_table);
-    if (r->relay_names) (void)hipFree(r->relay_names);
-    if (r->who) (void)hipFree(r->who);
+    for (const KeptTable& k : r->kept)
+        if (k.d) (void)hipFree(k.d);
     if (r->mirror) (void)hipHostFree(r->mirror);
     *r = Roster{};
     return 0;
@@ -3991,21 +4066,12 @@ static int speech_call(int handle, int k, const uint8_t* text, int64_t text_byte
         snprintf(g_err, sizeof(g_err), "the events' texts hold %lld bytes, not %lld", (long long)sum, (long long)text_bytes);
         return -1;
     }
-    if (!r->speech && !speech) {
-        snprintf(g_err, sizeof(g_err), "the roster's first speech call must give the speaker table");
-        return -1;
-    }
+    SpeakArgs s{};
+    const Given given[] = {{kKeptSpeech, speech, &s.speech}};
+    if (check_given(*r, given, "the roster's first speech call must give the speaker table")) return -1;
     if (record && ensure_rings(*r, g.stream)) return -1;
-    if (!r->speech) {
-        hipError_t e = hipMalloc((void**)&r->speech, (size_t)cap * kSpeechRec);
-        if (e != hipSuccess) {
-            r->speech = nullptr;
-            return fail("speaker table", e);
-        }
-    }
     const double t0 = now_ns();
     hipStream_t st = g.stream;
-    SpeakArgs s{};
     SpeakPlanArgs p{};
     s.k = p.k = k;
     s.capacity = p.capacity = cap;
@@ -4023,7 +4089,7 @@ static int speech_call(int handle, int k, const uint8_t* text, int64_t text_byte
     ParseArgs q{}, qo{};
     q.k = qo.k = k;
     const size_t need = layout_speak(0, (size_t)text_bytes, clear_bytes, so, po, &o_clear, parsed ? &qo : nullptr);
-    const size_t table_bytes = (uintptr_t)so.speech_new, speech_end = (uintptr_t)so.text;
+    const size_t table_bytes = (uintptr_t)so.kept[0].fresh, tables_end = (uintptr_t)so.text;
     const size_t in_bytes = (uintptr_t)so.violations + sizeof(int);
     const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
     if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
@@ -4034,7 +4100,6 @@ static int speech_call(int handle, int k, const uint8_t* text, int64_t text_byte
 
     uint8_t* h = r->mirror;
     const Put put{h};
-    if (speech) put(so.speech_new, speech, (size_t)cap * kSpeechRec);
     put(so.text, text, (size_t)text_bytes);
     put(parsed ? qo.read_off : so.text_off, text_off, (size_t)k * sizeof(int32_t));
     put(parsed ? qo.read_len : so.text_len, text_len, (size_t)k * sizeof(int32_t));
@@ -4051,13 +4116,11 @@ static int speech_call(int handle, int k, const uint8_t* text, int64_t text_byte
     put(o_clear, clear, clear_bytes);
     *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
     // the speaker table's upload lies between the table and the inputs: it travels only when it was given
-    size_t h2d = 0;
-    if (upload(*r, table_bytes, speech ? table_bytes : speech_end, in_bytes, &h2d)) return -1;
-    s.speech = speech ? s.speech_new : r->speech;
-    if (!speech) s.speech_new = nullptr;
-    s.speech_keep = r->speech;
+    size_t first = 0, h2d = 0;
+    unsigned copy_blocks = 0;
+    if (pass_kept(*r, given, so.kept, s.kept, tables_end, &first, &copy_blocks)) return -1;
+    if (upload(*r, table_bytes, first, in_bytes, &h2d)) return -1;
 
-    const unsigned copy_blocks = speech ? (unsigned)(((size_t)cap * (kSpeechRec / 4) + kBlock - 1) / kBlock) : 0u;
     ND_CHECK(hipEventRecord(g.ev0, st));
     if (parsed) {
         q.speech = s.speech;
@@ -4151,18 +4214,6 @@ int nd_roster_input(int handle, int k, const uint8_t* data, int64_t data_bytes, 
                        table, speech, clear, outcome, clen, bits, vn, vw, vwsz, ctext, var, timing, &parsed);
 }
 
-// A kept per-slot table of a roster (the speaker state, the AFK messages), made on the first call that gives it.
-static int ensure_kept(uint8_t** p, size_t bytes, const char* what)
-{
-    if (*p) return 0;
-    hipError_t e = hipMalloc((void**)p, bytes);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        return fail(what, e);
-    }
-    return 0;
-}
-
 // K private speech events of roster `handle`, as tell() and pemote() answer them.  Event b: the speaker's slot slots[b],
 // the command coms[b] (NP_TELL 5, NP_PEMOTE 8), inpstr and words[b] as nd_roster_speak's.  table and speech as
 // nd_roster_speak's, the speech flags byte with afk 8 and igntell 16 as well; afk is NULL when no AFK message changed
@@ -4202,16 +4253,12 @@ int nd_roster_tell(int handle, int k, const uint8_t* text, int64_t text_bytes, c
         snprintf(g_err, sizeof(g_err), "the events' texts hold %lld bytes, not %lld", (long long)sum, (long long)text_bytes);
         return -1;
     }
-    if ((!r->speech && !speech) || (!r->afk && !afk)) {
-        snprintf(g_err, sizeof(g_err), "the roster's first private speech call must give the speaker table and the AFK messages");
-        return -1;
-    }
+    TellArgs s{};
+    const Given given[] = {{kKeptSpeech, speech, &s.speech}, {kKeptAfk, afk, &s.afk}};
+    if (check_given(*r, given, "the roster's first private speech call must give the speaker table and the AFK messages")) return -1;
     if (record && ensure_rings(*r, g.stream, true)) return -1;
-    if (ensure_kept(&r->speech, (size_t)cap * kSpeechRec, "speaker table")) return -1;
-    if (ensure_kept(&r->afk, (size_t)cap * kAfkRec, "AFK messages")) return -1;
     const double t0 = now_ns();
     hipStream_t st = g.stream;
-    TellArgs s{};
     SpeakPlanArgs p{};                  // k = 0, tiles = 0: no room lines, a block per text
     s.k = k;
     s.capacity = p.capacity = cap;
@@ -4223,7 +4270,7 @@ int nd_roster_tell(int handle, int k, const uint8_t* text, int64_t text_bytes, c
     SpeakPlanArgs po = p;
     const uint8_t *o_clear = nullptr, *d_clear = nullptr;
     const size_t need = layout_tell(0, (size_t)text_bytes, clear_bytes, so, po, &o_clear);
-    const size_t table_bytes = (uintptr_t)so.speech_new, afk_at = (uintptr_t)so.afk_new, tables_end = (uintptr_t)so.text;
+    const size_t table_bytes = (uintptr_t)so.kept[0].fresh, tables_end = (uintptr_t)so.text;
     const size_t in_bytes = (uintptr_t)so.violations + sizeof(int);
     const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
     if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
@@ -4234,8 +4281,6 @@ int nd_roster_tell(int handle, int k, const uint8_t* text, int64_t text_bytes, c
 
     uint8_t* h = r->mirror;
     const Put put{h};
-    if (speech) put(so.speech_new, speech, (size_t)cap * kSpeechRec);
-    if (afk) put(so.afk_new, afk, (size_t)cap * kAfkRec);
     put(so.text, text, (size_t)text_bytes);
     put(so.text_off, text_off, (size_t)k * sizeof(int32_t));
     put(so.text_len, text_len, (size_t)k * sizeof(int32_t));
@@ -4249,20 +4294,14 @@ int nd_roster_tell(int handle, int k, const uint8_t* text, int64_t text_bytes, c
     }
     put(o_clear, clear, clear_bytes);
     *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
-    // the tables' uploads lie between the table and the inputs: what lies after the first one that changed travels too,
-    // but the kernel is told of the changed ones alone, so the mirror's bytes of the others need not be current
-    size_t h2d = 0;
-    if (upload(*r, table_bytes, speech ? table_bytes : afk ? afk_at : tables_end, in_bytes, &h2d)) return -1;
-    s.speech = speech ? s.speech_new : r->speech;
-    s.afk = afk ? s.afk_new : r->afk;
-    if (!speech) s.speech_new = nullptr;
-    if (!afk) s.afk_new = nullptr;
-    s.speech_keep = r->speech;
-    s.afk_keep = r->afk;
+    // the tables' uploads lie between the table and the inputs
+    size_t first = 0, h2d = 0;
+    unsigned copy_blocks = 0;
+    if (pass_kept(*r, given, so.kept, s.kept, tables_end, &first, &copy_blocks)) return -1;
+    if (upload(*r, table_bytes, first, in_bytes, &h2d)) return -1;
 
-    const size_t copy_words = (size_t)cap * ((speech ? kSpeechRec / 4 : 0) + (afk ? kAfkRec / 4 : 0));
     ND_CHECK(hipEventRecord(g.ev0, st));
-    hipLaunchKernelGGL(nuts_roster_tell, dim3((unsigned)(k + (copy_words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, s);
+    hipLaunchKernelGGL(nuts_roster_tell, dim3((unsigned)k + copy_blocks), dim3(kBlock), 0, st, s);
     ND_CHECK(hipGetLastError());
     hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)(2 * k)), dim3(kBlock), 0, st, p);
     ND_CHECK(hipGetLastError());
@@ -4297,7 +4336,7 @@ int nd_roster_look_rooms(int handle, int n)
 {
     Roster* r = roster_at(handle);
     if (!r) return -1;
-    if (n < 0 || n > kMaxLookRooms || r->room_table) {
+    if (n < 0 || n > kMaxLookRooms || r->kept[kKeptRooms].d) {
         snprintf(g_err, sizeof(g_err), "look rooms %d outside 0 .. %d, or the room table is already in use", n, kMaxLookRooms);
         return -1;
     }
@@ -4350,16 +4389,11 @@ int nd_roster_look(int handle, int k, const int32_t* slots, const int32_t* lroom
             snprintf(g_err, sizeof(g_err), "room %d of the call: no look room (0 .. %d), or its lines out of range", rms[i], nrooms - 1);
             return -1;
         }
-    if ((!r->speech && !speech) || (!r->room_table && !rooms) || (!r->udesc && !udesc)) {
-        snprintf(g_err, sizeof(g_err), "the roster's first look call must give the speaker table, the room table and the descriptions");
-        return -1;
-    }
-    if (ensure_kept(&r->speech, (size_t)cap * kSpeechRec, "speaker table")) return -1;
-    if (ensure_kept(&r->room_table, (size_t)nrooms * kRoomRow, "room table")) return -1;
-    if (ensure_kept(&r->udesc, (size_t)cap * kUserDescRow, "user descriptions")) return -1;
+    LookArgs s{};
+    const Given given[] = {{kKeptSpeech, speech, &s.speech}, {kKeptRooms, rooms, &s.rooms}, {kKeptUdesc, udesc, &s.udesc}};
+    if (check_given(*r, given, "the roster's first look call must give the speaker table, the room table and the descriptions")) return -1;
     const double t0 = now_ns();
     hipStream_t st = g.stream;
-    LookArgs s{};
     SpeakPlanArgs p{};                  // k = 0, tiles = 0: no room lines, a block per text
     s.k = k;
     s.nr = nr;
@@ -4371,8 +4405,8 @@ int nd_roster_look(int handle, int k, const int32_t* slots, const int32_t* lroom
     LookArgs so = s;                    // offsets of every array in the roster's allocation
     SpeakPlanArgs po = p;
     const size_t need = layout_look(0, nm, nl, so, po);
-    const size_t table_bytes = (uintptr_t)so.speech_new, rooms_at = (uintptr_t)so.rooms_new, udesc_at = (uintptr_t)so.udesc_new;
-    const size_t tables_end = (uintptr_t)so.slot, in_bytes = (uintptr_t)so.violations + sizeof(int);
+    const size_t table_bytes = (uintptr_t)so.kept[0].fresh, tables_end = (uintptr_t)so.slot;
+    const size_t in_bytes = (uintptr_t)so.violations + sizeof(int);
     const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
     if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
     if (table) new_table(*r, so.room, po.slot, table);
@@ -4388,9 +4422,6 @@ int nd_roster_look(int handle, int k, const int32_t* slots, const int32_t* lroom
 
     uint8_t* h = r->mirror;
     const Put put{h};
-    if (speech) put(so.speech_new, speech, (size_t)cap * kSpeechRec);
-    if (rooms) put(so.rooms_new, rooms, (size_t)nrooms * kRoomRow);
-    if (udesc) put(so.udesc_new, udesc, (size_t)cap * kUserDescRow);
     put(so.slot, slots, (size_t)k * sizeof(int32_t));
     put(so.lroom, lroom, (size_t)k * sizeof(int32_t));
     put(so.rms, rms, (size_t)nr * sizeof(int32_t));
@@ -4403,24 +4434,14 @@ int nd_roster_look(int handle, int k, const int32_t* slots, const int32_t* lroom
     for (size_t l = 0; l < nl; l++)
         coff[kLookTexts * nr + kLookFixed + l] = (int32_t)(nr * kLookTextStride + kLookFixedStride + l * kLineRow);
     *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
-    // the tables' uploads lie between the table and the inputs: what lies after the first one that changed travels too,
-    // but the kernel is told of the changed ones alone, so the mirror's bytes of the others need not be current
-    size_t h2d = 0;
-    if (upload(*r, table_bytes, speech ? table_bytes : rooms ? rooms_at : udesc ? udesc_at : tables_end, in_bytes, &h2d)) return -1;
-    s.speech = speech ? s.speech_new : r->speech;
-    s.rooms = rooms ? s.rooms_new : r->room_table;
-    s.udesc = udesc ? s.udesc_new : r->udesc;
-    if (!speech) s.speech_new = nullptr;
-    if (!rooms) s.rooms_new = nullptr;
-    if (!udesc) s.udesc_new = nullptr;
-    s.speech_keep = r->speech;
-    s.rooms_keep = r->room_table;
-    s.udesc_keep = r->udesc;
+    // the tables' uploads lie between the table and the inputs
+    size_t first = 0, h2d = 0;
+    unsigned copy_blocks = 0;
+    if (pass_kept(*r, given, so.kept, s.kept, tables_end, &first, &copy_blocks)) return -1;
+    if (upload(*r, table_bytes, first, in_bytes, &h2d)) return -1;
 
-    const size_t copy_words = (speech ? (size_t)cap * (kSpeechRec / 4) : 0) + (rooms ? (size_t)nrooms * (kRoomRow / 4) : 0) +
-                              (udesc ? (size_t)cap * (kUserDescRow / 4) : 0);
     ND_CHECK(hipEventRecord(g.ev0, st));
-    hipLaunchKernelGGL(nuts_roster_look, dim3((unsigned)(nr + k + (copy_words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, s);
+    hipLaunchKernelGGL(nuts_roster_look, dim3((unsigned)(nr + k) + copy_blocks), dim3(kBlock), 0, st, s);
     ND_CHECK(hipGetLastError());
     hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)texts), dim3(kBlock), 0, st, p);
     ND_CHECK(hipGetLastError());
@@ -4455,7 +4476,7 @@ int nd_roster_clones(int handle, int n)
 {
     Roster* r = roster_at(handle);
     if (!r) return -1;
-    if (n < 0 || n > kMaxCapacity || r->clone_table) {
+    if (n < 0 || n > kMaxCapacity || r->kept[kKeptClones].d) {
         snprintf(g_err, sizeof(g_err), "clone records %d outside 0 .. %d, or the records are already in use", n, kMaxCapacity);
         return -1;
     }
@@ -4499,21 +4520,12 @@ static int relay_call(int handle, int k, const uint8_t* text, int64_t text_bytes
             snprintf(g_err, sizeof(g_err), "broadcast %d: clone sender or text out of range", b);
             return -1;
         }
-    if ((!r->clone_table && !clones) || (!r->relay_names && !names)) {
-        snprintf(g_err, sizeof(g_err), "the roster's first relay call must give the clone records and the rooms' names");
-        return -1;
-    }
-    const int32_t *ko = nullptr, *kr = nullptr;      // the kept records are laid out as the upload's
-    const uint8_t* kh = nullptr;
-    Carver sized{0};
-    take_clones(sized, nc, ko, kr, kh);
-    const size_t clone_bytes = sized.at, name_bytes = (size_t)nrooms * kRelayNameRow;
-    if (ensure_kept(&r->clone_table, clone_bytes, "clone records")) return -1;
-    if (ensure_kept(&r->relay_names, name_bytes, "room names")) return -1;
+    RelayArgs q{};
+    const Given given[] = {{kKeptNames, names, &q.names}, {kKeptClones, clones, &q.records}};
+    if (check_given(*r, given, "the roster's first relay call must give the clone records and the rooms' names")) return -1;
     const double t0 = now_ns();
     hipStream_t st = g.stream;
     PlanArgs a{};
-    RelayArgs q{};
     SpeakPlanArgs p{};                   // k = 0, tiles = 0: no room lines, a block per relay text
     a.k = q.k = k;
     a.capacity = q.capacity = p.capacity = cap;
@@ -4528,26 +4540,19 @@ static int relay_call(int handle, int k, const uint8_t* text, int64_t text_bytes
     RelayArgs qo = q;
     SpeakPlanArgs po = p;
     const size_t clear_bytes = record && clear ? (size_t)r->review_rooms : 0;
-    const uint8_t *o_clear = nullptr, *d_clear = nullptr, *o_hear = nullptr, *d_hear = nullptr;
-    const int32_t *o_owner = nullptr, *o_room = nullptr, *d_owner = nullptr, *d_room = nullptr;
-    const size_t need = layout_relay(0, (size_t)text_bytes, clear_bytes, o, qo, po, &o_clear, &o_owner, &o_room, &o_hear);
-    const size_t table_bytes = (uintptr_t)qo.names_new, clones_at = (uintptr_t)o_owner, tables_end = (uintptr_t)o.text;
+    const uint8_t *o_clear = nullptr, *d_clear = nullptr;
+    const size_t need = layout_relay(0, (size_t)text_bytes, clear_bytes, o, qo, po, &o_clear);
+    const size_t table_bytes = (uintptr_t)qo.kept[0].fresh, tables_end = (uintptr_t)o.text;
     const size_t in_bytes = (uintptr_t)o.violations + sizeof(int);
     const size_t res_at = (uintptr_t)o.violations, res_bytes = (uintptr_t)po.var + rvar_bytes - res_at;
     if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
     if (table) new_table(*r, o.room, o.slot, table);
     if (grow_roster(*r, need)) return -1;
-    layout_relay((uintptr_t)r->d, (size_t)text_bytes, clear_bytes, a, q, p, &d_clear, &d_owner, &d_room, &d_hear);
+    layout_relay((uintptr_t)r->d, (size_t)text_bytes, clear_bytes, a, q, p, &d_clear);
     if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
 
     uint8_t* h = r->mirror;
     const Put put{h};
-    if (names) put(qo.names_new, names, name_bytes);
-    if (clones) {
-        put(o_owner, clones, (size_t)nc * sizeof(int32_t));
-        put(o_room, clones + (size_t)nc * sizeof(int32_t), (size_t)nc * sizeof(int32_t));
-        put(o_hear, clones + 2 * (size_t)nc * sizeof(int32_t), (size_t)nc);
-    }
     put(o.text, text, (size_t)text_bytes);
     put(o.text_off, text_off, (size_t)k * sizeof(int32_t));
     put(o.text_len, text_len, (size_t)k * sizeof(int32_t));
@@ -4560,26 +4565,18 @@ static int relay_call(int handle, int k, const uint8_t* text, int64_t text_bytes
     for (int b = 0; b < k; b++) roff[b] = text_off[b] + kRelaySlack * b;
     put(o_clear, clear, clear_bytes);
     *reinterpret_cast<int*>(h + (uintptr_t)o.violations) = 0;
-    // as nd_roster_look: what lies after the first table that changed travels too, but the kernel is told of the changed
-    // ones alone, so the mirror's bytes of the others need not be current
-    size_t h2d = 0;
-    if (upload(*r, table_bytes, names ? table_bytes : clones ? clones_at : tables_end, in_bytes, &h2d)) return -1;
-    q.records = clones ? reinterpret_cast<const uint8_t*>(d_owner) : r->clone_table;
-    q.names = names ? reinterpret_cast<const uint8_t*>(q.names_new) : r->relay_names;
-    if (!clones) q.clones_new = nullptr;
-    if (!names) q.names_new = nullptr;
-    q.clones_keep = reinterpret_cast<uint32_t*>(r->clone_table);
-    q.names_keep = reinterpret_cast<uint32_t*>(r->relay_names);
-    q.clone_words = (int)(clone_bytes / 4);
-    q.name_words = (int)(name_bytes / 4);
-    const size_t copy_words = (clones ? clone_bytes / 4 : 0) + (names ? name_bytes / 4 : 0);
+    // the tables' uploads lie between the table and the inputs
+    size_t first = 0, h2d = 0;
+    unsigned copy_blocks = 0;
+    if (pass_kept(*r, given, qo.kept, q.kept, tables_end, &first, &copy_blocks)) return -1;
+    if (upload(*r, table_bytes, first, in_bytes, &h2d)) return -1;
 
     ND_CHECK(hipEventRecord(g.ev0, st));
     hipLaunchKernelGGL(nuts_roster_plan, dim3((unsigned)(k * a.tiles)), dim3(kBlock), 0, st, a);
     ND_CHECK(hipGetLastError());
     if (record && launch_record(*r, k, a.text, a.text_off, a.text_len, a.rm, a.flags, clear_bytes ? d_clear : nullptr))
         return -1;
-    hipLaunchKernelGGL(nuts_roster_relay, dim3((unsigned)(k + (copy_words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, q);
+    hipLaunchKernelGGL(nuts_roster_relay, dim3((unsigned)k + copy_blocks), dim3(kBlock), 0, st, q);
     ND_CHECK(hipGetLastError());
     hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)k), dim3(kBlock), 0, st, p);
     ND_CHECK(hipGetLastError());
@@ -4666,18 +4663,14 @@ int nd_roster_who(int handle, int k, const int32_t* slots, int nl, int32_t now, 
             return -1;
         }
     if (!nrooms) rooms = nullptr;        // a roster without look rooms has no room table: its listed users are violations
-    if ((!r->speech && !speech) || (nrooms && !r->room_table && !rooms) || (!r->udesc && !udesc) || (!r->who && !who)) {
-        snprintf(g_err, sizeof(g_err), "the roster's first who call must give the speaker table, the room table, the descriptions "
-                 "and the who table");
+    WhoArgs s{};
+    const Given given[] = {{kKeptSpeech, speech, &s.speech}, {kKeptRooms, rooms, &s.rooms}, {kKeptUdesc, udesc, &s.udesc},
+                           {kKeptWho, who, &s.who}};
+    if (check_given(*r, given, "the roster's first who call must give the speaker table, the room table, the descriptions "
+                               "and the who table"))
         return -1;
-    }
-    if (ensure_kept(&r->speech, (size_t)cap * kSpeechRec, "speaker table")) return -1;
-    if (nrooms && ensure_kept(&r->room_table, (size_t)nrooms * kRoomRow, "room table")) return -1;
-    if (ensure_kept(&r->udesc, (size_t)cap * kUserDescRow, "user descriptions")) return -1;
-    if (ensure_kept(&r->who, (size_t)cap * kWhoRec, "who table")) return -1;
     const double t0 = now_ns();
     hipStream_t st = g.stream;
-    WhoArgs s{};
     SpeakPlanArgs p{};                  // k = 0, tiles = 0: no room lines, a block per text
     s.k = k;
     s.nl = nl;
@@ -4691,8 +4684,8 @@ int nd_roster_who(int handle, int k, const int32_t* slots, int nl, int32_t now, 
     WhoArgs so = s;                     // offsets of every array in the roster's allocation
     SpeakPlanArgs po = p;
     const size_t need = layout_who(0, so, po);
-    const size_t table_bytes = (uintptr_t)so.speech_new, rooms_at = (uintptr_t)so.rooms_new, udesc_at = (uintptr_t)so.udesc_new;
-    const size_t who_at = (uintptr_t)so.who_new, tables_end = (uintptr_t)so.slot, in_bytes = (uintptr_t)so.violations + sizeof(int);
+    const size_t table_bytes = (uintptr_t)so.kept[0].fresh, tables_end = (uintptr_t)so.slot;
+    const size_t in_bytes = (uintptr_t)so.violations + sizeof(int);
     const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
     if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
     if (table) new_table(*r, so.room, so.slotf, table);
@@ -4702,36 +4695,18 @@ int nd_roster_who(int handle, int k, const int32_t* slots, int nl, int32_t now, 
 
     uint8_t* h = r->mirror;
     const Put put{h};
-    if (speech) put(so.speech_new, speech, (size_t)cap * kSpeechRec);
-    if (rooms) put(so.rooms_new, rooms, (size_t)nrooms * kRoomRow);
-    if (udesc) put(so.udesc_new, udesc, (size_t)cap * kUserDescRow);
-    if (who) put(so.who_new, who, (size_t)cap * kWhoRec);
     put(so.slot, slots, (size_t)k * sizeof(int32_t));
     put(so.date, date, (size_t)date_len);
     *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
-    // the tables' uploads lie between the table and the inputs: what lies after the first one that changed travels too,
-    // but the kernel is told of the changed ones alone, so the mirror's bytes of the others need not be current
-    size_t h2d = 0;
-    if (upload(*r, table_bytes, speech ? table_bytes : rooms ? rooms_at : udesc ? udesc_at : who ? who_at : tables_end, in_bytes, &h2d))
-        return -1;
-    s.speech = speech ? s.speech_new : r->speech;
-    s.rooms = rooms ? s.rooms_new : r->room_table;
-    s.udesc = udesc ? s.udesc_new : r->udesc;
-    s.who = who ? s.who_new : r->who;
-    if (!speech) s.speech_new = nullptr;
-    if (!rooms) s.rooms_new = nullptr;
-    if (!udesc) s.udesc_new = nullptr;
-    if (!who) s.who_new = nullptr;
-    s.speech_keep = r->speech;
-    s.rooms_keep = r->room_table;
-    s.udesc_keep = r->udesc;
-    s.who_keep = r->who;
+    // the tables' uploads lie between the table and the inputs
+    size_t first = 0, h2d = 0;
+    unsigned copy_blocks = 0;
+    if (pass_kept(*r, given, so.kept, s.kept, tables_end, &first, &copy_blocks)) return -1;
+    if (upload(*r, table_bytes, first, in_bytes, &h2d)) return -1;
 
-    const size_t copy_words = (speech ? (size_t)cap * (kSpeechRec / 4) : 0) + (rooms ? (size_t)nrooms * (kRoomRow / 4) : 0) +
-                              (udesc ? (size_t)cap * (kUserDescRow / 4) : 0) + (who ? (size_t)cap * (kWhoRec / 4) : 0);
     const unsigned line_blocks = (unsigned)((cap + kBlock - 1) / kBlock), tiles = nl > kBlock ? (unsigned)((nl + kBlock - 1) / kBlock) : 1u;
     ND_CHECK(hipEventRecord(g.ev0, st));
-    hipLaunchKernelGGL(nuts_roster_who, dim3(line_blocks + 1 + (unsigned)((copy_words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, s);
+    hipLaunchKernelGGL(nuts_roster_who, dim3(line_blocks + 1 + copy_blocks), dim3(kBlock), 0, st, s);
     ND_CHECK(hipGetLastError());
     hipLaunchKernelGGL(nuts_roster_who_shown, dim3((unsigned)k * tiles), dim3(kBlock), 0, st, s);
     ND_CHECK(hipGetLastError());
@@ -4787,15 +4762,11 @@ int nd_roster_rooms(int handle, int k, const int32_t* slots, int kinds, const ui
             snprintf(g_err, sizeof(g_err), "rooms %d: slot out of range", b);
             return -1;
         }
-    if ((!r->speech && !speech) || (!r->room_table && !rooms)) {
-        snprintf(g_err, sizeof(g_err), "the roster's first rooms call must give the speaker table and the room table");
-        return -1;
-    }
-    if (ensure_kept(&r->speech, (size_t)cap * kSpeechRec, "speaker table")) return -1;
-    if (ensure_kept(&r->room_table, (size_t)nrooms * kRoomRow, "room table")) return -1;
+    RoomsArgs s{};
+    const Given given[] = {{kKeptSpeech, speech, &s.speech}, {kKeptRooms, rooms, &s.rooms}};
+    if (check_given(*r, given, "the roster's first rooms call must give the speaker table and the room table")) return -1;
     const double t0 = now_ns();
     hipStream_t st = g.stream;
-    RoomsArgs s{};
     SpeakPlanArgs p{};                  // k = 0, tiles = 0: no room lines, a block per text
     s.k = k;
     s.capacity = p.capacity = cap;
@@ -4806,7 +4777,7 @@ int nd_roster_rooms(int handle, int k, const int32_t* slots, int kinds, const ui
     RoomsArgs so = s;                   // offsets of every array in the roster's allocation
     SpeakPlanArgs po = p;
     const size_t need = layout_rooms(0, so, po);
-    const size_t table_bytes = (uintptr_t)so.speech_new, rooms_at = (uintptr_t)so.rooms_new, tables_end = (uintptr_t)so.slot;
+    const size_t table_bytes = (uintptr_t)so.kept[0].fresh, tables_end = (uintptr_t)so.slot;
     const size_t in_bytes = (uintptr_t)so.violations + sizeof(int);
     const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
     if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
@@ -4817,26 +4788,18 @@ int nd_roster_rooms(int handle, int k, const int32_t* slots, int kinds, const ui
 
     uint8_t* h = r->mirror;
     const Put put{h};
-    if (speech) put(so.speech_new, speech, (size_t)cap * kSpeechRec);
-    if (rooms) put(so.rooms_new, rooms, (size_t)nrooms * kRoomRow);
     put(so.slot, slots, (size_t)k * sizeof(int32_t));
     *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
-    // as nd_roster_who: what lies after the first table that changed travels too, but the kernel is told of the changed
-    // ones alone, so the mirror's bytes of the others need not be current
-    size_t h2d = 0;
-    if (upload(*r, table_bytes, speech ? table_bytes : rooms ? rooms_at : tables_end, in_bytes, &h2d)) return -1;
-    s.speech = speech ? s.speech_new : r->speech;
-    s.rooms = rooms ? s.rooms_new : r->room_table;
-    if (!speech) s.speech_new = nullptr;
-    if (!rooms) s.rooms_new = nullptr;
-    s.speech_keep = r->speech;
-    s.rooms_keep = r->room_table;
+    // the tables' uploads lie between the table and the inputs
+    size_t first = 0, h2d = 0;
+    unsigned copy_blocks = 0;
+    if (pass_kept(*r, given, so.kept, s.kept, tables_end, &first, &copy_blocks)) return -1;
+    if (upload(*r, table_bytes, first, in_bytes, &h2d)) return -1;
 
-    const size_t copy_words = (speech ? (size_t)cap * (kSpeechRec / 4) : 0) + (rooms ? (size_t)nrooms * (kRoomRow / 4) : 0);
     const unsigned count_blocks = (unsigned)((cap + kBlock - 1) / kBlock), line_blocks = (unsigned)((nrooms + kBlock - 1) / kBlock);
     ND_CHECK(hipEventRecord(g.ev0, st));
     ND_CHECK(hipMemsetAsync(s.counters, 0, (size_t)nrooms * sizeof(int32_t), st));
-    hipLaunchKernelGGL(nuts_roster_rooms_count, dim3(count_blocks + (unsigned)((copy_words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, s);
+    hipLaunchKernelGGL(nuts_roster_rooms_count, dim3(count_blocks + copy_blocks), dim3(kBlock), 0, st, s);
     ND_CHECK(hipGetLastError());
     hipLaunchKernelGGL(nuts_roster_rooms_lines, dim3(line_blocks + 1), dim3(kBlock), 0, st, s);
     ND_CHECK(hipGetLastError());

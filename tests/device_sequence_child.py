@@ -73,31 +73,30 @@ MIRRORS = ("_table", "_speech", "_afk", "_rooms", "_udesc", "_clones")
 
 _TABLE = frozenset(TABLE_FIELDS)
 #: What each call kind reads, from the kernels of nuts333_amd/device/fanout.hip and their nd_roster_* entry points (the
-#: lines are those of the kernels' bodies; an entry point hands a kernel the uploaded table or the kept one, never both).
+#: functions named are those kernels' bodies; an entry point hands a kernel the uploaded table or the kept one, never both).
 #: The table is one mirror with one flag, so a kind that reads one of its fields is listed with all five: colour is read
 #: on the host as well, by every kind that returns a Plan's colour_bits or a Look's colour.
 READS = {
-    # nd_roster_fanout -> roster_measure / roster_emit: listener_record(a.room[j], a.slot[j], ...) (fanout.hip:502), the
-    # colour bit of a.slot[j] picks the variant (fanout.hip:591)
+    # nd_roster_fanout -> roster_measure / roster_emit: listener_record(a.room[j], a.slot[j], ...) in roster_measure, the
+    # colour bit of a.slot[j] picks the variant in roster_emit
     "broadcast_many": _TABLE,
-    # plan_call -> roster_plan: listener_record(a.room[j], a.slot[j], ...) (fanout.hip:653)
+    # plan_call -> roster_plan: listener_record(a.room[j], a.slot[j], ...)
     "plan_many": _TABLE,
-    # speech_call -> roster_speak: a.room[slot] (fanout.hip:1126); of the speaker's 16 bytes the name and its length
-    # (1123-1125, 1153), muzzled (1133), command_mode (1134), vis (1153); roster_speak_plan: listener_record (1216).  Neither
-    # reads the level byte nor the afk and igntell bits
+    # speech_call -> roster_speak: a.room[slot]; of the speaker's 16 bytes the name and its length, muzzled, command_mode
+    # and vis; roster_speak_plan: listener_record.  Neither reads the level byte nor the afk and igntell bits
     "speak_many": _TABLE | {"name", "vis", "muzzled", "command_mode"},
-    # ... and roster_parse in front of them: command_mode (fanout.hip:1343) and the level byte (1344)
+    # ... and roster_parse in front of them: command_mode and the level byte
     "input_many": _TABLE | {"name", "vis", "muzzled", "command_mode", "level"},
-    # nd_roster_tell -> roster_tell: the speaker's name, muzzled and vis (fanout.hip:1545-1547, 1572, 1637); get_user over
-    # every slot's login flag and name (1587-1590); both levels (1621); the target's afk (1623), ignall (1624), igntell
-    # (1625), room (1626) and name (1634); its AFK message (1654).  It reads the level, which the issue's table of this
-    # test did not expect and update()'s docstring does not say; it does not read command_mode
+    # nd_roster_tell -> roster_tell: the speaker's name, muzzled and vis; get_user over every slot's login flag and name
+    # (name_match); both levels; the target's afk, ignall, igntell, room and name; its AFK message.  It reads the level,
+    # which the issue's table of this test did not expect and update()'s docstring does not say; it does not read
+    # command_mode
     "tell_many": _TABLE | {"name", "vis", "muzzled", "level", "afk", "igntell", "afk_mesg"},
-    # nd_roster_look -> roster_look: a.room[j] (fanout.hip:1946), the looker's level (1936), every slot's name, vis and level
-    # (1947-1950); look_line: vis (1896), the description (1894), afk (1912); look_room: the whole room record
+    # nd_roster_look -> roster_look: a.room[j], the looker's level, every slot's name, vis and level; look_line: vis, the
+    # description, afk; look_room: the whole room record
     "look_many": _TABLE | {"name", "vis", "level", "afk", "desc"} | {f"rooms.{f}" for f in ROOM_FIELDS},
-    # relay_call -> roster_plan (fanout.hip:653), roster_relay: the records' owner, room and hear (2072-2082), the owner's
-    # ignall (2083), the room's name from the 24-byte rows (2097-2098) and nothing else of the room table
+    # relay_call -> roster_plan, roster_relay: the records' owner, room and hear, the owner's ignall, the room's name from
+    # the 24-byte rows and nothing else of the room table
     "relay_many": _TABLE | {f"clones.{f}" for f in CLONE_FIELDS} | {RELAY_NAMES},
     # review_call: its layout steps over the table (layout_review), the kernel reads the rings alone
     "review_many": frozenset(),

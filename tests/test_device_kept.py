@@ -1,0 +1,127 @@
+"""The tables a roster keeps on the device between calls, through every subset of them that a call can pass.
+
+A roster call passes a kept table -- the speaker state, the AFK messages, the room table, the users' descriptions, the who
+table, the clone records, the relay's room names -- only when it changed.  The call uploads what it passes between the
+roster's table and its own inputs, its kernel reads the uploads, and a tail of extra blocks copies them into the kept
+allocations; a table that is not passed is read from its kept allocation (fanout.hip: ``pass_kept`` on the host,
+``copy_kept`` in the kernels).  The other device modules pass subsets as their fuzzing happens to; this one passes every
+subset of every call kind, 40 in all, on the smallest roster at which the copy tail can go wrong (65 slots, 3 look rooms,
+3 clone records: table boundaries inside a block, more than one block, a partial last block).
+
+Host tier (unmarked): the cases are the 40 of the kinds' tables, and the tables have the sizes the copy tail is told.
+
+GPU tier: everything that touches the device runs in ONE short-lived child for the module
+(tests/device_kept_child.py, under ``timeout``), and the tests assert on its JSON.  No number here is measured: the copy
+volumes are sums of 256-byte aligned slices of arrays whose sizes the module's mirrors give.
+"""
+from __future__ import annotations
+
+import json
+import subprocess
+import sys
+from pathlib import Path
+
+import pytest
+
+from device_kept_child import CAPACITY, TABLES, State, input_arrays, new_roster, passed, request, subsets, table_slices
+
+REPO = Path(__file__).resolve().parent.parent
+KINDS = tuple(TABLES)
+
+
+def slice_of(n: int) -> int:
+    """An array's 256-byte aligned slice of an upload (Carver of fanout.hip)."""
+    return -(-n // 256) * 256
+
+
+# ------------------------------------------------------------------ host tier
+def test_the_cases_are_every_subset_of_every_kind():
+    assert {k: len(subsets(t)) for k, t in TABLES.items()} == {"speak_many": 2, "input_many": 2, "tell_many": 4, "look_many": 8,
+                                                              "who_many": 16, "rooms_many": 4, "relay_many": 4}
+    assert sum(len(subsets(t)) for t in TABLES.values()) == 40
+    assert subsets(("a", "b")) == [(), ("a",), ("b",), ("a", "b")]
+
+
+def test_the_tables_have_the_sizes_the_copy_tail_is_told():
+    roster = new_roster(State("relay_many"))
+    words = {t: sum(slice_of(n) if len(arrays) > 1 else n for n in arrays) // 4 for t, arrays in table_slices(roster).items()}
+    assert words == {"speech": 260, "afk": 1040, "rooms": 804, "udesc": 520, "who": 130, "names": 18, "clones": 192}
+    # the boundaries fall inside a block, the who table and the names are shorter than one, and every tail but theirs ends in a
+    # partial block
+    assert all(w % 256 for w in words.values()) and words["who"] < 256 and words["names"] < 256 and CAPACITY == 65
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_a_change_sets_the_flag_of_its_table_alone(kind):
+    """Without a device: after the flags are cleared as a call clears them, every subset's changes set exactly its flags."""
+    st = State(kind)
+    roster = new_roster(st)
+    for subset in subsets(TABLES[kind]):
+        for f in ("_dirty", "_speech_dirty", "_private_dirty", "_afk_dirty", "_rooms_dirty", "_udesc_dirty", "_who_dirty", "_clones_dirty"):
+            setattr(roster, f, False)
+        if kind == "relay_many":
+            roster._relay_names = roster._prepare_relay(request(kind, st), None, None)[2]
+        for table in subset:
+            st.change(roster, table)
+        assert passed(kind, roster, request(kind, st)) == list(subset) and not roster._dirty
+        assert all(n >= 0 for n in input_arrays(kind, request(kind, st), st))
+
+
+# ------------------------------------------------------------------ GPU tier
+@pytest.fixture(scope="module")
+def kept_run(built):
+    cmd = ["timeout", "-k", "10", "120", sys.executable, str(REPO / "tests" / "device_kept_child.py")]
+    try:
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=180, cwd=str(REPO))
+    except subprocess.TimeoutExpired:
+        pytest.fail("device child did not finish in 180 s")
+    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_KEPT ")]
+    if p.returncode != 0 or not lines:
+        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
+    res = json.loads(lines[-1][len("DEVICE_KEPT "):])
+    print("\n[kept]", json.dumps(res)[:4000])
+    return res
+
+
+def cases_of(run, kind):
+    cases = [c for c in run["cases"] if c["kind"] == kind]
+    assert [tuple(c["subset"]) for c in cases] == subsets(TABLES[kind])
+    return cases
+
+
+@pytest.mark.gpu
+def test_every_subset_of_every_kind_ran(kept_run):
+    assert len(kept_run["cases"]) == 40 and kept_run["order"] == {k: list(v) for k, v in TABLES.items()}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", KINDS)
+def test_exactly_the_changed_tables_are_passed(kept_run, kind):
+    for c in cases_of(kept_run, kind):
+        assert c["flags"] == c["subset"] and not c["table_dirty"] and c["flags_after"] == [], c
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", KINDS)
+def test_the_uploads_and_the_kept_tables_read_alike(kept_run, kind):
+    """Call 1 read the uploads, call 2 the kept allocations its copy tail filled: the same bytes in every output array, and
+    through the accessors what a fresh roster in the final state returns, and what the CPU models say."""
+    for c in cases_of(kept_run, kind):
+        assert c["arrays"] >= 5 and c["arrays_differ"] == [], c
+        assert c["again_says_the_same"] and c["fresh_says_the_same"], c
+        assert c["model_differences"] == [[], []], c
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", KINDS)
+def test_the_first_passed_table_and_all_behind_it_travel(kept_run, kind):
+    """upload() copies from the first passed table to the end of the inputs: the clean figure is the inputs' slices and the
+    violation count, and call 1 adds the slices from the first passed table through the last table of the layout.  The
+    roster's table is resident: no slice of it in either."""
+    order = list(TABLES[kind])
+    for c in cases_of(kept_run, kind):
+        clean = sum(slice_of(n) for n in c["inputs"]) + 4
+        behind = order[min(order.index(t) for t in c["subset"]):] if c["subset"] else []
+        assert c["h2d"][1] == clean, c
+        assert c["h2d"][0] - clean == sum(slice_of(n) for t in behind for n in c["tables"][t]), c
+        assert c["d2h"][0] == c["d2h"][1], c
