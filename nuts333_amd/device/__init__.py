@@ -62,6 +62,15 @@ is sent.
 nuts333.c:5661-5700) as a :class:`Rooms`: the header of each kind, the tail and a line of each kind per named look room,
 with the users standing in every room counted over the whole roster on the device.  ``Roster.set_rooms(inlink=, netlink=)``
 keeps the three netlink facts ``.rmsn`` prints in the room record's flag byte.
+``Roster.update(in_phrase=, out_phrase=, invite_room=)`` keeps what ``.go`` reads of a mover beside those, and
+``Roster.go_many(events, gatecrash_level=, min_private_users=)`` answers K ``(slot, inpstr, word_count)`` ``.go`` events as
+``go()``, ``move_user()`` and ``reset_access()`` do (nuts333.c:4305-4459, 2087-2106) -- a :class:`Go`.  The device decides and
+composes: ``get_room``, the adjoined, private and gatecrash checks, the enter, leave and reset lines and the notices, with
+their plans.  An event that an earlier move of the same call touched -- its slot, its room or its target -- is deferred and
+comes back unanswered, so every answered event is exact against the roster as it was before the call.  The binding applies
+the moves to the host mirrors, and the look a move ends with is one ``look_many`` over the movers: at most two device visits.
+Left to the caller: the netlink branch (GO_NETLINK), ``.move``, ``.private`` / ``.public`` / ``.invite`` themselves, the relay
+of the three room texts to clones' owners, and the prompt.
 
 Input is validated before the device is touched (``ValueError``).  The library ``_build/libnuts_device.so`` is built by
 ``__graft_entry__.build()`` where ``hipcc`` exists, and on demand here when it is missing or older than its source.
@@ -242,6 +251,27 @@ MAX_RMST_LINE_BYTES, MAX_RMSN_LINE_BYTES, MAX_ROOMS_LINE_WRITES = 6 * MAX_RMST_L
 #: a rooms call's texts (rooms_fixed_at of fanout.hip): the two headers in 80 and 96 bytes, the tail in 4; then the
 #: ``.rmst`` lines, then the ``.rmsn`` lines
 _ROOMS_FIXED_AT, _ROOMS_FIXED_STRIDE = (0, 80, 176), 180
+#: ``.go`` (NP_GO), and the kernels go_many runs before nuts_roster_speak_plan
+COM_GO = 10
+GO_KERNELS = ("nuts_roster_go", "nuts_roster_go_order")
+#: what became of a ``.go`` event (Go.outcome).  The first three moved: by a link, by a WIZ's teleport, invisibly.  Then the
+#: notices to the mover alone -- "Go where?", no such room, already there, not adjoined, private -- with GO_NETLINK among
+#: them, the netlink branch that the caller answers, and GO_DEFERRED, an event the caller submits again
+(GO_WALKED, GO_TELEPORTED, GO_UNSEEN, GO_WHERE, GO_NETLINK, GO_NO_ROOM, GO_ALREADY, GO_NOT_ADJOINED, GO_PRIVATE,
+ GO_DEFERRED) = range(10)
+#: PHRASE_LEN (nuts333.h:26), and a slot's row of the go mirror (kGoRec of fanout.hip): in_phrase padded with zeros and its
+#: length at byte 40, out_phrase and its length at bytes 41 .. 81, two zeros, int32 invite_room (-1: none) at byte 84
+PHRASE_LEN, _GO_REC, _GO_OUT, _GO_INVITE = 40, 88, 41, 84
+#: the longest texts of a move before the transducer (kGoEnterMax .. kGoReplyMax of fanout.hip, pinned by a host test): the
+#: teleport's enter line, ``~FT~OL`` + a 12-byte name + 40 bytes; the leave line, a name, a blank, a 40-byte out_phrase,
+#: `` to the ``, a 20-byte room name and ``.\n``; the reset line; the not-adjoined notice over a 20-byte room name
+MAX_GO_ENTER, MAX_GO_LEAVE, MAX_GO_RESET, MAX_GO_REPLY = (6 + USER_NAME_LEN + 40, USER_NAME_LEN + 1 + PHRASE_LEN + 8 + ROOM_NAME_LEN + 2,
+                                                          35, 4 + ROOM_NAME_LEN + 26)
+#: their slots among a go call's texts (kGoEnterRow .. kGoReplyRow): with K events the enter lines, then the leave lines,
+#: the reset lines and the replies, event k's at ``K x (the rows before) + row x k`` (go_text_at)
+_GO_ROWS = (60, 84, 36, 52)
+#: the texts of an event in a Go, in that order
+GO_ENTER, GO_LEAVE, GO_RESET, GO_REPLY = range(4)
 #: a look room's row of the names relay_many uploads (kRelayNameRow of fanout.hip): 20 bytes of name padded with zeros, then
 #: its length; and what a relay text is longer than its broadcast at most, ``~FT[ `` + a 20-byte name + `` ]:~RS ``
 #: (kRelaySlack): its slot among a relay call's relay texts is that much wider than the text
@@ -766,6 +796,61 @@ class Relay:
 
 
 @dataclass
+class Go:
+    """What ``go()`` and ``move_user()`` write for K ``.go`` events (``Roster.go_many``), shaped like a :class:`Speech`.
+    ``outcome[k]`` is GO_WALKED, GO_TELEPORTED or GO_UNSEEN for an event that moved, else GO_WHERE, GO_NETLINK, GO_NO_ROOM,
+    GO_ALREADY, GO_NOT_ADJOINED, GO_PRIVATE or GO_DEFERRED; ``target[k]`` the room the word resolved to, or -1 when there is
+    none or ``get_room`` was not reached; ``old_room[k]`` the mover's room before the call; ``returned_public[k]`` whether
+    the move made the old room public again.  ``enter`` plans the line the target room gets, ``leave`` the line the old
+    room gets without the mover, ``reset`` the line the old room gets when it returns to public, ``reply`` the notice the
+    mover alone gets when it did not move.  They are ordinary plans over the roster as it was before the call and share
+    one variant buffer; a text that is not there has size -1, nobody admitted and both variants 0 bytes in 0 writes.  A
+    GO_NETLINK and a GO_DEFERRED event have no text at all, and a deferred event's ``target`` and ``old_room`` are what the
+    roster before the call gives.  ``look`` is the :class:`Look` of the movers after the moves,
+    in event order, or None when nobody moved, and ``look_index[k]`` event k's looker in it, or -1.
+
+    Delivery, per client: the events in call order, and of one event the enter line, the leave line, the mover's look,
+    the reset line (``reply`` instead of all four for an event that did not move).  A roster with clone records passes
+    the three room texts through ``relay_many``."""
+    outcome: np.ndarray           # int8 [K]
+    target: np.ndarray            # int32 [K]
+    old_room: np.ndarray          # int32 [K]
+    returned_public: np.ndarray   # bool [K]
+    enter: Plan
+    leave: Plan
+    reset: Plan
+    reply: Plan
+    texts: np.ndarray             # uint8, flat: the composed texts; gaps are allowed and unspecified
+    text_starts: np.ndarray       # int64 [4, K]   rows GO_ENTER, GO_LEAVE, GO_RESET, GO_REPLY
+    text_sizes: np.ndarray        # int64 [4, K]   -1: there is no such text
+    look: Look | None = None
+    look_index: np.ndarray | None = None         # int32 [K]
+    timing: dict = field(default_factory=dict)   # the first device visit's, as Plan's; the second's is look.timing
+
+    _text = Speech._text
+
+    def enter_text(self, k: int) -> bytes:
+        """The line event ``k`` sends to the room it enters; ``b""`` when it did not move."""
+        return self._text(GO_ENTER, k)
+
+    def leave_text(self, k: int) -> bytes:
+        """The line event ``k`` sends to the room it leaves; ``b""`` when it did not move."""
+        return self._text(GO_LEAVE, k)
+
+    def reset_text(self, k: int) -> bytes:
+        """The line the room event ``k`` left gets when it returns to public; ``b""`` when it does not."""
+        return self._text(GO_RESET, k)
+
+    def reply_text(self, k: int) -> bytes:
+        """The notice event ``k`` sends to its mover alone; ``b""`` when there is none."""
+        return self._text(GO_REPLY, k)
+
+    def moved(self) -> np.ndarray:
+        """The events that moved, ascending."""
+        return np.flatnonzero((self.outcome >= 0) & (self.outcome <= GO_UNSEEN))
+
+
+@dataclass
 class Input:
     """What ``user_input()`` and ``exec_com()`` make of K reads (``Roster.input_many``).  ``kind[k]`` is IAC, EMPTY,
     REPEAT, UNKNOWN, SPEECH or COMMAND; ``com[k]`` the command (enum np_com) of a SPEECH or COMMAND read, else -1;
@@ -996,6 +1081,9 @@ def _load():
         lib.nd_roster_who.restype = ctypes.c_int
         lib.nd_roster_rooms.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int] + [P] * 10 + [ctypes.POINTER(_RosterTiming)]
         lib.nd_roster_rooms.restype = ctypes.c_int
+        lib.nd_roster_go.argtypes = ([ctypes.c_int, ctypes.c_int, P, ctypes.c_int64, P, P, P, P, ctypes.c_int, ctypes.c_int] + [P] * 16
+                                     + [ctypes.POINTER(_RosterTiming)])
+        lib.nd_roster_go.restype = ctypes.c_int
         lib.nd_roster_clones.argtypes = [ctypes.c_int, ctypes.c_int]
         lib.nd_roster_clones.restype = ctypes.c_int
         lib.nd_roster_relay.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int64] + [P] * 22 + [ctypes.POINTER(_RosterTiming)]
@@ -1258,6 +1346,14 @@ class Roster:
         self._clone_room[:] = -1
         self._clones_dirty = True
         self._relay_names = None
+        # what go_many alone reads and uploads: 88 bytes per slot -- in_phrase and its length, out_phrase and its length, int32
+        # invite_room (-1: none) -- after update(in_phrase=, out_phrase=, invite_room=)
+        self._go = np.zeros((self.capacity, _GO_REC), dtype=np.uint8)
+        self._go_invite = self._go[:, _GO_INVITE:_GO_INVITE + 4].view(np.int32).reshape(self.capacity)
+        self._go[:, :6], self._go[:, PHRASE_LEN] = np.frombuffer(b"enters", dtype=np.uint8), 6
+        self._go[:, _GO_OUT:_GO_OUT + 4], self._go[:, _GO_OUT + PHRASE_LEN] = np.frombuffer(b"goes", dtype=np.uint8), 4
+        self._go_invite[:] = -1
+        self._go_dirty = True
         self._handle = None
         self._closed = False
 
@@ -1289,7 +1385,8 @@ class Roster:
 
     def update(self, slots, *, room=_KEEP, login=_KEEP, ignall=_KEEP, ignshout=_KEEP, colour=_KEEP, name=_KEEP,
                vis=_KEEP, muzzled=_KEEP, command_mode=_KEEP, level=_KEEP, afk=_KEEP, igntell=_KEEP,
-               afk_mesg=_KEEP, desc=_KEEP, last_login=_KEEP, away=_KEEP) -> None:
+               afk_mesg=_KEEP, desc=_KEEP, last_login=_KEEP, away=_KEEP, in_phrase=_KEEP, out_phrase=_KEEP,
+               invite_room=_KEEP) -> None:
         """Set fields of ``slots`` (a slot or a sequence of them).  Each field given is one value for every slot or a
         sequence of one per slot; a field not given stays as it is.  ``room`` is None (no room) or an int in
         [0, ROOM_LIMIT); the flags are 0/1 or bools.  A slot given more than once takes its last values.  Nothing
@@ -1314,7 +1411,12 @@ class Roster:
         ``last_login`` (an int in [0, 2^31), 0 at first) is ``user->last_login``, and ``away`` (None at first, or a look
         room whose record has a netlink) the link a user without a room left through, whose service ``who()`` shows in
         place of a room.  They live in a mirror of their own, 8 bytes per slot, that only ``who_many`` uploads: an update
-        of these two alone marks no other mirror."""
+        of these two alone marks no other mirror.
+
+        ``in_phrase`` and ``out_phrase`` (bytes or str of 0 .. PHRASE_LEN bytes, no NUL; ``enters`` and ``goes`` at first, as
+        a new user's are, nuts333.c:1575-1576) are what a walking user's room lines say, and ``invite_room`` (None at first,
+        or a look room) the private room a user may enter by invitation.  They live in a mirror of their own, 88 bytes per
+        slot, that only :meth:`go_many` uploads: an update of these three alone marks no other mirror."""
         self._check_open()
         if isinstance(slots, (int, np.integer)):
             slots = [slots]
@@ -1379,6 +1481,16 @@ class Roster:
                 raise ValueError(f"away: room {v} has no netlink")
             return v
 
+        def invited(v):
+            if v is None:
+                return -1
+            if isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"invite_room must be None or a look room, not {v!r}")
+            return self._look_room(v)
+
+        phrases = {f: _one_or_each(f, v, n, lambda x, f=f: _limited_text(f, x, PHRASE_LEN), _is_text)
+                   for f, v in (("in_phrase", in_phrase), ("out_phrase", out_phrase)) if v is not _KEEP}
+        invites = None if invite_room is _KEEP else per_slot("invite_room", invite_room, invited, np.int32)
         logins = None if last_login is _KEEP else per_slot("last_login", last_login, login_time, np.int32)
         aways = None if away is _KEEP else per_slot("away", away, away_room, np.int32)
         _, last = np.unique(idx[::-1], return_index=True)        # each slot's last position: last write wins
@@ -1417,12 +1529,23 @@ class Roster:
             self._who[at, 1] = aways[keep]
         if logins is not None or aways is not None:
             self._who_dirty = True
+        for f, v in phrases.items():
+            first = 0 if f == "in_phrase" else _GO_OUT
+            for j, p in zip(at.tolist(), keep.tolist()):
+                self._go[j, first:first + PHRASE_LEN + 1] = 0
+                self._go[j, first:first + len(v[p])] = np.frombuffer(v[p], dtype=np.uint8)
+                self._go[j, first + PHRASE_LEN] = len(v[p])
+        if invites is not None:
+            self._go_invite[at] = invites[keep]
+        if phrases or invites is not None:
+            self._go_dirty = True
         if names is not None or levels is not None or speech.keys() - {"afk", "igntell"}:
             self._speech_dirty = True
         if speech.keys() & {"afk", "igntell"}:
             self._private_dirty = True
         if rooms is not None or flags or not (names is not None or speech or levels is not None or mesgs is not None
-                                              or descs is not None or logins is not None or aways is not None):
+                                              or descs is not None or logins is not None or aways is not None
+                                              or phrases or invites is not None):
             self._dirty = True
 
     def table(self, rm, sender) -> np.ndarray:
@@ -2080,7 +2203,7 @@ class Roster:
         synchronise, whatever K and the capacity.  The bound counts a line per slot of the call's distinct rooms and a
         member per such slot and looker; a call whose variant bound exceeds MANY_ARENA_CAP is refused.
 
-        Out of scope: clones and remote users in the list, and ``.go``.  ``.who`` is :meth:`who_many`."""
+        Out of scope: clones and remote users in the list.  ``.who`` is :meth:`who_many`, ``.go`` :meth:`go_many`."""
         self._check_open()
         if isinstance(slots, (str, bytes, bytearray)) or not hasattr(slots, "__len__"):
             raise ValueError(f"slots must be a sequence of slots, not {slots!r}")
@@ -2328,6 +2451,180 @@ class Roster:
                      topics=kind_arr, counts=counts, texts=ctext, text_starts=tstarts, text_sizes=clen.astype(np.int64),
                      variants=var, variant_starts=_variant_starts(tstarts, clen), variant_sizes=vn, write_counts=vw,
                      write_sizes=vwsz, timing=_timing_of(t))
+
+    def _prepare_go(self, events, gatecrash_level, min_private_users):
+        """Each (slot, inpstr, word_count) and its mover's state checked, packed for nd_roster_go: the inpstr, their offsets
+        and lengths, the slots and the word counts."""
+        if isinstance(events, (str, bytes, bytearray, np.ndarray)) or not hasattr(events, "__len__"):
+            raise ValueError(f"events must be a sequence of tuples, not {type(events).__name__}")
+        if len(events) == 0:
+            raise ValueError("empty call: no events")
+        if not _is_int(gatecrash_level, 0, MAX_LEVEL):
+            raise ValueError(f"gatecrash_level must be an int in [0, {MAX_LEVEL}] (enum np_level), not {gatecrash_level!r}")
+        if not _is_int(min_private_users, 0, 2**31 - 1):
+            raise ValueError(f"min_private_users must be an int in [0, 2^31), not {min_private_users!r}")
+        if self.look_rooms < 1:
+            raise ValueError("the roster has no room records (look_rooms is 0): there is no room to go to")
+        if len(events) * self.capacity >= 2**31 - 1:
+            raise ValueError(f"{len(events)} events to {self.capacity} slots: K x capacity must be below 2^31 - 1")
+        bound = _variant_at(sum(_GO_ROWS) * len(events), 4 * len(events))
+        if bound > MANY_ARENA_CAP:
+            raise ValueError(f"call too large: its variant bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
+                             f"(MANY_ARENA_CAP): split it")
+        texts, slots, wcs = [], [], []
+        for k, ev in enumerate(events):
+            if not isinstance(ev, tuple) or len(ev) != 3:
+                raise ValueError(f"event {k}: expected a (slot, inpstr, word_count) tuple, "
+                                 f"got {type(ev).__name__}{f' of {len(ev)}' if isinstance(ev, tuple) else ''}")
+            slot, inpstr, wc = ev
+            try:
+                slot = self._slot(slot)
+                text = _as_text(inpstr)
+                if len(text) >= ARR_SIZE:
+                    raise ValueError(f"inpstr of {len(text)} bytes: the talker's input line holds at most {ARR_SIZE - 1}")
+                if not _is_int(wc, 0, MAX_WORDS):
+                    raise ValueError(f"word_count must be an int in [0, {MAX_WORDS}], not {wc!r}")
+                if not 0 <= self._room[slot] < self.look_rooms:
+                    raise ValueError(f"the mover, slot {slot}, is in " + (f"room {int(self._room[slot])}, which has no room record"
+                                     if self._room[slot] >= 0 else "no room") + f" (look_rooms is {self.look_rooms})")
+                if self._flags[slot] & ROSTER_FLAGS["login"]:
+                    raise ValueError(f"the mover, slot {slot}, is still logging in")
+                if self._speech[slot, USER_NAME_LEN] == 0:
+                    raise ValueError(f"the mover, slot {slot}, has no name")
+            except ValueError as e:
+                raise ValueError(f"event {k}: {e}") from None
+            texts.append(text)
+            slots.append(slot)
+            wcs.append(int(wc))
+        lens = np.fromiter((len(t) for t in texts), dtype=np.int64, count=len(texts))
+        if int(lens.sum()) >= 2**31 // 32:
+            raise ValueError("call text larger than 64 MiB: split it")
+        return (b"".join(texts), _offsets(lens, np.int32), lens.astype(np.int32), np.array(slots, dtype=np.int32),
+                np.array(wcs, dtype=np.uint8))
+
+    def go_many(self, events, *, gatecrash_level, min_private_users) -> Go:
+        """K ``.go`` events, decided and composed on the device: a non-empty sequence of ``(slot, inpstr, word_count)``
+        tuples, what a COMMAND read of :meth:`input_many` with ``com == COM_GO`` hands back -- ``"lounge"`` for ``.go
+        lounge`` (nuts333.c:4305-4459).  ``gatecrash_level`` is an int in [0, MAX_LEVEL] and ``min_private_users`` an int >=
+        0, the talker's two settings.  The roster needs ``look_rooms >= 1``; every mover needs a room in ``[0, look_rooms)``,
+        a name and no ``login`` flag; a slot may appear more than once.  Anything else raises ``ValueError("event k: ...")``
+        before the device is touched, and a call whose variant bound exceeds MANY_ARENA_CAP is refused.
+
+        The device does, per event and in the reference's order: ``word[1]`` is the first word of ``inpstr`` as
+        ``np_wordfind`` finds it, as :meth:`tell_many` takes its own, not capitalised.  GO_WHERE if ``word_count < 2``;
+        GO_NETLINK if the mover's room has a netlink, whatever its state, whose service begins with the word -- nothing is
+        composed, the caller does what ``go()`` does over the link; ``get_room`` is the lowest look room with a name that
+        begins with the word (a room without a name is no room), else GO_NO_ROOM; GO_ALREADY; GO_NOT_ADJOINED if the room is
+        not among the links of the mover's and its level is below WIZ; GO_PRIVATE if ``access & PRIVATE``, the level is
+        below ``gatecrash_level``, ``invite_room`` is another room and the room is not a fixed one entered by a WIZ; else
+        the move: GO_UNSEEN for an invisible mover, GO_WALKED by a link, GO_TELEPORTED without one.  A move composes the
+        enter line for the target room and the leave line for the old room without the mover -- ``invisenter`` and
+        ``invisleave``, the two lines of blue magic, or ``"<name> <in_phrase>.\\n"`` and ``"<name> <out_phrase> to the
+        <room>.\\n"``.  When the old room's access is exactly PRIVATE and fewer than ``min_private_users`` stay behind --
+        the slots with that room, a name and no ``login`` flag, and the clone records standing there -- it returns to
+        public: ``"Room access returned to ~FGPUBLIC.\\n"`` to the old room.
+
+        Every event is decided and planned against the roster as it was before the call.  To keep that exact, an event
+        whose slot, current room or resolved target room was touched by an earlier event of the call that moved is
+        GO_DEFERRED: it wrote nothing and changed nothing, and the caller submits it again in its next call.  A move
+        touches its slot, the room left and the room entered; nothing else touches anything.  The events that remain are
+        pairwise disjoint in slots and rooms, so each one decided against the snapshot is what running them one after
+        another gives.  A call of one event never defers.
+
+        The binding then applies the result to the host mirrors, through :meth:`update`, :meth:`set_rooms` and
+        :meth:`clear_review`, in ``move_user``'s order: the movers' rooms, their invites into their targets cleared; if
+        anyone moved, one :meth:`look_many` over the movers in event order; then every room that returned to public made
+        PUBLIC, with every slot's invite into it cleared and its review ring emptied when it has one.  ``move_user`` looks
+        before ``reset_access`` runs (nuts333.c:4457-4458), so a mover's look shows the room it left as it was, and the
+        rooms that earlier events returned to public as public.  The one look shows no room of the call as returned, so
+        the binding defers one more kind of event: a move whose new room adjoins a room that an earlier event of the
+        same call returned to public.  No kernel writes a kept table.  Returns a :class:`Go`.
+
+        A call therefore visits the device at most twice.  The first visit is one upload (the table, the speaker state, the
+        clone records, the room table and the go mirror only after an update of theirs), three kernel launches (GO_KERNELS,
+        then nuts_roster_speak_plan), one download at the bound size and one synchronise, whatever K and the capacity; the
+        second is ``look_many``'s.  After a move the table is stale on the device: the next call of any kind that reads it,
+        the look included, uploads its ``5 x capacity`` bytes; a room that returned to public costs the room table and
+        the go mirror as well.
+
+        Out of scope: ``.move`` (teleport 2); the netlink branch and the ``remote_com == GO`` release, which the caller does
+        before it submits; remote users; ``.private``, ``.public``, ``.invite`` and ``.letmein`` themselves -- the caller sets
+        ``set_rooms(access=)`` and ``update(invite_room=)``; the prompt; fusing the look into the first device visit;
+        applying the moves by a kernel.  ``go_many`` does not relay to clones' owners."""
+        self._check_open()
+        text, text_off, lens, slots, wcs = self._prepare_go(events, gatecrash_level, min_private_users)
+        lib = _load()
+        handle = self._device_handle(lib)
+        k, words = len(lens), (self.capacity + 63) // 64
+        ctext_bytes = sum(_GO_ROWS) * k
+        outcome, target, old = np.empty(k, dtype=np.int8), np.empty(k, dtype=np.int32), np.empty(k, dtype=np.int32)
+        returned = np.empty(k, dtype=np.uint8)
+        clen = np.empty((4, k), dtype=np.int32)
+        bits = np.zeros((4, k, words), dtype=np.uint64)            # the device's three, then the mover alone
+        vn, vw = np.empty((4, k, 2), dtype=np.int64), np.empty((4, k, 2), dtype=np.int32)
+        vwsz = np.empty((4, k, 2, MAX_WRITES), dtype=np.int32)
+        ctext = np.empty(ctext_bytes, dtype=np.uint8)
+        var = np.empty(_variant_at(ctext_bytes, 4 * k), dtype=np.uint8)
+        tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
+        t = _RosterTiming()
+        rc = lib.nd_roster_go(handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(slots), _ptr(wcs),
+                              int(gatecrash_level), int(min_private_users), _ptr(self._table) if self._dirty else None,
+                              _ptr(self._speech) if self._speech_dirty else None,
+                              _ptr(self._clones) if self._clones_dirty and self.clones else None,
+                              _ptr(self._rooms) if self._rooms_dirty else None, _ptr(self._go) if self._go_dirty else None,
+                              _ptr(outcome), _ptr(target), _ptr(old), _ptr(returned), _ptr(clen), _ptr(bits), _ptr(vn),
+                              _ptr(vw), _ptr(vwsz), _ptr(ctext), _ptr(var), ctypes.byref(t))
+        _check(rc, "device go failed")
+        self._private_dirty &= not self._speech_dirty         # the whole speaker mirror went up, or none of it
+        self._dirty = self._speech_dirty = self._rooms_dirty = self._go_dirty = False
+        if self.clones:
+            self._clones_dirty = False
+        rows = np.array(_GO_ROWS, dtype=np.int64)
+        tstarts = ((np.cumsum(rows) - rows) * k)[:, None] + rows[:, None] * np.arange(k, dtype=np.int64)
+        starts = _variant_starts(tstarts, clen)
+        has = np.flatnonzero(clen[GO_REPLY] >= 0)
+        bits[GO_REPLY, has, slots[has] // 64] = np.uint64(1) << (slots[has] % 64).astype(np.uint64)
+        timing = _timing_of(t)
+        colour_bits = _pack((self._flags & ROSTER_FLAGS["colour"]) != 0)
+        plans = [Plan(capacity=self.capacity, admitted_bits=bits[i], colour_bits=colour_bits, variants=var,
+                      variant_starts=starts[i], variant_sizes=vn[i], write_counts=vw[i], write_sizes=vwsz[i],
+                      timing=dict(timing)) for i in range(4)]
+        go = Go(outcome=outcome, target=target, old_room=old, returned_public=returned.astype(bool), enter=plans[GO_ENTER],
+                leave=plans[GO_LEAVE], reset=plans[GO_RESET], reply=plans[GO_REPLY], texts=ctext, text_starts=tstarts,
+                text_sizes=clen.astype(np.int64), look_index=np.full(k, -1, dtype=np.int32), timing=timing)
+        # move_user looks before reset_access runs (c:4457-4458): a look shows the rooms that earlier events returned to
+        # public as public and the mover's own old room as it was.  One look_many before the resets shows none of them
+        # public, so a mover whose new room adjoins a room that an earlier event of the call returned is deferred here
+        public = set()
+        for k in go.moved().tolist():
+            rec = self._room_rec[target[k]]
+            if public & set(rec[32:32 + 4 * int(rec[22])].view("<i4").tolist()):
+                outcome[k], go.returned_public[k] = GO_DEFERRED, False
+                go.text_sizes[:, k] = -1
+                for plan in plans:
+                    plan.admitted_bits[k], plan.variant_sizes[k], plan.write_counts[k] = 0, 0, 0
+            elif go.returned_public[k]:
+                public.add(int(old[k]))
+        # the moves, on the host mirrors: the next call of any kind uploads what it reads
+        moved = go.moved()
+        if len(moved):
+            movers, into = slots[moved], target[moved]
+            self.update(movers, room=into)
+            invited = movers[self._go_invite[movers] == into]
+            if len(invited):
+                self.update(invited, invite_room=None)
+            go.look = self.look_many(movers)
+            go.look_index[moved] = np.arange(len(moved), dtype=np.int32)
+        if public:
+            public = np.array(sorted(public), dtype=np.int32)
+            self.set_rooms(public, access=PUBLIC)
+            invited = np.flatnonzero(np.isin(self._go_invite, public))
+            if len(invited):
+                self.update(invited, invite_room=None)
+            rings = public[public < self.review_rooms]
+            if len(rings):
+                self.clear_review(rings)
+        return go
 
     def set_clones(self, clones, *, owner=_KEEP, room=_KEEP, hear=_KEEP) -> None:
         """Set fields of the clone records ``clones`` (a record or a sequence of them, each in ``[0, clones)``), by the

@@ -2616,6 +2616,331 @@ static_assert(kRmstLineMax == 121 && kRmsnLineMax == 162 && kRmstLineMax <= kRms
               kRmstRow % 4 == 0 && kRmsnRow % 4 == 0 && kRoomsFixedStride % 4 == 0, "roster_rooms: the longest lines fit their slots");
 static_assert(kRmsnRow < kTextSize && kMaxLookRooms * sizeof(int) <= 4096, "roster_rooms: a line fits speak_plan's LDS text; a 4 KB histogram");
 
+// ------------------------------------------------------------------ go() of a resident roster
+//
+// go() and move_user() (nuts333.c:4305-4459) with get_room (c:2383-2391), has_room_access (c:2412-2421) and what
+// reset_access (c:2087-2106) decides.  The device decides and composes; it writes no kept table.  The host binding applies
+// the moves to its mirrors afterwards, and the look a move ends with is a nuts_roster_look call of its own.
+// A fourth per-slot table kept like the speaker state holds what only this call reads of a user, 88 bytes per slot:
+//   go row        0 in_phrase[40] | 40 its length | 41 out_phrase[40] | 81 its length | 82 zeros | 84 int32 invite_room (-1: none)
+// An event has four texts, each in a slot of fixed width (their longest forms are pinned by a host test): the enter line the
+// target room gets, the leave line the old room gets, the reset line the old room gets when it returns to public, and the
+// notice the mover alone gets when it did not move.  With K events, text k is event k's enter line, K + k its leave line,
+// 2K + k its reset line and 3K + k its reply.
+//   go       nuts_roster_go, ONE BLOCK PER EVENT, in the shape of nuts_roster_tell.  word[1] is found as there, by every wave
+//            for itself.  The netlink test (c:4315-4316) is a prefix compare of the word with the room's service, a byte per
+//            lane.  get_room: lane l of wave w tests room 256 i + 64 w + l in step i -- a name, at least as long as the
+//            word, that begins with it --, a ballot per step, the first hit is the wave's lowest, and the four waves'
+//            minima meet in LDS.  The decision chain follows, block-uniform.  For a mover that leaves a room whose access is
+//            exactly PRIVATE the block counts who stays behind: a lane per slot (that room, a name, no login flag, not the
+//            mover) and a lane per clone record standing there, ballots summed per wave and the four sums through LDS.
+//            No atomics: the same answer on every run.  Wave 0 composes the texts with compose() and lane 0 stores the
+//            lengths, the outcome, the target, the old room, whether the old room returns to public, and rm / sender /
+//            com of the three room texts as nuts_roster_speak_plan takes them: the enter line to the target without a
+//            sender, the leave and the reset line to the old room with the mover as sender.  Every event is decided
+//            against the tables as they were before the call.
+//            Blocks past the events copy freshly uploaded tables into the kept allocations.
+//   order    nuts_roster_go_order, ONE WAVE, makes that exact.  It walks the events in call order with two bitmaps in LDS,
+//            a bit per look room and a bit per slot, "touched by an earlier event of this call that moved".  An event
+//            whose slot, current room or resolved target room is touched is deferred: its outcome becomes kGoDeferred, its
+//            four texts void, and it touches nothing.  An event that moved and was not deferred touches its slot, the room
+//            it left and the room it entered.  The events that remain are pairwise disjoint in slots and rooms, so each
+//            one decided and planned against the snapshot is what running them one after another gives.  The wave loads
+//            64 events at a time, a lane each, and steps through them by shuffles; lane 0 sets the bits.
+//   plan     nuts_roster_speak_plan with 3K room lines and K replies, over the table as it was before the call.
+constexpr int kGoRec = 88, kPhraseLen = 40;                // a slot's row of the go table; nuts333.h:26 PHRASE_LEN
+constexpr int kGoIn = 0, kGoInLen = 40, kGoOut = 41, kGoOutLen = 81, kGoInvite = 84;
+constexpr int kComGo = 10;                                 // enum np_com: NP_GO
+constexpr int kGoWalked = 0, kGoTeleported = 1, kGoUnseen = 2, kGoWhere = 3, kGoNetlink = 4, kGoNoRoom = 5, kGoAlready = 6,
+              kGoNotAdjoined = 7, kGoPrivate = 8, kGoDeferred = 9;      // an event moved iff its outcome is at most kGoUnseen
+constexpr uint8_t kAccessPrivate = 1, kAccessFixed = 2;    // nuts333.h: PRIVATE, FIXED
+constexpr int kGoTexts = 4;                                // enter, leave, reset, reply
+constexpr int kGoMaxSlots = 65536;                         // the most slots of a roster: a bit each in nuts_roster_go_order
+// the longest texts: "~FT~OL" + name + " appears in an explosion of blue magic!\n"; name + " " + out_phrase + " to the " +
+// room name + ".\n"; "Room access returned to ~FGPUBLIC.\n"; "The " + room name + " is not adjoined to here.\n" (and the
+// private notice, as long)
+constexpr int kGoEnterMax = 6 + kNameLen + 40, kGoLeaveMax = kNameLen + 1 + kPhraseLen + 8 + kRoomNameLen + 2, kGoResetMax = 35,
+              kGoReplyMax = 4 + kRoomNameLen + 26;
+constexpr int kGoEnterRow = 60, kGoLeaveRow = 84, kGoResetRow = 36, kGoReplyRow = 52;      // their slots
+constexpr int kGoRow = kGoEnterRow + kGoLeaveRow + kGoResetRow + kGoReplyRow;               // an event's bytes of composed text
+constexpr int go_row(int kind) { return kind == 0 ? kGoEnterRow : kind == 1 ? kGoLeaveRow : kind == 2 ? kGoResetRow : kGoReplyRow; }
+// Where text kind * k + b of a call of k events has its slot: the enter lines, then the leave lines, the reset lines, the replies.
+constexpr int64_t go_text_at(int kind, int64_t b, int64_t k)
+{
+    return (kind == 0 ? 0 : kind == 1 ? kGoEnterRow : kind == 2 ? kGoEnterRow + kGoLeaveRow : kGoEnterRow + kGoLeaveRow + kGoResetRow) * k
+           + go_row(kind) * b;
+}
+
+struct GoArgs {
+    const int32_t* room;         // [capacity] the roster's table
+    const uint8_t* slotf;        // [capacity] and its flag bytes: login
+    const uint8_t* speech;       // the tables this call reads, the uploads or the kept ones: the speaker state (name, vis, level),
+    const uint8_t* records;      // the clone records as take_clones lays them out (nullptr: the roster has none),
+    const uint8_t* rooms;        // the room records,
+    const uint8_t* go;           // [capacity * 88] and the go table
+    Kept kept[4];                // in that order
+    const uint8_t* text;         // the K inpstr, packed
+    const int32_t* text_off;     // [k]
+    const int32_t* text_len;     // [k]
+    const int32_t* slot;         // [k] the mover
+    const uint8_t* words;        // [k] word_count
+    const int32_t* ctext_off;    // [4k] where each text's slot starts in ctext
+    int k, capacity, look_rooms, clones, gatecrash_level, min_private_users;
+    int* violations;             // composed texts past their slot (zeroed by the host's upload)
+    uint8_t* ctext;              // the composed texts
+    int32_t* clen;               // [4k] their lengths; -1: no such text
+    int8_t* outcome;             // [k]
+    int32_t* target;             // [k] the room the word resolved to; -1: none, or get_room was not reached
+    int32_t* old_room;           // [k] the mover's room before the call
+    uint8_t* returned;           // [k] 1: the old room returns to public
+    int32_t* rm;                 // [3k] the room texts' rooms, as SpeakPlanArgs.rm
+    int32_t* sender;             // [3k] and their senders (-1: none)
+    int32_t* com_num;            // [3k]
+};
+
+// Does s[0 .. slen) begin with w[0 .. wlen), wlen <= kWordLen?  strncmp(s, w, strlen(w)) == 0 over a NUL-ended s, by a whole
+// wave, a byte per lane; wave-uniform.
+__device__ __forceinline__ bool begins_with(const uint8_t* s, int slen, const uint8_t* w, int wlen, int lane)
+{
+    const bool differs = lane < wlen && (lane >= slen || s[lane] != w[lane]);
+    return __ballot(differs) == 0;
+}
+
+__device__ void roster_go(const GoArgs& a)
+{
+    if ((int)blockIdx.x >= a.k) {           // the tables just uploaded, into the kept allocations: a word per lane
+        copy_kept(a.kept, ((int)blockIdx.x - a.k) * kBlock + (int)threadIdx.x);
+        return;
+    }
+    __shared__ int s_room[kBlock / 64], s_pop[kBlock / 64];
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int k = (int)blockIdx.x;
+    const int slot = a.slot[k], wc = a.words[k], len = a.text_len[k];
+    const uint8_t* in = a.text + a.text_off[k];
+    const uint8_t* sp = a.speech + (size_t)slot * kSpeechRec;
+    const uint8_t* gp = a.go + (size_t)slot * kGoRec;
+    const uint8_t state = sp[kNameLen + 1];
+    const int nlen = sp[kNameLen] < kNameLen ? sp[kNameLen] : kNameLen;
+    const int level = sp[kLevelByte];
+    const int here = a.room[slot];          // a look room: the host checked it
+    const uint8_t* hrec = a.rooms + (size_t)here * kRoomRec;
+
+    // word[1] as np_wordfind finds the line's second word (c:417-432): inpstr has lost the first
+    uint32_t wordb = 0;
+#pragma unroll
+    for (int x = 0; x < kReadSlice; x++) {
+        const int at = kReadSlice * lane + x;
+        wordb |= (uint32_t)(at < len && (int8_t)in[at] > 32) << x;
+    }
+    const int w0 = first_from(wordb, 0, lane, len);
+    const int w0_end = first_from(~wordb & 0xffffu, w0, lane, len);
+    const int wlen = w0_end - w0 < kWordLen ? w0_end - w0 : kWordLen;
+    const uint8_t* word = in + w0;
+
+    // c:4312-4316: too few words, then the netlink branch, which the caller answers; block-uniform
+    int outcome = -1;
+    if (wc < 2) outcome = kGoWhere;
+    else if (hrec[kRrNet] & (kNetUp | kNetDown | kNetVerifying)) {
+        const int slen = hrec[kRrServLen] < kServNameLen ? hrec[kRrServLen] : kServNameLen;
+        if (begins_with(hrec + kRrServ, slen, word, wlen, lane)) outcome = kGoNetlink;
+    }
+
+    // get_room (c:2388-2389): this wave's lowest room that has a name beginning with the word, among 64 w + 256 i + lane
+    int best = kNoMatch;
+    if (outcome < 0 && wlen <= kRoomNameLen) {
+        for (int base = 64 * wave; base < a.look_rooms; base += kBlock) {          // wave-uniform
+            const int r = base + lane;
+            bool hit = false;
+            if (r < a.look_rooms) {
+                const uint8_t* rec = a.rooms + (size_t)r * kRoomRec;
+                const int rl = rec[kRrNameLen] < kRoomNameLen ? rec[kRrNameLen] : kRoomNameLen;
+                hit = rl > 0 && wlen <= rl;                 // a room without a name is no room
+                for (int i = 0; i < wlen && hit; i++) hit = rec[i] == word[i];
+            }
+            const uint64_t b = __ballot(hit);
+            if (b) {
+                best = base + __ffsll((unsigned long long)b) - 1;
+                break;
+            }
+        }
+    }
+    if (lane == 0) s_room[wave] = best;
+    __syncthreads();
+    for (int w = 0; w < kBlock / 64; w++) best = s_room[w] < best ? s_room[w] : best;
+
+    // c:4384-4404 and move_user's first test (c:4417), block-uniform
+    int target = -1;
+    bool linked = false;
+    if (outcome < 0) {
+        if (best == kNoMatch) outcome = kGoNoRoom;
+        else {
+            target = best;
+            const int nlinks = hrec[kRrLinks] < kMaxLinks ? hrec[kRrLinks] : kMaxLinks;
+            const int32_t* link = reinterpret_cast<const int32_t*>(hrec + kRrLink);
+            for (int i = 0; i < nlinks; i++) linked |= link[i] == target;
+            const uint8_t access = a.rooms[(size_t)target * kRoomRec + kRrAccess];
+            const int32_t invite = *reinterpret_cast<const int32_t*>(gp + kGoInvite);
+            if (target == here) outcome = kGoAlready;
+            else if (!linked && level < kWiz) outcome = kGoNotAdjoined;
+            else if ((access & kAccessPrivate) && level < a.gatecrash_level && invite != target &&
+                     !((access & kAccessFixed) && level >= kWiz)) outcome = kGoPrivate;
+            else outcome = !(state & kVis) ? kGoUnseen : linked ? kGoWalked : kGoTeleported;
+        }
+    }
+    const bool moved = outcome <= kGoUnseen;
+
+    // reset_access(old_room) after the move (c:2093-2096): who still stands in a room that is exactly PRIVATE
+    int stay = 0;
+    if (moved && hrec[kRrAccess] == kAccessPrivate) {       // block-uniform
+        for (int base = 0; base < a.capacity; base += kBlock) {
+            const int j = base + (int)threadIdx.x;
+            const bool in_room = j < a.capacity && j != slot && a.room[j] == here && !(a.slotf[j] & kLogin) &&
+                                 a.speech[(size_t)j * kSpeechRec + kNameLen] != 0;
+            stay += __popcll(__ballot(in_room));
+        }
+        if (a.records) {                                    // clones count (c:2095 walks the whole user list)
+            const size_t slice = ((size_t)a.clones * sizeof(int32_t) + 255) & ~(size_t)255;
+            const int32_t* owner = reinterpret_cast<const int32_t*>(a.records);
+            const int32_t* croom = reinterpret_cast<const int32_t*>(a.records + slice);
+            for (int base = 0; base < a.clones; base += kBlock) {
+                const int c = base + (int)threadIdx.x;
+                const bool in_room = c < a.clones && owner[c] >= 0 && croom[c] == here;
+                stay += __popcll(__ballot(in_room));
+            }
+        }
+    }
+    if (lane == 0) s_pop[wave] = stay;
+    __syncthreads();
+    if (wave != 0) return;
+    stay = 0;
+    for (int w = 0; w < kBlock / 64; w++) stay += s_pop[w];
+    const bool returns = moved && hrec[kRrAccess] == kAccessPrivate && stay < a.min_private_users;
+
+    const int n = a.k;
+    uint8_t* enter = a.ctext + a.ctext_off[k];
+    uint8_t* leave = a.ctext + a.ctext_off[n + k];
+    const Piece none{nullptr, 0};
+    const Piece name{sp, nlen};
+    const uint8_t* trec = a.rooms + (size_t)(target < 0 ? here : target) * kRoomRec;
+    const Piece tname{trec, trec[kRrNameLen] < kRoomNameLen ? trec[kRrNameLen] : kRoomNameLen};
+    int enter_len = -1, leave_len = -1, reset_len = -1, reply_len = -1;
+    if (outcome == kGoUnseen) {             // c:4423-4427, invisenter and invisleave
+        const Piece e[5] = {lit("A presence enters the room...\n"), none, none, none, none};
+        const Piece l[5] = {lit("A presence leaves the room.\n"), none, none, none, none};
+        enter_len = compose(enter, kGoEnterRow, e, nullptr, 0, false, lane, a.violations);
+        leave_len = compose(leave, kGoLeaveRow, l, nullptr, 0, false, lane, a.violations);
+    } else if (outcome == kGoTeleported) {  // c:4428-4434
+        const Piece head[5] = {lit("~FT~OL"), name, none, none, none};
+        const Piece e[5] = {lit(" appears in an explosion of blue magic!\n"), none, none, none, none};
+        const Piece l[5] = {lit(" chants a spell and vanishes into a magical blue vortex!\n"), none, none, none, none};
+        enter_len = leave_len = 0;
+        append(enter, kGoEnterRow, enter_len, head, nullptr, 0, false, lane, a.violations);
+        append(enter, kGoEnterRow, enter_len, e, nullptr, 0, false, lane, a.violations);
+        append(leave, kGoLeaveRow, leave_len, head, nullptr, 0, false, lane, a.violations);
+        append(leave, kGoLeaveRow, leave_len, l, nullptr, 0, false, lane, a.violations);
+    } else if (outcome == kGoWalked) {      // c:4450-4453
+        const int ilen = gp[kGoInLen] < kPhraseLen ? gp[kGoInLen] : kPhraseLen;
+        const int olen = gp[kGoOutLen] < kPhraseLen ? gp[kGoOutLen] : kPhraseLen;
+        const Piece head[5] = {name, lit(" "), none, none, none};
+        const Piece e[5] = {lit(".\n"), none, none, none, none};
+        const Piece l[5] = {lit(" to the "), tname, lit(".\n"), none, none};
+        enter_len = leave_len = 0;
+        append(enter, kGoEnterRow, enter_len, head, gp + kGoIn, ilen, false, lane, a.violations);
+        append(enter, kGoEnterRow, enter_len, e, nullptr, 0, false, lane, a.violations);
+        append(leave, kGoLeaveRow, leave_len, head, gp + kGoOut, olen, false, lane, a.violations);
+        append(leave, kGoLeaveRow, leave_len, l, nullptr, 0, false, lane, a.violations);
+    } else if (outcome == kGoAlready) {     // c:4388
+        const Piece p[5] = {lit("You are already in the "), tname, lit("!\n"), none, none};
+        reply_len = compose(a.ctext + a.ctext_off[3 * n + k], kGoReplyRow, p, nullptr, 0, false, lane, a.violations);
+    } else if (outcome == kGoNotAdjoined) { // c:4400
+        const Piece p[5] = {lit("The "), tname, lit(" is not adjoined to here.\n"), none, none};
+        reply_len = compose(a.ctext + a.ctext_off[3 * n + k], kGoReplyRow, p, nullptr, 0, false, lane, a.violations);
+    } else if (outcome != kGoNetlink) {     // c:4313, nosuchroom, c:4418
+        const Piece p[5] = {outcome == kGoWhere ? lit("Go where?\n") : outcome == kGoNoRoom ? lit("There is no such room.\n")
+                            : lit("That room is currently private, you cannot enter.\n"), none, none, none, none};
+        reply_len = compose(a.ctext + a.ctext_off[3 * n + k], kGoReplyRow, p, nullptr, 0, false, lane, a.violations);
+    }
+    if (moved && (enter_len < 0 || leave_len < 0)) enter_len = leave_len = -1;     // a violation: the call fails
+    if (returns && enter_len >= 0) {        // c:2097
+        const Piece p[5] = {lit("Room access returned to ~FGPUBLIC.\n"), none, none, none, none};
+        reset_len = compose(a.ctext + a.ctext_off[2 * n + k], kGoResetRow, p, nullptr, 0, false, lane, a.violations);
+    }
+    if (lane == 0) {
+        a.clen[k] = enter_len;
+        a.clen[n + k] = leave_len;
+        a.clen[2 * n + k] = reset_len;
+        a.clen[3 * n + k] = reply_len;
+        a.outcome[k] = (int8_t)outcome;
+        a.target[k] = target;
+        a.old_room[k] = here;
+        a.returned[k] = reset_len >= 0;
+        a.rm[k] = target;                   // write_room(rm, ...): nobody is excepted
+        a.sender[k] = -1;
+        a.rm[n + k] = a.rm[2 * n + k] = here;               // the snapshot still has the mover there
+        a.sender[n + k] = a.sender[2 * n + k] = slot;
+        a.com_num[k] = a.com_num[n + k] = a.com_num[2 * n + k] = kComGo;
+    }
+}
+
+static_assert(kGoEnterMax == 58 && kGoLeaveMax == 83 && kGoReplyMax == 50 && kGoEnterMax <= kGoEnterRow && kGoLeaveMax <= kGoLeaveRow &&
+              kGoResetMax <= kGoResetRow && kGoReplyMax <= kGoReplyRow, "roster_go: the longest texts fit their slots");
+static_assert(sizeof(" appears in an explosion of blue magic!\n") - 1 == 40 && sizeof("Room access returned to ~FGPUBLIC.\n") - 1 == kGoResetMax &&
+              6 + kNameLen + sizeof(" chants a spell and vanishes into a magical blue vortex!\n") - 1 <= kGoLeaveMax &&
+              sizeof("That room is currently private, you cannot enter.\n") - 1 <= kGoReplyMax &&
+              sizeof("You are already in the !\n") - 1 + kRoomNameLen <= kGoReplyMax &&
+              sizeof("The  is not adjoined to here.\n") - 1 + kRoomNameLen == kGoReplyMax, "roster_go: the texts are as long as counted");
+static_assert(kGoRec % 4 == 0 && kGoInvite % 4 == 0 && kGoOutLen < kGoInvite && kGoRow % 4 == 0 && kGoLeaveRow < kTextSize,
+              "roster_go: a go row is whole words, and a text fits speak_plan's LDS text");
+static_assert(kWordLen < 64 && sizeof(" chants a spell and vanishes into a magical blue vortex!\n") - 1 <= 64,
+              "roster_go: a word is a byte per lane, and the pieces of a compose() fit a wave");
+
+struct GoOrderArgs {
+    const int32_t* slot;         // [k] the movers
+    const int32_t* old_room;     // [k] what nuts_roster_go wrote
+    const int32_t* target;       // [k]
+    int k;
+    int8_t* outcome;             // [k] becomes kGoDeferred for a deferred event
+    int32_t* clen;               // [4k] whose four texts become void
+    uint8_t* returned;           // [k] and whose room does not return
+};
+
+__device__ void roster_go_order(const GoOrderArgs& a)
+{
+    __shared__ uint32_t s_rooms[kMaxLookRooms / 32], s_slots[kGoMaxSlots / 32];
+    const int lane = (int)threadIdx.x;      // one wave
+    for (int i = lane; i < kMaxLookRooms / 32; i += 64) s_rooms[i] = 0;
+    for (int i = lane; i < kGoMaxSlots / 32; i += 64) s_slots[i] = 0;
+    __syncthreads();
+    for (int base = 0; base < a.k; base += 64) {
+        const int k = base + lane;
+        const bool live = k < a.k;
+        const int slot = live ? a.slot[k] : 0, old = live ? a.old_room[k] : 0, tgt = live ? a.target[k] : -1;
+        const int out = live ? a.outcome[k] : kGoWhere;
+        const int count = a.k - base < 64 ? a.k - base : 64;
+        bool defer = false;
+        for (int i = 0; i < count; i++) {   // in call order; every lane follows, lane 0 sets the bits
+            const int s = __shfl(slot, i), o = __shfl(old, i), t = __shfl(tgt, i), oc = __shfl(out, i);
+            const bool hit = ((s_slots[s >> 5] >> (s & 31)) & 1u) || ((s_rooms[o >> 5] >> (o & 31)) & 1u) ||
+                             (t >= 0 && ((s_rooms[t >> 5] >> (t & 31)) & 1u));
+            if (lane == i) defer = hit;
+            __syncthreads();
+            if (lane == 0 && !hit && oc <= kGoUnseen) {     // a move touches its slot, the room left and the room entered
+                s_slots[s >> 5] |= 1u << (s & 31);
+                s_rooms[o >> 5] |= 1u << (o & 31);
+                s_rooms[t >> 5] |= 1u << (t & 31);
+            }
+            __syncthreads();
+        }
+        if (live && defer) {
+            a.outcome[k] = (int8_t)kGoDeferred;
+            a.clen[k] = a.clen[a.k + k] = a.clen[2 * a.k + k] = a.clen[3 * a.k + k] = -1;
+            a.returned[k] = 0;
+        }
+    }
+}
+
+static_assert(kMaxLookRooms % 32 == 0 && kGoMaxSlots % 32 == 0, "roster_go_order: the bitmaps are whole words");
+
 }  // namespace
 
 // Stable, unmangled kernel names (they are what rocprofv3 reports).
@@ -2642,6 +2967,8 @@ extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_who(WhoArgs a) 
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_who_shown(WhoArgs a) { roster_who_shown(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_rooms_count(RoomsArgs a) { roster_rooms_count(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_rooms_lines(RoomsArgs a) { roster_rooms_lines(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_go(GoArgs a) { roster_go(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_go_order(GoOrderArgs a) { roster_go_order(a); }
 
 // ------------------------------------------------------------------------------------------ host library
 
@@ -2862,7 +3189,7 @@ constexpr int kMaxCapacity = 65536;
 
 // The tables a roster keeps on the device between calls, each in an allocation of its own that the first call to give
 // the table makes and that never moves.  A caller passes one only when it changed: see pass_kept().
-enum KeptId { kKeptSpeech, kKeptAfk, kKeptRooms, kKeptUdesc, kKeptWho, kKeptClones, kKeptNames, kKeptCount };
+enum KeptId { kKeptSpeech, kKeptAfk, kKeptRooms, kKeptUdesc, kKeptWho, kKeptClones, kKeptNames, kKeptGo, kKeptCount };
 struct KeptTable {
     const char* what;            // for error messages
     uint8_t* d = nullptr;
@@ -2883,7 +3210,7 @@ struct Roster {
     int look_rooms = 0;          // rooms 0 .. look_rooms - 1 own a room record
     int clones = 0;              // clone records 0 .. clones - 1
     KeptTable kept[kKeptCount] = {{"speaker table"}, {"AFK messages"}, {"room table"}, {"user descriptions"},
-                                  {"who table"}, {"clone records"}, {"room names"}};   // by KeptId; kept_bytes() has their sizes
+                                  {"who table"}, {"clone records"}, {"room names"}, {"go table"}};   // by KeptId; kept_bytes() has their sizes
 };
 Roster g_rosters[kMaxRosters];
 
@@ -2906,6 +3233,7 @@ size_t kept_bytes(int id, int capacity, int look_rooms, int clones)
     case kKeptUdesc: return (size_t)capacity * kUserDescRow;               // the users' descriptions, 32 bytes per slot
     case kKeptWho: return (size_t)capacity * kWhoRec;                      // last_login and away, 8 bytes per slot
     case kKeptNames: return (size_t)look_rooms * kRelayNameRow;            // the look rooms' names, 24 bytes per room
+    case kKeptGo: return (size_t)capacity * kGoRec;                        // the phrases and the invite, 88 bytes per slot
     default: {                                                             // the clones' owners, rooms and hear bytes
         Carver sized{0};
         const int32_t *owner, *room;
@@ -3238,6 +3566,53 @@ size_t layout_rooms(uintptr_t base, RoomsArgs& s, SpeakPlanArgs& p)
     p.text = s.ctext;
     p.text_off = s.ctext_off;
     p.text_len = s.clen;
+    p.violations = s.violations;
+    return take.at;
+}
+
+// nd_roster_go's layout of a roster's allocation, after layout_tell's pattern: the table, the uploads of the speaker table,
+// of the clone records, of the room table and of the go table (which the kept ones are filled from; the two that a go call's
+// own aftermath changes last), the call's inputs ending with violations, the results next to each other, and last what only
+// the kernels pass to each other.  p plans 3k room lines and k replies.
+size_t layout_go(uintptr_t base, size_t text_bytes, GoArgs& s, SpeakPlanArgs& p)
+{
+    Carver take{base};
+    const size_t k = (size_t)s.k, t = kGoTexts * k;
+    const size_t ctext_bytes = (size_t)kGoRow * k;
+    take_table(take, s.capacity, s.room, s.slotf);
+    take_kept(take, s.kept[0], kKeptSpeech, s.capacity);
+    take_kept(take, s.kept[1], kKeptClones, s.capacity, s.look_rooms, s.clones);
+    take_kept(take, s.kept[2], kKeptRooms, s.capacity, s.look_rooms);
+    take_kept(take, s.kept[3], kKeptGo, s.capacity);
+    take(s.text, text_bytes);
+    take(s.text_off, k);
+    take(s.text_len, k);
+    take(s.slot, k);
+    take(s.words, k);
+    take(s.ctext_off, t);
+    take(s.violations, 1);
+    take(s.outcome, k);
+    take(s.target, k);
+    take(s.old_room, k);
+    take(s.returned, k);
+    take(s.clen, t);
+    take(p.vn, 2 * t);
+    take(p.vw, 2 * t);
+    take(p.vwsz, 2 * t * kMaxWrites);
+    take(p.bits, 3 * k * (size_t)p.words);
+    take(s.ctext, ctext_bytes);
+    take(p.var, (size_t)var_at((int64_t)ctext_bytes, (int64_t)t));
+    take(s.rm, 3 * k);
+    take(s.sender, 3 * k);
+    take(s.com_num, 3 * k);
+    p.room = s.room;
+    p.slot = s.slotf;
+    p.text = s.ctext;
+    p.text_off = s.ctext_off;
+    p.text_len = s.clen;
+    p.rm = s.rm;
+    p.sender = s.sender;
+    p.com_num = s.com_num;
     p.violations = s.violations;
     return take.at;
 }
@@ -4820,6 +5195,136 @@ int nd_roster_rooms(int handle, int k, const int32_t* slots, int kinds, const ui
     memcpy(vn, res(po.vn), 2 * texts * sizeof(int64_t));
     memcpy(vw, res(po.vw), 2 * texts * sizeof(int32_t));
     memcpy(vwsz, res(po.vwsz), 2 * texts * kMaxWrites * sizeof(int32_t));
+    memcpy(ctext, res(so.ctext), ctext_bytes);
+    memcpy(var, res(po.var), var_bytes);
+
+    return fill_timing(timing, t0, t1, h2d, res_bytes);
+}
+
+// K .go events of roster `handle`, decided and composed as go() and move_user() do, against the tables as they are: nothing
+// the roster keeps is changed, the caller applies the moves.  Event b: the mover's slot slots[b], which stands in a look
+// room, inpstr and words[b] as nd_roster_tell's.  gatecrash_level (0 .. 4) and min_private_users (>= 0) are the talker's.
+// table, speech and rooms as nd_roster_look's, clones as nd_roster_relay's (NULL for a roster without clone records); go is
+// NULL when no go row changed since the last nd_roster_go of this roster, else all of them: 88 bytes per slot, in_phrase[40],
+// its length, out_phrase[40], its length, two zeros, int32 invite_room (-1: none); the roster's first call must give it.
+// Outputs (host, caller-allocated), with W = ceil(capacity / 64) and text t = b for event b's enter line, k + b its leave
+// line, 2k + b its reset line, 3k + b its reply: outcome[k] (0 walked, 1 teleported, 2 unseen, 3 where, 4 netlink, 5 no room,
+// 6 already, 7 not adjoined, 8 private, 9 deferred); target[k] the room the word resolved to, or -1; old_room[k];
+// returned[k] 1 when the old room returns to public; clen[4k], -1 where there is no text; ctext[232 k], the enter lines at
+// 60 b, the leave lines at 60 k + 84 b, the reset lines at 144 k + 36 b, the replies at 180 k + 52 b; bits[3k * W] the admit
+// bitmaps of the enter, leave and reset lines; vn[8k], vw[8k], vwsz[8k * 16] and var[12 * 232 k + 64 k] as nd_roster_speak's.
+// Per call, whatever k and the capacity: one upload, three kernels (nuts_roster_go, nuts_roster_go_order,
+// nuts_roster_speak_plan), one download at the bound size, one synchronise.  Returns 0, or -1 with nd_last_error() set.
+int nd_roster_go(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off, const int32_t* text_len,
+                 const int32_t* slots, const uint8_t* words, int gatecrash_level, int min_private_users, const uint8_t* table,
+                 const uint8_t* speech, const uint8_t* clones, const uint8_t* rooms, const uint8_t* go, int8_t* outcome,
+                 int32_t* target, int32_t* old_room, uint8_t* returned, int32_t* clen, uint64_t* bits, int64_t* vn, int32_t* vw,
+                 int32_t* vwsz, uint8_t* ctext, uint8_t* var, nd_roster_timing* timing)
+{
+    static_assert(kGoMaxSlots == kMaxCapacity, "nuts_roster_go_order has a bit per slot");
+    Roster* r = roster_at(handle);
+    if (!r || ensure_ready()) return -1;
+    const int cap = r->capacity, nwords = (cap + 63) / 64, nrooms = r->look_rooms;
+    if (k < 1 || (int64_t)k * cap >= INT32_MAX || (int64_t)k * kGoRow >= INT32_MAX / 16 || text_bytes < 0 ||
+        text_bytes >= INT32_MAX / 32 || nrooms < 1 || nrooms > kMaxLookRooms || gatecrash_level < 0 || gatecrash_level > kGod ||
+        min_private_users < 0) {
+        snprintf(g_err, sizeof(g_err), "%d events to %d slots over %d look rooms: need 1 <= k * capacity < 2^31 - 1, a look room, a "
+                 "gatecrash level in 0 .. %d and a minimum of private users >= 0", k, cap, nrooms, kGod);
+        return -1;
+    }
+    int64_t sum = 0;
+    for (int b = 0; b < k; b++) {       // the kernels index by these: nothing out of range reaches them
+        if (slots[b] < 0 || slots[b] >= cap || text_len[b] < 0 || text_len[b] >= kArrSize || text_off[b] != sum) {
+            snprintf(g_err, sizeof(g_err), "event %d: slot, text length or text offset out of range", b);
+            return -1;
+        }
+        sum += text_len[b];
+    }
+    if (sum != text_bytes) {
+        snprintf(g_err, sizeof(g_err), "the events' texts hold %lld bytes, not %lld", (long long)sum, (long long)text_bytes);
+        return -1;
+    }
+    GoArgs s{};
+    const Given given[] = {{kKeptSpeech, speech, &s.speech}, {kKeptClones, clones, &s.records}, {kKeptRooms, rooms, &s.rooms},
+                           {kKeptGo, go, &s.go}};
+    if (check_given(*r, given, "the roster's first go call must give the speaker table, the clone records, the room table and the go table"))
+        return -1;
+    const double t0 = now_ns();
+    hipStream_t st = g.stream;
+    SpeakPlanArgs p{};
+    s.k = k;
+    p.k = 3 * k;
+    s.capacity = p.capacity = cap;
+    s.look_rooms = nrooms;
+    s.clones = r->clones;
+    s.gatecrash_level = gatecrash_level;
+    s.min_private_users = min_private_users;
+    p.tiles = (cap + kBlock - 1) / kBlock;
+    p.words = nwords;
+    const size_t texts = (size_t)kGoTexts * k, ctext_bytes = (size_t)kGoRow * k;
+    const size_t var_bytes = (size_t)var_at((int64_t)ctext_bytes, (int64_t)texts);
+    GoArgs so = s;                      // offsets of every array in the roster's allocation
+    SpeakPlanArgs po = p;
+    const size_t need = layout_go(0, (size_t)text_bytes, so, po);
+    const size_t table_bytes = (uintptr_t)so.kept[0].fresh, tables_end = (uintptr_t)so.text;
+    const size_t in_bytes = (uintptr_t)so.violations + sizeof(int);
+    const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
+    if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
+    if (table) new_table(*r, so.room, so.slotf, table);
+    const int32_t* room = reinterpret_cast<const int32_t*>(r->mirror + (uintptr_t)so.room);
+    for (int b = 0; b < k; b++)         // nuts_roster_go reads its mover's room record
+        if (room[slots[b]] < 0 || room[slots[b]] >= nrooms) {
+            snprintf(g_err, sizeof(g_err), "event %d: the mover's room has no room record", b);
+            return -1;
+        }
+    if (grow_roster(*r, need)) return -1;
+    layout_go((uintptr_t)r->d, (size_t)text_bytes, s, p);
+    if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
+
+    uint8_t* h = r->mirror;
+    const Put put{h};
+    put(so.text, text, (size_t)text_bytes);
+    put(so.text_off, text_off, (size_t)k * sizeof(int32_t));
+    put(so.text_len, text_len, (size_t)k * sizeof(int32_t));
+    put(so.slot, slots, (size_t)k * sizeof(int32_t));
+    put(so.words, words, (size_t)k);
+    int32_t* coff = reinterpret_cast<int32_t*>(h + (uintptr_t)so.ctext_off);
+    for (int kind = 0; kind < kGoTexts; kind++)
+        for (int b = 0; b < k; b++) coff[(size_t)kind * k + b] = (int32_t)go_text_at(kind, b, k);
+    *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
+    // the tables' uploads lie between the table and the inputs
+    size_t first = 0, h2d = 0;
+    unsigned copy_blocks = 0;
+    if (pass_kept(*r, given, so.kept, s.kept, tables_end, &first, &copy_blocks)) return -1;
+    if (upload(*r, table_bytes, first, in_bytes, &h2d)) return -1;
+
+    const GoOrderArgs order{s.slot, s.old_room, s.target, k, s.outcome, s.clen, s.returned};
+    ND_CHECK(hipEventRecord(g.ev0, st));
+    hipLaunchKernelGGL(nuts_roster_go, dim3((unsigned)k + copy_blocks), dim3(kBlock), 0, st, s);
+    ND_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(nuts_roster_go_order, dim3(1), dim3(64), 0, st, order);
+    ND_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)(3 * k * p.tiles + k)), dim3(kBlock), 0, st, p);
+    ND_CHECK(hipGetLastError());
+    if (fetch_results(r->d, res_at, res_bytes)) return -1;
+    const double t1 = now_ns();
+
+    const Res res{gm.res, res_at};
+    const int violations = *reinterpret_cast<const int*>(res(so.violations));
+    if (violations) {
+        snprintf(g_err, sizeof(g_err), "%d text(s) exceeded the hard bounds (a text its slot; 6*len+4 bytes, %d writes transduced)",
+                 violations, kMaxWrites);
+        return -1;
+    }
+    memcpy(outcome, res(so.outcome), (size_t)k);
+    memcpy(target, res(so.target), (size_t)k * sizeof(int32_t));
+    memcpy(old_room, res(so.old_room), (size_t)k * sizeof(int32_t));
+    memcpy(returned, res(so.returned), (size_t)k);
+    memcpy(clen, res(so.clen), texts * sizeof(int32_t));
+    memcpy(vn, res(po.vn), 2 * texts * sizeof(int64_t));
+    memcpy(vw, res(po.vw), 2 * texts * sizeof(int32_t));
+    memcpy(vwsz, res(po.vwsz), 2 * texts * kMaxWrites * sizeof(int32_t));
+    memcpy(bits, res(po.bits), 3 * (size_t)k * nwords * sizeof(uint64_t));
     memcpy(ctext, res(so.ctext), ctext_bytes);
     memcpy(var, res(po.var), var_bytes);
 

@@ -2,7 +2,7 @@
 
     python -m nuts333_amd.devpath [--reps R] [--warmup W] [--pathbench-iterations I] [--per-call K[,K...]]
                                   [--roster K[,K...]] [--plan K[,K...]] [--review Q[,Q...]] [--speak K[,K...]]
-                                  [--input K[,K...]] [--tell K[,K...]] [--look K[,K...]] [--relay K[,K...]]
+                                  [--input K[,K...]] [--tell K[,K...]] [--look K[,K...]] [--relay K[,K...]] [--go K[,K...]]
                                   [--who K[,K...]] [--rooms K[,K...]]   -> one JSON line
 
 For N in {10, 100, 1000} listeners, the two texts oracle/pathbench.c times (``say``; ``shout`` carrying ``~OL``/``~RS``)
@@ -89,6 +89,14 @@ one kind (``.rmst``, then ``.rmsn``) per ``Roster.rooms_many`` call: the three t
 the CPU composing ``rooms()``'s strings for each looker in Python and the CPU restatement's transducer over them
 (``rooms_cpu_us_covers`` says what that is worth).  The first call of each case is checked against that transducer over
 those strings.
+
+``--go K[,K...]`` adds ``go``: a 1000-slot roster of WIZ users over the six default rooms, and K walks (slots 0 .. K - 1, each
+to a room that adjoins its own both ways) per ``Roster.go_many`` call, there in one call and back in the next, so that the
+state is periodic: the three times and the copy volume of both device visits added up, beside ``parts`` -- ``plan_many`` of
+the same composed lines, then ``look_many`` of the same movers, which is what a ``go_many`` call is made of -- and ``cpu_us``,
+the CPU composing the strings in Python and transducing them.  Six rooms hold at most three disjoint walks, so of K = 8 or
+64 events most are deferred: ``moved`` and ``deferred`` say how many.  The first call of each case is checked against the
+reference's formats and the CPU's transducer over ``look()``'s strings.
 """
 from __future__ import annotations
 
@@ -758,6 +766,149 @@ def rooms_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
             "rooms": cases}
 
 
+#: the six default rooms' links (provision.SIX_ROOMS): the hallway joins the drive, the corridor, the wizroom and the shop
+GO_LINKS = ([1], [0, 3, 2, 5], [1], [1, 4], [3], [1])
+#: where a mover standing in room r walks to, and back from: a room that adjoins r both ways
+GO_THERE = (1, 0, 1, 4, 3, 1)
+_ACCESS_WORDS = {device.PUBLIC: b"set to ~FGPUBLIC~RS", device.FIXED_PUBLIC: b"~FRfixed~RS to ~FGPUBLIC~RS",
+                 device.FIXED_PRIVATE: b"~FRfixed~RS to ~FRPRIVATE~RS"}
+
+
+class _Visits(NamedTuple):
+    """The device visits of one step, their timings added up: what ``_timed`` reads of a result."""
+    timing: dict
+
+
+def _visits(*results) -> _Visits:
+    total = {}
+    for r in results:
+        for f, v in (r.timing if r is not None else {}).items():
+            total[f] = total.get(f, 0) + v
+    return _Visits(total)
+
+
+def go_look_strings(room_of: np.ndarray, slot: int) -> list[bytes]:
+    """What look() hands to write_user for ``slot`` of the roster ``go_cases`` builds, its users standing in ``room_of``:
+    every user visible, of one level, without a description, no topic and no message anywhere."""
+    names, accesses = ROOMS_LISTS["6"]
+    rm = int(room_of[slot])
+    col = lambda r: b"~FR" if accesses[r] & 1 else b"~FG"
+    lines = [b"      User%d ~RS  \n" % j for j in np.flatnonzero(room_of == rm).tolist() if j != slot]
+    return ([b"\n~FTRoom: %s%s\n\n" % (col(rm), names[rm]), b"",
+             b"\n~FTExits are:" + b"".join(b"  %s%s" % (col(l), names[l]) for l in GO_LINKS[rm]) + b"\n\n"]
+            + ([b"~FTYou can see:\n"] + lines if lines else [b"~FTYou are all alone here.\n"])
+            + [b"\n", b"Access is %s and there are ~OL~FM0~RS messages on the board.\n" % _ACCESS_WORDS[accesses[rm]],
+               b"No topic has been set yet.\n"])
+
+
+def go_model(room_of: np.ndarray, events) -> list[tuple]:
+    """What go_many answers for ``events`` at that roster, where every user is a visible WIZ and no room is exactly PRIVATE:
+    per event ``(outcome, target, enter line, leave line, reply)``.  The moves are applied to ``room_of``."""
+    names = ROOMS_LISTS["6"][0]
+    slots, rooms, out = set(), set(), []
+    for slot, word, _wc in events:
+        here, target = int(room_of[slot]), names.index(word)
+        if slot in slots or here in rooms or target in rooms:
+            out.append((device.GO_DEFERRED, target, None, None, None))
+        elif target == here:
+            out.append((device.GO_ALREADY, target, None, None, b"You are already in the %s!\n" % word))
+        else:
+            out.append((device.GO_WALKED, target, b"User%d enters.\n" % slot, b"User%d goes to the %s.\n" % (slot, word), None))
+            slots.add(slot)
+            rooms |= {here, target}
+            room_of[slot] = target
+    return out
+
+
+def go_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
+    """The ``go`` section: go_many of K walks (slots 0 .. K - 1) at a 1000-slot roster over the six default rooms, there in
+    one call and back in the next, so that the state is periodic; beside the parts a go_many call is made of --
+    plan_many of the same composed lines, then look_many of the same movers -- and the CPU composing the strings in
+    Python and transducing them."""
+    n = 1000
+    names, accesses = ROOMS_LISTS["6"]
+    nr = len(names)
+    cases = []
+    for colour in COLOURS:
+        with device.Roster(n, look_rooms=nr) as roster:
+            col = colours(n, colour)
+            home = np.arange(n) % nr
+            roster.update(range(n), room=home.tolist(), colour=col, name=[b"User%d" % j for j in range(n)], level=2)
+            roster.set_rooms(list(range(nr)), name=names, access=accesses, links=[list(l) for l in GO_LINKS])
+            settings = {"gatecrash_level": 3, "min_private_users": 2}
+            for k in ks:
+                movers = [j % n for j in range(k)]
+                there = [(j, names[GO_THERE[int(home[j])]], 2) for j in movers]
+                back = [(j, names[int(home[j])], 2) for j in movers]
+                room_of = home.copy()
+                want_there = go_model(room_of, there)
+                moved = [j for j, w in zip(movers, want_there) if w[0] == device.GO_WALKED]
+                looks = {j: go_look_strings(room_of, j) for j in moved}
+                first = roster.go_many(there, **settings)
+                if first.outcome.tolist() != [w[0] for w in want_there] or first.target.tolist() != [w[1] for w in want_there]:
+                    raise SystemExit(f"devpath: go {k}, {colour}: the device's outcomes differ from the model's")
+                for i, w in enumerate(want_there):
+                    if (first.enter_text(i), first.leave_text(i), first.reply_text(i)) != tuple(x or b"" for x in w[2:]):
+                        raise SystemExit(f"devpath: go {k}, {colour}: event {i}'s texts differ from the reference's formats")
+                for i, j in enumerate(moved):
+                    if first.look.chunks(i) != [ch for text in looks[j] for ch in nuts_path.chunks(text, int(col[j]))]:
+                        raise SystemExit(f"devpath: go {k}, {colour}: look {i} differs from the CPU's transducer over look()'s strings")
+                want_back = go_model(room_of, back)
+                second = roster.go_many(back, **settings)
+                if second.outcome.tolist() != [w[0] for w in want_back] or not np.array_equal(room_of, home) or not np.array_equal(roster._room, home):
+                    raise SystemExit(f"devpath: go {k}, {colour}: the walk back does not end where the walk there began")
+                lines = [(w[2], w[1], None, 0, device.COM_GO) for w in want_there if w[2]]
+                lines += [(w[3], int(home[j]), j, 0, device.COM_GO) for j, w in zip(movers, want_there) if w[3]]
+                lines += [(w[4], None, None, 0, device.COM_GO) for w in want_there if w[4]]
+
+                def parts():
+                    return _visits(roster.plan_many(lines) if lines else None, roster.look_many(moved) if moved else None)
+
+                def cpu():
+                    rooms = home.copy()
+                    for j, w in zip(movers, go_model(rooms, there)):
+                        for text in w[2:]:
+                            if text:
+                                nuts_path.chunks(text, 0)
+                                nuts_path.chunks(text, 1)
+                        if w[0] == device.GO_WALKED:
+                            c = int(col[j])
+                            for text in go_look_strings(rooms, j):
+                                nuts_path.chunks(text, c)
+
+                def go(events):
+                    g = roster.go_many(events, **settings)
+                    return _visits(g, g.look)
+
+                timed = _timed(f"go {k}, {colour}", {"there": lambda: go(there), "back": lambda: go(back), "parts": parts, "cpu": cpu},
+                               reps, warmup)
+                dev, cpu_us = timed["there"], timed["cpu"].host_us
+                count = lambda want, what: sum(w[0] == what for w in want)
+                cases.append({"n": n, "k": k, "colour": colour, "rooms": nr, "moved": len(moved),
+                              "deferred": count(want_there, device.GO_DEFERRED), "already": count(want_there, device.GO_ALREADY),
+                              "back_moved": count(want_back, device.GO_WALKED), "back_already": count(want_back, device.GO_ALREADY),
+                              "back_deferred": count(want_back, device.GO_DEFERRED),
+                              "bytes_out": sum(len(first.look.output(i)) for i in range(len(moved))), **dev.fields, "cpu_us": cpu_us,
+                              "back": timed["back"].fields, "parts": timed["parts"].fields,
+                              "go_over_parts": {f: round(dev.times[f]["median"] / timed["parts"].times[f]["median"], 2) for f in FIELDS},
+                              "end_to_end_over_cpu": float(f"{dev.times['end_to_end_us']['median'] / cpu_us['median']:.3g}")})
+    return {"go_kernels": list(device.GO_KERNELS) + ["nuts_roster_speak_plan", "nuts_roster_look", "nuts_roster_speak_plan"],
+            "go_end_to_end_covers": "both device visits of a go_many call, added up.  The first: packing the K events into pinned "
+                                    "memory, one H2D (the events alone: the look of the call before left every mirror clean), "
+                                    "three kernels -- get_room, the decision chain, the texts; the deferral walk; both variants "
+                                    "of every text and the room lines' admit bitmaps --, one D2H at the bound size, one "
+                                    "synchronise.  Between the visits the binding applies the moves to the host mirrors.  The "
+                                    "second: look_many of the movers, which uploads the table the moves made stale, 5 bytes a "
+                                    "slot (python_us adds checking the events, the copies out of pinned memory, the applying "
+                                    "and building the Go)",
+            "go_parts_covers": "plan_many of the lines the same call composes, composed beforehand, then look_many of the same "
+                               "movers, at a roster nobody moved in: neither uploads the table",
+            "go_cpu_us_covers": "the model of the call in Python -- the deferral rule and the reference's formats, interpreted --, "
+                                "np_write_user_stream of the CPU restatement (nuts_path, through ctypes) over both variants of "
+                                "every line, and look()'s strings composed in Python for every mover and transduced for its colour",
+            "go": cases}
+
+
 RELAY_CLONES = 64
 
 
@@ -885,6 +1036,9 @@ SECTIONS = (
     ("rooms", "K[,K...]", "also time K .rmst and K .rmsn listings per Roster.rooms_many call at a 1000-slot roster over 6 and "
                           "over 1,024 rooms, for each K, beside the CPU composing and transducing rooms()'s strings (the "
                           "rooms section)", "rooms_cases"),
+    ("go", "K[,K...]", "also time K walks per Roster.go_many call at a 1000-slot roster over the six default rooms, there and "
+                       "back, for each K, beside plan_many and look_many of the same lines and movers and the CPU composing "
+                       "and transducing the strings (the go section)", "go_cases"),
 )
 
 
