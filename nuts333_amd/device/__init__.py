@@ -69,8 +69,14 @@ composes: ``get_room``, the adjoined, private and gatecrash checks, the enter, l
 their plans.  An event that an earlier move of the same call touched -- its slot, its room or its target -- is deferred and
 comes back unanswered, so every answered event is exact against the roster as it was before the call.  The binding applies
 the moves to the host mirrors, and the look a move ends with is one ``look_many`` over the movers: at most two device visits.
-Left to the caller: the netlink branch (GO_NETLINK), ``.move``, ``.private`` / ``.public`` / ``.invite`` themselves, the relay
-of the three room texts to clones' owners, and the prompt.
+Left to the caller: the netlink branch (GO_NETLINK), ``.move``, the relay of the three room texts to clones' owners, and the
+prompt.
+``Roster.access_many(events, gatecrash_level=, min_private_users=, ignore_mp_level=)`` answers what changes the two pieces of
+state ``.go`` decides by, a room's ``access`` and a user's ``invite_room``: K ``(slot, com, inpstr, word_count)`` events with
+``com`` COM_PUBLIC, COM_PRIVATE, COM_LETMEIN or COM_INVITE, as ``set_room_access()``, ``letmein()`` and ``invite()`` do
+(nuts333.c:4543-4693) -- an :class:`Access`.  The device runs ``get_room``, ``get_user`` and the head-count of a room, decides
+and composes the actor's line, the two room lines and the invitation, with their plans; an event that an earlier one of the
+same call touched is deferred; the binding sets the access and the invitations in the host mirrors.
 
 Input is validated before the device is touched (``ValueError``).  The library ``_build/libnuts_device.so`` is built by
 ``__graft_entry__.build()`` where ``hipcc`` exists, and on demand here when it is missing or older than its source.
@@ -272,6 +278,30 @@ MAX_GO_ENTER, MAX_GO_LEAVE, MAX_GO_RESET, MAX_GO_REPLY = (6 + USER_NAME_LEN + 40
 _GO_ROWS = (60, 84, 36, 52)
 #: the texts of an event in a Go, in that order
 GO_ENTER, GO_LEAVE, GO_RESET, GO_REPLY = range(4)
+#: ``.public``, ``.private``, ``.letmein`` and ``.invite`` (NP_PUBLIC .. NP_INVITE), and the kernels access_many runs before
+#: nuts_roster_speak_plan
+COM_PUBLIC, COM_PRIVATE, COM_LETMEIN, COM_INVITE = 16, 17, 18, 19
+ACCESS_KERNELS = ("nuts_roster_access", "nuts_roster_access_order")
+#: what became of such an event (Access.outcome).  The first three changed something -- a room set private, set public, a
+#: user invited -- and ACCESS_ASKED, a ``.letmein`` that was shouted, changed nothing.  Then the refusals to the actor alone,
+#: a branch of the reference each: of ``set_room_access`` (level too low for the room option, no such room, access fixed,
+#: already public, already private, too few occupants), of ``letmein`` (no word, no such room, already in, not adjoined, the
+#: room is public) and of ``invite`` (no word, the room is public, nobody of that name, oneself, already here, already
+#: invited); and ACCESS_DEFERRED, an event the caller submits again
+(ACCESS_SET_PRIVATE, ACCESS_SET_PUBLIC, ACCESS_INVITED, ACCESS_ASKED, ACCESS_LOW_LEVEL, ACCESS_NO_ROOM, ACCESS_FIXED,
+ ACCESS_ALREADY_PUBLIC, ACCESS_ALREADY_PRIVATE, ACCESS_TOO_FEW, ACCESS_LET_WHERE, ACCESS_LET_NO_ROOM, ACCESS_LET_ALREADY,
+ ACCESS_LET_NOT_ADJOINED, ACCESS_LET_PUBLIC, ACCESS_INVITE_WHO, ACCESS_INVITE_PUBLIC, ACCESS_INVITE_NOBODY, ACCESS_INVITE_SELF,
+ ACCESS_INVITE_HERE, ACCESS_INVITE_ALREADY, ACCESS_DEFERRED) = range(22)
+#: the longest texts of such an event before the transducer (kAccHereMax .. kAccNoticeMax of fanout.hip, pinned by a host
+#: test): ``letmein``'s line to the asker's room, a 12-byte name, `` shouts asking to be let into the ``, a 20-byte room name
+#: and ``.\n``; its line to the other room; the too-few notice with ten digits; the invitation, a name, `` has invited you
+#: into the ``, a room name and ``.\n``
+MAX_ACCESS_HERE, MAX_ACCESS_THERE, MAX_ACCESS_REPLY, MAX_ACCESS_NOTICE = (USER_NAME_LEN + 34 + ROOM_NAME_LEN + 2, USER_NAME_LEN + 29,
+                                                                         18 + 10 + 55, USER_NAME_LEN + 26 + ROOM_NAME_LEN + 2)
+#: their slots among an access call's texts (kAccHereRow .. kAccNoticeRow), laid out as _GO_ROWS lays a go call's
+_ACCESS_ROWS = (72, 44, 84, 60)
+#: the texts of an event in an Access, in that order: the two room lines first, then the two single-recipient texts
+ACCESS_HERE, ACCESS_THERE, ACCESS_REPLY, ACCESS_NOTICE = range(4)
 #: a look room's row of the names relay_many uploads (kRelayNameRow of fanout.hip): 20 bytes of name padded with zeros, then
 #: its length; and what a relay text is longer than its broadcast at most, ``~FT[ `` + a 20-byte name + `` ]:~RS ``
 #: (kRelaySlack): its slot among a relay call's relay texts is that much wider than the text
@@ -851,6 +881,56 @@ class Go:
 
 
 @dataclass
+class Access:
+    """What ``set_room_access()``, ``letmein()`` and ``invite()`` write for K events (``Roster.access_many``), shaped like a
+    :class:`Go`.  ``outcome[k]`` is one of the ACCESS_* constants; ``target_room[k]`` the room the event is about -- the
+    actor's own for a ``.public`` / ``.private`` without a word, else the room the word resolved to -- or -1 when
+    ``get_room`` found none or was not reached (an ``.invite`` never asks it: its room is the actor's); ``target_slot[k]``
+    the slot ``get_user`` found, or -1 when it found none or was not reached.  ``reply`` plans the actor's own line,
+    ``here`` the line the actor's room gets without the actor, ``there`` the line another room gets, ``notice`` the line
+    an invited user gets, whatever its ``ignall``, ``afk`` and room.  They are ordinary plans over the roster as it was
+    before the call and share one variant buffer; a text that is not there has size -1, nobody admitted and both
+    variants 0 bytes in 0 writes.  An ACCESS_DEFERRED event has no text at all, and its targets are what the roster
+    before the call gives.
+
+    Delivery, per client: the events in call order, and of one event the reply, the here or the there line, the notice
+    (the reference's order of writes).  A roster with clone records passes the two room lines through ``relay_many``."""
+    outcome: np.ndarray           # int8 [K]
+    target_room: np.ndarray       # int32 [K]
+    target_slot: np.ndarray       # int32 [K]
+    reply: Plan
+    here: Plan
+    there: Plan
+    notice: Plan
+    texts: np.ndarray             # uint8, flat: the composed texts; gaps are allowed and unspecified
+    text_starts: np.ndarray       # int64 [4, K]   rows ACCESS_HERE, ACCESS_THERE, ACCESS_REPLY, ACCESS_NOTICE
+    text_sizes: np.ndarray        # int64 [4, K]   -1: there is no such text
+    timing: dict = field(default_factory=dict)
+
+    _text = Speech._text
+
+    def reply_text(self, k: int) -> bytes:
+        """The line event ``k`` sends to its actor; ``b""`` for a deferred event."""
+        return self._text(ACCESS_REPLY, k)
+
+    def here_text(self, k: int) -> bytes:
+        """The line event ``k`` sends to its actor's room without the actor; ``b""`` when there is none."""
+        return self._text(ACCESS_HERE, k)
+
+    def there_text(self, k: int) -> bytes:
+        """The line event ``k`` sends to another room; ``b""`` when there is none."""
+        return self._text(ACCESS_THERE, k)
+
+    def notice_text(self, k: int) -> bytes:
+        """The line event ``k`` sends to the user it invited; ``b""`` when it invited nobody."""
+        return self._text(ACCESS_NOTICE, k)
+
+    def effective(self) -> np.ndarray:
+        """The events that set an access or invited someone, ascending."""
+        return np.flatnonzero((self.outcome >= 0) & (self.outcome <= ACCESS_INVITED))
+
+
+@dataclass
 class Input:
     """What ``user_input()`` and ``exec_com()`` make of K reads (``Roster.input_many``).  ``kind[k]`` is IAC, EMPTY,
     REPEAT, UNKNOWN, SPEECH or COMMAND; ``com[k]`` the command (enum np_com) of a SPEECH or COMMAND read, else -1;
@@ -1084,6 +1164,9 @@ def _load():
         lib.nd_roster_go.argtypes = ([ctypes.c_int, ctypes.c_int, P, ctypes.c_int64, P, P, P, P, ctypes.c_int, ctypes.c_int] + [P] * 16
                                      + [ctypes.POINTER(_RosterTiming)])
         lib.nd_roster_go.restype = ctypes.c_int
+        lib.nd_roster_access.argtypes = ([ctypes.c_int, ctypes.c_int, P, ctypes.c_int64, P, P, P, P, P, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int] + [P] * 15 + [ctypes.POINTER(_RosterTiming)])
+        lib.nd_roster_access.restype = ctypes.c_int
         lib.nd_roster_clones.argtypes = [ctypes.c_int, ctypes.c_int]
         lib.nd_roster_clones.restype = ctypes.c_int
         lib.nd_roster_relay.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int64] + [P] * 22 + [ctypes.POINTER(_RosterTiming)]
@@ -2548,8 +2631,9 @@ class Roster:
         the go mirror as well.
 
         Out of scope: ``.move`` (teleport 2); the netlink branch and the ``remote_com == GO`` release, which the caller does
-        before it submits; remote users; ``.private``, ``.public``, ``.invite`` and ``.letmein`` themselves -- the caller sets
-        ``set_rooms(access=)`` and ``update(invite_room=)``; the prompt; fusing the look into the first device visit;
+        before it submits; remote users; ``.private``, ``.public``, ``.invite`` and ``.letmein`` themselves -- they are
+        :meth:`access_many`'s, which keeps ``access`` and ``invite_room`` for this call; the prompt; fusing the look into the
+        first device visit;
         applying the moves by a kernel.  ``go_many`` does not relay to clones' owners."""
         self._check_open()
         text, text_off, lens, slots, wcs = self._prepare_go(events, gatecrash_level, min_private_users)
@@ -2625,6 +2709,167 @@ class Roster:
             if len(rings):
                 self.clear_review(rings)
         return go
+
+    def _prepare_access(self, events, gatecrash_level, min_private_users, ignore_mp_level):
+        """Each (slot, com, inpstr, word_count) and its actor's state checked, packed for nd_roster_access: the inpstr, their
+        offsets and lengths, the slots, the commands and the word counts."""
+        if isinstance(events, (str, bytes, bytearray, np.ndarray)) or not hasattr(events, "__len__"):
+            raise ValueError(f"events must be a sequence of tuples, not {type(events).__name__}")
+        if len(events) == 0:
+            raise ValueError("empty call: no events")
+        if not _is_int(gatecrash_level, 0, MAX_LEVEL):
+            raise ValueError(f"gatecrash_level must be an int in [0, {MAX_LEVEL}] (enum np_level), not {gatecrash_level!r}")
+        if not _is_int(min_private_users, 0, 2**31 - 1):
+            raise ValueError(f"min_private_users must be an int in [0, 2^31), not {min_private_users!r}")
+        if not _is_int(ignore_mp_level, 0, MAX_LEVEL + 1):
+            raise ValueError(f"ignore_mp_level must be an int in [0, {MAX_LEVEL + 1}], not {ignore_mp_level!r}")
+        if self.look_rooms < 1:
+            raise ValueError("the roster has no room records (look_rooms is 0): there is no room to set or to be let into")
+        if len(events) * self.capacity >= 2**31 - 1:
+            raise ValueError(f"{len(events)} events to {self.capacity} slots: K x capacity must be below 2^31 - 1")
+        bound = _variant_at(sum(_ACCESS_ROWS) * len(events), 4 * len(events))
+        if bound > MANY_ARENA_CAP:
+            raise ValueError(f"call too large: its variant bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
+                             f"(MANY_ARENA_CAP): split it")
+        texts, slots, coms, wcs = [], [], [], []
+        for k, ev in enumerate(events):
+            if not isinstance(ev, tuple) or len(ev) != 4:
+                raise ValueError(f"event {k}: expected a (slot, com, inpstr, word_count) tuple, "
+                                 f"got {type(ev).__name__}{f' of {len(ev)}' if isinstance(ev, tuple) else ''}")
+            slot, com, inpstr, wc = ev
+            try:
+                slot = self._slot(slot)
+                if not _is_int(com, COM_PUBLIC, COM_INVITE):
+                    raise ValueError(f"com must be COM_PUBLIC, COM_PRIVATE, COM_LETMEIN or COM_INVITE ({COM_PUBLIC} .. {COM_INVITE}), "
+                                     f"not {com!r}")
+                text = _as_text(inpstr)
+                if len(text) >= ARR_SIZE:
+                    raise ValueError(f"inpstr of {len(text)} bytes: the talker's input line holds at most {ARR_SIZE - 1}")
+                if not _is_int(wc, 0, MAX_WORDS):
+                    raise ValueError(f"word_count must be an int in [0, {MAX_WORDS}], not {wc!r}")
+                if not 0 <= self._room[slot] < self.look_rooms:
+                    raise ValueError(f"the actor, slot {slot}, is in " + (f"room {int(self._room[slot])}, which has no room record"
+                                     if self._room[slot] >= 0 else "no room") + f" (look_rooms is {self.look_rooms})")
+                if self._flags[slot] & ROSTER_FLAGS["login"]:
+                    raise ValueError(f"the actor, slot {slot}, is still logging in")
+                if self._speech[slot, USER_NAME_LEN] == 0:
+                    raise ValueError(f"the actor, slot {slot}, has no name")
+            except ValueError as e:
+                raise ValueError(f"event {k}: {e}") from None
+            texts.append(text)
+            slots.append(slot)
+            coms.append(int(com))
+            wcs.append(int(wc))
+        lens = np.fromiter((len(t) for t in texts), dtype=np.int64, count=len(texts))
+        if int(lens.sum()) >= 2**31 // 32:
+            raise ValueError("call text larger than 64 MiB: split it")
+        return (b"".join(texts), _offsets(lens, np.int32), lens.astype(np.int32), np.array(slots, dtype=np.int32),
+                np.array(coms, dtype=np.uint8), np.array(wcs, dtype=np.uint8))
+
+    def access_many(self, events, *, gatecrash_level, min_private_users, ignore_mp_level) -> Access:
+        """K ``.public`` / ``.private`` / ``.letmein`` / ``.invite`` events, decided and composed on the device: a non-empty
+        sequence of ``(slot, com, inpstr, word_count)`` tuples, what a COMMAND read of :meth:`input_many` hands back, with
+        ``com`` COM_PUBLIC, COM_PRIVATE, COM_LETMEIN or COM_INVITE (``set_room_access``, ``letmein`` and ``invite``,
+        nuts333.c:4543-4693).  ``gatecrash_level`` is an int in [0, MAX_LEVEL], ``min_private_users`` an int >= 0 and
+        ``ignore_mp_level`` an int in [0, MAX_LEVEL + 1], the talker's three settings.  The roster needs ``look_rooms >= 1``;
+        every actor needs a room in ``[0, look_rooms)``, a name and no ``login`` flag; a slot may appear more than once.
+        Anything else raises ``ValueError("event k: ...")`` before the device is touched, and a call whose variant bound
+        exceeds MANY_ARENA_CAP is refused.
+
+        The device does, per event and in the reference's order, with ``word[1]`` the first word of ``inpstr`` as
+        :meth:`go_many` takes it.  ``.public`` and ``.private``: the room is the actor's own when ``word_count < 2``; else
+        ACCESS_LOW_LEVEL below ``gatecrash_level``, and ``get_room`` as :meth:`go_many` runs it, else ACCESS_NO_ROOM.  Then
+        ACCESS_FIXED if ``access > PRIVATE``; ACCESS_ALREADY_PUBLIC; ACCESS_ALREADY_PRIVATE; ACCESS_TOO_FEW if the room holds
+        fewer than ``min_private_users`` -- the slots with that room, a name and no ``login`` flag, the actor among them,
+        and the clone records standing there -- and the actor's level is below ``ignore_mp_level``; else ACCESS_SET_PRIVATE
+        or ACCESS_SET_PUBLIC: ``reply`` is ``"Room set to ...\\n"``, and the actor's own room gets ``here`` without the
+        actor, ``"<name> has set the room to ...\\n"`` with ``invisname`` for an invisible actor, any other room gets
+        ``there``, ``"This room has been set to ...\\n"``.  The refusals say "This room" of the actor's own room and "That
+        room" of another.  ``.letmein``: ACCESS_LET_WHERE if ``word_count < 2``; ``get_room``, else ACCESS_LET_NO_ROOM;
+        ACCESS_LET_ALREADY; ACCESS_LET_NOT_ADJOINED if the room is not among the links of the actor's, whatever its level;
+        ACCESS_LET_PUBLIC unless ``access & PRIVATE``; else ACCESS_ASKED: the reply, ``here`` to the actor's room and
+        ``there`` to the room asked, both with the asker's own name even when it is invisible.  ``.invite``:
+        ACCESS_INVITE_WHO if ``word_count < 2``; ACCESS_INVITE_PUBLIC unless the actor's room has ``access & PRIVATE``;
+        ``get_user`` as :meth:`tell_many` runs it over the word with its first byte capitalised, else ACCESS_INVITE_NOBODY;
+        ACCESS_INVITE_SELF; ACCESS_INVITE_HERE; ACCESS_INVITE_ALREADY if the user's ``invite_room`` is this room; else
+        ACCESS_INVITED: the reply, and ``notice`` to the invited slot alone, ``"<name> has invited you into the
+        <room>.\\n"``.  The room lines' ``com_num`` is the event's ``com``.
+
+        Every event is decided and planned against the roster as it was before the call.  To keep that exact, an event is
+        ACCESS_DEFERRED when an earlier event of the same call that was not itself deferred touched its actor's room, the
+        room its word resolved to or the slot ``get_user`` found: it wrote nothing and changed nothing, and the caller
+        submits it again.  ACCESS_SET_PRIVATE and ACCESS_SET_PUBLIC touch the room whose access changes, ACCESS_INVITED
+        touches the invited slot; nothing else touches anything, so a repeated actor alone defers nothing, and a call of
+        one event never defers.
+
+        The binding then applies the result to the host mirrors in event order, through :meth:`set_rooms`, :meth:`update`
+        and :meth:`clear_review`: a room set private gets ``access=PRIVATE``; a room set public gets ``access=PUBLIC``,
+        every slot invited into it loses its ``invite_room`` and its review ring, when it has one, is emptied
+        (nuts333.c:4605-4611); an invited slot gets the actor's room as ``invite_room``.  No kernel writes a kept table: a
+        following :meth:`go_many`, :meth:`look_many` or :meth:`review_many` uploads what changed and sees the new state.
+
+        A call is one upload (the table, the speaker state, the clone records, the room table and the go mirror only
+        after an update of theirs), three kernel launches (ACCESS_KERNELS, then nuts_roster_speak_plan), one download at
+        the bound size and one synchronise, whatever K and the capacity.  Returns an :class:`Access`.
+
+        Out of scope: ``.topic``; ``.move``; the relay of the two room lines to clones' owners -- the caller passes them
+        to :meth:`relay_many`, as after :meth:`go_many`; remote users; the prompt."""
+        self._check_open()
+        text, text_off, lens, slots, coms, wcs = self._prepare_access(events, gatecrash_level, min_private_users, ignore_mp_level)
+        lib = _load()
+        handle = self._device_handle(lib)
+        k, words = len(lens), (self.capacity + 63) // 64
+        ctext_bytes = sum(_ACCESS_ROWS) * k
+        outcome, target_room, target_slot = np.empty(k, dtype=np.int8), np.empty(k, dtype=np.int32), np.empty(k, dtype=np.int32)
+        clen = np.empty((4, k), dtype=np.int32)
+        bits = np.zeros((4, k, words), dtype=np.uint64)            # the device's two, then the actor alone and the invited alone
+        vn, vw = np.empty((4, k, 2), dtype=np.int64), np.empty((4, k, 2), dtype=np.int32)
+        vwsz = np.empty((4, k, 2, MAX_WRITES), dtype=np.int32)
+        ctext = np.empty(ctext_bytes, dtype=np.uint8)
+        var = np.empty(_variant_at(ctext_bytes, 4 * k), dtype=np.uint8)
+        tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
+        t = _RosterTiming()
+        rc = lib.nd_roster_access(handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(slots), _ptr(coms), _ptr(wcs),
+                                  int(gatecrash_level), int(min_private_users), int(ignore_mp_level),
+                                  _ptr(self._table) if self._dirty else None, _ptr(self._speech) if self._speech_dirty else None,
+                                  _ptr(self._clones) if self._clones_dirty and self.clones else None,
+                                  _ptr(self._rooms) if self._rooms_dirty else None, _ptr(self._go) if self._go_dirty else None,
+                                  _ptr(outcome), _ptr(target_room), _ptr(target_slot), _ptr(clen), _ptr(bits), _ptr(vn), _ptr(vw),
+                                  _ptr(vwsz), _ptr(ctext), _ptr(var), ctypes.byref(t))
+        _check(rc, "device access failed")
+        self._private_dirty &= not self._speech_dirty         # the whole speaker mirror went up, or none of it
+        self._dirty = self._speech_dirty = self._rooms_dirty = self._go_dirty = False
+        if self.clones:
+            self._clones_dirty = False
+        rows = np.array(_ACCESS_ROWS, dtype=np.int64)
+        tstarts = ((np.cumsum(rows) - rows) * k)[:, None] + rows[:, None] * np.arange(k, dtype=np.int64)
+        starts = _variant_starts(tstarts, clen)
+        has = np.flatnonzero(clen[ACCESS_REPLY] >= 0)
+        bits[ACCESS_REPLY, has, slots[has] // 64] = np.uint64(1) << (slots[has] % 64).astype(np.uint64)
+        has = np.flatnonzero(clen[ACCESS_NOTICE] >= 0)          # write_user(u, text): ignall, afk and the room play no part
+        bits[ACCESS_NOTICE, has, target_slot[has] // 64] = np.uint64(1) << (target_slot[has] % 64).astype(np.uint64)
+        timing = _timing_of(t)
+        colour_bits = _pack((self._flags & ROSTER_FLAGS["colour"]) != 0)
+        plans = [Plan(capacity=self.capacity, admitted_bits=bits[i], colour_bits=colour_bits, variants=var,
+                      variant_starts=starts[i], variant_sizes=vn[i], write_counts=vw[i], write_sizes=vwsz[i],
+                      timing=dict(timing)) for i in range(4)]
+        access = Access(outcome=outcome, target_room=target_room, target_slot=target_slot, reply=plans[ACCESS_REPLY],
+                        here=plans[ACCESS_HERE], there=plans[ACCESS_THERE], notice=plans[ACCESS_NOTICE], texts=ctext,
+                        text_starts=tstarts, text_sizes=clen.astype(np.int64), timing=timing)
+        # the changes, on the host mirrors and in event order: the next call of any kind uploads what it reads
+        for k in access.effective().tolist():
+            if outcome[k] == ACCESS_INVITED:
+                self.update(int(target_slot[k]), invite_room=int(self._room[slots[k]]))
+                continue
+            rm = int(target_room[k])
+            self.set_rooms(rm, access=PRIVATE if outcome[k] == ACCESS_SET_PRIVATE else PUBLIC)
+            if outcome[k] == ACCESS_SET_PUBLIC:
+                invited = np.flatnonzero(self._go_invite == rm)
+                if len(invited):
+                    self.update(invited, invite_room=None)
+                if rm < self.review_rooms:
+                    self.clear_review([rm])
+        return access
 
     def set_clones(self, clones, *, owner=_KEEP, room=_KEEP, hear=_KEEP) -> None:
         """Set fields of the clone records ``clones`` (a record or a sequence of them, each in ``[0, clones)``), by the

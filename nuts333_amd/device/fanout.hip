@@ -1544,6 +1544,55 @@ __device__ __forceinline__ void name_match(uint64_t lo, uint32_t hi, int nlen, u
     *sub = any;
 }
 
+// A word's first 12 bytes packed as a name is, the first one capitalised (get_user c:2366, pemote c:4243).
+struct NameWord {
+    uint64_t lo;
+    uint32_t hi;
+};
+__device__ __forceinline__ NameWord pack_word(const uint8_t* word, int wlen)
+{
+    NameWord w{0, 0};
+#pragma unroll
+    for (int i = 0; i < kNameLen; i++) {
+        uint64_t c = i < wlen ? word[i] : 0;
+        if (i == 0 && c >= 'a' && c <= 'z') c -= 32;
+        if (i < 8) w.lo |= c << (8 * i);
+        else w.hi |= (uint32_t)c << (8 * (i - 8));
+    }
+    return w;
+}
+
+// get_user (c:2362-2379) for one wave of a block: its lowest exact match and its lowest substring match among the slots
+// 64 wave + 256 i + lane that have a name and no login flag; kNoMatch where there is none.  A wave that has an exact match
+// stops: a substring match no longer matters.  Wave-uniform; the block's waves meet in LDS.
+struct UserMatch {
+    int exact, sub;
+};
+__device__ __forceinline__ UserMatch wave_get_user(const uint8_t* speech, const uint8_t* slotf, int capacity, NameWord w, int wlen,
+                                                   int wave, int lane)
+{
+    UserMatch best{kNoMatch, kNoMatch};
+    if (wlen <= kNameLen) {
+        for (int base = 64 * wave; base < capacity; base += kBlock) {
+            const int j = base + lane;
+            bool exact = false, sub = false;
+            if (j < capacity && !(slotf[j] & kLogin)) {
+                const uint4 rec = reinterpret_cast<const uint4*>(speech)[j];
+                const int jl = (int)(rec.w & 0xff) < kNameLen ? (int)(rec.w & 0xff) : kNameLen;
+                if (jl > 0) name_match(rec.x | (uint64_t)rec.y << 32, rec.z, jl, w.lo, w.hi, wlen, &exact, &sub);
+            }
+            const uint64_t be = __ballot(exact);
+            if (be) {
+                best.exact = base + __ffsll((unsigned long long)be) - 1;
+                break;
+            }
+            const uint64_t bs = __ballot(sub);
+            if (bs && best.sub == kNoMatch) best.sub = base + __ffsll((unsigned long long)bs) - 1;
+        }
+    }
+    return best;
+}
+
 __device__ void roster_tell(const TellArgs& a)
 {
     if ((int)blockIdx.x >= a.k) {           // the tables just uploaded, into the kept allocations: a word per lane
@@ -1571,15 +1620,9 @@ __device__ void roster_tell(const TellArgs& a)
     const int w0_end = first_from(~wordb & 0xffffu, w0, lane, len);                // <= len: the byte at len is no word byte
     const int rest = first_from(wordb, w0_end, lane, len);
     const int wlen = w0_end - w0 < kWordLen ? w0_end - w0 : kWordLen;
-    uint64_t wlo = 0;
-    uint32_t whi = 0;
-#pragma unroll
-    for (int i = 0; i < kNameLen; i++) {
-        uint64_t c = i < wlen ? in[w0 + i] : 0;
-        if (i == 0 && c >= 'a' && c <= 'z') c -= 32;                               // get_user c:2366, pemote c:4243
-        if (i < 8) wlo |= c << (8 * i);
-        else whi |= (uint32_t)c << (8 * (i - 8));
-    }
+    const NameWord nw = pack_word(in + w0, wlen);
+    const uint64_t wlo = nw.lo;
+    const uint32_t whi = nw.hi;
 
     // what comes before get_user, in the reference's order (tell c:4133-4140, pemote c:4235-4247); block-uniform
     int outcome = kTold;
@@ -1594,23 +1637,10 @@ __device__ void roster_tell(const TellArgs& a)
 
     // get_user: this wave's lowest exact match and lowest substring match among its slots, 64 w + 256 i + lane
     int best_exact = kNoMatch, best_sub = kNoMatch;
-    if (outcome == kTold && wlen <= kNameLen) {
-        for (int base = 64 * wave; base < a.capacity; base += kBlock) {            // wave-uniform
-            const int j = base + lane;
-            bool exact = false, sub = false;
-            if (j < a.capacity && !(a.slotf[j] & kLogin)) {
-                const uint4 rec = reinterpret_cast<const uint4*>(a.speech)[j];
-                const int jl = (int)(rec.w & 0xff) < kNameLen ? (int)(rec.w & 0xff) : kNameLen;
-                if (jl > 0) name_match(rec.x | (uint64_t)rec.y << 32, rec.z, jl, wlo, whi, wlen, &exact, &sub);
-            }
-            const uint64_t be = __ballot(exact);
-            if (be) {
-                best_exact = base + __ffsll((unsigned long long)be) - 1;
-                break;                      // a substring match no longer matters
-            }
-            const uint64_t bs = __ballot(sub);
-            if (bs && best_sub == kNoMatch) best_sub = base + __ffsll((unsigned long long)bs) - 1;
-        }
+    if (outcome == kTold) {
+        const UserMatch m = wave_get_user(a.speech, a.slotf, a.capacity, nw, wlen, wave, lane);
+        best_exact = m.exact;
+        best_sub = m.sub;
     }
     if (lane == 0) {
         s_exact[wave] = best_exact;
@@ -2706,6 +2736,26 @@ __device__ __forceinline__ bool begins_with(const uint8_t* s, int slen, const ui
     return __ballot(differs) == 0;
 }
 
+// get_room (c:2388-2389) for one wave of a block: its lowest room among 64 wave + 256 i + lane that has a name beginning
+// with the word, or kNoMatch.  Wave-uniform; the block's waves meet in LDS.
+__device__ __forceinline__ int wave_get_room(const uint8_t* rooms, int look_rooms, const uint8_t* word, int wlen, int wave, int lane)
+{
+    if (wlen > kRoomNameLen) return kNoMatch;
+    for (int base = 64 * wave; base < look_rooms; base += kBlock) {
+        const int r = base + lane;
+        bool hit = false;
+        if (r < look_rooms) {
+            const uint8_t* rec = rooms + (size_t)r * kRoomRec;
+            const int rl = rec[kRrNameLen] < kRoomNameLen ? rec[kRrNameLen] : kRoomNameLen;
+            hit = rl > 0 && wlen <= rl;                     // a room without a name is no room
+            for (int i = 0; i < wlen && hit; i++) hit = rec[i] == word[i];
+        }
+        const uint64_t b = __ballot(hit);
+        if (b) return base + __ffsll((unsigned long long)b) - 1;
+    }
+    return kNoMatch;
+}
+
 __device__ void roster_go(const GoArgs& a)
 {
     if ((int)blockIdx.x >= a.k) {           // the tables just uploaded, into the kept allocations: a word per lane
@@ -2746,24 +2796,7 @@ __device__ void roster_go(const GoArgs& a)
     }
 
     // get_room (c:2388-2389): this wave's lowest room that has a name beginning with the word, among 64 w + 256 i + lane
-    int best = kNoMatch;
-    if (outcome < 0 && wlen <= kRoomNameLen) {
-        for (int base = 64 * wave; base < a.look_rooms; base += kBlock) {          // wave-uniform
-            const int r = base + lane;
-            bool hit = false;
-            if (r < a.look_rooms) {
-                const uint8_t* rec = a.rooms + (size_t)r * kRoomRec;
-                const int rl = rec[kRrNameLen] < kRoomNameLen ? rec[kRrNameLen] : kRoomNameLen;
-                hit = rl > 0 && wlen <= rl;                 // a room without a name is no room
-                for (int i = 0; i < wlen && hit; i++) hit = rec[i] == word[i];
-            }
-            const uint64_t b = __ballot(hit);
-            if (b) {
-                best = base + __ffsll((unsigned long long)b) - 1;
-                break;
-            }
-        }
-    }
+    int best = outcome < 0 ? wave_get_room(a.rooms, a.look_rooms, word, wlen, wave, lane) : kNoMatch;
     if (lane == 0) s_room[wave] = best;
     __syncthreads();
     for (int w = 0; w < kBlock / 64; w++) best = s_room[w] < best ? s_room[w] : best;
@@ -2941,6 +2974,373 @@ __device__ void roster_go_order(const GoOrderArgs& a)
 
 static_assert(kMaxLookRooms % 32 == 0 && kGoMaxSlots % 32 == 0, "roster_go_order: the bitmaps are whole words");
 
+// ------------------------------------------------------------------ a room's door, of a resident roster
+//
+// set_room_access(), letmein() and invite() (nuts333.c:4543-4693): .public, .private, .letmein and .invite, commands 16 to
+// 19.  As with go(), the device decides and composes and writes no kept table; the host binding sets the access and the
+// invitations in its mirrors afterwards.  It reads the five tables nuts_roster_go reads.
+// An event has four texts in slots of fixed width: the line the actor's room gets without the actor ("here"), the line
+// another room gets ("there"), the actor's own line ("reply") and the line an invited user gets ("notice").  With K events,
+// text k is event k's here line, K + k its there line, 2K + k its reply and 3K + k its notice: the 2K room lines first, as
+// nuts_roster_speak_plan wants them.
+//   access   nuts_roster_access, ONE BLOCK PER EVENT, in the shape of nuts_roster_go.  word[1] is found as there.  By the
+//            command the block runs get_user over the capitalised word (wave_get_user; first, while little else is
+//            live: the search needs the most registers), get_room (wave_get_room), and for a .private that reaches the
+//            count (c:4583-4584) the head-count of the room: a lane per slot (that room, a name, no login flag; the actor
+//            counts) and a lane per clone record standing there, ballots summed per wave.  The waves' results meet in
+//            LDS.  Wave 0 decides in the reference's order and composes: the actor's line from kAccReply, two fixed parts
+//            per outcome around a name or the count, the other three texts with compose() / append().  Lane 0 stores the lengths, the outcome, the room and the slot the word resolved to, and rm / sender / com of
+//            the two room lines: the here line to the actor's room with the actor as sender, the there line to the other
+//            room without one.  No atomics: the same bytes on every run.
+//            Blocks past the events copy freshly uploaded tables into the kept allocations.
+//   order    nuts_roster_access_order, ONE WAVE, after nuts_roster_go_order.  Set private and set public touch the room
+//            whose access changes, invited touches the invited slot.  An event whose actor's room, resolved room or found
+//            slot an earlier event of the call that was not itself deferred touched is deferred: its outcome becomes
+//            kAccDeferred and its four texts void.
+//   plan     nuts_roster_speak_plan with 2K room lines and 2K single-recipient texts.
+constexpr int kComPublic = 16, kComPrivate = 17, kComLetmein = 18, kComInvite = 19;        // enum np_com
+constexpr int kAccSetPrivate = 0, kAccSetPublic = 1, kAccInvited = 2, kAccAsked = 3, kAccLowLevel = 4, kAccNoRoom = 5, kAccFixed = 6,
+              kAccAlreadyPublic = 7, kAccAlreadyPrivate = 8, kAccTooFew = 9, kAccLetWhere = 10, kAccLetNoRoom = 11, kAccLetAlready = 12,
+              kAccLetNotAdjoined = 13, kAccLetPublic = 14, kAccInviteWho = 15, kAccInvitePublic = 16, kAccInviteNobody = 17,
+              kAccInviteSelf = 18, kAccInviteHere = 19, kAccInviteAlready = 20, kAccDeferred = 21;
+constexpr int kAccTexts = 4;                               // here, there, reply, notice
+// the longest texts: name + " shouts asking to be let into the " + room name + ".\n"; name + " shouts asking to be let in.\n";
+// "You need at least " + ten digits + " users/clones in a room before it can be made private.\n"; name + " has invited you
+// into the " + room name + ".\n"
+constexpr int kAccHereMax = kNameLen + 34 + kRoomNameLen + 2, kAccThereMax = kNameLen + 29, kAccReplyMax = 18 + 10 + 55,
+              kAccNoticeMax = kNameLen + 26 + kRoomNameLen + 2;
+constexpr int kAccHereRow = 72, kAccThereRow = 44, kAccReplyRow = 84, kAccNoticeRow = 60;  // their slots
+constexpr int kAccRow = kAccHereRow + kAccThereRow + kAccReplyRow + kAccNoticeRow;         // an event's bytes of composed text
+constexpr int acc_row(int kind) { return kind == 0 ? kAccHereRow : kind == 1 ? kAccThereRow : kind == 2 ? kAccReplyRow : kAccNoticeRow; }
+// Where text kind * k + b of a call of k events has its slot: the here lines, then the there lines, the replies, the notices.
+constexpr int64_t acc_text_at(int kind, int64_t b, int64_t k)
+{
+    return (kind == 0 ? 0 : kind == 1 ? kAccHereRow : kind == 2 ? kAccHereRow + kAccThereRow : kAccHereRow + kAccThereRow + kAccReplyRow) * k
+           + acc_row(kind) * b;
+}
+
+// The actor's own line by outcome (c:4555-4687, nuts333.h:145-146): two fixed parts, around the room, a name or the count.
+struct AccessReply {
+    char pre[63];
+    uint8_t npre;
+    char post[63];
+    uint8_t npost;
+};
+template <int N, int M>
+constexpr AccessReply access_reply(const char (&pre)[N], const char (&post)[M])
+{
+    static_assert(N <= 64 && M <= 64, "access_reply: a part fits its field, and a compose()");
+    AccessReply r{};
+    for (int i = 0; i < N - 1; i++) r.pre[i] = pre[i];
+    for (int i = 0; i < M - 1; i++) r.post[i] = post[i];
+    r.npre = N - 1;
+    r.npost = M - 1;
+    return r;
+}
+__device__ const AccessReply kAccReply[] = {
+    access_reply("Room set to ~FRPRIVATE.\n", ""),                                        // kAccSetPrivate
+    access_reply("Room set to ~FGPUBLIC.\n", ""),                                         // kAccSetPublic
+    access_reply("You invite ", " in.\n"),                                                // kAccInvited
+    access_reply("You shout asking to be let into the ", ".\n"),                          // kAccAsked
+    access_reply("You are not a high enough level to use the room option.\n", ""),        // kAccLowLevel
+    access_reply("There is no such room.\n", ""),                                         // kAccNoRoom
+    access_reply("", "'s access is fixed.\n"),                                            // kAccFixed
+    access_reply("", " is already public.\n"),                                            // kAccAlreadyPublic
+    access_reply("", " is already private.\n"),                                           // kAccAlreadyPrivate
+    access_reply("You need at least ", " users/clones in a room before it can be made private.\n"),      // kAccTooFew
+    access_reply("Let you into where?\n", ""),                                            // kAccLetWhere
+    access_reply("There is no such room.\n", ""),                                         // kAccLetNoRoom
+    access_reply("You are already in the ", "!\n"),                                       // kAccLetAlready
+    access_reply("The ", " is not adjoined to here.\n"),                                  // kAccLetNotAdjoined
+    access_reply("The ", " is currently public.\n"),                                      // kAccLetPublic
+    access_reply("Invite who?\n", ""),                                                    // kAccInviteWho
+    access_reply("This room is currently public.\n", ""),                                 // kAccInvitePublic
+    access_reply("There is no one of that name logged on.\n", ""),                        // kAccInviteNobody
+    access_reply("Inviting yourself to somewhere is the third sign of madness.\n", ""),   // kAccInviteSelf
+    access_reply("", " is already here!\n"),                                              // kAccInviteHere
+    access_reply("", " has already been invited into here.\n"),                           // kAccInviteAlready
+};
+static_assert(sizeof(kAccReply) / sizeof(kAccReply[0]) == kAccDeferred, "kAccReply: a line for every outcome nuts_roster_access decides");
+
+struct AccessArgs {
+    const int32_t* room;         // [capacity] the roster's table
+    const uint8_t* slotf;        // [capacity] and its flag bytes: login
+    const uint8_t* speech;       // the tables this call reads, the uploads or the kept ones: the speaker state (name, vis, level),
+    const uint8_t* records;      // the clone records as take_clones lays them out (nullptr: the roster has none),
+    const uint8_t* rooms;        // the room records,
+    const uint8_t* go;           // [capacity * 88] and the go table: invite_room
+    Kept kept[4];                // the speaker state, the clone records, the go table, the room records
+    const uint8_t* text;         // the K inpstr, packed
+    const int32_t* text_off;     // [k]
+    const int32_t* text_len;     // [k]
+    const int32_t* slot;         // [k] the actor
+    const uint8_t* com;          // [k] NP_PUBLIC, NP_PRIVATE, NP_LETMEIN or NP_INVITE
+    const uint8_t* words;        // [k] word_count
+    const int32_t* ctext_off;    // [4k] where each text's slot starts in ctext
+    int k, capacity, look_rooms, clones, gatecrash_level, min_private_users, ignore_mp_level;
+    int* violations;             // composed texts past their slot (zeroed by the host's upload)
+    uint8_t* ctext;              // the composed texts
+    int32_t* clen;               // [4k] their lengths; -1: no such text
+    int8_t* outcome;             // [k]
+    int32_t* target_room;        // [k] the room the event is about; -1: none, or the step was not reached
+    int32_t* target_slot;        // [k] the slot get_user found; -1: none, or it was not asked
+    int32_t* rm;                 // [2k] the room lines' rooms, as SpeakPlanArgs.rm
+    int32_t* sender;             // [2k] and their senders (-1: none)
+    int32_t* com_num;            // [2k]
+};
+
+__device__ void roster_access(const AccessArgs& a)
+{
+    if ((int)blockIdx.x >= a.k) {           // the tables just uploaded, into the kept allocations: a word per lane
+        copy_kept(a.kept, ((int)blockIdx.x - a.k) * kBlock + (int)threadIdx.x);
+        return;
+    }
+    __shared__ int s_room[kBlock / 64], s_pop[kBlock / 64], s_exact[kBlock / 64], s_sub[kBlock / 64];
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int k = (int)blockIdx.x;
+    const int slot = a.slot[k], com = a.com[k], wc = a.words[k], len = a.text_len[k];
+    const uint8_t* in = a.text + a.text_off[k];
+    const int level = a.speech[(size_t)slot * kSpeechRec + kLevelByte];
+    const int here = a.room[slot];          // a look room: the host checked it
+    const bool setting = com == kComPublic || com == kComPrivate;
+
+    // word[1] as np_wordfind finds the line's second word (c:417-432): inpstr has lost the first
+    uint32_t wordb = 0;
+#pragma unroll
+    for (int x = 0; x < kReadSlice; x++) {
+        const int at = kReadSlice * lane + x;
+        wordb |= (uint32_t)(at < len && (int8_t)in[at] > 32) << x;
+    }
+    const int w0 = first_from(wordb, 0, lane, len);
+    const int w0_end = first_from(~wordb & 0xffffu, w0, lane, len);
+    const int wlen = w0_end - w0 < kWordLen ? w0_end - w0 : kWordLen;
+    const uint8_t* word = in + w0;
+
+    // what comes before get_room and get_user (c:4552-4557, 4622-4624, 4662-4669); block-uniform
+    int outcome = -1, rm = -1;
+    bool want_room = false;
+    if (setting) {
+        if (wc < 2) rm = here;
+        else if (level < a.gatecrash_level) outcome = kAccLowLevel;
+        else want_room = true;
+    } else if (com == kComLetmein) {
+        if (wc < 2) outcome = kAccLetWhere;
+        else want_room = true;
+    } else if (wc < 2) outcome = kAccInviteWho;
+    else if (!(a.rooms[(size_t)here * kRoomRec + kRrAccess] & kAccessPrivate)) outcome = kAccInvitePublic;
+
+    // get_user over the capitalised word (c:4670), before anything else is kept: the search is what needs registers most
+    int best_exact = kNoMatch, best_sub = kNoMatch;
+    if (com == kComInvite && outcome < 0) {
+        const UserMatch m = wave_get_user(a.speech, a.slotf, a.capacity, pack_word(word, wlen), wlen, wave, lane);
+        best_exact = m.exact;
+        best_sub = m.sub;
+    }
+
+    int best = want_room ? wave_get_room(a.rooms, a.look_rooms, word, wlen, wave, lane) : kNoMatch;
+    if (lane == 0) s_room[wave] = best;
+    __syncthreads();
+    for (int w = 0; w < kBlock / 64; w++) best = s_room[w] < best ? s_room[w] : best;
+    if (want_room) {
+        if (best == kNoMatch) outcome = setting ? kAccNoRoom : kAccLetNoRoom;
+        else rm = best;
+    }
+
+    // the head-count of a room that could become private (c:4583-4584)
+    int cnt = 0;
+    if (com == kComPrivate && outcome < 0 && a.rooms[(size_t)rm * kRoomRec + kRrAccess] == 0) {       // block-uniform
+        for (int base = 0; base < a.capacity; base += kBlock) {
+            const int j = base + (int)threadIdx.x;
+            const bool in_room = j < a.capacity && a.room[j] == rm && !(a.slotf[j] & kLogin) &&
+                                 a.speech[(size_t)j * kSpeechRec + kNameLen] != 0;
+            cnt += __popcll(__ballot(in_room));
+        }
+        if (a.records) {                                    // clones count (c:4584 walks the whole user list)
+            const size_t slice = ((size_t)a.clones * sizeof(int32_t) + 255) & ~(size_t)255;
+            const int32_t* owner = reinterpret_cast<const int32_t*>(a.records);
+            const int32_t* croom = reinterpret_cast<const int32_t*>(a.records + slice);
+            for (int base = 0; base < a.clones; base += kBlock) {
+                const int c = base + (int)threadIdx.x;
+                const bool in_room = c < a.clones && owner[c] >= 0 && croom[c] == rm;
+                cnt += __popcll(__ballot(in_room));
+            }
+        }
+    }
+    if (lane == 0) {
+        s_pop[wave] = cnt;
+        s_exact[wave] = best_exact;
+        s_sub[wave] = best_sub;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    cnt = 0;
+    for (int w = 0; w < kBlock / 64; w++) {
+        cnt += s_pop[w];
+        best_exact = s_exact[w] < best_exact ? s_exact[w] : best_exact;
+        best_sub = s_sub[w] < best_sub ? s_sub[w] : best_sub;
+    }
+
+    // the three functions' decisions, in their order
+    const uint8_t* sp = a.speech + (size_t)slot * kSpeechRec;
+    const uint8_t* hrec = a.rooms + (size_t)here * kRoomRec;
+    const uint8_t* rrec = a.rooms + (size_t)(rm < 0 ? here : rm) * kRoomRec;
+    const uint8_t access = rrec[kRrAccess];
+    int target = -1;
+    if (outcome < 0 && setting) {           // c:4563-4605
+        if (access > kAccessPrivate) outcome = kAccFixed;
+        else if (com == kComPublic) outcome = access == 0 ? kAccAlreadyPublic : kAccSetPublic;
+        else if (access == kAccessPrivate) outcome = kAccAlreadyPrivate;
+        else outcome = cnt < a.min_private_users && level < a.ignore_mp_level ? kAccTooFew : kAccSetPrivate;
+    } else if (outcome < 0 && com == kComLetmein) {         // c:4628-4645
+        bool linked = false;
+        const int nlinks = hrec[kRrLinks] < kMaxLinks ? hrec[kRrLinks] : kMaxLinks;
+        const int32_t* link = reinterpret_cast<const int32_t*>(hrec + kRrLink);
+        for (int i = 0; i < nlinks; i++) linked |= link[i] == rm;
+        outcome = rm == here ? kAccLetAlready : !linked ? kAccLetNotAdjoined : !(access & kAccessPrivate) ? kAccLetPublic : kAccAsked;
+    } else if (outcome < 0) {               // c:4670-4687
+        target = best_exact != kNoMatch ? best_exact : best_sub != kNoMatch ? best_sub : -1;
+        if (target < 0) outcome = kAccInviteNobody;
+        else if (target == slot) outcome = kAccInviteSelf;
+        else if (a.room[target] == here) outcome = kAccInviteHere;
+        else if (*reinterpret_cast<const int32_t*>(a.go + (size_t)target * kGoRec + kGoInvite) == here) outcome = kAccInviteAlready;
+        else outcome = kAccInvited;
+    }
+
+    const int n = a.k;
+    uint8_t* here_t = a.ctext + a.ctext_off[k];
+    uint8_t* there_t = a.ctext + a.ctext_off[n + k];
+    uint8_t* reply_t = a.ctext + a.ctext_off[2 * n + k];
+    uint8_t* notice_t = a.ctext + a.ctext_off[3 * n + k];
+    const Piece none{nullptr, 0};
+    const Piece name{sp, sp[kNameLen] < kNameLen ? sp[kNameLen] : kNameLen};
+    const Piece shown = (sp[kNameLen + 1] & kVis) ? name : lit("A presence");
+    const Piece rname{rrec, rrec[kRrNameLen] < kRoomNameLen ? rrec[kRrNameLen] : kRoomNameLen};
+    const uint8_t* tp = a.speech + (size_t)(target < 0 ? slot : target) * kSpeechRec;
+    const Piece tname{tp, tp[kNameLen] < kNameLen ? tp[kNameLen] : kNameLen};
+    const bool mine = rm == here;
+    int here_len = -1, there_len = -1, reply_len = 0, notice_len = -1;
+    // the actor's line: the outcome's two fixed parts around the room ("This room" or "That room" where set_room_access
+    // refuses), the room's name, the found user's name or the count
+    {
+        const AccessReply& fixed = kAccReply[outcome];
+        const uint8_t* mid = nullptr;
+        int nmid = 0;
+        if (outcome >= kAccFixed && outcome <= kAccAlreadyPrivate) {
+            mid = reinterpret_cast<const uint8_t*>(mine ? "This room" : "That room");
+            nmid = 9;
+        } else if (outcome == kAccAsked || (outcome >= kAccLetAlready && outcome <= kAccLetPublic)) {
+            mid = rname.p;
+            nmid = rname.n;
+        } else if (outcome == kAccInvited || outcome >= kAccInviteHere) {
+            mid = tname.p;
+            nmid = tname.n;
+        }
+        const Piece pre[5] = {Piece{reinterpret_cast<const uint8_t*>(fixed.pre), fixed.npre}, none, none, none, none};
+        const Piece m[5] = {Piece{mid, nmid}, none, none, none, none};
+        const Piece post[5] = {Piece{reinterpret_cast<const uint8_t*>(fixed.post), fixed.npost}, none, none, none, none};
+        append(reply_t, kAccReplyRow, reply_len, pre, nullptr, 0, false, lane, a.violations);
+        if (outcome == kAccTooFew) append_count(reply_t, kAccReplyRow, reply_len, a.min_private_users, lane, a.violations);   // c:4586
+        else append(reply_t, kAccReplyRow, reply_len, m, nullptr, 0, false, lane, a.violations);
+        append(reply_t, kAccReplyRow, reply_len, post, nullptr, 0, false, lane, a.violations);
+    }
+    if (outcome == kAccSetPrivate || outcome == kAccSetPublic) {       // c:4591-4595, 4600-4604
+        const Piece to = outcome == kAccSetPrivate ? lit("~FRPRIVATE.\n") : lit("~FGPUBLIC.\n");
+        if (mine) {
+            const Piece h[5] = {shown, lit(" has set the room to "), to, none, none};
+            here_len = compose(here_t, kAccHereRow, h, nullptr, 0, false, lane, a.violations);
+        } else {
+            const Piece t[5] = {lit("This room has been set to "), to, none, none, none};
+            there_len = compose(there_t, kAccThereRow, t, nullptr, 0, false, lane, a.violations);
+        }
+        if (here_len < 0 && there_len < 0) reply_len = -1;
+    } else if (outcome == kAccAsked) {      // c:4647-4650: user->name, even of an invisible asker
+        const Piece h0[5] = {name, lit(" shouts asking to be let into the "), none, none, none};
+        const Piece h1[5] = {rname, lit(".\n"), none, none, none};
+        const Piece t[5] = {name, lit(" shouts asking to be let in.\n"), none, none, none};
+        here_len = 0;
+        append(here_t, kAccHereRow, here_len, h0, nullptr, 0, false, lane, a.violations);
+        append(here_t, kAccHereRow, here_len, h1, nullptr, 0, false, lane, a.violations);
+        there_len = compose(there_t, kAccThereRow, t, nullptr, 0, false, lane, a.violations);
+    } else if (outcome == kAccInvited) {    // c:4689-4691
+        const Piece v[5] = {shown, lit(" has invited you into the "), rname, lit(".\n"), none};
+        notice_len = compose(notice_t, kAccNoticeRow, v, nullptr, 0, false, lane, a.violations);
+    }
+    if (reply_len < 0 || (outcome == kAccAsked && (here_len < 0 || there_len < 0)) || (outcome == kAccInvited && notice_len < 0))
+        here_len = there_len = reply_len = notice_len = -1;            // a violation: the call fails
+    if (lane == 0) {
+        a.clen[k] = here_len;
+        a.clen[n + k] = there_len;
+        a.clen[2 * n + k] = reply_len;
+        a.clen[3 * n + k] = notice_len;
+        a.outcome[k] = (int8_t)outcome;
+        a.target_room[k] = rm;
+        a.target_slot[k] = target;
+        a.rm[k] = here;                     // write_room_except(user->room, text, user)
+        a.sender[k] = slot;
+        a.rm[n + k] = rm < 0 ? here : rm;   // write_room(rm, text): nobody is excepted
+        a.sender[n + k] = -1;
+        a.com_num[k] = a.com_num[n + k] = com;
+    }
+}
+
+static_assert(kAccHereMax == 68 && kAccThereMax == 41 && kAccReplyMax == 83 && kAccNoticeMax == 60 && kAccHereMax <= kAccHereRow &&
+              kAccThereMax <= kAccThereRow && kAccReplyMax <= kAccReplyRow && kAccNoticeMax <= kAccNoticeRow,
+              "roster_access: the longest texts fit their slots");
+static_assert(sizeof(" shouts asking to be let into the ") - 1 == 34 && sizeof(" shouts asking to be let in.\n") - 1 == 29 &&
+              sizeof("You need at least ") - 1 == 18 && sizeof(" users/clones in a room before it can be made private.\n") - 1 == 55 &&
+              sizeof(" has invited you into the ") - 1 == 26 && kNameLen + sizeof(" has set the room to ~FRPRIVATE.\n") - 1 <= kAccHereMax &&
+              sizeof("This room has been set to ~FRPRIVATE.\n") - 1 <= kAccThereMax &&
+              sizeof("You shout asking to be let into the .\n") - 1 + kRoomNameLen <= kAccReplyMax &&
+              sizeof("Inviting yourself to somewhere is the third sign of madness.\n") - 1 <= kAccReplyMax &&
+              kNameLen + sizeof(" has already been invited into here.\n") - 1 <= kAccReplyMax, "roster_access: the texts are as long as counted");
+static_assert(kAccRow % 4 == 0 && kAccHereRow % 4 == 0 && kAccThereRow % 4 == 0 && kAccReplyRow % 4 == 0 && kAccReplyRow < kTextSize,
+              "roster_access: the rows are whole words, and a text fits speak_plan's LDS text");
+static_assert(sizeof("You shout asking to be let into the .\n") - 1 + kRoomNameLen <= 64 && kAccNoticeMax <= 64 &&
+              sizeof("Inviting yourself to somewhere is the third sign of madness.\n") - 1 <= 64, "roster_access: the pieces of a compose() fit a wave");
+
+struct AccessOrderArgs {
+    const int32_t* room;         // [capacity] the roster's table: the actors' rooms
+    const int32_t* slot;         // [k] the actors
+    const int32_t* target_room;  // [k] what nuts_roster_access wrote
+    const int32_t* target_slot;  // [k]
+    int k;
+    int8_t* outcome;             // [k] becomes kAccDeferred for a deferred event
+    int32_t* clen;               // [4k] whose four texts become void
+};
+
+__device__ void roster_access_order(const AccessOrderArgs& a)
+{
+    __shared__ uint32_t s_rooms[kMaxLookRooms / 32], s_slots[kGoMaxSlots / 32];
+    const int lane = (int)threadIdx.x;      // one wave
+    for (int i = lane; i < kMaxLookRooms / 32; i += 64) s_rooms[i] = 0;
+    for (int i = lane; i < kGoMaxSlots / 32; i += 64) s_slots[i] = 0;
+    __syncthreads();
+    for (int base = 0; base < a.k; base += 64) {
+        const int k = base + lane;
+        const bool live = k < a.k;
+        const int here = live ? a.room[a.slot[k]] : 0, trm = live ? a.target_room[k] : -1, tsl = live ? a.target_slot[k] : -1;
+        const int out = live ? a.outcome[k] : kAccLetWhere;
+        const int count = a.k - base < 64 ? a.k - base : 64;
+        bool defer = false;
+        for (int i = 0; i < count; i++) {   // in call order; every lane follows, lane 0 sets the bits
+            const int h = __shfl(here, i), r = __shfl(trm, i), s = __shfl(tsl, i), oc = __shfl(out, i);
+            const bool hit = ((s_rooms[h >> 5] >> (h & 31)) & 1u) || (r >= 0 && ((s_rooms[r >> 5] >> (r & 31)) & 1u)) ||
+                             (s >= 0 && ((s_slots[s >> 5] >> (s & 31)) & 1u));
+            if (lane == i) defer = hit;
+            __syncthreads();
+            if (lane == 0 && !hit) {        // setting an access touches the room, an invitation the invited slot
+                if (oc == kAccSetPrivate || oc == kAccSetPublic) s_rooms[r >> 5] |= 1u << (r & 31);
+                else if (oc == kAccInvited) s_slots[s >> 5] |= 1u << (s & 31);
+            }
+            __syncthreads();
+        }
+        if (live && defer) {
+            a.outcome[k] = (int8_t)kAccDeferred;
+            a.clen[k] = a.clen[a.k + k] = a.clen[2 * a.k + k] = a.clen[3 * a.k + k] = -1;
+        }
+    }
+}
+
 }  // namespace
 
 // Stable, unmangled kernel names (they are what rocprofv3 reports).
@@ -2969,6 +3369,8 @@ extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_rooms_count(Roo
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_rooms_lines(RoomsArgs a) { roster_rooms_lines(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_go(GoArgs a) { roster_go(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_go_order(GoOrderArgs a) { roster_go_order(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_access(AccessArgs a) { roster_access(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_access_order(AccessOrderArgs a) { roster_access_order(a); }
 
 // ------------------------------------------------------------------------------------------ host library
 
@@ -3605,6 +4007,53 @@ size_t layout_go(uintptr_t base, size_t text_bytes, GoArgs& s, SpeakPlanArgs& p)
     take(s.rm, 3 * k);
     take(s.sender, 3 * k);
     take(s.com_num, 3 * k);
+    p.room = s.room;
+    p.slot = s.slotf;
+    p.text = s.ctext;
+    p.text_off = s.ctext_off;
+    p.text_len = s.clen;
+    p.rm = s.rm;
+    p.sender = s.sender;
+    p.com_num = s.com_num;
+    p.violations = s.violations;
+    return take.at;
+}
+
+// nd_roster_access's layout of a roster's allocation: layout_go's, with the events' commands, the two targets, and p planning
+// 2k room lines and 2k single-recipient texts.  Of the uploads the room table lies last and the go table before it: the
+// call's own aftermath changes an access more often than an invitation, and an upload runs from the first table given to
+// the end of the inputs.
+size_t layout_access(uintptr_t base, size_t text_bytes, AccessArgs& s, SpeakPlanArgs& p)
+{
+    Carver take{base};
+    const size_t k = (size_t)s.k, t = kAccTexts * k;
+    const size_t ctext_bytes = (size_t)kAccRow * k;
+    take_table(take, s.capacity, s.room, s.slotf);
+    take_kept(take, s.kept[0], kKeptSpeech, s.capacity);
+    take_kept(take, s.kept[1], kKeptClones, s.capacity, s.look_rooms, s.clones);
+    take_kept(take, s.kept[2], kKeptGo, s.capacity);
+    take_kept(take, s.kept[3], kKeptRooms, s.capacity, s.look_rooms);     // last: a set access alone uploads nothing else
+    take(s.text, text_bytes);
+    take(s.text_off, k);
+    take(s.text_len, k);
+    take(s.slot, k);
+    take(s.com, k);
+    take(s.words, k);
+    take(s.ctext_off, t);
+    take(s.violations, 1);
+    take(s.outcome, k);
+    take(s.target_room, k);
+    take(s.target_slot, k);
+    take(s.clen, t);
+    take(p.vn, 2 * t);
+    take(p.vw, 2 * t);
+    take(p.vwsz, 2 * t * kMaxWrites);
+    take(p.bits, 2 * k * (size_t)p.words);
+    take(s.ctext, ctext_bytes);
+    take(p.var, (size_t)var_at((int64_t)ctext_bytes, (int64_t)t));
+    take(s.rm, 2 * k);
+    take(s.sender, 2 * k);
+    take(s.com_num, 2 * k);
     p.room = s.room;
     p.slot = s.slotf;
     p.text = s.ctext;
@@ -5325,6 +5774,136 @@ int nd_roster_go(int handle, int k, const uint8_t* text, int64_t text_bytes, con
     memcpy(vw, res(po.vw), 2 * texts * sizeof(int32_t));
     memcpy(vwsz, res(po.vwsz), 2 * texts * kMaxWrites * sizeof(int32_t));
     memcpy(bits, res(po.bits), 3 * (size_t)k * nwords * sizeof(uint64_t));
+    memcpy(ctext, res(so.ctext), ctext_bytes);
+    memcpy(var, res(po.var), var_bytes);
+
+    return fill_timing(timing, t0, t1, h2d, res_bytes);
+}
+
+// K .public / .private / .letmein / .invite events of roster `handle`, decided and composed as set_room_access(), letmein()
+// and invite() do, against the tables as they are: nothing the roster keeps is changed, the caller sets the access and the
+// invitations.  Event b: the actor's slot slots[b], which stands in a look room, coms[b] (16 .. 19), inpstr and words[b] as
+// nd_roster_go's.  gatecrash_level (0 .. 4), min_private_users (>= 0) and ignore_mp_level (0 .. 5) are the talker's.  The five
+// tables are nd_roster_go's, NULL when unchanged since this roster's last call that took them.
+// Outputs (host, caller-allocated), with W = ceil(capacity / 64) and text t = b for event b's here line, k + b its there
+// line, 2k + b its reply, 3k + b its notice: outcome[k] (0 set private, 1 set public, 2 invited, 3 asked, 4 .. 20 the
+// refusals in the order of kAccLowLevel .. kAccInviteAlready, 21 deferred); target_room[k] and target_slot[k], or -1;
+// clen[4k], -1 where there is no text; ctext[260 k], the here lines at 72 b, the there lines at 72 k + 44 b, the replies at
+// 116 k + 84 b, the notices at 200 k + 60 b; bits[2k * W] the admit bitmaps of the here and the there lines; vn[8k], vw[8k],
+// vwsz[8k * 16] and var[12 * 260 k + 64 k] as nd_roster_speak's.
+// Per call, whatever k and the capacity: one upload, three kernels (nuts_roster_access, nuts_roster_access_order,
+// nuts_roster_speak_plan), one download at the bound size, one synchronise.  Returns 0, or -1 with nd_last_error() set.
+int nd_roster_access(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off, const int32_t* text_len,
+                     const int32_t* slots, const uint8_t* coms, const uint8_t* words, int gatecrash_level, int min_private_users,
+                     int ignore_mp_level, const uint8_t* table, const uint8_t* speech, const uint8_t* clones, const uint8_t* rooms,
+                     const uint8_t* go, int8_t* outcome, int32_t* target_room, int32_t* target_slot, int32_t* clen, uint64_t* bits,
+                     int64_t* vn, int32_t* vw, int32_t* vwsz, uint8_t* ctext, uint8_t* var, nd_roster_timing* timing)
+{
+    Roster* r = roster_at(handle);
+    if (!r || ensure_ready()) return -1;
+    const int cap = r->capacity, nwords = (cap + 63) / 64, nrooms = r->look_rooms;
+    if (k < 1 || (int64_t)k * cap >= INT32_MAX || (int64_t)k * kAccRow >= INT32_MAX / 16 || text_bytes < 0 ||
+        text_bytes >= INT32_MAX / 32 || nrooms < 1 || nrooms > kMaxLookRooms || gatecrash_level < 0 || gatecrash_level > kGod ||
+        min_private_users < 0 || ignore_mp_level < 0 || ignore_mp_level > kGod + 1) {
+        snprintf(g_err, sizeof(g_err), "%d events to %d slots over %d look rooms: need 1 <= k * capacity < 2^31 - 1, a look room, a "
+                 "gatecrash level in 0 .. %d, a minimum of private users >= 0 and an ignore level in 0 .. %d", k, cap, nrooms, kGod, kGod + 1);
+        return -1;
+    }
+    int64_t sum = 0;
+    for (int b = 0; b < k; b++) {       // the kernels index by these: nothing out of range reaches them
+        if (slots[b] < 0 || slots[b] >= cap || text_len[b] < 0 || text_len[b] >= kArrSize || text_off[b] != sum ||
+            coms[b] < kComPublic || coms[b] > kComInvite) {
+            snprintf(g_err, sizeof(g_err), "event %d: slot, command, text length or text offset out of range", b);
+            return -1;
+        }
+        sum += text_len[b];
+    }
+    if (sum != text_bytes) {
+        snprintf(g_err, sizeof(g_err), "the events' texts hold %lld bytes, not %lld", (long long)sum, (long long)text_bytes);
+        return -1;
+    }
+    AccessArgs s{};
+    const Given given[] = {{kKeptSpeech, speech, &s.speech}, {kKeptClones, clones, &s.records}, {kKeptGo, go, &s.go},
+                           {kKeptRooms, rooms, &s.rooms}};
+    if (check_given(*r, given, "the roster's first access call must give the speaker table, the clone records, the room table and the go table"))
+        return -1;
+    const double t0 = now_ns();
+    hipStream_t st = g.stream;
+    SpeakPlanArgs p{};
+    s.k = k;
+    p.k = 2 * k;
+    s.capacity = p.capacity = cap;
+    s.look_rooms = nrooms;
+    s.clones = r->clones;
+    s.gatecrash_level = gatecrash_level;
+    s.min_private_users = min_private_users;
+    s.ignore_mp_level = ignore_mp_level;
+    p.tiles = (cap + kBlock - 1) / kBlock;
+    p.words = nwords;
+    const size_t texts = (size_t)kAccTexts * k, ctext_bytes = (size_t)kAccRow * k;
+    const size_t var_bytes = (size_t)var_at((int64_t)ctext_bytes, (int64_t)texts);
+    AccessArgs so = s;                  // offsets of every array in the roster's allocation
+    SpeakPlanArgs po = p;
+    const size_t need = layout_access(0, (size_t)text_bytes, so, po);
+    const size_t table_bytes = (uintptr_t)so.kept[0].fresh, tables_end = (uintptr_t)so.text;
+    const size_t in_bytes = (uintptr_t)so.violations + sizeof(int);
+    const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
+    if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
+    if (table) new_table(*r, so.room, so.slotf, table);
+    const int32_t* room = reinterpret_cast<const int32_t*>(r->mirror + (uintptr_t)so.room);
+    for (int b = 0; b < k; b++)         // nuts_roster_access reads its actor's room record
+        if (room[slots[b]] < 0 || room[slots[b]] >= nrooms) {
+            snprintf(g_err, sizeof(g_err), "event %d: the actor's room has no room record", b);
+            return -1;
+        }
+    if (grow_roster(*r, need)) return -1;
+    layout_access((uintptr_t)r->d, (size_t)text_bytes, s, p);
+    if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
+
+    uint8_t* h = r->mirror;
+    const Put put{h};
+    put(so.text, text, (size_t)text_bytes);
+    put(so.text_off, text_off, (size_t)k * sizeof(int32_t));
+    put(so.text_len, text_len, (size_t)k * sizeof(int32_t));
+    put(so.slot, slots, (size_t)k * sizeof(int32_t));
+    put(so.com, coms, (size_t)k);
+    put(so.words, words, (size_t)k);
+    int32_t* coff = reinterpret_cast<int32_t*>(h + (uintptr_t)so.ctext_off);
+    for (int kind = 0; kind < kAccTexts; kind++)
+        for (int b = 0; b < k; b++) coff[(size_t)kind * k + b] = (int32_t)acc_text_at(kind, b, k);
+    *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
+    // the tables' uploads lie between the table and the inputs
+    size_t first = 0, h2d = 0;
+    unsigned copy_blocks = 0;
+    if (pass_kept(*r, given, so.kept, s.kept, tables_end, &first, &copy_blocks)) return -1;
+    if (upload(*r, table_bytes, first, in_bytes, &h2d)) return -1;
+
+    const AccessOrderArgs order{s.room, s.slot, s.target_room, s.target_slot, k, s.outcome, s.clen};
+    ND_CHECK(hipEventRecord(g.ev0, st));
+    hipLaunchKernelGGL(nuts_roster_access, dim3((unsigned)k + copy_blocks), dim3(kBlock), 0, st, s);
+    ND_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(nuts_roster_access_order, dim3(1), dim3(64), 0, st, order);
+    ND_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)(2 * k * p.tiles + 2 * k)), dim3(kBlock), 0, st, p);
+    ND_CHECK(hipGetLastError());
+    if (fetch_results(r->d, res_at, res_bytes)) return -1;
+    const double t1 = now_ns();
+
+    const Res res{gm.res, res_at};
+    const int violations = *reinterpret_cast<const int*>(res(so.violations));
+    if (violations) {
+        snprintf(g_err, sizeof(g_err), "%d text(s) exceeded the hard bounds (a text its slot; 6*len+4 bytes, %d writes transduced)",
+                 violations, kMaxWrites);
+        return -1;
+    }
+    memcpy(outcome, res(so.outcome), (size_t)k);
+    memcpy(target_room, res(so.target_room), (size_t)k * sizeof(int32_t));
+    memcpy(target_slot, res(so.target_slot), (size_t)k * sizeof(int32_t));
+    memcpy(clen, res(so.clen), texts * sizeof(int32_t));
+    memcpy(vn, res(po.vn), 2 * texts * sizeof(int64_t));
+    memcpy(vw, res(po.vw), 2 * texts * sizeof(int32_t));
+    memcpy(vwsz, res(po.vwsz), 2 * texts * kMaxWrites * sizeof(int32_t));
+    memcpy(bits, res(po.bits), 2 * (size_t)k * nwords * sizeof(uint64_t));
     memcpy(ctext, res(so.ctext), ctext_bytes);
     memcpy(var, res(po.var), var_bytes);
 

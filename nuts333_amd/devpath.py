@@ -3,7 +3,7 @@
     python -m nuts333_amd.devpath [--reps R] [--warmup W] [--pathbench-iterations I] [--per-call K[,K...]]
                                   [--roster K[,K...]] [--plan K[,K...]] [--review Q[,Q...]] [--speak K[,K...]]
                                   [--input K[,K...]] [--tell K[,K...]] [--look K[,K...]] [--relay K[,K...]] [--go K[,K...]]
-                                  [--who K[,K...]] [--rooms K[,K...]]   -> one JSON line
+                                  [--who K[,K...]] [--rooms K[,K...]] [--access K[,K...]]   -> one JSON line
 
 For N in {10, 100, 1000} listeners, the two texts oracle/pathbench.c times (``say``; ``shout`` carrying ``~OL``/``~RS``)
 and colour all-off / all-on / half, one ``nuts333_amd.device.broadcast`` per repetition (listener 0 is the sender, the
@@ -97,6 +97,15 @@ the same composed lines, then ``look_many`` of the same movers, which is what a 
 the CPU composing the strings in Python and transducing them.  Six rooms hold at most three disjoint walks, so of K = 8 or
 64 events most are deferred: ``moved`` and ``deferred`` say how many.  The first call of each case is checked against the
 reference's formats and the CPU's transducer over ``look()``'s strings.
+
+``--access K[,K...]`` adds ``access``: a 1000-slot roster of USERs over the six default rooms, and K ``.private`` events per
+``Roster.access_many`` call, each by an actor in its own room (``access_actors``: the first three stand in the three rooms
+that can be set), then K ``.public`` events by the same actors in the next call, so that the state is periodic and every
+call sets an access: the three times and the copy volume of the ``.private`` call (``public`` has the other's), beside
+``plan`` -- ``plan_many`` of the lines the ``.private`` call composes, composed beforehand, in the same rounds -- and
+``cpu_us``, the CPU modelling the call in Python and transducing the lines through ctypes.  Three rooms can be set, three
+are fixed, so of K = 8 or 64 events most are refused or deferred: ``set``, ``refused`` and ``deferred`` say how many.  Both
+calls of each case are checked first against the model, the reference's formats and the CPU's transducer.
 """
 from __future__ import annotations
 
@@ -909,6 +918,114 @@ def go_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
             "go": cases}
 
 
+_ACCESS_TO = {device.COM_PRIVATE: (b"~FRPRIVATE", device.PRIVATE, device.ACCESS_SET_PRIVATE, device.ACCESS_ALREADY_PRIVATE, b"private"),
+              device.COM_PUBLIC: (b"~FGPUBLIC", device.PUBLIC, device.ACCESS_SET_PUBLIC, device.ACCESS_ALREADY_PUBLIC, b"public")}
+
+
+def access_actors(k: int, n: int) -> list[int]:
+    """The actors of ``access_cases``: slot 3 + j stands in room (3 + j) % 6, so the first three stand in the rooms that can
+    be set -- the corridor, the lounge, the shop -- the next three in the fixed ones, and the seventh in the corridor again."""
+    return [(3 + j) % n for j in range(k)]
+
+
+def access_model(accesses: list, room_of: np.ndarray, events) -> list[tuple]:
+    """What access_many answers for ``.private`` and ``.public`` events without a word at the roster ``access_cases`` builds,
+    where every room holds more users than ``min_private_users``: per event ``(outcome, room, reply, here line)``.  The
+    changes are applied to ``accesses``."""
+    touched, out = set(), []
+    for slot, com, _inpstr, _wc in events:
+        rm = int(room_of[slot])
+        word, to, done, already, name = _ACCESS_TO[com]
+        if rm in touched:
+            out.append((device.ACCESS_DEFERRED, rm, None, None))
+        elif accesses[rm] > device.PRIVATE:
+            out.append((device.ACCESS_FIXED, rm, b"This room's access is fixed.\n", None))
+        elif accesses[rm] == to:
+            out.append((already, rm, b"This room is already %s.\n" % name, None))
+        else:
+            out.append((done, rm, b"Room set to %s.\n" % word, b"User%d has set the room to %s.\n" % (slot, word)))
+            accesses[rm] = to
+            touched.add(rm)
+    return out
+
+
+def access_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
+    """The ``access`` section: access_many of K ``.private`` events (``access_actors``, each in its own room) at a 1000-slot
+    roster over the six default rooms, and of K ``.public`` events by the same actors in the next call, so that the state is
+    periodic and every call sets an access; beside plan_many of the lines the ``.private`` call composes, composed
+    beforehand, and the CPU modelling the call in Python and transducing the lines."""
+    n = 1000
+    names, accesses = ROOMS_LISTS["6"]
+    nr = len(names)
+    cases = []
+    for colour in COLOURS:
+        with device.Roster(n, look_rooms=nr) as roster:
+            col = colours(n, colour)
+            room_of = np.arange(n) % nr
+            roster.update(range(n), room=room_of.tolist(), colour=col, name=[b"User%d" % j for j in range(n)], level=1)
+            roster.set_rooms(list(range(nr)), name=names, access=accesses, links=[list(l) for l in GO_LINKS])
+            settings = {"gatecrash_level": 3, "min_private_users": 2, "ignore_mp_level": 2}
+            for k in ks:
+                actors = access_actors(k, n)
+                private = [(j, device.COM_PRIVATE, b"", 1) for j in actors]
+                public = [(j, device.COM_PUBLIC, b"", 1) for j in actors]
+                state = list(accesses)
+                want_private = access_model(state, room_of, private)
+                first = roster.access_many(private, **settings)
+                want_public = access_model(state, room_of, public)
+                second = roster.access_many(public, **settings)
+                for label, got, want in (("private", first, want_private), ("public", second, want_public)):
+                    if got.outcome.tolist() != [w[0] for w in want] or any(
+                            got.target_room[i] != w[1] for i, w in enumerate(want) if w[0] != device.ACCESS_DEFERRED):
+                        raise SystemExit(f"devpath: access {k}, {colour}: the device's outcomes of the .{label} call differ from the model's")
+                    for i, w in enumerate(want):
+                        if (got.reply_text(i), got.here_text(i)) != tuple(x or b"" for x in w[2:]):
+                            raise SystemExit(f"devpath: access {k}, {colour}: event {i}'s texts differ from the reference's formats")
+                        j = actors[i]
+                        if w[3] and got.here.chunks(i, int(col[j])) != nuts_path.chunks(w[3], int(col[j])):
+                            raise SystemExit(f"devpath: access {k}, {colour}: event {i}'s line differs from the CPU's transducer")
+                if state != list(accesses) or roster._room_rec[:nr, 21].tolist() != list(accesses):
+                    raise SystemExit(f"devpath: access {k}, {colour}: the .public call does not end where the .private call began")
+                lines = [(w[3], w[1], j, 0, device.COM_PRIVATE) for j, w in zip(actors, want_private) if w[3]]
+                lines += [(w[2], None, None, 0, device.COM_PRIVATE) for w in want_private if w[2]]
+
+                def cpu():
+                    for w in access_model(list(accesses), room_of, private):
+                        for text in w[2:]:
+                            if text:
+                                nuts_path.chunks(text, 0)
+                                nuts_path.chunks(text, 1)
+
+                timed = _timed(f"access {k}, {colour}", {"private": lambda: roster.access_many(private, **settings),
+                                                         "public": lambda: roster.access_many(public, **settings),
+                                                         "plan": lambda: roster.plan_many(lines), "cpu": cpu}, reps, warmup)
+                dev, cpu_us = timed["private"], timed["cpu"].host_us
+                count = lambda want, whats: sum(w[0] in whats for w in want)
+                sets = (device.ACCESS_SET_PRIVATE, device.ACCESS_SET_PUBLIC)
+                refusals = (device.ACCESS_FIXED, device.ACCESS_ALREADY_PRIVATE, device.ACCESS_ALREADY_PUBLIC)
+                cases.append({"n": n, "k": k, "colour": colour, "rooms": nr, "set": count(want_private, sets),
+                              "refused": count(want_private, refusals), "deferred": count(want_private, (device.ACCESS_DEFERRED,)),
+                              "public_set": count(want_public, sets), "public_refused": count(want_public, refusals),
+                              "public_deferred": count(want_public, (device.ACCESS_DEFERRED,)), "lines": len(lines),
+                              **dev.fields, "cpu_us": cpu_us, "public": timed["public"].fields, "plan": timed["plan"].fields,
+                              "access_over_plan": {f: round(dev.times[f]["median"] / timed["plan"].times[f]["median"], 2) for f in FIELDS},
+                              "end_to_end_over_cpu": float(f"{dev.times['end_to_end_us']['median'] / cpu_us['median']:.3g}")})
+    return {"access_kernels": list(device.ACCESS_KERNELS) + ["nuts_roster_speak_plan"],
+            "access_end_to_end_covers": "packing the K events into pinned memory, one H2D (the events, and the room table, which "
+                                        "the call before changed: 1,072 bytes a room), three kernels -- get_room, get_user or "
+                                        "the head-count of the room, the decision chain and the texts; the deferral walk; both "
+                                        "variants of every text and the room lines' admit bitmaps --, one D2H at the bound size, "
+                                        "one synchronise (python_us adds checking the events, the copies out of pinned memory, "
+                                        "building the Access and applying it to the host mirrors through set_rooms)",
+            "access_plan_covers": "plan_many of the lines the .private call composes -- the room lines, then the actors' own -- "
+                                  "composed beforehand, at the same roster, in the same rounds; it uploads no table",
+            "access_cpu_us_covers": "the model of the .private call in Python -- the deferral rule and the reference's formats, "
+                                    "interpreted, without the head-count, which every room of this roster passes -- and "
+                                    "np_write_user_stream of the CPU restatement (nuts_path, through ctypes) over both variants "
+                                    "of every line",
+            "access": cases}
+
+
 RELAY_CLONES = 64
 
 
@@ -1039,6 +1156,9 @@ SECTIONS = (
     ("go", "K[,K...]", "also time K walks per Roster.go_many call at a 1000-slot roster over the six default rooms, there and "
                        "back, for each K, beside plan_many and look_many of the same lines and movers and the CPU composing "
                        "and transducing the strings (the go section)", "go_cases"),
+    ("access", "K[,K...]", "also time K .private events per Roster.access_many call at a 1000-slot roster over the six default "
+                           "rooms, and K .public events in the next, for each K, beside plan_many of the same lines and the CPU "
+                           "modelling the call and transducing the lines (the access section)", "access_cases"),
 )
 
 
