@@ -77,6 +77,12 @@ state ``.go`` decides by, a room's ``access`` and a user's ``invite_room``: K ``
 (nuts333.c:4543-4693) -- an :class:`Access`.  The device runs ``get_room``, ``get_user`` and the head-count of a room, decides
 and composes the actor's line, the two room lines and the invitation, with their plans; an event that an earlier one of the
 same call touched is deferred; the binding sets the access and the invitations in the host mirrors.
+``Roster.clone_many(events, max_clones=, gatecrash_level=, min_private_users=)`` answers what changes the clone records those
+calls read: K ``(slot, com, inpstr, word_count)`` events with ``com`` COM_CLONE, COM_DESTROY, COM_CSAY or COM_CHEAR, as
+``create_clone()``, ``destroy_clone()``, ``clone_say()`` and ``clone_hear()`` do (nuts333.c:7100-7210, 7293-7357) -- a
+:class:`Clone`.  The device runs ``get_room``, ``get_user``, a walk of the records and the head-count of a room a destroyed
+clone leaves, decides and composes the six texts with their plans; an event whose owner or room an earlier one of the same
+call touched is deferred; the binding creates, destroys and sets the records in the host mirrors and keeps them in list order.
 
 Input is validated before the device is touched (``ValueError``).  The library ``_build/libnuts_device.so`` is built by
 ``__graft_entry__.build()`` where ``hipcc`` exists, and on demand here when it is missing or older than its source.
@@ -302,6 +308,33 @@ MAX_ACCESS_HERE, MAX_ACCESS_THERE, MAX_ACCESS_REPLY, MAX_ACCESS_NOTICE = (USER_N
 _ACCESS_ROWS = (72, 44, 84, 60)
 #: the texts of an event in an Access, in that order: the two room lines first, then the two single-recipient texts
 ACCESS_HERE, ACCESS_THERE, ACCESS_REPLY, ACCESS_NOTICE = range(4)
+#: ``.clone``, ``.destroy``, ``.csay`` and ``.chear`` (NP_CLONE, NP_DESTROY, NP_CSAY, NP_CHEAR), and the kernels clone_many runs
+#: before nuts_roster_speak_plan
+COM_CLONE, COM_DESTROY, COM_CSAY, COM_CHEAR = 73, 74, 78, 79
+CLONE_KERNELS = ("nuts_roster_clone", "nuts_roster_clone_order")
+#: what became of such an event (Clone.outcome).  A ``.chear`` that was obeyed has the ``clone_hear`` value it set for its
+#: outcome: CLONE_HEAR_NOTHING, CLONE_HEAR_SWEARS or CLONE_HEAR_ALL, 0 .. 2.  Then a clone created, one destroyed and one that
+#: spoke; then the refusals to the actor alone, a branch of the reference each and in its order: of ``create_clone`` (no such
+#: room, the room is private, already a clone there, the maximum reached), of ``destroy_clone`` (no such room, nobody of that
+#: name, the owner's level, no clone of the actor's there, none of the named user's), of ``clone_say`` (muzzled, too few
+#: words, no such room, no clone there) and of ``clone_hear`` (usage, no such room, no clone there); and CLONE_DEFERRED, an
+#: event the caller submits again
+(CLONE_CREATED, CLONE_DESTROYED, CLONE_SAID, CLONE_NO_ROOM, CLONE_PRIVATE, CLONE_ALREADY, CLONE_MAX, CLONE_DESTROY_NO_ROOM,
+ CLONE_DESTROY_NOBODY, CLONE_DESTROY_LEVEL, CLONE_DESTROY_NONE_OWN, CLONE_DESTROY_NONE_THEIRS, CLONE_CSAY_MUZZLED, CLONE_CSAY_USAGE,
+ CLONE_CSAY_NO_ROOM, CLONE_CSAY_NONE, CLONE_CHEAR_USAGE, CLONE_CHEAR_NO_ROOM, CLONE_CHEAR_NONE, CLONE_DEFERRED) = range(3, 23)
+#: the longest of the five short texts of such an event before the transducer (kCloneHereMax .. kCloneNoticeMax of
+#: fanout.hip, pinned by a host test), by their format strings: ``~FB~OL``, a 12-byte name and `` whispers a haunting
+#: spell...\n``; ``~FB~OLA clone of ``, a name and `` appears in a swirling magical mist!\n``; ``Room access returned to
+#: ~FGPUBLIC.\n``; ``~FB~OLYou whisper a haunting spell and a clone is created in the ``, a 20-byte room name and ``.\n``;
+#: ``~OLSYSTEM: ~FR``, a name, `` has destroyed your clone in the ``, a room name and ``.\n``
+MAX_CLONE_HERE, MAX_CLONE_THERE, MAX_CLONE_RESET, MAX_CLONE_REPLY, MAX_CLONE_NOTICE = (
+    6 + USER_NAME_LEN + 30, 17 + USER_NAME_LEN + 37, 35, 65 + ROOM_NAME_LEN + 2, 14 + USER_NAME_LEN + 33 + ROOM_NAME_LEN + 2)
+#: their slots among a clone call's texts (kCloneHereRow .. kCloneNoticeRow): each the longest text rounded up to a multiple
+#: of 4, in the order above.  The said lines lie between the reset lines and the replies, each in a slot of its inpstr's
+#: length and _SPEAK_SLACK, as speak_many lays its composed lines: the texts lie in their own order, room lines first
+_CLONE_ROWS = (48, 68, 36, 88, 84)
+#: the texts of an event in a Clone, in that order: the four room lines first, then the two single-recipient texts
+CLONE_HERE, CLONE_THERE, CLONE_RESET, CLONE_SAID_LINE, CLONE_REPLY, CLONE_NOTICE = range(6)
 #: a look room's row of the names relay_many uploads (kRelayNameRow of fanout.hip): 20 bytes of name padded with zeros, then
 #: its length; and what a relay text is longer than its broadcast at most, ``~FT[ `` + a 20-byte name + `` ]:~RS ``
 #: (kRelaySlack): its slot among a relay call's relay texts is that much wider than the text
@@ -931,6 +964,77 @@ class Access:
 
 
 @dataclass
+class Clone:
+    """What ``create_clone()``, ``destroy_clone()``, ``clone_say()`` and ``clone_hear()`` write for K events
+    (``Roster.clone_many``), shaped like an :class:`Access`.  ``outcome[k]`` is CLONE_HEAR_NOTHING, CLONE_HEAR_SWEARS or
+    CLONE_HEAR_ALL for a ``.chear`` that was obeyed -- the value it set -- or one of the other CLONE_* constants;
+    ``target_room[k]`` the room the event is about -- the actor's own for a ``.clone`` or ``.destroy`` without a word, else
+    the room the word resolved to -- or -1 when ``get_room`` found none or was not reached; ``target_slot[k]`` the slot
+    ``get_user`` found for a ``.destroy`` with a name, the owner, or -1 when it found none or was not asked; ``reset[k]``
+    whether the room a destroyed clone left returned to public.  ``record[k]`` is the clone record the event found -- the
+    one destroyed, spoken through, set, or already there --, an index into the records as they were before the call, and -1
+    where there is none, as for a created one; ``created[k]`` is the record a CLONE_CREATED event was given, an index into
+    the records as the call leaves them, and -1 for every other event.
+
+    ``reply`` plans the actor's own line, ``here`` the line the actor's room gets without the actor, ``there`` the line the
+    clone's room gets (without the actor for a created clone, whole for a destroyed one), ``reset_plan`` the line a room
+    that returns to public gets, ``notice`` the line the owner of a clone that another destroyed gets, and ``said`` the
+    line a clone speaks to its room.  They are ordinary plans over the roster as it was before the call and share one
+    variant buffer; a text that is not there has size -1, nobody admitted and both variants 0 bytes in 0 writes.  A
+    CLONE_DEFERRED event has no text at all, and its targets are what the roster before the call gives.
+
+    Delivery, per client: the events in call order, and of one event the reset line, the reply, the here line, the there
+    line, the notice (``destroy_clone``'s order of writes; a created clone has no reset line and no notice), or the said
+    line alone.  The four room lines pass through ``relay_many``, over the records as the call leaves them."""
+    outcome: np.ndarray           # int8 [K]
+    target_room: np.ndarray       # int32 [K]
+    target_slot: np.ndarray       # int32 [K]
+    record: np.ndarray            # int32 [K]
+    created: np.ndarray           # int32 [K]
+    reset: np.ndarray             # bool [K]
+    reply: Plan
+    here: Plan
+    there: Plan
+    reset_plan: Plan
+    notice: Plan
+    said: Plan
+    texts: np.ndarray             # uint8, flat: the composed texts; gaps are allowed and unspecified
+    text_starts: np.ndarray       # int64 [6, K]   rows CLONE_HERE, CLONE_THERE, CLONE_RESET, CLONE_SAID_LINE, CLONE_REPLY, CLONE_NOTICE
+    text_sizes: np.ndarray        # int64 [6, K]   -1: there is no such text
+    timing: dict = field(default_factory=dict)
+
+    _text = Speech._text
+
+    def reply_text(self, k: int) -> bytes:
+        """The line event ``k`` sends to its actor; ``b""`` for a clone that spoke and for a deferred event."""
+        return self._text(CLONE_REPLY, k)
+
+    def here_text(self, k: int) -> bytes:
+        """The line event ``k`` sends to its actor's room without the actor; ``b""`` when there is none."""
+        return self._text(CLONE_HERE, k)
+
+    def there_text(self, k: int) -> bytes:
+        """The line event ``k`` sends to the clone's room; ``b""`` when there is none."""
+        return self._text(CLONE_THERE, k)
+
+    def reset_text(self, k: int) -> bytes:
+        """The line event ``k`` sends to a room that returns to public; ``b""`` when none does."""
+        return self._text(CLONE_RESET, k)
+
+    def notice_text(self, k: int) -> bytes:
+        """The line event ``k`` sends to the owner of the clone it destroyed; ``b""`` when that is the actor, or nobody."""
+        return self._text(CLONE_NOTICE, k)
+
+    def said_text(self, k: int) -> bytes:
+        """The line the clone of event ``k`` speaks; ``b""`` when none spoke."""
+        return self._text(CLONE_SAID_LINE, k)
+
+    def effective(self) -> np.ndarray:
+        """The events that set a ``clone_hear``, created a clone, destroyed one or made one speak, ascending."""
+        return np.flatnonzero((self.outcome >= 0) & (self.outcome <= CLONE_SAID))
+
+
+@dataclass
 class Input:
     """What ``user_input()`` and ``exec_com()`` make of K reads (``Roster.input_many``).  ``kind[k]`` is IAC, EMPTY,
     REPEAT, UNKNOWN, SPEECH or COMMAND; ``com[k]`` the command (enum np_com) of a SPEECH or COMMAND read, else -1;
@@ -1167,6 +1271,9 @@ def _load():
         lib.nd_roster_access.argtypes = ([ctypes.c_int, ctypes.c_int, P, ctypes.c_int64, P, P, P, P, P, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int] + [P] * 15 + [ctypes.POINTER(_RosterTiming)])
         lib.nd_roster_access.restype = ctypes.c_int
+        lib.nd_roster_clone.argtypes = ([ctypes.c_int, ctypes.c_int, P, ctypes.c_int64, P, P, P, P, P, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int] + [P] * 18 + [ctypes.POINTER(_RosterTiming)])
+        lib.nd_roster_clone.restype = ctypes.c_int
         lib.nd_roster_clones.argtypes = [ctypes.c_int, ctypes.c_int]
         lib.nd_roster_clones.restype = ctypes.c_int
         lib.nd_roster_relay.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int64] + [P] * 22 + [ctypes.POINTER(_RosterTiming)]
@@ -2634,7 +2741,8 @@ class Roster:
         before it submits; remote users; ``.private``, ``.public``, ``.invite`` and ``.letmein`` themselves -- they are
         :meth:`access_many`'s, which keeps ``access`` and ``invite_room`` for this call; the prompt; fusing the look into the
         first device visit;
-        applying the moves by a kernel.  ``go_many`` does not relay to clones' owners."""
+        applying the moves by a kernel.  ``go_many`` does not relay to clones' owners; the clone records it counts are
+        :meth:`set_clones`' and :meth:`clone_many`'s."""
         self._check_open()
         text, text_off, lens, slots, wcs = self._prepare_go(events, gatecrash_level, min_private_users)
         lib = _load()
@@ -2871,6 +2979,229 @@ class Roster:
                     self.clear_review([rm])
         return access
 
+    def _prepare_clone(self, events, max_clones, gatecrash_level, min_private_users, record):
+        """Each (slot, com, inpstr, word_count) and its actor's state checked, packed for nd_roster_clone: the inpstr, their
+        offsets and lengths, the slots, the commands and the word counts, whether the call records, and the first record
+        behind the last occupied one."""
+        if isinstance(events, (str, bytes, bytearray, np.ndarray)) or not hasattr(events, "__len__"):
+            raise ValueError(f"events must be a sequence of tuples, not {type(events).__name__}")
+        if len(events) == 0:
+            raise ValueError("empty call: no events")
+        if not _is_int(max_clones, 0, 2**31 - 1):
+            raise ValueError(f"max_clones must be an int in [0, 2^31), not {max_clones!r}")
+        if not _is_int(gatecrash_level, 0, MAX_LEVEL):
+            raise ValueError(f"gatecrash_level must be an int in [0, {MAX_LEVEL}] (enum np_level), not {gatecrash_level!r}")
+        if not _is_int(min_private_users, 0, 2**31 - 1):
+            raise ValueError(f"min_private_users must be an int in [0, 2^31), not {min_private_users!r}")
+        record = _flag("record", record)
+        if self.look_rooms < 1:
+            raise ValueError("the roster has no room records (look_rooms is 0): there is no room for a clone to stand in")
+        if self.clones < 1:
+            raise ValueError("the roster has no clone records (clones is 0)")
+        if record and self.review_rooms < self.look_rooms:
+            raise ValueError(f"record: a clone may speak in any of the {self.look_rooms} look rooms, and "
+                             f"{self._ring_rooms_are()}")
+        if 4 * len(events) * self.capacity >= 2**31 - 1:
+            raise ValueError(f"{len(events)} events to {self.capacity} slots: 4 x K x capacity must be below 2^31 - 1")
+        texts, slots, coms, wcs = [], [], [], []
+        for k, ev in enumerate(events):
+            if not isinstance(ev, tuple) or len(ev) != 4:
+                raise ValueError(f"event {k}: expected a (slot, com, inpstr, word_count) tuple, "
+                                 f"got {type(ev).__name__}{f' of {len(ev)}' if isinstance(ev, tuple) else ''}")
+            slot, com, inpstr, wc = ev
+            try:
+                slot = self._slot(slot)
+                if not _is_int(com, 0, NUM_COMMANDS - 1) or int(com) not in (COM_CLONE, COM_DESTROY, COM_CSAY, COM_CHEAR):
+                    raise ValueError(f"com must be COM_CLONE, COM_DESTROY, COM_CSAY or COM_CHEAR ({COM_CLONE}, {COM_DESTROY}, "
+                                     f"{COM_CSAY}, {COM_CHEAR}), not {com!r}")
+                text = _as_text(inpstr)
+                if len(text) >= ARR_SIZE:
+                    raise ValueError(f"inpstr of {len(text)} bytes: the talker's input line holds at most {ARR_SIZE - 1}")
+                if not _is_int(wc, 0, MAX_WORDS):
+                    raise ValueError(f"word_count must be an int in [0, {MAX_WORDS}], not {wc!r}")
+                if not 0 <= self._room[slot] < self.look_rooms:
+                    raise ValueError(f"the actor, slot {slot}, is in " + (f"room {int(self._room[slot])}, which has no room record"
+                                     if self._room[slot] >= 0 else "no room") + f" (look_rooms is {self.look_rooms})")
+                if self._flags[slot] & ROSTER_FLAGS["login"]:
+                    raise ValueError(f"the actor, slot {slot}, is still logging in")
+                if self._speech[slot, USER_NAME_LEN] == 0:
+                    raise ValueError(f"the actor, slot {slot}, has no name")
+            except ValueError as e:
+                raise ValueError(f"event {k}: {e}") from None
+            texts.append(text)
+            slots.append(slot)
+            coms.append(int(com))
+            wcs.append(int(wc))
+        # create_user() == NULL has no counterpart: every .clone of the call must find a record behind the last occupied one
+        owned = np.flatnonzero(self._clone_owner >= 0)
+        tail = int(owned[-1]) + 1 if len(owned) else 0
+        if coms.count(COM_CLONE) > self.clones - tail:
+            raise ValueError(f"{coms.count(COM_CLONE)} .clone events, and {self.clones - tail} empty clone records behind the last "
+                             f"occupied one, record {tail - 1}, of {self.clones}: split the call, or make a roster with more")
+        lens = np.fromiter((len(t) for t in texts), dtype=np.int64, count=len(texts))
+        if int(lens.sum()) >= 2**31 // 32:
+            raise ValueError("call text larger than 64 MiB: split it")
+        bound = _variant_at(sum(_CLONE_ROWS) * len(lens) + _composed_at(int(lens.sum()), len(lens)), 6 * len(lens))
+        if bound > MANY_ARENA_CAP:
+            raise ValueError(f"call too large: its variant bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
+                             f"(MANY_ARENA_CAP): split it")
+        return (b"".join(texts), _offsets(lens, np.int32), lens.astype(np.int32), np.array(slots, dtype=np.int32),
+                np.array(coms, dtype=np.uint8), np.array(wcs, dtype=np.uint8), record, tail)
+
+    def clone_many(self, events, *, max_clones, gatecrash_level, min_private_users, record=False) -> Clone:
+        """K ``.clone`` / ``.destroy`` / ``.csay`` / ``.chear`` events, decided and composed on the device: a non-empty
+        sequence of ``(slot, com, inpstr, word_count)`` tuples, what a COMMAND read of :meth:`input_many` hands back, with
+        ``com`` COM_CLONE, COM_DESTROY, COM_CSAY or COM_CHEAR (``create_clone``, ``destroy_clone``, ``clone_say`` and
+        ``clone_hear``, nuts333.c:7100-7210, 7293-7357).  :meth:`input_many` has held the command to the speaker's level; this
+        call checks no level beyond what those functions check.  ``max_clones`` is an int in [0, 2^31), ``gatecrash_level``
+        an int in [0, MAX_LEVEL] and ``min_private_users`` an int >= 0, the talker's three settings.  The roster needs
+        ``look_rooms >= 1`` and ``clones >= 1``; every actor needs a room in ``[0, look_rooms)``, a name and no ``login``
+        flag; a slot may appear more than once.  ``create_user() == NULL`` has no counterpart: a call that holds more
+        ``.clone`` events than there are empty records behind the last occupied one is refused -- by the count of such
+        events, not by their outcomes, which only the device knows: one that would be refused or deferred counts, and a
+        record an earlier ``.destroy`` of the same call frees does not.  Anything malformed raises
+        ``ValueError("event k: ...")`` before the device is touched, with no mirror and no dirty flag changed, and a call
+        whose variant bound exceeds MANY_ARENA_CAP is refused.
+
+        The device does, per event and in the reference's order, with ``word[1]`` the first word of ``inpstr`` and
+        ``word[2]`` the second, as :meth:`go_many` and :meth:`access_many` take theirs.  ``.clone``: the room is the actor's
+        own when ``word_count < 2``, else ``get_room``, else CLONE_NO_ROOM; CLONE_PRIVATE when ``has_room_access`` fails -- the
+        room has ``access & PRIVATE``, the actor's level is below ``gatecrash_level``, its ``invite_room`` is another room and
+        the room is not a fixed one asked by a WIZ or above.  Then, of the actor's records in record order, which is list
+        order: CLONE_ALREADY if one stands in the room and ``max_clones < 1`` or fewer than ``max_clones`` of them precede the
+        first that does; else CLONE_MAX if ``max_clones >= 1`` and the actor has that many; else CLONE_CREATED
+        (``max_clones`` 0 never refuses).  ``reply`` is the "created here" line in the actor's own room, else the "created in
+        the <room>" line; ``here`` goes to the actor's room without the actor, with ``invisname`` for an invisible actor;
+        ``there`` to the clone's room without the actor, with the real name -- both even when the two rooms are one.
+        ``.destroy``: the room as above, else CLONE_DESTROY_NO_ROOM; with ``word_count > 2``, ``get_user`` over ``word[2]``
+        as :meth:`tell_many` runs it, first byte capitalised (``get_user`` does that itself, nuts333.c:2367), else
+        CLONE_DESTROY_NOBODY, and CLONE_DESTROY_LEVEL if that user's level is not below the actor's -- the actor's own name
+        included; the first record of that owner in that room is destroyed, CLONE_DESTROYED, else CLONE_DESTROY_NONE_OWN or
+        CLONE_DESTROY_NONE_THEIRS (``"<name> does not have a clone the <room>.\\n"``, as the reference has it).  When the
+        room's access is exactly PRIVATE and fewer than ``min_private_users`` remain -- the slots with that room, a name and
+        no ``login`` flag, and the other clone records standing there -- it returns to public: ``reset[k]``, and
+        ``reset_plan`` to the whole room.  ``reply`` to the actor, ``here`` as above, ``there`` to the whole room of the clone,
+        the actor included if it stands there, ``notice`` to the owner alone when that is not the actor.  ``.csay``:
+        CLONE_CSAY_MUZZLED; CLONE_CSAY_USAGE if ``word_count < 3``; ``get_room``, else CLONE_CSAY_NO_ROOM; CLONE_CSAY_NONE
+        without a clone of the actor's there; else CLONE_SAID: ``said`` is ``"Clone of <name> <verb>s: <rest>\\n"`` to the
+        whole room, ``<rest>`` being ``inpstr`` behind its first word and the verb taken from its last byte as
+        :meth:`speak_many` takes it, with no swear check and no reply.  ``.chear``: CLONE_CHEAR_USAGE if ``word_count < 3`` or
+        ``word[2]`` is not exactly ``all``, ``swears`` or ``nothing``; CLONE_CHEAR_NO_ROOM; CLONE_CHEAR_NONE; else the value
+        set, CLONE_HEAR_ALL, CLONE_HEAR_SWEARS or CLONE_HEAR_NOTHING, with a reply.  The room lines' ``com_num`` is the
+        event's ``com``.
+
+        Every event is decided and planned against the roster as it was before the call.  To keep that exact, an event is
+        CLONE_DEFERRED when an earlier event of the same call that was not itself deferred touched its owner slot -- the
+        user ``get_user`` found, else the actor -- or the room its word resolved to: it wrote nothing, changed nothing and
+        recorded nothing, and the caller submits it again.  CLONE_CREATED touches the actor and the room, CLONE_DESTROYED
+        the owner and the room; nothing else touches anything, and a call of one event never defers.
+
+        ``record=True`` stores every said line in its room's review ring as ``speak_many(record=True)`` stores a say, in
+        event order, after the pending ``clear_review``; every look room must then be a ring room.
+
+        The binding then applies the result to the host mirrors, in event order and by the indices of the records as they
+        were, through :meth:`set_clones`, :meth:`set_rooms`, :meth:`update` and :meth:`clear_review`: a ``.chear`` sets
+        ``hear``; a destroyed record is emptied; a room that returned to public gets ``access=PUBLIC``, every slot invited
+        into it loses its ``invite_room`` and its ring is emptied, as after :meth:`go_many`; a created clone gets the next
+        empty record behind the last occupied one, with ``hear`` CLONE_HEAR_ALL.  When all are applied it closes the gaps
+        the destroyed records left: later records move down, order kept, so record order stays list order and the indices
+        behind a destroyed record decrease.  No kernel writes a kept table: a following :meth:`relay_many`,
+        :meth:`access_many`, :meth:`go_many` or :meth:`look_many` uploads what changed and sees the new state.
+
+        A call is one upload (the table, the speaker state, the go mirror, the room table and the clone records only after
+        an update of theirs), three kernel launches (CLONE_KERNELS, then nuts_roster_speak_plan) -- four in a call that
+        records (nuts_roster_record) --, one download at the bound size and one synchronise, whatever K, the capacity and
+        the records.  Returns a :class:`Clone`.
+
+        Out of scope: ``.switch``, which moves the user and ends in a look; ``.myclones`` and ``.allclones``, an ordered
+        compaction of their own; the relay of the room lines to clones' owners -- the caller passes them to
+        :meth:`relay_many`, which sees the records as this call left them, so a new clone relays the two lines of its own
+        creation and a destroyed one relays nothing, as in the reference; remote users; the prompt."""
+        self._check_open()
+        text, text_off, lens, slots, coms, wcs, recording, tail = self._prepare_clone(events, max_clones, gatecrash_level,
+                                                                                      min_private_users, record)
+        lib = _load()
+        handle = self._device_handle(lib)
+        k, words = len(lens), (self.capacity + 63) // 64
+        rows = np.array(_CLONE_ROWS, dtype=np.int64)
+        ctext_bytes = int(rows.sum()) * k + _composed_at(len(text), k)
+        outcome, target_room, target_slot = np.empty(k, dtype=np.int8), np.empty(k, dtype=np.int32), np.empty(k, dtype=np.int32)
+        rec, reset = np.empty(k, dtype=np.int32), np.empty(k, dtype=np.uint8)
+        clen = np.empty((6, k), dtype=np.int32)
+        bits = np.zeros((6, k, words), dtype=np.uint64)            # the device's four, then the actor alone and the owner alone
+        vn, vw = np.empty((6, k, 2), dtype=np.int64), np.empty((6, k, 2), dtype=np.int32)
+        vwsz = np.empty((6, k, 2, MAX_WRITES), dtype=np.int32)
+        ctext = np.empty(ctext_bytes, dtype=np.uint8)
+        var = np.empty(_variant_at(ctext_bytes, 6 * k), dtype=np.uint8)
+        tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
+        clear = self._pending_clear() if recording else None
+        t = _RosterTiming()
+        rc = lib.nd_roster_clone(handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(slots), _ptr(coms), _ptr(wcs),
+                                 int(gatecrash_level), int(min_private_users), int(max_clones), int(recording),
+                                 _ptr(self._table) if self._dirty else None, _ptr(self._speech) if self._speech_dirty else None,
+                                 _ptr(self._clones) if self._clones_dirty else None,
+                                 _ptr(self._rooms) if self._rooms_dirty else None, _ptr(self._go) if self._go_dirty else None,
+                                 _ptr(clear) if clear is not None else None, _ptr(outcome), _ptr(target_room), _ptr(target_slot),
+                                 _ptr(rec), _ptr(reset), _ptr(clen), _ptr(bits), _ptr(vn), _ptr(vw), _ptr(vwsz), _ptr(ctext),
+                                 _ptr(var), ctypes.byref(t))
+        _check(rc, "device clone failed")
+        self._private_dirty &= not self._speech_dirty         # the whole speaker mirror went up, or none of it
+        self._dirty = self._speech_dirty = self._rooms_dirty = self._go_dirty = self._clones_dirty = False
+        if recording:
+            self._clear_sent()
+        # the here, there and reset lines, the said lines as speak_many lays its own, the replies, the notices
+        at = np.arange(k, dtype=np.int64)
+        fixed = (np.cumsum(rows) - rows) * k
+        fixed[CLONE_SAID_LINE:] += _composed_at(len(text), k)
+        tstarts = np.stack([fixed[0] + rows[0] * at, fixed[1] + rows[1] * at, fixed[2] + rows[2] * at,
+                            int(rows[:3].sum()) * k + _composed_at(text_off.astype(np.int64), at),
+                            fixed[3] + rows[3] * at, fixed[4] + rows[4] * at])
+        starts = _variant_starts(tstarts, clen)
+        has = np.flatnonzero(clen[CLONE_REPLY] >= 0)
+        bits[CLONE_REPLY, has, slots[has] // 64] = np.uint64(1) << (slots[has] % 64).astype(np.uint64)
+        has = np.flatnonzero(clen[CLONE_NOTICE] >= 0)           # write_user(u2, text): ignall, afk and the room play no part
+        bits[CLONE_NOTICE, has, target_slot[has] // 64] = np.uint64(1) << (target_slot[has] % 64).astype(np.uint64)
+        timing = _timing_of(t)
+        colour_bits = _pack((self._flags & ROSTER_FLAGS["colour"]) != 0)
+        plans = [Plan(capacity=self.capacity, admitted_bits=bits[i], colour_bits=colour_bits, variants=var,
+                      variant_starts=starts[i], variant_sizes=vn[i], write_counts=vw[i], write_sizes=vwsz[i],
+                      timing=dict(timing)) for i in range(6)]
+        created = np.full(k, -1, dtype=np.int32)
+        clone = Clone(outcome=outcome, target_room=target_room, target_slot=target_slot, record=rec, created=created,
+                      reset=reset.astype(bool), reply=plans[CLONE_REPLY], here=plans[CLONE_HERE], there=plans[CLONE_THERE],
+                      reset_plan=plans[CLONE_RESET], notice=plans[CLONE_NOTICE], said=plans[CLONE_SAID_LINE], texts=ctext,
+                      text_starts=tstarts, text_sizes=clen.astype(np.int64), timing=timing)
+        # the changes, on the host mirrors, in event order and by the records' indices as they were: the next call of any
+        # kind uploads what it reads
+        for k in clone.effective().tolist():
+            if outcome[k] <= CLONE_HEAR_ALL:
+                self.set_clones(int(rec[k]), hear=int(outcome[k]))
+            elif outcome[k] == CLONE_CREATED:
+                self.set_clones(tail, owner=int(slots[k]), room=int(target_room[k]))
+                created[k], tail = tail, tail + 1
+            elif outcome[k] == CLONE_DESTROYED:
+                self.set_clones(int(rec[k]), owner=None)
+                if clone.reset[k]:
+                    rm = int(target_room[k])
+                    self.set_rooms(rm, access=PUBLIC)
+                    invited = np.flatnonzero(self._go_invite == rm)
+                    if len(invited):
+                        self.update(invited, invite_room=None)
+                    if rm < self.review_rooms:
+                        self.clear_review([rm])
+        # the gaps the destroyed records left close: later records move down, order kept, as the user list loses a node
+        gone = rec[outcome == CLONE_DESTROYED]
+        if len(gone):
+            kept = np.setdiff1d(np.arange(tail), gone)                 # a record that lay empty before the call keeps its place among them
+            moved = np.full(tail, -1, dtype=np.int32)
+            moved[kept] = np.arange(len(kept), dtype=np.int32)
+            owner, room, hear = self._clone_owner[kept].copy(), self._clone_room[kept].copy(), self._clone_hear[kept].copy()
+            self._clone_owner[:tail], self._clone_room[:tail], self._clone_hear[:tail] = -1, -1, CLONE_HEAR_NOTHING
+            self._clone_owner[:len(kept)], self._clone_room[:len(kept)], self._clone_hear[:len(kept)] = owner, room, hear
+            made = created >= 0
+            created[made] = moved[created[made]]
+        return clone
+
     def set_clones(self, clones, *, owner=_KEEP, room=_KEEP, hear=_KEEP) -> None:
         """Set fields of the clone records ``clones`` (a record or a sequence of them, each in ``[0, clones)``), by the
         conventions of :meth:`update` and :meth:`set_rooms`: each field given is one value for every record or a sequence
@@ -3002,8 +3333,8 @@ class Roster:
         (nuts_roster_record) --, one download at the bound size and one synchronise, whatever K, the capacity and the
         records.
 
-        Out of scope: ``.clone``, ``.destroy``, ``.switch`` and ``.chear`` themselves -- the caller calls
-        :meth:`set_clones` --, and remote users."""
+        Out of scope: ``.clone``, ``.destroy``, ``.csay`` and ``.chear`` themselves -- they are :meth:`clone_many`'s, which
+        keeps the records for this call --, ``.switch`` -- the caller calls :meth:`set_clones` --, and remote users."""
         self._check_open()
         packed, csender, names = self._prepare_relay(broadcasts, record, clone_sender)
         text, text_off, lens, rm, sender, flags, coms = packed

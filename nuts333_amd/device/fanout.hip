@@ -3341,6 +3341,461 @@ __device__ void roster_access_order(const AccessOrderArgs& a)
     }
 }
 
+// ------------------------------------------------------------------ the clone commands, of a resident roster
+//
+// create_clone(), destroy_clone(), clone_say() and clone_hear() (nuts333.c:7100-7210, 7293-7357): .clone, .destroy, .csay and
+// .chear, commands 73, 74, 78 and 79.  As with the room's door, the device decides and composes and writes no kept table;
+// the host binding creates, destroys and sets the records in its mirrors afterwards.  It reads the five tables
+// nuts_roster_access reads.
+// An event has six texts: the line the actor's room gets without the actor ("here"), the line the clone's room gets
+// ("there"), "Room access returned to ~FGPUBLIC.\n" for a room a destroyed clone leaves too empty ("reset"), the line the
+// clone speaks ("said"), the actor's own line ("reply") and the line the owner of a clone destroyed by another gets
+// ("notice").  With K events, text kind * K + k is event k's text of that kind, in that order: the 4K room lines first, as
+// nuts_roster_speak_plan wants them.  Five kinds have slots of fixed width; a said line has inpstr's length and kSpeakSlack,
+// as nuts_roster_speak's lines have.  The slots lie in the texts' order, so that var_at() keeps the variants apart.
+//   clone    nuts_roster_clone, ONE BLOCK PER EVENT, in the shape of nuts_roster_access.  word[1] and word[2] are found as
+//            np_wordfind finds them in inpstr.  The block runs get_user over the capitalised word[2] (a .destroy of
+//            another's clone; first, while little else is live), get_room over word[1], and then walks the clone records
+//            twice, lanes striding in block-sized steps: for the lowest record of (owner, room), a ballot per step and the
+//            waves' minima through LDS; then for the owner's records in all and those below that lowest one (the two counts
+//            create_clone's loop comes down to, see clone_created), and, for a destroy in a room that is exactly PRIVATE,
+//            the head-count reset_access takes without the destroyed record: popcounts of ballots, summed per wave and once
+//            across the waves through LDS.  No atomics: the same answer on every run.  Wave 0 decides in the reference's
+//            order and composes; lane 0 stores the lengths, the outcome, the room, the slot and the record the event
+//            resolved to, whether the room returns to public, and rm / sender / com / flags of the four room lines.
+//            Blocks past the events copy freshly uploaded tables into the kept allocations.
+//   order    nuts_roster_clone_order, ONE WAVE, after nuts_roster_access_order.  A created clone touches its owner and its
+//            room, a destroyed one likewise.  An event whose owner -- the user get_user found, else the actor -- or
+//            resolved room an earlier event of the call that was not itself deferred touched is deferred: its outcome
+//            becomes kCloneDeferred, its six texts void, and nothing of it is recorded.
+//   plan     nuts_roster_speak_plan with 4K room lines and 2K single-recipient texts.
+//   record   nuts_roster_record over the said lines, as after nuts_roster_speak.
+constexpr int kComClone = 73, kComDestroy = 74, kComCsay = 78, kComChear = 79;             // enum np_com
+// the first three are the clone_hear values a .chear sets (nuts333.h: CLONE_HEAR_NOTHING, CLONE_HEAR_SWEARS, CLONE_HEAR_ALL)
+constexpr int kCloneHearNothing = 0, kCloneHearSwears = 1, kCloneHearAll = 2, kCloneCreated = 3, kCloneDestroyed = 4, kCloneSaid = 5,
+              kCloneNoRoom = 6, kClonePrivate = 7, kCloneAlready = 8, kCloneMax = 9, kCloneDestroyNoRoom = 10, kCloneDestroyNobody = 11,
+              kCloneDestroyLevel = 12, kCloneDestroyNoneOwn = 13, kCloneDestroyNoneTheirs = 14, kCloneCsayMuzzled = 15,
+              kCloneCsayUsage = 16, kCloneCsayNoRoom = 17, kCloneCsayNone = 18, kCloneChearUsage = 19, kCloneChearNoRoom = 20,
+              kCloneChearNone = 21, kCloneDeferred = 22;
+constexpr int kCloneTexts = 6, kCloneLines = 4;            // here, there, reset, said: the room lines; then reply, notice
+constexpr int kCloneHere = 0, kCloneThere = 1, kCloneReset = 2, kCloneSaidText = 3, kCloneReply = 4, kCloneNotice = 5;
+// the longest texts: "~FB~OL" + name + " whispers a haunting spell...\n"; "~FB~OLA clone of " + name + " appears in a swirling
+// magical mist!\n"; "Room access returned to ~FGPUBLIC.\n"; "~FB~OLYou whisper a haunting spell and a clone is created in the "
+// + room name + ".\n"; "~OLSYSTEM: ~FR" + name + " has destroyed your clone in the " + room name + ".\n"
+constexpr int kCloneHereMax = 6 + kNameLen + 30, kCloneThereMax = 17 + kNameLen + 37, kCloneResetMax = 35,
+              kCloneReplyMax = 65 + kRoomNameLen + 2, kCloneNoticeMax = 14 + kNameLen + 33 + kRoomNameLen + 2;
+constexpr int kCloneHereRow = 48, kCloneThereRow = 68, kCloneResetRow = 36, kCloneReplyRow = 88, kCloneNoticeRow = 84;   // their slots
+constexpr int kCloneLineRows = kCloneHereRow + kCloneThereRow + kCloneResetRow;             // an event's fixed bytes before its said line
+constexpr int kCloneRow = kCloneLineRows + kCloneReplyRow + kCloneNoticeRow;                // and in all, beside the said line
+// Where text kind * k + b of a call of k events over text_bytes of inpstr has its slot, text_off being where event b's inpstr
+// starts: the here lines, the there lines, the reset lines, the said lines as ctext_at() lays them, the replies, the notices.
+constexpr int64_t clone_text_at(int kind, int64_t b, int64_t k, int64_t text_off, int64_t text_bytes)
+{
+    return kind == kCloneHere ? kCloneHereRow * b
+           : kind == kCloneThere ? kCloneHereRow * k + kCloneThereRow * b
+           : kind == kCloneReset ? (kCloneHereRow + kCloneThereRow) * k + kCloneResetRow * b
+           : kind == kCloneSaidText ? kCloneLineRows * k + ctext_at(text_off, b)
+           : kind == kCloneReply ? kCloneLineRows * k + ctext_at(text_bytes, k) + kCloneReplyRow * b
+           : kCloneLineRows * k + ctext_at(text_bytes, k) + kCloneReplyRow * k + kCloneNoticeRow * b;
+}
+constexpr int64_t clone_text_bytes(int64_t k, int64_t text_bytes) { return kCloneRow * k + ctext_at(text_bytes, k); }
+
+// create_clone's walk of the user list (c:7122-7135) without the walk.  Of the actor's records in list order, `found` says
+// that one stands in the room, `before` how many precede the first such one, `total` how many there are.  The loop answers
+// "already" at that first one unless "maximum" came first, which it does at the max_clones-th record that stands elsewhere:
+// when max_clones >= 1 and before >= max_clones.  Past the list it has counted every record, all of them elsewhere.
+// ++cnt == max_clones never holds for max_clones 0.  1: already, 2: maximum, 0: created.
+__host__ __device__ constexpr int clone_created(bool found, int before, int total, int max_clones)
+{
+    return found && (max_clones < 1 || before < max_clones) ? 1 : max_clones >= 1 && total >= max_clones ? 2 : 0;
+}
+
+struct CloneArgs {
+    const int32_t* room;         // [capacity] the roster's table
+    const uint8_t* slotf;        // [capacity] and its flag bytes: login
+    const uint8_t* speech;       // the tables this call reads, the uploads or the kept ones: the speaker state (name, vis, level),
+    const uint8_t* records;      // the clone records as take_clones lays them out,
+    const uint8_t* rooms;        // the room records,
+    const uint8_t* go;           // [capacity * 88] and the go table: invite_room
+    Kept kept[4];                // the speaker state, the go table, the room records, the clone records
+    const uint8_t* text;         // the K inpstr, packed
+    const int32_t* text_off;     // [k]
+    const int32_t* text_len;     // [k]
+    const int32_t* slot;         // [k] the actor
+    const uint8_t* com;          // [k] NP_CLONE, NP_DESTROY, NP_CSAY or NP_CHEAR
+    const uint8_t* words;        // [k] word_count
+    const int32_t* ctext_off;    // [6k] where each text's slot starts in ctext
+    int k, capacity, look_rooms, clones, gatecrash_level, min_private_users, max_clones, record;
+    int* violations;             // composed texts past their slot (zeroed by the host's upload)
+    uint8_t* ctext;              // the composed texts
+    int32_t* clen;               // [6k] their lengths; -1: no such text
+    int8_t* outcome;             // [k]
+    int32_t* found;              // [3k] the room the event is about (-1: none, or the step was not reached); at k, the slot
+                                 // get_user found (-1: none, or it was not asked); at 2k, the record found or destroyed (-1:
+                                 // none).  One array, and one below: the kernel's arguments stay in scalar registers
+    uint8_t* reset;              // [k] 1: the room returns to public
+    int32_t* line;               // [12k] the room lines' rooms, as SpeakPlanArgs.rm; at 4k, their senders (-1: none); at 8k,
+                                 // their com_num
+    uint8_t* flags;              // [k] bit 2: record the said line
+};
+
+// Who stands in room rm, as reset_access counts (c:2095): the slots with that room, a name and no login flag, and the clone
+// records standing there but record `skip`, by a whole block; each wave returns its own share.  nuts_roster_go and
+// nuts_roster_access keep their own loops: they skip a slot or nobody where this skips a record, and so their code stays
+// what their device tests passed with.
+__device__ __forceinline__ int wave_head_count(const int32_t* room, const uint8_t* slotf, const uint8_t* speech, int capacity,
+                                               const int32_t* owner, const int32_t* croom, int clones, int rm, int skip)
+{
+    int cnt = 0;
+    for (int base = 0; base < capacity; base += kBlock) {
+        const int j = base + (int)threadIdx.x;
+        const bool in_room = j < capacity && room[j] == rm && !(slotf[j] & kLogin) && speech[(size_t)j * kSpeechRec + kNameLen] != 0;
+        cnt += __popcll(__ballot(in_room));
+    }
+    for (int base = 0; base < clones; base += kBlock) {
+        const int r = base + (int)threadIdx.x;
+        const bool in_room = r < clones && r != skip && owner[r] >= 0 && croom[r] == rm;
+        cnt += __popcll(__ballot(in_room));
+    }
+    return cnt;
+}
+
+__device__ void roster_clone(const CloneArgs& c)
+{
+    if ((int)blockIdx.x >= c.k) {           // the tables just uploaded, into the kept allocations: a word per lane
+        copy_kept(c.kept, ((int)blockIdx.x - c.k) * kBlock + (int)threadIdx.x);
+        return;
+    }
+    __shared__ int s_room[kBlock / 64], s_exact[kBlock / 64], s_sub[kBlock / 64], s_min[kBlock / 64], s_total[kBlock / 64],
+        s_before[kBlock / 64], s_pop[kBlock / 64];
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int k = (int)blockIdx.x;
+    const int slot = c.slot[k], com = c.com[k], wc = c.words[k], len = c.text_len[k];
+    const uint8_t* in = c.text + c.text_off[k];
+
+    // word[1] and word[2] as np_wordfind finds the line's second and third word (c:417-432): inpstr has lost the first
+    uint32_t wordb = 0;
+#pragma unroll
+    for (int x = 0; x < kReadSlice; x++) {
+        const int at = kReadSlice * lane + x;
+        wordb |= (uint32_t)(at < len && (int8_t)in[at] > 32) << x;
+    }
+    const int w0 = first_from(wordb, 0, lane, len);
+    const int w0_end = first_from(~wordb & 0xffffu, w0, lane, len);
+    const int w1 = first_from(wordb, w0_end, lane, len);    // where np_remove_first's rest begins, too (c:2350-2358)
+    const int w1_end = first_from(~wordb & 0xffffu, w1, lane, len);
+    const int wlen = w0_end - w0 < kWordLen ? w0_end - w0 : kWordLen;
+    const int wlen2 = w1_end - w1 < kWordLen ? w1_end - w1 : kWordLen;
+    const uint8_t* word = in + w0;
+    const uint8_t* word2 = in + w1;
+
+    // get_user over the capitalised word[2] of a .destroy with a name (c:7179-7180), before anything else is kept: the search
+    // is what needs registers most.  get_room comes first in the reference; the decisions below keep that order
+    const bool want_user = com == kComDestroy && wc > 2;
+    int best_exact = kNoMatch, best_sub = kNoMatch;
+    if (want_user) {
+        const UserMatch u = wave_get_user(c.speech, c.slotf, c.capacity, pack_word(word2, wlen2), wlen2, wave, lane);
+        best_exact = u.exact;
+        best_sub = u.sub;
+    }
+
+    const uint8_t* sp = c.speech + (size_t)slot * kSpeechRec;
+    const int level = sp[kLevelByte];
+    const int here = c.room[slot];          // a look room: the host checked it
+
+    // what comes before get_room (c:7109, 7173, 7300-7307, 7328-7334); block-uniform
+    int outcome = -1, rm = -1, hear = -1;
+    bool want_room = false;
+    if (com == kComClone || com == kComDestroy) {
+        if (wc < 2) rm = here;
+        else want_room = true;
+    } else if (com == kComCsay) {
+        if (sp[kNameLen + 1] & kMuzzled) outcome = kCloneCsayMuzzled;
+        else if (wc < 3) outcome = kCloneCsayUsage;
+        else want_room = true;
+    } else {                                // strcmp(word[2], ...): exact
+        const auto is = [&](const char* s, int n) {
+            bool same = wlen2 == n;
+            for (int i = 0; i < n && same; i++) same = word2[i] == (uint8_t)s[i];
+            return same;
+        };
+        hear = is("all", 3) ? kCloneHearAll : is("swears", 6) ? kCloneHearSwears : is("nothing", 7) ? kCloneHearNothing : -1;
+        if (wc < 3 || hear < 0) outcome = kCloneChearUsage;
+        else want_room = true;
+    }
+
+    int best = want_room ? wave_get_room(c.rooms, c.look_rooms, word, wlen, wave, lane) : kNoMatch;
+    if (lane == 0) {
+        s_room[wave] = best;
+        s_exact[wave] = best_exact;
+        s_sub[wave] = best_sub;
+    }
+    __syncthreads();
+    for (int w = 0; w < kBlock / 64; w++) {
+        best = s_room[w] < best ? s_room[w] : best;
+        best_exact = s_exact[w] < best_exact ? s_exact[w] : best_exact;
+        best_sub = s_sub[w] < best_sub ? s_sub[w] : best_sub;
+    }
+    if (want_room) {
+        if (best == kNoMatch) outcome = com == kComClone ? kCloneNoRoom : com == kComDestroy ? kCloneDestroyNoRoom
+                                        : com == kComCsay ? kCloneCsayNoRoom : kCloneChearNoRoom;
+        else rm = best;
+    }
+    int target = -1;
+    if (outcome < 0 && want_user) {         // c:7180-7186
+        target = best_exact != kNoMatch ? best_exact : best_sub != kNoMatch ? best_sub : -1;
+        if (target < 0) outcome = kCloneDestroyNobody;
+        else if (c.speech[(size_t)target * kSpeechRec + kLevelByte] >= level) outcome = kCloneDestroyLevel;
+    }
+    const int own = target >= 0 ? target : slot;
+    const uint8_t* rrec = c.rooms + (size_t)(rm < 0 ? here : rm) * kRoomRec;
+    const uint8_t access = rrec[kRrAccess];
+    if (outcome < 0 && com == kComClone) {  // has_room_access, c:2416-2419
+        const int32_t invite = *reinterpret_cast<const int32_t*>(c.go + (size_t)slot * kGoRec + kGoInvite);
+        if ((access & kAccessPrivate) && level < c.gatecrash_level && invite != rm && !((access & kAccessFixed) && level >= kWiz))
+            outcome = kClonePrivate;
+    }
+
+    // the lowest record of (owner, room): each wave's first hit is its lowest, the waves' minima meet in LDS
+    const bool walk = outcome < 0;          // block-uniform
+    const size_t slice = ((size_t)c.clones * sizeof(int32_t) + 255) & ~(size_t)255;
+    const int32_t* owner = reinterpret_cast<const int32_t*>(c.records);
+    const int32_t* croom = reinterpret_cast<const int32_t*>(c.records + slice);
+    int m = kNoMatch;
+    if (walk) {
+        for (int base = 64 * wave; base < c.clones; base += kBlock) {          // wave-uniform
+            const int r = base + lane;
+            const uint64_t b = __ballot(r < c.clones && owner[r] == own && croom[r] == rm);
+            if (b) {
+                m = base + __ffsll((unsigned long long)b) - 1;
+                break;
+            }
+        }
+    }
+    if (lane == 0) s_min[wave] = m;
+    __syncthreads();
+    for (int w = 0; w < kBlock / 64; w++) m = s_min[w] < m ? s_min[w] : m;
+    const bool found = m != kNoMatch;
+
+    // the two counts of create_clone's loop; the head-count of a room a destroyed clone may leave too empty (c:7192)
+    int total = 0, before = 0, cnt = 0;
+    if (walk && com == kComClone) {
+        for (int base = 0; base < c.clones; base += kBlock) {
+            const int r = base + (int)threadIdx.x;
+            const bool mine = r < c.clones && owner[r] == own;
+            total += __popcll(__ballot(mine));
+            before += __popcll(__ballot(mine && r < m));
+        }
+    }
+    const bool counted = walk && com == kComDestroy && found && access == kAccessPrivate;
+    if (counted) cnt = wave_head_count(c.room, c.slotf, c.speech, c.capacity, owner, croom, c.clones, rm, m);
+    if (lane == 0) {
+        s_total[wave] = total;
+        s_before[wave] = before;
+        s_pop[wave] = cnt;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    total = before = cnt = 0;
+    for (int w = 0; w < kBlock / 64; w++) {
+        total += s_total[w];
+        before += s_before[w];
+        cnt += s_pop[w];
+    }
+
+    // the four functions' decisions
+    if (outcome < 0) {
+        if (com == kComClone) {
+            const int made = clone_created(found, before, total, c.max_clones);
+            outcome = made == 1 ? kCloneAlready : made == 2 ? kCloneMax : kCloneCreated;
+        } else if (com == kComDestroy) outcome = found ? kCloneDestroyed : target < 0 ? kCloneDestroyNoneOwn : kCloneDestroyNoneTheirs;
+        else if (com == kComCsay) outcome = found ? kCloneSaid : kCloneCsayNone;
+        else outcome = found ? hear : kCloneChearNone;
+    }
+    const bool returns = outcome == kCloneDestroyed && counted && cnt < c.min_private_users;
+    const int rec = outcome <= kCloneSaid || outcome == kCloneAlready ? (outcome == kCloneCreated ? -1 : m) : -1;
+
+    const int n = c.k;
+    const auto slot_of = [&](int kind) { return c.ctext + c.ctext_off[kind * n + k]; };   // at its use: few scalars stay live
+    const Piece none{nullptr, 0};
+    const Piece name{sp, sp[kNameLen] < kNameLen ? sp[kNameLen] : kNameLen};
+    const Piece shown = (sp[kNameLen + 1] & kVis) ? name : lit("A presence");
+    const Piece rname{rrec, rrec[kRrNameLen] < kRoomNameLen ? rrec[kRrNameLen] : kRoomNameLen};
+    const uint8_t* tp = c.speech + (size_t)own * kSpeechRec;
+    const Piece tname{tp, tp[kNameLen] < kNameLen ? tp[kNameLen] : kNameLen};
+    int here_len = -1, there_len = -1, reset_len = -1, said_len = -1, reply_len = 0, notice_len = -1;
+    const auto reply = [&](Piece p0, Piece p1, Piece p2) {             // three pieces, each shorter than a wave
+        const Piece a0[5] = {p0, none, none, none, none}, a1[5] = {p1, p2, none, none, none};
+        append(slot_of(kCloneReply), kCloneReplyRow, reply_len, a0, nullptr, 0, false, lane, c.violations);
+        append(slot_of(kCloneReply), kCloneReplyRow, reply_len, a1, nullptr, 0, false, lane, c.violations);
+    };
+    switch (outcome) {
+    case kCloneHearNothing: reply(lit("Clone will now hear nothing.\n"), none, none); break;
+    case kCloneHearSwears: reply(lit("Clone will now only hear swearing.\n"), none, none); break;
+    case kCloneHearAll: reply(lit("Clone will now hear everything.\n"), none, none); break;
+    case kCloneCreated:                     // c:7150-7155
+        if (rm == here) reply(lit("~FB~OLYou whisper a haunting spell and a clone "), lit("is created here.\n"), none);
+        else {
+            reply(lit("~FB~OLYou whisper a haunting spell and a clone "), lit("is created in the "), rname);
+            reply(lit(".\n"), none, none);
+        }
+        break;
+    case kCloneDestroyed: reply(lit("~FM~OLYou whisper a sharp spell and the clone is destroyed.\n"), none, none); break;
+    case kCloneSaid: reply_len = -1; break;                            // say() of a clone writes nothing to its owner
+    case kCloneNoRoom:
+    case kCloneDestroyNoRoom:
+    case kCloneCsayNoRoom:
+    case kCloneChearNoRoom: reply(lit("There is no such room.\n"), none, none); break;
+    case kClonePrivate: reply(lit("That room is currently private, "), lit("you cannot create a clone there.\n"), none); break;
+    case kCloneAlready: reply(lit("You already have a clone in the "), rname, lit(".\n")); break;
+    case kCloneMax: reply(lit("You already have the maximum number of clones allowed.\n"), none, none); break;
+    case kCloneDestroyNobody: reply(lit("There is no one of that name logged on.\n"), none, none); break;
+    case kCloneDestroyLevel: reply(lit("You cannot destroy the clone of a user "), lit("of an equal or higher level.\n"), none); break;
+    case kCloneDestroyNoneOwn: reply(lit("You do not have a clone in the "), rname, lit(".\n")); break;
+    case kCloneDestroyNoneTheirs:           // c:7208, "a clone the" as it stands
+        reply(tname, lit(" does not have a clone the "), rname);
+        reply(lit(".\n"), none, none);
+        break;
+    case kCloneCsayMuzzled: reply(lit("You are muzzled, your clone cannot speak.\n"), none, none); break;
+    case kCloneCsayUsage: reply(lit("Usage: csay <room clone is in> <message>\n"), none, none); break;
+    case kCloneChearUsage: reply(lit("Usage: chear <room clone is in> all/swears/nothing\n"), none, none); break;
+    default: reply(lit("You do not have a clone in that room.\n"), none, none); break;     // kCloneCsayNone, kCloneChearNone
+    }
+    bool whole = reply_len >= 0 || outcome == kCloneSaid;
+    if (outcome == kCloneCreated) {         // c:7156-7160: invisname here, the real name there
+        const Piece h[5] = {lit("~FB~OL"), shown, lit(" whispers a haunting spell...\n"), none, none};
+        const Piece t0[5] = {lit("~FB~OLA clone of "), name, none, none, none};
+        const Piece t1[5] = {lit(" appears in a swirling magical mist!\n"), none, none, none, none};
+        here_len = compose(slot_of(kCloneHere), kCloneHereRow, h, nullptr, 0, false, lane, c.violations);
+        there_len = 0;
+        append(slot_of(kCloneThere), kCloneThereRow, there_len, t0, nullptr, 0, false, lane, c.violations);
+        append(slot_of(kCloneThere), kCloneThereRow, there_len, t1, nullptr, 0, false, lane, c.violations);
+        whole = whole && here_len >= 0 && there_len >= 0;
+    } else if (outcome == kCloneDestroyed) {               // c:7192-7202
+        const Piece h[5] = {lit("~FM~OL"), shown, lit(" whispers a sharp spell...\n"), none, none};
+        const Piece t[5] = {lit("~FM~OLThe clone of "), tname, lit(" shimmers and vanishes.\n"), none, none};
+        here_len = compose(slot_of(kCloneHere), kCloneHereRow, h, nullptr, 0, false, lane, c.violations);
+        there_len = compose(slot_of(kCloneThere), kCloneThereRow, t, nullptr, 0, false, lane, c.violations);
+        whole = whole && here_len >= 0 && there_len >= 0;
+        if (returns) {
+            const Piece r[5] = {lit("Room access returned to ~FGPUBLIC.\n"), none, none, none, none};
+            reset_len = compose(slot_of(kCloneReset), kCloneResetRow, r, nullptr, 0, false, lane, c.violations);
+            whole = whole && reset_len >= 0;
+        }
+        if (own != slot) {
+            const Piece v0[5] = {lit("~OLSYSTEM: ~FR"), name, lit(" has destroyed your clone in the "), none, none};
+            const Piece v1[5] = {rname, lit(".\n"), none, none, none};
+            notice_len = 0;
+            append(slot_of(kCloneNotice), kCloneNoticeRow, notice_len, v0, nullptr, 0, false, lane, c.violations);
+            append(slot_of(kCloneNotice), kCloneNoticeRow, notice_len, v1, nullptr, 0, false, lane, c.violations);
+            whole = whole && notice_len >= 0;
+        }
+    } else if (outcome == kCloneSaid) {     // say() of a clone, c:4080-4089: the owner's name as it is, no swear check
+        const uint8_t last = len > 0 ? in[len - 1] : 0;    // the last byte of the rest is inpstr's last
+        const Piece verb = last == '?' ? lit("ask") : last == '!' ? lit("exclaim") : lit("say");
+        const Piece l[5] = {lit("Clone of "), name, lit(" "), verb, lit("s: ")};
+        said_len = compose(slot_of(kCloneSaidText), len + kSpeakSlack, l, in + w1, len - w1, true, lane, c.violations);
+        whole = said_len >= 0;
+    }
+    if (!whole) here_len = there_len = reset_len = said_len = reply_len = notice_len = -1;             // a violation: the call fails
+    if (lane == 0) {
+        c.clen[kCloneHere * n + k] = here_len;
+        c.clen[kCloneThere * n + k] = there_len;
+        c.clen[kCloneReset * n + k] = reset_len;
+        c.clen[kCloneSaidText * n + k] = said_len;
+        c.clen[kCloneReply * n + k] = reply_len;
+        c.clen[kCloneNotice * n + k] = notice_len;
+        c.outcome[k] = (int8_t)outcome;
+        c.found[k] = rm;
+        c.found[n + k] = target;
+        c.found[2 * n + k] = rec;
+        c.reset[k] = returns && whole;
+        const int to = rm < 0 ? here : rm;
+        int32_t* lrm = c.line + k;
+        int32_t* sender = lrm + kCloneLines * n;
+        int32_t* com_num = sender + kCloneLines * n;
+        lrm[kCloneHere * n] = here;         // write_room_except(user->room, text, user)
+        sender[kCloneHere * n] = slot;
+        lrm[kCloneThere * n] = to;          // write_room_except(rm, text, user) of a created clone, write_room(rm, text) of a destroyed one
+        sender[kCloneThere * n] = outcome == kCloneCreated ? slot : -1;
+        lrm[kCloneReset * n] = lrm[kCloneSaidText * n] = to;                   // write_room(rm, text): nobody is excepted
+        sender[kCloneReset * n] = sender[kCloneSaidText * n] = -1;
+        for (int kind = 0; kind < kCloneLines; kind++) com_num[kind * n] = com;
+        c.flags[k] = said_len >= 0 && c.record ? kRecordBit : 0;
+    }
+}
+
+static_assert(kCloneHereMax == 48 && kCloneThereMax == 66 && kCloneResetMax == 35 && kCloneReplyMax == 87 && kCloneNoticeMax == 81 &&
+              kCloneHereMax <= kCloneHereRow && kCloneThereMax <= kCloneThereRow && kCloneResetMax <= kCloneResetRow &&
+              kCloneReplyMax <= kCloneReplyRow && kCloneNoticeMax <= kCloneNoticeRow, "roster_clone: the longest texts fit their slots");
+static_assert(sizeof(" whispers a haunting spell...\n") - 1 == 30 && sizeof("~FB~OLA clone of ") - 1 == 17 &&
+              sizeof(" appears in a swirling magical mist!\n") - 1 == 37 && sizeof("Room access returned to ~FGPUBLIC.\n") - 1 == kCloneResetMax &&
+              sizeof("~FB~OLYou whisper a haunting spell and a clone is created in the ") - 1 == 65 && sizeof("~OLSYSTEM: ~FR") - 1 == 14 &&
+              sizeof(" has destroyed your clone in the ") - 1 == 33 && 6 + kNameLen + sizeof(" whispers a sharp spell...\n") - 1 <= kCloneHereMax &&
+              sizeof("~FM~OLThe clone of  shimmers and vanishes.\n") - 1 + kNameLen <= kCloneThereMax &&
+              sizeof(" does not have a clone the .\n") - 1 + kNameLen + kRoomNameLen <= kCloneReplyMax &&
+              sizeof("You cannot destroy the clone of a user of an equal or higher level.\n") - 1 <= kCloneReplyMax,
+              "roster_clone: the texts are as long as counted");
+static_assert(kCloneHereRow % 4 == 0 && kCloneThereRow % 4 == 0 && kCloneResetRow % 4 == 0 && kCloneReplyRow % 4 == 0 &&
+              kCloneNoticeRow % 4 == 0 && kCloneHereRow - kCloneHereMax < 4 && kCloneThereRow - kCloneThereMax < 4 &&
+              kCloneResetRow - kCloneResetMax < 4 && kCloneReplyRow - kCloneReplyMax < 4 && kCloneNoticeRow - kCloneNoticeMax < 4,
+              "roster_clone: a row is its longest text rounded up to a whole word");
+static_assert(kCloneThereRow < kTextSize && kCloneReplyRow < kTextSize && kCloneNoticeRow < kTextSize && kArrSize - 1 + kSpeakSlack < kTextSize,
+              "roster_clone: a text fits speak_plan's LDS text");
+static_assert(sizeof("Clone of  exclaims: ") - 1 + kNameLen + 1 <= kSpeakSlack && sizeof("Clone of  exclaims: ") - 1 + kNameLen <= 64 &&
+              sizeof("~FM~OLYou whisper a sharp spell and the clone is destroyed.\n") - 1 <= 64 && 14 + kNameLen + 33 <= 64 &&
+              sizeof("~FM~OLThe clone of  shimmers and vanishes.\n") - 1 + kNameLen <= 64 && kCloneHereMax <= 64,
+              "roster_clone: a said line fits its slot, and the pieces of a compose() fit a wave");
+static_assert(clone_created(true, 0, 1, 0) == 1 && clone_created(false, 5, 5, 0) == 0 && clone_created(true, 1, 2, 2) == 1 &&
+              clone_created(true, 2, 3, 2) == 2 && clone_created(false, 1, 1, 2) == 0 && clone_created(false, 2, 2, 2) == 2,
+              "clone_created: create_clone's loop on paper");
+
+struct CloneOrderArgs {
+    const int32_t* slot;         // [k] the actors
+    const int32_t* target_room;  // [k] what nuts_roster_clone wrote
+    const int32_t* target_slot;  // [k]
+    int k;
+    int8_t* outcome;             // [k] becomes kCloneDeferred for a deferred event
+    int32_t* clen;               // [6k] whose six texts become void,
+    uint8_t* reset;              // [k] whose room does not return to public,
+    uint8_t* flags;              // [k] and whose said line is not recorded
+};
+
+__device__ void roster_clone_order(const CloneOrderArgs& a)
+{
+    __shared__ uint32_t s_rooms[kMaxLookRooms / 32], s_slots[kGoMaxSlots / 32];
+    const int lane = (int)threadIdx.x;      // one wave
+    for (int i = lane; i < kMaxLookRooms / 32; i += 64) s_rooms[i] = 0;
+    for (int i = lane; i < kGoMaxSlots / 32; i += 64) s_slots[i] = 0;
+    __syncthreads();
+    for (int base = 0; base < a.k; base += 64) {
+        const int k = base + lane;
+        const bool live = k < a.k;
+        const int tsl = live ? a.target_slot[k] : -1;
+        const int own = live ? (tsl >= 0 ? tsl : a.slot[k]) : 0, trm = live ? a.target_room[k] : -1;
+        const int out = live ? a.outcome[k] : kCloneChearUsage;
+        const int count = a.k - base < 64 ? a.k - base : 64;
+        bool defer = false;
+        for (int i = 0; i < count; i++) {   // in call order; every lane follows, lane 0 sets the bits
+            const int s = __shfl(own, i), r = __shfl(trm, i), oc = __shfl(out, i);
+            const bool hit = ((s_slots[s >> 5] >> (s & 31)) & 1u) || (r >= 0 && ((s_rooms[r >> 5] >> (r & 31)) & 1u));
+            if (lane == i) defer = hit;
+            __syncthreads();
+            if (lane == 0 && !hit && (oc == kCloneCreated || oc == kCloneDestroyed)) {      // r >= 0: a clone has a room
+                s_slots[s >> 5] |= 1u << (s & 31);
+                s_rooms[r >> 5] |= 1u << (r & 31);
+            }
+            __syncthreads();
+        }
+        if (live && defer) {
+            a.outcome[k] = (int8_t)kCloneDeferred;
+            for (int kind = 0; kind < kCloneTexts; kind++) a.clen[kind * a.k + k] = -1;
+            a.reset[k] = 0;
+            a.flags[k] = 0;
+        }
+    }
+}
+
 }  // namespace
 
 // Stable, unmangled kernel names (they are what rocprofv3 reports).
@@ -3371,6 +3826,8 @@ extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_go(GoArgs a) { 
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_go_order(GoOrderArgs a) { roster_go_order(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_access(AccessArgs a) { roster_access(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_access_order(AccessOrderArgs a) { roster_access_order(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_clone(CloneArgs a) { roster_clone(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_clone_order(CloneOrderArgs a) { roster_clone_order(a); }
 
 // ------------------------------------------------------------------------------------------ host library
 
@@ -4062,6 +4519,53 @@ size_t layout_access(uintptr_t base, size_t text_bytes, AccessArgs& s, SpeakPlan
     p.rm = s.rm;
     p.sender = s.sender;
     p.com_num = s.com_num;
+    p.violations = s.violations;
+    return take.at;
+}
+
+// nd_roster_clone's layout of a roster's allocation: layout_access's, with the record, the reset and the record flags among
+// the results, the pending clears among the inputs, and p planning 4k room lines and 2k single-recipient texts.  Of the
+// uploads the clone records lie last: the call's own aftermath changes them, and an upload runs from the first table given
+// to the end of the inputs.
+size_t layout_clone(uintptr_t base, size_t text_bytes, size_t clear_bytes, CloneArgs& s, SpeakPlanArgs& p, const uint8_t** clear)
+{
+    Carver take{base};
+    const size_t k = (size_t)s.k, t = kCloneTexts * k;
+    const size_t ctext_bytes = (size_t)clone_text_bytes((int64_t)k, (int64_t)text_bytes);
+    take_table(take, s.capacity, s.room, s.slotf);
+    take_kept(take, s.kept[0], kKeptSpeech, s.capacity);
+    take_kept(take, s.kept[1], kKeptGo, s.capacity);
+    take_kept(take, s.kept[2], kKeptRooms, s.capacity, s.look_rooms);
+    take_kept(take, s.kept[3], kKeptClones, s.capacity, s.look_rooms, s.clones);   // last: a created clone alone uploads nothing else
+    take(s.text, text_bytes);
+    take(s.text_off, k);
+    take(s.text_len, k);
+    take(s.slot, k);
+    take(s.com, k);
+    take(s.words, k);
+    take(s.ctext_off, t);
+    take(*clear, clear_bytes);
+    take(s.violations, 1);
+    take(s.outcome, k);
+    take(s.reset, k);
+    take(s.found, 3 * k);
+    take(s.clen, t);
+    take(p.vn, 2 * t);
+    take(p.vw, 2 * t);
+    take(p.vwsz, 2 * t * kMaxWrites);
+    take(p.bits, kCloneLines * k * (size_t)p.words);
+    take(s.ctext, ctext_bytes);
+    take(p.var, (size_t)var_at((int64_t)ctext_bytes, (int64_t)t));
+    take(s.line, 3 * kCloneLines * k);
+    take(s.flags, k);
+    p.room = s.room;
+    p.slot = s.slotf;
+    p.text = s.ctext;
+    p.text_off = s.ctext_off;
+    p.text_len = s.clen;
+    p.rm = s.line;
+    p.sender = s.line + kCloneLines * k;
+    p.com_num = s.line + 2 * kCloneLines * k;
     p.violations = s.violations;
     return take.at;
 }
@@ -5904,6 +6408,160 @@ int nd_roster_access(int handle, int k, const uint8_t* text, int64_t text_bytes,
     memcpy(vw, res(po.vw), 2 * texts * sizeof(int32_t));
     memcpy(vwsz, res(po.vwsz), 2 * texts * kMaxWrites * sizeof(int32_t));
     memcpy(bits, res(po.bits), 2 * (size_t)k * nwords * sizeof(uint64_t));
+    memcpy(ctext, res(so.ctext), ctext_bytes);
+    memcpy(var, res(po.var), var_bytes);
+
+    return fill_timing(timing, t0, t1, h2d, res_bytes);
+}
+
+// K .clone / .destroy / .csay / .chear events of roster `handle`, decided and composed as create_clone(), destroy_clone(),
+// clone_say() and clone_hear() do, against the tables as they are: nothing the roster keeps is changed but the rings of a
+// recording call, the caller creates, destroys and sets the records.  Event b: the actor's slot slots[b], which stands in a
+// look room, coms[b] (73, 74, 78 or 79), inpstr and words[b] as nd_roster_go's.  gatecrash_level (0 .. 4), min_private_users
+// (>= 0) and max_clones (>= 0) are the talker's.  record: store the said lines in their rooms' rings, after clearing those
+// that clear marks (NULL: none), as nd_roster_speak does; the caller has checked that every look room is a ring room.  The
+// five tables are nd_roster_go's, NULL when unchanged since this roster's last call that took them; the roster has clone
+// records.
+// Outputs (host, caller-allocated), with W = ceil(capacity / 64) and text t = kind * k + b for event b's here line (kind
+// 0), there line, reset line, said line, reply and notice (kind 5): outcome[k] (0 .. 2 the clone_hear value set, 3 created, 4
+// destroyed, 5 said, 6 .. 21 the refusals in the order of kCloneNoRoom .. kCloneChearNone, 22 deferred); target_room[k] and
+// target_slot[k], or -1; rec[k] the record found or destroyed, or -1; reset[k] 1 where the room returns to public; clen[6k],
+// -1 where there is no text; ctext[324 k + text_bytes + 36 k], the here lines at 48 b, the there lines at 48 k + 68 b, the
+// reset lines at 116 k + 36 b, the said lines at 152 k + text_off[b] + 36 b, the replies at 188 k + text_bytes + 88 b, the
+// notices at 276 k + text_bytes + 84 b; bits[4k * W] the admit bitmaps of the four room lines; vn[12k], vw[12k], vwsz[12k *
+// 16] and var[12 * ctext bytes + 96 k] as nd_roster_speak's.
+// Per call, whatever k and the capacity: one upload, three kernels (nuts_roster_clone, nuts_roster_clone_order,
+// nuts_roster_speak_plan) and nuts_roster_record as a fourth when record is set, one download at the bound size, one
+// synchronise.  Returns 0, or -1 with nd_last_error() set.
+int nd_roster_clone(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off, const int32_t* text_len,
+                    const int32_t* slots, const uint8_t* coms, const uint8_t* words, int gatecrash_level, int min_private_users,
+                    int max_clones, int record, const uint8_t* table, const uint8_t* speech, const uint8_t* clones, const uint8_t* rooms,
+                    const uint8_t* go, const uint8_t* clear, int8_t* outcome, int32_t* target_room, int32_t* target_slot, int32_t* rec,
+                    uint8_t* reset, int32_t* clen, uint64_t* bits, int64_t* vn, int32_t* vw, int32_t* vwsz, uint8_t* ctext, uint8_t* var,
+                    nd_roster_timing* timing)
+{
+    Roster* r = roster_at(handle);
+    if (!r || ensure_ready()) return -1;
+    const int cap = r->capacity, nwords = (cap + 63) / 64, nrooms = r->look_rooms;
+    if (k < 1 || (int64_t)kCloneLines * k * cap >= INT32_MAX || (int64_t)k * kCloneRow >= INT32_MAX / 16 || text_bytes < 0 ||
+        text_bytes >= INT32_MAX / 32 || nrooms < 1 || nrooms > kMaxLookRooms || r->clones < 1 || cap > kGoMaxSlots ||
+        gatecrash_level < 0 || gatecrash_level > kGod || min_private_users < 0 || max_clones < 0) {
+        snprintf(g_err, sizeof(g_err), "%d events to %d slots over %d look rooms and %d clone records: need 1 <= 4 k * capacity < 2^31 - 1, "
+                 "a look room, a clone record, a gatecrash level in 0 .. %d, a minimum of private users >= 0 and a maximum of clones >= 0",
+                 k, cap, nrooms, r->clones, kGod);
+        return -1;
+    }
+    int64_t sum = 0;
+    for (int b = 0; b < k; b++) {       // the kernels index by these: nothing out of range reaches them
+        const bool com_ok = coms[b] == kComClone || coms[b] == kComDestroy || coms[b] == kComCsay || coms[b] == kComChear;
+        if (slots[b] < 0 || slots[b] >= cap || text_len[b] < 0 || text_len[b] >= kArrSize || text_off[b] != sum || !com_ok) {
+            snprintf(g_err, sizeof(g_err), "event %d: slot, command, text length or text offset out of range", b);
+            return -1;
+        }
+        sum += text_len[b];
+    }
+    if (sum != text_bytes) {
+        snprintf(g_err, sizeof(g_err), "the events' texts hold %lld bytes, not %lld", (long long)sum, (long long)text_bytes);
+        return -1;
+    }
+    CloneArgs s{};
+    const Given given[] = {{kKeptSpeech, speech, &s.speech}, {kKeptGo, go, &s.go}, {kKeptRooms, rooms, &s.rooms},
+                           {kKeptClones, clones, &s.records}};
+    if (check_given(*r, given, "the roster's first clone call must give the speaker table, the go table, the room table and the clone records"))
+        return -1;
+    if (record && (r->review_rooms < nrooms || ensure_rings(*r, g.stream))) {
+        if (r->review_rooms < nrooms) snprintf(g_err, sizeof(g_err), "a recording clone call needs a review ring for every look room");
+        return -1;
+    }
+    const double t0 = now_ns();
+    hipStream_t st = g.stream;
+    SpeakPlanArgs p{};
+    s.k = k;
+    p.k = kCloneLines * k;
+    s.capacity = p.capacity = cap;
+    s.look_rooms = nrooms;
+    s.clones = r->clones;
+    s.gatecrash_level = gatecrash_level;
+    s.min_private_users = min_private_users;
+    s.max_clones = max_clones;
+    s.record = record != 0;
+    p.tiles = (cap + kBlock - 1) / kBlock;
+    p.words = nwords;
+    const size_t texts = (size_t)kCloneTexts * k, ctext_bytes = (size_t)clone_text_bytes(k, text_bytes);
+    const size_t var_bytes = (size_t)var_at((int64_t)ctext_bytes, (int64_t)texts);
+    const size_t clear_bytes = record && clear ? (size_t)r->review_rooms : 0;
+    CloneArgs so = s;                   // offsets of every array in the roster's allocation
+    SpeakPlanArgs po = p;
+    const uint8_t *o_clear = nullptr, *d_clear = nullptr;
+    const size_t need = layout_clone(0, (size_t)text_bytes, clear_bytes, so, po, &o_clear);
+    const size_t table_bytes = (uintptr_t)so.kept[0].fresh, tables_end = (uintptr_t)so.text;
+    const size_t in_bytes = (uintptr_t)so.violations + sizeof(int);
+    const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
+    if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
+    if (table) new_table(*r, so.room, so.slotf, table);
+    const int32_t* room = reinterpret_cast<const int32_t*>(r->mirror + (uintptr_t)so.room);
+    for (int b = 0; b < k; b++)         // nuts_roster_clone reads its actor's room record
+        if (room[slots[b]] < 0 || room[slots[b]] >= nrooms) {
+            snprintf(g_err, sizeof(g_err), "event %d: the actor's room has no room record", b);
+            return -1;
+        }
+    if (grow_roster(*r, need)) return -1;
+    layout_clone((uintptr_t)r->d, (size_t)text_bytes, clear_bytes, s, p, &d_clear);
+    if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
+
+    uint8_t* h = r->mirror;
+    const Put put{h};
+    put(so.text, text, (size_t)text_bytes);
+    put(so.text_off, text_off, (size_t)k * sizeof(int32_t));
+    put(so.text_len, text_len, (size_t)k * sizeof(int32_t));
+    put(so.slot, slots, (size_t)k * sizeof(int32_t));
+    put(so.com, coms, (size_t)k);
+    put(so.words, words, (size_t)k);
+    int32_t* coff = reinterpret_cast<int32_t*>(h + (uintptr_t)so.ctext_off);
+    for (int kind = 0; kind < kCloneTexts; kind++)
+        for (int b = 0; b < k; b++) coff[(size_t)kind * k + b] = (int32_t)clone_text_at(kind, b, k, text_off[b], text_bytes);
+    put(o_clear, clear, clear_bytes);
+    *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
+    // the tables' uploads lie between the table and the inputs
+    size_t first = 0, h2d = 0;
+    unsigned copy_blocks = 0;
+    if (pass_kept(*r, given, so.kept, s.kept, tables_end, &first, &copy_blocks)) return -1;
+    if (upload(*r, table_bytes, first, in_bytes, &h2d)) return -1;
+
+    const CloneOrderArgs order{s.slot, s.found, s.found + k, k, s.outcome, s.clen, s.reset, s.flags};
+    ND_CHECK(hipEventRecord(g.ev0, st));
+    hipLaunchKernelGGL(nuts_roster_clone, dim3((unsigned)k + copy_blocks), dim3(kBlock), 0, st, s);
+    ND_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(nuts_roster_clone_order, dim3(1), dim3(64), 0, st, order);
+    ND_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)(kCloneLines * k * p.tiles + (kCloneTexts - kCloneLines) * k)), dim3(kBlock),
+                       0, st, p);
+    ND_CHECK(hipGetLastError());
+    // on the said lines nuts_roster_clone wrote, less those nuts_roster_clone_order deferred
+    if (record && launch_record(*r, k, s.ctext, s.ctext_off + (size_t)kCloneSaidText * k, s.clen + (size_t)kCloneSaidText * k,
+                                s.line + (size_t)kCloneSaidText * k, s.flags, clear_bytes ? d_clear : nullptr))
+        return -1;
+    if (fetch_results(r->d, res_at, res_bytes)) return -1;
+    const double t1 = now_ns();
+
+    const Res res{gm.res, res_at};
+    const int violations = *reinterpret_cast<const int*>(res(so.violations));
+    if (violations) {
+        snprintf(g_err, sizeof(g_err), "%d text(s) exceeded the hard bounds (a text its slot; 6*len+4 bytes, %d writes transduced)",
+                 violations, kMaxWrites);
+        return -1;
+    }
+    memcpy(outcome, res(so.outcome), (size_t)k);
+    memcpy(reset, res(so.reset), (size_t)k);
+    const int32_t* found = reinterpret_cast<const int32_t*>(res(so.found));
+    memcpy(target_room, found, (size_t)k * sizeof(int32_t));
+    memcpy(target_slot, found + k, (size_t)k * sizeof(int32_t));
+    memcpy(rec, found + 2 * (size_t)k, (size_t)k * sizeof(int32_t));
+    memcpy(clen, res(so.clen), texts * sizeof(int32_t));
+    memcpy(vn, res(po.vn), 2 * texts * sizeof(int64_t));
+    memcpy(vw, res(po.vw), 2 * texts * sizeof(int32_t));
+    memcpy(vwsz, res(po.vwsz), 2 * texts * kMaxWrites * sizeof(int32_t));
+    memcpy(bits, res(po.bits), (size_t)kCloneLines * k * nwords * sizeof(uint64_t));
     memcpy(ctext, res(so.ctext), ctext_bytes);
     memcpy(var, res(po.var), var_bytes);
 

@@ -3,7 +3,8 @@
     python -m nuts333_amd.devpath [--reps R] [--warmup W] [--pathbench-iterations I] [--per-call K[,K...]]
                                   [--roster K[,K...]] [--plan K[,K...]] [--review Q[,Q...]] [--speak K[,K...]]
                                   [--input K[,K...]] [--tell K[,K...]] [--look K[,K...]] [--relay K[,K...]] [--go K[,K...]]
-                                  [--who K[,K...]] [--rooms K[,K...]] [--access K[,K...]]   -> one JSON line
+                                  [--who K[,K...]] [--rooms K[,K...]] [--access K[,K...]] [--clone K[,K...]]
+                                                                                                       -> one JSON line
 
 For N in {10, 100, 1000} listeners, the two texts oracle/pathbench.c times (``say``; ``shout`` carrying ``~OL``/``~RS``)
 and colour all-off / all-on / half, one ``nuts333_amd.device.broadcast`` per repetition (listener 0 is the sender, the
@@ -106,6 +107,16 @@ call sets an access: the three times and the copy volume of the ``.private`` cal
 ``cpu_us``, the CPU modelling the call in Python and transducing the lines through ctypes.  Three rooms can be set, three
 are fixed, so of K = 8 or 64 events most are refused or deferred: ``set``, ``refused`` and ``deferred`` say how many.  Both
 calls of each case are checked first against the model, the reference's formats and the CPU's transducer.
+
+``--clone K[,K...]`` adds ``clone``: a 1000-slot roster of ARCHs over the six default rooms with a clone record for each of
+the first K users, and K ``.csay`` events per ``Roster.clone_many`` call, each by another owner through its clone: the three
+times and the copy volume of that call, beside ``speak`` -- ``speak_many`` of the same bodies as says by the same users, in
+the same rounds -- and ``cpu_us``, the CPU composing the lines in Python and transducing them through ctypes;
+``csay_over_speak`` is the ratio of the medians, ``csay_over_speak_p10_p90`` the loosest the rounds allow.  Then, in rounds of
+their own, ``clone`` -- K ``.clone`` events by K users who own none, each in its own room -- and ``destroy`` -- K ``.destroy``
+events by the same users, which returns the records to their start.  Six rooms take six clones a call, so of K = 8 or 64
+events most are deferred: ``created`` and ``deferred`` say how many.  Every call is checked first against the reference's
+formats, the CPU's transducer and the rule of the call.
 """
 from __future__ import annotations
 
@@ -1026,6 +1037,100 @@ def access_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
             "access": cases}
 
 
+def clone_csays(k: int, names) -> list[tuple]:
+    """K ``.csay`` events by the owners 0 .. K - 1, each through its clone in room ``j % 6``, with the bodies of
+    ``speak_events(k)``; and the lines they compose."""
+    bodies = [ev[2] for ev in speak_events(k)]
+    events = [(j, device.COM_CSAY, names[j % len(names)] + b" " + body, 9) for j, body in enumerate(bodies)]
+    return events, [b"Clone of User%d says: %s\n" % (j, body) for j, body in enumerate(bodies)]
+
+
+def clone_model(room_of: np.ndarray, actors, destroy: bool) -> list[int]:
+    """What clone_many answers for ``.clone`` events without a word by ``actors``, who own no clone, at the roster
+    ``clone_cases`` builds, and for the ``.destroy`` events by the same actors in the call after it: the first actor of a
+    room is answered, the later ones of that room wait."""
+    touched, out = set(), []
+    for j in actors:
+        rm = int(room_of[j])
+        out.append(device.CLONE_DEFERRED if rm in touched else device.CLONE_DESTROYED if destroy else device.CLONE_CREATED)
+        touched.add(rm)
+    return out
+
+
+def clone_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
+    """The ``clone`` section: clone_many of K ``.csay`` events by K distinct owners at a 1000-slot roster over the six default
+    rooms, beside speak_many of the same bodies as says by the same users, in the same rounds, and the CPU composing and
+    transducing the lines; and clone_many of K ``.clone`` events, then of K ``.destroy`` events by the same actors, which
+    returns the records to their start."""
+    n = 1000
+    names, accesses = ROOMS_LISTS["6"]
+    nr, most = len(names), max(ks)
+    cases = []
+    for colour in COLOURS:
+        with device.Roster(n, look_rooms=nr, clones=2 * most) as roster:
+            col = colours(n, colour)
+            room_of = np.arange(n) % nr
+            roster.update(range(n), room=room_of.tolist(), colour=col, name=[b"User%d" % j for j in range(n)], level=3)
+            roster.set_rooms(list(range(nr)), name=names, access=accesses, links=[list(l) for l in GO_LINKS])
+            roster.set_clones(list(range(most)), owner=list(range(most)), room=[j % nr for j in range(most)])
+            settings = {"max_clones": 2, "gatecrash_level": 3, "min_private_users": 2}
+            for k in ks:
+                csays, lines = clone_csays(k, names)
+                says = [(j, device.COM_SAY, ev[2], 8) for j, ev in enumerate(speak_events(k))]
+                actors = list(range(most, most + k))
+                clones = [(j, device.COM_CLONE, b"", 1) for j in actors]
+                destroys = [(j, device.COM_DESTROY, b"", 1) for j in actors]
+                before = roster._clones.copy()
+                made, gone = roster.clone_many(clones, **settings), roster.clone_many(destroys, **settings)
+                if made.outcome.tolist() != clone_model(room_of, actors, False) or gone.outcome.tolist() != clone_model(room_of, actors, True):
+                    raise SystemExit(f"devpath: clone {k}, {colour}: the .clone and the .destroy call differ from the model's")
+                if not np.array_equal(roster._clones, before):
+                    raise SystemExit(f"devpath: clone {k}, {colour}: the .destroy call does not end where the .clone call began")
+                first = roster.clone_many(csays, **settings)           # it uploads the records: the timed .csay calls upload none
+                for i, t in enumerate(lines):
+                    ok = (first.outcome[i] == device.CLONE_SAID and first.said_text(i) == t and first.record[i] == i
+                          and all(first.said.chunks(i, c) == nuts_path.chunks(t, c) for c in (0, 1)))
+                    if not ok:
+                        raise SystemExit(f"devpath: clone {k}, {colour}: .csay event {i} differs from the reference's format or the "
+                                         f"CPU's transducer")
+
+                def cpu():
+                    for j, ev in enumerate(says):
+                        text = b"Clone of User%d %ss: %s\n" % (j, nuts_path.lib().np_say_verb(ev[2]), ev[2])
+                        nuts_path.chunks(text, 0)
+                        nuts_path.chunks(text, 1)
+
+                timed = _timed(f"clone {k}, {colour}", {"csay": lambda: roster.clone_many(csays, **settings),
+                                                        "speak": lambda: roster.speak_many(says), "cpu": cpu}, reps, warmup)
+                roster.set_clones(0, hear=device.CLONE_HEAR_ALL)       # every timed .clone call uploads the records, the first too
+                there = _timed(f"clone {k}, {colour}", {"clone": lambda: roster.clone_many(clones, **settings),
+                                                        "destroy": lambda: roster.clone_many(destroys, **settings)}, reps, warmup)
+                dev, sp, cpu_us = timed["csay"], timed["speak"], timed["cpu"].host_us
+                cases.append({"n": n, "k": k, "colour": colour, "rooms": nr, "records": 2 * most, **dev.fields, "speak": sp.fields,
+                              "cpu_us": cpu_us,
+                              "csay_over_speak": {f: round(dev.times[f]["median"] / sp.times[f]["median"], 2) for f in FIELDS},
+                              # the loosest the rounds allow: the one side's p10 over the other's p90, and the other way round
+                              "csay_over_speak_p10_p90": {f: [round(dev.times[f]["p10"] / sp.times[f]["p90"], 2),
+                                                              round(dev.times[f]["p90"] / sp.times[f]["p10"], 2)] for f in FIELDS},
+                              "end_to_end_over_cpu": float(f"{dev.times['end_to_end_us']['median'] / cpu_us['median']:.3g}"),
+                              "created": made.outcome.tolist().count(device.CLONE_CREATED),
+                              "deferred": made.outcome.tolist().count(device.CLONE_DEFERRED),
+                              "clone": there["clone"].fields, "destroy": there["destroy"].fields})
+    return {"clone_kernels": list(device.CLONE_KERNELS) + ["nuts_roster_speak_plan"],
+            "clone_end_to_end_covers": "packing the K events into pinned memory, one H2D (the events; in the .clone and the "
+                                       ".destroy call also the clone records, which the call before changed: 9 bytes a record "
+                                       "in three 256-byte slices), three kernels -- get_room, get_user, the two walks of the "
+                                       "records, the decision chain and the texts; the deferral walk; both variants of every "
+                                       "text and the room lines' admit bitmaps --, one D2H at the bound size, one synchronise "
+                                       "(python_us adds checking the events, the copies out of pinned memory, building the Clone "
+                                       "and applying it to the host mirrors through set_clones)",
+            "clone_speak_covers": "speak_many of the same K bodies as says by the same K users, at the same roster, in the same "
+                                  "rounds: two kernels, two texts an event where the .csay call has one of its six",
+            "clone_cpu_us_covers": "np_say_verb, the reference's format in Python and np_write_user_stream of the CPU "
+                                   "restatement (nuts_path, through ctypes) over both variants of every said line",
+            "clone": cases}
+
+
 RELAY_CLONES = 64
 
 
@@ -1159,6 +1264,9 @@ SECTIONS = (
     ("access", "K[,K...]", "also time K .private events per Roster.access_many call at a 1000-slot roster over the six default "
                            "rooms, and K .public events in the next, for each K, beside plan_many of the same lines and the CPU "
                            "modelling the call and transducing the lines (the access section)", "access_cases"),
+    ("clone", "K[,K...]", "also time K .csay events by K owners per Roster.clone_many call at a 1000-slot roster over the six "
+                          "default rooms, for each K, beside speak_many of the same bodies and the CPU composing and transducing "
+                          "the lines, and K .clone events, then K .destroy events (the clone section)", "clone_cases"),
 )
 
 
