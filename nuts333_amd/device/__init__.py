@@ -83,6 +83,14 @@ calls read: K ``(slot, com, inpstr, word_count)`` events with ``com`` COM_CLONE,
 :class:`Clone`.  The device runs ``get_room``, ``get_user``, a walk of the records and the head-count of a room a destroyed
 clone leaves, decides and composes the six texts with their plans; an event whose owner or room an earlier one of the same
 call touched is deferred; the binding creates, destroys and sets the records in the host mirrors and keeps them in list order.
+``Roster.set_many(events)`` answers the third group of commands that change what the other calls read, the fields a user
+sets on itself and the topic of its room: K ``(slot, com, inpstr, word_count)`` events with ``com`` one of the fourteen
+SET_COMS -- ``.mode``, ``.ignall``, ``.prompt``, ``.desc``, ``.inphr``, ``.outphr``, ``.topic``, ``.vis``, ``.invis``,
+``.charecho``, ``.afk``, ``.colour``, ``.ignshout`` and ``.igntell`` -- as the reference's twelve functions do
+(nuts333.c:4009, 4463-4539, 4697, 6434, 6881, 7409-7507) -- a :class:`Settings`.  These commands need no ``get_user``, no
+``get_room`` and no walk over the roster: a wave per event reads its actor's own rows, decides and composes the actor's two
+lines and the room's line, with their plans; an event that an earlier one of the same call touched is deferred; the binding
+sets the flags, the texts and the topic in the host mirrors.
 
 Input is validated before the device is touched (``ValueError``).  The library ``_build/libnuts_device.so`` is built by
 ``__graft_entry__.build()`` where ``hipcc`` exists, and on demand here when it is missing or older than its source.
@@ -153,6 +161,8 @@ _TELL_SLACK = 96
 AFK_MESG_LEN, _AFK_ROW = 60, 64
 #: the flags byte of a slot's speaker state, as fanout.hip reads it
 SPEECH_FLAGS = {"vis": 1, "muzzled": 2, "command_mode": 4, "afk": 8, "igntell": 16}
+#: the two bits of that byte only set_many reads (kPrompt, kCharecho of fanout.hip)
+SET_FLAGS = {"prompt": 32, "charmode_echo": 64}
 #: where a slot's speaker state keeps the speaker's level, and the highest one (enum np_level: NEW 0 .. GOD 4)
 _LEVEL_BYTE, MAX_LEVEL = 14, 4
 #: what became of a read (Input.kind): a telnet IAC reply, a line without a word, "." alone, a line exec_com answers
@@ -335,6 +345,38 @@ MAX_CLONE_HERE, MAX_CLONE_THERE, MAX_CLONE_RESET, MAX_CLONE_REPLY, MAX_CLONE_NOT
 _CLONE_ROWS = (48, 68, 36, 88, 84)
 #: the texts of an event in a Clone, in that order: the four room lines first, then the two single-recipient texts
 CLONE_HERE, CLONE_THERE, CLONE_RESET, CLONE_SAID_LINE, CLONE_REPLY, CLONE_NOTICE = range(6)
+#: the commands a user sets its own state with (NP_MODE .. NP_IGNTELL of enum np_com), and the kernels set_many runs before
+#: nuts_roster_speak_plan
+(COM_MODE, COM_IGNALL, COM_PROMPT, COM_DESC, COM_INPHR, COM_OUTPHR, COM_TOPIC, COM_VIS, COM_INVIS, COM_CHARECHO, COM_AFK, COM_COLOUR,
+ COM_IGNSHOUT, COM_IGNTELL) = 2, 11, 12, 13, 14, 15, 20, 55, 56, 66, 82, 84, 85, 86
+SET_COMS = (COM_MODE, COM_IGNALL, COM_PROMPT, COM_DESC, COM_INPHR, COM_OUTPHR, COM_TOPIC, COM_VIS, COM_INVIS, COM_CHARECHO, COM_AFK,
+            COM_COLOUR, COM_IGNSHOUT, COM_IGNTELL)
+SET_KERNELS = ("nuts_roster_set", "nuts_roster_set_order")
+#: what became of such an event (Settings.outcome), a branch of the reference each.  The first 22 changed something: the
+#: toggles by the flag they found -- ``toggle_mode``, ``toggle_ignall``, ``toggle_prompt`` --, a description, an in phrase, an
+#: out phrase and a topic set, a user who became visible or invisible, ``toggle_charecho``, AFK and AFK with the session
+#: locked, ``toggle_colour``, ``toggle_ignshout`` and ``toggle_igntell``.  Then what changed nothing: the video test of
+#: ``toggle_colour``, whose twenty lines are the caller's (COLOUR_TEST); of ``set_desc`` the query, ``(CLONE)`` in the first
+#: word and a description too long; of ``set_iophrase`` a phrase too long and the two queries; of ``set_topic`` the query
+#: without a topic, the query and a topic too long; already visible, already invisible; an AFK message too long; and
+#: SET_DEFERRED, an event the caller submits again
+(SET_MODE_COMMAND, SET_MODE_SPEECH, SET_IGNALL_ON, SET_IGNALL_OFF, SET_PROMPT_ON, SET_PROMPT_OFF, SET_DESC_SET, SET_INPHR_SET,
+ SET_OUTPHR_SET, SET_TOPIC_SET, SET_VISIBLE, SET_INVISIBLE, SET_CHARECHO_ON, SET_CHARECHO_OFF, SET_AFK, SET_AFK_LOCKED, SET_COLOUR_ON,
+ SET_COLOUR_OFF, SET_IGNSHOUT_ON, SET_IGNSHOUT_OFF, SET_IGNTELL_ON, SET_IGNTELL_OFF, SET_COLOUR_TEST, SET_DESC_QUERY, SET_DESC_CLONE,
+ SET_DESC_LONG, SET_PHRASE_LONG, SET_INPHR_QUERY, SET_OUTPHR_QUERY, SET_TOPIC_NONE, SET_TOPIC_QUERY, SET_TOPIC_LONG,
+ SET_ALREADY_VISIBLE, SET_ALREADY_INVISIBLE, SET_AFK_LONG, SET_DEFERRED) = range(36)
+#: the longest texts of such an event before the transducer (kSetHereMax .. kSetReply2Max of fanout.hip, pinned by a host
+#: test): a 12-byte name, `` has set the topic to: ``, a 60-byte topic and the newline; ``The current topic is: ``, a topic and
+#: the newline; ``AFK message set.\n``
+MAX_SET_HERE, MAX_SET_REPLY, MAX_SET_REPLY2 = USER_NAME_LEN + 23 + TOPIC_LEN + 1, 22 + TOPIC_LEN + 1, 17
+#: their slots among a set call's texts (kSetHereRow .. kSetReply2Row), laid out as _ACCESS_ROWS lays an access call's
+_SET_ROWS = (96, 84, 20)
+#: the texts of an event in a Settings, in that order: the room line first, then the actor's two
+SET_HERE, SET_REPLY, SET_REPLY2 = range(3)
+#: the names of colcom[1 .. 20] (nuts333.c colcom, without ``RS`` at 0), and the twenty lines the video test of ``.colour``
+#: writes, a ``write_user`` each (nuts333.c:7466-7469): what the caller sends for SET_COLOUR_TEST
+_COLCOM = ("OL", "UL", "LI", "RV", "FK", "FR", "FG", "FY", "FB", "FM", "FT", "FW", "BK", "BR", "BG", "BY", "BB", "BM", "BT", "BW")
+COLOUR_TEST = tuple(f"{c}: ~{c}NUTS 3 VIDEO TEST~RS\n".encode() for c in _COLCOM)
 #: a look room's row of the names relay_many uploads (kRelayNameRow of fanout.hip): 20 bytes of name padded with zeros, then
 #: its length; and what a relay text is longer than its broadcast at most, ``~FT[ `` + a 20-byte name + `` ]:~RS ``
 #: (kRelaySlack): its slot among a relay call's relay texts is that much wider than the text
@@ -1035,6 +1077,52 @@ class Clone:
 
 
 @dataclass
+class Settings:
+    """What the commands a user sets its own state with write for K events (``Roster.set_many``), shaped like an
+    :class:`Access`.  ``outcome[k]`` is one of the SET_* constants.  ``reply`` plans the actor's first ``write_user``,
+    ``reply2`` its second -- only an ``.afk`` that set a message has one, ``"AFK message set.\\n"``, a ``write(2)`` of its own
+    -- and ``here`` the line ``write_room_except(user->room, text, user)`` sends: the actor's room without the actor,
+    without ``login`` slots and without ``ignall`` listeners.  They are ordinary plans over the roster as it was before the
+    call and share one variant buffer; a text that is not there has size -1, nobody admitted and both variants 0 bytes in 0
+    writes.  A SET_DEFERRED event has no text at all; SET_COLOUR_TEST has none either, its twenty lines are COLOUR_TEST.
+
+    ``reply_colour[k]`` is the colour the actor's two replies are written with: the roster's flag, but 1 for SET_COLOUR_ON
+    and SET_COLOUR_OFF, since the reference writes both while ``user->colour`` is 1 (it sets the flag before the write and
+    clears it after, nuts333.c:7472-7479).  A ``.colour`` reply is therefore delivered by ``reply_colour``, not by
+    ``reply.colour_bits``, which hold the flags before the call.
+
+    Delivery, per client: the events in call order, and of one event ``reply``, ``reply2``, ``here`` (the reference's order
+    of writes).  A roster with clone records passes the here lines through ``relay_many``."""
+    outcome: np.ndarray           # int8 [K]
+    reply: Plan
+    reply2: Plan
+    here: Plan
+    reply_colour: np.ndarray      # uint8 [K]
+    texts: np.ndarray             # uint8, flat: the composed texts; gaps are allowed and unspecified
+    text_starts: np.ndarray       # int64 [3, K]   rows SET_HERE, SET_REPLY, SET_REPLY2
+    text_sizes: np.ndarray        # int64 [3, K]   -1: there is no such text
+    timing: dict = field(default_factory=dict)
+
+    _text = Speech._text
+
+    def reply_text(self, k: int) -> bytes:
+        """The first line event ``k`` sends to its actor; ``b""`` for a deferred event and for the video test."""
+        return self._text(SET_REPLY, k)
+
+    def reply2_text(self, k: int) -> bytes:
+        """The second line event ``k`` sends to its actor; ``b""`` when there is none."""
+        return self._text(SET_REPLY2, k)
+
+    def here_text(self, k: int) -> bytes:
+        """The line event ``k`` sends to its actor's room without the actor; ``b""`` when there is none."""
+        return self._text(SET_HERE, k)
+
+    def effective(self) -> np.ndarray:
+        """The events that changed something, ascending."""
+        return np.flatnonzero((self.outcome >= 0) & (self.outcome <= SET_IGNTELL_OFF))
+
+
+@dataclass
 class Input:
     """What ``user_input()`` and ``exec_com()`` make of K reads (``Roster.input_many``).  ``kind[k]`` is IAC, EMPTY,
     REPEAT, UNKNOWN, SPEECH or COMMAND; ``com[k]`` the command (enum np_com) of a SPEECH or COMMAND read, else -1;
@@ -1095,6 +1183,20 @@ def _as_text(t) -> bytes:
     if len(t) >= TEXT_SIZE:
         raise ValueError(f"text of {len(t)} bytes: the talker's text buffer holds at most {TEXT_SIZE - 1}")
     return t
+
+
+def _remove_first(inpstr: bytes) -> bytes:
+    """``remove_first()`` (nuts333.c:2350-2358): ``inpstr`` behind its first word and the blanks around it.  A word byte
+    is above 32 as a signed char."""
+    word = lambda c: 32 < c < 128
+    pos, n = 0, len(inpstr)
+    while pos < n and not word(inpstr[pos]):
+        pos += 1
+    while pos < n and word(inpstr[pos]):
+        pos += 1
+    while pos < n and not word(inpstr[pos]):
+        pos += 1
+    return inpstr[pos:]
 
 
 def _flag(name: str, v) -> int:
@@ -1274,6 +1376,8 @@ def _load():
         lib.nd_roster_clone.argtypes = ([ctypes.c_int, ctypes.c_int, P, ctypes.c_int64, P, P, P, P, P, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, ctypes.c_int] + [P] * 18 + [ctypes.POINTER(_RosterTiming)])
         lib.nd_roster_clone.restype = ctypes.c_int
+        lib.nd_roster_set.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int64] + [P] * 19 + [ctypes.POINTER(_RosterTiming)]
+        lib.nd_roster_set.restype = ctypes.c_int
         lib.nd_roster_clones.argtypes = [ctypes.c_int, ctypes.c_int]
         lib.nd_roster_clones.restype = ctypes.c_int
         lib.nd_roster_relay.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int64] + [P] * 22 + [ctypes.POINTER(_RosterTiming)]
@@ -1504,6 +1608,9 @@ class Roster:
         # afk and igntell live in the speaker mirror's flags byte, but only tell_many reads them: an update of theirs
         # alone makes tell_many upload the speaker mirror, and no other call
         self._private_dirty = False
+        # prompt and charmode_echo live in that byte too, and only set_many reads them: an update of theirs alone makes
+        # set_many upload the speaker mirror, and no other call
+        self._set_dirty = False
         # the AFK messages' mirror, as nd_roster_tell takes it: 64 bytes per slot -- the message padded with zeros, then
         # its length at byte AFK_MESG_LEN.  Only tell_many uploads it, after an update of afk_mesg
         self._afk = np.zeros((self.capacity, _AFK_ROW), dtype=np.uint8)
@@ -1576,7 +1683,7 @@ class Roster:
     def update(self, slots, *, room=_KEEP, login=_KEEP, ignall=_KEEP, ignshout=_KEEP, colour=_KEEP, name=_KEEP,
                vis=_KEEP, muzzled=_KEEP, command_mode=_KEEP, level=_KEEP, afk=_KEEP, igntell=_KEEP,
                afk_mesg=_KEEP, desc=_KEEP, last_login=_KEEP, away=_KEEP, in_phrase=_KEEP, out_phrase=_KEEP,
-               invite_room=_KEEP) -> None:
+               invite_room=_KEEP, prompt=_KEEP, charmode_echo=_KEEP) -> None:
         """Set fields of ``slots`` (a slot or a sequence of them).  Each field given is one value for every slot or a
         sequence of one per slot; a field not given stays as it is.  ``room`` is None (no room) or an int in
         [0, ROOM_LIMIT); the flags are 0/1 or bools.  A slot given more than once takes its last values.  Nothing
@@ -1606,7 +1713,12 @@ class Roster:
         ``in_phrase`` and ``out_phrase`` (bytes or str of 0 .. PHRASE_LEN bytes, no NUL; ``enters`` and ``goes`` at first, as
         a new user's are, nuts333.c:1575-1576) are what a walking user's room lines say, and ``invite_room`` (None at first,
         or a look room) the private room a user may enter by invitation.  They live in a mirror of their own, 88 bytes per
-        slot, that only :meth:`go_many` uploads: an update of these three alone marks no other mirror."""
+        slot, that only :meth:`go_many` uploads: an update of these three alone marks no other mirror.
+
+        ``prompt`` and ``charmode_echo`` (0/1, 0 at first) are ``user->prompt`` and ``user->charmode_echo``, which
+        ``.prompt``, ``.charecho`` and the video test of ``.colour`` read.  They live in the last two bits of the speaker
+        mirror's flags byte, with a dirty flag of their own: only :meth:`set_many` uploads after an update of these two
+        alone."""
         self._check_open()
         if isinstance(slots, (int, np.integer)):
             slots = [slots]
@@ -1641,7 +1753,7 @@ class Roster:
                 names = [_speaker_name(x) for x in name]
         speech = {f: per_slot(f, v, lambda x, f=f: _flag(f, x), np.uint8)
                   for f, v in (("vis", vis), ("muzzled", muzzled), ("command_mode", command_mode), ("afk", afk),
-                               ("igntell", igntell)) if v is not _KEEP}
+                               ("igntell", igntell), ("prompt", prompt), ("charmode_echo", charmode_echo)) if v is not _KEEP}
         levels = None if level is _KEEP else per_slot("level", level, _level, np.uint8)
         mesgs = None
         if afk_mesg is not _KEEP:
@@ -1697,7 +1809,7 @@ class Roster:
                 self._speech[j, :len(names[p])] = np.frombuffer(names[p], dtype=np.uint8)
                 self._speech[j, USER_NAME_LEN] = len(names[p])
         for f, v in speech.items():
-            bit, col = np.uint8(SPEECH_FLAGS[f]), self._speech[:, USER_NAME_LEN + 1]
+            bit, col = np.uint8(SPEECH_FLAGS.get(f) or SET_FLAGS[f]), self._speech[:, USER_NAME_LEN + 1]
             col[at] = np.where(v[keep] != 0, col[at] | bit, col[at] & ~bit)
         if levels is not None:
             self._speech[at, _LEVEL_BYTE] = levels[keep]
@@ -1729,10 +1841,12 @@ class Roster:
             self._go_invite[at] = invites[keep]
         if phrases or invites is not None:
             self._go_dirty = True
-        if names is not None or levels is not None or speech.keys() - {"afk", "igntell"}:
+        if names is not None or levels is not None or speech.keys() - {"afk", "igntell", "prompt", "charmode_echo"}:
             self._speech_dirty = True
         if speech.keys() & {"afk", "igntell"}:
             self._private_dirty = True
+        if speech.keys() & {"prompt", "charmode_echo"}:
+            self._set_dirty = True
         if rooms is not None or flags or not (names is not None or speech or levels is not None or mesgs is not None
                                               or descs is not None or logins is not None or aways is not None
                                               or phrases or invites is not None):
@@ -3201,6 +3315,175 @@ class Roster:
             made = created >= 0
             created[made] = moved[created[made]]
         return clone
+
+    def _prepare_set(self, events):
+        """Each (slot, com, inpstr, word_count) and its actor's state checked, packed for nd_roster_set: the inpstr, their
+        offsets and lengths, the slots, the commands and the word counts."""
+        if isinstance(events, (str, bytes, bytearray, np.ndarray)) or not hasattr(events, "__len__"):
+            raise ValueError(f"events must be a sequence of tuples, not {type(events).__name__}")
+        if len(events) == 0:
+            raise ValueError("empty call: no events")
+        if len(events) * self.capacity >= 2**31 - 1:
+            raise ValueError(f"{len(events)} events to {self.capacity} slots: K x capacity must be below 2^31 - 1")
+        bound = _variant_at(sum(_SET_ROWS) * len(events), 3 * len(events))
+        if bound > MANY_ARENA_CAP:
+            raise ValueError(f"call too large: its variant bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
+                             f"(MANY_ARENA_CAP): split it")
+        texts, slots, coms, wcs = [], [], [], []
+        for k, ev in enumerate(events):
+            if not isinstance(ev, tuple) or len(ev) != 4:
+                raise ValueError(f"event {k}: expected a (slot, com, inpstr, word_count) tuple, "
+                                 f"got {type(ev).__name__}{f' of {len(ev)}' if isinstance(ev, tuple) else ''}")
+            slot, com, inpstr, wc = ev
+            try:
+                slot = self._slot(slot)
+                if not _is_int(com, 0, NUM_COMMANDS - 1) or com not in SET_COMS:
+                    raise ValueError(f"com must be one of the fourteen commands of SET_COMS {SET_COMS}, not {com!r}")
+                text = _as_text(inpstr)
+                if len(text) >= ARR_SIZE:
+                    raise ValueError(f"inpstr of {len(text)} bytes: the talker's input line holds at most {ARR_SIZE - 1}")
+                if not _is_int(wc, 0, MAX_WORDS):
+                    raise ValueError(f"word_count must be an int in [0, {MAX_WORDS}], not {wc!r}")
+                if self._room[slot] < 0:
+                    raise ValueError(f"the actor, slot {slot}, is in no room")
+                if self._flags[slot] & ROSTER_FLAGS["login"]:
+                    raise ValueError(f"the actor, slot {slot}, is still logging in")
+                if self._speech[slot, USER_NAME_LEN] == 0:
+                    raise ValueError(f"the actor, slot {slot}, has no name")
+                if com == COM_TOPIC and not self._room[slot] < self.look_rooms:
+                    raise ValueError(f"a .topic by slot {slot} in room {int(self._room[slot])}, which has no room record "
+                                     f"(look_rooms is {self.look_rooms})")
+            except ValueError as e:
+                raise ValueError(f"event {k}: {e}") from None
+            texts.append(text)
+            slots.append(slot)
+            coms.append(int(com))
+            wcs.append(int(wc))
+        lens = np.fromiter((len(t) for t in texts), dtype=np.int64, count=len(texts))
+        if int(lens.sum()) >= 2**31 // 32:
+            raise ValueError("call text larger than 64 MiB: split it")
+        return (texts, _offsets(lens, np.int32), lens.astype(np.int32), np.array(slots, dtype=np.int32),
+                np.array(coms, dtype=np.uint8), np.array(wcs, dtype=np.uint8))
+
+    def set_many(self, events) -> Settings:
+        """K events by which a user sets its own state, decided and composed on the device: a non-empty sequence of
+        ``(slot, com, inpstr, word_count)`` tuples, what a COMMAND read of :meth:`input_many` hands back, with ``com`` one
+        of the fourteen SET_COMS: COM_MODE, COM_IGNALL, COM_PROMPT, COM_DESC, COM_INPHR, COM_OUTPHR, COM_TOPIC, COM_VIS,
+        COM_INVIS, COM_CHARECHO, COM_AFK, COM_COLOUR, COM_IGNSHOUT and COM_IGNTELL (``toggle_mode``, ``toggle_ignall``,
+        ``toggle_prompt``, ``set_desc``, ``set_iophrase``, ``set_topic``, ``visibility``, ``toggle_charecho``, ``afk``,
+        ``toggle_colour``, ``toggle_ignshout`` and ``toggle_igntell``, nuts333.c:4009, 4463-4539, 4697, 6434, 6881, 7409-7507).
+        Every actor needs a room, a name and no ``login`` flag; a slot may appear more than once.  A ``.topic`` needs
+        ``look_rooms >= 1`` and its actor's room in ``[0, look_rooms)``; the other thirteen need no room records.  Anything
+        else raises ``ValueError("event k: ...")`` before the device is touched, and a call whose variant bound exceeds
+        MANY_ARENA_CAP is refused.  A rejected call changes nothing.
+
+        The device does, per event and in the reference's branch order, with ``word[1]`` the first word of ``inpstr`` as
+        :meth:`go_many` takes it, cut at 39 bytes.  The six toggles have two outcomes each, by the flag before the call;
+        only ``.ignall`` has a ``here`` line, ``"<name> is now ignoring everyone.\\n"`` or ``"<name> is listening
+        again.\\n"``, with the real name even of an invisible actor.  ``.vis`` / ``.invis``: SET_ALREADY_VISIBLE,
+        SET_ALREADY_INVISIBLE, or SET_VISIBLE / SET_INVISIBLE with a ``here`` line that carries the real name.  ``.colour``:
+        SET_COLOUR_TEST when the actor has ``command_mode``, ``ignall`` and ``charmode_echo`` all set -- nothing is written
+        and nothing changes, the caller sends the twenty lines of COLOUR_TEST --, else SET_COLOUR_OFF or SET_COLOUR_ON,
+        whose reply is written with colour on either way (:class:`Settings`: ``reply_colour``).  ``.desc``: SET_DESC_QUERY
+        if ``word_count < 2``, which prints the kept ``desc``; SET_DESC_CLONE if ``word[1]`` contains ``(CLONE)``;
+        SET_DESC_LONG if ``inpstr`` is longer than USER_DESC_LEN; else SET_DESC_SET.  ``.inphr`` / ``.outphr``:
+        SET_PHRASE_LONG if ``inpstr`` is longer than PHRASE_LEN, first; then the query; then the set.  ``.topic``:
+        SET_TOPIC_NONE or SET_TOPIC_QUERY if ``word_count < 2``; SET_TOPIC_LONG past TOPIC_LEN; else SET_TOPIC_SET, with a
+        reply and a ``here`` line, ``"<name> has set the topic to: <inpstr>\\n"`` with ``invisname`` for an invisible actor.
+        ``.afk``: with ``word_count < 2`` no message is looked at; with ``word[1] == "lock"`` exactly the message is
+        ``remove_first(inpstr)`` and the outcome SET_AFK_LOCKED; else the message is the whole ``inpstr`` and the outcome
+        SET_AFK.  A message longer than AFK_MESG_LEN is SET_AFK_LONG, before anything is written.  A non-empty message
+        is stored and answered with ``reply2``, ``"AFK message set.\\n"``; an empty one keeps the old ``afk_mesg``.  A
+        visible actor's room gets ``"<name> goes AFK: <mesg>\\n"``, with the message as it stands after the store, or
+        ``"<name> goes AFK...\\n"``; an invisible actor's room gets nothing.  The ``here`` lines' ``com_num`` is the event's
+        ``com``.
+
+        Every event is decided and planned against the roster as it was before the call.  To keep that exact, event k is
+        SET_DEFERRED when an earlier effective event of the call, itself not deferred, had the same actor; or changed
+        ``ignall`` or ``colour`` of a slot in k's actor's room, and k has a ``here`` line; or set the topic of k's actor's
+        room, and k is a ``.topic``.  A deferred event wrote nothing and changed nothing, and the caller submits it again.
+        Queries and refusals touch nothing, and a call of one event never defers.
+
+        The binding then applies the effective events to the host mirrors in event order, through :meth:`update` and
+        ``set_rooms(topic=)``: the toggled flag; ``desc``, ``in_phrase``, ``out_phrase`` or the room's ``topic`` from
+        ``inpstr``; ``vis``; ``afk=1`` for both AFK outcomes (the roster keeps ``afk`` as a flag) and ``afk_mesg`` when a
+        message was set.  No kernel writes a kept table: the next call of any kind uploads what changed and sees it.
+
+        A call is one upload (the table, the speaker state, the AFK messages, the descriptions and the go mirror only
+        after an update of theirs; the room table only after one and when the call holds a ``.topic``), three kernel
+        launches (SET_KERNELS, then nuts_roster_speak_plan), one download at the bound size and one synchronise, whatever K
+        and the capacity.  The speaker state goes up when any of its three dirty flags is set, and all three are cleared.
+        Returns a :class:`Settings`.
+
+        Out of scope: the prompt; the return from AFK (nuts333.c:180-203), and the session lock itself, which stay with
+        the caller; remote users and "home execution"; the relay of the ``here`` lines to clones' owners -- the caller
+        passes them to :meth:`relay_many`, as after :meth:`access_many`; the commands' level check, which
+        :meth:`input_many` has already made."""
+        self._check_open()
+        inps, text_off, lens, slots, coms, wcs = self._prepare_set(events)
+        text = b"".join(inps)
+        lib = _load()
+        handle = self._device_handle(lib)
+        k, words = len(lens), (self.capacity + 63) // 64
+        ctext_bytes = sum(_SET_ROWS) * k
+        outcome, clen = np.empty(k, dtype=np.int8), np.empty((3, k), dtype=np.int32)
+        bits = np.zeros((3, k, words), dtype=np.uint64)             # the device's, then the actor alone twice
+        vn, vw = np.empty((3, k, 2), dtype=np.int64), np.empty((3, k, 2), dtype=np.int32)
+        vwsz = np.empty((3, k, 2, MAX_WRITES), dtype=np.int32)
+        ctext = np.empty(ctext_bytes, dtype=np.uint8)
+        var = np.empty(_variant_at(ctext_bytes, 3 * k), dtype=np.uint8)
+        tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
+        speech_dirty = self._speech_dirty or self._private_dirty or self._set_dirty
+        rooms_read = bool((coms == COM_TOPIC).any())
+        t = _RosterTiming()
+        rc = lib.nd_roster_set(handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(slots), _ptr(coms), _ptr(wcs),
+                               _ptr(self._table) if self._dirty else None, _ptr(self._speech) if speech_dirty else None,
+                               _ptr(self._afk) if self._afk_dirty else None, _ptr(self._udesc) if self._udesc_dirty else None,
+                               _ptr(self._go) if self._go_dirty else None,
+                               _ptr(self._rooms) if rooms_read and self._rooms_dirty else None,
+                               _ptr(outcome), _ptr(clen), _ptr(bits), _ptr(vn), _ptr(vw), _ptr(vwsz), _ptr(ctext), _ptr(var),
+                               ctypes.byref(t))
+        _check(rc, "device set failed")
+        self._dirty = self._speech_dirty = self._private_dirty = self._set_dirty = False
+        self._afk_dirty = self._udesc_dirty = self._go_dirty = False
+        if rooms_read:
+            self._rooms_dirty = False
+        rows = np.array(_SET_ROWS, dtype=np.int64)
+        tstarts = ((np.cumsum(rows) - rows) * k)[:, None] + rows[:, None] * np.arange(k, dtype=np.int64)
+        starts = _variant_starts(tstarts, clen)
+        for row in (SET_REPLY, SET_REPLY2):
+            has = np.flatnonzero(clen[row] >= 0)
+            bits[row, has, slots[has] // 64] = np.uint64(1) << (slots[has] % 64).astype(np.uint64)
+        timing = _timing_of(t)
+        colour = (self._flags & ROSTER_FLAGS["colour"]) != 0
+        colour_bits = _pack(colour)
+        reply_colour = colour[slots].astype(np.uint8)
+        reply_colour[(outcome == SET_COLOUR_ON) | (outcome == SET_COLOUR_OFF)] = 1
+        plans = [Plan(capacity=self.capacity, admitted_bits=bits[i], colour_bits=colour_bits, variants=var,
+                      variant_starts=starts[i], variant_sizes=vn[i], write_counts=vw[i], write_sizes=vwsz[i],
+                      timing=dict(timing)) for i in range(3)]
+        got = Settings(outcome=outcome, reply=plans[SET_REPLY], reply2=plans[SET_REPLY2], here=plans[SET_HERE],
+                       reply_colour=reply_colour, texts=ctext, text_starts=tstarts, text_sizes=clen.astype(np.int64), timing=timing)
+        # the changes, on the host mirrors and in event order: the next call of any kind uploads what it reads
+        toggles = {SET_MODE_COMMAND: ("command_mode", 1), SET_MODE_SPEECH: ("command_mode", 0), SET_IGNALL_ON: ("ignall", 1),
+                   SET_IGNALL_OFF: ("ignall", 0), SET_PROMPT_ON: ("prompt", 1), SET_PROMPT_OFF: ("prompt", 0), SET_VISIBLE: ("vis", 1),
+                   SET_INVISIBLE: ("vis", 0), SET_CHARECHO_ON: ("charmode_echo", 1), SET_CHARECHO_OFF: ("charmode_echo", 0),
+                   SET_COLOUR_ON: ("colour", 1), SET_COLOUR_OFF: ("colour", 0), SET_IGNSHOUT_ON: ("ignshout", 1),
+                   SET_IGNSHOUT_OFF: ("ignshout", 0), SET_IGNTELL_ON: ("igntell", 1), SET_IGNTELL_OFF: ("igntell", 0)}
+        texts_set = {SET_DESC_SET: "desc", SET_INPHR_SET: "in_phrase", SET_OUTPHR_SET: "out_phrase"}
+        for k in got.effective().tolist():
+            slot, oc = int(slots[k]), int(outcome[k])
+            if oc in toggles:
+                self.update(slot, **{toggles[oc][0]: toggles[oc][1]})
+            elif oc in texts_set:
+                self.update(slot, **{texts_set[oc]: inps[k]})
+            elif oc == SET_TOPIC_SET:
+                self.set_rooms(int(self._room[slot]), topic=inps[k])
+            elif clen[SET_REPLY2, k] >= 0:                              # SET_AFK, SET_AFK_LOCKED: a message was set
+                self.update(slot, afk=1, afk_mesg=inps[k] if oc == SET_AFK else _remove_first(inps[k]))
+            else:
+                self.update(slot, afk=1)
+        return got
 
     def set_clones(self, clones, *, owner=_KEEP, room=_KEEP, hear=_KEEP) -> None:
         """Set fields of the clone records ``clones`` (a record or a sequence of them, each in ``[0, clones)``), by the

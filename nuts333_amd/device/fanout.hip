@@ -31,6 +31,10 @@
 // then gives every text its two variants (its section below).
 // nuts_roster_relay answers the clone branch of write_room_except after nuts_roster_plan, in the same call: which of the
 // roster's clone records relay each broadcast to their owners, and the prefixed text they send (its section below).
+// nuts_roster_go, nuts_roster_access, nuts_roster_clone and nuts_roster_set decide and compose the commands that change what
+// the other kernels read -- a user's room, a room's access and the invitations, the clone records, and what a user sets on
+// itself -- each followed by a one-wave kernel that defers the events an earlier one of the call touched; none of them
+// writes a kept table (their sections below).
 //
 // Hard bounds per item of a text of len < 2000 bytes: 6*len + 4 output bytes (a '\n' with colour
 // on is the costliest input byte, plus the trailing reset) and 16 writes.  The host sizes its buffers
@@ -3796,6 +3800,339 @@ __device__ void roster_clone_order(const CloneOrderArgs& a)
     }
 }
 
+// ------------------------------------------------------------------ a user's own settings, of a resident roster
+//
+// toggle_mode (nuts333.c:4009), toggle_ignall (4463), toggle_prompt (4481), set_desc (4494), set_iophrase (4515), set_topic
+// (4697), visibility (6434), toggle_charecho (6881), afk (7409), toggle_colour (7458), toggle_ignshout (7484) and
+// toggle_igntell (7497): the fourteen commands a user sets its own state with, and the topic of its room.  They need no
+// get_user, no get_room and no walk over the roster: an event reads its actor's own rows -- the speaker state, the table's
+// flag byte, the AFK message, the description, the two phrases -- and for a .topic its room's record.  As with the door
+// commands the device decides and composes and writes no kept table; the host binding applies the result afterwards.
+// An event has three texts in slots of fixed width: the line write_room_except(user->room, text, user) sends ("here"), the
+// actor's first write_user ("reply") and its second ("reply2": "AFK message set.\n", a write(2) of its own).  With K events
+// text k is event k's here line, K + k its reply and 2K + k its reply2: the K room lines first, as nuts_roster_speak_plan
+// wants them.
+//   set      nuts_roster_set, ONE WAVE PER EVENT, four events per block, in the shape of nuts_roster_speak.  word[1] is
+//            found as nuts_roster_go finds it, and where remove_first stops as nuts_roster_tell finds it.  The wave
+//            decides in the reference's branch order, wave-uniformly, and composes: the reply from kSetReply, a fixed
+//            part per outcome and behind it, where the line quotes one, the kept description, phrase or topic or the
+//            inpstr; the here line with compose() / append().  Lane 0 stores the lengths, the outcome, and rm / sender /
+//            com of the here line.  No atomics: the same bytes on every run.
+//            Blocks past the events copy freshly uploaded tables into the kept allocations.
+//   order    nuts_roster_set_order, ONE WAVE, after nuts_roster_access_order.  An effective event touches its actor;
+//            one that toggles ignall or colour also its actor's room, as the admit bitmaps and the colour bits of that
+//            room's lines read them; a set topic the topic of its room.  An event whose actor an earlier event of the call
+//            that was not itself deferred touched, or which has a here line in a room so touched, or which is a .topic in
+//            a room whose topic was so set, is deferred: its outcome becomes kSetDeferred and its three texts void.  A
+//            room is known by its rank among the rooms of the call's actors (the host's, below 65,536 as the slots are).
+//   plan     nuts_roster_speak_plan with K room lines and 2K single-recipient texts.
+constexpr int kComMode = 2, kComIgnall = 11, kComPrompt = 12, kComDesc = 13, kComInphr = 14, kComOutphr = 15, kComTopic = 20,
+              kComVis = 55, kComInvis = 56, kComCharecho = 66, kComAfk = 82, kComColour = 84, kComIgnshout = 85,
+              kComIgntell = 86;                              // enum np_com
+constexpr uint8_t kPrompt = 32, kCharecho = 64;            // the last two bits of the flags byte of a slot's speaker state
+// the outcomes, the effective ones first: kSetModeCommand .. kSetIgntellOff changed something
+constexpr int kSetModeCommand = 0, kSetModeSpeech = 1, kSetIgnallOn = 2, kSetIgnallOff = 3, kSetPromptOn = 4, kSetPromptOff = 5,
+              kSetDescSet = 6, kSetInphrSet = 7, kSetOutphrSet = 8, kSetTopicSet = 9, kSetVisible = 10, kSetInvisible = 11,
+              kSetCharechoOn = 12, kSetCharechoOff = 13, kSetAfk = 14, kSetAfkLocked = 15, kSetColourOn = 16, kSetColourOff = 17,
+              kSetIgnshoutOn = 18, kSetIgnshoutOff = 19, kSetIgntellOn = 20, kSetIgntellOff = 21, kSetColourTest = 22,
+              kSetDescQuery = 23, kSetDescClone = 24, kSetDescLong = 25, kSetPhraseLong = 26, kSetInphrQuery = 27,
+              kSetOutphrQuery = 28, kSetTopicNone = 29, kSetTopicQuery = 30, kSetTopicLong = 31, kSetAlreadyVisible = 32,
+              kSetAlreadyInvisible = 33, kSetAfkLong = 34, kSetDeferred = 35;
+constexpr int kSetTexts = 3;                               // here, reply, reply2
+// the longest texts: name + " has set the topic to: " + a 60-byte topic + "\n"; "The current topic is: " + topic + "\n";
+// "AFK message set.\n"
+constexpr int kSetHereMax = kNameLen + 23 + kTopicLen + 1, kSetReplyMax = 22 + kTopicLen + 1, kSetReply2Max = 17;
+constexpr int kSetHereRow = 96, kSetReplyRow = 84, kSetReply2Row = 20;      // their slots
+constexpr int kSetRow = kSetHereRow + kSetReplyRow + kSetReply2Row;         // an event's bytes of composed text
+constexpr int set_row(int kind) { return kind == 0 ? kSetHereRow : kind == 1 ? kSetReplyRow : kSetReply2Row; }
+// Where text kind * k + b of a call of k events has its slot: the here lines, then the replies, then the second replies.
+constexpr int64_t set_text_at(int kind, int64_t b, int64_t k)
+{
+    return (kind == 0 ? 0 : kind == 1 ? kSetHereRow : kSetHereRow + kSetReplyRow) * k + set_row(kind) * b;
+}
+
+// The actor's first line by outcome: a fixed part, and whether a quoted text and a newline follow it.
+struct SetReply {
+    char pre[79];
+    uint8_t npre;
+    bool quotes;
+};
+template <int N>
+constexpr SetReply set_reply(const char (&pre)[N], bool quotes = false)
+{
+    static_assert(N <= 80, "set_reply: the part fits its field");
+    SetReply r{};
+    for (int i = 0; i < N - 1; i++) r.pre[i] = pre[i];
+    r.npre = N - 1;
+    r.quotes = quotes;
+    return r;
+}
+__device__ const SetReply kSetReply[] = {
+    set_reply("Now in COMMAND mode.\n"),                                                   // kSetModeCommand    c:4016
+    set_reply("Now in SPEECH mode.\n"),                                                    // kSetModeSpeech     c:4013
+    set_reply("You are now ignoring everyone.\n"),                                         // kSetIgnallOn       c:4467
+    set_reply("You will now hear everyone again.\n"),                                      // kSetIgnallOff      c:4473
+    set_reply("Prompt ~FGON.\n"),                                                          // kSetPromptOn       c:4488
+    set_reply("Prompt ~FROFF.\n"),                                                         // kSetPromptOff      c:4485
+    set_reply("Description set.\n"),                                                       // kSetDescSet        c:4510
+    set_reply("In phrase set.\n"),                                                         // kSetInphrSet       c:4529
+    set_reply("Out phrase set.\n"),                                                        // kSetOutphrSet      c:4538
+    set_reply("Topic set to: ", true),                                                     // kSetTopicSet       c:4716
+    set_reply("~FB~OLYou recite a melodic incantation and reappear.\n"),                   // kSetVisible        c:6442
+    set_reply("~FB~OLYou recite a melodic incantation and fade out.\n"),                   // kSetInvisible      c:6451
+    set_reply("Echoing for character mode clients ~FGON.\n"),                              // kSetCharechoOn     c:6885
+    set_reply("Echoing for character mode clients ~FROFF.\n"),                             // kSetCharechoOff    c:6889
+    set_reply("You are now AFK, press <return> to reset.\n"),                              // kSetAfk            c:7436, 7445
+    set_reply("You are now AFK with the session locked, enter your password to unlock it.\n"),   // kSetAfkLocked c:7425
+    set_reply("Colour ~FGON.\n"),                                                          // kSetColourOn       c:7478
+    set_reply("Colour ~FROFF.\n"),                                                         // kSetColourOff      c:7473
+    set_reply("You are now ignoring shouts and shout emotes.\n"),                          // kSetIgnshoutOn     c:7492
+    set_reply("You are no longer ignoring shouts and shout emotes.\n"),                    // kSetIgnshoutOff    c:7488
+    set_reply("You are now ignoring tells and private emotes.\n"),                         // kSetIgntellOn      c:7505
+    set_reply("You are no longer ignoring tells and private emotes.\n"),                   // kSetIgntellOff     c:7501
+    set_reply(""),                                                                         // kSetColourTest: the caller's twenty lines
+    set_reply("Your current description is: ", true),                                      // kSetDescQuery      c:4499
+    set_reply("You cannot have that description.\n"),                                      // kSetDescClone      c:4504
+    set_reply("Description too long.\n"),                                                  // kSetDescLong       c:4507
+    set_reply("Phrase too long.\n"),                                                       // kSetPhraseLong     c:4520
+    set_reply("Your current in phrase is: ", true),                                        // kSetInphrQuery     c:4524
+    set_reply("Your current out phrase is: ", true),                                       // kSetOutphrQuery    c:4533
+    set_reply("No topic has been set yet.\n"),                                             // kSetTopicNone      c:4707
+    set_reply("The current topic is: ", true),                                             // kSetTopicQuery     c:4709
+    set_reply("Topic too long.\n"),                                                        // kSetTopicLong      c:4714
+    set_reply("You are already visible.\n"),                                               // kSetAlreadyVisible c:6440
+    set_reply("You are already invisible.\n"),                                             // kSetAlreadyInvisible c:6449
+    set_reply("AFK message too long.\n"),                                                  // kSetAfkLong        c:7423, 7434
+};
+static_assert(sizeof(kSetReply) / sizeof(kSetReply[0]) == kSetDeferred, "kSetReply: a line for every outcome nuts_roster_set decides");
+
+struct SetArgs {
+    const int32_t* room;         // [capacity] the roster's table
+    const uint8_t* slotf;        // [capacity] and its flag bytes: ignall
+    const uint8_t* rooms;        // the tables this call reads, the uploads or the kept ones: the room records (nullptr: no .topic),
+    const uint8_t* go;           // [capacity * 88] the go table (the two phrases),
+    const uint8_t* afk;          // [capacity * 64] the AFK messages,
+    const uint8_t* udesc;        // [capacity * 32] the users' descriptions,
+    const uint8_t* speech;       // [capacity * 16] and the speaker state: name, vis, command_mode, afk, igntell, prompt, charmode_echo
+    Kept kept[5];                // in that order
+    const uint8_t* text;         // the K inpstr, packed
+    const int32_t* text_off;     // [k]
+    const int32_t* text_len;     // [k]
+    const int32_t* slot;         // [k] the actor
+    const uint8_t* com;          // [k] one of the fourteen commands
+    const uint8_t* words;        // [k] word_count
+    const int32_t* rid;          // [k] the rank of the actor's room among the rooms of the call's actors (nuts_roster_set_order)
+    const int32_t* ctext_off;    // [3k] where each text's slot starts in ctext
+    int k, capacity, blocks;     // blocks: those that compose; the ones after them copy the uploaded tables
+    int* violations;             // composed texts past their slot (zeroed by the host's upload)
+    uint8_t* ctext;              // the composed texts
+    int32_t* clen;               // [3k] their lengths; -1: no such text
+    int8_t* outcome;             // [k]
+    int32_t* rm;                 // [k] the here lines' rooms, as SpeakPlanArgs.rm
+    int32_t* sender;             // [k] and their senders
+    int32_t* com_num;            // [k]
+};
+
+__device__ void roster_set(const SetArgs& a)
+{
+    if ((int)blockIdx.x >= a.blocks) {      // the tables just uploaded, into the kept allocations: a word per lane
+        copy_kept(a.kept, ((int)blockIdx.x - a.blocks) * kBlock + (int)threadIdx.x);
+        return;
+    }
+    const int lane = (int)threadIdx.x & 63;
+    const int k = (int)blockIdx.x * (kBlock / 64) + ((int)threadIdx.x >> 6);      // wave-uniform
+    if (k >= a.k) return;
+    const int slot = a.slot[k], com = a.com[k], wc = a.words[k], len = a.text_len[k];
+    const uint8_t* in = a.text + a.text_off[k];
+    const uint8_t* sp = a.speech + (size_t)slot * kSpeechRec;
+    const uint8_t state = sp[kNameLen + 1], listens = a.slotf[slot];
+    const int here = a.room[slot];
+    const bool vis = (state & kVis) != 0;
+
+    // word[1] as np_wordfind finds the line's second word (c:417-432), and where remove_first stops behind it (c:2350-2358)
+    uint32_t wordb = 0;
+#pragma unroll
+    for (int x = 0; x < kReadSlice; x++) {
+        const int at = kReadSlice * lane + x;
+        wordb |= (uint32_t)(at < len && (int8_t)in[at] > 32) << x;
+    }
+    const int w0 = first_from(wordb, 0, lane, len);
+    const int w0_end = first_from(~wordb & 0xffffu, w0, lane, len);
+    const int rest = first_from(wordb, w0_end, lane, len);
+    const int wlen = w0_end - w0 < kWordLen ? w0_end - w0 : kWordLen;
+    const uint8_t* word = in + w0;
+
+    // the kept text a query quotes, the text a set stores, the message an .afk takes
+    Piece quoted{nullptr, 0};
+    const uint8_t* mesg = in;               // afk: the whole inpstr, or what follows "lock"
+    int mesg_len = len;
+    int outcome;
+    if (com == kComMode) outcome = (state & kCommandMode) ? kSetModeSpeech : kSetModeCommand;               // c:4012-4017
+    else if (com == kComIgnall) outcome = (listens & kIgnall) ? kSetIgnallOff : kSetIgnallOn;              // c:4466-4476
+    else if (com == kComPrompt) outcome = (state & kPrompt) ? kSetPromptOff : kSetPromptOn;                // c:4484-4489
+    else if (com == kComCharecho) outcome = (state & kCharecho) ? kSetCharechoOff : kSetCharechoOn;        // c:6884-6891
+    else if (com == kComIgnshout) outcome = (listens & kIgnshout) ? kSetIgnshoutOff : kSetIgnshoutOn;      // c:7487-7493
+    else if (com == kComIgntell) outcome = (state & kIgntell) ? kSetIgntellOff : kSetIgntellOn;            // c:7500-7506
+    else if (com == kComVis) outcome = vis ? kSetAlreadyVisible : kSetVisible;                             // c:6438-6445
+    else if (com == kComInvis) outcome = vis ? kSetInvisible : kSetAlreadyInvisible;                       // c:6448-6454
+    else if (com == kComColour) {           // c:7465-7479
+        if ((state & kCommandMode) && (listens & kIgnall) && (state & kCharecho)) outcome = kSetColourTest;
+        else outcome = (listens & kColour) ? kSetColourOff : kSetColourOn;
+    } else if (com == kComDesc) {           // c:4498-4510
+        const bool clone = __ballot(lane + 7 <= wlen && word[lane] == '(' && word[lane + 1] == 'C' && word[lane + 2] == 'L' &&
+                                    word[lane + 3] == 'O' && word[lane + 4] == 'N' && word[lane + 5] == 'E' && word[lane + 6] == ')') != 0;
+        const uint8_t* d = a.udesc + (size_t)slot * kUserDescRow;
+        quoted = Piece{d, d[kUserDescLen] < kUserDescLen ? d[kUserDescLen] : kUserDescLen};
+        outcome = wc < 2 ? kSetDescQuery : clone ? kSetDescClone : len > kUserDescLen ? kSetDescLong : kSetDescSet;
+    } else if (com == kComInphr || com == kComOutphr) {     // c:4519-4538
+        const uint8_t* g = a.go + (size_t)slot * kGoRec;
+        const bool inp = com == kComInphr;
+        const int n = g[inp ? kGoInLen : kGoOutLen];
+        quoted = Piece{g + (inp ? kGoIn : kGoOut), n < kPhraseLen ? n : kPhraseLen};
+        outcome = len > kPhraseLen ? kSetPhraseLong : wc < 2 ? (inp ? kSetInphrQuery : kSetOutphrQuery) : inp ? kSetInphrSet : kSetOutphrSet;
+    } else if (com == kComTopic) {          // c:4705-4721
+        const uint8_t* rec = a.rooms + (size_t)here * kRoomRec;        // a look room: the host checked it
+        quoted = Piece{rec + kRrTopic, rec[kRrTopicLen] < kTopicLen ? rec[kRrTopicLen] : kTopicLen};
+        if (wc < 2) outcome = quoted.n ? kSetTopicQuery : kSetTopicNone;
+        else {
+            outcome = len > kTopicLen ? kSetTopicLong : kSetTopicSet;
+            quoted = Piece{in, len};
+        }
+    } else {                                // afk, c:7413-7447
+        outcome = kSetAfk;
+        if (wc > 1) {
+            const bool lock = w0_end - w0 == 4 && word[0] == 'l' && word[1] == 'o' && word[2] == 'c' && word[3] == 'k';
+            if (lock) {
+                outcome = kSetAfkLocked;
+                mesg = in + rest;
+                mesg_len = len - rest;
+            }
+            if (mesg_len > kAfkMesgLen) outcome = kSetAfkLong;
+        } else mesg_len = 0;                // c:7445: the message is not looked at
+    }
+
+    const int n = a.k;
+    uint8_t* here_t = a.ctext + a.ctext_off[k];
+    uint8_t* reply_t = a.ctext + a.ctext_off[n + k];
+    uint8_t* reply2_t = a.ctext + a.ctext_off[2 * n + k];
+    const Piece none{nullptr, 0};
+    const Piece nothing[5] = {none, none, none, none, none};
+    const Piece name{sp, sp[kNameLen] < kNameLen ? sp[kNameLen] : kNameLen};
+    int here_len = -1, reply_len = -1, reply2_len = -1;
+    bool lines = false;                     // the event has a here line
+    if (outcome != kSetColourTest) {        // the actor's line: the outcome's fixed part, then what it quotes and a newline
+        const SetReply& fixed = kSetReply[outcome];
+        reply_len = compose(reply_t, kSetReplyRow, nothing, reinterpret_cast<const uint8_t*>(fixed.pre), fixed.npre, false, lane, a.violations);
+        if (fixed.quotes) append(reply_t, kSetReplyRow, reply_len, nothing, quoted.p, quoted.n, true, lane, a.violations);
+    }
+    if (outcome == kSetIgnallOn || outcome == kSetIgnallOff) {         // c:4468, 4474: user->name
+        const Piece h[5] = {name, outcome == kSetIgnallOn ? lit(" is now ignoring everyone.\n") : lit(" is listening again.\n"), none, none, none};
+        here_len = compose(here_t, kSetHereRow, h, nullptr, 0, false, lane, a.violations);
+        lines = true;
+    } else if (outcome == kSetVisible) {    // c:6443: user->name
+        const Piece h0[5] = {lit("~FB~OLYou hear a melodic incantation chanted and "), name, none, none, none};
+        const Piece h1[5] = {lit(" materialises!\n"), none, none, none, none};
+        here_len = compose(here_t, kSetHereRow, h0, nullptr, 0, false, lane, a.violations);
+        append(here_t, kSetHereRow, here_len, h1, nullptr, 0, false, lane, a.violations);
+        lines = true;
+    } else if (outcome == kSetInvisible) {  // c:6452
+        const Piece h0[5] = {lit("~FB~OL"), name, none, none, none};
+        const Piece h1[5] = {lit(" recites a melodic incantation and disappears!\n"), none, none, none, none};
+        here_len = compose(here_t, kSetHereRow, h0, nullptr, 0, false, lane, a.violations);
+        append(here_t, kSetHereRow, here_len, h1, nullptr, 0, false, lane, a.violations);
+        lines = true;
+    } else if (outcome == kSetTopicSet) {   // c:4718-4720: invisname for an invisible actor
+        const Piece h[5] = {vis ? name : lit("A presence"), lit(" has set the topic to: "), none, none, none};
+        here_len = compose(here_t, kSetHereRow, h, in, len, true, lane, a.violations);
+        lines = true;
+    } else if (outcome == kSetAfk || outcome == kSetAfkLocked) {       // c:7426-7429, 7437-7440, 7448-7453
+        if (mesg_len > 0) {
+            const Piece p[5] = {lit("AFK message set.\n"), none, none, none, none};
+            reply2_len = compose(reply2_t, kSetReply2Row, p, nullptr, 0, false, lane, a.violations);
+            if (reply2_len < 0) reply_len = -1;
+        } else {                            // the message kept from before
+            const uint8_t* m = a.afk + (size_t)slot * kAfkRec;
+            mesg = m;
+            mesg_len = m[kAfkMesgLen] < kAfkMesgLen ? m[kAfkMesgLen] : kAfkMesgLen;
+        }
+        if (vis) {
+            const Piece h[5] = {name, mesg_len > 0 ? lit(" goes AFK: ") : lit(" goes AFK...\n"), none, none, none};
+            here_len = compose(here_t, kSetHereRow, h, mesg, mesg_len, mesg_len > 0, lane, a.violations);
+            lines = true;
+        }
+    }
+    if ((outcome != kSetColourTest && reply_len < 0) || (lines && here_len < 0)) here_len = reply_len = reply2_len = -1;   // a violation: the call fails
+    if (lane == 0) {
+        a.clen[k] = here_len;
+        a.clen[n + k] = reply_len;
+        a.clen[2 * n + k] = reply2_len;
+        a.outcome[k] = (int8_t)outcome;
+        a.rm[k] = here;                     // write_room_except(user->room, text, user)
+        a.sender[k] = slot;
+        a.com_num[k] = com;
+    }
+}
+
+static_assert(kSetHereMax == 96 && kSetReplyMax == 83 && kSetReply2Max == 17 && kSetHereMax <= kSetHereRow && kSetReplyMax <= kSetReplyRow &&
+              kSetReply2Max <= kSetReply2Row, "roster_set: the longest texts fit their slots");
+static_assert(sizeof(" has set the topic to: ") - 1 == 23 && sizeof("The current topic is: ") - 1 == 22 && sizeof("AFK message set.\n") - 1 == 17 &&
+              sizeof("You are now AFK with the session locked, enter your password to unlock it.\n") - 1 <= kSetReplyMax &&
+              sizeof("Your current out phrase is: ") - 1 + kPhraseLen + 1 <= kSetReplyMax &&
+              sizeof("Your current description is: ") - 1 + kUserDescLen + 1 <= kSetReplyMax && sizeof("Topic set to: ") - 1 + kTopicLen + 1 <= kSetReplyMax &&
+              kNameLen + sizeof(" goes AFK: ") - 1 + kAfkMesgLen + 1 <= kSetHereMax &&
+              sizeof("~FB~OLYou hear a melodic incantation chanted and  materialises!\n") - 1 + kNameLen <= kSetHereMax &&
+              sizeof("~FB~OL recites a melodic incantation and disappears!\n") - 1 + kNameLen <= kSetHereMax &&
+              kNameLen + sizeof(" is now ignoring everyone.\n") - 1 <= kSetHereMax, "roster_set: the texts are as long as counted");
+static_assert(kSetRow % 4 == 0 && kSetHereRow % 4 == 0 && kSetReplyRow % 4 == 0 && kSetHereRow < kTextSize,
+              "roster_set: the rows are whole words, and a text fits speak_plan's LDS text");
+static_assert(sizeof("~FB~OLYou hear a melodic incantation chanted and ") - 1 + kNameLen <= 64 &&
+              sizeof(" recites a melodic incantation and disappears!\n") - 1 <= 64 && kNameLen + sizeof(" has set the topic to: ") - 1 <= 64,
+              "roster_set: the pieces of a compose() fit a wave");
+static_assert(64 * kReadSlice >= kArrSize && kWordLen + 7 <= 64, "roster_set: the word masks cover the longest inpstr, a lane per byte of word[1]");
+
+struct SetOrderArgs {
+    const int32_t* slot;         // [k] the actors
+    const int32_t* rid;          // [k] their rooms' ranks
+    const uint8_t* com;          // [k]
+    int k;
+    int8_t* outcome;             // [k] becomes kSetDeferred for a deferred event
+    int32_t* clen;               // [3k] whose three texts become void
+};
+
+__device__ void roster_set_order(const SetOrderArgs& a)
+{
+    __shared__ uint32_t s_slots[kGoMaxSlots / 32], s_heard[kGoMaxSlots / 32], s_topic[kGoMaxSlots / 32];
+    const int lane = (int)threadIdx.x;      // one wave
+    for (int i = lane; i < kGoMaxSlots / 32; i += 64) s_slots[i] = s_heard[i] = s_topic[i] = 0;
+    __syncthreads();
+    for (int base = 0; base < a.k; base += 64) {
+        const int k = base + lane;
+        const bool live = k < a.k;
+        const int own = live ? a.slot[k] : 0, room = live ? a.rid[k] : 0, out = live ? a.outcome[k] : kSetDeferred;
+        const bool lines = live && a.clen[k] >= 0, topic = live && a.com[k] == kComTopic;
+        const int count = a.k - base < 64 ? a.k - base : 64;
+        bool defer = false;
+        for (int i = 0; i < count; i++) {   // in call order; every lane follows, lane 0 sets the bits
+            const int s = __shfl(own, i), r = __shfl(room, i), oc = __shfl(out, i);
+            const bool l = __shfl((int)lines, i) != 0, t = __shfl((int)topic, i) != 0;
+            const bool hit = ((s_slots[s >> 5] >> (s & 31)) & 1u) || (l && ((s_heard[r >> 5] >> (r & 31)) & 1u)) ||
+                             (t && ((s_topic[r >> 5] >> (r & 31)) & 1u));
+            if (lane == i) defer = hit;
+            __syncthreads();
+            if (lane == 0 && !hit && oc <= kSetIgntellOff) {            // an effective event
+                s_slots[s >> 5] |= 1u << (s & 31);
+                if (oc == kSetIgnallOn || oc == kSetIgnallOff || oc == kSetColourOn || oc == kSetColourOff) s_heard[r >> 5] |= 1u << (r & 31);
+                if (oc == kSetTopicSet) s_topic[r >> 5] |= 1u << (r & 31);
+            }
+            __syncthreads();
+        }
+        if (live && defer) {
+            a.outcome[k] = (int8_t)kSetDeferred;
+            a.clen[k] = a.clen[a.k + k] = a.clen[2 * a.k + k] = -1;
+        }
+    }
+}
+
 }  // namespace
 
 // Stable, unmangled kernel names (they are what rocprofv3 reports).
@@ -3828,6 +4165,8 @@ extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_access(AccessAr
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_access_order(AccessOrderArgs a) { roster_access_order(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_clone(CloneArgs a) { roster_clone(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_clone_order(CloneOrderArgs a) { roster_clone_order(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_set(SetArgs a) { roster_set(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_set_order(SetOrderArgs a) { roster_set_order(a); }
 
 // ------------------------------------------------------------------------------------------ host library
 
@@ -4570,6 +4909,54 @@ size_t layout_clone(uintptr_t base, size_t text_bytes, size_t clear_bytes, Clone
     return take.at;
 }
 
+// nd_roster_set's layout of a roster's allocation, after layout_access's: the table, the uploads of the five tables -- the
+// room table first, which only a .topic reads, then the slots' tables from the widest row to the narrowest, since an upload
+// runs from the first table given to the end of the inputs: a changed speaker table, 16 bytes a slot, travels alone --, the
+// events with their rooms' ranks, the results next to each other, p planning k room lines and 2k single-recipient texts, and
+// last what only the kernels pass on.
+size_t layout_set(uintptr_t base, size_t text_bytes, int look_rooms, SetArgs& s, SpeakPlanArgs& p)
+{
+    Carver take{base};
+    const size_t k = (size_t)s.k, t = kSetTexts * k;
+    const size_t ctext_bytes = (size_t)kSetRow * k;
+    take_table(take, s.capacity, s.room, s.slotf);
+    take_kept(take, s.kept[0], kKeptRooms, s.capacity, look_rooms);
+    take_kept(take, s.kept[1], kKeptGo, s.capacity);
+    take_kept(take, s.kept[2], kKeptAfk, s.capacity);
+    take_kept(take, s.kept[3], kKeptUdesc, s.capacity);
+    take_kept(take, s.kept[4], kKeptSpeech, s.capacity);
+    take(s.text, text_bytes);
+    take(s.text_off, k);
+    take(s.text_len, k);
+    take(s.slot, k);
+    take(s.com, k);
+    take(s.words, k);
+    take(s.rid, k);
+    take(s.ctext_off, t);
+    take(s.violations, 1);
+    take(s.outcome, k);
+    take(s.clen, t);
+    take(p.vn, 2 * t);
+    take(p.vw, 2 * t);
+    take(p.vwsz, 2 * t * kMaxWrites);
+    take(p.bits, k * (size_t)p.words);
+    take(s.ctext, ctext_bytes);
+    take(p.var, (size_t)var_at((int64_t)ctext_bytes, (int64_t)t));
+    take(s.rm, k);
+    take(s.sender, k);
+    take(s.com_num, k);
+    p.room = s.room;
+    p.slot = s.slotf;
+    p.text = s.ctext;
+    p.text_off = s.ctext_off;
+    p.text_len = s.clen;
+    p.rm = s.rm;
+    p.sender = s.sender;
+    p.com_num = s.com_num;
+    p.violations = s.violations;
+    return take.at;
+}
+
 // nd_roster_relay's layout of a roster's allocation, after layout_plan's pattern: the table, the uploads of the rooms' names
 // and of the clone records (which the kept ones are filled from), nd_roster_plan's inputs with the clone senders and the
 // relay texts' offsets, ending with violations, then the plan's results and the relay's (p plans the relay texts) next to
@@ -4701,6 +5088,7 @@ struct Given {
     int id;                      // which of the roster's kept tables
     const uint8_t* src;          // the caller's, passed because it changed; else nullptr
     const uint8_t** read;        // the kernel's pointer to what this call reads: the upload, or the kept table
+    bool unused = false;         // this call does not read the table: it is neither asked for, made nor copied, and *read is nullptr
 };
 
 // A table the device does not hold yet must be given: `sentence` is the call's own way to say so.  A table of no
@@ -4709,7 +5097,7 @@ template <int N>
 int check_given(const Roster& r, const Given (&t)[N], const char* sentence)
 {
     for (const Given& e : t)
-        if (kept_bytes(r, e.id) && !r.kept[e.id].d && !e.src) {
+        if (!e.unused && kept_bytes(r, e.id) && !r.kept[e.id].d && !e.src) {
             snprintf(g_err, sizeof(g_err), "%s", sentence);
             return -1;
         }
@@ -4748,6 +5136,11 @@ int pass_kept(Roster& r, const Given (&t)[N], const Kept (&at)[N], Kept (&kept)[
     size_t copy_words = 0;
     *first = tables_end;
     for (int i = 0; i < N; i++) {
+        if (t[i].unused) {
+            kept[i] = Kept{nullptr, nullptr, 0};
+            *t[i].read = nullptr;
+            continue;
+        }
         KeptTable& k = r.kept[t[i].id];
         const size_t bytes = kept_bytes(r, t[i].id);
         if (bytes && !k.d) {
@@ -6562,6 +6955,141 @@ int nd_roster_clone(int handle, int k, const uint8_t* text, int64_t text_bytes, 
     memcpy(vw, res(po.vw), 2 * texts * sizeof(int32_t));
     memcpy(vwsz, res(po.vwsz), 2 * texts * kMaxWrites * sizeof(int32_t));
     memcpy(bits, res(po.bits), (size_t)kCloneLines * k * nwords * sizeof(uint64_t));
+    memcpy(ctext, res(so.ctext), ctext_bytes);
+    memcpy(var, res(po.var), var_bytes);
+
+    return fill_timing(timing, t0, t1, h2d, res_bytes);
+}
+
+// K events of roster `handle` by which a user sets its own state -- .mode, .ignall, .prompt, .desc, .inphr, .outphr, .topic,
+// .vis, .invis, .charecho, .afk, .colour, .ignshout, .igntell -- decided and composed as the reference's functions do (the
+// section of nuts_roster_set lists them), against the tables as they are: nothing the roster keeps is changed, the caller
+// applies the result.  Event b: the actor's slot slots[b], which has a room, coms[b] (one of the fourteen), inpstr and
+// words[b] as nd_roster_go's.  The actor of a .topic stands in a look room.  The six tables are NULL when unchanged since this
+// roster's last call that took them; rooms is read, and asked for, only by a call that holds a .topic.
+// Outputs (host, caller-allocated), with W = ceil(capacity / 64) and text t = b for event b's here line, k + b its reply,
+// 2k + b its second reply: outcome[k] (0 .. 21 the effective outcomes in the order of kSetModeCommand .. kSetIgntellOff,
+// 22 .. 34 the video test, the queries and the refusals, 35 deferred); clen[3k], -1 where there is no text; ctext[200 k], the
+// here lines at 96 b, the replies at 96 k + 84 b, the second replies at 180 k + 20 b; bits[k * W] the admit bitmaps of the
+// here lines; vn[6k], vw[6k], vwsz[6k * 16] and var[12 * 200 k + 48 k] as nd_roster_speak's.
+// Per call, whatever k and the capacity: one upload, three kernels (nuts_roster_set, nuts_roster_set_order,
+// nuts_roster_speak_plan), one download at the bound size, one synchronise.  Returns 0, or -1 with nd_last_error() set.
+int nd_roster_set(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off, const int32_t* text_len,
+                  const int32_t* slots, const uint8_t* coms, const uint8_t* words, const uint8_t* table, const uint8_t* speech,
+                  const uint8_t* afk, const uint8_t* udesc, const uint8_t* go, const uint8_t* rooms, int8_t* outcome, int32_t* clen,
+                  uint64_t* bits, int64_t* vn, int32_t* vw, int32_t* vwsz, uint8_t* ctext, uint8_t* var, nd_roster_timing* timing)
+{
+    Roster* r = roster_at(handle);
+    if (!r || ensure_ready()) return -1;
+    const int cap = r->capacity, nwords = (cap + 63) / 64, nrooms = r->look_rooms;
+    if (k < 1 || (int64_t)k * cap >= INT32_MAX || (int64_t)k * kSetRow >= INT32_MAX / 16 || text_bytes < 0 ||
+        text_bytes >= INT32_MAX / 32 || nrooms < 0 || nrooms > kMaxLookRooms) {
+        snprintf(g_err, sizeof(g_err), "%d events to %d slots: need 1 <= k * capacity < 2^31 - 1", k, cap);
+        return -1;
+    }
+    int64_t sum = 0;
+    bool topics = false;
+    for (int b = 0; b < k; b++) {       // the kernels index by these: nothing out of range reaches them
+        const int c = coms[b];
+        const bool known = c == kComMode || (c >= kComIgnall && c <= kComOutphr) || c == kComTopic || c == kComVis || c == kComInvis ||
+                           c == kComCharecho || c == kComAfk || (c >= kComColour && c <= kComIgntell);
+        if (slots[b] < 0 || slots[b] >= cap || text_len[b] < 0 || text_len[b] >= kArrSize || text_off[b] != sum || !known) {
+            snprintf(g_err, sizeof(g_err), "event %d: slot, command, text length or text offset out of range", b);
+            return -1;
+        }
+        topics |= c == kComTopic;
+        sum += text_len[b];
+    }
+    if (sum != text_bytes) {
+        snprintf(g_err, sizeof(g_err), "the events' texts hold %lld bytes, not %lld", (long long)sum, (long long)text_bytes);
+        return -1;
+    }
+    SetArgs s{};
+    const Given given[] = {{kKeptRooms, topics ? rooms : nullptr, &s.rooms, !topics}, {kKeptGo, go, &s.go}, {kKeptAfk, afk, &s.afk},
+                           {kKeptUdesc, udesc, &s.udesc}, {kKeptSpeech, speech, &s.speech}};
+    if (check_given(*r, given, "the roster's first set call must give the go table, the AFK messages, the user descriptions, the speaker "
+                               "table and, for a .topic, the room table"))
+        return -1;
+    const double t0 = now_ns();
+    hipStream_t st = g.stream;
+    SpeakPlanArgs p{};
+    s.k = p.k = k;
+    s.capacity = p.capacity = cap;
+    s.blocks = (k + kBlock / 64 - 1) / (kBlock / 64);
+    p.tiles = (cap + kBlock - 1) / kBlock;
+    p.words = nwords;
+    const size_t texts = (size_t)kSetTexts * k, ctext_bytes = (size_t)kSetRow * k;
+    const size_t var_bytes = (size_t)var_at((int64_t)ctext_bytes, (int64_t)texts);
+    SetArgs so = s;                     // offsets of every array in the roster's allocation
+    SpeakPlanArgs po = p;
+    const size_t need = layout_set(0, (size_t)text_bytes, nrooms, so, po);
+    const size_t table_bytes = (uintptr_t)so.kept[0].fresh, tables_end = (uintptr_t)so.text;
+    const size_t in_bytes = (uintptr_t)so.violations + sizeof(int);
+    const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
+    if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
+    if (table) new_table(*r, so.room, so.slotf, table);
+    uint8_t* h = r->mirror;
+    const int32_t* room = reinterpret_cast<const int32_t*>(h + (uintptr_t)so.room);
+    int32_t* rid = reinterpret_cast<int32_t*>(h + (uintptr_t)so.rid);
+    for (int b = 0; b < k; b++) {       // every actor has a room, and a .topic's a record: nuts_roster_set reads it
+        rid[b] = room[slots[b]];
+        if (rid[b] < 0 || (coms[b] == kComTopic && rid[b] >= nrooms)) {
+            snprintf(g_err, sizeof(g_err), "event %d: the actor has no room, or a .topic's room has no room record", b);
+            return -1;
+        }
+    }
+    if (grow_roster(*r, need)) return -1;
+    layout_set((uintptr_t)r->d, (size_t)text_bytes, nrooms, s, p);
+    if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
+
+    const Put put{h};
+    put(so.text, text, (size_t)text_bytes);
+    put(so.text_off, text_off, (size_t)k * sizeof(int32_t));
+    put(so.text_len, text_len, (size_t)k * sizeof(int32_t));
+    put(so.slot, slots, (size_t)k * sizeof(int32_t));
+    put(so.com, coms, (size_t)k);
+    put(so.words, words, (size_t)k);
+    {                                   // the actors' rooms become their ranks among the call's rooms: fewer than 65,536, as the slots are
+        int32_t* sorted = reinterpret_cast<int32_t*>(gm.res);           // scratch until the results land there: k * 4 <= res_bytes
+        std::copy(rid, rid + k, sorted);
+        std::sort(sorted, sorted + k);
+        const int32_t* last = std::unique(sorted, sorted + k);
+        for (int b = 0; b < k; b++) rid[b] = (int32_t)(std::lower_bound((const int32_t*)sorted, last, rid[b]) - sorted);
+    }
+    int32_t* coff = reinterpret_cast<int32_t*>(h + (uintptr_t)so.ctext_off);
+    for (int kind = 0; kind < kSetTexts; kind++)
+        for (int b = 0; b < k; b++) coff[(size_t)kind * k + b] = (int32_t)set_text_at(kind, b, k);
+    *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
+    // the tables' uploads lie between the table and the inputs
+    size_t first = 0, h2d = 0;
+    unsigned copy_blocks = 0;
+    if (pass_kept(*r, given, so.kept, s.kept, tables_end, &first, &copy_blocks)) return -1;
+    if (upload(*r, table_bytes, first, in_bytes, &h2d)) return -1;
+
+    const SetOrderArgs order{s.slot, s.rid, s.com, k, s.outcome, s.clen};
+    ND_CHECK(hipEventRecord(g.ev0, st));
+    hipLaunchKernelGGL(nuts_roster_set, dim3((unsigned)s.blocks + copy_blocks), dim3(kBlock), 0, st, s);
+    ND_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(nuts_roster_set_order, dim3(1), dim3(64), 0, st, order);
+    ND_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)(k * p.tiles + 2 * k)), dim3(kBlock), 0, st, p);
+    ND_CHECK(hipGetLastError());
+    if (fetch_results(r->d, res_at, res_bytes)) return -1;
+    const double t1 = now_ns();
+
+    const Res res{gm.res, res_at};
+    const int violations = *reinterpret_cast<const int*>(res(so.violations));
+    if (violations) {
+        snprintf(g_err, sizeof(g_err), "%d text(s) exceeded the hard bounds (a text its slot; 6*len+4 bytes, %d writes transduced)",
+                 violations, kMaxWrites);
+        return -1;
+    }
+    memcpy(outcome, res(so.outcome), (size_t)k);
+    memcpy(clen, res(so.clen), texts * sizeof(int32_t));
+    memcpy(vn, res(po.vn), 2 * texts * sizeof(int64_t));
+    memcpy(vw, res(po.vw), 2 * texts * sizeof(int32_t));
+    memcpy(vwsz, res(po.vwsz), 2 * texts * kMaxWrites * sizeof(int32_t));
+    memcpy(bits, res(po.bits), (size_t)k * nwords * sizeof(uint64_t));
     memcpy(ctext, res(so.ctext), ctext_bytes);
     memcpy(var, res(po.var), var_bytes);
 

@@ -4,7 +4,7 @@
                                   [--roster K[,K...]] [--plan K[,K...]] [--review Q[,Q...]] [--speak K[,K...]]
                                   [--input K[,K...]] [--tell K[,K...]] [--look K[,K...]] [--relay K[,K...]] [--go K[,K...]]
                                   [--who K[,K...]] [--rooms K[,K...]] [--access K[,K...]] [--clone K[,K...]]
-                                                                                                       -> one JSON line
+                                  [--set K[,K...]]                                                     -> one JSON line
 
 For N in {10, 100, 1000} listeners, the two texts oracle/pathbench.c times (``say``; ``shout`` carrying ``~OL``/``~RS``)
 and colour all-off / all-on / half, one ``nuts333_amd.device.broadcast`` per repetition (listener 0 is the sender, the
@@ -117,6 +117,18 @@ their own, ``clone`` -- K ``.clone`` events by K users who own none, each in its
 events by the same users, which returns the records to their start.  Six rooms take six clones a call, so of K = 8 or 64
 events most are deferred: ``created`` and ``deferred`` say how many.  Every call is checked first against the reference's
 formats, the CPU's transducer and the rule of the call.
+
+``--set K[,K...]`` adds ``set``: a 1000-slot roster of USERs over the six default rooms, and per ``Roster.set_many`` call K
+``.ignall`` events by K actors (``ignall``) and K ``.desc <text>`` events by the same actors (``desc``): the three times and
+the copy volume of each call, each beside ``speak`` -- ``speak_many`` of the same bodies as says by the same users, in the
+same rounds -- and ``cpu_us``, the CPU composing the lines in Python and transducing them through ctypes;
+``ignall_over_speak`` and ``desc_over_speak`` are the ratios of the medians, ``..._p10_p90`` the loosest the rounds allow.
+An ``.ignall`` changes who hears its room, so the first actor of a room is answered and the later ones of that room wait:
+of K = 8 or 64 events six toggle, ``toggled`` and ``deferred`` say how many.  What a call changes travels with the next call
+that reads it: the ``.desc`` call uploads the descriptions its last call changed, 32 bytes a slot, with the speaker table
+that lies behind them, 16, and in the ``.ignall`` rounds it is ``speak_many`` that uploads the table the ``.ignall`` call
+changed, 5 bytes a slot (``h2d_bytes`` shows both).
+Both calls are checked first against the reference's formats, the CPU's transducer and the rule of the call.
 """
 from __future__ import annotations
 
@@ -1131,6 +1143,106 @@ def clone_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
             "clone": cases}
 
 
+def set_events(k: int) -> tuple:
+    """K ``.ignall`` events and K ``.desc <text>`` events by the actors 0 .. K - 1, the descriptions the bodies of
+    ``speak_events(k)`` cut to USER_DESC_LEN bytes, and K says of the same bodies by the same users."""
+    bodies = [ev[2][:device.USER_DESC_LEN].rstrip() for ev in speak_events(k)]
+    return ([(j, device.COM_IGNALL, b"", 1) for j in range(k)], [(j, device.COM_DESC, body, 7) for j, body in enumerate(bodies)],
+            [(j, device.COM_SAY, body, 7) for j, body in enumerate(bodies)])
+
+
+def set_model(room_of: np.ndarray, actors, on: bool) -> list[int]:
+    """What set_many answers for ``.ignall`` events by ``actors``, one each, at the roster ``set_cases`` builds: the first
+    actor of a room toggles -- on in a call, off in the next --, the later ones of that room wait."""
+    touched, out = set(), []
+    for j in actors:
+        rm = int(room_of[j])
+        out.append(device.SET_DEFERRED if rm in touched else device.SET_IGNALL_ON if on else device.SET_IGNALL_OFF)
+        touched.add(rm)
+    return out
+
+
+def set_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
+    """The ``set`` section: set_many of K ``.ignall`` events by K actors, and of K ``.desc <text>`` events by the same
+    actors, at a 1000-slot roster over the six default rooms, each beside speak_many of the same bodies as says by the same
+    users, in the same rounds, and the CPU composing and transducing the lines."""
+    n = 1000
+    names, accesses = ROOMS_LISTS["6"]
+    nr = len(names)
+    cases = []
+    for colour in COLOURS:
+        with device.Roster(n, look_rooms=nr) as roster:
+            col = colours(n, colour)
+            room_of = np.arange(n) % nr
+            roster.update(range(n), room=room_of.tolist(), colour=col, name=[b"User%d" % j for j in range(n)], level=1)
+            roster.set_rooms(list(range(nr)), name=names, access=accesses, links=[list(l) for l in GO_LINKS])
+            for k in ks:
+                ignalls, descs, says = set_events(k)
+                actors = list(range(k))
+                for on in (True, False):                                # two calls: the flags end where they began
+                    got = roster.set_many(ignalls)
+                    want = set_model(room_of, actors, on)
+                    line = b"User%d is now ignoring everyone.\n" if on else b"User%d is listening again.\n"
+                    ok = got.outcome.tolist() == want and all(
+                        got.here_text(j) == line % j and all(got.here.chunks(j, c) == nuts_path.chunks(line % j, c) for c in (0, 1))
+                        for j in actors if want[j] != device.SET_DEFERRED)
+                    if not ok:
+                        raise SystemExit(f"devpath: set {k}, {colour}: the .ignall call differs from the rule of the call, the "
+                                         f"reference's format or the CPU's transducer")
+                first = roster.set_many(descs)                         # it leaves the descriptions changed, as every timed call does
+                if first.outcome.tolist() != [device.SET_DESC_SET] * k or any(
+                        first.reply_text(j) != b"Description set.\n" or bytes(roster._udesc[j, :len(descs[j][2])]) != descs[j][2] for j in actors):
+                    raise SystemExit(f"devpath: set {k}, {colour}: the .desc call differs from the reference's format")
+                toggled = want.count(device.SET_IGNALL_OFF)
+
+                def cpu_ignall():
+                    for j in actors[:toggled]:
+                        for text in (b"You are now ignoring everyone.\n", b"User%d is now ignoring everyone.\n" % j):
+                            nuts_path.chunks(text, 0)
+                            nuts_path.chunks(text, 1)
+
+                def cpu_desc():
+                    for _ in actors:
+                        nuts_path.chunks(b"Description set.\n", 0)
+                        nuts_path.chunks(b"Description set.\n", 1)
+
+                roster.set_many(ignalls)                                # the table is changed: the first timed speak_many uploads it too
+                one = _timed(f"set {k}, {colour}", {"speak": lambda: roster.speak_many(says), "ignall": lambda: roster.set_many(ignalls),
+                                                    "cpu": cpu_ignall}, reps, warmup)
+                roster.set_many(descs)                                  # it takes that table, and leaves the descriptions changed
+                two = _timed(f"set {k}, {colour}", {"speak": lambda: roster.speak_many(says), "desc": lambda: roster.set_many(descs),
+                                                    "cpu": cpu_desc}, reps, warmup)
+                if (warmup + reps) % 2 == 0:                            # an odd count of .ignall calls: once more, back to the start
+                    roster.set_many(ignalls)
+
+                def over(dev, sp):
+                    return ({f: round(dev.times[f]["median"] / sp.times[f]["median"], 2) for f in FIELDS},
+                            # the loosest the rounds allow: the one side's p10 over the other's p90, and the other way round
+                            {f: [round(dev.times[f]["p10"] / sp.times[f]["p90"], 2), round(dev.times[f]["p90"] / sp.times[f]["p10"], 2)]
+                             for f in FIELDS})
+
+                ig, de = over(one["ignall"], one["speak"]), over(two["desc"], two["speak"])
+                cases.append({"n": n, "k": k, "colour": colour, "rooms": nr, "toggled": toggled, "deferred": k - toggled,
+                              "ignall": {**one["ignall"].fields, "speak": one["speak"].fields, "cpu_us": one["cpu"].host_us},
+                              "ignall_over_speak": ig[0], "ignall_over_speak_p10_p90": ig[1],
+                              "desc": {**two["desc"].fields, "speak": two["speak"].fields, "cpu_us": two["cpu"].host_us},
+                              "desc_over_speak": de[0], "desc_over_speak_p10_p90": de[1]})
+    return {"set_kernels": list(device.SET_KERNELS) + ["nuts_roster_speak_plan"],
+            "set_end_to_end_covers": "packing the K events into pinned memory and ranking their actors' rooms, one H2D (the events, "
+                                     "and in the .desc call the descriptions the call before changed and the speaker table behind them, 48 bytes a slot; the table "
+                                     "an .ignall call changes, 5 bytes a slot, travels with the speak_many that follows it), "
+                                     "three kernels -- the decision and the "
+                                     "three texts of every event; the deferral walk; both variants of every text and the here "
+                                     "lines' admit bitmaps --, one D2H at the bound size, one synchronise (python_us adds checking "
+                                     "the events, the copies out of pinned memory, building the Settings and applying it to the "
+                                     "host mirrors through update)",
+            "set_speak_covers": "speak_many of the same K bodies as says by the same K users, at the same roster, in the same "
+                                "rounds: two kernels, two texts an event where the set call has three",
+            "set_cpu_us_covers": "the reference's formats in Python and np_write_user_stream of the CPU restatement (nuts_path, "
+                                 "through ctypes) over both variants of the lines of the events that are answered",
+            "set": cases}
+
+
 RELAY_CLONES = 64
 
 
@@ -1267,6 +1379,9 @@ SECTIONS = (
     ("clone", "K[,K...]", "also time K .csay events by K owners per Roster.clone_many call at a 1000-slot roster over the six "
                           "default rooms, for each K, beside speak_many of the same bodies and the CPU composing and transducing "
                           "the lines, and K .clone events, then K .destroy events (the clone section)", "clone_cases"),
+    ("set", "K[,K...]", "also time K .ignall events and K .desc events by K actors per Roster.set_many call at a 1000-slot roster "
+                        "over the six default rooms, for each K, each beside speak_many of the same bodies and the CPU composing "
+                        "and transducing the lines (the set section)", "set_cases"),
 )
 
 
