@@ -316,6 +316,8 @@ MAX_ACCESS_HERE, MAX_ACCESS_THERE, MAX_ACCESS_REPLY, MAX_ACCESS_NOTICE = (USER_N
                                                                          18 + 10 + 55, USER_NAME_LEN + 26 + ROOM_NAME_LEN + 2)
 #: their slots among an access call's texts (kAccHereRow .. kAccNoticeRow), laid out as _GO_ROWS lays a go call's
 _ACCESS_ROWS = (72, 44, 84, 60)
+_ACCESS_COMS = (COM_PUBLIC, COM_PRIVATE, COM_LETMEIN, COM_INVITE)
+_ACCESS_COM_RULE = f"com must be COM_PUBLIC, COM_PRIVATE, COM_LETMEIN or COM_INVITE ({COM_PUBLIC} .. {COM_INVITE})"
 #: the texts of an event in an Access, in that order: the two room lines first, then the two single-recipient texts
 ACCESS_HERE, ACCESS_THERE, ACCESS_REPLY, ACCESS_NOTICE = range(4)
 #: ``.clone``, ``.destroy``, ``.csay`` and ``.chear`` (NP_CLONE, NP_DESTROY, NP_CSAY, NP_CHEAR), and the kernels clone_many runs
@@ -343,6 +345,8 @@ MAX_CLONE_HERE, MAX_CLONE_THERE, MAX_CLONE_RESET, MAX_CLONE_REPLY, MAX_CLONE_NOT
 #: of 4, in the order above.  The said lines lie between the reset lines and the replies, each in a slot of its inpstr's
 #: length and _SPEAK_SLACK, as speak_many lays its composed lines: the texts lie in their own order, room lines first
 _CLONE_ROWS = (48, 68, 36, 88, 84)
+_CLONE_COMS = (COM_CLONE, COM_DESTROY, COM_CSAY, COM_CHEAR)
+_CLONE_COM_RULE = f"com must be COM_CLONE, COM_DESTROY, COM_CSAY or COM_CHEAR ({COM_CLONE}, {COM_DESTROY}, {COM_CSAY}, {COM_CHEAR})"
 #: the texts of an event in a Clone, in that order: the four room lines first, then the two single-recipient texts
 CLONE_HERE, CLONE_THERE, CLONE_RESET, CLONE_SAID_LINE, CLONE_REPLY, CLONE_NOTICE = range(6)
 #: the commands a user sets its own state with (NP_MODE .. NP_IGNTELL of enum np_com), and the kernels set_many runs before
@@ -371,6 +375,7 @@ SET_KERNELS = ("nuts_roster_set", "nuts_roster_set_order")
 MAX_SET_HERE, MAX_SET_REPLY, MAX_SET_REPLY2 = USER_NAME_LEN + 23 + TOPIC_LEN + 1, 22 + TOPIC_LEN + 1, 17
 #: their slots among a set call's texts (kSetHereRow .. kSetReply2Row), laid out as _ACCESS_ROWS lays an access call's
 _SET_ROWS = (96, 84, 20)
+_SET_COM_RULE = f"com must be one of the fourteen commands of SET_COMS {SET_COMS}"
 #: the texts of an event in a Settings, in that order: the room line first, then the actor's two
 SET_HERE, SET_REPLY, SET_REPLY2 = range(3)
 #: the names of colcom[1 .. 20] (nuts333.c colcom, without ``RS`` at 0), and the twenty lines the video test of ``.colour``
@@ -2756,55 +2761,142 @@ class Roster:
                      variants=var, variant_starts=_variant_starts(tstarts, clen), variant_sizes=vn, write_counts=vw,
                      write_sizes=vwsz, timing=_timing_of(t))
 
-    def _prepare_go(self, events, gatecrash_level, min_private_users):
-        """Each (slot, inpstr, word_count) and its mover's state checked, packed for nd_roster_go: the inpstr, their offsets
-        and lengths, the slots and the word counts."""
+    @staticmethod
+    def _check_sequence(events) -> None:
+        """An event call takes a non-empty sequence: what every _prepare_* checks first, before its own settings."""
         if isinstance(events, (str, bytes, bytearray, np.ndarray)) or not hasattr(events, "__len__"):
             raise ValueError(f"events must be a sequence of tuples, not {type(events).__name__}")
         if len(events) == 0:
             raise ValueError("empty call: no events")
+
+    def _prepare_events(self, events, *, actor, rows, texts, coms=None, com_rule=None, need_room_record=True,
+                        check_last=(None, None), said=False, then=None):
+        """The events of an event call and their actors' state checked, packed for the library: the list of inpstr, their
+        offsets and lengths, the slots, the commands and the word counts.  ``coms`` is None for go_many's events, (slot,
+        inpstr, word_count); else the events are (slot, com, inpstr, word_count) with com one of ``coms``, and
+        ``com_rule`` is how the call says so.  ``actor`` is the call's noun for the slot of an event; rows and texts are
+        the call's text rows and its number of texts per event.  ``said`` is clone's: four admit cells an event against
+        K x capacity, and a said line in the variant bound, which is then known only behind the loop and checked there.
+        check_last is (com, check): check(slot) is the call's own last condition on the events of that command;
+        then(coms) is its condition on all of them."""
+        n, cells = len(events), "4 x K" if said else "K"
+        if (4 if said else 1) * n * self.capacity >= 2**31 - 1:
+            raise ValueError(f"{n} events to {self.capacity} slots: {cells} x capacity must be below 2^31 - 1")
+
+        def check_bound(text_bytes):
+            bound = _variant_at(sum(rows) * n + text_bytes, texts * n)
+            if bound > MANY_ARENA_CAP:
+                raise ValueError(f"call too large: its variant bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
+                                 f"(MANY_ARENA_CAP): split it")
+        if not said:
+            check_bound(0)
+        arity, names = (3, "(slot, inpstr, word_count)") if coms is None else (4, "(slot, com, inpstr, word_count)")
+        last_com, last_check = check_last
+        look_rooms, login, com = self.look_rooms, ROSTER_FLAGS["login"], None
+        inps, slots, given, wcs = [], [], [], []
+        for k, ev in enumerate(events):
+            if not isinstance(ev, tuple) or len(ev) != arity:
+                raise ValueError(f"event {k}: expected a {names} tuple, "
+                                 f"got {type(ev).__name__}{f' of {len(ev)}' if isinstance(ev, tuple) else ''}")
+            try:
+                if coms is None:
+                    slot, inpstr, wc = ev
+                    slot = self._slot(slot)
+                else:
+                    slot, com, inpstr, wc = ev
+                    slot = self._slot(slot)
+                    if not _is_int(com, 0, NUM_COMMANDS - 1) or int(com) not in coms:
+                        raise ValueError(f"{com_rule}, not {com!r}")
+                    given.append(int(com))
+                text = _as_text(inpstr)
+                if len(text) >= ARR_SIZE:
+                    raise ValueError(f"inpstr of {len(text)} bytes: the talker's input line holds at most {ARR_SIZE - 1}")
+                if not _is_int(wc, 0, MAX_WORDS):
+                    raise ValueError(f"word_count must be an int in [0, {MAX_WORDS}], not {wc!r}")
+                room = self._room[slot]
+                if need_room_record:
+                    if not 0 <= room < look_rooms:
+                        raise ValueError(f"the {actor}, slot {slot}, is in " + (f"room {int(room)}, which has no room record"
+                                         if room >= 0 else "no room") + f" (look_rooms is {look_rooms})")
+                elif room < 0:
+                    raise ValueError(f"the {actor}, slot {slot}, is in no room")
+                if self._flags[slot] & login:
+                    raise ValueError(f"the {actor}, slot {slot}, is still logging in")
+                if self._speech[slot, USER_NAME_LEN] == 0:
+                    raise ValueError(f"the {actor}, slot {slot}, has no name")
+                if last_check is not None and com == last_com:
+                    last_check(slot)
+            except ValueError as e:
+                raise ValueError(f"event {k}: {e}") from None
+            inps.append(text)
+            slots.append(slot)
+            wcs.append(int(wc))
+        if then is not None:
+            then(given)
+        lens = np.fromiter((len(t) for t in inps), dtype=np.int64, count=n)
+        if int(lens.sum()) >= 2**31 // 32:
+            raise ValueError("call text larger than 64 MiB: split it")
+        if said:
+            check_bound(_composed_at(int(lens.sum()), n))
+        return (inps, _offsets(lens, np.int32), lens.astype(np.int32), np.array(slots, dtype=np.int32),
+                np.array(given, dtype=np.uint8), np.array(wcs, dtype=np.uint8))
+
+    def _event_arrays(self, k: int, rows, texts: int, said_bytes: int = 0):
+        """The arrays an event call's library function fills in for k events of ``texts`` texts each, ``rows`` bytes an
+        event for the fixed ones and said_bytes in all for clone's said lines, as _event_plans takes them: outcome, clen,
+        bits (zeroed: the rows addressed to a single slot are set by the binding), vn, vw, vwsz, ctext, var."""
+        ctext_bytes = sum(rows) * k + said_bytes
+        return (np.empty(k, dtype=np.int8), np.empty((texts, k), dtype=np.int32),
+                np.zeros((texts, k, (self.capacity + 63) // 64), dtype=np.uint64), np.empty((texts, k, 2), dtype=np.int64),
+                np.empty((texts, k, 2), dtype=np.int32), np.empty((texts, k, 2, MAX_WRITES), dtype=np.int32),
+                np.empty(ctext_bytes, dtype=np.uint8), np.empty(_variant_at(ctext_bytes, texts * k), dtype=np.uint8))
+
+    def _event_plans(self, rows, clen, bits, vn, vw, vwsz, var, t, single, said=None):
+        """What an event call's library function filled in, as (text_starts, plans, timing): one Plan per text.
+        ``single`` lists (text, slots) for the texts that go to one slot alone -- write_user(u, text): ignall, afk and the
+        room play no part --, whose bits are set here.  ``said`` is (text, text_off, text_bytes) when that text is
+        clone's said line, laid as speak_many lays its own between the fixed rows around it."""
+        k = clen.shape[1]
+        rows, at = np.array(rows, dtype=np.int64), np.arange(k, dtype=np.int64)
+        tstarts = ((np.cumsum(rows) - rows) * k)[:, None] + rows[:, None] * at
+        if said is not None:
+            row, text_off, text_bytes = said
+            tstarts[row:] += _composed_at(text_bytes, k)
+            lines = int(rows[:row].sum()) * k + _composed_at(text_off.astype(np.int64), at)
+            tstarts = np.concatenate([tstarts[:row], lines[None], tstarts[row:]])
+        starts = _variant_starts(tstarts, clen)
+        for row, slots in single:
+            has = np.flatnonzero(clen[row] >= 0)
+            bits[row, has, slots[has] // 64] = np.uint64(1) << (slots[has] % 64).astype(np.uint64)
+        timing = _timing_of(t)
+        colour_bits = _pack((self._flags & ROSTER_FLAGS["colour"]) != 0)
+        plans = [Plan(capacity=self.capacity, admitted_bits=bits[i], colour_bits=colour_bits, variants=var,
+                      variant_starts=starts[i], variant_sizes=vn[i], write_counts=vw[i], write_sizes=vwsz[i],
+                      timing=dict(timing)) for i in range(len(clen))]
+        return tstarts, plans, timing
+
+    def _returned_to_public(self, rm: int) -> None:
+        """A room that returned to public, on the host mirrors: access PUBLIC, every slot's invite into it cleared, and its
+        review ring emptied when it has one (reset_access, nuts333.c:4605-4611)."""
+        self.set_rooms(rm, access=PUBLIC)
+        invited = np.flatnonzero(self._go_invite == rm)
+        if len(invited):
+            self.update(invited, invite_room=None)
+        if rm < self.review_rooms:
+            self.clear_review([rm])
+
+    def _prepare_go(self, events, gatecrash_level, min_private_users):
+        """Each (slot, inpstr, word_count) and its mover's state checked, packed for nd_roster_go: the inpstr, their offsets
+        and lengths, the slots and the word counts."""
+        self._check_sequence(events)
         if not _is_int(gatecrash_level, 0, MAX_LEVEL):
             raise ValueError(f"gatecrash_level must be an int in [0, {MAX_LEVEL}] (enum np_level), not {gatecrash_level!r}")
         if not _is_int(min_private_users, 0, 2**31 - 1):
             raise ValueError(f"min_private_users must be an int in [0, 2^31), not {min_private_users!r}")
         if self.look_rooms < 1:
             raise ValueError("the roster has no room records (look_rooms is 0): there is no room to go to")
-        if len(events) * self.capacity >= 2**31 - 1:
-            raise ValueError(f"{len(events)} events to {self.capacity} slots: K x capacity must be below 2^31 - 1")
-        bound = _variant_at(sum(_GO_ROWS) * len(events), 4 * len(events))
-        if bound > MANY_ARENA_CAP:
-            raise ValueError(f"call too large: its variant bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
-                             f"(MANY_ARENA_CAP): split it")
-        texts, slots, wcs = [], [], []
-        for k, ev in enumerate(events):
-            if not isinstance(ev, tuple) or len(ev) != 3:
-                raise ValueError(f"event {k}: expected a (slot, inpstr, word_count) tuple, "
-                                 f"got {type(ev).__name__}{f' of {len(ev)}' if isinstance(ev, tuple) else ''}")
-            slot, inpstr, wc = ev
-            try:
-                slot = self._slot(slot)
-                text = _as_text(inpstr)
-                if len(text) >= ARR_SIZE:
-                    raise ValueError(f"inpstr of {len(text)} bytes: the talker's input line holds at most {ARR_SIZE - 1}")
-                if not _is_int(wc, 0, MAX_WORDS):
-                    raise ValueError(f"word_count must be an int in [0, {MAX_WORDS}], not {wc!r}")
-                if not 0 <= self._room[slot] < self.look_rooms:
-                    raise ValueError(f"the mover, slot {slot}, is in " + (f"room {int(self._room[slot])}, which has no room record"
-                                     if self._room[slot] >= 0 else "no room") + f" (look_rooms is {self.look_rooms})")
-                if self._flags[slot] & ROSTER_FLAGS["login"]:
-                    raise ValueError(f"the mover, slot {slot}, is still logging in")
-                if self._speech[slot, USER_NAME_LEN] == 0:
-                    raise ValueError(f"the mover, slot {slot}, has no name")
-            except ValueError as e:
-                raise ValueError(f"event {k}: {e}") from None
-            texts.append(text)
-            slots.append(slot)
-            wcs.append(int(wc))
-        lens = np.fromiter((len(t) for t in texts), dtype=np.int64, count=len(texts))
-        if int(lens.sum()) >= 2**31 // 32:
-            raise ValueError("call text larger than 64 MiB: split it")
-        return (b"".join(texts), _offsets(lens, np.int32), lens.astype(np.int32), np.array(slots, dtype=np.int32),
-                np.array(wcs, dtype=np.uint8))
+        inps, text_off, lens, slots, _, wcs = self._prepare_events(events, actor="mover", rows=_GO_ROWS, texts=4)
+        return b"".join(inps), text_off, lens, slots, wcs
 
     def go_many(self, events, *, gatecrash_level, min_private_users) -> Go:
         """K ``.go`` events, decided and composed on the device: a non-empty sequence of ``(slot, inpstr, word_count)``
@@ -2861,16 +2953,9 @@ class Roster:
         text, text_off, lens, slots, wcs = self._prepare_go(events, gatecrash_level, min_private_users)
         lib = _load()
         handle = self._device_handle(lib)
-        k, words = len(lens), (self.capacity + 63) // 64
-        ctext_bytes = sum(_GO_ROWS) * k
-        outcome, target, old = np.empty(k, dtype=np.int8), np.empty(k, dtype=np.int32), np.empty(k, dtype=np.int32)
-        returned = np.empty(k, dtype=np.uint8)
-        clen = np.empty((4, k), dtype=np.int32)
-        bits = np.zeros((4, k, words), dtype=np.uint64)            # the device's three, then the mover alone
-        vn, vw = np.empty((4, k, 2), dtype=np.int64), np.empty((4, k, 2), dtype=np.int32)
-        vwsz = np.empty((4, k, 2, MAX_WRITES), dtype=np.int32)
-        ctext = np.empty(ctext_bytes, dtype=np.uint8)
-        var = np.empty(_variant_at(ctext_bytes, 4 * k), dtype=np.uint8)
+        k = len(lens)
+        outcome, clen, bits, vn, vw, vwsz, ctext, var = self._event_arrays(k, _GO_ROWS, 4)
+        target, old, returned = np.empty(k, dtype=np.int32), np.empty(k, dtype=np.int32), np.empty(k, dtype=np.uint8)
         tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
         t = _RosterTiming()
         rc = lib.nd_roster_go(handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(slots), _ptr(wcs),
@@ -2885,16 +2970,8 @@ class Roster:
         self._dirty = self._speech_dirty = self._rooms_dirty = self._go_dirty = False
         if self.clones:
             self._clones_dirty = False
-        rows = np.array(_GO_ROWS, dtype=np.int64)
-        tstarts = ((np.cumsum(rows) - rows) * k)[:, None] + rows[:, None] * np.arange(k, dtype=np.int64)
-        starts = _variant_starts(tstarts, clen)
-        has = np.flatnonzero(clen[GO_REPLY] >= 0)
-        bits[GO_REPLY, has, slots[has] // 64] = np.uint64(1) << (slots[has] % 64).astype(np.uint64)
-        timing = _timing_of(t)
-        colour_bits = _pack((self._flags & ROSTER_FLAGS["colour"]) != 0)
-        plans = [Plan(capacity=self.capacity, admitted_bits=bits[i], colour_bits=colour_bits, variants=var,
-                      variant_starts=starts[i], variant_sizes=vn[i], write_counts=vw[i], write_sizes=vwsz[i],
-                      timing=dict(timing)) for i in range(4)]
+        # the device's three, then the mover alone
+        tstarts, plans, timing = self._event_plans(_GO_ROWS, clen, bits, vn, vw, vwsz, var, t, [(GO_REPLY, slots)])
         go = Go(outcome=outcome, target=target, old_room=old, returned_public=returned.astype(bool), enter=plans[GO_ENTER],
                 leave=plans[GO_LEAVE], reset=plans[GO_RESET], reply=plans[GO_REPLY], texts=ctext, text_starts=tstarts,
                 text_sizes=clen.astype(np.int64), look_index=np.full(k, -1, dtype=np.int32), timing=timing)
@@ -2921,24 +2998,14 @@ class Roster:
                 self.update(invited, invite_room=None)
             go.look = self.look_many(movers)
             go.look_index[moved] = np.arange(len(moved), dtype=np.int32)
-        if public:
-            public = np.array(sorted(public), dtype=np.int32)
-            self.set_rooms(public, access=PUBLIC)
-            invited = np.flatnonzero(np.isin(self._go_invite, public))
-            if len(invited):
-                self.update(invited, invite_room=None)
-            rings = public[public < self.review_rooms]
-            if len(rings):
-                self.clear_review(rings)
+        for rm in sorted(public):
+            self._returned_to_public(rm)
         return go
 
     def _prepare_access(self, events, gatecrash_level, min_private_users, ignore_mp_level):
         """Each (slot, com, inpstr, word_count) and its actor's state checked, packed for nd_roster_access: the inpstr, their
         offsets and lengths, the slots, the commands and the word counts."""
-        if isinstance(events, (str, bytes, bytearray, np.ndarray)) or not hasattr(events, "__len__"):
-            raise ValueError(f"events must be a sequence of tuples, not {type(events).__name__}")
-        if len(events) == 0:
-            raise ValueError("empty call: no events")
+        self._check_sequence(events)
         if not _is_int(gatecrash_level, 0, MAX_LEVEL):
             raise ValueError(f"gatecrash_level must be an int in [0, {MAX_LEVEL}] (enum np_level), not {gatecrash_level!r}")
         if not _is_int(min_private_users, 0, 2**31 - 1):
@@ -2947,46 +3014,9 @@ class Roster:
             raise ValueError(f"ignore_mp_level must be an int in [0, {MAX_LEVEL + 1}], not {ignore_mp_level!r}")
         if self.look_rooms < 1:
             raise ValueError("the roster has no room records (look_rooms is 0): there is no room to set or to be let into")
-        if len(events) * self.capacity >= 2**31 - 1:
-            raise ValueError(f"{len(events)} events to {self.capacity} slots: K x capacity must be below 2^31 - 1")
-        bound = _variant_at(sum(_ACCESS_ROWS) * len(events), 4 * len(events))
-        if bound > MANY_ARENA_CAP:
-            raise ValueError(f"call too large: its variant bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
-                             f"(MANY_ARENA_CAP): split it")
-        texts, slots, coms, wcs = [], [], [], []
-        for k, ev in enumerate(events):
-            if not isinstance(ev, tuple) or len(ev) != 4:
-                raise ValueError(f"event {k}: expected a (slot, com, inpstr, word_count) tuple, "
-                                 f"got {type(ev).__name__}{f' of {len(ev)}' if isinstance(ev, tuple) else ''}")
-            slot, com, inpstr, wc = ev
-            try:
-                slot = self._slot(slot)
-                if not _is_int(com, COM_PUBLIC, COM_INVITE):
-                    raise ValueError(f"com must be COM_PUBLIC, COM_PRIVATE, COM_LETMEIN or COM_INVITE ({COM_PUBLIC} .. {COM_INVITE}), "
-                                     f"not {com!r}")
-                text = _as_text(inpstr)
-                if len(text) >= ARR_SIZE:
-                    raise ValueError(f"inpstr of {len(text)} bytes: the talker's input line holds at most {ARR_SIZE - 1}")
-                if not _is_int(wc, 0, MAX_WORDS):
-                    raise ValueError(f"word_count must be an int in [0, {MAX_WORDS}], not {wc!r}")
-                if not 0 <= self._room[slot] < self.look_rooms:
-                    raise ValueError(f"the actor, slot {slot}, is in " + (f"room {int(self._room[slot])}, which has no room record"
-                                     if self._room[slot] >= 0 else "no room") + f" (look_rooms is {self.look_rooms})")
-                if self._flags[slot] & ROSTER_FLAGS["login"]:
-                    raise ValueError(f"the actor, slot {slot}, is still logging in")
-                if self._speech[slot, USER_NAME_LEN] == 0:
-                    raise ValueError(f"the actor, slot {slot}, has no name")
-            except ValueError as e:
-                raise ValueError(f"event {k}: {e}") from None
-            texts.append(text)
-            slots.append(slot)
-            coms.append(int(com))
-            wcs.append(int(wc))
-        lens = np.fromiter((len(t) for t in texts), dtype=np.int64, count=len(texts))
-        if int(lens.sum()) >= 2**31 // 32:
-            raise ValueError("call text larger than 64 MiB: split it")
-        return (b"".join(texts), _offsets(lens, np.int32), lens.astype(np.int32), np.array(slots, dtype=np.int32),
-                np.array(coms, dtype=np.uint8), np.array(wcs, dtype=np.uint8))
+        inps, *packed = self._prepare_events(events, actor="actor", rows=_ACCESS_ROWS, texts=4, coms=_ACCESS_COMS,
+                                             com_rule=_ACCESS_COM_RULE)
+        return (b"".join(inps), *packed)
 
     def access_many(self, events, *, gatecrash_level, min_private_users, ignore_mp_level) -> Access:
         """K ``.public`` / ``.private`` / ``.letmein`` / ``.invite`` events, decided and composed on the device: a non-empty
@@ -3040,15 +3070,9 @@ class Roster:
         text, text_off, lens, slots, coms, wcs = self._prepare_access(events, gatecrash_level, min_private_users, ignore_mp_level)
         lib = _load()
         handle = self._device_handle(lib)
-        k, words = len(lens), (self.capacity + 63) // 64
-        ctext_bytes = sum(_ACCESS_ROWS) * k
-        outcome, target_room, target_slot = np.empty(k, dtype=np.int8), np.empty(k, dtype=np.int32), np.empty(k, dtype=np.int32)
-        clen = np.empty((4, k), dtype=np.int32)
-        bits = np.zeros((4, k, words), dtype=np.uint64)            # the device's two, then the actor alone and the invited alone
-        vn, vw = np.empty((4, k, 2), dtype=np.int64), np.empty((4, k, 2), dtype=np.int32)
-        vwsz = np.empty((4, k, 2, MAX_WRITES), dtype=np.int32)
-        ctext = np.empty(ctext_bytes, dtype=np.uint8)
-        var = np.empty(_variant_at(ctext_bytes, 4 * k), dtype=np.uint8)
+        k = len(lens)
+        outcome, clen, bits, vn, vw, vwsz, ctext, var = self._event_arrays(k, _ACCESS_ROWS, 4)
+        target_room, target_slot = np.empty(k, dtype=np.int32), np.empty(k, dtype=np.int32)
         tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
         t = _RosterTiming()
         rc = lib.nd_roster_access(handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(slots), _ptr(coms), _ptr(wcs),
@@ -3063,18 +3087,9 @@ class Roster:
         self._dirty = self._speech_dirty = self._rooms_dirty = self._go_dirty = False
         if self.clones:
             self._clones_dirty = False
-        rows = np.array(_ACCESS_ROWS, dtype=np.int64)
-        tstarts = ((np.cumsum(rows) - rows) * k)[:, None] + rows[:, None] * np.arange(k, dtype=np.int64)
-        starts = _variant_starts(tstarts, clen)
-        has = np.flatnonzero(clen[ACCESS_REPLY] >= 0)
-        bits[ACCESS_REPLY, has, slots[has] // 64] = np.uint64(1) << (slots[has] % 64).astype(np.uint64)
-        has = np.flatnonzero(clen[ACCESS_NOTICE] >= 0)          # write_user(u, text): ignall, afk and the room play no part
-        bits[ACCESS_NOTICE, has, target_slot[has] // 64] = np.uint64(1) << (target_slot[has] % 64).astype(np.uint64)
-        timing = _timing_of(t)
-        colour_bits = _pack((self._flags & ROSTER_FLAGS["colour"]) != 0)
-        plans = [Plan(capacity=self.capacity, admitted_bits=bits[i], colour_bits=colour_bits, variants=var,
-                      variant_starts=starts[i], variant_sizes=vn[i], write_counts=vw[i], write_sizes=vwsz[i],
-                      timing=dict(timing)) for i in range(4)]
+        # the device's two, then the actor alone and the invited alone
+        tstarts, plans, timing = self._event_plans(_ACCESS_ROWS, clen, bits, vn, vw, vwsz, var, t,
+                                                   [(ACCESS_REPLY, slots), (ACCESS_NOTICE, target_slot)])
         access = Access(outcome=outcome, target_room=target_room, target_slot=target_slot, reply=plans[ACCESS_REPLY],
                         here=plans[ACCESS_HERE], there=plans[ACCESS_THERE], notice=plans[ACCESS_NOTICE], texts=ctext,
                         text_starts=tstarts, text_sizes=clen.astype(np.int64), timing=timing)
@@ -3082,25 +3097,17 @@ class Roster:
         for k in access.effective().tolist():
             if outcome[k] == ACCESS_INVITED:
                 self.update(int(target_slot[k]), invite_room=int(self._room[slots[k]]))
-                continue
-            rm = int(target_room[k])
-            self.set_rooms(rm, access=PRIVATE if outcome[k] == ACCESS_SET_PRIVATE else PUBLIC)
-            if outcome[k] == ACCESS_SET_PUBLIC:
-                invited = np.flatnonzero(self._go_invite == rm)
-                if len(invited):
-                    self.update(invited, invite_room=None)
-                if rm < self.review_rooms:
-                    self.clear_review([rm])
+            elif outcome[k] == ACCESS_SET_PRIVATE:
+                self.set_rooms(int(target_room[k]), access=PRIVATE)
+            else:
+                self._returned_to_public(int(target_room[k]))
         return access
 
     def _prepare_clone(self, events, max_clones, gatecrash_level, min_private_users, record):
         """Each (slot, com, inpstr, word_count) and its actor's state checked, packed for nd_roster_clone: the inpstr, their
         offsets and lengths, the slots, the commands and the word counts, whether the call records, and the first record
         behind the last occupied one."""
-        if isinstance(events, (str, bytes, bytearray, np.ndarray)) or not hasattr(events, "__len__"):
-            raise ValueError(f"events must be a sequence of tuples, not {type(events).__name__}")
-        if len(events) == 0:
-            raise ValueError("empty call: no events")
+        self._check_sequence(events)
         if not _is_int(max_clones, 0, 2**31 - 1):
             raise ValueError(f"max_clones must be an int in [0, 2^31), not {max_clones!r}")
         if not _is_int(gatecrash_level, 0, MAX_LEVEL):
@@ -3115,52 +3122,17 @@ class Roster:
         if record and self.review_rooms < self.look_rooms:
             raise ValueError(f"record: a clone may speak in any of the {self.look_rooms} look rooms, and "
                              f"{self._ring_rooms_are()}")
-        if 4 * len(events) * self.capacity >= 2**31 - 1:
-            raise ValueError(f"{len(events)} events to {self.capacity} slots: 4 x K x capacity must be below 2^31 - 1")
-        texts, slots, coms, wcs = [], [], [], []
-        for k, ev in enumerate(events):
-            if not isinstance(ev, tuple) or len(ev) != 4:
-                raise ValueError(f"event {k}: expected a (slot, com, inpstr, word_count) tuple, "
-                                 f"got {type(ev).__name__}{f' of {len(ev)}' if isinstance(ev, tuple) else ''}")
-            slot, com, inpstr, wc = ev
-            try:
-                slot = self._slot(slot)
-                if not _is_int(com, 0, NUM_COMMANDS - 1) or int(com) not in (COM_CLONE, COM_DESTROY, COM_CSAY, COM_CHEAR):
-                    raise ValueError(f"com must be COM_CLONE, COM_DESTROY, COM_CSAY or COM_CHEAR ({COM_CLONE}, {COM_DESTROY}, "
-                                     f"{COM_CSAY}, {COM_CHEAR}), not {com!r}")
-                text = _as_text(inpstr)
-                if len(text) >= ARR_SIZE:
-                    raise ValueError(f"inpstr of {len(text)} bytes: the talker's input line holds at most {ARR_SIZE - 1}")
-                if not _is_int(wc, 0, MAX_WORDS):
-                    raise ValueError(f"word_count must be an int in [0, {MAX_WORDS}], not {wc!r}")
-                if not 0 <= self._room[slot] < self.look_rooms:
-                    raise ValueError(f"the actor, slot {slot}, is in " + (f"room {int(self._room[slot])}, which has no room record"
-                                     if self._room[slot] >= 0 else "no room") + f" (look_rooms is {self.look_rooms})")
-                if self._flags[slot] & ROSTER_FLAGS["login"]:
-                    raise ValueError(f"the actor, slot {slot}, is still logging in")
-                if self._speech[slot, USER_NAME_LEN] == 0:
-                    raise ValueError(f"the actor, slot {slot}, has no name")
-            except ValueError as e:
-                raise ValueError(f"event {k}: {e}") from None
-            texts.append(text)
-            slots.append(slot)
-            coms.append(int(com))
-            wcs.append(int(wc))
         # create_user() == NULL has no counterpart: every .clone of the call must find a record behind the last occupied one
         owned = np.flatnonzero(self._clone_owner >= 0)
         tail = int(owned[-1]) + 1 if len(owned) else 0
-        if coms.count(COM_CLONE) > self.clones - tail:
-            raise ValueError(f"{coms.count(COM_CLONE)} .clone events, and {self.clones - tail} empty clone records behind the last "
-                             f"occupied one, record {tail - 1}, of {self.clones}: split the call, or make a roster with more")
-        lens = np.fromiter((len(t) for t in texts), dtype=np.int64, count=len(texts))
-        if int(lens.sum()) >= 2**31 // 32:
-            raise ValueError("call text larger than 64 MiB: split it")
-        bound = _variant_at(sum(_CLONE_ROWS) * len(lens) + _composed_at(int(lens.sum()), len(lens)), 6 * len(lens))
-        if bound > MANY_ARENA_CAP:
-            raise ValueError(f"call too large: its variant bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
-                             f"(MANY_ARENA_CAP): split it")
-        return (b"".join(texts), _offsets(lens, np.int32), lens.astype(np.int32), np.array(slots, dtype=np.int32),
-                np.array(coms, dtype=np.uint8), np.array(wcs, dtype=np.uint8), record, tail)
+
+        def check_free(coms):
+            if coms.count(COM_CLONE) > self.clones - tail:
+                raise ValueError(f"{coms.count(COM_CLONE)} .clone events, and {self.clones - tail} empty clone records behind the "
+                                 f"last occupied one, record {tail - 1}, of {self.clones}: split the call, or make a roster with more")
+        inps, *packed = self._prepare_events(events, actor="actor", rows=_CLONE_ROWS, texts=6, coms=_CLONE_COMS,
+                                             com_rule=_CLONE_COM_RULE, said=True, then=check_free)
+        return (b"".join(inps), *packed, record, tail)
 
     def clone_many(self, events, *, max_clones, gatecrash_level, min_private_users, record=False) -> Clone:
         """K ``.clone`` / ``.destroy`` / ``.csay`` / ``.chear`` events, decided and composed on the device: a non-empty
@@ -3236,17 +3208,10 @@ class Roster:
                                                                                       min_private_users, record)
         lib = _load()
         handle = self._device_handle(lib)
-        k, words = len(lens), (self.capacity + 63) // 64
-        rows = np.array(_CLONE_ROWS, dtype=np.int64)
-        ctext_bytes = int(rows.sum()) * k + _composed_at(len(text), k)
-        outcome, target_room, target_slot = np.empty(k, dtype=np.int8), np.empty(k, dtype=np.int32), np.empty(k, dtype=np.int32)
+        k = len(lens)
+        outcome, clen, bits, vn, vw, vwsz, ctext, var = self._event_arrays(k, _CLONE_ROWS, 6, _composed_at(len(text), k))
+        target_room, target_slot = np.empty(k, dtype=np.int32), np.empty(k, dtype=np.int32)
         rec, reset = np.empty(k, dtype=np.int32), np.empty(k, dtype=np.uint8)
-        clen = np.empty((6, k), dtype=np.int32)
-        bits = np.zeros((6, k, words), dtype=np.uint64)            # the device's four, then the actor alone and the owner alone
-        vn, vw = np.empty((6, k, 2), dtype=np.int64), np.empty((6, k, 2), dtype=np.int32)
-        vwsz = np.empty((6, k, 2, MAX_WRITES), dtype=np.int32)
-        ctext = np.empty(ctext_bytes, dtype=np.uint8)
-        var = np.empty(_variant_at(ctext_bytes, 6 * k), dtype=np.uint8)
         tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
         clear = self._pending_clear() if recording else None
         t = _RosterTiming()
@@ -3263,23 +3228,11 @@ class Roster:
         self._dirty = self._speech_dirty = self._rooms_dirty = self._go_dirty = self._clones_dirty = False
         if recording:
             self._clear_sent()
-        # the here, there and reset lines, the said lines as speak_many lays its own, the replies, the notices
-        at = np.arange(k, dtype=np.int64)
-        fixed = (np.cumsum(rows) - rows) * k
-        fixed[CLONE_SAID_LINE:] += _composed_at(len(text), k)
-        tstarts = np.stack([fixed[0] + rows[0] * at, fixed[1] + rows[1] * at, fixed[2] + rows[2] * at,
-                            int(rows[:3].sum()) * k + _composed_at(text_off.astype(np.int64), at),
-                            fixed[3] + rows[3] * at, fixed[4] + rows[4] * at])
-        starts = _variant_starts(tstarts, clen)
-        has = np.flatnonzero(clen[CLONE_REPLY] >= 0)
-        bits[CLONE_REPLY, has, slots[has] // 64] = np.uint64(1) << (slots[has] % 64).astype(np.uint64)
-        has = np.flatnonzero(clen[CLONE_NOTICE] >= 0)           # write_user(u2, text): ignall, afk and the room play no part
-        bits[CLONE_NOTICE, has, target_slot[has] // 64] = np.uint64(1) << (target_slot[has] % 64).astype(np.uint64)
-        timing = _timing_of(t)
-        colour_bits = _pack((self._flags & ROSTER_FLAGS["colour"]) != 0)
-        plans = [Plan(capacity=self.capacity, admitted_bits=bits[i], colour_bits=colour_bits, variants=var,
-                      variant_starts=starts[i], variant_sizes=vn[i], write_counts=vw[i], write_sizes=vwsz[i],
-                      timing=dict(timing)) for i in range(6)]
+        # the here, there and reset lines, the said lines as speak_many lays its own, the replies, the notices: the
+        # device's four, then the actor alone and the owner alone
+        tstarts, plans, timing = self._event_plans(_CLONE_ROWS, clen, bits, vn, vw, vwsz, var, t,
+                                                   [(CLONE_REPLY, slots), (CLONE_NOTICE, target_slot)],
+                                                   said=(CLONE_SAID_LINE, text_off, len(text)))
         created = np.full(k, -1, dtype=np.int32)
         clone = Clone(outcome=outcome, target_room=target_room, target_slot=target_slot, record=rec, created=created,
                       reset=reset.astype(bool), reply=plans[CLONE_REPLY], here=plans[CLONE_HERE], there=plans[CLONE_THERE],
@@ -3296,13 +3249,7 @@ class Roster:
             elif outcome[k] == CLONE_DESTROYED:
                 self.set_clones(int(rec[k]), owner=None)
                 if clone.reset[k]:
-                    rm = int(target_room[k])
-                    self.set_rooms(rm, access=PUBLIC)
-                    invited = np.flatnonzero(self._go_invite == rm)
-                    if len(invited):
-                        self.update(invited, invite_room=None)
-                    if rm < self.review_rooms:
-                        self.clear_review([rm])
+                    self._returned_to_public(int(target_room[k]))
         # the gaps the destroyed records left close: later records move down, order kept, as the user list loses a node
         gone = rec[outcome == CLONE_DESTROYED]
         if len(gone):
@@ -3319,51 +3266,14 @@ class Roster:
     def _prepare_set(self, events):
         """Each (slot, com, inpstr, word_count) and its actor's state checked, packed for nd_roster_set: the inpstr, their
         offsets and lengths, the slots, the commands and the word counts."""
-        if isinstance(events, (str, bytes, bytearray, np.ndarray)) or not hasattr(events, "__len__"):
-            raise ValueError(f"events must be a sequence of tuples, not {type(events).__name__}")
-        if len(events) == 0:
-            raise ValueError("empty call: no events")
-        if len(events) * self.capacity >= 2**31 - 1:
-            raise ValueError(f"{len(events)} events to {self.capacity} slots: K x capacity must be below 2^31 - 1")
-        bound = _variant_at(sum(_SET_ROWS) * len(events), 3 * len(events))
-        if bound > MANY_ARENA_CAP:
-            raise ValueError(f"call too large: its variant bound is {bound} bytes, the cap is {MANY_ARENA_CAP} "
-                             f"(MANY_ARENA_CAP): split it")
-        texts, slots, coms, wcs = [], [], [], []
-        for k, ev in enumerate(events):
-            if not isinstance(ev, tuple) or len(ev) != 4:
-                raise ValueError(f"event {k}: expected a (slot, com, inpstr, word_count) tuple, "
-                                 f"got {type(ev).__name__}{f' of {len(ev)}' if isinstance(ev, tuple) else ''}")
-            slot, com, inpstr, wc = ev
-            try:
-                slot = self._slot(slot)
-                if not _is_int(com, 0, NUM_COMMANDS - 1) or com not in SET_COMS:
-                    raise ValueError(f"com must be one of the fourteen commands of SET_COMS {SET_COMS}, not {com!r}")
-                text = _as_text(inpstr)
-                if len(text) >= ARR_SIZE:
-                    raise ValueError(f"inpstr of {len(text)} bytes: the talker's input line holds at most {ARR_SIZE - 1}")
-                if not _is_int(wc, 0, MAX_WORDS):
-                    raise ValueError(f"word_count must be an int in [0, {MAX_WORDS}], not {wc!r}")
-                if self._room[slot] < 0:
-                    raise ValueError(f"the actor, slot {slot}, is in no room")
-                if self._flags[slot] & ROSTER_FLAGS["login"]:
-                    raise ValueError(f"the actor, slot {slot}, is still logging in")
-                if self._speech[slot, USER_NAME_LEN] == 0:
-                    raise ValueError(f"the actor, slot {slot}, has no name")
-                if com == COM_TOPIC and not self._room[slot] < self.look_rooms:
-                    raise ValueError(f"a .topic by slot {slot} in room {int(self._room[slot])}, which has no room record "
-                                     f"(look_rooms is {self.look_rooms})")
-            except ValueError as e:
-                raise ValueError(f"event {k}: {e}") from None
-            texts.append(text)
-            slots.append(slot)
-            coms.append(int(com))
-            wcs.append(int(wc))
-        lens = np.fromiter((len(t) for t in texts), dtype=np.int64, count=len(texts))
-        if int(lens.sum()) >= 2**31 // 32:
-            raise ValueError("call text larger than 64 MiB: split it")
-        return (texts, _offsets(lens, np.int32), lens.astype(np.int32), np.array(slots, dtype=np.int32),
-                np.array(coms, dtype=np.uint8), np.array(wcs, dtype=np.uint8))
+        self._check_sequence(events)
+
+        def check_topic(slot):
+            if not self._room[slot] < self.look_rooms:
+                raise ValueError(f"a .topic by slot {slot} in room {int(self._room[slot])}, which has no room record "
+                                 f"(look_rooms is {self.look_rooms})")
+        return self._prepare_events(events, actor="actor", rows=_SET_ROWS, texts=3, coms=SET_COMS, com_rule=_SET_COM_RULE,
+                                    need_room_record=False, check_last=(COM_TOPIC, check_topic))
 
     def set_many(self, events) -> Settings:
         """K events by which a user sets its own state, decided and composed on the device: a non-empty sequence of
@@ -3424,14 +3334,8 @@ class Roster:
         text = b"".join(inps)
         lib = _load()
         handle = self._device_handle(lib)
-        k, words = len(lens), (self.capacity + 63) // 64
-        ctext_bytes = sum(_SET_ROWS) * k
-        outcome, clen = np.empty(k, dtype=np.int8), np.empty((3, k), dtype=np.int32)
-        bits = np.zeros((3, k, words), dtype=np.uint64)             # the device's, then the actor alone twice
-        vn, vw = np.empty((3, k, 2), dtype=np.int64), np.empty((3, k, 2), dtype=np.int32)
-        vwsz = np.empty((3, k, 2, MAX_WRITES), dtype=np.int32)
-        ctext = np.empty(ctext_bytes, dtype=np.uint8)
-        var = np.empty(_variant_at(ctext_bytes, 3 * k), dtype=np.uint8)
+        k = len(lens)
+        outcome, clen, bits, vn, vw, vwsz, ctext, var = self._event_arrays(k, _SET_ROWS, 3)
         tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
         speech_dirty = self._speech_dirty or self._private_dirty or self._set_dirty
         rooms_read = bool((coms == COM_TOPIC).any())
@@ -3448,20 +3352,11 @@ class Roster:
         self._afk_dirty = self._udesc_dirty = self._go_dirty = False
         if rooms_read:
             self._rooms_dirty = False
-        rows = np.array(_SET_ROWS, dtype=np.int64)
-        tstarts = ((np.cumsum(rows) - rows) * k)[:, None] + rows[:, None] * np.arange(k, dtype=np.int64)
-        starts = _variant_starts(tstarts, clen)
-        for row in (SET_REPLY, SET_REPLY2):
-            has = np.flatnonzero(clen[row] >= 0)
-            bits[row, has, slots[has] // 64] = np.uint64(1) << (slots[has] % 64).astype(np.uint64)
-        timing = _timing_of(t)
-        colour = (self._flags & ROSTER_FLAGS["colour"]) != 0
-        colour_bits = _pack(colour)
-        reply_colour = colour[slots].astype(np.uint8)
+        # the device's, then the actor alone twice
+        tstarts, plans, timing = self._event_plans(_SET_ROWS, clen, bits, vn, vw, vwsz, var, t,
+                                                   [(SET_REPLY, slots), (SET_REPLY2, slots)])
+        reply_colour = ((self._flags[slots] & ROSTER_FLAGS["colour"]) != 0).astype(np.uint8)
         reply_colour[(outcome == SET_COLOUR_ON) | (outcome == SET_COLOUR_OFF)] = 1
-        plans = [Plan(capacity=self.capacity, admitted_bits=bits[i], colour_bits=colour_bits, variants=var,
-                      variant_starts=starts[i], variant_sizes=vn[i], write_counts=vw[i], write_sizes=vwsz[i],
-                      timing=dict(timing)) for i in range(3)]
         got = Settings(outcome=outcome, reply=plans[SET_REPLY], reply2=plans[SET_REPLY2], here=plans[SET_HERE],
                        reply_colour=reply_colour, texts=ctext, text_starts=tstarts, text_sizes=clen.astype(np.int64), timing=timing)
         # the changes, on the host mirrors and in event order: the next call of any kind uploads what it reads

@@ -34,7 +34,10 @@
 // nuts_roster_go, nuts_roster_access, nuts_roster_clone and nuts_roster_set decide and compose the commands that change what
 // the other kernels read -- a user's room, a room's access and the invitations, the clone records, and what a user sets on
 // itself -- each followed by a one-wave kernel that defers the events an earlier one of the call touched; none of them
-// writes a kept table (their sections below).
+// writes a kept table (their sections below).  The four are one kind of call, the event call, and what they share is
+// written once: the head of their arguments (EventArgs), the walk of the order kernels (order_events, with a rule per
+// kernel: its keys, what hits, what touches), and on the host the layouts' head and tail (take_events, take_event_texts)
+// and the steps of the call from check_events to copy_event_results.
 //
 // Hard bounds per item of a text of len < 2000 bytes: 6*len + 4 output bytes (a '\n' with colour
 // on is the costliest input byte, plus the trailing reset) and 16 writes.  The host sizes its buffers
@@ -2679,8 +2682,9 @@ static_assert(kRmsnRow < kTextSize && kMaxLookRooms * sizeof(int) <= 4096, "rost
 //            whose slot, current room or resolved target room is touched is deferred: its outcome becomes kGoDeferred, its
 //            four texts void, and it touches nothing.  An event that moved and was not deferred touches its slot, the room
 //            it left and the room it entered.  The events that remain are pairwise disjoint in slots and rooms, so each
-//            one decided and planned against the snapshot is what running them one after another gives.  The wave loads
-//            64 events at a time, a lane each, and steps through them by shuffles; lane 0 sets the bits.
+//            one decided and planned against the snapshot is what running them one after another gives.  The walk is
+//            order_events, which the order kernels of the other three event calls share with a rule of their own: the
+//            wave loads 64 events at a time, a lane each, and steps through them by shuffles; lane 0 sets the bits.
 //   plan     nuts_roster_speak_plan with 3K room lines and K replies, over the table as it was before the call.
 constexpr int kGoRec = 88, kPhraseLen = 40;                // a slot's row of the go table; nuts333.h:26 PHRASE_LEN
 constexpr int kGoIn = 0, kGoInLen = 40, kGoOut = 41, kGoOutLen = 81, kGoInvite = 84;
@@ -2705,31 +2709,39 @@ constexpr int64_t go_text_at(int kind, int64_t b, int64_t k)
            + go_row(kind) * b;
 }
 
-struct GoArgs {
+// What the compose kernels of the four event calls -- go, access, clone, set -- are all passed, the head of their arguments:
+// the host writes the steps that read only these once (check_events .. copy_event_results).  Each call's own members follow
+// in one order -- the results, the commands and settings, the tables -- under which nuts_roster_access and nuts_roster_clone,
+// which use every scalar register there is, still keep all their arguments in them.
+struct EventArgs {
     const int32_t* room;         // [capacity] the roster's table
-    const uint8_t* slotf;        // [capacity] and its flag bytes: login
-    const uint8_t* speech;       // the tables this call reads, the uploads or the kept ones: the speaker state (name, vis, level),
-    const uint8_t* records;      // the clone records as take_clones lays them out (nullptr: the roster has none),
-    const uint8_t* rooms;        // the room records,
-    const uint8_t* go;           // [capacity * 88] and the go table
-    Kept kept[4];                // in that order
+    const uint8_t* slotf;        // [capacity] and its flag bytes
     const uint8_t* text;         // the K inpstr, packed
     const int32_t* text_off;     // [k]
     const int32_t* text_len;     // [k]
-    const int32_t* slot;         // [k] the mover
+    const int32_t* slot;         // [k] the event's user: the mover, the actor
     const uint8_t* words;        // [k] word_count
-    const int32_t* ctext_off;    // [4k] where each text's slot starts in ctext
-    int k, capacity, look_rooms, clones, gatecrash_level, min_private_users;
+    const int32_t* ctext_off;    // [texts * k] where each text's slot starts in ctext
+    int k, capacity;
     int* violations;             // composed texts past their slot (zeroed by the host's upload)
     uint8_t* ctext;              // the composed texts
-    int32_t* clen;               // [4k] their lengths; -1: no such text
+    int32_t* clen;               // [texts * k] their lengths; -1: no such text
     int8_t* outcome;             // [k]
+};
+
+struct GoArgs : EventArgs {      // slotf: login
     int32_t* target;             // [k] the room the word resolved to; -1: none, or get_room was not reached
     int32_t* old_room;           // [k] the mover's room before the call
     uint8_t* returned;           // [k] 1: the old room returns to public
     int32_t* rm;                 // [3k] the room texts' rooms, as SpeakPlanArgs.rm
     int32_t* sender;             // [3k] and their senders (-1: none)
     int32_t* com_num;            // [3k]
+    int look_rooms, clones, gatecrash_level, min_private_users;
+    const uint8_t* speech;       // the tables this call reads, the uploads or the kept ones: the speaker state (name, vis, level),
+    const uint8_t* records;      // the clone records as take_clones lays them out (nullptr: the roster has none),
+    const uint8_t* rooms;        // the room records,
+    const uint8_t* go;           // [capacity * 88] and the go table
+    Kept kept[4];                // in that order
 };
 
 // Does s[0 .. slen) begin with w[0 .. wlen), wlen <= kWordLen?  strncmp(s, w, strlen(w)) == 0 over a NUL-ended s, by a whole
@@ -2931,6 +2943,58 @@ static_assert(kGoRec % 4 == 0 && kGoInvite % 4 == 0 && kGoOutLen < kGoInvite && 
 static_assert(kWordLen < 64 && sizeof(" chants a spell and vanishes into a magical blue vortex!\n") - 1 <= 64,
               "roster_go: a word is a byte per lane, and the pieces of a compose() fit a wave");
 
+// The order stage of an event call (go, access, clone, set): ONE WAVE walks the call's events in call order and defers those
+// that an earlier event of the call, itself effective and not deferred, touched -- so every event that remains was decided
+// against a snapshot that nothing before it in the call changed.  What is touched is kept as bits in LDS, zeroed first.  The
+// events are taken 64 at a time, a lane each; each event's keys and outcome are then handed to the whole wave in turn, tested
+// against the bitmaps, and marked by lane 0 between two barriers that every lane reaches.  A deferred event gets the rule's
+// deferred outcome, its texts become void, and the rule clears what else the compose kernel wrote for it.
+// A Rule is the kernel's argument struct: outcome[k], clen[kTexts * k], k; kKeys ints an event, which load() reads for
+// event b (any in-range value for a lane without an event, which nobody looks at); hit(key, maps), whether an earlier event
+// touched one of them; touch(key, outcome, maps), which marks what an effective event touches; kDeferred; kMapWords of
+// bitmaps, which the rule divides among its keys; also_void(b).
+constexpr int kOrderRoomWords = kMaxLookRooms / 32, kOrderSlotWords = kGoMaxSlots / 32;
+__device__ __forceinline__ bool bit_of(const uint32_t* map, int i) { return (map[i >> 5] >> (i & 31)) & 1u; }
+__device__ __forceinline__ void set_bit(uint32_t* map, int i) { map[i >> 5] |= 1u << (i & 31); }
+
+template <typename Rule>
+__device__ void order_events(const Rule& a)
+{
+    static_assert(Rule::kMapWords % 4 == 0, "order_events: the bitmaps are zeroed four words a store");
+    __shared__ uint4 s_zeroed[Rule::kMapWords / 4];
+    uint32_t* s_maps = reinterpret_cast<uint32_t*>(s_zeroed);
+    const int lane = (int)threadIdx.x;      // one wave
+    for (int i = lane; i < Rule::kMapWords / 4; i += 64) s_zeroed[i] = make_uint4(0, 0, 0, 0);   // most of a small call's time
+    __syncthreads();
+    for (int base = 0; base < a.k; base += 64) {
+        const int k = base + lane;
+        const bool live = k < a.k;
+        int mine[Rule::kKeys], key[Rule::kKeys];
+        a.load(k, live, mine);
+        const int out = live ? a.outcome[k] : Rule::kDeferred;
+        const int count = a.k - base < 64 ? a.k - base : 64;
+        bool defer = false;
+        for (int i = 0; i < count; i++) {   // in call order; every lane follows, lane 0 sets the bits
+#pragma unroll
+            for (int j = 0; j < Rule::kKeys; j++) key[j] = __shfl(mine[j], i);
+            const int oc = __shfl(out, i);
+            const bool hit = Rule::hit(key, s_maps);
+            if (lane == i) defer = hit;
+            __syncthreads();
+            if (lane == 0 && !hit) Rule::touch(key, oc, s_maps);
+            __syncthreads();
+        }
+        if (live && defer) {
+            a.outcome[k] = (int8_t)Rule::kDeferred;
+#pragma unroll
+            for (int kind = 0; kind < Rule::kTexts; kind++) a.clen[kind * a.k + k] = -1;
+            a.also_void(k);
+        }
+    }
+}
+
+// nuts_roster_go_order's rule.  Keys: the mover's slot, the room left, the room the word resolved to (-1: none).  Its bitmaps,
+// as nuts_roster_access_order's and nuts_roster_clone_order's: a bit per look room, then a bit per slot.
 struct GoOrderArgs {
     const int32_t* slot;         // [k] the movers
     const int32_t* old_room;     // [k] what nuts_roster_go wrote
@@ -2939,42 +3003,25 @@ struct GoOrderArgs {
     int8_t* outcome;             // [k] becomes kGoDeferred for a deferred event
     int32_t* clen;               // [4k] whose four texts become void
     uint8_t* returned;           // [k] and whose room does not return
-};
 
-__device__ void roster_go_order(const GoOrderArgs& a)
-{
-    __shared__ uint32_t s_rooms[kMaxLookRooms / 32], s_slots[kGoMaxSlots / 32];
-    const int lane = (int)threadIdx.x;      // one wave
-    for (int i = lane; i < kMaxLookRooms / 32; i += 64) s_rooms[i] = 0;
-    for (int i = lane; i < kGoMaxSlots / 32; i += 64) s_slots[i] = 0;
-    __syncthreads();
-    for (int base = 0; base < a.k; base += 64) {
-        const int k = base + lane;
-        const bool live = k < a.k;
-        const int slot = live ? a.slot[k] : 0, old = live ? a.old_room[k] : 0, tgt = live ? a.target[k] : -1;
-        const int out = live ? a.outcome[k] : kGoWhere;
-        const int count = a.k - base < 64 ? a.k - base : 64;
-        bool defer = false;
-        for (int i = 0; i < count; i++) {   // in call order; every lane follows, lane 0 sets the bits
-            const int s = __shfl(slot, i), o = __shfl(old, i), t = __shfl(tgt, i), oc = __shfl(out, i);
-            const bool hit = ((s_slots[s >> 5] >> (s & 31)) & 1u) || ((s_rooms[o >> 5] >> (o & 31)) & 1u) ||
-                             (t >= 0 && ((s_rooms[t >> 5] >> (t & 31)) & 1u));
-            if (lane == i) defer = hit;
-            __syncthreads();
-            if (lane == 0 && !hit && oc <= kGoUnseen) {     // a move touches its slot, the room left and the room entered
-                s_slots[s >> 5] |= 1u << (s & 31);
-                s_rooms[o >> 5] |= 1u << (o & 31);
-                s_rooms[t >> 5] |= 1u << (t & 31);
-            }
-            __syncthreads();
-        }
-        if (live && defer) {
-            a.outcome[k] = (int8_t)kGoDeferred;
-            a.clen[k] = a.clen[a.k + k] = a.clen[2 * a.k + k] = a.clen[3 * a.k + k] = -1;
-            a.returned[k] = 0;
-        }
+    static constexpr int kKeys = 3, kTexts = kGoTexts, kDeferred = kGoDeferred, kMapWords = kOrderRoomWords + kOrderSlotWords;
+    __device__ void load(int b, bool live, int (&key)[kKeys]) const
+    {
+        key[0] = live ? slot[b] : 0, key[1] = live ? old_room[b] : 0, key[2] = live ? target[b] : -1;
     }
-}
+    static __device__ bool hit(const int (&key)[kKeys], const uint32_t* maps)
+    {
+        return bit_of(maps + kOrderRoomWords, key[0]) || bit_of(maps, key[1]) || (key[2] >= 0 && bit_of(maps, key[2]));
+    }
+    static __device__ void touch(const int (&key)[kKeys], int outcome, uint32_t* maps)
+    {
+        if (outcome > kGoUnseen) return;    // a move touches its slot, the room left and the room entered
+        set_bit(maps + kOrderRoomWords, key[0]);
+        set_bit(maps, key[1]);
+        set_bit(maps, key[2]);
+    }
+    __device__ void also_void(int b) const { returned[b] = 0; }
+};
 
 static_assert(kMaxLookRooms % 32 == 0 && kGoMaxSlots % 32 == 0, "roster_go_order: the bitmaps are whole words");
 
@@ -2997,7 +3044,7 @@ static_assert(kMaxLookRooms % 32 == 0 && kGoMaxSlots % 32 == 0, "roster_go_order
 //            the two room lines: the here line to the actor's room with the actor as sender, the there line to the other
 //            room without one.  No atomics: the same bytes on every run.
 //            Blocks past the events copy freshly uploaded tables into the kept allocations.
-//   order    nuts_roster_access_order, ONE WAVE, after nuts_roster_go_order.  Set private and set public touch the room
+//   order    nuts_roster_access_order, ONE WAVE: order_events by its own rule.  Set private and set public touch the room
 //            whose access changes, invited touches the invited slot.  An event whose actor's room, resolved room or found
 //            slot an earlier event of the call that was not itself deferred touched is deferred: its outcome becomes
 //            kAccDeferred and its four texts void.
@@ -3066,31 +3113,19 @@ __device__ const AccessReply kAccReply[] = {
 };
 static_assert(sizeof(kAccReply) / sizeof(kAccReply[0]) == kAccDeferred, "kAccReply: a line for every outcome nuts_roster_access decides");
 
-struct AccessArgs {
-    const int32_t* room;         // [capacity] the roster's table
-    const uint8_t* slotf;        // [capacity] and its flag bytes: login
-    const uint8_t* speech;       // the tables this call reads, the uploads or the kept ones: the speaker state (name, vis, level),
-    const uint8_t* records;      // the clone records as take_clones lays them out (nullptr: the roster has none),
-    const uint8_t* rooms;        // the room records,
-    const uint8_t* go;           // [capacity * 88] and the go table: invite_room
-    Kept kept[4];                // the speaker state, the clone records, the go table, the room records
-    const uint8_t* text;         // the K inpstr, packed
-    const int32_t* text_off;     // [k]
-    const int32_t* text_len;     // [k]
-    const int32_t* slot;         // [k] the actor
-    const uint8_t* com;          // [k] NP_PUBLIC, NP_PRIVATE, NP_LETMEIN or NP_INVITE
-    const uint8_t* words;        // [k] word_count
-    const int32_t* ctext_off;    // [4k] where each text's slot starts in ctext
-    int k, capacity, look_rooms, clones, gatecrash_level, min_private_users, ignore_mp_level;
-    int* violations;             // composed texts past their slot (zeroed by the host's upload)
-    uint8_t* ctext;              // the composed texts
-    int32_t* clen;               // [4k] their lengths; -1: no such text
-    int8_t* outcome;             // [k]
+struct AccessArgs : EventArgs {  // slotf: login
     int32_t* target_room;        // [k] the room the event is about; -1: none, or the step was not reached
     int32_t* target_slot;        // [k] the slot get_user found; -1: none, or it was not asked
     int32_t* rm;                 // [2k] the room lines' rooms, as SpeakPlanArgs.rm
     int32_t* sender;             // [2k] and their senders (-1: none)
     int32_t* com_num;            // [2k]
+    const uint8_t* com;          // [k] NP_PUBLIC, NP_PRIVATE, NP_LETMEIN or NP_INVITE
+    int look_rooms, clones, gatecrash_level, min_private_users, ignore_mp_level;
+    const uint8_t* speech;       // the tables this call reads, the uploads or the kept ones: the speaker state (name, vis, level),
+    const uint8_t* records;      // the clone records as take_clones lays them out (nullptr: the roster has none),
+    const uint8_t* rooms;        // the room records,
+    const uint8_t* go;           // [capacity * 88] and the go table: invite_room
+    Kept kept[4];                // the speaker state, the clone records, the go table, the room records
 };
 
 __device__ void roster_access(const AccessArgs& a)
@@ -3302,6 +3337,7 @@ static_assert(kAccRow % 4 == 0 && kAccHereRow % 4 == 0 && kAccThereRow % 4 == 0 
 static_assert(sizeof("You shout asking to be let into the .\n") - 1 + kRoomNameLen <= 64 && kAccNoticeMax <= 64 &&
               sizeof("Inviting yourself to somewhere is the third sign of madness.\n") - 1 <= 64, "roster_access: the pieces of a compose() fit a wave");
 
+// nuts_roster_access_order's rule.  Keys: the actor's room, the room and the slot the word resolved to (-1: none).
 struct AccessOrderArgs {
     const int32_t* room;         // [capacity] the roster's table: the actors' rooms
     const int32_t* slot;         // [k] the actors
@@ -3310,40 +3346,23 @@ struct AccessOrderArgs {
     int k;
     int8_t* outcome;             // [k] becomes kAccDeferred for a deferred event
     int32_t* clen;               // [4k] whose four texts become void
-};
 
-__device__ void roster_access_order(const AccessOrderArgs& a)
-{
-    __shared__ uint32_t s_rooms[kMaxLookRooms / 32], s_slots[kGoMaxSlots / 32];
-    const int lane = (int)threadIdx.x;      // one wave
-    for (int i = lane; i < kMaxLookRooms / 32; i += 64) s_rooms[i] = 0;
-    for (int i = lane; i < kGoMaxSlots / 32; i += 64) s_slots[i] = 0;
-    __syncthreads();
-    for (int base = 0; base < a.k; base += 64) {
-        const int k = base + lane;
-        const bool live = k < a.k;
-        const int here = live ? a.room[a.slot[k]] : 0, trm = live ? a.target_room[k] : -1, tsl = live ? a.target_slot[k] : -1;
-        const int out = live ? a.outcome[k] : kAccLetWhere;
-        const int count = a.k - base < 64 ? a.k - base : 64;
-        bool defer = false;
-        for (int i = 0; i < count; i++) {   // in call order; every lane follows, lane 0 sets the bits
-            const int h = __shfl(here, i), r = __shfl(trm, i), s = __shfl(tsl, i), oc = __shfl(out, i);
-            const bool hit = ((s_rooms[h >> 5] >> (h & 31)) & 1u) || (r >= 0 && ((s_rooms[r >> 5] >> (r & 31)) & 1u)) ||
-                             (s >= 0 && ((s_slots[s >> 5] >> (s & 31)) & 1u));
-            if (lane == i) defer = hit;
-            __syncthreads();
-            if (lane == 0 && !hit) {        // setting an access touches the room, an invitation the invited slot
-                if (oc == kAccSetPrivate || oc == kAccSetPublic) s_rooms[r >> 5] |= 1u << (r & 31);
-                else if (oc == kAccInvited) s_slots[s >> 5] |= 1u << (s & 31);
-            }
-            __syncthreads();
-        }
-        if (live && defer) {
-            a.outcome[k] = (int8_t)kAccDeferred;
-            a.clen[k] = a.clen[a.k + k] = a.clen[2 * a.k + k] = a.clen[3 * a.k + k] = -1;
-        }
+    static constexpr int kKeys = 3, kTexts = kAccTexts, kDeferred = kAccDeferred, kMapWords = kOrderRoomWords + kOrderSlotWords;
+    __device__ void load(int b, bool live, int (&key)[kKeys]) const
+    {
+        key[0] = live ? room[slot[b]] : 0, key[1] = live ? target_room[b] : -1, key[2] = live ? target_slot[b] : -1;
     }
-}
+    static __device__ bool hit(const int (&key)[kKeys], const uint32_t* maps)
+    {
+        return bit_of(maps, key[0]) || (key[1] >= 0 && bit_of(maps, key[1])) || (key[2] >= 0 && bit_of(maps + kOrderRoomWords, key[2]));
+    }
+    static __device__ void touch(const int (&key)[kKeys], int outcome, uint32_t* maps)
+    {                                       // setting an access touches the room, an invitation the invited slot
+        if (outcome == kAccSetPrivate || outcome == kAccSetPublic) set_bit(maps, key[1]);
+        else if (outcome == kAccInvited) set_bit(maps + kOrderRoomWords, key[2]);
+    }
+    __device__ void also_void(int) const {}
+};
 
 // ------------------------------------------------------------------ the clone commands, of a resident roster
 //
@@ -3368,7 +3387,7 @@ __device__ void roster_access_order(const AccessOrderArgs& a)
 //            order and composes; lane 0 stores the lengths, the outcome, the room, the slot and the record the event
 //            resolved to, whether the room returns to public, and rm / sender / com / flags of the four room lines.
 //            Blocks past the events copy freshly uploaded tables into the kept allocations.
-//   order    nuts_roster_clone_order, ONE WAVE, after nuts_roster_access_order.  A created clone touches its owner and its
+//   order    nuts_roster_clone_order, ONE WAVE: order_events by its own rule.  A created clone touches its owner and its
 //            room, a destroyed one likewise.  An event whose owner -- the user get_user found, else the actor -- or
 //            resolved room an earlier event of the call that was not itself deferred touched is deferred: its outcome
 //            becomes kCloneDeferred, its six texts void, and nothing of it is recorded.
@@ -3414,26 +3433,7 @@ __host__ __device__ constexpr int clone_created(bool found, int before, int tota
     return found && (max_clones < 1 || before < max_clones) ? 1 : max_clones >= 1 && total >= max_clones ? 2 : 0;
 }
 
-struct CloneArgs {
-    const int32_t* room;         // [capacity] the roster's table
-    const uint8_t* slotf;        // [capacity] and its flag bytes: login
-    const uint8_t* speech;       // the tables this call reads, the uploads or the kept ones: the speaker state (name, vis, level),
-    const uint8_t* records;      // the clone records as take_clones lays them out,
-    const uint8_t* rooms;        // the room records,
-    const uint8_t* go;           // [capacity * 88] and the go table: invite_room
-    Kept kept[4];                // the speaker state, the go table, the room records, the clone records
-    const uint8_t* text;         // the K inpstr, packed
-    const int32_t* text_off;     // [k]
-    const int32_t* text_len;     // [k]
-    const int32_t* slot;         // [k] the actor
-    const uint8_t* com;          // [k] NP_CLONE, NP_DESTROY, NP_CSAY or NP_CHEAR
-    const uint8_t* words;        // [k] word_count
-    const int32_t* ctext_off;    // [6k] where each text's slot starts in ctext
-    int k, capacity, look_rooms, clones, gatecrash_level, min_private_users, max_clones, record;
-    int* violations;             // composed texts past their slot (zeroed by the host's upload)
-    uint8_t* ctext;              // the composed texts
-    int32_t* clen;               // [6k] their lengths; -1: no such text
-    int8_t* outcome;             // [k]
+struct CloneArgs : EventArgs {   // slotf: login
     int32_t* found;              // [3k] the room the event is about (-1: none, or the step was not reached); at k, the slot
                                  // get_user found (-1: none, or it was not asked); at 2k, the record found or destroyed (-1:
                                  // none).  One array, and one below: the kernel's arguments stay in scalar registers
@@ -3441,6 +3441,13 @@ struct CloneArgs {
     int32_t* line;               // [12k] the room lines' rooms, as SpeakPlanArgs.rm; at 4k, their senders (-1: none); at 8k,
                                  // their com_num
     uint8_t* flags;              // [k] bit 2: record the said line
+    const uint8_t* com;          // [k] NP_CLONE, NP_DESTROY, NP_CSAY or NP_CHEAR
+    int look_rooms, clones, gatecrash_level, min_private_users, max_clones, record;
+    const uint8_t* speech;       // the tables this call reads, the uploads or the kept ones: the speaker state (name, vis, level),
+    const uint8_t* records;      // the clone records as take_clones lays them out,
+    const uint8_t* rooms;        // the room records,
+    const uint8_t* go;           // [capacity * 88] and the go table: invite_room
+    Kept kept[4];                // the speaker state, the go table, the room records, the clone records
 };
 
 // Who stands in room rm, as reset_access counts (c:2095): the slots with that room, a name and no login flag, and the clone
@@ -3754,6 +3761,8 @@ static_assert(clone_created(true, 0, 1, 0) == 1 && clone_created(false, 5, 5, 0)
               clone_created(true, 2, 3, 2) == 2 && clone_created(false, 1, 1, 2) == 0 && clone_created(false, 2, 2, 2) == 2,
               "clone_created: create_clone's loop on paper");
 
+// nuts_roster_clone_order's rule.  Keys: the owner -- the slot get_user found, else the actor -- and the room the word
+// resolved to (-1: none).
 struct CloneOrderArgs {
     const int32_t* slot;         // [k] the actors
     const int32_t* target_room;  // [k] what nuts_roster_clone wrote
@@ -3763,42 +3772,25 @@ struct CloneOrderArgs {
     int32_t* clen;               // [6k] whose six texts become void,
     uint8_t* reset;              // [k] whose room does not return to public,
     uint8_t* flags;              // [k] and whose said line is not recorded
-};
 
-__device__ void roster_clone_order(const CloneOrderArgs& a)
-{
-    __shared__ uint32_t s_rooms[kMaxLookRooms / 32], s_slots[kGoMaxSlots / 32];
-    const int lane = (int)threadIdx.x;      // one wave
-    for (int i = lane; i < kMaxLookRooms / 32; i += 64) s_rooms[i] = 0;
-    for (int i = lane; i < kGoMaxSlots / 32; i += 64) s_slots[i] = 0;
-    __syncthreads();
-    for (int base = 0; base < a.k; base += 64) {
-        const int k = base + lane;
-        const bool live = k < a.k;
-        const int tsl = live ? a.target_slot[k] : -1;
-        const int own = live ? (tsl >= 0 ? tsl : a.slot[k]) : 0, trm = live ? a.target_room[k] : -1;
-        const int out = live ? a.outcome[k] : kCloneChearUsage;
-        const int count = a.k - base < 64 ? a.k - base : 64;
-        bool defer = false;
-        for (int i = 0; i < count; i++) {   // in call order; every lane follows, lane 0 sets the bits
-            const int s = __shfl(own, i), r = __shfl(trm, i), oc = __shfl(out, i);
-            const bool hit = ((s_slots[s >> 5] >> (s & 31)) & 1u) || (r >= 0 && ((s_rooms[r >> 5] >> (r & 31)) & 1u));
-            if (lane == i) defer = hit;
-            __syncthreads();
-            if (lane == 0 && !hit && (oc == kCloneCreated || oc == kCloneDestroyed)) {      // r >= 0: a clone has a room
-                s_slots[s >> 5] |= 1u << (s & 31);
-                s_rooms[r >> 5] |= 1u << (r & 31);
-            }
-            __syncthreads();
-        }
-        if (live && defer) {
-            a.outcome[k] = (int8_t)kCloneDeferred;
-            for (int kind = 0; kind < kCloneTexts; kind++) a.clen[kind * a.k + k] = -1;
-            a.reset[k] = 0;
-            a.flags[k] = 0;
-        }
+    static constexpr int kKeys = 2, kTexts = kCloneTexts, kDeferred = kCloneDeferred, kMapWords = kOrderRoomWords + kOrderSlotWords;
+    __device__ void load(int b, bool live, int (&key)[kKeys]) const
+    {
+        const int found = live ? target_slot[b] : -1;
+        key[0] = live ? (found >= 0 ? found : slot[b]) : 0, key[1] = live ? target_room[b] : -1;
     }
-}
+    static __device__ bool hit(const int (&key)[kKeys], const uint32_t* maps)
+    {
+        return bit_of(maps + kOrderRoomWords, key[0]) || (key[1] >= 0 && bit_of(maps, key[1]));
+    }
+    static __device__ void touch(const int (&key)[kKeys], int outcome, uint32_t* maps)
+    {
+        if (outcome != kCloneCreated && outcome != kCloneDestroyed) return;     // key[1] >= 0: a clone has a room
+        set_bit(maps + kOrderRoomWords, key[0]);
+        set_bit(maps, key[1]);
+    }
+    __device__ void also_void(int b) const { reset[b] = 0, flags[b] = 0; }
+};
 
 // ------------------------------------------------------------------ a user's own settings, of a resident roster
 //
@@ -3819,7 +3811,7 @@ __device__ void roster_clone_order(const CloneOrderArgs& a)
 //            inpstr; the here line with compose() / append().  Lane 0 stores the lengths, the outcome, and rm / sender /
 //            com of the here line.  No atomics: the same bytes on every run.
 //            Blocks past the events copy freshly uploaded tables into the kept allocations.
-//   order    nuts_roster_set_order, ONE WAVE, after nuts_roster_access_order.  An effective event touches its actor;
+//   order    nuts_roster_set_order, ONE WAVE: order_events by its own rule.  An effective event touches its actor;
 //            one that toggles ignall or colour also its actor's room, as the admit bitmaps and the colour bits of that
 //            room's lines read them; a set topic the topic of its room.  An event whose actor an earlier event of the call
 //            that was not itself deferred touched, or which has a here line in a room so touched, or which is a .topic in
@@ -3906,31 +3898,19 @@ __device__ const SetReply kSetReply[] = {
 };
 static_assert(sizeof(kSetReply) / sizeof(kSetReply[0]) == kSetDeferred, "kSetReply: a line for every outcome nuts_roster_set decides");
 
-struct SetArgs {
-    const int32_t* room;         // [capacity] the roster's table
-    const uint8_t* slotf;        // [capacity] and its flag bytes: ignall
+struct SetArgs : EventArgs {     // slotf: ignall
+    int32_t* rm;                 // [k] the here lines' rooms, as SpeakPlanArgs.rm
+    int32_t* sender;             // [k] and their senders
+    int32_t* com_num;            // [k]
+    const uint8_t* com;          // [k] one of the fourteen commands
+    const int32_t* rid;          // [k] the rank of the actor's room among the rooms of the call's actors (nuts_roster_set_order)
+    int blocks;                  // those that compose; the ones after them copy the uploaded tables
     const uint8_t* rooms;        // the tables this call reads, the uploads or the kept ones: the room records (nullptr: no .topic),
     const uint8_t* go;           // [capacity * 88] the go table (the two phrases),
     const uint8_t* afk;          // [capacity * 64] the AFK messages,
     const uint8_t* udesc;        // [capacity * 32] the users' descriptions,
     const uint8_t* speech;       // [capacity * 16] and the speaker state: name, vis, command_mode, afk, igntell, prompt, charmode_echo
     Kept kept[5];                // in that order
-    const uint8_t* text;         // the K inpstr, packed
-    const int32_t* text_off;     // [k]
-    const int32_t* text_len;     // [k]
-    const int32_t* slot;         // [k] the actor
-    const uint8_t* com;          // [k] one of the fourteen commands
-    const uint8_t* words;        // [k] word_count
-    const int32_t* rid;          // [k] the rank of the actor's room among the rooms of the call's actors (nuts_roster_set_order)
-    const int32_t* ctext_off;    // [3k] where each text's slot starts in ctext
-    int k, capacity, blocks;     // blocks: those that compose; the ones after them copy the uploaded tables
-    int* violations;             // composed texts past their slot (zeroed by the host's upload)
-    uint8_t* ctext;              // the composed texts
-    int32_t* clen;               // [3k] their lengths; -1: no such text
-    int8_t* outcome;             // [k]
-    int32_t* rm;                 // [k] the here lines' rooms, as SpeakPlanArgs.rm
-    int32_t* sender;             // [k] and their senders
-    int32_t* com_num;            // [k]
 };
 
 __device__ void roster_set(const SetArgs& a)
@@ -4090,6 +4070,9 @@ static_assert(sizeof("~FB~OLYou hear a melodic incantation chanted and ") - 1 + 
               "roster_set: the pieces of a compose() fit a wave");
 static_assert(64 * kReadSlice >= kArrSize && kWordLen + 7 <= 64, "roster_set: the word masks cover the longest inpstr, a lane per byte of word[1]");
 
+// nuts_roster_set_order's rule.  Keys: the actor, its room's rank, whether the event has a here line, whether it is a .topic.
+// Three bitmaps of ranks and slots, fewer than 65,536 each: the actors, the rooms where ignall or colour changed, the rooms
+// whose topic was set.
 struct SetOrderArgs {
     const int32_t* slot;         // [k] the actors
     const int32_t* rid;          // [k] their rooms' ranks
@@ -4097,41 +4080,27 @@ struct SetOrderArgs {
     int k;
     int8_t* outcome;             // [k] becomes kSetDeferred for a deferred event
     int32_t* clen;               // [3k] whose three texts become void
-};
 
-__device__ void roster_set_order(const SetOrderArgs& a)
-{
-    __shared__ uint32_t s_slots[kGoMaxSlots / 32], s_heard[kGoMaxSlots / 32], s_topic[kGoMaxSlots / 32];
-    const int lane = (int)threadIdx.x;      // one wave
-    for (int i = lane; i < kGoMaxSlots / 32; i += 64) s_slots[i] = s_heard[i] = s_topic[i] = 0;
-    __syncthreads();
-    for (int base = 0; base < a.k; base += 64) {
-        const int k = base + lane;
-        const bool live = k < a.k;
-        const int own = live ? a.slot[k] : 0, room = live ? a.rid[k] : 0, out = live ? a.outcome[k] : kSetDeferred;
-        const bool lines = live && a.clen[k] >= 0, topic = live && a.com[k] == kComTopic;
-        const int count = a.k - base < 64 ? a.k - base : 64;
-        bool defer = false;
-        for (int i = 0; i < count; i++) {   // in call order; every lane follows, lane 0 sets the bits
-            const int s = __shfl(own, i), r = __shfl(room, i), oc = __shfl(out, i);
-            const bool l = __shfl((int)lines, i) != 0, t = __shfl((int)topic, i) != 0;
-            const bool hit = ((s_slots[s >> 5] >> (s & 31)) & 1u) || (l && ((s_heard[r >> 5] >> (r & 31)) & 1u)) ||
-                             (t && ((s_topic[r >> 5] >> (r & 31)) & 1u));
-            if (lane == i) defer = hit;
-            __syncthreads();
-            if (lane == 0 && !hit && oc <= kSetIgntellOff) {            // an effective event
-                s_slots[s >> 5] |= 1u << (s & 31);
-                if (oc == kSetIgnallOn || oc == kSetIgnallOff || oc == kSetColourOn || oc == kSetColourOff) s_heard[r >> 5] |= 1u << (r & 31);
-                if (oc == kSetTopicSet) s_topic[r >> 5] |= 1u << (r & 31);
-            }
-            __syncthreads();
-        }
-        if (live && defer) {
-            a.outcome[k] = (int8_t)kSetDeferred;
-            a.clen[k] = a.clen[a.k + k] = a.clen[2 * a.k + k] = -1;
-        }
+    static constexpr int kKeys = 4, kTexts = kSetTexts, kDeferred = kSetDeferred, kMapWords = 3 * kOrderSlotWords;
+    __device__ void load(int b, bool live, int (&key)[kKeys]) const
+    {
+        key[0] = live ? slot[b] : 0, key[1] = live ? rid[b] : 0, key[2] = live && clen[b] >= 0, key[3] = live && com[b] == kComTopic;
     }
-}
+    static __device__ bool hit(const int (&key)[kKeys], const uint32_t* slots)
+    {
+        return bit_of(slots, key[0]) || (key[2] && bit_of(slots + kOrderSlotWords, key[1])) ||
+               (key[3] && bit_of(slots + 2 * kOrderSlotWords, key[1]));
+    }
+    static __device__ void touch(const int (&key)[kKeys], int outcome, uint32_t* slots)
+    {
+        if (outcome > kSetIgntellOff) return;       // only an effective event touches anything
+        set_bit(slots, key[0]);
+        if (outcome == kSetIgnallOn || outcome == kSetIgnallOff || outcome == kSetColourOn || outcome == kSetColourOff)
+            set_bit(slots + kOrderSlotWords, key[1]);
+        if (outcome == kSetTopicSet) set_bit(slots + 2 * kOrderSlotWords, key[1]);
+    }
+    __device__ void also_void(int) const {}
+};
 
 }  // namespace
 
@@ -4160,13 +4129,13 @@ extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_who_shown(WhoAr
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_rooms_count(RoomsArgs a) { roster_rooms_count(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_rooms_lines(RoomsArgs a) { roster_rooms_lines(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_go(GoArgs a) { roster_go(a); }
-extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_go_order(GoOrderArgs a) { roster_go_order(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_go_order(GoOrderArgs a) { order_events(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_access(AccessArgs a) { roster_access(a); }
-extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_access_order(AccessOrderArgs a) { roster_access_order(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_access_order(AccessOrderArgs a) { order_events(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_clone(CloneArgs a) { roster_clone(a); }
-extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_clone_order(CloneOrderArgs a) { roster_clone_order(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_clone_order(CloneOrderArgs a) { order_events(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_set(SetArgs a) { roster_set(a); }
-extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_set_order(SetOrderArgs a) { roster_set_order(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_set_order(SetOrderArgs a) { order_events(a); }
 
 // ------------------------------------------------------------------------------------------ host library
 
@@ -4468,6 +4437,39 @@ void take_table(Carver& take, int capacity, const int32_t*& room, const uint8_t*
 {
     take(room, (size_t)capacity);
     take(slot, (size_t)capacity);
+}
+
+// Behind its tables every event call's layout has the events as they are uploaded: the inpstr, their offsets and lengths,
+// the slots, the commands when the call has them (com; nullptr: nd_roster_go's events have none) and the word counts.
+void take_events(Carver& take, EventArgs& s, size_t text_bytes, const uint8_t** com)
+{
+    const size_t k = (size_t)s.k;
+    take(s.text, text_bytes);
+    take(s.text_off, k);
+    take(s.text_len, k);
+    take(s.slot, k);
+    if (com) take(*com, k);
+    take(s.words, k);
+}
+
+// And behind its own results what nuts_roster_speak_plan makes of the call's t texts over ctext_bytes, next to each other
+// for the one download: their lengths, the variants' sizes and writes, the admit bitmaps of the `lines` room lines, the
+// composed texts and the variants.  p reads the table, the texts and violations where the compose kernel has them.
+void take_event_texts(Carver& take, EventArgs& s, SpeakPlanArgs& p, size_t t, size_t lines, size_t ctext_bytes)
+{
+    take(s.clen, t);
+    take(p.vn, 2 * t);
+    take(p.vw, 2 * t);
+    take(p.vwsz, 2 * t * kMaxWrites);
+    take(p.bits, lines * (size_t)p.words);
+    take(s.ctext, ctext_bytes);
+    take(p.var, (size_t)var_at((int64_t)ctext_bytes, (int64_t)t));
+    p.room = s.room;
+    p.slot = s.slotf;
+    p.text = s.ctext;
+    p.text_off = s.ctext_off;
+    p.text_len = s.clen;
+    p.violations = s.violations;
 }
 
 size_t layout_roster(uintptr_t base, size_t text_bytes, RosterArgs& a)
@@ -4776,42 +4778,25 @@ size_t layout_go(uintptr_t base, size_t text_bytes, GoArgs& s, SpeakPlanArgs& p)
 {
     Carver take{base};
     const size_t k = (size_t)s.k, t = kGoTexts * k;
-    const size_t ctext_bytes = (size_t)kGoRow * k;
     take_table(take, s.capacity, s.room, s.slotf);
     take_kept(take, s.kept[0], kKeptSpeech, s.capacity);
     take_kept(take, s.kept[1], kKeptClones, s.capacity, s.look_rooms, s.clones);
     take_kept(take, s.kept[2], kKeptRooms, s.capacity, s.look_rooms);
     take_kept(take, s.kept[3], kKeptGo, s.capacity);
-    take(s.text, text_bytes);
-    take(s.text_off, k);
-    take(s.text_len, k);
-    take(s.slot, k);
-    take(s.words, k);
+    take_events(take, s, text_bytes, nullptr);
     take(s.ctext_off, t);
     take(s.violations, 1);
     take(s.outcome, k);
     take(s.target, k);
     take(s.old_room, k);
     take(s.returned, k);
-    take(s.clen, t);
-    take(p.vn, 2 * t);
-    take(p.vw, 2 * t);
-    take(p.vwsz, 2 * t * kMaxWrites);
-    take(p.bits, 3 * k * (size_t)p.words);
-    take(s.ctext, ctext_bytes);
-    take(p.var, (size_t)var_at((int64_t)ctext_bytes, (int64_t)t));
+    take_event_texts(take, s, p, t, 3 * k, (size_t)kGoRow * k);
     take(s.rm, 3 * k);
     take(s.sender, 3 * k);
     take(s.com_num, 3 * k);
-    p.room = s.room;
-    p.slot = s.slotf;
-    p.text = s.ctext;
-    p.text_off = s.ctext_off;
-    p.text_len = s.clen;
     p.rm = s.rm;
     p.sender = s.sender;
     p.com_num = s.com_num;
-    p.violations = s.violations;
     return take.at;
 }
 
@@ -4823,42 +4808,24 @@ size_t layout_access(uintptr_t base, size_t text_bytes, AccessArgs& s, SpeakPlan
 {
     Carver take{base};
     const size_t k = (size_t)s.k, t = kAccTexts * k;
-    const size_t ctext_bytes = (size_t)kAccRow * k;
     take_table(take, s.capacity, s.room, s.slotf);
     take_kept(take, s.kept[0], kKeptSpeech, s.capacity);
     take_kept(take, s.kept[1], kKeptClones, s.capacity, s.look_rooms, s.clones);
     take_kept(take, s.kept[2], kKeptGo, s.capacity);
     take_kept(take, s.kept[3], kKeptRooms, s.capacity, s.look_rooms);     // last: a set access alone uploads nothing else
-    take(s.text, text_bytes);
-    take(s.text_off, k);
-    take(s.text_len, k);
-    take(s.slot, k);
-    take(s.com, k);
-    take(s.words, k);
+    take_events(take, s, text_bytes, &s.com);
     take(s.ctext_off, t);
     take(s.violations, 1);
     take(s.outcome, k);
     take(s.target_room, k);
     take(s.target_slot, k);
-    take(s.clen, t);
-    take(p.vn, 2 * t);
-    take(p.vw, 2 * t);
-    take(p.vwsz, 2 * t * kMaxWrites);
-    take(p.bits, 2 * k * (size_t)p.words);
-    take(s.ctext, ctext_bytes);
-    take(p.var, (size_t)var_at((int64_t)ctext_bytes, (int64_t)t));
+    take_event_texts(take, s, p, t, 2 * k, (size_t)kAccRow * k);
     take(s.rm, 2 * k);
     take(s.sender, 2 * k);
     take(s.com_num, 2 * k);
-    p.room = s.room;
-    p.slot = s.slotf;
-    p.text = s.ctext;
-    p.text_off = s.ctext_off;
-    p.text_len = s.clen;
     p.rm = s.rm;
     p.sender = s.sender;
     p.com_num = s.com_num;
-    p.violations = s.violations;
     return take.at;
 }
 
@@ -4870,42 +4837,24 @@ size_t layout_clone(uintptr_t base, size_t text_bytes, size_t clear_bytes, Clone
 {
     Carver take{base};
     const size_t k = (size_t)s.k, t = kCloneTexts * k;
-    const size_t ctext_bytes = (size_t)clone_text_bytes((int64_t)k, (int64_t)text_bytes);
     take_table(take, s.capacity, s.room, s.slotf);
     take_kept(take, s.kept[0], kKeptSpeech, s.capacity);
     take_kept(take, s.kept[1], kKeptGo, s.capacity);
     take_kept(take, s.kept[2], kKeptRooms, s.capacity, s.look_rooms);
     take_kept(take, s.kept[3], kKeptClones, s.capacity, s.look_rooms, s.clones);   // last: a created clone alone uploads nothing else
-    take(s.text, text_bytes);
-    take(s.text_off, k);
-    take(s.text_len, k);
-    take(s.slot, k);
-    take(s.com, k);
-    take(s.words, k);
+    take_events(take, s, text_bytes, &s.com);
     take(s.ctext_off, t);
     take(*clear, clear_bytes);
     take(s.violations, 1);
     take(s.outcome, k);
     take(s.reset, k);
     take(s.found, 3 * k);
-    take(s.clen, t);
-    take(p.vn, 2 * t);
-    take(p.vw, 2 * t);
-    take(p.vwsz, 2 * t * kMaxWrites);
-    take(p.bits, kCloneLines * k * (size_t)p.words);
-    take(s.ctext, ctext_bytes);
-    take(p.var, (size_t)var_at((int64_t)ctext_bytes, (int64_t)t));
+    take_event_texts(take, s, p, t, kCloneLines * k, (size_t)clone_text_bytes((int64_t)k, (int64_t)text_bytes));
     take(s.line, 3 * kCloneLines * k);
     take(s.flags, k);
-    p.room = s.room;
-    p.slot = s.slotf;
-    p.text = s.ctext;
-    p.text_off = s.ctext_off;
-    p.text_len = s.clen;
     p.rm = s.line;
     p.sender = s.line + kCloneLines * k;
     p.com_num = s.line + 2 * kCloneLines * k;
-    p.violations = s.violations;
     return take.at;
 }
 
@@ -4918,42 +4867,24 @@ size_t layout_set(uintptr_t base, size_t text_bytes, int look_rooms, SetArgs& s,
 {
     Carver take{base};
     const size_t k = (size_t)s.k, t = kSetTexts * k;
-    const size_t ctext_bytes = (size_t)kSetRow * k;
     take_table(take, s.capacity, s.room, s.slotf);
     take_kept(take, s.kept[0], kKeptRooms, s.capacity, look_rooms);
     take_kept(take, s.kept[1], kKeptGo, s.capacity);
     take_kept(take, s.kept[2], kKeptAfk, s.capacity);
     take_kept(take, s.kept[3], kKeptUdesc, s.capacity);
     take_kept(take, s.kept[4], kKeptSpeech, s.capacity);
-    take(s.text, text_bytes);
-    take(s.text_off, k);
-    take(s.text_len, k);
-    take(s.slot, k);
-    take(s.com, k);
-    take(s.words, k);
+    take_events(take, s, text_bytes, &s.com);
     take(s.rid, k);
     take(s.ctext_off, t);
     take(s.violations, 1);
     take(s.outcome, k);
-    take(s.clen, t);
-    take(p.vn, 2 * t);
-    take(p.vw, 2 * t);
-    take(p.vwsz, 2 * t * kMaxWrites);
-    take(p.bits, k * (size_t)p.words);
-    take(s.ctext, ctext_bytes);
-    take(p.var, (size_t)var_at((int64_t)ctext_bytes, (int64_t)t));
+    take_event_texts(take, s, p, t, k, (size_t)kSetRow * k);
     take(s.rm, k);
     take(s.sender, k);
     take(s.com_num, k);
-    p.room = s.room;
-    p.slot = s.slotf;
-    p.text = s.ctext;
-    p.text_off = s.ctext_off;
-    p.text_len = s.clen;
     p.rm = s.rm;
     p.sender = s.sender;
     p.com_num = s.com_num;
-    p.violations = s.violations;
     return take.at;
 }
 
@@ -5177,6 +5108,154 @@ int launch_record(Roster& r, int k, const uint8_t* text, const int32_t* text_off
     hipLaunchKernelGGL(tell ? nuts_roster_record_tell : nuts_roster_record, dim3((unsigned)s.count), dim3(kBlock), 0,
                        g.stream, rec);
     ND_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---- the steps the four event calls share: nd_roster_go, nd_roster_access, nd_roster_clone and nd_roster_set.  Each takes
+// k events (slots, [coms,] inpstr, words), composes `texts` texts an event of which `lines` are room lines, defers in a
+// *_order kernel, plans with nuts_roster_speak_plan and downloads once.  What differs -- the settings, the kept tables and
+// their order, the results of its own -- stays in the call.
+
+// The limits every event call shares: k events of `cells` admit cells a slot and `row` bytes of fixed text slots.
+bool events_fit(int k, int cap, int cells, int row, int64_t text_bytes, int nrooms)
+{
+    return k >= 1 && (int64_t)cells * k * cap < INT32_MAX && (int64_t)k * row < INT32_MAX / 16 && text_bytes >= 0 &&
+           text_bytes < INT32_MAX / 32 && nrooms <= kMaxLookRooms;
+}
+
+// The kernels index by the events' slots and texts: nothing out of range reaches them.  coms is nullptr for events without
+// a command, else com_ok(coms[b]) says whether the call knows it.
+template <typename ComOk>
+int check_events(int k, int cap, const int32_t* slots, const int32_t* text_off, const int32_t* text_len, int64_t text_bytes,
+                 const uint8_t* coms, ComOk com_ok)
+{
+    int64_t sum = 0;
+    for (int b = 0; b < k; b++) {
+        if (slots[b] < 0 || slots[b] >= cap || text_len[b] < 0 || text_len[b] >= kArrSize || text_off[b] != sum ||
+            (coms && !com_ok((int)coms[b]))) {
+            snprintf(g_err, sizeof(g_err), "event %d: slot, %stext length or text offset out of range", b, coms ? "command, " : "");
+            return -1;
+        }
+        sum += text_len[b];
+    }
+    if (sum != text_bytes) {
+        snprintf(g_err, sizeof(g_err), "the events' texts hold %lld bytes, not %lld", (long long)sum, (long long)text_bytes);
+        return -1;
+    }
+    return 0;
+}
+
+// What both sets of arguments are told before the layouts: `lines` is the number of room lines an event has.
+void size_events(EventArgs& s, SpeakPlanArgs& p, int k, int lines, int cap)
+{
+    s.k = k;
+    p.k = lines * k;
+    s.capacity = p.capacity = cap;
+    p.tiles = (cap + kBlock - 1) / kBlock;
+    p.words = (cap + 63) / 64;
+}
+
+// The sizes of an event call, from its layout at base 0 (so, po; first_kept is where the table ends and the first kept
+// table's upload starts): one upload runs to the end of violations, one download from violations to the end of the variants.
+struct EventSizes {
+    size_t texts, ctext_bytes, var_bytes, table_bytes, tables_end, in_bytes, res_at, res_bytes;
+};
+EventSizes event_sizes(const EventArgs& so, const SpeakPlanArgs& po, const void* first_kept, int texts, size_t ctext_bytes)
+{
+    EventSizes z{};
+    z.texts = (size_t)texts * so.k;
+    z.ctext_bytes = ctext_bytes;
+    z.var_bytes = (size_t)var_at((int64_t)ctext_bytes, (int64_t)z.texts);
+    z.table_bytes = (uintptr_t)first_kept;
+    z.tables_end = (uintptr_t)so.text;
+    z.in_bytes = (uintptr_t)so.violations + sizeof(int);
+    z.res_at = (uintptr_t)so.violations;
+    z.res_bytes = (uintptr_t)po.var + z.var_bytes - z.res_at;
+    return z;
+}
+
+// The mirror holds the call's inputs, and the table when the caller gave one.
+int take_given_table(Roster& r, const EventArgs& so, const EventSizes& z, const uint8_t* table)
+{
+    if (grow_mirror(r, z.in_bytes, z.table_bytes)) return -1;
+    if (table) new_table(r, so.room, so.slotf, table);
+    return 0;
+}
+
+// The compose kernel reads the room record of its event's user (`who`: "mover", "actor").
+int check_rooms_of(const Roster& r, const EventArgs& so, const int32_t* slots, const char* who)
+{
+    const int32_t* room = reinterpret_cast<const int32_t*>(r.mirror + (uintptr_t)so.room);
+    for (int b = 0; b < so.k; b++)
+        if (room[slots[b]] < 0 || room[slots[b]] >= r.look_rooms) {
+            snprintf(g_err, sizeof(g_err), "event %d: the %s's room has no room record", b, who);
+            return -1;
+        }
+    return 0;
+}
+
+// The events into the mirror as they lie on the device, every text's slot from text_at(kind, b), and violations zeroed.
+template <typename TextAt>
+void put_events(const Roster& r, const EventArgs& so, const EventSizes& z, const uint8_t* text, int64_t text_bytes,
+                const int32_t* text_off, const int32_t* text_len, const int32_t* slots, const uint8_t* words, TextAt text_at)
+{
+    const Put put{r.mirror};
+    const size_t k = (size_t)so.k;
+    put(so.text, text, (size_t)text_bytes);
+    put(so.text_off, text_off, k * sizeof(int32_t));
+    put(so.text_len, text_len, k * sizeof(int32_t));
+    put(so.slot, slots, k * sizeof(int32_t));
+    put(so.words, words, k);
+    int32_t* coff = reinterpret_cast<int32_t*>(r.mirror + (uintptr_t)so.ctext_off);
+    for (size_t kind = 0; kind < z.texts / k; kind++)
+        for (size_t b = 0; b < k; b++) coff[kind * k + b] = (int32_t)text_at((int)kind, (int)b);
+    *reinterpret_cast<int*>(r.mirror + (uintptr_t)so.violations) = 0;
+}
+
+// The one upload: the tables' uploads lie between the table and the inputs.
+template <int N>
+int upload_events(Roster& r, const Given (&given)[N], const Kept (&at)[N], Kept (&kept)[N], const EventSizes& z, size_t* h2d,
+                  unsigned* copy_blocks)
+{
+    size_t first = 0;
+    if (pass_kept(r, given, at, kept, z.tables_end, &first, copy_blocks)) return -1;
+    return upload(r, z.table_bytes, first, z.in_bytes, h2d);
+}
+
+// The three launches: the compose kernel, its order kernel -- one wave --, and the plan of p.k room lines, a block a tile,
+// and the other texts, a block each.
+template <typename A, typename O>
+int launch_events(void (*compose)(A), unsigned blocks, const A& s, void (*order)(O), const O& o, const SpeakPlanArgs& p,
+                  const EventSizes& z)
+{
+    ND_CHECK(hipEventRecord(g.ev0, g.stream));
+    hipLaunchKernelGGL(compose, dim3(blocks), dim3(kBlock), 0, g.stream, s);
+    ND_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(order, dim3(1), dim3(64), 0, g.stream, o);
+    ND_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)((size_t)p.k * p.tiles + z.texts - p.k)), dim3(kBlock), 0, g.stream, p);
+    ND_CHECK(hipGetLastError());
+    return 0;
+}
+
+// What every event call hands back, from the pinned results, unless a text broke its bounds.
+int copy_event_results(const Res& res, const EventArgs& so, const SpeakPlanArgs& po, const EventSizes& z, int8_t* outcome,
+                       int32_t* clen, uint64_t* bits, int64_t* vn, int32_t* vw, int32_t* vwsz, uint8_t* ctext, uint8_t* var)
+{
+    const int violations = *reinterpret_cast<const int*>(res(so.violations));
+    if (violations) {
+        snprintf(g_err, sizeof(g_err), "%d text(s) exceeded the hard bounds (a text its slot; 6*len+4 bytes, %d writes transduced)",
+                 violations, kMaxWrites);
+        return -1;
+    }
+    memcpy(outcome, res(so.outcome), (size_t)so.k);
+    memcpy(clen, res(so.clen), z.texts * sizeof(int32_t));
+    memcpy(vn, res(po.vn), 2 * z.texts * sizeof(int64_t));
+    memcpy(vw, res(po.vw), 2 * z.texts * sizeof(int32_t));
+    memcpy(vwsz, res(po.vwsz), 2 * z.texts * kMaxWrites * sizeof(int32_t));
+    memcpy(bits, res(po.bits), (size_t)po.k * po.words * sizeof(uint64_t));
+    memcpy(ctext, res(so.ctext), z.ctext_bytes);
+    memcpy(var, res(po.var), z.var_bytes);
     return 0;
 }
 
@@ -6570,111 +6649,50 @@ int nd_roster_go(int handle, int k, const uint8_t* text, int64_t text_bytes, con
     static_assert(kGoMaxSlots == kMaxCapacity, "nuts_roster_go_order has a bit per slot");
     Roster* r = roster_at(handle);
     if (!r || ensure_ready()) return -1;
-    const int cap = r->capacity, nwords = (cap + 63) / 64, nrooms = r->look_rooms;
-    if (k < 1 || (int64_t)k * cap >= INT32_MAX || (int64_t)k * kGoRow >= INT32_MAX / 16 || text_bytes < 0 ||
-        text_bytes >= INT32_MAX / 32 || nrooms < 1 || nrooms > kMaxLookRooms || gatecrash_level < 0 || gatecrash_level > kGod ||
+    const int cap = r->capacity, nrooms = r->look_rooms;
+    if (!events_fit(k, cap, 1, kGoRow, text_bytes, nrooms) || nrooms < 1 || gatecrash_level < 0 || gatecrash_level > kGod ||
         min_private_users < 0) {
         snprintf(g_err, sizeof(g_err), "%d events to %d slots over %d look rooms: need 1 <= k * capacity < 2^31 - 1, a look room, a "
                  "gatecrash level in 0 .. %d and a minimum of private users >= 0", k, cap, nrooms, kGod);
         return -1;
     }
-    int64_t sum = 0;
-    for (int b = 0; b < k; b++) {       // the kernels index by these: nothing out of range reaches them
-        if (slots[b] < 0 || slots[b] >= cap || text_len[b] < 0 || text_len[b] >= kArrSize || text_off[b] != sum) {
-            snprintf(g_err, sizeof(g_err), "event %d: slot, text length or text offset out of range", b);
-            return -1;
-        }
-        sum += text_len[b];
-    }
-    if (sum != text_bytes) {
-        snprintf(g_err, sizeof(g_err), "the events' texts hold %lld bytes, not %lld", (long long)sum, (long long)text_bytes);
-        return -1;
-    }
+    if (check_events(k, cap, slots, text_off, text_len, text_bytes, nullptr, [](int) { return true; })) return -1;
     GoArgs s{};
     const Given given[] = {{kKeptSpeech, speech, &s.speech}, {kKeptClones, clones, &s.records}, {kKeptRooms, rooms, &s.rooms},
                            {kKeptGo, go, &s.go}};
     if (check_given(*r, given, "the roster's first go call must give the speaker table, the clone records, the room table and the go table"))
         return -1;
     const double t0 = now_ns();
-    hipStream_t st = g.stream;
     SpeakPlanArgs p{};
-    s.k = k;
-    p.k = 3 * k;
-    s.capacity = p.capacity = cap;
+    size_events(s, p, k, 3, cap);
     s.look_rooms = nrooms;
     s.clones = r->clones;
     s.gatecrash_level = gatecrash_level;
     s.min_private_users = min_private_users;
-    p.tiles = (cap + kBlock - 1) / kBlock;
-    p.words = nwords;
-    const size_t texts = (size_t)kGoTexts * k, ctext_bytes = (size_t)kGoRow * k;
-    const size_t var_bytes = (size_t)var_at((int64_t)ctext_bytes, (int64_t)texts);
     GoArgs so = s;                      // offsets of every array in the roster's allocation
     SpeakPlanArgs po = p;
     const size_t need = layout_go(0, (size_t)text_bytes, so, po);
-    const size_t table_bytes = (uintptr_t)so.kept[0].fresh, tables_end = (uintptr_t)so.text;
-    const size_t in_bytes = (uintptr_t)so.violations + sizeof(int);
-    const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
-    if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
-    if (table) new_table(*r, so.room, so.slotf, table);
-    const int32_t* room = reinterpret_cast<const int32_t*>(r->mirror + (uintptr_t)so.room);
-    for (int b = 0; b < k; b++)         // nuts_roster_go reads its mover's room record
-        if (room[slots[b]] < 0 || room[slots[b]] >= nrooms) {
-            snprintf(g_err, sizeof(g_err), "event %d: the mover's room has no room record", b);
-            return -1;
-        }
-    if (grow_roster(*r, need)) return -1;
+    const EventSizes z = event_sizes(so, po, so.kept[0].fresh, kGoTexts, (size_t)kGoRow * k);
+    if (take_given_table(*r, so, z, table) || check_rooms_of(*r, so, slots, "mover") || grow_roster(*r, need)) return -1;
     layout_go((uintptr_t)r->d, (size_t)text_bytes, s, p);
-    if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
+    if (grow_host(&gm.res, &gm.cap_res, z.res_bytes, "pinned results")) return -1;
 
-    uint8_t* h = r->mirror;
-    const Put put{h};
-    put(so.text, text, (size_t)text_bytes);
-    put(so.text_off, text_off, (size_t)k * sizeof(int32_t));
-    put(so.text_len, text_len, (size_t)k * sizeof(int32_t));
-    put(so.slot, slots, (size_t)k * sizeof(int32_t));
-    put(so.words, words, (size_t)k);
-    int32_t* coff = reinterpret_cast<int32_t*>(h + (uintptr_t)so.ctext_off);
-    for (int kind = 0; kind < kGoTexts; kind++)
-        for (int b = 0; b < k; b++) coff[(size_t)kind * k + b] = (int32_t)go_text_at(kind, b, k);
-    *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
-    // the tables' uploads lie between the table and the inputs
-    size_t first = 0, h2d = 0;
+    put_events(*r, so, z, text, text_bytes, text_off, text_len, slots, words, [k](int kind, int b) { return go_text_at(kind, b, k); });
+    size_t h2d = 0;
     unsigned copy_blocks = 0;
-    if (pass_kept(*r, given, so.kept, s.kept, tables_end, &first, &copy_blocks)) return -1;
-    if (upload(*r, table_bytes, first, in_bytes, &h2d)) return -1;
+    if (upload_events(*r, given, so.kept, s.kept, z, &h2d, &copy_blocks)) return -1;
 
     const GoOrderArgs order{s.slot, s.old_room, s.target, k, s.outcome, s.clen, s.returned};
-    ND_CHECK(hipEventRecord(g.ev0, st));
-    hipLaunchKernelGGL(nuts_roster_go, dim3((unsigned)k + copy_blocks), dim3(kBlock), 0, st, s);
-    ND_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(nuts_roster_go_order, dim3(1), dim3(64), 0, st, order);
-    ND_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)(3 * k * p.tiles + k)), dim3(kBlock), 0, st, p);
-    ND_CHECK(hipGetLastError());
-    if (fetch_results(r->d, res_at, res_bytes)) return -1;
+    if (launch_events(nuts_roster_go, (unsigned)k + copy_blocks, s, nuts_roster_go_order, order, p, z)) return -1;
+    if (fetch_results(r->d, z.res_at, z.res_bytes)) return -1;
     const double t1 = now_ns();
 
-    const Res res{gm.res, res_at};
-    const int violations = *reinterpret_cast<const int*>(res(so.violations));
-    if (violations) {
-        snprintf(g_err, sizeof(g_err), "%d text(s) exceeded the hard bounds (a text its slot; 6*len+4 bytes, %d writes transduced)",
-                 violations, kMaxWrites);
-        return -1;
-    }
-    memcpy(outcome, res(so.outcome), (size_t)k);
+    const Res res{gm.res, z.res_at};
+    if (copy_event_results(res, so, po, z, outcome, clen, bits, vn, vw, vwsz, ctext, var)) return -1;
     memcpy(target, res(so.target), (size_t)k * sizeof(int32_t));
     memcpy(old_room, res(so.old_room), (size_t)k * sizeof(int32_t));
     memcpy(returned, res(so.returned), (size_t)k);
-    memcpy(clen, res(so.clen), texts * sizeof(int32_t));
-    memcpy(vn, res(po.vn), 2 * texts * sizeof(int64_t));
-    memcpy(vw, res(po.vw), 2 * texts * sizeof(int32_t));
-    memcpy(vwsz, res(po.vwsz), 2 * texts * kMaxWrites * sizeof(int32_t));
-    memcpy(bits, res(po.bits), 3 * (size_t)k * nwords * sizeof(uint64_t));
-    memcpy(ctext, res(so.ctext), ctext_bytes);
-    memcpy(var, res(po.var), var_bytes);
-
-    return fill_timing(timing, t0, t1, h2d, res_bytes);
+    return fill_timing(timing, t0, t1, h2d, z.res_bytes);
 }
 
 // K .public / .private / .letmein / .invite events of roster `handle`, decided and composed as set_room_access(), letmein()
@@ -6698,113 +6716,52 @@ int nd_roster_access(int handle, int k, const uint8_t* text, int64_t text_bytes,
 {
     Roster* r = roster_at(handle);
     if (!r || ensure_ready()) return -1;
-    const int cap = r->capacity, nwords = (cap + 63) / 64, nrooms = r->look_rooms;
-    if (k < 1 || (int64_t)k * cap >= INT32_MAX || (int64_t)k * kAccRow >= INT32_MAX / 16 || text_bytes < 0 ||
-        text_bytes >= INT32_MAX / 32 || nrooms < 1 || nrooms > kMaxLookRooms || gatecrash_level < 0 || gatecrash_level > kGod ||
+    const int cap = r->capacity, nrooms = r->look_rooms;
+    if (!events_fit(k, cap, 1, kAccRow, text_bytes, nrooms) || nrooms < 1 || gatecrash_level < 0 || gatecrash_level > kGod ||
         min_private_users < 0 || ignore_mp_level < 0 || ignore_mp_level > kGod + 1) {
         snprintf(g_err, sizeof(g_err), "%d events to %d slots over %d look rooms: need 1 <= k * capacity < 2^31 - 1, a look room, a "
                  "gatecrash level in 0 .. %d, a minimum of private users >= 0 and an ignore level in 0 .. %d", k, cap, nrooms, kGod, kGod + 1);
         return -1;
     }
-    int64_t sum = 0;
-    for (int b = 0; b < k; b++) {       // the kernels index by these: nothing out of range reaches them
-        if (slots[b] < 0 || slots[b] >= cap || text_len[b] < 0 || text_len[b] >= kArrSize || text_off[b] != sum ||
-            coms[b] < kComPublic || coms[b] > kComInvite) {
-            snprintf(g_err, sizeof(g_err), "event %d: slot, command, text length or text offset out of range", b);
-            return -1;
-        }
-        sum += text_len[b];
-    }
-    if (sum != text_bytes) {
-        snprintf(g_err, sizeof(g_err), "the events' texts hold %lld bytes, not %lld", (long long)sum, (long long)text_bytes);
+    if (check_events(k, cap, slots, text_off, text_len, text_bytes, coms, [](int c) { return c >= kComPublic && c <= kComInvite; }))
         return -1;
-    }
     AccessArgs s{};
     const Given given[] = {{kKeptSpeech, speech, &s.speech}, {kKeptClones, clones, &s.records}, {kKeptGo, go, &s.go},
                            {kKeptRooms, rooms, &s.rooms}};
     if (check_given(*r, given, "the roster's first access call must give the speaker table, the clone records, the room table and the go table"))
         return -1;
     const double t0 = now_ns();
-    hipStream_t st = g.stream;
     SpeakPlanArgs p{};
-    s.k = k;
-    p.k = 2 * k;
-    s.capacity = p.capacity = cap;
+    size_events(s, p, k, 2, cap);
     s.look_rooms = nrooms;
     s.clones = r->clones;
     s.gatecrash_level = gatecrash_level;
     s.min_private_users = min_private_users;
     s.ignore_mp_level = ignore_mp_level;
-    p.tiles = (cap + kBlock - 1) / kBlock;
-    p.words = nwords;
-    const size_t texts = (size_t)kAccTexts * k, ctext_bytes = (size_t)kAccRow * k;
-    const size_t var_bytes = (size_t)var_at((int64_t)ctext_bytes, (int64_t)texts);
     AccessArgs so = s;                  // offsets of every array in the roster's allocation
     SpeakPlanArgs po = p;
     const size_t need = layout_access(0, (size_t)text_bytes, so, po);
-    const size_t table_bytes = (uintptr_t)so.kept[0].fresh, tables_end = (uintptr_t)so.text;
-    const size_t in_bytes = (uintptr_t)so.violations + sizeof(int);
-    const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
-    if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
-    if (table) new_table(*r, so.room, so.slotf, table);
-    const int32_t* room = reinterpret_cast<const int32_t*>(r->mirror + (uintptr_t)so.room);
-    for (int b = 0; b < k; b++)         // nuts_roster_access reads its actor's room record
-        if (room[slots[b]] < 0 || room[slots[b]] >= nrooms) {
-            snprintf(g_err, sizeof(g_err), "event %d: the actor's room has no room record", b);
-            return -1;
-        }
-    if (grow_roster(*r, need)) return -1;
+    const EventSizes z = event_sizes(so, po, so.kept[0].fresh, kAccTexts, (size_t)kAccRow * k);
+    if (take_given_table(*r, so, z, table) || check_rooms_of(*r, so, slots, "actor") || grow_roster(*r, need)) return -1;
     layout_access((uintptr_t)r->d, (size_t)text_bytes, s, p);
-    if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
+    if (grow_host(&gm.res, &gm.cap_res, z.res_bytes, "pinned results")) return -1;
 
-    uint8_t* h = r->mirror;
-    const Put put{h};
-    put(so.text, text, (size_t)text_bytes);
-    put(so.text_off, text_off, (size_t)k * sizeof(int32_t));
-    put(so.text_len, text_len, (size_t)k * sizeof(int32_t));
-    put(so.slot, slots, (size_t)k * sizeof(int32_t));
-    put(so.com, coms, (size_t)k);
-    put(so.words, words, (size_t)k);
-    int32_t* coff = reinterpret_cast<int32_t*>(h + (uintptr_t)so.ctext_off);
-    for (int kind = 0; kind < kAccTexts; kind++)
-        for (int b = 0; b < k; b++) coff[(size_t)kind * k + b] = (int32_t)acc_text_at(kind, b, k);
-    *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
-    // the tables' uploads lie between the table and the inputs
-    size_t first = 0, h2d = 0;
+    put_events(*r, so, z, text, text_bytes, text_off, text_len, slots, words, [k](int kind, int b) { return acc_text_at(kind, b, k); });
+    Put{r->mirror}(so.com, coms, (size_t)k);
+    size_t h2d = 0;
     unsigned copy_blocks = 0;
-    if (pass_kept(*r, given, so.kept, s.kept, tables_end, &first, &copy_blocks)) return -1;
-    if (upload(*r, table_bytes, first, in_bytes, &h2d)) return -1;
+    if (upload_events(*r, given, so.kept, s.kept, z, &h2d, &copy_blocks)) return -1;
 
     const AccessOrderArgs order{s.room, s.slot, s.target_room, s.target_slot, k, s.outcome, s.clen};
-    ND_CHECK(hipEventRecord(g.ev0, st));
-    hipLaunchKernelGGL(nuts_roster_access, dim3((unsigned)k + copy_blocks), dim3(kBlock), 0, st, s);
-    ND_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(nuts_roster_access_order, dim3(1), dim3(64), 0, st, order);
-    ND_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)(2 * k * p.tiles + 2 * k)), dim3(kBlock), 0, st, p);
-    ND_CHECK(hipGetLastError());
-    if (fetch_results(r->d, res_at, res_bytes)) return -1;
+    if (launch_events(nuts_roster_access, (unsigned)k + copy_blocks, s, nuts_roster_access_order, order, p, z)) return -1;
+    if (fetch_results(r->d, z.res_at, z.res_bytes)) return -1;
     const double t1 = now_ns();
 
-    const Res res{gm.res, res_at};
-    const int violations = *reinterpret_cast<const int*>(res(so.violations));
-    if (violations) {
-        snprintf(g_err, sizeof(g_err), "%d text(s) exceeded the hard bounds (a text its slot; 6*len+4 bytes, %d writes transduced)",
-                 violations, kMaxWrites);
-        return -1;
-    }
-    memcpy(outcome, res(so.outcome), (size_t)k);
+    const Res res{gm.res, z.res_at};
+    if (copy_event_results(res, so, po, z, outcome, clen, bits, vn, vw, vwsz, ctext, var)) return -1;
     memcpy(target_room, res(so.target_room), (size_t)k * sizeof(int32_t));
     memcpy(target_slot, res(so.target_slot), (size_t)k * sizeof(int32_t));
-    memcpy(clen, res(so.clen), texts * sizeof(int32_t));
-    memcpy(vn, res(po.vn), 2 * texts * sizeof(int64_t));
-    memcpy(vw, res(po.vw), 2 * texts * sizeof(int32_t));
-    memcpy(vwsz, res(po.vwsz), 2 * texts * kMaxWrites * sizeof(int32_t));
-    memcpy(bits, res(po.bits), 2 * (size_t)k * nwords * sizeof(uint64_t));
-    memcpy(ctext, res(so.ctext), ctext_bytes);
-    memcpy(var, res(po.var), var_bytes);
-
-    return fill_timing(timing, t0, t1, h2d, res_bytes);
+    return fill_timing(timing, t0, t1, h2d, z.res_bytes);
 }
 
 // K .clone / .destroy / .csay / .chear events of roster `handle`, decided and composed as create_clone(), destroy_clone(),
@@ -6835,28 +6792,17 @@ int nd_roster_clone(int handle, int k, const uint8_t* text, int64_t text_bytes, 
 {
     Roster* r = roster_at(handle);
     if (!r || ensure_ready()) return -1;
-    const int cap = r->capacity, nwords = (cap + 63) / 64, nrooms = r->look_rooms;
-    if (k < 1 || (int64_t)kCloneLines * k * cap >= INT32_MAX || (int64_t)k * kCloneRow >= INT32_MAX / 16 || text_bytes < 0 ||
-        text_bytes >= INT32_MAX / 32 || nrooms < 1 || nrooms > kMaxLookRooms || r->clones < 1 || cap > kGoMaxSlots ||
+    const int cap = r->capacity, nrooms = r->look_rooms;
+    if (!events_fit(k, cap, kCloneLines, kCloneRow, text_bytes, nrooms) || nrooms < 1 || r->clones < 1 || cap > kGoMaxSlots ||
         gatecrash_level < 0 || gatecrash_level > kGod || min_private_users < 0 || max_clones < 0) {
         snprintf(g_err, sizeof(g_err), "%d events to %d slots over %d look rooms and %d clone records: need 1 <= 4 k * capacity < 2^31 - 1, "
                  "a look room, a clone record, a gatecrash level in 0 .. %d, a minimum of private users >= 0 and a maximum of clones >= 0",
                  k, cap, nrooms, r->clones, kGod);
         return -1;
     }
-    int64_t sum = 0;
-    for (int b = 0; b < k; b++) {       // the kernels index by these: nothing out of range reaches them
-        const bool com_ok = coms[b] == kComClone || coms[b] == kComDestroy || coms[b] == kComCsay || coms[b] == kComChear;
-        if (slots[b] < 0 || slots[b] >= cap || text_len[b] < 0 || text_len[b] >= kArrSize || text_off[b] != sum || !com_ok) {
-            snprintf(g_err, sizeof(g_err), "event %d: slot, command, text length or text offset out of range", b);
-            return -1;
-        }
-        sum += text_len[b];
-    }
-    if (sum != text_bytes) {
-        snprintf(g_err, sizeof(g_err), "the events' texts hold %lld bytes, not %lld", (long long)sum, (long long)text_bytes);
+    if (check_events(k, cap, slots, text_off, text_len, text_bytes, coms,
+                     [](int c) { return c == kComClone || c == kComDestroy || c == kComCsay || c == kComChear; }))
         return -1;
-    }
     CloneArgs s{};
     const Given given[] = {{kKeptSpeech, speech, &s.speech}, {kKeptGo, go, &s.go}, {kKeptRooms, rooms, &s.rooms},
                            {kKeptClones, clones, &s.records}};
@@ -6867,98 +6813,50 @@ int nd_roster_clone(int handle, int k, const uint8_t* text, int64_t text_bytes, 
         return -1;
     }
     const double t0 = now_ns();
-    hipStream_t st = g.stream;
     SpeakPlanArgs p{};
-    s.k = k;
-    p.k = kCloneLines * k;
-    s.capacity = p.capacity = cap;
+    size_events(s, p, k, kCloneLines, cap);
     s.look_rooms = nrooms;
     s.clones = r->clones;
     s.gatecrash_level = gatecrash_level;
     s.min_private_users = min_private_users;
     s.max_clones = max_clones;
     s.record = record != 0;
-    p.tiles = (cap + kBlock - 1) / kBlock;
-    p.words = nwords;
-    const size_t texts = (size_t)kCloneTexts * k, ctext_bytes = (size_t)clone_text_bytes(k, text_bytes);
-    const size_t var_bytes = (size_t)var_at((int64_t)ctext_bytes, (int64_t)texts);
     const size_t clear_bytes = record && clear ? (size_t)r->review_rooms : 0;
     CloneArgs so = s;                   // offsets of every array in the roster's allocation
     SpeakPlanArgs po = p;
     const uint8_t *o_clear = nullptr, *d_clear = nullptr;
     const size_t need = layout_clone(0, (size_t)text_bytes, clear_bytes, so, po, &o_clear);
-    const size_t table_bytes = (uintptr_t)so.kept[0].fresh, tables_end = (uintptr_t)so.text;
-    const size_t in_bytes = (uintptr_t)so.violations + sizeof(int);
-    const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
-    if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
-    if (table) new_table(*r, so.room, so.slotf, table);
-    const int32_t* room = reinterpret_cast<const int32_t*>(r->mirror + (uintptr_t)so.room);
-    for (int b = 0; b < k; b++)         // nuts_roster_clone reads its actor's room record
-        if (room[slots[b]] < 0 || room[slots[b]] >= nrooms) {
-            snprintf(g_err, sizeof(g_err), "event %d: the actor's room has no room record", b);
-            return -1;
-        }
-    if (grow_roster(*r, need)) return -1;
+    const EventSizes z = event_sizes(so, po, so.kept[0].fresh, kCloneTexts, (size_t)clone_text_bytes(k, text_bytes));
+    if (take_given_table(*r, so, z, table) || check_rooms_of(*r, so, slots, "actor") || grow_roster(*r, need)) return -1;
     layout_clone((uintptr_t)r->d, (size_t)text_bytes, clear_bytes, s, p, &d_clear);
-    if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
+    if (grow_host(&gm.res, &gm.cap_res, z.res_bytes, "pinned results")) return -1;
 
-    uint8_t* h = r->mirror;
-    const Put put{h};
-    put(so.text, text, (size_t)text_bytes);
-    put(so.text_off, text_off, (size_t)k * sizeof(int32_t));
-    put(so.text_len, text_len, (size_t)k * sizeof(int32_t));
-    put(so.slot, slots, (size_t)k * sizeof(int32_t));
+    put_events(*r, so, z, text, text_bytes, text_off, text_len, slots, words,
+               [=](int kind, int b) { return clone_text_at(kind, b, k, text_off[b], text_bytes); });
+    const Put put{r->mirror};
     put(so.com, coms, (size_t)k);
-    put(so.words, words, (size_t)k);
-    int32_t* coff = reinterpret_cast<int32_t*>(h + (uintptr_t)so.ctext_off);
-    for (int kind = 0; kind < kCloneTexts; kind++)
-        for (int b = 0; b < k; b++) coff[(size_t)kind * k + b] = (int32_t)clone_text_at(kind, b, k, text_off[b], text_bytes);
     put(o_clear, clear, clear_bytes);
-    *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
-    // the tables' uploads lie between the table and the inputs
-    size_t first = 0, h2d = 0;
+    size_t h2d = 0;
     unsigned copy_blocks = 0;
-    if (pass_kept(*r, given, so.kept, s.kept, tables_end, &first, &copy_blocks)) return -1;
-    if (upload(*r, table_bytes, first, in_bytes, &h2d)) return -1;
+    if (upload_events(*r, given, so.kept, s.kept, z, &h2d, &copy_blocks)) return -1;
 
     const CloneOrderArgs order{s.slot, s.found, s.found + k, k, s.outcome, s.clen, s.reset, s.flags};
-    ND_CHECK(hipEventRecord(g.ev0, st));
-    hipLaunchKernelGGL(nuts_roster_clone, dim3((unsigned)k + copy_blocks), dim3(kBlock), 0, st, s);
-    ND_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(nuts_roster_clone_order, dim3(1), dim3(64), 0, st, order);
-    ND_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)(kCloneLines * k * p.tiles + (kCloneTexts - kCloneLines) * k)), dim3(kBlock),
-                       0, st, p);
-    ND_CHECK(hipGetLastError());
+    if (launch_events(nuts_roster_clone, (unsigned)k + copy_blocks, s, nuts_roster_clone_order, order, p, z)) return -1;
     // on the said lines nuts_roster_clone wrote, less those nuts_roster_clone_order deferred
     if (record && launch_record(*r, k, s.ctext, s.ctext_off + (size_t)kCloneSaidText * k, s.clen + (size_t)kCloneSaidText * k,
                                 s.line + (size_t)kCloneSaidText * k, s.flags, clear_bytes ? d_clear : nullptr))
         return -1;
-    if (fetch_results(r->d, res_at, res_bytes)) return -1;
+    if (fetch_results(r->d, z.res_at, z.res_bytes)) return -1;
     const double t1 = now_ns();
 
-    const Res res{gm.res, res_at};
-    const int violations = *reinterpret_cast<const int*>(res(so.violations));
-    if (violations) {
-        snprintf(g_err, sizeof(g_err), "%d text(s) exceeded the hard bounds (a text its slot; 6*len+4 bytes, %d writes transduced)",
-                 violations, kMaxWrites);
-        return -1;
-    }
-    memcpy(outcome, res(so.outcome), (size_t)k);
+    const Res res{gm.res, z.res_at};
+    if (copy_event_results(res, so, po, z, outcome, clen, bits, vn, vw, vwsz, ctext, var)) return -1;
     memcpy(reset, res(so.reset), (size_t)k);
     const int32_t* found = reinterpret_cast<const int32_t*>(res(so.found));
     memcpy(target_room, found, (size_t)k * sizeof(int32_t));
     memcpy(target_slot, found + k, (size_t)k * sizeof(int32_t));
     memcpy(rec, found + 2 * (size_t)k, (size_t)k * sizeof(int32_t));
-    memcpy(clen, res(so.clen), texts * sizeof(int32_t));
-    memcpy(vn, res(po.vn), 2 * texts * sizeof(int64_t));
-    memcpy(vw, res(po.vw), 2 * texts * sizeof(int32_t));
-    memcpy(vwsz, res(po.vwsz), 2 * texts * kMaxWrites * sizeof(int32_t));
-    memcpy(bits, res(po.bits), (size_t)kCloneLines * k * nwords * sizeof(uint64_t));
-    memcpy(ctext, res(so.ctext), ctext_bytes);
-    memcpy(var, res(po.var), var_bytes);
-
-    return fill_timing(timing, t0, t1, h2d, res_bytes);
+    return fill_timing(timing, t0, t1, h2d, z.res_bytes);
 }
 
 // K events of roster `handle` by which a user sets its own state -- .mode, .ignall, .prompt, .desc, .inphr, .outphr, .topic,
@@ -6981,29 +6879,17 @@ int nd_roster_set(int handle, int k, const uint8_t* text, int64_t text_bytes, co
 {
     Roster* r = roster_at(handle);
     if (!r || ensure_ready()) return -1;
-    const int cap = r->capacity, nwords = (cap + 63) / 64, nrooms = r->look_rooms;
-    if (k < 1 || (int64_t)k * cap >= INT32_MAX || (int64_t)k * kSetRow >= INT32_MAX / 16 || text_bytes < 0 ||
-        text_bytes >= INT32_MAX / 32 || nrooms < 0 || nrooms > kMaxLookRooms) {
+    const int cap = r->capacity, nrooms = r->look_rooms;
+    if (!events_fit(k, cap, 1, kSetRow, text_bytes, nrooms) || nrooms < 0) {
         snprintf(g_err, sizeof(g_err), "%d events to %d slots: need 1 <= k * capacity < 2^31 - 1", k, cap);
         return -1;
     }
-    int64_t sum = 0;
-    bool topics = false;
-    for (int b = 0; b < k; b++) {       // the kernels index by these: nothing out of range reaches them
-        const int c = coms[b];
-        const bool known = c == kComMode || (c >= kComIgnall && c <= kComOutphr) || c == kComTopic || c == kComVis || c == kComInvis ||
-                           c == kComCharecho || c == kComAfk || (c >= kComColour && c <= kComIgntell);
-        if (slots[b] < 0 || slots[b] >= cap || text_len[b] < 0 || text_len[b] >= kArrSize || text_off[b] != sum || !known) {
-            snprintf(g_err, sizeof(g_err), "event %d: slot, command, text length or text offset out of range", b);
-            return -1;
-        }
-        topics |= c == kComTopic;
-        sum += text_len[b];
-    }
-    if (sum != text_bytes) {
-        snprintf(g_err, sizeof(g_err), "the events' texts hold %lld bytes, not %lld", (long long)sum, (long long)text_bytes);
+    if (check_events(k, cap, slots, text_off, text_len, text_bytes, coms, [](int c) {
+            return c == kComMode || (c >= kComIgnall && c <= kComOutphr) || c == kComTopic || c == kComVis || c == kComInvis ||
+                   c == kComCharecho || c == kComAfk || (c >= kComColour && c <= kComIgntell);
+        }))
         return -1;
-    }
+    const bool topics = std::find(coms, coms + k, (uint8_t)kComTopic) != coms + k;
     SetArgs s{};
     const Given given[] = {{kKeptRooms, topics ? rooms : nullptr, &s.rooms, !topics}, {kKeptGo, go, &s.go}, {kKeptAfk, afk, &s.afk},
                            {kKeptUdesc, udesc, &s.udesc}, {kKeptSpeech, speech, &s.speech}};
@@ -7011,23 +6897,14 @@ int nd_roster_set(int handle, int k, const uint8_t* text, int64_t text_bytes, co
                                "table and, for a .topic, the room table"))
         return -1;
     const double t0 = now_ns();
-    hipStream_t st = g.stream;
     SpeakPlanArgs p{};
-    s.k = p.k = k;
-    s.capacity = p.capacity = cap;
+    size_events(s, p, k, 1, cap);
     s.blocks = (k + kBlock / 64 - 1) / (kBlock / 64);
-    p.tiles = (cap + kBlock - 1) / kBlock;
-    p.words = nwords;
-    const size_t texts = (size_t)kSetTexts * k, ctext_bytes = (size_t)kSetRow * k;
-    const size_t var_bytes = (size_t)var_at((int64_t)ctext_bytes, (int64_t)texts);
     SetArgs so = s;                     // offsets of every array in the roster's allocation
     SpeakPlanArgs po = p;
     const size_t need = layout_set(0, (size_t)text_bytes, nrooms, so, po);
-    const size_t table_bytes = (uintptr_t)so.kept[0].fresh, tables_end = (uintptr_t)so.text;
-    const size_t in_bytes = (uintptr_t)so.violations + sizeof(int);
-    const size_t res_at = (uintptr_t)so.violations, res_bytes = (uintptr_t)po.var + var_bytes - res_at;
-    if (grow_mirror(*r, in_bytes, table_bytes)) return -1;
-    if (table) new_table(*r, so.room, so.slotf, table);
+    const EventSizes z = event_sizes(so, po, so.kept[0].fresh, kSetTexts, (size_t)kSetRow * k);
+    if (take_given_table(*r, so, z, table)) return -1;
     uint8_t* h = r->mirror;
     const int32_t* room = reinterpret_cast<const int32_t*>(h + (uintptr_t)so.room);
     int32_t* rid = reinterpret_cast<int32_t*>(h + (uintptr_t)so.rid);
@@ -7040,15 +6917,10 @@ int nd_roster_set(int handle, int k, const uint8_t* text, int64_t text_bytes, co
     }
     if (grow_roster(*r, need)) return -1;
     layout_set((uintptr_t)r->d, (size_t)text_bytes, nrooms, s, p);
-    if (grow_host(&gm.res, &gm.cap_res, res_bytes, "pinned results")) return -1;
+    if (grow_host(&gm.res, &gm.cap_res, z.res_bytes, "pinned results")) return -1;
 
-    const Put put{h};
-    put(so.text, text, (size_t)text_bytes);
-    put(so.text_off, text_off, (size_t)k * sizeof(int32_t));
-    put(so.text_len, text_len, (size_t)k * sizeof(int32_t));
-    put(so.slot, slots, (size_t)k * sizeof(int32_t));
-    put(so.com, coms, (size_t)k);
-    put(so.words, words, (size_t)k);
+    put_events(*r, so, z, text, text_bytes, text_off, text_len, slots, words, [k](int kind, int b) { return set_text_at(kind, b, k); });
+    Put{h}(so.com, coms, (size_t)k);
     {                                   // the actors' rooms become their ranks among the call's rooms: fewer than 65,536, as the slots are
         int32_t* sorted = reinterpret_cast<int32_t*>(gm.res);           // scratch until the results land there: k * 4 <= res_bytes
         std::copy(rid, rid + k, sorted);
@@ -7056,44 +6928,17 @@ int nd_roster_set(int handle, int k, const uint8_t* text, int64_t text_bytes, co
         const int32_t* last = std::unique(sorted, sorted + k);
         for (int b = 0; b < k; b++) rid[b] = (int32_t)(std::lower_bound((const int32_t*)sorted, last, rid[b]) - sorted);
     }
-    int32_t* coff = reinterpret_cast<int32_t*>(h + (uintptr_t)so.ctext_off);
-    for (int kind = 0; kind < kSetTexts; kind++)
-        for (int b = 0; b < k; b++) coff[(size_t)kind * k + b] = (int32_t)set_text_at(kind, b, k);
-    *reinterpret_cast<int*>(h + (uintptr_t)so.violations) = 0;
-    // the tables' uploads lie between the table and the inputs
-    size_t first = 0, h2d = 0;
+    size_t h2d = 0;
     unsigned copy_blocks = 0;
-    if (pass_kept(*r, given, so.kept, s.kept, tables_end, &first, &copy_blocks)) return -1;
-    if (upload(*r, table_bytes, first, in_bytes, &h2d)) return -1;
+    if (upload_events(*r, given, so.kept, s.kept, z, &h2d, &copy_blocks)) return -1;
 
     const SetOrderArgs order{s.slot, s.rid, s.com, k, s.outcome, s.clen};
-    ND_CHECK(hipEventRecord(g.ev0, st));
-    hipLaunchKernelGGL(nuts_roster_set, dim3((unsigned)s.blocks + copy_blocks), dim3(kBlock), 0, st, s);
-    ND_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(nuts_roster_set_order, dim3(1), dim3(64), 0, st, order);
-    ND_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(nuts_roster_speak_plan, dim3((unsigned)(k * p.tiles + 2 * k)), dim3(kBlock), 0, st, p);
-    ND_CHECK(hipGetLastError());
-    if (fetch_results(r->d, res_at, res_bytes)) return -1;
+    if (launch_events(nuts_roster_set, (unsigned)s.blocks + copy_blocks, s, nuts_roster_set_order, order, p, z)) return -1;
+    if (fetch_results(r->d, z.res_at, z.res_bytes)) return -1;
     const double t1 = now_ns();
 
-    const Res res{gm.res, res_at};
-    const int violations = *reinterpret_cast<const int*>(res(so.violations));
-    if (violations) {
-        snprintf(g_err, sizeof(g_err), "%d text(s) exceeded the hard bounds (a text its slot; 6*len+4 bytes, %d writes transduced)",
-                 violations, kMaxWrites);
-        return -1;
-    }
-    memcpy(outcome, res(so.outcome), (size_t)k);
-    memcpy(clen, res(so.clen), texts * sizeof(int32_t));
-    memcpy(vn, res(po.vn), 2 * texts * sizeof(int64_t));
-    memcpy(vw, res(po.vw), 2 * texts * sizeof(int32_t));
-    memcpy(vwsz, res(po.vwsz), 2 * texts * kMaxWrites * sizeof(int32_t));
-    memcpy(bits, res(po.bits), (size_t)k * nwords * sizeof(uint64_t));
-    memcpy(ctext, res(so.ctext), ctext_bytes);
-    memcpy(var, res(po.var), var_bytes);
-
-    return fill_timing(timing, t0, t1, h2d, res_bytes);
+    if (copy_event_results(Res{gm.res, z.res_at}, so, po, z, outcome, clen, bits, vn, vw, vwsz, ctext, var)) return -1;
+    return fill_timing(timing, t0, t1, h2d, z.res_bytes);
 }
 
 }  // extern "C"

@@ -197,6 +197,22 @@ def test_a_roster_without_rooms_or_records_rings_a_closed_one_the_tail_and_the_c
         r.clone_many([(0, CLO, b"", 1)], **KW)
 
 
+def test_a_call_of_too_many_cells_and_one_of_too_much_text(no_library):
+    """Four admit cells an event, so a quarter of the events the other event calls take; and the said line makes the
+    variant bound depend on the text, so the text's own limit is checked first."""
+    big = device.Roster(G.MAX_CAPACITY, look_rooms=1, clones=1)
+    big.update(0, room=0, name=b"Alice")
+    with pytest.raises(ValueError, match="8192 events to 65536 slots: 4 x K x capacity must be below"):
+        big.clone_many([(0, SAY, b"den hi", 3)] * 8192, **KW)
+    with pytest.raises(ValueError, match="event 8190: word_count"):      # 8191 events pass that check: the next one fails
+        big.clone_many([(0, SAY, b"den hi", 3)] * 8190 + [(0, SAY, b"den hi", 11)], **KW)
+    r, _, _ = seated()
+    state, before = flags(r), mirrors(r)
+    with pytest.raises(ValueError, match="call text larger than 64 MiB: split it"):
+        r.clone_many([(0, SAY, b"den " + b"x" * 995, 3)] * (2**26 // 999 + 1), **KW)
+    assert flags(r) == state and all(np.array_equal(a, b) for a, b in zip(mirrors(r), before))
+
+
 # ------------------------------------------------------------------ host tier: the model against the recordings
 @pytest.fixture(scope="module")
 def model_replays():
