@@ -13,9 +13,6 @@ recorded sessions through a backend's ``access`` method and compares every clien
 """
 from __future__ import annotations
 
-import argparse
-import hashlib
-import json
 import random
 import sys
 import time
@@ -30,13 +27,14 @@ sys.path.insert(0, str(REPO / "tests"))
 import session_replay as sr  # noqa: E402
 from device_go_child import (ARCH, EVENTS, WIZ, GoDeviceBackend, GoModelBackend, GoReplayer, admitted, cases,  # noqa: E402
                              first_word, fuzz_events, fuzz_rooms, fuzz_users, get_room, go_call, go_differences, go_user, look_of,
-                             mirror_differences, movers_of, plan_of, seat, seat_clones, set_rooms)
+                             mirror_differences, movers_of, seat, seat_clones, set_rooms)
 from device_rooms_child import list_room  # noqa: E402
 from device_tell_child import get_user  # noqa: E402
+from event_checks import child_main, event_differences, lines_of, load, plan_of  # noqa: E402
+from event_checks import digest as digest_of  # noqa: E402
 from nuts333_amd import device, nuts_path  # noqa: E402
 
 G = device
-GOLDEN = REPO / "tests" / "golden"
 SESSIONS = ("reference_only/access.json", "reference_only/go.json", "reference_only/rmst.json")
 COMS = {"public": G.COM_PUBLIC, "private": G.COM_PRIVATE, "letmein": G.COM_LETMEIN, "invite": G.COM_INVITE}
 EFFECTIVE = (G.ACCESS_SET_PRIVATE, G.ACCESS_SET_PUBLIC, G.ACCESS_INVITED)
@@ -172,31 +170,9 @@ def texts_of(got: G.Access):
 
 def access_differences(got: G.Access, call: dict) -> list:
     """Everything an Access says against the model's call."""
-    bad = []
-    kinds = texts_of(got)
-    for k, res in enumerate(call["events"]):
-        where = {"event": k, "slot": res["slot"], "com": res["com"], "model": res["outcome"]}
-        if res["outcome"] == G.ACCESS_DEFERRED:                         # its targets are the snapshot's: not compared
-            if int(got.outcome[k]) != G.ACCESS_DEFERRED or (got.text_sizes[:, k] != -1).any() or any(
-                    p.admitted(k).any() or p.variant_sizes[k].any() or p.write_counts[k].any() for _, p, _ in kinds):
-                bad.append({**where, "what": "a deferred event", "device": int(got.outcome[k])})
-            continue
-        have = (int(got.outcome[k]), int(got.target_room[k]), int(got.target_slot[k]))
-        if have != (res["outcome"], res["target_room"], res["target_slot"]):
-            bad.append({**where, "what": "outcome", "device": list(have), "want": [res["outcome"], res["target_room"], res["target_slot"]]})
-            continue
-        for row, (kind, plan, text) in enumerate(kinds):
-            want = res[kind]
-            if text(k) != (want or b"") or (got.text_sizes[row, k] >= 0) != (want is not None):
-                bad.append({**where, "what": kind + " text", "device": text(k).decode("latin-1"), "want": repr(want)})
-                continue
-            p = plan_of(plan, k)
-            want_chunks = {c: nuts_path.chunks(want, c) if want is not None else [] for c in (0, 1)}
-            if p["admitted"] != res["plans"][kind] or p["chunks"] != want_chunks:
-                bad.append({**where, "what": kind + " plan", "device": p["admitted"][:20], "want": res["plans"][kind][:20]})
-    if got.effective().tolist() != [k for k, r in enumerate(call["events"]) if r["outcome"] in EFFECTIVE]:
-        bad.append({"what": "effective", "device": got.effective().tolist()})
-    return bad
+    return event_differences(
+        got, call, texts_of(got), G.ACCESS_DEFERRED,
+        lambda k, res: ((int(got.target_room[k]), int(got.target_slot[k])), (res["target_room"], res["target_slot"])), effective=EFFECTIVE)
 
 
 # ------------------------------------------------------------------ seeded streams
@@ -378,12 +354,7 @@ def get_room_part() -> dict:
 
 # ------------------------------------------------------------------ repeatability, regrowth, limits
 def digest(got: G.Access) -> str:
-    h = hashlib.sha256()
-    h.update(got.outcome.tobytes() + got.target_room.tobytes() + got.target_slot.tobytes())
-    for _, plan, text in texts_of(got):
-        for k in range(len(got.outcome)):
-            h.update(text(k) + plan.admitted_bits[k].tobytes() + b"".join(b"|".join(plan.chunks(k, c)) for c in (0, 1)))
-    return h.hexdigest()
+    return digest_of(got, [got.target_room, got.target_slot], texts_of(got))
 
 
 def determinism_part(seed: int) -> dict:
@@ -558,11 +529,7 @@ class AccessReplayer(GoReplayer):
 
 
 def access_lines(doc: dict) -> int:
-    return sum(1 for s in doc["steps"] if s["op"] == "line" and (s["send"].split() or [""])[0] in ("." + c for c in COMS))
-
-
-def load(name: str) -> dict:
-    return json.loads((GOLDEN / name).read_text())
+    return lines_of(doc, COMS)
 
 
 def replay_sessions(backend_class=AccessModelBackend, layouts=(sr.COMPACT,)) -> dict:
@@ -581,30 +548,20 @@ def replay_sessions(backend_class=AccessModelBackend, layouts=(sr.COMPACT,)) -> 
     return out
 
 
+def parts(seed: int) -> tuple:
+    return (("golden", lambda: replay_sessions(AccessDeviceBackend, (sr.COMPACT, sr.SPREAD))), ("fuzz", lambda: fuzz_part(seed)),
+            ("head_count", head_count_part), ("get_user", get_user_part), ("get_room", get_room_part),
+            ("determinism", lambda: determinism_part(seed + 1)), ("regrown", lambda: regrown_part(seed + 2)), ("limits", limits_part))
+
+
+def profile(res: dict) -> dict:
+    return {"seconds": res["seconds"], "fuzz": {k: res["fuzz"][k] for k in ("calls", "events", "outcomes")},
+            "golden": {k: {"access": v["access"], "comparisons": v["comparisons"]} for k, v in res["golden"].items()},
+            "limits_seconds": res["limits"]["seconds"]}
+
+
 def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--seed", type=int, default=20262)
-    ap.add_argument("--profile", help="write the parts' seconds here, as JSON")
-    args = ap.parse_args()
-    if G.device_count() < 1:
-        print("no GPU visible", file=sys.stderr)
-        return 3
-    parts = (("golden", lambda: replay_sessions(AccessDeviceBackend, (sr.COMPACT, sr.SPREAD))), ("fuzz", lambda: fuzz_part(args.seed)),
-             ("head_count", head_count_part), ("get_user", get_user_part), ("get_room", get_room_part),
-             ("determinism", lambda: determinism_part(args.seed + 1)), ("regrown", lambda: regrown_part(args.seed + 2)),
-             ("limits", limits_part))
-    res, seconds = {}, {}
-    for name, part in parts:
-        t0 = time.perf_counter()
-        res[name] = part()
-        seconds[name] = round(time.perf_counter() - t0, 3)
-    res["seconds"] = seconds
-    print("DEVICE_ACCESS " + json.dumps(res))
-    if args.profile:
-        Path(args.profile).write_text(json.dumps({"seconds": seconds, "fuzz": {k: res["fuzz"][k] for k in ("calls", "events", "outcomes")},
-                                                  "golden": {k: {"access": v["access"], "comparisons": v["comparisons"]} for k, v in res["golden"].items()},
-                                                  "limits_seconds": res["limits"]["seconds"]}, indent=1) + "\n")
-    return 0
+    return child_main("DEVICE_ACCESS", parts, profile, seed=20262)
 
 
 if __name__ == "__main__":

@@ -15,12 +15,8 @@ included.
 """
 from __future__ import annotations
 
-import argparse
-import hashlib
-import json
 import random
 import sys
-import time
 from pathlib import Path
 
 import numpy as np
@@ -32,13 +28,14 @@ sys.path.insert(0, str(REPO / "tests"))
 import session_replay as sr  # noqa: E402
 from device_access_child import AccessDeviceBackend, AccessModelBackend, AccessReplayer  # noqa: E402
 from device_go_child import (ARCH, WIZ, admitted, fuzz_rooms, fuzz_users, get_room, go_user, has_room_access, mirror_differences,  # noqa: E402
-                             movers_of, plan_of, seat, seat_clones, set_rooms)
+                             movers_of, seat, seat_clones, set_rooms)
 from device_rooms_child import list_room  # noqa: E402
 from device_tell_child import get_user  # noqa: E402
+from event_checks import child_main, event_differences, lines_of, load, plan_of  # noqa: E402
+from event_checks import digest as digest_of  # noqa: E402
 from nuts333_amd import device, nuts_path  # noqa: E402
 
 G = device
-GOLDEN = REPO / "tests" / "golden"
 SESSIONS = ("reference_only/clone.json", "clones.json", "reference_only/access.json") + tuple(
     f"reference_only/replay_{seed}.json" for seed in sr.SEEDS)
 COMS = {"clone": G.COM_CLONE, "destroy": G.COM_DESTROY, "csay": G.COM_CSAY, "chear": G.COM_CHEAR}
@@ -240,33 +237,11 @@ def texts_of(got: G.Clone):
 
 def clone_differences(got: G.Clone, call: dict) -> list:
     """Everything a Clone says against the model's call."""
-    bad = []
-    kinds = texts_of(got)
-    for k, res in enumerate(call["events"]):
-        where = {"event": k, "slot": res["slot"], "com": res["com"], "model": res["outcome"]}
-        if res["outcome"] == G.CLONE_DEFERRED:                          # its targets are the snapshot's: not compared
-            if int(got.outcome[k]) != G.CLONE_DEFERRED or got.reset[k] or got.created[k] != -1 or (got.text_sizes[:, k] != -1).any() or any(
-                    p.admitted(k).any() or p.variant_sizes[k].any() or p.write_counts[k].any() for _, p, _ in kinds):
-                bad.append({**where, "what": "a deferred event", "device": int(got.outcome[k])})
-            continue
-        have = (int(got.outcome[k]), int(got.target_room[k]), int(got.target_slot[k]), int(got.record[k]), bool(got.reset[k]),
-                int(got.created[k]))
-        want = (res["outcome"], res["target_room"], res["target_slot"], res["record"], res["returned"], res["created"])
-        if have != want:
-            bad.append({**where, "what": "outcome", "device": list(have), "want": list(want)})
-            continue
-        for row, (kind, plan, text) in enumerate(kinds):
-            wanted = res[kind]
-            if text(k) != (wanted or b"") or (got.text_sizes[row, k] >= 0) != (wanted is not None):
-                bad.append({**where, "what": kind + " text", "device": text(k).decode("latin-1"), "want": repr(wanted)})
-                continue
-            p = plan_of(plan, k)
-            want_chunks = {c: nuts_path.chunks(wanted, c) if wanted is not None else [] for c in (0, 1)}
-            if p["admitted"] != res["plans"][kind] or p["chunks"] != want_chunks:
-                bad.append({**where, "what": kind + " plan", "device": p["admitted"][:20], "want": res["plans"][kind][:20]})
-    if got.effective().tolist() != [k for k, r in enumerate(call["events"]) if r["outcome"] in EFFECTIVE]:
-        bad.append({"what": "effective", "device": got.effective().tolist()})
-    return bad
+    return event_differences(
+        got, call, texts_of(got), G.CLONE_DEFERRED,
+        lambda k, res: ((int(got.target_room[k]), int(got.target_slot[k]), int(got.record[k]), bool(got.reset[k]), int(got.created[k])),
+                        (res["target_room"], res["target_slot"], res["record"], res["returned"], res["created"])),
+        also_deferred=lambda k: got.reset[k] or got.created[k] != -1, effective=EFFECTIVE)
 
 
 def record_differences(roster: G.Roster, clones) -> list:
@@ -446,13 +421,7 @@ def same_owner_part() -> dict:
 
 
 def digest(got: G.Clone) -> str:
-    h = hashlib.sha256()
-    h.update(got.outcome.tobytes() + got.target_room.tobytes() + got.target_slot.tobytes() + got.record.tobytes() + got.created.tobytes()
-             + got.reset.tobytes())
-    for _, plan, text in texts_of(got):
-        for k in range(len(got.outcome)):
-            h.update(text(k) + plan.admitted_bits[k].tobytes() + b"".join(b"|".join(plan.chunks(k, c)) for c in (0, 1)))
-    return h.hexdigest()
+    return digest_of(got, [got.target_room, got.target_slot, got.record, got.created, got.reset], texts_of(got))
 
 
 def stream(seed: int, cap: int, k: int):
@@ -646,11 +615,7 @@ class CloneReplayer(AccessReplayer):
 
 
 def clone_lines(doc: dict) -> int:
-    return sum(1 for s in doc["steps"] if s["op"] == "line" and (s["send"].split() or [""])[0] in ("." + c for c in COMS))
-
-
-def load(name: str) -> dict:
-    return json.loads((GOLDEN / name).read_text())
+    return lines_of(doc, COMS)
 
 
 def replay_sessions(backend_class=CloneModelBackend, layouts=(sr.COMPACT,)) -> dict:
@@ -669,29 +634,20 @@ def replay_sessions(backend_class=CloneModelBackend, layouts=(sr.COMPACT,)) -> d
     return out
 
 
+def parts(seed: int) -> tuple:
+    return (("golden", lambda: replay_sessions(CloneDeviceBackend, (sr.COMPACT, sr.SPREAD))), ("fuzz", lambda: fuzz_part(seed)),
+            ("walk", walk_part), ("same_owner", same_owner_part), ("determinism", lambda: determinism_part(seed + 1)),
+            ("regrown", lambda: regrown_part(seed + 2)))
+
+
+def profile(res: dict) -> dict:
+    return {"seconds": res["seconds"], "fuzz": {k: res["fuzz"][k] for k in ("calls", "events", "outcomes")},
+            "golden": {k: {"clone": v["clone"], "comparisons": v["comparisons"]} for k, v in res["golden"].items()},
+            "walk_cases": res["walk"]["cases"], "walk_tables": res["walk"]["tables"]}
+
+
 def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--seed", type=int, default=20263)
-    ap.add_argument("--profile", help="write the parts' seconds here, as JSON")
-    args = ap.parse_args()
-    if G.device_count() < 1:
-        print("no GPU visible", file=sys.stderr)
-        return 3
-    parts = (("golden", lambda: replay_sessions(CloneDeviceBackend, (sr.COMPACT, sr.SPREAD))), ("fuzz", lambda: fuzz_part(args.seed)),
-             ("walk", walk_part), ("same_owner", same_owner_part), ("determinism", lambda: determinism_part(args.seed + 1)),
-             ("regrown", lambda: regrown_part(args.seed + 2)))
-    res, seconds = {}, {}
-    for name, part in parts:
-        t0 = time.perf_counter()
-        res[name] = part()
-        seconds[name] = round(time.perf_counter() - t0, 3)
-    res["seconds"] = seconds
-    print("DEVICE_CLONE " + json.dumps(res))
-    if args.profile:
-        Path(args.profile).write_text(json.dumps({"seconds": seconds, "fuzz": {k: res["fuzz"][k] for k in ("calls", "events", "outcomes")},
-                                                  "golden": {k: {"clone": v["clone"], "comparisons": v["comparisons"]} for k, v in res["golden"].items()},
-                                                  "walk_cases": res["walk"]["cases"], "walk_tables": res["walk"]["tables"]}, indent=1) + "\n")
-    return 0
+    return child_main("DEVICE_CLONE", parts, profile, seed=20263)
 
 
 if __name__ == "__main__":

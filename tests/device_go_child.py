@@ -13,9 +13,6 @@ compares every client's bytes, the mover's included.
 """
 from __future__ import annotations
 
-import argparse
-import hashlib
-import json
 import random
 import sys
 import time
@@ -31,9 +28,10 @@ import session_replay as sr  # noqa: E402
 from device_look_child import look_user  # noqa: E402
 from device_look_child import model_chunks as look_chunks  # noqa: E402
 from device_rooms_child import counted, list_room  # noqa: E402
+from event_checks import child_main, event_differences, lines_of, load, plan_of  # noqa: E402
+from event_checks import digest as digest_of  # noqa: E402
 from nuts333_amd import device, nuts_path  # noqa: E402
 
-GOLDEN = REPO / "tests" / "golden"
 SESSIONS = ("reference_only/go.json", "rooms.json", "reference_only/rmst.json", "reference_only/who.json", "clones.json") + tuple(
     f"reference_only/replay_{seed}.json" for seed in sr.SEEDS)
 WIZ, ARCH = 2, 3
@@ -223,37 +221,17 @@ def seat_clones(roster: device.Roster, clones) -> None:
             roster.set_clones(c, owner=rec[0], room=rec[1], hear=rec[2])
 
 
-def plan_of(plan: device.Plan, k: int) -> dict:
-    return {"admitted": np.flatnonzero(plan.admitted(k)).tolist(), "chunks": {c: plan.chunks(k, c) for c in (0, 1)}}
+def texts_of(got: device.Go):
+    return (("enter", got.enter, got.enter_text), ("leave", got.leave, got.leave_text), ("reset", got.reset, got.reset_text),
+            ("reply", got.reply, got.reply_text))
 
 
 def go_differences(got: device.Go, call: dict, users: dict, rooms) -> list:
     """Everything a Go says against the model's call; ``users`` and ``rooms`` are the state after it."""
-    bad = []
-    kinds = (("enter", got.enter, got.enter_text), ("leave", got.leave, got.leave_text), ("reset", got.reset, got.reset_text),
-             ("reply", got.reply, got.reply_text))
-    for k, res in enumerate(call["events"]):
-        where = {"event": k, "slot": res["slot"], "model": res["outcome"]}
-        if res["outcome"] == device.GO_DEFERRED:                        # its target and old room are the snapshot's: not compared
-            if int(got.outcome[k]) != device.GO_DEFERRED or got.returned_public[k] or (got.text_sizes[:, k] != -1).any() or any(
-                    p.admitted(k).any() or p.variant_sizes[k].any() or p.write_counts[k].any() for _, p, _ in kinds):
-                bad.append({**where, "what": "a deferred event", "device": int(got.outcome[k])})
-            continue
-        if (int(got.outcome[k]), int(got.target[k]), int(got.old_room[k]), bool(got.returned_public[k])) != (
-                res["outcome"], res["target"], res["old"], res["returned"]):
-            bad.append({**where, "what": "outcome", "device": [int(got.outcome[k]), int(got.target[k]), int(got.old_room[k]),
-                                                              bool(got.returned_public[k])],
-                        "want": [res["outcome"], res["target"], res["old"], res["returned"]]})
-            continue
-        for row, (kind, plan, text) in enumerate(kinds):
-            want = res[kind]
-            if text(k) != (want or b"") or (got.text_sizes[row, k] >= 0) != (want is not None):
-                bad.append({**where, "what": kind + " text", "device": text(k).decode("latin-1"), "want": repr(want)})
-                continue
-            p = plan_of(plan, k)
-            want_chunks = {c: nuts_path.chunks(want, c) if want is not None else [] for c in (0, 1)}
-            if p["admitted"] != res["plans"][kind] or p["chunks"] != want_chunks:
-                bad.append({**where, "what": kind + " plan", "device": p["admitted"][:20], "want": res["plans"][kind][:20]})
+    bad = event_differences(
+        got, call, texts_of(got), device.GO_DEFERRED,
+        lambda k, res: ((int(got.target[k]), int(got.old_room[k]), bool(got.returned_public[k])), (res["target"], res["old"], res["returned"])),
+        also_deferred=lambda k: got.returned_public[k])
     movers = call["movers"]
     if (got.look is None) != (not movers) or got.moved().tolist() != [k for k, r in enumerate(call["events"]) if r["outcome"] in MOVED]:
         bad.append({"what": "movers", "device": got.moved().tolist()})
@@ -470,15 +448,8 @@ def population_part() -> dict:
 
 # ------------------------------------------------------------------ repeatability, regrowth, limits
 def digest(got: device.Go) -> str:
-    h = hashlib.sha256()
-    h.update(got.outcome.tobytes() + got.target.tobytes() + got.old_room.tobytes() + got.returned_public.tobytes())
-    for plan in (got.enter, got.leave, got.reset, got.reply):
-        for k in range(len(got.outcome)):
-            h.update(plan.admitted_bits[k].tobytes() + b"".join(b"|".join(plan.chunks(k, c)) for c in (0, 1)))
-    if got.look is not None:
-        for i in range(len(got.look.slots)):
-            h.update(got.look.output(i))
-    return h.hexdigest()
+    looks = [got.look.output(i) for i in range(len(got.look.slots))] if got.look is not None else []
+    return digest_of(got, [got.target, got.old_room, got.returned_public, *looks], texts_of(got))
 
 
 def determinism_part(seed: int) -> dict:
@@ -670,10 +641,8 @@ class GoDeviceBackend(sr.DeviceBackend):
             for j, u in st.users.items():
                 self.sent[j]["invite"] = u["invite"]
             self.sent_access = [rm["access"] for rm in st.rooms]
-        plans = {kind: plan_of(plan, 0) for kind, plan in (("enter", got.enter), ("leave", got.leave), ("reset", got.reset),
-                                                           ("reply", got.reply))}
-        texts = {"enter": got.enter_text(0) or None, "leave": got.leave_text(0) or None, "reset": got.reset_text(0) or None,
-                 "reply": got.reply_text(0) or None}
+        plans = {kind: plan_of(plan, 0) for kind, plan, _ in texts_of(got)}
+        texts = {kind: text(0) or None for kind, _, text in texts_of(got)}
         return {"outcome": outcome, "target": int(got.target[0]), "old": int(got.old_room[0]), "returned": bool(got.returned_public[0]),
                 "look": got.look.output(0) if got.look is not None else None, "texts": texts, "plans": plans}
 
@@ -836,11 +805,7 @@ class GoReplayer(sr.Replayer):
 
 
 def go_lines(doc: dict) -> int:
-    return sum(1 for s in doc["steps"] if s["op"] == "line" and (s["send"].split() or [""])[0] == ".go")
-
-
-def load(name: str) -> dict:
-    return json.loads((GOLDEN / name).read_text())
+    return lines_of(doc, ("go",))
 
 
 def replay_sessions(backend_class=GoModelBackend, layouts=(sr.COMPACT,)) -> dict:
@@ -858,29 +823,20 @@ def replay_sessions(backend_class=GoModelBackend, layouts=(sr.COMPACT,)) -> dict
     return out
 
 
+def parts(seed: int) -> tuple:
+    return (("golden", lambda: replay_sessions(GoDeviceBackend, (sr.COMPACT, sr.SPREAD))), ("fuzz", lambda: fuzz_part(seed)),
+            ("get_room", get_room_part), ("population", population_part), ("determinism", lambda: determinism_part(seed + 1)),
+            ("regrown", lambda: regrown_part(seed + 2)), ("limits", limits_part))
+
+
+def profile(res: dict) -> dict:
+    return {"seconds": res["seconds"], "fuzz": {k: res["fuzz"][k] for k in ("calls", "events", "outcomes")},
+            "golden": {k: {"go": v["go"], "comparisons": v["comparisons"]} for k, v in res["golden"].items()},
+            "limits_seconds": res["limits"]["seconds"]}
+
+
 def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--seed", type=int, default=20261)
-    ap.add_argument("--profile", help="write the parts' seconds here, as JSON")
-    args = ap.parse_args()
-    if device.device_count() < 1:
-        print("no GPU visible", file=sys.stderr)
-        return 3
-    parts = (("golden", lambda: replay_sessions(GoDeviceBackend, (sr.COMPACT, sr.SPREAD))), ("fuzz", lambda: fuzz_part(args.seed)),
-             ("get_room", get_room_part), ("population", population_part), ("determinism", lambda: determinism_part(args.seed + 1)),
-             ("regrown", lambda: regrown_part(args.seed + 2)), ("limits", limits_part))
-    res, seconds = {}, {}
-    for name, part in parts:
-        t0 = time.perf_counter()
-        res[name] = part()
-        seconds[name] = round(time.perf_counter() - t0, 3)
-    res["seconds"] = seconds
-    print("DEVICE_GO " + json.dumps(res))
-    if args.profile:
-        Path(args.profile).write_text(json.dumps({"seconds": seconds, "fuzz": {k: res["fuzz"][k] for k in ("calls", "events", "outcomes")},
-                                                  "golden": {k: {"go": v["go"], "comparisons": v["comparisons"]} for k, v in res["golden"].items()},
-                                                  "limits_seconds": res["limits"]["seconds"]}, indent=1) + "\n")
-    return 0
+    return child_main("DEVICE_GO", parts, profile, seed=20261)
 
 
 if __name__ == "__main__":

@@ -16,12 +16,8 @@ and the replayer composes it from the format strings.
 """
 from __future__ import annotations
 
-import argparse
-import hashlib
-import json
 import random
 import sys
-import time
 from pathlib import Path
 
 import numpy as np
@@ -31,16 +27,18 @@ sys.path.insert(0, str(REPO))
 sys.path.insert(0, str(REPO / "tests"))
 
 import session_replay as sr  # noqa: E402
-from device_go_child import admitted, first_word, go_call, go_differences, go_user, look_of, plan_of  # noqa: E402
+from device_go_child import admitted, first_word, go_call, go_differences, go_user, look_of  # noqa: E402
 from device_go_child import set_rooms as set_list_rooms  # noqa: E402
 from device_rooms_child import list_room  # noqa: E402
 from device_rooms_child import model_chunks as rooms_chunks  # noqa: E402
 from device_tell_child import private  # noqa: E402
 from device_who_child import model_chunks as who_chunks  # noqa: E402
+from event_checks import child_main, event_differences, plan_of  # noqa: E402
+from event_checks import digest as digest_of  # noqa: E402
+from event_checks import load as load_golden  # noqa: E402
 from nuts333_amd import device, nuts_path  # noqa: E402
 
 G = device
-GOLDEN = REPO / "tests" / "golden" / "reference_only"
 NAMES = {"mode": G.COM_MODE, "ignall": G.COM_IGNALL, "prompt": G.COM_PROMPT, "desc": G.COM_DESC, "inphr": G.COM_INPHR,
          "outphr": G.COM_OUTPHR, "topic": G.COM_TOPIC, "vis": G.COM_VIS, "invis": G.COM_INVIS, "charecho": G.COM_CHARECHO,
          "afk": G.COM_AFK, "colour": G.COM_COLOUR, "ignshout": G.COM_IGNSHOUT, "igntell": G.COM_IGNTELL}
@@ -192,30 +190,8 @@ def texts_of(got: G.Settings):
 
 def set_differences(got: G.Settings, call: dict) -> list:
     """Everything a Settings says against the model's call."""
-    bad = []
-    kinds = texts_of(got)
-    for k, res in enumerate(call["events"]):
-        where = {"event": k, "slot": res["slot"], "com": res["com"], "model": res["outcome"]}
-        if res["outcome"] == G.SET_DEFERRED:
-            if int(got.outcome[k]) != G.SET_DEFERRED or (got.text_sizes[:, k] != -1).any() or any(
-                    p.admitted(k).any() or p.variant_sizes[k].any() or p.write_counts[k].any() for _, p, _ in kinds):
-                bad.append({**where, "what": "a deferred event", "device": int(got.outcome[k])})
-            continue
-        if int(got.outcome[k]) != res["outcome"] or int(got.reply_colour[k]) != res["reply_colour"]:
-            bad.append({**where, "what": "outcome", "device": [int(got.outcome[k]), int(got.reply_colour[k])]})
-            continue
-        for row, (kind, plan, text) in enumerate(kinds):
-            want = res[kind]
-            if text(k) != (want or b"") or (got.text_sizes[row, k] >= 0) != (want is not None):
-                bad.append({**where, "what": kind + " text", "device": text(k).decode("latin-1"), "want": repr(want)})
-                continue
-            p = plan_of(plan, k)
-            want_chunks = {c: nuts_path.chunks(want, c) if want is not None else [] for c in (0, 1)}
-            if p["admitted"] != res["plans"][kind] or p["chunks"] != want_chunks:
-                bad.append({**where, "what": kind + " plan", "device": p["admitted"][:20], "want": res["plans"][kind][:20]})
-    if got.effective().tolist() != [k for k, r in enumerate(call["events"]) if r["outcome"] in EFFECTIVE]:
-        bad.append({"what": "effective", "device": got.effective().tolist()})
-    return bad
+    return event_differences(got, call, texts_of(got), G.SET_DEFERRED, lambda k, res: ((int(got.reply_colour[k]),), (res["reply_colour"],)),
+                             effective=EFFECTIVE)
 
 
 def deliveries(users_before: dict, call: dict) -> dict:
@@ -456,12 +432,7 @@ def following_part() -> dict:
 
 # ------------------------------------------------------------------ repeatability, regrowth
 def digest(got: G.Settings) -> str:
-    h = hashlib.sha256()
-    h.update(got.outcome.tobytes() + got.reply_colour.tobytes())
-    for _, plan, text in texts_of(got):
-        for k in range(len(got.outcome)):
-            h.update(text(k) + plan.admitted_bits[k].tobytes() + b"".join(b"|".join(plan.chunks(k, c)) for c in (0, 1)))
-    return h.hexdigest()
+    return digest_of(got, [got.reply_colour], texts_of(got))
 
 
 def determinism_part(seed: int) -> dict:
@@ -690,7 +661,7 @@ SESSIONS = ("set",) + tuple(f"replay_{seed}" for seed in sr.SEEDS)
 
 
 def load(name: str) -> dict:
-    return json.loads((GOLDEN / f"{name}.json").read_text())
+    return load_golden(f"reference_only/{name}.json")
 
 
 def set_lines(doc: dict) -> int:
@@ -711,34 +682,24 @@ def replay_sessions(backend_class=SetModelBackend, layouts=(sr.COMPACT,)) -> dic
     return out
 
 
+def parts(seed: int) -> tuple:
+    return (("golden", lambda: replay_sessions(SetDeviceBackend, (sr.COMPACT, sr.SPREAD))), ("fuzz", lambda: fuzz_part(seed)),
+            ("edges", edges_part), ("following", following_part), ("determinism", lambda: determinism_part(seed + 1)),
+            ("regrown", lambda: regrown_part(seed + 2)))
+
+
+def profile(res: dict) -> dict:
+    golden = res["golden"]
+    steps = sum(v["set"] for v in golden.values())
+    comparisons = sum(v["comparisons"] for v in golden.values())
+    differs = sum(v["n_mismatches"] for v in golden.values()) + sum(res[p]["n_bad"] for p in ("fuzz", "edges", "following", "regrown"))
+    return {"steps": steps, "comparisons": comparisons, "verdict": "nothing differs" if not differs else f"{differs} differences",
+            "seconds": res["seconds"], "fuzz": {k: res["fuzz"][k] for k in ("calls", "events", "outcomes")},
+            "golden": {k: {"set": v["set"], "comparisons": v["comparisons"]} for k, v in golden.items()}}
+
+
 def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--seed", type=int, default=20263)
-    ap.add_argument("--profile", help="write the parts' seconds here, as JSON")
-    args = ap.parse_args()
-    if G.device_count() < 1:
-        print("no GPU visible", file=sys.stderr)
-        return 3
-    parts = (("golden", lambda: replay_sessions(SetDeviceBackend, (sr.COMPACT, sr.SPREAD))), ("fuzz", lambda: fuzz_part(args.seed)),
-             ("edges", edges_part), ("following", following_part), ("determinism", lambda: determinism_part(args.seed + 1)),
-             ("regrown", lambda: regrown_part(args.seed + 2)))
-    res, seconds = {}, {}
-    for name, part in parts:
-        t0 = time.perf_counter()
-        res[name] = part()
-        seconds[name] = round(time.perf_counter() - t0, 3)
-    res["seconds"] = seconds
-    print("DEVICE_SET " + json.dumps(res))
-    if args.profile:
-        golden = res["golden"]
-        steps = sum(v["set"] for v in golden.values())
-        comparisons = sum(v["comparisons"] for v in golden.values())
-        differs = sum(v["n_mismatches"] for v in golden.values()) + sum(res[p]["n_bad"] for p in ("fuzz", "edges", "following", "regrown"))
-        Path(args.profile).write_text(json.dumps({
-            "steps": steps, "comparisons": comparisons, "verdict": "nothing differs" if not differs else f"{differs} differences",
-            "seconds": seconds, "fuzz": {k: res["fuzz"][k] for k in ("calls", "events", "outcomes")},
-            "golden": {k: {"set": v["set"], "comparisons": v["comparisons"]} for k, v in golden.items()}}, indent=1) + "\n")
-    return 0
+    return child_main("DEVICE_SET", parts, profile, seed=20263)
 
 
 if __name__ == "__main__":

@@ -15,13 +15,11 @@ GPU tier: everything that touches the device runs in ONE short-lived child for t
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 import session_replay as sr
 from device_access_child import (EDGE_SLOTS, GET_USER_WORDS, SESSIONS, AccessReplayer, access, access_call, access_lines,
                                  fuzz_part, load)
@@ -30,7 +28,6 @@ from device_rooms_child import list_room
 from nuts333_amd import device, nuts_path
 from test_device_go import FLAGS, FakeLibrary, clean, flags, mirrors, model_state_differences, only, passed
 
-REPO = Path(__file__).resolve().parent.parent
 G = device
 KW = {"gatecrash_level": ARCH, "min_private_users": 2, "ignore_mp_level": WIZ}
 PUB, PRIV, LET, INV = G.COM_PUBLIC, G.COM_PRIVATE, G.COM_LETMEIN, G.COM_INVITE
@@ -445,15 +442,7 @@ def test_a_rejected_call_changes_nothing_after_an_accepted_one(fake):
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def access_run(built):
-    cmd = ["timeout", "-k", "10", "300", sys.executable, str(REPO / "tests" / "device_access_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=360, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 360 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_ACCESS ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_ACCESS "):])
+    res = child_run.run_child("device_access_child.py", "DEVICE_ACCESS", 300)
     print("\n[access]", json.dumps(res)[:6000])
     return res
 

@@ -14,15 +14,13 @@ from __future__ import annotations
 import json
 import re
 import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 from nuts333_amd import device
 
-REPO = Path(__file__).resolve().parent.parent
 MANY_KERNELS = ("nuts_fanout_measure_many", "nuts_fanout_emit_many")
 
 
@@ -155,15 +153,7 @@ def test_broadcast_offsets_address_items_by_broadcast_and_listener():
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def many_run(built):
-    cmd = ["timeout", "-k", "10", "900", sys.executable, str(REPO / "tests" / "device_many_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=960, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 960 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_MANY ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_MANY "):])
+    res = child_run.run_child("device_many_child.py", "DEVICE_MANY", 900)
     print("\n[broadcast_many]", json.dumps(res)[:1500])
     return res
 

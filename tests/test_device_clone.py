@@ -20,13 +20,11 @@ from __future__ import annotations
 import itertools
 import json
 import re
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 import session_replay as sr
 from device_access_child import access_call
 from device_clone_child import (CAPACITIES, EVENTS, KINDS, SESSIONS, WALK_CLONES, CloneReplayer, clone, clone_call, clone_lines, create_loop,
@@ -36,7 +34,6 @@ from device_rooms_child import list_room
 from nuts333_amd import device, nuts_path
 from test_device_go import FLAGS, FakeLibrary, clean, flags, mirrors, model_state_differences, only, passed
 
-REPO = Path(__file__).resolve().parent.parent
 G = device
 KW = {"max_clones": 2, "gatecrash_level": ARCH, "min_private_users": 2}
 CLO, DES, SAY, HEAR = G.COM_CLONE, G.COM_DESTROY, G.COM_CSAY, G.COM_CHEAR
@@ -530,15 +527,7 @@ def test_a_rejected_call_changes_nothing_after_an_accepted_one(fake):
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def clone_run(built):
-    cmd = ["timeout", "-k", "10", "300", sys.executable, str(REPO / "tests" / "device_clone_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=360, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 360 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_CLONE ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_CLONE "):])
+    res = child_run.run_child("device_clone_child.py", "DEVICE_CLONE", 300)
     print("\n[clone]", json.dumps(res)[:6000])
     return res
 

@@ -7,15 +7,11 @@ message and measures nothing -- there is no CPU fall-back.
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
+import child_run
 from nuts333_amd import devpath
-
-REPO = Path(__file__).resolve().parent.parent
 
 
 def test_devpath_without_a_gpu_exits_nonzero_and_says_why(monkeypatch, capsys):
@@ -42,16 +38,8 @@ def test_listener_tables_have_one_sender_and_the_asked_colours():
 
 @pytest.mark.gpu
 def test_devpath_command_prints_one_well_formed_json_line(built):
-    cmd = ["timeout", "-k", "10", "600", sys.executable, "-m", "nuts333_amd.devpath", "--reps", "20", "--warmup", "5",
-           "--pathbench-iterations", "200000"]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=660, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("devpath did not finish in 660 s")
-    assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
-    lines = p.stdout.decode().strip().splitlines()
-    assert len(lines) == 1
-    j = json.loads(lines[0])
+    line = child_run.run_devpath_line("devpath", 600, "--reps", "20", "--warmup", "5", "--pathbench-iterations", "200000")
+    j = json.loads(line)
     assert j["reps"] == 20 and "nuts_fanout_measure_broadcast" in j["kernels"]
     assert len(j["cases"]) == 3 * 2 * 3
     assert {(c["n"], c["text"], c["colour"]) for c in j["cases"]} == {
@@ -60,4 +48,4 @@ def test_devpath_command_prints_one_well_formed_json_line(built):
         assert c["recipients"] == c["n"] - 1 and c["bytes_out"] > 0 and c["cpu_derived_us"] > 0
         assert 0 < c["kernels_us"]["median"] <= c["end_to_end_us"]["median"]
         assert c["kernels_us"]["p10"] <= c["kernels_us"]["median"] <= c["kernels_us"]["p90"]
-    print("\n[devpath]", lines[0][:800])
+    print("\n[devpath]", line[:800])

@@ -20,6 +20,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import child_run
 from nuts333_amd import device, nuts_path
 
 REPO = Path(__file__).resolve().parent.parent
@@ -131,16 +132,7 @@ def test_size_and_write_bounds_hold_on_the_cpu_restatement():
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def device_run(built):
-    cmd = ["timeout", "-k", "10", "900", sys.executable, str(REPO / "tests" / "device_fanout_child.py"),
-           "--fuzz", str(FUZZ)]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=960, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 960 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_FANOUT ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_FANOUT "):])
+    res = child_run.run_child("device_fanout_child.py", "DEVICE_FANOUT", 900, "--fuzz", str(FUZZ))
     print("\n[device fan-out]", json.dumps({k: v for k, v in res.items() if k != "vectors"})[:1500])
     return res
 

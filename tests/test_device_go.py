@@ -16,20 +16,19 @@ under ``timeout``), and the tests assert on its JSON.
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 import session_replay as sr
 from device_go_child import (ARCH, CAPACITIES, EVENTS, LOOK_ROOMS, MOVED, POPULATION_SLOTS, SESSIONS, GoReplayer, cases, go, go_call,
                              go_lines, go_user, load, seat, seat_clones, set_rooms)
 from device_rooms_child import list_room
+from event_checks import digest as digest_of
+from event_checks import event_differences
 from nuts333_amd import device, nuts_path
 
-REPO = Path(__file__).resolve().parent.parent
 FLAGS = ("_dirty", "_speech_dirty", "_private_dirty", "_afk_dirty", "_rooms_dirty", "_udesc_dirty", "_who_dirty", "_clones_dirty",
          "_go_dirty")
 MIRRORS = ("_table", "_speech", "_rooms", "_udesc", "_who", "_afk", "_clones", "_go")
@@ -589,18 +588,107 @@ def test_go_many_interleaved_with_the_other_calls(fake):
     assert int(r._room_rec[2, 21]) == device.PUBLIC                     # the den was emptied on the way
 
 
+# ------------------------------------------------------------------ host tier: the comparison the event children share
+STAND_IN_KINDS, STAND_IN_DEFERRED, STAND_IN_EFFECTIVE, STAND_IN_CAPACITY = ("here", "reply"), 9, (1,), 8
+
+
+class StandInPlan:
+    """What event_differences and digest read of a device.Plan, held as given."""
+
+    def __init__(self, slots, chunks):
+        self.bits = np.zeros((len(slots), STAND_IN_CAPACITY), dtype=bool)
+        for k, admitted in enumerate(slots):
+            self.bits[k, admitted] = True
+        self.chunk_lists = chunks                                       # [k][c]: a list of bytes
+        self.variant_sizes = np.array([[sum(map(len, both[c])) for c in (0, 1)] for both in chunks], dtype=np.int32)
+        self.write_counts = np.array([[len(both[c]) for c in (0, 1)] for both in chunks], dtype=np.int32)
+
+    @property
+    def admitted_bits(self):
+        return np.packbits(self.bits, axis=1, bitorder="little")
+
+    def admitted(self, k):
+        return self.bits[k]
+
+    def chunks(self, k, c):
+        return list(self.chunk_lists[k][c])
+
+
+class StandIn:
+    """A result as the event calls give one, built from a model's call: every field says what the model says."""
+
+    def __init__(self, call):
+        events = call["events"]
+        self.outcome = np.array([e["outcome"] for e in events], dtype=np.int32)
+        self.target = np.array([e["target"] for e in events], dtype=np.int32)
+        self.held = np.zeros(len(events), dtype=bool)                   # a field a deferred event must leave alone
+        self.texts = {kind: [e[kind] or b"" for e in events] for kind in STAND_IN_KINDS}
+        self.text_sizes = np.array([[-1 if e[kind] is None else len(e[kind]) for e in events] for kind in STAND_IN_KINDS], dtype=np.int32)
+        self.plans = {kind: StandInPlan([e["plans"][kind] for e in events],
+                                        [[nuts_path.chunks(e[kind], c) if e[kind] is not None else [] for c in (0, 1)] for e in events])
+                      for kind in STAND_IN_KINDS}
+        self.effective_events = [k for k, e in enumerate(events) if e["outcome"] in STAND_IN_EFFECTIVE]
+
+    def effective(self):
+        return np.array(self.effective_events, dtype=np.int64)
+
+    def kinds(self):
+        return tuple((kind, self.plans[kind], lambda k, kind=kind: self.texts[kind][k]) for kind in STAND_IN_KINDS)
+
+    def differences(self, call):
+        return event_differences(self, call, self.kinds(), STAND_IN_DEFERRED, lambda k, res: ((int(self.target[k]),), (res["target"],)),
+                                 also_deferred=lambda k: self.held[k], effective=STAND_IN_EFFECTIVE)
+
+    def digest(self):
+        return digest_of(self, [self.target], self.kinds())
+
+
+def test_the_shared_comparison_finds_each_single_change_and_the_digest_moves():
+    nothing = {"here": None, "reply": None, "plans": {"here": [], "reply": []}}
+    call = {"events": [
+        {"slot": 0, "com": 4, "outcome": 1, "target": 5, "here": b"~FRUaaa~RS waves.\n", "reply": b"You wave.\n",
+         "plans": {"here": [1, 2, 7], "reply": [0]}},
+        {"slot": 1, "com": 4, "outcome": 3, "target": -1, "here": None, "reply": b"Wave at whom?\n", "plans": {"here": [], "reply": [1]}},
+        {"slot": 0, "com": 4, "outcome": STAND_IN_DEFERRED, "target": 5, **nothing}]}
+    assert nuts_path.chunks(call["events"][0]["here"], 0) != nuts_path.chunks(call["events"][0]["here"], 1)
+    faithful = StandIn(call)
+    assert faithful.differences(call) == []
+
+    def outcome(g): g.outcome[0] = 3
+    def extra_field(g): g.target[0] = 6
+    def text_byte(g): g.texts["here"][0] = g.texts["here"][0].replace(b"waves", b"wavez")
+    def present_empty_text(g): g.text_sizes[0, 1] = 0                   # the text itself is b"" either way
+    def admitted_slot(g): g.plans["here"].bits[0, 3] = True
+    def chunk_of_colour_1(g): g.plans["reply"].chunk_lists[0][1][0] += b"!"
+    def deferred_write_count(g): g.plans["reply"].write_counts[2, 1] = 1
+    def deferred_variant_size(g): g.plans["here"].variant_sizes[2, 0] = 1
+    def deferred_admitted_slot(g): g.plans["here"].bits[2, 0] = True
+    def deferred_text_size(g): g.text_sizes[1, 2] = 0
+    def deferred_own_field(g): g.held[2] = True
+    def effective_list(g): g.effective_events.append(1)
+
+    changes = ((outcome, "outcome", 0, True), (extra_field, "outcome", 0, True), (text_byte, "here text", 0, True),
+               (present_empty_text, "here text", 1, True), (admitted_slot, "here plan", 0, True), (chunk_of_colour_1, "reply plan", 0, True),
+               (deferred_write_count, "a deferred event", 2, False), (deferred_variant_size, "a deferred event", 2, False),
+               (deferred_admitted_slot, "a deferred event", 2, True), (deferred_text_size, "a deferred event", 2, True),
+               (deferred_own_field, "a deferred event", 2, False), (effective_list, "effective", None, False))
+    for change, what, event, hashed in changes:
+        got = StandIn(call)
+        assert got.digest() == faithful.digest()
+        change(got)
+        bad = got.differences(call)
+        assert [(b["what"], b.get("event")) for b in bad] == [(what, event)], (change.__name__, bad)
+        if event is not None:
+            e = call["events"][event]
+            assert (bad[0]["slot"], bad[0]["com"], bad[0]["model"]) == (e["slot"], e["com"], e["outcome"]) and "device" in bad[0]
+            assert ("want" in bad[0]) == (what != "a deferred event"), bad
+        assert (got.digest() != faithful.digest()) == hashed, change.__name__
+
+
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def go_run(built):
-    cmd = ["timeout", "-k", "10", "300", sys.executable, str(REPO / "tests" / "device_go_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=360, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 360 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_GO ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_GO "):])
+    res = child_run.run_child("device_go_child.py", "DEVICE_GO", 300)
     print("\n[go]", json.dumps(res)[:6000])
     return res
 

@@ -19,13 +19,12 @@ from __future__ import annotations
 import json
 import random
 import re
-import subprocess
-import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 from device_input_child import (CAPACITIES, COMMAND, EMPTY, IAC, KINDS, READS_PER_CALL, REPEAT, SPEECH, UNKNOWN,
                                 UNKNOWN_NOTICE, answer_of, command_table, dispatch, fuzz_read, model_answer, parse_rule,
                                 replay_reads, systematic_reads)
@@ -422,15 +421,7 @@ def test_a_hand_built_input_obeys_its_accessors(no_library):
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def input_run(built):
-    cmd = ["timeout", "-k", "10", "600", sys.executable, str(REPO / "tests" / "device_input_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=660, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 660 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_INPUT ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_INPUT "):])
+    res = child_run.run_child("device_input_child.py", "DEVICE_INPUT", 600)
     print("\n[input]", json.dumps(res)[:4000])
     return res
 

@@ -23,15 +23,12 @@ volumes are sums of 256-byte aligned slices of arrays whose sizes the module's m
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
+import child_run
 from device_kept_child import CAPACITY, TABLES, TWICE, State, go_walks, input_arrays, new_roster, passed, request, subsets, table_slices
 
-REPO = Path(__file__).resolve().parent.parent
 #: the kinds whose cases are one call made twice; go_many's have tests of their own below
 KINDS = TWICE
 
@@ -87,15 +84,7 @@ def test_a_change_sets_the_flag_of_its_table_alone(kind):
 # ------------------------------------------------------------------ GPU tier
 @pytest.fixture(scope="module")
 def kept_run(built):
-    cmd = ["timeout", "-k", "10", "120", sys.executable, str(REPO / "tests" / "device_kept_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=180, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 180 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_KEPT ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_KEPT "):])
+    res = child_run.run_child("device_kept_child.py", "DEVICE_KEPT", 120)
     print("\n[kept]", json.dumps(res)[:4000])
     return res
 

@@ -18,13 +18,11 @@ any part, a positive number of comparisons in every part, and the coverage condi
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 import device_limits_child as limits
 from device_limits_child import (CAPACITY, EDGE_CLONES, EDGE_ROOMS, EDGE_SLOTS, FULL_LOOKERS, FULL_WHO_LOOKERS, GUARD_K, GUARD_LINES, LAST,
                                  LAST_ROOM, admit_words, admits_np, edge_coverage, edge_description, edge_script, footer_counts,
@@ -34,7 +32,6 @@ from device_tell_child import private
 from device_who_child import colour_com_count, listed, shown
 from nuts333_amd import device, nuts_path
 
-REPO = Path(__file__).resolve().parent.parent
 CALLS = ("plan_many", "broadcast_many", "expand", "speak_many", "input_many", "review_many", "tell_many", "revtell_many", "look_many",
          "who_many", "relay_many")
 
@@ -208,15 +205,7 @@ def test_every_tell_case_resolves_to_the_branch_it_is_named_for(built, full):
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def limits_run(built):
-    cmd = ["timeout", "-k", "10", "900", sys.executable, str(REPO / "tests" / "device_limits_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=960, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 960 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_LIMITS ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_LIMITS "):])
+    res = child_run.run_child("device_limits_child.py", "DEVICE_LIMITS", 900)
     print("\n[limits]", json.dumps(res)[:6000])
     return res
 

@@ -15,18 +15,14 @@ from __future__ import annotations
 
 import itertools
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 from device_look_child import (CAPACITIES, GOLDEN, LOOKERS_PER_CALL, WORST_DESCS, WORST_NAMES, fuzz_rooms, golden_looks, look,
                                look_user, member_line, members, model_answer, model_chunks, new_room, replay_looks)
 from nuts333_amd import device, nuts_path
-
-REPO = Path(__file__).resolve().parent.parent
 
 
 def roomed(capacity=4, look_rooms=3, **kw) -> device.Roster:
@@ -387,15 +383,7 @@ def test_a_hand_built_look_obeys_the_contract(no_library):
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def look_run(built):
-    cmd = ["timeout", "-k", "10", "600", sys.executable, str(REPO / "tests" / "device_look_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=660, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 660 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_LOOK ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_LOOK "):])
+    res = child_run.run_child("device_look_child.py", "DEVICE_LOOK", 600)
     print("\n[look]", json.dumps(res)[:4000])
     return res
 

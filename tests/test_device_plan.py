@@ -14,18 +14,15 @@ worst case.
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 import test_device_roster as roster_tests
 from device_many_child import Cpu, compare, expected
 from nuts333_amd import device, nuts_path
 
-REPO = Path(__file__).resolve().parent.parent
 FIELDS = ("admitted", "out_offsets", "arena", "write_offsets", "write_sizes", "broadcast_offsets")
 GOOD = roster_tests.GOOD
 
@@ -261,15 +258,7 @@ def test_expand_needs_nothing_but_the_plans_own_arrays(no_library):
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def plan_run(built):
-    cmd = ["timeout", "-k", "10", "900", sys.executable, str(REPO / "tests" / "device_plan_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=960, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 960 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_PLAN ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_PLAN "):])
+    res = child_run.run_child("device_plan_child.py", "DEVICE_PLAN", 900)
     print("\n[plan]", json.dumps(res)[:1500])
     return res
 

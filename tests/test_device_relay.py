@@ -14,13 +14,12 @@ GPU tier: everything that touches the device runs in ONE short-lived child for t
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 from device_relay_child import (ALL, BROADCASTS_PER_CALL, CAPACITIES, CLONES, NOTHING, SWEARS, longest_text, relay_text, relays,
                                 relays_of, replay_relays, swearing)
 from nuts333_amd import device, nuts_path
@@ -371,15 +370,7 @@ def test_a_hand_built_relay_obeys_the_contract(no_library):
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def relay_run(built):
-    cmd = ["timeout", "-k", "10", "300", sys.executable, str(REPO / "tests" / "device_relay_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=360, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 360 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_RELAY ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_RELAY "):])
+    res = child_run.run_child("device_relay_child.py", "DEVICE_RELAY", 300)
     print("\n[relay]", json.dumps(res)[:4000])
     return res
 

@@ -18,12 +18,12 @@ from __future__ import annotations
 
 import copy
 import json
-import subprocess
 import sys
 from pathlib import Path
 
 import pytest
 
+import child_run
 import device_review_child
 import device_tell_child
 import scenarios
@@ -163,15 +163,7 @@ def test_who_json_regenerates_byte_for_byte(ref_binary, monkeypatch):
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def replay_run(built):
-    cmd = ["timeout", "-k", "10", "300", sys.executable, str(REPO / "tests" / "device_replay_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=360, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 360 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_REPLAY ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_REPLAY "):])
+    res = child_run.run_child("device_replay_child.py", "DEVICE_REPLAY", 300)
     print("\n[replay]", json.dumps(res)[:6000])
     return res
 

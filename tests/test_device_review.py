@@ -19,13 +19,12 @@ from __future__ import annotations
 
 import json
 import random
-import subprocess
-import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 from device_review_child import RESET, WAVE_LIMIT, Rings, local_rule, special_texts
 from nuts333_amd import device, nuts_path
 
@@ -310,15 +309,7 @@ def test_the_local_rule_equals_the_transducer_up_to_994_bytes():
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def review_run(built):
-    cmd = ["timeout", "-k", "10", "600", sys.executable, str(REPO / "tests" / "device_review_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=660, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 660 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_REVIEW ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_REVIEW "):])
+    res = child_run.run_child("device_review_child.py", "DEVICE_REVIEW", 600)
     print("\n[review]", json.dumps(res)[:3000])
     return res
 

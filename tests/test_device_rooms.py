@@ -19,13 +19,12 @@ from __future__ import annotations
 
 import json
 import re
-import subprocess
-import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 from device_look_child import look_user
 from device_rooms_child import (CAPACITIES, HEAD_LINKS, HEAD_TOPICS, LOOK_ROOMS, LOOKERS_PER_CALL, cases, counted, golden_listings,
                                 list_room, model_chunks, replay_listings, room_line, rooms, set_rooms, worst_rooms, COMMANDS)
@@ -515,15 +514,7 @@ def test_rooms_many_interleaved_with_the_other_calls(fake):
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def rooms_run(built):
-    cmd = ["timeout", "-k", "10", "300", sys.executable, str(REPO / "tests" / "device_rooms_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=360, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 360 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_ROOMS ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_ROOMS "):])
+    res = child_run.run_child("device_rooms_child.py", "DEVICE_ROOMS", 300)
     print("\n[rooms]", json.dumps(res)[:4000])
     return res
 

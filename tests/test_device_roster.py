@@ -13,16 +13,13 @@ changed, isolation between rosters, the bench step and the worst case.
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 from nuts333_amd import device, nuts_path
 
-REPO = Path(__file__).resolve().parent.parent
 COL = device.LISTENER_FIELDS.index
 
 
@@ -232,15 +229,7 @@ def test_building_and_updating_does_not_touch_the_device(no_library):
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def roster_run(built):
-    cmd = ["timeout", "-k", "10", "900", sys.executable, str(REPO / "tests" / "device_roster_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=960, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 960 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_ROSTER ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_ROSTER "):])
+    res = child_run.run_child("device_roster_child.py", "DEVICE_ROSTER", 900)
     print("\n[roster]", json.dumps(res)[:1500])
     return res
 

@@ -18,20 +18,17 @@ from __future__ import annotations
 
 import json
 import random
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 from device_sequence_child import (CAPACITIES, CLONE_FIELDS, FIELDS, GO_TABLES, KINDS, LOOK_ROOMS, MIRROR_OF, MIRRORS, READS,
                                    RECORDING_KINDS, RELAY_NAMES, REPLACEMENT_CAPACITY, REVIEW_ROOMS, ROOM_FIELDS, SEEDS,
                                    STEPS_PER_ROSTER, TABLE_FIELDS, TABLE_KINDS, UNREAD, USER_FIELDS, Coverage, Runner, State,
                                    clear_blocks, new_roster, op_for, random_op, sequence_part, slice_of)
 from nuts333_amd import device
 
-REPO = Path(__file__).resolve().parent.parent
 HOST_STEPS = 3000
 #: the least a seed's device run counts, from the model's calls: see assert_the_counts
 #: (the dry run counts 121 and 133 moves, 25 and 26 rooms returned, 295 and 384 deferred events, 6,810 and 7,138 who lines, 634
@@ -539,15 +536,7 @@ def test_the_device_stream_alone_reaches_what_the_device_tier_asserts(fake):
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def sequence_run(built):
-    cmd = ["timeout", "-k", "10", "300", sys.executable, str(REPO / "tests" / "device_sequence_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=360, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 360 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_SEQUENCE ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_SEQUENCE "):])
+    res = child_run.run_child("device_sequence_child.py", "DEVICE_SEQUENCE", 300)
     print("\n[sequence]", json.dumps(res)[:6000])
     return res
 

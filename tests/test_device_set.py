@@ -15,13 +15,12 @@ under ``timeout``), and the tests assert on its JSON.
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 import session_replay as sr
 from device_rooms_child import list_room
 from device_set_child import (CAPACITIES, EDGE_SLOTS, EVENTS, NAMES, SESSIONS, WAS_TRACKED, SetReplayer, deliveries, fuzz_part, load,
@@ -465,15 +464,7 @@ def test_an_update_of_prompt_and_charmode_echo_alone_makes_no_other_call_upload(
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def set_run(built):
-    cmd = ["timeout", "-k", "10", "300", sys.executable, str(REPO / "tests" / "device_set_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=360, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 360 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_SET ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_SET "):])
+    res = child_run.run_child("device_set_child.py", "DEVICE_SET", 300)
     print("\n[set]", json.dumps(res)[:6000])
     return res
 

@@ -17,13 +17,12 @@ from __future__ import annotations
 
 import json
 import random
-import subprocess
-import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 from device_speak_child import (CAPACITIES, COMS, EMOTE, EVENTS_PER_CALL, GOLDEN, GOLDEN_COMPARISONS, MUZZLED_NOTICE,
                                 NOSWEARING, SAY, SEMOTE, SHOUT, SWEAR_WORDS, WHAT_NOTICE, model, model_answer, replay,
                                 swear_rule)
@@ -392,15 +391,7 @@ def test_a_hand_built_speech_obeys_the_contract(no_library):
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def speak_run(built):
-    cmd = ["timeout", "-k", "10", "600", sys.executable, str(REPO / "tests" / "device_speak_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=660, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 660 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_SPEAK ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_SPEAK "):])
+    res = child_run.run_child("device_speak_child.py", "DEVICE_SPEAK", 600)
     print("\n[speak]", json.dumps(res)[:4000])
     return res
 

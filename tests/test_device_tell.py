@@ -17,13 +17,12 @@ from __future__ import annotations
 
 import json
 import random
-import subprocess
-import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 from device_tell_child import (AFK, CAPACITIES, COMS, EVENTS_PER_CALL, GOLDEN, GOLDEN_COMPARISONS, GOLDEN_PRIVATE_STEPS,
                                IGNALL, IGNTELL, MUZZLED, MUZZLED_NOTICE, NOBODY, NOBODY_NOTICE, NOTHING, OFFSITE, OUTCOMES,
                                PEMOTE, SELF, SELF_NOTICE, TELL, TOLD, WHAT_NOTICE, TellRings, get_user, lookup_rule,
@@ -476,15 +475,7 @@ def test_a_hand_built_private_obeys_the_contract(no_library):
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def tell_run(built):
-    cmd = ["timeout", "-k", "10", "600", sys.executable, str(REPO / "tests" / "device_tell_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=660, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 660 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_TELL ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_TELL "):])
+    res = child_run.run_child("device_tell_child.py", "DEVICE_TELL", 600)
     print("\n[tell]", json.dumps(res)[:4000])
     return res
 

@@ -17,13 +17,12 @@ GPU tier: everything that touches the device runs in ONE short-lived child for t
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 from device_look_child import set_rooms
 from device_who_child import (CAPACITIES, DATE, EDGES, LOOKERS_PER_CALL, QUIRK_DESCS, cases, colour_com_count, fuzz_rooms, golden_whos,
                               listed, model_chunks, replay_whos, seat, shown, who, who_line, who_user, worst_user)
@@ -466,15 +465,7 @@ def test_who_many_interleaved_with_the_other_calls(fake):
 # ------------------------------------------------------------------ GPU tier: one child for the module
 @pytest.fixture(scope="module")
 def who_run(built):
-    cmd = ["timeout", "-k", "10", "300", sys.executable, str(REPO / "tests" / "device_who_child.py")]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=360, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("device child did not finish in 360 s")
-    lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("DEVICE_WHO ")]
-    if p.returncode != 0 or not lines:
-        pytest.fail(f"device child exited {p.returncode}: {p.stderr.decode(errors='replace')[-2000:]}")
-    res = json.loads(lines[-1][len("DEVICE_WHO "):])
+    res = child_run.run_child("device_who_child.py", "DEVICE_WHO", 300)
     print("\n[who]", json.dumps(res)[:4000])
     return res
 

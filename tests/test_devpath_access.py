@@ -10,19 +10,15 @@ condition but their order: the kernels within the call, the call within the Pyth
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 from device_access_child import access_call
 from device_go_child import go_user
 from device_rooms_child import list_room
 from nuts333_amd import device, devpath
-
-REPO = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("value", ["0", "-1", "1,0", "x", "", "1,,2", "2.5"])
@@ -76,16 +72,8 @@ def test_the_call_handed_to_the_cpu_is_the_models():
 
 @pytest.mark.gpu
 def test_devpath_access_prints_one_line_with_the_parts_and_the_cpu(built):
-    cmd = ["timeout", "-k", "10", "300", sys.executable, "-m", "nuts333_amd.devpath", "--access", "1,8",
-           "--reps", "3", "--warmup", "1", "--pathbench-iterations", "200000"]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=360, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("devpath --access did not finish in 360 s")
-    assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
-    lines = p.stdout.decode().strip().splitlines()
-    assert len(lines) == 1
-    j = json.loads(lines[0])
+    j = child_run.run_devpath("devpath --access", 300, "--access", "1,8",
+                              "--reps", "3", "--warmup", "1", "--pathbench-iterations", "200000")
     assert len(j["cases"]) == 18 and not {"plan", "roster", "look", "relay", "who", "rooms", "go"} & set(j)
     assert j["access_kernels"][:2] == list(device.ACCESS_KERNELS) and j["access_end_to_end_covers"] and j["access_plan_covers"]
     assert j["access_cpu_us_covers"]

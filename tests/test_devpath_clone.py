@@ -11,19 +11,15 @@ condition but their order: the kernels within the call, the call within the Pyth
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 from device_clone_child import clone_call
 from device_go_child import go_user
 from device_rooms_child import list_room
 from nuts333_amd import device, devpath
-
-REPO = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("value", ["0", "-1", "1,0", "x", "", "1,,2", "2.5"])
@@ -74,16 +70,7 @@ def test_the_calls_the_command_submits_are_answered_as_it_expects():
 
 @pytest.mark.gpu
 def test_devpath_clone_prints_one_line_with_the_parts_and_the_cpu(built):
-    cmd = ["timeout", "-k", "10", "300", sys.executable, "-m", "nuts333_amd.devpath", "--clone", "1,8",
-           "--reps", "3", "--warmup", "1", "--pathbench-iterations", "200000"]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=360, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("devpath --clone did not finish in 360 s")
-    assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
-    lines = p.stdout.decode().strip().splitlines()
-    assert len(lines) == 1
-    j = json.loads(lines[0])
+    j = child_run.run_devpath("devpath --clone", 300, "--clone", "1,8", "--reps", "3", "--warmup", "1", "--pathbench-iterations", "200000")
     assert len(j["cases"]) == 18 and not {"plan", "roster", "look", "relay", "who", "rooms", "go", "access"} & set(j)
     assert j["clone_kernels"][:2] == list(device.CLONE_KERNELS) and j["clone_end_to_end_covers"] and j["clone_speak_covers"]
     assert j["clone_cpu_us_covers"]

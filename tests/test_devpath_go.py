@@ -9,19 +9,15 @@ GPU tier: the command, at a small repetition count, in one short-lived child und
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 from device_go_child import go_call, go_user, look_of
 from device_rooms_child import list_room
 from nuts333_amd import device, devpath, nuts_path
 from nuts333_amd.provision import SIX_ROOMS
-
-REPO = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("value", ["0", "-1", "1,0", "x", "", "1,,2", "2.5"])
@@ -74,16 +70,7 @@ def test_the_call_handed_to_the_cpu_is_the_models():
 
 @pytest.mark.gpu
 def test_devpath_go_prints_one_line_with_the_parts_and_the_cpu(built):
-    cmd = ["timeout", "-k", "10", "300", sys.executable, "-m", "nuts333_amd.devpath", "--go", "1,8",
-           "--reps", "3", "--warmup", "1", "--pathbench-iterations", "200000"]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=360, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("devpath --go did not finish in 360 s")
-    assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
-    lines = p.stdout.decode().strip().splitlines()
-    assert len(lines) == 1
-    j = json.loads(lines[0])
+    j = child_run.run_devpath("devpath --go", 300, "--go", "1,8", "--reps", "3", "--warmup", "1", "--pathbench-iterations", "200000")
     assert len(j["cases"]) == 18 and not {"plan", "roster", "look", "relay", "who", "rooms"} & set(j)
     assert j["go_kernels"][:2] == list(device.GO_KERNELS) and j["go_end_to_end_covers"] and j["go_parts_covers"] and j["go_cpu_us_covers"]
     gs = j["go"]

@@ -9,16 +9,12 @@ with both sides' times and a download that grows with K alone.  No time is a pas
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
+import child_run
 from device_input_child import SPEECH, answer_of
 from nuts333_amd import device, devpath
-
-REPO = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("value", ["0", "-1", "1,0", "10,-3", "x", "1,x", "", "1,,2", "2.5"])
@@ -61,16 +57,8 @@ def test_the_timed_reads_parse_into_the_events_speak_times():
 
 @pytest.mark.gpu
 def test_devpath_input_prints_one_line_with_both_sides(built):
-    cmd = ["timeout", "-k", "10", "600", sys.executable, "-m", "nuts333_amd.devpath", "--input", "1,8,64",
-           "--reps", "10", "--warmup", "2", "--pathbench-iterations", "200000"]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=660, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("devpath --input did not finish in 660 s")
-    assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
-    lines = p.stdout.decode().strip().splitlines()
-    assert len(lines) == 1
-    j = json.loads(lines[0])
+    j = child_run.run_devpath("devpath --input", 600, "--input", "1,8,64",
+                              "--reps", "10", "--warmup", "2", "--pathbench-iterations", "200000")
     assert len(j["cases"]) == 18 and not {"plan", "roster", "per_call", "review", "speak"} & set(j)
     assert j["input_kernels"] == ["nuts_roster_parse", "nuts_roster_speak", "nuts_roster_speak_plan"]
     assert set(j["input_kernels"]) <= set(device.KERNELS) and j["input_end_to_end_covers"] and j["input_cpu_us_covers"]

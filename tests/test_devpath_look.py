@@ -9,16 +9,12 @@ is a pass condition.
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
+import child_run
 from device_look_child import look, look_user, new_room
 from nuts333_amd import device, devpath
-
-REPO = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("value", ["0", "-1", "1,0", "10,-3", "x", "1,x", "", "1,,2", "2.5"])
@@ -58,16 +54,7 @@ def test_the_strings_handed_to_the_cpu_are_the_models():
 
 @pytest.mark.gpu
 def test_devpath_look_prints_one_line_with_both_sides(built):
-    cmd = ["timeout", "-k", "10", "600", sys.executable, "-m", "nuts333_amd.devpath", "--look", "1,8,64",
-           "--reps", "5", "--warmup", "1", "--pathbench-iterations", "200000"]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=660, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("devpath --look did not finish in 660 s")
-    assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
-    lines = p.stdout.decode().strip().splitlines()
-    assert len(lines) == 1
-    j = json.loads(lines[0])
+    j = child_run.run_devpath("devpath --look", 600, "--look", "1,8,64", "--reps", "5", "--warmup", "1", "--pathbench-iterations", "200000")
     assert len(j["cases"]) == 18 and not {"plan", "roster", "per_call", "review", "speak", "input", "tell"} & set(j)
     assert j["look_kernels"] == ["nuts_roster_look", "nuts_roster_speak_plan"] and j["look_end_to_end_covers"]
     assert set(j["look_kernels"]) <= set(device.KERNELS) and "leaves the CPU's composing out" in j["look_cpu_us_covers"]

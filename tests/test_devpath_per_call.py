@@ -7,15 +7,11 @@ prints one line with the 18 single-broadcast cases and the per-call cases, and b
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
+import child_run
 from nuts333_amd import devpath
-
-REPO = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("value", ["0", "-1", "1,0", "10,-3", "x", "1,x", "", "1,,2", "2.5"])
@@ -47,16 +43,9 @@ def test_line_texts_differ_only_in_their_line_number():
 
 @pytest.mark.gpu
 def test_devpath_per_call_prints_one_line_and_amortises(built):
-    cmd = ["timeout", "-k", "10", "600", sys.executable, "-m", "nuts333_amd.devpath", "--per-call", "1,100",
-           "--reps", "10", "--warmup", "2", "--pathbench-iterations", "200000"]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=660, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("devpath --per-call did not finish in 660 s")
-    assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
-    lines = p.stdout.decode().strip().splitlines()
-    assert len(lines) == 1
-    j = json.loads(lines[0])
+    line = child_run.run_devpath_line("devpath --per-call", 600, "--per-call", "1,100",
+                                       "--reps", "10", "--warmup", "2", "--pathbench-iterations", "200000")
+    j = json.loads(line)
     assert len(j["cases"]) == 3 * 2 * 3
     assert "nuts_fanout_measure_many" in j["per_call_kernels"] and "nuts_fanout_emit_many" in j["per_call_kernels"]
     pc = j["per_call"]
@@ -72,4 +61,4 @@ def test_devpath_per_call_prints_one_line_and_amortises(built):
     for text in ("say", "shout"):
         for colour in ("off", "on", "half"):
             assert e2e[text, colour, 100] < 0.5 * e2e[text, colour, 1], (text, colour, e2e)
-    print("\n[devpath --per-call]", lines[0][:800])
+    print("\n[devpath --per-call]", line[:800])

@@ -8,15 +8,11 @@ Python than the ``roster`` case of the same command at N = 1000, K = 100, and am
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
+import child_run
 from nuts333_amd import devpath
-
-REPO = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("value", ["0", "-1", "1,0", "10,-3", "x", "1,x", "", "1,,2", "2.5"])
@@ -38,16 +34,9 @@ def test_plan_without_a_gpu_exits_2_and_measures_nothing(monkeypatch, capsys):
 
 @pytest.mark.gpu
 def test_devpath_plan_prints_one_line_and_beats_the_roster(built):
-    cmd = ["timeout", "-k", "10", "600", sys.executable, "-m", "nuts333_amd.devpath", "--roster", "100",
-           "--plan", "1,100", "--reps", "10", "--warmup", "2", "--pathbench-iterations", "200000"]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=660, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("devpath --plan did not finish in 660 s")
-    assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
-    lines = p.stdout.decode().strip().splitlines()
-    assert len(lines) == 1
-    j = json.loads(lines[0])
+    line = child_run.run_devpath_line("devpath --plan", 600, "--roster", "100",
+                                       "--plan", "1,100", "--reps", "10", "--warmup", "2", "--pathbench-iterations", "200000")
+    j = json.loads(line)
     assert "nuts_roster_plan" in j["plan_kernels"] and j["plan_end_to_end_covers"]
     pl = j["plan"]
     assert len(pl) == 36 and {(c["n"], c["text"], c["colour"], c["k"]) for c in pl} == {
@@ -76,4 +65,4 @@ def test_devpath_plan_prints_one_line_and_beats_the_roster(built):
             assert c["end_to_end_us_per_broadcast"]["median"] < r["end_to_end_us_per_broadcast"]["median"], c
             assert c["python_us_per_broadcast"]["median"] < r["python_us_per_broadcast"]["median"], c
             assert e2e[c["text"], c["colour"], 100] < 0.5 * e2e[c["text"], c["colour"], 1], (c["text"], e2e)
-    print("\n[devpath --plan]", lines[0][:800])
+    print("\n[devpath --plan]", line[:800])

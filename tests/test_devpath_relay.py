@@ -9,16 +9,12 @@ and what each figure covers.  No time is a pass condition.
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
+import child_run
 from device_relay_child import longest_text, relay_text
 from nuts333_amd import device, devpath
-
-REPO = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("value", ["0", "-1", "1,0", "10,-3", "x", "1,x", "", "1,,2", "2.5"])
@@ -57,16 +53,8 @@ def test_the_broadcasts_are_says_to_room_0_that_a_clone_can_relay():
 
 @pytest.mark.gpu
 def test_devpath_relay_prints_one_line_with_both_sides(built):
-    cmd = ["timeout", "-k", "10", "600", sys.executable, "-m", "nuts333_amd.devpath", "--relay", "1,8,64",
-           "--reps", "5", "--warmup", "1", "--pathbench-iterations", "200000"]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=660, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("devpath --relay did not finish in 660 s")
-    assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
-    lines = p.stdout.decode().strip().splitlines()
-    assert len(lines) == 1
-    j = json.loads(lines[0])
+    j = child_run.run_devpath("devpath --relay", 600, "--relay", "1,8,64",
+                              "--reps", "5", "--warmup", "1", "--pathbench-iterations", "200000")
     assert len(j["cases"]) == 18 and not {"plan", "roster", "per_call", "review", "speak", "input", "tell", "look"} & set(j)
     assert j["relay_kernels"] == ["nuts_roster_relay"] and set(j["relay_kernels"]) <= set(device.RELAY_KERNELS)
     assert "nuts_roster_plan" in j["relay_end_to_end_covers"] and "nuts_roster_speak_plan" in j["relay_end_to_end_covers"]

@@ -10,15 +10,11 @@ pass condition.
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
+import child_run
 from nuts333_amd import device, devpath
-
-REPO = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("value", ["0", "-1", "1,0", "10,-3", "x", "1,x", "", "1,,2", "2.5",
@@ -48,16 +44,8 @@ def test_review_cases_have_no_cpu_fall_back(monkeypatch):
 
 @pytest.mark.gpu
 def test_devpath_review_prints_one_line_with_both_sides(built):
-    cmd = ["timeout", "-k", "10", "600", sys.executable, "-m", "nuts333_amd.devpath", "--review", "1,8,64",
-           "--reps", "10", "--warmup", "2", "--pathbench-iterations", "200000"]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=660, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("devpath --review did not finish in 660 s")
-    assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
-    lines = p.stdout.decode().strip().splitlines()
-    assert len(lines) == 1
-    j = json.loads(lines[0])
+    j = child_run.run_devpath("devpath --review", 600, "--review", "1,8,64",
+                              "--reps", "10", "--warmup", "2", "--pathbench-iterations", "200000")
     assert len(j["cases"]) == 18 and "plan" not in j and "roster" not in j          # the other sections as they were
     assert j["review_kernels"] == ["nuts_roster_review"] and j["review_rings"] == 64
     assert "nuts_roster_record" in j["record_kernels"] and j["review_end_to_end_covers"]

@@ -10,18 +10,14 @@ condition.
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
+import child_run
 from device_look_child import look_user
 from device_rooms_child import HEAD_LINKS, HEAD_TOPICS, list_room, rooms
 from nuts333_amd import device, devpath
 from nuts333_amd.provision import SIX_ROOMS
-
-REPO = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("value", ["0", "-1", "1,0", "10,-3", "x", "1,x", "", "1,,2", "2.5"])
@@ -65,16 +61,7 @@ def test_the_strings_handed_to_the_cpu_are_the_models():
 
 @pytest.mark.gpu
 def test_devpath_rooms_prints_one_line_with_both_sides(built):
-    cmd = ["timeout", "-k", "10", "300", sys.executable, "-m", "nuts333_amd.devpath", "--rooms", "1,8",
-           "--reps", "3", "--warmup", "1", "--pathbench-iterations", "200000"]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=360, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("devpath --rooms did not finish in 360 s")
-    assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
-    lines = p.stdout.decode().strip().splitlines()
-    assert len(lines) == 1
-    j = json.loads(lines[0])
+    j = child_run.run_devpath("devpath --rooms", 300, "--rooms", "1,8", "--reps", "3", "--warmup", "1", "--pathbench-iterations", "200000")
     assert len(j["cases"]) == 18 and not {"plan", "roster", "per_call", "review", "speak", "input", "tell", "look", "relay", "who"} & set(j)
     assert j["rooms_kernels"] == ["nuts_roster_rooms_count", "nuts_roster_rooms_lines", "nuts_roster_speak_plan"] and j["rooms_end_to_end_covers"]
     assert j["rooms_kernels"][:2] == list(device.ROOMS_KERNELS) and "composing rooms()'s strings" in j["rooms_cpu_us_covers"]

@@ -8,15 +8,11 @@ amortises its per-call cost.
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
+import child_run
 from nuts333_amd import devpath
-
-REPO = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("value", ["0", "-1", "1,0", "10,-3", "x", "1,x", "", "1,,2", "2.5"])
@@ -37,16 +33,9 @@ def test_roster_without_a_gpu_exits_2_and_measures_nothing(monkeypatch, capsys):
 
 @pytest.mark.gpu
 def test_devpath_roster_prints_one_line_and_beats_per_call(built):
-    cmd = ["timeout", "-k", "10", "600", sys.executable, "-m", "nuts333_amd.devpath", "--per-call", "100",
-           "--roster", "1,100", "--reps", "10", "--warmup", "2", "--pathbench-iterations", "200000"]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=660, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("devpath --roster did not finish in 660 s")
-    assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
-    lines = p.stdout.decode().strip().splitlines()
-    assert len(lines) == 1
-    j = json.loads(lines[0])
+    line = child_run.run_devpath_line("devpath --roster", 600, "--per-call", "100",
+                                       "--roster", "1,100", "--reps", "10", "--warmup", "2", "--pathbench-iterations", "200000")
+    j = json.loads(line)
     assert "nuts_roster_measure" in j["roster_kernels"] and "nuts_roster_emit" in j["roster_kernels"]
     ro = j["roster"]
     assert {(c["n"], c["text"], c["colour"], c["k"]) for c in ro} == {
@@ -66,4 +55,4 @@ def test_devpath_roster_prints_one_line_and_beats_per_call(built):
         if c["n"] == 1000 and c["k"] == 100:
             assert c["python_us_per_broadcast"]["median"] < py[c["text"], c["colour"]], c
             assert e2e[c["text"], c["colour"], 100] < 0.5 * e2e[c["text"], c["colour"], 1], (c["text"], e2e)
-    print("\n[devpath --roster]", lines[0][:800])
+    print("\n[devpath --roster]", line[:800])

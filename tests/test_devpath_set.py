@@ -10,18 +10,14 @@ condition but their order: the kernels within the call, the call within the Pyth
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import child_run
 from device_rooms_child import list_room
 from device_set_child import set_call, set_user
 from nuts333_amd import device, devpath
-
-REPO = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("value", ["0", "-1", "1,0", "x", "", "1,,2", "2.5"])
@@ -74,16 +70,7 @@ def test_the_calls_the_command_submits_are_answered_as_it_expects():
 
 @pytest.mark.gpu
 def test_devpath_set_prints_one_line_with_the_parts_and_the_cpu(built):
-    cmd = ["timeout", "-k", "10", "300", sys.executable, "-m", "nuts333_amd.devpath", "--set", "1,8",
-           "--reps", "3", "--warmup", "1", "--pathbench-iterations", "200000"]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=360, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("devpath --set did not finish in 360 s")
-    assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
-    lines = p.stdout.decode().strip().splitlines()
-    assert len(lines) == 1
-    j = json.loads(lines[0])
+    j = child_run.run_devpath("devpath --set", 300, "--set", "1,8", "--reps", "3", "--warmup", "1", "--pathbench-iterations", "200000")
     assert len(j["cases"]) == 18 and not {"plan", "roster", "look", "relay", "who", "rooms", "go", "access", "clone"} & set(j)
     assert j["set_kernels"][:2] == list(device.SET_KERNELS) and j["set_end_to_end_covers"] and j["set_speak_covers"]
     assert j["set_cpu_us_covers"]

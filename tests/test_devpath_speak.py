@@ -10,16 +10,12 @@ from __future__ import annotations
 
 import ctypes
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
+import child_run
 from device_speak_child import model
 from nuts333_amd import device, devpath, nuts_path
-
-REPO = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("value", ["0", "-1", "1,0", "10,-3", "x", "1,x", "", "1,,2", "2.5"])
@@ -59,16 +55,8 @@ def test_the_timed_events_compose_the_say_texts():
 
 @pytest.mark.gpu
 def test_devpath_speak_prints_one_line_with_both_sides(built):
-    cmd = ["timeout", "-k", "10", "600", sys.executable, "-m", "nuts333_amd.devpath", "--speak", "1,8,64",
-           "--reps", "10", "--warmup", "2", "--pathbench-iterations", "200000"]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=660, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("devpath --speak did not finish in 660 s")
-    assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
-    lines = p.stdout.decode().strip().splitlines()
-    assert len(lines) == 1
-    j = json.loads(lines[0])
+    j = child_run.run_devpath("devpath --speak", 600, "--speak", "1,8,64",
+                              "--reps", "10", "--warmup", "2", "--pathbench-iterations", "200000")
     assert len(j["cases"]) == 18 and not {"plan", "roster", "per_call", "review"} & set(j)     # the other sections as they were
     assert j["speak_kernels"] == ["nuts_roster_speak", "nuts_roster_speak_plan"] and j["speak_end_to_end_covers"]
     assert set(j["speak_kernels"]) <= set(device.KERNELS)

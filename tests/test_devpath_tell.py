@@ -9,16 +9,12 @@ time is a pass condition.
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
+import child_run
 from device_tell_child import TOLD, new_user, private
 from nuts333_amd import device, devpath
-
-REPO = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("value", ["0", "-1", "1,0", "10,-3", "x", "1,x", "", "1,,2", "2.5"])
@@ -58,16 +54,8 @@ def test_the_timed_events_are_tells_of_the_say_bodies_to_one_target():
 
 @pytest.mark.gpu
 def test_devpath_tell_prints_one_line_with_both_sides(built):
-    cmd = ["timeout", "-k", "10", "600", sys.executable, "-m", "nuts333_amd.devpath", "--tell", "1,8,64",
-           "--reps", "10", "--warmup", "2", "--pathbench-iterations", "200000"]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=660, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("devpath --tell did not finish in 660 s")
-    assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
-    lines = p.stdout.decode().strip().splitlines()
-    assert len(lines) == 1
-    j = json.loads(lines[0])
+    j = child_run.run_devpath("devpath --tell", 600, "--tell", "1,8,64",
+                              "--reps", "10", "--warmup", "2", "--pathbench-iterations", "200000")
     assert len(j["cases"]) == 18 and not {"plan", "roster", "per_call", "review", "speak", "input"} & set(j)
     assert j["tell_kernels"] == ["nuts_roster_tell", "nuts_roster_speak_plan"] and j["tell_end_to_end_covers"]
     assert set(j["tell_kernels"]) <= set(device.KERNELS) and "estimate" in j["tell_cpu_derived_estimate_us_covers"]

@@ -8,17 +8,13 @@ GPU tier: the command, at a small repetition count, in one short-lived child und
 from __future__ import annotations
 
 import json
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
+import child_run
 from device_look_child import new_room
 from device_who_child import colour_com_count, who, who_user
 from nuts333_amd import device, devpath
-
-REPO = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("value", ["0", "-1", "1,0", "10,-3", "x", "1,x", "", "1,,2", "2.5"])
@@ -58,16 +54,7 @@ def test_the_strings_handed_to_the_cpu_are_the_models():
 
 @pytest.mark.gpu
 def test_devpath_who_prints_one_line_with_both_sides(built):
-    cmd = ["timeout", "-k", "10", "300", sys.executable, "-m", "nuts333_amd.devpath", "--who", "1,8",
-           "--reps", "3", "--warmup", "1", "--pathbench-iterations", "200000"]
-    try:
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=360, cwd=str(REPO))
-    except subprocess.TimeoutExpired:
-        pytest.fail("devpath --who did not finish in 360 s")
-    assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
-    lines = p.stdout.decode().strip().splitlines()
-    assert len(lines) == 1
-    j = json.loads(lines[0])
+    j = child_run.run_devpath("devpath --who", 300, "--who", "1,8", "--reps", "3", "--warmup", "1", "--pathbench-iterations", "200000")
     assert len(j["cases"]) == 18 and not {"plan", "roster", "per_call", "review", "speak", "input", "tell", "look", "relay"} & set(j)
     assert j["who_kernels"] == ["nuts_roster_who", "nuts_roster_who_shown", "nuts_roster_speak_plan"] and j["who_end_to_end_covers"]
     assert j["who_kernels"][:2] == list(device.WHO_KERNELS) and "composing who()'s strings" in j["who_cpu_us_covers"]
