@@ -3,13 +3,17 @@ that module shares with it: the state a sequence test owns, the fields every cal
 
 As tests/device_relay_child.py: the test module starts this script once, under ``timeout``, and asserts on the one JSON
 line it prints (``DEVICE_SEQUENCE {...}``).  Every other ``device_*_child.py`` fuzzes one call kind on a roster it has just
-built.  This one interleaves the twelve device calls of a ``device.Roster`` with ``update``, ``set_rooms``, ``set_clones``,
+built.  This one interleaves the fifteen device calls of a ``device.Roster`` with ``update``, ``set_rooms``, ``set_clones``,
 ``clear_review`` and ``clear_revtell`` on rosters that live long, two of them at once, and compares every call in full
 with the models of those children, computed from a ``State`` kept here in plain Python and never from the roster's mirrors.
-``go_many`` is the one call that changes the roster itself: the model's ``go_call`` moves the State's users as the call
-moves the roster's, and the next call of any kind meets what it left.  ``regrowth_part`` makes, for every ordered pair of
-the ten table-reading kinds, 90 of them, a small call of the one and then a large call of the other, so that the second
-finds a device allocation that was freed and made anew.
+Four calls change the roster themselves: ``go_many``, ``access_many``, ``clone_many`` and ``set_many``.  The model's
+``go_call``, ``access_call``, ``clone_call`` or ``set_call`` changes the State as the call's apply step changes the roster's
+mirrors -- the users' rooms and invitations, the rooms' access and topics, the clone records and where they lie, the flags
+and texts a user sets of itself -- and the next call of any kind meets what it left.  No call of the three breaks what the
+State promises every kind: none moves slot 0, takes its name or sets its login flag, and where a ``.destroy`` takes the
+last record the Runner makes record 0 anew with a ``set_clones`` of its own.  ``regrowth_part`` makes, for every ordered
+pair of the thirteen table-reading kinds, 156 of them, a small call of the one and then a large call of the other, so that
+the second finds a device allocation that was freed and made anew.
 
     python tests/device_sequence_child.py [--seed S] [--seed2 T]
 """
@@ -28,6 +32,12 @@ REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO))
 sys.path.insert(0, str(REPO / "tests"))
 
+from device_access_child import EFFECTIVE as ACCESS_EFFECTIVE  # noqa: E402
+from device_access_child import access_call, access_differences, access_events  # noqa: E402
+from device_access_child import settings as access_settings  # noqa: E402
+from device_clone_child import EFFECTIVE as CLONE_EFFECTIVE  # noqa: E402
+from device_clone_child import clone_call, clone_differences, clone_events, record_differences, trim  # noqa: E402
+from device_clone_child import settings as clone_settings  # noqa: E402
 from device_fanout_child import fuzz_items  # noqa: E402
 from device_go_child import MOVED, WORST_PHRASES, fuzz_events, go, go_call, go_differences, mirror_differences  # noqa: E402
 from device_input_child import answer_of, fuzz_read, input_differences  # noqa: E402
@@ -41,6 +51,10 @@ from device_relay_child import ALL, NOTHING, SWEARS, longest_text, relay_text, r
 from device_review_child import Rings, review_differences  # noqa: E402
 from device_rooms_child import rooms_differences  # noqa: E402
 from device_roster_child import Model  # noqa: E402
+from device_set_child import EFFECTIVE as SET_EFFECTIVE  # noqa: E402
+from device_set_child import fuzz_events as set_events  # noqa: E402
+from device_set_child import mirror_differences as set_mirror_differences  # noqa: E402
+from device_set_child import set_call, set_differences  # noqa: E402
 from device_speak_child import COMS as SPEECH_COMS  # noqa: E402
 from device_speak_child import EMOTE, SAY, fuzz_inpstr, model, speech_differences  # noqa: E402
 from device_tell_child import COMS as TELL_COMS  # noqa: E402
@@ -51,16 +65,20 @@ from device_who_child import new_counts as who_counts  # noqa: E402
 from nuts333_amd import device, nuts_path  # noqa: E402
 
 KINDS = ("broadcast_many", "plan_many", "speak_many", "input_many", "tell_many", "look_many", "relay_many", "who_many",
-         "rooms_many", "go_many", "review_many", "revtell_many")
+         "rooms_many", "go_many", "access_many", "clone_many", "set_many", "review_many", "revtell_many")
 #: the kinds whose kernels read the table (nd_roster_review and nd_roster_revtell neither read nor upload it)
-TABLE_KINDS = KINDS[:10]
-#: the kinds that can record into the rooms' review rings, and the two that touch the slots' revtell rings
+TABLE_KINDS = KINDS[:13]
+#: the three whose apply step changes the mirrors as go_many's does, compared and counted alike
+EVENT_KINDS = ("access_many", "clone_many", "set_many")
+#: the kinds that can record into the rooms' review rings, and the two that touch the slots' revtell rings; clone_many
+#: records only on a roster whose every look room has a ring (State.records_clones)
 RECORDING_KINDS = ("plan_many", "speak_many", "input_many", "relay_many")
+#: the ring rooms of a State and its roster unless it is made with another number; LOOK_ROOMS of them let clone_many record
 REVIEW_ROOMS, LOOK_ROOMS = 3, 5
 CAPACITIES = (1, 64, 65, 257)
 #: the roster made in the closed one's place
 REPLACEMENT_CAPACITY = 130
-STEPS_PER_ROSTER = 200
+STEPS_PER_ROSTER = 320
 #: the seeds of the device run, and of the host tier's dry run of the same streams
 SEEDS = (20262, 20263)
 #: the rooms a roomless user may be away over: State keeps a netlink that is UP on both, whatever set_rooms draws
@@ -75,7 +93,7 @@ NOWHERE = b"zzq"
 
 # ------------------------------------------------------------------ the fields, and where each lives
 TABLE_FIELDS = ("room", "login", "ignall", "ignshout", "colour")
-SPEECH_FIELDS = ("name", "vis", "muzzled", "command_mode", "level", "afk", "igntell")
+SPEECH_FIELDS = ("name", "vis", "muzzled", "command_mode", "level", "afk", "igntell", "prompt", "charmode_echo")
 WHO_FIELDS = ("last_login", "away")
 GO_FIELDS = ("in_phrase", "out_phrase", "invite_room")
 USER_FIELDS = TABLE_FIELDS + SPEECH_FIELDS + ("afk_mesg", "desc") + WHO_FIELDS + GO_FIELDS
@@ -136,14 +154,46 @@ READS = {
     # roster_speak_plan: listener_record
     "go_many": _TABLE | {"name", "vis", "level", "clones.owner", "clones.room", "in_phrase", "out_phrase", "invite_room"}
                | {f"rooms.{f}" for f in ("name", "access", "links", "netlink")},
+    # nd_roster_access -> roster_access: a.room[slot], and for the head-count of a .private every slot's room, login flag
+    # and name length; the actor's name, vis and level; wave_get_user over every slot's login flag and name, the found
+    # slot's room and its invite_room; wave_get_room over every record's name (its name length and bytes, nothing of the
+    # netlink, which the issue's table of this test left open); the actor's room's access and links, the target's access
+    # and name.  Of a clone record the owner and the room.  order_events<AccessOrderArgs>: a.room again.
+    # roster_speak_plan: listener_record
+    "access_many": _TABLE | {"name", "vis", "level", "clones.owner", "clones.room", "invite_room"}
+                   | {f"rooms.{f}" for f in ("name", "access", "links")},
+    # nd_roster_clone -> roster_clone: c.room[slot]; the actor's name, vis, level and muzzled; wave_get_user (.destroy
+    # <room> <name>) and the found owner's level and name; wave_get_room; the target's access and name; the actor's
+    # invite_room (has_room_access); the records' owner and room (the walk, create_clone's two counts, wave_head_count with
+    # every slot's room, login flag and name length).  No kernel reads hear: a .chear's value is set on the host, so "all
+    # three fields", as the issue's table expected, is one too many.  roster_speak_plan: listener_record
+    "clone_many": _TABLE | {"name", "vis", "level", "muzzled", "clones.owner", "clones.room", "invite_room", "rooms.name",
+                            "rooms.access"},
+    # nd_roster_set -> roster_set: a.room[slot] and the actor's flag byte of the table (ignall, ignshout, colour); of its 16
+    # speaker bytes the name, vis, command_mode, igntell, prompt and charmode_echo -- not the afk bit, though SetArgs'
+    # comment lists it, and neither muzzled nor the level; its description (.desc), AFK message (.afk without one) and two
+    # phrases; a.rooms only under com == kComTopic, and nd_roster_set hands it the room table only when the call holds a
+    # .topic: rooms.topic is read by such a call alone (reads_of).  roster_speak_plan: listener_record
+    "set_many": _TABLE | {"name", "vis", "command_mode", "igntell", "prompt", "charmode_echo", "afk_mesg", "desc", "in_phrase",
+                          "out_phrase", "rooms.topic"},
     # review_call: its layout steps over the table (layout_review), the kernel reads the rings alone
     "review_many": frozenset(),
     "revtell_many": frozenset(),
 }
+#: what of READS a call reads only when it holds a .topic
+TOPIC_READS = frozenset({"rooms.topic"})
+
+
+def reads_of(kind: str, topic: bool = False) -> frozenset:
+    """What one call reads: READS of its kind, and for a set_many the room's topic only when the call holds a ``.topic``."""
+    return READS[kind] if kind != "set_many" or topic else READS[kind] - TOPIC_READS
+
+
 #: a field each kind does not read, for the step "an update of only fields it does not read"
 UNREAD = {"broadcast_many": "desc", "plan_many": "name", "speak_many": "afk", "input_many": "igntell", "tell_many": "desc",
           "look_many": "muzzled", "relay_many": "level", "who_many": "rooms.access", "rooms_many": "afk", "go_many": "clones.hear",
-          "review_many": "room", "revtell_many": "colour"}
+          "access_many": "rooms.netlink", "clone_many": "clones.hear", "set_many": "afk", "review_many": "room",
+          "revtell_many": "colour"}
 
 ROOM_NAME_POOL = (b"d", b"N" * 20, b"hallway", b"~FRred/", b"wiz", b"R" * 20, b"alone", b"pair", b"e", b"/~", b"drive")
 SYLLABLES = (b"al", b"ice", b"bob", b"by", b"car", b"ol", b"dave", b"x", b"Zed", b"9", b"\xe9", b"an", b"na")
@@ -170,10 +220,11 @@ def op_for(field: str) -> tuple:
 class State:
     """The truth, in plain Python: a dict per slot, the room records, the clone records as ``[owner, room, hear]`` (owner
     None: an empty record) and both sets of rings.  Slot 0 is always a speaker in a ring room and record 0 always owned, so
-    that every call kind has somebody to call it for."""
+    that every call kind has somebody to call it for.  ``review_rooms`` is how many of the LOOK_ROOMS have a review ring,
+    here and in the roster made for it (new_roster): with all of them, clone_many may record."""
 
-    def __init__(self, rng: random.Random, cap: int, nclones: int):
-        self.cap, self.nclones = cap, nclones
+    def __init__(self, rng: random.Random, cap: int, nclones: int, review_rooms: int = REVIEW_ROOMS):
+        self.cap, self.nclones, self.review_rooms = cap, nclones, review_rooms
         self.rooms = fuzz_rooms(rng)                                     # AWAY_ROOMS have a netlink that is UP in these
         for rm in self.rooms:
             rm["inlink"] = rng.random() < 0.5
@@ -189,7 +240,7 @@ class State:
             empty = c > 0 and rng.random() < 0.15
             self.records.append([None, None, NOTHING] if empty else
                                 [rng.randrange(cap), rng.randrange(4), rng.choice((NOTHING, SWEARS, ALL, ALL))])
-        self.rings, self.tell_rings = Rings(REVIEW_ROOMS), TellRings(cap)
+        self.rings, self.tell_rings = Rings(review_rooms), TellRings(cap)
 
     def value(self, rng: random.Random, f: str, slot: int):
         if f == "room":
@@ -219,7 +270,7 @@ class State:
         if f == "invite_room":
             return rng.choice((None, None, 0, 1, 2, 3, 4))
         chance = {"ignall": 0.2, "ignshout": 0.3, "colour": 0.5, "vis": 0.7, "muzzled": 0.1, "command_mode": 0.3, "afk": 0.15,
-                  "igntell": 0.2}[f]
+                  "igntell": 0.2, "prompt": 0.3, "charmode_echo": 0.3}[f]
         return int(rng.random() < chance)
 
     def room_value(self, rng: random.Random, f: str, rm: int):
@@ -267,7 +318,28 @@ class State:
     def speakers(self, ring: bool = False) -> list:
         """The slots that may speak: a room, no login flag, a name; ``ring``: and their room has a review ring."""
         return [j for j, u in self.users.items() if u["room"] is not None and not u["login"] and u["name"]
-                and (not ring or u["room"] < REVIEW_ROOMS)]
+                and (not ring or u["room"] < self.review_rooms)]
+
+    @property
+    def records_clones(self) -> bool:
+        """clone_many(record=True) wants a ring for every look room."""
+        return self.review_rooms >= LOOK_ROOMS
+
+    def take_clones(self, clones) -> None:
+        """The records as clone_call left them (tuples, None for an empty one), back into the State's lists."""
+        self.records = [[None, None, NOTHING] if c is None else list(c) for c in clones]
+
+    def snapshot(self) -> dict:
+        """Every field's values, to be compared after a model's call (changed_since)."""
+        out = {f: [u[KEY.get(f, f)] for u in self.users.values()] for f in USER_FIELDS}
+        out.update({f"rooms.{f}": [rm[f] if f != "links" else list(rm[f]) for rm in self.rooms] for f in ROOM_FIELDS})
+        out.update({f"clones.{f}": [r[i] for r in self.records] for i, f in enumerate(CLONE_FIELDS)})
+        return out
+
+    def changed_since(self, before: dict) -> set:
+        """The fields a model's call changed: what is stale on the device after the roster's call, whatever the roster says."""
+        now = self.snapshot()
+        return {f for f in now if now[f] != before[f]}
 
     def relay_records(self) -> list:
         return [tuple(r) for r in self.records]
@@ -289,17 +361,23 @@ class State:
 class Coverage:
     """Which call kind ran directly after which update, and which was the first to touch the rings after a clear."""
 
+    #: the calls whose apply step can return a ring room to public, and so leave a review clear pending
+    CLEAR_SOURCES = {"go_many": "go", "access_many": "access", "clone_many": "clone"}
+
     def __init__(self):
         self.runs, self.after_read, self.after_unread = {}, {}, {}
         self.first_after_clear_review, self.first_after_clear_revtell = {}, {}
-        self.first_after_go_clear, self.after_go = {}, {}                # ... after a clear that a go_many left; label -> it did
+        #: ... after a clear that a go_many, an access_many or a clone_many left; label -> the source of the pending one
+        self.first_after = {source: {} for source in self.CLEAR_SOURCES.values()}
+        self.clear_from = {}
         self.last = {}                                                   # roster label -> fields of the step just before
         self.pending = {}                                                # roster label -> [review clear, revtell clear]
-        self.go_subsets = {}                                             # the kept tables a go_many passed -> calls the model agreed with
+        #: kind -> the kept tables a call of it passed -> calls the model agreed with
+        self.subsets = {kind: {} for kind in ("go_many",) + EVENT_KINDS}
 
-    def go_passed(self, subset) -> None:
+    def passed(self, kind: str, subset) -> None:
         key = "+".join(subset)
-        self.go_subsets[key] = self.go_subsets.get(key, 0) + 1
+        self.subsets[kind][key] = self.subsets[kind].get(key, 0) + 1
 
     def updated(self, label: str, fields) -> None:
         self.last[label] = set(fields)
@@ -308,36 +386,54 @@ class Coverage:
         self.last.pop(label, None)
         self.pending.setdefault(label, [False, False])[int(tell)] = True
 
-    def called(self, label: str, kind: str, review_rings: bool, revtell_rings: bool, go: dict | None = None) -> None:
+    def called(self, label: str, kind: str, review_rings: bool, revtell_rings: bool, go: dict | None = None,
+               change: dict | None = None, reads=None) -> None:
         """``review_rings`` / ``revtell_rings``: the call records into, or reads, those rings.  ``go``: what the model says a
-        go_many changed -- ``moved``, ``invites_dropped``, and ``returned``, the rooms that went back to public; one of
-        those with a ring leaves a review clear pending, as clear_review does."""
+        go_many changed -- ``moved``, ``invites_dropped``, and ``rings``, the ring rooms that went back to public; one of
+        those leaves a review clear pending, as clear_review does.  ``change``: the same of an access_many, a clone_many or a
+        set_many -- ``stale``, the fields the model's call changed, and ``rings``.  ``reads``: what this call reads, where
+        that is not READS of its kind (reads_of)."""
+        reads = READS[kind] if reads is None else reads
         per = self.runs.setdefault(label, {k: 0 for k in KINDS})
         per[kind] += 1
         last = self.last.pop(label, None)
         if last:
-            for f in last & READS[kind]:
+            for f in last & reads:
                 self.after_read[f"{kind}/{f}"] = self.after_read.get(f"{kind}/{f}", 0) + 1
-            if not last & READS[kind]:
+            if not last & reads:
                 self.after_unread[kind] = self.after_unread.get(kind, 0) + 1
         pending = self.pending.setdefault(label, [False, False])
         for i, (touches, first) in enumerate(((review_rings, self.first_after_clear_review),
                                               (revtell_rings, self.first_after_clear_revtell))):
             if touches and pending[i]:
                 first[kind] = first.get(kind, 0) + 1
-                if i == 0 and self.after_go.get(label):
-                    self.first_after_go_clear[kind] = self.first_after_go_clear.get(kind, 0) + 1
+                source = self.clear_from.get(label)
+                if i == 0 and source:
+                    self.first_after[source][kind] = self.first_after[source].get(kind, 0) + 1
                 pending[i] = False
                 if i == 0:
-                    self.after_go[label] = False
-        if go and any(rm < REVIEW_ROOMS for rm in go["returned"]):
-            pending[0] = self.after_go[label] = True
+                    self.clear_from[label] = None
+        if (go or change or {}).get("rings"):
+            pending[0], self.clear_from[label] = True, self.CLEAR_SOURCES[kind]
 
     def as_json(self) -> dict:
         return {"runs": self.runs, "after_read": self.after_read, "after_unread": self.after_unread,
                 "first_after_clear_review": self.first_after_clear_review,
-                "first_after_clear_revtell": self.first_after_clear_revtell, "first_after_go_clear": self.first_after_go_clear,
-                "go_subsets": self.go_subsets}
+                "first_after_clear_revtell": self.first_after_clear_revtell,
+                **{f"first_after_{source}_clear": first for source, first in self.first_after.items()},
+                "go_subsets": self.subsets["go_many"], **{f"{kind[:-5]}_subsets": self.subsets[kind] for kind in EVENT_KINDS}}
+
+
+#: what a run counts of access_many, clone_many and set_many, from the model's calls alone: per kind the effective and the
+#: deferred events; the rooms an access call set private or returned to public, and those a destroy returned; the records
+#: created and destroyed, the calls after which records moved down, the said lines a recording call stored; the set calls
+#: that held a .topic, and those that held none while the roster's room table was dirty
+EVENT_COUNTS = tuple(f"{kind[:-5]}_{what}" for what in ("effective", "deferred") for kind in EVENT_KINDS) + (
+    "set_private", "access_returned", "destroy_returned", "created", "destroyed", "compacted", "said_recorded", "topic_calls",
+    "topicless_dirty")
+#: set_many's kept tables in layout order; the room table is passed only by a call that holds a .topic, else kept back
+SET_TABLES = ("speech", "afk", "udesc", "go", "rooms")
+KEPT_BACK = "rooms-kept-back"
 
 
 def text_of(rng: random.Random, lo: int, hi: int) -> bytes:
@@ -351,8 +447,10 @@ def text_of(rng: random.Random, lo: int, hi: int) -> bytes:
 # ------------------------------------------------------------------ one roster, its state, and the steps
 class Runner:
     """Makes steps on ``roster`` and on ``state`` alike.  With ``check`` every call's result is compared with the models
-    (``bad`` collects what differs); without, only the calls are made, for a library that computes nothing.  ``seen`` is
-    told of every step: ``updated(label, fields)``, ``cleared(label, tell)``, ``called(label, kind, review, revtell)``."""
+    (``bad`` collects what differs); without, only the calls are made, for a library that computes nothing -- and after an
+    access_many, a clone_many or a set_many, whose apply step is the binding's own, the roster's mirrors are still compared
+    with the State.  ``seen`` is told of every step: ``updated(label, fields)``, ``cleared(label, tell)``, ``called(label,
+    kind, review, revtell)`` with what the model says a call changed."""
 
     def __init__(self, rng: random.Random, roster: device.Roster, state: State, label: str, seen, check: bool = True,
                  cpu: Cpu | None = None, pool=None, script: list | None = None):
@@ -369,7 +467,8 @@ class Runner:
                        "who": who_counts(), "rooms": {"colours": set(), "empty": 0, "single": 0, "all": 0, "uncounted": 0,
                                                       "nameless_rooms": 0, "states": set(), "inlinks": set(), "fixed": 0},
                        # from the model alone, so that a run over a library that computes nothing counts the same
-                       "moves": 0, "returned_public": 0, "deferred": 0, "invites_dropped": 0, "who_lines": 0, "rooms_listings": 0}
+                       "moves": 0, "returned_public": 0, "deferred": 0, "invites_dropped": 0, "who_lines": 0, "rooms_listings": 0,
+                       **{name: 0 for name in EVENT_COUNTS}}
         self.last_timing = {}
         #: the most bytes a call of this roster copied both ways: about what its allocation holds beside the tables
         self.largest = 0
@@ -408,13 +507,13 @@ class Runner:
                 st.rooms[rm][f] = values[f][i]
         self.seen.updated(self.label, [f"rooms.{f}" for f in fields] + ([RELAY_NAMES] if "name" in fields else []))
 
-    def _set_clones(self, fields) -> None:
+    def _set_clones(self, fields, at: int | None = None) -> None:
         """``owner`` alone gives an owned record another owner, and CLONE_HEAR_ALL with it; ``room`` or ``hear`` alone change
         an owned record; all three make a record anew, or (owner None) empty it."""
         rng, st = self.rng, self.state
         owned = [c for c, r in enumerate(st.records) if r[0] is not None]
         if set(fields) == set(CLONE_FIELDS):
-            c = rng.randrange(st.nclones)
+            c = rng.randrange(st.nclones) if at is None else at
             if c and rng.random() < 0.25:
                 self.roster.set_clones(c, owner=None)
                 st.records[c] = [None, None, NOTHING]
@@ -434,7 +533,7 @@ class Runner:
         self.seen.updated(self.label, [f"clones.{f}" for f in fields])
 
     def _clear_review(self, _=None) -> None:
-        rooms = [self.rng.randrange(REVIEW_ROOMS) for _ in range(self.rng.randint(1, 2))]
+        rooms = [self.rng.randrange(self.state.review_rooms) for _ in range(self.rng.randint(1, 2))]
         self.roster.clear_review(rooms)
         for rm in rooms:
             self.state.rings.clear(rm)
@@ -473,7 +572,7 @@ class Runner:
         for b in range(self._k(opts)):
             rm = rng.choice((0, 0, 1, 2, 3, 4, 77, None))
             if b == 0 and opts.get("record"):
-                rm = rng.randrange(REVIEW_ROOMS)
+                rm = rng.randrange(st.review_rooms)
             text = self._text(opts)
             if "longest" in opts and cloned:
                 rm = rng.choice(sorted(cloned))
@@ -486,7 +585,7 @@ class Runner:
                 csender = rng.choice(here) if here else rng.randrange(st.nclones)
             sender = None if csender is not None or rng.random() < 0.3 else rng.randrange(st.cap)
             bs.append((text, rm, sender, rng.randrange(2), rng.choice(BROADCAST_COMS)))
-            record.append(bool(want_record and rm is not None and rm < REVIEW_ROOMS and (rng.random() < 0.6 or (b == 0 and opts.get("record")))))
+            record.append(bool(want_record and rm is not None and rm < st.review_rooms and (rng.random() < 0.6 or (b == 0 and opts.get("record")))))
             csenders.append(csender)
         for text, *_ in bs:
             self.counts["longest_text"] = max(self.counts["longest_text"], len(text))
@@ -697,7 +796,7 @@ class Runner:
             return events, gatecrash, min_private
         if opts.get("returns"):
             here = st.users[0]["room"]
-            there = rng.choice([r for r in range(REVIEW_ROOMS) if r != here])
+            there = rng.choice([r for r in range(st.review_rooms) if r != here])
             self.renamed += 1                                           # names of one width: none begins another
             names = [b"here%04d" % self.renamed, b"there%04d" % self.renamed]
             self._put_rooms([here, there], {"name": names, "access": [device.PRIVATE, device.PUBLIC]})
@@ -709,7 +808,7 @@ class Runner:
         for i, (slot, inpstr, wc) in enumerate(events):
             if slot == 0:
                 res = go(st.users, st.rooms, st.go_clones(), slot, inpstr, wc, gatecrash, min_private)
-                if res["outcome"] in MOVED and res["target"] >= REVIEW_ROOMS:
+                if res["outcome"] in MOVED and res["target"] >= st.review_rooms:
                     events[i] = (slot, inpstr, 1)
         return events, gatecrash, min_private
 
@@ -738,10 +837,8 @@ class Runner:
         got = self.roster.go_many(events, gatecrash_level=gatecrash, min_private_users=min_private)
         dropped = sum(1 for j, u in st.users.items() if u["invite"] != invites[j])
         self.seen.called(self.label, "go_many", False, False,
-                         go={"moved": bool(call["movers"]), "invites_dropped": dropped, "returned": list(call["cleared"])})
-        for rm in call["cleared"]:                                      # reset_access empties the room's ring
-            if rm < REVIEW_ROOMS:
-                st.rings.clear(rm)
+                         go={"moved": bool(call["movers"]), "invites_dropped": dropped, "returned": list(call["cleared"]),
+                             "rings": self._rings_cleared(call["cleared"])})
         c = self.counts
         c["moves"] += len(call["movers"])
         c["returned_public"] += len(call["cleared"])
@@ -751,10 +848,219 @@ class Runner:
             bad = go_differences(got, call, st.users, st.rooms) + mirror_differences(self.roster, st.users, st.rooms)
             self._note("go_many", got.timing, bad)
         if not self.check or not bad:
-            self.seen.go_passed(flags)
+            self.seen.passed("go_many", flags)
+
+    # -------------------------------------------------------------- the three calls that change the roster as go_many does
+    def _rings_cleared(self, rooms) -> list:
+        """The ring rooms among those a model's call returned to public: reset_access empties their rings."""
+        rings = [rm for rm in rooms if rm < self.state.review_rooms]
+        for rm in rings:
+            self.state.rings.clear(rm)
+        return rings
+
+    def mirrors_differences(self) -> list:
+        """The roster's mirrors against the State, after the apply step of any of the three: the rooms, the invitations and
+        the rooms' access (go's comparison), the flags, descriptions, AFK messages, phrases and topics (set's), and the
+        clone records where they lie (clone's)."""
+        st = self.state
+        return (mirror_differences(self.roster, st.users, st.rooms) + set_mirror_differences(self.roster, st.users, st.rooms)
+                + record_differences(self.roster, st.go_clones()))
+
+    def event_flags(self, kind: str, topic: bool = False) -> tuple:
+        """The kept tables that the roster's flags say its next call of ``kind`` passes: go_many's four for access_many and
+        clone_many; for set_many its own, the speaker state on any of its three flags, and the room table only with a
+        ``.topic`` in the call -- without one a dirty room table is kept back."""
+        if kind != "set_many":
+            return self.go_flags()
+        r = self.roster
+        flag = {"speech": r._speech_dirty or r._private_dirty or r._set_dirty, "afk": r._afk_dirty, "udesc": r._udesc_dirty,
+                "go": r._go_dirty, "rooms": r._rooms_dirty and topic, KEPT_BACK: r._rooms_dirty and not topic}
+        return tuple(t for t in SET_TABLES + (KEPT_BACK,) if flag[t])
+
+    def _own_record(self, rm: int) -> None:
+        """The Runner's own set_clones: record 0 is slot 0's, in ``rm``."""
+        if self.state.records[0][:2] != [0, rm]:
+            self.roster.set_clones(0, owner=0, room=rm, hear=ALL)
+            self.state.records[0] = [0, rm, ALL]
+            self.seen.updated(self.label, [f"clones.{f}" for f in CLONE_FIELDS])
+
+    def _named_apart(self, rm: int, word: bytes, **more) -> bytes:
+        """The Runner's own set_rooms: a name for ``rm`` that no other room's begins with, so that get_room finds it."""
+        self.renamed += 1
+        name = b"%s%04d" % (word, self.renamed)
+        self._put_rooms([rm], {"name": [name], **{f: [v] for f, v in more.items()}})
+        return name
+
+    def _access_events(self, opts) -> tuple:
+        """The events of an access_many and the talker's three settings.  ``quiet``: a word that names no room, with
+        gatecrash_level 0, so that no ``.private <room>`` is refused for the level first: nothing can change.  ``sized``:
+        such words with a long rest.  ``returns``: slot 0's room is made PRIVATE, some slot is invited into it, and slot 0
+        says ``.public``: the call flips the access, drops the invite and leaves the room's review clear pending.
+        ``invites``, for the host tier's one-by-one cases on a roster of two slots or more: slot 0's room is made PRIVATE,
+        slot 1 gets a name of its own, another room and no invitation, and slot 0 invites it."""
+        rng, st = self.rng, self.state
+        gatecrash, min_private, ignore_mp = access_settings(rng)
+        coms = (device.COM_PUBLIC, device.COM_PRIVATE, device.COM_LETMEIN)
+        if "sized" in opts:
+            lo, hi = opts["sized"]
+            return ([(j, rng.choice(coms), (NOWHERE + b" " + text_of(rng, lo, hi))[:hi], 3) for j in self._speakers(opts, False)],
+                    0, min_private, ignore_mp)
+        if opts.get("quiet"):
+            return ([(j, rng.choice(coms), NOWHERE + rng.choice((b"", b" now")), 2) for j in self._speakers(opts, False)],
+                    0, min_private, ignore_mp)
+        if opts.get("returns"):
+            here = st.users[0]["room"]
+            self._put_rooms([here], {"access": [device.PRIVATE]})
+            self._put_users([rng.randrange(st.cap)], {"invite_room": [here]})
+            return [(0, device.COM_PUBLIC, b"", 1)], gatecrash, min_private, ignore_mp
+        if opts.get("invites"):
+            here = st.users[0]["room"]
+            self.renamed += 1
+            name = b"Guest%04d" % self.renamed
+            self._put_rooms([here], {"access": [device.PRIVATE]})
+            self._put_users([1], {"name": [name], "login": [0], "room": [(here + 1) % LOOK_ROOMS], "invite_room": [None]})
+            return [(0, device.COM_INVITE, name.lower(), 2)], gatecrash, min_private, ignore_mp
+        return access_events(rng, st.users, st.rooms, self._k(opts)), gatecrash, min_private, ignore_mp
+
+    def _access_many(self, opts) -> None:
+        st, c = self.state, self.counts
+        events, gatecrash, min_private, ignore_mp = self._access_events(opts)
+        flags = self.event_flags("access_many")                        # before the call, as go_many's
+        before = st.snapshot()
+        call = access_call(st.users, st.rooms, st.go_clones(), events, gatecrash, min_private, ignore_mp)      # the State changes
+        if self.script is not None:
+            self.script.append([(e["outcome"], e["target_room"], e["target_slot"]) for e in call["events"]])
+        got = self.roster.access_many(events, gatecrash_level=gatecrash, min_private_users=min_private, ignore_mp_level=ignore_mp)
+        self.seen.called(self.label, "access_many", False, False,
+                         change={"stale": st.changed_since(before), "rings": self._rings_cleared(call["cleared"])})
+        outcomes = [e["outcome"] for e in call["events"]]
+        c["access_effective"] += sum(o in ACCESS_EFFECTIVE for o in outcomes)
+        c["access_deferred"] += outcomes.count(device.ACCESS_DEFERRED)
+        c["set_private"] += outcomes.count(device.ACCESS_SET_PRIVATE)
+        c["access_returned"] += len(call["cleared"])
+        # the mirrors are the binding's own work: compared over a library that computes nothing too
+        bad = (access_differences(got, call) if self.check else []) + self.mirrors_differences()
+        self._note("access_many", got.timing, bad)
+        if not bad:
+            self.seen.passed("access_many", flags)
+
+    def _clone_events(self, opts) -> tuple:
+        """The events of a clone_many and the talker's three settings.  ``quiet``: a ``.csay`` or a ``.chear`` to a word that
+        names no room.  ``sized``: the same with a long rest.  ``returns``: record 0 is made slot 0's in its own room, the
+        room exactly PRIVATE under a name of its own, some slot invited into it, and slot 0 destroys that clone with more
+        users asked for than the roster holds: the room returns to public, the records behind move down.  ``record`` True:
+        the first event is a ``.csay`` of slot 0 through a record of its own, so the call has a said line to store."""
+        rng, st = self.rng, self.state
+        max_clones, gatecrash, min_private = clone_settings(rng)
+        coms = (device.COM_CSAY, device.COM_CHEAR)
+        if "sized" in opts:
+            lo, hi = opts["sized"]
+            return ([(j, rng.choice(coms), (NOWHERE + b" " + text_of(rng, lo, hi))[:hi], 3) for j in self._speakers(opts, False)],
+                    max_clones, gatecrash, min_private)
+        if opts.get("quiet"):
+            rest = {device.COM_CSAY: b" hello", device.COM_CHEAR: b" all"}
+            picked = [(j, rng.choice(coms)) for j in self._speakers(opts, False)]
+            return [(j, com, NOWHERE + rest[com], 3) for j, com in picked], max_clones, gatecrash, min_private
+        here = st.users[0]["room"]
+        if opts.get("returns"):
+            name = self._named_apart(here, b"den", access=device.PRIVATE)
+            self._own_record(here)
+            self._put_users([rng.randrange(st.cap)], {"invite_room": [here]})
+            return [(0, device.COM_DESTROY, name, 2)], max_clones, gatecrash, st.cap + st.nclones + 1
+        clones = st.go_clones()
+        events = trim(clone_events(rng, st.users, st.rooms, clones, self._k(opts)), clones)
+        if opts.get("record") and st.records_clones:
+            name = self._named_apart(here, b"stage")
+            self._own_record(here)
+            if st.users[0]["muzzled"]:
+                self._put_users([0], {"muzzled": [0]})
+            events[0] = (0, device.COM_CSAY, name + b" testing, one ~OLtwo~RS", 5)
+        return events, max_clones, gatecrash, min_private
+
+    def _clone_many(self, opts) -> None:
+        """``record`` is kept only on a roster whose every look room has a ring: the binding refuses it on the others."""
+        st, c = self.state, self.counts
+        record = bool(opts.get("record", self.rng.random() < 0.4)) and st.records_clones
+        events, max_clones, gatecrash, min_private = self._clone_events(opts)
+        flags = self.event_flags("clone_many")
+        before = st.snapshot()
+        clones = st.go_clones()
+        owned_before = [i for i, r in enumerate(clones) if r is not None]
+        call = clone_call(st.users, st.rooms, clones, events, max_clones, gatecrash, min_private, st.rings if record else None)
+        st.take_clones(clones)                                          # moved down as the user list loses its nodes
+        if self.script is not None:
+            # a deferred event may have found a record that an earlier event of the call made: no index of before the call
+            self.script.append([(e["outcome"], e["target_room"], e["target_slot"], e["record"] if isinstance(e["record"], int) else -1,
+                                 int(e["returned"])) for e in call["events"]])
+        got = self.roster.clone_many(events, max_clones=max_clones, gatecrash_level=gatecrash, min_private_users=min_private,
+                                     record=record)
+        self.seen.called(self.label, "clone_many", record, False,
+                         change={"stale": st.changed_since(before), "rings": self._rings_cleared(call["cleared"])})
+        outcomes = [e["outcome"] for e in call["events"]]
+        gone = [e["record"] for e in call["events"] if e["outcome"] == device.CLONE_DESTROYED]
+        c["clone_effective"] += sum(o in CLONE_EFFECTIVE for o in outcomes)
+        c["clone_deferred"] += outcomes.count(device.CLONE_DEFERRED)
+        c["created"] += outcomes.count(device.CLONE_CREATED)
+        c["destroyed"] += len(gone)
+        c["destroy_returned"] += len(call["cleared"])
+        c["compacted"] += bool(gone) and any(i > min(gone) and i not in gone for i in owned_before)
+        c["said_recorded"] += record * outcomes.count(device.CLONE_SAID)
+        # the mirrors are the binding's own work: compared over a library that computes nothing too
+        bad = (clone_differences(got, call) if self.check else []) + self.mirrors_differences()
+        self._note("clone_many", got.timing, bad)
+        if not bad:
+            self.seen.passed("clone_many", flags)
+        if st.records[0][0] is None:                                    # a .destroy took the last record: record 0 is owned
+            self._set_clones(CLONE_FIELDS, at=0)
+
+    def _set_events(self, opts) -> list:
+        """The events of a set_many, by slots that have a room, a name and no login flag.  ``quiet``: queries and length
+        refusals, which change nothing.  ``sized``: long descriptions, which are refused.  ``topic`` True: the first event
+        is a ``.topic`` (a query in a quiet call); False: no event is one; None: as they come."""
+        rng, st, G = self.rng, self.state, device
+        topic = opts.get("topic")
+        if "sized" in opts:
+            events = [(j, G.COM_DESC, text_of(rng, *opts["sized"]), 3) for j in self._speakers(opts, False)]
+        elif opts.get("quiet"):
+            still = ((G.COM_DESC, b"", 1), (G.COM_INPHR, b"", 1), (G.COM_OUTPHR, b"", 1), (G.COM_DESC, b"d" * (G.USER_DESC_LEN + 1), 2),
+                     (G.COM_OUTPHR, b"p" * (G.PHRASE_LEN + 1), 2), (G.COM_AFK, b"m" * (G.AFK_MESG_LEN + 1), 2))
+            events = [(j, *rng.choice(still)) for j in self._speakers(opts, False)]
+        else:
+            events = set_events(rng, st.users, st.rooms, st.speakers(), self._k(opts))
+        if topic:
+            said = (b"", 1) if "sized" in opts or opts.get("quiet") else rng.choice(((b"", 1), (b"a new topic", 4), (b"t" * 60, 2), (b"~FRred/", 2)))
+            events[0] = (events[0][0], G.COM_TOPIC, *said)
+        elif topic is not None:
+            events = [(j, G.COM_DESC, b"", 1) if com == G.COM_TOPIC else (j, com, inpstr, wc) for j, com, inpstr, wc in events]
+        return events
+
+    def _set_many(self, opts) -> None:
+        st, c = self.state, self.counts
+        events = self._set_events(opts)
+        topic = any(com == device.COM_TOPIC for _, com, _, _ in events)
+        flags = self.event_flags("set_many", topic)
+        before = st.snapshot()
+        call = set_call(st.users, st.rooms, events)
+        for slot, *_ in events:                                         # the roster keeps afk as a flag: a locked session is AFK
+            st.users[slot]["afk"] = int(bool(st.users[slot]["afk"]))
+        if self.script is not None:
+            self.script.append([(e["outcome"], e["reply2"] is not None) for e in call["events"]])
+        got = self.roster.set_many(events)
+        self.seen.called(self.label, "set_many", False, False, change={"stale": st.changed_since(before), "rings": []},
+                         reads=reads_of("set_many", topic))
+        outcomes = [e["outcome"] for e in call["events"]]
+        c["set_effective"] += sum(o in SET_EFFECTIVE for o in outcomes)
+        c["set_deferred"] += outcomes.count(device.SET_DEFERRED)
+        c["topic_calls"] += topic
+        c["topicless_dirty"] += KEPT_BACK in flags
+        # the mirrors are the binding's own work: compared over a library that computes nothing too
+        bad = (set_differences(got, call) if self.check else []) + self.mirrors_differences()
+        self._note("set_many", got.timing, bad)
+        if not bad:
+            self.seen.passed("set_many", flags)
 
     def _review_many(self, opts) -> None:
-        rooms = [self.rng.randrange(REVIEW_ROOMS) for _ in range(self.rng.randint(1, 4))]
+        rooms = [self.rng.randrange(self.state.review_rooms) for _ in range(self.rng.randint(1, 4))]
         rv = self.roster.review_many(rooms)
         self.seen.called(self.label, "review_many", True, False)
         if self.check:
@@ -770,33 +1076,49 @@ class Runner:
 
 # ------------------------------------------------------------------ the step streams
 def pair_blocks() -> list:
-    """[an update of one field, a call]: every kind after every field it reads, and after one it does not."""
-    blocks = [[op_for(f), (kind, {})] for kind in KINDS for f in sorted(READS[kind])]
+    """[an update of one field, a call]: every kind after every field it reads, and after one it does not.  A set_many
+    reads the room's topic only in a call that holds a ``.topic``: that pair forces one."""
+    blocks = [[op_for(f), (kind, {"topic": True} if kind == "set_many" and f in TOPIC_READS else {})]
+              for kind in KINDS for f in sorted(READS[kind])]
     return blocks + [[op_for(UNREAD[kind]), (kind, {})] for kind in KINDS]
 
 
 GO_TABLES = ("speech", "clones", "rooms", "go")
+#: the fields that take turns at making a kept table dirty; afk and igntell raise _private_dirty, prompt and
+#: charmode_echo _set_dirty, on either of which set_many alone uploads the speaker state
+SUBSET_FIELDS = {"speech": ("name", "vis", "level"), "clones": ("clones.owner", "clones.room", "clones.hear"),
+                 "rooms": ("rooms.access", "rooms.links", "rooms.name", "rooms.netlink"), "go": GO_FIELDS}
+SET_SUBSET_FIELDS = {"speech": ("name", "afk", "prompt", "vis", "igntell", "charmode_echo", "command_mode"), "afk": ("afk_mesg",),
+                     "udesc": ("desc",), "go": GO_FIELDS}
 
 
 def subset_blocks() -> list:
-    """[a go_many that moves nobody and leaves its four kept tables clean, an update of one field of each table of the
-    subset, a go_many]: every subset of the four is the one passed, the fields taking turns."""
-    fields = {"speech": ("name", "vis", "level"), "clones": ("clones.owner", "clones.room", "clones.hear"),
-              "rooms": ("rooms.access", "rooms.links", "rooms.name", "rooms.netlink"), "go": GO_FIELDS}
+    """[a call that changes nothing and leaves its kept tables clean, an update of one field of each table of the subset,
+    a call]: for go_many, access_many and clone_many every subset of their four tables is the one passed, the fields taking
+    turns.  For set_many every subset of its first four, three times: with the room table clean, with it dirty and a
+    ``.topic`` in the call, which passes it, and with it dirty and no ``.topic``, which keeps it back."""
     blocks = []
+    for kind in ("go_many", "access_many", "clone_many"):
+        for i in range(16):
+            subset = [t for b, t in enumerate(GO_TABLES) if i >> b & 1]
+            blocks.append([(kind, {"quiet": True})] + [op_for(SUBSET_FIELDS[t][i % len(SUBSET_FIELDS[t])]) for t in subset] + [(kind, {})])
     for i in range(16):
-        subset = [t for b, t in enumerate(GO_TABLES) if i >> b & 1]
-        blocks.append([("go_many", {"quiet": True})] + [op_for(fields[t][i % len(fields[t])]) for t in subset] + [("go_many", {})])
+        subset = [t for b, t in enumerate(SET_TABLES[:4]) if i >> b & 1]
+        dirty = [op_for(SET_SUBSET_FIELDS[t][i % len(SET_SUBSET_FIELDS[t])]) for t in subset]
+        for topic in (None, True, False):
+            rooms = [] if topic is None else [op_for("rooms.topic" if i % 2 else "rooms.mesg_cnt")]
+            blocks.append([("set_many", {"quiet": True, "topic": True})] + dirty + rooms + [("set_many", {"topic": bool(topic)})])
     return blocks
 
 
 def clear_blocks() -> list:
     """[a clear, the first call to touch those rings after it]; the clear is clear_review's, clear_revtell's, or what a
-    go_many leaves that returns a ring room to public."""
-    return ([[("clear_review",), (kind, {"record": True})] for kind in RECORDING_KINDS] + [[("clear_review",), ("review_many", {})]]
-            + [[("clear_revtell",), ("tell_many", {"record": True})], [("clear_revtell",), ("revtell_many", {})]]
-            + [[("go_many", {"returns": True}), (kind, {"record": True})] for kind in RECORDING_KINDS]
-            + [[("go_many", {"returns": True}), ("review_many", {})]])
+    go_many, an access_many or a clone_many leaves that returns a ring room to public.  clone_many is among the first only
+    on a roster where it may record; on the others it passes the clear by."""
+    sources = [("clear_review",)] + [(kind, {"returns": True}) for kind in ("go_many", "access_many", "clone_many")]
+    firsts = [(kind, {"record": True}) for kind in RECORDING_KINDS + ("clone_many",)] + [("review_many", {})]
+    return ([[source, first] for source in sources for first in firsts]
+            + [[("clear_revtell",), ("tell_many", {"record": True})], [("clear_revtell",), ("revtell_many", {})]])
 
 
 def random_op(rng: random.Random) -> tuple:
@@ -824,14 +1146,16 @@ def roster_steps(rng: random.Random, blocks: list, steps: int, each: int = 8) ->
     return [op for b in blocks for op in b]
 
 
-def new_roster(cap: int, nclones: int) -> device.Roster:
-    return device.Roster(cap, review_rooms=REVIEW_ROOMS, revtell=True, look_rooms=LOOK_ROOMS, clones=nclones)
+def new_roster(cap: int, nclones: int, review_rooms: int = REVIEW_ROOMS) -> device.Roster:
+    return device.Roster(cap, review_rooms=review_rooms, revtell=True, look_rooms=LOOK_ROOMS, clones=nclones)
 
 
 # ------------------------------------------------------------------ the parts of the device run
 def sequence_part(seed: int, cov: Coverage, check: bool = True, script: list | None = None) -> dict:
     """One roster for each capacity; 1 and 64 on their own, then 65 and 257 live at once, their steps alternating; when
     the 65-slot one has made its steps it is closed and a roster of another capacity takes its handle and its turn.
+    That one has a review ring for every look room, so clone_many records there and takes the pending review clears; the
+    other four keep three ring rooms and the paths for rooms without a ring.
     ``check=False`` with a ``script``: over a library that computes nothing, for what the stream alone reaches."""
     rng = random.Random(seed)
     cpu = Cpu()
@@ -844,9 +1168,9 @@ def sequence_part(seed: int, cov: Coverage, check: bool = True, script: list | N
         dealt[i % 6].append(b)
     out = {"rosters": [], "n_bad": 0, "first_bad": [], "steps": 0, "counts": {}}
 
-    def make(cap, nclones, share, steps):
-        state = State(rng, cap, nclones)
-        roster = new_roster(cap, nclones)
+    def make(cap, nclones, share, steps, review_rooms=REVIEW_ROOMS):
+        state = State(rng, cap, nclones, review_rooms)
+        roster = new_roster(cap, nclones, review_rooms)
         state.seat(roster)
         runner = Runner(rng, roster, state, f"{seed}:{cap}/{nclones}", cov, check=check, cpu=cpu, pool=pool, script=script)
         return runner, roster_steps(rng, share, steps)
@@ -862,7 +1186,7 @@ def sequence_part(seed: int, cov: Coverage, check: bool = True, script: list | N
         for name, n in (("recorded", c["recorded"]), ("told", c["told"]), ("relays", c["relays"]), ("clone_senders", c["clone_senders"]),
                         ("empty_texts", c["empty_texts"]), ("lines_compared", c["review"]["lines_compared"]), ("moves", c["moves"]),
                         ("returned_public", c["returned_public"]), ("deferred", c["deferred"]), ("invites_dropped", c["invites_dropped"]),
-                        ("who_lines", c["who_lines"]), ("rooms_listings", c["rooms_listings"])):
+                        ("who_lines", c["who_lines"]), ("rooms_listings", c["rooms_listings"]), *((name, c[name]) for name in EVENT_COUNTS)):
             out["counts"][name] = out["counts"].get(name, 0) + n
         out["counts"]["longest_text"] = max(out["counts"].get("longest_text", 0), c["longest_text"])
 
@@ -881,7 +1205,7 @@ def sequence_part(seed: int, cov: Coverage, check: bool = True, script: list | N
         a.step(op)
     handle = a.roster._handle                                           # mid-run: the 257-slot roster goes on
     done(a)
-    c, c_steps = make(REPLACEMENT_CAPACITY, clones[1], dealt[5], STEPS_PER_ROSTER)
+    c, c_steps = make(REPLACEMENT_CAPACITY, clones[1], dealt[5], STEPS_PER_ROSTER, LOOK_ROOMS)    # clone_many may record here
     rest = b_steps[n:]
     for i in range(max(len(c_steps), len(rest))):
         if i < len(c_steps):
@@ -896,10 +1220,12 @@ def sequence_part(seed: int, cov: Coverage, check: bool = True, script: list | N
 
 
 def regrowth_part(seed: int) -> dict:
-    """Every ordered pair (A, B) of the ten table-reading kinds on a fresh 65-slot roster whose every mirror has been
+    """Every ordered pair (A, B) of the thirteen table-reading kinds on a fresh 65-slot roster whose every mirror has been
     uploaded: a tiny A, then a big B, twice.  The first B finds the allocation made anew and uploads the table from the
     pinned mirror, though the roster passes none; its repeat does not.  A big B is 16 long texts; of go_many 16 long lines
-    that move nobody, or its repeat would be another call and find the table dirty; of who_many and rooms_many, which take
+    that move nobody, or its repeat would be another call and find the table dirty; of access_many, clone_many and set_many
+    for the same reason 16 long lines that change nothing (a word that names no room, a description too long); of who_many
+    and rooms_many, which take
     no text, many lookers.  A pair that does not regrow doubles K."""
     rng = random.Random(seed)
     cap, nclones = 65, 65
@@ -912,7 +1238,7 @@ def regrowth_part(seed: int) -> dict:
         roster = new_roster(cap, nclones)
         state.seat(roster)
         runner = Runner(rng, roster, state, "regrowth", cov, cpu=cpu, pool=[b"hello"])
-        for kind in ("tell_many", "look_many", "relay_many", "input_many", "who_many", "go_many"):     # every mirror goes up once
+        for kind in ("tell_many", "look_many", "relay_many", "input_many", "who_many", "go_many") + EVENT_KINDS:   # every mirror goes up once
             runner.step((kind, tiny))
         return runner
 
