@@ -1097,7 +1097,9 @@ class Settings:
     ``reply.colour_bits``, which hold the flags before the call.
 
     Delivery, per client: the events in call order, and of one event ``reply``, ``reply2``, ``here`` (the reference's order
-    of writes).  A roster with clone records passes the here lines through ``relay_many``."""
+    of writes).  A roster with clone records passes the here lines through ``relay_many``; that of a SET_IGNALL_ON with
+    ``ignall={actor: 0}`` and that of a SET_IGNALL_OFF with ``ignall={actor: 1}``, the flag as it was while the reference
+    wrote the line (nuts333.c:4466-4476)."""
     outcome: np.ndarray           # int8 [K]
     reply: Plan
     reply2: Plan
@@ -3327,7 +3329,8 @@ class Roster:
 
         Out of scope: the prompt; the return from AFK (nuts333.c:180-203), and the session lock itself, which stay with
         the caller; remote users and "home execution"; the relay of the ``here`` lines to clones' owners -- the caller
-        passes them to :meth:`relay_many`, as after :meth:`access_many`; the commands' level check, which
+        passes them to :meth:`relay_many`, as after :meth:`access_many`, and an ``.ignall``'s with ``ignall={actor: the
+        flag as it was}``, because ``toggle_ignall`` flips the flag behind its line and this call has applied the flip; the commands' level check, which
         :meth:`input_many` has already made."""
         self._check_open()
         inps, text_off, lens, slots, coms, wcs = self._prepare_set(events)
@@ -3479,13 +3482,35 @@ class Roster:
         names[:, :ROOM_NAME_LEN + 1] = self._room_rec[:, :ROOM_NAME_LEN + 1]
         return packed, csender, names
 
-    def relay_many(self, broadcasts, record=None, clone_sender=None) -> Relay:
+    def _table_with_ignall(self, ignall) -> np.ndarray:
+        """A copy of the table mirror with the ``ignall`` flags of ``relay_many(ignall=)``, checked."""
+        if not isinstance(ignall, dict) or not ignall:
+            raise ValueError(f"ignall must be None or a non-empty dict of slot -> 0/1, not {ignall!r}")
+        table = self._table.copy()
+        flags = table[4 * self.capacity:]
+        for slot, v in ignall.items():
+            try:
+                j, on = self._slot(slot), _flag("its flag", v)
+            except ValueError as e:
+                raise ValueError(f"ignall: {e}") from None
+            flags[j] = (int(flags[j]) & (0xFF ^ ROSTER_FLAGS["ignall"])) | (ROSTER_FLAGS["ignall"] if on else 0)
+        return table
+
+    def relay_many(self, broadcasts, record=None, clone_sender=None, ignall=None) -> Relay:
         """``write_room_except`` whole for K broadcasts to a roster with clone records, in one device call
         (nuts333.c:1401-1429).  ``broadcasts`` and ``record`` are what :meth:`plan_many` takes, checked by the same
         rules; ``clone_sender`` is None, or K entries each None or the clone record that is ``user`` in
         ``write_room_except(rm, str, user)`` (``clone_switch``, nuts333.c:7283) -- that broadcast's ``sender`` must then
         be None.  Returns a :class:`Relay`: its ``plan`` equals ``plan_many(broadcasts, record)`` field by field, and
         the rings end up as after it.
+
+        ``ignall`` is None, or a dict of slot -> 0/1: the whole call, predicate and relay, runs over the roster with these
+        slots' ``ignall`` flags as given instead of the roster's.  It is for the one line the reference writes while a
+        flag is not yet what an earlier call has made it: ``toggle_ignall`` sends its line and flips the flag last
+        (nuts333.c:4466-4476), :meth:`set_many` has applied the flip, so the caller relays the ``here`` line of a
+        SET_IGNALL_ON with ``ignall={actor: 0}`` and that of a SET_IGNALL_OFF with ``ignall={actor: 1}`` -- the actor's own
+        clone in its room relays "is now ignoring everyone" to it and not "is listening again".  The roster's mirrors do
+        not change; such a call uploads its own copy of the table and leaves the table to be uploaded again.
 
         A clone standing in room ``rm`` does not receive a broadcast, it sends ``"~FT[ <room name> ]:~RS " + text`` to
         its owner.  Clone record ``c`` relays broadcast ``k`` iff ``rm`` is not None and the record has an owner; its
@@ -3516,6 +3541,7 @@ class Roster:
         self._check_open()
         packed, csender, names = self._prepare_relay(broadcasts, record, clone_sender)
         text, text_off, lens, rm, sender, flags, coms = packed
+        table = self._table if ignall is None else self._table_with_ignall(ignall)
         recording = bool((flags & _RECORD_BIT).any())
         new_names = self._relay_names is None or not np.array_equal(names, self._relay_names)
         lib = _load()
@@ -3532,7 +3558,7 @@ class Roster:
         tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
         t = _RosterTiming()
         args = (handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(rm), _ptr(sender), _ptr(flags),
-                _ptr(coms), _ptr(csender), _ptr(self._table) if self._dirty else None,
+                _ptr(coms), _ptr(csender), _ptr(table) if self._dirty or ignall is not None else None,
                 _ptr(self._clones) if self._clones_dirty else None, _ptr(names) if new_names else None, _ptr(bits),
                 _ptr(vn), _ptr(vw), _ptr(vwsz), _ptr(var), _ptr(rbits), _ptr(rlen), _ptr(rvn), _ptr(rvw), _ptr(rvwsz),
                 _ptr(rtext), _ptr(rvar), ctypes.byref(t))
@@ -3542,7 +3568,7 @@ class Roster:
         else:
             rc = lib.nd_roster_relay(*args)
         _check(rc, "device relay failed")
-        self._dirty = self._clones_dirty = False
+        self._dirty, self._clones_dirty = ignall is not None, False     # a table with other flags is on the device
         self._relay_names = names
         if recording:
             self._clear_sent()

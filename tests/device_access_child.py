@@ -473,7 +473,8 @@ class AccessReplayer(GoReplayer):
     """The GoReplayer with ``.public``, ``.private``, ``.letmein`` and ``.invite`` answered: the outcome and the texts come
     from the backend's ``access``, nothing of them from the recording, and the actor's own bytes are compared.  The two
     room lines reach the clones' owners as after ``go_many``: composed here from the clone records, as ``relay_many``
-    relays them."""
+    relays them.  A line that is none of these four, nor the GoReplayer's, is ``sr.Replayer``'s, which answers it through the
+    Roster's own calls."""
 
     def __init__(self, doc: dict, backend_class=AccessModelBackend, layout: str = sr.COMPACT):
         super().__init__(doc, backend_class, layout)

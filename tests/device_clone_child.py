@@ -37,7 +37,7 @@ from nuts333_amd import device, nuts_path  # noqa: E402
 
 G = device
 SESSIONS = ("reference_only/clone.json", "clones.json", "reference_only/access.json") + tuple(
-    f"reference_only/replay_{seed}.json" for seed in sr.SEEDS)
+    f"reference_only/replay_{seed}.json" for seed in sr.FIRST_SEEDS)
 COMS = {"clone": G.COM_CLONE, "destroy": G.COM_DESTROY, "csay": G.COM_CSAY, "chear": G.COM_CHEAR}
 EFFECTIVE = (G.CLONE_HEAR_NOTHING, G.CLONE_HEAR_SWEARS, G.CLONE_HEAR_ALL, G.CLONE_CREATED, G.CLONE_DESTROYED, G.CLONE_SAID)
 KINDS = ("here", "there", "reset", "said", "reply", "notice")           # the rows of Clone.text_sizes
@@ -540,7 +540,8 @@ class CloneReplayer(AccessReplayer):
     from the backend's ``clone``, nothing of them from the recording, and the actor's own bytes are compared.  The room
     lines reach the clones' owners through the backend's ``relay``, over the records as the call left them: a new clone
     relays the two lines of its own creation and a destroyed one relays nothing, and ``relay``'s plan of each line must
-    equal the call's.  ``.muzzle`` and ``.unmuzzle`` change the state a ``.csay`` reads."""
+    equal the call's.  ``.muzzle`` and ``.unmuzzle`` change the state a ``.csay`` reads.  A line that is none of these, nor the
+    AccessReplayer's, is ``sr.Replayer``'s, which answers it through the Roster's own calls."""
     STATE_ONLY = AccessReplayer.STATE_ONLY + ("muzzle", "unmuzzle")
 
     def __init__(self, doc: dict, backend_class=CloneModelBackend, layout: str = sr.COMPACT):

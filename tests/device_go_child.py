@@ -33,7 +33,7 @@ from event_checks import digest as digest_of  # noqa: E402
 from nuts333_amd import device, nuts_path  # noqa: E402
 
 SESSIONS = ("reference_only/go.json", "rooms.json", "reference_only/rmst.json", "reference_only/who.json", "clones.json") + tuple(
-    f"reference_only/replay_{seed}.json" for seed in sr.SEEDS)
+    f"reference_only/replay_{seed}.json" for seed in sr.FIRST_SEEDS)
 WIZ, ARCH = 2, 3
 MOVED = (device.GO_WALKED, device.GO_TELEPORTED, device.GO_UNSEEN)
 GO_WHERE, NOSUCHROOM = b"Go where?\n", b"There is no such room.\n"                       # c:4313, nuts333.h:145
@@ -603,7 +603,7 @@ class GoModelBackend(sr.ModelBackend):
                 "plans": {kind: {"admitted": res["plans"][kind], "chunks": sr.both(res[kind])} for kind in res["plans"]}}
 
 
-class GoDeviceBackend(sr.DeviceBackend):
+class GoDeviceBackend(sr.UploadingBackend):
     """One roster for the session; ``sync`` also uploads the phrases, the invites and the rooms' access."""
 
     def __init__(self, st):
@@ -650,19 +650,15 @@ class GoDeviceBackend(sr.DeviceBackend):
 class GoReplayer(sr.Replayer):
     """The Replayer with ``.go`` answered: the outcome, the texts and the look come from the backend's ``go``, nothing of
     them from the recording, and the mover's own bytes are compared.  ``.private``, ``.public`` and ``.invite`` are
-    tracked from the reference's format strings; a command the Replayer does not know -- the sessions of the other
-    calls' tests hold some -- changes the state where a later ``.go`` could see it and is compared with nothing."""
+    composed here from the reference's format strings, where the actor's bytes say that they took effect; the commands
+    of STATE_ONLY -- the sessions of the other calls' tests hold some -- change the state where a later ``.go`` could
+    see it and are compared with nothing.  Every other line is ``sr.Replayer``'s: it answers ``.clone``, ``.ignall``
+    and the rest through the Roster's own event calls, and ``UploadingBackend`` then uploads the same state again."""
     STATE_ONLY = ("topic", "write", "rmst", "rmsn", "afk", "myclones", "switch", "inphr", "outphr", "desc")
 
     def __init__(self, doc: dict, backend_class=GoModelBackend, layout: str = sr.COMPACT):
-        self.doc = doc
-        self.st = GoState(doc, layout)
-        self.backend = backend_class(self.st)
-        self.frozen = False
-        self.recorded = {}
-        self.res = {"answered": 0, "tracked": 0, "comparisons": 0, "plan_checks": 0, "plan_disagreements": 0, "mismatches": [],
-                    "commands": {}, "coverage": {k: 0 for k in sr.COVERAGE}, "capacity": self.st.capacity, "slots": [],
-                    "go": 0, "go_outcomes": {}, "state_only": 0, "go_not_dispatched": 0}
+        self._begin(doc, GoState(doc, layout), backend_class)
+        self.res.update(go=0, go_outcomes={}, state_only=0, go_not_dispatched=0)
 
     def _go(self, u: dict, inp: dict, out: dict) -> None:
         st, slot, com = self.st, u["slot"], inp["com"]

@@ -2,11 +2,13 @@
 
 As tests/device_who_child.py: the test module starts this script once, under ``timeout``, and asserts on the one JSON line
 it prints (``DEVICE_REPLAY {...}``).  Every session of tests/golden/reference_only/replay_*.json is replayed by
-tests/session_replay.py through ``DeviceBackend`` -- one ``Roster`` per session, updated with what changed and no more --
-twice: with the users seated next to each other in an 8-slot roster, and with the users seated at slots 0, 63, 64, 255, 256
+tests/session_replay.py through ``DeviceBackend`` -- one ``Roster`` per session, seated at the logins and left to keep its own
+state after them -- twice: with the users seated next to each other in an 8-slot roster, and with the users seated at slots 0, 63, 64, 255, 256
 and between them in a 257-slot one.  (Both rosters have one more slot per possible clone behind those: look() lists the
-clones.)  The result holds, per session and layout, the counts of answered steps, tracked steps, client comparisons and
-plan comparisons between ``input_many`` and ``relay_many``, the Roster calls made, and every mismatch.
+clones.)  The result holds, per session and layout, the counts of answered steps, client comparisons, comparisons of the
+roster's mirrors with the replayer's state and plan comparisons between ``relay_many`` and the call that composed a line, the
+Roster calls made, the ``update`` / ``set_clones`` / ``set_rooms`` calls the backend made after the logins by what they
+addressed, and every mismatch -- a mirror that differs is one.
 
     python tests/device_replay_child.py [--out FILE]
 """
@@ -25,7 +27,8 @@ sys.path.insert(0, str(REPO / "tests"))
 from nuts333_amd import device  # noqa: E402
 from session_replay import COMPACT, SEEDS, SPREAD, DeviceBackend, load, replay  # noqa: E402
 
-KEPT = ("answered", "tracked", "comparisons", "plan_checks", "plan_disagreements", "capacity", "slots", "calls", "commands")
+KEPT = ("answered", "tracked", "comparisons", "plan_checks", "plan_disagreements", "capacity", "slots", "calls", "commands",
+        "mirror_checks", "uploads")
 
 
 def main() -> int:

@@ -501,7 +501,7 @@ class SetModelBackend(sr.ModelBackend):
 MORE_FIELDS = ("afk", "afk_mesg", "in_phrase", "out_phrase", "prompt", "charmode_echo")
 
 
-class SetDeviceBackend(sr.DeviceBackend):
+class SetDeviceBackend(sr.UploadingBackend):
     """One roster for the session.  After a ``set_many`` the replayer's state takes the event's changes and is marked as
     sent: nothing of them is uploaded by ``sync``, so a later call sees what the binding applied."""
 
@@ -542,17 +542,14 @@ class SetDeviceBackend(sr.DeviceBackend):
 class SetReplayer(sr.Replayer):
     """The Replayer with the fourteen commands answered: the outcome and the texts come from the backend's ``set``, nothing
     of them from the recording, and the actor's own bytes are compared.  The here lines reach the clones' owners as after
-    ``access_many``: composed here from the clone records, as ``relay_many`` relays them."""
+    ``access_many``: composed here from the clone records, as ``relay_many`` relays them -- over the flags as the call
+    left them, which is right for every line of these sessions; ``sr.Replayer`` delivers an ``.ignall`` next to a clone of
+    the actor's own, from ``Settings.ignall_relays``.  Every other line is ``sr.Replayer``'s, which answers ``.go``,
+    ``.clone`` and the rest through the Roster's own event calls; ``UploadingBackend`` then uploads the same state again."""
 
     def __init__(self, doc: dict, backend_class=SetModelBackend, layout: str = sr.COMPACT):
-        self.doc = doc
-        self.st = SetState(doc, layout)
-        self.backend = backend_class(self.st)
-        self.frozen = False
-        self.recorded = {}
-        self.res = {"answered": 0, "tracked": 0, "comparisons": 0, "plan_checks": 0, "plan_disagreements": 0, "mismatches": [],
-                    "commands": {}, "coverage": {k: 0 for k in sr.COVERAGE}, "capacity": self.st.capacity, "slots": [],
-                    "set": 0, "set_outcomes": {}, "set_lines": 0, "returns": 0}
+        self._begin(doc, SetState(doc, layout), backend_class)
+        self.res.update(set=0, set_outcomes={}, set_lines=0, returns=0)
 
     def _compare(self, index: int, step: dict, out: dict, recv: dict) -> None:
         for actor, j in self.st.seats.items():
@@ -657,7 +654,7 @@ class SetReplayer(sr.Replayer):
         return res
 
 
-SESSIONS = ("set",) + tuple(f"replay_{seed}" for seed in sr.SEEDS)
+SESSIONS = ("set",) + tuple(f"replay_{seed}" for seed in sr.FIRST_SEEDS)
 
 
 def load(name: str) -> dict:

@@ -9,18 +9,32 @@ As make_who_golden.py: the scenarios are registered in this process only and rec
 provisioning, the input lines and, per step, the bytes each client received --, ``long_date(1)`` in who()'s header is
 replaced by the literal ``DATE``, and nothing is written unless the -O2 build, the -O0 build and a second run agree.
 
+The sessions of ``session_replay.FIRST_SEEDS`` draw from the first command profile, described next.  Every other seed draws
+from the second (below): the first profile's draws are untouched by it, so the first sessions regenerate byte for byte.
+
 A session: four to six accounts of the levels NEW .. GOD with both colour bits, in every second session one in command
 mode, in every fourth one muzzled, descriptions with ``~FBBM`` among them; ``max_clones`` 2; ``ban_swearing`` in every
 second session.  Everybody logs in, then 60 line steps follow, drawn from the commands tests/session_replay.py answers
 (speech in all its forms, tell and pemote at full names, prefixes, substrings, ``Nobody`` and oneself, ``.look``,
-``.review`` with and without a room, ``.revtell``, ``.who``, and what ends in ``Unknown command.``) and from those it
-tracks (``.go``, the toggles, ``.vis`` / ``.invis``, ``.clone``, ``.destroy``, ``.chear``, ``.csay``).  The texts are
+``.review`` with and without a room, ``.revtell``, ``.who``, what ends in ``Unknown command.``, ``.go``, the toggles,
+``.vis`` / ``.invis``, ``.clone``, ``.destroy``, ``.chear``, ``.csay``).  The texts are
 ``random_text`` of tests/test_differential_fuzz.py.  The generator keeps a guess of where everybody's clones stand only
 to aim ``.chear``, ``.csay`` and ``.destroy`` at them more often than chance would; what happened is the reference's word.
 
+The second profile takes four steps in ten from ``second_line`` and the rest from the mix above: ``.public``, ``.private``,
+``.letmein <room>`` and ``.invite <name>``, aimed by a guess of who stands where and which room is private; ``.rmst`` and
+``.rmsn``; ``.desc``, ``.topic``, ``.inphr`` and ``.outphr`` with a text, without one and with one that is too long;
+``.vis`` / ``.invis`` with a ``.go`` by the same user behind it; ``.go`` by a WIZ or above to a room that is not adjoined;
+``.ignall`` twice by the same user, next to a clone of its own; ``.destroy <room> <name>`` by a GOD at an ARCH's clone; an
+``.invite`` with the invited user's ``.go`` behind it; a third ``.clone``; once a session, a USER who walks to the corridor and
+may not make it private alone, may with a second user there, says a line, and invites a third who was refused at the door;
+and five lines that leave the clones' list order
+different from their creation order, with a ``.look`` at them: a clone destroyed in front of another owner's, and a new one
+created in that one's room.
+
 Before it writes, the script replays every session through the CPU models (``session_replay.replay``) and asserts the
 coverage tests/test_device_replay.py asserts again from the fixtures: every property of ``session_replay.COVERAGE`` is met
-somewhere in the set, every session has an answered share of 0.6 or more, and all five levels, both colour bits, a command
+somewhere in the set, every step of every session is answered, and all five levels, both colour bits, a command
 mode and a muzzled account are present.  ``--try`` records the given seeds without writing and prints what each covers:
 that is how ``session_replay.SEEDS`` was chosen.
 """
@@ -49,6 +63,12 @@ KEYS = "abcdef"
 ROOMS = ["drive", "hallway", "corridor", "lounge", "wizroom", "nowhere", "ha", "dr", "w", "co"]
 DESCS = ["is here", "~FRis red", "is a plain user", "~OLbold~RS one", "~FBKcounts two"]
 LINE_STEPS = 60
+LINKS = {r.name: [x.name for x in pv.DEFAULT_ROOMS if x.label in r.links] for r in pv.DEFAULT_ROOMS}
+SETTABLE = [r.name for r in pv.DEFAULT_ROOMS if r.access in ("", "BOTH")]          # the rooms .private and .public may change
+# the texts the second profile sets: each ends in a plain word, which session_replay.last_word looks for in a listing
+TEXTS = {".desc": ["~FGgreen~RS thumbs", "hums along", "is ~OLbold~RS today"], ".topic": ["the ~FRred~RS door", "nothing much", "who took the ~FYlast~RS biscuit"],
+         ".inphr": ["tiptoes in", "~FMslides~RS over"], ".outphr": ["tiptoes off", "~FMslides~RS away"]}
+TOO_LONG = "long " * 20                                                              # past USER_DESC_LEN, PHRASE_LEN and TOPIC_LEN
 LONGEST_LINE = 700          # a broadcast and its relay prefix must fit the reference's text2[ARR_SIZE] (nuts333.c:1407)
 OUT_DIR = Path(__file__).resolve().parent / "reference_only"
 SIZE_LIMIT = (Path(__file__).resolve().parent / "vectors" / "transducer.json").stat().st_size
@@ -77,6 +97,98 @@ def make_script(seed: int):
     wizards = [i for i, a in enumerate(accounts) if a.level >= 3]
     guess = {i: [] for i in range(n)}               # where i's clones probably stand
     steps = []
+    second = seed not in session_replay.FIRST_SEEDS
+    where, private, asked = {i: "drive" for i in range(n)}, set(), set()     # the second profile's guesses: rooms, access, who typed .ignall
+    partied, hidden = [], set()                     # who made the corridor private with company; who is probably invisible
+
+    def went(i: int, room: str) -> str:
+        """``.go room`` by i, and the guess of where that leaves it."""
+        level = accounts[i].level
+        if room in LINKS and (room in LINKS[where[i]] or level >= 2) and (room not in private or level >= 3) and (room != "wizroom" or level >= 2):
+            where[i] = room
+        return ".go " + room
+
+    def second_line(i: int) -> list:
+        """The next lines of the second profile, one to a dozen: a line is user i's, or ``(user, line)``."""
+        here, level, x = where[i], accounts[i].level, rng.random()
+        if x < 0.28:                                # moves: along a link towards the settable rooms, anywhere, nowhere
+            y = rng.random()
+            room = (rng.choice([r for r in LINKS[here] if r != "drive"] or LINKS[here]) if y < 0.55 else rng.choice(SETTABLE) if y < 0.8
+                    else here if y < 0.9 else rng.choice(ROOMS))
+            lines = []
+            if level >= 3 and rng.random() < 0.35:
+                turn = rng.random() < 0.8           # mostly the one of the two that takes effect
+                lines = [".vis" if (i in hidden) == turn else ".invis"]
+                if turn:
+                    hidden.symmetric_difference_update({i})
+            return lines + [went(i, room)]
+        if x < 0.56:                                # access
+            y = rng.random()
+            locked = [r for r in LINKS[here] if r in private]
+            users = [k for k in range(n) if accounts[k].level == 1]
+            guests = [k for k in range(n) if accounts[k].level in (1, 2) and k not in users[:1]]
+            if "corridor" not in private and not partied and users and guests and y < 0.5:
+                # a USER alone in the corridor may not make it private; with a second user it may; a third is refused at the
+                # door, invited, and walks in
+                p, g = users[0], rng.choice(guests)
+                h = rng.choice([k for k in range(n) if k not in (p, g) and accounts[k].level >= 1])
+                walk = lambda k, to: [(k, went(k, room)) for room in {"drive": ["hallway", "corridor"], "wizroom": ["hallway", "corridor"],
+                                                                      "corridor": []}.get(where[k], ["corridor"])[:to]]
+                lines = (walk(p, 2) + [(p, ".private")] + walk(h, 2) + [(p, ".private"), (p, ".say " + random_text(rng)[:60])] + walk(g, 1)
+                         + [(g, ".go corridor"), (p, ".invite " + names[g].lower()), (g, ".go corridor")])
+                private.add("corridor")
+                partied.append(p)
+                where[g] = "corridor"
+                return lines
+            if y < 0.12:
+                return [rng.choice([".public", ".invite", ".letmein", ".invite nobody", ".letmein drive", ".private drive", ".private nowhere",
+                                    ".letmein " + rng.choice(ROOMS)])]
+            if locked and y < 0.6:
+                return [".letmein " + rng.choice(locked)]
+            if here in private:
+                if y < 0.75:                        # an invitation, and half of the time the invited on its way at once
+                    k = rng.choice([k for k in range(n) if where[k] in LINKS[here]] or [k for k in range(n) if where[k] != here] or [i])
+                    return [".invite " + names[k].lower()] + ([(k, went(k, here))] if rng.random() < 0.5 else [])
+                private.discard(here)
+                return [".public"]
+            if here in SETTABLE or level >= 3 and y < 0.5:
+                room = here if here in SETTABLE else rng.choice(SETTABLE)
+                if level >= 2 or sum(w == room for w in where.values()) >= 2:
+                    private.add(room)
+                return [".private" if room == here else ".private " + room]
+            return [went(i, rng.choice(SETTABLE + LINKS[here]))]
+        if x < 0.64:
+            return [rng.choice([".rmst", ".rmsn"])]
+        if x < 0.86:                                # what a user sets of its own
+            com, y = rng.choice(list(TEXTS)), rng.random()
+            return [com if y < 0.2 else com + " " + TOO_LONG if y < 0.32 else com + " " + rng.choice(TEXTS[com])]
+        if wizards and rng.random() < 0.7:          # next to a clone of one's own; a GOD at an ARCH's clone
+            i = rng.choice(wizards)
+            gods = [k for k in wizards if accounts[k].level == 4]
+            theirs = [(k, room) for k in wizards if accounts[k].level == 3 for room in guess[k]]
+            if gods and theirs and rng.random() < 0.4:
+                k, room = rng.choice(theirs)
+                guess[k].remove(room)
+                return [(gods[0], ".destroy " + room + " " + names[k].lower())]
+            others = [k for k in wizards if k != i and len(guess[k]) < 2 and where[i] not in guess[k]]
+            if others and not guess[i] and where[i] != "corridor" and rng.random() < 0.5:
+                # a record destroyed in front of another's, and a new one in that one's room: list order is not creation order
+                k, room = rng.choice(others), where[i]
+                guess[k].append(room)
+                guess[i].append(room)
+                looker = rng.choice([j for j in range(n) if where[j] == room] or [i])
+                return [(i, ".clone corridor"), (k, ".clone " + room), (i, ".destroy corridor"), (i, ".clone " + room), (looker, ".look")]
+            if len(guess[i]) >= 2:
+                return [(i, ".clone " + rng.choice(SETTABLE))]
+            if where[i] not in guess[i]:
+                guess[i].append(where[i])
+                return [(i, ".clone"), (i, ".ignall")]
+            return [(i, ".ignall")]
+        if i in asked:
+            asked.discard(i)
+        else:
+            asked.add(i)
+        return [".ignall"] + ([(rng.choice(sorted(asked)), ".ignall")] if asked and rng.random() < 0.5 else [])
 
     def target() -> str:
         name = rng.choice(names)
@@ -92,6 +204,11 @@ def make_script(seed: int):
 
     while len(steps) < LINE_STEPS:
         i = rng.randrange(n)
+        if second and rng.random() < 0.4:
+            for line in second_line(i):
+                k, line = line if isinstance(line, tuple) else (i, line)
+                steps.append((KEYS[k], line, {}))
+            continue
         r = rng.random()
         flags = {}
         if r < 0.21:
@@ -150,6 +267,8 @@ def make_script(seed: int):
                 line = ".csay " + room + " " + random_text(rng)
         steps.append((KEYS[i], line[:LONGEST_LINE], flags))
 
+    del steps[LINE_STEPS:]
+
     def script(s):
         for k, a in zip(KEYS, accounts):
             s.connect(k)
@@ -198,7 +317,7 @@ def main(argv) -> int:
             except Exception as e:                  # a seed that types something the replayer does not answer
                 print(seed, "unusable:", repr(e)[:200])
                 continue
-            print(seed, f"share {res['answered_share']:.2f}", f"mismatches {len(res['mismatches'])}", f"bytes {len(render(doc))}",
+            print(seed, f"answered {res['answered']} tracked {res['tracked']}", f"mismatches {len(res['mismatches'])}", f"bytes {len(render(doc))}",
                   " ".join(f"{k}={v}" for k, v in res["coverage"].items() if v), sorted({a["level"] for a in doc["accounts"][0]}))
             for m in res["mismatches"][:2]:
                 print("   ", m)

@@ -116,6 +116,18 @@ def test_a_bad_clone_sender_is_rejected(no_library, sender, why):
     assert state(r) == before
 
 
+@pytest.mark.parametrize("ignall, why", [
+    ({}, "non-empty dict"), ([1], "non-empty dict"), (1, "non-empty dict"), ({-1: 0}, "ignall: "), ({10**6: 0}, "ignall: "),
+    ({1: 2}, "its flag must be 0/1"), ({1: None}, "its flag must be 0/1"), ({1: "1"}, "its flag must be 0/1"),
+])
+def test_a_bad_ignall_is_rejected(no_library, ignall, why):
+    r = cloned()
+    before = state(r)
+    with pytest.raises(ValueError, match=why):
+        r.relay_many(BS, ignall=ignall)
+    assert state(r) == before
+
+
 def test_what_plan_many_rejects_relay_many_rejects(no_library):
     r = cloned()
     before = state(r)
