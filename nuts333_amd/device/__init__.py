@@ -91,6 +91,12 @@ SET_COMS -- ``.mode``, ``.ignall``, ``.prompt``, ``.desc``, ``.inphr``, ``.outph
 ``get_room`` and no walk over the roster: a wave per event reads its actor's own rows, decides and composes the actor's two
 lines and the room's line, with their plans; an event that an earlier one of the same call touched is deferred; the binding
 sets the flags, the texts and the topic in the host mirrors.
+``Roster.act_many(events, gatecrash_level=, min_private_users=)`` answers the commands a user aims at another user, ``.move``,
+``.wake``, ``.muzzle`` and ``.unmuzzle`` (``move``, ``wake``, ``muzzle`` and ``unmuzzle`` with ``move_user(u, rm, 2)``,
+nuts333.c:4726-4768, 6496-6522, 6571-6703, 4409-4459) -- an :class:`Act`.  A block per event runs ``get_user`` over
+``word[1]`` and ``get_room`` over ``word[2]``, takes the head-count of a room a moved user leaves, decides and composes the
+six texts with their plans; an event whose slots or rooms an earlier one of the same call touched is deferred; the binding
+moves the targets, looks for them with one ``look_many`` and keeps ``Roster.update(muzzle_level=)``, the level of a muzzle.
 
 Input is validated before the device is touched (``ValueError``).  The library ``_build/libnuts_device.so`` is built by
 ``__graft_entry__.build()`` where ``hipcc`` exists, and on demand here when it is missing or older than its source.
@@ -349,6 +355,39 @@ _CLONE_COMS = (COM_CLONE, COM_DESTROY, COM_CSAY, COM_CHEAR)
 _CLONE_COM_RULE = f"com must be COM_CLONE, COM_DESTROY, COM_CSAY or COM_CHEAR ({COM_CLONE}, {COM_DESTROY}, {COM_CSAY}, {COM_CHEAR})"
 #: the texts of an event in a Clone, in that order: the four room lines first, then the two single-recipient texts
 CLONE_HERE, CLONE_THERE, CLONE_RESET, CLONE_SAID_LINE, CLONE_REPLY, CLONE_NOTICE = range(6)
+#: ``.move``, ``.wake``, ``.muzzle`` and ``.unmuzzle`` (NP_MOVE, NP_WAKE, NP_MUZZLE, NP_UNMUZZLE), the commands a user aims at
+#: another user, and the kernels act_many runs before nuts_roster_speak_plan
+COM_MOVE, COM_WAKE, COM_MUZZLE, COM_UNMUZZLE = 21, 58, 60, 61
+ACT_KERNELS = ("nuts_roster_act", "nuts_roster_act_order")
+#: what became of such an event (Act.outcome).  The first four changed something -- a user moved, seen or unseen, a muzzle
+#: set, a muzzle removed -- and ACT_WOKEN, a wake-up call that was sent, changed nothing.  Then the refusals to the actor
+#: alone, a branch of the reference each and in its order: of ``move`` (usage, nobody of that name, no such room, oneself,
+#: the target's level, already there, the room is private to the actor, and ACT_MOVE_AWAY, a target that stands in no look
+#: room, which the caller answers), of ``wake`` (usage, the actor is muzzled, nobody, oneself, the target is AFK), of
+#: ``muzzle`` (usage, ACT_MUZZLE_ABSENT -- nobody of that name is logged on and the reference goes to the user file: the
+#: caller's --, oneself, the target's level, already muzzled) and of ``unmuzzle`` (usage, ACT_UNMUZZLE_ABSENT, oneself, not
+#: muzzled -- which writes nothing --, a muzzle above the actor's level); and ACT_DEFERRED, an event the caller submits again
+(ACT_MOVED, ACT_MOVED_UNSEEN, ACT_MUZZLED, ACT_UNMUZZLED, ACT_WOKEN, ACT_MOVE_USAGE, ACT_MOVE_NOBODY, ACT_MOVE_NO_ROOM, ACT_MOVE_SELF,
+ ACT_MOVE_LEVEL, ACT_MOVE_ALREADY, ACT_MOVE_PRIVATE, ACT_MOVE_AWAY, ACT_WAKE_USAGE, ACT_WAKE_MUZZLED, ACT_WAKE_NOBODY, ACT_WAKE_SELF,
+ ACT_WAKE_AFK, ACT_MUZZLE_USAGE, ACT_MUZZLE_ABSENT, ACT_MUZZLE_SELF, ACT_MUZZLE_LEVEL, ACT_MUZZLE_ALREADY, ACT_UNMUZZLE_USAGE,
+ ACT_UNMUZZLE_ABSENT, ACT_UNMUZZLE_SELF, ACT_UNMUZZLE_NOT, ACT_UNMUZZLE_ABOVE, ACT_DEFERRED) = range(29)
+#: the longest texts of such an event before the transducer (kActHereMax .. kActNoticeMax of fanout.hip, pinned by a host
+#: test), by their format strings: ``~FT~OL``, a 12-byte name and `` chants an ancient spell...\n``; ``~FT~OL``, a name and
+#: `` falls out of a magical blue vortex!\n``; ``~FT~OLA giant hand grabs ``, a name and `` who is pulled into a magical blue
+#: vortex!\n``; ``Room access returned to ~FGPUBLIC.\n``; a name, ``'s muzzle is set to level ``, a level's name of at most 4
+#: bytes and ``, you do not have the power to remove it.\n``; the giant hand's line to the moved user
+MAX_ACT_HERE, MAX_ACT_ENTER, MAX_ACT_LEAVE, MAX_ACT_RESET, MAX_ACT_REPLY, MAX_ACT_NOTICE = (
+    6 + USER_NAME_LEN + 28, 6 + USER_NAME_LEN + 37, 25 + USER_NAME_LEN + 43, 35, USER_NAME_LEN + 26 + 4 + 42, 72)
+#: their slots among an act call's texts (kActHereRow .. kActNoticeRow): each the longest text rounded up to a multiple of 4,
+#: laid out as _GO_ROWS lays a go call's
+_ACT_ROWS = (48, 56, 80, 36, 84, 72)
+_ACT_COMS = (COM_MOVE, COM_WAKE, COM_MUZZLE, COM_UNMUZZLE)
+_ACT_COM_RULE = f"com must be COM_MOVE, COM_WAKE, COM_MUZZLE or COM_UNMUZZLE ({COM_MOVE}, {COM_WAKE}, {COM_MUZZLE}, {COM_UNMUZZLE})"
+#: the texts of an event in an Act, in that order: the four room lines first, then the two single-recipient texts
+ACT_HERE, ACT_ENTER, ACT_LEAVE, ACT_RESET, ACT_REPLY, ACT_NOTICE = range(6)
+#: the muzzle level's byte in a slot's speaker row (kMuzzleByte of fanout.hip), and WIZ, the lowest level that can type
+#: ``.muzzle``: the muzzle of a slot whose ``muzzled`` bit is set over a level byte of 0
+_MUZZLE_BYTE, LEVEL_WIZ = 15, 2
 #: the commands a user sets its own state with (NP_MODE .. NP_IGNTELL of enum np_com), and the kernels set_many runs before
 #: nuts_roster_speak_plan
 (COM_MODE, COM_IGNALL, COM_PROMPT, COM_DESC, COM_INPHR, COM_OUTPHR, COM_TOPIC, COM_VIS, COM_INVIS, COM_CHARECHO, COM_AFK, COM_COLOUR,
@@ -1082,6 +1121,80 @@ class Clone:
 
 
 @dataclass
+class Act:
+    """What ``move()``, ``wake()``, ``muzzle()`` and ``unmuzzle()`` write for K events (``Roster.act_many``), shaped like a
+    :class:`Clone`.  ``outcome[k]`` is one of the ACT_* constants; ``target_slot[k]`` the slot ``get_user`` found, or -1 when
+    it found none or was not asked; ``target_room[k]`` the room the event is about -- the room ``word[2]`` of a ``.move``
+    resolved to, the actor's own without such a word -- or -1 when ``get_room`` found none or was not reached;
+    ``old_room[k]`` the found slot's room before the call, the room a move leaves, or -1 without a slot;
+    ``returned_public[k]`` whether the move made that room public again.
+
+    ``reply`` plans the actor's own line, ``here`` the chant line the actor's room gets without the actor, ``enter`` the
+    line the room entered gets, ``leave`` the line the room left gets without the target, ``reset`` the line a room that
+    returns to public gets, and ``notice`` the target's own line: the giant hand (a visible target only), the wake-up
+    call, or the word of a muzzle set or removed.  They are ordinary plans over the roster as it was before the call and
+    share one variant buffer; a text that is not there has size -1, nobody admitted and both variants 0 bytes in 0 writes.
+    ACT_MOVE_AWAY, the two ``*_ABSENT`` outcomes, ACT_UNMUZZLE_NOT and ACT_DEFERRED have no text at all, and a deferred
+    event's targets are what the roster before the call gives.  ``look`` is the :class:`Look` of the moved targets after
+    the moves, in event order, or None when nobody moved, and ``look_index[k]`` event k's looker in it, or -1.
+
+    Delivery, per client: the events in call order, and of one event the reply, the here line, the notice, the enter line,
+    the leave line, the target's look, the reset line.  A roster with clone records passes the four room lines through
+    ``relay_many``."""
+    outcome: np.ndarray           # int8 [K]
+    target_slot: np.ndarray       # int32 [K]
+    target_room: np.ndarray       # int32 [K]
+    old_room: np.ndarray          # int32 [K]
+    returned_public: np.ndarray   # bool [K]
+    reply: Plan
+    here: Plan
+    enter: Plan
+    leave: Plan
+    reset: Plan
+    notice: Plan
+    texts: np.ndarray             # uint8, flat: the composed texts; gaps are allowed and unspecified
+    text_starts: np.ndarray       # int64 [6, K]   rows ACT_HERE, ACT_ENTER, ACT_LEAVE, ACT_RESET, ACT_REPLY, ACT_NOTICE
+    text_sizes: np.ndarray        # int64 [6, K]   -1: there is no such text
+    look: Look | None = None
+    look_index: np.ndarray | None = None         # int32 [K]
+    timing: dict = field(default_factory=dict)   # the first device visit's, as Plan's; the second's is look.timing
+
+    _text = Speech._text
+
+    def reply_text(self, k: int) -> bytes:
+        """The line event ``k`` sends to its actor; ``b""`` when there is none."""
+        return self._text(ACT_REPLY, k)
+
+    def here_text(self, k: int) -> bytes:
+        """The chant line event ``k`` sends to its actor's room without the actor; ``b""`` when nobody moved."""
+        return self._text(ACT_HERE, k)
+
+    def enter_text(self, k: int) -> bytes:
+        """The line event ``k`` sends to the room its target enters; ``b""`` when nobody moved."""
+        return self._text(ACT_ENTER, k)
+
+    def leave_text(self, k: int) -> bytes:
+        """The line event ``k`` sends to the room its target leaves; ``b""`` when nobody moved."""
+        return self._text(ACT_LEAVE, k)
+
+    def reset_text(self, k: int) -> bytes:
+        """The line the room event ``k``'s target left gets when it returns to public; ``b""`` when it does not."""
+        return self._text(ACT_RESET, k)
+
+    def notice_text(self, k: int) -> bytes:
+        """The line event ``k`` sends to its target alone; ``b""`` when there is none."""
+        return self._text(ACT_NOTICE, k)
+
+    def moved(self) -> np.ndarray:
+        """The events that moved their target, ascending."""
+        return np.flatnonzero((self.outcome >= 0) & (self.outcome <= ACT_MOVED_UNSEEN))
+
+    def effective(self) -> np.ndarray:
+        """The events that moved a user, set a muzzle or removed one, ascending."""
+        return np.flatnonzero((self.outcome >= 0) & (self.outcome <= ACT_UNMUZZLED))
+
+
+@dataclass
 class Settings:
     """What the commands a user sets its own state with write for K events (``Roster.set_many``), shaped like an
     :class:`Access`.  ``outcome[k]`` is one of the SET_* constants.  ``reply`` plans the actor's first ``write_user``,
@@ -1383,6 +1496,9 @@ def _load():
         lib.nd_roster_clone.argtypes = ([ctypes.c_int, ctypes.c_int, P, ctypes.c_int64, P, P, P, P, P, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, ctypes.c_int] + [P] * 18 + [ctypes.POINTER(_RosterTiming)])
         lib.nd_roster_clone.restype = ctypes.c_int
+        lib.nd_roster_act.argtypes = ([ctypes.c_int, ctypes.c_int, P, ctypes.c_int64, P, P, P, P, P, ctypes.c_int, ctypes.c_int]
+                                      + [P] * 17 + [ctypes.POINTER(_RosterTiming)])
+        lib.nd_roster_act.restype = ctypes.c_int
         lib.nd_roster_set.argtypes = [ctypes.c_int, ctypes.c_int, P, ctypes.c_int64] + [P] * 19 + [ctypes.POINTER(_RosterTiming)]
         lib.nd_roster_set.restype = ctypes.c_int
         lib.nd_roster_clones.argtypes = [ctypes.c_int, ctypes.c_int]
@@ -1690,7 +1806,7 @@ class Roster:
     def update(self, slots, *, room=_KEEP, login=_KEEP, ignall=_KEEP, ignshout=_KEEP, colour=_KEEP, name=_KEEP,
                vis=_KEEP, muzzled=_KEEP, command_mode=_KEEP, level=_KEEP, afk=_KEEP, igntell=_KEEP,
                afk_mesg=_KEEP, desc=_KEEP, last_login=_KEEP, away=_KEEP, in_phrase=_KEEP, out_phrase=_KEEP,
-               invite_room=_KEEP, prompt=_KEEP, charmode_echo=_KEEP) -> None:
+               invite_room=_KEEP, prompt=_KEEP, charmode_echo=_KEEP, muzzle_level=_KEEP) -> None:
         """Set fields of ``slots`` (a slot or a sequence of them).  Each field given is one value for every slot or a
         sequence of one per slot; a field not given stays as it is.  ``room`` is None (no room) or an int in
         [0, ROOM_LIMIT); the flags are 0/1 or bools.  A slot given more than once takes its last values.  Nothing
@@ -1706,8 +1822,9 @@ class Roster:
         ``afk`` and ``igntell`` (0/1, 0 at first) and ``afk_mesg`` (bytes or str of 0 .. AFK_MESG_LEN bytes, no NUL,
         empty at first) are what :meth:`tell_many` reads of a **target**: a read that comes from an AFK slot remains
         the caller's business.  The two flags live in the speaker mirror's flags byte, with a dirty flag of their
-        own; the messages in a mirror of their own.  Only ``tell_many`` uploads after an update of these three alone:
-        no other call copies more for it.
+        own; the messages in a mirror of their own.  Only ``tell_many`` uploads after an update of these three alone,
+        and :meth:`act_many`, whose ``.wake`` reads a target's ``afk``, after one of the two flags: no other call copies
+        more for it.
 
         ``desc`` (bytes or str of 0 .. USER_DESC_LEN bytes, no NUL, empty at first) is ``user->desc``, which ``look()``
         shows beside a name.  It lives in a mirror of its own that only :meth:`look_many` and :meth:`who_many` upload.
@@ -1725,7 +1842,14 @@ class Roster:
         ``prompt`` and ``charmode_echo`` (0/1, 0 at first) are ``user->prompt`` and ``user->charmode_echo``, which
         ``.prompt``, ``.charecho`` and the video test of ``.colour`` read.  They live in the last two bits of the speaker
         mirror's flags byte, with a dirty flag of their own: only :meth:`set_many` uploads after an update of these two
-        alone."""
+        alone.
+
+        ``muzzle_level`` (an int in [0, MAX_LEVEL], 0 at first) is ``user->muzzled``, the level of the user who set the
+        muzzle.  It lives in byte 15 of a slot's speaker row, and setting it also sets the ``muzzled`` bit to ``level >
+        0``; it marks the speaker mirror as ``level`` does.  ``muzzled`` stays what it was: it writes the bit and never
+        byte 15, so the two cannot be given in one update.  :meth:`act_many` reads a slot's muzzle as byte 15 when the bit
+        is set and the byte is not 0, as WIZ -- the lowest level that can type ``.muzzle`` -- when the bit is set over a
+        byte of 0, and as 0 when the bit is clear; every other call reads the bit alone."""
         self._check_open()
         if isinstance(slots, (int, np.integer)):
             slots = [slots]
@@ -1762,6 +1886,15 @@ class Roster:
                   for f, v in (("vis", vis), ("muzzled", muzzled), ("command_mode", command_mode), ("afk", afk),
                                ("igntell", igntell), ("prompt", prompt), ("charmode_echo", charmode_echo)) if v is not _KEEP}
         levels = None if level is _KEEP else per_slot("level", level, _level, np.uint8)
+        if muzzle_level is not _KEEP and muzzled is not _KEEP:
+            raise ValueError("muzzled and muzzle_level cannot be given in one update: muzzle_level sets the muzzled bit too")
+
+        def muzzle(v):
+            if not _is_int(v, 0, MAX_LEVEL):
+                raise ValueError(f"muzzle_level must be an int in [0, {MAX_LEVEL}] (enum np_level), not {v!r}")
+            return int(v)
+
+        muzzles = None if muzzle_level is _KEEP else per_slot("muzzle_level", muzzle_level, muzzle, np.uint8)
         mesgs = None
         if afk_mesg is not _KEEP:
             if isinstance(afk_mesg, (str, bytes, bytearray, memoryview)):
@@ -1820,6 +1953,10 @@ class Roster:
             col[at] = np.where(v[keep] != 0, col[at] | bit, col[at] & ~bit)
         if levels is not None:
             self._speech[at, _LEVEL_BYTE] = levels[keep]
+        if muzzles is not None:
+            bit, col = np.uint8(SPEECH_FLAGS["muzzled"]), self._speech[:, USER_NAME_LEN + 1]
+            self._speech[at, _MUZZLE_BYTE] = muzzles[keep]
+            col[at] = np.where(muzzles[keep] != 0, col[at] | bit, col[at] & ~bit)
         if mesgs is not None:
             for j, p in zip(at.tolist(), keep.tolist()):
                 self._afk[j] = 0
@@ -1848,13 +1985,15 @@ class Roster:
             self._go_invite[at] = invites[keep]
         if phrases or invites is not None:
             self._go_dirty = True
-        if names is not None or levels is not None or speech.keys() - {"afk", "igntell", "prompt", "charmode_echo"}:
+        if (names is not None or levels is not None or muzzles is not None
+                or speech.keys() - {"afk", "igntell", "prompt", "charmode_echo"}):
             self._speech_dirty = True
         if speech.keys() & {"afk", "igntell"}:
             self._private_dirty = True
         if speech.keys() & {"prompt", "charmode_echo"}:
             self._set_dirty = True
-        if rooms is not None or flags or not (names is not None or speech or levels is not None or mesgs is not None
+        if rooms is not None or flags or not (names is not None or speech or levels is not None or muzzles is not None
+                                              or mesgs is not None
                                               or descs is not None or logins is not None or aways is not None
                                               or phrases or invites is not None):
             self._dirty = True
@@ -2945,7 +3084,7 @@ class Roster:
         the look included, uploads its ``5 x capacity`` bytes; a room that returned to public costs the room table and
         the go mirror as well.
 
-        Out of scope: ``.move`` (teleport 2); the netlink branch and the ``remote_com == GO`` release, which the caller does
+        Out of scope: ``.move`` (teleport 2), which is :meth:`act_many`'s; the netlink branch and the ``remote_com == GO`` release, which the caller does
         before it submits; remote users; ``.private``, ``.public``, ``.invite`` and ``.letmein`` themselves -- they are
         :meth:`access_many`'s, which keeps ``access`` and ``invite_room`` for this call; the prompt; fusing the look into the
         first device visit;
@@ -3066,7 +3205,7 @@ class Roster:
         after an update of theirs), three kernel launches (ACCESS_KERNELS, then nuts_roster_speak_plan), one download at
         the bound size and one synchronise, whatever K and the capacity.  Returns an :class:`Access`.
 
-        Out of scope: ``.topic``; ``.move``; the relay of the two room lines to clones' owners -- the caller passes them
+        Out of scope: ``.topic``; ``.move``, which is :meth:`act_many`'s; the relay of the two room lines to clones' owners -- the caller passes them
         to :meth:`relay_many`, as after :meth:`go_many`; remote users; the prompt."""
         self._check_open()
         text, text_off, lens, slots, coms, wcs = self._prepare_access(events, gatecrash_level, min_private_users, ignore_mp_level)
@@ -3104,6 +3243,140 @@ class Roster:
             else:
                 self._returned_to_public(int(target_room[k]))
         return access
+
+    def _prepare_act(self, events, gatecrash_level, min_private_users):
+        """Each (slot, com, inpstr, word_count) and its actor's state checked, packed for nd_roster_act: the inpstr, their
+        offsets and lengths, the slots, the commands and the word counts."""
+        self._check_sequence(events)
+        if not _is_int(gatecrash_level, 0, MAX_LEVEL):
+            raise ValueError(f"gatecrash_level must be an int in [0, {MAX_LEVEL}] (enum np_level), not {gatecrash_level!r}")
+        if not _is_int(min_private_users, 0, 2**31 - 1):
+            raise ValueError(f"min_private_users must be an int in [0, 2^31), not {min_private_users!r}")
+        if self.look_rooms < 1:
+            raise ValueError("the roster has no room records (look_rooms is 0): there is no room to move anyone to")
+        inps, *packed = self._prepare_events(events, actor="actor", rows=_ACT_ROWS, texts=6, coms=_ACT_COMS,
+                                             com_rule=_ACT_COM_RULE)
+        return (b"".join(inps), *packed)
+
+    def act_many(self, events, *, gatecrash_level, min_private_users) -> Act:
+        """K ``.move`` / ``.wake`` / ``.muzzle`` / ``.unmuzzle`` events, the commands a user aims at another user, decided and
+        composed on the device: a non-empty sequence of ``(slot, com, inpstr, word_count)`` tuples, what a COMMAND read of
+        :meth:`input_many` hands back, with ``com`` COM_MOVE, COM_WAKE, COM_MUZZLE or COM_UNMUZZLE (``move``, ``wake``,
+        ``muzzle`` and ``unmuzzle``, nuts333.c:4726-4768, 6496-6522, 6571-6703, with ``move_user(u, rm, 2)``, 4409-4459).
+        ``gatecrash_level`` is an int in [0, MAX_LEVEL] and ``min_private_users`` an int >= 0, the talker's two settings.
+        The roster needs ``look_rooms >= 1``; every actor needs a room in ``[0, look_rooms)``, a name and no ``login`` flag;
+        a slot may appear more than once.  Anything else raises ``ValueError("event k: ...")`` before the device is
+        touched, and a call whose variant bound exceeds MANY_ARENA_CAP is refused.
+
+        The device does, per event and in the reference's order, with ``word[1]`` and ``word[2]`` the first two words of
+        ``inpstr`` as :meth:`clone_many` takes them, and ``get_user`` over ``word[1]`` as :meth:`tell_many` runs it.
+        ``.move``: ACT_MOVE_USAGE if ``word_count < 2``; ACT_MOVE_NOBODY; the room is the actor's own when ``word_count <
+        3``, else ``get_room`` over ``word[2]`` as :meth:`go_many` runs it, else ACT_MOVE_NO_ROOM; ACT_MOVE_SELF;
+        ACT_MOVE_LEVEL if the target's level is not below the actor's; ACT_MOVE_ALREADY; ACT_MOVE_PRIVATE if the *actor*
+        has no access to the room -- ``access & PRIVATE``, the actor's level below ``gatecrash_level``, the actor's
+        ``invite_room`` another room and the room not a fixed one entered by a WIZ; ACT_MOVE_AWAY if the target stands in
+        no look room (the reference's netlink release): nothing is composed; else ACT_MOVED, or ACT_MOVED_UNSEEN for an
+        invisible target.  A move composes ``reply``, ``here`` -- ``"~FT~OL<name> chants an ancient spell...\\n"`` with
+        ``invisname`` for an invisible actor --, ``enter`` and ``leave`` -- the vortex and the giant hand with the target's
+        name, or ``invisenter`` and ``invisleave`` -- and, for a visible target, the giant hand's ``notice``.  When the
+        room left is exactly PRIVATE and fewer than ``min_private_users`` stay behind, counted as :meth:`go_many` counts
+        them, it returns to public: ``reset`` to that room.  ``.wake``: ACT_WAKE_USAGE; ACT_WAKE_MUZZLED if the actor's
+        ``muzzled`` bit is set; ACT_WAKE_NOBODY; ACT_WAKE_SELF; ACT_WAKE_AFK; else ACT_WOKEN: the reply and the wake-up
+        call as ``notice``, with ``invisname`` for an invisible actor.  ``.muzzle``: ACT_MUZZLE_USAGE; ACT_MUZZLE_ABSENT if
+        ``get_user`` found nobody -- the reference goes to the user file, nothing is composed; ACT_MUZZLE_SELF;
+        ACT_MUZZLE_LEVEL; ACT_MUZZLE_ALREADY if the target's muzzle (see :meth:`update`) is not below the actor's level;
+        else ACT_MUZZLED.  ``.unmuzzle``: ACT_UNMUZZLE_USAGE; ACT_UNMUZZLE_ABSENT; ACT_UNMUZZLE_SELF; ACT_UNMUZZLE_NOT,
+        which writes nothing, as the reference does (nuts333.c:6656-6658); ACT_UNMUZZLE_ABOVE if the muzzle is above the
+        actor's level; else ACT_UNMUZZLED.  The room lines' ``com_num`` is the event's ``com``.
+
+        Every event is decided and planned against the roster as it was before the call.  To keep that exact, an event is
+        ACT_DEFERRED when an earlier event of the same call that was not itself deferred touched one of its two slots --
+        the actor's and the one ``get_user`` found -- or three rooms -- the actor's, the found slot's and the resolved
+        one: it wrote nothing and changed nothing, and the caller submits it again.  A move touches the target's slot, the
+        room left and the room entered; a muzzle set or removed touches the target's slot; nothing else touches anything,
+        and a call of one event never defers.
+
+        The binding then applies the result to the host mirrors, through :meth:`update`, :meth:`set_rooms` and
+        :meth:`clear_review`, in ``move_user``'s order and as :meth:`go_many` does: the targets' rooms; their invitations
+        into the rooms entered cleared; if anyone moved, one :meth:`look_many` over the moved targets in event order; then
+        every room that returned to public made PUBLIC, with every slot's invite into it cleared and its review ring
+        emptied when it has one; then ``muzzle_level`` set to the actor's level, or to 0.  As in :meth:`go_many`, the one
+        look shows no room of the call as returned, so the binding defers one more kind of event: a move whose new room
+        adjoins a room that an earlier event of the same call returned to public.  No kernel writes a kept table.
+
+        A call therefore visits the device at most twice.  The first visit is one upload (the table, the speaker state, the
+        clone records, the room table and the go mirror only after an update of theirs; the speaker state after an update
+        of ``afk`` or ``igntell`` as well, since a ``.wake`` reads ``afk``), three kernel launches
+        (ACT_KERNELS, then nuts_roster_speak_plan), one download at the bound size and one synchronise, whatever K and the
+        capacity; the second is ``look_many``'s.  Returns an :class:`Act`.
+
+        Delivery, per client: the events in call order, and of one event the reply, the here line, the notice, the enter
+        line, the leave line, the target's look, the reset line.
+
+        What stays with the caller: the two ``*_ABSENT`` branches, which read and write the user file, and
+        ACT_MOVE_AWAY, the release of a user over its netlink (nuts333.c:4439-4443); the syslog lines of a muzzle and an unmuzzle; ``prompt(u)`` for the moved user; the relay of the four room lines
+        to clones' owners, through :meth:`relay_many`; remote users; the check of the command's level, which
+        :meth:`input_many` makes."""
+        self._check_open()
+        text, text_off, lens, slots, coms, wcs = self._prepare_act(events, gatecrash_level, min_private_users)
+        lib = _load()
+        handle = self._device_handle(lib)
+        k = len(lens)
+        outcome, clen, bits, vn, vw, vwsz, ctext, var = self._event_arrays(k, _ACT_ROWS, 6)
+        target_slot, target_room, old = (np.empty(k, dtype=np.int32) for _ in range(3))
+        returned = np.empty(k, dtype=np.uint8)
+        tbuf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, dtype=np.uint8)
+        t = _RosterTiming()
+        # ``.wake`` reads a target's ``afk`` bit, which marks _private_dirty alone: the speaker mirror travels for it too
+        speech_stale = self._speech_dirty or self._private_dirty
+        rc = lib.nd_roster_act(handle, k, _ptr(tbuf), len(text), _ptr(text_off), _ptr(lens), _ptr(slots), _ptr(coms), _ptr(wcs),
+                               int(gatecrash_level), int(min_private_users), _ptr(self._table) if self._dirty else None,
+                               _ptr(self._speech) if speech_stale else None,
+                               _ptr(self._clones) if self._clones_dirty and self.clones else None,
+                               _ptr(self._rooms) if self._rooms_dirty else None, _ptr(self._go) if self._go_dirty else None,
+                               _ptr(outcome), _ptr(target_slot), _ptr(target_room), _ptr(old), _ptr(returned), _ptr(clen),
+                               _ptr(bits), _ptr(vn), _ptr(vw), _ptr(vwsz), _ptr(ctext), _ptr(var), ctypes.byref(t))
+        _check(rc, "device act failed")
+        self._private_dirty = False                           # the whole speaker mirror went up, or nothing of it was stale
+        self._dirty = self._speech_dirty = self._rooms_dirty = self._go_dirty = False
+        if self.clones:
+            self._clones_dirty = False
+        # the device's four, then the actor alone and the target alone
+        tstarts, plans, timing = self._event_plans(_ACT_ROWS, clen, bits, vn, vw, vwsz, var, t,
+                                                   [(ACT_REPLY, slots), (ACT_NOTICE, target_slot)])
+        act = Act(outcome=outcome, target_slot=target_slot, target_room=target_room, old_room=old,
+                  returned_public=returned.astype(bool), reply=plans[ACT_REPLY], here=plans[ACT_HERE], enter=plans[ACT_ENTER],
+                  leave=plans[ACT_LEAVE], reset=plans[ACT_RESET], notice=plans[ACT_NOTICE], texts=ctext, text_starts=tstarts,
+                  text_sizes=clen.astype(np.int64), look_index=np.full(k, -1, dtype=np.int32), timing=timing)
+        # as in go_many: a moved target whose new room adjoins a room that an earlier event of the call returned to public
+        # would look at it before the one look_many shows it public, and is deferred here
+        public = set()
+        for b in act.moved().tolist():
+            rec = self._room_rec[target_room[b]]
+            if public & set(rec[32:32 + 4 * int(rec[22])].view("<i4").tolist()):
+                outcome[b], act.returned_public[b] = ACT_DEFERRED, False
+                act.text_sizes[:, b] = -1
+                for plan in plans:
+                    plan.admitted_bits[b], plan.variant_sizes[b], plan.write_counts[b] = 0, 0, 0
+            elif act.returned_public[b]:
+                public.add(int(old[b]))
+        # the changes, on the host mirrors: the next call of any kind uploads what it reads
+        moved = act.moved()
+        if len(moved):
+            movers, into = target_slot[moved], target_room[moved]
+            self.update(movers, room=into)
+            invited = movers[self._go_invite[movers] == into]
+            if len(invited):
+                self.update(invited, invite_room=None)
+            act.look = self.look_many(movers)
+            act.look_index[moved] = np.arange(len(moved), dtype=np.int32)
+        for rm in sorted(public):
+            self._returned_to_public(rm)
+        muzzles = np.flatnonzero((outcome == ACT_MUZZLED) | (outcome == ACT_UNMUZZLED))
+        if len(muzzles):                # one update: the order kernel leaves a target one such event a call
+            levels = np.where(outcome[muzzles] == ACT_MUZZLED, self._speech[slots[muzzles], _LEVEL_BYTE], 0)
+            self.update(target_slot[muzzles], muzzle_level=levels.tolist())
+        return act
 
     def _prepare_clone(self, events, max_clones, gatecrash_level, min_private_users, record):
         """Each (slot, com, inpstr, word_count) and its actor's state checked, packed for nd_roster_clone: the inpstr, their

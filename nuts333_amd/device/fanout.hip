@@ -31,10 +31,11 @@
 // then gives every text its two variants (its section below).
 // nuts_roster_relay answers the clone branch of write_room_except after nuts_roster_plan, in the same call: which of the
 // roster's clone records relay each broadcast to their owners, and the prefixed text they send (its section below).
-// nuts_roster_go, nuts_roster_access, nuts_roster_clone and nuts_roster_set decide and compose the commands that change what
-// the other kernels read -- a user's room, a room's access and the invitations, the clone records, and what a user sets on
-// itself -- each followed by a one-wave kernel that defers the events an earlier one of the call touched; none of them
-// writes a kept table (their sections below).  The four are one kind of call, the event call, and what they share is
+// nuts_roster_go, nuts_roster_access, nuts_roster_clone, nuts_roster_set and nuts_roster_act decide and compose the commands
+// that change what the other kernels read -- a user's room, a room's access and the invitations, the clone records, what a
+// user sets on itself, and another user's room and muzzle -- each followed by a one-wave kernel that defers the events an
+// earlier one of the call touched; none of them writes a kept table (their sections below).  The five are one kind of call,
+// the event call, and what they share is
 // written once: the head of their arguments (EventArgs), the walk of the order kernels (order_events, with a rule per
 // kernel: its keys, what hits, what touches), and on the host the layouts' head and tail (take_events, take_event_texts)
 // and the steps of the call from check_events to copy_event_results.
@@ -3792,6 +3793,390 @@ struct CloneOrderArgs {
     __device__ void also_void(int b) const { reset[b] = 0, flags[b] = 0; }
 };
 
+// ------------------------------------------------------------------ the commands aimed at another user, of a resident roster
+//
+// move(), wake(), muzzle() and unmuzzle() (nuts333.c:4726-4768, 6496-6522, 6571-6703) with move_user(u, rm, 2)
+// (c:4409-4459): .move, .wake, .muzzle and .unmuzzle, commands 21, 58, 60 and 61.  As with the clone commands, the device
+// decides and composes and writes no kept table; the host binding moves the targets and sets their muzzles in its mirrors
+// afterwards.  It reads the five tables nuts_roster_go reads.  Byte 15 of a slot's speaker state is its muzzle level: a slot's
+// muzzle is that byte when the muzzled bit is set and the byte is not 0, WIZ -- the lowest level that can type .muzzle -- when
+// the bit is set and the byte is 0, and 0 when the bit is clear.
+// An event has six texts in slots of fixed width: the chant line the actor's room gets without the actor ("here"), the vortex
+// line the room entered gets ("enter"), the giant-hand line the room left gets without the target ("leave"), "Room access
+// returned to ~FGPUBLIC.\n" for a room left too empty ("reset"), the actor's own line ("reply") and the target's own line
+// ("notice").  With K events, text kind * K + k is event k's text of that kind, in that order: the 4K room lines first, as
+// nuts_roster_speak_plan wants them.
+//   act      nuts_roster_act, ONE BLOCK PER EVENT, in the shape of nuts_roster_access.  word[1] and word[2] are found as
+//            nuts_roster_clone finds them.  The block runs get_user over the capitalised word[1] (first, while little else is
+//            live), get_room over word[2] of a .move of three words -- otherwise the room is the actor's --, and for a move
+//            that happens out of a room that is exactly PRIVATE the head-count of the room left without the target, as
+//            nuts_roster_go takes it: popcounts of ballots, summed per wave and across the waves through LDS.  No atomics:
+//            the same answer on every run.  Wave 0 decides in the reference's order and composes; lane 0 stores the lengths,
+//            the outcome, the slot found, the room resolved, the room left, whether it returns to public, and rm / sender /
+//            com of the four room lines: the here line to the actor's room with the actor as sender, the enter line to the
+//            room entered without one, the leave and the reset line to the room left with the target as sender.
+//            Blocks past the events copy freshly uploaded tables into the kept allocations.
+//   order    nuts_roster_act_order, ONE WAVE: order_events by its own rule.  A move touches the target's slot, the room left
+//            and the room entered; a muzzle set or removed touches the target's slot.  An event whose actor's slot or room,
+//            found slot, that slot's room or resolved room an earlier event of the call that was not itself deferred
+//            touched is deferred: its outcome becomes kActDeferred, its six texts void, and its room does not return.
+//   plan     nuts_roster_speak_plan with 4K room lines and 2K single-recipient texts.
+constexpr int kComMove = 21, kComWake = 58, kComMuzzle = 60, kComUnmuzzle = 61;            // enum np_com
+constexpr int kMuzzleByte = kNameLen + 3;                  // the muzzle level in a slot's speaker state
+// the effective ones first -- an event moved iff its outcome is at most kActMovedUnseen --, then a branch of the reference each
+constexpr int kActMoved = 0, kActMovedUnseen = 1, kActMuzzled = 2, kActUnmuzzled = 3, kActWoken = 4, kActMoveUsage = 5,
+              kActMoveNobody = 6, kActMoveNoRoom = 7, kActMoveSelf = 8, kActMoveLevel = 9, kActMoveAlready = 10, kActMovePrivate = 11,
+              kActMoveAway = 12, kActWakeUsage = 13, kActWakeMuzzled = 14, kActWakeNobody = 15, kActWakeSelf = 16, kActWakeAfk = 17,
+              kActMuzzleUsage = 18, kActMuzzleAbsent = 19, kActMuzzleSelf = 20, kActMuzzleLevel = 21, kActMuzzleAlready = 22,
+              kActUnmuzzleUsage = 23, kActUnmuzzleAbsent = 24, kActUnmuzzleSelf = 25, kActUnmuzzleNot = 26, kActUnmuzzleAbove = 27,
+              kActDeferred = 28;
+constexpr int kActTexts = 6, kActLines = 4;                // here, enter, leave, reset: the room lines; then reply, notice
+constexpr int kActHere = 0, kActEnter = 1, kActLeave = 2, kActReset = 3, kActReply = 4, kActNotice = 5;
+// the longest texts: "~FT~OL" + name + " chants an ancient spell...\n"; "~FT~OL" + name + " falls out of a magical blue
+// vortex!\n"; "~FT~OLA giant hand grabs " + name + " who is pulled into a magical blue vortex!\n"; "Room access returned to
+// ~FGPUBLIC.\n"; name + "'s muzzle is set to level " + a level's name + ", you do not have the power to remove it.\n";
+// "\n~FT~OLA giant hand grabs you and pulls you into a magical blue vortex!\n"
+constexpr int kActHereMax = 6 + kNameLen + 28, kActEnterMax = 6 + kNameLen + 37, kActLeaveMax = 25 + kNameLen + 43, kActResetMax = 35,
+              kActReplyMax = kNameLen + 26 + 4 + 42, kActNoticeMax = 72;
+constexpr int kActHereRow = 48, kActEnterRow = 56, kActLeaveRow = 80, kActResetRow = 36, kActReplyRow = 84, kActNoticeRow = 72;
+constexpr int kActRow = kActHereRow + kActEnterRow + kActLeaveRow + kActResetRow + kActReplyRow + kActNoticeRow;
+constexpr int act_row(int kind)
+{
+    return kind == kActHere ? kActHereRow : kind == kActEnter ? kActEnterRow : kind == kActLeave ? kActLeaveRow
+           : kind == kActReset ? kActResetRow : kind == kActReply ? kActReplyRow : kActNoticeRow;
+}
+// Where text kind * k + b of a call of k events has its slot: the kinds in their order, each kind's rows event by event.
+constexpr int64_t act_text_at(int kind, int64_t b, int64_t k)
+{
+    int64_t before = 0;
+    for (int i = 0; i < kind; i++) before += act_row(i);
+    return before * k + act_row(kind) * b;
+}
+
+struct ActArgs : EventArgs {     // slotf: login
+    int32_t* found;              // [3k] the slot get_user found (-1: none, or it was not asked); at k, the room the event is
+                                 // about (-1: get_room found none, or was not reached); at 2k, the found slot's room (-1: no
+                                 // slot).  One array, and one below: the kernel's arguments stay in scalar registers
+    uint8_t* returned;           // [k] 1: the room left returns to public
+    int32_t* line;               // [12k] the room lines' rooms, as SpeakPlanArgs.rm; at 4k, their senders (-1: none); at 8k,
+                                 // their com_num
+    const uint8_t* com;          // [k] NP_MOVE, NP_WAKE, NP_MUZZLE or NP_UNMUZZLE
+    int look_rooms, clones, gatecrash_level, min_private_users;
+    const uint8_t* speech;       // the tables this call reads, the uploads or the kept ones: the speaker state (name, vis, level, muzzle),
+    const uint8_t* records;      // the clone records as take_clones lays them out (nullptr: the roster has none),
+    const uint8_t* rooms;        // the room records,
+    const uint8_t* go;           // [capacity * 88] and the go table: invite_room
+    Kept kept[4];                // the clone records, the room records, the go table, the speaker state
+};
+
+__device__ __forceinline__ Piece level_piece(int level)   // level_name[] (nuts333.c), as nuts_roster_who prints it
+{
+    return level == kNew ? lit("NEW") : level == kUser ? lit("USER") : level == kWiz ? lit("WIZ") : level == kArch ? lit("ARCH") : lit("GOD");
+}
+
+// p0, then p1 and p2, behind what a text already holds: two compose()s, each shorter than a wave.
+__device__ __forceinline__ void append3(uint8_t* dst, int cap, int& at, Piece p0, Piece p1, Piece p2, int lane, int* violations)
+{
+    const Piece none{nullptr, 0};
+    const Piece a0[5] = {p0, none, none, none, none}, a1[5] = {p1, p2, none, none, none};
+    append(dst, cap, at, a0, nullptr, 0, false, lane, violations);
+    append(dst, cap, at, a1, nullptr, 0, false, lane, violations);
+}
+
+__device__ void roster_act(const ActArgs& e)
+{
+    if ((int)blockIdx.x >= e.k) {           // the tables just uploaded, into the kept allocations: a word per lane
+        copy_kept(e.kept, ((int)blockIdx.x - e.k) * kBlock + (int)threadIdx.x);
+        return;
+    }
+    __shared__ int s_room[kBlock / 64], s_exact[kBlock / 64], s_sub[kBlock / 64], s_pop[kBlock / 64];
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int k = (int)blockIdx.x;
+    const int slot = e.slot[k], com = e.com[k], wc = e.words[k], len = e.text_len[k];
+    const uint8_t* in = e.text + e.text_off[k];
+
+    // word[1] and word[2] as np_wordfind finds the line's second and third word (c:417-432): inpstr has lost the first
+    uint32_t wordb = 0;
+#pragma unroll
+    for (int x = 0; x < kReadSlice; x++) {
+        const int at = kReadSlice * lane + x;
+        wordb |= (uint32_t)(at < len && (int8_t)in[at] > 32) << x;
+    }
+    const int w0 = first_from(wordb, 0, lane, len);
+    const int w0_end = first_from(~wordb & 0xffffu, w0, lane, len);
+    const int w1 = first_from(wordb, w0_end, lane, len);
+    const int w1_end = first_from(~wordb & 0xffffu, w1, lane, len);
+    const int wlen = w0_end - w0 < kWordLen ? w0_end - w0 : kWordLen;
+    const int wlen2 = w1_end - w1 < kWordLen ? w1_end - w1 : kWordLen;
+    const uint8_t* word = in + w0;
+    const uint8_t* word2 = in + w1;
+
+    // get_user over the capitalised word[1], before anything else is kept: the search is what needs registers most.  A
+    // muzzled waker is refused before it in the reference (c:6505); the decisions below keep that order
+    int best_exact = kNoMatch, best_sub = kNoMatch;
+    if (wc >= 2) {
+        const UserMatch u = wave_get_user(e.speech, e.slotf, e.capacity, pack_word(word, wlen), wlen, wave, lane);
+        best_exact = u.exact;
+        best_sub = u.sub;
+    }
+    const bool want_room = com == kComMove && wc >= 3;     // c:4739-4744
+    int best = want_room ? wave_get_room(e.rooms, e.look_rooms, word2, wlen2, wave, lane) : kNoMatch;
+    if (lane == 0) {
+        s_room[wave] = best;
+        s_exact[wave] = best_exact;
+        s_sub[wave] = best_sub;
+    }
+    __syncthreads();
+    for (int w = 0; w < kBlock / 64; w++) {
+        best = s_room[w] < best ? s_room[w] : best;
+        best_exact = s_exact[w] < best_exact ? s_exact[w] : best_exact;
+        best_sub = s_sub[w] < best_sub ? s_sub[w] : best_sub;
+    }
+
+    const uint8_t* sp = e.speech + (size_t)slot * kSpeechRec;
+    const int level = sp[kLevelByte];
+    const int here = e.room[slot];          // a look room: the host checked it
+
+    // what comes before get_user (c:4733, 6502-6507, 6576, 6648); block-uniform
+    int outcome = -1;
+    if (wc < 2) outcome = com == kComMove ? kActMoveUsage : com == kComWake ? kActWakeUsage : com == kComMuzzle ? kActMuzzleUsage : kActUnmuzzleUsage;
+    else if (com == kComWake && (sp[kNameLen + 1] & kMuzzled)) outcome = kActWakeMuzzled;
+    const int target = outcome >= 0 ? -1 : best_exact != kNoMatch ? best_exact : best_sub != kNoMatch ? best_sub : -1;
+    const uint8_t* tp = e.speech + (size_t)(target < 0 ? slot : target) * kSpeechRec;
+    const int old = target < 0 ? -1 : e.room[target];
+    int rm = here;
+
+    // the four functions' decisions, in their order; block-uniform
+    if (outcome < 0) {
+        const int tlevel = tp[kLevelByte];
+        const int muzzle = !(tp[kNameLen + 1] & kMuzzled) ? 0 : tp[kMuzzleByte] ? tp[kMuzzleByte] : kWiz;
+        if (com == kComMove) {              // c:4736-4761
+            if (want_room) rm = target < 0 || best == kNoMatch ? -1 : best;
+            if (target < 0) outcome = kActMoveNobody;
+            else if (rm < 0) outcome = kActMoveNoRoom;
+            else if (target == slot) outcome = kActMoveSelf;
+            else if (tlevel >= level) outcome = kActMoveLevel;
+            else if (rm == old) outcome = kActMoveAlready;
+            else {                          // has_room_access(user, rm), c:2416-2419: the actor's level and invitation
+                const uint8_t access = e.rooms[(size_t)rm * kRoomRec + kRrAccess];
+                const int32_t invite = *reinterpret_cast<const int32_t*>(e.go + (size_t)slot * kGoRec + kGoInvite);
+                if ((access & kAccessPrivate) && level < e.gatecrash_level && invite != rm && !((access & kAccessFixed) && level >= kWiz))
+                    outcome = kActMovePrivate;
+                else if (old < 0 || old >= e.look_rooms) outcome = kActMoveAway;
+                else outcome = (tp[kNameLen + 1] & kVis) ? kActMoved : kActMovedUnseen;
+            }
+        } else if (com == kComWake) {       // c:6508-6521
+            outcome = target < 0 ? kActWakeNobody : target == slot ? kActWakeSelf : (tp[kNameLen + 1] & kAfk) ? kActWakeAfk : kActWoken;
+        } else if (com == kComMuzzle) {     // c:6579-6598
+            outcome = target < 0 ? kActMuzzleAbsent : target == slot ? kActMuzzleSelf : tlevel >= level ? kActMuzzleLevel
+                      : muzzle >= level ? kActMuzzleAlready : kActMuzzled;
+        } else {                            // c:6651-6669
+            outcome = target < 0 ? kActUnmuzzleAbsent : target == slot ? kActUnmuzzleSelf : muzzle == 0 ? kActUnmuzzleNot
+                      : muzzle > level ? kActUnmuzzleAbove : kActUnmuzzled;
+        }
+    }
+    const bool moved = outcome <= kActMovedUnseen;
+
+    // reset_access(old_room) after the move (c:2093-2096): who still stands in a room that is exactly PRIVATE
+    const bool counted = moved && e.rooms[(size_t)old * kRoomRec + kRrAccess] == kAccessPrivate;    // block-uniform
+    int stay = 0;
+    if (counted) {
+        for (int base = 0; base < e.capacity; base += kBlock) {
+            const int j = base + (int)threadIdx.x;
+            const bool in_room = j < e.capacity && j != target && e.room[j] == old && !(e.slotf[j] & kLogin) &&
+                                 e.speech[(size_t)j * kSpeechRec + kNameLen] != 0;
+            stay += __popcll(__ballot(in_room));
+        }
+        if (e.records) {                    // clones count (c:2095 walks the whole user list)
+            const size_t slice = ((size_t)e.clones * sizeof(int32_t) + 255) & ~(size_t)255;
+            const int32_t* owner = reinterpret_cast<const int32_t*>(e.records);
+            const int32_t* croom = reinterpret_cast<const int32_t*>(e.records + slice);
+            for (int base = 0; base < e.clones; base += kBlock) {
+                const int r = base + (int)threadIdx.x;
+                const bool in_room = r < e.clones && owner[r] >= 0 && croom[r] == old;
+                stay += __popcll(__ballot(in_room));
+            }
+        }
+    }
+    if (lane == 0) s_pop[wave] = stay;
+    __syncthreads();
+    if (wave != 0) return;
+    stay = 0;
+    for (int w = 0; w < kBlock / 64; w++) stay += s_pop[w];
+    const bool returns = counted && stay < e.min_private_users;
+
+    const int n = e.k;
+    const auto slot_of = [&](int kind) { return e.ctext + e.ctext_off[kind * n + k]; };   // at its use: few scalars stay live
+    const Piece none{nullptr, 0};
+    const Piece name{sp, sp[kNameLen] < kNameLen ? sp[kNameLen] : kNameLen};
+    const Piece shown = (sp[kNameLen + 1] & kVis) ? name : lit("A presence");
+    const Piece tname{tp, tp[kNameLen] < kNameLen ? tp[kNameLen] : kNameLen};
+    const uint8_t* rrec = e.rooms + (size_t)(rm < 0 ? here : rm) * kRoomRec;
+    const Piece rname{rrec, rrec[kRrNameLen] < kRoomNameLen ? rrec[kRrNameLen] : kRoomNameLen};
+    int here_len = -1, enter_len = -1, leave_len = -1, reset_len = -1, reply_len = 0, notice_len = -1;
+    const auto say = [&](int kind, int cap, int& at, Piece p0, Piece p1, Piece p2) {       // p0, and p1 + p2, each shorter than a wave
+        append3(slot_of(kind), cap, at, p0, p1, p2, lane, e.violations);
+    };
+    const auto reply = [&](Piece p0, Piece p1, Piece p2) { say(kActReply, kActReplyRow, reply_len, p0, p1, p2); };
+    switch (outcome) {
+    case kActMoved:
+    case kActMovedUnseen: reply(lit("~FT~OLYou chant an ancient spell...\n"), none, none); break;    // c:4762
+    case kActMuzzled:                       // c:6592
+        reply(lit("~FR~OL"), tname, lit(" now has a muzzle of level: ~RS~OL"));
+        reply(level_piece(level), lit(".\n"), none);
+        break;
+    case kActUnmuzzled: reply(lit("~FG~OLYou remove "), tname, lit("'s muzzle.\n")); break;
+    case kActWoken: reply(lit("Wake up call sent.\n"), none, none); break;
+    case kActMoveUsage: reply(lit("Usage: move <user> [<room>]\n"), none, none); break;
+    case kActMoveNobody:
+    case kActWakeNobody: reply(lit("There is no one of that name logged on.\n"), none, none); break;
+    case kActMoveNoRoom: reply(lit("There is no such room.\n"), none, none); break;
+    case kActMoveSelf: reply(lit("Trying to move yourself this way is the fourth sign of madness.\n"), none, none); break;
+    case kActMoveLevel: reply(lit("You cannot move a user of equal or higher "), lit("level than yourself.\n"), none); break;
+    case kActMoveAlready:
+        reply(tname, lit(" is already in the "), rname);
+        reply(lit(".\n"), none, none);
+        break;
+    case kActMovePrivate:
+        reply(lit("The "), rname, lit(" is currently private, "));
+        reply(tname, lit(" cannot be moved there.\n"), none);
+        break;
+    case kActWakeUsage: reply(lit("Usage: wake <user>\n"), none, none); break;
+    case kActWakeMuzzled: reply(lit("You are muzzled, you cannot wake anyone.\n"), none, none); break;
+    case kActWakeSelf: reply(lit("Trying to wake yourself up is the eighth sign of madness.\n"), none, none); break;
+    case kActWakeAfk: reply(lit("You cannot wake someone who is AFK.\n"), none, none); break;
+    case kActMuzzleUsage: reply(lit("Usage: muzzle <user>\n"), none, none); break;
+    case kActMuzzleSelf: reply(lit("Trying to muzzle yourself is the ninth sign of madness.\n"), none, none); break;
+    case kActMuzzleLevel: reply(lit("You cannot muzzle a user of equal or higher "), lit("level than yourself.\n"), none); break;
+    case kActMuzzleAlready: reply(tname, lit(" is already muzzled.\n"), none); break;
+    case kActUnmuzzleUsage: reply(lit("Usage: unmuzzle <user>\n"), none, none); break;
+    case kActUnmuzzleSelf: reply(lit("Trying to unmuzzle yourself is the tenth sign of madness.\n"), none, none); break;
+    case kActUnmuzzleAbove: {               // c:6660: level_name[u->muzzled]
+        const int muzzle = tp[kMuzzleByte] ? tp[kMuzzleByte] : kWiz;
+        reply(tname, lit("'s muzzle is set to level "), level_piece(muzzle));
+        reply(lit(", you do not have the power to remove it.\n"), none, none);
+        break;
+    }
+    default: reply_len = -1; break;         // kActMoveAway and the two absent branches are the caller's; kActUnmuzzleNot
+                                            // sprintf()s and writes nothing (c:6656-6658)
+    }
+    const bool silent = outcome == kActMoveAway || outcome == kActMuzzleAbsent || outcome == kActUnmuzzleAbsent || outcome == kActUnmuzzleNot;
+    bool whole = reply_len >= 0 || silent;
+    if (moved) {                            // c:4763-4765, then move_user(u, rm, 2), c:4423-4447
+        here_len = 0;
+        say(kActHere, kActHereRow, here_len, lit("~FT~OL"), shown, lit(" chants an ancient spell...\n"));
+        if (outcome == kActMovedUnseen) {
+            enter_len = leave_len = 0;
+            say(kActEnter, kActEnterRow, enter_len, lit("A presence enters the room...\n"), none, none);
+            say(kActLeave, kActLeaveRow, leave_len, lit("A presence leaves the room.\n"), none, none);
+        } else {
+            enter_len = leave_len = notice_len = 0;
+            say(kActNotice, kActNoticeRow, notice_len, lit("\n~FT~OLA giant hand grabs you and pulls you "), lit("into a magical blue vortex!\n"), none);
+            say(kActEnter, kActEnterRow, enter_len, lit("~FT~OL"), tname, lit(" falls out of a magical blue vortex!\n"));
+            say(kActLeave, kActLeaveRow, leave_len, lit("~FT~OLA giant hand grabs "), tname, none);
+            say(kActLeave, kActLeaveRow, leave_len, lit(" who is pulled into a magical blue vortex!\n"), none, none);
+            whole = whole && notice_len >= 0;
+        }
+        whole = whole && here_len >= 0 && enter_len >= 0 && leave_len >= 0;
+        if (returns) {                      // c:2097
+            reset_len = 0;
+            say(kActReset, kActResetRow, reset_len, lit("Room access returned to ~FGPUBLIC.\n"), none, none);
+            whole = whole && reset_len >= 0;
+        }
+    } else if (outcome == kActWoken) {      // c:6518-6520
+        notice_len = 0;
+        say(kActNotice, kActNoticeRow, notice_len, lit("\07\n~BR*** "), shown, lit(" says: ~OL~LIWAKE UP!!!~RS~BR ***\n\n"));
+        whole = whole && notice_len >= 0;
+    } else if (outcome == kActMuzzled || outcome == kActUnmuzzled) {   // c:6594, 6665
+        notice_len = 0;
+        say(kActNotice, kActNoticeRow, notice_len, outcome == kActMuzzled ? lit("~FR~OLYou have been muzzled!\n") : lit("~FG~OLYou have been unmuzzled!\n"),
+            none, none);
+        whole = whole && notice_len >= 0;
+    }
+    if (!whole) here_len = enter_len = leave_len = reset_len = reply_len = notice_len = -1;         // a violation: the call fails
+    if (lane == 0) {
+        e.clen[kActHere * n + k] = here_len;
+        e.clen[kActEnter * n + k] = enter_len;
+        e.clen[kActLeave * n + k] = leave_len;
+        e.clen[kActReset * n + k] = reset_len;
+        e.clen[kActReply * n + k] = reply_len;
+        e.clen[kActNotice * n + k] = notice_len;
+        e.outcome[k] = (int8_t)outcome;
+        e.found[k] = target;
+        e.found[n + k] = rm;
+        e.found[2 * n + k] = old;
+        e.returned[k] = returns && whole;
+        const int left = moved ? old : here;
+        int32_t* lrm = e.line + k;
+        int32_t* sender = lrm + kActLines * n;
+        int32_t* com_num = sender + kActLines * n;
+        lrm[kActHere * n] = here;           // write_room_except(user->room, text, user)
+        sender[kActHere * n] = slot;
+        lrm[kActEnter * n] = rm < 0 ? here : rm;               // write_room(rm, text): nobody is excepted
+        sender[kActEnter * n] = -1;
+        lrm[kActLeave * n] = lrm[kActReset * n] = left;        // the snapshot still has the target there
+        sender[kActLeave * n] = sender[kActReset * n] = moved ? target : -1;
+        for (int kind = 0; kind < kActLines; kind++) com_num[kind * n] = com;
+    }
+}
+
+static_assert(kActHereMax == 46 && kActEnterMax == 55 && kActLeaveMax == 80 && kActResetMax == 35 && kActReplyMax == 84 && kActNoticeMax == 72 &&
+              kActHereMax <= kActHereRow && kActEnterMax <= kActEnterRow && kActLeaveMax <= kActLeaveRow && kActResetMax <= kActResetRow &&
+              kActReplyMax <= kActReplyRow && kActNoticeMax <= kActNoticeRow, "roster_act: the longest texts fit their slots");
+static_assert(sizeof(" chants an ancient spell...\n") - 1 == 28 && sizeof(" falls out of a magical blue vortex!\n") - 1 == 37 &&
+              sizeof("~FT~OLA giant hand grabs ") - 1 == 25 && sizeof(" who is pulled into a magical blue vortex!\n") - 1 == 43 &&
+              sizeof("Room access returned to ~FGPUBLIC.\n") - 1 == kActResetMax && sizeof("'s muzzle is set to level ") - 1 == 26 &&
+              sizeof(", you do not have the power to remove it.\n") - 1 == 42 && sizeof("A presence enters the room...\n") - 1 <= kActEnterMax &&
+              sizeof("\n~FT~OLA giant hand grabs you and pulls you into a magical blue vortex!\n") - 1 == kActNoticeMax &&
+              sizeof("\07\n~BR***  says: ~OL~LIWAKE UP!!!~RS~BR ***\n\n") - 1 + kNameLen <= kActNoticeMax &&
+              sizeof("The  is currently private,  cannot be moved there.\n") - 1 + kRoomNameLen + kNameLen <= kActReplyMax &&
+              sizeof("~FR~OL now has a muzzle of level: ~RS~OL.\n") - 1 + kNameLen + 4 <= kActReplyMax &&
+              sizeof("You cannot muzzle a user of equal or higher level than yourself.\n") - 1 <= kActReplyMax &&
+              sizeof(" is already in the .\n") - 1 + kNameLen + kRoomNameLen <= kActReplyMax, "roster_act: the texts are as long as counted");
+static_assert(kActHereRow % 4 == 0 && kActEnterRow % 4 == 0 && kActLeaveRow % 4 == 0 && kActResetRow % 4 == 0 && kActReplyRow % 4 == 0 &&
+              kActNoticeRow % 4 == 0 && kActHereRow - kActHereMax < 4 && kActEnterRow - kActEnterMax < 4 && kActLeaveRow - kActLeaveMax < 4 &&
+              kActResetRow - kActResetMax < 4 && kActReplyRow - kActReplyMax < 4 && kActNoticeRow - kActNoticeMax < 4 && kActReplyRow < kTextSize,
+              "roster_act: a row is its longest text rounded up to a whole word, and a text fits speak_plan's LDS text");
+static_assert(sizeof("Trying to move yourself this way is the fourth sign of madness.\n") - 1 <= 64 &&
+              kNameLen + sizeof(" is already in the ") - 1 + kRoomNameLen <= 64 && 4 + kRoomNameLen + sizeof(" is currently private, ") - 1 <= 64 &&
+              6 + kNameLen + sizeof(" now has a muzzle of level: ~RS~OL") - 1 <= 64 && kNameLen + 26 + 4 <= 64 && kMuzzleByte < kSpeechRec &&
+              sizeof("\n~FT~OLA giant hand grabs you and pulls you ") - 1 <= 64 && 10 + sizeof(" says: ~OL~LIWAKE UP!!!~RS~BR ***\n\n") - 1 <= 64,
+              "roster_act: the pieces of a compose() fit a wave; the muzzle's byte");
+
+// nuts_roster_act_order's rule.  Keys: the actor's slot and room, the slot get_user found (-1: none), that slot's room, and
+// the room the event resolved to (-1: none).  A slot's room may be no look room: such a room has no bit and touches nothing.
+struct ActOrderArgs {
+    const int32_t* room;         // [capacity] the roster's table: the actors' rooms
+    const int32_t* slot;         // [k] the actors
+    const int32_t* found;        // [3k] what nuts_roster_act wrote: the slots found, the rooms resolved, the found slots' rooms
+    int k;
+    int8_t* outcome;             // [k] becomes kActDeferred for a deferred event
+    int32_t* clen;               // [6k] whose six texts become void
+    uint8_t* returned;           // [k] and whose room does not return
+
+    static constexpr int kKeys = 5, kTexts = kActTexts, kDeferred = kActDeferred, kMapWords = kOrderRoomWords + kOrderSlotWords;
+    __device__ void load(int b, bool live, int (&key)[kKeys]) const
+    {
+        key[0] = live ? slot[b] : 0, key[1] = live ? room[slot[b]] : -1, key[2] = live ? found[b] : -1;
+        key[3] = live ? found[2 * k + b] : -1, key[4] = live ? found[k + b] : -1;
+    }
+    static __device__ bool room_bit(const uint32_t* maps, int r) { return r >= 0 && r < kMaxLookRooms && bit_of(maps, r); }
+    static __device__ bool hit(const int (&key)[kKeys], const uint32_t* maps)
+    {
+        return bit_of(maps + kOrderRoomWords, key[0]) || room_bit(maps, key[1]) || (key[2] >= 0 && bit_of(maps + kOrderRoomWords, key[2])) ||
+               room_bit(maps, key[3]) || room_bit(maps, key[4]);
+    }
+    static __device__ void touch(const int (&key)[kKeys], int outcome, uint32_t* maps)
+    {
+        if (outcome > kActUnmuzzled) return;                    // a move or a muzzle touches the target's slot,
+        set_bit(maps + kOrderRoomWords, key[2]);
+        if (outcome > kActMovedUnseen) return;                  // a move the room left and the room entered: both look rooms
+        set_bit(maps, key[3]);
+        set_bit(maps, key[4]);
+    }
+    __device__ void also_void(int b) const { returned[b] = 0; }
+};
+
 // ------------------------------------------------------------------ a user's own settings, of a resident roster
 //
 // toggle_mode (nuts333.c:4009), toggle_ignall (4463), toggle_prompt (4481), set_desc (4494), set_iophrase (4515), set_topic
@@ -4134,6 +4519,8 @@ extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_access(AccessAr
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_access_order(AccessOrderArgs a) { order_events(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_clone(CloneArgs a) { roster_clone(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_clone_order(CloneOrderArgs a) { order_events(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_act(ActArgs a) { roster_act(a); }
+extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_act_order(ActOrderArgs a) { order_events(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_set(SetArgs a) { roster_set(a); }
 extern "C" __global__ void __launch_bounds__(kBlock) nuts_roster_set_order(SetOrderArgs a) { order_events(a); }
 
@@ -4858,6 +5245,33 @@ size_t layout_clone(uintptr_t base, size_t text_bytes, size_t clear_bytes, Clone
     return take.at;
 }
 
+// nd_roster_act's layout of a roster's allocation: layout_clone's without the said lines and the clears, with the slot found,
+// the room resolved and the room left in one array, and p planning 4k room lines and 2k single-recipient texts.  Of the
+// uploads the speaker table lies last, behind the go table and the room table: a muzzle set, the call's own aftermath, then
+// travels alone, and an upload runs from the first table given to the end of the inputs.
+size_t layout_act(uintptr_t base, size_t text_bytes, ActArgs& s, SpeakPlanArgs& p)
+{
+    Carver take{base};
+    const size_t k = (size_t)s.k, t = kActTexts * k;
+    take_table(take, s.capacity, s.room, s.slotf);
+    take_kept(take, s.kept[0], kKeptClones, s.capacity, s.look_rooms, s.clones);
+    take_kept(take, s.kept[1], kKeptRooms, s.capacity, s.look_rooms);
+    take_kept(take, s.kept[2], kKeptGo, s.capacity);
+    take_kept(take, s.kept[3], kKeptSpeech, s.capacity);                   // last: a muzzle alone uploads nothing else
+    take_events(take, s, text_bytes, &s.com);
+    take(s.ctext_off, t);
+    take(s.violations, 1);
+    take(s.outcome, k);
+    take(s.returned, k);
+    take(s.found, 3 * k);
+    take_event_texts(take, s, p, t, kActLines * k, (size_t)kActRow * k);
+    take(s.line, 3 * kActLines * k);
+    p.rm = s.line;
+    p.sender = s.line + kActLines * k;
+    p.com_num = s.line + 2 * kActLines * k;
+    return take.at;
+}
+
 // nd_roster_set's layout of a roster's allocation, after layout_access's: the table, the uploads of the five tables -- the
 // room table first, which only a .topic reads, then the slots' tables from the widest row to the narrowest, since an upload
 // runs from the first table given to the end of the inputs: a changed speaker table, 16 bytes a slot, travels alone --, the
@@ -5111,7 +5525,7 @@ int launch_record(Roster& r, int k, const uint8_t* text, const int32_t* text_off
     return 0;
 }
 
-// ---- the steps the four event calls share: nd_roster_go, nd_roster_access, nd_roster_clone and nd_roster_set.  Each takes
+// ---- the steps the five event calls share: nd_roster_go, nd_roster_access, nd_roster_clone, nd_roster_set and nd_roster_act.  Each takes
 // k events (slots, [coms,] inpstr, words), composes `texts` texts an event of which `lines` are room lines, defers in a
 // *_order kernel, plans with nuts_roster_speak_plan and downloads once.  What differs -- the settings, the kept tables and
 // their order, the results of its own -- stays in the call.
@@ -6856,6 +7270,81 @@ int nd_roster_clone(int handle, int k, const uint8_t* text, int64_t text_bytes, 
     memcpy(target_room, found, (size_t)k * sizeof(int32_t));
     memcpy(target_slot, found + k, (size_t)k * sizeof(int32_t));
     memcpy(rec, found + 2 * (size_t)k, (size_t)k * sizeof(int32_t));
+    return fill_timing(timing, t0, t1, h2d, z.res_bytes);
+}
+
+// K .move / .wake / .muzzle / .unmuzzle events of roster `handle`, decided and composed as move(), wake(), muzzle(), unmuzzle()
+// and move_user(u, rm, 2) do, against the tables as they are: nothing the roster keeps is changed, the caller moves the
+// targets and sets their muzzles.  Event b: the actor's slot slots[b], which stands in a look room, coms[b] (21, 58, 60 or
+// 61), inpstr and words[b] as nd_roster_go's.  gatecrash_level (0 .. 4) and min_private_users (>= 0) are the talker's.  The
+// five tables are nd_roster_go's, NULL when unchanged since this roster's last call that took them; byte 15 of a slot's
+// speaker state is its muzzle level.
+// Outputs (host, caller-allocated), with W = ceil(capacity / 64) and text t = kind * k + b for event b's here line (kind
+// 0), enter line, leave line, reset line, reply and notice (kind 5): outcome[k] (0 moved, 1 moved unseen, 2 muzzled, 3
+// unmuzzled, 4 woken, 5 .. 27 the refusals in the order of kActMoveUsage .. kActUnmuzzleAbove, 28 deferred); target_slot[k]
+// the slot get_user found, target_room[k] the room the event is about and old_room[k] the found slot's room, or -1;
+// returned[k] 1 where the room left returns to public; clen[6k], -1 where there is no text; ctext[376 k], the here lines at
+// 48 b, the enter lines at 48 k + 56 b, the leave lines at 104 k + 80 b, the reset lines at 184 k + 36 b, the replies at
+// 220 k + 84 b, the notices at 304 k + 72 b; bits[4k * W] the admit bitmaps of the four room lines; vn[12k], vw[12k],
+// vwsz[12k * 16] and var[12 * 376 k + 96 k] as nd_roster_speak's.
+// Per call, whatever k and the capacity: one upload, three kernels (nuts_roster_act, nuts_roster_act_order,
+// nuts_roster_speak_plan), one download at the bound size, one synchronise.  Returns 0, or -1 with nd_last_error() set.
+int nd_roster_act(int handle, int k, const uint8_t* text, int64_t text_bytes, const int32_t* text_off, const int32_t* text_len,
+                  const int32_t* slots, const uint8_t* coms, const uint8_t* words, int gatecrash_level, int min_private_users,
+                  const uint8_t* table, const uint8_t* speech, const uint8_t* clones, const uint8_t* rooms, const uint8_t* go,
+                  int8_t* outcome, int32_t* target_slot, int32_t* target_room, int32_t* old_room, uint8_t* returned, int32_t* clen,
+                  uint64_t* bits, int64_t* vn, int32_t* vw, int32_t* vwsz, uint8_t* ctext, uint8_t* var, nd_roster_timing* timing)
+{
+    Roster* r = roster_at(handle);
+    if (!r || ensure_ready()) return -1;
+    const int cap = r->capacity, nrooms = r->look_rooms;
+    if (!events_fit(k, cap, 1, kActRow, text_bytes, nrooms) || nrooms < 1 || cap > kGoMaxSlots || gatecrash_level < 0 ||
+        gatecrash_level > kGod || min_private_users < 0) {
+        snprintf(g_err, sizeof(g_err), "%d events to %d slots over %d look rooms: need 1 <= k * capacity < 2^31 - 1, a look room, a "
+                 "gatecrash level in 0 .. %d and a minimum of private users >= 0", k, cap, nrooms, kGod);
+        return -1;
+    }
+    if (check_events(k, cap, slots, text_off, text_len, text_bytes, coms,
+                     [](int c) { return c == kComMove || c == kComWake || c == kComMuzzle || c == kComUnmuzzle; }))
+        return -1;
+    ActArgs s{};
+    const Given given[] = {{kKeptClones, clones, &s.records}, {kKeptRooms, rooms, &s.rooms}, {kKeptGo, go, &s.go},
+                           {kKeptSpeech, speech, &s.speech}};
+    if (check_given(*r, given, "the roster's first act call must give the speaker table, the clone records, the room table and the go table"))
+        return -1;
+    const double t0 = now_ns();
+    SpeakPlanArgs p{};
+    size_events(s, p, k, kActLines, cap);
+    s.look_rooms = nrooms;
+    s.clones = r->clones;
+    s.gatecrash_level = gatecrash_level;
+    s.min_private_users = min_private_users;
+    ActArgs so = s;                     // offsets of every array in the roster's allocation
+    SpeakPlanArgs po = p;
+    const size_t need = layout_act(0, (size_t)text_bytes, so, po);
+    const EventSizes z = event_sizes(so, po, so.kept[0].fresh, kActTexts, (size_t)kActRow * k);
+    if (take_given_table(*r, so, z, table) || check_rooms_of(*r, so, slots, "actor") || grow_roster(*r, need)) return -1;
+    layout_act((uintptr_t)r->d, (size_t)text_bytes, s, p);
+    if (grow_host(&gm.res, &gm.cap_res, z.res_bytes, "pinned results")) return -1;
+
+    put_events(*r, so, z, text, text_bytes, text_off, text_len, slots, words, [k](int kind, int b) { return act_text_at(kind, b, k); });
+    Put{r->mirror}(so.com, coms, (size_t)k);
+    size_t h2d = 0;
+    unsigned copy_blocks = 0;
+    if (upload_events(*r, given, so.kept, s.kept, z, &h2d, &copy_blocks)) return -1;
+
+    const ActOrderArgs order{s.room, s.slot, s.found, k, s.outcome, s.clen, s.returned};
+    if (launch_events(nuts_roster_act, (unsigned)k + copy_blocks, s, nuts_roster_act_order, order, p, z)) return -1;
+    if (fetch_results(r->d, z.res_at, z.res_bytes)) return -1;
+    const double t1 = now_ns();
+
+    const Res res{gm.res, z.res_at};
+    if (copy_event_results(res, so, po, z, outcome, clen, bits, vn, vw, vwsz, ctext, var)) return -1;
+    memcpy(returned, res(so.returned), (size_t)k);
+    const int32_t* found = reinterpret_cast<const int32_t*>(res(so.found));
+    memcpy(target_slot, found, (size_t)k * sizeof(int32_t));
+    memcpy(target_room, found + k, (size_t)k * sizeof(int32_t));
+    memcpy(old_room, found + 2 * (size_t)k, (size_t)k * sizeof(int32_t));
     return fill_timing(timing, t0, t1, h2d, z.res_bytes);
 }
 

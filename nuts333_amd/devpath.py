@@ -4,7 +4,7 @@
                                   [--roster K[,K...]] [--plan K[,K...]] [--review Q[,Q...]] [--speak K[,K...]]
                                   [--input K[,K...]] [--tell K[,K...]] [--look K[,K...]] [--relay K[,K...]] [--go K[,K...]]
                                   [--who K[,K...]] [--rooms K[,K...]] [--access K[,K...]] [--clone K[,K...]]
-                                  [--set K[,K...]]                                                     -> one JSON line
+                                  [--set K[,K...]] [--act K[,K...]]                                    -> one JSON line
 
 For N in {10, 100, 1000} listeners, the two texts oracle/pathbench.c times (``say``; ``shout`` carrying ``~OL``/``~RS``)
 and colour all-off / all-on / half, one ``nuts333_amd.device.broadcast`` per repetition (listener 0 is the sender, the
@@ -129,6 +129,17 @@ that reads it: the ``.desc`` call uploads the descriptions its last call changed
 that lies behind them, 16, and in the ``.ignall`` rounds it is ``speak_many`` that uploads the table the ``.ignall`` call
 changed, 5 bytes a slot (``h2d_bytes`` shows both).
 Both calls are checked first against the reference's formats, the CPU's transducer and the rule of the call.
+
+``--act K[,K...]`` adds ``act``: a 1000-slot roster over the six default rooms whose first half are WIZes and whose second
+half are USERs, and per ``Roster.act_many`` call K ``.wake`` events by K actors, each of another user (``wake``), and K
+``.move <user> <room>`` events by K WIZ actors, each of another USER into the room behind its own (``move``), with the moves
+back in the next call (``back``), so that the state is periodic: the three times and the copy volume of each call -- of
+both device visits of a call that moves, added up --, each beside ``parts`` -- ``plan_many`` of the lines the call
+composes, composed beforehand, then, for the moves, ``look_many`` of the same users, in the same rounds -- and ``cpu_us``,
+the CPU modelling the call in Python and transducing the lines, and the looks, through ctypes.  A wake changes nothing, so
+every one is answered; a move touches a slot and two rooms, and its actor's room counts too, so six rooms take two moves
+a call: ``moved``, ``already`` and ``deferred`` say how many.  Every call is checked first against the model, the
+reference's formats and the CPU's transducer.
 """
 from __future__ import annotations
 
@@ -1049,6 +1060,155 @@ def access_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
             "access": cases}
 
 
+ACT_HALF = 500          # the roster of ``act_cases``: slots below are WIZes, the actors; slots from here on USERs, the targets
+
+
+def act_model(room_of: np.ndarray, events) -> list[tuple]:
+    """What act_many answers for ``.wake <user>`` and ``.move <user> <room>`` events at the roster ``act_cases`` builds, where
+    every user is visible, nobody is muzzled or AFK, every actor a WIZ and every target a USER named in full, and no room is
+    exactly PRIVATE: per event ``(outcome, target, room, texts)`` with the texts by kind.  The moves are applied to ``room_of``."""
+    names = ROOMS_LISTS["6"][0]
+    slots, rooms, out = set(), set(), []
+    for slot, com, inpstr, _wc in events:
+        words = inpstr.split()
+        who, here = int(words[0][4:]), int(room_of[slot])
+        old = int(room_of[who])
+        rm = names.index(words[1]) if com == device.COM_MOVE else here
+        if {slot, who} & slots or {here, old, rm} & rooms:
+            out.append((device.ACT_DEFERRED, who, rm, {}))
+        elif com == device.COM_WAKE:
+            out.append((device.ACT_WOKEN, who, rm, {"reply": b"Wake up call sent.\n",
+                                                    "notice": b"\07\n~BR*** User%d says: ~OL~LIWAKE UP!!!~RS~BR ***\n\n" % slot}))
+        elif rm == old:
+            out.append((device.ACT_MOVE_ALREADY, who, rm, {"reply": b"User%d is already in the %s.\n" % (who, names[rm])}))
+        else:
+            out.append((device.ACT_MOVED, who, rm, {
+                "reply": b"~FT~OLYou chant an ancient spell...\n", "here": b"~FT~OLUser%d chants an ancient spell...\n" % slot,
+                "notice": b"\n~FT~OLA giant hand grabs you and pulls you into a magical blue vortex!\n",
+                "enter": b"~FT~OLUser%d falls out of a magical blue vortex!\n" % who,
+                "leave": b"~FT~OLA giant hand grabs User%d who is pulled into a magical blue vortex!\n" % who}))
+            slots.add(who)
+            rooms |= {old, rm}
+            room_of[who] = rm
+    return out
+
+
+def act_lines(room_of: np.ndarray, events, want) -> list[tuple]:
+    """The lines of a call as plan_many takes them: the room lines to their rooms, the single-recipient ones to every room."""
+    lines = []
+    for (slot, com, _i, _w), (_o, who, rm, texts) in zip(events, want):
+        for kind, to, sender in (("here", int(room_of[slot]), slot), ("enter", rm, None), ("leave", int(room_of[who]), who),
+                                 ("reply", None, None), ("notice", None, None)):
+            if texts.get(kind):
+                lines.append((texts[kind], to, sender, 0, com))
+    return lines
+
+
+def act_cases(ks: list[int], reps: int, warmup: int, pb: dict) -> dict:
+    """The ``act`` section: act_many of K ``.wake`` events, and of K ``.move`` events there in one call and back in the next,
+    at a 1000-slot roster over the six default rooms; each beside the parts such a call is made of -- plan_many of the same
+    composed lines, then look_many of the moved users -- and the CPU modelling the call and transducing the strings."""
+    n = 1000
+    names, accesses = ROOMS_LISTS["6"]
+    nr = len(names)
+    texts_of = lambda a, i: {"here": a.here_text(i), "enter": a.enter_text(i), "leave": a.leave_text(i), "reply": a.reply_text(i),
+                             "notice": a.notice_text(i)}
+    cases = []
+    for colour in COLOURS:
+        with device.Roster(n, look_rooms=nr) as roster:
+            col = colours(n, colour)
+            home = np.arange(n) % nr
+            roster.update(range(n), room=home.tolist(), colour=col, name=[b"User%d" % j for j in range(n)],
+                          level=[2 if j < ACT_HALF else 1 for j in range(n)])
+            roster.set_rooms(list(range(nr)), name=names, access=accesses, links=[list(l) for l in GO_LINKS])
+            settings = {"gatecrash_level": 3, "min_private_users": 2}
+            for k in ks:
+                actors = [j % ACT_HALF for j in range(k)]
+                target = lambda j: ACT_HALF + j % ACT_HALF
+                wake = [(j, device.COM_WAKE, b"user%d" % target(j), 2) for j in actors]
+                there = [(j, device.COM_MOVE, b"user%d %s" % (target(j), names[(int(home[target(j)]) + 1) % nr]), 3) for j in actors]
+                back = [(j, device.COM_MOVE, b"user%d %s" % (target(j), names[int(home[target(j)])]), 3) for j in actors]
+                room_of = home.copy()
+                want_wake = act_model(room_of, wake)
+                wake_lines = act_lines(room_of, wake, want_wake)
+                there_lines = act_lines(room_of, there, act_model(home.copy(), there))
+                want_there = act_model(room_of, there)
+                moved = [w[1] for w in want_there if w[0] == device.ACT_MOVED]
+                looks = {j: go_look_strings(room_of, j) for j in moved}
+                got_wake, got_there = roster.act_many(wake, **settings), roster.act_many(there, **settings)
+                want_back = act_model(room_of, back)
+                got_back = roster.act_many(back, **settings)
+                for label, got, want in (("wake", got_wake, want_wake), ("move", got_there, want_there), ("back", got_back, want_back)):
+                    if got.outcome.tolist() != [w[0] for w in want] or any(
+                            (got.target_slot[i], got.target_room[i]) != w[1:3] for i, w in enumerate(want) if w[0] != device.ACT_DEFERRED):
+                        raise SystemExit(f"devpath: act {k}, {colour}: the device's outcomes of the {label} call differ from the model's")
+                    for i, w in enumerate(want):
+                        if texts_of(got, i) != {kind: w[3].get(kind, b"") for kind in ("here", "enter", "leave", "reply", "notice")}:
+                            raise SystemExit(f"devpath: act {k}, {colour}: event {i}'s texts of the {label} call differ from the reference's formats")
+                        c = int(col[w[1]])
+                        if w[3].get("notice") and got.notice.chunks(i, c) != nuts_path.chunks(w[3]["notice"], c):
+                            raise SystemExit(f"devpath: act {k}, {colour}: event {i}'s notice differs from the CPU's transducer")
+                for i, j in enumerate(moved):
+                    if got_there.look.chunks(i) != [ch for text in looks[j] for ch in nuts_path.chunks(text, int(col[j]))]:
+                        raise SystemExit(f"devpath: act {k}, {colour}: look {i} differs from the CPU's transducer over look()'s strings")
+                if not np.array_equal(room_of, home) or not np.array_equal(roster._room, home):
+                    raise SystemExit(f"devpath: act {k}, {colour}: the moves back do not end where the moves there began")
+
+                def cpu(events, looking):
+                    rooms = home.copy()
+                    for w in act_model(rooms, events):
+                        for text in w[3].values():
+                            nuts_path.chunks(text, 0)
+                            nuts_path.chunks(text, 1)
+                        if looking and w[0] == device.ACT_MOVED:
+                            c = int(col[w[1]])
+                            for text in go_look_strings(rooms, w[1]):
+                                nuts_path.chunks(text, c)
+
+                def act(events):
+                    a = roster.act_many(events, **settings)
+                    return _visits(a, a.look)
+
+                timed = _timed(f"act {k}, {colour}", {
+                    "wake": lambda: act(wake), "wake_parts": lambda: roster.plan_many(wake_lines), "wake_cpu": lambda: cpu(wake, False),
+                    "move": lambda: act(there), "back": lambda: act(back),
+                    "move_parts": lambda: _visits(roster.plan_many(there_lines), roster.look_many(moved) if moved else None),
+                    "move_cpu": lambda: cpu(there, True)}, reps, warmup)
+                count = lambda want, what: sum(w[0] == what for w in want)
+
+                def beside(name):
+                    dev, parts, cpu_us = timed[name], timed[name + "_parts"], timed[name + "_cpu"].host_us
+                    ratio = lambda f, a, b: round(dev.times[f][a] / parts.times[f][b], 2)
+                    return {**dev.fields, "parts": parts.fields, "cpu_us": cpu_us,
+                            "over_parts": {f: ratio(f, "median", "median") for f in FIELDS},
+                            "over_parts_p10_p90": {f: [ratio(f, "p10", "p90"), ratio(f, "p90", "p10")] for f in FIELDS},
+                            "end_to_end_over_cpu": float(f"{dev.times['end_to_end_us']['median'] / cpu_us['median']:.3g}")}
+
+                cases.append({"n": n, "k": k, "colour": colour, "rooms": nr, "woken": count(want_wake, device.ACT_WOKEN),
+                              "wake_lines": len(wake_lines), "moved": len(moved), "already": count(want_there, device.ACT_MOVE_ALREADY),
+                              "deferred": count(want_there, device.ACT_DEFERRED), "back_moved": count(want_back, device.ACT_MOVED),
+                              "back_already": count(want_back, device.ACT_MOVE_ALREADY), "back_deferred": count(want_back, device.ACT_DEFERRED),
+                              "move_lines": len(there_lines), "look_bytes_out": sum(len(got_there.look.output(i)) for i in range(len(moved))),
+                              "wake": beside("wake"), "move": beside("move"), "back": timed["back"].fields})
+    return {"act_kernels": list(device.ACT_KERNELS) + ["nuts_roster_speak_plan", "nuts_roster_look", "nuts_roster_speak_plan"],
+            "act_end_to_end_covers": "the device visits of an act_many call, added up.  The first: packing the K events into pinned "
+                                     "memory, one H2D (the events; after a call that moved, nothing else: its look left every "
+                                     "mirror clean), three kernels -- get_user, get_room, the decision chain and the six texts; "
+                                     "the deferral walk; both variants of every text and the room lines' admit bitmaps --, one D2H "
+                                     "at the bound size, one synchronise.  A call that moved somebody then applies the moves to the "
+                                     "host mirrors and visits again: look_many of the moved users, which uploads the table the moves "
+                                     "made stale, 5 bytes a slot (python_us adds checking the events, the copies out of pinned "
+                                     "memory, the applying and building the Act)",
+            "act_parts_covers": "plan_many of the lines the same call composes, composed beforehand -- the room lines to their "
+                                "rooms, the actors' and the targets' own lines as lines to every room --, then, for the moves, "
+                                "look_many of the same users, at a roster nobody moved in: neither uploads the table",
+            "act_cpu_us_covers": "the model of the call in Python -- the deferral rule and the reference's formats, interpreted, "
+                                 "with the names taken as given, no get_user and no get_room --, np_write_user_stream of the CPU "
+                                 "restatement (nuts_path, through ctypes) over both variants of every line, and for a move "
+                                 "look()'s strings composed in Python for every moved user and transduced for its colour",
+            "act": cases}
+
+
 def clone_csays(k: int, names) -> list[tuple]:
     """K ``.csay`` events by the owners 0 .. K - 1, each through its clone in room ``j % 6``, with the bodies of
     ``speak_events(k)``; and the lines they compose."""
@@ -1382,6 +1542,10 @@ SECTIONS = (
     ("set", "K[,K...]", "also time K .ignall events and K .desc events by K actors per Roster.set_many call at a 1000-slot roster "
                         "over the six default rooms, for each K, each beside speak_many of the same bodies and the CPU composing "
                         "and transducing the lines (the set section)", "set_cases"),
+    ("act", "K[,K...]", "also time K .wake events and K .move events by K actors per Roster.act_many call at a 1000-slot roster "
+                        "over the six default rooms, the moves there and back, for each K, each beside plan_many (and look_many) "
+                        "of the same lines and users and the CPU modelling the call and transducing the strings (the act section)",
+     "act_cases"),
 )
 
 
