@@ -3,17 +3,18 @@ that module shares with it: the state a sequence test owns, the fields every cal
 
 As tests/device_relay_child.py: the test module starts this script once, under ``timeout``, and asserts on the one JSON
 line it prints (``DEVICE_SEQUENCE {...}``).  Every other ``device_*_child.py`` fuzzes one call kind on a roster it has just
-built.  This one interleaves the fifteen device calls of a ``device.Roster`` with ``update``, ``set_rooms``, ``set_clones``,
+built.  This one interleaves the sixteen device calls of a ``device.Roster`` with ``update``, ``set_rooms``, ``set_clones``,
 ``clear_review`` and ``clear_revtell`` on rosters that live long, two of them at once, and compares every call in full
 with the models of those children, computed from a ``State`` kept here in plain Python and never from the roster's mirrors.
-Four calls change the roster themselves: ``go_many``, ``access_many``, ``clone_many`` and ``set_many``.  The model's
-``go_call``, ``access_call``, ``clone_call`` or ``set_call`` changes the State as the call's apply step changes the roster's
-mirrors -- the users' rooms and invitations, the rooms' access and topics, the clone records and where they lie, the flags
-and texts a user sets of itself -- and the next call of any kind meets what it left.  No call of the three breaks what the
-State promises every kind: none moves slot 0, takes its name or sets its login flag, and where a ``.destroy`` takes the
-last record the Runner makes record 0 anew with a ``set_clones`` of its own.  ``regrowth_part`` makes, for every ordered
-pair of the thirteen table-reading kinds, 156 of them, a small call of the one and then a large call of the other, so that
-the second finds a device allocation that was freed and made anew.
+Five calls change the roster themselves: ``go_many``, ``access_many``, ``clone_many``, ``set_many`` and ``act_many``.  The
+model's ``go_call``, ``access_call``, ``clone_call``, ``set_call`` or ``act_call`` changes the State as the call's apply step
+changes the roster's mirrors -- the users' rooms and invitations, the rooms' access and topics, the clone records and where
+they lie, the flags and texts a user sets of itself, the muzzle one user sets on another -- and the next call of any kind
+meets what it left.  No call of the four breaks what the State promises every kind: none moves slot 0 out of the ring
+rooms, takes its name or sets its login flag, and where a ``.destroy`` takes the last record the Runner makes record 0 anew
+with a ``set_clones`` of its own.  ``regrowth_part`` makes, for every ordered pair of the fourteen table-reading kinds, 182
+of them, a small call of the one and then a large call of the other, so that the second finds a device allocation that
+was freed and made anew.
 
     python tests/device_sequence_child.py [--seed S] [--seed2 T]
 """
@@ -35,11 +36,14 @@ sys.path.insert(0, str(REPO / "tests"))
 from device_access_child import EFFECTIVE as ACCESS_EFFECTIVE  # noqa: E402
 from device_access_child import access_call, access_differences, access_events  # noqa: E402
 from device_access_child import settings as access_settings  # noqa: E402
+from device_act_child import EFFECTIVE as ACT_EFFECTIVE  # noqa: E402
+from device_act_child import MOVED as ACT_MOVED  # noqa: E402
+from device_act_child import act, act_call, act_differences, act_events, muzzle_differences  # noqa: E402
 from device_clone_child import EFFECTIVE as CLONE_EFFECTIVE  # noqa: E402
 from device_clone_child import clone_call, clone_differences, clone_events, record_differences, trim  # noqa: E402
 from device_clone_child import settings as clone_settings  # noqa: E402
 from device_fanout_child import fuzz_items  # noqa: E402
-from device_go_child import MOVED, WORST_PHRASES, fuzz_events, go, go_call, go_differences, mirror_differences  # noqa: E402
+from device_go_child import MOVED, WIZ, WORST_PHRASES, fuzz_events, go, go_call, go_differences, mirror_differences  # noqa: E402
 from device_input_child import answer_of, fuzz_read, input_differences  # noqa: E402
 from device_input_child import new_counts as input_counts  # noqa: E402
 from device_look_child import WORST_DESCS, WORST_NAMES, fuzz_rooms, look_differences  # noqa: E402
@@ -65,11 +69,11 @@ from device_who_child import new_counts as who_counts  # noqa: E402
 from nuts333_amd import device, nuts_path  # noqa: E402
 
 KINDS = ("broadcast_many", "plan_many", "speak_many", "input_many", "tell_many", "look_many", "relay_many", "who_many",
-         "rooms_many", "go_many", "access_many", "clone_many", "set_many", "review_many", "revtell_many")
+         "rooms_many", "go_many", "access_many", "clone_many", "set_many", "act_many", "review_many", "revtell_many")
 #: the kinds whose kernels read the table (nd_roster_review and nd_roster_revtell neither read nor upload it)
-TABLE_KINDS = KINDS[:13]
-#: the three whose apply step changes the mirrors as go_many's does, compared and counted alike
-EVENT_KINDS = ("access_many", "clone_many", "set_many")
+TABLE_KINDS = KINDS[:14]
+#: the four whose apply step changes the mirrors as go_many's does, compared and counted alike
+EVENT_KINDS = ("access_many", "clone_many", "set_many", "act_many")
 #: the kinds that can record into the rooms' review rings, and the two that touch the slots' revtell rings; clone_many
 #: records only on a roster whose every look room has a ring (State.records_clones)
 RECORDING_KINDS = ("plan_many", "speak_many", "input_many", "relay_many")
@@ -78,7 +82,7 @@ REVIEW_ROOMS, LOOK_ROOMS = 3, 5
 CAPACITIES = (1, 64, 65, 257)
 #: the roster made in the closed one's place
 REPLACEMENT_CAPACITY = 130
-STEPS_PER_ROSTER = 320
+STEPS_PER_ROSTER = 400
 #: the seeds of the device run, and of the host tier's dry run of the same streams
 SEEDS = (20262, 20263)
 #: the rooms a roomless user may be away over: State keeps a netlink that is UP on both, whatever set_rooms draws
@@ -93,13 +97,15 @@ NOWHERE = b"zzq"
 
 # ------------------------------------------------------------------ the fields, and where each lives
 TABLE_FIELDS = ("room", "login", "ignall", "ignshout", "colour")
-SPEECH_FIELDS = ("name", "vis", "muzzled", "command_mode", "level", "afk", "igntell", "prompt", "charmode_echo")
+SPEECH_FIELDS = ("name", "vis", "muzzled", "muzzle_level", "command_mode", "level", "afk", "igntell", "prompt", "charmode_echo")
 WHO_FIELDS = ("last_login", "away")
 GO_FIELDS = ("in_phrase", "out_phrase", "invite_room")
 USER_FIELDS = TABLE_FIELDS + SPEECH_FIELDS + ("afk_mesg", "desc") + WHO_FIELDS + GO_FIELDS
 ROOM_FIELDS = ("name", "access", "desc", "links", "topic", "mesg_cnt", "netlink", "inlink")
-#: the key of a user's dict where it is not the field's name: go_user's
-KEY = {"invite_room": "invite"}
+#: the key of a user's dict where it is not the field's name: go_user's, and act_user's
+KEY = {"invite_room": "invite", "muzzle_level": "muzzle"}
+#: Roster.update refuses the two in one call: muzzle_level writes the muzzled bit too
+MUZZLE_FIELDS = ("muzzled", "muzzle_level")
 CLONE_FIELDS = ("owner", "room", "hear")
 #: the rooms' names as relay_many keeps them: no host mirror of the roster, an array it builds per call and compares
 RELAY_NAMES = "relay.names"
@@ -176,6 +182,16 @@ READS = {
     # .topic: rooms.topic is read by such a call alone (reads_of).  roster_speak_plan: listener_record
     "set_many": _TABLE | {"name", "vis", "command_mode", "igntell", "prompt", "charmode_echo", "afk_mesg", "desc", "in_phrase",
                           "out_phrase", "rooms.topic"},
+    # nd_roster_act -> roster_act: a.room[slot] and a.room[target]; wave_get_user over every slot's login flag and name;
+    # wave_get_room over every record's name; of the actor's 16 speaker bytes the name, vis, the level and muzzled (a muzzled
+    # waker); of the target's the name, vis, the level, afk (.wake), muzzled and byte 15, the muzzle's level; the actor's
+    # invite_room (has_room_access); the resolved room's access and name and the access of the room left; the head count of
+    # the room left over every slot's room, login flag and name length and the records' owner and room.
+    # order_events<ActOrderArgs>: a.room again.  roster_speak_plan: listener_record.  As the issue's table of this test
+    # expected, and of what it left open neither: the kernel reads no links -- the deferral over them is the binding's, from
+    # the host mirror -- and nothing of a netlink: ACT_MOVE_AWAY is decided by the target's room index
+    "act_many": _TABLE | {"name", "vis", "level", "muzzled", "muzzle_level", "afk", "invite_room", "clones.owner", "clones.room",
+                          "rooms.name", "rooms.access"},
     # review_call: its layout steps over the table (layout_review), the kernel reads the rings alone
     "review_many": frozenset(),
     "revtell_many": frozenset(),
@@ -192,7 +208,7 @@ def reads_of(kind: str, topic: bool = False) -> frozenset:
 #: a field each kind does not read, for the step "an update of only fields it does not read"
 UNREAD = {"broadcast_many": "desc", "plan_many": "name", "speak_many": "afk", "input_many": "igntell", "tell_many": "desc",
           "look_many": "muzzled", "relay_many": "level", "who_many": "rooms.access", "rooms_many": "afk", "go_many": "clones.hear",
-          "access_many": "rooms.netlink", "clone_many": "clones.hear", "set_many": "afk", "review_many": "room",
+          "access_many": "rooms.netlink", "clone_many": "clones.hear", "set_many": "afk", "act_many": "desc", "review_many": "room",
           "revtell_many": "colour"}
 
 ROOM_NAME_POOL = (b"d", b"N" * 20, b"hallway", b"~FRred/", b"wiz", b"R" * 20, b"alone", b"pair", b"e", b"/~", b"drive")
@@ -203,6 +219,17 @@ AFK_MESGS = (b"", b"", b"back in five", b"m" * 60, b"~FRred~RS \xe9")
 def slice_of(n: int) -> int:
     """An array's 256-byte aligned slice of an upload (Carver of fanout.hip)."""
     return -(-n // 256) * 256
+
+
+def apart(fields) -> tuple:
+    """``fields`` without the second of MUZZLE_FIELDS where it holds both."""
+    both = [f for f in fields if f in MUZZLE_FIELDS]
+    return tuple(f for f in fields if f not in both[1:])
+
+
+def written(fields) -> list:
+    """The fields an update of ``fields`` writes: a muzzle's level writes the muzzled bit as well."""
+    return list(fields) + ["muzzled"] * ("muzzle_level" in fields and "muzzled" not in fields)
 
 
 def op_for(field: str) -> tuple:
@@ -233,6 +260,8 @@ class State:
         for j, u in self.users.items():
             for f in USER_FIELDS:
                 u[KEY.get(f, f)] = self.value(rng, f, j)
+            if u["muzzle"]:
+                u["muzzled"] = 1                                         # a muzzle of a level is a muzzle: seat() can make it
             if j and rng.random() < 0.1:
                 u["name"] = None                                         # a slot that never got a name
         self.records = []
@@ -269,6 +298,8 @@ class State:
             return rng.choice(WORST_PHRASES + ((b"enters", b"strolls in") if f == "in_phrase" else (b"goes", b"wanders off")))
         if f == "invite_room":
             return rng.choice((None, None, 0, 1, 2, 3, 4))
+        if f == "muzzle_level":                                         # none most often; a GOD's, which a WIZ cannot remove
+            return rng.choice((0, 0, 0, 0, 0, 0, 1, 2, 3, device.MAX_LEVEL, device.MAX_LEVEL))
         chance = {"ignall": 0.2, "ignshout": 0.3, "colour": 0.5, "vis": 0.7, "muzzled": 0.1, "command_mode": 0.3, "afk": 0.15,
                   "igntell": 0.2, "prompt": 0.3, "charmode_echo": 0.3}[f]
         return int(rng.random() < chance)
@@ -296,11 +327,16 @@ class State:
         return rng.choice((None, (b"far", True, device.LINK_DOWN), (b"s" * 80, False, device.LINK_VERIFYING)) + up)
 
     def seat(self, roster: device.Roster) -> None:
-        """A roster that has just been made, in this state: the rooms first, update(away=) wants a room with a link."""
+        """A roster that has just been made, in this state: the rooms first, update(away=) wants a room with a link.  The
+        muzzles as seat_all of tests/device_act_child.py seats them: the level, which writes the bit too, then the bit alone
+        where the level left another -- a muzzle without a level, or a level whose bit an update of ``muzzled`` took."""
         ids = list(range(LOOK_ROOMS))
         roster.set_rooms(ids, **{f: [self.rooms[i][f] for i in ids] for f in ROOM_FIELDS})
         slots = list(range(self.cap))
-        roster.update(slots, **{f: [self.users[j][KEY.get(f, f)] for j in slots] for f in USER_FIELDS if f != "name"})
+        roster.update(slots, **{f: [self.users[j][KEY.get(f, f)] for j in slots] for f in USER_FIELDS if f not in ("name", "muzzled")})
+        bits = [j for j in slots if bool(self.users[j]["muzzled"]) != bool(self.users[j]["muzzle"])]
+        if bits:
+            roster.update(bits, muzzled=[self.users[j]["muzzled"] for j in bits])
         named = [j for j in slots if self.users[j]["name"]]
         roster.update(named, name=[self.users[j]["name"] for j in named])
         for c, (owner, room, hear) in enumerate(self.records):
@@ -362,12 +398,13 @@ class Coverage:
     """Which call kind ran directly after which update, and which was the first to touch the rings after a clear."""
 
     #: the calls whose apply step can return a ring room to public, and so leave a review clear pending
-    CLEAR_SOURCES = {"go_many": "go", "access_many": "access", "clone_many": "clone"}
+    CLEAR_SOURCES = {"go_many": "go", "access_many": "access", "clone_many": "clone", "act_many": "act"}
 
     def __init__(self):
         self.runs, self.after_read, self.after_unread = {}, {}, {}
         self.first_after_clear_review, self.first_after_clear_revtell = {}, {}
-        #: ... after a clear that a go_many, an access_many or a clone_many left; label -> the source of the pending one
+        #: ... after a clear that a go_many, an access_many, a clone_many or an act_many left; label -> the source of the
+        #: pending one
         self.first_after = {source: {} for source in self.CLEAR_SOURCES.values()}
         self.clear_from = {}
         self.last = {}                                                   # roster label -> fields of the step just before
@@ -390,8 +427,8 @@ class Coverage:
                change: dict | None = None, reads=None) -> None:
         """``review_rings`` / ``revtell_rings``: the call records into, or reads, those rings.  ``go``: what the model says a
         go_many changed -- ``moved``, ``invites_dropped``, and ``rings``, the ring rooms that went back to public; one of
-        those leaves a review clear pending, as clear_review does.  ``change``: the same of an access_many, a clone_many or a
-        set_many -- ``stale``, the fields the model's call changed, and ``rings``.  ``reads``: what this call reads, where
+        those leaves a review clear pending, as clear_review does.  ``change``: the same of an access_many, a clone_many, a
+        set_many or an act_many -- ``stale``, the fields the model's call changed, and ``rings``; of an act_many ``moved`` too.  ``reads``: what this call reads, where
         that is not READS of its kind (reads_of)."""
         reads = READS[kind] if reads is None else reads
         per = self.runs.setdefault(label, {k: 0 for k in KINDS})
@@ -424,13 +461,17 @@ class Coverage:
                 "go_subsets": self.subsets["go_many"], **{f"{kind[:-5]}_subsets": self.subsets[kind] for kind in EVENT_KINDS}}
 
 
-#: what a run counts of access_many, clone_many and set_many, from the model's calls alone: per kind the effective and the
-#: deferred events; the rooms an access call set private or returned to public, and those a destroy returned; the records
-#: created and destroyed, the calls after which records moved down, the said lines a recording call stored; the set calls
-#: that held a .topic, and those that held none while the roster's room table was dirty
+#: what a run counts of access_many, clone_many, set_many and act_many, from the model's calls alone: per kind the effective
+#: and the deferred events; the rooms an access call set private or returned to public, and those a destroy returned; the
+#: records created and destroyed, the calls after which records moved down, the said lines a recording call stored; the set
+#: calls that held a .topic, and those that held none while the roster's room table was dirty; the targets an act call
+#: moved, the rooms it returned to public, the invitations its moves and returns cleared, the muzzles set and removed, the
+#: wake-up calls sent and those refused for an AFK target, the muzzles that were above their remover -- and, from the
+#: roster's flags before the call, the act calls that passed the speaker state on _private_dirty alone
 EVENT_COUNTS = tuple(f"{kind[:-5]}_{what}" for what in ("effective", "deferred") for kind in EVENT_KINDS) + (
     "set_private", "access_returned", "destroy_returned", "created", "destroyed", "compacted", "said_recorded", "topic_calls",
-    "topicless_dirty")
+    "topicless_dirty", "act_moved", "act_returned", "act_invites_cleared", "act_muzzled", "act_unmuzzled", "act_woken",
+    "act_wake_afk", "act_unmuzzle_above", "act_private_alone")
 #: set_many's kept tables in layout order; the room table is passed only by a call that holds a .topic, else kept back
 SET_TABLES = ("speech", "afk", "udesc", "go", "rooms")
 KEPT_BACK = "rooms-kept-back"
@@ -448,7 +489,7 @@ def text_of(rng: random.Random, lo: int, hi: int) -> bytes:
 class Runner:
     """Makes steps on ``roster`` and on ``state`` alike.  With ``check`` every call's result is compared with the models
     (``bad`` collects what differs); without, only the calls are made, for a library that computes nothing -- and after an
-    access_many, a clone_many or a set_many, whose apply step is the binding's own, the roster's mirrors are still compared
+    access_many, a clone_many, a set_many or an act_many, whose apply step is the binding's own, the roster's mirrors are still compared
     with the State.  ``seen`` is told of every step: ``updated(label, fields)``, ``cleared(label, tell)``, ``called(label,
     kind, review, revtell)`` with what the model says a call changed."""
 
@@ -488,14 +529,24 @@ class Runner:
             self.bad.append({"step": self.steps, "what": "roster.table() is not the state's table"})
 
     def _update(self, fields) -> None:
+        """``muzzled`` and ``muzzle_level`` never in one update, which the roster refuses: the second of them is dropped."""
         rng, st = self.rng, self.state
+        fields = apart(fields)
         slots = [rng.randrange(st.cap) for _ in range(rng.randint(1, 4))]
         values = {f: [st.value(rng, f, j) for j in slots] for f in fields}
         self.roster.update(slots, **values)
         for i, j in enumerate(slots):                                   # in order: the last value wins
             for f in fields:
-                st.users[j][KEY.get(f, f)] = values[f][i]
-        self.seen.updated(self.label, fields)
+                self._took(j, f, values[f][i])
+        self.seen.updated(self.label, written(fields))
+
+    def _took(self, slot: int, f: str, value) -> None:
+        """The State after an update of one field of one slot: a muzzle's level writes the muzzled bit too, the bit alone
+        leaves the level as it was."""
+        u = self.state.users[slot]
+        u[KEY.get(f, f)] = value
+        if f == "muzzle_level":
+            u["muzzled"] = int(value != 0)
 
     def _set_rooms(self, fields) -> None:
         rng, st = self.rng, self.state
@@ -823,8 +874,8 @@ class Runner:
         self.roster.update(slots, **values)
         for i, j in enumerate(slots):
             for f in values:
-                self.state.users[j][KEY.get(f, f)] = values[f][i]
-        self.seen.updated(self.label, list(values))
+                self._took(j, f, values[f][i])
+        self.seen.updated(self.label, written(values))
 
     def _go_many(self, opts) -> None:
         st = self.state
@@ -850,7 +901,7 @@ class Runner:
         if not self.check or not bad:
             self.seen.passed("go_many", flags)
 
-    # -------------------------------------------------------------- the three calls that change the roster as go_many does
+    # -------------------------------------------------------------- the four calls that change the roster as go_many does
     def _rings_cleared(self, rooms) -> list:
         """The ring rooms among those a model's call returned to public: reset_access empties their rings."""
         rings = [rm for rm in rooms if rm < self.state.review_rooms]
@@ -859,7 +910,7 @@ class Runner:
         return rings
 
     def mirrors_differences(self) -> list:
-        """The roster's mirrors against the State, after the apply step of any of the three: the rooms, the invitations and
+        """The roster's mirrors against the State, after the apply step of any of the four: the rooms, the invitations and
         the rooms' access (go's comparison), the flags, descriptions, AFK messages, phrases and topics (set's), and the
         clone records where they lie (clone's)."""
         st = self.state
@@ -868,8 +919,10 @@ class Runner:
 
     def event_flags(self, kind: str, topic: bool = False) -> tuple:
         """The kept tables that the roster's flags say its next call of ``kind`` passes: go_many's four for access_many and
-        clone_many; for set_many its own, the speaker state on any of its three flags, and the room table only with a
-        ``.topic`` in the call -- without one a dirty room table is kept back."""
+        clone_many; act_many's (act_flags); for set_many its own, the speaker state on any of its three flags, and the room
+        table only with a ``.topic`` in the call -- without one a dirty room table is kept back."""
+        if kind == "act_many":
+            return self.act_flags()
         if kind != "set_many":
             return self.go_flags()
         r = self.roster
@@ -1059,6 +1112,97 @@ class Runner:
         if not bad:
             self.seen.passed("set_many", flags)
 
+    def act_flags(self) -> tuple:
+        """act_many's kept tables: go_many's four, but the speaker state travels after an update of ``afk`` or ``igntell``
+        alone as well, since a ``.wake`` reads the target's ``afk`` bit."""
+        r = self.roster
+        flag = {"speech": r._speech_dirty or r._private_dirty, "clones": r._clones_dirty and r.clones > 0, "rooms": r._rooms_dirty,
+                "go": r._go_dirty}
+        return tuple(t for t in GO_TABLES if flag[t])
+
+    def _act_events(self, opts) -> tuple:
+        """The events of an act_many and the talker's two settings.  ``quiet``: nothing can change -- a word count of 1, or
+        NOWHERE for the user, a word that no name the State draws contains, so that get_user's substring pass finds nobody.
+        ``sized``: that word with a long rest.  ``returns``, on a roster of two slots or more: slot 0 is made a GOD; slot 1
+        gets a name of its own, a lower level, no login flag and a ring room that is not slot 0's, made exactly PRIVATE with
+        some slot invited into it, and is itself invited into slot 0's room; slot 0 moves it there with more users asked
+        for than the roster holds: the call moves a user, clears both invitations, returns a ring room to public and leaves
+        its review clear pending.  A roster of one slot has nobody to move, and makes an ordinary call.  ``muzzles``, for the
+        host tier's one-by-one cases on a roster of two slots or more: slot 0, a GOD, muzzles slot 1, which has none.
+        ``above``, likewise: slot 1 gets a GOD's muzzle through ``muzzle_level``, loses the bit and gets it back through
+        ``muzzled``, which leaves the level where it was, and slot 0, a WIZ, may not remove it: ACT_UNMUZZLE_ABOVE."""
+        rng, st, G = self.rng, self.state, device
+        gatecrash, min_private = rng.randrange(G.MAX_LEVEL + 1), rng.randrange(4)
+        coms = (G.COM_MOVE, G.COM_WAKE, G.COM_MUZZLE, G.COM_UNMUZZLE)
+        if "sized" in opts:
+            lo, hi = opts["sized"]
+            return ([(j, rng.choice(coms), (NOWHERE + b" " + text_of(rng, lo, hi))[:hi], 3) for j in self._speakers(opts, False)],
+                    gatecrash, min_private)
+        if opts.get("quiet"):
+            picked = [(j, rng.choice(coms)) for j in self._speakers(opts, False)]
+            return ([(j, com, b"", 1) if rng.random() < 0.5 else (j, com, NOWHERE + rng.choice((b"", b" now")), 2) for j, com in picked],
+                    gatecrash, min_private)
+        if (opts.get("returns") or opts.get("muzzles") or opts.get("above")) and st.cap > 1:
+            self.renamed += 1
+            name = b"Mover%04d" % self.renamed                          # no other name contains it, and slot 0's is another
+            below = rng.randrange(G.MAX_LEVEL)
+            if opts.get("above"):
+                self._put_users([0], {"level": [WIZ]})
+                self._put_users([1], {"name": [name], "login": [0], "muzzle_level": [G.MAX_LEVEL]})
+                self._put_users([1], {"muzzled": [0]})
+                self._put_users([1], {"muzzled": [1]})
+                return [(0, G.COM_UNMUZZLE, name.lower(), 2)], gatecrash, min_private
+            self._put_users([0], {"level": [G.MAX_LEVEL]})
+            if opts.get("muzzles"):
+                self._put_users([1], {"name": [name], "level": [below], "login": [0], "muzzle_level": [0]})
+                return [(0, G.COM_MUZZLE, name.lower(), 2)], gatecrash, min_private
+            here = st.users[0]["room"]
+            there = rng.choice([r for r in range(st.review_rooms) if r != here])
+            self._put_rooms([there], {"access": [G.PRIVATE]})
+            self._put_users([rng.choice([j for j in range(st.cap) if j != 1])], {"invite_room": [there]})
+            self._put_users([1], {"name": [name], "level": [below], "login": [0], "room": [there], "invite_room": [here]})
+            return [(0, G.COM_MOVE, name.lower(), 2)], gatecrash, st.cap + st.nclones + 1
+        events = act_events(rng, st.users, st.rooms, self._k(opts))     # its movers_of is State.speakers()
+        # slot 0 stays in a ring room: a move of it out of them becomes a usage line.  The snapshot decides as the call
+        # does, because an event that an earlier one of the call could change is deferred
+        for i, (slot, com, inpstr, wc) in enumerate(events):
+            res = act(st.users, st.rooms, st.go_clones(), slot, com, inpstr, wc, gatecrash, min_private)
+            if res["outcome"] in ACT_MOVED and res["target_slot"] == 0 and res["target_room"] >= st.review_rooms:
+                events[i] = (slot, com, inpstr, 1)
+        return events, gatecrash, min_private
+
+    def _act_many(self, opts) -> None:
+        st, c, G = self.state, self.counts, device
+        events, gatecrash, min_private = self._act_events(opts)
+        flags = self.act_flags()                                        # before the call, as go_many's
+        private_alone = bool(self.roster._private_dirty and not self.roster._speech_dirty)
+        before = st.snapshot()
+        call = act_call(st.users, st.rooms, st.go_clones(), events, gatecrash, min_private)     # the State changes
+        if self.script is not None:
+            self.script.append([(e["outcome"], e["target_slot"], e["target_room"], e["old"], int(e["returned"])) for e in call["events"]])
+        got = self.roster.act_many(events, gatecrash_level=gatecrash, min_private_users=min_private)
+        self.seen.called(self.label, "act_many", False, False,
+                         change={"stale": st.changed_since(before), "rings": self._rings_cleared(call["cleared"]),
+                                 "moved": bool(call["movers"])})
+        outcomes = [e["outcome"] for e in call["events"]]
+        c["act_effective"] += sum(o in ACT_EFFECTIVE for o in outcomes)
+        c["act_deferred"] += outcomes.count(G.ACT_DEFERRED)
+        c["act_moved"] += len(call["movers"])
+        c["act_returned"] += len(call["cleared"])
+        c["act_invites_cleared"] += sum(1 for was, u in zip(before["invite_room"], st.users.values()) if u["invite"] != was)
+        for name, outcome in (("act_muzzled", G.ACT_MUZZLED), ("act_unmuzzled", G.ACT_UNMUZZLED), ("act_woken", G.ACT_WOKEN),
+                              ("act_wake_afk", G.ACT_WAKE_AFK), ("act_unmuzzle_above", G.ACT_UNMUZZLE_ABOVE)):
+            c[name] += outcomes.count(outcome)
+        c["act_private_alone"] += private_alone
+        # the mirrors are the binding's own work: compared over a library that computes nothing too
+        bad = ((act_differences(got, call, st.users) if self.check else []) + self.mirrors_differences()
+               + muzzle_differences(self.roster, st.users))
+        if st.users[0]["room"] is None or st.users[0]["room"] >= st.review_rooms:
+            bad.append({"what": "the Runner let slot 0 be moved out of the ring rooms", "room": st.users[0]["room"]})
+        self._note("act_many", got.timing, bad)
+        if not bad:
+            self.seen.passed("act_many", flags)
+
     def _review_many(self, opts) -> None:
         rooms = [self.rng.randrange(self.state.review_rooms) for _ in range(self.rng.randint(1, 4))]
         rv = self.roster.review_many(rooms)
@@ -1088,6 +1232,8 @@ GO_TABLES = ("speech", "clones", "rooms", "go")
 #: charmode_echo _set_dirty, on either of which set_many alone uploads the speaker state
 SUBSET_FIELDS = {"speech": ("name", "vis", "level"), "clones": ("clones.owner", "clones.room", "clones.hear"),
                  "rooms": ("rooms.access", "rooms.links", "rooms.name", "rooms.netlink"), "go": GO_FIELDS}
+#: act_many's speaker fields: afk and igntell raise _private_dirty alone, on which act_many uploads the speaker state too
+ACT_SUBSET_FIELDS = {**SUBSET_FIELDS, "speech": ("name", "vis", "level", "muzzled", "muzzle_level", "afk", "igntell")}
 SET_SUBSET_FIELDS = {"speech": ("name", "afk", "prompt", "vis", "igntell", "charmode_echo", "command_mode"), "afk": ("afk_mesg",),
                      "udesc": ("desc",), "go": GO_FIELDS}
 
@@ -1095,13 +1241,17 @@ SET_SUBSET_FIELDS = {"speech": ("name", "afk", "prompt", "vis", "igntell", "char
 def subset_blocks() -> list:
     """[a call that changes nothing and leaves its kept tables clean, an update of one field of each table of the subset,
     a call]: for go_many, access_many and clone_many every subset of their four tables is the one passed, the fields taking
-    turns.  For set_many every subset of its first four, three times: with the room table clean, with it dirty and a
-    ``.topic`` in the call, which passes it, and with it dirty and no ``.topic``, which keeps it back."""
+    turns.  For act_many the same sixteen, the speaker state over its own fields: of the eight subsets that hold it, the
+    one with the room table is reached by ``afk`` alone and the one with the room table and the go table by ``igntell``
+    alone, both on ``_private_dirty``, and the one with the clone records and the go table by ``muzzle_level`` alone.  For
+    set_many every subset of its first four, three times: with the room table clean, with it dirty and a ``.topic`` in the
+    call, which passes it, and with it dirty and no ``.topic``, which keeps it back."""
     blocks = []
-    for kind in ("go_many", "access_many", "clone_many"):
+    for kind in ("go_many", "access_many", "clone_many", "act_many"):
+        fields = ACT_SUBSET_FIELDS if kind == "act_many" else SUBSET_FIELDS
         for i in range(16):
             subset = [t for b, t in enumerate(GO_TABLES) if i >> b & 1]
-            blocks.append([(kind, {"quiet": True})] + [op_for(SUBSET_FIELDS[t][i % len(SUBSET_FIELDS[t])]) for t in subset] + [(kind, {})])
+            blocks.append([(kind, {"quiet": True})] + [op_for(fields[t][i % len(fields[t])]) for t in subset] + [(kind, {})])
     for i in range(16):
         subset = [t for b, t in enumerate(SET_TABLES[:4]) if i >> b & 1]
         dirty = [op_for(SET_SUBSET_FIELDS[t][i % len(SET_SUBSET_FIELDS[t])]) for t in subset]
@@ -1113,9 +1263,10 @@ def subset_blocks() -> list:
 
 def clear_blocks() -> list:
     """[a clear, the first call to touch those rings after it]; the clear is clear_review's, clear_revtell's, or what a
-    go_many, an access_many or a clone_many leaves that returns a ring room to public.  clone_many is among the first only
-    on a roster where it may record; on the others it passes the clear by."""
-    sources = [("clear_review",)] + [(kind, {"returns": True}) for kind in ("go_many", "access_many", "clone_many")]
+    go_many, an access_many, a clone_many or an act_many leaves that returns a ring room to public.  clone_many is among the
+    first only on a roster where it may record; on the others it passes the clear by.  An act_many returns no room on a
+    roster of one slot, which has nobody to move: there its block is two ordinary calls."""
+    sources = [("clear_review",)] + [(kind, {"returns": True}) for kind in Coverage.CLEAR_SOURCES]
     firsts = [(kind, {"record": True}) for kind in RECORDING_KINDS + ("clone_many",)] + [("review_many", {})]
     return ([[source, first] for source in sources for first in firsts]
             + [[("clear_revtell",), ("tell_many", {"record": True})], [("clear_revtell",), ("revtell_many", {})]])
@@ -1124,7 +1275,7 @@ def clear_blocks() -> list:
 def random_op(rng: random.Random) -> tuple:
     x = rng.random()
     if x < 0.30:
-        return ("update", tuple(rng.sample(USER_FIELDS, rng.choice((1, 1, 2, 3, 5)))))
+        return ("update", apart(rng.sample(USER_FIELDS, rng.choice((1, 1, 2, 3, 5)))))
     if x < 0.37:
         return ("set_rooms", tuple(rng.sample(ROOM_FIELDS, rng.choice((1, 2, len(ROOM_FIELDS))))))
     if x < 0.44:
@@ -1137,9 +1288,11 @@ def random_op(rng: random.Random) -> tuple:
 
 
 def roster_steps(rng: random.Random, blocks: list, steps: int, each: int = 8) -> list:
-    """A roster's steps: the blocks dealt to it, every clear block, ``each`` calls of every kind, and random steps up to
-    ``steps``; the blocks stay whole, their order is shuffled."""
-    blocks = [list(b) for b in blocks] + clear_blocks() + [[(kind, {})] for kind in KINDS for _ in range(each)]
+    """A roster's steps: the blocks dealt to it, every clear block, an ``.unmuzzle`` of a muzzle whose bit was taken and
+    put back (``above``), ``each`` calls of every kind, and random steps up to ``steps``; the blocks stay whole, their order
+    is shuffled."""
+    blocks = ([list(b) for b in blocks] + clear_blocks() + [[("act_many", {"above": True})]]
+              + [[(kind, {})] for kind in KINDS for _ in range(each)])
     while sum(map(len, blocks)) < steps:
         blocks.append([random_op(rng)])
     rng.shuffle(blocks)
@@ -1220,11 +1373,12 @@ def sequence_part(seed: int, cov: Coverage, check: bool = True, script: list | N
 
 
 def regrowth_part(seed: int) -> dict:
-    """Every ordered pair (A, B) of the thirteen table-reading kinds on a fresh 65-slot roster whose every mirror has been
+    """Every ordered pair (A, B) of the fourteen table-reading kinds on a fresh 65-slot roster whose every mirror has been
     uploaded: a tiny A, then a big B, twice.  The first B finds the allocation made anew and uploads the table from the
     pinned mirror, though the roster passes none; its repeat does not.  A big B is 16 long texts; of go_many 16 long lines
-    that move nobody, or its repeat would be another call and find the table dirty; of access_many, clone_many and set_many
-    for the same reason 16 long lines that change nothing (a word that names no room, a description too long); of who_many
+    that move nobody, or its repeat would be another call and find the table dirty; of access_many, clone_many, set_many
+    and act_many for the same reason 16 long lines that change nothing (a word that names no room or no user, a description
+    too long); of who_many
     and rooms_many, which take
     no text, many lookers.  A pair that does not regrow doubles K."""
     rng = random.Random(seed)
